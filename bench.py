@@ -2,7 +2,7 @@
 """
 bench.py - throughput of the MTM hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR]
 
 N > 1 runs either way: launched by ``torch.distributed.run --nproc-per-node N`` (WORLD_SIZE set) it is one process per
 GPU with an RCCL all-gather of the hit records; started plainly (``python bench.py --gpus N``) it is ONE process
@@ -58,6 +58,7 @@ I8_MFMA_RANDOM_OPERANDS_TOPS = 3960.0
 I8_OPS_PER_CLK = 1024 * 2048   # whole chip, per shader cycle
 PREWARM_SECONDS = float(os.environ.get("BENCH_PREWARM_S", "0.6"))   # untimed load before the W warm-up calls (clock ramp)
 CONFIGS = ("north_star", "cfg2", "cfg3", "cfg4", "cfg5")
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: at most this much in all
 
 
 def parse():
@@ -75,7 +76,12 @@ def parse():
     ap.add_argument("--skip-extras", action="store_true",
                     help="only the timed calls (profiling runs): no resident / fresh-template / map-mode / stream side measurements")
     ap.add_argument("--cpu-sample-templates", type=int, default=0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the hit list of the last timed call as DIR/<name>.npy (dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def build_workload(name, n_gpus):
@@ -248,6 +254,27 @@ def cpu_baseline(img, units, method, thr, n_sample):
             "sample": "%d of %d templates on the full %dx%d image, %s, %d worker threads of %d host cores, %.2f s"
                       % (n_sample, len(units), img.shape[1], img.shape[0], what, used, cores, dt),
             "seconds": round(dt, 3)}
+
+
+def dump_outputs(out_dir, hits, units, limit_bytes=DUMP_LIMIT_BYTES):
+    """What the timed call returned, as arrays a later build's dump can be compared with element by element, in the order
+    MTM.matchTemplates returned the hits: hits_label_index (position of the hit's label among the workload's distinct
+    labels in list order), hits_box_xywh (x, y, width, height) and hits_score.  Above `limit_bytes` in all, the same
+    seeded sample of rows (in their order) is written from every array.  Returns {name: rows written}."""
+    index = {}
+    for u in units:
+        index.setdefault(u[0], len(index))
+    arrays = {"hits_label_index": np.array([index[h[0]] for h in hits], dtype=np.float64),
+              "hits_box_xywh": np.array([h[1] for h in hits], dtype=np.float64).reshape(len(hits), 4),
+              "hits_score": np.array([h[2] for h in hits], dtype=np.float32)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit_bytes:
+        keep = np.sort(np.random.default_rng(0).choice(len(hits), len(hits) * limit_bytes // total, replace=False))
+        arrays = {name: a[keep] for name, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: len(a) for name, a in arrays.items()}
 
 
 def resolve_group_exchange(group, requested):
@@ -491,6 +518,8 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hits, units)
 
     px = img.shape[0] * img.shape[1]
     rate = lambda ms: round(px * len(units) / ms / 1e3, 1)        # noqa: E731  ms per call -> Mpx-corr/s

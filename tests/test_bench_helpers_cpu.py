@@ -4,6 +4,7 @@ import os
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
@@ -120,3 +121,34 @@ def test_exchange_flag_and_fallback(monkeypatch):
     assert bench.resolve_group_exchange(g, "host")[:2] == ("host", 0) and g.inits == 0
     kind, ranks, note = bench.resolve_group_exchange(FakeGroup(False), None)
     assert kind == "host" and ranks == 0 and "listed twice" in note
+
+
+def test_dump_outputs_arrays_and_limit(tmp_path, monkeypatch):
+    """--dump-outputs: the hit list as float arrays in the order it was returned, labels as their position among the
+    workload's distinct labels; above the size limit the same seeded rows of every array, in order, and the same rows
+    from run to run.  --steps below 1 is refused (ms_per_step divides by it)."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--dump-outputs", str(tmp_path)])
+    a = bench.parse()
+    assert a.steps == 7 and a.dump_outputs == str(tmp_path)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    units = [("b", None), ("a", None), ("b", None), ("c", None)]
+    hits = [("c", (5, 6, 64, 64), np.float32(0.75)), ("b", (1, 2, 3, 4), np.float32(0.5)),
+            ("a", (7, 8, 9, 10), np.float32(0.625))]
+    assert bench.dump_outputs(str(tmp_path / "all"), hits, units) == {"hits_label_index": 3, "hits_box_xywh": 3, "hits_score": 3}
+    lab, box, score = (np.load(str(tmp_path / "all" / (n + ".npy"))) for n in ("hits_label_index", "hits_box_xywh", "hits_score"))
+    assert lab.dtype == np.float64 and box.dtype == np.float64 and score.dtype == np.float32
+    assert lab.tolist() == [2.0, 0.0, 1.0] and box.tolist() == [[5, 6, 64, 64], [1, 2, 3, 4], [7, 8, 9, 10]]
+    assert score.tolist() == [0.75, 0.5, 0.625]
+    many = [("a", (i, 2 * i, 8, 8), np.float32(i / 1000.0)) for i in range(1000)]
+    rows = bench.dump_outputs(str(tmp_path / "s1"), many, units, limit_bytes=44 * 100)     # 44 bytes per hit
+    assert set(rows.values()) == {100}
+    total = sum(os.path.getsize(str(p)) for p in (tmp_path / "s1").iterdir())
+    assert total <= 44 * 100 + 3 * 128                                                     # (.npy headers)
+    box = np.load(str(tmp_path / "s1" / "hits_box_xywh.npy"))
+    x = box[:, 0]
+    assert np.all(np.diff(x) > 0) and np.array_equal(box[:, 1], 2 * x)
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "hits_score.npy")), (x / 1000.0).astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "s2"), many, units, limit_bytes=44 * 100)
+    assert np.array_equal(np.load(str(tmp_path / "s2" / "hits_box_xywh.npy")), box)

@@ -2605,6 +2605,36 @@ def test_bench_gpus_flag_runs_the_device_group_without_a_launcher():
     assert out["planted_found"] and out["hits"] >= 64 and out["value"] > 0
 
 
+def test_bench_dump_outputs_is_the_timed_calls_hit_list(mtm, tmp_path):
+    """`python bench.py --steps 3 --dump-outputs DIR`: the line reports 3 timed steps and the milliseconds one of them took
+    (value x ms_per_step = pixel-correlations of one step), and DIR holds the hit list of the last timed call - the list
+    MTM.matchTemplates returns for the same seeded workload in this process."""
+    import json
+    import subprocess
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["BENCH_PREWARM_S"] = "0.05"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--no-cpu-baseline", "--skip-extras", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, env=env, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    img, units, _, method, thr, _ = bench.build_workload("north_star", 1)
+    px_corr = img.shape[0] * img.shape[1] * len(units)
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    assert abs(out["value"] * out["ms_per_step"] * 1e3 / px_corr - 1.0) < 2e-3
+    lab, box, score = (np.load(str(tmp_path / (n + ".npy"))) for n in ("hits_label_index", "hits_box_xywh", "hits_score"))
+    assert lab.dtype == np.float64 and box.dtype == np.float64 and score.dtype == np.float32
+    assert len(lab) == len(box) == len(score) == out["hits"] and out["planted_found"]
+    exp = mtm.matchTemplates(units, img, method=method, score_threshold=thr, maxOverlap=0.25)
+    labels = [u[0] for u in units]
+    assert lab.tolist() == [float(labels.index(h[0])) for h in exp]
+    assert box.tolist() == [[float(v) for v in h[1]] for h in exp]
+    assert np.abs(score - np.array([h[2] for h in exp], dtype=np.float32)).max() <= 1e-6
+
+
 def test_4k_photograph_default_mode_hit_lists(mtm):
     """A 4K photograph-like image (smooth score maps: thousands of peaks per template, plateau-free but full of
     near-ties) in the library's DEFAULT mode - reciprocal normalisation (not MTM_OPT_EXACT_DIV), hits-only first, map

@@ -3,6 +3,7 @@ worker threads and the generation-counter hand-over of the single-process multi-
 UndefinedBehaviorSanitizer and under ThreadSanitizer: tests/native/sanitize_host.cpp drives them with a fake per-device
 context (no GPU needed) through a few thousand randomised jobs.  SURVEY section 5 / round-2 review: "no sanitizer run"."""
 import os
+import platform
 import shutil
 import subprocess
 
@@ -27,5 +28,11 @@ def test_host_units_under_sanitizers(tmp_path, san):
     assert r.returncode == 0, r.stderr[-3000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
                TSAN_OPTIONS="halt_on_error=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=env)
+    run = [exe]
+    if san == "thread" and shutil.which("setarch"):
+        # GCC's ThreadSanitizer runtime expects the program's mappings at fixed addresses that a kernel with high-entropy
+        # ASLR (vm.mmap_rnd_bits = 32) places libraries far below: the program dies with SIGSEGV before main.  Newer LLVM
+        # runtimes re-exec themselves without randomisation in that case; this does the same for this one process.
+        run = ["setarch", platform.machine(), "-R", exe]
+    r = subprocess.run(run, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0 and "sanitize_host: ok" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])

@@ -278,8 +278,9 @@ int mtm_find_matches_image(mtm_ctx* ctx, const void* px, int rows, int cols, int
  * the hits of all templates (MTM/__init__.py:290-296 -> MTM/NMS.py:53-84 -> cv2.dnn.NMSBoxes): hits whose score passes
  * `score_threshold` (1 - score for TM_SQDIFF_NORMED, as NMS.py:73-75 transforms it), best first, each kept unless it
  * overlaps an already kept one by more than `max_overlap` (intersection over union, OpenCV's float expression); at most
- * `n_object` of them (n_object < 0: all).  Returns the kept hits in that order - the list mtm_nms would select from the
- * list mtm_find_matches_image returns.  Of thousands of peaks (dense images) the ones a neighbourhood's best peak suppresses
+ * `n_object` of them (n_object < 0: all - a sentinel, NOT Python's indexes[:n_object]: MTM.matchTemplates sends a finite
+ * negative N_object the two-step way, mtm_find_matches_image + mtm_nms + the slice).  Returns the kept hits in that
+ * order - the list mtm_nms would select from the list mtm_find_matches_image returns.  Of thousands of peaks (dense images) the ones a neighbourhood's best peak suppresses
  * are dropped on the device and never cross PCIe; mtm_timing.n_hits is the number of peaks before the suppression. */
 int mtm_find_matches_image_nms(mtm_ctx* ctx, const void* px, int rows, int cols, int chans, int dtype,
                                int64_t row_stride_bytes, double score_threshold, double max_overlap, int64_t n_object,

@@ -210,8 +210,8 @@ def _raw_matches(listTemplates, image, method, N_object, score_threshold, contex
             mask = None
             if len(tempTuple) >= 3:
                 if method in (0, 3):
-                    mask = tempTuple[2]
-                    if not (mask.shape == t.shape and mask.dtype == _U8):
+                    mask = tempTuple[2]         # (None: no mask, as the reference's TemplateTuple allows)
+                    if mask is not None and not (mask.shape == t.shape and mask.dtype == _U8):
                         units = None
                         break
                 else:
@@ -228,7 +228,9 @@ def _raw_matches(listTemplates, image, method, N_object, score_threshold, contex
             warnings.warn(_MSG_MASK_UNSUPPORTED)
         engine = context or _lib.engine_for(devices)
         with engine.lock:
-            if nms and hasattr(engine, "search_nms"):
+            # a finite negative N_object cuts the kept list from the end (indexes[:N_object], MTM/NMS.py:81-82), while the
+            # native call reads every negative value as "no limit": those calls take the two-step route
+            if nms and hasattr(engine, "search_nms") and (N_object == float("inf") or N_object >= 0):
                 n_obj = -1 if N_object == float("inf") else int(N_object)
                 hits = engine.search_nms(units, image, method, score_threshold, nms[0], n_obj)
                 del nms[:]

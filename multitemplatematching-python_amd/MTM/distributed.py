@@ -256,8 +256,8 @@ def _u8_units(sub, image, method):
         if len(t) >= 3:
             if method not in (0, 3):
                 return None                 # (the reference warns about the ignored mask: the general route does)
-            mask = t[2]
-            if not (mask.shape == a.shape and mask.dtype == np.uint8):
+            mask = t[2]                     # (None: no mask)
+            if mask is not None and not (mask.shape == a.shape and mask.dtype == np.uint8):
                 return None
         units.append((a, mask))
     return units
@@ -277,7 +277,10 @@ def matchTemplates_sharded(listTemplates, image, exchange: HitExchange, method=5
     sub = [listTemplates[i] for i in mine]
     # 8-bit inputs over the RCCL exchange: search, index remap, all-gather, merge and NMS in ONE native call
     # (mtm_find_matches_image_sharded_nms, round 5) - the same collective, the same selection
-    if find_local is None and exchange.backend == "rccl" and exchange.ctx is not None and N_object != 1:
+    # (a finite negative N_object cuts the kept list from the end, indexes[:N_object]; the native call reads it as "no
+    # limit": such calls take the step-by-step route)
+    if find_local is None and exchange.backend == "rccl" and exchange.ctx is not None and N_object != 1 and \
+            (N_object == float("inf") or N_object >= 0):
         units = _u8_units(sub, image, method)
         if units is not None:
             n_obj = -1 if N_object == float("inf") else int(N_object)

@@ -2,7 +2,7 @@
 Stand-in for the four cv2 entry points the reference's hot path touches (MTM/__init__.py:92,
 :226; MTM/NMS.py:78) plus the TM_* constants, backed by oracle/mtm_oracle.py.
 
-Used ONLY by tests/golden/make_golden.py, in the build container, to drive the UNMODIFIED
+Used ONLY by tests/golden/make_golden.py and make_hostfuzz.py, in the build container, to drive the UNMODIFIED
 reference package (cv2 is not installable here: no network).  Never shipped, never imported by the
 product or by the tests themselves.
 """

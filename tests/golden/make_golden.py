@@ -12,6 +12,9 @@ to tests/golden/*.npz / *.json.  No reference source is copied.
 
 Also stores the hit lists printed in the reference's executed notebooks (G1-G3); those values were
 produced by real OpenCV 4.7.0 and are what pins the oracle's arithmetic.
+
+Its companion tests/golden/make_hostfuzz.py (same container, same stand-in) records the seeded differential fuzz of the
+host layer, hostfuzz.json.gz; border_rules.py holds the nearest_border() patch both use.
 """
 import json
 import os
@@ -23,6 +26,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, "..", ".."))
 sys.path.insert(0, os.path.join(HERE, "cv2_standin"))
+sys.path.insert(0, HERE)
 sys.path.insert(0, "/root/reference")
 sys.path.append(os.path.join(ROOT, "multitemplatematching-python_amd"))     # synth only: `MTM` must be the reference's
 sys.dont_write_bytecode = True
@@ -116,32 +120,7 @@ ref["sqdiff_normed"] = hits_json(MTM.matchTemplates([("small", small), ("big", b
 # maximum filter with mode='constant'; releases >= 0.19 pass mode='nearest' - with zero padding a local MINIMUM
 # on the map border (methods 0/1: the map is negated, MTM/__init__.py:53) can never be a peak.  The
 # "<name>@nearest" fixtures are the same calls through the same 0.18.3 code with that one argument replaced.
-import contextlib  # noqa: E402
-import skimage.feature.peak as _pk  # noqa: E402
-
-
-class _NdiNearest:
-    """scipy.ndimage with maximum_filter(..., mode='nearest'), every other attribute untouched."""
-
-    def __init__(self, ndi):
-        self._ndi = ndi
-
-    def __getattr__(self, name):
-        return getattr(self._ndi, name)
-
-    def maximum_filter(self, *a, **kw):
-        kw["mode"] = "nearest"
-        return self._ndi.maximum_filter(*a, **kw)
-
-
-@contextlib.contextmanager
-def nearest_border():
-    saved = _pk.ndi
-    _pk.ndi = _NdiNearest(saved)
-    try:
-        yield
-    finally:
-        _pk.ndi = saved
+from border_rules import nearest_border  # noqa: E402
 
 
 corner = image[0:38, 0:41]          # an object touching the image corner: its best match is map pixel (0, 0)

@@ -1,70 +1,13 @@
 """The Python host layer (dtype policy, unit grouping, searchBox offsets, hit construction, NMS
 hand-off) exercised on CPU with a stand-in context whose kernels are the oracle.  This checks the
 host logic only; the HIP kernels are checked by tests/test_gpu_parity.py on the GPU box."""
-import threading
-
 import numpy as np
 import pytest
 
 import mtm_oracle as O
-from helpers import assert_hits_equal, canon, coin_templates, load_coins, load_golden
+from helpers import FusedContext, OracleContext, assert_hits_equal, canon, coin_templates, load_coins, load_golden
 
 REF = load_golden()["reference_run"]
-
-
-class OracleContext:
-    """Implements the _lib.Context surface the host layer uses, on the oracle."""
-
-    def __init__(self, hit_dtype):
-        self.lock = threading.RLock()
-        self.hit_dtype = hit_dtype
-
-    @staticmethod
-    def _as_cv2_sees_it(a):
-        # MTM_U16: the library takes uint16 pixels as they are; the reference casts them to float32
-        # (exactly) before cv2.matchTemplate (MTM/__init__.py:71-74)
-        return a.astype(np.float32) if a is not None and a.dtype == np.uint16 else a
-
-    def set_image(self, image, downscale=1):
-        self.image = self._as_cv2_sees_it(O.downscale_area(image, downscale))       # mtm_set_image_downscaled
-
-    def set_templates(self, templates, method):
-        self.templates, self.method = [(self._as_cv2_sees_it(t), self._as_cv2_sees_it(m)) for t, m in templates], method
-
-    def score_map(self, idx, shape):
-        t, m = self.templates[idx]
-        out = O.match_template(self.image, t, self.method, mask=m)
-        assert out.shape == tuple(shape)
-        return out
-
-    def search(self, templates, image, method, mode, thr):          # the engine interface (Context / Group)
-        self.set_templates(templates, method)
-        return self.find_matches_image(image, mode, thr)
-
-    def find_matches_image(self, image, mode, thr):                 # mtm_find_matches_image
-        self.set_image(image)
-        return self._find(mode, thr)
-
-    def find_matches(self, mode, thr, next_image=None):
-        try:
-            return self._find(mode, thr)
-        finally:
-            if next_image is not None:      # mtm_find_matches_next: the next image becomes current
-                self.image = next_image
-
-    def _find(self, mode, thr):
-        rows = []
-        for i, (t, m) in enumerate(self.templates):
-            cmap = O.match_template(self.image, t, self.method, mask=m)
-            if mode == 1:
-                _, _, mn, mx = O.min_max_loc(cmap)
-                peaks = [mn[::-1]] if self.method in (0, 1) else [mx[::-1]]
-            elif self.method in (0, 1):
-                peaks = O.find_local_min(cmap, thr)
-            else:
-                peaks = O.find_local_max(cmap, thr)
-            rows += [(i, int(p[1]), int(p[0]), t.shape[1], t.shape[0], cmap[tuple(p)]) for p in peaks]
-        return np.array(rows, dtype=self.hit_dtype) if rows else np.zeros(0, dtype=self.hit_dtype)
 
 
 @pytest.fixture()
@@ -101,18 +44,6 @@ def test_fused_search_and_nms_entry_is_used_and_equivalent(mtm, monkeypatch):
     """matchTemplates hands the non-maxima suppression to the engine where the engine offers `search_nms` (one native call:
     mtm_find_matches_image_nms) - for every N_object but 1, never for TM_SQDIFF, never for the general (non 8-bit) path -
     and returns what the two-step route returns.  The stand-in's search_nms is search + the library's host NMS (mtm_nms)."""
-    from MTM import _lib
-    calls = []
-
-    class FusedContext(OracleContext):
-        def search_nms(self, templates, image, method, thr, max_overlap, n_object=-1):
-            calls.append((method, n_object))
-            raw = self.search(templates, image, method, 0, thr)
-            if len(raw) <= 1:                                   # MTM/NMS.py:53-55
-                return raw
-            idx = _lib.nms_hits(raw, thr, max_overlap, ascending=(method == 1))
-            return raw[idx] if n_object < 0 else raw[idx][:n_object]
-
     coins = load_coins()
     small, big = coin_templates(coins)
     lt = [("small", small), ("big", big)]
@@ -121,7 +52,9 @@ def test_fused_search_and_nms_entry_is_used_and_equivalent(mtm, monkeypatch):
              dict(score_threshold=0.3, method=3, maxOverlap=0.3, N_object=0), dict(score_threshold=0.99, method=5)]
     two_step = [mtm.matchTemplates(lt, coins, **kw) for kw in cases]
     best = mtm.matchTemplates(lt, coins, method=5, N_object=1)
-    monkeypatch.setattr(mtm._lib, "_default_ctx", FusedContext(mtm._lib.HIT_DTYPE))
+    fused = FusedContext(mtm._lib.HIT_DTYPE)
+    calls = fused.calls
+    monkeypatch.setattr(mtm._lib, "_default_ctx", fused)
     assert [mtm.matchTemplates(lt, coins, **kw) for kw in cases] == two_step
     assert calls == [(5, -1), (5, 3), (1, -1), (5, -1), (3, 0), (5, -1)]
     assert mtm.matchTemplates(lt, coins, method=5, N_object=1) == best and len(calls) == 6           # the global extremum: search()

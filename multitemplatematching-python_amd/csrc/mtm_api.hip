@@ -45,13 +45,166 @@ int stage_next_image(mtm_ctx* c, NextImage* nx) {
 }
 
 int find_matches_impl(mtm_ctx* c, int mode, double score_threshold, mtm_hit* out, int64_t capacity,
-                      int64_t* n_out, NextImage* next, const ImageArgs* up = nullptr);
+                      int64_t* n_out, NextImage* next, const ImageArgs* up = nullptr, const NmsRequest* nms = nullptr);
 
 constexpr size_t kHitPrefetch = 1024;       // candidate / hit records fetched together with the counters
 
-int fm_begin(mtm_ctx* c, int mode, double score_threshold, NextImage* next, FmState& S, const ImageArgs* up = nullptr) {
+// The route of a call on the placed templates and the current image (`banded`: it arrives in row bands), decided from the
+// context's switches and back-off counters.  No HIP call, no change to the context: fm_begin acts on what it returns.
+CallRoute plan_call(const mtm_ctx* c, int mode, float thr, bool banded) {
+    CallRoute R;
+    const int n = (int)c->templs.size();
+    const bool mode_min = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_SQDIFF_NORMED;
+    R.mode = mode;
+    R.n = n;
+    R.thr = thr;
+    R.mode_min = mode_min;
+    R.cand_cap = std::min<int64_t>(c->hit_cap, 4096LL * 256);
+    R.banded_u8 = banded && c->dtype == MTM_U8;
+    // masked float32 classes: the bf16 screen needs the threshold - local extrema, or (mbf_global) the templates' best
+    // lower bounds and everything that reaches them; mtm_score_map keeps the float64 kernel.  What the peak pass compares
+    // with: the float32 threshold, on float32 scores.
+    R.mbf_thr_on = n > 0 && f32_refined(c);
+    R.mbf_global = mode == MTM_PEAKS_GLOBAL;
+    R.mbf_thr = thr;
+
+    // fused peak candidates: only when every class runs the MFMA kernel - and not while the maps of this context are
+    // known to be dense (the last attempts overflowed the candidate list: smooth images at a low threshold), where the
+    // full peak pass over the maps is the cheaper route
+    bool fused = mode == MTM_PEAKS_LOCAL && n > 0 && c->fuse_backoff == 0;
+    // Segment flags (the default route while the back-off lasts): the maps go to memory as in map mode, and the score kernel
+    // sets a flag per row segment (a wave's 256 outputs of one template row) in which something passes the threshold;
+    // peaks_sparse_kernel visits those instead of scanning 1 GB of maps (4K x 32 templates).  A first version wrote only
+    // the flagged segments, from the hits-only screens: no faster - on such images the screens pass nearly everywhere.
+    // uint8 classes on the lean 1- / 3-channel MFMA epilogue, every map 2-D.
+    if (mode == MTM_PEAKS_LOCAL && n > 0 && !fused && c->sparse_maps && c->hits_only &&
+        c->dtype == MTM_U8 && (c->chans == 1 || c->chans == 3) && (int)c->list2d.size() == n) {
+        bool ok = true;
+        int max_oh = 0, max_nseg = 0;
+        for (const SizeClass& sc : c->classes) {
+            ok = ok && resolved_kernel(c, sc) == MTM_KERNEL_MFMA && sc.slabs.empty();
+            max_oh = std::max(max_oh, c->rows - sc.h + 1);
+            max_nseg = std::max(max_nseg, (c->cols - sc.w + 1 + kMfSeg - 1) / kMfSeg);
+        }
+        // (bounded: the flags are cleared on every call and compact_hits_kernel sums the per-(template, strip) counters in
+        // every block - with thousands of templates the flagged route would cost more than the full scan it replaces)
+        if (ok && (long long)n * max_oh * max_nseg <= (64ll << 20) && (long long)n * max_nseg <= 4096) {
+            R.flag_rstride = max_nseg;
+            R.flag_tstride = max_oh * max_nseg;
+            R.sparse = true;
+            R.cand_min = mode_min;          // the threshold the score kernel flags against (launch_ncc)
+            R.cand_thr = mode_min ? -thr : thr;
+        }
+    }
+    for (const SizeClass& sc : c->classes) {
+        const int rk = resolved_kernel(c, sc);
+        fused = fused && (rk == MTM_KERNEL_MFMA || rk == MTM_KERNEL_MFMA16 || rk == MTM_KERNEL_MFMA_F32);
+    }
+    // float32 images on the bf16 matrix cores: the kernel's scores are a screen, the decisions are taken on exact
+    // float64 scores (mtm_refine.hip.h).  Calls that mix bf16 classes with float64-kernel ones (float masks) run
+    // everything on the float64 kernel.  (refine and f32_exact exclude each other on every route.)
+    {
+        bool any_bf16 = false, all_bf16 = n > 0;
+        for (const SizeClass& sc : c->classes) {
+            const bool b = resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32;
+            any_bf16 = any_bf16 || b;
+            all_bf16 = all_bf16 && b;
+        }
+        // raw sums (TM_SQDIFF / TM_CCORR / TM_CCOEFF): only the refined global extremum runs on the matrix cores - maps and
+        // thresholds on unnormalised sums have no error the bf16 pieces could promise (an exact copy is TM_SQDIFF 0)
+        const bool raw_m = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_CCORR || c->method == MTM_TM_CCOEFF;
+        // ... except, round 5, local extrema against a threshold while the kernel's candidate list is available: every output
+        // whose upper bound (score + E, E in the sum's own units) passes the threshold is listed and re-scored exactly -
+        // route 1 only; maps, the map scan and every overflow keep the float64 kernel
+        R.raw_rig = any_bf16 && all_bf16 && raw_m && mode == MTM_PEAKS_LOCAL && f32_refined(c) && fused;
+        if (any_bf16 && raw_m && (mode != MTM_PEAKS_GLOBAL || !f32_refined(c)) && !R.raw_rig) {
+            R.f32_exact = true;
+        } else if (any_bf16 && f32_refined(c)) {
+            if (all_bf16) R.refine = true;
+            else R.f32_exact = true;
+        }
+    }
+    if (R.f32_exact) fused = false;                 // the float64 kernel writes maps and lists no candidates
+    // fused global extremum (cv2.minMaxLoc inside the score kernel): every class on the 1- or 3-channel MFMA kernel
+    // (plain, two-row, row-multiplexed or in slabs - there in slab_combine_kernel; binary masks with the reciprocal
+    // normalisation), the uint16 byte-plane kernel
+    // or the float32 kernel; same switch as the hits-only mode (MTM_OPT_HITS_ONLY)
+    if (mode == MTM_PEAKS_GLOBAL && c->hits_only && n > 0 && (c->chans == 1 || c->chans == 3) && !R.f32_exact) {
+        bool ok = true;
+        for (const SizeClass& sc : c->classes)
+            ok = ok && ((resolved_kernel(c, sc) == MTM_KERNEL_MFMA &&
+                         (!sc.masked || (c->exact_div < 2 && c->chans == 1 && c->method <= MTM_TM_CCORR_NORMED))) ||
+                        resolved_kernel(c, sc) == MTM_KERNEL_MFMA16 || resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32);
+        if (ok) {
+            R.ext = R.cand_on = R.hits_only = true;
+            R.cand_min = mode_min;
+            R.cand_thr = 0.0f;
+        }
+    }
+    if (mode == MTM_PEAKS_GLOBAL && R.refine && !R.ext) {
+        // no fused extremum in this configuration (maps requested, MTM_FUSE_PEAKS=0): the float64 kernel + extremum_kernel
+        R.refine = false;
+        R.f32_exact = true;
+    }
+    // the refined routes' own thresholds: rig_thr the exact one, rig_cap the widest error bound the map scan's tolerances
+    // cover (4 x the largest class constant: windows whose mean lies within ~4 standard deviations of their tile's)
+    if (R.refine) {
+        const float tq = mode_min ? -thr : thr;
+        R.rig_thr = tq;
+        float eps = 0.0f;
+        for (const SizeClass& sc : c->classes)
+            if (resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32) eps = std::max(eps, bf16_rig_eps(c->chans, sc.h, bf16_nkb(sc.w)));
+        R.rig_cap = std::max(kRefineThrMargin, 4.0f * eps);
+        R.scan_thr = tq - R.rig_cap * std::max(1.0f, std::fabs(tq));
+    }
+    // float32 refinement without kernel candidates: the potential peaks of a map scan, listed in the candidate buffer
+    if (mode == MTM_PEAKS_LOCAL && R.refine && !fused && n > 0) {
+        R.pp_mode = R.refine_scan = true;
+        R.cand_min = mode_min;
+        R.cand_thr = R.scan_thr;
+    }
+    if (fused) {
+        R.fused = R.cand_on = true;
+        // the counter is normally cleared right after the previous call fetched it (off the critical path); round 5: a banded
+        // uint8 call lets its first statistics launch do it (zero_pending; run_score_banded) - no fill command at all
+        R.zero_pending = R.banded_u8;
+        R.cand_min = mode_min;
+        R.cand_thr = mode_min ? -thr : thr;
+        // (float32 refinement: everything within the margin of the threshold is listed and re-scored)
+        if (R.refine) R.cand_thr -= kRefineThrMargin * std::max(1.0f, std::fabs(R.cand_thr));
+        // hits-only: single-channel MFMA classes, every map 2-D, no recent candidate overflow
+        R.hits_only = c->hits_only && (c->chans == 1 || c->chans == 3) && (int)c->list2d.size() == n;
+    }
+    // hash table of the candidate positions (hits-only verification on the device: only when the
+    // candidates are too many to be checked on the host, see fm_end)
+    if (R.hits_only && !R.ext) {
+        size_t hsz = 1024;
+        while (hsz < 2 * (size_t)R.cand_cap) hsz <<= 1;
+        R.hash_mask = (unsigned)(hsz - 1);
+    }
+    // The landing buffer of the candidate list (pinned).  Round 5: when every class of the call runs ncc_mfma_kernel's own
+    // epilogue, the waves that fill the first slots of the list write them there as well (MfmaParams::cand_pin) and the
+    // host finds them when the last score launch has ended - no fetch kernel (or copy command) with its kernel boundary
+    // behind the score pass.
+    R.prefetched = mode == MTM_PEAKS_LOCAL && fused && !c->list2d.empty();
+    if (R.prefetched) {
+        bool pin = c->cand_pinned != 0 && !R.refine;
+        for (const SizeClass& sc : c->classes) {
+            const int rk = resolved_kernel(c, sc);
+            pin = pin && ((rk == MTM_KERNEL_MFMA && sc.slabs.empty()) || rk == MTM_KERNEL_MFMA16);
+        }
+        R.cand_pin = pin;
+        R.cand_pin_n = std::min<size_t>(kHitPrefetch, (size_t)R.cand_cap);
+    }
+    // float32: the hits-only refined routes (kernel candidates re-scored; the fused extremum by bounds) and the masked
+    // classes' screen start with ONE piece product unless a recent call overflowed its list that way
+    R.bf16_np = c->dtype == MTM_F32 && c->f32_mfma == 1 && c->np1_backoff == 0 ? 1 : 3;
+    return R;
+}
+
+int fm_begin(mtm_ctx* c, int mode, double score_threshold, NextImage* next, CallRoute& R, const ImageArgs* up = nullptr) {
     HIPC(hipSetDevice(c->device));
-    bool banded = false;
+    bool banded = false, single_band = false;
     if (up) {
         // the geometry first (placement depends on it); the pixels follow in stream order
         adopt_image(c, up->rows, up->cols, up->chans, up->dtype);
@@ -66,7 +219,7 @@ int fm_begin(mtm_ctx* c, int mode, double score_threshold, NextImage* next, FmSt
     MTMC(place_templates(c));
     host_trace(c, 2);
     if (up) {
-        banded = banded_ok(c, *up);
+        banded = banded_ok(c, *up, &single_band);
         if (!banded) {
             const int rc = upload_image(c, c->slot[c->cur], up->px, up->stride, up->rows, up->cols, up->chans, up->dtype,
                                         c->stream);
@@ -76,182 +229,37 @@ int fm_begin(mtm_ctx* c, int mode, double score_threshold, NextImage* next, FmSt
             }
         }
     }
-    const int n = (int)c->templs.size();
-    const bool mode_min = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_SQDIFF_NORMED;
-    // numpy compares the float32 map with the python-float threshold in float32
-    const float thr = (float)score_threshold;
     c->timing = mtm_timing{};
     c->maps_valid = false;
-    c->seg_skip_used = false;
-    // masked float32 classes: the bf16 screen needs the threshold (local extrema only; mtm_score_map and N_object == 1 keep
-    // the float64 kernel).  What the peak pass compares with: the float32 threshold, on float32 scores.
-    c->mbf_used = false;
-    c->mbf_thr_on = (mode == MTM_PEAKS_LOCAL || mode == MTM_PEAKS_GLOBAL) && n > 0 && f32_refined(c);
-    c->mbf_global = mode == MTM_PEAKS_GLOBAL;
-    c->mbf_thr = thr;
-
-    // fused peak candidates: only when every class runs the MFMA kernel - and not while the maps of this context are
-    // known to be dense (the last attempts overflowed the candidate list: smooth images at a low threshold), where the
-    // full peak pass over the maps is the cheaper route
-    bool fused = mode == MTM_PEAKS_LOCAL && n > 0;
-    if (fused && c->fuse_backoff > 0) {
-        --c->fuse_backoff;
-        fused = false;
-    }
-    // Segment flags (the default route while the back-off lasts): the maps go to memory as in map mode, and the score kernel
-    // sets a flag per row segment (a wave's 256 outputs of one template row) in which something passes the threshold;
-    // peaks_sparse_kernel visits those instead of scanning 1 GB of maps (4K x 32 templates).  A first version wrote only
-    // the flagged segments, from the hits-only screens: no faster - on such images the screens pass nearly everywhere.
-    // uint8 classes on the lean 1- / 3-channel MFMA epilogue, every map 2-D.
-    c->sparse_now = false;
-    if (mode == MTM_PEAKS_LOCAL && n > 0 && !fused && c->sparse_maps && c->hits_only &&
-        c->dtype == MTM_U8 && (c->chans == 1 || c->chans == 3) && (int)c->list2d.size() == n) {
-        bool ok = true;
-        int max_oh = 0, max_nseg = 0;
-        for (const SizeClass& sc : c->classes) {
-            ok = ok && resolved_kernel(c, sc) == MTM_KERNEL_MFMA && sc.slabs.empty();
-            max_oh = std::max(max_oh, c->rows - sc.h + 1);
-            max_nseg = std::max(max_nseg, (c->cols - sc.w + 1 + kMfSeg - 1) / kMfSeg);
-        }
-        // (bounded: the flags are cleared on every call and compact_hits_kernel sums the per-(template, strip) counters in
-        // every block - with thousands of templates the flagged route would cost more than the full scan it replaces)
-        if (ok && (long long)n * max_oh * max_nseg <= (64ll << 20) && (long long)n * max_nseg <= 4096) {
-            c->flag_rstride = max_nseg;
-            c->flag_tstride = max_oh * max_nseg;
-            MTMC(c->seg_flags.ensure((size_t)n * c->flag_tstride));
-            HIPC(hipMemsetAsync(c->seg_flags.p, 0, (size_t)n * c->flag_tstride, c->stream));
-            c->sparse_now = true;
-        }
-    }
-    for (const SizeClass& sc : c->classes) {
-        const int rk = resolved_kernel(c, sc);
-        fused = fused && (rk == MTM_KERNEL_MFMA || rk == MTM_KERNEL_MFMA16 || rk == MTM_KERNEL_MFMA_F32);
-    }
-    c->cand_on = false;
-    c->hits_only_now = false;
-    c->ext_now = false;
-    if (c->sparse_now) {                // the threshold the score kernel flags against (launch_ncc)
-        c->cand_min = mode_min;
-        c->cand_thr = mode_min ? -thr : thr;
-    }
-    // float32 images on the bf16 matrix cores: the kernel's scores are a screen, the decisions are taken on exact
-    // float64 scores (mtm_refine.hip.h).  Calls that mix bf16 classes with float64-kernel ones (float masks) run
-    // everything on the float64 kernel.
-    c->refine_now = c->refine_scan_now = c->f32_exact_now = false;
-    {
-        bool any_bf16 = false, all_bf16 = n > 0;
-        for (const SizeClass& sc : c->classes) {
-            const bool b = resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32;
-            any_bf16 = any_bf16 || b;
-            all_bf16 = all_bf16 && b;
-        }
-        // raw sums (TM_SQDIFF / TM_CCORR / TM_CCOEFF): only the refined global extremum runs on the matrix cores - maps and
-        // thresholds on unnormalised sums have no error the bf16 pieces could promise (an exact copy is TM_SQDIFF 0)
-        const bool raw_m = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_CCORR || c->method == MTM_TM_CCOEFF;
-        // ... except, round 5, local extrema against a threshold while the kernel's candidate list is available: every output
-        // whose upper bound (score + E, E in the sum's own units) passes the threshold is listed and re-scored exactly -
-        // route 1 only; maps, the map scan and every overflow keep the float64 kernel
-        c->raw_rig_now = any_bf16 && all_bf16 && raw_m && mode == MTM_PEAKS_LOCAL && f32_refined(c) && fused;
-        if (any_bf16 && raw_m && (mode != MTM_PEAKS_GLOBAL || !f32_refined(c)) && !c->raw_rig_now) {
-            c->f32_exact_now = true;
-        } else if (any_bf16 && f32_refined(c)) {
-            if (all_bf16) c->refine_now = true;
-            else c->f32_exact_now = true;
-        }
-    }
-    if (c->f32_exact_now) fused = false;            // the float64 kernel writes maps and lists no candidates
-    // fused global extremum (cv2.minMaxLoc inside the score kernel): every class on the 1- or 3-channel MFMA kernel
-    // (plain, two-row, row-multiplexed or in slabs - there in slab_combine_kernel; binary masks with the reciprocal
-    // normalisation), the uint16 byte-plane kernel
-    // or the float32 kernel; same switch as the hits-only mode (MTM_OPT_HITS_ONLY)
-    if (mode == MTM_PEAKS_GLOBAL && c->hits_only && n > 0 && (c->chans == 1 || c->chans == 3) &&
-        !c->f32_exact_now) {
-        bool ok = true;
-        for (const SizeClass& sc : c->classes)
-            ok = ok && ((resolved_kernel(c, sc) == MTM_KERNEL_MFMA &&
-                         (!sc.masked || (c->exact_div < 2 && c->chans == 1 && c->method <= MTM_TM_CCORR_NORMED))) ||
-                        resolved_kernel(c, sc) == MTM_KERNEL_MFMA16 || resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32);
-        if (ok) {
-            MTMC(c->counters.ensure(sizeof(unsigned long long) * 2 * (size_t)n));
-            HIPC(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * 2 * (size_t)n, c->stream));
-            c->ext_now = true;
-            c->cand_on = true;
-            c->hits_only_now = true;
-            c->cand_min = mode_min;
-            c->cand_thr = 0.0f;
-        }
-    }
+    // numpy compares the float32 map with the python-float threshold in float32
+    R = plan_call(c, mode, (float)score_threshold, banded);
+    R.single_band = single_band;
     host_trace(c, 18);
-    const int64_t cand_cap = std::min<int64_t>(c->hit_cap, 4096LL * 256);
-    if (mode == MTM_PEAKS_GLOBAL && c->refine_now && !c->ext_now) {
-        // no fused extremum in this configuration (maps requested, MTM_FUSE_PEAKS=0): the float64 kernel + extremum_kernel
-        c->refine_now = false;
-        c->f32_exact_now = true;
+    // the back-off countdowns: a call the back-off kept from its route counts it down
+    if (mode == MTM_PEAKS_LOCAL && R.n > 0 && c->fuse_backoff > 0) --c->fuse_backoff;
+    if (c->dtype == MTM_F32 && c->f32_mfma == 1 && c->np1_backoff > 0) --c->np1_backoff;
+
+    // the route's buffers
+    if (R.sparse) {
+        MTMC(c->seg_flags.ensure((size_t)R.n * R.flag_tstride));
+        HIPC(hipMemsetAsync(c->seg_flags.p, 0, (size_t)R.n * R.flag_tstride, c->stream));
     }
-    // the refined routes list their records in the candidate buffer: the outputs within the margin of the running best
-    // (global extremum), the potential peaks of the map scan (local extrema without kernel candidates)
-    const bool pp_mode = mode == MTM_PEAKS_LOCAL && c->refine_now && !fused && n > 0;
-    if ((c->refine_now && c->ext_now) || pp_mode) {
-        const size_t cands_cap = c->cands.cap;
-        MTMC(c->cands.ensure(16 + sizeof(mtm_hit) * (size_t)c->hit_cap));
-        if (c->cands.cap != cands_cap) c->cands_zeroed = nullptr;
-        if (c->cands.p != c->cands_zeroed) HIPC(hipMemsetAsync(c->cands.p, 0, 16, c->stream));
-        c->cands_zeroed = nullptr;
+    if (R.ext) {
+        MTMC(c->counters.ensure(sizeof(unsigned long long) * 2 * (size_t)R.n));
+        HIPC(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * 2 * (size_t)R.n, c->stream));
     }
-    // the refined routes' own thresholds: rig_thr the exact one, rig_cap the widest error bound the map scan's tolerances
-    // cover (4 x the largest class constant: windows whose mean lies within ~4 standard deviations of their tile's)
-    if (c->refine_now) {
-        const float tq = mode_min ? -thr : thr;
-        c->rig_thr = tq;
-        float eps = 0.0f;
-        for (const SizeClass& sc : c->classes)
-            if (resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32) eps = std::max(eps, bf16_rig_eps(c->chans, sc.h, bf16_nkb(sc.w)));
-        c->rig_cap = std::max(kRefineThrMargin, 4.0f * eps);
-        c->scan_thr = tq - c->rig_cap * std::max(1.0f, std::fabs(tq));
-    }
-    if (pp_mode) {
-        c->refine_scan_now = true;
-        c->cand_min = mode_min;
-        c->cand_thr = c->scan_thr;
-    }
-    if (fused) {
+    // the candidate buffer: kernel candidates, and the refined routes' records - the outputs within the margin of the running
+    // best (global extremum), the potential peaks of the map scan (local extrema without kernel candidates)
+    if (R.fused || R.pp_mode || (R.refine && R.ext)) {
         const size_t cands_cap = c->cands.cap;
         MTMC(c->cands.ensure(16 + sizeof(mtm_hit) * (size_t)c->hit_cap));
         if (c->cands.cap != cands_cap) c->cands_zeroed = nullptr;      // reallocated (possibly at the same address)
-        // the counter is normally cleared right after the previous call fetched it (off the critical path); round 5: a banded
-        // uint8 call lets its first statistics launch do it (zero_pending; run_score_banded) - no fill command at all
-        c->zero_pending = false;
-        if (banded && c->dtype == MTM_U8) c->zero_pending = true;
-        else if (c->cands.p != c->cands_zeroed) HIPC(hipMemsetAsync(c->cands.p, 0, 16, c->stream));
+        if (!R.zero_pending && c->cands.p != c->cands_zeroed) HIPC(hipMemsetAsync(c->cands.p, 0, 16, c->stream));
         c->cands_zeroed = nullptr;
-        c->cand_on = true;
-        c->cand_min = mode_min;
-        c->cand_thr = mode_min ? -thr : thr;
-        // (float32 refinement: everything within the margin of the threshold is listed and re-scored)
-        if (c->refine_now) c->cand_thr -= kRefineThrMargin * std::max(1.0f, std::fabs(c->cand_thr));
-        // hits-only: single-channel MFMA classes, every map 2-D, no recent candidate overflow
-        bool honly = c->hits_only && (c->chans == 1 || c->chans == 3) && (int)c->list2d.size() == n;
-        c->hits_only_now = honly;
     }
-    // hash table of the candidate positions (hits-only verification on the device: only when the
-    // candidates are too many to be checked on the host, see below)
-    unsigned hash_mask = 0;
-    if (c->hits_only_now && !c->ext_now) {
-        size_t hsz = 1024;
-        while (hsz < 2 * (size_t)cand_cap) hsz <<= 1;
-        hash_mask = (unsigned)(hsz - 1);
-        MTMC(c->chash.ensure(hsz * (sizeof(unsigned long long) + sizeof(int))));
-    }
-
-    // The landing buffer of the candidate list (pinned).  Round 5: when every class of the call runs ncc_mfma_kernel's own
-    // epilogue, the waves that fill the first slots of the list write them there as well (MfmaParams::cand_pin) and the
-    // host finds them when the last score launch has ended - no fetch kernel (or copy command) with its kernel boundary
-    // behind the score pass.  The window starts out as "no record" (template index -1) in every slot.
-    c->cand_pin_now = false;
-    const bool want_prefetch = mode == MTM_PEAKS_LOCAL && fused && !c->list2d.empty();
-    const size_t nfetch_w = std::min<size_t>(kHitPrefetch, (size_t)cand_cap);
-    if (want_prefetch) {
-        const size_t fetch_bytes = 16 + sizeof(mtm_hit) * nfetch_w;
+    if (R.hash_mask) MTMC(c->chash.ensure(((size_t)R.hash_mask + 1) * (sizeof(unsigned long long) + sizeof(int))));
+    if (R.prefetched) {
+        const size_t fetch_bytes = 16 + sizeof(mtm_hit) * R.cand_pin_n;
         if (c->pinned_cap < fetch_bytes) {
             if (c->pinned) (void)hipHostFree(c->pinned);
             c->pinned = nullptr;
@@ -259,73 +267,46 @@ int fm_begin(mtm_ctx* c, int mode, double score_threshold, NextImage* next, FmSt
             HIPC(hipHostMalloc(&c->pinned, fetch_bytes, hipHostMallocDefault));
             c->pinned_cap = fetch_bytes;
         }
-        bool pin = c->cand_pinned != 0 && !c->refine_now;
-        for (const SizeClass& sc : c->classes) {
-            const int rk = resolved_kernel(c, sc);
-            pin = pin && ((rk == MTM_KERNEL_MFMA && sc.slabs.empty()) || rk == MTM_KERNEL_MFMA16);
-        }
-        if (pin) {
+        if (R.cand_pin) {               // the window starts out as "no record" (template index -1) in every slot
             uint8_t* land = static_cast<uint8_t*>(c->pinned);
             std::memset(land, 0, 16);
             mtm_hit* w = reinterpret_cast<mtm_hit*>(land + 16);
-            for (size_t i = 0; i < nfetch_w; ++i) w[i].templ_idx = -1;
-            c->cand_pin_now = true;
-            c->cand_pin_n = nfetch_w;
+            for (size_t i = 0; i < R.cand_pin_n; ++i) w[i].templ_idx = -1;
         }
-    }
-    // float32: the hits-only refined routes (kernel candidates re-scored; the fused extremum by bounds) and the masked
-    // classes' screen start with ONE piece product (mtm_ctx::bf16_np_now) unless a recent call overflowed its list that way
-    c->bf16_np_now = 3;
-    if (c->dtype == MTM_F32 && c->f32_mfma == 1) {
-        if (c->np1_backoff > 0) --c->np1_backoff;
-        else c->bf16_np_now = 1;
     }
     host_trace(c, 3);
     // start of the GPU time of the call (timing.total_ms).  Banded: recorded by run_score_banded once the first band's
     // copy is on its way - nothing is queued ahead of that copy that does not have to be (every API call is 5-10 us)
     if (!banded) HIPC(hipEventRecord(c->ev[0], c->stream));
     if (banded) {
-        const int rc = run_score_banded(c, *up);
+        const int rc = run_score_banded(c, R, *up);
         if (rc != MTM_OK) {
             c->have_image = false;                   // possibly half an image on the device
             (void)hipStreamSynchronize(c->copy_stream);
             return rc;
         }
     } else {
-        MTMC(run_score_all(c));
+        MTMC(run_score_all(c, R));
     }
     HIPC(hipEventRecord(c->ev[1], c->stream));
     host_trace(c, 9);
-    c->cand_on = false;
-    const bool pin_direct = c->cand_pin_now;
-    c->cand_pin_now = false;
+    // (the first pass only: a re-run of the score pass lists no candidates unless its transition asks for them)
+    R.cand_on = false;
+    R.pin_direct = R.cand_pin;
+    R.cand_pin = false;
     // stream mode: the kernels of this image are on their way - start the upload of the next one now.
     // (Not later: the device-to-host copy of the hit records below lands in pageable memory, which
     // the runtime executes synchronously, i.e. after the kernels.)
     MTMC(stage_next_image(c, next));
-
-    S.mode = mode;
-    S.thr = thr;
-    S.mode_min = mode_min;
-    S.fused = fused;
-    S.n = n;
-    S.cand_cap = cand_cap;
-    S.hash_mask = hash_mask;
-    S.prefetched = false;
-    S.pp_mode = pp_mode;
-    S.pin_direct = pin_direct;
-    S.banded_u8 = banded && c->dtype == MTM_U8;
-    if (want_prefetch) {
+    if (R.prefetched) {
         // Few candidates (the usual case): they are in the pinned landing buffer when the stream is done and the 3x3 test
         // runs on the host (fm_end) - written there by the score kernel itself (pin_direct), else by a one-group kernel
-        const size_t nfetch = nfetch_w;
-        if (!pin_direct) {
+        if (!R.pin_direct) {
             hipLaunchKernelGGL(fetch_cands_kernel, dim3(1), dim3(256), 0, c->stream, c->cands.as<uint4>(),
-                               static_cast<uint4*>(c->pinned), (unsigned long long)nfetch);
+                               static_cast<uint4*>(c->pinned), (unsigned long long)R.cand_pin_n);
             HIPC(hipGetLastError());
         }
         HIPC(hipEventRecord(c->ev[2], c->stream));
-        S.prefetched = true;
     }
     return MTM_OK;
 }
@@ -341,7 +322,7 @@ struct DeviceNms {
     const mtm_hit* out = nullptr;
 };
 
-int queue_device_nms(mtm_ctx* c, const mtm_hit* dhits, const unsigned long long* dcount, bool ascending, DeviceNms* q) {
+int queue_device_nms(mtm_ctx* c, const NmsRequest& req, const mtm_hit* dhits, const unsigned long long* dcount, bool ascending, DeviceNms* q) {
     // (a cell larger than the largest box side is still correct - the 3x3 cell neighbourhood covers every partner - and
     // small templates on a large image would otherwise make millions of cells to clear and scan on every attempt)
     int cell = 32;
@@ -355,8 +336,8 @@ int queue_device_nms(mtm_ctx* c, const mtm_hit* dhits, const unsigned long long*
     p.ascending = ascending ? 1 : 0;
     // MTM/NMS.py:73-78: the scores are float32 (1 - score for the difference methods), the threshold a python float
     // transformed in double and narrowed by the cv2 binding
-    p.thr_score = (float)(ascending ? (1.0 - c->nms_req.score_threshold) : c->nms_req.score_threshold);
-    p.thr_overlap = (float)c->nms_req.max_overlap;
+    p.thr_score = (float)(ascending ? (1.0 - req.score_threshold) : req.score_threshold);
+    p.thr_overlap = (float)req.max_overlap;
     p.cell = cell;
     p.gw = c->cols / cell + 3;
     p.gh = c->rows / cell + 3;
@@ -415,24 +396,102 @@ int fetch_device_nms(mtm_ctx* c, const DeviceNms& qd, unsigned long long count, 
     return MTM_OK;
 }
 
+// ---- The fallback ladder.  An overflowing list moves the call one step down: each transition below lowers the route (a
+// slower route, or a longer list), keeps the context's back-off in step and re-runs what the lowered route needs.
+inline void back_off(int& counter, int& len) {      // the next `len` calls skip the route; the period doubles while they overflow
+    counter = len;
+    len = std::min(2 * len, 1024);
+}
+
+// re-runs the score pass on the lowered route
+int rescore(mtm_ctx* c, CallRoute& R) {
+    c->timing.ncc_launches = 0;
+    c->timing.sq_launches = 0;
+    MTMC(run_score_all(c, R));
+    HIPC(hipEventRecord(c->ev[1], c->stream));
+    return MTM_OK;
+}
+
+// float32 refinement, the ONE-PRODUCT screen listed more than the list holds: the same route with three piece products -
+// bounds 2^8 times tighter - before anything slower is tried (and the next calls start there)
+int to_three_products(mtm_ctx* c, CallRoute& R) {
+    R.bf16_np = 3;
+    back_off(c->np1_backoff, c->np1_backoff_len);
+    HIPC(hipMemsetAsync(c->cands.p, 0, 16, c->stream));
+    if (R.ext) HIPC(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * 2 * std::max(1, R.n), c->stream));
+    else if (R.hits_only) HIPC(hipMemsetAsync(c->chash.p, 0, ((size_t)R.hash_mask + 1) * sizeof(unsigned long long), c->stream));
+    R.cand_on = true;
+    MTMC(rescore(c, R));
+    R.cand_on = false;
+    return MTM_OK;
+}
+
+// float32 refinement, the kernel candidates (everything above the threshold) overflowed: the potential peaks of a map scan
+// instead - far fewer
+int to_map_scan(mtm_ctx* c, CallRoute& R) {
+    back_off(c->fuse_backoff, c->backoff_len);
+    R.hits_only = false;
+    R.pp_mode = R.refine_scan = true;
+    HIPC(hipMemsetAsync(c->cands.p, 0, 16, c->stream));
+    return rescore(c, R);
+}
+
+// float32: the float64 kernel decides, on maps in memory (the refined lists overflowed, or a bound is too wide for the map
+// scan's tolerances)
+int to_float64(mtm_ctx* c, CallRoute& R) {
+    if (R.raw_rig) back_off(c->fuse_backoff, c->backoff_len);   // raw sums have no map-scan route: the next calls start here
+    R.raw_rig = R.refine = R.refine_scan = R.pp_mode = false;
+    R.fused = R.hits_only = R.ext = false;
+    R.f32_exact = true;
+    return rescore(c, R);
+}
+
+// dense maps, the candidate list overflowed: the next calls on this context go straight to map mode (dense route, or the
+// full peak pass), this one takes the full peak pass.  (An overflow of the dense route's own list - row maxima only - is no
+// retry: the back-off it runs under keeps counting down.)
+int to_maps(mtm_ctx* c, CallRoute& R) {
+    R.fused = false;
+    back_off(c->fuse_backoff, c->backoff_len);
+    if (!R.hits_only) return MTM_OK;
+    R.hits_only = false;                // no maps in memory: compute them (this call pays twice - the overflowed launch left early)
+    return rescore(c, R);
+}
+
+// the per-segment lists of the flagged route are bounded in total: if growing them did not help, the full scan with its single
+// list takes over - the maps are complete unless the score pass left the unflagged segments out (then once more, in full:
+// the maps may be published)
+int leave_segments(mtm_ctx* c, CallRoute& R) {
+    R.sparse = false;
+    if (!R.seg_skip_used) return MTM_OK;
+    R.seg_skip_used = false;
+    return rescore(c, R);
+}
+
+int ladder_exhausted() {
+    set_error("mtm_find_matches: internal state (the overflow fallbacks ran out of passes)");
+    return MTM_E_STATE;
+}
+
 // Synchronising half: waits for the stream, verifies / extracts the peaks, delivers the hits.
-int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t* n_out) {
+int fm_end(mtm_ctx* c, CallRoute& R, mtm_hit* out, int64_t capacity, int64_t* n_out) {
     HIPC(hipSetDevice(c->device));
-    const int mode = S.mode, n = S.n;
-    const float thr = S.thr;
-    const bool mode_min = S.mode_min, fused = S.fused;
-    const int64_t cand_cap = S.cand_cap;
-    const unsigned hash_mask = S.hash_mask;
+    const int mode = R.mode, n = R.n;
+    const float thr = R.thr;
+    const bool mode_min = R.mode_min;
+    const int64_t cand_cap = R.cand_cap;
+    const unsigned hash_mask = R.hash_mask;
     std::vector<mtm_hit> hits;
 
     if (mode == MTM_PEAKS_GLOBAL) {
         std::vector<unsigned long long> best(2 * (size_t)std::max(1, n));
-        for (int attempt = 0; attempt < 3; ++attempt) {
-            if (!c->ext_now) {
+        // passes: the first, then one per step down - three products, the float64 kernel (which lists nothing)
+        bool done = false;
+        for (int pass = 0; pass < 3 && !done; ++pass) {
+            if (!R.ext) {
                 MTMC(c->counters.ensure(sizeof(unsigned long long) * 2 * std::max(1, n)));
                 HIPC(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * 2 * std::max(1, n), c->stream));
             }
-            if (n > 0 && !c->ext_now) {
+            if (n > 0 && !R.ext) {
                 const int nb = 256;
                 hipLaunchKernelGGL(extremum_kernel, dim3(nb, n), dim3(256), 0, c->stream, c->maps.as<float>(),
                                    c->td.as<TemplDev>(), nb, c->counters.as<unsigned long long>());
@@ -442,40 +501,22 @@ int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t
             HIPC(hipMemcpyAsync(best.data(), c->counters.p, sizeof(unsigned long long) * 2 * std::max(1, n),
                                 hipMemcpyDeviceToHost, c->stream));
             unsigned long long nlisted = 0;
-            const bool refined = c->refine_now && c->ext_now;
+            const bool refined = R.refine && R.ext;
             if (refined)
                 HIPC(hipMemcpyAsync(&nlisted, c->cands.p, sizeof(nlisted), hipMemcpyDeviceToHost, c->stream));
             HIPC(hipStreamSynchronize(c->stream));
             if (!refined || (int64_t)nlisted <= cand_cap) {
-                if (refined && c->bf16_np_now == 1) c->np1_backoff_len = 16;
-                break;
+                if (refined && R.bf16_np == 1) c->np1_backoff_len = 16;
+                done = true;
+            } else if (R.bf16_np == 1) {
+                // (the one-product screen's bounds let more outputs reach their template's best than the list holds)
+                MTMC(to_three_products(c, R));
+            } else {
+                // more outputs within the margin of their template's best than the list holds (near-flat maps)
+                MTMC(to_float64(c, R));
             }
-            if (c->bf16_np_now == 1) {
-                // the one-product screen's bounds let more outputs reach their template's best than the list holds: the
-                // same route with three piece products (and the next calls start there)
-                c->bf16_np_now = 3;
-                c->np1_backoff = c->np1_backoff_len;
-                c->np1_backoff_len = std::min(2 * c->np1_backoff_len, 1024);
-                c->timing.ncc_launches = 0;
-                c->timing.sq_launches = 0;
-                HIPC(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * 2 * std::max(1, n), c->stream));
-                HIPC(hipMemsetAsync(c->cands.p, 0, 16, c->stream));
-                MTMC(run_score_all(c));
-                HIPC(hipEventRecord(c->ev[1], c->stream));
-                continue;
-            }
-            // float32 refinement: more outputs within the margin of their template's best than the list holds (near-flat
-            // maps) - the float64 kernel decides, on maps in memory
-            c->refine_now = false;
-            c->f32_exact_now = true;
-            c->ext_now = false;
-            c->hits_only_now = false;
-            c->cand_on = false;
-            c->timing.ncc_launches = 0;
-            c->timing.sq_launches = 0;
-            MTMC(run_score_all(c));
-            HIPC(hipEventRecord(c->ev[1], c->stream));
         }
+        if (!done) return ladder_exhausted();
         for (int t = 0; t < n; ++t) {
             const unsigned long long key = best[2 * t + (mode_min ? 1 : 0)];
             const TemplDev& d = c->td_host[t];
@@ -503,25 +544,19 @@ int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t
         unsigned long long count = 0;
         std::vector<int> tflags((size_t)std::max(1, n), 0);
         std::vector<uint8_t> host_buf;
-        bool use_fused = fused;
         // Few candidates (the usual case): they come back in one copy and the 3x3 test runs on the host.
         // Every pixel above the threshold is in the list (in both modes), so a neighbour that is not
         // is <= threshold < candidate: the list alone decides.  Saves two kernels, three fills and a copy.
         bool verified_on_host = false;
-        bool pp_mode = S.pp_mode;
         const float thr_q = mode_min ? -thr : thr;      // a hit's quality (score, or -score for minima) exceeds this
-        if (use_fused && n2d > 0 && !pp_mode) {
-            // the candidate list is already on its way into the pinned landing buffer (fm_begin)
-            const size_t nfetch = std::min<size_t>(kHitPrefetch, (size_t)cand_cap);
-            if (!S.prefetched) {
-                set_error("mtm_find_matches: internal state (candidate fetch not queued)");
-                return MTM_E_INVALID;
-            }
+        if (R.fused && n2d > 0 && !R.pp_mode) {
+            // the candidate list is already on its way into the pinned landing buffer (fm_begin: R.prefetched)
+            const size_t nfetch = R.cand_pin_n;
             HIPC(hipStreamSynchronize(c->stream));
             host_trace(c, 10);
             uint8_t* land = static_cast<uint8_t*>(c->pinned);
             unsigned long long ncand = 0;
-            if (S.pin_direct) {
+            if (R.pin_direct) {
                 // the window's slots fill from 0 upwards (every reserved slot below the capacity is written before the
                 // launch ends): the count is the first slot that still says "no record"
                 const mtm_hit* w = reinterpret_cast<const mtm_hit*>(land + 16);
@@ -537,7 +572,7 @@ int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t
             if (ncand <= nfetch) {
                 // everything needed is on the host: clear the counter for the next call while this one finishes
                 // (unless this context's calls clear it in their own first kernel: banded uint8 calls)
-                if (!S.banded_u8 && hipMemsetAsync(c->cands.p, 0, 16, c->stream) == hipSuccess)
+                if (!R.banded_u8 && hipMemsetAsync(c->cands.p, 0, 16, c->stream) == hipSuccess)
                     c->cands_zeroed = c->cands.p;
                 const mtm_hit* cd = reinterpret_cast<const mtm_hit*>(land + 16);
                 // open-addressing table over the candidates (key -> index), kept in the context between calls
@@ -589,14 +624,20 @@ int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t
                 }
                 count = hits.size();
                 verified_on_host = true;
-                if (c->refine_now && c->bf16_np_now == 1) c->np1_backoff_len = 16;
+                if (R.refine && R.bf16_np == 1) c->np1_backoff_len = 16;
             }
         }
-        if (!verified_on_host && c->hits_only_now)
+        if (!verified_on_host && R.hits_only)
             HIPC(hipMemsetAsync(c->chash.p, 0, ((size_t)hash_mask + 1) * sizeof(unsigned long long), c->stream));
-        if (pp_mode) use_fused = true;          // the potential peaks are in the candidate buffer, their neighbourhoods in the maps
+        if (R.pp_mode) R.fused = true;          // the potential peaks are in the candidate buffer, their neighbourhoods in the maps
         DeviceNms dnms;                 // (the device's share of a suppression request, queued behind the flagged-segment peak pass)
-        for (int attempt = 0; attempt < 5 && n2d > 0 && !verified_on_host; ++attempt) {
+        // Passes: the first, then one per step down the ladder; no step is taken twice in a call.  Float32 refinement: three
+        // products, map scan, the float64 kernel or a grown list for the candidates (either ends them), a grown list for the
+        // full pass (it then holds every peak of the same maps) - 4 steps.  Integer candidates: the maps or a grown list, then
+        // the full pass's list - 2.  Flagged segments: their lists grown, left, the full pass's list grown - 3.  Hence at most
+        // 5 passes; a ladder that runs out is an internal error, never an empty list.
+        bool done = n2d == 0 || verified_on_host;
+        for (int attempt = 0; attempt < 5 && !done; ++attempt) {
             dnms.queued = false;
             MTMC(c->hits.ensure(hdr_bytes + sizeof(mtm_hit) * (size_t)c->hit_cap));
             uint8_t* dbase = c->hits.as<uint8_t>();
@@ -604,13 +645,13 @@ int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t
             unsigned long long* counter = reinterpret_cast<unsigned long long*>(dbase);
             int* flags = reinterpret_cast<int*>(counter + 3);
             mtm_hit* dhits = reinterpret_cast<mtm_hit*>(dbase + hdr_bytes);
-            if (use_fused) {
+            if (R.fused) {
                 // counter[1] <- candidate count (for the overflow check on the host)
                 HIPC(hipMemcpyAsync(counter + 1, c->cands.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice,
                                     c->stream));
                 const unsigned blocks = std::min((unsigned)((c->hit_cap + 255) / 256), 4096u);
                 const mtm_hit* dcands = reinterpret_cast<const mtm_hit*>(c->cands.as<uint8_t>() + 16);
-                if (c->hits_only_now) {
+                if (R.hits_only) {
                     unsigned long long* keys = c->chash.as<unsigned long long>();
                     int* vals = reinterpret_cast<int*>(keys + (size_t)hash_mask + 1);
                     hipLaunchKernelGGL(cand_hash_insert_kernel, dim3(blocks), dim3(256), 0, c->stream, dcands,
@@ -633,7 +674,7 @@ int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t
                     max_ow = std::max(max_ow, c->td_host[t].ow);
                 }
                 const dim3 grd((max_ow + kPkCols - 1) / kPkCols, (max_oh + 4 * kPkRows - 1) / (4 * kPkRows), n2d);
-                if (c->sparse_now) {
+                if (R.sparse) {
                     const dim3 grd((max_ow + kPkCols - 1) / kPkCols, (max_oh + 4 * kPkSparseRows - 1) / (4 * kPkSparseRows), n2d);
                     // a list per (template, strip column) (at most 64 MB of them) + their counters, then one list for the host
                     const unsigned long long n_lists = (unsigned long long)n2d * grd.x;
@@ -647,13 +688,13 @@ int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t
                     hipLaunchKernelGGL(peaks_sparse_kernel, grd, dim3(256), 0, c->stream, c->maps.as<float>(),
                                        c->td.as<TemplDev>(), c->tlist.as<int>() + c->list2d_off, mode_min ? 1 : 0, thr,
                                        c->opt_border, hits_t, cap_t, counts_t, flags, c->seg_flags.as<uint8_t>(),
-                                       c->flag_tstride, c->flag_rstride, c->seg_skip_used ? 1 : 0);
+                                       R.flag_tstride, R.flag_rstride, R.seg_skip_used ? 1 : 0);
                     hipLaunchKernelGGL(compact_hits_kernel, dim3((unsigned)n_lists), dim3(256), 0, c->stream, hits_t, cap_t, counts_t,
                                        (int)n_lists, dhits, (unsigned long long)c->hit_cap, counter);
                     // a suppression request: its device share follows at once (it reads the list's length on the device)
                     dnms = DeviceNms{};
-                    if (c->nms_req.on && c->nms_req.max_overlap >= 0.0)
-                        MTMC(queue_device_nms(c, dhits, counter, mode_min, &dnms));
+                    if (R.nms.on && R.nms.max_overlap >= 0.0)
+                        MTMC(queue_device_nms(c, R.nms, dhits, counter, mode_min, &dnms));
                 } else
                     hipLaunchKernelGGL(peaks_kernel, grd, dim3(256), 0, c->stream, c->maps.as<float>(),
                                        c->td.as<TemplDev>(), c->tlist.as<int>() + c->list2d_off, mode_min ? 1 : 0, thr,
@@ -670,99 +711,34 @@ int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t
             std::memcpy(&ncand, host_buf.data() + sizeof(count), sizeof(ncand));
             std::memcpy(tflags.data(), host_buf.data() + 3 * sizeof(count), sizeof(int) * n);
             unsigned int rig_wide = 0;
-            if (use_fused) std::memcpy(&rig_wide, host_buf.data() + 2 * sizeof(count), sizeof(rig_wide));
-            if (pp_mode && c->refine_now && rig_wide != 0) {
-                // float32 map mode: some output that could pass the threshold has an error bound beyond what the scan's
-                // tolerances cover (a low-contrast window beside a brightness step) - the float64 kernel decides
-                c->cand_on = false;
-                c->hits_only_now = false;
-                c->timing.ncc_launches = 0;
-                c->timing.sq_launches = 0;
-                pp_mode = false;
-                use_fused = false;
-                c->refine_now = c->refine_scan_now = false;
-                c->f32_exact_now = true;
-                MTMC(run_score_all(c));
-                HIPC(hipEventRecord(c->ev[1], c->stream));
+            if (R.fused) std::memcpy(&rig_wide, host_buf.data() + 2 * sizeof(count), sizeof(rig_wide));
+            // float32 map mode: some output that could pass the threshold has an error bound beyond what the scan's
+            // tolerances cover (a low-contrast window beside a brightness step)
+            if (R.pp_mode && rig_wide != 0) {
+                MTMC(to_float64(c, R));
                 continue;
             }
-            if (use_fused && !pp_mode && (int64_t)ncand > cand_cap && c->refine_now && c->bf16_np_now == 1) {
-                // float32 refinement, the ONE-PRODUCT screen listed more than the list holds: the same route with three piece
-                // products - bounds 2^8 times tighter - before anything slower is tried (and the next calls start there)
-                c->bf16_np_now = 3;
-                c->np1_backoff = c->np1_backoff_len;
-                c->np1_backoff_len = std::min(2 * c->np1_backoff_len, 1024);
-                c->timing.ncc_launches = 0;
-                c->timing.sq_launches = 0;
-                HIPC(hipMemsetAsync(c->cands.p, 0, 16, c->stream));
-                if (c->hits_only_now)
-                    HIPC(hipMemsetAsync(c->chash.p, 0, ((size_t)hash_mask + 1) * sizeof(unsigned long long), c->stream));
-                c->cand_on = true;
-                const int rc_np = run_score_all(c);
-                c->cand_on = false;
-                MTMC(rc_np);
-                HIPC(hipEventRecord(c->ev[1], c->stream));
+            if (R.fused && (int64_t)ncand > cand_cap) {
+                if (!R.refine) MTMC(to_maps(c, R));
+                else if (!R.pp_mode && R.bf16_np == 1) MTMC(to_three_products(c, R));
+                else if (!R.pp_mode && !R.raw_rig) MTMC(to_map_scan(c, R));
+                else MTMC(to_float64(c, R));        // (the map scan's potential peaks overflowed too: plateau-rich maps)
                 continue;
             }
-            if (use_fused && (int64_t)ncand > cand_cap && c->refine_now) {
-                // float32 refinement, list overflowed.  Kernel candidates (everything above the threshold): take the
-                // potential peaks of a map scan instead - far fewer.  Those too (plateau-rich maps): the float64 kernel.
-                c->cand_on = false;
-                c->hits_only_now = false;
-                c->timing.ncc_launches = 0;
-            c->timing.sq_launches = 0;
-                if (!pp_mode && !c->raw_rig_now) {
-                    c->fuse_backoff = c->backoff_len;
-                    c->backoff_len = std::min(2 * c->backoff_len, 1024);
-                    pp_mode = true;
-                    c->refine_scan_now = true;
-                    HIPC(hipMemsetAsync(c->cands.p, 0, 16, c->stream));
-                } else {
-                    if (c->raw_rig_now) {           // raw sums have no map-scan route: the next calls start on the float64 kernel
-                        c->fuse_backoff = c->backoff_len;
-                        c->backoff_len = std::min(2 * c->backoff_len, 1024);
-                        c->raw_rig_now = false;
-                    }
-                    pp_mode = false;
-                    use_fused = false;
-                    c->refine_now = c->refine_scan_now = false;
-                    c->f32_exact_now = true;
-                }
-                MTMC(run_score_all(c));
-                HIPC(hipEventRecord(c->ev[1], c->stream));
-                continue;
-            }
-            if (use_fused && (int64_t)ncand > cand_cap) {
-                use_fused = false;                  // dense maps: candidate list overflowed
-                // the next calls on this context go straight to map mode (dense route, or the full peak pass); the period
-                // doubles while the retries keep overflowing.  (An overflow of the dense route's own list - row maxima
-                // only - is no retry: the back-off it runs under keeps counting down, this call takes the full peak pass.)
-                c->fuse_backoff = c->backoff_len;
-                c->backoff_len = std::min(2 * c->backoff_len, 1024);
-                if (c->hits_only_now) {
-                    // no maps in memory: compute them (this call pays twice - the overflowed launch left early)
-                    c->hits_only_now = false;
-                    c->cand_on = false;
-                    c->timing.ncc_launches = 0;
-            c->timing.sq_launches = 0;
-                    MTMC(run_score_all(c));
-                    HIPC(hipEventRecord(c->ev[1], c->stream));
-                }
-                continue;
-            }
-            if (use_fused && !pp_mode) c->backoff_len = 16;     // the candidates fitted
-            if (use_fused && !pp_mode && c->refine_now && c->bf16_np_now == 1) c->np1_backoff_len = 16;
+            if (R.fused && !R.pp_mode) c->backoff_len = 16;     // the candidates fitted
+            if (R.fused && !R.pp_mode && R.refine && R.bf16_np == 1) c->np1_backoff_len = 16;
             if ((int64_t)count <= c->hit_cap) {
                 // thousands of peaks and a suppression request: decide on the device, fetch the kept ones
-                if (dnms.queued && c->sparse_now && !use_fused && (long long)count >= c->nms_device_min && count <= dnms.n_max) {
+                if (dnms.queued && R.sparse && !R.fused && (long long)count >= c->nms_device_min && count <= dnms.n_max) {
                     bool trivial = false;       // (a map every pixel of which equals its local maximum loses its peaks below)
                     for (int t : c->list2d) {
                         const unsigned f = (unsigned)tflags[(size_t)t];
                         trivial = trivial || ((f & 0xFFu) == 0 && !((f & 0xFF00u) != 0 && (f & 0xFF0000u) != 0));
                     }
                     if (!trivial) {
-                        MTMC(fetch_device_nms(c, dnms, count, hits, &c->nms_sure));
-                        c->nms_raw_count = (long long)count;
+                        MTMC(fetch_device_nms(c, dnms, count, hits, &R.nms_sure));
+                        R.nms_raw_count = (long long)count;
+                        done = true;
                         break;
                     }
                 }
@@ -774,23 +750,14 @@ int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t
                                         hipMemcpyDeviceToHost, c->stream));
                     HIPC(hipStreamSynchronize(c->stream));
                 }
+                done = true;
                 break;
             }
             c->hit_cap = (int64_t)count + 1024;     // grow and rerun the compaction pass
-            use_fused = false;
-            // (the per-segment lists of the flagged route are bounded in total: if growing did not help, the full scan with
-            // its single list takes over - the maps are complete)
-            if (c->sparse_now && attempt >= 1) {
-                c->sparse_now = false;
-                if (c->seg_skip_used) {         // (round 5: ... unless the score pass left the unflagged segments out - once more, in full)
-                    c->timing.ncc_launches = 0;
-                    c->timing.sq_launches = 0;
-                    c->seg_skip_used = false;   // (the re-run writes every output: the maps are complete and may be published)
-                    MTMC(run_score_all(c));
-                    HIPC(hipEventRecord(c->ev[1], c->stream));
-                }
-            }
+            R.fused = false;
+            if (R.sparse && attempt >= 1) MTMC(leave_segments(c, R));
         }
+        if (!done) return ladder_exhausted();
         if (n2d == 0) {
             HIPC(hipEventRecord(c->ev[2], c->stream));
             HIPC(hipStreamSynchronize(c->stream));
@@ -803,7 +770,7 @@ int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t
                                       [&](const mtm_hit& h) {
                                           const TemplDev& d = c->td_host[h.templ_idx];
                                           if (d.oh <= 1 || d.ow <= 1) return true;   // 1-D / 1x1 maps: host path below
-                                          if (use_fused) return (long long)tflags[h.templ_idx] == (long long)d.oh * d.ow;
+                                          if (R.fused) return (long long)tflags[h.templ_idx] == (long long)d.oh * d.ow;
                                           // (bytes 1 and 2: peaks_sparse_kernel - segments above and below the threshold exist)
                                           const unsigned f = (unsigned)tflags[h.templ_idx];
                                           return (f & 0xFFu) == 0 && !((f & 0xFF00u) != 0 && (f & 0xFF0000u) != 0);
@@ -841,20 +808,20 @@ int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t
         // deterministic order: template, then descending quality, then row-major position
         host_trace(c, 11);
         // (the device may have pruned the list already - queue_device_nms / fetch_device_nms -: the count of peaks is the one before that)
-        const int64_t n_raw = c->nms_raw_count >= 0 ? (int64_t)c->nms_raw_count : (int64_t)hits.size();
-        if (c->nms_req.on && n_raw > 1) {               // MTM.NMS (a list of one hit is returned as it is: MTM/NMS.py:53-55)
-            const float thr_s = (float)(mode_min ? (1.0 - c->nms_req.score_threshold) : c->nms_req.score_threshold);
+        const int64_t n_raw = R.nms_raw_count >= 0 ? (int64_t)R.nms_raw_count : (int64_t)hits.size();
+        if (R.nms.on && n_raw > 1) {                    // MTM.NMS (a list of one hit is returned as it is: MTM/NMS.py:53-55)
+            const float thr_s = (float)(mode_min ? (1.0 - R.nms.score_threshold) : R.nms.score_threshold);
             std::vector<int32_t> keep;
-            nms_select(hits.data(), (int64_t)hits.size(), mode_min ? 1 : 0, thr_s, (float)c->nms_req.max_overlap, keep,
-                       c->nms_raw_count >= 0 ? c->nms_sure : 0);
+            nms_select(hits.data(), (int64_t)hits.size(), mode_min ? 1 : 0, thr_s, (float)R.nms.max_overlap, keep,
+                       R.nms_raw_count >= 0 ? R.nms_sure : 0);
             std::vector<mtm_hit> kept(keep.size());
             for (size_t i = 0; i < keep.size(); ++i) kept[i] = hits[(size_t)keep[i]];
             hits.swap(kept);
         } else {
             sort_hits(hits, mode_min);
         }
-        if (c->nms_req.on && c->nms_req.n_object >= 0 && (long long)hits.size() > c->nms_req.n_object)
-            hits.resize((size_t)c->nms_req.n_object);          // MTM/NMS.py:81-82
+        if (R.nms.on && R.nms.n_object >= 0 && (long long)hits.size() > R.nms.n_object)
+            hits.resize((size_t)R.nms.n_object);                // MTM/NMS.py:81-82
         c->timing.n_hits = n_raw;
         host_trace(c, 12);
     }
@@ -863,17 +830,11 @@ int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t
     HIPC(hipEventElapsedTime(&c->timing.peaks_ms, c->ev[1], c->ev[2]));
     HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[2]));
     MTMC(collect_ncc_time(c));
-    if (mode != MTM_PEAKS_LOCAL || !c->nms_req.on) c->timing.n_hits = (int64_t)hits.size();
-    c->nms_raw_count = -1;
-    c->nms_sure = 0;
-    c->timing.hits_only = c->sparse_now ? 2 : c->hits_only_now ? 1 : 0;
-    c->timing.f32_route = c->mbf_used ? 4 : c->f32_exact_now ? 3 : !c->refine_now ? 0 : (c->refine_scan_now ? 2 : 1);
-    c->maps_valid = !c->hits_only_now && !c->ext_now && !c->seg_skip_used && !c->mbf_used;
-    c->mbf_thr_on = false;
-    c->refine_now = c->refine_scan_now = c->f32_exact_now = false;      // states of this call only
-    c->sparse_now = false;
-    c->raw_rig_now = false;
-    c->zero_pending = false;
+    if (mode != MTM_PEAKS_LOCAL || !R.nms.on) c->timing.n_hits = (int64_t)hits.size();
+    // what the call's route came to
+    c->timing.hits_only = R.sparse ? 2 : R.hits_only ? 1 : 0;
+    c->timing.f32_route = R.mbf_used ? 4 : R.f32_exact ? 3 : !R.refine ? 0 : (R.refine_scan ? 2 : 1);
+    c->maps_valid = !R.hits_only && !R.ext && !R.seg_skip_used && !R.mbf_used;
     *n_out = (int64_t)hits.size();
     c->last_hits.swap(hits);
     if ((int64_t)c->last_hits.size() > capacity) {
@@ -885,7 +846,7 @@ int fm_end(mtm_ctx* c, const FmState& S, mtm_hit* out, int64_t capacity, int64_t
 }
 
 int find_matches_impl(mtm_ctx* c, int mode, double score_threshold, mtm_hit* out, int64_t capacity,
-                      int64_t* n_out, NextImage* next, const ImageArgs* up) {
+                      int64_t* n_out, NextImage* next, const ImageArgs* up, const NmsRequest* nms) {
     if (!c || !n_out || capacity < 0 || (capacity > 0 && !out) ||
         (mode != MTM_PEAKS_LOCAL && mode != MTM_PEAKS_GLOBAL)) {
         set_error("mtm_find_matches: bad arguments");
@@ -895,9 +856,10 @@ int find_matches_impl(mtm_ctx* c, int mode, double score_threshold, mtm_hit* out
         set_error("mtm_find_matches: a mtm_find_matches_async call is in flight (collect it with mtm_find_matches_wait)");
         return MTM_E_INVALID;
     }
-    FmState S;
-    MTMC(fm_begin(c, mode, score_threshold, next, S, up));
-    return fm_end(c, S, out, capacity, n_out);
+    CallRoute R;
+    MTMC(fm_begin(c, mode, score_threshold, next, R, up));
+    if (nms) R.nms = *nms;
+    return fm_end(c, R, out, capacity, n_out);
 }
 
 }  // namespace
@@ -928,13 +890,13 @@ int mtm_score_map(mtm_ctx* c, int templ_idx, float* out, int64_t out_row_stride_
     c->timing = mtm_timing{};
     StatPlanes st;
     MTMC(ensure_maps(c));
-    // float32 classes: maps of the raw-sum methods come from the float64 kernel (see fm_begin)
-    c->f32_exact_now = resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32 &&
-                       (c->method == MTM_TM_SQDIFF || c->method == MTM_TM_CCORR || c->method == MTM_TM_CCOEFF);
-    const int rc_st = launch_stats(c, sc, &st);
-    const int rc_nc = rc_st == MTM_OK ? launch_ncc(c, sc, sc.tlist_off + pos, 1, st, pos) : rc_st;
-    c->f32_exact_now = false;
-    MTMC(rc_nc);
+    // a map-mode route: no candidates, no extremum; float32 classes take the maps of the raw-sum methods from the float64
+    // kernel (plan_call)
+    CallRoute R;
+    R.f32_exact = resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32 &&
+                  (c->method == MTM_TM_SQDIFF || c->method == MTM_TM_CCORR || c->method == MTM_TM_CCOEFF);
+    MTMC(launch_stats(c, R, sc, &st));
+    MTMC(launch_ncc(c, R, sc, sc.tlist_off + pos, 1, st, pos));
     HIPC(hipMemcpy2DAsync(out, (size_t)out_row_stride_bytes, c->maps.as<float>() + d.map_off,
                           sizeof(float) * d.map_pitch, sizeof(float) * d.ow, d.oh, hipMemcpyDeviceToHost,
                           c->stream));
@@ -972,13 +934,8 @@ int mtm_find_matches_image_nms(mtm_ctx* c, const void* px, int rows, int cols, i
     host_trace(c, 0);
     MTMC(check_image_args(px, rows, cols, chans, dtype, row_stride_bytes, "mtm_find_matches_image_nms"));
     const ImageArgs up{px, rows, cols, chans, dtype, row_stride_bytes};
-    c->nms_req.on = true;
-    c->nms_req.score_threshold = score_threshold;
-    c->nms_req.max_overlap = max_overlap;
-    c->nms_req.n_object = n_object;
-    const int rc = find_matches_impl(c, MTM_PEAKS_LOCAL, score_threshold, out, capacity, n_out, nullptr, &up);
-    c->nms_req.on = false;
-    c->nms_raw_count = -1;
+    const NmsRequest nms{true, score_threshold, max_overlap, n_object};
+    const int rc = find_matches_impl(c, MTM_PEAKS_LOCAL, score_threshold, out, capacity, n_out, nullptr, &up, &nms);
     host_trace(c, 15);
     return rc;
 }

@@ -138,21 +138,60 @@ struct SizeClass {
 
 }  // namespace mtmi
 
-// What mtm_find_matches knows after its asynchronous half (everything up to and including the kernels and the
-// first fetch are queued on the stream) and needs in its synchronising half.  mtm_find_matches_async /
-// mtm_find_matches_wait keep one of these in the context between the two calls.
+// The route of one mtm_find_matches call: what plan_call decides from the context, the mode and the threshold, what the
+// launches record for the call, and where fm_end's overflow transitions take it.  It lives as long as the call
+// (mtm_find_matches_async / mtm_find_matches_wait keep it in mtm_ctx::fm in between); what lasts across calls - the
+// back-off counters, hit_cap, cands_zeroed - stays on the context.
 namespace mtmi {
-struct FmState {
-    int mode = 0;
-    float thr = 0.0f;
-    bool mode_min = false, fused = false, prefetched = false;
-    bool banded_u8 = false;     // the call's image came in row bands (uint8): the next such call clears the candidate header itself
-    bool pin_direct = false;    // the score kernel wrote the head of the candidate list into the pinned window itself (no fetch)
-    bool pp_mode = false;       // float32 refinement by map scan: the candidate buffer holds potential peaks whose
-                                // neighbourhoods in the maps are exact - decisions by verify_peaks_kernel, never from the list alone
+// mtm_find_matches_image_nms: MTM.matchTemplates' non-maxima suppression as part of the call (the host's nms_boxes on
+// the fetched list).  Thousands of peaks on the device (the flagged-segment route of dense images) are pruned there
+// first (mtm_k_nms.hip.h; MTM_NMS_DEVICE=0: never): what a neighbourhood's best hit suppresses never crosses PCIe.
+struct NmsRequest {
+    bool on = false;
+    double score_threshold = 0.0, max_overlap = 0.0;
+    long long n_object = -1;
+};
+struct CallRoute {
+    int mode = MTM_PEAKS_LOCAL;
     int n = 0;
+    float thr = 0.0f;
+    bool mode_min = false;
+    // candidate emission of the launches being queued: threshold (quality: -score for minima) and direction
+    bool cand_on = false, cand_min = false;
+    float cand_thr = 0.0f;
+    bool fused = false;         // local extrema from the kernels' candidate list (verify_peaks / the host's 3x3 test)
+    bool hits_only = false;     // ... and no maps in memory (candidates + hash verify)
+    bool ext = false;           // global extrema come out of the MFMA epilogue (no maps, no extremum_kernel)
+    bool sparse = false;        // segment flags: maps in memory, peaks_sparse_kernel over the flagged row segments
+    int flag_tstride = 0, flag_rstride = 0;     // ... the flags' layout (seg_flags[t * flag_tstride + row * flag_rstride + segment])
+    bool seg_skip_used = false; // some map holds placeholders for outputs that cannot pass (the maps are not published)
+    // float32 refinement (mtm_refine.hip.h)
+    bool refine = false;        // bf16 classes are refined
+    bool refine_scan = false;   // ... by map scan + ring re-scoring (maps in memory) instead of kernel candidates
+    bool pp_mode = false;       // the candidate buffer holds the map scan's potential peaks, whose neighbourhoods in the maps
+                                // are exact - decisions by verify_peaks_kernel, never from the list alone
+    bool f32_exact = false;     // bf16 classes run the float64 kernel
+    bool raw_rig = false;       // a raw-sum method with a threshold, listed by the bound of the sum (kernel candidates only)
+    float rig_thr = 0.0f;       // the exact quality threshold (the lists' own cand_thr carries a margin in map mode)
+    float scan_thr = 0.0f;      // map mode: the threshold of refine_scan_kernel (rig_thr lowered by rig_cap)
+    float rig_cap = 0.0f;       // map mode: the bound up to which the scan's tolerances hold (else: float64 kernel)
+    int bf16_np = 3;            // piece products of the hits-only screens (1: the one-product screen)
+    // masked float32 classes screened on the bf16 matrix cores (launch_masked_bf16)
+    bool mbf_thr_on = false;    // local extrema against mbf_thr, or (mbf_global) the global extremum
+    bool mbf_global = false;
+    float mbf_thr = 0.0f;
+    bool mbf_used = false;      // some class's maps hold "below the threshold" placeholders
+    // the candidate list's landing buffer: the score kernel writes its head there itself (cand_pin: the first pass only)
+    bool cand_pin = false, pin_direct = false, prefetched = false;
+    size_t cand_pin_n = 0;
+    bool banded_u8 = false;     // the image came in row bands (uint8): such calls clear the candidate header themselves
+    bool zero_pending = false;  // ... and this one has not done so yet
+    bool single_band = false;   // the banded upload is ONE band (banded_ok: a call too small for two score launches)
     int64_t cand_cap = 0;
     unsigned hash_mask = 0;
+    NmsRequest nms;
+    long long nms_raw_count = -1;   // >= 0: the device pruned the peak list; the count before that
+    long long nms_sure = 0;         // ... and its first nms_sure hits are kept for certain (the neighbourhoods' best)
 };
 }  // namespace mtmi
 
@@ -160,7 +199,7 @@ struct mtm_ctx {
     using DevBuf = mtmi::DevBuf;
     using HostTempl = mtmi::HostTempl;
     using SizeClass = mtmi::SizeClass;
-    using FmState = mtmi::FmState;
+    using CallRoute = mtmi::CallRoute;
     using TemplDev = mtm::TemplDev;
     using UnitSrc = mtm::UnitSrc;
     int device = 0;
@@ -170,10 +209,6 @@ struct mtm_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> sq_ev;       // event pairs of the sum I^2 M passes (timing.masked_stat_ms)
     int cand_pinned = 1;        // MTM_CAND_PINNED: the score kernel writes the first records of its candidate list into the pinned
                                 // landing buffer itself (MfmaParams::cand_pin) - no fetch kernel behind the score launch (0: round 4)
-    bool cand_pin_now = false;  // ... in the launches being queued
-    size_t cand_pin_n = 0;
-    bool single_band_now = false;
-    bool zero_pending = false;  // ... and has not done so yet
     int fuse_layout = 1;        // MTM_FUSE_LAYOUT: banded uploads convert a band's rows inside its statistics launch (0: planarize kernel)
     int lay_r0 = 0, lay_r1 = 0; // ... the rows the statistics launch being queued converts (run_score_banded -> launch_stats)
     int masksq_fused = 1;       // MTM_MASKSQ_FUSED: sum I^2 M of a masked class as ONE launch over both byte planes of I^2 that
@@ -195,25 +230,13 @@ struct mtm_ctx {
     DevBuf sq_planes;           // two planes: [high byte of I^2 ^ 0x80][low byte ^ 0x80] of the current uint8 image
     bool sq_valid = false;
     hipStream_t copy_stream = nullptr;
-    // mtm_find_matches_image_nms: MTM.matchTemplates' non-maxima suppression as part of the call (the host's nms_boxes on
-    // the fetched list).  Thousands of peaks on the device (the flagged-segment route of dense images) are pruned there
-    // first (mtm_k_nms.hip.h; MTM_NMS_DEVICE=0: never): what a neighbourhood's best hit suppresses never crosses PCIe.
-    struct NmsRequest {
-        bool on = false;
-        double score_threshold = 0.0, max_overlap = 0.0;
-        long long n_object = -1;
-    } nms_req;
-    long long nms_raw_count = -1;           // >= 0: the device pruned this call's peak list; the count before that
-    long long nms_sure = 0;                 // ... and its first nms_sure hits are kept for certain (the neighbourhoods' best)
-    long long nms_device_min = 4096;        // fewer peaks than this: the host is as fast
+    long long nms_device_min = 4096;        // CallRoute::nms: fewer peaks than this are pruned on the host (as fast)
     DevBuf nms_buf;
     // segment flags (MTM_SPARSE_MAPS, default 1): the route of a call on dense maps (candidate list overflowed recently)
     // when every class runs the lean MFMA epilogue - maps in memory, one flag per row segment that holds something above the
     // threshold, peaks_sparse_kernel over the flagged segments instead of the full scan (MfmaParams::seg_flags)
     int sparse_maps = 1;
-    bool sparse_now = false;
     DevBuf seg_flags, hits_t;               // (hits_t: per-template peak lists of peaks_sparse_kernel + their counters)
-    int flag_tstride = 0, flag_rstride = 0;
     hipEvent_t next_ready = nullptr;
     // mtm_find_matches_image: the image arrives in row bands on copy_stream (copy, layout conversion, window
     // statistics of the rows that became computable); the score kernel of a band waits for its event
@@ -228,18 +251,8 @@ struct mtm_ctx {
     // Round 6: the hits-only refined routes screen with ONE piece product first (ncc_bf16_kernel<MB, 1>, a third of the
     // matrix-core work, bound 2^-7 instead of 2^-15 of the norms' product); a list that overflows repeats the launch with
     // three products, and the next np1_backoff calls start there
-    int bf16_np_now = 3;                    // this call's piece products of the hits-only screens (fm_begin)
     int np1_backoff = 0, np1_backoff_len = 16;
     int seg_skip = 1;                       // MTM_SEG_SKIP: dense route - outputs that cannot pass the threshold are not finished (MfmaParams::seg_skip)
-    bool seg_skip_used = false;             // this call: some map holds such placeholders (the maps are not published)
-    bool raw_rig_now = false;               // this call: a raw-sum method with a threshold, listed by the bound of the sum (route 1 only)
-    float rig_thr = 0.0f;                   // the exact quality threshold of the call (the lists' own cand_thr carries a margin in map mode)
-    float scan_thr = 0.0f;                  // map mode: the threshold of refine_scan_kernel (rig_thr lowered by rig_cap)
-    float rig_cap = 0.0f;                   // map mode: the bound up to which the scan's tolerances hold (else: float64 kernel)
-    // float32 refinement (mtm_refine.hip.h), state of the current mtm_find_matches
-    bool refine_now = false;                // bf16 classes of this call are refined
-    bool refine_scan_now = false;           // ... by map scan + ring re-scoring (maps in memory) instead of kernel candidates
-    bool f32_exact_now = false;             // bf16 classes run the float64 kernel in this call (refinement lists overflowed)
     int templ_on_device = 1;                // MTM_TEMPL_ON_DEVICE: uint8 template sets live on the device (views + device packing); 0 = packed on
                                             // the host (the independent restatement test_template_sets_on_device compares with)
     int mfma_r2 = 1;                        // MTM_MFMA_R2: 1 = two-row variant of the MFMA kernel where it applies, 0 = off
@@ -297,10 +310,6 @@ struct mtm_ctx {
     // masked float32 classes screened on the bf16 matrix cores: the U / V template tables, the approximate c1 / c2 maps,
     // J = I^2, the window sums of I and J, the launches' tile constants, the list of outputs to re-score exactly
     DevBuf td_u, td_v, mbf_maps, f32_sq, mbf_stats, mbf_mu, mbf_list, mbf_best;
-    bool mbf_thr_on = false;                        // this call: local extrema against mbf_thr, or (mbf_global) N_object == 1 (find_matches_impl)
-    bool mbf_global = false;
-    float mbf_thr = 0.0f;
-    bool mbf_used = false;                          // this call: some class's maps hold "below the threshold" placeholders
     bool f32_sq_valid = false;                      // f32_sq holds the square of the current float32 plane
     DevBuf tsrc, usrc_dev, tsums_dev, tgather;      // template source arena, unit views, source sums, gather scratch
     DevBuf td, tlist, weights, packs, apacks, maps, hs1, hs2, stats, hits, counters, sched, cands, mask_td, chash, raw16, stats_hi, tsum, stats_rsq, stats_blk;
@@ -322,21 +331,15 @@ struct mtm_ctx {
     double band_min_fill = 1.0;   // MTM_BAND_MIN_FILL: a band is only worth a launch of its own if its work items fill the resident
                                // work-group slots this many times (0 lets the band tests use small images)
     int n_cus = 0;
-    // candidate emission of the current launch sequence (set by mtm_find_matches)
-    bool cand_on = false;
-    bool cand_min = false;
-    float cand_thr = 0.f;
     int hits_only = 1;         // MTM_OPT_HITS_ONLY: mtm_find_matches does not materialise the score maps when
                                // every class runs the single-channel MFMA kernel (candidates + hash verify)
     int backoff_len = 16;      // length of the next back-off period: doubles with every overflow in a row (<= 1024), reset by a
                                // call whose candidates fitted
     int fuse_backoff = 0;      // calls left without fused candidates (map mode + full peak pass: maps known to be dense)
-    bool hits_only_now = false;
     bool maps_valid = false;   // the map arena holds every score map of the last mtm_find_matches (mtm_last_score_map)
-    FmState fm;                         // mtm_find_matches_async -> mtm_find_matches_wait
+    CallRoute fm;                       // the route of the mtm_find_matches_async call in flight (mtm_find_matches_wait)
     bool fm_in_flight = false;
     const void* cands_zeroed = nullptr;   // candidate buffer whose counter was cleared after the previous call's fetch
-    bool ext_now = false;      // this call: global extrema come out of the MFMA epilogue (no maps, no extremum_kernel)
     int exact_div = 1;         // MTM_OPT_EXACT_DIV: 1 (default since round 5) = IEEE division in the MFMA epilogue, bit-identical to the
                                // oracle; 0 = correctly rounded reciprocals (<= 1 ulp(float32) on ~1e-8 of the outputs); 2 = strict: also
                                // the fused extremum of masked classes (reciprocal-only kernels) goes through maps + extremum_kernel
@@ -484,13 +487,13 @@ int place_templates(mtm_ctx* c);
 // ---- mtm_launch.hip
 int resolved_kernel(const mtm_ctx* c, const SizeClass& sc);
 bool dot_variant_ok(int64_t v);
-int launch_stats(mtm_ctx* c, const SizeClass& sc, StatPlanes* out, int sb0 = 0, int sb1 = -1);
-int launch_ncc(mtm_ctx* c, const SizeClass& sc, int list_off, int n_list, const StatPlanes& st, int only_li = -1,
+int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out, int sb0 = 0, int sb1 = -1);
+int launch_ncc(mtm_ctx* c, CallRoute& R, const SizeClass& sc, int list_off, int n_list, const StatPlanes& st, int only_li = -1,
                int yb0 = 0, int yb1 = -1);
 int ensure_maps(mtm_ctx* c);
-int run_score_all(mtm_ctx* c);
-bool banded_ok(mtm_ctx* c, const ImageArgs& a);
-int run_score_banded(mtm_ctx* c, const ImageArgs& a);
+int run_score_all(mtm_ctx* c, CallRoute& R);
+bool banded_ok(mtm_ctx* c, const ImageArgs& a, bool* single_band);
+int run_score_banded(mtm_ctx* c, CallRoute& R, const ImageArgs& a);
 int collect_ncc_time(mtm_ctx* c);
 
 }  // namespace mtmi

@@ -68,7 +68,7 @@ int ensure_square_planes(mtm_ctx* c) {
 // Window statistics of one size class (two kernels), into c->stats.  Returns the plane table.
 // `sb0`, `sb1`: range of kStatBand4-row output blocks to compute (banded image upload; fused single-channel
 // kernel only), sb1 < 0 = all.
-int launch_stats(mtm_ctx* c, const SizeClass& sc, StatPlanes* out, int sb0, int sb1) {
+int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out, int sb0, int sb1) {
     const int h = sc.h, w = sc.w;
     const int oh = c->rows - h + 1, ow = c->cols - w + 1;
     const int method = c->method;
@@ -141,9 +141,9 @@ int launch_stats(mtm_ctx* c, const SizeClass& sc, StatPlanes* out, int sb0, int 
                 src = sl.raw.as<uint8_t>();
                 src_pitch = c->cols;
             }
-            if (c->zero_pending && c->stats_stream != nullptr) {        // banded call: the candidate header is cleared here
+            if (R.zero_pending && c->stats_stream != nullptr) {         // banded call: the candidate header is cleared here
                 lay.zero16 = c->cands.as<unsigned long long>();
-                c->zero_pending = false;
+                R.zero_pending = false;
             }
             hipLaunchKernelGGL(stats_u8_kernel, gs, dim3(256), 0, c->stats_stream ? c->stats_stream : c->stream, src,
                                src_pitch, h, w, oh, ow, owg, inv_area, num_type, normed ? 1 : 0, want_t, want_sum2, tp[0],
@@ -347,7 +347,7 @@ int launch_stats(mtm_ctx* c, const SizeClass& sc, StatPlanes* out, int sb0, int 
 // launches of ncc_bf16_kernel (I x U = T M^2, J x V = M^2) into scratch maps, the combine pass (placeholders + the list of
 // outputs that could pass the threshold), exact re-scoring of the list into the score maps.  *done = false: the list
 // overflowed (a threshold that passes nearly everything) - the caller runs the float64 kernel.
-static int launch_masked_bf16(mtm_ctx* c, const SizeClass& sc, float* maps, bool* done) {
+static int launch_masked_bf16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, float* maps, bool* done) {
     *done = false;
     const int h = sc.h, w = sc.w, oh = c->rows - h + 1, ow = c->cols - w + 1, n_all = (int)sc.members.size();
     const ImageDev img = image_dev(c);
@@ -421,7 +421,7 @@ static int launch_masked_bf16(mtm_ctx* c, const SizeClass& sc, float* maps, bool
     unsigned long long count = 0;
     // Round 6: ONE piece product first (ncc_bf16_kernel<MB, 1>: bounds 2^-7 instead of 2^-15 of the norms' products - the
     // combine pass states them with the eps of the launch that ran); a list that overflows repeats the screen with three
-    for (int np = c->bf16_np_now == 1 ? 1 : 3;; np = 3) {
+    for (int np = R.bf16_np == 1 ? 1 : 3;; np = 3) {
     for (int pl = 0; pl < 2; ++pl) {
         p.img = pl == 0 ? img.f32 : c->f32_sq.as<float>();
         p.mu_out = c->mbf_mu.as<float>() + (size_t)pl * n_tiles;
@@ -451,7 +451,7 @@ static int launch_masked_bf16(mtm_ctx* c, const SizeClass& sc, float* maps, bool
     q.nseg = p.nseg;
     q.method = c->method;
     q.mode_min = c->method == MTM_TM_SQDIFF ? 1 : 0;
-    q.thr = c->mbf_thr;
+    q.thr = R.mbf_thr;
     q.eps = bf16_rig_eps(1, h, p.nkb, np);
     q.h = h;
     q.w = w;
@@ -461,7 +461,7 @@ static int launch_masked_bf16(mtm_ctx* c, const SizeClass& sc, float* maps, bool
     q.list = reinterpret_cast<mtm_hit*>(c->mbf_list.as<uint8_t>() + 16);
     q.counter = c->mbf_list.as<unsigned long long>();
     q.cap = cap;
-    if (c->mbf_global) {
+    if (R.mbf_global) {
         // N_object == 1: the templates' best lower bounds first (ordered-float keys behind the list's header + records), then
         // everything that reaches them
         MTMC(c->mbf_best.ensure(sizeof(unsigned int) * c->templs.size()));
@@ -481,7 +481,7 @@ static int launch_masked_bf16(mtm_ctx* c, const SizeClass& sc, float* maps, bool
         break;
     }
     if (np == 3) return MTM_OK;                                 // *done stays false: float64 kernel
-    c->bf16_np_now = 3;                                         // (this call's other classes and the next calls start with three)
+    R.bf16_np = 3;                                              // (this call's other classes and the next calls start with three)
     c->np1_backoff = c->np1_backoff_len;
     c->np1_backoff_len = std::min(2 * c->np1_backoff_len, 1024);
     }
@@ -501,15 +501,15 @@ static int launch_masked_bf16(mtm_ctx* c, const SizeClass& sc, float* maps, bool
         hipLaunchKernelGGL(refine_rescore_masked_kernel, dim3(rgrid), dim3(64), 0, c->stream, r);
         HIPC(hipGetLastError());
     }
-    c->mbf_used = true;
+    R.mbf_used = true;
     *done = true;
     return MTM_OK;
 }
 
 // Score maps of `n_list` templates of class `sc` (device list at tlist + list_off).
 // `yb0`, `yb1`: range of output row blocks (MFMA kernel only; banded image upload), yb1 < 0 = all.
-int launch_ncc(mtm_ctx* c, const SizeClass& sc, int list_off, int n_list, const StatPlanes& st, int only_li, int yb0,
-               int yb1) {
+int launch_ncc(mtm_ctx* c, CallRoute& R, const SizeClass& sc, int list_off, int n_list, const StatPlanes& st, int only_li,
+               int yb0, int yb1) {
     const int h = sc.h, w = sc.w;
     const int oh = c->rows - h + 1, ow = c->cols - w + 1;
     const ImageDev img = image_dev(c);
@@ -675,14 +675,14 @@ int launch_ncc(mtm_ctx* c, const SizeClass& sc, int list_off, int n_list, const 
         q.w = w;
         q.h = h;
         q.chans = c->chans;
-        q.cand_on = (c->cand_on && only_li < 0) ? 1 : 0;
-        q.cand_min = c->cand_min ? 1 : 0;
-        q.cand_thr = c->cand_thr;
+        q.cand_on = R.cand_on ? 1 : 0;
+        q.cand_min = R.cand_min ? 1 : 0;
+        q.cand_thr = R.cand_thr;
         q.cand_cap = (unsigned long long)std::min<int64_t>(c->hit_cap, 4096LL * 256);
         q.cand_counter = c->cands.as<unsigned long long>();
         q.cand_hits = reinterpret_cast<mtm_hit*>(c->cands.as<uint8_t>() + 16);
-        q.hits_only = (q.cand_on && c->hits_only_now) ? 1 : 0;
-        if (c->ext_now && only_li < 0) {              // fused global extremum: keys instead of maps / candidates
+        q.hits_only = (q.cand_on && R.hits_only) ? 1 : 0;
+        if (R.ext) {                                  // fused global extremum: keys instead of maps / candidates
             q.ext_on = 1;
             q.ext_best = c->counters.as<unsigned long long>();
             q.cand_on = 0;
@@ -722,30 +722,30 @@ int launch_ncc(mtm_ctx* c, const SizeClass& sc, int list_off, int n_list, const 
         p.cpr_magic = 65536 / p.cpr + 1;
         p.group_bytes = sc.group_bytes;
         p.only_li = only_li;
-        p.cand_on = (c->cand_on && only_li < 0) ? 1 : 0;
-        p.hits_only = (p.cand_on && c->hits_only_now) ? 1 : 0;
-        p.cand_thr_lo = (double)c->cand_thr - 1e-6 * std::max(1.0, std::fabs((double)c->cand_thr));
+        p.cand_on = R.cand_on ? 1 : 0;
+        p.hits_only = (p.cand_on && R.hits_only) ? 1 : 0;
+        p.cand_thr_lo = (double)R.cand_thr - 1e-6 * std::max(1.0, std::fabs((double)R.cand_thr));
         p.screen_hi = std::min(p.cand_thr_lo, 0.999999) - 1e-6;
         p.sq_floor = 0.99 / std::sqrt((double)w * (double)h);
         p.screen_l1 = c->screen_l1;
-        p.cand_min = c->cand_min ? 1 : 0;
-        p.cand_thr = c->cand_thr;
-        if (c->sparse_now && only_li < 0) {     // maps in memory + a flag per row segment that holds something above the threshold
+        p.cand_min = R.cand_min ? 1 : 0;
+        p.cand_thr = R.cand_thr;
+        if (R.sparse) {                         // maps in memory + a flag per row segment that holds something above the threshold
             p.seg_flags = c->seg_flags.as<uint8_t>();
-            p.flag_tstride = c->flag_tstride;
-            p.flag_rstride = c->flag_rstride;
+            p.flag_tstride = R.flag_tstride;
+            p.flag_rstride = R.flag_rstride;
             const bool normed_m = c->method == MTM_TM_SQDIFF_NORMED || c->method == MTM_TM_CCORR_NORMED || c->method == MTM_TM_CCOEFF_NORMED;
             p.seg_skip = (c->seg_skip && !sc.masked && normed_m) ? 1 : 0;
-            c->seg_skip_used = c->seg_skip_used || p.seg_skip != 0;
+            R.seg_skip_used = R.seg_skip_used || p.seg_skip != 0;
         }
         p.cand_cap = (unsigned long long)c->hit_cap;
         p.cand_counter = c->cands.as<unsigned long long>();
         p.cand_hits = reinterpret_cast<mtm_hit*>(c->cands.as<uint8_t>() + 16);
         // the 8 spare bytes of the candidate header carry the shader clock the kernel measured (fetched with it)
         p.clk_out = (p.cand_on && c->cands.p) ? reinterpret_cast<float*>(c->cands.as<uint8_t>() + 8) : nullptr;
-        if (c->cand_pin_now && p.cand_on && c->pinned) {       // the head of the list also into the host's landing buffer
+        if (R.cand_pin && p.cand_on && c->pinned) {       // the head of the list also into the host's landing buffer
             p.cand_pin = reinterpret_cast<mtm_hit*>(static_cast<uint8_t*>(c->pinned) + 16);
-            p.cand_pin_n = (unsigned long long)c->cand_pin_n;
+            p.cand_pin_n = (unsigned long long)R.cand_pin_n;
             p.clk_out = reinterpret_cast<float*>(static_cast<uint8_t*>(c->pinned) + 8);
         }
         int tg0 = 0;
@@ -778,7 +778,7 @@ int launch_ncc(mtm_ctx* c, const SizeClass& sc, int list_off, int n_list, const 
         // statistics prefetch region: (channels + 2) planes per wave (RM loads its statistics directly)
         size_t lds = (size_t)p.st_off + (rm ? 0 : r2 ? (size_t)kMfRows * ((mb + 1) / 2) * 1024
                                                      : (size_t)kMfRows * mf_stat_bytes_per_wave(c->chans == 3 ? 3 : 1));
-        const bool ext = c->ext_now && only_li < 0;      // find_matches_impl checked the class
+        const bool ext = R.ext;                          // plan_call checked the class
         if (ext) {
             p.ext_off = (int)lds;                         // 4 waves x 32 keys
             lds += (size_t)kMfRows * 32 * sizeof(unsigned long long);
@@ -875,22 +875,22 @@ int launch_ncc(mtm_ctx* c, const SizeClass& sc, int list_off, int n_list, const 
         p.u16_tsum = ts + tg0 * 16;
         p.u16_npad = n_pad;
         p.u16_area = (double)h * (double)w;
-        p.cand_on = (c->cand_on && only_li < 0) ? 1 : 0;
-        p.hits_only = (p.cand_on && c->hits_only_now) ? 1 : 0;
-        p.cand_min = c->cand_min ? 1 : 0;
-        p.cand_thr = c->cand_thr;
+        p.cand_on = R.cand_on ? 1 : 0;
+        p.hits_only = (p.cand_on && R.hits_only) ? 1 : 0;
+        p.cand_min = R.cand_min ? 1 : 0;
+        p.cand_thr = R.cand_thr;
         p.cand_cap = (unsigned long long)std::min<int64_t>(c->hit_cap, 4096LL * 256);
         p.cand_counter = c->cands.as<unsigned long long>();
         p.cand_hits = reinterpret_cast<mtm_hit*>(c->cands.as<uint8_t>() + 16);
-        if (c->cand_pin_now && p.cand_on && c->pinned) {
+        if (R.cand_pin && p.cand_on && c->pinned) {
             p.cand_pin = reinterpret_cast<mtm_hit*>(static_cast<uint8_t*>(c->pinned) + 16);
-            p.cand_pin_n = (unsigned long long)c->cand_pin_n;
+            p.cand_pin_n = (unsigned long long)R.cand_pin_n;
         }
-        p.cand_thr_lo = (double)c->cand_thr - 1e-6 * std::max(1.0, std::fabs((double)c->cand_thr));
+        p.cand_thr_lo = (double)R.cand_thr - 1e-6 * std::max(1.0, std::fabs((double)R.cand_thr));
         p.screen_hi = std::min(p.cand_thr_lo, 0.999999) - 1e-6;
         p.sq_floor = 0.99 / std::sqrt((double)w * (double)h);
         p.screen_l1 = c->screen_l1;
-        const bool ext = c->ext_now && only_li < 0;      // fused global extremum (find_matches_impl checked the classes)
+        const bool ext = R.ext;                          // fused global extremum (plan_call checked the classes)
         if (ext) {
             p.ext_off = (int)lds;                         // 4 waves x 32 keys
             lds += (size_t)kMfRows * 32 * sizeof(unsigned long long);
@@ -910,7 +910,7 @@ int launch_ncc(mtm_ctx* c, const SizeClass& sc, int list_off, int n_list, const 
         sel16.exact_div = c->exact_div != 0;
         hipLaunchKernelGGL(mfma_kernel(sel16), dim3(grid), dim3(256), lds, ncc_s, p, td, tl_k, ap, st, maps);
         c->timing.kernel_used = MTM_KERNEL_MFMA16;
-    } else if (kernel == MTM_KERNEL_MFMA_F32 && !c->f32_exact_now) {
+    } else if (kernel == MTM_KERNEL_MFMA_F32 && !R.f32_exact) {
         const int n_all = (int)sc.members.size();
         const int mb = n_all > 16 ? 2 : 1;
         Bf16Params p{};
@@ -947,45 +947,43 @@ int launch_ncc(mtm_ctx* c, const SizeClass& sc, int list_off, int n_list, const 
             p.only_li = only_li - tg0 * 16 * mb;
         }
         p.n_work = p.nseg * p.nyb * p.ntg;
-        p.cand_on = (c->cand_on && only_li < 0) ? 1 : 0;
-        p.cand_min = c->cand_min ? 1 : 0;
-        p.cand_thr = c->cand_thr;
+        p.cand_on = R.cand_on ? 1 : 0;
+        p.cand_min = R.cand_min ? 1 : 0;
+        p.cand_thr = R.cand_thr;
         p.cand_cap = (unsigned long long)std::min<int64_t>(c->hit_cap, 4096LL * 256);
         p.cand_counter = c->cands.as<unsigned long long>();
         p.cand_hits = reinterpret_cast<mtm_hit*>(c->cands.as<uint8_t>() + 16);
-        p.hits_only = (p.cand_on && c->hits_only_now) ? 1 : 0;
+        p.hits_only = (p.cand_on && R.hits_only) ? 1 : 0;
         const bool raw_m = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_CCORR || c->method == MTM_TM_CCOEFF;
         // piece products of this launch: one where only a list leaves the kernel and every listing decision rests on a
         // bound that knows it (below: rig 1 / 2, the refined extremum by bounds); three everywhere else
         int np = 3;
-        if (c->bf16_np_now == 1 && c->refine_now && only_li < 0 && (p.hits_only || c->ext_now) &&
-            (!raw_m || c->ext_now || c->raw_rig_now))
-            np = 1;
-        if (c->refine_now && !raw_m && only_li < 0) {
+        if (R.bf16_np == 1 && R.refine && (p.hits_only || R.ext) && (!raw_m || R.ext || R.raw_rig)) np = 1;
+        if (R.refine && !raw_m) {
             // Round 5: the listing decisions of the refined routes by the rigorous per-output bound (Bf16Params::rig)
             p.rig = 1;
             p.rig_eps = bf16_rig_eps(c->chans, h, p.nkb, np);
-            p.rig_thr = c->rig_thr;
-            p.list_all = c->cand_min ? (c->rig_thr < -1.0f ? 1 : 0) : (c->rig_thr < 0.0f ? 1 : 0);
-            if (c->refine_scan_now) {           // map mode: the scan's tolerances hold while no bound exceeds the cap
-                p.rig_cap = c->rig_cap;
+            p.rig_thr = R.rig_thr;
+            p.list_all = R.cand_min ? (R.rig_thr < -1.0f ? 1 : 0) : (R.rig_thr < 0.0f ? 1 : 0);
+            if (R.refine_scan) {                // map mode: the scan's tolerances hold while no bound exceeds the cap
+                p.rig_cap = R.rig_cap;
                 p.rig_flag = reinterpret_cast<unsigned int*>(c->cands.as<uint8_t>() + 8);
             }
         }
-        if (c->refine_now && raw_m && c->raw_rig_now && !c->ext_now && only_li < 0) {
+        if (R.refine && raw_m && R.raw_rig && !R.ext) {
             // raw sums with a threshold (round 5): everything whose UPPER bound passes is listed and re-scored exactly
             p.rig = 2;
             p.rig_eps = bf16_rig_eps(c->chans, h, p.nkb, np);
-            p.rig_thr = c->rig_thr;
+            p.rig_thr = R.rig_thr;
             p.list_all = 0;
         }
-        if (c->ext_now && only_li < 0) {                  // fused global extremum (find_matches_impl checked the classes)
+        if (R.ext) {                                      // fused global extremum (plan_call checked the classes)
             p.ext_on = 1;
             p.ext_best = c->counters.as<unsigned long long>();
             p.cand_on = 1;
             p.hits_only = 1;
-            p.ext_margin = c->refine_now ? kRefineThrMargin : 0.0f;
-            if (raw_m && c->refine_now) {
+            p.ext_margin = R.refine ? kRefineThrMargin : 0.0f;
+            if (raw_m && R.refine) {
                 // rigorous bounds instead of a relative margin (Bf16Params::ext_raw): 2^-15 for the dropped piece products
                 // and the two 16-bit representations, 2^-24 per float32 accumulation (three MFMAs per 32-tap block)
                 p.ext_raw = 1;
@@ -1038,12 +1036,11 @@ int launch_ncc(mtm_ctx* c, const SizeClass& sc, int list_off, int n_list, const 
         // masked float32 class, local extrema against a threshold: two raw launches of the bf16 kernel as a screen + exact
         // re-scoring of everything that could pass (mtm_maskf32.hip.h); the float64 kernel only if that list overflows
         bool screened = false;
-        if (sc.masked && sc.mask_bf16 && c->mbf_thr_on && only_li < 0 && n_list == (int)sc.members.size() && kernel == MTM_KERNEL_AUTO)
-            MTMC(launch_masked_bf16(c, sc, maps, &screened));
-        if (screened) {
+        if (sc.masked && sc.mask_bf16 && R.mbf_thr_on && n_list == (int)sc.members.size() && kernel == MTM_KERNEL_AUTO)
+            MTMC(launch_masked_bf16(c, R, sc, maps, &screened));
+        if (screened)
             c->timing.kernel_used = MTM_KERNEL_MFMA_F32;
-            c->timing.f32_route = 4;
-        } else if (sc.masked)
+        else if (sc.masked)
             hipLaunchKernelGGL(ncc_f64_kernel<true>, grd, dim3(256), 0, c->stream, img, td, tl,
                                c->weights.as<double>(), st, c->method, maps, ntx);
         else
@@ -1113,28 +1110,35 @@ int launch_refine(mtm_ctx* c, const SizeClass& sc, const StatPlanes& st, bool ri
 }
 
 // refined global extremum: the keys the score kernel kept are approximate - rebuild them from the re-scored list
-static int launch_refine_extremum(mtm_ctx* c) {
+static int launch_refine_extremum(mtm_ctx* c, const CallRoute& R) {
     const size_t n = c->templs.size();
     HIPC(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * 2 * n, c->stream));
     const unsigned long long cap = (unsigned long long)std::min<int64_t>(c->hit_cap, 4096LL * 256);
     hipLaunchKernelGGL(refine_extremum_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, c->stream,
                        reinterpret_cast<const mtm_hit*>(c->cands.as<uint8_t>() + 16), c->cands.as<unsigned long long>(), cap,
-                       c->td.as<TemplDev>(), c->cand_min ? 1 : 0, c->counters.as<unsigned long long>());
+                       c->td.as<TemplDev>(), R.cand_min ? 1 : 0, c->counters.as<unsigned long long>());
     HIPC(hipGetLastError());
     return MTM_OK;
 }
 
 // the map scan of the refined route: potential peaks of class `sc` (approximate maps in memory) -> candidate buffer
-int launch_refine_scan(mtm_ctx* c, const SizeClass& sc) {
+static int launch_refine_scan(mtm_ctx* c, const CallRoute& R, const SizeClass& sc) {
     const int oh = c->rows - sc.h + 1, ow = c->cols - sc.w + 1;
     const dim3 grd((ow + kPkCols - 1) / kPkCols, (oh + 4 * kPkRows - 1) / (4 * kPkRows), (unsigned)sc.members.size());
     hipLaunchKernelGGL(refine_scan_kernel, grd, dim3(256), 0, c->stream, c->maps.as<float>(), c->td.as<TemplDev>(),
-                       c->tlist.as<int>() + sc.tlist_off, c->cand_min ? 1 : 0, c->scan_thr,
-                       2.0f * c->rig_cap, c->opt_border,
+                       c->tlist.as<int>() + sc.tlist_off, R.cand_min ? 1 : 0, R.scan_thr,
+                       2.0f * R.rig_cap, c->opt_border,
                        reinterpret_cast<mtm_hit*>(c->cands.as<uint8_t>() + 16),
                        (unsigned long long)std::min<int64_t>(c->hit_cap, 4096LL * 256), c->cands.as<unsigned long long>());
     HIPC(hipGetLastError());
     return MTM_OK;
+}
+
+// what follows a bf16 class's score launch on the refined routes: the exact re-scoring of what the screen listed
+static int launch_refine_class(mtm_ctx* c, const CallRoute& R, const SizeClass& sc, const StatPlanes& st) {
+    if (!R.refine_scan) return launch_refine(c, sc, st, false, !R.hits_only);
+    MTMC(launch_refine_scan(c, R, sc));
+    return launch_refine(c, sc, st, true, true);
 }
 
 namespace {
@@ -1181,15 +1185,15 @@ static bool class_reads_f32(const mtm_ctx* c, const SizeClass& sc) {
 // Statistics + score launches of every size class but `skip` (the class a banded call has already queued; -1: none).
 // `fork`: the event the lanes start behind instead of the present end of c->stream (banded calls: the last band's event -
 // the image is complete - so that the next class runs under the banded class's last launch).
-static int run_score_classes(mtm_ctx* c, int skip, hipEvent_t fork) {
-    if (!c->hits_only_now) MTMC(ensure_maps(c));
+static int run_score_classes(mtm_ctx* c, CallRoute& R, int skip, hipEvent_t fork) {
+    if (!R.hits_only) MTMC(ensure_maps(c));
     // several size classes: alternate them over lanes (see mtm_ctx::Lane).  Not while the float32 refinement is on: its
     // re-scoring kernels walk the candidate list of the class that just ran.
     int n_lanes = 1;
     const size_t n_todo = c->classes.size() - (skip >= 0 ? 1 : 0);
     bool mbf_any = false;                  // (masked float32 classes screened on the bf16 cores share their scratch buffers)
-    for (const SizeClass& sc : c->classes) mbf_any = mbf_any || (sc.mask_bf16 && c->mbf_thr_on);
-    if (c->classes.size() > 1 && n_todo > 0 && c->class_lanes > 1 && !c->refine_now && !c->refine_scan_now && !c->f32_exact_now && !mbf_any)
+    for (const SizeClass& sc : c->classes) mbf_any = mbf_any || (sc.mask_bf16 && R.mbf_thr_on);
+    if (c->classes.size() > 1 && n_todo > 0 && c->class_lanes > 1 && !R.refine && !R.f32_exact && !mbf_any)
         n_lanes = (int)std::min<size_t>(skip >= 0 ? n_todo + 1 : n_todo, (size_t)c->class_lanes);
     if (n_lanes > 1) {
         MTMC(ensure_lanes(c, n_lanes - 1));
@@ -1241,28 +1245,21 @@ static int run_score_classes(mtm_ctx* c, int skip, hipEvent_t fork) {
             HIPC(hipEventRecord(c->slab_fork, c->stream));
             c->slab_fork_early = true;
         }
-        const int rc_st = launch_stats(c, sc, &st);
-        const int rc_ncc = rc_st == MTM_OK ? launch_ncc(c, sc, sc.tlist_off, (int)sc.members.size(), st) : rc_st;
+        const int rc_st = launch_stats(c, R, sc, &st);
+        const int rc_ncc = rc_st == MTM_OK ? launch_ncc(c, R, sc, sc.tlist_off, (int)sc.members.size(), st) : rc_st;
         c->slab_fork_early = false;
         MTMC(rc_ncc);
-        if (c->refine_now && !c->f32_exact_now && resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32) {
-            if (c->refine_scan_now) {
-                MTMC(launch_refine_scan(c, sc));
-                MTMC(launch_refine(c, sc, st, true, true));
-            } else {
-                MTMC(launch_refine(c, sc, st, false, !c->hits_only_now));
-            }
-        }
+        if (R.refine && resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32) MTMC(launch_refine_class(c, R, sc, st));
     }
     for (int i = 0; i + 1 < n_lanes; ++i) {             // join: everything after the score pass is queued on c->stream
         HIPC(hipEventRecord(c->lanes[(size_t)i].done, c->lanes[(size_t)i].stream));
         HIPC(hipStreamWaitEvent(c->stream, c->lanes[(size_t)i].done, 0));
     }
-    if (c->refine_now && !c->f32_exact_now && c->ext_now) MTMC(launch_refine_extremum(c));
+    if (R.refine && R.ext) MTMC(launch_refine_extremum(c, R));
     return MTM_OK;
 }
 
-int run_score_all(mtm_ctx* c) { return run_score_classes(c, -1, nullptr); }
+int run_score_all(mtm_ctx* c, CallRoute& R) { return run_score_classes(c, R, -1, nullptr); }
 
 // Time during which at least one score-kernel launch of the call was running: the launches of a banded call
 // overlap (two compute streams), so their intervals are laid on the timeline of the first one and united.
@@ -1309,7 +1306,7 @@ static bool class_bandable(const mtm_ctx* c, const ImageArgs& a, const SizeClass
 
 // Several size classes: the class with the most multiply-accumulates among those that qualify is the one that runs under
 // the upload (c->banded_cls); the others follow on the complete image (run_score_banded).
-bool banded_ok(mtm_ctx* c, const ImageArgs& a) {
+bool banded_ok(mtm_ctx* c, const ImageArgs& a, bool* single_band) {
     c->banded_cls = -1;
     double best = 0.0;
     for (size_t i = 0; i < c->classes.size(); ++i) {
@@ -1319,7 +1316,7 @@ bool banded_ok(mtm_ctx* c, const ImageArgs& a) {
             c->banded_cls = (int)i;
         }
     }
-    c->single_band_now = false;
+    *single_band = false;
     if (c->banded_cls < 0 && c->classes.size() == 1 && a.dtype == MTM_U8) {
         // Round 5: a call too small to be worth two score launches (1080p x 8 templates) still takes the banded path's
         // kernels, as ONE band - layout conversion inside the statistics launch, the candidate header cleared there: two
@@ -1327,7 +1324,7 @@ bool banded_ok(mtm_ctx* c, const ImageArgs& a) {
         double work = 0.0;
         if (class_bandable(c, a, c->classes[0], &work, true)) {
             c->banded_cls = 0;
-            c->single_band_now = true;
+            *single_band = true;
         }
     }
     return c->banded_cls >= 0;
@@ -1374,9 +1371,9 @@ static bool class_bandable(const mtm_ctx* c, const ImageArgs& a, const SizeClass
 // ... of a float32 image (round 6): two bands; the first ends where ~30 % of the output rows are complete, at a whole number of
 // vsum bands (their column sums restart per band: the statistics planes are those of one launch) - the second band's 23 MB
 // cross PCIe under the first band's score launch.  The rows go straight into the padded float32 plane.
-static int run_score_banded_f32(mtm_ctx* c, const ImageArgs& a) {
+static int run_score_banded_f32(mtm_ctx* c, CallRoute& R, const ImageArgs& a) {
     const SizeClass& sc = c->classes[(size_t)c->banded_cls];
-    if (!c->hits_only_now) MTMC(ensure_maps(c));
+    if (!R.hits_only) MTMC(ensure_maps(c));
     MTMC(ensure_copy_stream(c));
     mtm_ctx::ImageSlot& sl = c->slot[c->cur];
     SlotGeom g{};
@@ -1387,14 +1384,14 @@ static int run_score_banded_f32(mtm_ctx* c, const ImageArgs& a) {
         c->band_ev.push_back(e);
     }
     const hipStream_t bs0 = c->copy_stream;
-    if (c->f32_exact_now) {
+    if (R.f32_exact) {
         // (this call's method / mode sends the class to the float64 kernel after all - decided behind the banding decision:
         // the whole image in one piece, then the plain score pass)
         MTMC(upload_rows_f32c1(sl, g, a.px, a.stride, 0, a.rows, bs0));
         HIPC(hipEventRecord(c->band_ev[0], bs0));
         HIPC(hipStreamWaitEvent(c->stream, c->band_ev[0], 0));
         HIPC(hipEventRecord(c->ev[0], c->stream));
-        return run_score_all(c);
+        return run_score_all(c, R);
     }
     const int h = sc.h, oh = a.rows - h + 1;
     const int nyb = (oh + kBfRows - 1) / kBfRows;
@@ -1411,7 +1408,7 @@ static int run_score_banded_f32(mtm_ctx* c, const ImageArgs& a) {
         c->lay_r0 = r_done;
         c->lay_r1 = r1;
         c->stats_stream = bs;
-        const int rc = launch_stats(c, sc, &st, last ? o_split / kStatBand4 : 0, last ? -1 : o_split / kStatBand4);
+        const int rc = launch_stats(c, R, sc, &st, last ? o_split / kStatBand4 : 0, last ? -1 : o_split / kStatBand4);
         c->stats_stream = nullptr;
         c->lay_r0 = c->lay_r1 = 0;
         MTMC(rc);
@@ -1419,34 +1416,29 @@ static int run_score_banded_f32(mtm_ctx* c, const ImageArgs& a) {
         HIPC(hipEventRecord(c->band_ev[(size_t)k], bs));
         (void)hipStreamQuery(bs);
         HIPC(hipStreamWaitEvent(c->stream, c->band_ev[(size_t)k], 0));
-        MTMC(launch_ncc(c, sc, sc.tlist_off, (int)sc.members.size(), st, -1, last ? o_split / kBfRows : 0, last ? nyb : o_split / kBfRows));
+        MTMC(launch_ncc(c, R, sc, sc.tlist_off, (int)sc.members.size(), st, -1, last ? o_split / kBfRows : 0, last ? nyb : o_split / kBfRows));
         (void)hipStreamQuery(c->stream);
     }
     // what run_score_all does behind a bf16 class's launch: the exact re-scoring of what the screen listed
-    if (c->refine_now && !c->f32_exact_now) {
-        if (c->refine_scan_now) {
-            MTMC(launch_refine_scan(c, sc));
-            MTMC(launch_refine(c, sc, st, true, true));
-        } else {
-            MTMC(launch_refine(c, sc, st, false, !c->hits_only_now));
-        }
-        if (c->ext_now) MTMC(launch_refine_extremum(c));
+    if (R.refine) {
+        MTMC(launch_refine_class(c, R, sc, st));
+        if (R.ext) MTMC(launch_refine_extremum(c, R));
     }
     return MTM_OK;
 }
 
-int run_score_banded(mtm_ctx* c, const ImageArgs& a) {
-    if (a.dtype == MTM_F32) return run_score_banded_f32(c, a);
+int run_score_banded(mtm_ctx* c, CallRoute& R, const ImageArgs& a) {
+    if (a.dtype == MTM_F32) return run_score_banded_f32(c, R, a);
     const SizeClass& sc = c->classes[(size_t)c->banded_cls];
     host_trace(c, 16);
-    if (!c->hits_only_now) MTMC(ensure_maps(c));
+    if (!R.hits_only) MTMC(ensure_maps(c));
     MTMC(ensure_copy_stream(c));
     host_trace(c, 17);
     mtm_ctx::ImageSlot& sl = c->slot[c->cur];
     SlotGeom g{};
     const bool u16 = a.dtype == MTM_U16;
     static const std::vector<double> kOneBand{1.0};
-    const std::vector<double>& bands = c->single_band_now ? kOneBand : c->upload_bands;
+    const std::vector<double>& bands = R.single_band ? kOneBand : c->upload_bands;
     const int nb = (int)bands.size();
     // (Round 4 measured three other layouts of the same work against this one and round 5 removed their code: the first
     // band on the score stream itself, consecutive bands on two copy-side streams, score launches alternating between two
@@ -1515,7 +1507,7 @@ int run_score_banded(mtm_ctx* c, const ImageArgs& a) {
         host_trace(c, k == 0 ? 4 : 7);                           // the band's copy call returned
         StatPlanes st;
         c->stats_stream = bs;
-        const int rc = launch_stats(c, sc, &st, sb_done, sb1);
+        const int rc = launch_stats(c, R, sc, &st, sb_done, sb1);
         c->stats_stream = nullptr;
         c->lay_r0 = c->lay_r1 = 0;
         MTMC(rc);
@@ -1527,12 +1519,12 @@ int run_score_banded(mtm_ctx* c, const ImageArgs& a) {
         int yb1 = last ? nyb : (sb1 * kStatBand4) / RB;
         if (!last && gen_blocks > 0.0) yb1 = std::min(yb1, yb_target);      // (exactly the whole generations, not the rows' rounding on top)
         if (yb1 > yb_done) {
-            if (c->zero_pending) {          // (no statistics launch took the clearing of the candidate header along)
+            if (R.zero_pending) {           // (no statistics launch took the clearing of the candidate header along)
                 HIPC(hipMemsetAsync(c->cands.p, 0, 16, c->stream));
-                c->zero_pending = false;
+                R.zero_pending = false;
             }
             HIPC(hipStreamWaitEvent(c->stream, c->band_ev[(size_t)k], 0));
-            const int rc2 = launch_ncc(c, sc, sc.tlist_off, (int)sc.members.size(), st, -1, yb_done, yb1);
+            const int rc2 = launch_ncc(c, R, sc, sc.tlist_off, (int)sc.members.size(), st, -1, yb_done, yb1);
             MTMC(rc2);
             (void)hipStreamQuery(c->stream);
             host_trace(c, k == 0 ? 6 : 8);                       // the band's score launch is submitted
@@ -1542,7 +1534,7 @@ int run_score_banded(mtm_ctx* c, const ImageArgs& a) {
     // the other size classes, on the complete image: the first of them on a lane behind the last band's event - under
     // the banded class's last launch - the rest alternating as in run_score_all
     // (k_prev: the last band that was queued - trailing bands without rows of their own record no event)
-    if (c->classes.size() > 1) MTMC(run_score_classes(c, c->banded_cls, c->band_ev[(size_t)(k_prev >= 0 ? k_prev : nb - 1)]));
+    if (c->classes.size() > 1) MTMC(run_score_classes(c, R, c->banded_cls, c->band_ev[(size_t)(k_prev >= 0 ? k_prev : nb - 1)]));
     return MTM_OK;
 }
 

@@ -109,6 +109,9 @@ extern "C" {
                                    3: as 1 without the one-product tier;
                                    4: diagnostic - as 2 with one piece product (the screen's raw scores: what the tests
                                    measure its bound on; never a result).  Environment: MTM_F32_MFMA. */
+#define MTM_OPT_BATCH_MAX_ROWS 8 /* mtm_find_matches_batch: the most stacked image rows in one chunk (1 .. 65535, the default:
+                                   the tightest bound a tall map has to respect, kBatchMaxRows in csrc/mtm_ctx.h).  A chunk
+                                   holds at least one image; smaller values only split a batch into more chunks. */
 
 /* error codes */
 #define MTM_OK            0
@@ -296,6 +299,27 @@ int mtm_find_matches_image_sharded_nms(mtm_ctx* ctx, const void* px, int rows, i
                                        int64_t row_stride_bytes, double score_threshold, double max_overlap,
                                        int64_t n_object, int method, const int32_t* global_idx, int n_local_templ,
                                        mtm_hit* out, int64_t capacity, int64_t* n_out);
+
+/* A batch of images of ONE shape against the templates of the last mtm_set_templates ("thousands of images", reference
+ * tutorials/Tutorial3-SpeedingUp.ipynb: well plates, time-lapse stacks): what n_images calls of mtm_find_matches_image
+ * return, in one chain of launches instead of one per image.  images[b] points at image b's first row; every image has
+ * rows x cols x chans pixels of `dtype` and the row stride `row_stride_bytes` (a cropped view of a larger image needs no
+ * host copy).  uint8 and uint16 only: MTM_F32 returns MTM_E_INVALID (the float32 screen and re-scoring routes work on
+ * neighbourhoods of one image); so does a template taller or wider than the images.
+ * The images are uploaded as ONE image of n_images * rows rows, and the statistics and score launches run over the whole
+ * stack.  Map rows whose windows straddle two images are computed and ignored: the peak pass treats the rows outside
+ * image b's own map rows as outside the map (the border rule of MTM_OPT_PEAK_BORDER), the global extremum is taken per
+ * (image, template) in the image's own row-major order, and 1-D / 1x1 per-image maps take the host's find_peaks_1d path.
+ * The maps are always materialised (no kernel candidate list, no fused extremum).  Batches taller than
+ * MTM_OPT_BATCH_MAX_ROWS, or than a device-memory budget for the maps, run in chunks of whole images; results do not depend
+ * on the chunking.
+ * Output: the hits of image 0, then image 1, ... - each image's records exactly those (and in the order) mtm_find_matches_image
+ * returns for it alone, coordinates in the image's own frame; counts[b] = records of image b.  counts is filled on
+ * MTM_E_OVERFLOW too: *n_out is then the capacity needed and mtm_last_hits returns the records.  Afterwards the context has
+ * no current image (mtm_find_matches, mtm_last_score_map: MTM_E_STATE until the next mtm_set_image). */
+int mtm_find_matches_batch(mtm_ctx* ctx, const void* const* images, int n_images, int rows, int cols, int chans,
+                           int dtype, int64_t row_stride_bytes, int mode, double score_threshold,
+                           mtm_hit* out, int64_t capacity, int64_t* counts, int64_t* n_out);
 
 /* Stream form of mtm_find_matches ("thousands of images", reference
  * tutorials/Tutorial3-SpeedingUp.ipynb:564: same templates, one image after the other): returns the

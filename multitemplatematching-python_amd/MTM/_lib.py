@@ -23,7 +23,10 @@ PEAKS_LOCAL, PEAKS_GLOBAL = 0, 1
 BORDER_CONSTANT, BORDER_NEAREST = 0, 1
 KERNEL_AUTO, KERNEL_NAIVE, KERNEL_DOT4, KERNEL_MFMA = 0, 1, 2, 3
 OPT_KERNEL, OPT_PEAK_BORDER, OPT_HIT_CAPACITY, OPT_DOT4_VARIANT, OPT_EXACT_DIV, OPT_HITS_ONLY, OPT_F32_MFMA = 1, 2, 3, 4, 5, 6, 7
-ALL_OPTIONS = (OPT_KERNEL, OPT_PEAK_BORDER, OPT_HIT_CAPACITY, OPT_DOT4_VARIANT, OPT_EXACT_DIV, OPT_HITS_ONLY, OPT_F32_MFMA)
+OPT_BATCH_MAX_ROWS = 8
+ALL_OPTIONS = (OPT_KERNEL, OPT_PEAK_BORDER, OPT_HIT_CAPACITY, OPT_DOT4_VARIANT, OPT_EXACT_DIV, OPT_HITS_ONLY, OPT_F32_MFMA,
+               OPT_BATCH_MAX_ROWS)
+BATCH_MAX_ROWS = 65535      # the default (and largest) MTM_OPT_BATCH_MAX_ROWS: stacked rows of one mtm_find_matches_batch chunk
 POISON_SCRATCH, POISON_LDS, POISON_ARENAS = 1, 2, 4
 E_OVERFLOW = -5
 E_HIP = -2
@@ -96,6 +99,9 @@ SYMBOLS = {
                                                           ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
                                                           ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                                           ctypes.c_void_p, ctypes.c_int64, _P(ctypes.c_int64)]),
+    "mtm_find_matches_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
+                                              ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _P(ctypes.c_int64)]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
                                              ctypes.c_int64, _P(ctypes.c_int64), ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
@@ -449,6 +455,32 @@ class Context(_RecordMemo):
             rc = self._lib.mtm_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(n))
         check(rc, "mtm_find_matches_image")
         return out[:n.value]
+
+    def find_matches_batch(self, images, mode, score_threshold):
+        """Images of one shape and dtype against the current templates in one native call (mtm_find_matches_batch): a list
+        of hit arrays, one per image, each what find_matches_image returns for that image alone.  uint8 / uint16 only."""
+        n = len(images)
+        if n == 0:
+            return []
+        rows = [_pixel_rows(a) for a in images]
+        if len({r[2] for r in rows}) > 1:       # (one row stride for the whole batch)
+            rows = [_pixel_rows(np.ascontiguousarray(a)) for a in images]
+        a0, _, stride = rows[0]
+        chans = 1 if a0.ndim == 2 else a0.shape[2]
+        ptrs = (ctypes.c_void_p * n)(*[r[1] for r in rows])
+        counts = np.zeros(n, dtype=np.int64)
+        cap = max(4096, 64 * n)
+        out = np.empty(cap, dtype=HIT_DTYPE)
+        total = ctypes.c_int64(0)
+        rc = self._lib.mtm_find_matches_batch(self._h, ptrs, n, a0.shape[0], a0.shape[1], chans, _dtype_code(a0), stride,
+                                              int(mode), float(score_threshold), out.ctypes.data, cap, counts.ctypes.data,
+                                              ctypes.byref(total))
+        if rc == E_OVERFLOW:        # the records stay in the context; counts are filled
+            cap = int(total.value)
+            out = np.empty(cap, dtype=HIT_DTYPE)
+            rc = self._lib.mtm_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(total))
+        check(rc, "mtm_find_matches_batch")
+        return np.split(out[:total.value], np.cumsum(counts)[:-1])
 
     def search_nms(self, templates, image, method, score_threshold, max_overlap, n_object=-1):
         """search() + MTM's non-maxima suppression in one native call (mtm_find_matches_image_nms): the kept hits, best

@@ -862,6 +862,164 @@ int find_matches_impl(mtm_ctx* c, int mode, double score_threshold, mtm_hit* out
     return fm_end(c, R, out, capacity, n_out);
 }
 
+// ---- mtm_find_matches_batch: n images of one shape as ONE tall image of n * rows rows (include/mtm_hip.h).  Map row y
+// belongs to image b = y / rows; it is a window of that image when y % rows < rows - h + 1 and straddles a seam otherwise.
+
+// Images per chunk: the row bound (MTM_OPT_BATCH_MAX_ROWS) and the device memory of the chunk - a float per template and
+// pixel for the maps, the raw copy and the uint8 / int8 / float32 planes per channel, the window statistics.
+int batch_chunk_images(const mtm_ctx* c, int rows, int cols, int chans) {
+    const double pitch = (double)round_up((size_t)cols + kPadCols, 64);
+    const double per_image = (double)rows * pitch * (4.0 * (double)c->templs.size() + 10.0 * chans + 48.0);
+    const int by_rows = std::max(1, c->batch_max_rows / rows);
+    const int by_mem = (int)std::max(1.0, std::min(1e9, kBatchChunkBytes / per_image));
+    return std::min(by_rows, by_mem);
+}
+
+// Images px[0 .. nb) of the batch as one stack: upload, statistics and score launches over the whole stack (maps in memory),
+// then the seam-aware peak pass (peaks_batch_kernel) or the per-image extremum (extremum_batch_kernel); 1-D / 1x1 per-image
+// maps on the host.  Appends each image's records, ordered as fm_end orders them, to per_img[b].
+int batch_chunk(mtm_ctx* c, const void* const* px, int nb, int rows, int cols, int chans, int dtype, int64_t stride, int mode,
+                float thr, std::vector<mtm_hit>* per_img) {
+    adopt_image(c, nb * rows, cols, chans, dtype);
+    MTMC(place_templates(c));
+    MTMC(upload_image_stack(c, c->slot[c->cur], px, nb, stride, rows, cols, chans, dtype, c->stream));
+    c->timing = mtm_timing{};
+    const int n = (int)c->templs.size();
+    const bool mode_min = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_SQDIFF_NORMED;
+    // the map route: no candidate list, no fused extremum, no segment flags (each keeps one answer per template over the
+    // whole launch, or packs stack rows where the seams need image rows)
+    CallRoute R;
+    R.mode = mode;
+    R.n = n;
+    R.thr = thr;
+    R.mode_min = mode_min;
+    HIPC(hipEventRecord(c->ev[0], c->stream));
+    MTMC(run_score_all(c, R));
+    HIPC(hipEventRecord(c->ev[1], c->stream));
+    const float* maps = c->maps.as<float>();
+    if (mode == MTM_PEAKS_GLOBAL) {
+        std::vector<unsigned long long> best(2 * (size_t)nb * std::max(1, n), 0ull);
+        long long max_px = 1;
+        for (const TemplDev& d : c->td_host) max_px = std::max(max_px, (long long)(rows - d.rows + 1) * d.ow);
+        MTMC(c->counters.ensure(sizeof(unsigned long long) * best.size()));
+        HIPC(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * best.size(), c->stream));
+        if (n > 0) {
+            const int nbk = (int)std::min<long long>(256, (max_px + 4095) / 4096);
+            hipLaunchKernelGGL(extremum_batch_kernel, dim3(nbk, n, nb), dim3(256), 0, c->stream, maps, c->td.as<TemplDev>(), rows,
+                               nbk, c->counters.as<unsigned long long>());
+            HIPC(hipGetLastError());
+        }
+        HIPC(hipEventRecord(c->ev[2], c->stream));
+        HIPC(hipMemcpyAsync(best.data(), c->counters.p, sizeof(unsigned long long) * best.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        for (int b = 0; b < nb; ++b)
+            for (int t = 0; t < n; ++t) {           // (fm_end's decoding, on the image's own index)
+                const unsigned long long key = best[2 * ((size_t)b * n + t) + (mode_min ? 1 : 0)];
+                const TemplDev& d = c->td_host[t];
+                uint32_t o = (uint32_t)(key >> 32);
+                if (mode_min) o = ~o;
+                const uint32_t idx = key ? (0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu)) : 0u;
+                mtm_hit h;
+                h.templ_idx = t;
+                h.x = (int)(idx % (uint32_t)d.ow);
+                h.y = (int)(idx / (uint32_t)d.ow);
+                h.w = d.cols;
+                h.h = d.rows;
+                h.score = key ? decode_order(o) : NAN;
+                per_img[b].push_back(h);
+            }
+    } else {
+        const int n2d = (int)c->list2d.size();
+        std::vector<int> nontriv((size_t)nb * std::max(1, n), 0);
+        std::vector<mtm_hit> hits;
+        if (n2d > 0) {
+            int max_oh = 0, max_ow = 0;
+            for (int t : c->list2d) {
+                max_oh = std::max(max_oh, c->td_host[t].oh);
+                max_ow = std::max(max_ow, c->td_host[t].ow);
+            }
+            // [hit count | nontrivial flag per (image, template)] [records]
+            const size_t hdr = round_up(sizeof(unsigned long long) + sizeof(int) * nontriv.size(), 16);
+            const dim3 grd((max_ow + kPkCols - 1) / kPkCols, (max_oh + 4 * kPkRows - 1) / (4 * kPkRows), n2d);
+            bool done = false;
+            for (int pass = 0; pass < 2 && !done; ++pass) {         // (a list that overflowed: once more, large enough)
+                MTMC(c->hits.ensure(hdr + sizeof(mtm_hit) * (size_t)c->hit_cap));
+                uint8_t* dbase = c->hits.as<uint8_t>();
+                unsigned long long* counter = reinterpret_cast<unsigned long long*>(dbase);
+                mtm_hit* dhits = reinterpret_cast<mtm_hit*>(dbase + hdr);
+                HIPC(hipMemsetAsync(dbase, 0, hdr, c->stream));
+                hipLaunchKernelGGL(peaks_batch_kernel, grd, dim3(256), 0, c->stream, maps, c->td.as<TemplDev>(),
+                                   c->tlist.as<int>() + c->list2d_off, mode_min ? 1 : 0, thr, c->opt_border, dhits,
+                                   (unsigned long long)c->hit_cap, counter, reinterpret_cast<int*>(counter + 1), rows, n);
+                HIPC(hipGetLastError());
+                std::vector<uint8_t> hb(hdr);
+                HIPC(hipMemcpyAsync(hb.data(), dbase, hdr, hipMemcpyDeviceToHost, c->stream));
+                HIPC(hipStreamSynchronize(c->stream));
+                unsigned long long count = 0;
+                std::memcpy(&count, hb.data(), sizeof(count));
+                std::memcpy(nontriv.data(), hb.data() + sizeof(count), sizeof(int) * nontriv.size());
+                if ((int64_t)count <= c->hit_cap) {
+                    hits.resize((size_t)count);
+                    if (count) {
+                        HIPC(hipMemcpyAsync(hits.data(), dhits, sizeof(mtm_hit) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
+                        HIPC(hipStreamSynchronize(c->stream));
+                    }
+                    done = true;
+                } else {
+                    c->hit_cap = (int64_t)count + 1024;
+                }
+            }
+            if (!done) return ladder_exhausted();
+        }
+        HIPC(hipEventRecord(c->ev[2], c->stream));
+        // stack rows -> (image, row); skimage: a map in which every pixel equals its local maximum has no peaks at all
+        for (const mtm_hit& h : hits) {
+            const int b = h.y / rows;
+            if (!nontriv[(size_t)b * n + h.templ_idx]) continue;
+            mtm_hit r = h;
+            r.y -= b * rows;
+            per_img[b].push_back(r);
+        }
+        // 1-D and 1x1 per-image maps (MTM/__init__.py:25-41) on the host, as fm_end does for one image
+        for (int t = 0; t < n; ++t) {
+            const TemplDev& d = c->td_host[t];
+            const int oh_b = rows - d.rows + 1;
+            if (oh_b > 1 && d.ow > 1) continue;
+            std::vector<float> mp((size_t)d.oh * d.ow);
+            HIPC(hipMemcpy2DAsync(mp.data(), sizeof(float) * d.ow, maps + d.map_off, sizeof(float) * d.map_pitch,
+                                  sizeof(float) * d.ow, d.oh, hipMemcpyDeviceToHost, c->stream));
+            HIPC(hipStreamSynchronize(c->stream));
+            const int len = std::max(oh_b, d.ow);
+            for (int b = 0; b < nb; ++b) {
+                const float* line = mp.data() + (size_t)b * rows * d.ow;      // (a row, or a column of a one-column map)
+                std::vector<int> pk;
+                if (len == 1) {
+                    const float v = mode_min ? -line[0] : line[0];
+                    if (v >= (mode_min ? -thr : thr)) pk.push_back(0);
+                } else {
+                    pk = find_peaks_1d(line, len, 1, mode_min ? -thr : thr, mode_min);
+                }
+                for (int i : pk) {
+                    mtm_hit h;
+                    h.templ_idx = t;
+                    h.x = oh_b == 1 ? i : 0;
+                    h.y = oh_b == 1 ? 0 : i;
+                    h.w = d.cols;
+                    h.h = d.rows;
+                    h.score = line[(size_t)i];
+                    per_img[b].push_back(h);
+                }
+            }
+        }
+        for (int b = 0; b < nb; ++b) sort_hits(per_img[b], mode_min);
+    }
+    HIPC(hipEventSynchronize(c->ev[2]));
+    HIPC(hipEventElapsedTime(&c->timing.score_ms, c->ev[0], c->ev[1]));
+    HIPC(hipEventElapsedTime(&c->timing.peaks_ms, c->ev[1], c->ev[2]));
+    HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[2]));
+    return collect_ncc_time(c);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1053,6 +1211,73 @@ int mtm_find_matches_next(mtm_ctx* c, int mode, double score_threshold, mtm_hit*
     c->cur = 1 - c->cur;
     adopt_image(c, rows, cols, chans, dtype);
     return rc;
+}
+
+int mtm_find_matches_batch(mtm_ctx* c, const void* const* images, int n_images, int rows, int cols, int chans, int dtype,
+                           int64_t row_stride_bytes, int mode, double score_threshold, mtm_hit* out, int64_t capacity,
+                           int64_t* counts, int64_t* n_out) {
+    if (!c || !n_out || n_images < 0 || (n_images > 0 && (!images || !counts)) || capacity < 0 || (capacity > 0 && !out) ||
+        (mode != MTM_PEAKS_LOCAL && mode != MTM_PEAKS_GLOBAL)) {
+        set_error("mtm_find_matches_batch: bad arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, "mtm_find_matches_batch");
+    if (dtype == MTM_F32) {
+        set_error("mtm_find_matches_batch: uint8 and uint16 images only (float32: mtm_find_matches_image per image)");
+        return MTM_E_INVALID;
+    }
+    *n_out = 0;
+    if (n_images == 0) return MTM_OK;
+    for (int b = 0; b < n_images; ++b)
+        MTMC(check_image_args(images[b], rows, cols, chans, dtype, row_stride_bytes, "mtm_find_matches_batch"));
+    if (!c->have_templ) {
+        set_error("mtm_find_matches_batch: set the templates first");
+        return MTM_E_STATE;
+    }
+    for (const HostTempl& t : c->templs)
+        if (t.rows > rows || t.cols > cols) {        // (the stack would hide it: a template taller than one image fits it)
+            set_error("mtm_find_matches_batch: a template is larger than the images");
+            return MTM_E_INVALID;
+        }
+    HIPC(hipSetDevice(c->device));
+    const int per_chunk = batch_chunk_images(c, rows, cols, chans);
+    std::vector<std::vector<mtm_hit>> per_img((size_t)n_images);
+    mtm_timing acc{};
+    int rc = MTM_OK;
+    for (int b0 = 0; b0 < n_images && rc == MTM_OK; b0 += per_chunk) {
+        const int nb = std::min(per_chunk, n_images - b0);
+        rc = batch_chunk(c, images + b0, nb, rows, cols, chans, dtype, row_stride_bytes, mode, (float)score_threshold,
+                         per_img.data() + b0);
+        acc.total_ms += c->timing.total_ms;
+        acc.score_ms += c->timing.score_ms;
+        acc.peaks_ms += c->timing.peaks_ms;
+        acc.ncc_kernel_ms += c->timing.ncc_kernel_ms;
+        acc.ncc_sum_ms += c->timing.ncc_sum_ms;
+        acc.ncc_launches += c->timing.ncc_launches;
+        acc.sq_launches += c->timing.sq_launches;
+        acc.masked_stat_ms += c->timing.masked_stat_ms;
+        acc.kernel_used = c->timing.kernel_used;
+        acc.sclk_mhz = c->timing.sclk_mhz;
+    }
+    // the stack is none of the caller's images: no current image, no published maps
+    c->have_image = false;
+    c->maps_valid = false;
+    if (rc != MTM_OK) return rc;
+    std::vector<mtm_hit> all;
+    for (int b = 0; b < n_images; ++b) {
+        counts[b] = (int64_t)per_img[(size_t)b].size();
+        all.insert(all.end(), per_img[(size_t)b].begin(), per_img[(size_t)b].end());
+    }
+    acc.n_hits = (int64_t)all.size();
+    c->timing = acc;
+    *n_out = (int64_t)all.size();
+    c->last_hits.swap(all);
+    if ((int64_t)c->last_hits.size() > capacity) {
+        set_error("mtm_find_matches_batch: output capacity too small (fetch the result with mtm_last_hits)");
+        return MTM_E_OVERFLOW;
+    }
+    if (!c->last_hits.empty()) std::memcpy(out, c->last_hits.data(), sizeof(mtm_hit) * c->last_hits.size());
+    return MTM_OK;
 }
 
 int mtm_last_hits(mtm_ctx* c, mtm_hit* out, int64_t capacity, int64_t* n_out) {

@@ -121,13 +121,10 @@ int upload_rows_u16c1(mtm_ctx::ImageSlot& sl, const SlotGeom& g, const void* src
 
 // Upload one image into `sl` and build its planar padded planes on `stream`.  `src` has tightly
 // packed rows when `src_stride` == cols * chans * elem size or any larger stride.
-int upload_image(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* src, int64_t src_stride, int src_rows, int src_cols,
-                 int chans, int dtype, hipStream_t stream, int factor) {
-    SlotGeom g{};
-    MTMC(prepare_slot(c, sl, src_rows, src_cols, chans, dtype, stream, factor, &g));
+// The planar padded planes of `sl` from its raw buffer (tightly packed rows, as uploaded) on `stream`.
+static int convert_raw(mtm_ctx::ImageSlot& sl, const SlotGeom& g, int src_cols, int chans, int dtype, hipStream_t stream,
+                       int factor) {
     sl.f32_valid = true;
-    const size_t tight = (size_t)src_cols * chans * elem_size(dtype);
-    HIPC(hipMemcpy2DAsync(sl.raw.p, tight, src, (size_t)src_stride, tight, src_rows, hipMemcpyHostToDevice, stream));
     const int rows = g.rows, cols = g.cols, rows_alloc = g.rows_alloc, pitch = g.pitch;
     const size_t u8_bytes = g.u8_bytes;
     const bool u16_planes = dtype == MTM_U16 && chans == 1;
@@ -164,6 +161,29 @@ int upload_image(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* src, int64_t sr
                            sl.f32.as<float>(), pitch, (long long)pitch * rows_alloc);
     HIPC(hipGetLastError());
     return MTM_OK;
+}
+
+int upload_image(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* src, int64_t src_stride, int src_rows, int src_cols,
+                 int chans, int dtype, hipStream_t stream, int factor) {
+    SlotGeom g{};
+    MTMC(prepare_slot(c, sl, src_rows, src_cols, chans, dtype, stream, factor, &g));
+    const size_t tight = (size_t)src_cols * chans * elem_size(dtype);
+    HIPC(hipMemcpy2DAsync(sl.raw.p, tight, src, (size_t)src_stride, tight, src_rows, hipMemcpyHostToDevice, stream));
+    return convert_raw(sl, g, src_cols, chans, dtype, stream, factor);
+}
+
+// n images of one shape as ONE image of n * rows rows (mtm_find_matches_batch): image b's rows are copied to rows
+// b * rows .. of the raw buffer - one 2-D copy each, from the caller's own rows and stride - and the planes are built over
+// the whole stack by the kernels upload_image runs.
+int upload_image_stack(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* const* px, int n, int64_t src_stride, int rows,
+                       int cols, int chans, int dtype, hipStream_t stream) {
+    SlotGeom g{};
+    MTMC(prepare_slot(c, sl, n * rows, cols, chans, dtype, stream, 1, &g));
+    const size_t tight = (size_t)cols * chans * elem_size(dtype);
+    for (int b = 0; b < n; ++b)
+        HIPC(hipMemcpy2DAsync(sl.raw.as<uint8_t>() + (size_t)b * rows * tight, tight, px[b], (size_t)src_stride, tight, rows,
+                              hipMemcpyHostToDevice, stream));
+    return convert_raw(sl, g, cols, chans, dtype, stream, 1);
 }
 
 void adopt_image(mtm_ctx* c, int rows, int cols, int chans, int dtype) {
@@ -415,6 +435,10 @@ int mtm_set_option(mtm_ctx* c, int option, int64_t value) {
             if (!dot_variant_ok(value)) break;
             c->dot_variant = (int)value;
             return MTM_OK;
+        case MTM_OPT_BATCH_MAX_ROWS:
+            if (value < 1 || value > kBatchMaxRows) break;
+            c->batch_max_rows = (int)value;
+            return MTM_OK;
         default: break;
     }
     set_error("mtm_set_option: bad option or value");
@@ -431,6 +455,7 @@ int mtm_get_option(mtm_ctx* c, int option, int64_t* value) {
         case MTM_OPT_HITS_ONLY: *value = c->hits_only; return MTM_OK;
         case MTM_OPT_F32_MFMA: *value = c->f32_mfma; return MTM_OK;
         case MTM_OPT_DOT4_VARIANT: *value = c->dot_variant; return MTM_OK;
+        case MTM_OPT_BATCH_MAX_ROWS: *value = c->batch_max_rows; return MTM_OK;
         default: break;
     }
     set_error("mtm_get_option: bad option");

@@ -56,6 +56,15 @@ using namespace mtm;
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// mtm_find_matches_batch stacks its images into one tall image.  The rows of one chunk are bounded by the tightest packing a
+// tall map can reach: launches with one grid row per map row (masksq_combine_kernel, slab_combine_kernel, the
+// masked float32 kernels: grid.y = oh) stay within 16 bits.  Looser ones: the candidate key (cand_key, the host's 3x3 table)
+// packs y into 21 bits; sort_hits' radix path needs y < 2^16 (per image after the split: it falls back to std::sort
+// otherwise); mtm_hit, map_off (64-bit) and the statistics pitch (columns) do not depend on the row count.
+constexpr int kBatchMaxRows = 65535;
+// ... and the device memory of a chunk (score maps of every template + image planes + statistics, per pixel) stays below this
+constexpr double kBatchChunkBytes = 8.0 * (1ull << 30);
+
 inline size_t elem_size(int dtype) { return dtype == MTM_U8 ? 1 : dtype == MTM_U16 ? 2 : 4; }
 
 struct DevBuf {
@@ -344,6 +353,7 @@ struct mtm_ctx {
                                // oracle; 0 = correctly rounded reciprocals (<= 1 ulp(float32) on ~1e-8 of the outputs); 2 = strict: also
                                // the fused extremum of masked classes (reciprocal-only kernels) goes through maps + extremum_kernel
     int auto_kernel = MTM_KERNEL_MFMA;   // what MTM_KERNEL_AUTO resolves to for uint8 classes (dot4 when not eligible)
+    int batch_max_rows = mtmi::kBatchMaxRows;  // MTM_OPT_BATCH_MAX_ROWS: most stacked image rows in one chunk of mtm_find_matches_batch
 
     mtm_timing timing{};
     std::vector<mtm_hit> last_hits;     // result of the last mtm_find_matches (for mtm_last_hits)
@@ -473,6 +483,8 @@ int upload_rows_u16c1(mtm_ctx::ImageSlot& sl, const SlotGeom& g, const void* src
                       hipStream_t stream, hipEvent_t copy_done = nullptr, hipEvent_t before_kernels = nullptr);
 int upload_image(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* src, int64_t src_stride, int src_rows, int src_cols,
                  int chans, int dtype, hipStream_t stream, int factor = 1);
+int upload_image_stack(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* const* px, int n, int64_t src_stride, int rows,
+                       int cols, int chans, int dtype, hipStream_t stream);
 void adopt_image(mtm_ctx* c, int rows, int cols, int chans, int dtype);
 int check_image_args(const void* px, int rows, int cols, int chans, int dtype, int64_t row_stride_bytes, const char* who);
 int ensure_f32_plane(mtm_ctx* c);

@@ -21,20 +21,26 @@ namespace mtm {
 // coalesced float4 load per lane (4 pixels), the horizontal neighbours come from the adjacent
 // lanes by shuffle (strip edges: two scalar loads), three rows of horizontal 3-maxima stay in
 // registers.  A work-group is 4 such strips stacked vertically.
-__global__ __launch_bounds__(256) void peaks_kernel(const float* __restrict__ maps,
-                                                    const TemplDev* __restrict__ td,
-                                                    const int* __restrict__ tlist, int mode_min,
-                                                    float thr, int border, mtm_hit* __restrict__ hits,
-                                                    unsigned long long cap,
-                                                    unsigned long long* __restrict__ counter,
-                                                    int* __restrict__ nontrivial) {
+// kSeam (mtm_find_matches_batch): the map belongs to a stack of images of img_rows rows each (image b = map rows
+// b img_rows ..).  Map row y is a window of image b = y / img_rows only if y % img_rows < oh_b = img_rows - h + 1; the other
+// h - 1 rows of each image straddle a seam: they are neither peaks nor neighbours - a row outside [b img_rows, b img_rows
+// + oh_b) is "outside the map" of image b and reads as the border rule's pad value.  nontrivial[b * n_templ + t] is kept
+// per image (plain stores of 1, one per lane and image: a strip spans several small images).  Maps whose per-image form is
+// a line (oh_b == 1) are the host's (find_peaks_1d).  kSeam = false is peaks_kernel as it was.
+template <bool kSeam>
+__device__ __forceinline__ void peaks_scan(const float* __restrict__ maps, const TemplDev* __restrict__ td,
+                                           const int* __restrict__ tlist, int mode_min, float thr, int border,
+                                           mtm_hit* __restrict__ hits, unsigned long long cap,
+                                           unsigned long long* __restrict__ counter, int* __restrict__ nontrivial,
+                                           int img_rows, int n_templ) {
     const int t = tlist[blockIdx.z];
     const TemplDev T = td[t];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int xs = blockIdx.x * kPkCols;
     const int y0 = (blockIdx.y * 4 + wave) * kPkRows;
     int nontriv = 0;
-    if (xs < T.ow && y0 < T.oh) {
+    const int oh_b = kSeam ? img_rows - T.rows + 1 : T.oh;
+    if (xs < T.ow && y0 < T.oh && (!kSeam || oh_b > 1)) {
         const float* m = maps + T.map_off;
         const float padv = (border == MTM_BORDER_CONSTANT) ? 0.0f : -INFINITY;
         const float thr2 = mode_min ? -thr : thr;
@@ -61,6 +67,11 @@ __global__ __launch_bounds__(256) void peaks_kernel(const float* __restrict__ ma
         peaks_finish_row(r1, lane, mode_min, vb, hl, hr);
         hmax(vb, hl, hr, hm_b);
         const int y1 = min(y0 + kPkRows, T.oh);
+        int img = 0, yl = 0, marked = -1;                     // (kSeam) image of row y, row inside it, last image flagged
+        if (kSeam) {
+            img = y0 / img_rows;
+            yl = y0 - img * img_rows;
+        }
         for (int y = y0; y < y1; ++y) {
             const PeakRow rn = peaks_fetch_row(m, T.map_pitch, T.oh, T.ow, y + 4, xb, lane, padr);
             peaks_finish_row(r2, lane, mode_min, vc, hl, hr);
@@ -68,14 +79,20 @@ __global__ __launch_bounds__(256) void peaks_kernel(const float* __restrict__ ma
             r3 = r4;
             r4 = rn;
             hmax(vc, hl, hr, hm_c);
+            const bool row_ok = !kSeam || yl < oh_b;
+            const bool top = kSeam && yl == 0, bottom = kSeam && yl == oh_b - 1;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int x = xb + k;
-                if (x < T.ow) {
+                if (x < T.ow && row_ok) {
                     const float v = vb[k];
-                    const float mx = fmaxf(fmaxf(hm_a[k], hm_b[k]), hm_c[k]);
+                    const float mx = fmaxf(fmaxf(top ? padv : hm_a[k], hm_b[k]), bottom ? padv : hm_c[k]);
                     if (!(v == mx)) {
                         nontriv = 1;
+                        if (kSeam && marked != img) {
+                            nontrivial[(size_t)img * n_templ + t] = 1;
+                            marked = img;
+                        }
                     } else if (v > thr2) {
                         const unsigned long long slot = atomicAdd(counter, 1ull);
                         if (slot < cap) {
@@ -97,9 +114,32 @@ __global__ __launch_bounds__(256) void peaks_kernel(const float* __restrict__ ma
                 hm_a[k] = hm_b[k];
                 hm_b[k] = hm_c[k];
             }
+            if (kSeam && ++yl == img_rows) {
+                yl = 0;
+                ++img;
+            }
         }
     }
-    if (__syncthreads_or(nontriv) && threadIdx.x == 0) nontrivial[t] = 1;
+    if (!kSeam && __syncthreads_or(nontriv) && threadIdx.x == 0) nontrivial[t] = 1;
+}
+
+__global__ __launch_bounds__(256) void peaks_kernel(const float* __restrict__ maps,
+                                                    const TemplDev* __restrict__ td,
+                                                    const int* __restrict__ tlist, int mode_min,
+                                                    float thr, int border, mtm_hit* __restrict__ hits,
+                                                    unsigned long long cap,
+                                                    unsigned long long* __restrict__ counter,
+                                                    int* __restrict__ nontrivial) {
+    peaks_scan<false>(maps, td, tlist, mode_min, thr, border, hits, cap, counter, nontrivial, 0, 0);
+}
+
+// The scan over the maps of a stack of images (mtm_find_matches_batch): peaks_scan<true>.  Records carry stack rows.
+__global__ __launch_bounds__(256) void peaks_batch_kernel(const float* __restrict__ maps, const TemplDev* __restrict__ td,
+                                                          const int* __restrict__ tlist, int mode_min, float thr, int border,
+                                                          mtm_hit* __restrict__ hits, unsigned long long cap,
+                                                          unsigned long long* __restrict__ counter,
+                                                          int* __restrict__ nontrivial, int img_rows, int n_templ) {
+    peaks_scan<true>(maps, td, tlist, mode_min, thr, border, hits, cap, counter, nontrivial, img_rows, n_templ);
 }
 
 // The same scan over the FLAGGED row segments only (MfmaParams::seg_flags): the score kernel set a flag per row segment -
@@ -475,6 +515,41 @@ __global__ __launch_bounds__(256) void extremum_kernel(const float* __restrict__
     }
 }
 
+// The same over a stack of images (mtm_find_matches_batch): one key pair per (image, template) - best[2 (b n_templ + t) + k],
+// grid (n_blocks_per_map, n_templ, images) - over the oh_b = img_rows - h + 1 map rows of image b, the index taken in that
+// image's own row-major order (first occurrence in the image wins, as cv2.minMaxLoc on the image alone).  Rows that straddle
+// a seam are never read.
+__global__ __launch_bounds__(256) void extremum_batch_kernel(const float* __restrict__ maps, const TemplDev* __restrict__ td,
+                                                             int img_rows, int n_blocks_per_map,
+                                                             unsigned long long* __restrict__ best) {
+    const int t = blockIdx.y, b = blockIdx.z;
+    const TemplDev T = td[t];
+    const long long n = (long long)(img_rows - T.rows + 1) * T.ow;
+    const float* m = maps + T.map_off + (size_t)b * img_rows * T.map_pitch;
+    unsigned long long kmax = 0ull, kmin = 0ull;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)n_blocks_per_map * 256) {
+        const int y = (int)(i / T.ow), x = (int)(i - (long long)y * T.ow);
+        const float v = m[(size_t)y * T.map_pitch + x];
+        if (v != v) continue;   // NaN never wins
+        const uint32_t o = float_order(v);
+        const uint32_t ri = 0xFFFFFFFFu - (uint32_t)i;
+        const unsigned long long a = ((unsigned long long)o << 32) | ri;
+        const unsigned long long c = ((unsigned long long)(~o) << 32) | ri;
+        kmax = a > kmax ? a : kmax;
+        kmin = c > kmin ? c : kmin;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long a = __shfl_down(kmax, off);
+        const unsigned long long c = __shfl_down(kmin, off);
+        kmax = a > kmax ? a : kmax;
+        kmin = c > kmin ? c : kmin;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        unsigned long long* out = best + 2 * ((size_t)b * gridDim.y + t);
+        if (kmax) atomicMax(&out[0], kmax);
+        if (kmin) atomicMax(&out[1], kmin);
+    }
+}
 
 // The candidate list of a hits-only call goes to the host's page-locked landing buffer from a kernel (one small
 // work-group behind the score launch) instead of a device-to-host copy command: a queued kernel starts the moment its

@@ -59,7 +59,7 @@ CallRoute plan_call(const mtm_ctx* c, int mode, float thr, bool banded) {
     R.n = n;
     R.thr = thr;
     R.mode_min = mode_min;
-    R.cand_cap = std::min<int64_t>(c->hit_cap, 4096LL * 256);
+    R.cand_cap = std::min<int64_t>(c->hit_cap, kCandListMax);
     R.banded_u8 = banded && c->dtype == MTM_U8;
     // masked float32 classes: the bf16 screen needs the threshold - local extrema, or (mbf_global) the templates' best
     // lower bounds and everything that reaches them; mtm_score_map keeps the float64 kernel.  What the peak pass compares

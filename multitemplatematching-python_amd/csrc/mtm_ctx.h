@@ -427,14 +427,23 @@ inline long long class_rm_pack_bytes(const SizeClass& sc) {
 }
 inline int bf16_nkb(int w) { return (w + 31) / 32; }
 inline long long bf16_group_bytes(int h, int w, int chans) { return (long long)chans * h * bf16_nkb(w) * 1024; }
-// dynamic LDS of one ncc_mfma_kernel work-group: image tile (aliased by the epilogue buffers), per-template constants,
-// work-group scratch words, prefetched statistics
-inline size_t mfma_lds_bytes(int tile_rows, int nb, size_t stat_bytes) {
-    const size_t lds_pitch = (size_t)(16 + 4 * nb + 1) * 16;
-    const size_t lds_main = (std::max<size_t>((size_t)tile_rows * lds_pitch, (size_t)kMfRows * kMfEpiBytesPerWave) + 15) & ~(size_t)15;
-    const size_t st_off = (lds_main + sizeof(MfTemplConst) * 32 + kMfItemBytes + 15) & ~(size_t)15;
-    return st_off + stat_bytes;
+// bytes per LDS image-tile row of an ncc_mfma_kernel work-group over `nb` 64-tap blocks (MfmaParams::lds_pitch)
+inline int mfma_lds_pitch(int nb) { return (16 + 4 * nb + 1) * 16; }
+// image rows of a row-multiplexed tile (R output rows per MFMA group): a chunk of the h + 2R - 1 rows a wave walks, and
+// 2R more for each further wave
+inline int rm_tile_rows(int h, int R) { return std::min(h + 2 * R - 1, kMfChunkH) + (kMfRows - 1) * 2 * R; }
+// templates per MFMA group of a row-multiplexed launch of n <= 16 templates h x w (R = 16 / nt rows each): the next power of
+// two, doubled while the tile needs more than 72 KB - two work-groups per CU need <= ~76 KB of LDS each
+inline int rm_group_templates(int n, int h, int w) {
+    int nt = 1;
+    while (nt < n) nt <<= 1;
+    const size_t lds_pitch = (size_t)mfma_lds_pitch((w + 63) / 64);
+    while (nt < 16 && (size_t)rm_tile_rows(h, 16 / nt) * lds_pitch > 72 * 1024) nt <<= 1;
+    return nt;
 }
+// longest candidate list a score kernel appends to (mtm_ctx::cands; a larger hit_cap only sizes the hit buffers)
+constexpr int64_t kCandListMax = 4096LL * 256;
+inline unsigned long long cand_list_cap(const mtm_ctx* c) { return (unsigned long long)std::min<int64_t>(c->hit_cap, kCandListMax); }
 
 // the image of a fused "upload + search" call (mtm_find_matches_image)
 struct ImageArgs {

@@ -40,6 +40,167 @@ MfmaFn mfma_raw_fn(bool row_mux, bool packed_k) {
     return mfma_kernel(s);
 }
 
+// work items in whole groups of 8 work-groups
+dim3 work_grid(int n_work) { return dim3((unsigned)(((n_work + 7) / 8) * 8)); }
+
+// the timing event pair `i` of `evs` (mtm_ctx::ncc_ev, sq_ev), created on first use
+int event_pair(std::vector<std::pair<hipEvent_t, hipEvent_t>>& evs, int i, std::pair<hipEvent_t, hipEvent_t>** out) {
+    if ((int)evs.size() <= i) {
+        hipEvent_t a, b;
+        HIPC(hipEventCreate(&a));
+        HIPC(hipEventCreate(&b));
+        evs.emplace_back(a, b);
+    }
+    *out = &evs[(size_t)i];
+    return MTM_OK;
+}
+
+// An ncc_mfma_kernel launch over an h x w template (or slab) and `chans` byte planes of the int8 image at `img`: the image
+// and tile fields every launch shares, everything else zero
+MfmaParams mfma_geometry(const uint8_t* img, const ImageDev& d, int chans, int h, int w, int oh, int ow, int method) {
+    MfmaParams p{};
+    p.img = img;
+    p.pitch = d.u8_pitch;
+    p.plane = d.u8_plane;
+    p.chans = chans;
+    p.h = h;
+    p.w = w;
+    p.oh = oh;
+    p.ow = ow;
+    p.nb = (w + 63) / 64;
+    p.nseg = (ow + kMfSeg - 1) / kMfSeg;
+    p.method = method;
+    p.lds_pitch = mfma_lds_pitch(p.nb);
+    p.cpr = p.lds_pitch / 16;
+    p.cpr_rstep = 256 / p.cpr;
+    p.cpr_dstep = 256 % p.cpr;
+    p.cpr_magic = 65536 / p.cpr + 1;
+    p.only_li = -1;
+    return p;
+}
+
+// image rows of a plain (one output row per wave) tile
+int plain_tile_rows(int h) { return std::min(h, kMfChunkH) + kMfRows - 1; }
+
+// LDS layout of an ncc_mfma_kernel work-group: the image tile of `tile_rows` rows (aliased by the epilogue's buffers,
+// `epi_bytes` per wave), the per-template constants, the work-group scratch words.  Returns the bytes up to st_off, where
+// the statistics prefetch region starts.
+size_t mfma_lds_layout(MfmaParams& p, int tile_rows, size_t epi_bytes) {
+    const size_t lds_main = (std::max<size_t>((size_t)tile_rows * p.lds_pitch, (size_t)kMfRows * epi_bytes) + 15) & ~(size_t)15;
+    p.tc_off = (int)lds_main;
+    p.st_off = (int)((lds_main + sizeof(MfTemplConst) * 32 + kMfItemBytes + 15) & ~(size_t)15);
+    return (size_t)p.st_off;
+}
+
+// row-multiplexed tiling, nt templates x R output rows per MFMA group: its fields and work grid.  Returns the tile rows.
+int mfma_row_mux(MfmaParams& p, int R, int nt) {
+    p.rm_R = R;
+    p.rm_nt = nt;
+    while ((1 << p.rm_log2nt) < nt) ++p.rm_log2nt;
+    p.rm_steps = p.h + 2 * R - 1;
+    p.nyb = (p.oh + 8 * R - 1) / (8 * R);
+    p.ntg = 1;
+    return rm_tile_rows(p.h, R);
+}
+
+// the candidate list (mtm_ctx::cands: a 16-byte header, then the records) a score kernel appends to, `cap` records long
+template <class P>
+void wire_candidates(P& p, const mtm_ctx* c, const CallRoute& R, unsigned long long cap) {
+    p.cand_on = R.cand_on ? 1 : 0;
+    p.hits_only = (p.cand_on && R.hits_only) ? 1 : 0;
+    p.cand_min = R.cand_min ? 1 : 0;
+    p.cand_thr = R.cand_thr;
+    p.cand_cap = cap;
+    p.cand_counter = c->cands.as<unsigned long long>();
+    p.cand_hits = reinterpret_cast<mtm_hit*>(c->cands.as<uint8_t>() + 16);
+}
+
+// ... of an ncc_mfma_kernel launch: with the hits-only screen's thresholds and the head of the list also into the host's
+// landing buffer
+void wire_mfma_candidates(MfmaParams& p, const mtm_ctx* c, const CallRoute& R, unsigned long long cap) {
+    wire_candidates(p, c, R, cap);
+    p.cand_thr_lo = (double)R.cand_thr - 1e-6 * std::max(1.0, std::fabs((double)R.cand_thr));
+    p.screen_hi = std::min(p.cand_thr_lo, 0.999999) - 1e-6;
+    p.sq_floor = 0.99 / std::sqrt((double)p.w * (double)p.h);
+    p.screen_l1 = c->screen_l1;
+    if (R.cand_pin && p.cand_on && c->pinned) {
+        p.cand_pin = reinterpret_cast<mtm_hit*>(static_cast<uint8_t*>(c->pinned) + 16);
+        p.cand_pin_n = (unsigned long long)R.cand_pin_n;
+    }
+}
+
+// The fused global extremum (keys instead of maps or candidates: 4 waves x 32 in LDS) or else, with a candidate list, the
+// wave-private candidate staging buffers (see emit_at), behind the first `lds` bytes.  Returns the work-group's LDS bytes.
+size_t mfma_ext_or_staging(MfmaParams& p, const mtm_ctx* c, bool ext, size_t lds) {
+    if (ext) {
+        p.ext_off = (int)lds;
+        lds += (size_t)kMfRows * 32 * sizeof(unsigned long long);
+        p.ext_best = c->counters.as<unsigned long long>();
+        p.cand_on = 1;
+        p.hits_only = 1;
+    } else if (p.cand_on) {
+        lds = (lds + 15) & ~(size_t)15;
+        p.cs_off = (int)lds;
+        lds += (size_t)kMfRows * kMfCandStageBytes;
+    }
+    return lds;
+}
+
+// An ncc_bf16_kernel launch over the class's templates in groups of 16 mb (`group_bytes` per group and piece) and `chans`
+// float32 planes of the image: geometry and work grid, everything else zero
+Bf16Params bf16_geometry(const mtm_ctx* c, const SizeClass& sc, int chans, int mb, long long group_bytes, int method) {
+    const ImageDev d = image_dev(c);
+    const int n = (int)sc.members.size();
+    Bf16Params p{};
+    p.img = d.f32;
+    p.pitch = d.f32_pitch;
+    p.plane = d.f32_plane;
+    p.chans = chans;
+    p.rows = c->rows;
+    p.cols = c->cols;
+    p.h = sc.h;
+    p.w = sc.w;
+    p.oh = c->rows - sc.h + 1;
+    p.ow = c->cols - sc.w + 1;
+    p.nkb = bf16_nkb(sc.w);
+    p.chunk_h = p.nkb <= 2 ? 64 : 32;
+    p.lds_cols = kBfSeg + 32 * p.nkb;
+    p.n_list = n;
+    p.nseg = (p.ow + kBfSeg - 1) / kBfSeg;
+    p.nyb = (p.oh + kBfRows - 1) / kBfRows;
+    p.ntg = (n + 16 * mb - 1) / (16 * mb);
+    p.method = method;
+    p.group_bytes = group_bytes;
+    p.piece_bytes = group_bytes * mfma_groups_alloc(n);
+    p.only_li = -1;
+    p.n_work = p.nseg * p.nyb * p.ntg;
+    return p;
+}
+
+// A launch of dot4 kernel variant `v` over n_list templates h x w and `chans` planes of the uint8 image
+DotParams dot_params(const mtm_ctx* c, const DotVariant& v, int chans, int h, int w, int n_list) {
+    const ImageDev d = image_dev(c);
+    DotParams p{};
+    p.img = d.u8;
+    p.pitch = d.u8_pitch;
+    p.plane = d.u8_plane;
+    p.chans = chans;
+    p.h = h;
+    p.w = w;
+    p.oh = c->rows - h + 1;
+    p.ow = c->cols - w + 1;
+    const int w4 = (w + 3) & ~3;
+    p.ncy = (h + kDotChunk - 1) / kDotChunk;
+    p.ncx = (w4 + kDotChunk - 1) / kDotChunk;
+    p.n_list = n_list;
+    p.ntx = (p.ow + 32 * v.px - 1) / (32 * v.px);
+    p.nty = (p.oh + 8 * v.py - 1) / (8 * v.py);
+    p.nchunks = (n_list + v.nt - 1) / v.nt;
+    p.n_work = p.ntx * p.nty * p.nchunks;
+    p.method = c->method;
+    return p;
+}
+
 }  // namespace
 
 namespace mtmi {
@@ -64,6 +225,8 @@ int ensure_square_planes(mtm_ctx* c) {
     c->sq_valid = true;
     return MTM_OK;
 }
+
+static int launch_masked_sumsq(mtm_ctx* c, const SizeClass& sc, bool fused_stats, const StatPlanes& st, double* sum2);
 
 // Window statistics of one size class (two kernels), into c->stats.  Returns the plane table.
 // `sb0`, `sb1`: range of kStatBand4-row output blocks to compute (banded image upload; fused single-channel
@@ -220,76 +383,54 @@ int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out,
     for (int k = 0; k < kMaxChans; ++k) st.t[k] = tp[k];
     st.sum2 = sum2;
     st.sq = sq;
-    if (masked_mfma && sc.mask_rm_off >= 0 && fused_stats) {
-        // sum I^2 * M over every window on the matrix cores (see square_planes_kernel): two row-multiplexed
-        // raw correlations of the byte planes of I^2 with the mask, combined into the sum2 plane
+    if (masked_mfma) MTMC(launch_masked_sumsq(c, sc, fused_stats, st, sum2));
+    *out = st;
+    return MTM_OK;
+}
+
+// sum I^2 * M over every window of a masked uint8 class on the MFMA kernel, into `sum2`, the sum2 plane of `st` (it
+// overwrites the unmasked window sum of squares, which the masked path never uses).  `fused_stats`: launch_stats ran the
+// fused kernel.
+static int launch_masked_sumsq(mtm_ctx* c, const SizeClass& sc, bool fused_stats, const StatPlanes& st, double* sum2) {
+    const int h = sc.h, w = sc.w, oh = c->rows - h + 1, ow = c->cols - w + 1;
+    const ImageDev img = image_dev(c);
+    if (sc.mask_rm_off >= 0 && fused_stats) {
+        // on the matrix cores (see square_planes_kernel): two row-multiplexed raw correlations of the byte planes of I^2
+        // with the mask, combined into the sum2 plane
         const size_t plane_bytes = (size_t)img.u8_plane;
         MTMC(ensure_square_planes(c));
         const int map_pitch = (int)round_up((size_t)ow, 4);
         const long long raw_map = (long long)oh * map_pitch;
         const bool fused_sq = c->masksq_fused != 0;
         if (!fused_sq) MTMC(c->raw16.ensure(sizeof(int) * (size_t)(2 * raw_map)));
-        MfmaParams p{};
-        p.pitch = img.u8_pitch;
-        p.plane = img.u8_plane;
-        p.chans = 1;
-        p.h = h;
-        p.w = w;
-        p.oh = oh;
-        p.ow = ow;
-        p.nb = (w + 63) / 64;
+        MfmaParams p = mfma_geometry(nullptr, img, 1, h, w, oh, ow, c->method);
+        const size_t lds = mfma_lds_layout(p, mfma_row_mux(p, 16, 1), kMfEpiBytesPerWave);
         p.n_list = 1;
-        p.rm_R = 16;
-        p.rm_nt = 1;
-        p.rm_log2nt = 0;
-        p.rm_steps = h + 2 * 16 - 1;
-        p.nseg = (ow + kMfSeg - 1) / kMfSeg;
-        p.nyb = (oh + 8 * 16 - 1) / (8 * 16);
-        p.ntg = 1;
         p.n_work = p.nseg * p.nyb;
-        p.method = method;
-        p.lds_pitch = (16 + 4 * p.nb + 1) * 16;
-        p.cpr = p.lds_pitch / 16;
-        p.cpr_rstep = 256 / p.cpr;
-        p.cpr_dstep = 256 % p.cpr;
-        p.cpr_magic = 65536 / p.cpr + 1;
         p.group_bytes = -(long long)16 * p.nb * 1024;
-        p.only_li = -1;
         p.raw_map = raw_map;
         p.raw_pitch = map_pitch;
-        const int tile_rows = std::min(p.rm_steps, kMfChunkH) + (kMfRows - 1) * 2 * 16;
-        const size_t lds_main = (std::max<size_t>((size_t)tile_rows * p.lds_pitch, (size_t)kMfRows * kMfEpiBytesPerWave) + 15) &
-                                ~(size_t)15;
-        p.tc_off = (int)lds_main;
-        p.st_off = (int)((lds_main + sizeof(MfTemplConst) * 32 + kMfItemBytes + 15) & ~(size_t)15);
-        const size_t lds = (size_t)p.st_off;
         const uint8_t* ap = c->apacks.as<uint8_t>() + sc.mask_rm_off + (long long)16 * p.nb * 1024;
-        const int grid = ((p.n_work + 7) / 8) * 8;
         const double km257 = 257.0 * 128.0 * sc.mask_ones;      // the mask operand is not biased
         // the pass is part of the masked class's score work: its own event pair (bench.py: roofline.masked_stat)
-        if ((int)c->sq_ev.size() <= c->timing.sq_launches) {
-            hipEvent_t a, b;
-            HIPC(hipEventCreate(&a));
-            HIPC(hipEventCreate(&b));
-            c->sq_ev.emplace_back(a, b);
-        }
-        auto& sqe = c->sq_ev[(size_t)c->timing.sq_launches];
-        HIPC(hipEventRecord(sqe.first, c->stream));
+        std::pair<hipEvent_t, hipEvent_t>* sqe;
+        MTMC(event_pair(c->sq_ev, c->timing.sq_launches, &sqe));
+        HIPC(hipEventRecord(sqe->first, c->stream));
         if (fused_sq) {
             // ONE launch: the byte planes of I^2 are its two channels, the epilogue writes sum2 and the block minima
+            // (the kernel's output planes travel in the plane table)
             p.chans = 2;
             p.img = c->sq_planes.as<uint8_t>();
             p.plane = (long long)plane_bytes;
             p.sq_fused = 1;
             p.sq_k = km257;
-            st.sum2 = sum2;             // (the kernel's output planes travel in the plane table)
-            hipLaunchKernelGGL(mfma_raw_fn(true, false), dim3(grid), dim3(256), lds, c->stream, p,
+            hipLaunchKernelGGL(mfma_raw_fn(true, false), work_grid(p.n_work), dim3(256), lds, c->stream, p,
                                c->td.as<TemplDev>(), c->tlist.as<int>(), ap, st, c->maps.as<float>());
         } else {
             for (int x = 0; x < 2; ++x) {
                 p.img = c->sq_planes.as<uint8_t>() + (size_t)x * plane_bytes;
                 p.raw_out = c->raw16.as<int>() + (size_t)x * raw_map;
-                hipLaunchKernelGGL(mfma_raw_fn(true, false), dim3(grid), dim3(256), lds, c->stream, p,
+                hipLaunchKernelGGL(mfma_raw_fn(true, false), work_grid(p.n_work), dim3(256), lds, c->stream, p,
                                    c->td.as<TemplDev>(), c->tlist.as<int>(), ap, st, c->maps.as<float>());
             }
             hipLaunchKernelGGL(masksq_combine_kernel, dim3((ow + 255) / 256, oh), dim3(256), 0, c->stream, c->raw16.as<int>(),
@@ -297,49 +438,29 @@ int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out,
                                const_cast<double*>(st.blk), st.blk_pitch);
         }
         HIPC(hipGetLastError());
-        HIPC(hipEventRecord(sqe.second, c->stream));
+        HIPC(hipEventRecord(sqe->second, c->stream));
         c->timing.sq_launches++;
-    } else if (masked_mfma) {
-        // sum I^2 * M over every window: dot4 kernel with the mask bytes as the "template", into the
-        // sum2 plane (overwrites the unmasked window sum of squares, which the masked path never uses)
-        if (sc.mask_pack_off < 0) {
-            set_error("internal: masked class without a dot4 mask pack");
-            return MTM_E_STATE;
-        }
-        const DotVariant v = {4, 4, 1, false, ncc_dot4_kernel<4, 4, 1, false, true>};
-        DotParams p{};
-        p.img = img.u8;
-        p.pitch = img.u8_pitch;
-        p.plane = img.u8_plane;
-        p.chans = 1;
-        p.h = h;
-        p.w = w;
-        p.oh = oh;
-        p.ow = ow;
-        const int w4 = (w + 3) & ~3;
-        p.ncy = (h + kDotChunk - 1) / kDotChunk;
-        p.ncx = (w4 + kDotChunk - 1) / kDotChunk;
-        p.n_list = 1;
-        p.ntx = (ow + 32 * v.px - 1) / (32 * v.px);
-        p.nty = (oh + 8 * v.py - 1) / (8 * v.py);
-        p.nchunks = 1;
-        p.n_work = p.ntx * p.nty;
-        p.method = method;
-        p.sumsq_out = sum2;
-        // the kernel addresses its single template through td[tlist[0]].pack_off: point a scratch
-        // TemplDev at the class's mask pack (only pack_off is read on the MASKSQ path)
-        TemplDev mk = c->td_host[sc.members[0]];
-        mk.pack_off = sc.mask_pack_off;
-        MTMC(c->mask_td.ensure(sizeof(TemplDev) + sizeof(int)));
-        HIPC(hipMemcpyAsync(c->mask_td.p, &mk, sizeof(TemplDev), hipMemcpyHostToDevice, c->stream));
-        HIPC(hipMemsetAsync(c->mask_td.as<uint8_t>() + sizeof(TemplDev), 0, sizeof(int), c->stream));
-        const int grid = ((p.n_work + 7) / 8) * 8;
-        hipLaunchKernelGGL(v.fn, dim3(grid), dim3(256), 0, c->stream, p, c->mask_td.as<TemplDev>(),
-                           reinterpret_cast<const int*>(c->mask_td.as<uint8_t>() + sizeof(TemplDev)),
-                           c->packs.as<uint8_t>(), st, c->maps.as<float>());
-        HIPC(hipGetLastError());
+        return MTM_OK;
     }
-    *out = st;
+    // otherwise the dot4 kernel with the mask bytes as the "template"
+    if (sc.mask_pack_off < 0) {
+        set_error("internal: masked class without a dot4 mask pack");
+        return MTM_E_STATE;
+    }
+    const DotVariant v = {4, 4, 1, false, ncc_dot4_kernel<4, 4, 1, false, true>};
+    DotParams p = dot_params(c, v, 1, h, w, 1);
+    p.sumsq_out = sum2;
+    // the kernel addresses its single template through td[tlist[0]].pack_off: point a scratch
+    // TemplDev at the class's mask pack (only pack_off is read on the MASKSQ path)
+    TemplDev mk = c->td_host[sc.members[0]];
+    mk.pack_off = sc.mask_pack_off;
+    MTMC(c->mask_td.ensure(sizeof(TemplDev) + sizeof(int)));
+    HIPC(hipMemcpyAsync(c->mask_td.p, &mk, sizeof(TemplDev), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemsetAsync(c->mask_td.as<uint8_t>() + sizeof(TemplDev), 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL(v.fn, work_grid(p.n_work), dim3(256), 0, c->stream, p, c->mask_td.as<TemplDev>(),
+                       reinterpret_cast<const int*>(c->mask_td.as<uint8_t>() + sizeof(TemplDev)),
+                       c->packs.as<uint8_t>(), st, c->maps.as<float>());
+    HIPC(hipGetLastError());
     return MTM_OK;
 }
 
@@ -386,36 +507,14 @@ static int launch_masked_bf16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, flo
     // the two raw launches
     MTMC(c->mbf_maps.ensure(sizeof(float) * 2 * std::max<size_t>(4, c->maps_floats)));
     const int mb = n_all > 16 ? 2 : 1;
-    Bf16Params p{};
-    p.pitch = img.f32_pitch;
-    p.plane = img.f32_plane;
-    p.chans = 1;
-    p.rows = c->rows;
-    p.cols = c->cols;
-    p.h = h;
-    p.w = w;
-    p.oh = oh;
-    p.ow = ow;
-    p.nkb = bf16_nkb(w);
-    p.chunk_h = p.nkb <= 2 ? 64 : 32;
-    p.lds_cols = kBfSeg + 32 * p.nkb;
-    p.n_list = n_all;
-    p.nseg = (ow + kBfSeg - 1) / kBfSeg;
-    p.nyb = (oh + kBfRows - 1) / kBfRows;
-    p.ntg = (n_all + 16 * mb - 1) / (16 * mb);
-    p.method = MTM_TM_CCORR;                                    // raw sums: acc + centre * S1
-    p.group_bytes = sc.mbf_group_bytes;
-    p.piece_bytes = sc.mbf_group_bytes * mfma_groups_alloc(n_all);
-    p.only_li = -1;
-    p.n_work = p.nseg * p.nyb * p.ntg;
+    Bf16Params p = bf16_geometry(c, sc, 1, mb, sc.mbf_group_bytes, MTM_TM_CCORR);      // raw sums: acc + centre * S1
     const size_t n_tiles = (size_t)p.nseg * p.nyb;
     MTMC(c->mbf_mu.ensure(sizeof(float) * 2 * n_tiles));
     const size_t lds = bf16_lds_bytes(p.chunk_h, p.lds_cols);
-    const int grid = ((p.n_work + 7) / 8) * 8;
     const int* tl_k = c->tlist.as<int>() + sc.tlist_off;
     StatPlanes st{};
     st.pitch = st_pitch;
-    const unsigned long long cap = (unsigned long long)std::min<int64_t>(std::max<int64_t>(c->hit_cap, 1 << 18), 4096LL * 256);
+    const unsigned long long cap = (unsigned long long)std::min<int64_t>(std::max<int64_t>(c->hit_cap, 1 << 18), kCandListMax);
     MTMC(c->mbf_list.ensure(16 + sizeof(mtm_hit) * (size_t)cap));
     MaskF32Params q{};
     unsigned long long count = 0;
@@ -430,7 +529,8 @@ static int launch_masked_bf16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, flo
         st.sq = st.sum2;                                        // (not read by a raw-sum launch)
         const uint8_t* ap = c->apacks.as<uint8_t>() + (pl == 0 ? sc.mbf_off_u : sc.mbf_off_v);
         const TemplDev* tdp = (pl == 0 ? c->td_u : c->td_v).as<TemplDev>();
-        hipLaunchKernelGGL(bf16_kernel(mb, np), dim3(grid), dim3(256), lds, c->stream, p, tdp, tl_k, ap, st, c->mbf_maps.as<float>());
+        hipLaunchKernelGGL(bf16_kernel(mb, np), work_grid(p.n_work), dim3(256), lds, c->stream, p, tdp, tl_k, ap, st,
+                           c->mbf_maps.as<float>());
     }
     c->timing.f32_pieces = np;
     // combine: placeholders into the score maps, the rest listed
@@ -506,550 +606,416 @@ static int launch_masked_bf16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, flo
     return MTM_OK;
 }
 
-// Score maps of `n_list` templates of class `sc` (device list at tlist + list_off).
-// `yb0`, `yb1`: range of output row blocks (MFMA kernel only; banded image upload), yb1 < 0 = all.
-int launch_ncc(mtm_ctx* c, CallRoute& R, const SizeClass& sc, int list_off, int n_list, const StatPlanes& st, int only_li,
-               int yb0, int yb1) {
-    const int h = sc.h, w = sc.w;
-    const int oh = c->rows - h + 1, ow = c->cols - w + 1;
+// naive kernel (float64 accumulation straight from the image: MTM_KERNEL_NAIVE)
+static int launch_naive(mtm_ctx* c, const SizeClass& sc, const int* tl, int n_list, const StatPlanes& st) {
+    const int oh = c->rows - sc.h + 1, ow = c->cols - sc.w + 1;
+    MTMC(ensure_f32_plane(c));
+    hipLaunchKernelGGL(ncc_naive_kernel, dim3((ow + 63) / 64, (oh + 3) / 4, n_list), dim3(64, 4), 0, c->stream, image_dev(c),
+                       c->td.as<TemplDev>(), tl, c->weights.as<double>(), st, c->method, sc.masked ? 1 : 0, c->maps.as<float>());
+    c->timing.kernel_used = MTM_KERNEL_NAIVE;
+    return MTM_OK;
+}
+
+// Large templates on the MFMA kernel: one RAW launch per slab (a template of its own against the image shifted by the
+// slab's offset), then slab_combine_kernel adds the slabs up, restores the bias terms and normalises.  *ev_own: the
+// timing pair `ev` went to the side stream of a merged launch (on the score stream it would bracket the fork and the
+// join, not the launch).
+static int launch_mfma_slabs(mtm_ctx* c, CallRoute& R, const SizeClass& sc, const StatPlanes& st, int only_li,
+                             const std::pair<hipEvent_t, hipEvent_t>& ev, bool* ev_own) {
+    const int h = sc.h, w = sc.w, oh = c->rows - h + 1, ow = c->cols - w + 1;
     const ImageDev img = image_dev(c);
-    const int* tl = c->tlist.as<int>() + list_off;
     const TemplDev* td = c->td.as<TemplDev>();
     float* maps = c->maps.as<float>();
-    const int kernel = resolved_kernel(c, sc);      // the same decision place_templates packed for
-
-    // timing events around the dominant kernel
-    if ((int)c->ncc_ev.size() <= c->timing.ncc_launches) {
-        hipEvent_t a, b;
-        HIPC(hipEventCreate(&a));
-        HIPC(hipEventCreate(&b));
-        c->ncc_ev.emplace_back(a, b);
+    const hipStream_t ncc_s = c->stream;
+    const int n_all = (int)sc.members.size();
+    const int map_pitch = (int)round_up((size_t)ow, 4);
+    const long long raw_map = (long long)oh * map_pitch;
+    const int S = (int)sc.slabs.size();
+    MTMC(c->slab_raw.ensure(sizeof(int) * (size_t)S * n_all * (size_t)raw_map));
+    const bool rmr = sc.slab_R > 0;
+    // The slabs' launches are independent.  One of them is (output rows / 8R) x (columns / 256) work items - 91 for the
+    // reference's own benchmark shape (2048^2 image, one 414 x 400 template: four slabs), against 512 resident
+    // work-group slots: launches that do not fill the chip twice over run side by side on up to slab_concurrency
+    // streams, forked from and joined into the score stream.
+    int n_side = 1;
+    {
+        const int rows_per_item = rmr ? 8 * sc.slab_R : kMfRows;
+        const long long items = (long long)((ow + kMfSeg - 1) / kMfSeg) * ((oh + rows_per_item - 1) / rows_per_item) *
+                                (rmr ? 1 : (n_all + 31) / 32);
+        const int cus = c->n_cus > 0 ? c->n_cus : 256;
+        if (items < 4LL * cus) n_side = (int)std::min<long long>(std::min(S, kSlabStreams), (4LL * cus + items - 1) / items);
     }
-    auto& evp = c->ncc_ev[c->timing.ncc_launches];
-    hipStream_t ncc_s = c->stream;
+    // MTM_SLAB_MERGE (default 1): slabs of equal height and block count go out as ONE launch (MfmaParams::n_slab) - the
+    // hardware fills the chip from one grid and back-fills as work-groups finish, where several launches on several
+    // streams share four hardware queues (the fourth of four side-by-side slab launches started when the first had
+    // ended: profiles/r04_r04v_slab) - on one side stream, so that the statistics pass still runs under it.
+    bool merged = rmr && S > 1;
+    for (int k = 1; k < S && merged; ++k) {
+        const SizeClass::Slab &a = sc.slabs[0], &b = sc.slabs[(size_t)k];
+        merged = (b.r1 - b.r0) == (a.r1 - a.r0) && (b.c1 - b.c0 + 63) / 64 == (a.c1 - a.c0 + 63) / 64 &&
+                 b.apack_off - a.apack_off == (long long)k * rm_pack_bytes(a.r1 - a.r0, a.c1 - a.c0, sc.slab_R);
+    }
+    if (merged) n_side = c->slab_fork_early ? 2 : 1;        // (2: "side streams in use"; only the first one is)
+    if (n_side > 1) {
+        while ((int)c->slab_streams.size() < n_side) {
+            hipStream_t s2;
+            hipEvent_t e2;
+            HIPC(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
+            HIPC(hipEventCreateWithFlags(&e2, hipEventDisableTiming));
+            c->slab_streams.push_back(s2);
+            c->slab_done.push_back(e2);
+        }
+        if (!c->slab_fork) HIPC(hipEventCreateWithFlags(&c->slab_fork, hipEventDisableTiming));
+        if (!c->slab_fork_early) HIPC(hipEventRecord(c->slab_fork, ncc_s));      // (else: recorded ahead of the statistics)
+        for (int i = 0; i < n_side; ++i) HIPC(hipStreamWaitEvent(c->slab_streams[(size_t)i], c->slab_fork, 0));
+    }
+    for (int k = 0; k < (merged ? 1 : S); ++k) {
+        const SizeClass::Slab& sl = sc.slabs[(size_t)k];
+        const int hs = sl.r1 - sl.r0, ws = sl.c1 - sl.c0;
+        hipStream_t slab_s = n_side > 1 ? c->slab_streams[(size_t)(merged ? 0 : k % n_side)] : ncc_s;
+        MfmaParams p = mfma_geometry(c->slot[c->cur].u8b.as<uint8_t>() + (size_t)sl.ch * img.u8_plane + (size_t)sl.r0 * img.u8_pitch + sl.c0,
+                                     img, 1, hs, ws, oh, ow, c->method);
+        p.n_list = n_all;
+        p.raw_map = raw_map;
+        p.raw_pitch = map_pitch;
+        p.raw_out = c->slab_raw.as<int>() + (size_t)k * n_all * (size_t)raw_map;
+        int tile_rows;
+        if (rmr) {
+            tile_rows = mfma_row_mux(p, sc.slab_R, sc.slab_nt);
+            p.rm_cstride = rm_pack_bytes(hs, ws, sc.slab_R);
+            p.group_bytes = -(long long)sc.slab_R * p.nb * 1024;
+        } else {
+            p.nyb = (oh + kMfRows - 1) / kMfRows;
+            p.ntg = (n_all + 31) / 32;
+            p.group_bytes = mfma_group_bytes(hs, ws, 1);
+            tile_rows = plain_tile_rows(hs);
+        }
+        p.n_work = p.nseg * p.nyb * p.ntg;
+        if (merged) {                       // every slab of the class: slab 0's geometry (the widest), S times the items
+            int ncb = 0;
+            for (const auto& q : sc.slabs) ncb += (q.ch == sl.ch && q.r0 == sl.r0) ? 1 : 0;
+            p.n_slab = S;
+            p.slab_ncb = ncb;
+            p.slab_nrb = S / (ncb * c->chans);
+            p.slab_cw = ncb > 1 ? sc.slabs[1].c0 - sl.c0 : 0;
+            p.slab_rh = hs;
+            p.slab_ap_step = rm_pack_bytes(hs, ws, sc.slab_R);
+            p.slab_raw_step = (long long)n_all * raw_map;
+            p.n_work *= S;
+        }
+        // statistics prefetch region: none for the row-multiplexed launches (differs by tiling; this code does not decide whether it should)
+        const size_t lds = mfma_lds_layout(p, tile_rows, kMfEpiBytesPerWave) + (rmr ? 0 : (size_t)kMfRows * kMfStatBytesPerWave);
+        const uint8_t* ap = c->apacks.as<uint8_t>() + sl.apack_off + (rmr ? (long long)sc.slab_R * p.nb * 1024 : 0);
+        if (merged && slab_s != ncc_s) HIPC(hipEventRecord(ev.first, slab_s));
+        hipLaunchKernelGGL(mfma_raw_fn(rmr, false), work_grid(p.n_work), dim3(256), lds, slab_s, p, td,
+                           c->tlist.as<int>() + sc.tlist_off, ap, st, maps);
+        if (merged && slab_s != ncc_s) {
+            HIPC(hipEventRecord(ev.second, slab_s));
+            *ev_own = true;
+        }
+    }
+    for (int i = 0; i < (merged ? 1 : n_side) && n_side > 1; ++i) {
+        HIPC(hipEventRecord(c->slab_done[(size_t)i], c->slab_streams[(size_t)i]));
+        HIPC(hipStreamWaitEvent(ncc_s, c->slab_done[(size_t)i], 0));
+    }
+    SlabParams q{};
+    q.raw = c->slab_raw.as<int>();
+    q.raw_slab = (long long)n_all * raw_map;
+    q.raw_map = raw_map;
+    q.n_slabs = S;
+    q.oh = oh;
+    q.ow = ow;
+    q.pitch = map_pitch;
+    q.n_list = n_all;
+    q.method = c->method;
+    q.w = w;
+    q.h = h;
+    q.chans = c->chans;
+    wire_candidates(q, c, R, cand_list_cap(c));     // (cand_cap differs from the plain int8 launch; not decided here)
+    if (R.ext) {                                  // fused global extremum: keys instead of maps / candidates
+        q.ext_on = 1;
+        q.ext_best = c->counters.as<unsigned long long>();
+        q.cand_on = 0;
+        q.hits_only = 1;
+    }
+    hipLaunchKernelGGL(slab_combine_kernel, dim3((ow + 255) / 256, oh, n_all), dim3(256), 0, c->stream, q, td,
+                       c->tlist.as<int>() + sc.tlist_off, st, maps, only_li);
+    c->timing.kernel_used = MTM_KERNEL_MFMA;
+    return MTM_OK;
+}
+
+// uint8 classes on the MFMA kernel: plain, two-row (r2) or row-multiplexed tiling.  The kernel works on whole 16-template
+// groups of the class list; a single-template request (mtm_score_map) computes its group and stores only that template.
+static int launch_mfma(mtm_ctx* c, CallRoute& R, const SizeClass& sc, const StatPlanes& st, int only_li, int yb0, int yb1) {
+    const int h = sc.h, w = sc.w, oh = c->rows - h + 1, ow = c->cols - w + 1;
+    const int n_all = (int)sc.members.size();
+    const bool rm = sc.rm_R > 0;
+    const bool r2 = sc.r2 > 0;
+    const int mb = r2 ? sc.r2 : (n_all > 16 || rm) ? 2 : 1;
+    const int tgsz = r2 ? 16 : 16 * mb;          // templates per work item
+    // (the int8 view: bytes ^ 0x80, same geometry as img.u8)
+    MfmaParams p = mfma_geometry(c->slot[c->cur].u8b.as<uint8_t>(), image_dev(c), c->chans, h, w, oh, ow, c->method);
+    p.nyb = r2 ? (oh + mb * kMfRows - 1) / (mb * kMfRows) : (oh + kMfRows - 1) / kMfRows;
+    p.ntg = (n_all + tgsz - 1) / tgsz;
+    p.group_bytes = sc.group_bytes;
+    // (cand_cap is the whole hit_cap here, min(hit_cap, kCandListMax) on the other launches: differs; not decided here)
+    wire_mfma_candidates(p, c, R, (unsigned long long)c->hit_cap);
+    // the 8 spare bytes of the candidate header - or of the host's landing buffer - carry the shader clock the kernel
+    // measured (fetched with it).  (Only this launch sets clk_out: differs; not decided here.)
+    if (p.cand_pin)
+        p.clk_out = reinterpret_cast<float*>(static_cast<uint8_t*>(c->pinned) + 8);
+    else if (p.cand_on && c->cands.p)
+        p.clk_out = reinterpret_cast<float*>(c->cands.as<uint8_t>() + 8);
+    if (R.sparse) {                         // maps in memory + a flag per row segment that holds something above the threshold
+        p.seg_flags = c->seg_flags.as<uint8_t>();
+        p.flag_tstride = R.flag_tstride;
+        p.flag_rstride = R.flag_rstride;
+        const bool normed_m = c->method == MTM_TM_SQDIFF_NORMED || c->method == MTM_TM_CCORR_NORMED || c->method == MTM_TM_CCOEFF_NORMED;
+        p.seg_skip = (c->seg_skip && !sc.masked && normed_m) ? 1 : 0;
+        R.seg_skip_used = R.seg_skip_used || p.seg_skip != 0;
+    }
+    int tg0 = 0;
+    if (only_li >= 0 && !rm) {   // one template: just its group
+        tg0 = only_li / tgsz;
+        p.ntg = 1;
+    }
+    int tile_rows = r2 ? std::min(h + mb - 1, kMfChunkR2) + (kMfRows - 1) * mb : plain_tile_rows(h);
+    if (rm) {
+        tile_rows = mfma_row_mux(p, sc.rm_R, sc.rm_nt);
+        p.rm_cstride = class_rm_pack_bytes(sc);
+        p.rm_rsq = c->stats_rsq.as<double>();
+    }
+    if (yb1 >= 0) {                     // banded launch: row blocks yb0 .. yb1 - 1 (the caller keeps the range non-empty)
+        p.yb0 = yb0;
+        p.nyb = std::min(yb1, p.nyb) - yb0;
+    }
+    p.n_work = p.nseg * p.nyb * p.ntg;
+    // statistics prefetch region: (channels + 2) planes per wave; none for the row-multiplexed tiling (it loads its
+    // statistics directly), (mb + 1) / 2 KB per wave for the two-row one (differs by tiling; not decided here)
+    const size_t stat_bytes = rm ? 0 : r2 ? (size_t)kMfRows * ((mb + 1) / 2) * 1024
+                                          : (size_t)kMfRows * mf_stat_bytes_per_wave(c->chans == 3 ? 3 : 1);
+    const bool ext = R.ext;                          // plan_call checked the class
+    const size_t lds = mfma_ext_or_staging(p, c, ext, mfma_lds_layout(p, tile_rows, kMfEpiBytesPerWave) + stat_bytes);
+    p.kp_nseg = sc.kp_nseg;
+    p.kp_blocks = sc.kp_nseg ? kp_blocks(h, sc.kp_nseg) : 0;
+    const uint8_t* ap = c->apacks.as<uint8_t>() + sc.apack_off +
+                        (rm ? (sc.kp_nseg ? 0LL : (long long)sc.rm_R * p.nb * 1024)
+                            : (long long)tg0 * (r2 ? 1 : mb) * sc.group_bytes);
+    // with a group offset the kernel's list positions must stay class-relative: shift the list
+    // pointer and the counts instead (positions inside the kernel are relative to tg0)
+    p.n_list = n_all - tg0 * tgsz;
+    if (only_li >= 0) p.only_li = only_li - tg0 * tgsz;
+    const int* tl_k = c->tlist.as<int>() + sc.tlist_off + tg0 * tgsz;
+    // the instantiation of ncc_mfma_kernel for this class (the kernels live in the mtm_mfma_*.hip units)
+    MfmaSel sel;
+    sel.mb = mb;
+    sel.masked = sc.masked;
+    sel.rm = rm;
+    sel.ch = (c->chans == 3 && !sc.masked) ? 3 : 1;
+    sel.method = (c->chans == 1 || sel.ch == 3) ? c->method : -1;     // other channel counts: the generic epilogue
+    sel.ext = ext;
+    // IEEE division in the epilogue (the default since round 5: measured free on the hits-only path, profiles/r05*).  The
+    // fused global extremum of MASKED classes only exists with the reciprocal normalisation (<= 1 ulp(float32) on ~1e-8
+    // of the outputs); exact_div == 2 (strict) sends those calls through maps + extremum_kernel instead (fm_begin).
+    // (The uint16 launch does not leave `ext && sc.masked` out: differs; not decided here.)
+    sel.exact_div = c->exact_div != 0 && !(ext && sc.masked);
+    sel.r2 = r2;
+    sel.kp = sc.kp_nseg > 0;
+    const MfmaFn fn = mfma_kernel(sel);
+    if (!fn) {
+        set_error("internal: no ncc_mfma_kernel instantiation for this class");
+        return MTM_E_STATE;
+    }
+    hipLaunchKernelGGL(fn, work_grid(p.n_work), dim3(256), lds, c->stream, p, c->td.as<TemplDev>(), tl_k, ap, st,
+                       c->maps.as<float>());
+    c->timing.kernel_used = MTM_KERNEL_MFMA;
+    return MTM_OK;
+}
+
+// uint16: ONE launch over the image's two byte planes (the "channels" of the launch) x [T_hi | T_lo] of 16 templates
+// per work item; the high-byte partial sums stay in registers while the low-byte plane is walked, and the epilogue
+// finishes the exact 16-bit correlation + normalisation (kMfU16, mtm_mfma.hip.h).
+static int launch_mfma16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, const StatPlanes& st, int only_li, int yb0, int yb1) {
+    const int h = sc.h, w = sc.w, oh = c->rows - h + 1, ow = c->cols - w + 1;
+    const int n_all = (int)sc.members.size(), n_pad = sc.n_pad;
+    // (plane 0: high bytes, plane 1: low bytes)
+    MfmaParams p = mfma_geometry(c->slot[c->cur].u8b.as<uint8_t>(), image_dev(c), 2, h, w, oh, ow, c->method);
+    p.nyb = (oh + kMfRows - 1) / kMfRows;
+    p.ntg = n_pad / 16;
+    p.group_bytes = sc.group_bytes;
+    int tg0 = 0;
+    if (only_li >= 0) {                 // one template: just its group of 16
+        tg0 = only_li / 16;
+        p.ntg = 1;
+    }
+    if (yb1 >= 0) {                     // banded launch: row blocks yb0 .. yb1 - 1
+        p.yb0 = yb0;
+        p.nyb = std::min(yb1, p.nyb) - yb0;
+    }
+    p.n_work = p.nseg * p.nyb * p.ntg;
+    p.kp_nseg = sc.kp_nseg;
+    p.kp_blocks = sc.kp_nseg ? kp_blocks(h, sc.kp_nseg) : 0;
+    p.n_list = n_all - tg0 * 16;                            // list positions inside the kernel are relative to tg0
+    if (only_li >= 0) p.only_li = only_li - tg0 * 16;
+    p.u16_tsum = c->tsum.as<double>() + sc.tsum_off + tg0 * 16;
+    p.u16_npad = n_pad;
+    p.u16_area = (double)h * (double)w;
+    wire_mfma_candidates(p, c, R, cand_list_cap(c));       // (cand_cap differs from the plain int8 launch; not decided here)
+    // (no statistics prefetch: the epilogue reads them from memory - differs from the int8 launch; not decided here)
+    const bool ext = R.ext;                          // fused global extremum (plan_call checked the classes)
+    const size_t lds = mfma_ext_or_staging(p, c, ext, mfma_lds_layout(p, plain_tile_rows(h), kMfU16EpiBytesPerWave));
+    const uint8_t* ap = c->apacks.as<uint8_t>() + sc.apack_off + (long long)tg0 * 2 * sc.group_bytes;
+    const int* tl_k = c->tlist.as<int>() + sc.tlist_off + tg0 * 16;
+    MfmaSel sel16;
+    sel16.method = kMfU16;
+    sel16.kp = sc.kp_nseg > 0;
+    sel16.ext = ext;
+    sel16.exact_div = c->exact_div != 0;            // (differs from the int8 launch's rule; not decided here)
+    hipLaunchKernelGGL(mfma_kernel(sel16), work_grid(p.n_work), dim3(256), lds, c->stream, p, c->td.as<TemplDev>(), tl_k, ap,
+                       st, c->maps.as<float>());
+    c->timing.kernel_used = MTM_KERNEL_MFMA16;
+    return MTM_OK;
+}
+
+// float32 classes on the bf16 matrix cores (ncc_bf16_kernel: two or three bf16 piece products per tap)
+static int launch_bf16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, const StatPlanes& st, int only_li, int yb0, int yb1) {
+    const int h = sc.h;
+    const int n_all = (int)sc.members.size();
+    const int mb = n_all > 16 ? 2 : 1;
+    Bf16Params p = bf16_geometry(c, sc, c->chans, mb, sc.group_bytes, c->method);
+    if (yb1 >= 0) {                             // a band of row blocks (run_score_banded, float32 uploads)
+        p.yb0 = yb0;
+        p.nyb = std::min(yb1, p.nyb) - yb0;
+    }
+    int tg0 = 0;
+    if (only_li >= 0) {
+        tg0 = only_li / (16 * mb);
+        p.ntg = 1;
+        p.n_list = n_all - tg0 * 16 * mb;
+        p.only_li = only_li - tg0 * 16 * mb;
+    }
+    p.n_work = p.nseg * p.nyb * p.ntg;
+    // (cand_cap min(hit_cap, kCandListMax) and no cand_pin: both differ from the int8 launch; not decided here)
+    wire_candidates(p, c, R, cand_list_cap(c));
+    const bool raw_m = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_CCORR || c->method == MTM_TM_CCOEFF;
+    // piece products of this launch: one where only a list leaves the kernel and every listing decision rests on a
+    // bound that knows it (below: rig 1 / 2, the refined extremum by bounds); three everywhere else
+    int np = 3;
+    if (R.bf16_np == 1 && R.refine && (p.hits_only || R.ext) && (!raw_m || R.ext || R.raw_rig)) np = 1;
+    if (R.refine && !raw_m) {
+        // Round 5: the listing decisions of the refined routes by the rigorous per-output bound (Bf16Params::rig)
+        p.rig = 1;
+        p.rig_eps = bf16_rig_eps(c->chans, h, p.nkb, np);
+        p.rig_thr = R.rig_thr;
+        p.list_all = R.cand_min ? (R.rig_thr < -1.0f ? 1 : 0) : (R.rig_thr < 0.0f ? 1 : 0);
+        if (R.refine_scan) {                // map mode: the scan's tolerances hold while no bound exceeds the cap
+            p.rig_cap = R.rig_cap;
+            p.rig_flag = reinterpret_cast<unsigned int*>(c->cands.as<uint8_t>() + 8);
+        }
+    }
+    if (R.refine && raw_m && R.raw_rig && !R.ext) {
+        // raw sums with a threshold (round 5): everything whose UPPER bound passes is listed and re-scored exactly
+        p.rig = 2;
+        p.rig_eps = bf16_rig_eps(c->chans, h, p.nkb, np);
+        p.rig_thr = R.rig_thr;
+        p.list_all = 0;
+    }
+    if (R.ext) {                                      // fused global extremum (plan_call checked the classes)
+        p.ext_on = 1;
+        p.ext_best = c->counters.as<unsigned long long>();
+        p.cand_on = 1;
+        p.hits_only = 1;
+        p.ext_margin = R.refine ? kRefineThrMargin : 0.0f;
+        if (raw_m && R.refine) {
+            // rigorous bounds instead of a relative margin (Bf16Params::ext_raw): 2^-15 for the dropped piece products
+            // and the two 16-bit representations, 2^-24 per float32 accumulation (three MFMAs per 32-tap block)
+            p.ext_raw = 1;
+            p.ext_eps = bf16_ext_eps(c->chans, h, p.nkb, np);
+        } else if (p.rig) {
+            p.ext_raw = 1;                              // (bounds of the quality instead of scores: the rig branch of the epilogue)
+            p.list_all = 0;
+        }
+    }
+    const size_t lds = bf16_lds_bytes(p.chunk_h, p.lds_cols);
+    const uint8_t* ap = c->apacks.as<uint8_t>() + sc.apack_off + (long long)tg0 * mb * sc.group_bytes;
+    const int* tl_k = c->tlist.as<int>() + sc.tlist_off + tg0 * 16 * mb;
+    // (a launch that is neither listing by a bound nor the bound-keeping extremum must not run the screen: its scores
+    // would be taken at face value)
+    if (np == 1 && !(p.rig != 0 || (p.ext_on && p.ext_raw))) np = 3;
+    if (np == 1 && !p.hits_only) np = 3;
+    if (c->f32_mfma == 4) np = 1;               // (diagnostic: the screen's scores as they are)
+    hipLaunchKernelGGL(bf16_kernel(mb, np), work_grid(p.n_work), dim3(256), lds, c->stream, p, c->td.as<TemplDev>(), tl_k, ap,
+                       st, c->maps.as<float>());
+    c->timing.kernel_used = MTM_KERNEL_MFMA_F32;
+    c->timing.f32_pieces = np;
+    return MTM_OK;
+}
+
+// uint8 classes on the dot4 (VALU) kernel
+static void launch_dot4(mtm_ctx* c, const SizeClass& sc, const int* tl, int n_list, const StatPlanes& st) {
+    const bool wide = (double)c->chans * sc.w * sc.h * 65025.0 >= 4294967296.0;
+    const DotVariant& v = kDotVariants[wide ? kDotWideVariant : c->dot_variant];
+    const DotParams p = dot_params(c, v, c->chans, sc.h, sc.w, n_list);
+    hipLaunchKernelGGL(v.fn, work_grid(p.n_work), dim3(256), 0, c->stream, p, c->td.as<TemplDev>(), tl, c->packs.as<uint8_t>(),
+                       st, c->maps.as<float>());
+    c->timing.kernel_used = MTM_KERNEL_DOT4;
+}
+
+// The float64 kernel.  A masked float32 class, local extrema against a threshold: two raw launches of the bf16 kernel as
+// a screen + exact re-scoring of everything that could pass (mtm_maskf32.hip.h); the float64 kernel only if that list
+// overflows.
+static int launch_f64(mtm_ctx* c, CallRoute& R, const SizeClass& sc, int kernel, const int* tl, int n_list, const StatPlanes& st) {
+    const int oh = c->rows - sc.h + 1, ow = c->cols - sc.w + 1;
+    const int ntx = (ow + kF64BX - 1) / kF64BX, nty = (oh + kF64BY - 1) / kF64BY;
+    const dim3 grd(ntx * nty, n_list);
+    const ImageDev img = image_dev(c);
+    float* maps = c->maps.as<float>();
+    MTMC(ensure_f32_plane(c));
+    bool screened = false;
+    if (sc.masked && sc.mask_bf16 && R.mbf_thr_on && n_list == (int)sc.members.size() && kernel == MTM_KERNEL_AUTO)
+        MTMC(launch_masked_bf16(c, R, sc, maps, &screened));
+    if (screened)
+        c->timing.kernel_used = MTM_KERNEL_MFMA_F32;
+    else if (sc.masked)
+        hipLaunchKernelGGL(ncc_f64_kernel<true>, grd, dim3(256), 0, c->stream, img, c->td.as<TemplDev>(), tl,
+                           c->weights.as<double>(), st, c->method, maps, ntx);
+    else
+        hipLaunchKernelGGL(ncc_f64_kernel<false>, grd, dim3(256), 0, c->stream, img, c->td.as<TemplDev>(), tl,
+                           c->weights.as<double>(), st, c->method, maps, ntx);
+    if (c->timing.kernel_used == 0) c->timing.kernel_used = MTM_KERNEL_AUTO;
+    return MTM_OK;
+}
+
+// Score maps of `n_list` templates of class `sc` (device list at tlist + list_off), on the kernel family the class resolves to.
+// `yb0`, `yb1`: range of output row blocks (MFMA and bf16 kernels; banded image upload), yb1 < 0 = all.
+int launch_ncc(mtm_ctx* c, CallRoute& R, const SizeClass& sc, int list_off, int n_list, const StatPlanes& st, int only_li,
+               int yb0, int yb1) {
+    const int kernel = resolved_kernel(c, sc);      // the same decision place_templates packed for
+    const int* tl = c->tlist.as<int>() + list_off;
+    // timing events around the dominant kernel
     // (The events are stream commands of their own.  Handing them to the launch itself - hipExtLaunchKernelGGL's start /
     // stop events - was measured in round 4: the gaps around the launches stayed, the call got 14 us SLOWER;
     // profiles/r04_r04w.)
-    bool ev_own = false;                // a branch below records the pair itself (on the stream its launch goes to)
-    HIPC(hipEventRecord(evp.first, ncc_s));
-
-    if (kernel == MTM_KERNEL_NAIVE) {
-        const dim3 blk(64, 4), grd((ow + 63) / 64, (oh + 3) / 4, n_list);
-        MTMC(ensure_f32_plane(c));
-        hipLaunchKernelGGL(ncc_naive_kernel, grd, blk, 0, c->stream, img, td, tl, c->weights.as<double>(), st,
-                           c->method, sc.masked ? 1 : 0, maps);
-        c->timing.kernel_used = MTM_KERNEL_NAIVE;
-    } else if (kernel == MTM_KERNEL_MFMA && !sc.slabs.empty()) {
-        // large templates: one RAW launch per slab (a template of its own against the image shifted by the slab's
-        // offset), then slab_combine_kernel adds the slabs up, restores the bias terms and normalises
-        const int n_all = (int)sc.members.size();
-        const int map_pitch = (int)round_up((size_t)ow, 4);
-        const long long raw_map = (long long)oh * map_pitch;
-        const int S = (int)sc.slabs.size();
-        MTMC(c->slab_raw.ensure(sizeof(int) * (size_t)S * n_all * (size_t)raw_map));
-        const bool rmr = sc.slab_R > 0;
-        // The slabs' launches are independent.  One of them is (output rows / 8R) x (columns / 256) work items - 91 for the
-        // reference's own benchmark shape (2048^2 image, one 414 x 400 template: four slabs), against 512 resident
-        // work-group slots: launches that do not fill the chip twice over run side by side on up to slab_concurrency
-        // streams, forked from and joined into the score stream.
-        int n_side = 1;
-        {
-            const int rows_per_item = rmr ? 8 * sc.slab_R : kMfRows;
-            const long long items = (long long)((ow + kMfSeg - 1) / kMfSeg) * ((oh + rows_per_item - 1) / rows_per_item) *
-                                    (rmr ? 1 : (n_all + 31) / 32);
-            const int cus = c->n_cus > 0 ? c->n_cus : 256;
-            if (items < 4LL * cus) n_side = (int)std::min<long long>(std::min(S, kSlabStreams), (4LL * cus + items - 1) / items);
-        }
-        // MTM_SLAB_MERGE (default 1): slabs of equal height and block count go out as ONE launch (MfmaParams::n_slab) - the
-        // hardware fills the chip from one grid and back-fills as work-groups finish, where several launches on several
-        // streams share four hardware queues (the fourth of four side-by-side slab launches started when the first had
-        // ended: profiles/r04_r04v_slab) - on one side stream, so that the statistics pass still runs under it.
-        bool merged = rmr && S > 1;
-        for (int k = 1; k < S && merged; ++k) {
-            const SizeClass::Slab &a = sc.slabs[0], &b = sc.slabs[(size_t)k];
-            merged = (b.r1 - b.r0) == (a.r1 - a.r0) && (b.c1 - b.c0 + 63) / 64 == (a.c1 - a.c0 + 63) / 64 &&
-                     b.apack_off - a.apack_off == (long long)k * rm_pack_bytes(a.r1 - a.r0, a.c1 - a.c0, sc.slab_R);
-        }
-        if (merged) n_side = c->slab_fork_early ? 2 : 1;        // (2: "side streams in use"; only the first one is)
-        if (n_side > 1) {
-            while ((int)c->slab_streams.size() < n_side) {
-                hipStream_t s2;
-                hipEvent_t e2;
-                HIPC(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-                HIPC(hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-                c->slab_streams.push_back(s2);
-                c->slab_done.push_back(e2);
-            }
-            if (!c->slab_fork) HIPC(hipEventCreateWithFlags(&c->slab_fork, hipEventDisableTiming));
-            if (!c->slab_fork_early) HIPC(hipEventRecord(c->slab_fork, ncc_s));      // (else: recorded ahead of the statistics)
-            for (int i = 0; i < n_side; ++i) HIPC(hipStreamWaitEvent(c->slab_streams[(size_t)i], c->slab_fork, 0));
-        }
-        for (int k = 0; k < (merged ? 1 : S); ++k) {
-            const SizeClass::Slab& sl = sc.slabs[(size_t)k];
-            const int hs = sl.r1 - sl.r0, ws = sl.c1 - sl.c0;
-            hipStream_t slab_s = n_side > 1 ? c->slab_streams[(size_t)(merged ? 0 : k % n_side)] : ncc_s;
-            MfmaParams p{};
-            p.img = c->slot[c->cur].u8b.as<uint8_t>() + (size_t)sl.ch * img.u8_plane + (size_t)sl.r0 * img.u8_pitch + sl.c0;
-            p.pitch = img.u8_pitch;
-            p.plane = img.u8_plane;
-            p.chans = 1;
-            p.h = hs;
-            p.w = ws;
-            p.oh = oh;
-            p.ow = ow;
-            p.nb = (ws + 63) / 64;
-            p.n_list = n_all;
-            p.nseg = (ow + kMfSeg - 1) / kMfSeg;
-            p.method = c->method;
-            p.lds_pitch = (16 + 4 * p.nb + 1) * 16;
-            p.cpr = p.lds_pitch / 16;
-            p.cpr_rstep = 256 / p.cpr;
-            p.cpr_dstep = 256 % p.cpr;
-        p.cpr_magic = 65536 / p.cpr + 1;
-            p.only_li = -1;
-            p.raw_map = raw_map;
-            p.raw_pitch = map_pitch;
-            p.raw_out = c->slab_raw.as<int>() + (size_t)k * n_all * (size_t)raw_map;
-            int tile_rows;
-            if (rmr) {
-                const int R = sc.slab_R;
-                p.rm_R = R;
-                p.rm_nt = sc.slab_nt;
-                while ((1 << p.rm_log2nt) < sc.slab_nt) ++p.rm_log2nt;
-                p.rm_steps = hs + 2 * R - 1;
-                p.rm_cstride = rm_pack_bytes(hs, ws, R);
-                p.nyb = (oh + 8 * R - 1) / (8 * R);
-                p.ntg = 1;
-                p.group_bytes = -(long long)R * p.nb * 1024;
-                        tile_rows = std::min(p.rm_steps, kMfChunkH) + (kMfRows - 1) * 2 * R;
-            } else {
-                p.nyb = (oh + kMfRows - 1) / kMfRows;
-                p.ntg = (n_all + 31) / 32;
-                p.group_bytes = mfma_group_bytes(hs, ws, 1);
-                tile_rows = std::min(hs, kMfChunkH) + kMfRows - 1;
-            }
-            p.n_work = p.nseg * p.nyb * p.ntg;
-            if (merged) {                       // every slab of the class: slab 0's geometry (the widest), S times the items
-                int ncb = 0;
-                for (const auto& q : sc.slabs) ncb += (q.ch == sl.ch && q.r0 == sl.r0) ? 1 : 0;
-                p.n_slab = S;
-                p.slab_ncb = ncb;
-                p.slab_nrb = S / (ncb * c->chans);
-                p.slab_cw = ncb > 1 ? sc.slabs[1].c0 - sl.c0 : 0;
-                p.slab_rh = hs;
-                p.slab_ap_step = rm_pack_bytes(hs, ws, sc.slab_R);
-                p.slab_raw_step = (long long)n_all * raw_map;
-                p.n_work *= S;
-            }
-            const size_t lds_main = (std::max<size_t>((size_t)tile_rows * p.lds_pitch, (size_t)kMfRows * kMfEpiBytesPerWave) + 15) &
-                                    ~(size_t)15;
-            p.tc_off = (int)lds_main;
-            p.st_off = (int)((lds_main + sizeof(MfTemplConst) * 32 + kMfItemBytes + 15) & ~(size_t)15);
-            const size_t lds = (size_t)p.st_off + (rmr ? 0 : (size_t)kMfRows * kMfStatBytesPerWave);
-            const int grid = ((p.n_work + 7) / 8) * 8;
-            const uint8_t* ap = c->apacks.as<uint8_t>() + sl.apack_off + (rmr ? (long long)sc.slab_R * p.nb * 1024 : 0);
-            // (merged launch on a side stream: the timing pair goes there too - on the score stream it would bracket
-            // the fork and the join, not the launch)
-            if (merged && slab_s != ncc_s) HIPC(hipEventRecord(evp.first, slab_s));
-            hipLaunchKernelGGL(mfma_raw_fn(rmr, false), dim3(grid), dim3(256), lds, slab_s, p, td,
-                               c->tlist.as<int>() + sc.tlist_off, ap, st, maps);
-            if (merged && slab_s != ncc_s) {
-                HIPC(hipEventRecord(evp.second, slab_s));
-                ev_own = true;
-            }
-        }
-        for (int i = 0; i < (merged ? 1 : n_side) && n_side > 1; ++i) {
-            HIPC(hipEventRecord(c->slab_done[(size_t)i], c->slab_streams[(size_t)i]));
-            HIPC(hipStreamWaitEvent(ncc_s, c->slab_done[(size_t)i], 0));
-        }
-        SlabParams q{};
-        q.raw = c->slab_raw.as<int>();
-        q.raw_slab = (long long)n_all * raw_map;
-        q.raw_map = raw_map;
-        q.n_slabs = S;
-        q.oh = oh;
-        q.ow = ow;
-        q.pitch = map_pitch;
-        q.n_list = n_all;
-        q.method = c->method;
-        q.w = w;
-        q.h = h;
-        q.chans = c->chans;
-        q.cand_on = R.cand_on ? 1 : 0;
-        q.cand_min = R.cand_min ? 1 : 0;
-        q.cand_thr = R.cand_thr;
-        q.cand_cap = (unsigned long long)std::min<int64_t>(c->hit_cap, 4096LL * 256);
-        q.cand_counter = c->cands.as<unsigned long long>();
-        q.cand_hits = reinterpret_cast<mtm_hit*>(c->cands.as<uint8_t>() + 16);
-        q.hits_only = (q.cand_on && R.hits_only) ? 1 : 0;
-        if (R.ext) {                                  // fused global extremum: keys instead of maps / candidates
-            q.ext_on = 1;
-            q.ext_best = c->counters.as<unsigned long long>();
-            q.cand_on = 0;
-            q.hits_only = 1;
-        }
-        hipLaunchKernelGGL(slab_combine_kernel, dim3((ow + 255) / 256, oh, n_all), dim3(256), 0, c->stream, q, td,
-                           c->tlist.as<int>() + sc.tlist_off, st, maps, only_li);
-        c->timing.kernel_used = MTM_KERNEL_MFMA;
-    } else if (kernel == MTM_KERNEL_MFMA) {
-        // the MFMA kernel works on whole 16-template groups of the class list; a single-template
-        // request (mtm_score_map) computes its group and stores only that template
-        const int n_all = (int)sc.members.size();
-        const bool rm = sc.rm_R > 0;
-        const bool r2 = sc.r2 > 0;
-        const int mb = r2 ? sc.r2 : (n_all > 16 || rm) ? 2 : 1;
-        const int tgsz = r2 ? 16 : 16 * mb;          // templates per work item
-        MfmaParams p{};
-        p.img = c->slot[c->cur].u8b.as<uint8_t>();        // int8 view (bytes ^ 0x80), same geometry as img.u8
-        p.pitch = img.u8_pitch;
-        p.plane = img.u8_plane;
-        p.chans = c->chans;
-        p.h = h;
-        p.w = w;
-        p.oh = oh;
-        p.ow = ow;
-        p.nb = (w + 63) / 64;
-        p.n_list = n_all;
-        p.nseg = (ow + kMfSeg - 1) / kMfSeg;
-        p.nyb = (oh + kMfRows - 1) / kMfRows;
-        p.ntg = (n_all + tgsz - 1) / tgsz;
-        if (r2) p.nyb = (oh + mb * kMfRows - 1) / (mb * kMfRows);
-        p.method = c->method;
-        p.lds_pitch = (16 + 4 * p.nb + 1) * 16;
-        p.cpr = p.lds_pitch / 16;
-        p.cpr_rstep = 256 / p.cpr;
-        p.cpr_dstep = 256 % p.cpr;
-        p.cpr_magic = 65536 / p.cpr + 1;
-        p.group_bytes = sc.group_bytes;
-        p.only_li = only_li;
-        p.cand_on = R.cand_on ? 1 : 0;
-        p.hits_only = (p.cand_on && R.hits_only) ? 1 : 0;
-        p.cand_thr_lo = (double)R.cand_thr - 1e-6 * std::max(1.0, std::fabs((double)R.cand_thr));
-        p.screen_hi = std::min(p.cand_thr_lo, 0.999999) - 1e-6;
-        p.sq_floor = 0.99 / std::sqrt((double)w * (double)h);
-        p.screen_l1 = c->screen_l1;
-        p.cand_min = R.cand_min ? 1 : 0;
-        p.cand_thr = R.cand_thr;
-        if (R.sparse) {                         // maps in memory + a flag per row segment that holds something above the threshold
-            p.seg_flags = c->seg_flags.as<uint8_t>();
-            p.flag_tstride = R.flag_tstride;
-            p.flag_rstride = R.flag_rstride;
-            const bool normed_m = c->method == MTM_TM_SQDIFF_NORMED || c->method == MTM_TM_CCORR_NORMED || c->method == MTM_TM_CCOEFF_NORMED;
-            p.seg_skip = (c->seg_skip && !sc.masked && normed_m) ? 1 : 0;
-            R.seg_skip_used = R.seg_skip_used || p.seg_skip != 0;
-        }
-        p.cand_cap = (unsigned long long)c->hit_cap;
-        p.cand_counter = c->cands.as<unsigned long long>();
-        p.cand_hits = reinterpret_cast<mtm_hit*>(c->cands.as<uint8_t>() + 16);
-        // the 8 spare bytes of the candidate header carry the shader clock the kernel measured (fetched with it)
-        p.clk_out = (p.cand_on && c->cands.p) ? reinterpret_cast<float*>(c->cands.as<uint8_t>() + 8) : nullptr;
-        if (R.cand_pin && p.cand_on && c->pinned) {       // the head of the list also into the host's landing buffer
-            p.cand_pin = reinterpret_cast<mtm_hit*>(static_cast<uint8_t*>(c->pinned) + 16);
-            p.cand_pin_n = (unsigned long long)R.cand_pin_n;
-            p.clk_out = reinterpret_cast<float*>(static_cast<uint8_t*>(c->pinned) + 8);
-        }
-        int tg0 = 0;
-        if (only_li >= 0 && !rm) {   // one template: just its group
-            tg0 = only_li / tgsz;
-            p.ntg = 1;
-        }
-        int tile_rows = r2 ? std::min(h + mb - 1, kMfChunkR2) + (kMfRows - 1) * mb : std::min(h, kMfChunkH) + kMfRows - 1;
-        if (rm) {
-            p.rm_R = sc.rm_R;
-            p.rm_nt = sc.rm_nt;
-            p.rm_log2nt = 0;
-            while ((1 << p.rm_log2nt) < sc.rm_nt) ++p.rm_log2nt;
-            p.rm_steps = h + 2 * sc.rm_R - 1;
-            p.rm_cstride = class_rm_pack_bytes(sc);
-            p.rm_rsq = c->stats_rsq.as<double>();
-                p.nyb = (oh + 8 * sc.rm_R - 1) / (8 * sc.rm_R);
-            p.ntg = 1;
-            tile_rows = std::min(p.rm_steps, kMfChunkH) + (kMfRows - 1) * 2 * sc.rm_R;
-        }
-        if (yb1 >= 0) {                     // banded launch: row blocks yb0 .. yb1 - 1 (the caller keeps the range non-empty)
-            p.yb0 = yb0;
-            p.nyb = std::min(yb1, p.nyb) - yb0;
-        }
-        p.n_work = p.nseg * p.nyb * p.ntg;
-        const size_t lds_main = (std::max<size_t>((size_t)tile_rows * p.lds_pitch,
-                                                  (size_t)kMfRows * kMfEpiBytesPerWave) + 15) & ~(size_t)15;
-        p.tc_off = (int)lds_main;
-        p.st_off = (int)((lds_main + sizeof(MfTemplConst) * 32 + kMfItemBytes + 15) & ~(size_t)15);
-        // statistics prefetch region: (channels + 2) planes per wave (RM loads its statistics directly)
-        size_t lds = (size_t)p.st_off + (rm ? 0 : r2 ? (size_t)kMfRows * ((mb + 1) / 2) * 1024
-                                                     : (size_t)kMfRows * mf_stat_bytes_per_wave(c->chans == 3 ? 3 : 1));
-        const bool ext = R.ext;                          // plan_call checked the class
-        if (ext) {
-            p.ext_off = (int)lds;                         // 4 waves x 32 keys
-            lds += (size_t)kMfRows * 32 * sizeof(unsigned long long);
-            p.ext_best = c->counters.as<unsigned long long>();
-            p.cand_on = 1;
-            p.hits_only = 1;
-        }
-        if (p.cand_on && !ext) {             // wave-private candidate staging (see emit_at)
-            lds = (lds + 15) & ~(size_t)15;
-            p.cs_off = (int)lds;
-            lds += (size_t)kMfRows * kMfCandStageBytes;
-        }
-        const int grid = ((p.n_work + 7) / 8) * 8;
-        const int* tl_class = c->tlist.as<int>() + sc.tlist_off;
-        p.kp_nseg = sc.kp_nseg;
-        p.kp_blocks = sc.kp_nseg ? kp_blocks(h, sc.kp_nseg) : 0;
-        const uint8_t* ap = c->apacks.as<uint8_t>() + sc.apack_off +
-                            (rm ? (sc.kp_nseg ? 0LL : (long long)sc.rm_R * p.nb * 1024)
-                                : (long long)tg0 * (r2 ? 1 : mb) * sc.group_bytes);
-        // with a group offset the kernel's list positions must stay class-relative: shift the list
-        // pointer and the counts instead (positions inside the kernel are relative to tg0)
-        p.n_list = n_all - tg0 * tgsz;
-        if (only_li >= 0) p.only_li = only_li - tg0 * tgsz;
-        const int* tl_k = tl_class + tg0 * tgsz;
-        // the instantiation of ncc_mfma_kernel for this class (the kernels live in the mtm_mfma_*.hip units)
-        MfmaSel sel;
-        sel.mb = mb;
-        sel.masked = sc.masked;
-        sel.rm = rm;
-        sel.ch = (c->chans == 3 && !sc.masked) ? 3 : 1;
-        sel.method = (c->chans == 1 || sel.ch == 3) ? c->method : -1;     // other channel counts: the generic epilogue
-        sel.ext = ext;
-        // IEEE division in the epilogue (the default since round 5: measured free on the hits-only path, profiles/r05*).  The
-        // fused global extremum of MASKED classes only exists with the reciprocal normalisation (<= 1 ulp(float32) on ~1e-8
-        // of the outputs); exact_div == 2 (strict) sends those calls through maps + extremum_kernel instead (fm_begin).
-        sel.exact_div = c->exact_div != 0 && !(ext && sc.masked);
-        sel.r2 = r2;
-        sel.kp = sc.kp_nseg > 0;
-        const MfmaFn fn = mfma_kernel(sel);
-        if (!fn) {
-            set_error("internal: no ncc_mfma_kernel instantiation for this class");
-            return MTM_E_STATE;
-        }
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds, ncc_s, p, td, tl_k, ap, st, maps);
-        c->timing.kernel_used = MTM_KERNEL_MFMA;
-    } else if (kernel == MTM_KERNEL_MFMA16) {
-        // uint16: ONE launch over the image's two byte planes (the "channels" of the launch) x [T_hi | T_lo] of 16 templates
-        // per work item; the high-byte partial sums stay in registers while the low-byte plane is walked, and the epilogue
-        // finishes the exact 16-bit correlation + normalisation (kMfU16, mtm_mfma.hip.h).
-        const int n_all = (int)sc.members.size(), n_pad = sc.n_pad;
-        MfmaParams p{};
-        p.pitch = img.u8_pitch;
-        p.plane = img.u8_plane;
-        p.chans = 2;                                            // byte planes: high, low
-        p.h = h;
-        p.w = w;
-        p.oh = oh;
-        p.ow = ow;
-        p.nb = (w + 63) / 64;
-        p.nseg = (ow + kMfSeg - 1) / kMfSeg;
-        p.nyb = (oh + kMfRows - 1) / kMfRows;
-        p.ntg = n_pad / 16;
-        p.method = c->method;
-        p.lds_pitch = (16 + 4 * p.nb + 1) * 16;
-        p.cpr = p.lds_pitch / 16;
-        p.cpr_rstep = 256 / p.cpr;
-        p.cpr_dstep = 256 % p.cpr;
-        p.cpr_magic = 65536 / p.cpr + 1;
-        p.group_bytes = sc.group_bytes;
-        int tg0 = 0;
-        if (only_li >= 0) {                 // one template: just its group of 16
-            tg0 = only_li / 16;
-            p.ntg = 1;
-        }
-        if (yb1 >= 0) {                     // banded launch: row blocks yb0 .. yb1 - 1
-            p.yb0 = yb0;
-            p.nyb = std::min(yb1, p.nyb) - yb0;
-        }
-        p.n_work = p.nseg * p.nyb * p.ntg;
-        const size_t lds_main = (std::max<size_t>((size_t)(std::min(h, kMfChunkH) + kMfRows - 1) * p.lds_pitch,
-                                                  (size_t)kMfRows * kMfU16EpiBytesPerWave) + 15) & ~(size_t)15;
-        p.tc_off = (int)lds_main;
-        p.st_off = (int)((lds_main + sizeof(MfTemplConst) * 32 + kMfItemBytes + 15) & ~(size_t)15);
-        size_t lds = (size_t)p.st_off;                          // (no statistics prefetch: the epilogue reads them from memory)
-        const int grid = ((p.n_work + 7) / 8) * 8;
-        const uint8_t* ap = c->apacks.as<uint8_t>() + sc.apack_off + (long long)tg0 * 2 * sc.group_bytes;
-        const int* tl_k = c->tlist.as<int>() + sc.tlist_off + tg0 * 16;
-        p.img = c->slot[c->cur].u8b.as<uint8_t>();             // plane 0: high bytes, plane 1: low bytes
-        p.kp_nseg = sc.kp_nseg;
-        p.kp_blocks = sc.kp_nseg ? kp_blocks(h, sc.kp_nseg) : 0;
-        p.n_list = n_all - tg0 * 16;                            // list positions inside the kernel are relative to tg0
-        p.only_li = only_li >= 0 ? only_li - tg0 * 16 : -1;
-        const double* ts = c->tsum.as<double>() + sc.tsum_off;
-        p.u16_tsum = ts + tg0 * 16;
-        p.u16_npad = n_pad;
-        p.u16_area = (double)h * (double)w;
-        p.cand_on = R.cand_on ? 1 : 0;
-        p.hits_only = (p.cand_on && R.hits_only) ? 1 : 0;
-        p.cand_min = R.cand_min ? 1 : 0;
-        p.cand_thr = R.cand_thr;
-        p.cand_cap = (unsigned long long)std::min<int64_t>(c->hit_cap, 4096LL * 256);
-        p.cand_counter = c->cands.as<unsigned long long>();
-        p.cand_hits = reinterpret_cast<mtm_hit*>(c->cands.as<uint8_t>() + 16);
-        if (R.cand_pin && p.cand_on && c->pinned) {
-            p.cand_pin = reinterpret_cast<mtm_hit*>(static_cast<uint8_t*>(c->pinned) + 16);
-            p.cand_pin_n = (unsigned long long)R.cand_pin_n;
-        }
-        p.cand_thr_lo = (double)R.cand_thr - 1e-6 * std::max(1.0, std::fabs((double)R.cand_thr));
-        p.screen_hi = std::min(p.cand_thr_lo, 0.999999) - 1e-6;
-        p.sq_floor = 0.99 / std::sqrt((double)w * (double)h);
-        p.screen_l1 = c->screen_l1;
-        const bool ext = R.ext;                          // fused global extremum (plan_call checked the classes)
-        if (ext) {
-            p.ext_off = (int)lds;                         // 4 waves x 32 keys
-            lds += (size_t)kMfRows * 32 * sizeof(unsigned long long);
-            p.ext_best = c->counters.as<unsigned long long>();
-            p.cand_on = 1;
-            p.hits_only = 1;
-        }
-        if (p.cand_on && !ext) {
-            lds = (lds + 15) & ~(size_t)15;
-            p.cs_off = (int)lds;
-            lds += (size_t)kMfRows * kMfCandStageBytes;
-        }
-        MfmaSel sel16;
-        sel16.method = kMfU16;
-        sel16.kp = sc.kp_nseg > 0;
-        sel16.ext = ext;
-        sel16.exact_div = c->exact_div != 0;
-        hipLaunchKernelGGL(mfma_kernel(sel16), dim3(grid), dim3(256), lds, ncc_s, p, td, tl_k, ap, st, maps);
-        c->timing.kernel_used = MTM_KERNEL_MFMA16;
-    } else if (kernel == MTM_KERNEL_MFMA_F32 && !R.f32_exact) {
-        const int n_all = (int)sc.members.size();
-        const int mb = n_all > 16 ? 2 : 1;
-        Bf16Params p{};
-        p.img = img.f32;
-        p.pitch = img.f32_pitch;
-        p.plane = img.f32_plane;
-        p.chans = c->chans;
-        p.rows = c->rows;
-        p.cols = c->cols;
-        p.h = h;
-        p.w = w;
-        p.oh = oh;
-        p.ow = ow;
-        p.nkb = bf16_nkb(w);
-        p.chunk_h = p.nkb <= 2 ? 64 : 32;
-        p.lds_cols = kBfSeg + 32 * p.nkb;
-        p.n_list = n_all;
-        p.nseg = (ow + kBfSeg - 1) / kBfSeg;
-        p.nyb = (oh + kBfRows - 1) / kBfRows;
-        if (yb1 >= 0) {                             // a band of row blocks (run_score_banded, float32 uploads)
-            p.yb0 = yb0;
-            p.nyb = std::min(yb1, p.nyb) - yb0;
-        }
-        p.ntg = (n_all + 16 * mb - 1) / (16 * mb);
-        p.method = c->method;
-        p.group_bytes = sc.group_bytes;
-        p.piece_bytes = sc.group_bytes * mfma_groups_alloc(n_all);
-        p.only_li = only_li;
-        int tg0 = 0;
-        if (only_li >= 0) {
-            tg0 = only_li / (16 * mb);
-            p.ntg = 1;
-            p.n_list = n_all - tg0 * 16 * mb;
-            p.only_li = only_li - tg0 * 16 * mb;
-        }
-        p.n_work = p.nseg * p.nyb * p.ntg;
-        p.cand_on = R.cand_on ? 1 : 0;
-        p.cand_min = R.cand_min ? 1 : 0;
-        p.cand_thr = R.cand_thr;
-        p.cand_cap = (unsigned long long)std::min<int64_t>(c->hit_cap, 4096LL * 256);
-        p.cand_counter = c->cands.as<unsigned long long>();
-        p.cand_hits = reinterpret_cast<mtm_hit*>(c->cands.as<uint8_t>() + 16);
-        p.hits_only = (p.cand_on && R.hits_only) ? 1 : 0;
-        const bool raw_m = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_CCORR || c->method == MTM_TM_CCOEFF;
-        // piece products of this launch: one where only a list leaves the kernel and every listing decision rests on a
-        // bound that knows it (below: rig 1 / 2, the refined extremum by bounds); three everywhere else
-        int np = 3;
-        if (R.bf16_np == 1 && R.refine && (p.hits_only || R.ext) && (!raw_m || R.ext || R.raw_rig)) np = 1;
-        if (R.refine && !raw_m) {
-            // Round 5: the listing decisions of the refined routes by the rigorous per-output bound (Bf16Params::rig)
-            p.rig = 1;
-            p.rig_eps = bf16_rig_eps(c->chans, h, p.nkb, np);
-            p.rig_thr = R.rig_thr;
-            p.list_all = R.cand_min ? (R.rig_thr < -1.0f ? 1 : 0) : (R.rig_thr < 0.0f ? 1 : 0);
-            if (R.refine_scan) {                // map mode: the scan's tolerances hold while no bound exceeds the cap
-                p.rig_cap = R.rig_cap;
-                p.rig_flag = reinterpret_cast<unsigned int*>(c->cands.as<uint8_t>() + 8);
-            }
-        }
-        if (R.refine && raw_m && R.raw_rig && !R.ext) {
-            // raw sums with a threshold (round 5): everything whose UPPER bound passes is listed and re-scored exactly
-            p.rig = 2;
-            p.rig_eps = bf16_rig_eps(c->chans, h, p.nkb, np);
-            p.rig_thr = R.rig_thr;
-            p.list_all = 0;
-        }
-        if (R.ext) {                                      // fused global extremum (plan_call checked the classes)
-            p.ext_on = 1;
-            p.ext_best = c->counters.as<unsigned long long>();
-            p.cand_on = 1;
-            p.hits_only = 1;
-            p.ext_margin = R.refine ? kRefineThrMargin : 0.0f;
-            if (raw_m && R.refine) {
-                // rigorous bounds instead of a relative margin (Bf16Params::ext_raw): 2^-15 for the dropped piece products
-                // and the two 16-bit representations, 2^-24 per float32 accumulation (three MFMAs per 32-tap block)
-                p.ext_raw = 1;
-                p.ext_eps = bf16_ext_eps(c->chans, h, p.nkb, np);
-            } else if (p.rig) {
-                p.ext_raw = 1;                              // (bounds of the quality instead of scores: the rig branch of the epilogue)
-                p.list_all = 0;
-            }
-        }
-        const size_t lds = bf16_lds_bytes(p.chunk_h, p.lds_cols);
-        const int grid = ((p.n_work + 7) / 8) * 8;
-        const uint8_t* ap = c->apacks.as<uint8_t>() + sc.apack_off + (long long)tg0 * mb * sc.group_bytes;
-        const int* tl_k = c->tlist.as<int>() + sc.tlist_off + tg0 * 16 * mb;
-        // (a launch that is neither listing by a bound nor the bound-keeping extremum must not run the screen: its scores
-        // would be taken at face value)
-        if (np == 1 && !(p.rig != 0 || (p.ext_on && p.ext_raw))) np = 3;
-        if (np == 1 && !p.hits_only) np = 3;
-        if (c->f32_mfma == 4) np = 1;               // (diagnostic: the screen's scores as they are)
-        hipLaunchKernelGGL(bf16_kernel(mb, np), dim3(grid), dim3(256), lds, c->stream, p, td, tl_k, ap, st, maps);
-        c->timing.kernel_used = MTM_KERNEL_MFMA_F32;
-        c->timing.f32_pieces = np;
-    } else if (kernel == MTM_KERNEL_DOT4) {
-        const bool wide = (double)c->chans * w * h * 65025.0 >= 4294967296.0;
-        const DotVariant& v = kDotVariants[wide ? kDotWideVariant : c->dot_variant];
-        DotParams p{};
-        p.img = img.u8;
-        p.pitch = img.u8_pitch;
-        p.plane = img.u8_plane;
-        p.chans = c->chans;
-        p.h = h;
-        p.w = w;
-        p.oh = oh;
-        p.ow = ow;
-        const int w4 = (w + 3) & ~3;
-        p.ncy = (h + kDotChunk - 1) / kDotChunk;
-        p.ncx = (w4 + kDotChunk - 1) / kDotChunk;
-        p.n_list = n_list;
-        p.ntx = (ow + 32 * v.px - 1) / (32 * v.px);
-        p.nty = (oh + 8 * v.py - 1) / (8 * v.py);
-        p.nchunks = (n_list + v.nt - 1) / v.nt;
-        p.n_work = p.ntx * p.nty * p.nchunks;
-        p.method = c->method;
-        const int grid = ((p.n_work + 7) / 8) * 8;
-        hipLaunchKernelGGL(v.fn, dim3(grid), dim3(256), 0, c->stream, p, td, tl, c->packs.as<uint8_t>(), st, maps);
-        c->timing.kernel_used = MTM_KERNEL_DOT4;
-    } else {
-        const int ntx = (ow + kF64BX - 1) / kF64BX, nty = (oh + kF64BY - 1) / kF64BY;
-        const dim3 grd(ntx * nty, n_list);
-        MTMC(ensure_f32_plane(c));
-        // masked float32 class, local extrema against a threshold: two raw launches of the bf16 kernel as a screen + exact
-        // re-scoring of everything that could pass (mtm_maskf32.hip.h); the float64 kernel only if that list overflows
-        bool screened = false;
-        if (sc.masked && sc.mask_bf16 && R.mbf_thr_on && n_list == (int)sc.members.size() && kernel == MTM_KERNEL_AUTO)
-            MTMC(launch_masked_bf16(c, R, sc, maps, &screened));
-        if (screened)
-            c->timing.kernel_used = MTM_KERNEL_MFMA_F32;
-        else if (sc.masked)
-            hipLaunchKernelGGL(ncc_f64_kernel<true>, grd, dim3(256), 0, c->stream, img, td, tl,
-                               c->weights.as<double>(), st, c->method, maps, ntx);
-        else
-            hipLaunchKernelGGL(ncc_f64_kernel<false>, grd, dim3(256), 0, c->stream, img, td, tl,
-                               c->weights.as<double>(), st, c->method, maps, ntx);
-        if (c->timing.kernel_used == 0) c->timing.kernel_used = MTM_KERNEL_AUTO;
-    }
+    std::pair<hipEvent_t, hipEvent_t>* evp;
+    MTMC(event_pair(c->ncc_ev, c->timing.ncc_launches, &evp));
+    HIPC(hipEventRecord(evp->first, c->stream));
+    bool ev_own = false;                // the slab launcher recorded the pair itself (on the stream its launch went to)
+    if (kernel == MTM_KERNEL_NAIVE)
+        MTMC(launch_naive(c, sc, tl, n_list, st));
+    else if (kernel == MTM_KERNEL_MFMA && !sc.slabs.empty())
+        MTMC(launch_mfma_slabs(c, R, sc, st, only_li, *evp, &ev_own));
+    else if (kernel == MTM_KERNEL_MFMA)
+        MTMC(launch_mfma(c, R, sc, st, only_li, yb0, yb1));
+    else if (kernel == MTM_KERNEL_MFMA16)
+        MTMC(launch_mfma16(c, R, sc, st, only_li, yb0, yb1));
+    else if (kernel == MTM_KERNEL_MFMA_F32 && !R.f32_exact)
+        MTMC(launch_bf16(c, R, sc, st, only_li, yb0, yb1));
+    else if (kernel == MTM_KERNEL_DOT4)
+        launch_dot4(c, sc, tl, n_list, st);
+    else
+        MTMC(launch_f64(c, R, sc, kernel, tl, n_list, st));
     HIPC(hipGetLastError());
-    if (!ev_own) HIPC(hipEventRecord(evp.second, ncc_s));
+    if (!ev_own) HIPC(hipEventRecord(evp->second, c->stream));
     c->timing.ncc_launches++;
     return MTM_OK;
 }
@@ -1099,7 +1065,7 @@ int launch_refine(mtm_ctx* c, const SizeClass& sc, const StatPlanes& st, bool ri
     p.ring = ring ? 1 : 0;
     p.list = reinterpret_cast<mtm_hit*>(c->cands.as<uint8_t>() + 16);
     p.count = c->cands.as<unsigned long long>();
-    p.cap = (unsigned long long)std::min<int64_t>(c->hit_cap, 4096LL * 256);
+    p.cap = cand_list_cap(c);
     p.maps = patch_maps ? c->maps.as<float>() : nullptr;
     // one wave per record, records strided over a grid that fills the chip a few times (the list length is only known
     // on the device; most calls list a few hundred records)
@@ -1113,7 +1079,7 @@ int launch_refine(mtm_ctx* c, const SizeClass& sc, const StatPlanes& st, bool ri
 static int launch_refine_extremum(mtm_ctx* c, const CallRoute& R) {
     const size_t n = c->templs.size();
     HIPC(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * 2 * n, c->stream));
-    const unsigned long long cap = (unsigned long long)std::min<int64_t>(c->hit_cap, 4096LL * 256);
+    const unsigned long long cap = cand_list_cap(c);
     hipLaunchKernelGGL(refine_extremum_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, c->stream,
                        reinterpret_cast<const mtm_hit*>(c->cands.as<uint8_t>() + 16), c->cands.as<unsigned long long>(), cap,
                        c->td.as<TemplDev>(), R.cand_min ? 1 : 0, c->counters.as<unsigned long long>());
@@ -1129,7 +1095,7 @@ static int launch_refine_scan(mtm_ctx* c, const CallRoute& R, const SizeClass& s
                        c->tlist.as<int>() + sc.tlist_off, R.cand_min ? 1 : 0, R.scan_thr,
                        2.0f * R.rig_cap, c->opt_border,
                        reinterpret_cast<mtm_hit*>(c->cands.as<uint8_t>() + 16),
-                       (unsigned long long)std::min<int64_t>(c->hit_cap, 4096LL * 256), c->cands.as<unsigned long long>());
+                       cand_list_cap(c), c->cands.as<unsigned long long>());
     HIPC(hipGetLastError());
     return MTM_OK;
 }

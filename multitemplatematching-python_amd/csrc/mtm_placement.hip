@@ -71,12 +71,7 @@ std::vector<SizeClass::Slab> slab_layout(const mtm_ctx* c, const SizeClass& sc) 
             hs = std::max(hs, sl.r1 - sl.r0);
             ws = std::max(ws, sl.c1 - sl.c0);
         }
-        int nt = 1;
-        while (nt < (int)sc.members.size()) nt <<= 1;
-        const size_t lds_pitch = (size_t)(16 + 4 * ((ws + 63) / 64) + 1) * 16;
-        auto tile_bytes = [&](int R) { return (size_t)(std::min(hs + 2 * R - 1, kMfChunkH) + 6 * R) * lds_pitch; };
-        while (nt < 16 && tile_bytes(16 / nt) > 72 * 1024) nt <<= 1;
-        const int R = 16 / nt;
+        const int R = 16 / rm_group_templates((int)sc.members.size(), hs, ws);
         const long long items = (long long)((ow + kMfSeg - 1) / kMfSeg) * ((oh + 8 * R - 1) / (8 * R));
         std::vector<double> cost;                         // one entry per work-group, longest first
         for (const auto& sl : v)
@@ -190,8 +185,6 @@ bool masked_bf16_class_ok(const mtm_ctx* c, const SizeClass& sc) {
     return f32_refined(c) && c->dtype == MTM_F32 && sc.all_f32 && sc.masked && c->chans == 1 && sc.w <= kBfMaxW &&
            c->rows > sc.h && c->cols > sc.w && (c->method == MTM_TM_SQDIFF || c->method == MTM_TM_CCORR_NORMED);
 }
-inline int bf16_nkb(int w) { return (w + 31) / 32; }
-long long bf16_group_bytes(int h, int w, int chans) { return (long long)chans * h * bf16_nkb(w) * 1024; }
 
 // A packs of a float32 class for ncc_bf16_kernel: [piece 0 | piece 1][group of 16][ch][dy][32-tap block][lane = 16 q + i]
 // [8 bf16]: lane (i, q) holds taps 32 kb + 8 q .. + 7 of template i, centred by its channel mean and split
@@ -442,14 +435,9 @@ int place_templates(mtm_ctx* c) {
         if (c->row_mux && class_kernel[k] == MTM_KERNEL_MFMA && n_cls <= 16 && c->fuse_stats &&
             (c->chans == 1 || (c->chans == 3 && !sc.masked)) &&
             (double)c->chans * sc.w * sc.h * 65025.0 < 4294967296.0) {
-            int nt = 1;
-            while (nt < (int)n_cls) nt <<= 1;
-            // two work-groups per CU need <= ~76 KB of LDS each: wide templates take fewer rows per MFMA group
-            const size_t lds_pitch = (size_t)(16 + 4 * ((sc.w + 63) / 64) + 1) * 16;
-            auto tile_bytes = [&](int R) { return (size_t)(std::min(sc.h + 2 * R - 1, kMfChunkH) + 6 * R) * lds_pitch; };
-            while (nt < 16 && tile_bytes(16 / nt) > 72 * 1024) nt <<= 1;
-            sc.rm_nt = nt;
-            sc.rm_R = 16 / nt;
+            // (wide templates take fewer rows per MFMA group: rm_group_templates)
+            sc.rm_nt = rm_group_templates((int)n_cls, sc.h, sc.w);
+            sc.rm_R = 16 / sc.rm_nt;
         }
         sc.slabs.clear();
         sc.slab_nt = sc.slab_R = 0;
@@ -458,18 +446,13 @@ int place_templates(mtm_ctx* c) {
             sc.slabs = slab_layout(c, sc);
             sc.rm_nt = sc.rm_R = 0;
             if (n_cls <= 16) {                     // row-multiplexed raw launches: nt templates x R rows per MFMA group
-                int nt = 1;
-                while (nt < (int)n_cls) nt <<= 1;
                 int hs = 0, ws = 0;
                 for (const auto& sl : sc.slabs) {
                     hs = std::max(hs, sl.r1 - sl.r0);
                     ws = std::max(ws, sl.c1 - sl.c0);
                 }
-                const size_t lds_pitch = (size_t)(16 + 4 * ((ws + 63) / 64) + 1) * 16;
-                auto tile_bytes = [&](int R) { return (size_t)(std::min(hs + 2 * R - 1, kMfChunkH) + 6 * R) * lds_pitch; };
-                while (nt < 16 && tile_bytes(16 / nt) > 72 * 1024) nt <<= 1;
-                sc.slab_nt = nt;
-                sc.slab_R = 16 / nt;
+                sc.slab_nt = rm_group_templates((int)n_cls, hs, ws);
+                sc.slab_R = 16 / sc.slab_nt;
             }
         }
         sc.r2 = (c->mfma_r2 && class_kernel[k] == MTM_KERNEL_MFMA && sc.rm_R == 0 && sc.slabs.empty() && n_cls > 16 &&

@@ -321,6 +321,29 @@ int mtm_find_matches_batch(mtm_ctx* ctx, const void* const* images, int n_images
                            int dtype, int64_t row_stride_bytes, int mode, double score_threshold,
                            mtm_hit* out, int64_t capacity, int64_t* counts, int64_t* n_out);
 
+/* Coarse-to-fine search (reference tutorials/Tutorial3-SpeedingUp.ipynb: the searchBox and downscaling recipes combined;
+ * DESIGN 5.2).  The image (uint8, `rows` x `cols` before any downscale) crosses PCIe once; the coarse image - its
+ * integer-factor area downscale, as mtm_set_image_downscaled makes it - is derived on the device from the same upload.
+ * Templates: those of the last mtm_set_templates (unmasked uint8, method 1..5), downscaled by `factor` on the host with the
+ * same arithmetic for the coarse level.
+ *   coarse level: the local extrema of every template's coarse map that pass `coarse_threshold` (mtm_find_matches'
+ *                 rule, border option and "no non-maximum pixel, no peaks" rule); the best `max_candidates` per template.
+ *   windows:      a candidate at coarse output (cy, cx) stands for the full-resolution positions rows
+ *                 [cy f - radius, cy f + radius] x columns [cx f - radius, cx f + radius], clipped to the score map.
+ *   fine level:   mode MTM_PEAKS_LOCAL - the positions of the windows' union that are local extrema of the full-resolution
+ *                 map under mtm_find_matches' rule (neighbours outside the windows count; the map's own border rule) and
+ *                 pass `score_threshold`; a template whose windows hold no position that differs from its neighbourhood's
+ *                 extremum has none.  MTM_PEAKS_GLOBAL - per template with candidates, the extremum over the union (ties:
+ *                 first in row-major order).  Scores are bit for bit those of mtm_score_map.
+ * Hits in mtm_find_matches' order, coordinates relative to the image.  Every coarse and full-resolution score map must be
+ * at least 2 x 2 and every coarse template at least 2 x 2 (MTM_E_INVALID otherwise).  On MTM_E_OVERFLOW *n_out holds the
+ * capacity needed and mtm_last_hits returns the records.  The image becomes the context's current image; the templates
+ * stay as they were set. */
+int mtm_find_matches_pyramid(mtm_ctx* ctx, const void* px, int rows, int cols, int chans, int dtype,
+                             int64_t row_stride_bytes, int factor, int mode, double coarse_threshold,
+                             double score_threshold, int radius, int max_candidates, mtm_hit* out, int64_t capacity,
+                             int64_t* n_out);
+
 /* Stream form of mtm_find_matches ("thousands of images", reference
  * tutorials/Tutorial3-SpeedingUp.ipynb:564: same templates, one image after the other): returns the
  * hits of the CURRENT image exactly like mtm_find_matches and makes `next_px` the current image for

@@ -25,6 +25,7 @@ from .version import __version__
 pinned_empty = _lib.pinned_empty        # numpy arrays in page-locked memory (faster uploads); optional
 
 __all__ = ["NMS", "Hit", "matchTemplates", "findMatches", "computeScoreMap", "TemplateMatcher", "matchTemplatesBatch",
+           "findMatchesPyramid", "matchTemplatesPyramid",
            "pinned_empty", "drawBoxesOnRGB",
            "drawBoxesOnGray", "TM_SQDIFF", "TM_SQDIFF_NORMED", "TM_CCORR", "TM_CCORR_NORMED",
            "TM_CCOEFF", "TM_CCOEFF_NORMED", "__version__"]
@@ -655,3 +656,4 @@ def drawBoxesOnGray(image: np.ndarray, listHit: Sequence[Hit], boxThickness: int
 
 
 from . import augment  # noqa: E402,F401  (template augmentation / downscaled matching helpers)
+from .pyramid import findMatchesPyramid, matchTemplatesPyramid  # noqa: E402  (coarse-to-fine search)

@@ -102,6 +102,10 @@ SYMBOLS = {
     "mtm_find_matches_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
                                               ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _P(ctypes.c_int64)]),
+    "mtm_find_matches_pyramid": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                                ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                                _P(ctypes.c_int64)]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
                                              ctypes.c_int64, _P(ctypes.c_int64), ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
@@ -454,6 +458,24 @@ class Context(_RecordMemo):
             out = np.empty(cap, dtype=HIT_DTYPE)
             rc = self._lib.mtm_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(n))
         check(rc, "mtm_find_matches_image")
+        return out[:n.value]
+
+    def find_matches_pyramid(self, image, factor, mode, coarse_threshold, score_threshold, radius, max_candidates):
+        """Coarse-to-fine search of the current templates in one native call (mtm_find_matches_pyramid): candidates from
+        the image downscaled by `factor`, exact full-resolution scores in windows of +-`radius` around them."""
+        a, ptr, stride = _pixel_rows(image)
+        chans = 1 if a.ndim == 2 else a.shape[2]
+        cap = 4096
+        out = np.empty(cap, dtype=HIT_DTYPE)
+        n = ctypes.c_int64(0)
+        rc = self._lib.mtm_find_matches_pyramid(self._h, ptr, a.shape[0], a.shape[1], chans, _dtype_code(a), stride,
+                                                int(factor), int(mode), float(coarse_threshold), float(score_threshold),
+                                                int(radius), int(max_candidates), out.ctypes.data, cap, ctypes.byref(n))
+        if rc == E_OVERFLOW:        # the result stays in the context: fetch it, do not recompute
+            cap = int(n.value)
+            out = np.empty(cap, dtype=HIT_DTYPE)
+            rc = self._lib.mtm_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(n))
+        check(rc, "mtm_find_matches_pyramid")
         return out[:n.value]
 
     def find_matches_batch(self, images, mode, score_threshold):

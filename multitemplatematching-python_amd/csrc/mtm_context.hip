@@ -186,6 +186,21 @@ int upload_image_stack(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* const* px
     return convert_raw(sl, g, cols, chans, dtype, stream, 1);
 }
 
+int derive_downscaled_u8(mtm_ctx* dst, const mtm_ctx::ImageSlot& src, int src_rows, int src_cols, int chans, int factor,
+                         hipStream_t stream) {
+    mtm_ctx::ImageSlot& sl = dst->slot[dst->cur];
+    SlotGeom g{};
+    MTMC(prepare_slot(dst, sl, src_rows, src_cols, chans, MTM_U8, stream, factor, &g));
+    hipLaunchKernelGGL(planarize_u8_down_kernel, dim3((g.cols + 255) / 256, g.rows), dim3(256), 0, stream,
+                       src.raw.as<uint8_t>(), src_cols, chans, factor, g.rows, g.cols, sl.u8.as<uint8_t>(),
+                       sl.u8b.as<uint8_t>(), g.pitch, (long long)g.pitch * g.rows_alloc, sl.f32.as<float>(), g.pitch,
+                       (long long)g.pitch * g.rows_alloc);
+    HIPC(hipGetLastError());
+    sl.f32_valid = true;
+    adopt_image(dst, g.rows, g.cols, chans, MTM_U8);
+    return MTM_OK;
+}
+
 void adopt_image(mtm_ctx* c, int rows, int cols, int chans, int dtype) {
     c->sq_valid = false;
     c->f32_sq_valid = false;
@@ -349,6 +364,8 @@ void mtm_ctx_destroy(mtm_ctx* c) {
     mtm_comm_destroy(c);
     (void)hipStreamSynchronize(c->stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    if (c->pyr_sub) mtm_ctx_destroy(c->pyr_sub);
+    for (DevBuf* b : {&c->pyr_tpx, &c->pyr_toff_dev, &c->pyr_wins, &c->pyr_buf, &c->pyr_hits, &c->pyr_flags}) b->release();
     for (auto& sl : c->slot)
         for (DevBuf* b : {&sl.raw, &sl.u8, &sl.u8b, &sl.f32}) b->release();
     for (DevBuf* b : {&c->tsrc, &c->usrc_dev, &c->tsums_dev, &c->tgather, &c->slab_raw, &c->seg_flags, &c->hits_t, &c->nms_buf, &c->td_u, &c->td_v,

@@ -1,7 +1,8 @@
 // Internal header of libmtm_hip.so's GPU side: the context, the size classes of a template set, and the functions the
 // translation units share.  Units: mtm_context.hip (context, options, image upload), mtm_placement.hip (template sets ->
 // size classes, packs, constants), mtm_launch.hip (window statistics and score-map launches), mtm_api.hip
-// (mtm_find_matches and friends: peak extraction, hit lists), mtm_comm.hip (RCCL hit exchange).  Not part of the ABI.
+// (mtm_find_matches and friends: peak extraction, hit lists), mtm_comm.hip (RCCL hit exchange), mtm_pyramid.hip (the
+// coarse-to-fine search).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -363,6 +364,15 @@ struct mtm_ctx {
     void* comm_pin = nullptr;           // pinned staging of the hit exchange: [my slot | gathered slots]
     size_t comm_pin_cap = 0;
     std::vector<uint8_t> templ_blob;    // bytes of the templates of the last mtm_set_templates (unchanged-input test)
+    // mtm_find_matches_pyramid (mtm_pyramid.hip): the coarse level runs in a context of its own on the same device (its
+    // templates are the downscaled ones, its image the downscaled planes made from this context's upload); the fine level's
+    // full-resolution template pixels (planar, per template at pyr_toff[t]) and per-call buffers live here.  pyr_blob /
+    // pyr_factor: the template set and factor they were made for.
+    mtm_ctx* pyr_sub = nullptr;
+    std::vector<uint8_t> pyr_blob;
+    int pyr_factor = 0;
+    std::vector<long long> pyr_toff;
+    DevBuf pyr_tpx, pyr_toff_dev, pyr_wins, pyr_buf, pyr_hits, pyr_flags;
 
     // RCCL
     void* rccl_lib = nullptr;
@@ -495,6 +505,10 @@ int upload_image(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* src, int64_t sr
 int upload_image_stack(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* const* px, int n, int64_t src_stride, int rows,
                        int cols, int chans, int dtype, hipStream_t stream);
 void adopt_image(mtm_ctx* c, int rows, int cols, int chans, int dtype);
+// The planes of `dst`'s current slot from the raw uint8 image already in `src` (src_rows x src_cols, tightly packed),
+// area-downscaled by `factor` on `stream`; `dst` adopts the downscaled image (mtm_find_matches_pyramid's coarse level).
+int derive_downscaled_u8(mtm_ctx* dst, const mtm_ctx::ImageSlot& src, int src_rows, int src_cols, int chans, int factor,
+                         hipStream_t stream);
 int check_image_args(const void* px, int rows, int cols, int chans, int dtype, int64_t row_stride_bytes, const char* who);
 int ensure_f32_plane(mtm_ctx* c);
 int upload_rows_f32c1(mtm_ctx::ImageSlot& sl, const SlotGeom& g, const void* src, int64_t src_stride, int r0, int r1, hipStream_t stream);

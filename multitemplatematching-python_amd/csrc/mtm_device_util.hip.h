@@ -13,8 +13,12 @@ namespace mtm {
 // ---------------------------------------------------------------------------------------------
 // normalisation epilogue (common_matchTemplate / matchTemplateMask), float64 -> float32
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float finish_unmasked(int method, double corr, const StatPlanes& st,
-                                                 size_t sidx, const TemplDev& T, int chans) {
+// The window statistics are read through accessors (s1(c): window sum of channel c, sum2(): sum of squares over all
+// channels, sq(): the guarded sqrt of window_norm), each only when the method needs it: finish_unmasked reads them from the
+// statistics planes, pyr_window_kernel passes the sums it computed itself.
+template <class S1, class Sum2, class Sq>
+__device__ __forceinline__ float finish_unmasked_with(int method, double corr, S1 s1, Sum2 sum2, Sq sq, const TemplDev& T,
+                                                      int chans) {
     if (T.all_ones) return 1.0f;
     if (method == MTM_TM_CCORR) return (float)corr;
     const int num_type = (method == MTM_TM_CCORR_NORMED) ? 0
@@ -25,19 +29,36 @@ __device__ __forceinline__ float finish_unmasked(int method, double corr, const 
     if (num_type == 1) {
 #pragma unroll
         for (int c = 0; c < kMaxChans; ++c)
-            if (c < chans) num -= st.t[c][sidx] * T.mean[c];
+            if (c < chans) num -= s1(c) * T.mean[c];
     } else if (num_type == 2) {
-        num = st.sum2[sidx] - 2.0 * num + T.templ_sum2;
+        num = sum2() - 2.0 * num + T.templ_sum2;
         num = fmax(num, 0.0);
     }
     if (normed) {
-        const double t = st.sq[sidx] * T.templ_norm;
+        const double t = sq() * T.templ_norm;
         const double an = fabs(num);
         if (an < t) num = num / t;
         else if (an < t * 1.125) num = (num > 0.0) ? 1.0 : -1.0;
         else num = (method == MTM_TM_SQDIFF_NORMED) ? 1.0 : 0.0;
     }
     return (float)num;
+}
+
+__device__ __forceinline__ float finish_unmasked(int method, double corr, const StatPlanes& st,
+                                                 size_t sidx, const TemplDev& T, int chans) {
+    return finish_unmasked_with(
+        method, corr, [&](int c) { return st.t[c][sidx]; }, [&]() { return st.sum2[sidx]; },
+        [&]() { return st.sq[sidx]; }, T, chans);
+}
+
+// The normalisation denominator of a window (OpenCV common_matchTemplate): sqrt(sum2 - wnd_mean2), zero where the
+// window is flat to float32 precision.  sum2 = sum over channels of the window's sum of squares, wnd_mean2 = (sum over
+// channels of S1_c^2) / area for TM_CCOEFF_NORMED, 0 otherwise.  Every statistics kernel (stats_u8_kernel,
+// stats_u8_mc_kernel, vsum_stats_kernel) and pyr_window_kernel take it from here.
+__device__ __forceinline__ double window_norm(double sum2, double wnd_mean2) {
+    const double diff2 = fmax(sum2 - wnd_mean2, 0.0);
+    const bool small = diff2 <= fmin(0.5, (10.0 * (double)FLT_EPSILON) * sum2);
+    return small ? 0.0 : sqrt(diff2);
 }
 
 __device__ __forceinline__ float finish_masked(int method, double c_i_tm2, double c_i2_m2,

@@ -315,9 +315,7 @@ __global__ __launch_bounds__(256) void stats_u8_kernel(const uint8_t* __restrict
                 ws2[k] = (double)s2;
                 double wnd_mean2 = 0.0;
                 if (num_type == 1) wnd_mean2 = (tt[k] * tt[k]) * inv_area;
-                const double diff2 = fmax(ws2[k] - wnd_mean2, 0.0);
-                const bool small = diff2 <= fmin(0.5, (10.0 * (double)FLT_EPSILON) * ws2[k]);
-                sqv[k] = small ? 0.0 : sqrt(diff2);
+                sqv[k] = window_norm(ws2[k], wnd_mean2);
                 rs[k] = sqv[k] > 0.0 ? 1.0 / sqv[k] : 0.0;
                 blk_s1[k] = tt[k];
                 blk_sq[k] = sqv[k];
@@ -648,9 +646,7 @@ __global__ __launch_bounds__(256) void stats_u8_mc_kernel(const uint8_t* __restr
             for (int k = 0; k < 4; ++k) {
                 ws2[k] = (double)(E[CH][4 * t + k + w] - e[CH][k]);
                 const double wnd_mean2 = mean2[k] * inv_area;
-                const double diff2 = fmax(ws2[k] - wnd_mean2, 0.0);
-                const bool small = diff2 <= fmin(0.5, (10.0 * (double)FLT_EPSILON) * ws2[k]);
-                sqv[k] = small ? 0.0 : sqrt(diff2);
+                sqv[k] = window_norm(ws2[k], wnd_mean2);
             }
             if (want_sum2) {
                 *reinterpret_cast<double2*>(sum2 + o) = make_double2(ws2[0], ws2[1]);
@@ -752,11 +748,7 @@ __global__ void vsum_stats_kernel(const AccT* __restrict__ hs1, const AccT* __re
         }
         wnd_mean2 *= inv_area;
         sum2[(size_t)y * pitch + x] = wnd_sum2;
-        if (want_sq) {
-            const double diff2 = fmax(wnd_sum2 - wnd_mean2, 0.0);
-            const bool small = diff2 <= fmin(0.5, (10.0 * (double)FLT_EPSILON) * wnd_sum2);
-            sq[(size_t)y * pitch + x] = small ? 0.0 : sqrt(diff2);
-        }
+        if (want_sq) sq[(size_t)y * pitch + x] = window_norm(wnd_sum2, wnd_mean2);
         if (y + 1 < y1) {
 #pragma unroll
             for (int c = 0; c < kMaxChans; ++c) {

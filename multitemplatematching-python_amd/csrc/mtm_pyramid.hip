@@ -1,0 +1,474 @@
+// libmtm_hip.so - coarse-to-fine search (mtm_find_matches_pyramid): the local extrema of a downscaled search
+// propose candidates, full-resolution scores are computed only in small windows around them (pyr_window_kernel), with the
+// exact integer sums and the epilogue of every other score kernel, and the peak test of the exhaustive search is applied
+// there.  uint8, unmasked templates of one mtm_set_templates call.
+#include "mtm_ctx.h"
+#include "mtm_device_util.hip.h"
+
+using namespace mtm;
+using namespace mtmi;
+
+namespace mtm {
+
+// One candidate window of a template: the full-resolution positions it stands for and the region scored for them (the
+// window and a one-pixel ring, both clipped to the score map).  A template's windows are consecutive, best candidate first.
+struct PyrWin {
+    int t;                      // template index
+    int first;                  // index of the template's first window in the list
+    int y0, y1, x0, x1;         // window (inclusive bounds)
+    int ry0, ry1, rx0, rx1;     // scored region (inclusive bounds)
+    long long buf_off;          // float offset of the region's scores in the score buffer, row-major, rx1 - rx0 + 1 per row
+};
+
+constexpr int kPyrTile = 16;                    // a tile of 16 x 16 outputs, one per thread
+constexpr int kPyrKR = 16, kPyrKC = 64;         // template chunk in LDS: rows x columns
+constexpr int kPyrIW = kPyrTile + kPyrKC + 4;   // bytes per LDS image row: the dword right of the last one a thread reads
+constexpr int kPyrIR = kPyrTile + kPyrKR - 1;   // LDS image rows
+// the uint32 sums of one chunk cannot overflow; they are flushed to uint64 after every chunk
+static_assert((unsigned long long)kPyrKR * kPyrKC * 255ull * 255ull < (1ull << 32), "chunk too large for uint32 sums");
+
+// Grid: one work-group per window.  Phase 1 scores the region tile by tile: per output the exact correlation and the
+// window sums S1 (per channel) and S2 come from v_dot4_u32_u8 over a template chunk and an image tile in LDS (the
+// template streams through LDS chunk by chunk, so its size is not bounded by LDS), then window_norm and
+// finish_unmasked_with make the float32 score exactly as the exhaustive kernels do.  Phase 2 reads the region back:
+//   local mode  - the peak test of peaks_kernel (v == max of its 3x3 neighbourhood, border rule `border`, v > thr_q in
+//                 quality space) on the window's positions; a position another window of the same template listed earlier
+//                 also covers is left to that window, so every position is emitted once.  nontrivial[t] records that some
+//                 position of the window differs from its neighbourhood's maximum.
+//   global mode - the best (quality, first in row-major order) position over the window into best[t] (atomicMax on
+//                 order(quality) << 32 | ~index, as extremum_kernel keys it).
+template <int CH>
+__global__ __launch_bounds__(256) void pyr_window_kernel(ImageDev img, const uint8_t* __restrict__ tpx,
+                                                         const long long* __restrict__ toff, const TemplDev* __restrict__ td,
+                                                         const PyrWin* __restrict__ wins, float* __restrict__ buf, int method,
+                                                         int mode_min, int global, float thr_q, int border,
+                                                         mtm_hit* __restrict__ hits, unsigned long long cap,
+                                                         unsigned long long* __restrict__ counter,
+                                                         unsigned long long* __restrict__ best,
+                                                         int* __restrict__ nontrivial) {
+    __shared__ __attribute__((aligned(16))) uint32_t Tl[kPyrKR][kPyrKC / 4];
+    __shared__ __attribute__((aligned(16))) uint32_t Il[kPyrIR][kPyrIW / 4];
+    const PyrWin W = wins[blockIdx.x];
+    const TemplDev T = td[W.t];
+    const int h = T.rows, w = T.cols;
+    const uint8_t* tp = tpx + toff[W.t];
+    const int tid = threadIdx.x, ly = tid / kPyrTile, lx = tid % kPyrTile;
+    const int RH = W.ry1 - W.ry0 + 1, RW = W.rx1 - W.rx0 + 1;
+    float* rb = buf + W.buf_off;
+    const double inv_area = 1.0 / ((double)h * (double)w);
+    const bool centred = method == MTM_TM_CCOEFF || method == MTM_TM_CCOEFF_NORMED;
+
+    for (int ty0 = 0; ty0 < RH; ty0 += kPyrTile)
+        for (int tx0 = 0; tx0 < RW; tx0 += kPyrTile) {
+            const int oy0 = W.ry0 + ty0, ox0 = W.rx0 + tx0;       // the tile's first output (= its window's top-left pixel)
+            unsigned long long corr = 0ull, s2 = 0ull, s1[CH];
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                s1[c] = 0ull;
+                const uint8_t* ip = img.u8 + c * img.u8_plane;
+                const uint8_t* tc = tp + (size_t)c * h * w;
+                for (int r0 = 0; r0 < h; r0 += kPyrKR)
+                    for (int c0 = 0; c0 < w; c0 += kPyrKC) {
+                        __syncthreads();            // the previous chunk's LDS reads are done
+                        // template rows r0 .., columns c0 .. (zero outside the template)
+                        for (int k = tid; k < kPyrKR * (kPyrKC / 4); k += 256) {
+                            const int i = k / (kPyrKC / 4), j = (k % (kPyrKC / 4)) * 4;
+                            uint32_t v = 0u;
+                            if (r0 + i < h)
+#pragma unroll
+                                for (int b = 0; b < 4; ++b)
+                                    if (c0 + j + b < w) v |= (uint32_t)tc[(size_t)(r0 + i) * w + c0 + j + b] << (8 * b);
+                            Tl[i][j >> 2] = v;
+                        }
+                        // image rows oy0 + r0 .., columns ox0 + c0 .. (zero outside the image: only outputs outside the
+                        // map, which are never stored, read them)
+                        for (int k = tid; k < kPyrIR * (kPyrIW / 4); k += 256) {
+                            const int i = k / (kPyrIW / 4), j = (k % (kPyrIW / 4)) * 4;
+                            const int y = oy0 + r0 + i, x = ox0 + c0 + j;
+                            uint32_t v = 0u;
+                            if (y < img.rows)
+#pragma unroll
+                                for (int b = 0; b < 4; ++b)
+                                    if (x + b < img.cols) v |= (uint32_t)ip[(size_t)y * img.u8_pitch + x + b] << (8 * b);
+                            Il[i][j >> 2] = v;
+                        }
+                        __syncthreads();
+                        const int ni = min(kPyrKR, h - r0), nj = min(kPyrKC, w - c0);
+                        const int sh = lx & 3;
+                        uint32_t a_corr = 0u, a_s1 = 0u, a_s2 = 0u;
+                        for (int i = 0; i < ni; ++i) {
+                            const uint32_t* irow = &Il[ly + i][0];
+                            for (int j = 0; j < nj; j += 4) {
+                                const int q = (lx + j) >> 2;
+                                uint32_t v = __builtin_amdgcn_alignbyte(irow[q + 1], irow[q], sh);   // bytes lx + j .. + 3
+                                if (nj - j < 4) v &= (1u << (8 * (nj - j))) - 1u;                 // columns past the template
+                                a_corr = __builtin_amdgcn_udot4(v, Tl[i][j >> 2], a_corr, false);
+                                a_s1 = __builtin_amdgcn_udot4(v, 0x01010101u, a_s1, false);
+                                a_s2 = __builtin_amdgcn_udot4(v, v, a_s2, false);
+                            }
+                        }
+                        corr += a_corr;
+                        s1[c] += a_s1;
+                        s2 += a_s2;
+                    }
+            }
+            if (ty0 + ly < RH && tx0 + lx < RW) {
+                // the statistics of stats_u8_kernel / stats_u8_mc_kernel / vsum_stats_kernel: exact sums, the same order
+                double s1d[kMaxChans] = {0.0, 0.0, 0.0, 0.0};
+                double mean2 = 0.0;
+#pragma unroll
+                for (int c = 0; c < CH; ++c) {
+                    s1d[c] = (double)s1[c];
+                    if (centred) mean2 += s1d[c] * s1d[c];
+                }
+                const double sum2 = (double)s2;
+                const double wnd_mean2 = mean2 * inv_area;
+                const float score = finish_unmasked_with(
+                    method, (double)corr, [&](int c) { return s1d[c]; }, [&]() { return sum2; },
+                    [&]() { return window_norm(sum2, wnd_mean2); }, T, CH);
+                rb[(size_t)(ty0 + ly) * RW + tx0 + lx] = score;
+            }
+        }
+    __syncthreads();            // the region's scores are visible to the whole work-group
+
+    const float padv = (border == MTM_BORDER_CONSTANT) ? 0.0f : -INFINITY;
+    auto q_at = [&](int y, int x) -> float {        // quality at map position (y, x); the pad value outside the map
+        if (y < 0 || y >= T.oh || x < 0 || x >= T.ow) return padv;
+        const float s = rb[(size_t)(y - W.ry0) * RW + (x - W.rx0)];
+        return mode_min ? -s : s;
+    };
+    const int WH = W.y1 - W.y0 + 1, WW = W.x1 - W.x0 + 1;
+    int nontriv = 0;
+    unsigned long long bk = 0ull;
+    for (int k = tid; k < WH * WW; k += 256) {
+        const int y = W.y0 + k / WW, x = W.x0 + k % WW;
+        const float v = q_at(y, x);
+        bool emit = false;
+        if (global) {
+            const unsigned long long key = ((unsigned long long)mf_float_order(v) << 32) |
+                                           (0xFFFFFFFFull - (unsigned long long)((long long)y * T.ow + x));
+            bk = key > bk ? key : bk;
+        } else {
+            float mx = v;
+#pragma unroll
+            for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+                for (int dx = -1; dx <= 1; ++dx) mx = fmaxf(mx, q_at(y + dy, x + dx));
+            if (!(v == mx)) {
+                nontriv = 1;
+            } else if (v > thr_q) {
+                emit = true;
+                for (int j = W.first; j < (int)blockIdx.x; ++j)
+                    if (y >= wins[j].y0 && y <= wins[j].y1 && x >= wins[j].x0 && x <= wins[j].x1) {
+                        emit = false;
+                        break;
+                    }
+            }
+        }
+        mtm_hit rec;
+        rec.templ_idx = W.t;
+        rec.x = x;
+        rec.y = y;
+        rec.w = w;
+        rec.h = h;
+        rec.score = mode_min ? -v : v;
+        cand_append(emit, counter, cap, hits, rec);
+    }
+    if (global) {
+        if (bk != 0ull) atomicMax(best + W.t, bk);
+    } else if (__syncthreads_or(nontriv) && tid == 0) {
+        nontrivial[W.t] = 1;
+    }
+}
+
+}  // namespace mtm
+
+namespace {
+
+struct BlobTempl {
+    int rows, cols, chans;
+    const uint8_t* px;      // interleaved, tightly packed rows
+};
+
+// The templates of the last mtm_set_templates, read back from the bytes the context keeps of them (mtm_ctx::templ_blob,
+// written by set_templates_impl: n_templ, method, n_var, then per template {rows, cols, chans, dtype, has_mask} + rows).
+int parse_templ_blob(const std::vector<uint8_t>& b, std::vector<BlobTempl>& out, const char* who) {
+    size_t off = 0;
+    auto rd = [&](void* dst, size_t n) {
+        if (off + n > b.size()) return false;
+        std::memcpy(dst, b.data() + off, n);
+        off += n;
+        return true;
+    };
+    int n_templ = 0, method = 0, n_var = 0;
+    if (!rd(&n_templ, sizeof(int)) || !rd(&method, sizeof(int)) || !rd(&n_var, sizeof(int))) {
+        set_error(std::string(who) + ": no templates set");
+        return MTM_E_STATE;
+    }
+    if (n_var != 0) {
+        set_error(std::string(who) + ": takes the templates of mtm_set_templates (not an augmented set)");
+        return MTM_E_INVALID;
+    }
+    out.clear();
+    for (int i = 0; i < n_templ; ++i) {
+        int hdr[5];
+        if (!rd(hdr, sizeof(hdr))) return MTM_E_STATE;
+        if (hdr[3] != MTM_U8 || hdr[4] != 0) {
+            set_error(std::string(who) + ": template " + std::to_string(i) + " is not an unmasked uint8 template");
+            return MTM_E_INVALID;
+        }
+        const size_t bytes = (size_t)hdr[0] * hdr[1] * hdr[2];
+        if (off + bytes > b.size()) return MTM_E_STATE;
+        out.push_back(BlobTempl{hdr[0], hdr[1], hdr[2], b.data() + off});
+        off += bytes;
+    }
+    return MTM_OK;
+}
+
+// augment.downscale / planarize_u8_down_kernel on the host: factor 2 -> (sum + 2) >> 2, else rint((float)sum / f^2)
+std::vector<uint8_t> downscale_u8(const BlobTempl& t, int f) {
+    const int r = t.rows / f, cc = t.cols / f, C = t.chans;
+    std::vector<uint8_t> o((size_t)r * cc * C);
+    const float scale = 1.0f / (float)(f * f);
+    for (int y = 0; y < r; ++y)
+        for (int x = 0; x < cc; ++x)
+            for (int c = 0; c < C; ++c) {
+                unsigned sum = 0;
+                for (int dy = 0; dy < f; ++dy)
+                    for (int dx = 0; dx < f; ++dx) sum += t.px[((size_t)(y * f + dy) * t.cols + (size_t)x * f + dx) * C + c];
+                const unsigned v = (f == 2) ? ((sum + 2u) >> 2) : (unsigned)rintf((float)sum * scale);
+                o[((size_t)y * cc + x) * C + c] = (uint8_t)(v > 255u ? 255u : v);
+            }
+    return o;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtm_find_matches_pyramid(mtm_ctx* c, const void* px, int rows, int cols, int chans, int dtype,
+                             int64_t row_stride_bytes, int factor, int mode, double coarse_threshold,
+                             double score_threshold, int radius, int max_candidates, mtm_hit* out, int64_t capacity,
+                             int64_t* n_out) {
+    const char* who = "mtm_find_matches_pyramid";
+    if (!c || !n_out || capacity < 0 || (capacity > 0 && !out) || (mode != MTM_PEAKS_LOCAL && mode != MTM_PEAKS_GLOBAL) ||
+        factor < 2 || factor > 64 || radius < 0 || max_candidates < 1) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    MTMC(check_image_args(px, rows, cols, chans, dtype, row_stride_bytes, who));
+    if (dtype != MTM_U8) {
+        set_error(std::string(who) + ": takes uint8 images");
+        return MTM_E_INVALID;
+    }
+    if (!c->have_templ) {
+        set_error(std::string(who) + ": no templates set");
+        return MTM_E_STATE;
+    }
+    if (c->method == MTM_TM_SQDIFF) {
+        set_error(std::string(who) + ": TM_SQDIFF is not supported");
+        return MTM_E_INVALID;
+    }
+    std::vector<BlobTempl> tl;
+    MTMC(parse_templ_blob(c->templ_blob, tl, who));
+    const int n = (int)tl.size();
+    const int crows = rows / factor, ccols = cols / factor;
+    for (int i = 0; i < n; ++i) {
+        const BlobTempl& t = tl[(size_t)i];
+        const int hc = t.rows / factor, wc = t.cols / factor;
+        if (t.chans != chans || hc < 2 || wc < 2 || crows - hc + 1 < 2 || ccols - wc + 1 < 2 || rows - t.rows + 1 < 2 ||
+            cols - t.cols + 1 < 2) {
+            set_error(std::string(who) + ": template " + std::to_string(i) +
+                      ": channel count differs from the image, or its coarse template / a score map is smaller than 2x2");
+            return MTM_E_INVALID;
+        }
+    }
+    HIPC(hipSetDevice(c->device));
+    if (!c->pyr_sub) MTMC(mtm_ctx_create(&c->pyr_sub, c->device));
+    mtm_ctx* s = c->pyr_sub;
+    s->opt_border = c->opt_border;
+    if (c->pyr_factor != factor || c->pyr_blob != c->templ_blob) {
+        // the coarse templates (the coarse context's set) and the full-resolution pixels, planar [C][h][w] per template
+        c->pyr_blob.clear();
+        std::vector<std::vector<uint8_t>> coarse((size_t)n);
+        std::vector<mtm_templ> recs((size_t)n);
+        std::vector<uint8_t> planar;
+        c->pyr_toff.assign((size_t)n, 0);
+        for (int i = 0; i < n; ++i) {
+            const BlobTempl& t = tl[(size_t)i];
+            coarse[(size_t)i] = downscale_u8(t, factor);
+            mtm_templ& r = recs[(size_t)i];
+            r.px = coarse[(size_t)i].data();
+            r.mask = nullptr;
+            r.rows = t.rows / factor;
+            r.cols = t.cols / factor;
+            r.chans = t.chans;
+            r.dtype = MTM_U8;
+            r.row_stride = (int64_t)r.cols * r.chans;
+            r.mask_row_stride = 0;
+            c->pyr_toff[(size_t)i] = (long long)planar.size();
+            const size_t plane = (size_t)t.rows * t.cols;
+            planar.resize(planar.size() + plane * t.chans);
+            uint8_t* dst = planar.data() + c->pyr_toff[(size_t)i];
+            for (size_t p = 0; p < plane; ++p)
+                for (int k = 0; k < t.chans; ++k) dst[(size_t)k * plane + p] = t.px[p * t.chans + k];
+        }
+        MTMC(mtm_set_templates(s, recs.data(), n, c->method));
+        if (!planar.empty()) {
+            MTMC(c->pyr_tpx.ensure(planar.size()));
+            HIPC(hipMemcpy(c->pyr_tpx.p, planar.data(), planar.size(), hipMemcpyHostToDevice));
+            MTMC(c->pyr_toff_dev.ensure(sizeof(long long) * (size_t)n));
+            HIPC(hipMemcpy(c->pyr_toff_dev.p, c->pyr_toff.data(), sizeof(long long) * (size_t)n, hipMemcpyHostToDevice));
+        }
+        c->pyr_blob = c->templ_blob;
+        c->pyr_factor = factor;
+    }
+
+    // ONE upload: the full-resolution planes, and the coarse planes derived on the device from the same raw copy
+    c->timing = mtm_timing{};
+    c->maps_valid = false;
+    c->last_hits.clear();
+    MTMC(upload_image(c, c->slot[c->cur], px, row_stride_bytes, rows, cols, chans, MTM_U8, c->stream, 1));
+    adopt_image(c, rows, cols, chans, MTM_U8);
+    MTMC(derive_downscaled_u8(s, c->slot[c->cur], rows, cols, chans, factor, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+
+    // coarse level: the local extrema of the downscaled search that pass coarse_threshold, in mtm_find_matches' order
+    std::vector<mtm_hit> ch(4096);
+    int64_t nc = 0;
+    int rc = mtm_find_matches(s, MTM_PEAKS_LOCAL, coarse_threshold, ch.data(), (int64_t)ch.size(), &nc);
+    if (rc == MTM_E_OVERFLOW) {
+        ch.resize((size_t)nc);
+        rc = mtm_last_hits(s, ch.data(), nc, &nc);
+    }
+    if (rc != MTM_OK) return rc;
+    ch.resize((size_t)nc);
+
+    // windows: the best max_candidates of every template (the list is ordered by quality, ties row-major)
+    MTMC(place_templates(c));
+    std::vector<PyrWin> wins;
+    long long buf_floats = 0;
+    int cur_t = -1, taken = 0, first = 0;
+    for (const mtm_hit& hc : ch) {
+        if (hc.templ_idx != cur_t) {
+            cur_t = hc.templ_idx;
+            taken = 0;
+            first = (int)wins.size();
+        }
+        if (taken >= max_candidates) continue;
+        ++taken;
+        const TemplDev& d = c->td_host[(size_t)cur_t];
+        const long long cy = (long long)hc.y * factor, cx = (long long)hc.x * factor;
+        const int y0 = (int)std::max(0LL, cy - radius), y1 = (int)std::min((long long)d.oh - 1, cy + radius);
+        const int x0 = (int)std::max(0LL, cx - radius), x1 = (int)std::min((long long)d.ow - 1, cx + radius);
+        if (y0 > y1 || x0 > x1) continue;
+        PyrWin W;
+        W.t = cur_t;
+        W.first = first;
+        W.y0 = y0;
+        W.y1 = y1;
+        W.x0 = x0;
+        W.x1 = x1;
+        W.ry0 = std::max(0, y0 - 1);
+        W.ry1 = std::min(d.oh - 1, y1 + 1);
+        W.rx0 = std::max(0, x0 - 1);
+        W.rx1 = std::min(d.ow - 1, x1 + 1);
+        W.buf_off = buf_floats;
+        buf_floats += (long long)(W.ry1 - W.ry0 + 1) * (W.rx1 - W.rx0 + 1);
+        wins.push_back(W);
+    }
+    if (buf_floats > (1LL << 30)) {
+        set_error(std::string(who) + ": the candidate windows need more than 2^30 scores (lower radius or max_candidates)");
+        return MTM_E_INVALID;
+    }
+
+    const bool mode_min = c->method == MTM_TM_SQDIFF_NORMED;
+    std::vector<mtm_hit> hits;
+    if (!wins.empty()) {
+        MTMC(c->pyr_wins.ensure(sizeof(PyrWin) * wins.size()));
+        HIPC(hipMemcpyAsync(c->pyr_wins.p, wins.data(), sizeof(PyrWin) * wins.size(), hipMemcpyHostToDevice, c->stream));
+        MTMC(c->pyr_buf.ensure(sizeof(float) * (size_t)buf_floats));
+        // [hit counter][best key per template][nontrivial flag per template]
+        const size_t flag_bytes = sizeof(unsigned long long) * (1 + (size_t)n) + sizeof(int) * (size_t)n;
+        MTMC(c->pyr_flags.ensure(flag_bytes));
+        std::vector<uint8_t> fl(flag_bytes);
+        if (c->pyr_hits.cap < sizeof(mtm_hit) * 4096) MTMC(c->pyr_hits.ensure(sizeof(mtm_hit) * 4096));
+        const float thr = (float)score_threshold;       // numpy compares the float32 map with the threshold in float32
+        unsigned long long count = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            const unsigned long long cap = c->pyr_hits.cap / sizeof(mtm_hit);
+            HIPC(hipMemsetAsync(c->pyr_flags.p, 0, flag_bytes, c->stream));
+            unsigned long long* counter = c->pyr_flags.as<unsigned long long>();
+            int* nontrivial = reinterpret_cast<int*>(counter + 1 + n);
+            const ImageDev img = image_dev(c);
+#define MTM_PYR_LAUNCH(CH)                                                                                                  \
+    hipLaunchKernelGGL(pyr_window_kernel<CH>, dim3((unsigned)wins.size()), dim3(256), 0, c->stream, img,                    \
+                       c->pyr_tpx.as<uint8_t>(), c->pyr_toff_dev.as<long long>(), c->td.as<TemplDev>(),                     \
+                       c->pyr_wins.as<PyrWin>(), c->pyr_buf.as<float>(), c->method, mode_min ? 1 : 0,                        \
+                       mode == MTM_PEAKS_GLOBAL ? 1 : 0, mode_min ? -thr : thr, c->opt_border, c->pyr_hits.as<mtm_hit>(), \
+                       cap, counter, counter + 1, nontrivial)
+            switch (chans) {
+                case 1: MTM_PYR_LAUNCH(1); break;
+                case 2: MTM_PYR_LAUNCH(2); break;
+                case 3: MTM_PYR_LAUNCH(3); break;
+                default: MTM_PYR_LAUNCH(4); break;
+            }
+#undef MTM_PYR_LAUNCH
+            HIPC(hipGetLastError());
+            HIPC(hipMemcpyAsync(fl.data(), c->pyr_flags.p, flag_bytes, hipMemcpyDeviceToHost, c->stream));
+            HIPC(hipStreamSynchronize(c->stream));
+            std::memcpy(&count, fl.data(), sizeof(count));
+            if (count <= cap) break;
+            if (pass == 1) {        // (cannot happen: the second pass runs with room for every record of the first)
+                set_error(std::string(who) + ": hit list overflowed twice");
+                return MTM_E_HIP;
+            }
+            MTMC(c->pyr_hits.ensure(sizeof(mtm_hit) * (size_t)count));
+        }
+        const unsigned long long* best = reinterpret_cast<const unsigned long long*>(fl.data()) + 1;
+        const int* nontrivial = reinterpret_cast<const int*>(fl.data() + sizeof(unsigned long long) * (1 + (size_t)n));
+        if (mode == MTM_PEAKS_GLOBAL) {
+            for (int t = 0; t < n; ++t) {
+                unsigned long long key;
+                std::memcpy(&key, best + t, sizeof(key));
+                if (key == 0ull) continue;
+                const TemplDev& d = c->td_host[(size_t)t];
+                const uint32_t o = (uint32_t)(key >> 32);
+                const long long idx = 0xFFFFFFFFll - (long long)(key & 0xFFFFFFFFull);
+                const uint32_t b = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;      // mf_order_float
+                float q;
+                std::memcpy(&q, &b, sizeof(q));
+                mtm_hit hrec;
+                hrec.templ_idx = t;
+                hrec.x = (int32_t)(idx % d.ow);
+                hrec.y = (int32_t)(idx / d.ow);
+                hrec.w = d.cols;
+                hrec.h = d.rows;
+                hrec.score = (mode_min ? -q : q) + 0.0f;
+                hits.push_back(hrec);
+            }
+        } else {
+            std::vector<mtm_hit> raw((size_t)count);
+            if (count > 0)
+                HIPC(hipMemcpy(raw.data(), c->pyr_hits.p, sizeof(mtm_hit) * (size_t)count, hipMemcpyDeviceToHost));
+            for (const mtm_hit& r : raw) {
+                int nt;
+                std::memcpy(&nt, nontrivial + r.templ_idx, sizeof(nt));
+                if (nt) hits.push_back(r);      // a template whose windows hold no non-maximum position has no peaks
+            }
+            sort_hits(hits, mode_min);
+        }
+    }
+    c->last_hits = hits;
+    c->timing.n_hits = (int64_t)hits.size();
+    *n_out = (int64_t)hits.size();
+    if ((int64_t)hits.size() > capacity) {
+        set_error(std::string(who) + ": output capacity too small");
+        return MTM_E_OVERFLOW;
+    }
+    if (!hits.empty()) std::memcpy(out, hits.data(), sizeof(mtm_hit) * hits.size());
+    return MTM_OK;
+}
+
+}  // extern "C"

@@ -112,6 +112,9 @@ extern "C" {
 #define MTM_OPT_BATCH_MAX_ROWS 8 /* mtm_find_matches_batch: the most stacked image rows in one chunk (1 .. 65535, the default:
                                    the tightest bound a tall map has to respect, kBatchMaxRows in csrc/mtm_ctx.h).  A chunk
                                    holds at least one image; smaller values only split a batch into more chunks. */
+#define MTM_OPT_BOXES_MAX_FLOATS 9 /* mtm_find_matches_boxes: the most unit score-map floats held on the device at once
+                                   (default 2^26, 256 MB).  Units whose maps together exceed it run in chunks of whole units
+                                   (a chunk holds at least one unit); results do not depend on it. */
 
 /* error codes */
 #define MTM_OK            0
@@ -142,6 +145,13 @@ typedef struct mtm_hit {
     int32_t x, y, w, h;
     float   score;
 } mtm_hit;
+
+/* One (region, template) pair of mtm_find_matches_boxes: a template of the last mtm_set_templates and the region of the
+ * image it is searched in, rows y0 .. y0 + rows - 1 and columns x0 .. x0 + cols - 1 (already clipped to the image). */
+typedef struct mtm_box_unit {
+    int32_t templ_idx;
+    int32_t y0, x0, rows, cols;
+} mtm_box_unit;
 
 /* timing of the last mtm_find_matches call, measured with HIP events on the context's stream */
 typedef struct mtm_timing {
@@ -344,6 +354,21 @@ int mtm_find_matches_pyramid(mtm_ctx* ctx, const void* px, int rows, int cols, i
                              double score_threshold, int radius, int max_candidates, mtm_hit* out, int64_t capacity,
                              int64_t* n_out);
 
+/* Many searchBoxes of one image in one call: what n_units calls of mtm_find_matches on the crops return -
+ * unit u's template (units[u].templ_idx, of the last mtm_set_templates) searched in the region of unit u as if the crop
+ * were the whole image: its own score map of (rows - h + 1) x (cols - w + 1) outputs, whose edges are the map border of
+ * MTM_OPT_PEAK_BORDER's rule, mtm_find_matches' "no non-maximum pixel, no peaks" rule and 1-D / 1x1 rules per unit,
+ * mode MTM_PEAKS_GLOBAL the unit's extremum (ties: first in row-major order).  Scores are bit for bit those of
+ * mtm_score_map on the crop.  The image (uint8 with 1 or 3 channels, or single-channel uint16, the templates' pixel type;
+ * unmasked templates, method 0..5) crosses PCIe once.  Hits come grouped by unit in unit order, each group in
+ * mtm_find_matches' order; counts[u] = the number of records of unit u; coordinates are in the full image.  A template
+ * larger than its unit's region, or a region outside the image, returns MTM_E_INVALID.  Units whose maps together exceed
+ * MTM_OPT_BOXES_MAX_FLOATS run in chunks of whole units.  On MTM_E_OVERFLOW *n_out holds the capacity needed, counts are
+ * written and mtm_last_hits returns the records.  The image becomes the context's current image. */
+int mtm_find_matches_boxes(mtm_ctx* ctx, const void* px, int rows, int cols, int chans, int dtype,
+                           int64_t row_stride_bytes, const mtm_box_unit* units, int n_units, int mode,
+                           double score_threshold, mtm_hit* out, int64_t capacity, int64_t* counts, int64_t* n_out);
+
 /* Stream form of mtm_find_matches ("thousands of images", reference
  * tutorials/Tutorial3-SpeedingUp.ipynb:564: same templates, one image after the other): returns the
  * hits of the CURRENT image exactly like mtm_find_matches and makes `next_px` the current image for
@@ -385,6 +410,14 @@ int mtm_get_timing(mtm_ctx* ctx, mtm_timing* out);
  * keep[] receives indices into hits[]; capacity of keep must be >= n. */
 int mtm_nms(const mtm_hit* hits, int64_t n, double score_threshold, int ascending,
             int64_t n_object, double max_overlap, int32_t* keep, int64_t* n_keep);
+
+/* mtm_nms on each of n_seg consecutive segments of hits[] (segment s: seg_counts[s] records, in mtm_find_matches' order) as
+ * MTM.matchTemplates applies it to one search's hit list: a segment of at most one hit is kept as it is (MTM/NMS.py
+ * returns such a list unchanged), every other one goes through the suppression without a limit on the count.  keep[]
+ * receives the kept records' indices into hits[], segment after segment; keep_counts[s] = how many of them are segment s's.
+ * Capacity of keep: the total number of hits.  Host code (C++), no GPU needed. */
+int mtm_nms_segments(const mtm_hit* hits, const int64_t* seg_counts, int64_t n_seg, double score_threshold, int ascending,
+                     double max_overlap, int32_t* keep, int64_t* keep_counts);
 
 /* ---- multi-GPU, one process: a group of per-device contexts -------------------------------- */
 /* The units (templates / rotations / scales) of a search are independent given the image - the reference runs

@@ -25,7 +25,7 @@ from .version import __version__
 pinned_empty = _lib.pinned_empty        # numpy arrays in page-locked memory (faster uploads); optional
 
 __all__ = ["NMS", "Hit", "matchTemplates", "findMatches", "computeScoreMap", "TemplateMatcher", "matchTemplatesBatch",
-           "findMatchesPyramid", "matchTemplatesPyramid",
+           "findMatchesPyramid", "matchTemplatesPyramid", "findMatchesInBoxes", "matchTemplatesInBoxes",
            "pinned_empty", "drawBoxesOnRGB",
            "drawBoxesOnGray", "TM_SQDIFF", "TM_SQDIFF_NORMED", "TM_CCORR", "TM_CCORR_NORMED",
            "TM_CCOEFF", "TM_CCOEFF_NORMED", "__version__"]
@@ -487,6 +487,28 @@ class TemplateMatcher:
                 raws = [self._ctx.find_matches_image(p[0], mode, self.score_threshold) for p in prepared]
         return [self._finish(raw, p[1], p[2]) for raw, p in zip(raws, prepared)]
 
+    def match_boxes(self, image: np.ndarray, searchBoxes) -> List[List[Hit]]:
+        """
+        ``matchTemplatesInBoxes(listTemplates, image, searchBoxes, ...)`` with the constructor's arguments: the same hits
+        and exceptions, on this matcher's context with its templates resident across calls (a tracking loop that searches
+        a few boxes per frame uploads only the frame).  Scope as matchTemplatesInBoxes', for every template of the list.
+        """
+        from . import boxes
+        self._not_streaming()
+        with self._ctx.lock:
+            if len(searchBoxes) and self.method in boxes._SCOPE_METHODS:     # every resident template is in scope
+                boxes._check_scope(self.listTemplates, image, range(len(self.listTemplates)), self.method,
+                                   boxes._SCOPE_METHODS)
+            # the call may replace the resident templates: until it returns, nothing is known to be resident (a call that
+            # raises leaves match() to upload again)
+            before, self._uploaded_for = self._uploaded_for, None
+            hits, uploaded = boxes._match_boxes(self.listTemplates, image, searchBoxes, self.method, self.N_object,
+                                                self.score_threshold, self.maxOverlap, self._ctx, True)
+            # the whole list is resident when templates were set, as _upload would have made it for this image; otherwise
+            # the context still holds what it held before
+            self._uploaded_for = (str(image.dtype), 1 if image.ndim == 2 else image.shape[2]) if uploaded else before
+        return hits
+
     def match_stream(self, images, searchBox: Optional[BBox] = None):
         """
         Generator over an iterable of images: yields ``match(image)`` for each, in order.  The upload
@@ -657,3 +679,4 @@ def drawBoxesOnGray(image: np.ndarray, listHit: Sequence[Hit], boxThickness: int
 
 from . import augment  # noqa: E402,F401  (template augmentation / downscaled matching helpers)
 from .pyramid import findMatchesPyramid, matchTemplatesPyramid  # noqa: E402  (coarse-to-fine search)
+from .boxes import findMatchesInBoxes, matchTemplatesInBoxes  # noqa: E402  (many searchBoxes in one call)

@@ -24,8 +24,9 @@ BORDER_CONSTANT, BORDER_NEAREST = 0, 1
 KERNEL_AUTO, KERNEL_NAIVE, KERNEL_DOT4, KERNEL_MFMA = 0, 1, 2, 3
 OPT_KERNEL, OPT_PEAK_BORDER, OPT_HIT_CAPACITY, OPT_DOT4_VARIANT, OPT_EXACT_DIV, OPT_HITS_ONLY, OPT_F32_MFMA = 1, 2, 3, 4, 5, 6, 7
 OPT_BATCH_MAX_ROWS = 8
+OPT_BOXES_MAX_FLOATS = 9
 ALL_OPTIONS = (OPT_KERNEL, OPT_PEAK_BORDER, OPT_HIT_CAPACITY, OPT_DOT4_VARIANT, OPT_EXACT_DIV, OPT_HITS_ONLY, OPT_F32_MFMA,
-               OPT_BATCH_MAX_ROWS)
+               OPT_BATCH_MAX_ROWS, OPT_BOXES_MAX_FLOATS)
 BATCH_MAX_ROWS = 65535      # the default (and largest) MTM_OPT_BATCH_MAX_ROWS: stacked rows of one mtm_find_matches_batch chunk
 POISON_SCRATCH, POISON_LDS, POISON_ARENAS = 1, 2, 4
 E_OVERFLOW = -5
@@ -58,6 +59,8 @@ class MtmTiming(ctypes.Structure):
 
 HIT_DTYPE = np.dtype([("templ_idx", "<i4"), ("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"),
                       ("score", "<f4")])
+# mtm_box_unit: a template index and the region (y0, x0, rows, cols) it is searched in
+BOX_UNIT_DTYPE = np.dtype([("templ_idx", "<i4"), ("y0", "<i4"), ("x0", "<i4"), ("rows", "<i4"), ("cols", "<i4")])
 assert HIT_DTYPE.itemsize == ctypes.sizeof(MtmHit) == 24
 # mtm_templ as a numpy record: a whole template list is filled column-wise instead of field by field
 TEMPL_DTYPE = np.dtype([("px", "<u8"), ("mask", "<u8"), ("rows", "<i4"), ("cols", "<i4"), ("chans", "<i4"),
@@ -106,6 +109,10 @@ SYMBOLS = {
                                                 ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                                 ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                                 _P(ctypes.c_int64)]),
+    "mtm_find_matches_boxes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_double, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                              _P(ctypes.c_int64)]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
                                              ctypes.c_int64, _P(ctypes.c_int64), ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
@@ -116,6 +123,8 @@ SYMBOLS = {
     "mtm_get_timing": (ctypes.c_int, [ctypes.c_void_p, _P(MtmTiming)]),
     "mtm_nms": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_int,
                                ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, _P(ctypes.c_int64)]),
+    "mtm_nms_segments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_int,
+                                        ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_group_create": (ctypes.c_int, [_P(ctypes.c_void_p), _P(ctypes.c_int), ctypes.c_int]),
     "mtm_group_destroy": (None, [ctypes.c_void_p]),
     "mtm_group_size": (ctypes.c_int, [ctypes.c_void_p]),
@@ -478,6 +487,28 @@ class Context(_RecordMemo):
         check(rc, "mtm_find_matches_pyramid")
         return out[:n.value]
 
+    def find_matches_boxes(self, image, units, mode, score_threshold):
+        """The current templates searched in many regions of one image in one native call (mtm_find_matches_boxes).
+        `units`: BOX_UNIT_DTYPE records.  Returns (hits, counts): the records grouped by unit (full-image coordinates,
+        templ_idx = the unit's template) and the number of records of each unit."""
+        a, ptr, stride = _pixel_rows(image)
+        chans = 1 if a.ndim == 2 else a.shape[2]
+        units = np.ascontiguousarray(units, dtype=BOX_UNIT_DTYPE)
+        n = len(units)
+        counts = np.zeros(n, dtype=np.int64)
+        cap = max(4096, 16 * n)
+        out = np.empty(cap, dtype=HIT_DTYPE)
+        total = ctypes.c_int64(0)
+        rc = self._lib.mtm_find_matches_boxes(self._h, ptr, a.shape[0], a.shape[1], chans, _dtype_code(a), stride,
+                                              units.ctypes.data, n, int(mode), float(score_threshold), out.ctypes.data, cap,
+                                              counts.ctypes.data, ctypes.byref(total))
+        if rc == E_OVERFLOW:        # the records stay in the context; counts are filled
+            cap = int(total.value)
+            out = np.empty(cap, dtype=HIT_DTYPE)
+            rc = self._lib.mtm_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(total))
+        check(rc, "mtm_find_matches_boxes")
+        return out[:total.value], counts
+
     def find_matches_batch(self, images, mode, score_threshold):
         """Images of one shape and dtype against the current templates in one native call (mtm_find_matches_batch): a list
         of hit arrays, one per image, each what find_matches_image returns for that image alone.  uint8 / uint16 only."""
@@ -786,6 +817,22 @@ def nms_hits(hits, score_threshold, max_overlap, ascending=False):
     check(load().mtm_nms(hits.ctypes.data, n, float(score_threshold), int(bool(ascending)), -1, float(max_overlap),
                          keep.ctypes.data, ctypes.byref(m)), "mtm_nms")
     return keep[:m.value]
+
+
+def nms_segments(hits, counts, score_threshold, max_overlap, ascending=False):
+    """nms_hits on each of the consecutive segments of `hits` (counts[s] records each) as matchTemplates applies it to one
+    search's list (a segment of at most one hit is kept as it is), in one native call (mtm_nms_segments).  Returns the
+    kept records' indices into `hits`, segment after segment, and the number kept per segment."""
+    if hits.dtype != HIT_DTYPE or not hits.flags.c_contiguous:
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    counts = np.ascontiguousarray(counts, dtype=np.int64)
+    keep = np.empty(max(len(hits), 1), dtype=np.int32)
+    kept = np.zeros(max(len(counts), 1), dtype=np.int64)
+    check(load().mtm_nms_segments(hits.ctypes.data, counts.ctypes.data, len(counts), float(score_threshold),
+                                  int(bool(ascending)), float(max_overlap), keep.ctypes.data, kept.ctypes.data),
+          "mtm_nms_segments")
+    kept = kept[:len(counts)]
+    return keep[:int(kept.sum())], kept
 
 
 _default_ctx = None

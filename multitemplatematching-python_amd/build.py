@@ -23,12 +23,12 @@ _TAG = os.environ.get("MTM_BUILD_TAG", "")
 OBJ = os.path.join(CSRC, "build" + ("_" + _TAG if _TAG else ""))
 LIB = os.path.join(HERE, "MTM", "libmtm_hip%s.so" % ("_" + _TAG if _TAG else ""))
 STAMP = LIB + ".stamp"
-SOURCES = ["mtm_context.hip", "mtm_placement.hip", "mtm_launch.hip", "mtm_api.hip", "mtm_comm.hip", "mtm_mfma_plain.hip", "mtm_mfma_rm.hip", "mtm_mfma_ext.hip", "mtm_mfma_kp.hip", "mtm_mfma_rows.hip", "mtm_bf16.hip", "mtm_pyramid.hip",
+SOURCES = ["mtm_context.hip", "mtm_placement.hip", "mtm_launch.hip", "mtm_api.hip", "mtm_comm.hip", "mtm_mfma_plain.hip", "mtm_mfma_rm.hip", "mtm_mfma_ext.hip", "mtm_mfma_kp.hip", "mtm_mfma_rows.hip", "mtm_bf16.hip", "mtm_pyramid.hip", "mtm_boxes.hip",
            "mtm_host.cpp", "mtm_group.cpp"]
 HEADERS = ["mtm_ctx.h", "mtm_k_image.hip.h", "mtm_k_stats.hip.h", "mtm_k_score.hip.h", "mtm_k_peaks.hip.h", "mtm_score_params.h",
            "mtm_templates_params.h", "mtm_device_util.hip.h", "mtm_mfma.hip.h", "mtm_mfma_params.h", "mtm_templates.hip.h",
            "mtm_bf16.hip.h", "mtm_bf16_params.h", "mtm_refine.hip.h", "mtm_mfma_step_asm.inc", "mtm_kernels.h", "mtm_internal.h",
-           "mtm_k_nms.hip.h", "mtm_nms_core.h",
+           "mtm_k_nms.hip.h", "mtm_nms_core.h", "mtm_k_window.hip.h",
            os.path.join("..", "..", "include", "mtm_hip.h")]
 # -save-temps=obj: the device assembly of every unit stays next to its object (csrc/build/*-gfx950.s) - what
 # tools/spill_exec_scan.py and tests/test_abi_cpu.py::test_no_spill_ahead_of_an_exec_restore read (this compiler

@@ -1,0 +1,429 @@
+// libmtm_hip.so - many searchBoxes of one image in one call (mtm_find_matches_boxes): every (region, template)
+// pair - a unit - gets the score map of its crop, computed tile by tile over the whole chip with the exact integer sums and
+// the epilogue of every other score kernel (boxes_score_kernel), and the peak rules of mtm_find_matches applied to that map
+// alone (boxes_peaks_kernel; 1-D and 1x1 maps on the host, as mtm_find_matches treats them).  uint8 (1 or 3 channels) and
+// single-channel uint16, unmasked templates of one mtm_set_templates call.
+#include "mtm_ctx.h"
+#include "mtm_device_util.hip.h"
+#include "mtm_k_window.hip.h"
+
+using namespace mtm;
+using namespace mtmi;
+
+namespace mtm {
+
+// A unit as the kernels see it: its template, the image pixel of its map's output (0, 0), the map's size and place in the
+// chunk's score buffer (row-major, ow floats per row).
+struct BoxUnit {
+    int t;
+    int y0, x0;
+    int oh, ow;
+    long long buf_off;
+};
+
+// One 16 x 16 tile of outputs of unit u (an index into the chunk's unit table), first output (ty0, tx0) of its map.
+struct BoxTile {
+    int u, ty0, tx0;
+};
+constexpr size_t kBoxLaunchTiles = (size_t)1 << 22;     // most work-groups (tiles) of one boxes_* launch
+
+// Grid: one work-group per tile of the chunk's tile table, so that a large region spreads over the chip and many small
+// ones fill it together.  The tile's windows are summed by win_tile_sums_u8 / win_tile_sums_u16 straight from the image's
+// planes (a unit's outputs only read pixels of its region) and finished by win_score: the exhaustive map's float32 values.
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void boxes_score_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
+                                                          const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
+                                                          const TemplDev* __restrict__ td, const BoxUnit* __restrict__ units,
+                                                          const BoxTile* __restrict__ tiles, float* __restrict__ buf,
+                                                          int method) {
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
+    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
+    const BoxTile K = tiles[blockIdx.x];
+    const BoxUnit U = units[K.u];
+    const TemplDev T = td[U.t];
+    const int h = T.rows, w = T.cols;
+    const uint8_t* tp = tpx + toff[U.t];
+    const int tid = threadIdx.x;
+    const double inv_area = 1.0 / ((double)h * (double)w);
+    unsigned long long corr, s2, s1[CH];
+    if constexpr (U16)
+        win_tile_sums_u16(Tl[0], Tl[1], Il[0], Il[1], img.u8, lo_b, img.u8_pitch, img.rows, img.cols, tp, h, w,
+                          U.y0 + K.ty0, U.x0 + K.tx0, corr, s1[0], s2);
+    else
+        win_tile_sums_u8<CH>(Tl[0], Il[0], img.u8, img.u8_plane, img.u8_pitch, img.rows, img.cols, tp, h, w, U.y0 + K.ty0,
+                             U.x0 + K.tx0, corr, s1, s2);
+    const int y = K.ty0 + tid / kWinTile, x = K.tx0 + tid % kWinTile;
+    if (y < U.oh && x < U.ow) buf[U.buf_off + (long long)y * U.ow + x] = win_score<CH>(method, T, inv_area, corr, s1, s2);
+}
+
+// Grid: the tiles again (local mode: only those of units with 2-D maps).  Per output of the unit's own map:
+//   local mode  - the peak test of peaks_kernel (v == max of its 3x3 neighbourhood, the unit map's edges padded by the
+//                 border rule `border`, v > thr_q in quality space); nontrivial[u] records that some output of the unit
+//                 differs from its neighbourhood's maximum.  Records carry the unit index in templ_idx.
+//   global mode - the unit's best (quality, first in row-major order) output into best[u] (atomicMax on
+//                 order(quality) << 32 | ~index, as extremum_kernel keys it).
+__global__ __launch_bounds__(256) void boxes_peaks_kernel(const BoxUnit* __restrict__ units, const BoxTile* __restrict__ tiles,
+                                                          const float* __restrict__ buf, const TemplDev* __restrict__ td,
+                                                          int mode_min, int global, float thr_q, int border,
+                                                          mtm_hit* __restrict__ hits, unsigned long long cap,
+                                                          unsigned long long* __restrict__ counter,
+                                                          unsigned long long* __restrict__ best, int* __restrict__ nontrivial) {
+    const BoxTile K = tiles[blockIdx.x];
+    const BoxUnit U = units[K.u];
+    const int tid = threadIdx.x;
+    const int y = K.ty0 + tid / kWinTile, x = K.tx0 + tid % kWinTile;
+    const bool on = y < U.oh && x < U.ow;
+    const float* m = buf + U.buf_off;
+    const float padv = (border == MTM_BORDER_CONSTANT) ? 0.0f : -INFINITY;
+    auto q_at = [&](int yy, int xx) -> float {      // quality at output (yy, xx) of the unit's map; the pad value outside it
+        if (yy < 0 || yy >= U.oh || xx < 0 || xx >= U.ow) return padv;
+        const float s = m[(long long)yy * U.ow + xx];
+        return mode_min ? -s : s;
+    };
+    const float v = on ? q_at(y, x) : padv;
+    if (global) {
+        unsigned long long key = 0ull;
+        if (on)
+            key = ((unsigned long long)mf_float_order(v) << 32) |
+                  (0xFFFFFFFFull - (unsigned long long)((long long)y * U.ow + x));
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const unsigned long long o = __shfl_xor(key, off);
+            key = o > key ? o : key;
+        }
+        if ((tid & 63) == 0 && key != 0ull) atomicMax(best + K.u, key);
+        return;
+    }
+    bool emit = false;
+    int nontriv = 0;
+    if (on) {
+        float mx = v;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) mx = fmaxf(mx, q_at(y + dy, x + dx));
+        if (!(v == mx)) nontriv = 1;
+        else emit = v > thr_q;
+    }
+    mtm_hit rec;
+    rec.templ_idx = K.u;
+    rec.x = x;
+    rec.y = y;
+    rec.w = td[U.t].cols;
+    rec.h = td[U.t].rows;
+    rec.score = mode_min ? -v : v;
+    cand_append(emit, counter, cap, hits, rec);
+    if (__syncthreads_or(nontriv) && tid == 0) nontrivial[K.u] = 1;
+}
+
+}  // namespace mtm
+
+namespace {
+
+// The byte planes of every template (uint8: [C][h][w]; uint16: high bytes, then low bytes) and the epilogue constants of
+// mtm_set_templates' statistics, uploaded once per template set.
+int prepare_box_templates(mtm_ctx* c, const std::vector<BlobTempl>& tl) {
+    if (c->box_blob == c->templ_blob) return MTM_OK;
+    const int n = (int)tl.size();
+    if ((int)c->templs.size() != n) {
+        set_error("mtm_find_matches_boxes: template set and its statistics differ in size");
+        return MTM_E_STATE;
+    }
+    c->box_blob.clear();
+    std::vector<uint8_t> planar;
+    std::vector<TemplDev> td((size_t)n, TemplDev{});
+    c->box_toff.assign((size_t)n, 0);
+    for (int i = 0; i < n; ++i) {
+        const BlobTempl& t = tl[(size_t)i];
+        const size_t plane = (size_t)t.rows * t.cols;
+        c->box_toff[(size_t)i] = (long long)planar.size();
+        if (t.dtype == MTM_U16) {
+            planar.resize(planar.size() + 2 * plane);
+            uint8_t* dst = planar.data() + c->box_toff[(size_t)i];
+            for (size_t p = 0; p < plane; ++p) {
+                uint16_t v;
+                std::memcpy(&v, t.px + 2 * p, sizeof(v));
+                dst[p] = (uint8_t)(v >> 8);
+                dst[plane + p] = (uint8_t)(v & 255u);
+            }
+        } else {
+            planar.resize(planar.size() + plane * t.chans);
+            uint8_t* dst = planar.data() + c->box_toff[(size_t)i];
+            for (size_t p = 0; p < plane; ++p)
+                for (int k = 0; k < t.chans; ++k) dst[(size_t)k * plane + p] = t.px[p * t.chans + k];
+        }
+        const HostTempl& ht = c->templs[(size_t)i];
+        TemplDev& d = td[(size_t)i];
+        for (int k = 0; k < kMaxChans; ++k) d.mean[k] = ht.st.mean[k];
+        d.templ_norm = ht.st.templ_norm;
+        d.templ_sum2 = ht.st.templ_sum2;
+        d.all_ones = ht.st.all_ones;
+        d.rows = t.rows;
+        d.cols = t.cols;
+    }
+    if (!planar.empty()) {
+        MTMC(c->box_tpx.ensure(planar.size()));
+        HIPC(hipMemcpy(c->box_tpx.p, planar.data(), planar.size(), hipMemcpyHostToDevice));
+    }
+    if (n > 0) {
+        MTMC(c->box_toff_dev.ensure(sizeof(long long) * (size_t)n));
+        HIPC(hipMemcpy(c->box_toff_dev.p, c->box_toff.data(), sizeof(long long) * (size_t)n, hipMemcpyHostToDevice));
+        MTMC(c->box_td.ensure(sizeof(TemplDev) * (size_t)n));
+        HIPC(hipMemcpy(c->box_td.p, td.data(), sizeof(TemplDev) * (size_t)n, hipMemcpyHostToDevice));
+    }
+    c->box_blob = c->templ_blob;
+    return MTM_OK;
+}
+
+// Units u0 .. u1 - 1 (whole units, their maps within the memory budget): maps, peaks, records.  Appends the records of
+// each unit, in mtm_find_matches' order and image coordinates, to `hits`, and their number to counts[u].
+int boxes_chunk(mtm_ctx* c, const mtm_box_unit* units, const std::vector<BlobTempl>& tl, int u0, int u1, int chans,
+                int dtype, int mode, float thr, std::vector<mtm_hit>& hits, int64_t* counts) {
+    const int nu = u1 - u0;
+    const bool mode_min = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_SQDIFF_NORMED;
+    const bool global = mode == MTM_PEAKS_GLOBAL;
+    // unit table: the maps of 2-D units first, those of 1-D / 1x1 units after them in one block (local mode reads that
+    // block back for the host's rules in one copy); tile table: the tiles of 2-D units first (the peak kernel's grid in
+    // local mode)
+    std::vector<BoxUnit> bu((size_t)nu);
+    std::vector<BoxTile> tiles;
+    long long off = 0, off1d = 0;
+    size_t n_tiles_2d = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 1) {
+            off1d = off;
+            n_tiles_2d = tiles.size();
+        }
+        for (int k = 0; k < nu; ++k) {
+            const mtm_box_unit& s = units[u0 + k];
+            const BlobTempl& t = tl[(size_t)s.templ_idx];
+            BoxUnit& b = bu[(size_t)k];
+            b.t = s.templ_idx;
+            b.y0 = s.y0;
+            b.x0 = s.x0;
+            b.oh = s.rows - t.rows + 1;
+            b.ow = s.cols - t.cols + 1;
+            const bool line = b.oh <= 1 || b.ow <= 1;
+            if (line != (pass == 1)) continue;
+            b.buf_off = off;
+            off += (long long)b.oh * b.ow;
+            for (int ty = 0; ty < b.oh; ty += kWinTile)
+                for (int tx = 0; tx < b.ow; tx += kWinTile) tiles.push_back(BoxTile{k, ty, tx});
+        }
+    }
+    const long long n1d_floats = off - off1d;
+    MTMC(c->box_units.ensure(sizeof(BoxUnit) * bu.size()));
+    MTMC(c->box_tiles.ensure(sizeof(BoxTile) * tiles.size()));
+    MTMC(c->box_buf.ensure(sizeof(float) * (size_t)off));
+    HIPC(hipMemcpyAsync(c->box_units.p, bu.data(), sizeof(BoxUnit) * bu.size(), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->box_tiles.p, tiles.data(), sizeof(BoxTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
+
+    const ImageDev img = image_dev(c);
+    const uint8_t* lo_b = c->slot[c->cur].u8b.as<uint8_t>() + img.u8_plane;     // uint16: [high ^ 0x80][low ^ 0x80]
+    // (both kernels run over the tile table in slices of at most kBoxLaunchTiles work-groups: one dispatch stays far below
+    // 2^32 work items however many tiles a chunk or a single unit has)
+#define MTM_BOX_LAUNCH(CH, U16)                                                                                              \
+    hipLaunchKernelGGL((boxes_score_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, lo_b,                          \
+                       c->box_tpx.as<uint8_t>(), c->box_toff_dev.as<long long>(), c->box_td.as<TemplDev>(),                  \
+                       c->box_units.as<BoxUnit>(), c->box_tiles.as<BoxTile>() + t0, c->box_buf.as<float>(), c->method)
+    for (size_t t0 = 0; t0 < tiles.size(); t0 += kBoxLaunchTiles) {
+        const unsigned nt = (unsigned)std::min(kBoxLaunchTiles, tiles.size() - t0);
+        if (dtype == MTM_U16) MTM_BOX_LAUNCH(1, true);
+        else if (chans == 1) MTM_BOX_LAUNCH(1, false);
+        else MTM_BOX_LAUNCH(3, false);
+        HIPC(hipGetLastError());
+    }
+#undef MTM_BOX_LAUNCH
+
+    // [hit counter][best key per unit][nontrivial flag per unit]
+    const size_t flag_bytes = sizeof(unsigned long long) * (1 + (size_t)nu) + sizeof(int) * (size_t)nu;
+    MTMC(c->box_flags.ensure(flag_bytes));
+    std::vector<uint8_t> fl(flag_bytes);
+    std::vector<float> maps1d(global ? 0 : (size_t)n1d_floats);
+    unsigned long long cap = (unsigned long long)std::max<int64_t>(1, c->hit_cap), count = 0;
+    const size_t peak_tiles = global ? tiles.size() : n_tiles_2d;
+    for (int pass = 0; pass < 2; ++pass) {          // (a list that overflowed: once more, large enough)
+        MTMC(c->box_hits.ensure(sizeof(mtm_hit) * (size_t)cap));
+        HIPC(hipMemsetAsync(c->box_flags.p, 0, flag_bytes, c->stream));
+        unsigned long long* counter = c->box_flags.as<unsigned long long>();
+        int* nontrivial = reinterpret_cast<int*>(counter + 1 + nu);
+        for (size_t t0 = 0; t0 < peak_tiles; t0 += kBoxLaunchTiles) {
+            const unsigned nt = (unsigned)std::min(kBoxLaunchTiles, peak_tiles - t0);
+            hipLaunchKernelGGL(boxes_peaks_kernel, dim3(nt), dim3(256), 0, c->stream, c->box_units.as<BoxUnit>(),
+                               c->box_tiles.as<BoxTile>() + t0, c->box_buf.as<float>(), c->box_td.as<TemplDev>(),
+                               mode_min ? 1 : 0, global ? 1 : 0, mode_min ? -thr : thr, c->opt_border,
+                               c->box_hits.as<mtm_hit>(), cap, counter, counter + 1, nontrivial);
+            HIPC(hipGetLastError());
+        }
+        HIPC(hipMemcpyAsync(fl.data(), c->box_flags.p, flag_bytes, hipMemcpyDeviceToHost, c->stream));
+        if (pass == 0 && !maps1d.empty())
+            HIPC(hipMemcpyAsync(maps1d.data(), c->box_buf.as<float>() + off1d, sizeof(float) * maps1d.size(),
+                                hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        std::memcpy(&count, fl.data(), sizeof(count));
+        if (count <= cap) break;
+        if (pass == 1) {            // (cannot happen: the second pass runs with room for every record of the first)
+            set_error("mtm_find_matches_boxes: hit list overflowed twice");
+            return MTM_E_HIP;
+        }
+        cap = count + 1024;
+    }
+    const unsigned long long* best = reinterpret_cast<const unsigned long long*>(fl.data()) + 1;
+    const int* nontrivial = reinterpret_cast<const int*>(fl.data() + sizeof(unsigned long long) * (1 + (size_t)nu));
+    std::vector<mtm_hit> ch;            // this chunk's records, templ_idx = the unit's index in the chunk, unit coordinates
+    if (global) {
+        for (int k = 0; k < nu; ++k) {
+            unsigned long long key;
+            std::memcpy(&key, best + k, sizeof(key));
+            const BoxUnit& b = bu[(size_t)k];
+            const uint32_t o = (uint32_t)(key >> 32);
+            const long long idx = 0xFFFFFFFFll - (long long)(key & 0xFFFFFFFFull);
+            const uint32_t bits = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;      // mf_order_float
+            float q;
+            std::memcpy(&q, &bits, sizeof(q));
+            mtm_hit h;
+            h.templ_idx = k;
+            h.x = (int32_t)(idx % b.ow);
+            h.y = (int32_t)(idx / b.ow);
+            h.w = tl[(size_t)b.t].cols;
+            h.h = tl[(size_t)b.t].rows;
+            h.score = key ? (mode_min ? -q : q) + 0.0f : NAN;
+            ch.push_back(h);
+        }
+    } else {
+        std::vector<mtm_hit> raw((size_t)count);
+        if (count > 0)
+            HIPC(hipMemcpy(raw.data(), c->box_hits.p, sizeof(mtm_hit) * (size_t)count, hipMemcpyDeviceToHost));
+        for (const mtm_hit& r : raw) {
+            int nt;
+            std::memcpy(&nt, nontrivial + r.templ_idx, sizeof(nt));
+            if (nt) ch.push_back(r);        // a unit map with no output that differs from its neighbourhood's max has no peaks
+        }
+        // 1-D and 1x1 unit maps (MTM/__init__.py:25-41), as mtm_find_matches treats a whole map of that shape
+        for (int k = 0; k < nu; ++k) {
+            const BoxUnit& b = bu[(size_t)k];
+            if (b.oh > 1 && b.ow > 1) continue;
+            const float* line = maps1d.data() + (b.buf_off - off1d);
+            const int len = std::max(b.oh, b.ow);
+            std::vector<int> pk;
+            if (len == 1) {
+                const float v = mode_min ? -line[0] : line[0];
+                if (v >= (mode_min ? -thr : thr)) pk.push_back(0);
+            } else {
+                pk = find_peaks_1d(line, len, 1, mode_min ? -thr : thr, mode_min);
+            }
+            for (int i : pk) {
+                mtm_hit h;
+                h.templ_idx = k;
+                h.x = b.oh == 1 ? i : 0;
+                h.y = b.oh == 1 ? 0 : i;
+                h.w = tl[(size_t)b.t].cols;
+                h.h = tl[(size_t)b.t].rows;
+                h.score = line[(size_t)i];
+                ch.push_back(h);
+            }
+        }
+        sort_hits(ch, mode_min);
+    }
+    for (mtm_hit h : ch) {
+        const BoxUnit& b = bu[(size_t)h.templ_idx];
+        ++counts[u0 + h.templ_idx];
+        h.templ_idx = b.t;
+        h.x += b.x0;
+        h.y += b.y0;
+        hits.push_back(h);
+    }
+    return MTM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtm_find_matches_boxes(mtm_ctx* c, const void* px, int rows, int cols, int chans, int dtype, int64_t row_stride_bytes,
+                           const mtm_box_unit* units, int n_units, int mode, double score_threshold, mtm_hit* out,
+                           int64_t capacity, int64_t* counts, int64_t* n_out) {
+    const char* who = "mtm_find_matches_boxes";
+    if (!c || !n_out || n_units < 0 || (n_units > 0 && (!units || !counts)) || capacity < 0 || (capacity > 0 && !out) ||
+        (mode != MTM_PEAKS_LOCAL && mode != MTM_PEAKS_GLOBAL)) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    MTMC(check_image_args(px, rows, cols, chans, dtype, row_stride_bytes, who));
+    if (!((dtype == MTM_U8 && (chans == 1 || chans == 3)) || (dtype == MTM_U16 && chans == 1))) {
+        set_error(std::string(who) + ": takes uint8 images with 1 or 3 channels and single-channel uint16 images");
+        return MTM_E_INVALID;
+    }
+    if (!c->have_templ) {
+        set_error(std::string(who) + ": no templates set");
+        return MTM_E_STATE;
+    }
+    std::vector<BlobTempl> tl;
+    MTMC(parse_templ_blob(c->templ_blob, tl, who, true));
+    for (int u = 0; u < n_units; ++u) {
+        const mtm_box_unit& s = units[u];
+        const std::string where = std::string(who) + ": unit " + std::to_string(u);
+        if (s.templ_idx < 0 || s.templ_idx >= (int)tl.size()) {
+            set_error(where + ": template index out of range");
+            return MTM_E_INVALID;
+        }
+        if (s.y0 < 0 || s.x0 < 0 || s.rows < 1 || s.cols < 1 || s.rows > rows - s.y0 || s.cols > cols - s.x0) {
+            set_error(where + ": region outside the image");
+            return MTM_E_INVALID;
+        }
+        const BlobTempl& t = tl[(size_t)s.templ_idx];
+        if (t.dtype != dtype || t.chans != chans) {
+            set_error(where + ": template and image differ in pixel type or channel count");
+            return MTM_E_INVALID;
+        }
+        if (t.rows > s.rows || t.cols > s.cols) {
+            set_error(where + ": template larger than the region");
+            return MTM_E_INVALID;
+        }
+        // (uint16: correlations of up to 2^21 pixels stay below 2^53, exact in float64 as the exhaustive kernels need)
+        if (dtype == MTM_U16 && (long long)t.rows * t.cols > (1ll << 21)) {
+            set_error(where + ": uint16 template of more than 2^21 pixels");
+            return MTM_E_INVALID;
+        }
+    }
+    *n_out = 0;
+    for (int u = 0; u < n_units; ++u) counts[u] = 0;
+    HIPC(hipSetDevice(c->device));
+    MTMC(prepare_box_templates(c, tl));
+
+    // ONE upload of the image; every unit reads its region from the same planes
+    c->timing = mtm_timing{};
+    c->maps_valid = false;
+    c->last_hits.clear();
+    MTMC(upload_image(c, c->slot[c->cur], px, row_stride_bytes, rows, cols, chans, dtype, c->stream, 1));
+    adopt_image(c, rows, cols, chans, dtype);
+
+    const float thr = (float)score_threshold;       // numpy compares the float32 map with the threshold in float32
+    std::vector<mtm_hit> hits;
+    for (int u0 = 0; u0 < n_units;) {
+        // whole units while their maps fit the budget (at least one)
+        long long floats = 0;
+        int u1 = u0;
+        while (u1 < n_units) {
+            const BlobTempl& t = tl[(size_t)units[u1].templ_idx];
+            const long long f = (long long)(units[u1].rows - t.rows + 1) * (units[u1].cols - t.cols + 1);
+            if (u1 > u0 && floats + f > c->boxes_max_floats) break;
+            floats += f;
+            ++u1;
+        }
+        MTMC(boxes_chunk(c, units, tl, u0, u1, chans, dtype, mode, thr, hits, counts));
+        u0 = u1;
+    }
+    c->last_hits = hits;
+    c->timing.n_hits = (int64_t)hits.size();
+    *n_out = (int64_t)hits.size();
+    if ((int64_t)hits.size() > capacity) {
+        set_error(std::string(who) + ": output capacity too small");
+        return MTM_E_OVERFLOW;
+    }
+    if (!hits.empty()) std::memcpy(out, hits.data(), sizeof(mtm_hit) * hits.size());
+    return MTM_OK;
+}
+
+}  // extern "C"

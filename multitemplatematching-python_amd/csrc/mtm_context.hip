@@ -366,6 +366,9 @@ void mtm_ctx_destroy(mtm_ctx* c) {
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->pyr_sub) mtm_ctx_destroy(c->pyr_sub);
     for (DevBuf* b : {&c->pyr_tpx, &c->pyr_toff_dev, &c->pyr_wins, &c->pyr_buf, &c->pyr_hits, &c->pyr_flags}) b->release();
+    for (DevBuf* b : {&c->box_tpx, &c->box_toff_dev, &c->box_td, &c->box_units, &c->box_tiles, &c->box_buf, &c->box_hits,
+                      &c->box_flags})
+        b->release();
     for (auto& sl : c->slot)
         for (DevBuf* b : {&sl.raw, &sl.u8, &sl.u8b, &sl.f32}) b->release();
     for (DevBuf* b : {&c->tsrc, &c->usrc_dev, &c->tsums_dev, &c->tgather, &c->slab_raw, &c->seg_flags, &c->hits_t, &c->nms_buf, &c->td_u, &c->td_v,
@@ -456,6 +459,10 @@ int mtm_set_option(mtm_ctx* c, int option, int64_t value) {
             if (value < 1 || value > kBatchMaxRows) break;
             c->batch_max_rows = (int)value;
             return MTM_OK;
+        case MTM_OPT_BOXES_MAX_FLOATS:
+            if (value < 1) break;
+            c->boxes_max_floats = value;
+            return MTM_OK;
         default: break;
     }
     set_error("mtm_set_option: bad option or value");
@@ -473,6 +480,7 @@ int mtm_get_option(mtm_ctx* c, int option, int64_t* value) {
         case MTM_OPT_F32_MFMA: *value = c->f32_mfma; return MTM_OK;
         case MTM_OPT_DOT4_VARIANT: *value = c->dot_variant; return MTM_OK;
         case MTM_OPT_BATCH_MAX_ROWS: *value = c->batch_max_rows; return MTM_OK;
+        case MTM_OPT_BOXES_MAX_FLOATS: *value = c->boxes_max_floats; return MTM_OK;
         default: break;
     }
     set_error("mtm_get_option: bad option");

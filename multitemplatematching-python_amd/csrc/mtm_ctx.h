@@ -2,7 +2,7 @@
 // translation units share.  Units: mtm_context.hip (context, options, image upload), mtm_placement.hip (template sets ->
 // size classes, packs, constants), mtm_launch.hip (window statistics and score-map launches), mtm_api.hip
 // (mtm_find_matches and friends: peak extraction, hit lists), mtm_comm.hip (RCCL hit exchange), mtm_pyramid.hip (the
-// coarse-to-fine search).  Not part of the ABI.
+// coarse-to-fine search), mtm_boxes.hip (many searchBoxes in one call).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -373,6 +373,13 @@ struct mtm_ctx {
     int pyr_factor = 0;
     std::vector<long long> pyr_toff;
     DevBuf pyr_tpx, pyr_toff_dev, pyr_wins, pyr_buf, pyr_hits, pyr_flags;
+    // mtm_find_matches_boxes (mtm_boxes.hip): the templates' pixels as byte planes (uint8: [C][h][w]; uint16: high bytes,
+    // then low bytes) at box_toff[t], their epilogue constants (box_td), all made for the template set box_blob; the
+    // per-call tables, unit maps, hit list and flags.  boxes_max_floats: MTM_OPT_BOXES_MAX_FLOATS.
+    std::vector<uint8_t> box_blob;
+    std::vector<long long> box_toff;
+    DevBuf box_tpx, box_toff_dev, box_td, box_units, box_tiles, box_buf, box_hits, box_flags;
+    int64_t boxes_max_floats = 1ll << 26;
 
     // RCCL
     void* rccl_lib = nullptr;
@@ -505,6 +512,14 @@ int upload_image(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* src, int64_t sr
 int upload_image_stack(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* const* px, int n, int64_t src_stride, int rows,
                        int cols, int chans, int dtype, hipStream_t stream);
 void adopt_image(mtm_ctx* c, int rows, int cols, int chans, int dtype);
+// One template of the last mtm_set_templates as its bytes in mtm_ctx::templ_blob (interleaved, tightly packed rows of
+// `dtype` pixels); parse_templ_blob (mtm_pyramid.hip) lists them - unmasked uint8 templates, with `u16_ok` also unmasked
+// single-channel uint16 ones - for mtm_find_matches_pyramid and mtm_find_matches_boxes.
+struct BlobTempl {
+    int rows, cols, chans, dtype;
+    const uint8_t* px;
+};
+int parse_templ_blob(const std::vector<uint8_t>& b, std::vector<BlobTempl>& out, const char* who, bool u16_ok);
 // The planes of `dst`'s current slot from the raw uint8 image already in `src` (src_rows x src_cols, tightly packed),
 // area-downscaled by `factor` on `stream`; `dst` adopts the downscaled image (mtm_find_matches_pyramid's coarse level).
 int derive_downscaled_u8(mtm_ctx* dst, const mtm_ctx::ImageSlot& src, int src_rows, int src_cols, int chans, int factor,

@@ -448,4 +448,45 @@ int mtm_nms(const mtm_hit* hits, int64_t n, double score_threshold, int ascendin
     return MTM_OK;
 }
 
+int mtm_nms_segments(const mtm_hit* hits, const int64_t* seg_counts, int64_t n_seg, double score_threshold, int ascending,
+                     double max_overlap, int32_t* keep, int64_t* keep_counts) {
+    if (n_seg < 0 || (n_seg > 0 && (seg_counts == nullptr || keep_counts == nullptr))) {
+        mtm::set_error("mtm_nms_segments: bad arguments");
+        return MTM_E_INVALID;
+    }
+    int64_t total = 0;
+    for (int64_t s = 0; s < n_seg; ++s) {
+        if (seg_counts[s] < 0) {
+            mtm::set_error("mtm_nms_segments: negative segment length");
+            return MTM_E_INVALID;
+        }
+        total += seg_counts[s];
+    }
+    if (total > 0 && (hits == nullptr || keep == nullptr)) {
+        mtm::set_error("mtm_nms_segments: bad arguments");
+        return MTM_E_INVALID;
+    }
+    // as mtm_nms: float32 scores (1 - score for the difference methods), the threshold transformed in double and narrowed
+    const float thr = (float)(ascending ? (1.0 - score_threshold) : score_threshold);
+    std::vector<float> scores;
+    std::vector<int32_t> kept;
+    int64_t off = 0, n_keep = 0;
+    for (int64_t s = 0; s < n_seg; ++s) {
+        const int64_t n = seg_counts[s];
+        const mtm_hit* h = hits + off;
+        if (n <= 1) {                                   // MTM/NMS.py: a list of one hit is returned as it is
+            for (int64_t i = 0; i < n; ++i) keep[n_keep++] = (int32_t)(off + i);
+            keep_counts[s] = n;
+        } else {
+            scores.resize((size_t)n);
+            for (int64_t i = 0; i < n; ++i) scores[(size_t)i] = ascending ? (1.0f - h[i].score) : h[i].score;
+            mtm::nms_boxes(h, n, scores.data(), thr, (float)max_overlap, kept);
+            for (int32_t k : kept) keep[n_keep++] = (int32_t)(off + k);
+            keep_counts[s] = (int64_t)kept.size();
+        }
+        off += n;
+    }
+    return MTM_OK;
+}
+
 }  // extern "C"

@@ -1,0 +1,169 @@
+// Exact window sums of one 16 x 16 tile of score-map outputs, for the kernels that score arbitrary regions of a map
+// (pyr_window_kernel, mtm_pyramid.hip; boxes_score_kernel, mtm_boxes.hip): the template streams through LDS in chunks of
+// kWinKR x kWinKC pixels next to the image rows the tile's windows cover, and v_dot4_u32_u8 forms the correlation and the
+// window sums S1 (per channel) and S2 of the chunk in uint32; they are flushed to uint64 after every chunk, so the
+// template's size is bounded by neither LDS nor the uint32 range.  Thread (ly, lx) = (tid / 16, tid % 16) of a 256-thread
+// work-group owns output (oy0 + ly, ox0 + lx), whose window's top-left pixel is image pixel (oy0 + ly, ox0 + lx).
+// Image pixels outside `rows` x `cols` read as zero: only outputs outside the map read them, and those are never stored.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "mtm_device_util.hip.h"
+
+namespace mtm {
+
+constexpr int kWinTile = 16;                    // a tile of 16 x 16 outputs, one per thread
+constexpr int kWinKR = 16, kWinKC = 64;         // template chunk in LDS: rows x columns
+constexpr int kWinIW = kWinTile + kWinKC + 4;   // bytes per LDS image row: the dword right of the last one a thread reads
+constexpr int kWinIR = kWinTile + kWinKR - 1;   // LDS image rows
+// the uint32 sums of one chunk cannot overflow; they are flushed to uint64 after every chunk
+static_assert((unsigned long long)kWinKR * kWinKC * 255ull * 255ull < (1ull << 32), "chunk too large for uint32 sums");
+
+typedef uint32_t WinTemplLds[kWinKR][kWinKC / 4];
+typedef uint32_t WinImageLds[kWinIR][kWinIW / 4];
+
+// Template rows r0 .., columns c0 .. of one byte plane `tc` (h x w, tightly packed) into LDS, zero outside the template.
+__device__ __forceinline__ void win_load_templ(WinTemplLds& Tl, const uint8_t* __restrict__ tc, int h, int w, int r0, int c0,
+                                               int tid) {
+    for (int k = tid; k < kWinKR * (kWinKC / 4); k += 256) {
+        const int i = k / (kWinKC / 4), j = (k % (kWinKC / 4)) * 4;
+        uint32_t v = 0u;
+        if (r0 + i < h)
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (c0 + j + b < w) v |= (uint32_t)tc[(size_t)(r0 + i) * w + c0 + j + b] << (8 * b);
+        Tl[i][j >> 2] = v;
+    }
+}
+
+// Image rows y0 .., columns x0 .. of one byte plane into LDS (zero outside rows x cols); every byte XOR `bias`.
+__device__ __forceinline__ void win_load_image(WinImageLds& Il, const uint8_t* __restrict__ ip, int pitch, int rows, int cols,
+                                               int y0, int x0, uint32_t bias, int tid) {
+    for (int k = tid; k < kWinIR * (kWinIW / 4); k += 256) {
+        const int i = k / (kWinIW / 4), j = (k % (kWinIW / 4)) * 4;
+        const int y = y0 + i, x = x0 + j;
+        uint32_t v = 0u;
+        if (y < rows)
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (x + b < cols) v |= ((uint32_t)ip[(size_t)y * pitch + x + b] ^ bias) << (8 * b);
+        Il[i][j >> 2] = v;
+    }
+}
+
+// Bytes lx + j .. lx + j + 3 of LDS image row `irow`, the columns past the chunk's last template column (nj) masked off.
+__device__ __forceinline__ uint32_t win_image_quad(const uint32_t* irow, int lx, int j, int nj) {
+    const int q = (lx + j) >> 2;
+    uint32_t v = __builtin_amdgcn_alignbyte(irow[q + 1], irow[q], lx & 3);
+    if (nj - j < 4) v &= (1u << (8 * (nj - j))) - 1u;
+    return v;
+}
+
+// uint8 pixels, CH planes: corr = sum I T, s1[c] = sum I over channel c, s2 = sum I^2 over all channels, for the window of
+// output (oy0 + ly, ox0 + lx).  `ip` plane c at ip + c * plane; template plane c at tp + c * h * w.
+template <int CH>
+__device__ __forceinline__ void win_tile_sums_u8(WinTemplLds& Tl, WinImageLds& Il, const uint8_t* __restrict__ ip,
+                                                 long long plane, int pitch, int rows, int cols,
+                                                 const uint8_t* __restrict__ tp, int h, int w, int oy0, int ox0,
+                                                 unsigned long long& corr, unsigned long long (&s1)[CH],
+                                                 unsigned long long& s2) {
+    const int tid = threadIdx.x, ly = tid / kWinTile, lx = tid % kWinTile;
+    corr = 0ull;
+    s2 = 0ull;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        s1[c] = 0ull;
+        const uint8_t* ipc = ip + c * plane;
+        const uint8_t* tc = tp + (size_t)c * h * w;
+        for (int r0 = 0; r0 < h; r0 += kWinKR)
+            for (int c0 = 0; c0 < w; c0 += kWinKC) {
+                __syncthreads();            // the previous chunk's LDS reads are done
+                win_load_templ(Tl, tc, h, w, r0, c0, tid);
+                win_load_image(Il, ipc, pitch, rows, cols, oy0 + r0, ox0 + c0, 0u, tid);
+                __syncthreads();
+                const int ni = min(kWinKR, h - r0), nj = min(kWinKC, w - c0);
+                uint32_t a_corr = 0u, a_s1 = 0u, a_s2 = 0u;
+                for (int i = 0; i < ni; ++i) {
+                    const uint32_t* irow = &Il[ly + i][0];
+                    for (int j = 0; j < nj; j += 4) {
+                        const uint32_t v = win_image_quad(irow, lx, j, nj);
+                        a_corr = __builtin_amdgcn_udot4(v, Tl[i][j >> 2], a_corr, false);
+                        a_s1 = __builtin_amdgcn_udot4(v, 0x01010101u, a_s1, false);
+                        a_s2 = __builtin_amdgcn_udot4(v, v, a_s2, false);
+                    }
+                }
+                corr += a_corr;
+                s1[c] += a_s1;
+                s2 += a_s2;
+            }
+    }
+}
+
+// uint16 pixels, one channel, as byte planes: I = 256 Ih + Il, T = 256 Th + Tl.  Nine v_dot4 streams per chunk -
+// Ih Th, Ih Tl, Il Th, Il Tl (the correlation), Ih, Il (S1), Ih^2, Ih Il, Il^2 (S2) - each < 2^32 per chunk, combined in
+// uint64: every sum is exact.  `hi` = the high-byte plane, `lo_b` = the low-byte plane with every byte XOR 0x80 (the
+// planes the MFMA kernel reads); template planes: high bytes at tp, low bytes at tp + h * w.
+__device__ __forceinline__ void win_tile_sums_u16(WinTemplLds& Th, WinTemplLds& Tlo, WinImageLds& Ih, WinImageLds& Ilo,
+                                                  const uint8_t* __restrict__ hi, const uint8_t* __restrict__ lo_b, int pitch,
+                                                  int rows, int cols, const uint8_t* __restrict__ tp, int h, int w, int oy0,
+                                                  int ox0, unsigned long long& corr, unsigned long long& s1,
+                                                  unsigned long long& s2) {
+    const int tid = threadIdx.x, ly = tid / kWinTile, lx = tid % kWinTile;
+    corr = s1 = s2 = 0ull;
+    const uint8_t* tlo = tp + (size_t)h * w;
+    for (int r0 = 0; r0 < h; r0 += kWinKR)
+        for (int c0 = 0; c0 < w; c0 += kWinKC) {
+            __syncthreads();
+            win_load_templ(Th, tp, h, w, r0, c0, tid);
+            win_load_templ(Tlo, tlo, h, w, r0, c0, tid);
+            win_load_image(Ih, hi, pitch, rows, cols, oy0 + r0, ox0 + c0, 0u, tid);
+            win_load_image(Ilo, lo_b, pitch, rows, cols, oy0 + r0, ox0 + c0, 0x80u, tid);
+            __syncthreads();
+            const int ni = min(kWinKR, h - r0), nj = min(kWinKC, w - c0);
+            uint32_t hh = 0u, hl = 0u, lh = 0u, ll = 0u, s1h = 0u, s1l = 0u, s2hh = 0u, s2hl = 0u, s2ll = 0u;
+            for (int i = 0; i < ni; ++i) {
+                const uint32_t* rh = &Ih[ly + i][0];
+                const uint32_t* rl = &Ilo[ly + i][0];
+                for (int j = 0; j < nj; j += 4) {
+                    const uint32_t vh = win_image_quad(rh, lx, j, nj), vl = win_image_quad(rl, lx, j, nj);
+                    const uint32_t th = Th[i][j >> 2], tl = Tlo[i][j >> 2];
+                    hh = __builtin_amdgcn_udot4(vh, th, hh, false);
+                    hl = __builtin_amdgcn_udot4(vh, tl, hl, false);
+                    lh = __builtin_amdgcn_udot4(vl, th, lh, false);
+                    ll = __builtin_amdgcn_udot4(vl, tl, ll, false);
+                    s1h = __builtin_amdgcn_udot4(vh, 0x01010101u, s1h, false);
+                    s1l = __builtin_amdgcn_udot4(vl, 0x01010101u, s1l, false);
+                    s2hh = __builtin_amdgcn_udot4(vh, vh, s2hh, false);
+                    s2hl = __builtin_amdgcn_udot4(vh, vl, s2hl, false);
+                    s2ll = __builtin_amdgcn_udot4(vl, vl, s2ll, false);
+                }
+            }
+            corr += ((unsigned long long)hh << 16) + (((unsigned long long)hl + lh) << 8) + ll;
+            s1 += ((unsigned long long)s1h << 8) + s1l;
+            s2 += ((unsigned long long)s2hh << 16) + ((unsigned long long)s2hl << 9) + s2ll;
+        }
+}
+
+// The float32 score of a window from its exact sums: the statistics of stats_u8_kernel / stats_u8_mc_kernel /
+// stats_u16_kernel / vsum_stats_kernel (exact sums, S1^2 summed over the channels, times 1 / area) and the epilogue of every
+// score kernel (window_norm, finish_unmasked_with) - the exhaustive map's value bit for bit.
+template <int CH>
+__device__ __forceinline__ float win_score(int method, const TemplDev& T, double inv_area, unsigned long long corr,
+                                           const unsigned long long (&s1)[CH], unsigned long long s2) {
+    const bool centred = method == MTM_TM_CCOEFF || method == MTM_TM_CCOEFF_NORMED;
+    double s1d[kMaxChans] = {0.0, 0.0, 0.0, 0.0};
+    double mean2 = 0.0;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        s1d[c] = (double)s1[c];
+        if (centred) mean2 += s1d[c] * s1d[c];
+    }
+    const double sum2 = (double)s2;
+    const double wnd_mean2 = mean2 * inv_area;
+    return finish_unmasked_with(
+        method, (double)corr, [&](int c) { return s1d[c]; }, [&]() { return sum2; },
+        [&]() { return window_norm(sum2, wnd_mean2); }, T, CH);
+}
+
+}  // namespace mtm

@@ -4,6 +4,7 @@
 // there.  uint8, unmasked templates of one mtm_set_templates call.
 #include "mtm_ctx.h"
 #include "mtm_device_util.hip.h"
+#include "mtm_k_window.hip.h"
 
 using namespace mtm;
 using namespace mtmi;
@@ -19,13 +20,6 @@ struct PyrWin {
     int ry0, ry1, rx0, rx1;     // scored region (inclusive bounds)
     long long buf_off;          // float offset of the region's scores in the score buffer, row-major, rx1 - rx0 + 1 per row
 };
-
-constexpr int kPyrTile = 16;                    // a tile of 16 x 16 outputs, one per thread
-constexpr int kPyrKR = 16, kPyrKC = 64;         // template chunk in LDS: rows x columns
-constexpr int kPyrIW = kPyrTile + kPyrKC + 4;   // bytes per LDS image row: the dword right of the last one a thread reads
-constexpr int kPyrIR = kPyrTile + kPyrKR - 1;   // LDS image rows
-// the uint32 sums of one chunk cannot overflow; they are flushed to uint64 after every chunk
-static_assert((unsigned long long)kPyrKR * kPyrKC * 255ull * 255ull < (1ull << 32), "chunk too large for uint32 sums");
 
 // Grid: one work-group per window.  Phase 1 scores the region tile by tile: per output the exact correlation and the
 // window sums S1 (per channel) and S2 come from v_dot4_u32_u8 over a template chunk and an image tile in LDS (the
@@ -46,86 +40,25 @@ __global__ __launch_bounds__(256) void pyr_window_kernel(ImageDev img, const uin
                                                          unsigned long long* __restrict__ counter,
                                                          unsigned long long* __restrict__ best,
                                                          int* __restrict__ nontrivial) {
-    __shared__ __attribute__((aligned(16))) uint32_t Tl[kPyrKR][kPyrKC / 4];
-    __shared__ __attribute__((aligned(16))) uint32_t Il[kPyrIR][kPyrIW / 4];
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl;
+    __shared__ __attribute__((aligned(16))) WinImageLds Il;
     const PyrWin W = wins[blockIdx.x];
     const TemplDev T = td[W.t];
     const int h = T.rows, w = T.cols;
     const uint8_t* tp = tpx + toff[W.t];
-    const int tid = threadIdx.x, ly = tid / kPyrTile, lx = tid % kPyrTile;
+    const int tid = threadIdx.x, ly = tid / kWinTile, lx = tid % kWinTile;
     const int RH = W.ry1 - W.ry0 + 1, RW = W.rx1 - W.rx0 + 1;
     float* rb = buf + W.buf_off;
     const double inv_area = 1.0 / ((double)h * (double)w);
-    const bool centred = method == MTM_TM_CCOEFF || method == MTM_TM_CCOEFF_NORMED;
 
-    for (int ty0 = 0; ty0 < RH; ty0 += kPyrTile)
-        for (int tx0 = 0; tx0 < RW; tx0 += kPyrTile) {
-            const int oy0 = W.ry0 + ty0, ox0 = W.rx0 + tx0;       // the tile's first output (= its window's top-left pixel)
-            unsigned long long corr = 0ull, s2 = 0ull, s1[CH];
-#pragma unroll
-            for (int c = 0; c < CH; ++c) {
-                s1[c] = 0ull;
-                const uint8_t* ip = img.u8 + c * img.u8_plane;
-                const uint8_t* tc = tp + (size_t)c * h * w;
-                for (int r0 = 0; r0 < h; r0 += kPyrKR)
-                    for (int c0 = 0; c0 < w; c0 += kPyrKC) {
-                        __syncthreads();            // the previous chunk's LDS reads are done
-                        // template rows r0 .., columns c0 .. (zero outside the template)
-                        for (int k = tid; k < kPyrKR * (kPyrKC / 4); k += 256) {
-                            const int i = k / (kPyrKC / 4), j = (k % (kPyrKC / 4)) * 4;
-                            uint32_t v = 0u;
-                            if (r0 + i < h)
-#pragma unroll
-                                for (int b = 0; b < 4; ++b)
-                                    if (c0 + j + b < w) v |= (uint32_t)tc[(size_t)(r0 + i) * w + c0 + j + b] << (8 * b);
-                            Tl[i][j >> 2] = v;
-                        }
-                        // image rows oy0 + r0 .., columns ox0 + c0 .. (zero outside the image: only outputs outside the
-                        // map, which are never stored, read them)
-                        for (int k = tid; k < kPyrIR * (kPyrIW / 4); k += 256) {
-                            const int i = k / (kPyrIW / 4), j = (k % (kPyrIW / 4)) * 4;
-                            const int y = oy0 + r0 + i, x = ox0 + c0 + j;
-                            uint32_t v = 0u;
-                            if (y < img.rows)
-#pragma unroll
-                                for (int b = 0; b < 4; ++b)
-                                    if (x + b < img.cols) v |= (uint32_t)ip[(size_t)y * img.u8_pitch + x + b] << (8 * b);
-                            Il[i][j >> 2] = v;
-                        }
-                        __syncthreads();
-                        const int ni = min(kPyrKR, h - r0), nj = min(kPyrKC, w - c0);
-                        const int sh = lx & 3;
-                        uint32_t a_corr = 0u, a_s1 = 0u, a_s2 = 0u;
-                        for (int i = 0; i < ni; ++i) {
-                            const uint32_t* irow = &Il[ly + i][0];
-                            for (int j = 0; j < nj; j += 4) {
-                                const int q = (lx + j) >> 2;
-                                uint32_t v = __builtin_amdgcn_alignbyte(irow[q + 1], irow[q], sh);   // bytes lx + j .. + 3
-                                if (nj - j < 4) v &= (1u << (8 * (nj - j))) - 1u;                 // columns past the template
-                                a_corr = __builtin_amdgcn_udot4(v, Tl[i][j >> 2], a_corr, false);
-                                a_s1 = __builtin_amdgcn_udot4(v, 0x01010101u, a_s1, false);
-                                a_s2 = __builtin_amdgcn_udot4(v, v, a_s2, false);
-                            }
-                        }
-                        corr += a_corr;
-                        s1[c] += a_s1;
-                        s2 += a_s2;
-                    }
-            }
+    for (int ty0 = 0; ty0 < RH; ty0 += kWinTile)
+        for (int tx0 = 0; tx0 < RW; tx0 += kWinTile) {
+            unsigned long long corr, s2, s1[CH];
+            // (the tile's first output = its window's top-left pixel)
+            win_tile_sums_u8<CH>(Tl, Il, img.u8, img.u8_plane, img.u8_pitch, img.rows, img.cols, tp, h, w, W.ry0 + ty0,
+                                 W.rx0 + tx0, corr, s1, s2);
             if (ty0 + ly < RH && tx0 + lx < RW) {
-                // the statistics of stats_u8_kernel / stats_u8_mc_kernel / vsum_stats_kernel: exact sums, the same order
-                double s1d[kMaxChans] = {0.0, 0.0, 0.0, 0.0};
-                double mean2 = 0.0;
-#pragma unroll
-                for (int c = 0; c < CH; ++c) {
-                    s1d[c] = (double)s1[c];
-                    if (centred) mean2 += s1d[c] * s1d[c];
-                }
-                const double sum2 = (double)s2;
-                const double wnd_mean2 = mean2 * inv_area;
-                const float score = finish_unmasked_with(
-                    method, (double)corr, [&](int c) { return s1d[c]; }, [&]() { return sum2; },
-                    [&]() { return window_norm(sum2, wnd_mean2); }, T, CH);
+                const float score = win_score<CH>(method, T, inv_area, corr, s1, s2);
                 rb[(size_t)(ty0 + ly) * RW + tx0 + lx] = score;
             }
         }
@@ -183,16 +116,12 @@ __global__ __launch_bounds__(256) void pyr_window_kernel(ImageDev img, const uin
 
 }  // namespace mtm
 
-namespace {
-
-struct BlobTempl {
-    int rows, cols, chans;
-    const uint8_t* px;      // interleaved, tightly packed rows
-};
+namespace mtmi {
 
 // The templates of the last mtm_set_templates, read back from the bytes the context keeps of them (mtm_ctx::templ_blob,
 // written by set_templates_impl: n_templ, method, n_var, then per template {rows, cols, chans, dtype, has_mask} + rows).
-int parse_templ_blob(const std::vector<uint8_t>& b, std::vector<BlobTempl>& out, const char* who) {
+// Unmasked uint8 templates; with `u16_ok` also unmasked single-channel uint16 ones.
+int parse_templ_blob(const std::vector<uint8_t>& b, std::vector<BlobTempl>& out, const char* who, bool u16_ok) {
     size_t off = 0;
     auto rd = [&](void* dst, size_t n) {
         if (off + n > b.size()) return false;
@@ -213,17 +142,24 @@ int parse_templ_blob(const std::vector<uint8_t>& b, std::vector<BlobTempl>& out,
     for (int i = 0; i < n_templ; ++i) {
         int hdr[5];
         if (!rd(hdr, sizeof(hdr))) return MTM_E_STATE;
-        if (hdr[3] != MTM_U8 || hdr[4] != 0) {
-            set_error(std::string(who) + ": template " + std::to_string(i) + " is not an unmasked uint8 template");
+        const bool u16 = u16_ok && hdr[3] == MTM_U16 && hdr[2] == 1;
+        if ((hdr[3] != MTM_U8 && !u16) || hdr[4] != 0) {
+            set_error(std::string(who) + ": template " + std::to_string(i) +
+                      (u16_ok ? " is not an unmasked uint8 or single-channel uint16 template"
+                              : " is not an unmasked uint8 template"));
             return MTM_E_INVALID;
         }
-        const size_t bytes = (size_t)hdr[0] * hdr[1] * hdr[2];
+        const size_t bytes = (size_t)hdr[0] * hdr[1] * hdr[2] * (u16 ? 2 : 1);
         if (off + bytes > b.size()) return MTM_E_STATE;
-        out.push_back(BlobTempl{hdr[0], hdr[1], hdr[2], b.data() + off});
+        out.push_back(BlobTempl{hdr[0], hdr[1], hdr[2], hdr[3], b.data() + off});
         off += bytes;
     }
     return MTM_OK;
 }
+
+}  // namespace mtmi
+
+namespace {
 
 // augment.downscale / planarize_u8_down_kernel on the host: factor 2 -> (sum + 2) >> 2, else rint((float)sum / f^2)
 std::vector<uint8_t> downscale_u8(const BlobTempl& t, int f) {
@@ -271,7 +207,7 @@ int mtm_find_matches_pyramid(mtm_ctx* c, const void* px, int rows, int cols, int
         return MTM_E_INVALID;
     }
     std::vector<BlobTempl> tl;
-    MTMC(parse_templ_blob(c->templ_blob, tl, who));
+    MTMC(parse_templ_blob(c->templ_blob, tl, who, false));
     const int n = (int)tl.size();
     const int crows = rows / factor, ccols = cols / factor;
     for (int i = 0; i < n; ++i) {

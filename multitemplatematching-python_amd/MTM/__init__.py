@@ -42,6 +42,7 @@ _MSG_MASK_METHOD = ("Template matching method not compatible with use of mask (o
 _MSG_MASK_SHAPE = "Mask does not have the same dimension or bit depth than the template.\n-> Ignoring mask."
 _MSG_MASK_UNSUPPORTED = ("Template matching method not supporting the use of Mask. "
                          "Use 0/TM_SQDIFF or 3/TM_CCORR_NORMED.")
+_MSG_SQDIFF = "The method TM_SQDIFF is not supported. Use TM_SQDIFF_NORMED instead."
 
 
 def _apply_pixel_policy(template, image, method, mask):
@@ -362,7 +363,7 @@ def matchTemplates(listTemplates: List[TemplateTuple], image: np.ndarray, method
     raw = _raw_matches(listTemplates, image_s, method, N_object, score_threshold, devices=devices, nms=nms)
 
     if method == 0:     # as in the reference, only after the search ran (MTM/__init__.py:291)
-        raise ValueError("The method TM_SQDIFF is not supported. Use TM_SQDIFF_NORMED instead.")
+        raise ValueError(_MSG_SQDIFF)
 
     sortAscending = (method == 1)
     kept = raw if nms == [] else _nms_raw(raw, score_threshold, sortAscending, N_object, maxOverlap)
@@ -436,7 +437,7 @@ class TemplateMatcher:
 
     def _finish(self, raw, xOffset, yOffset):
         if self.method == 0:
-            raise ValueError("The method TM_SQDIFF is not supported. Use TM_SQDIFF_NORMED instead.")
+            raise ValueError(_MSG_SQDIFF)
         kept = _nms_raw(raw, self.score_threshold, self.method == 1, self.N_object, self.maxOverlap)
         return _to_hit_list(kept, self.listTemplates, xOffset, yOffset)
 

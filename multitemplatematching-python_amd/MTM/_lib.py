@@ -197,6 +197,21 @@ def check(rc, what=""):
         raise MtmError("%s failed (%d): %s" % (what or "libmtm_hip call", rc, (msg or b"").decode()))
 
 
+def _hits_call(fn, fetch, name, handle, *args, cap=4096, counts=None, tail=()):
+    """fn(handle, *args, out, cap[, counts], &n, *tail) into a `cap`-record buffer: the hit records.  On E_OVERFLOW the
+    result stays in the native object (counts are filled): it is fetched with fetch(handle, out, n, &n), not recomputed."""
+    out = np.empty(cap, dtype=HIT_DTYPE)
+    n = ctypes.c_int64(0)
+    mid = () if counts is None else (counts.ctypes.data,)
+    rc = fn(handle, *args, out.ctypes.data, cap, *mid, ctypes.byref(n), *tail)
+    if rc == E_OVERFLOW:
+        cap = int(n.value)
+        out = np.empty(cap, dtype=HIT_DTYPE)
+        rc = fetch(handle, out.ctypes.data, cap, ctypes.byref(n))
+    check(rc, name)
+    return out[:n.value]
+
+
 def _pixel_rows(a):
     """Return (array_kept_alive, pointer, row_stride_bytes) for a (rows, cols[, C]) array whose
     rows have contiguous pixels; anything else (e.g. a transposed view) is copied."""
@@ -433,59 +448,31 @@ class Context(_RecordMemo):
     def find_matches(self, mode, score_threshold, next_image=None):
         """Hits of the current image.  With `next_image`, that image is uploaded while the kernels run
         and is the current image when the call returns (mtm_find_matches_next)."""
-        cap = 4096
-        out = np.empty(cap, dtype=HIT_DTYPE)
-        n = ctypes.c_int64(0)
         if next_image is None:
-            rc = self._lib.mtm_find_matches(self._h, int(mode), float(score_threshold), out.ctypes.data, cap,
-                                            ctypes.byref(n))
-        else:
-            a, ptr, stride = _pixel_rows(next_image)
-            chans = 1 if a.ndim == 2 else a.shape[2]
-            rc = self._lib.mtm_find_matches_next(self._h, int(mode), float(score_threshold), out.ctypes.data, cap,
-                                                 ctypes.byref(n), ptr, a.shape[0], a.shape[1], chans,
-                                                 _dtype_code(a), stride)
-        if rc == E_OVERFLOW:        # the result stays in the context: fetch it, do not recompute
-            cap = int(n.value)
-            out = np.empty(cap, dtype=HIT_DTYPE)
-            rc = self._lib.mtm_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(n))
-        check(rc, "mtm_find_matches")
-        return out[:n.value]
+            return _hits_call(self._lib.mtm_find_matches, self._lib.mtm_last_hits, "mtm_find_matches", self._h, int(mode),
+                              float(score_threshold))
+        a, ptr, stride = _pixel_rows(next_image)
+        chans = 1 if a.ndim == 2 else a.shape[2]
+        next_args = (ptr, a.shape[0], a.shape[1], chans, _dtype_code(a), stride)
+        return _hits_call(self._lib.mtm_find_matches_next, self._lib.mtm_last_hits, "mtm_find_matches", self._h, int(mode),
+                          float(score_threshold), tail=next_args)
 
     def find_matches_image(self, image, mode, score_threshold):
         """set_image + find_matches in one native call (mtm_find_matches_image): no round trip in between, the
         image crosses PCIe in row bands under the score kernel where the layout allows."""
         a, ptr, stride = _pixel_rows(image)
         chans = 1 if a.ndim == 2 else a.shape[2]
-        cap = 4096
-        out = np.empty(cap, dtype=HIT_DTYPE)
-        n = ctypes.c_int64(0)
-        rc = self._lib.mtm_find_matches_image(self._h, ptr, a.shape[0], a.shape[1], chans, _dtype_code(a), stride,
-                                              int(mode), float(score_threshold), out.ctypes.data, cap, ctypes.byref(n))
-        if rc == E_OVERFLOW:
-            cap = int(n.value)
-            out = np.empty(cap, dtype=HIT_DTYPE)
-            rc = self._lib.mtm_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(n))
-        check(rc, "mtm_find_matches_image")
-        return out[:n.value]
+        return _hits_call(self._lib.mtm_find_matches_image, self._lib.mtm_last_hits, "mtm_find_matches_image", self._h, ptr,
+                          a.shape[0], a.shape[1], chans, _dtype_code(a), stride, int(mode), float(score_threshold))
 
     def find_matches_pyramid(self, image, factor, mode, coarse_threshold, score_threshold, radius, max_candidates):
         """Coarse-to-fine search of the current templates in one native call (mtm_find_matches_pyramid): candidates from
         the image downscaled by `factor`, exact full-resolution scores in windows of +-`radius` around them."""
         a, ptr, stride = _pixel_rows(image)
         chans = 1 if a.ndim == 2 else a.shape[2]
-        cap = 4096
-        out = np.empty(cap, dtype=HIT_DTYPE)
-        n = ctypes.c_int64(0)
-        rc = self._lib.mtm_find_matches_pyramid(self._h, ptr, a.shape[0], a.shape[1], chans, _dtype_code(a), stride,
-                                                int(factor), int(mode), float(coarse_threshold), float(score_threshold),
-                                                int(radius), int(max_candidates), out.ctypes.data, cap, ctypes.byref(n))
-        if rc == E_OVERFLOW:        # the result stays in the context: fetch it, do not recompute
-            cap = int(n.value)
-            out = np.empty(cap, dtype=HIT_DTYPE)
-            rc = self._lib.mtm_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(n))
-        check(rc, "mtm_find_matches_pyramid")
-        return out[:n.value]
+        return _hits_call(self._lib.mtm_find_matches_pyramid, self._lib.mtm_last_hits, "mtm_find_matches_pyramid", self._h,
+                          ptr, a.shape[0], a.shape[1], chans, _dtype_code(a), stride, int(factor), int(mode),
+                          float(coarse_threshold), float(score_threshold), int(radius), int(max_candidates))
 
     def find_matches_boxes(self, image, units, mode, score_threshold):
         """The current templates searched in many regions of one image in one native call (mtm_find_matches_boxes).
@@ -496,18 +483,10 @@ class Context(_RecordMemo):
         units = np.ascontiguousarray(units, dtype=BOX_UNIT_DTYPE)
         n = len(units)
         counts = np.zeros(n, dtype=np.int64)
-        cap = max(4096, 16 * n)
-        out = np.empty(cap, dtype=HIT_DTYPE)
-        total = ctypes.c_int64(0)
-        rc = self._lib.mtm_find_matches_boxes(self._h, ptr, a.shape[0], a.shape[1], chans, _dtype_code(a), stride,
-                                              units.ctypes.data, n, int(mode), float(score_threshold), out.ctypes.data, cap,
-                                              counts.ctypes.data, ctypes.byref(total))
-        if rc == E_OVERFLOW:        # the records stay in the context; counts are filled
-            cap = int(total.value)
-            out = np.empty(cap, dtype=HIT_DTYPE)
-            rc = self._lib.mtm_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(total))
-        check(rc, "mtm_find_matches_boxes")
-        return out[:total.value], counts
+        hits = _hits_call(self._lib.mtm_find_matches_boxes, self._lib.mtm_last_hits, "mtm_find_matches_boxes", self._h,
+                          ptr, a.shape[0], a.shape[1], chans, _dtype_code(a), stride, units.ctypes.data, n, int(mode),
+                          float(score_threshold), cap=max(4096, 16 * n), counts=counts)
+        return hits, counts
 
     def find_matches_batch(self, images, mode, score_threshold):
         """Images of one shape and dtype against the current templates in one native call (mtm_find_matches_batch): a list
@@ -522,18 +501,10 @@ class Context(_RecordMemo):
         chans = 1 if a0.ndim == 2 else a0.shape[2]
         ptrs = (ctypes.c_void_p * n)(*[r[1] for r in rows])
         counts = np.zeros(n, dtype=np.int64)
-        cap = max(4096, 64 * n)
-        out = np.empty(cap, dtype=HIT_DTYPE)
-        total = ctypes.c_int64(0)
-        rc = self._lib.mtm_find_matches_batch(self._h, ptrs, n, a0.shape[0], a0.shape[1], chans, _dtype_code(a0), stride,
-                                              int(mode), float(score_threshold), out.ctypes.data, cap, counts.ctypes.data,
-                                              ctypes.byref(total))
-        if rc == E_OVERFLOW:        # the records stay in the context; counts are filled
-            cap = int(total.value)
-            out = np.empty(cap, dtype=HIT_DTYPE)
-            rc = self._lib.mtm_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(total))
-        check(rc, "mtm_find_matches_batch")
-        return np.split(out[:total.value], np.cumsum(counts)[:-1])
+        hits = _hits_call(self._lib.mtm_find_matches_batch, self._lib.mtm_last_hits, "mtm_find_matches_batch", self._h,
+                          ptrs, n, a0.shape[0], a0.shape[1], chans, _dtype_code(a0), stride, int(mode),
+                          float(score_threshold), cap=max(4096, 64 * n), counts=counts)
+        return np.split(hits, np.cumsum(counts)[:-1])
 
     def search_nms(self, templates, image, method, score_threshold, max_overlap, n_object=-1):
         """search() + MTM's non-maxima suppression in one native call (mtm_find_matches_image_nms): the kept hits, best
@@ -541,18 +512,9 @@ class Context(_RecordMemo):
         self.set_templates(templates, method)
         a, ptr, stride = _pixel_rows(image)
         chans = 1 if a.ndim == 2 else a.shape[2]
-        cap = 4096
-        out = np.empty(cap, dtype=HIT_DTYPE)
-        n = ctypes.c_int64(0)
-        rc = self._lib.mtm_find_matches_image_nms(self._h, ptr, a.shape[0], a.shape[1], chans, _dtype_code(a), stride,
-                                                  float(score_threshold), float(max_overlap), int(n_object), out.ctypes.data,
-                                                  cap, ctypes.byref(n))
-        if rc == E_OVERFLOW:
-            cap = int(n.value)
-            out = np.empty(cap, dtype=HIT_DTYPE)
-            rc = self._lib.mtm_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(n))
-        check(rc, "mtm_find_matches_image_nms")
-        return out[:n.value]
+        return _hits_call(self._lib.mtm_find_matches_image_nms, self._lib.mtm_last_hits, "mtm_find_matches_image_nms",
+                          self._h, ptr, a.shape[0], a.shape[1], chans, _dtype_code(a), stride, float(score_threshold),
+                          float(max_overlap), int(n_object))
 
     def search_sharded_nms(self, templates, image, method, score_threshold, max_overlap, n_object, global_idx):
         """This rank's step of a sharded matchTemplates in one native call (mtm_find_matches_image_sharded_nms): search
@@ -567,18 +529,9 @@ class Context(_RecordMemo):
             shape, code = a.shape, _dtype_code(a)
         else:
             ptr, stride, chans, shape, code = None, 0, 1, (0, 0), MTM_U8
-        cap = 4096
-        out = np.empty(cap, dtype=HIT_DTYPE)
-        n = ctypes.c_int64(0)
-        rc = self._lib.mtm_find_matches_image_sharded_nms(self._h, ptr, shape[0], shape[1], chans, code, stride,
-                                                          float(score_threshold), float(max_overlap), int(n_object),
-                                                          int(method), gidx.ctypes.data, n_t, out.ctypes.data, cap, ctypes.byref(n))
-        if rc == E_OVERFLOW:
-            cap = int(n.value)
-            out = np.empty(cap, dtype=HIT_DTYPE)
-            rc = self._lib.mtm_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(n))
-        check(rc, "mtm_find_matches_image_sharded_nms")
-        return out[:n.value]
+        return _hits_call(self._lib.mtm_find_matches_image_sharded_nms, self._lib.mtm_last_hits,
+                          "mtm_find_matches_image_sharded_nms", self._h, ptr, shape[0], shape[1], chans, code, stride,
+                          float(score_threshold), float(max_overlap), int(n_object), int(method), gidx.ctypes.data, n_t)
 
     def find_matches_async(self, mode, score_threshold):
         """Start mtm_find_matches on the context's worker thread and return at once; collect the hits with
@@ -586,16 +539,7 @@ class Context(_RecordMemo):
         check(self._lib.mtm_find_matches_async(self._h, int(mode), float(score_threshold)), "mtm_find_matches_async")
 
     def find_matches_wait(self):
-        cap = 4096
-        out = np.empty(cap, dtype=HIT_DTYPE)
-        n = ctypes.c_int64(0)
-        rc = self._lib.mtm_find_matches_wait(self._h, out.ctypes.data, cap, ctypes.byref(n))
-        if rc == E_OVERFLOW:
-            cap = int(n.value)
-            out = np.empty(cap, dtype=HIT_DTYPE)
-            rc = self._lib.mtm_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(n))
-        check(rc, "mtm_find_matches_wait")
-        return out[:n.value]
+        return _hits_call(self._lib.mtm_find_matches_wait, self._lib.mtm_last_hits, "mtm_find_matches_wait", self._h)
 
     def last_score_map(self, idx, shape):
         """Score map of template `idx` as the last find_matches computed it (map mode only)."""
@@ -711,18 +655,9 @@ class Group(_RecordMemo):
         rec = self._records(templates)
         a, ptr, stride = _pixel_rows(image)
         chans = 1 if a.ndim == 2 else a.shape[2]
-        cap = 4096
-        out = np.empty(cap, dtype=HIT_DTYPE)
-        n = ctypes.c_int64(0)
-        rc = self._lib.mtm_group_find_matches(self._h, rec.ctypes.data, len(templates), int(method), ptr, a.shape[0],
-                                              a.shape[1], chans, _dtype_code(a), stride, int(mode), float(score_threshold),
-                                              out.ctypes.data, cap, ctypes.byref(n))
-        if rc == E_OVERFLOW:
-            cap = int(n.value)
-            out = np.empty(cap, dtype=HIT_DTYPE)
-            rc = self._lib.mtm_group_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(n))
-        check(rc, "mtm_group_find_matches")
-        return out[:n.value]
+        return _hits_call(self._lib.mtm_group_find_matches, self._lib.mtm_group_last_hits, "mtm_group_find_matches",
+                          self._h, rec.ctypes.data, len(templates), int(method), ptr, a.shape[0], a.shape[1], chans,
+                          _dtype_code(a), stride, int(mode), float(score_threshold))
 
 
     def search_nms(self, templates, image, method, score_threshold, max_overlap, n_object=-1):
@@ -730,18 +665,10 @@ class Group(_RecordMemo):
         rec = self._records(templates)
         a, ptr, stride = _pixel_rows(image)
         chans = 1 if a.ndim == 2 else a.shape[2]
-        cap = 4096
-        out = np.empty(cap, dtype=HIT_DTYPE)
-        n = ctypes.c_int64(0)
-        rc = self._lib.mtm_group_find_matches_nms(self._h, rec.ctypes.data, len(templates), int(method), ptr, a.shape[0],
-                                                  a.shape[1], chans, _dtype_code(a), stride, float(score_threshold),
-                                                  float(max_overlap), int(n_object), out.ctypes.data, cap, ctypes.byref(n))
-        if rc == E_OVERFLOW:
-            cap = int(n.value)
-            out = np.empty(cap, dtype=HIT_DTYPE)
-            rc = self._lib.mtm_group_last_hits(self._h, out.ctypes.data, cap, ctypes.byref(n))
-        check(rc, "mtm_group_find_matches_nms")
-        return out[:n.value]
+        return _hits_call(self._lib.mtm_group_find_matches_nms, self._lib.mtm_group_last_hits,
+                          "mtm_group_find_matches_nms", self._h, rec.ctypes.data, len(templates), int(method), ptr,
+                          a.shape[0], a.shape[1], chans, _dtype_code(a), stride, float(score_threshold), float(max_overlap),
+                          int(n_object))
 
 
 def parse_devices(spec):

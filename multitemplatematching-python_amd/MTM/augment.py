@@ -29,7 +29,7 @@ import numpy as np
 
 from . import _lib
 from . import (TM_CCOEFF_NORMED, _apply_pixel_policy, _check_opencv_preconditions, _nms_raw, _to_hit_list,
-               _validate_search, _MSG_MASK_UNSUPPORTED)
+               _validate_search, _MSG_MASK_UNSUPPORTED, _MSG_SQDIFF)
 
 import warnings
 
@@ -203,7 +203,7 @@ def matchTemplatesAugmented(listTemplates, spec, image: np.ndarray, method: int 
         ctx.set_templates_augmented(bases, [rec for _, rec in spec], method)
         raw = ctx.find_matches_image(image_s, mode, score_threshold)
     if method == 0:
-        raise ValueError("The method TM_SQDIFF is not supported. Use TM_SQDIFF_NORMED instead.")
+        raise ValueError(_MSG_SQDIFF)
     kept = _nms_raw(raw, score_threshold, method == 1, N_object, maxOverlap)
     return _to_hit_list(kept, shapes_only, xOffset, yOffset)
 
@@ -260,6 +260,6 @@ def matchTemplatesDownscaled(listTemplates, image: np.ndarray, factor: int, meth
         ctx.set_templates(units, method)
         raw = ctx.find_matches(mode, score_threshold).copy()
     if method == 0:
-        raise ValueError("The method TM_SQDIFF is not supported. Use TM_SQDIFF_NORMED instead.")
+        raise ValueError(_MSG_SQDIFF)
     kept = _nms_raw(raw, score_threshold, method == 1, N_object, maxOverlap)
     return upscale_hits(_to_hit_list(kept, small, 0, 0), factor)

@@ -24,11 +24,10 @@ from typing import List, Sequence
 import numpy as np
 
 from . import _lib
-from . import _MSG_MASK_UNSUPPORTED, Hit, TemplateTuple, TM_CCOEFF_NORMED
+from . import _MSG_MASK_UNSUPPORTED, _MSG_SQDIFF, Hit, TemplateTuple, TM_CCOEFF_NORMED
 
 __all__ = ["findMatchesInBoxes", "matchTemplatesInBoxes"]
 
-_MSG_SQDIFF = "The method TM_SQDIFF is not supported. Use TM_SQDIFF_NORMED instead."
 _MSG_TUPLES = "listTemplates should be a list of tuples as ('name','array') or ('name', 'array', 'mask')"
 _I64 = np.dtype(np.int64)
 _SCOPE_METHODS = (0, 1, 2, 3, 4, 5)

@@ -28,6 +28,7 @@ from typing import List, Sequence
 import numpy as np
 
 from . import _lib
+from . import _MSG_SQDIFF
 
 
 def unit_cost(template, image_shape, masked=False) -> float:
@@ -287,7 +288,7 @@ def matchTemplates_sharded(listTemplates, image, exchange: HitExchange, method=5
             with exchange.ctx.lock:
                 raw = exchange.ctx.search_sharded_nms(units, image, method, score_threshold, maxOverlap, n_obj, mine)
             if method == 0:
-                raise ValueError("The method TM_SQDIFF is not supported. Use TM_SQDIFF_NORMED instead.")
+                raise ValueError(_MSG_SQDIFF)
             from . import _to_hit_list
             return _to_hit_list(raw, listTemplates, xOffset, yOffset)
     if find_local is not None:
@@ -300,5 +301,5 @@ def matchTemplates_sharded(listTemplates, image, exchange: HitExchange, method=5
     raw["templ_idx"] = np.asarray(mine, dtype=np.int32)[raw["templ_idx"]] if len(raw) else raw["templ_idx"]
     gathered = exchange.allgather(raw)
     if method == 0:
-        raise ValueError("The method TM_SQDIFF is not supported. Use TM_SQDIFF_NORMED instead.")
+        raise ValueError(_MSG_SQDIFF)
     return merge_and_nms(gathered, listTemplates, method, N_object, score_threshold, maxOverlap, xOffset, yOffset)

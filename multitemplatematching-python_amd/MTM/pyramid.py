@@ -26,12 +26,11 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from . import _MSG_MASK_UNSUPPORTED, _nms_raw, _to_hit_list, _validate_search, BBox, Hit, TemplateTuple
+from . import _MSG_MASK_UNSUPPORTED, _MSG_SQDIFF, _nms_raw, _to_hit_list, _validate_search, BBox, Hit, TemplateTuple
 from . import TM_CCOEFF_NORMED
 
 __all__ = ["findMatchesPyramid", "matchTemplatesPyramid"]
 
-_MSG_SQDIFF = "The method TM_SQDIFF is not supported. Use TM_SQDIFF_NORMED instead."
 
 
 def _is_int(v):

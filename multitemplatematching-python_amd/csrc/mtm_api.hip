@@ -9,13 +9,6 @@ using namespace mtmi;
 
 namespace {
 
-inline float decode_order(uint32_t o) {
-    const uint32_t b = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-    float v;
-    std::memcpy(&v, &b, 4);
-    return v;
-}
-
 struct NextImage {
     const void* px;
     int rows, cols, chans, dtype;
@@ -518,19 +511,8 @@ int fm_end(mtm_ctx* c, CallRoute& R, mtm_hit* out, int64_t capacity, int64_t* n_
         }
         if (!done) return ladder_exhausted();
         for (int t = 0; t < n; ++t) {
-            const unsigned long long key = best[2 * t + (mode_min ? 1 : 0)];
             const TemplDev& d = c->td_host[t];
-            uint32_t o = (uint32_t)(key >> 32);
-            if (mode_min) o = ~o;
-            const uint32_t idx = key ? (0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu)) : 0u;
-            mtm_hit hrec;
-            hrec.templ_idx = t;
-            hrec.x = (int)(idx % (uint32_t)d.ow);
-            hrec.y = (int)(idx / (uint32_t)d.ow);
-            hrec.w = d.cols;
-            hrec.h = d.rows;
-            hrec.score = key ? decode_order(o) : NAN;
-            hits.push_back(hrec);
+            hits.push_back(decode_extremum_key(best[2 * t + (mode_min ? 1 : 0)], mode_min, t, d.ow, d.cols, d.rows));
         }
     } else {
         // ---- 2-D maps.  One device buffer holds [64-bit counter | per-template ints | hit records];
@@ -787,23 +769,7 @@ int fm_end(mtm_ctx* c, CallRoute& R, mtm_hit* out, int64_t capacity, int64_t* n_
                                   c->maps.as<float>() + d.map_off, sizeof(float) * d.map_pitch,
                                   sizeof(float) * d.ow, d.oh, hipMemcpyDeviceToHost, c->stream));
             HIPC(hipStreamSynchronize(c->stream));
-            std::vector<int> pk;
-            if (len == 1) {
-                const float v = mode_min ? -line[0] : line[0];
-                if (v >= (mode_min ? -thr : thr)) pk.push_back(0);
-            } else {
-                pk = find_peaks_1d(line.data(), len, 1, mode_min ? -thr : thr, mode_min);
-            }
-            for (int i : pk) {
-                mtm_hit hrec;
-                hrec.templ_idx = t;
-                hrec.x = d.oh == 1 ? i : 0;
-                hrec.y = d.oh == 1 ? 0 : i;
-                hrec.w = d.cols;
-                hrec.h = d.rows;
-                hrec.score = line[(size_t)i];
-                hits.push_back(hrec);
-            }
+            line_map_peaks(line.data(), d.oh, d.ow, thr, mode_min, t, d.cols, d.rows, hits);
         }
         // deterministic order: template, then descending quality, then row-major position
         host_trace(c, 11);
@@ -835,14 +801,8 @@ int fm_end(mtm_ctx* c, CallRoute& R, mtm_hit* out, int64_t capacity, int64_t* n_
     c->timing.hits_only = R.sparse ? 2 : R.hits_only ? 1 : 0;
     c->timing.f32_route = R.mbf_used ? 4 : R.f32_exact ? 3 : !R.refine ? 0 : (R.refine_scan ? 2 : 1);
     c->maps_valid = !R.hits_only && !R.ext && !R.seg_skip_used && !R.mbf_used;
-    *n_out = (int64_t)hits.size();
-    c->last_hits.swap(hits);
-    if ((int64_t)c->last_hits.size() > capacity) {
-        set_error("mtm_find_matches: output capacity too small (fetch the result with mtm_last_hits)");
-        return MTM_E_OVERFLOW;
-    }
-    if (!c->last_hits.empty()) std::memcpy(out, c->last_hits.data(), sizeof(mtm_hit) * c->last_hits.size());
-    return MTM_OK;
+    return publish_hits(hits, c->last_hits, out, capacity, n_out,
+                        "mtm_find_matches: output capacity too small (fetch the result with mtm_last_hits)");
 }
 
 int find_matches_impl(mtm_ctx* c, int mode, double score_threshold, mtm_hit* out, int64_t capacity,
@@ -914,19 +874,9 @@ int batch_chunk(mtm_ctx* c, const void* const* px, int nb, int rows, int cols, i
         HIPC(hipStreamSynchronize(c->stream));
         for (int b = 0; b < nb; ++b)
             for (int t = 0; t < n; ++t) {           // (fm_end's decoding, on the image's own index)
-                const unsigned long long key = best[2 * ((size_t)b * n + t) + (mode_min ? 1 : 0)];
                 const TemplDev& d = c->td_host[t];
-                uint32_t o = (uint32_t)(key >> 32);
-                if (mode_min) o = ~o;
-                const uint32_t idx = key ? (0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu)) : 0u;
-                mtm_hit h;
-                h.templ_idx = t;
-                h.x = (int)(idx % (uint32_t)d.ow);
-                h.y = (int)(idx / (uint32_t)d.ow);
-                h.w = d.cols;
-                h.h = d.rows;
-                h.score = key ? decode_order(o) : NAN;
-                per_img[b].push_back(h);
+                per_img[b].push_back(decode_extremum_key(best[2 * ((size_t)b * n + t) + (mode_min ? 1 : 0)], mode_min, t,
+                                                         d.ow, d.cols, d.rows));
             }
     } else {
         const int n2d = (int)c->list2d.size();
@@ -989,27 +939,8 @@ int batch_chunk(mtm_ctx* c, const void* const* px, int nb, int rows, int cols, i
             HIPC(hipMemcpy2DAsync(mp.data(), sizeof(float) * d.ow, maps + d.map_off, sizeof(float) * d.map_pitch,
                                   sizeof(float) * d.ow, d.oh, hipMemcpyDeviceToHost, c->stream));
             HIPC(hipStreamSynchronize(c->stream));
-            const int len = std::max(oh_b, d.ow);
-            for (int b = 0; b < nb; ++b) {
-                const float* line = mp.data() + (size_t)b * rows * d.ow;      // (a row, or a column of a one-column map)
-                std::vector<int> pk;
-                if (len == 1) {
-                    const float v = mode_min ? -line[0] : line[0];
-                    if (v >= (mode_min ? -thr : thr)) pk.push_back(0);
-                } else {
-                    pk = find_peaks_1d(line, len, 1, mode_min ? -thr : thr, mode_min);
-                }
-                for (int i : pk) {
-                    mtm_hit h;
-                    h.templ_idx = t;
-                    h.x = oh_b == 1 ? i : 0;
-                    h.y = oh_b == 1 ? 0 : i;
-                    h.w = d.cols;
-                    h.h = d.rows;
-                    h.score = line[(size_t)i];
-                    per_img[b].push_back(h);
-                }
-            }
+            for (int b = 0; b < nb; ++b)        // (a row, or a column of a one-column map)
+                line_map_peaks(mp.data() + (size_t)b * rows * d.ow, oh_b, d.ow, thr, mode_min, t, d.cols, d.rows, per_img[b]);
         }
         for (int b = 0; b < nb; ++b) sort_hits(per_img[b], mode_min);
     }
@@ -1021,6 +952,46 @@ int batch_chunk(mtm_ctx* c, const void* const* px, int nb, int rows, int cols, i
 }
 
 }  // namespace
+
+namespace mtmi {
+
+int window_peak_pass(mtm_ctx* c, int n, bool global, const WindowPeakLaunch& launch, std::vector<unsigned long long>& best,
+                     std::vector<mtm_hit>& recs, const char* who) {
+    const size_t flag_bytes = sizeof(unsigned long long) * (1 + (size_t)n) + sizeof(int) * (size_t)n;
+    MTMC(c->win_flags.ensure(flag_bytes));
+    std::vector<uint8_t> fl(flag_bytes);
+    unsigned long long cap = (unsigned long long)std::max<int64_t>(1, c->hit_cap), count = 0;
+    for (int pass = 0; pass < 2; ++pass) {          // (a list that overflowed: once more, large enough)
+        MTMC(c->win_hits.ensure(sizeof(mtm_hit) * (size_t)cap));
+        HIPC(hipMemsetAsync(c->win_flags.p, 0, flag_bytes, c->stream));
+        unsigned long long* counter = c->win_flags.as<unsigned long long>();
+        MTMC(launch(c->win_hits.as<mtm_hit>(), cap, counter, counter + 1, reinterpret_cast<int*>(counter + 1 + n)));
+        HIPC(hipMemcpyAsync(fl.data(), c->win_flags.p, flag_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        std::memcpy(&count, fl.data(), sizeof(count));
+        if (count <= cap) break;
+        if (pass == 1) {            // (cannot happen: the second pass runs with room for every record of the first)
+            set_error(std::string(who) + ": hit list overflowed twice");
+            return MTM_E_HIP;
+        }
+        cap = count + 1024;
+    }
+    if (global) {
+        best.resize((size_t)n);
+        if (n > 0) std::memcpy(best.data(), fl.data() + sizeof(unsigned long long), sizeof(unsigned long long) * (size_t)n);
+        return MTM_OK;
+    }
+    std::vector<mtm_hit> raw((size_t)count);
+    if (count > 0) HIPC(hipMemcpy(raw.data(), c->win_hits.p, sizeof(mtm_hit) * (size_t)count, hipMemcpyDeviceToHost));
+    std::vector<int> nontrivial((size_t)n);
+    if (n > 0) std::memcpy(nontrivial.data(), fl.data() + sizeof(unsigned long long) * (1 + (size_t)n), sizeof(int) * (size_t)n);
+    for (const mtm_hit& r : raw)
+        if (nontrivial[(size_t)r.templ_idx]) recs.push_back(r);     // a slot with no output that differs from its
+                                                                    // neighbourhood's max has no peaks
+    return MTM_OK;
+}
+
+}  // namespace mtmi
 
 extern "C" {
 
@@ -1181,14 +1152,8 @@ int mtm_find_matches_image_sharded_nms(mtm_ctx* c, const void* px, int rows, int
         all.swap(kept);
     }
     if (n_object >= 0 && (int64_t)all.size() > n_object) all.resize((size_t)n_object);
-    *n_out = (int64_t)all.size();
-    c->last_hits.swap(all);
-    if ((int64_t)c->last_hits.size() > capacity) {
-        set_error("mtm_find_matches_image_sharded_nms: output capacity too small (fetch the result with mtm_last_hits)");
-        return MTM_E_OVERFLOW;
-    }
-    if (!c->last_hits.empty()) std::memcpy(out, c->last_hits.data(), sizeof(mtm_hit) * c->last_hits.size());
-    return MTM_OK;
+    return publish_hits(all, c->last_hits, out, capacity, n_out,
+                        "mtm_find_matches_image_sharded_nms: output capacity too small (fetch the result with mtm_last_hits)");
 }
 
 int mtm_find_matches_next(mtm_ctx* c, int mode, double score_threshold, mtm_hit* out, int64_t capacity,
@@ -1270,14 +1235,8 @@ int mtm_find_matches_batch(mtm_ctx* c, const void* const* images, int n_images, 
     }
     acc.n_hits = (int64_t)all.size();
     c->timing = acc;
-    *n_out = (int64_t)all.size();
-    c->last_hits.swap(all);
-    if ((int64_t)c->last_hits.size() > capacity) {
-        set_error("mtm_find_matches_batch: output capacity too small (fetch the result with mtm_last_hits)");
-        return MTM_E_OVERFLOW;
-    }
-    if (!c->last_hits.empty()) std::memcpy(out, c->last_hits.data(), sizeof(mtm_hit) * c->last_hits.size());
-    return MTM_OK;
+    return publish_hits(all, c->last_hits, out, capacity, n_out,
+                        "mtm_find_matches_batch: output capacity too small (fetch the result with mtm_last_hits)");
 }
 
 int mtm_last_hits(mtm_ctx* c, mtm_hit* out, int64_t capacity, int64_t* n_out) {
@@ -1285,13 +1244,7 @@ int mtm_last_hits(mtm_ctx* c, mtm_hit* out, int64_t capacity, int64_t* n_out) {
         set_error("mtm_last_hits: bad arguments");
         return MTM_E_INVALID;
     }
-    *n_out = (int64_t)c->last_hits.size();
-    if ((int64_t)c->last_hits.size() > capacity) {
-        set_error("mtm_last_hits: output capacity too small");
-        return MTM_E_OVERFLOW;
-    }
-    if (!c->last_hits.empty()) std::memcpy(out, c->last_hits.data(), sizeof(mtm_hit) * c->last_hits.size());
-    return MTM_OK;
+    return copy_out_hits(c->last_hits, out, capacity, n_out, "mtm_last_hits: output capacity too small");
 }
 
 int mtm_last_score_map(mtm_ctx* c, int templ_idx, float* out, int64_t out_row_stride_bytes) {

@@ -120,58 +120,31 @@ __global__ __launch_bounds__(256) void boxes_peaks_kernel(const BoxUnit* __restr
 
 namespace {
 
-// The byte planes of every template (uint8: [C][h][w]; uint16: high bytes, then low bytes) and the epilogue constants of
-// mtm_set_templates' statistics, uploaded once per template set.
-int prepare_box_templates(mtm_ctx* c, const std::vector<BlobTempl>& tl) {
-    if (c->box_blob == c->templ_blob) return MTM_OK;
+// The epilogue constants of mtm_set_templates' statistics for every template, uploaded once per template set.
+int prepare_box_td(mtm_ctx* c, const std::vector<BlobTempl>& tl) {
+    if (c->box_gen == c->templ_gen) return MTM_OK;
     const int n = (int)tl.size();
     if ((int)c->templs.size() != n) {
         set_error("mtm_find_matches_boxes: template set and its statistics differ in size");
         return MTM_E_STATE;
     }
-    c->box_blob.clear();
-    std::vector<uint8_t> planar;
+    c->box_gen = 0;
     std::vector<TemplDev> td((size_t)n, TemplDev{});
-    c->box_toff.assign((size_t)n, 0);
     for (int i = 0; i < n; ++i) {
-        const BlobTempl& t = tl[(size_t)i];
-        const size_t plane = (size_t)t.rows * t.cols;
-        c->box_toff[(size_t)i] = (long long)planar.size();
-        if (t.dtype == MTM_U16) {
-            planar.resize(planar.size() + 2 * plane);
-            uint8_t* dst = planar.data() + c->box_toff[(size_t)i];
-            for (size_t p = 0; p < plane; ++p) {
-                uint16_t v;
-                std::memcpy(&v, t.px + 2 * p, sizeof(v));
-                dst[p] = (uint8_t)(v >> 8);
-                dst[plane + p] = (uint8_t)(v & 255u);
-            }
-        } else {
-            planar.resize(planar.size() + plane * t.chans);
-            uint8_t* dst = planar.data() + c->box_toff[(size_t)i];
-            for (size_t p = 0; p < plane; ++p)
-                for (int k = 0; k < t.chans; ++k) dst[(size_t)k * plane + p] = t.px[p * t.chans + k];
-        }
         const HostTempl& ht = c->templs[(size_t)i];
         TemplDev& d = td[(size_t)i];
         for (int k = 0; k < kMaxChans; ++k) d.mean[k] = ht.st.mean[k];
         d.templ_norm = ht.st.templ_norm;
         d.templ_sum2 = ht.st.templ_sum2;
         d.all_ones = ht.st.all_ones;
-        d.rows = t.rows;
-        d.cols = t.cols;
-    }
-    if (!planar.empty()) {
-        MTMC(c->box_tpx.ensure(planar.size()));
-        HIPC(hipMemcpy(c->box_tpx.p, planar.data(), planar.size(), hipMemcpyHostToDevice));
+        d.rows = tl[(size_t)i].rows;
+        d.cols = tl[(size_t)i].cols;
     }
     if (n > 0) {
-        MTMC(c->box_toff_dev.ensure(sizeof(long long) * (size_t)n));
-        HIPC(hipMemcpy(c->box_toff_dev.p, c->box_toff.data(), sizeof(long long) * (size_t)n, hipMemcpyHostToDevice));
         MTMC(c->box_td.ensure(sizeof(TemplDev) * (size_t)n));
         HIPC(hipMemcpy(c->box_td.p, td.data(), sizeof(TemplDev) * (size_t)n, hipMemcpyHostToDevice));
     }
-    c->box_blob = c->templ_blob;
+    c->box_gen = c->templ_gen;
     return MTM_OK;
 }
 
@@ -214,7 +187,7 @@ int boxes_chunk(mtm_ctx* c, const mtm_box_unit* units, const std::vector<BlobTem
     const long long n1d_floats = off - off1d;
     MTMC(c->box_units.ensure(sizeof(BoxUnit) * bu.size()));
     MTMC(c->box_tiles.ensure(sizeof(BoxTile) * tiles.size()));
-    MTMC(c->box_buf.ensure(sizeof(float) * (size_t)off));
+    MTMC(c->win_buf.ensure(sizeof(float) * (size_t)off));
     HIPC(hipMemcpyAsync(c->box_units.p, bu.data(), sizeof(BoxUnit) * bu.size(), hipMemcpyHostToDevice, c->stream));
     HIPC(hipMemcpyAsync(c->box_tiles.p, tiles.data(), sizeof(BoxTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
 
@@ -224,8 +197,8 @@ int boxes_chunk(mtm_ctx* c, const mtm_box_unit* units, const std::vector<BlobTem
     // 2^32 work items however many tiles a chunk or a single unit has)
 #define MTM_BOX_LAUNCH(CH, U16)                                                                                              \
     hipLaunchKernelGGL((boxes_score_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, lo_b,                          \
-                       c->box_tpx.as<uint8_t>(), c->box_toff_dev.as<long long>(), c->box_td.as<TemplDev>(),                  \
-                       c->box_units.as<BoxUnit>(), c->box_tiles.as<BoxTile>() + t0, c->box_buf.as<float>(), c->method)
+                       c->win_tpx.as<uint8_t>(), c->win_toff.as<long long>(), c->box_td.as<TemplDev>(),                      \
+                       c->box_units.as<BoxUnit>(), c->box_tiles.as<BoxTile>() + t0, c->win_buf.as<float>(), c->method)
     for (size_t t0 = 0; t0 < tiles.size(); t0 += kBoxLaunchTiles) {
         const unsigned nt = (unsigned)std::min(kBoxLaunchTiles, tiles.size() - t0);
         if (dtype == MTM_U16) MTM_BOX_LAUNCH(1, true);
@@ -235,93 +208,40 @@ int boxes_chunk(mtm_ctx* c, const mtm_box_unit* units, const std::vector<BlobTem
     }
 #undef MTM_BOX_LAUNCH
 
-    // [hit counter][best key per unit][nontrivial flag per unit]
-    const size_t flag_bytes = sizeof(unsigned long long) * (1 + (size_t)nu) + sizeof(int) * (size_t)nu;
-    MTMC(c->box_flags.ensure(flag_bytes));
-    std::vector<uint8_t> fl(flag_bytes);
     std::vector<float> maps1d(global ? 0 : (size_t)n1d_floats);
-    unsigned long long cap = (unsigned long long)std::max<int64_t>(1, c->hit_cap), count = 0;
     const size_t peak_tiles = global ? tiles.size() : n_tiles_2d;
-    for (int pass = 0; pass < 2; ++pass) {          // (a list that overflowed: once more, large enough)
-        MTMC(c->box_hits.ensure(sizeof(mtm_hit) * (size_t)cap));
-        HIPC(hipMemsetAsync(c->box_flags.p, 0, flag_bytes, c->stream));
-        unsigned long long* counter = c->box_flags.as<unsigned long long>();
-        int* nontrivial = reinterpret_cast<int*>(counter + 1 + nu);
+    bool first = true;
+    std::vector<mtm_hit> ch;            // this chunk's records, templ_idx = the unit's index in the chunk, unit coordinates
+    auto launch = [&](mtm_hit* dhits, unsigned long long cap, unsigned long long* counter, unsigned long long* best,
+                      int* nontrivial) -> int {
         for (size_t t0 = 0; t0 < peak_tiles; t0 += kBoxLaunchTiles) {
             const unsigned nt = (unsigned)std::min(kBoxLaunchTiles, peak_tiles - t0);
             hipLaunchKernelGGL(boxes_peaks_kernel, dim3(nt), dim3(256), 0, c->stream, c->box_units.as<BoxUnit>(),
-                               c->box_tiles.as<BoxTile>() + t0, c->box_buf.as<float>(), c->box_td.as<TemplDev>(),
-                               mode_min ? 1 : 0, global ? 1 : 0, mode_min ? -thr : thr, c->opt_border,
-                               c->box_hits.as<mtm_hit>(), cap, counter, counter + 1, nontrivial);
+                               c->box_tiles.as<BoxTile>() + t0, c->win_buf.as<float>(), c->box_td.as<TemplDev>(),
+                               mode_min ? 1 : 0, global ? 1 : 0, mode_min ? -thr : thr, c->opt_border, dhits, cap, counter,
+                               best, nontrivial);
             HIPC(hipGetLastError());
         }
-        HIPC(hipMemcpyAsync(fl.data(), c->box_flags.p, flag_bytes, hipMemcpyDeviceToHost, c->stream));
-        if (pass == 0 && !maps1d.empty())
-            HIPC(hipMemcpyAsync(maps1d.data(), c->box_buf.as<float>() + off1d, sizeof(float) * maps1d.size(),
+        if (first && !maps1d.empty())
+            HIPC(hipMemcpyAsync(maps1d.data(), c->win_buf.as<float>() + off1d, sizeof(float) * maps1d.size(),
                                 hipMemcpyDeviceToHost, c->stream));
-        HIPC(hipStreamSynchronize(c->stream));
-        std::memcpy(&count, fl.data(), sizeof(count));
-        if (count <= cap) break;
-        if (pass == 1) {            // (cannot happen: the second pass runs with room for every record of the first)
-            set_error("mtm_find_matches_boxes: hit list overflowed twice");
-            return MTM_E_HIP;
-        }
-        cap = count + 1024;
-    }
-    const unsigned long long* best = reinterpret_cast<const unsigned long long*>(fl.data()) + 1;
-    const int* nontrivial = reinterpret_cast<const int*>(fl.data() + sizeof(unsigned long long) * (1 + (size_t)nu));
-    std::vector<mtm_hit> ch;            // this chunk's records, templ_idx = the unit's index in the chunk, unit coordinates
+        first = false;
+        return MTM_OK;
+    };
+    std::vector<unsigned long long> best;
+    MTMC(window_peak_pass(c, nu, global, launch, best, ch, "mtm_find_matches_boxes"));
     if (global) {
         for (int k = 0; k < nu; ++k) {
-            unsigned long long key;
-            std::memcpy(&key, best + k, sizeof(key));
             const BoxUnit& b = bu[(size_t)k];
-            const uint32_t o = (uint32_t)(key >> 32);
-            const long long idx = 0xFFFFFFFFll - (long long)(key & 0xFFFFFFFFull);
-            const uint32_t bits = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;      // mf_order_float
-            float q;
-            std::memcpy(&q, &bits, sizeof(q));
-            mtm_hit h;
-            h.templ_idx = k;
-            h.x = (int32_t)(idx % b.ow);
-            h.y = (int32_t)(idx / b.ow);
-            h.w = tl[(size_t)b.t].cols;
-            h.h = tl[(size_t)b.t].rows;
-            h.score = key ? (mode_min ? -q : q) + 0.0f : NAN;
-            ch.push_back(h);
+            ch.push_back(decode_quality_key(best[(size_t)k], mode_min, k, b.ow, tl[(size_t)b.t].cols, tl[(size_t)b.t].rows));
         }
     } else {
-        std::vector<mtm_hit> raw((size_t)count);
-        if (count > 0)
-            HIPC(hipMemcpy(raw.data(), c->box_hits.p, sizeof(mtm_hit) * (size_t)count, hipMemcpyDeviceToHost));
-        for (const mtm_hit& r : raw) {
-            int nt;
-            std::memcpy(&nt, nontrivial + r.templ_idx, sizeof(nt));
-            if (nt) ch.push_back(r);        // a unit map with no output that differs from its neighbourhood's max has no peaks
-        }
         // 1-D and 1x1 unit maps (MTM/__init__.py:25-41), as mtm_find_matches treats a whole map of that shape
         for (int k = 0; k < nu; ++k) {
             const BoxUnit& b = bu[(size_t)k];
             if (b.oh > 1 && b.ow > 1) continue;
-            const float* line = maps1d.data() + (b.buf_off - off1d);
-            const int len = std::max(b.oh, b.ow);
-            std::vector<int> pk;
-            if (len == 1) {
-                const float v = mode_min ? -line[0] : line[0];
-                if (v >= (mode_min ? -thr : thr)) pk.push_back(0);
-            } else {
-                pk = find_peaks_1d(line, len, 1, mode_min ? -thr : thr, mode_min);
-            }
-            for (int i : pk) {
-                mtm_hit h;
-                h.templ_idx = k;
-                h.x = b.oh == 1 ? i : 0;
-                h.y = b.oh == 1 ? 0 : i;
-                h.w = tl[(size_t)b.t].cols;
-                h.h = tl[(size_t)b.t].rows;
-                h.score = line[(size_t)i];
-                ch.push_back(h);
-            }
+            line_map_peaks(maps1d.data() + (b.buf_off - off1d), b.oh, b.ow, thr, mode_min, k, tl[(size_t)b.t].cols,
+                           tl[(size_t)b.t].rows, ch);
         }
         sort_hits(ch, mode_min);
     }
@@ -390,7 +310,8 @@ int mtm_find_matches_boxes(mtm_ctx* c, const void* px, int rows, int cols, int c
     *n_out = 0;
     for (int u = 0; u < n_units; ++u) counts[u] = 0;
     HIPC(hipSetDevice(c->device));
-    MTMC(prepare_box_templates(c, tl));
+    MTMC(prepare_window_templates(c, tl));
+    MTMC(prepare_box_td(c, tl));
 
     // ONE upload of the image; every unit reads its region from the same planes
     c->timing = mtm_timing{};
@@ -415,15 +336,8 @@ int mtm_find_matches_boxes(mtm_ctx* c, const void* px, int rows, int cols, int c
         MTMC(boxes_chunk(c, units, tl, u0, u1, chans, dtype, mode, thr, hits, counts));
         u0 = u1;
     }
-    c->last_hits = hits;
     c->timing.n_hits = (int64_t)hits.size();
-    *n_out = (int64_t)hits.size();
-    if ((int64_t)hits.size() > capacity) {
-        set_error(std::string(who) + ": output capacity too small");
-        return MTM_E_OVERFLOW;
-    }
-    if (!hits.empty()) std::memcpy(out, hits.data(), sizeof(mtm_hit) * hits.size());
-    return MTM_OK;
+    return publish_hits(hits, c->last_hits, out, capacity, n_out, std::string(who) + ": output capacity too small");
 }
 
 }  // extern "C"

@@ -365,9 +365,8 @@ void mtm_ctx_destroy(mtm_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->pyr_sub) mtm_ctx_destroy(c->pyr_sub);
-    for (DevBuf* b : {&c->pyr_tpx, &c->pyr_toff_dev, &c->pyr_wins, &c->pyr_buf, &c->pyr_hits, &c->pyr_flags}) b->release();
-    for (DevBuf* b : {&c->box_tpx, &c->box_toff_dev, &c->box_td, &c->box_units, &c->box_tiles, &c->box_buf, &c->box_hits,
-                      &c->box_flags})
+    for (DevBuf* b : {&c->win_tpx, &c->win_toff, &c->win_buf, &c->win_hits, &c->win_flags, &c->pyr_wins, &c->box_td,
+                      &c->box_units, &c->box_tiles})
         b->release();
     for (auto& sl : c->slot)
         for (DevBuf* b : {&sl.raw, &sl.u8, &sl.u8b, &sl.f32}) b->release();

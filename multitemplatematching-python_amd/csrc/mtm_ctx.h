@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <thread>
@@ -364,21 +365,25 @@ struct mtm_ctx {
     void* comm_pin = nullptr;           // pinned staging of the hit exchange: [my slot | gathered slots]
     size_t comm_pin_cap = 0;
     std::vector<uint8_t> templ_blob;    // bytes of the templates of the last mtm_set_templates (unchanged-input test)
+    uint64_t templ_gen = 0;             // bumped whenever templ_blob changes: what caches of the template set are keyed on
+    // The window searches (mtm_find_matches_pyramid, mtm_find_matches_boxes): the templates' byte planes at win_toff[t] in
+    // win_tpx (prepare_window_templates; made for the template set win_gen, whose bytes win_blob keeps so that the set
+    // set again after others finds them), and the per-call score buffer, hit list and flags of the peak pass
+    // (window_peak_pass).
+    uint64_t win_gen = 0;
+    std::vector<uint8_t> win_blob;
+    DevBuf win_tpx, win_toff, win_buf, win_hits, win_flags;
     // mtm_find_matches_pyramid (mtm_pyramid.hip): the coarse level runs in a context of its own on the same device (its
-    // templates are the downscaled ones, its image the downscaled planes made from this context's upload); the fine level's
-    // full-resolution template pixels (planar, per template at pyr_toff[t]) and per-call buffers live here.  pyr_blob /
-    // pyr_factor: the template set and factor they were made for.
+    // templates are the downscaled ones, its image the downscaled planes made from this context's upload); pyr_gen /
+    // pyr_factor: the template set and factor its templates were made for.  pyr_wins: the call's window table.
     mtm_ctx* pyr_sub = nullptr;
-    std::vector<uint8_t> pyr_blob;
+    uint64_t pyr_gen = 0;
     int pyr_factor = 0;
-    std::vector<long long> pyr_toff;
-    DevBuf pyr_tpx, pyr_toff_dev, pyr_wins, pyr_buf, pyr_hits, pyr_flags;
-    // mtm_find_matches_boxes (mtm_boxes.hip): the templates' pixels as byte planes (uint8: [C][h][w]; uint16: high bytes,
-    // then low bytes) at box_toff[t], their epilogue constants (box_td), all made for the template set box_blob; the
-    // per-call tables, unit maps, hit list and flags.  boxes_max_floats: MTM_OPT_BOXES_MAX_FLOATS.
-    std::vector<uint8_t> box_blob;
-    std::vector<long long> box_toff;
-    DevBuf box_tpx, box_toff_dev, box_td, box_units, box_tiles, box_buf, box_hits, box_flags;
+    DevBuf pyr_wins;
+    // mtm_find_matches_boxes (mtm_boxes.hip): the templates' epilogue constants (box_td, made for the template set
+    // box_gen), the per-call unit and tile tables.  boxes_max_floats: MTM_OPT_BOXES_MAX_FLOATS.
+    uint64_t box_gen = 0;
+    DevBuf box_td, box_units, box_tiles;
     int64_t boxes_max_floats = 1ll << 26;
 
     // RCCL
@@ -513,13 +518,24 @@ int upload_image_stack(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* const* px
                        int cols, int chans, int dtype, hipStream_t stream);
 void adopt_image(mtm_ctx* c, int rows, int cols, int chans, int dtype);
 // One template of the last mtm_set_templates as its bytes in mtm_ctx::templ_blob (interleaved, tightly packed rows of
-// `dtype` pixels); parse_templ_blob (mtm_pyramid.hip) lists them - unmasked uint8 templates, with `u16_ok` also unmasked
+// `dtype` pixels); parse_templ_blob (mtm_placement.hip) lists them - unmasked uint8 templates, with `u16_ok` also unmasked
 // single-channel uint16 ones - for mtm_find_matches_pyramid and mtm_find_matches_boxes.
 struct BlobTempl {
     int rows, cols, chans, dtype;
     const uint8_t* px;
 };
 int parse_templ_blob(const std::vector<uint8_t>& b, std::vector<BlobTempl>& out, const char* who, bool u16_ok);
+int prepare_window_templates(mtm_ctx* c, const std::vector<BlobTempl>& tl);
+// The peak pass of the window searches (mtm_api.hip) over n slots (pyramid: templates, boxes: units).  Flags laid out as
+// [u64 record count][u64 best key x n][int nontrivial x n] are zeroed, `launch` enqueues the peak kernels (and anything that
+// must follow them before the read-back) writing records to (hits, cap), the flags come back in one copy; a list that
+// overflowed runs once more with room for every record.  Global mode: the best key per slot into `best`.  Local mode: the
+// records of the slots flagged nontrivial, unsorted, appended to `recs`.  The list starts at mtm_ctx::hit_cap records and
+// grows for this call only: hit_cap is left as it is (later mtm_find_matches routes size candidate lists by it).
+using WindowPeakLaunch = std::function<int(mtm_hit* hits, unsigned long long cap, unsigned long long* counter,
+                                           unsigned long long* best, int* nontrivial)>;
+int window_peak_pass(mtm_ctx* c, int n, bool global, const WindowPeakLaunch& launch, std::vector<unsigned long long>& best,
+                     std::vector<mtm_hit>& recs, const char* who);
 // The planes of `dst`'s current slot from the raw uint8 image already in `src` (src_rows x src_cols, tightly packed),
 // area-downscaled by `factor` on `stream`; `dst` adopts the downscaled image (mtm_find_matches_pyramid's coarse level).
 int derive_downscaled_u8(mtm_ctx* dst, const mtm_ctx::ImageSlot& src, int src_rows, int src_cols, int chans, int factor,

@@ -428,14 +428,8 @@ static int group_search(mtm_group* g, const mtm_templ* templs, int n_templ, int 
         }
         if (nms.n_object >= 0 && (int64_t)all.size() > nms.n_object) all.resize((size_t)nms.n_object);
     }
-    *n_out = (int64_t)all.size();
-    g->last_hits.swap(all);
-    if ((int64_t)g->last_hits.size() > capacity) {
-        set_error("mtm_group_find_matches: output capacity too small (fetch the result with mtm_group_last_hits)");
-        return MTM_E_OVERFLOW;
-    }
-    if (!g->last_hits.empty()) std::memcpy(out, g->last_hits.data(), sizeof(mtm_hit) * g->last_hits.size());
-    return MTM_OK;
+    return publish_hits(all, g->last_hits, out, capacity, n_out,
+                        "mtm_group_find_matches: output capacity too small (fetch the result with mtm_group_last_hits)");
 }
 
 extern "C" {
@@ -464,13 +458,7 @@ int mtm_group_last_hits(mtm_group* g, mtm_hit* out, int64_t capacity, int64_t* n
         set_error("mtm_group_last_hits: bad arguments");
         return MTM_E_INVALID;
     }
-    *n_out = (int64_t)g->last_hits.size();
-    if ((int64_t)g->last_hits.size() > capacity) {
-        set_error("mtm_group_last_hits: output capacity too small");
-        return MTM_E_OVERFLOW;
-    }
-    if (!g->last_hits.empty()) std::memcpy(out, g->last_hits.data(), sizeof(mtm_hit) * g->last_hits.size());
-    return MTM_OK;
+    return copy_out_hits(g->last_hits, out, capacity, n_out, "mtm_group_last_hits: output capacity too small");
 }
 
 }  // extern "C"

@@ -169,6 +169,77 @@ std::vector<int> find_peaks_1d(const float* x, int n, int stride, float height, 
     return peaks;
 }
 
+void line_map_peaks(const float* line, int oh, int ow, float thr, bool mode_min, int templ_idx, int w, int h,
+                    std::vector<mtm_hit>& out) {
+    const int len = std::max(oh, ow);
+    const float thr_q = mode_min ? -thr : thr;
+    std::vector<int> pk;
+    if (len == 1) {
+        if ((mode_min ? -line[0] : line[0]) >= thr_q) pk.push_back(0);
+    } else {
+        pk = find_peaks_1d(line, len, 1, thr_q, mode_min);
+    }
+    for (int i : pk) {
+        mtm_hit r;
+        r.templ_idx = templ_idx;
+        r.x = oh == 1 ? i : 0;
+        r.y = oh == 1 ? 0 : i;
+        r.w = w;
+        r.h = h;
+        r.score = line[(size_t)i];
+        out.push_back(r);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Extremum keys and published results.
+// ---------------------------------------------------------------------------------------------
+float order_to_float(uint32_t o) {
+    const uint32_t b = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;
+    float v;
+    std::memcpy(&v, &b, 4);
+    return v;
+}
+
+static mtm_hit key_record(uint32_t idx, float score, int templ_idx, int ow, int w, int h) {
+    mtm_hit r;
+    r.templ_idx = templ_idx;
+    r.x = (int)(idx % (uint32_t)ow);
+    r.y = (int)(idx / (uint32_t)ow);
+    r.w = w;
+    r.h = h;
+    r.score = score;
+    return r;
+}
+
+mtm_hit decode_extremum_key(unsigned long long key, bool mode_min, int templ_idx, int ow, int w, int h) {
+    const uint32_t o = (uint32_t)(key >> 32);
+    const uint32_t idx = key ? (0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu)) : 0u;
+    return key_record(idx, key ? order_to_float(mode_min ? ~o : o) : NAN, templ_idx, ow, w, h);
+}
+
+mtm_hit decode_quality_key(unsigned long long key, bool mode_min, int templ_idx, int ow, int w, int h) {
+    const float q = order_to_float((uint32_t)(key >> 32));
+    const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu);
+    return key_record(idx, key ? (mode_min ? -q : q) + 0.0f : NAN, templ_idx, ow, w, h);
+}
+
+int copy_out_hits(const std::vector<mtm_hit>& hits, mtm_hit* out, int64_t capacity, int64_t* n_out, const std::string& msg) {
+    *n_out = (int64_t)hits.size();
+    if ((int64_t)hits.size() > capacity) {
+        set_error(msg);
+        return MTM_E_OVERFLOW;
+    }
+    if (!hits.empty()) std::memcpy(out, hits.data(), sizeof(mtm_hit) * hits.size());
+    return MTM_OK;
+}
+
+int publish_hits(std::vector<mtm_hit>& hits, std::vector<mtm_hit>& last_hits, mtm_hit* out, int64_t capacity,
+                 int64_t* n_out, const std::string& msg) {
+    last_hits.swap(hits);
+    return copy_out_hits(last_hits, out, capacity, n_out, msg);
+}
+
 // ---------------------------------------------------------------------------------------------
 // cv2.dnn.NMSBoxes (OpenCV dnn/nms.cpp + nms.inl.hpp) as called at reference MTM/NMS.py:78.
 // ---------------------------------------------------------------------------------------------

@@ -39,6 +39,29 @@ void u8_run_sums(const uint8_t* p, size_t n, unsigned long long* sum, unsigned l
 // scipy.signal.find_peaks(x, height=h)[0]
 std::vector<int> find_peaks_1d(const float* x, int n, int stride, float height, bool negate);
 
+// The peaks of a 1-D or 1x1 score map (MTM/__init__.py:25-41) as records of template `templ_idx` (a w x h box), appended to
+// `out`: a 1x1 map is a peak when its quality reaches `thr`, a longer line goes through find_peaks_1d.  `line` holds the map's
+// max(oh, ow) values contiguously; the record's x runs along a row (oh == 1), its y down a column.
+void line_map_peaks(const float* line, int oh, int ow, float thr, bool mode_min, int templ_idx, int w, int h,
+                    std::vector<mtm_hit>& out);
+
+// the float32 of an order key's high word (the inverse of mf_float_order, mtm_device_util.hip.h)
+float order_to_float(uint32_t o);
+
+// Hit records from the 64-bit extremum keys of a map ow outputs wide (order << 32 | ~row-major index):
+//  - decode_extremum_key: one of the max / min pair of extremum_kernel / extremum_batch_kernel (the minimum's order is
+//    stored complemented); key == 0 (no output) -> score NaN at (0, 0)
+//  - decode_quality_key: the window kernels' key over the quality (score, or -score for the difference methods);
+//    key == 0 -> score NaN, the index as the key reads
+mtm_hit decode_extremum_key(unsigned long long key, bool mode_min, int templ_idx, int ow, int w, int h);
+mtm_hit decode_quality_key(unsigned long long key, bool mode_min, int templ_idx, int ow, int w, int h);
+
+// A call's result: `hits` becomes `last_hits` (what mtm_last_hits / mtm_group_last_hits hand out afterwards), *n_out its
+// size; MTM_E_OVERFLOW with `msg` when it exceeds `capacity`, else it is copied to `out`.  copy_out_hits: the copy alone.
+int copy_out_hits(const std::vector<mtm_hit>& hits, mtm_hit* out, int64_t capacity, int64_t* n_out, const std::string& msg);
+int publish_hits(std::vector<mtm_hit>& hits, std::vector<mtm_hit>& last_hits, mtm_hit* out, int64_t capacity,
+                 int64_t* n_out, const std::string& msg);
+
 // float32-faithful restatement of cv2.dnn.NMSBoxes as called by MTM.NMS
 void nms_boxes(const mtm_hit* hits, int64_t n, const float* scores, float score_threshold,
                float nms_threshold, std::vector<int32_t>& keep);

@@ -774,6 +774,95 @@ int place_templates(mtm_ctx* c) {
     return MTM_OK;
 }
 
+// The templates of the last mtm_set_templates, read back from the bytes the context keeps of them (mtm_ctx::templ_blob,
+// written by set_templates_impl: n_templ, method, n_var, then per template {rows, cols, chans, dtype, has_mask} + rows).
+// Unmasked uint8 templates; with `u16_ok` also unmasked single-channel uint16 ones.
+int parse_templ_blob(const std::vector<uint8_t>& b, std::vector<BlobTempl>& out, const char* who, bool u16_ok) {
+    size_t off = 0;
+    auto rd = [&](void* dst, size_t n) {
+        if (off + n > b.size()) return false;
+        std::memcpy(dst, b.data() + off, n);
+        off += n;
+        return true;
+    };
+    int n_templ = 0, method = 0, n_var = 0;
+    if (!rd(&n_templ, sizeof(int)) || !rd(&method, sizeof(int)) || !rd(&n_var, sizeof(int))) {
+        set_error(std::string(who) + ": no templates set");
+        return MTM_E_STATE;
+    }
+    if (n_var != 0) {
+        set_error(std::string(who) + ": takes the templates of mtm_set_templates (not an augmented set)");
+        return MTM_E_INVALID;
+    }
+    out.clear();
+    for (int i = 0; i < n_templ; ++i) {
+        int hdr[5];
+        if (!rd(hdr, sizeof(hdr))) return MTM_E_STATE;
+        const bool u16 = u16_ok && hdr[3] == MTM_U16 && hdr[2] == 1;
+        if ((hdr[3] != MTM_U8 && !u16) || hdr[4] != 0) {
+            set_error(std::string(who) + ": template " + std::to_string(i) +
+                      (u16_ok ? " is not an unmasked uint8 or single-channel uint16 template"
+                              : " is not an unmasked uint8 template"));
+            return MTM_E_INVALID;
+        }
+        const size_t bytes = (size_t)hdr[0] * hdr[1] * hdr[2] * (u16 ? 2 : 1);
+        if (off + bytes > b.size()) return MTM_E_STATE;
+        out.push_back(BlobTempl{hdr[0], hdr[1], hdr[2], hdr[3], b.data() + off});
+        off += bytes;
+    }
+    return MTM_OK;
+}
+
+// The byte planes of every template for the window searches (mtm_find_matches_pyramid / _boxes): uint8 [C][h][w], a
+// single-channel uint16 template its high bytes, then its low bytes; template t's at win_tpx + win_toff[t].  Built once
+// per template set (win_gen).
+int prepare_window_templates(mtm_ctx* c, const std::vector<BlobTempl>& tl) {
+    if (c->win_gen != c->templ_gen && !c->win_blob.empty() && c->win_blob == c->templ_blob) {
+        // the set they were made from, set again after others (sets used in turn on one context): every cache made for
+        // it moves to the new generation
+        if (c->pyr_gen == c->win_gen) c->pyr_gen = c->templ_gen;
+        if (c->box_gen == c->win_gen) c->box_gen = c->templ_gen;
+        c->win_gen = c->templ_gen;
+    }
+    if (c->win_gen == c->templ_gen) return MTM_OK;
+    c->win_gen = 0;
+    c->win_blob.clear();
+    const size_t n = tl.size();
+    std::vector<uint8_t> planar;
+    std::vector<long long> toff(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const BlobTempl& t = tl[i];
+        const size_t plane = (size_t)t.rows * t.cols;
+        toff[i] = (long long)planar.size();
+        if (t.dtype == MTM_U16) {
+            planar.resize(planar.size() + 2 * plane);
+            uint8_t* dst = planar.data() + toff[i];
+            for (size_t p = 0; p < plane; ++p) {
+                uint16_t v;
+                std::memcpy(&v, t.px + 2 * p, sizeof(v));
+                dst[p] = (uint8_t)(v >> 8);
+                dst[plane + p] = (uint8_t)(v & 255u);
+            }
+        } else {
+            planar.resize(planar.size() + plane * t.chans);
+            uint8_t* dst = planar.data() + toff[i];
+            for (size_t p = 0; p < plane; ++p)
+                for (int k = 0; k < t.chans; ++k) dst[(size_t)k * plane + p] = t.px[p * t.chans + k];
+        }
+    }
+    if (!planar.empty()) {
+        MTMC(c->win_tpx.ensure(planar.size()));
+        HIPC(hipMemcpy(c->win_tpx.p, planar.data(), planar.size(), hipMemcpyHostToDevice));
+    }
+    if (n > 0) {
+        MTMC(c->win_toff.ensure(sizeof(long long) * n));
+        HIPC(hipMemcpy(c->win_toff.p, toff.data(), sizeof(long long) * n, hipMemcpyHostToDevice));
+    }
+    c->win_blob = c->templ_blob;
+    c->win_gen = c->templ_gen;
+    return MTM_OK;
+}
+
 }  // namespace mtmi
 
 extern "C" {
@@ -1118,6 +1207,7 @@ int set_templates_impl(mtm_ctx* c, const mtm_templ* templs, int n_templ, const m
         blob.reserve(total);
         walk([&](const void* p, size_t n) { blob.insert(blob.end(), (const uint8_t*)p, (const uint8_t*)p + n); });
         c->templ_blob.swap(blob);
+        ++c->templ_gen;
         c->have_templ = false;          // until the new set is complete
     }
     std::vector<HostTempl> hts;
@@ -1125,6 +1215,7 @@ int set_templates_impl(mtm_ctx* c, const mtm_templ* templs, int n_templ, const m
         const int rc = set_templates_device(c, templs, n_templ, variants, n_var, method, hts);
         if (rc != MTM_OK) {
             c->templ_blob.clear();
+            ++c->templ_gen;
             return rc;
         }
         n_templ = (int)hts.size();

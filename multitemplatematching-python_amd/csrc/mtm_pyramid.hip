@@ -116,49 +116,6 @@ __global__ __launch_bounds__(256) void pyr_window_kernel(ImageDev img, const uin
 
 }  // namespace mtm
 
-namespace mtmi {
-
-// The templates of the last mtm_set_templates, read back from the bytes the context keeps of them (mtm_ctx::templ_blob,
-// written by set_templates_impl: n_templ, method, n_var, then per template {rows, cols, chans, dtype, has_mask} + rows).
-// Unmasked uint8 templates; with `u16_ok` also unmasked single-channel uint16 ones.
-int parse_templ_blob(const std::vector<uint8_t>& b, std::vector<BlobTempl>& out, const char* who, bool u16_ok) {
-    size_t off = 0;
-    auto rd = [&](void* dst, size_t n) {
-        if (off + n > b.size()) return false;
-        std::memcpy(dst, b.data() + off, n);
-        off += n;
-        return true;
-    };
-    int n_templ = 0, method = 0, n_var = 0;
-    if (!rd(&n_templ, sizeof(int)) || !rd(&method, sizeof(int)) || !rd(&n_var, sizeof(int))) {
-        set_error(std::string(who) + ": no templates set");
-        return MTM_E_STATE;
-    }
-    if (n_var != 0) {
-        set_error(std::string(who) + ": takes the templates of mtm_set_templates (not an augmented set)");
-        return MTM_E_INVALID;
-    }
-    out.clear();
-    for (int i = 0; i < n_templ; ++i) {
-        int hdr[5];
-        if (!rd(hdr, sizeof(hdr))) return MTM_E_STATE;
-        const bool u16 = u16_ok && hdr[3] == MTM_U16 && hdr[2] == 1;
-        if ((hdr[3] != MTM_U8 && !u16) || hdr[4] != 0) {
-            set_error(std::string(who) + ": template " + std::to_string(i) +
-                      (u16_ok ? " is not an unmasked uint8 or single-channel uint16 template"
-                              : " is not an unmasked uint8 template"));
-            return MTM_E_INVALID;
-        }
-        const size_t bytes = (size_t)hdr[0] * hdr[1] * hdr[2] * (u16 ? 2 : 1);
-        if (off + bytes > b.size()) return MTM_E_STATE;
-        out.push_back(BlobTempl{hdr[0], hdr[1], hdr[2], hdr[3], b.data() + off});
-        off += bytes;
-    }
-    return MTM_OK;
-}
-
-}  // namespace mtmi
-
 namespace {
 
 // augment.downscale / planarize_u8_down_kernel on the host: factor 2 -> (sum + 2) >> 2, else rint((float)sum / f^2)
@@ -224,13 +181,12 @@ int mtm_find_matches_pyramid(mtm_ctx* c, const void* px, int rows, int cols, int
     if (!c->pyr_sub) MTMC(mtm_ctx_create(&c->pyr_sub, c->device));
     mtm_ctx* s = c->pyr_sub;
     s->opt_border = c->opt_border;
-    if (c->pyr_factor != factor || c->pyr_blob != c->templ_blob) {
-        // the coarse templates (the coarse context's set) and the full-resolution pixels, planar [C][h][w] per template
-        c->pyr_blob.clear();
+    MTMC(prepare_window_templates(c, tl));
+    if (c->pyr_factor != factor || c->pyr_gen != c->templ_gen) {
+        // the coarse templates (the coarse context's set)
+        c->pyr_gen = 0;
         std::vector<std::vector<uint8_t>> coarse((size_t)n);
         std::vector<mtm_templ> recs((size_t)n);
-        std::vector<uint8_t> planar;
-        c->pyr_toff.assign((size_t)n, 0);
         for (int i = 0; i < n; ++i) {
             const BlobTempl& t = tl[(size_t)i];
             coarse[(size_t)i] = downscale_u8(t, factor);
@@ -243,21 +199,9 @@ int mtm_find_matches_pyramid(mtm_ctx* c, const void* px, int rows, int cols, int
             r.dtype = MTM_U8;
             r.row_stride = (int64_t)r.cols * r.chans;
             r.mask_row_stride = 0;
-            c->pyr_toff[(size_t)i] = (long long)planar.size();
-            const size_t plane = (size_t)t.rows * t.cols;
-            planar.resize(planar.size() + plane * t.chans);
-            uint8_t* dst = planar.data() + c->pyr_toff[(size_t)i];
-            for (size_t p = 0; p < plane; ++p)
-                for (int k = 0; k < t.chans; ++k) dst[(size_t)k * plane + p] = t.px[p * t.chans + k];
         }
         MTMC(mtm_set_templates(s, recs.data(), n, c->method));
-        if (!planar.empty()) {
-            MTMC(c->pyr_tpx.ensure(planar.size()));
-            HIPC(hipMemcpy(c->pyr_tpx.p, planar.data(), planar.size(), hipMemcpyHostToDevice));
-            MTMC(c->pyr_toff_dev.ensure(sizeof(long long) * (size_t)n));
-            HIPC(hipMemcpy(c->pyr_toff_dev.p, c->pyr_toff.data(), sizeof(long long) * (size_t)n, hipMemcpyHostToDevice));
-        }
-        c->pyr_blob = c->templ_blob;
+        c->pyr_gen = c->templ_gen;
         c->pyr_factor = factor;
     }
 
@@ -320,91 +264,45 @@ int mtm_find_matches_pyramid(mtm_ctx* c, const void* px, int rows, int cols, int
     }
 
     const bool mode_min = c->method == MTM_TM_SQDIFF_NORMED;
+    const bool global = mode == MTM_PEAKS_GLOBAL;
     std::vector<mtm_hit> hits;
     if (!wins.empty()) {
         MTMC(c->pyr_wins.ensure(sizeof(PyrWin) * wins.size()));
         HIPC(hipMemcpyAsync(c->pyr_wins.p, wins.data(), sizeof(PyrWin) * wins.size(), hipMemcpyHostToDevice, c->stream));
-        MTMC(c->pyr_buf.ensure(sizeof(float) * (size_t)buf_floats));
-        // [hit counter][best key per template][nontrivial flag per template]
-        const size_t flag_bytes = sizeof(unsigned long long) * (1 + (size_t)n) + sizeof(int) * (size_t)n;
-        MTMC(c->pyr_flags.ensure(flag_bytes));
-        std::vector<uint8_t> fl(flag_bytes);
-        if (c->pyr_hits.cap < sizeof(mtm_hit) * 4096) MTMC(c->pyr_hits.ensure(sizeof(mtm_hit) * 4096));
+        MTMC(c->win_buf.ensure(sizeof(float) * (size_t)buf_floats));
         const float thr = (float)score_threshold;       // numpy compares the float32 map with the threshold in float32
-        unsigned long long count = 0;
-        for (int pass = 0; pass < 2; ++pass) {
-            const unsigned long long cap = c->pyr_hits.cap / sizeof(mtm_hit);
-            HIPC(hipMemsetAsync(c->pyr_flags.p, 0, flag_bytes, c->stream));
-            unsigned long long* counter = c->pyr_flags.as<unsigned long long>();
-            int* nontrivial = reinterpret_cast<int*>(counter + 1 + n);
-            const ImageDev img = image_dev(c);
+        const ImageDev img = image_dev(c);
 #define MTM_PYR_LAUNCH(CH)                                                                                                  \
     hipLaunchKernelGGL(pyr_window_kernel<CH>, dim3((unsigned)wins.size()), dim3(256), 0, c->stream, img,                    \
-                       c->pyr_tpx.as<uint8_t>(), c->pyr_toff_dev.as<long long>(), c->td.as<TemplDev>(),                     \
-                       c->pyr_wins.as<PyrWin>(), c->pyr_buf.as<float>(), c->method, mode_min ? 1 : 0,                        \
-                       mode == MTM_PEAKS_GLOBAL ? 1 : 0, mode_min ? -thr : thr, c->opt_border, c->pyr_hits.as<mtm_hit>(), \
-                       cap, counter, counter + 1, nontrivial)
+                       c->win_tpx.as<uint8_t>(), c->win_toff.as<long long>(), c->td.as<TemplDev>(), c->pyr_wins.as<PyrWin>(), \
+                       c->win_buf.as<float>(), c->method, mode_min ? 1 : 0, global ? 1 : 0, mode_min ? -thr : thr,           \
+                       c->opt_border, dhits, cap, counter, best, nontrivial)
+        auto launch = [&](mtm_hit* dhits, unsigned long long cap, unsigned long long* counter, unsigned long long* best,
+                          int* nontrivial) -> int {
             switch (chans) {
                 case 1: MTM_PYR_LAUNCH(1); break;
                 case 2: MTM_PYR_LAUNCH(2); break;
                 case 3: MTM_PYR_LAUNCH(3); break;
                 default: MTM_PYR_LAUNCH(4); break;
             }
-#undef MTM_PYR_LAUNCH
             HIPC(hipGetLastError());
-            HIPC(hipMemcpyAsync(fl.data(), c->pyr_flags.p, flag_bytes, hipMemcpyDeviceToHost, c->stream));
-            HIPC(hipStreamSynchronize(c->stream));
-            std::memcpy(&count, fl.data(), sizeof(count));
-            if (count <= cap) break;
-            if (pass == 1) {        // (cannot happen: the second pass runs with room for every record of the first)
-                set_error(std::string(who) + ": hit list overflowed twice");
-                return MTM_E_HIP;
-            }
-            MTMC(c->pyr_hits.ensure(sizeof(mtm_hit) * (size_t)count));
-        }
-        const unsigned long long* best = reinterpret_cast<const unsigned long long*>(fl.data()) + 1;
-        const int* nontrivial = reinterpret_cast<const int*>(fl.data() + sizeof(unsigned long long) * (1 + (size_t)n));
-        if (mode == MTM_PEAKS_GLOBAL) {
+            return MTM_OK;
+        };
+#undef MTM_PYR_LAUNCH
+        std::vector<unsigned long long> best;
+        MTMC(window_peak_pass(c, n, global, launch, best, hits, who));
+        if (global) {
             for (int t = 0; t < n; ++t) {
-                unsigned long long key;
-                std::memcpy(&key, best + t, sizeof(key));
-                if (key == 0ull) continue;
+                if (best[(size_t)t] == 0ull) continue;
                 const TemplDev& d = c->td_host[(size_t)t];
-                const uint32_t o = (uint32_t)(key >> 32);
-                const long long idx = 0xFFFFFFFFll - (long long)(key & 0xFFFFFFFFull);
-                const uint32_t b = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;      // mf_order_float
-                float q;
-                std::memcpy(&q, &b, sizeof(q));
-                mtm_hit hrec;
-                hrec.templ_idx = t;
-                hrec.x = (int32_t)(idx % d.ow);
-                hrec.y = (int32_t)(idx / d.ow);
-                hrec.w = d.cols;
-                hrec.h = d.rows;
-                hrec.score = (mode_min ? -q : q) + 0.0f;
-                hits.push_back(hrec);
+                hits.push_back(decode_quality_key(best[(size_t)t], mode_min, t, d.ow, d.cols, d.rows));
             }
         } else {
-            std::vector<mtm_hit> raw((size_t)count);
-            if (count > 0)
-                HIPC(hipMemcpy(raw.data(), c->pyr_hits.p, sizeof(mtm_hit) * (size_t)count, hipMemcpyDeviceToHost));
-            for (const mtm_hit& r : raw) {
-                int nt;
-                std::memcpy(&nt, nontrivial + r.templ_idx, sizeof(nt));
-                if (nt) hits.push_back(r);      // a template whose windows hold no non-maximum position has no peaks
-            }
             sort_hits(hits, mode_min);
         }
     }
-    c->last_hits = hits;
     c->timing.n_hits = (int64_t)hits.size();
-    *n_out = (int64_t)hits.size();
-    if ((int64_t)hits.size() > capacity) {
-        set_error(std::string(who) + ": output capacity too small");
-        return MTM_E_OVERFLOW;
-    }
-    if (!hits.empty()) std::memcpy(out, hits.data(), sizeof(mtm_hit) * hits.size());
-    return MTM_OK;
+    return publish_hits(hits, c->last_hits, out, capacity, n_out, std::string(who) + ": output capacity too small");
 }
 
 }  // extern "C"

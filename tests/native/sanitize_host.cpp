@@ -1,11 +1,12 @@
 // Sanitizer driver for the host-only C++ of libmtm_hip.so (no GPU, no HIP): mtm_host.cpp (NMS, 1-D peaks, hit
-// sorting, template statistics) and mtm_group.cpp (worker threads, generation counter, LPT shards, host merge) are
+// sorting, extremum-key decoding, result hand-over, template statistics) and mtm_group.cpp (worker threads, generation counter, LPT shards, host merge) are
 // compiled as they are, with -fsanitize=address,undefined and again with -fsanitize=thread; the per-device context
 // API the group drives (mtm_ctx_create, mtm_set_templates, mtm_find_matches_image, ...) is replaced by a fake that
 // returns deterministic hits - so the group's threading protocol runs thousands of jobs under the sanitizers.
 // Built and run by tests/test_native_sanitizers_cpu.py.
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -313,6 +314,73 @@ static void test_host(std::mt19937& rng) {
         for (auto& v : line) v = (float)(rng() % 7) * 0.1f;
         const std::vector<int> pk = find_peaks_1d(line.data(), len, 1, 0.25f, (rep & 2) != 0);
         for (int p : pk) CHECK(p > 0 && p < len - 1);
+        // line_map_peaks: the 1x1 rule and find_peaks_1d restated, in both orientations and both modes
+        for (int orient = 0; orient < 2; ++orient) {
+            const bool mode_min = (rep & 4) != 0;
+            const float thr = mode_min ? 0.35f : 0.25f;
+            const int oh = orient ? len : 1, ow = orient ? 1 : len;
+            std::vector<int> expect;
+            if (len == 1) {
+                if ((mode_min ? -line[0] : line[0]) >= (mode_min ? -thr : thr)) expect.push_back(0);
+            } else {
+                expect = find_peaks_1d(line.data(), len, 1, mode_min ? -thr : thr, mode_min);
+            }
+            std::vector<mtm_hit> recs(1);
+            recs[0].templ_idx = -1;
+            line_map_peaks(line.data(), oh, ow, thr, mode_min, 3, 7, 9, recs);
+            CHECK(recs.size() == 1 + expect.size() && recs[0].templ_idx == -1);
+            for (size_t i = 0; i < expect.size(); ++i) {
+                const mtm_hit& r = recs[1 + i];
+                CHECK(r.templ_idx == 3 && r.w == 7 && r.h == 9 && r.x == (orient ? 0 : expect[i]) &&
+                      r.y == (orient ? expect[i] : 0) && std::memcmp(&r.score, &line[(size_t)expect[i]], 4) == 0);
+            }
+        }
+        // extremum keys: both encodings round-trip through a host restatement of mf_float_order (-0 -> +0)
+        {
+            auto float_order = [](float v) {
+                if (v == 0.0f) v = 0.0f;
+                uint32_t b;
+                std::memcpy(&b, &v, 4);
+                return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+            };
+            const float specials[] = {-0.0f, 0.0f, INFINITY, -INFINITY, 1e-40f, -3.5f};
+            const bool mode_min = (rep & 1) != 0;
+            const int ow = 1 + (int)(rng() % 500), oh = 1 + (int)(rng() % 500);
+            const uint32_t idx = (uint32_t)(rng() % ((uint32_t)ow * (uint32_t)oh));
+            const float v = rep % 3 == 0 ? specials[rep / 3 % 6] : (uf(rng) - 0.5f) * 1e3f;
+            const float vn = v + 0.0f;
+            // (a) extremum_kernel: the max key over the score, the min key over the complemented order
+            const uint32_t oa = mode_min ? ~float_order(v) : float_order(v);
+            const unsigned long long ka = ((unsigned long long)oa << 32) | (0xFFFFFFFFull - idx);
+            mtm_hit a = decode_extremum_key(ka, mode_min, 2, ow, 5, 6);
+            CHECK(a.templ_idx == 2 && a.w == 5 && a.h == 6 && a.x == (int)(idx % ow) && a.y == (int)(idx / ow) &&
+                  std::memcmp(&a.score, &vn, 4) == 0);
+            CHECK(order_to_float(float_order(v)) == v && std::signbit(order_to_float(float_order(v))) == std::signbit(vn));
+            a = decode_extremum_key(0ull, mode_min, 2, ow, 5, 6);
+            CHECK(a.x == 0 && a.y == 0 && a.score != a.score);
+            // (b) the window kernels: the key over the quality
+            const unsigned long long kb = ((unsigned long long)float_order(mode_min ? -v : v) << 32) | (0xFFFFFFFFull - idx);
+            mtm_hit b = decode_quality_key(kb, mode_min, 4, ow, 5, 6);
+            CHECK(b.templ_idx == 4 && b.x == (int)(idx % ow) && b.y == (int)(idx / ow) && std::memcmp(&b.score, &vn, 4) == 0);
+            b = decode_quality_key(0ull, mode_min, 4, ow, 5, 6);
+            CHECK(b.x == (int)(0xFFFFFFFFu % (uint32_t)ow) && b.y == (int)(0xFFFFFFFFu / (uint32_t)ow) && b.score != b.score);
+        }
+        // publish_hits / copy_out_hits below, at and above the number of hits
+        {
+            const int64_t cap = n == 0 ? (int64_t)(rng() % 2) : (int64_t)n - 1 + (int64_t)(rng() % 3);
+            std::vector<mtm_hit> res = hits, last(3), out((size_t)std::max<int64_t>(cap, 1));
+            int64_t n_out = -1;
+            const int rc = publish_hits(res, last, out.data(), cap, &n_out, "sanitize: too small");
+            CHECK(n_out == n && last.size() == hits.size() && res.size() == 3);
+            CHECK(last.empty() || std::memcmp(last.data(), hits.data(), sizeof(mtm_hit) * hits.size()) == 0);
+            if (n > cap) {
+                CHECK(rc == MTM_E_OVERFLOW && std::strcmp(mtm_last_error(), "sanitize: too small") == 0);
+            } else {
+                CHECK(rc == MTM_OK && (n == 0 || std::memcmp(out.data(), hits.data(), sizeof(mtm_hit) * (size_t)n) == 0));
+            }
+            std::vector<mtm_hit> all((size_t)std::max(n, 1));
+            CHECK(copy_out_hits(last, all.data(), n, &n_out, "unused") == MTM_OK && n_out == n);
+        }
         // template constants from pixels and from sums agree in size and do not read out of bounds
         const int th = 1 + (int)(rng() % 20), tw = 1 + (int)(rng() % 20), tc = 1 + (int)(rng() % 3);
         std::vector<double> px((size_t)th * tw * tc), mk((size_t)th * tw * tc);

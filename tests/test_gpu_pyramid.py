@@ -159,5 +159,15 @@ def test_abi_overflow_protocol_and_the_context_afterwards():
         rest = np.empty(n.value, dtype=_lib.HIT_DTYPE)
         assert ctx._lib.mtm_last_hits(ctx._h, rest.ctypes.data, n.value, ctypes.byref(n)) == 0
         assert rest.tobytes() == full.tobytes()
+        # a hit list smaller than the window pass's records: it runs once more with room for all of them, same result
+        dense = ctx.find_matches_pyramid(img, 2, _lib.PEAKS_LOCAL, 0.0, -1.0, 4, 64)
+        assert len(dense) > 16
+        old_cap = ctx.get_option(_lib.OPT_HIT_CAPACITY)
+        ctx.set_option(_lib.OPT_HIT_CAPACITY, 16)
+        try:
+            small = ctx.find_matches_pyramid(img, 2, _lib.PEAKS_LOCAL, 0.0, -1.0, 4, 64)
+        finally:
+            ctx.set_option(_lib.OPT_HIT_CAPACITY, old_cap)
+        assert small.tobytes() == dense.tobytes()
     after = MTM.matchTemplates(units, img, 5, score_threshold=0.2)
     assert _key(after) == _key(before)

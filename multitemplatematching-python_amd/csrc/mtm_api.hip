@@ -75,7 +75,7 @@ CallRoute plan_call(const mtm_ctx* c, int mode, float thr, bool banded) {
         bool ok = true;
         int max_oh = 0, max_nseg = 0;
         for (const SizeClass& sc : c->classes) {
-            ok = ok && resolved_kernel(c, sc) == MTM_KERNEL_MFMA && sc.slabs.empty();
+            ok = ok && sc.kernel == MTM_KERNEL_MFMA && sc.slabs.empty();
             max_oh = std::max(max_oh, c->rows - sc.h + 1);
             max_nseg = std::max(max_nseg, (c->cols - sc.w + 1 + kMfSeg - 1) / kMfSeg);
         }
@@ -90,8 +90,7 @@ CallRoute plan_call(const mtm_ctx* c, int mode, float thr, bool banded) {
         }
     }
     for (const SizeClass& sc : c->classes) {
-        const int rk = resolved_kernel(c, sc);
-        fused = fused && (rk == MTM_KERNEL_MFMA || rk == MTM_KERNEL_MFMA16 || rk == MTM_KERNEL_MFMA_F32);
+        fused = fused && (sc.kernel == MTM_KERNEL_MFMA || sc.kernel == MTM_KERNEL_MFMA16 || sc.kernel == MTM_KERNEL_MFMA_F32);
     }
     // float32 images on the bf16 matrix cores: the kernel's scores are a screen, the decisions are taken on exact
     // float64 scores (mtm_refine.hip.h).  Calls that mix bf16 classes with float64-kernel ones (float masks) run
@@ -99,7 +98,7 @@ CallRoute plan_call(const mtm_ctx* c, int mode, float thr, bool banded) {
     {
         bool any_bf16 = false, all_bf16 = n > 0;
         for (const SizeClass& sc : c->classes) {
-            const bool b = resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32;
+            const bool b = sc.kernel == MTM_KERNEL_MFMA_F32;
             any_bf16 = any_bf16 || b;
             all_bf16 = all_bf16 && b;
         }
@@ -125,9 +124,9 @@ CallRoute plan_call(const mtm_ctx* c, int mode, float thr, bool banded) {
     if (mode == MTM_PEAKS_GLOBAL && c->hits_only && n > 0 && (c->chans == 1 || c->chans == 3) && !R.f32_exact) {
         bool ok = true;
         for (const SizeClass& sc : c->classes)
-            ok = ok && ((resolved_kernel(c, sc) == MTM_KERNEL_MFMA &&
+            ok = ok && ((sc.kernel == MTM_KERNEL_MFMA &&
                          (!sc.masked || (c->exact_div < 2 && c->chans == 1 && c->method <= MTM_TM_CCORR_NORMED))) ||
-                        resolved_kernel(c, sc) == MTM_KERNEL_MFMA16 || resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32);
+                        sc.kernel == MTM_KERNEL_MFMA16 || sc.kernel == MTM_KERNEL_MFMA_F32);
         if (ok) {
             R.ext = R.cand_on = R.hits_only = true;
             R.cand_min = mode_min;
@@ -146,7 +145,7 @@ CallRoute plan_call(const mtm_ctx* c, int mode, float thr, bool banded) {
         R.rig_thr = tq;
         float eps = 0.0f;
         for (const SizeClass& sc : c->classes)
-            if (resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32) eps = std::max(eps, bf16_rig_eps(c->chans, sc.h, bf16_nkb(sc.w)));
+            if (sc.kernel == MTM_KERNEL_MFMA_F32) eps = std::max(eps, bf16_rig_eps(c->chans, sc.h, bf16_nkb(sc.w)));
         R.rig_cap = std::max(kRefineThrMargin, 4.0f * eps);
         R.scan_thr = tq - R.rig_cap * std::max(1.0f, std::fabs(tq));
     }
@@ -183,8 +182,7 @@ CallRoute plan_call(const mtm_ctx* c, int mode, float thr, bool banded) {
     if (R.prefetched) {
         bool pin = c->cand_pinned != 0 && !R.refine;
         for (const SizeClass& sc : c->classes) {
-            const int rk = resolved_kernel(c, sc);
-            pin = pin && ((rk == MTM_KERNEL_MFMA && sc.slabs.empty()) || rk == MTM_KERNEL_MFMA16);
+            pin = pin && ((sc.kernel == MTM_KERNEL_MFMA && sc.slabs.empty()) || sc.kernel == MTM_KERNEL_MFMA16);
         }
         R.cand_pin = pin;
         R.cand_pin_n = std::min<size_t>(kHitPrefetch, (size_t)R.cand_cap);
@@ -1022,7 +1020,7 @@ int mtm_score_map(mtm_ctx* c, int templ_idx, float* out, int64_t out_row_stride_
     // a map-mode route: no candidates, no extremum; float32 classes take the maps of the raw-sum methods from the float64
     // kernel (plan_call)
     CallRoute R;
-    R.f32_exact = resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32 &&
+    R.f32_exact = sc.kernel == MTM_KERNEL_MFMA_F32 &&
                   (c->method == MTM_TM_SQDIFF || c->method == MTM_TM_CCORR || c->method == MTM_TM_CCOEFF);
     MTMC(launch_stats(c, R, sc, &st));
     MTMC(launch_ncc(c, R, sc, sc.tlist_off + pos, 1, st, pos));

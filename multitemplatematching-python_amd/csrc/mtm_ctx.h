@@ -114,8 +114,7 @@ struct SizeClass {
     bool all_u8 = true;
     bool all_u16 = true;
     bool all_f32 = true;
-    bool bf16_ok = false;       // float32 class on the bf16 matrix cores (ncc_bf16_kernel)
-    bool mfma16_ok = false;     // uint16 class on the int8 MFMA path (byte-plane decomposition)
+    int kernel = MTM_KERNEL_AUTO;   // the kernel that runs the class, decided (and packed for) by place_templates
     int rm_nt = 0, rm_R = 0;    // > 0: row-multiplexed MFMA mode (<= 16 templates: nt x R = 16 A rows)
     int kp_nseg = 0;            // > 0: packed K (MfmaParams::kp_nseg): ceil(w / 16) segments per template row, 4 per MFMA step
     // large templates (w > 256 or w*h*C > 131071) on the MFMA kernel: cut into slabs (slab_combine_kernel)
@@ -135,7 +134,6 @@ struct SizeClass {
     long long tsum_off = -1;    // doubles: [sum(T_hi) per member][sum(T_lo) per member] in the tsum arena
     std::vector<int> members;
     int tlist_off = 0;          // offset into the device tlist array
-    bool mfma_ok = false;       // packed for ncc_mfma_kernel
     bool masked_int = false;    // masked class on the integer path: binary uint8 mask shared by all members
     unsigned long long mask_hash = 0;
     long long mask_pack_off = -1;   // dot4 pack of the mask bytes (0xFF / 0) in the pack arena (MTM_ROW_MUX=0 / MTM_FUSE_STATS=0 only)
@@ -551,7 +549,6 @@ int comm_allgather_hits_flagged(mtm_ctx* c, const mtm_hit* local, int64_t n_loca
 // ---- mtm_placement.hip
 int place_templates(mtm_ctx* c);
 // ---- mtm_launch.hip
-int resolved_kernel(const mtm_ctx* c, const SizeClass& sc);
 bool dot_variant_ok(int64_t v);
 int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out, int sb0 = 0, int sb1 = -1);
 int launch_ncc(mtm_ctx* c, CallRoute& R, const SizeClass& sc, int list_off, int n_list, const StatPlanes& st, int only_li = -1,

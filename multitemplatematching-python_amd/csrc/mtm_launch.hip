@@ -213,7 +213,7 @@ int ensure_square_planes(mtm_ctx* c) {
     if (c->sq_valid || c->dtype != MTM_U8 || c->chans != 1) return MTM_OK;
     bool any = false;
     for (const SizeClass& sc : c->classes)
-        any = any || (sc.masked && sc.mask_rm_off >= 0 && resolved_kernel(c, sc) == MTM_KERNEL_MFMA);
+        any = any || (sc.masked && sc.mask_rm_off >= 0 && sc.kernel == MTM_KERNEL_MFMA);
     if (!any) return MTM_OK;
     const ImageDev img = image_dev(c);
     const size_t plane_bytes = (size_t)img.u8_plane;
@@ -238,7 +238,7 @@ int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out,
     StatPlanes st{};
     st.pitch = (int)round_up((size_t)ow, 4);
     *out = st;
-    const int rk = resolved_kernel(c, sc);
+    const int rk = sc.kernel;
     const bool want_t_always = rk == MTM_KERNEL_MFMA || rk == MTM_KERNEL_MFMA16 || rk == MTM_KERNEL_MFMA_F32;
     const bool masked_mfma = sc.masked && rk == MTM_KERNEL_MFMA;
     if ((sc.masked && !masked_mfma) || (method == MTM_TM_CCORR && !want_t_always)) return MTM_OK;   // none needed
@@ -990,7 +990,7 @@ static int launch_f64(mtm_ctx* c, CallRoute& R, const SizeClass& sc, int kernel,
 // `yb0`, `yb1`: range of output row blocks (MFMA and bf16 kernels; banded image upload), yb1 < 0 = all.
 int launch_ncc(mtm_ctx* c, CallRoute& R, const SizeClass& sc, int list_off, int n_list, const StatPlanes& st, int only_li,
                int yb0, int yb1) {
-    const int kernel = resolved_kernel(c, sc);      // the same decision place_templates packed for
+    const int kernel = sc.kernel;
     const int* tl = c->tlist.as<int>() + list_off;
     // timing events around the dominant kernel
     // (The events are stream commands of their own.  Handing them to the launch itself - hipExtLaunchKernelGGL's start /
@@ -1018,23 +1018,6 @@ int launch_ncc(mtm_ctx* c, CallRoute& R, const SizeClass& sc, int list_off, int 
     if (!ev_own) HIPC(hipEventRecord(evp->second, c->stream));
     c->timing.ncc_launches++;
     return MTM_OK;
-}
-
-int resolved_kernel(const mtm_ctx* c, const SizeClass& sc) {
-    const bool dot_ok = c->dtype == MTM_U8 && sc.all_u8 && !sc.masked;
-    int kernel = c->opt_kernel;
-    if (c->dtype == MTM_F32) {
-        if ((kernel == MTM_KERNEL_AUTO || kernel == MTM_KERNEL_MFMA) && sc.bf16_ok) return MTM_KERNEL_MFMA_F32;
-        return kernel == MTM_KERNEL_NAIVE ? MTM_KERNEL_NAIVE : MTM_KERNEL_AUTO;
-    }
-    if (c->dtype == MTM_U16) {
-        if ((kernel == MTM_KERNEL_AUTO || kernel == MTM_KERNEL_MFMA) && sc.mfma16_ok) return MTM_KERNEL_MFMA16;
-        return kernel == MTM_KERNEL_NAIVE ? MTM_KERNEL_NAIVE : MTM_KERNEL_AUTO;
-    }
-    if (kernel == MTM_KERNEL_AUTO) kernel = c->auto_kernel;
-    if (kernel == MTM_KERNEL_MFMA && (!sc.mfma_ok || (sc.masked && c->method > 3))) kernel = MTM_KERNEL_DOT4;
-    if (kernel == MTM_KERNEL_DOT4 && !dot_ok) kernel = MTM_KERNEL_AUTO;
-    return kernel;
 }
 
 // side lanes 1 .. n of multi-class calls (mtm_ctx::Lane): a stream + its join event each
@@ -1138,8 +1121,7 @@ struct LaneScope {
 // Does anything class `sc` launches read the float32 plane of the image (the float64 / naive score kernels, the two-pass
 // statistics)?  A banded uint8 upload leaves that plane out (ensure_f32_plane rebuilds it on demand).
 static bool class_reads_f32(const mtm_ctx* c, const SizeClass& sc) {
-    const int rk = resolved_kernel(c, sc);
-    if (rk == MTM_KERNEL_NAIVE || rk == MTM_KERNEL_AUTO) return true;               // ncc_naive_kernel / ncc_f64_kernel
+    if (sc.kernel == MTM_KERNEL_NAIVE || sc.kernel == MTM_KERNEL_AUTO) return true;     // ncc_naive_kernel / ncc_f64_kernel
     if (c->dtype == MTM_U8) {
         const bool fused1 = c->chans == 1 && sc.w <= 768 && (double)sc.w * sc.h * 65025.0 < 4294967296.0 && c->fuse_stats;
         const bool fused3 = c->chans == 3 && sc.w <= 768 && 3.0 * sc.w * sc.h * 65025.0 < 4294967296.0 && c->fuse_stats;
@@ -1206,7 +1188,7 @@ static int run_score_classes(mtm_ctx* c, CallRoute& R, int skip, hipEvent_t fork
         // slabs: the raw launches read no statistics (slab_combine_kernel does) - their side streams fork HERE, ahead of
         // the statistics pass, which then runs under them (2048^2 x 414x400: hsum + vsum took 0.25 of the call's 1.16 ms)
         c->slab_fork_early = false;
-        if (!sc.slabs.empty() && resolved_kernel(c, sc) == MTM_KERNEL_MFMA) {
+        if (!sc.slabs.empty() && sc.kernel == MTM_KERNEL_MFMA) {
             if (!c->slab_fork) HIPC(hipEventCreateWithFlags(&c->slab_fork, hipEventDisableTiming));
             HIPC(hipEventRecord(c->slab_fork, c->stream));
             c->slab_fork_early = true;
@@ -1215,7 +1197,7 @@ static int run_score_classes(mtm_ctx* c, CallRoute& R, int skip, hipEvent_t fork
         const int rc_ncc = rc_st == MTM_OK ? launch_ncc(c, R, sc, sc.tlist_off, (int)sc.members.size(), st) : rc_st;
         c->slab_fork_early = false;
         MTMC(rc_ncc);
-        if (R.refine && resolved_kernel(c, sc) == MTM_KERNEL_MFMA_F32) MTMC(launch_refine_class(c, R, sc, st));
+        if (R.refine && sc.kernel == MTM_KERNEL_MFMA_F32) MTMC(launch_refine_class(c, R, sc, st));
     }
     for (int i = 0; i + 1 < n_lanes; ++i) {             // join: everything after the score pass is queued on c->stream
         HIPC(hipEventRecord(c->lanes[(size_t)i].done, c->lanes[(size_t)i].stream));
@@ -1302,7 +1284,7 @@ static bool class_bandable(const mtm_ctx* c, const ImageArgs& a, const SizeClass
         // Round 6: single-channel float32 images whose one size class runs the bf16 kernel - 33 MB cross PCIe at 4K, 0.7 ms
         // next to a 1.9 ms score launch since the one-product screen; two bands, the second under the first's score launch
         if (any_fill || c->upload_bands.size() < 2 || a.chans != 1 || c->classes.size() != 1 || sc.masked || sc.w > 1024 ||
-            resolved_kernel(c, sc) != MTM_KERNEL_MFMA_F32)
+            sc.kernel != MTM_KERNEL_MFMA_F32)
             return false;
         const int oh = a.rows - sc.h + 1;
         if (!((size_t)a.rows * a.cols >= ((size_t)1 << 20) && oh >= 8 * kVsumBand)) return false;
@@ -1310,7 +1292,7 @@ static bool class_bandable(const mtm_ctx* c, const ImageArgs& a, const SizeClass
         return true;
     }
     if (c->upload_bands.size() < 2 || (a.dtype != MTM_U8 && !u16) || a.chans != 1) return false;
-    if (sc.masked || !c->fuse_stats || !sc.slabs.empty() || resolved_kernel(c, sc) != (u16 ? MTM_KERNEL_MFMA16 : MTM_KERNEL_MFMA))
+    if (sc.masked || !c->fuse_stats || !sc.slabs.empty() || sc.kernel != (u16 ? MTM_KERNEL_MFMA16 : MTM_KERNEL_MFMA))
         return false;
     if (!(sc.w <= 768 && (double)sc.w * sc.h * (u16 ? 65535.0 : 65025.0) < 4294967296.0)) return false;   // the fused statistics
     if (!any_fill && !((size_t)a.rows * a.cols >= ((size_t)1 << 20) && a.rows - sc.h + 1 >= 256)) return false;

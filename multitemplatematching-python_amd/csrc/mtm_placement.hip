@@ -119,11 +119,11 @@ void pack_mask_rm(const mtm_ctx* c, const SizeClass& sc, uint8_t* out) {
         }
 }
 
-void pack_class_rm(const mtm_ctx* c, const SizeClass& sc, uint8_t* out) {
+void pack_class_rm(const mtm_ctx* c, const SizeClass& sc, uint8_t* out, size_t bytes) {
     const int h = sc.h, w = sc.w, nb = (w + 63) / 64, R = sc.rm_R, nt = sc.rm_nt, nseg = sc.kp_nseg;
     const int chans = sc.masked ? 1 : c->chans;                 // one pack per channel, class_rm_pack_bytes apart
     const size_t cstride = (size_t)class_rm_pack_bytes(sc);
-    std::memset(out, 0, cstride * chans);
+    std::memset(out, 0, bytes);
     if (nseg) {                                  // packed K: [ch][group g][step][lane][16], stream row r: dy = r - g R - rho
         const size_t gbytes = cstride / 2;
         for (int ch = 0; ch < chans; ++ch)
@@ -186,17 +186,37 @@ bool masked_bf16_class_ok(const mtm_ctx* c, const SizeClass& sc) {
            c->rows > sc.h && c->cols > sc.w && (c->method == MTM_TM_SQDIFF || c->method == MTM_TM_CCORR_NORMED);
 }
 
+// The kernel that runs a class, recorded by placement in SizeClass::kernel.  Everything it reads re-places when it changes:
+// opt_kernel and f32_mfma (mtm_set_option, which bf16_class_ok only tests for non-zero), dtype and the image dimensions
+// (adopt_image), method (a new template set); auto_kernel is fixed at construction.
+int resolved_kernel(const mtm_ctx* c, const SizeClass& sc) {
+    const bool dot_ok = c->dtype == MTM_U8 && sc.all_u8 && !sc.masked;
+    int kernel = c->opt_kernel;
+    if (c->dtype == MTM_F32) {
+        if ((kernel == MTM_KERNEL_AUTO || kernel == MTM_KERNEL_MFMA) && bf16_class_ok(c, sc)) return MTM_KERNEL_MFMA_F32;
+        return kernel == MTM_KERNEL_NAIVE ? MTM_KERNEL_NAIVE : MTM_KERNEL_AUTO;
+    }
+    if (c->dtype == MTM_U16) {
+        if ((kernel == MTM_KERNEL_AUTO || kernel == MTM_KERNEL_MFMA) && mfma16_class_ok(c, sc)) return MTM_KERNEL_MFMA16;
+        return kernel == MTM_KERNEL_NAIVE ? MTM_KERNEL_NAIVE : MTM_KERNEL_AUTO;
+    }
+    if (kernel == MTM_KERNEL_AUTO) kernel = c->auto_kernel;
+    if (kernel == MTM_KERNEL_MFMA && (!mfma_class_ok(c, sc) || (sc.masked && c->method > 3))) kernel = MTM_KERNEL_DOT4;
+    if (kernel == MTM_KERNEL_DOT4 && !dot_ok) kernel = MTM_KERNEL_AUTO;
+    return kernel;
+}
+
 // A packs of a float32 class for ncc_bf16_kernel: [piece 0 | piece 1][group of 16][ch][dy][32-tap block][lane = 16 q + i]
 // [8 bf16]: lane (i, q) holds taps 32 kb + 8 q .. + 7 of template i, centred by its channel mean and split
 // v = v0 + v1 (bfloat16, round to nearest even).  centre[] receives the means (TemplDev::centre).
 // `which`: 0 = the template's pixels; 1 = U = T M^2, 2 = V = M^2 (masked classes, single channel: mtm_maskf32.hip.h) - then
 // td_host is the U / V copy of the table: centre and centred_sum2 of the packed values go there
-void pack_class_bf16(const mtm_ctx* c, const SizeClass& sc, uint8_t* out, std::vector<TemplDev>& td_host, int which = 0) {
+// `gb`: bytes per group of 16 templates, `bytes`: of both pieces.
+void pack_class_bf16(const mtm_ctx* c, const SizeClass& sc, uint8_t* out, long long gb, size_t bytes,
+                     std::vector<TemplDev>& td_host, int which) {
     const int h = sc.h, w = sc.w, nkb = bf16_nkb(w), chans = c->chans;
-    const long long gb = bf16_group_bytes(h, w, chans);
-    const int groups = mfma_groups_alloc((int)sc.members.size());
-    const long long piece = gb * groups;
-    std::memset(out, 0, (size_t)(2 * piece));
+    const size_t piece = bytes / 2;
+    std::memset(out, 0, bytes);
     auto rne = [](float v) {
         uint32_t b;
         std::memcpy(&b, &v, 4);
@@ -239,10 +259,10 @@ void pack_class_bf16(const mtm_ctx* c, const SizeClass& sc, uint8_t* out, std::v
 // [low bytes of the same members] - one work item of ncc_mfma_kernel (32 pseudo-templates) holds both byte planes of
 // 16 templates.  Same lane order as pack_class_mfma.  Also the byte sums of every member (bias terms of the
 // combination): tsum[li] high bytes, tsum[n_pad + li] low bytes.
-void pack_class_mfma16(const mtm_ctx* c, const SizeClass& sc, uint8_t* out, double* tsum) {
+void pack_class_mfma16(const mtm_ctx* c, const SizeClass& sc, uint8_t* out, size_t bytes, double* tsum) {
     const int h = sc.h, w = sc.w, nb = (w + 63) / 64, n_pad = sc.n_pad, nseg = sc.kp_nseg;
     const long long gb = sc.group_bytes;
-    std::memset(out, 0, (size_t)gb * (2 * n_pad / 16));
+    std::memset(out, 0, bytes);
     for (int k = 0; k < 2 * n_pad; ++k) tsum[k] = 0.0;
     for (size_t li = 0; li < sc.members.size(); ++li) {
         const HostTempl& t = c->templs[sc.members[li]];
@@ -268,11 +288,11 @@ void pack_class_mfma16(const mtm_ctx* c, const SizeClass& sc, uint8_t* out, doub
     }
 }
 
-void pack_class_mfma(const mtm_ctx* c, const SizeClass& sc, uint8_t* out) {
+void pack_class_mfma(const mtm_ctx* c, const SizeClass& sc, uint8_t* out, size_t bytes) {
     const int h = sc.h, w = sc.w, nb = (w + 63) / 64, chans = c->chans, nseg = sc.kp_nseg;
     // multi-row variant: groups of h + r2 - 1 rows (one channel), the extra rows stay zero; packed K: kp_blocks steps per channel
-    const long long gb = (sc.r2 || nseg) ? sc.group_bytes : mfma_group_bytes(h, w, chans);
-    std::memset(out, 0, (size_t)gb * (sc.r2 ? ((int)sc.members.size() + 15) / 16 : mfma_groups_alloc((int)sc.members.size())));
+    const long long gb = sc.group_bytes;
+    std::memset(out, 0, bytes);
     for (size_t li = 0; li < sc.members.size(); ++li) {
         const HostTempl& t = c->templs[sc.members[li]];
         uint8_t* g = out + (li / 16) * gb;
@@ -395,6 +415,354 @@ int pack_class_on_device(mtm_ctx* c, const SizeClass& sc) {
     return MTM_OK;
 }
 
+// Regions of one arena, handed out back to back
+struct Bump {
+    size_t size = 0;
+    long long take(size_t n) {
+        size += n;
+        return (long long)(size - n);
+    }
+};
+
+// What place_templates derives from the context before any HIP call: each class's kernel and tiling, the arenas' layout,
+// the per-template constants, the template lists and slab views, and which operands the host packs.
+struct Placement {
+    std::vector<SizeClass> classes;
+    std::vector<char> dev_pack;     // per class: A packs gathered on the device (pack_class_on_device)
+    std::vector<size_t> a_bytes;    // per class: bytes of its host-packed A packs (masked bf16: of each of its U and V packs)
+    std::vector<int> host_px;       // device-resident templates whose pixels the host packers read
+    std::vector<TemplDev> td, td_u, td_v;
+    std::vector<int> tlist, list2d;
+    int list2d_off = 0;
+    std::vector<UnitSrc> units;     // the unit table, slab views appended
+    Bump maps, w, p, a, ts;         // floats of the score maps; float64 weights; dot4 packs; A packs; uint16 tsums
+    bool any_host_pack = false, any_mbf = false;
+};
+
+// The tiling of a class on the int8 MFMA kernel - uint8: row-multiplexed, slabs, two-row or packed K; uint16: packed K.
+void choose_tiling(const mtm_ctx* c, SizeClass& sc) {
+    const int n_cls = (int)sc.members.size(), nseg = (sc.w + 15) / 16;
+    sc.rm_nt = sc.rm_R = sc.slab_nt = sc.slab_R = sc.r2 = sc.kp_nseg = 0;
+    sc.slabs.clear();
+    // packed K for the two byte-plane passes (widths that are not multiples of 64), as for uint8 classes
+    if (sc.kernel == MTM_KERNEL_MFMA16) sc.kp_nseg = nseg % 4 != 0 ? nseg : 0;
+    if (sc.kernel != MTM_KERNEL_MFMA) return;
+    if (sc.w > kMfmaMaxW || (long long)c->chans * sc.w * sc.h > 131071) {
+        sc.slabs = slab_layout(c, sc);
+        if (n_cls <= 16) {                     // row-multiplexed raw launches: nt templates x R rows per MFMA group
+            int hs = 0, ws = 0;
+            for (const auto& sl : sc.slabs) {
+                hs = std::max(hs, sl.r1 - sl.r0);
+                ws = std::max(ws, sl.c1 - sl.c0);
+            }
+            sc.slab_nt = rm_group_templates(n_cls, hs, ws);
+            sc.slab_R = 16 / sc.slab_nt;
+        }
+        return;
+    }
+    const bool one_pack = c->chans == 1 || (c->chans == 3 && !sc.masked);
+    // row-multiplexed mode: <= 16 templates (one channel, masked or not, or unmasked RGB) whose window statistics the fused
+    // kernels produce (the single-channel one also writes the 1/sqrt plane); wide templates take fewer rows per MFMA group
+    if (c->row_mux && n_cls <= 16 && c->fuse_stats && one_pack && (double)c->chans * sc.w * sc.h * 65025.0 < 4294967296.0) {
+        sc.rm_nt = rm_group_templates(n_cls, sc.h, sc.w);
+        sc.rm_R = 16 / sc.rm_nt;
+    }
+    // packed K: widths that leave part of the last 64-tap block empty, on the normalised methods (the instantiated variants
+    // ncc_mfma_kernel<.., KP>).  Replaces the two-row variant where both apply (that one saves template loads, this one
+    // whole MFMA steps).
+    const bool normed = c->method == MTM_TM_SQDIFF_NORMED || c->method == MTM_TM_CCORR_NORMED ||
+                        c->method == MTM_TM_CCOEFF_NORMED;
+    if (nseg % 4 != 0 && normed && one_pack && (!sc.masked || c->method != MTM_TM_CCOEFF_NORMED))
+        sc.kp_nseg = nseg;
+    else if (c->mfma_r2 && sc.rm_R == 0 && n_cls > 16 && sc.w <= 64 && c->chans == 1 && !sc.masked &&
+             c->method >= MTM_TM_CCORR && c->fuse_stats)
+        sc.r2 = 2;
+}
+
+// A class's regions of the A arena (uint16: and of the tsum arena); returns the bytes of its A packs.  Fields of the
+// families a class is not in keep their values.
+size_t place_apacks(const mtm_ctx* c, SizeClass& sc, Bump& a, Bump& ts) {
+    const int n_cls = (int)sc.members.size(), groups = mfma_groups_alloc(n_cls);
+    size_t bytes = 0;
+    switch (sc.kernel) {
+        case MTM_KERNEL_MFMA:
+            sc.mask_rm_off = -1;
+            if (sc.masked && c->row_mux && c->fuse_stats) {
+                sc.mask_rm_off = a.take((size_t)rm_pack_bytes(sc.h, sc.w, 16));
+                const HostTempl& m0 = c->templs[sc.members[0]];
+                sc.mask_ones = m0.on_device ? m0.mask_ones : 0.0;
+                if (!m0.on_device)
+                    for (double m : m0.mask) sc.mask_ones += m > 0.0 ? 1.0 : 0.0;
+            }
+            if (!sc.slabs.empty()) {          // one pack per slab (a template of its own, one channel)
+                sc.apack_off = (long long)a.size;
+                for (auto& sl : sc.slabs) {
+                    const int hs = sl.r1 - sl.r0, ws = sl.c1 - sl.c0;
+                    sl.apack_off = a.take(sc.slab_R > 0 ? (size_t)rm_pack_bytes(hs, ws, sc.slab_R)
+                                                        : (size_t)mfma_group_bytes(hs, ws, 1) * groups);
+                }
+                return 0;
+            }
+            if (sc.rm_R > 0) {
+                sc.group_bytes = sc.kp_nseg ? class_rm_pack_bytes(sc) / 2          // packed K: a pack per MFMA group
+                                            : -(long long)sc.rm_R * ((sc.w + 63) / 64) * 1024;
+                bytes = (size_t)class_rm_pack_bytes(sc) * (sc.masked ? 1 : c->chans);
+            } else if (sc.r2) {
+                sc.group_bytes = mfma_group_bytes(sc.h + sc.r2 - 1, sc.w, 1);        // h + r2 - 1 rows, the extra ones zero
+                bytes = (size_t)sc.group_bytes * ((n_cls + 15) / 16);
+            } else {
+                sc.group_bytes = sc.kp_nseg ? (long long)c->chans * kp_blocks(sc.h, sc.kp_nseg) * 1024
+                                            : mfma_group_bytes(sc.h, sc.w, c->chans);
+                bytes = (size_t)sc.group_bytes * groups;
+            }
+            break;
+        case MTM_KERNEL_MFMA_F32:
+            sc.group_bytes = bf16_group_bytes(sc.h, sc.w, c->chans);
+            bytes = (size_t)(2 * sc.group_bytes * groups);
+            break;
+        case MTM_KERNEL_MFMA16:
+            sc.group_bytes = sc.kp_nseg ? (long long)kp_blocks(sc.h, sc.kp_nseg) * 1024 : mfma_group_bytes(sc.h, sc.w, 1);
+            bytes = (size_t)sc.group_bytes * (2 * sc.n_pad / 16);
+            sc.tsum_off = ts.take(2 * (size_t)sc.n_pad);
+            break;
+        default:                              // masked float32 classes on the bf16 screen: the U and V packs
+            if (!sc.mask_bf16) return 0;
+            sc.mbf_group_bytes = bf16_group_bytes(sc.h, sc.w, 1);
+            bytes = (size_t)(2 * sc.mbf_group_bytes * groups);
+            sc.mbf_off_u = a.take(bytes);
+            sc.mbf_off_v = a.take(bytes);
+            return bytes;
+    }
+    sc.apack_off = a.take(bytes);
+    return bytes;
+}
+
+// The layout of a placement (no HIP call, no change to the context).  Errors: a template that does not fit the image.
+int plan_placement(const mtm_ctx* c, Placement& P) {
+    const int n = (int)c->templs.size();
+    P.classes = c->classes;
+    for (SizeClass& sc : P.classes) {
+        sc.kernel = resolved_kernel(c, sc);
+        sc.n_pad = (int)round_up(sc.members.size(), 16);
+        choose_tiling(c, sc);
+        sc.masked_int = sc.masked && sc.kernel == MTM_KERNEL_MFMA;
+        sc.mask_bf16 = sc.kernel == MTM_KERNEL_AUTO && masked_bf16_class_ok(c, sc);      // (AUTO: the float64 kernel)
+        sc.mbf_off_u = sc.mbf_off_v = sc.tsum_off = -1;
+    }
+    P.td.assign((size_t)n, TemplDev{});
+    for (int i = 0; i < n; ++i) {
+        const HostTempl& t = c->templs[i];
+        const int kern = P.classes[(size_t)t.cls].kernel;
+        if (t.chans != c->chans) {
+            set_error("template " + std::to_string(i) + " has a different channel count than the image");
+            return MTM_E_INVALID;
+        }
+        if (t.rows > c->rows || t.cols > c->cols) {
+            set_error("template " + std::to_string(i) + " is larger than the image");
+            return MTM_E_INVALID;
+        }
+        TemplDev& d = P.td[i];
+        for (int k = 0; k < kMaxChans; ++k) d.mean[k] = t.st.mean[k];
+        d.templ_norm = t.st.templ_norm;
+        d.templ_sum2 = t.st.templ_sum2;
+        d.centred_sum2 = t.st.centred_sum2;
+        d.templ2_mask2_sum = t.st.templ2_mask2_sum;
+        d.all_ones = t.st.all_ones;
+        double sum_t = t.sum_t;  // exact: integers
+        if (t.dtype == MTM_U8 && !t.on_device)
+            for (size_t k = 0; k < t.px.size(); ++k) sum_t += t.masked ? t.px[k] * t.mask[k] : t.px[k];
+        d.mfma_k = 128.0 * sum_t - 16384.0 * (double)t.rows * (double)t.cols * (double)t.chans;
+        d.rows = t.rows;
+        d.cols = t.cols;
+        d.cls = t.cls;
+        d.oh = c->rows - t.rows + 1;
+        d.ow = c->cols - t.cols + 1;
+        d.map_pitch = (int)round_up((size_t)d.ow, 4);
+        d.map_off = P.maps.take((size_t)d.map_pitch * d.oh);
+        // float64 weights: the float64 / naive kernels, and the exact re-scoring behind the bf16 kernel
+        const size_t plane = (size_t)t.chans * t.rows * t.cols;
+        const bool want_f64 = kern == MTM_KERNEL_AUTO || kern == MTM_KERNEL_NAIVE || kern == MTM_KERNEL_MFMA_F32;
+        d.k1_off = want_f64 ? P.w.take(plane) : -1;
+        d.k2_off = want_f64 && t.masked ? P.w.take(plane) : -1;
+        const bool dot4 = kern == MTM_KERNEL_DOT4 && c->dtype == MTM_U8 && t.dtype == MTM_U8 && !t.masked;
+        d.pack_off = dot4 ? P.p.take(dot_pack_bytes(t.rows, t.cols, t.chans)) : -1;
+    }
+    // masked classes on the integer path: one dot4 pack of the (shared, binary) mask bytes per class - the dot4 route of
+    // sum I^2 M (otherwise: matrix cores)
+    for (SizeClass& sc : P.classes)
+        sc.mask_pack_off = sc.masked_int && !(c->row_mux && c->fuse_stats) ? P.p.take(dot_pack_bytes(sc.h, sc.w, 1)) : -1;
+    // the A arena by family: int8 MFMA, bf16, masked bf16 (U / V), uint16
+    P.a_bytes.assign(P.classes.size(), 0);
+    for (int fam : {MTM_KERNEL_MFMA, MTM_KERNEL_MFMA_F32, MTM_KERNEL_AUTO, MTM_KERNEL_MFMA16})
+        for (size_t k = 0; k < P.classes.size(); ++k)
+            if (P.classes[k].kernel == fam) P.a_bytes[k] = place_apacks(c, P.classes[k], P.a, P.ts);
+    // classes whose members all live on the device are packed there (after the uploads); the host packs the rest, and
+    // reads the pixels of device-resident templates whose kernel (or class mask pack) is host-packed
+    P.dev_pack.assign(P.classes.size(), 0);
+    for (size_t k = 0; k < P.classes.size(); ++k) {
+        const SizeClass& sc = P.classes[k];
+        bool all_dev = sc.kernel == MTM_KERNEL_MFMA;
+        for (int m : sc.members) all_dev = all_dev && c->templs[(size_t)m].on_device;
+        P.dev_pack[k] = all_dev ? 1 : 0;
+        P.any_host_pack = P.any_host_pack || (!all_dev && (sc.kernel == MTM_KERNEL_MFMA || sc.kernel == MTM_KERNEL_MFMA16 ||
+                                                           sc.kernel == MTM_KERNEL_MFMA_F32));
+        P.any_mbf = P.any_mbf || sc.mask_bf16;
+    }
+    P.any_host_pack = P.any_host_pack || P.any_mbf;
+    for (int i = 0; i < n; ++i) {
+        const SizeClass& sc = P.classes[(size_t)c->templs[i].cls];
+        if (c->templs[i].on_device && !(P.dev_pack[(size_t)c->templs[i].cls] && sc.mask_pack_off < 0)) P.host_px.push_back(i);
+    }
+    // masked float32 classes: copies of the template table for the U = T M^2 / V = M^2 packs (centre, centred energy, and
+    // where the approximate c1 / c2 maps go: the real maps' layout, twice, in a scratch arena of their own)
+    if (P.any_mbf) {
+        P.td_u = P.td_v = P.td;
+        for (const SizeClass& sc : P.classes) {
+            if (!sc.mask_bf16) continue;
+            for (int m : sc.members) {
+                P.td_u[(size_t)m].all_ones = P.td_v[(size_t)m].all_ones = 0;
+                P.td_v[(size_t)m].map_off += (long long)P.maps.size;       // second half of the scratch arena
+            }
+        }
+    }
+    // template lists: one per class, then the list of templates with a 2-D score map
+    for (SizeClass& sc : P.classes) {
+        sc.tlist_off = (int)P.tlist.size();
+        P.tlist.insert(P.tlist.end(), sc.members.begin(), sc.members.end());
+    }
+    for (int i = 0; i < n; ++i)
+        if (P.td[i].oh > 1 && P.td[i].ow > 1) P.list2d.push_back(i);
+    P.list2d_off = (int)P.tlist.size();
+    P.tlist.insert(P.tlist.end(), P.list2d.begin(), P.list2d.end());
+    // slab views: windows into the units of a large-template class, appended to the unit table (a view of a view:
+    // the offsets move, the orientation stays)
+    P.units.assign(c->usrc_host.begin(), c->usrc_host.begin() + (long)std::min(c->usrc_units, c->usrc_host.size()));
+    for (SizeClass& sc : P.classes)
+        for (auto& sl : sc.slabs) {
+            sl.tlist_off = (int)P.tlist.size();
+            for (int m : sc.members) {
+                UnitSrc v = c->templs[(size_t)m].src;
+                v.off += (long long)sl.ch * v.sh * v.sw;
+                v.moff = -1;
+                v.cy += v.ay * sl.r0 + v.by * sl.c0;
+                v.cx += v.ax * sl.r0 + v.bx * sl.c0;
+                v.h = sl.r1 - sl.r0;
+                v.w = sl.c1 - sl.c0;
+                v.chans = 1;
+                P.tlist.push_back((int)P.units.size());
+                P.units.push_back(v);
+            }
+        }
+    return MTM_OK;
+}
+
+// The host-packed operands of a plan; the centres of the bf16 packs go to the plan's template tables.
+struct HostArenas {
+    std::vector<double> wts, tsums;
+    std::vector<uint8_t> packs, apacks;
+};
+void pack_on_host(const mtm_ctx* c, Placement& P, HostArenas& H) {
+    H.wts.resize(P.w.size);
+    H.packs.resize(P.p.size);
+    H.apacks.resize(P.any_host_pack ? P.a.size : 0);
+    H.tsums.resize(P.ts.size);
+    uint8_t* a = H.apacks.data();
+    for (size_t i = 0; i < P.td.size(); ++i) {
+        const HostTempl& t = c->templs[i];
+        const TemplDev& d = P.td[i];
+        if (d.k1_off >= 0 && t.masked) {        // weights (float64): K1 = T (or T*M^2), K2 = M^2
+            for (size_t k = 0; k < t.px.size(); ++k) {
+                const double m2 = t.mask[k] * t.mask[k];
+                H.wts[d.k1_off + k] = t.px[k] * m2;
+                H.wts[d.k2_off + k] = m2;
+            }
+        } else if (d.k1_off >= 0) {
+            std::copy(t.px.begin(), t.px.end(), H.wts.begin() + d.k1_off);
+        }
+        if (d.pack_off >= 0) pack_template_dot4(t, H.packs.data() + d.pack_off);
+    }
+    for (size_t k = 0; k < P.classes.size(); ++k) {
+        const SizeClass& sc = P.classes[k];
+        if (sc.mask_pack_off >= 0) {
+            HostTempl mk = c->templs[sc.members[0]];
+            for (size_t q = 0; q < mk.px.size(); ++q) mk.px[q] = mk.mask[q] > 0.0 ? 255.0 : 0.0;
+            pack_template_dot4(mk, H.packs.data() + sc.mask_pack_off);
+        }
+        if (sc.mask_bf16) {
+            pack_class_bf16(c, sc, a + sc.mbf_off_u, sc.mbf_group_bytes, P.a_bytes[k], P.td_u, 1);
+            pack_class_bf16(c, sc, a + sc.mbf_off_v, sc.mbf_group_bytes, P.a_bytes[k], P.td_v, 2);
+        }
+        if (P.dev_pack[k]) continue;
+        if (sc.kernel == MTM_KERNEL_MFMA && sc.mask_rm_off >= 0) pack_mask_rm(c, sc, a + sc.mask_rm_off);
+        if (sc.kernel == MTM_KERNEL_MFMA && sc.rm_R > 0)
+            pack_class_rm(c, sc, a + sc.apack_off, P.a_bytes[k]);
+        else if (sc.kernel == MTM_KERNEL_MFMA)
+            pack_class_mfma(c, sc, a + sc.apack_off, P.a_bytes[k]);
+        if (sc.kernel == MTM_KERNEL_MFMA16) pack_class_mfma16(c, sc, a + sc.apack_off, P.a_bytes[k], H.tsums.data() + sc.tsum_off);
+        if (sc.kernel == MTM_KERNEL_MFMA_F32) pack_class_bf16(c, sc, a + sc.apack_off, sc.group_bytes, P.a_bytes[k], P.td, 0);
+    }
+}
+
+// Uploads a plan and its host-packed operands, packs the device-packed classes and hands the tables to the context.
+int upload_placement(mtm_ctx* c, Placement& P, HostArenas& H) {
+    // From here on copies from P's and H's vectors are in flight: an error return drains the stream before they go out of
+    // scope (the normal path hands the long-lived ones to the context and says so in place_pending).
+    struct DrainGuard {
+        hipStream_t s;
+        bool armed = true;
+        ~DrainGuard() {
+            if (armed) (void)hipStreamSynchronize(s);
+        }
+    } drain{c->stream};
+    const size_t n = P.td.size(), a_off = P.a.size, w_off = P.w.size, p_off = P.p.size, ts_off = P.ts.size;
+    const bool new_units = P.units.size() > c->usrc_units;
+    if (new_units) {
+        MTMC(c->usrc_dev.ensure(sizeof(UnitSrc) * P.units.size()));
+        HIPC(hipMemcpyAsync(c->usrc_dev.p, P.units.data(), sizeof(UnitSrc) * P.units.size(), hipMemcpyHostToDevice, c->stream));
+    }
+    MTMC(c->td.ensure(sizeof(TemplDev) * n));
+    MTMC(c->tlist.ensure(sizeof(int) * std::max<size_t>(1, P.tlist.size())));
+    MTMC(c->weights.ensure(sizeof(double) * std::max<size_t>(1, w_off)));
+    MTMC(c->packs.ensure(std::max<size_t>(4, p_off)));
+    MTMC(c->apacks.ensure(std::max<size_t>(16, a_off) + 16384));     // the K loop requests up to two steps past a pack
+    // host-packed classes (device-packed regions of the same arena are written afterwards, in stream order, by
+    // pack_units_kernel below)
+    if (a_off && P.any_host_pack) HIPC(hipMemcpyAsync(c->apacks.p, H.apacks.data(), a_off, hipMemcpyHostToDevice, c->stream));
+    // the score-map arena (4 bytes per pixel and template) is only allocated when something writes maps:
+    // mtm_find_matches in hits-only mode never does (ensure_maps, called by the launch paths)
+    HIPC(hipMemcpyAsync(c->td.p, P.td.data(), sizeof(TemplDev) * n, hipMemcpyHostToDevice, c->stream));
+    if (!P.tlist.empty())
+        HIPC(hipMemcpyAsync(c->tlist.p, P.tlist.data(), sizeof(int) * P.tlist.size(), hipMemcpyHostToDevice, c->stream));
+    if (w_off) HIPC(hipMemcpyAsync(c->weights.p, H.wts.data(), sizeof(double) * w_off, hipMemcpyHostToDevice, c->stream));
+    if (p_off) HIPC(hipMemcpyAsync(c->packs.p, H.packs.data(), p_off, hipMemcpyHostToDevice, c->stream));
+    if (P.any_mbf) {
+        MTMC(c->td_u.ensure(sizeof(TemplDev) * n));
+        MTMC(c->td_v.ensure(sizeof(TemplDev) * n));
+        HIPC(hipMemcpyAsync(c->td_u.p, P.td_u.data(), sizeof(TemplDev) * n, hipMemcpyHostToDevice, c->stream));
+        HIPC(hipMemcpyAsync(c->td_v.p, P.td_v.data(), sizeof(TemplDev) * n, hipMemcpyHostToDevice, c->stream));
+    }
+    MTMC(c->tsum.ensure(sizeof(double) * std::max<size_t>(2, ts_off)));
+    if (ts_off) HIPC(hipMemcpyAsync(c->tsum.p, H.tsums.data(), sizeof(double) * ts_off, hipMemcpyHostToDevice, c->stream));
+    // device-side packing: gathers the A operands straight from the unit views (the template list is in place)
+    for (size_t k = 0; k < P.classes.size(); ++k)
+        if (P.dev_pack[k]) MTMC(pack_class_on_device(c, P.classes[k]));
+    // host staging vectors go out of scope; the tables that stay in the context (td, tlist) need no wait
+    // (set_templates_device)
+    const bool local_sources = P.any_host_pack || P.any_mbf || w_off || p_off || ts_off || new_units;
+    if (local_sources) HIPC(hipStreamSynchronize(c->stream));
+    c->place_pending = !local_sources;
+    drain.armed = false;
+    if (new_units) c->usrc_host.swap(P.units);
+    c->classes.swap(P.classes);
+    c->td_host.swap(P.td);
+    c->tlist_host.swap(P.tlist);
+    c->list2d.swap(P.list2d);
+    c->list2d_off = P.list2d_off;
+    c->maps_floats = P.maps.size;
+    c->placed = true;
+    return MTM_OK;
+}
+
 }  // namespace
 
 namespace mtmi {
@@ -409,369 +777,14 @@ int place_templates(mtm_ctx* c) {
         HIPC(hipStreamSynchronize(c->stream));
         c->place_pending = false;
     }
-    const int n = (int)c->templs.size();
-    // Everything is derived into locals and committed at the end: a failure half-way (an allocation, a copy)
-    // leaves the context exactly as it was - templates set, not placed.
-    std::vector<SizeClass> classes = c->classes;
-    std::vector<TemplDev> td_host((size_t)n, TemplDev{});
-    std::vector<int> tlist_host, list2d;
-    size_t map_off = 0, w_off = 0, p_off = 0;
-    const bool img_u8 = c->dtype == MTM_U8;
-    // Which kernel will run each class decides what has to be packed: int8 A-packs for the MFMA kernel,
-    // dot4 packs for the VALU kernel, float64 weights for the float64 / naive kernels.  (Changing
-    // MTM_OPT_KERNEL re-places.)
-    std::vector<int> class_kernel(classes.size(), MTM_KERNEL_AUTO);
-    for (size_t k = 0; k < classes.size(); ++k) {
-        classes[k].mfma_ok = mfma_class_ok(c, classes[k]);
-        classes[k].mfma16_ok = mfma16_class_ok(c, classes[k]);
-        classes[k].bf16_ok = bf16_class_ok(c, classes[k]);
-        classes[k].n_pad = (int)round_up(classes[k].members.size(), 16);
-        class_kernel[k] = resolved_kernel(c, classes[k]);
-        // row-multiplexed mode: uint8 class of <= 16 templates (one channel, masked or not, or unmasked RGB) whose
-        // window statistics the fused kernels produce (the single-channel one also writes the 1/sqrt plane)
-        SizeClass& sc = classes[k];
-        sc.rm_nt = sc.rm_R = 0;
-        const size_t n_cls = sc.members.size();
-        if (c->row_mux && class_kernel[k] == MTM_KERNEL_MFMA && n_cls <= 16 && c->fuse_stats &&
-            (c->chans == 1 || (c->chans == 3 && !sc.masked)) &&
-            (double)c->chans * sc.w * sc.h * 65025.0 < 4294967296.0) {
-            // (wide templates take fewer rows per MFMA group: rm_group_templates)
-            sc.rm_nt = rm_group_templates((int)n_cls, sc.h, sc.w);
-            sc.rm_R = 16 / sc.rm_nt;
-        }
-        sc.slabs.clear();
-        sc.slab_nt = sc.slab_R = 0;
-        const bool big = sc.w > kMfmaMaxW || (long long)c->chans * sc.w * sc.h > 131071;
-        if (class_kernel[k] == MTM_KERNEL_MFMA && big) {
-            sc.slabs = slab_layout(c, sc);
-            sc.rm_nt = sc.rm_R = 0;
-            if (n_cls <= 16) {                     // row-multiplexed raw launches: nt templates x R rows per MFMA group
-                int hs = 0, ws = 0;
-                for (const auto& sl : sc.slabs) {
-                    hs = std::max(hs, sl.r1 - sl.r0);
-                    ws = std::max(ws, sl.c1 - sl.c0);
-                }
-                sc.slab_nt = rm_group_templates((int)n_cls, hs, ws);
-                sc.slab_R = 16 / sc.slab_nt;
-            }
-        }
-        sc.r2 = (c->mfma_r2 && class_kernel[k] == MTM_KERNEL_MFMA && sc.rm_R == 0 && sc.slabs.empty() && n_cls > 16 &&
-                 sc.w <= 64 && c->chans == 1 && !sc.masked && c->method >= MTM_TM_CCORR && c->fuse_stats) ? 2 : 0;
-        // packed K: uint8 classes (one channel, masked or not; RGB) on the plain or row-multiplexed tiling whose width
-        // leaves part of the last 64-tap block empty.  Replaces the two-row variant where both apply (that one saves template loads,
-        // this one whole MFMA steps).
-        sc.kp_nseg = 0;
-        {
-            const int nseg = (sc.w + 15) / 16;
-            const bool normed = c->method == MTM_TM_SQDIFF_NORMED || c->method == MTM_TM_CCORR_NORMED ||
-                                c->method == MTM_TM_CCOEFF_NORMED;       // the instantiated variants (ncc_mfma_kernel<.., KP>)
-            if (class_kernel[k] == MTM_KERNEL_MFMA && sc.slabs.empty() && nseg % 4 != 0 && normed &&
-                (c->chans == 1 || (c->chans == 3 && !sc.masked)) && (!sc.masked || c->method != MTM_TM_CCOEFF_NORMED)) {
-                sc.kp_nseg = nseg;
-                sc.r2 = false;
-            }
-        }
-    }
-    for (int i = 0; i < n; ++i) {
-        const HostTempl& t = c->templs[i];
-        const int kern = class_kernel[(size_t)t.cls];
-        // float64 weights: the float64 / naive kernels, and the exact re-scoring behind the bf16 kernel
-        const bool want_f64 = kern == MTM_KERNEL_AUTO || kern == MTM_KERNEL_NAIVE || kern == MTM_KERNEL_MFMA_F32;
-        if (t.chans != c->chans) {
-            set_error("template " + std::to_string(i) + " has a different channel count than the image");
-            return MTM_E_INVALID;
-        }
-        if (t.rows > c->rows || t.cols > c->cols) {
-            set_error("template " + std::to_string(i) + " is larger than the image");
-            return MTM_E_INVALID;
-        }
-        TemplDev& d = td_host[i];
-        for (int k = 0; k < kMaxChans; ++k) d.mean[k] = t.st.mean[k];
-        d.templ_norm = t.st.templ_norm;
-        d.templ_sum2 = t.st.templ_sum2;
-        d.centred_sum2 = t.st.centred_sum2;
-        d.templ2_mask2_sum = t.st.templ2_mask2_sum;
-        d.all_ones = t.st.all_ones;
-        {
-            double sum_t = t.sum_t;  // exact: integers
-            if (t.dtype == MTM_U8 && !t.on_device)
-                for (size_t k = 0; k < t.px.size(); ++k) sum_t += t.masked ? t.px[k] * t.mask[k] : t.px[k];
-            d.mfma_k = 128.0 * sum_t - 16384.0 * (double)t.rows * (double)t.cols * (double)t.chans;
-        }
-        d.rows = t.rows;
-        d.cols = t.cols;
-        d.cls = t.cls;
-        d.oh = c->rows - t.rows + 1;
-        d.ow = c->cols - t.cols + 1;
-        d.map_pitch = (int)round_up((size_t)d.ow, 4);
-        d.map_off = (long long)map_off;
-        map_off += (size_t)d.map_pitch * d.oh;
-        const size_t plane = (size_t)t.chans * t.rows * t.cols;
-        d.k1_off = d.k2_off = -1;
-        if (want_f64) {
-            d.k1_off = (long long)w_off;
-            w_off += plane;
-            if (t.masked) {
-                d.k2_off = (long long)w_off;
-                w_off += plane;
-            }
-        }
-        if (kern == MTM_KERNEL_DOT4 && img_u8 && t.dtype == MTM_U8 && !t.masked) {
-            d.pack_off = (long long)p_off;
-            p_off += dot_pack_bytes(t.rows, t.cols, t.chans);
-        } else {
-            d.pack_off = -1;
-        }
-    }
-    // masked classes on the integer path: one dot4 pack of the (shared, binary) mask bytes per class
-    for (size_t k = 0; k < classes.size(); ++k) {
-        SizeClass& sc = classes[k];
-        sc.masked_int = sc.masked && class_kernel[k] == MTM_KERNEL_MFMA;
-        sc.mask_pack_off = -1;
-        if (sc.masked_int && !(c->row_mux && c->fuse_stats)) {   // dot4 route of sum I^2 M (otherwise: matrix cores)
-            sc.mask_pack_off = (long long)p_off;
-            p_off += dot_pack_bytes(sc.h, sc.w, 1);
-        }
-    }
-    // templates that live on the device but are matched by a kernel with host-packed operands: fetch their pixels
-    for (int i = 0; i < n; ++i) {
-        const int kern = class_kernel[(size_t)c->templs[i].cls];
-        const bool mfma_dev = kern == MTM_KERNEL_MFMA && !(classes[(size_t)c->templs[i].cls].masked_int &&
-                                                           classes[(size_t)c->templs[i].cls].mask_pack_off >= 0);
-        if (c->templs[i].on_device && !mfma_dev) MTMC(ensure_host_pixels(c, i));
-    }
-    // weights (float64): K1 = T (or T*M^2), K2 = M^2
-    std::vector<double> wts(w_off);
-    std::vector<uint8_t> packs(p_off);
-    for (int i = 0; i < n; ++i) {
-        const HostTempl& t = c->templs[i];
-        const TemplDev& d = td_host[i];
-        const size_t plane = (size_t)t.chans * t.rows * t.cols;
-        if (d.k1_off >= 0 && t.masked) {
-            for (size_t k = 0; k < plane; ++k) {
-                const double m2 = t.mask[k] * t.mask[k];
-                wts[d.k1_off + k] = t.px[k] * m2;
-                wts[d.k2_off + k] = m2;
-            }
-        } else if (d.k1_off >= 0) {
-            std::copy(t.px.begin(), t.px.end(), wts.begin() + d.k1_off);
-        }
-        if (d.pack_off >= 0) pack_template_dot4(t, packs.data() + d.pack_off);
-    }
-    for (const SizeClass& sc : classes)
-        if (sc.masked_int && sc.mask_pack_off >= 0) {
-            HostTempl mk = c->templs[sc.members[0]];
-            for (size_t k = 0; k < mk.px.size(); ++k) mk.px[k] = mk.mask[k] > 0.0 ? 255.0 : 0.0;
-            pack_template_dot4(mk, packs.data() + sc.mask_pack_off);
-        }
-    // int8 MFMA packs, per eligible class
-    size_t a_off = 0;
-    for (size_t k = 0; k < classes.size(); ++k) {
-        SizeClass& sc = classes[k];
-        if (class_kernel[k] != MTM_KERNEL_MFMA) continue;
-        sc.mask_rm_off = -1;
-        if (sc.masked && c->row_mux && c->fuse_stats) {
-            sc.mask_rm_off = (long long)a_off;
-            a_off += (size_t)rm_pack_bytes(sc.h, sc.w, 16);
-            const HostTempl& m0 = c->templs[sc.members[0]];
-            sc.mask_ones = m0.on_device ? m0.mask_ones : 0.0;
-            if (!m0.on_device)
-                for (double m : m0.mask) sc.mask_ones += m > 0.0 ? 1.0 : 0.0;
-        }
-        if (sc.rm_R > 0) {
-            sc.group_bytes = sc.kp_nseg ? class_rm_pack_bytes(sc) / 2          // packed K: a pack per MFMA group
-                                        : -(long long)sc.rm_R * ((sc.w + 63) / 64) * 1024;
-            sc.apack_off = (long long)a_off;
-            a_off += (size_t)class_rm_pack_bytes(sc) * (sc.masked ? 1 : c->chans);
-            continue;
-        }
-        if (!sc.slabs.empty()) {              // one pack per slab (a template of its own, one channel)
-            sc.apack_off = (long long)a_off;
-            for (auto& sl : sc.slabs) {
-                sl.apack_off = (long long)a_off;
-                const int hs = sl.r1 - sl.r0, ws = sl.c1 - sl.c0;
-                a_off += sc.slab_R > 0 ? (size_t)rm_pack_bytes(hs, ws, sc.slab_R)
-                                       : (size_t)mfma_group_bytes(hs, ws, 1) * mfma_groups_alloc((int)sc.members.size());
-            }
-            continue;
-        }
-        if (sc.r2) {
-            sc.group_bytes = mfma_group_bytes(sc.h + sc.r2 - 1, sc.w, 1);        // h + r2 - 1 rows, the extra ones zero
-            sc.apack_off = (long long)a_off;
-            a_off += (size_t)sc.group_bytes * (((int)sc.members.size() + 15) / 16);
-            continue;
-        }
-        sc.group_bytes = sc.kp_nseg ? (long long)c->chans * kp_blocks(sc.h, sc.kp_nseg) * 1024
-                                    : mfma_group_bytes(sc.h, sc.w, c->chans);
-        sc.apack_off = (long long)a_off;
-        a_off += (size_t)sc.group_bytes * mfma_groups_alloc((int)sc.members.size());
-    }
-    for (size_t k = 0; k < classes.size(); ++k) {
-        SizeClass& sc = classes[k];
-        if (class_kernel[k] != MTM_KERNEL_MFMA_F32) continue;
-        sc.group_bytes = bf16_group_bytes(sc.h, sc.w, c->chans);
-        sc.apack_off = (long long)a_off;
-        a_off += (size_t)(2 * sc.group_bytes * mfma_groups_alloc((int)sc.members.size()));
-    }
-    bool any_mbf = false;
-    for (size_t k = 0; k < classes.size(); ++k) {
-        SizeClass& sc = classes[k];
-        sc.mask_bf16 = class_kernel[k] == MTM_KERNEL_AUTO && masked_bf16_class_ok(c, sc);      // (AUTO: the float64 kernel)
-        sc.mbf_off_u = sc.mbf_off_v = -1;
-        if (!sc.mask_bf16) continue;
-        any_mbf = true;
-        sc.mbf_group_bytes = bf16_group_bytes(sc.h, sc.w, 1);
-        const size_t set_bytes = (size_t)(2 * sc.mbf_group_bytes * mfma_groups_alloc((int)sc.members.size()));
-        sc.mbf_off_u = (long long)a_off;
-        a_off += set_bytes;
-        sc.mbf_off_v = (long long)a_off;
-        a_off += set_bytes;
-    }
-    size_t ts_off = 0;
-    for (size_t k = 0; k < classes.size(); ++k) {
-        SizeClass& sc = classes[k];
-        sc.tsum_off = -1;
-        if (class_kernel[k] != MTM_KERNEL_MFMA16) continue;
-        {   // packed K for the two byte-plane passes (widths that are not multiples of 64), as for uint8 classes
-            const int nseg = (sc.w + 15) / 16;
-            sc.kp_nseg = (nseg % 4 != 0) ? nseg : 0;
-        }
-        sc.group_bytes = sc.kp_nseg ? (long long)kp_blocks(sc.h, sc.kp_nseg) * 1024 : mfma_group_bytes(sc.h, sc.w, 1);
-        sc.apack_off = (long long)a_off;
-        a_off += (size_t)sc.group_bytes * (2 * sc.n_pad / 16);
-        sc.tsum_off = (long long)ts_off;
-        ts_off += 2 * (size_t)sc.n_pad;
-    }
-    // classes whose members all live on the device are packed there (after the uploads below)
-    std::vector<char> dev_pack(classes.size(), 0);
-    bool any_host_pack = false;
-    for (size_t k = 0; k < classes.size(); ++k) {
-        if (class_kernel[k] != MTM_KERNEL_MFMA && class_kernel[k] != MTM_KERNEL_MFMA16 && class_kernel[k] != MTM_KERNEL_MFMA_F32)
-            continue;
-        bool all_dev = class_kernel[k] == MTM_KERNEL_MFMA;
-        for (int m : classes[k].members) all_dev = all_dev && c->templs[(size_t)m].on_device;
-        dev_pack[k] = all_dev ? 1 : 0;
-        any_host_pack = any_host_pack || !all_dev;
-    }
-    any_host_pack = any_host_pack || any_mbf;
-    std::vector<uint8_t> apacks(any_host_pack ? a_off : 0);
-    // masked float32 classes: the U = T M^2 / V = M^2 packs and their copies of the template table (centre, centred
-    // energy, and where the approximate c1 / c2 maps go: the real maps' layout, twice, in a scratch arena of their own)
-    std::vector<TemplDev> td_u, td_v;
-    if (any_mbf) {
-        td_u = td_host;
-        td_v = td_host;
-        for (size_t k = 0; k < classes.size(); ++k) {
-            if (!classes[k].mask_bf16) continue;
-            SizeClass u = classes[k];
-            u.group_bytes = classes[k].mbf_group_bytes;
-            pack_class_bf16(c, u, apacks.data() + classes[k].mbf_off_u, td_u, 1);
-            pack_class_bf16(c, u, apacks.data() + classes[k].mbf_off_v, td_v, 2);
-            for (int m : classes[k].members) {
-                td_u[(size_t)m].all_ones = td_v[(size_t)m].all_ones = 0;
-                td_v[(size_t)m].map_off += (long long)map_off;       // second half of the scratch arena
-            }
-        }
-    }
-    std::vector<double> tsums(ts_off);
-    for (size_t k = 0; k < classes.size(); ++k) {
-        if (dev_pack[k]) continue;
-        if (class_kernel[k] == MTM_KERNEL_MFMA)
-            for (int m : classes[k].members) MTMC(ensure_host_pixels(c, m));
-        if (class_kernel[k] == MTM_KERNEL_MFMA && classes[k].mask_rm_off >= 0)
-            pack_mask_rm(c, classes[k], apacks.data() + classes[k].mask_rm_off);
-        if (class_kernel[k] == MTM_KERNEL_MFMA && classes[k].rm_R > 0)
-            pack_class_rm(c, classes[k], apacks.data() + classes[k].apack_off);
-        else if (class_kernel[k] == MTM_KERNEL_MFMA)
-            pack_class_mfma(c, classes[k], apacks.data() + classes[k].apack_off);
-        if (class_kernel[k] == MTM_KERNEL_MFMA16)
-            pack_class_mfma16(c, classes[k], apacks.data() + classes[k].apack_off, tsums.data() + classes[k].tsum_off);
-        if (class_kernel[k] == MTM_KERNEL_MFMA_F32) pack_class_bf16(c, classes[k], apacks.data() + classes[k].apack_off, td_host);
-    }
-    // template lists: one per class, then the list of templates with a 2-D score map
-    for (SizeClass& sc : classes) {
-        sc.tlist_off = (int)tlist_host.size();
-        tlist_host.insert(tlist_host.end(), sc.members.begin(), sc.members.end());
-    }
-    for (int i = 0; i < n; ++i)
-        if (td_host[i].oh > 1 && td_host[i].ow > 1) list2d.push_back(i);
-    const int list2d_off = (int)tlist_host.size();
-    tlist_host.insert(tlist_host.end(), list2d.begin(), list2d.end());
-    // slab views: windows into the units of a large-template class, appended to the unit table (a view of a view:
-    // the offsets move, the orientation stays)
-    std::vector<UnitSrc> units_all(c->usrc_host.begin(), c->usrc_host.begin() + (long)std::min(c->usrc_units, c->usrc_host.size()));
-    for (SizeClass& sc : classes)
-        for (auto& sl : sc.slabs) {
-            sl.tlist_off = (int)tlist_host.size();
-            for (int m : sc.members) {
-                UnitSrc v = c->templs[(size_t)m].src;
-                v.off += (long long)sl.ch * v.sh * v.sw;
-                v.moff = -1;
-                v.cy += v.ay * sl.r0 + v.by * sl.c0;
-                v.cx += v.ax * sl.r0 + v.bx * sl.c0;
-                v.h = sl.r1 - sl.r0;
-                v.w = sl.c1 - sl.c0;
-                v.chans = 1;
-                tlist_host.push_back((int)units_all.size());
-                units_all.push_back(v);
-            }
-        }
-    // From here on copies from this function's own vectors are in flight: an error return below drains the stream before
-    // they go out of scope (the normal path hands the long-lived ones to the context and says so in place_pending).
-    struct DrainGuard {
-        hipStream_t s;
-        bool armed = true;
-        ~DrainGuard() {
-            if (armed) (void)hipStreamSynchronize(s);
-        }
-    } drain{c->stream};
-    if (units_all.size() > c->usrc_units) {
-        MTMC(c->usrc_dev.ensure(sizeof(UnitSrc) * units_all.size()));
-        HIPC(hipMemcpyAsync(c->usrc_dev.p, units_all.data(), sizeof(UnitSrc) * units_all.size(), hipMemcpyHostToDevice, c->stream));
-    }
-
-    MTMC(c->td.ensure(sizeof(TemplDev) * n));
-    MTMC(c->tlist.ensure(sizeof(int) * std::max<size_t>(1, tlist_host.size())));
-    MTMC(c->weights.ensure(sizeof(double) * std::max<size_t>(1, w_off)));
-    MTMC(c->packs.ensure(std::max<size_t>(4, p_off)));
-    MTMC(c->apacks.ensure(std::max<size_t>(16, a_off) + 16384));     // the K loop requests up to two steps past a pack
-    // host-packed classes (device-packed regions of the same arena are written afterwards, in stream order, by
-    // pack_units_kernel below)
-    if (a_off && any_host_pack) HIPC(hipMemcpyAsync(c->apacks.p, apacks.data(), a_off, hipMemcpyHostToDevice, c->stream));
-    // the score-map arena (4 bytes per pixel and template) is only allocated when something writes maps:
-    // mtm_find_matches in hits-only mode never does (ensure_maps, called by the launch paths)
-    HIPC(hipMemcpyAsync(c->td.p, td_host.data(), sizeof(TemplDev) * n, hipMemcpyHostToDevice, c->stream));
-    if (!tlist_host.empty())
-        HIPC(hipMemcpyAsync(c->tlist.p, tlist_host.data(), sizeof(int) * tlist_host.size(),
-                            hipMemcpyHostToDevice, c->stream));
-    if (w_off) HIPC(hipMemcpyAsync(c->weights.p, wts.data(), sizeof(double) * w_off, hipMemcpyHostToDevice, c->stream));
-    if (p_off) HIPC(hipMemcpyAsync(c->packs.p, packs.data(), p_off, hipMemcpyHostToDevice, c->stream));
-    if (any_mbf) {
-        MTMC(c->td_u.ensure(sizeof(TemplDev) * n));
-        MTMC(c->td_v.ensure(sizeof(TemplDev) * n));
-        HIPC(hipMemcpyAsync(c->td_u.p, td_u.data(), sizeof(TemplDev) * n, hipMemcpyHostToDevice, c->stream));
-        HIPC(hipMemcpyAsync(c->td_v.p, td_v.data(), sizeof(TemplDev) * n, hipMemcpyHostToDevice, c->stream));
-    }
-    MTMC(c->tsum.ensure(sizeof(double) * std::max<size_t>(2, ts_off)));
-    if (ts_off) HIPC(hipMemcpyAsync(c->tsum.p, tsums.data(), sizeof(double) * ts_off, hipMemcpyHostToDevice, c->stream));
-    // device-side packing: gathers the A operands straight from the unit views (the template list is in place)
-    for (size_t k = 0; k < classes.size(); ++k)
-        if (dev_pack[k]) MTMC(pack_class_on_device(c, classes[k]));
-    // host staging vectors go out of scope; the tables that stay in the context (td_host, tlist_host) need no wait
-    // (set_templates_device)
-    const bool local_sources = any_host_pack || any_mbf || w_off || p_off || ts_off || units_all.size() > c->usrc_units;
-    if (local_sources) HIPC(hipStreamSynchronize(c->stream));
-    c->place_pending = !local_sources;
-    drain.armed = false;
-    if (units_all.size() > c->usrc_units) c->usrc_host.swap(units_all);
-    c->classes.swap(classes);
-    c->td_host.swap(td_host);
-    c->tlist_host.swap(tlist_host);
-    c->list2d.swap(list2d);
-    c->list2d_off = list2d_off;
-    c->maps_floats = map_off;
-    c->placed = true;
-    return MTM_OK;
+    // Everything is derived into the plan and committed at the end: a failure half-way (an allocation, a copy) leaves the
+    // context as it was - templates set, not placed (the host copies of device-resident templates may have been fetched).
+    Placement P;
+    MTMC(plan_placement(c, P));
+    for (int i : P.host_px) MTMC(ensure_host_pixels(c, i));
+    HostArenas H;
+    pack_on_host(c, P, H);
+    return upload_placement(c, P, H);
 }
 
 // The templates of the last mtm_set_templates, read back from the bytes the context keeps of them (mtm_ctx::templ_blob,
@@ -1145,6 +1158,82 @@ int mtm_set_templates_augmented(mtm_ctx* c, const mtm_templ* bases, int n_bases,
 
 namespace {
 
+// Templates of other pixel types, or with MTM_TEMPL_ON_DEVICE=0: planar float64 copies on the host, statistics.
+void host_templates(const mtm_templ* templs, int n_templ, int method, std::vector<HostTempl>& hts) {
+    hts.assign((size_t)n_templ, HostTempl{});
+    for (int i = 0; i < n_templ; ++i) {
+        const mtm_templ& s = templs[i];
+        HostTempl& t = hts[i];
+        t.rows = s.rows;
+        t.cols = s.cols;
+        t.chans = s.chans;
+        t.dtype = s.dtype;
+        t.masked = s.mask != nullptr;
+        const size_t plane = (size_t)s.rows * s.cols;
+        t.px.resize(plane * s.chans);
+        if (t.masked) t.mask.resize(plane * s.chans);
+        for (int y = 0; y < s.rows; ++y) {
+            const uint8_t* rp = (const uint8_t*)s.px + (size_t)y * s.row_stride;
+            const uint8_t* mp = t.masked ? (const uint8_t*)s.mask + (size_t)y * s.mask_row_stride : nullptr;
+            for (int x = 0; x < s.cols; ++x)
+                for (int k = 0; k < s.chans; ++k) {
+                    const size_t src = (size_t)x * s.chans + k;
+                    const size_t dst = (size_t)k * plane + (size_t)y * s.cols + x;
+                    if (s.dtype == MTM_U8) {
+                        t.px[dst] = (double)rp[src];
+                        // CV_8U masks are binary masks (matchTemplateMask)
+                        if (mp) t.mask[dst] = mp[src] > 0 ? 1.0 : 0.0;
+                    } else if (s.dtype == MTM_U16) {
+                        // the reference casts uint16 to float32 (exact) before cv2 (MTM/__init__.py:71-74):
+                        // a mask is then a float32 weight image, not a binary mask
+                        t.px[dst] = (double)((const uint16_t*)rp)[src];
+                        if (mp) t.mask[dst] = (double)((const uint16_t*)mp)[src];
+                    } else {
+                        t.px[dst] = (double)((const float*)rp)[src];
+                        if (mp) t.mask[dst] = (double)((const float*)mp)[src];
+                    }
+                }
+        }
+        t.st = compute_templ_stats(t.px.data(), t.masked ? t.mask.data() : nullptr, t.rows, t.cols, t.chans,
+                                   method, s.dtype == MTM_U8 || s.dtype == MTM_U16);
+    }
+}
+
+// Size classes, in order of first appearance; every template's `cls`.
+void size_classes(std::vector<HostTempl>& hts, std::vector<SizeClass>& classes) {
+    // masked templates only share a class (and its masked window statistics) when their masks are equal
+    auto mask_hash = [](const HostTempl& t) {
+        unsigned long long hsh = 1469598103934665603ull;
+        for (double v : t.mask) {
+            unsigned long long bits;
+            std::memcpy(&bits, &v, 8);
+            hsh = (hsh ^ bits) * 1099511628211ull;
+        }
+        if (t.on_device) return t.masked ? t.mask_key : 0ull;
+        return t.masked ? hsh : 0ull;
+    };
+    std::map<std::tuple<int, int, bool, unsigned long long>, int> index;
+    for (size_t i = 0; i < hts.size(); ++i) {
+        const auto key = std::make_tuple(hts[i].rows, hts[i].cols, hts[i].masked, mask_hash(hts[i]));
+        auto it = index.find(key);
+        if (it == index.end()) {
+            SizeClass sc;
+            sc.h = hts[i].rows;
+            sc.w = hts[i].cols;
+            sc.masked = hts[i].masked;
+            sc.mask_hash = std::get<3>(key);
+            it = index.emplace(key, (int)classes.size()).first;
+            classes.push_back(sc);
+        }
+        SizeClass& sc = classes[it->second];
+        sc.members.push_back((int)i);
+        sc.all_u8 = sc.all_u8 && hts[i].dtype == MTM_U8;
+        sc.all_u16 = sc.all_u16 && hts[i].dtype == MTM_U16;
+        sc.all_f32 = sc.all_f32 && hts[i].dtype == MTM_F32;
+        hts[i].cls = it->second;
+    }
+}
+
 int set_templates_impl(mtm_ctx* c, const mtm_templ* templs, int n_templ, const mtm_variant* variants, int n_var, int method,
                        const char* who) {
     if (!c || n_templ < 0 || (n_templ > 0 && !templs) || method < 0 || method > 5) {
@@ -1218,79 +1307,11 @@ int set_templates_impl(mtm_ctx* c, const mtm_templ* templs, int n_templ, const m
             ++c->templ_gen;
             return rc;
         }
-        n_templ = (int)hts.size();
     } else {
-    hts.assign((size_t)n_templ, HostTempl{});
-    for (int i = 0; i < n_templ; ++i) {
-        const mtm_templ& s = templs[i];
-        HostTempl& t = hts[i];
-        t.rows = s.rows;
-        t.cols = s.cols;
-        t.chans = s.chans;
-        t.dtype = s.dtype;
-        t.masked = s.mask != nullptr;
-        const size_t plane = (size_t)s.rows * s.cols;
-        t.px.resize(plane * s.chans);
-        if (t.masked) t.mask.resize(plane * s.chans);
-        for (int y = 0; y < s.rows; ++y) {
-            const uint8_t* rp = (const uint8_t*)s.px + (size_t)y * s.row_stride;
-            const uint8_t* mp = t.masked ? (const uint8_t*)s.mask + (size_t)y * s.mask_row_stride : nullptr;
-            for (int x = 0; x < s.cols; ++x)
-                for (int k = 0; k < s.chans; ++k) {
-                    const size_t src = (size_t)x * s.chans + k;
-                    const size_t dst = (size_t)k * plane + (size_t)y * s.cols + x;
-                    if (s.dtype == MTM_U8) {
-                        t.px[dst] = (double)rp[src];
-                        // CV_8U masks are binary masks (matchTemplateMask)
-                        if (mp) t.mask[dst] = mp[src] > 0 ? 1.0 : 0.0;
-                    } else if (s.dtype == MTM_U16) {
-                        // the reference casts uint16 to float32 (exact) before cv2 (MTM/__init__.py:71-74):
-                        // a mask is then a float32 weight image, not a binary mask
-                        t.px[dst] = (double)((const uint16_t*)rp)[src];
-                        if (mp) t.mask[dst] = (double)((const uint16_t*)mp)[src];
-                    } else {
-                        t.px[dst] = (double)((const float*)rp)[src];
-                        if (mp) t.mask[dst] = (double)((const float*)mp)[src];
-                    }
-                }
-        }
-        t.st = compute_templ_stats(t.px.data(), t.masked ? t.mask.data() : nullptr, t.rows, t.cols, t.chans,
-                                   method, s.dtype == MTM_U8 || s.dtype == MTM_U16);
+        host_templates(templs, n_templ, method, hts);
     }
-    }   // host path
-    // size classes, in order of first appearance
     std::vector<SizeClass> classes;
-    // masked templates only share a class (and its masked window statistics) when their masks are equal
-    auto mask_hash = [](const HostTempl& t) {
-        unsigned long long hsh = 1469598103934665603ull;
-        for (double v : t.mask) {
-            unsigned long long bits;
-            std::memcpy(&bits, &v, 8);
-            hsh = (hsh ^ bits) * 1099511628211ull;
-        }
-        if (t.on_device) return t.masked ? t.mask_key : 0ull;
-        return t.masked ? hsh : 0ull;
-    };
-    std::map<std::tuple<int, int, bool, unsigned long long>, int> index;
-    for (int i = 0; i < n_templ; ++i) {
-        const auto key = std::make_tuple(hts[i].rows, hts[i].cols, hts[i].masked, mask_hash(hts[i]));
-        auto it = index.find(key);
-        if (it == index.end()) {
-            SizeClass sc;
-            sc.h = hts[i].rows;
-            sc.w = hts[i].cols;
-            sc.masked = hts[i].masked;
-            sc.mask_hash = std::get<3>(key);
-            it = index.emplace(key, (int)classes.size()).first;
-            classes.push_back(sc);
-        }
-        SizeClass& sc = classes[it->second];
-        sc.members.push_back(i);
-        sc.all_u8 = sc.all_u8 && hts[i].dtype == MTM_U8;
-        sc.all_u16 = sc.all_u16 && hts[i].dtype == MTM_U16;
-        sc.all_f32 = sc.all_f32 && hts[i].dtype == MTM_F32;
-        hts[i].cls = it->second;
-    }
+    size_classes(hts, classes);
     c->templs.swap(hts);
     c->classes.swap(classes);
     c->method = method;

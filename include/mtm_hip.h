@@ -29,6 +29,9 @@
 extern "C" {
 #endif
 
+/* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
+ * mtm_find_matches_boxes, mtm_track_boxes - are new symbols only and left it at 9: a caller built against an older 9
+ * finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -368,6 +371,25 @@ int mtm_find_matches_pyramid(mtm_ctx* ctx, const void* px, int rows, int cols, i
 int mtm_find_matches_boxes(mtm_ctx* ctx, const void* px, int rows, int cols, int chans, int dtype,
                            int64_t row_stride_bytes, const mtm_box_unit* units, int n_units, int mode,
                            double score_threshold, mtm_hit* out, int64_t capacity, int64_t* counts, int64_t* n_out);
+
+/* Templates tracked through a stack of frames in one call: what a loop of mtm_find_matches_boxes calls in
+ * mode MTM_PEAKS_GLOBAL returns, one per frame, each frame's boxes computed from the previous frame's hits.  Track k
+ * follows template start[k].templ_idx (of the last mtm_set_templates) from the region of start[k] in frame 0 (clipped to
+ * the frame, as mtm_find_matches_boxes takes it).  For frame f, track k's record is the extremum of its template's score
+ * map over its current region (ties: first in row-major order; scores bit for bit those of mtm_score_map on the crop),
+ * in frame coordinates.  The region of frame f + 1 is that hit widened by `margin` pixels on every side and clipped to
+ * the frame - x0 = max(0, x - margin), y0 = max(0, y - margin), x1 = min(cols, x + w + margin),
+ * y1 = min(rows, y + h + margin) - unless use_min is set and the score does not pass min_score (methods 0 and 1: score <
+ * min_score, the others: score > min_score, compared in double; a NaN score never passes), in which case the region is
+ * kept.  Frames: n_frames arrays of one shape, pixel type and row stride (uint8 with 1 or 3 channels, or single-channel
+ * uint16, the templates' pixel type; unmasked templates, method 0..5).  They go up in chunks of frames bounded by
+ * MTM_OPT_BATCH_MAX_ROWS and a device-memory budget for their planes; the regions stay on the device between frames and
+ * chunks, and the host waits once, for the records.  out: n_frames * n_tracks records, frame-major (out[f * n_tracks +
+ * k]); templ_idx = the track's template.  A template larger than its frame-0 region, or a region outside the frame,
+ * returns MTM_E_INVALID.  Afterwards the context has no current image (as after mtm_find_matches_batch). */
+int mtm_track_boxes(mtm_ctx* ctx, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                    int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min,
+                    double min_score, mtm_hit* out);
 
 /* Stream form of mtm_find_matches ("thousands of images", reference
  * tutorials/Tutorial3-SpeedingUp.ipynb:564: same templates, one image after the other): returns the

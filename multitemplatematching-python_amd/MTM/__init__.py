@@ -25,7 +25,7 @@ from .version import __version__
 pinned_empty = _lib.pinned_empty        # numpy arrays in page-locked memory (faster uploads); optional
 
 __all__ = ["NMS", "Hit", "matchTemplates", "findMatches", "computeScoreMap", "TemplateMatcher", "matchTemplatesBatch",
-           "findMatchesPyramid", "matchTemplatesPyramid", "findMatchesInBoxes", "matchTemplatesInBoxes",
+           "findMatchesPyramid", "matchTemplatesPyramid", "findMatchesInBoxes", "matchTemplatesInBoxes", "trackTemplates",
            "pinned_empty", "drawBoxesOnRGB",
            "drawBoxesOnGray", "TM_SQDIFF", "TM_SQDIFF_NORMED", "TM_CCORR", "TM_CCORR_NORMED",
            "TM_CCOEFF", "TM_CCOEFF_NORMED", "__version__"]
@@ -510,6 +510,22 @@ class TemplateMatcher:
             self._uploaded_for = (str(image.dtype), 1 if image.ndim == 2 else image.shape[2]) if uploaded else before
         return hits
 
+    def track(self, frames, tracks, margin: int, min_score=None) -> List[List[List[Hit]]]:
+        """
+        ``trackTemplates(listTemplates, frames, tracks, margin, method, min_score)`` with this matcher's list and method: the
+        same hits and exceptions, on this matcher's context with its templates resident across calls.  Scope as
+        trackTemplates', for every template of the list.
+        """
+        from . import tracking
+        self._not_streaming()
+        with self._ctx.lock:
+            # as match_boxes: until the call returns, nothing is known to be resident
+            before, self._uploaded_for = self._uploaded_for, None
+            hits, f0, uploaded = tracking._track(self.listTemplates, frames, tracks, margin, self.method, min_score,
+                                                 self._ctx, True)
+            self._uploaded_for = (str(f0.dtype), 1 if f0.ndim == 2 else f0.shape[2]) if uploaded else before
+        return hits
+
     def match_stream(self, images, searchBox: Optional[BBox] = None):
         """
         Generator over an iterable of images: yields ``match(image)`` for each, in order.  The upload
@@ -681,3 +697,4 @@ def drawBoxesOnGray(image: np.ndarray, listHit: Sequence[Hit], boxThickness: int
 from . import augment  # noqa: E402,F401  (template augmentation / downscaled matching helpers)
 from .pyramid import findMatchesPyramid, matchTemplatesPyramid  # noqa: E402  (coarse-to-fine search)
 from .boxes import findMatchesInBoxes, matchTemplatesInBoxes  # noqa: E402  (many searchBoxes in one call)
+from .tracking import trackTemplates  # noqa: E402  (templates tracked through a stack of frames)

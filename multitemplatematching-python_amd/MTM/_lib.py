@@ -113,6 +113,9 @@ SYMBOLS = {
                                               ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_double, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                               _P(ctypes.c_int64)]),
+    "mtm_track_boxes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
                                              ctypes.c_int64, _P(ctypes.c_int64), ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
@@ -487,6 +490,27 @@ class Context(_RecordMemo):
                           ptr, a.shape[0], a.shape[1], chans, _dtype_code(a), stride, units.ctypes.data, n, int(mode),
                           float(score_threshold), cap=max(4096, 16 * n), counts=counts)
         return hits, counts
+
+    def track_boxes(self, frames, units, margin, min_score=None):
+        """The current templates tracked through frames of one shape and dtype in one native call (mtm_track_boxes).
+        `units`: BOX_UNIT_DTYPE records, each track's template and frame-0 region.  Returns the len(frames) * len(units)
+        records, frame-major (frame coordinates, templ_idx = the track's template)."""
+        n, nt = len(frames), len(units)
+        if n == 0 or nt == 0:
+            return np.zeros(0, dtype=HIT_DTYPE)
+        rows = [_pixel_rows(a) for a in frames]
+        if len({r[2] for r in rows}) > 1:       # (one row stride for every frame)
+            rows = [_pixel_rows(np.ascontiguousarray(a)) for a in frames]
+        a0, _, stride = rows[0]
+        chans = 1 if a0.ndim == 2 else a0.shape[2]
+        ptrs = (ctypes.c_void_p * n)(*[r[1] for r in rows])
+        units = np.ascontiguousarray(units, dtype=BOX_UNIT_DTYPE)
+        out = np.empty(n * nt, dtype=HIT_DTYPE)
+        use_min = min_score is not None
+        check(self._lib.mtm_track_boxes(self._h, ptrs, n, a0.shape[0], a0.shape[1], chans, _dtype_code(a0), stride,
+                                        units.ctypes.data, nt, int(margin), int(use_min),
+                                        float(min_score) if use_min else 0.0, out.ctypes.data), "mtm_track_boxes")
+        return out
 
     def find_matches_batch(self, images, mode, score_threshold):
         """Images of one shape and dtype against the current templates in one native call (mtm_find_matches_batch): a list

@@ -1,0 +1,129 @@
+"""
+Templates tracked through a stack of frames in one engine call: the loop a user writes today,
+
+    out, boxes = [], [b for b, _ in tracks]
+    for f in frames:
+        r = findMatchesInBoxes(listTemplates, f, [(b, [j]) for b, (_, j) in zip(boxes, tracks)], method, N_object=1)
+        out.append(r)
+        boxes = [next_box(b, ri[0] if ri else None, margin, f.shape, method, min_score) for b, ri in zip(boxes, r)]
+
+with the same hits, labels, boxes, float32 score bits, exceptions and warnings, computed by one native call
+(mtm_track_boxes): the frames go up in chunks, and the next frame's search boxes are computed on the GPU from
+this frame's hits, so the host waits once per call instead of twice per frame.
+
+A track is a pair ``((x, y, w, h), j)``: template ``listTemplates[j]``, searched in that box in frame 0 and around its
+last hit afterwards (``next_box``).
+
+Scope (anything else raises before any native call): findMatchesInBoxes' scope with N_object=1 - uint8 frames with 1 or 3
+channels or single-channel uint16 ones, methods 0..5, no masks for methods 0 and 3 - and frames of one shape and dtype,
+``margin`` an integer >= 0.  Frame 0's boxes raise what the loop's first call raises; later boxes always hold their
+template, so later frames raise nothing.
+"""
+import numbers
+import warnings
+from typing import List
+
+import numpy as np
+
+from . import _lib, boxes
+from . import _MSG_MASK_UNSUPPORTED, Hit, TM_CCOEFF_NORMED
+
+__all__ = ["trackTemplates", "next_box"]
+
+
+def next_box(box, hit, margin, image_shape, method, min_score=None):
+    """The search box of the next frame from this frame's ``hit`` (a Hit, or None when the search returned none) in
+    box ``box`` of an image of shape ``image_shape``: the hit's box widened by ``margin`` pixels on every side and clipped
+    to the image, ``(x0, y0, x1 - x0, y1 - y0)`` with x0 = max(0, x - margin), y0 = max(0, y - margin),
+    x1 = min(W, x + w + margin), y1 = min(H, y + h + margin).  ``box`` itself is returned when there is no hit, or when
+    ``min_score`` is set and the hit's score does not pass it: methods 0 and 1 (minima) pass with score < min_score, the
+    others with score > min_score, compared as Python floats; a NaN score never passes."""
+    if hit is None:
+        return tuple(box)
+    if min_score is not None:
+        s, m = float(hit[2]), float(min_score)
+        if not (s < m if method in (0, 1) else s > m):
+            return tuple(box)
+    x, y, w, h = (int(v) for v in hit[1])
+    H, W = int(image_shape[0]), int(image_shape[1])
+    x0, y0 = max(0, x - margin), max(0, y - margin)
+    x1, y1 = min(W, x + w + margin), min(H, y + h + margin)
+    return (x0, y0, x1 - x0, y1 - y0)
+
+
+def _frames(frames):
+    """frames -> a list of arrays of one shape and dtype (an (F, H, W[, C]) array is split along its first axis)."""
+    if isinstance(frames, np.ndarray):
+        if frames.ndim not in (3, 4):
+            raise ValueError("frames: an array of frames has the shape (F, H, W) or (F, H, W, C) (got %s)" % (frames.shape,))
+        return list(frames)
+    fl = list(frames)
+    for i, f in enumerate(fl):
+        if not isinstance(f, np.ndarray):
+            raise ValueError("frames[%d] is not a numpy array" % i)
+        if f.shape != fl[0].shape or f.dtype != fl[0].dtype:
+            raise ValueError("frames[%d] differs from frames[0] in shape or dtype (%s %s, frames[0] %s %s)" % (
+                i, f.shape, f.dtype, fl[0].shape, fl[0].dtype))
+    return fl
+
+
+def _check_args(margin, min_score):
+    if not isinstance(margin, numbers.Integral) or isinstance(margin, bool) or margin < 0:
+        raise ValueError("margin must be an integer >= 0 (got %r)" % (margin,))
+    if min_score is not None and (not isinstance(min_score, numbers.Real) or isinstance(min_score, bool)):
+        raise ValueError("min_score must be a number or None (got %r)" % (min_score,))
+
+
+def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, resident):
+    """trackTemplates on `ctx`.  `resident`: the context holds every template of listTemplates in list order
+    (TemplateMatcher); otherwise the templates the tracks use are set now.  Returns (hits per frame and track, the first
+    frame or None, whether templates were set on the context)."""
+    fl = _frames(frames)
+    _check_args(margin, min_score)
+    regions = [(b, [j]) for b, j in tracks]         # (the loop's unpacking of the pairs, and its errors)
+    if not fl:
+        return [], None, False
+    if not regions:
+        return [[] for _ in fl], fl[0], False
+    f0 = fl[0]
+    if resident and method in boxes._SCOPE_METHODS:       # every resident template is in scope
+        boxes._check_scope(listTemplates, f0, range(len(listTemplates)), method, boxes._SCOPE_METHODS)
+    # frame 0's errors and warnings, as the loop's first call raises and emits them
+    _, units = boxes._plan(listTemplates, f0, regions, method, 1, boxes._SCOPE_METHODS)
+    if method not in (0, 3) and len(fl) > 1:        # the mask warnings of the loop's later calls
+        n_warn = sum(1 for j in units["templ_idx"].tolist() if len(listTemplates[j]) >= 3)
+        for _ in range(n_warn * (len(fl) - 1)):
+            warnings.warn(_MSG_MASK_UNSUPPORTED)
+    if resident:
+        used = None
+        templates = [(t[1], None) for t in listTemplates]
+    else:
+        used = np.unique(units["templ_idx"])
+        units = units.copy()
+        units["templ_idx"] = np.searchsorted(used, units["templ_idx"])
+        templates = [(listTemplates[j][1], None) for j in used.tolist()]
+    # (a margin past the frame's larger side clips to the whole frame, as a margin of that side does)
+    m = int(min(margin, max(f0.shape[0], f0.shape[1])))
+    ctx = ctx or _lib.default_context()         # (only now: every argument error comes before "no GPU")
+    with ctx.lock:
+        ctx.set_templates(templates, method)
+        raw = ctx.track_boxes(fl, units, m, min_score)
+    tidx = raw["templ_idx"] if used is None else used[raw["templ_idx"]]
+    labels = boxes._labels(listTemplates)
+    xywh = zip(raw["x"].tolist(), raw["y"].tolist(), raw["w"].tolist(), raw["h"].tolist())
+    hits = list(zip(labels[tidx].tolist(), xywh, list(raw["score"])))
+    T = len(units)
+    return [[[hits[f * T + k]] for k in range(T)] for f in range(len(fl))], f0, True
+
+
+def trackTemplates(listTemplates, frames, tracks, margin: int, method: int = TM_CCOEFF_NORMED, min_score=None, *,
+                   context=None) -> List[List[List[Hit]]]:
+    """
+    Follow each track through ``frames`` (a sequence of arrays of one shape and dtype, or one ``(F, H, W[, C])`` array):
+    element ``[f][k]`` is what ``findMatchesInBoxes(listTemplates, frames[f], ..., method, N_object=1)`` returns for track
+    k - ``[hit]`` - in the loop of this module's docstring, where each frame's search box is ``next_box`` of the previous
+    frame's hit.  ``tracks``: pairs ``((x, y, w, h), j)``, template ``listTemplates[j]`` starting from that box in frame
+    0.  ``min_score``: a hit that does not pass it (``next_box``) leaves its track's box where it was.  ``context``: the
+    _lib.Context to run on (default: the process's).
+    """
+    return _track(listTemplates, frames, tracks, margin, method, min_score, context, False)[0]

@@ -118,9 +118,10 @@ __global__ __launch_bounds__(256) void boxes_peaks_kernel(const BoxUnit* __restr
 
 }  // namespace mtm
 
-namespace {
+namespace mtmi {
 
-// The epilogue constants of mtm_set_templates' statistics for every template, uploaded once per template set.
+// The epilogue constants of mtm_set_templates' statistics for every template, uploaded once per template set (also
+// mtm_track_boxes').
 int prepare_box_td(mtm_ctx* c, const std::vector<BlobTempl>& tl) {
     if (c->box_gen == c->templ_gen) return MTM_OK;
     const int n = (int)tl.size();
@@ -147,6 +148,10 @@ int prepare_box_td(mtm_ctx* c, const std::vector<BlobTempl>& tl) {
     c->box_gen = c->templ_gen;
     return MTM_OK;
 }
+
+}  // namespace mtmi
+
+namespace {
 
 // Units u0 .. u1 - 1 (whole units, their maps within the memory budget): maps, peaks, records.  Appends the records of
 // each unit, in mtm_find_matches' order and image coordinates, to `hits`, and their number to counts[u].

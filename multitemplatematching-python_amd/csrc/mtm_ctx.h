@@ -383,6 +383,9 @@ struct mtm_ctx {
     uint64_t box_gen = 0;
     DevBuf box_td, box_units, box_tiles;
     int64_t boxes_max_floats = 1ll << 26;
+    // mtm_track_boxes (mtm_track.hip): the per-call track table (rewritten on the device every frame), tile table, extremum
+    // keys and records.
+    DevBuf trk_units, trk_tiles, trk_keys, trk_out;
 
     // RCCL
     void* rccl_lib = nullptr;
@@ -524,6 +527,9 @@ struct BlobTempl {
 };
 int parse_templ_blob(const std::vector<uint8_t>& b, std::vector<BlobTempl>& out, const char* who, bool u16_ok);
 int prepare_window_templates(mtm_ctx* c, const std::vector<BlobTempl>& tl);
+// The templates' epilogue constants (TemplDev, statistics of the last mtm_set_templates and the sizes of `tl`) in
+// mtm_ctx::box_td, uploaded once per template set (mtm_boxes.hip; the boxes and tracking searches).
+int prepare_box_td(mtm_ctx* c, const std::vector<BlobTempl>& tl);
 // The peak pass of the window searches (mtm_api.hip) over n slots (pyramid: templates, boxes: units).  Flags laid out as
 // [u64 record count][u64 best key x n][int nontrivial x n] are zeroed, `launch` enqueues the peak kernels (and anything that
 // must follow them before the read-back) writing records to (hits, cap), the flags come back in one copy; a list that

@@ -1,0 +1,249 @@
+// libmtm_hip.so - templates tracked through a stack of frames in one call (mtm_track_boxes): per frame and
+// track, the extremum of the track template's score map over the track's search box (what mtm_find_matches_boxes returns
+// for that unit in MTM_PEAKS_GLOBAL mode), then the next frame's box from that hit - both on the device, so that the host
+// waits once per call instead of twice per frame.  uint8 (1 or 3 channels) and single-channel uint16, unmasked templates
+// of one mtm_set_templates call.
+#include "mtm_ctx.h"
+#include "mtm_device_util.hip.h"
+#include "mtm_k_window.hip.h"
+
+using namespace mtm;
+using namespace mtmi;
+
+namespace mtm {
+
+// A track as the kernels see it: its template, the frame pixel of its map's output (0, 0) and the map's size.  Frame
+// coordinates: the score kernel adds the frame's row offset in the chunk's stack.  Rewritten by track_update_kernel.
+struct TrackUnit {
+    int t;
+    int y0, x0;
+    int oh, ow;
+};
+
+// One 16 x 16 tile of outputs of track k, first output (ty0, tx0) of its map.  The table covers the largest map the track
+// can have during the call; tiles outside the current map leave at once.
+struct TrackTile {
+    int k, ty0, tx0;
+};
+constexpr size_t kTrackLaunchTiles = (size_t)1 << 22;     // most work-groups (tiles) of one track_score_kernel launch
+
+// Grid: one work-group per tile of the call's tile table.  The tile's windows are summed and scored exactly as
+// boxes_score_kernel does (win_tile_sums_u8 / win_tile_sums_u16, win_score: the same float32 bits), and instead of a map
+// the tile's best output goes into keys[k]: order(quality) << 32 | ~(index in the track's current map), reduced per wave
+// and merged with one atomicMax per wave, as boxes_peaks_kernel keys a unit's extremum in global mode.
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void track_score_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
+                                                          const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
+                                                          const TemplDev* __restrict__ td, const TrackUnit* __restrict__ units,
+                                                          const TrackTile* __restrict__ tiles, int row_off, int method,
+                                                          int mode_min, unsigned long long* __restrict__ keys) {
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
+    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
+    const TrackTile K = tiles[blockIdx.x];
+    const TrackUnit U = units[K.k];
+    if (K.ty0 >= U.oh || K.tx0 >= U.ow) return;         // (the same for the whole work-group: before any barrier)
+    const TemplDev T = td[U.t];
+    const int h = T.rows, w = T.cols;
+    const uint8_t* tp = tpx + toff[U.t];
+    const int tid = threadIdx.x;
+    const double inv_area = 1.0 / ((double)h * (double)w);
+    unsigned long long corr, s2, s1[CH];
+    if constexpr (U16)
+        win_tile_sums_u16(Tl[0], Tl[1], Il[0], Il[1], img.u8, lo_b, img.u8_pitch, img.rows, img.cols, tp, h, w,
+                          row_off + U.y0 + K.ty0, U.x0 + K.tx0, corr, s1[0], s2);
+    else
+        win_tile_sums_u8<CH>(Tl[0], Il[0], img.u8, img.u8_plane, img.u8_pitch, img.rows, img.cols, tp, h, w,
+                             row_off + U.y0 + K.ty0, U.x0 + K.tx0, corr, s1, s2);
+    const int y = K.ty0 + tid / kWinTile, x = K.tx0 + tid % kWinTile;
+    unsigned long long key = 0ull;
+    if (y < U.oh && x < U.ow) {
+        const float s = win_score<CH>(method, T, inv_area, corr, s1, s2);
+        const float v = mode_min ? -s : s;
+        key = ((unsigned long long)mf_float_order(v) << 32) | (0xFFFFFFFFull - (unsigned long long)((long long)y * U.ow + x));
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = __shfl_xor(key, off);
+        key = o > key ? o : key;
+    }
+    if ((tid & 63) == 0 && key != 0ull) atomicMax(keys + K.k, key);
+}
+
+// One lane per track, after the frame's score launch: the frame's record of the track from its key (decode_quality_key,
+// mtm_host.cpp), in frame coordinates, into out[k]; the next frame's box (MTM.tracking.next_box: the hit widened by
+// `margin` on every side, clipped to the frame; kept when use_min is set and the score does not pass min_score - below it
+// for the difference methods, above it for the others, never when NaN); the key cleared for the next frame.
+__global__ __launch_bounds__(256) void track_update_kernel(TrackUnit* __restrict__ units, const TemplDev* __restrict__ td,
+                                                           unsigned long long* __restrict__ keys, int n, int mode_min,
+                                                           int margin, int use_min, double min_score, int rows, int cols,
+                                                           mtm_hit* __restrict__ out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    TrackUnit U = units[k];
+    const unsigned long long key = keys[k];
+    const int w = td[U.t].cols, h = td[U.t].rows;
+    const float q = mf_order_float((uint32_t)(key >> 32));
+    const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull);
+    mtm_hit r;
+    r.templ_idx = U.t;
+    r.x = U.x0 + (int)(idx % (uint32_t)U.ow);
+    r.y = U.y0 + (int)(idx / (uint32_t)U.ow);
+    r.w = w;
+    r.h = h;
+    r.score = key ? (mode_min ? -q : q) + 0.0f : __builtin_nanf("");
+    out[k] = r;
+    const double s = (double)r.score;
+    const bool pass = !use_min || (mode_min ? s < min_score : s > min_score);
+    if (pass) {
+        const long long x0 = max(0ll, (long long)r.x - margin), y0 = max(0ll, (long long)r.y - margin);
+        const long long x1 = min((long long)cols, (long long)r.x + w + margin);
+        const long long y1 = min((long long)rows, (long long)r.y + h + margin);
+        U.x0 = (int)x0;
+        U.y0 = (int)y0;
+        U.ow = (int)(x1 - x0) - w + 1;
+        U.oh = (int)(y1 - y0) - h + 1;
+        units[k] = U;
+    }
+    keys[k] = 0ull;
+}
+
+}  // namespace mtm
+
+namespace {
+
+// Frames per chunk: the row bound of the stacked image (MTM_OPT_BATCH_MAX_ROWS) and the device memory of its planes (raw
+// copy, uint8 / byte / float32 planes: at most 10 bytes per pixel and channel); no score maps are held.
+int track_chunk_frames(const mtm_ctx* c, int rows, int cols, int chans) {
+    const double pitch = (double)round_up((size_t)cols + kPadCols, 64);
+    const double per_frame = (double)(rows + kPadRows) * pitch * 10.0 * chans;
+    const int by_rows = std::max(1, c->batch_max_rows / rows);
+    const int by_mem = (int)std::max(1.0, std::min(1e9, kBatchChunkBytes / per_frame));
+    return std::min(by_rows, by_mem);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtm_track_boxes(mtm_ctx* c, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                    int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min,
+                    double min_score, mtm_hit* out) {
+    const char* who = "mtm_track_boxes";
+    if (!c || n_frames < 0 || n_tracks < 0 || margin < 0 || (n_frames > 0 && !frames) ||
+        (n_tracks > 0 && !start) || (n_frames > 0 && n_tracks > 0 && !out)) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    if (n_frames == 0 || n_tracks == 0) return MTM_OK;
+    for (int f = 0; f < n_frames; ++f) MTMC(check_image_args(frames[f], rows, cols, chans, dtype, row_stride_bytes, who));
+    if (!((dtype == MTM_U8 && (chans == 1 || chans == 3)) || (dtype == MTM_U16 && chans == 1))) {
+        set_error(std::string(who) + ": takes uint8 frames with 1 or 3 channels and single-channel uint16 frames");
+        return MTM_E_INVALID;
+    }
+    if (!c->have_templ) {
+        set_error(std::string(who) + ": no templates set");
+        return MTM_E_STATE;
+    }
+    std::vector<BlobTempl> tl;
+    MTMC(parse_templ_blob(c->templ_blob, tl, who, true));
+    // the track table, and the tile table that covers every map a track can have: the frame-0 map, or one of at most
+    // (2 margin + 1) outputs per side (a box is the hit widened by the margin), neither larger than the frame's own map
+    std::vector<TrackUnit> tu((size_t)n_tracks);
+    std::vector<TrackTile> tiles;
+    for (int k = 0; k < n_tracks; ++k) {
+        const mtm_box_unit& s = start[k];
+        const std::string where = std::string(who) + ": track " + std::to_string(k);
+        if (s.templ_idx < 0 || s.templ_idx >= (int)tl.size()) {
+            set_error(where + ": template index out of range");
+            return MTM_E_INVALID;
+        }
+        if (s.y0 < 0 || s.x0 < 0 || s.rows < 1 || s.cols < 1 || s.rows > rows - s.y0 || s.cols > cols - s.x0) {
+            set_error(where + ": box outside the frame");
+            return MTM_E_INVALID;
+        }
+        const BlobTempl& t = tl[(size_t)s.templ_idx];
+        if (t.dtype != dtype || t.chans != chans) {
+            set_error(where + ": template and frames differ in pixel type or channel count");
+            return MTM_E_INVALID;
+        }
+        if (t.rows > s.rows || t.cols > s.cols) {
+            set_error(where + ": template larger than the box");
+            return MTM_E_INVALID;
+        }
+        if (dtype == MTM_U16 && (long long)t.rows * t.cols > (1ll << 21)) {
+            set_error(where + ": uint16 template of more than 2^21 pixels");
+            return MTM_E_INVALID;
+        }
+        TrackUnit& u = tu[(size_t)k];
+        u.t = s.templ_idx;
+        u.y0 = s.y0;
+        u.x0 = s.x0;
+        u.oh = s.rows - t.rows + 1;
+        u.ow = s.cols - t.cols + 1;
+        const long long side = 2ll * margin + 1;
+        const int th = (int)std::min<long long>(std::max<long long>(u.oh, side), rows - t.rows + 1);
+        const int tw = (int)std::min<long long>(std::max<long long>(u.ow, side), cols - t.cols + 1);
+        for (int ty = 0; ty < th; ty += kWinTile)
+            for (int tx = 0; tx < tw; tx += kWinTile) tiles.push_back(TrackTile{k, ty, tx});
+    }
+    HIPC(hipSetDevice(c->device));
+    MTMC(prepare_window_templates(c, tl));
+    MTMC(prepare_box_td(c, tl));
+
+    c->timing = mtm_timing{};
+    c->maps_valid = false;
+    c->last_hits.clear();
+    const bool mode_min = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_SQDIFF_NORMED;
+    const size_t n_out = (size_t)n_frames * n_tracks;
+    MTMC(c->trk_units.ensure(sizeof(TrackUnit) * tu.size()));
+    MTMC(c->trk_tiles.ensure(sizeof(TrackTile) * tiles.size()));
+    MTMC(c->trk_keys.ensure(sizeof(unsigned long long) * (size_t)n_tracks));
+    MTMC(c->trk_out.ensure(sizeof(mtm_hit) * n_out));
+    HIPC(hipEventRecord(c->ev[0], c->stream));
+    HIPC(hipMemcpyAsync(c->trk_units.p, tu.data(), sizeof(TrackUnit) * tu.size(), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->trk_tiles.p, tiles.data(), sizeof(TrackTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemsetAsync(c->trk_keys.p, 0, sizeof(unsigned long long) * (size_t)n_tracks, c->stream));
+
+    // chunks of frames as one stacked image (frame f of the chunk at rows f * rows ..), the track table carried across
+    // them on the device: the stream orders a chunk's upload behind the previous chunk's launches, the host never waits
+    const int per_chunk = track_chunk_frames(c, rows, cols, chans);
+    const int ublocks = (n_tracks + 255) / 256;
+    for (int f0 = 0; f0 < n_frames; f0 += per_chunk) {
+        const int nb = std::min(per_chunk, n_frames - f0);
+        adopt_image(c, nb * rows, cols, chans, dtype);
+        MTMC(upload_image_stack(c, c->slot[c->cur], frames + f0, nb, row_stride_bytes, rows, cols, chans, dtype, c->stream));
+        const ImageDev img = image_dev(c);
+        const uint8_t* lo_b = c->slot[c->cur].u8b.as<uint8_t>() + img.u8_plane;     // uint16: [high ^ 0x80][low ^ 0x80]
+        for (int fl = 0; fl < nb; ++fl) {
+#define MTM_TRACK_LAUNCH(CH, U16)                                                                                            \
+    hipLaunchKernelGGL((track_score_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, lo_b, c->win_tpx.as<uint8_t>(), \
+                       c->win_toff.as<long long>(), c->box_td.as<TemplDev>(), c->trk_units.as<TrackUnit>(),                  \
+                       c->trk_tiles.as<TrackTile>() + t0, fl * rows, c->method, mode_min ? 1 : 0,                            \
+                       c->trk_keys.as<unsigned long long>())
+            for (size_t t0 = 0; t0 < tiles.size(); t0 += kTrackLaunchTiles) {
+                const unsigned nt = (unsigned)std::min(kTrackLaunchTiles, tiles.size() - t0);
+                if (dtype == MTM_U16) MTM_TRACK_LAUNCH(1, true);
+                else if (chans == 1) MTM_TRACK_LAUNCH(1, false);
+                else MTM_TRACK_LAUNCH(3, false);
+                HIPC(hipGetLastError());
+            }
+#undef MTM_TRACK_LAUNCH
+            hipLaunchKernelGGL(track_update_kernel, dim3(ublocks), dim3(256), 0, c->stream, c->trk_units.as<TrackUnit>(),
+                               c->box_td.as<TemplDev>(), c->trk_keys.as<unsigned long long>(), n_tracks, mode_min ? 1 : 0,
+                               margin, use_min ? 1 : 0, min_score, rows, cols,
+                               c->trk_out.as<mtm_hit>() + (size_t)(f0 + fl) * n_tracks);
+            HIPC(hipGetLastError());
+        }
+    }
+    HIPC(hipEventRecord(c->ev[1], c->stream));
+    HIPC(hipMemcpyAsync(out, c->trk_out.p, sizeof(mtm_hit) * n_out, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
+    c->timing.n_hits = (int64_t)n_out;
+    // the stack is none of the caller's frames: no current image, no published maps
+    c->have_image = false;
+    return MTM_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""Milliseconds per frame, from numpy arrays to hit lists, of four ways to track templates through a stack of frames, one
+JSON line per workload:
+  track        - MTM.trackTemplates(templates, frames, tracks, margin): one native call for the whole stack
+  matcher      - TemplateMatcher(templates).track(frames, tracks, margin): the same with the templates resident
+  loop_boxes   - the loop of findMatchesInBoxes(..., N_object=1) calls and next_box a user writes without trackTemplates
+  loop_matcher - the same loop with TemplateMatcher(templates, N_object=1).match_boxes
+The results of track and matcher are checked equal to loop_boxes' (labels, boxes, float32 score bits), and the fraction
+of (frame, track) hits at the true position is reported.
+
+Data: each frame is one of 8 synth.smooth_u8 backgrounds (uint16: 257 x that plus noise in the low byte) with each
+track's template - a crop of another smooth_u8 image - pasted at a position that moves up to margin / 2 pixels per frame
+in each direction.  Each method is warmed up first; the four are interleaved within a repetition; medians over the
+repetitions.
+
+Usage: tools/track_throughput.py [--reps 3] [--warmup 1] [--only T1|T2|T3]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "multitemplatematching-python_amd"))
+
+# name, frames, (rows, cols), channels, dtype, tracks, template side, margin
+WORKLOADS = [
+    ("T1", 200, (1080, 1920), 1, "uint8", 64, 32, 16),
+    ("T2", 100, (2048, 2048), 1, "uint16", 16, 48, 24),
+    ("T3", 50, (2160, 3840), 3, "uint8", 8, 64, 32),
+]
+N_BACKGROUNDS = 8
+
+
+def _image(seed, hw, chans, dtype, rng):
+    import synth
+    planes = [synth.smooth_u8(seed + 101 * c, hw) for c in range(chans)]
+    img = planes[0] if chans == 1 else np.ascontiguousarray(np.stack(planes, axis=2))
+    if dtype == "uint16":
+        img = (img.astype(np.uint16) * 257 + rng.integers(0, 64, size=img.shape, dtype=np.uint16)).astype(np.uint16)
+    return img
+
+
+def workload(spec, seed=0):
+    name, n_frames, hw, chans, dtype, n_tracks, side, margin = spec
+    rng = np.random.default_rng(seed)
+    backs = [_image(seed + 1 + b, hw, chans, dtype, rng) for b in range(N_BACKGROUNDS)]
+    src = _image(seed + 99, hw, chans, dtype, rng)
+    templs = []
+    for k in range(n_tracks):
+        y, x = int(rng.integers(0, hw[0] - side)), int(rng.integers(0, hw[1] - side))
+        templs.append(("t%d" % k, np.ascontiguousarray(src[y:y + side, x:x + side])))
+    pos = np.stack([rng.integers(0, hw[1] - side, n_tracks), rng.integers(0, hw[0] - side, n_tracks)], axis=1)
+    frames = np.empty((n_frames,) + backs[0].shape, backs[0].dtype)
+    truth = np.empty((n_frames, n_tracks, 2), np.int64)
+    for f in range(n_frames):
+        frames[f] = backs[f % N_BACKGROUNDS]
+        for k in range(n_tracks):
+            x, y = pos[k]
+            frames[f, y:y + side, x:x + side] = templs[k][1]
+        truth[f] = pos
+        step = rng.integers(-(margin // 2), margin // 2 + 1, size=pos.shape)
+        pos = np.clip(pos + step, 0, [hw[1] - side, hw[0] - side])
+    tracks = [((max(0, int(x) - margin), max(0, int(y) - margin), side + 2 * margin, side + 2 * margin), k)
+              for k, (x, y) in enumerate(truth[0])]
+    return templs, frames, tracks, truth
+
+
+def _key(res):
+    return [[(h[0][0], tuple(int(v) for v in h[0][1]), np.float32(h[0][2]).tobytes()) for h in fr] for fr in res]
+
+
+def run(MTM, spec, reps, warmup):
+    from MTM.tracking import next_box
+    name, n_frames, hw, chans, dtype, n_tracks, side, margin = spec
+    templs, frames, tracks, truth = workload(spec)
+    frame_list = list(frames)
+    method = MTM.TM_CCOEFF_NORMED
+
+    def loop(search):
+        out, bxs = [], [b for b, _ in tracks]
+        for f in frame_list:
+            r = search(f, [(b, [j]) for b, (_, j) in zip(bxs, tracks)])
+            out.append(r)
+            bxs = [next_box(b, ri[0] if ri else None, margin, f.shape, method) for b, ri in zip(bxs, r)]
+        return out
+
+    matcher = MTM.TemplateMatcher(templs, method)
+    matcher1 = MTM.TemplateMatcher(templs, method, N_object=1)
+    methods = {
+        "track": lambda: MTM.trackTemplates(templs, frames, tracks, margin, method),
+        "matcher": lambda: matcher.track(frames, tracks, margin),
+        "loop_boxes": lambda: loop(lambda f, reg: MTM.findMatchesInBoxes(templs, f, reg, method, N_object=1)),
+        "loop_matcher": lambda: loop(matcher1.match_boxes),
+    }
+    results = {}
+    for k, fn in methods.items():
+        for _ in range(warmup):
+            results[k] = fn()
+    ms = {k: [] for k in methods}
+    for _ in range(reps):
+        for k, fn in methods.items():
+            t0 = time.perf_counter()
+            fn()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    ref = _key(results["loop_boxes"])
+    equal = {k: _key(results[k]) == ref for k in ("track", "matcher", "loop_matcher")}
+    got = np.array([[h[0][1][:2] for h in fr] for fr in results["track"]])
+    recovered = float(np.mean(np.all(got == truth, axis=2)))
+    methods["track"]()                              # (the default context's timing: this call's, upload to last launch)
+    t = MTM._lib.default_context().timing()
+    return {
+        "workload": name, "frames": n_frames, "frame": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype), "tracks": n_tracks,
+        "template": "%dx%d" % (side, side), "margin": margin,
+        "ms_per_frame": {k: round(v / n_frames, 4) for k, v in med.items()},
+        "ms_per_frame_min": {k: round(min(v) / n_frames, 4) for k, v in ms.items()},
+        "speedup_vs_loop_boxes": {k: round(med["loop_boxes"] / med[k], 2) for k in ("track", "matcher", "loop_matcher")},
+        "track_device_ms": round(float(t["total_ms"]), 3),
+        "equal_to_loop_boxes": equal,
+        "recovered": round(recovered, 4),
+        "reps": reps,
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--only", default=None, help="run the one workload of this name (profiling runs)")
+    args = ap.parse_args()
+    import build as mtm_build
+    mtm_build.build()
+    import MTM
+    for spec in WORKLOADS:
+        if args.only and spec[0] != args.only:
+            continue
+        print(json.dumps(run(MTM, spec, args.reps, args.warmup)), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -30,7 +30,7 @@ extern "C" {
 #endif
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
- * mtm_find_matches_boxes, mtm_track_boxes - are new symbols only and left it at 9: a caller built against an older 9
+ * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods - are new symbols only and left it at 9: a caller built against an older 9
  * finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
@@ -155,6 +155,12 @@ typedef struct mtm_box_unit {
     int32_t templ_idx;
     int32_t y0, x0, rows, cols;
 } mtm_box_unit;
+
+/* One hit of mtm_hit_neighbourhoods: a template of the last mtm_set_templates and the window (x, y) of its score map at the
+ * centre of the neighbourhood. */
+typedef struct mtm_point {
+    int32_t templ_idx, x, y;
+} mtm_point;
 
 /* timing of the last mtm_find_matches call, measured with HIP events on the context's stream */
 typedef struct mtm_timing {
@@ -390,6 +396,17 @@ int mtm_find_matches_boxes(mtm_ctx* ctx, const void* px, int rows, int cols, int
 int mtm_track_boxes(mtm_ctx* ctx, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
                     int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min,
                     double min_score, mtm_hit* out);
+
+/* The 3 x 3 score neighbourhoods of n points in one call: out[9 k + 3 (1 + dy) + (1 + dx)] = the score of
+ * template pts[k].templ_idx at window (x + dx, y + dy) of the image's score map, NaN for a window outside the map.  Image:
+ * uint8 or float32 with 1 or 3 channels, or single-channel uint16, the templates' pixel type; masked templates (uint8 or
+ * float32, methods 0..3) as mtm_set_templates took them.  uint8 and uint16 scores are mtm_score_map's bit for bit in the
+ * default MTM_OPT_EXACT_DIV mode; float32 scores agree with it to rounding (window sums in float64 of the window itself).
+ * The image crosses PCIe once.  A template index out of range, a window outside the map, or a template whose pixel type or
+ * channel count differs from the image's returns MTM_E_INVALID and names the point.  The image becomes the context's
+ * current image. */
+int mtm_hit_neighbourhoods(mtm_ctx* ctx, const void* px, int rows, int cols, int chans, int dtype,
+                           int64_t row_stride_bytes, const mtm_point* pts, int n, float* out);
 
 /* Stream form of mtm_find_matches ("thousands of images", reference
  * tutorials/Tutorial3-SpeedingUp.ipynb:564: same templates, one image after the other): returns the

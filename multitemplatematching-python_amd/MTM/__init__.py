@@ -26,6 +26,7 @@ pinned_empty = _lib.pinned_empty        # numpy arrays in page-locked memory (fa
 
 __all__ = ["NMS", "Hit", "matchTemplates", "findMatches", "computeScoreMap", "TemplateMatcher", "matchTemplatesBatch",
            "findMatchesPyramid", "matchTemplatesPyramid", "findMatchesInBoxes", "matchTemplatesInBoxes", "trackTemplates",
+           "hitNeighbourhoods", "refineHits",
            "pinned_empty", "drawBoxesOnRGB",
            "drawBoxesOnGray", "TM_SQDIFF", "TM_SQDIFF_NORMED", "TM_CCORR", "TM_CCORR_NORMED",
            "TM_CCOEFF", "TM_CCOEFF_NORMED", "__version__"]
@@ -526,6 +527,22 @@ class TemplateMatcher:
             self._uploaded_for = (str(f0.dtype), 1 if f0.ndim == 2 else f0.shape[2]) if uploaded else before
         return hits
 
+    def refine(self, image: np.ndarray, hits) -> List[tuple]:
+        """
+        ``refineHits(listTemplates, image, hits, method)`` with this matcher's list and method: the same results and
+        exceptions, on this matcher's context.  The call sets the whole list as ``match`` would for this image, so that
+        the templates stay resident for the next ``match``.
+        """
+        from . import subpixel
+        self._not_streaming()
+        hits = list(hits)
+        with self._ctx.lock:
+            # as match_boxes: until the call returns, nothing is known to be resident
+            before, self._uploaded_for = self._uploaded_for, None
+            nb, kind = subpixel._neighbourhoods(self.listTemplates, image, hits, self.method, self._ctx, True)
+            self._uploaded_for = kind if kind is not None else before
+        return subpixel._refined(hits, nb, self.method)
+
     def match_stream(self, images, searchBox: Optional[BBox] = None):
         """
         Generator over an iterable of images: yields ``match(image)`` for each, in order.  The upload
@@ -698,3 +715,4 @@ from . import augment  # noqa: E402,F401  (template augmentation / downscaled ma
 from .pyramid import findMatchesPyramid, matchTemplatesPyramid  # noqa: E402  (coarse-to-fine search)
 from .boxes import findMatchesInBoxes, matchTemplatesInBoxes  # noqa: E402  (many searchBoxes in one call)
 from .tracking import trackTemplates  # noqa: E402  (templates tracked through a stack of frames)
+from .subpixel import hitNeighbourhoods, refineHits  # noqa: E402  (sub-pixel positions from score neighbourhoods)

@@ -61,6 +61,8 @@ HIT_DTYPE = np.dtype([("templ_idx", "<i4"), ("x", "<i4"), ("y", "<i4"), ("w", "<
                       ("score", "<f4")])
 # mtm_box_unit: a template index and the region (y0, x0, rows, cols) it is searched in
 BOX_UNIT_DTYPE = np.dtype([("templ_idx", "<i4"), ("y0", "<i4"), ("x0", "<i4"), ("rows", "<i4"), ("cols", "<i4")])
+# mtm_point: a template index and the window (x, y) at the centre of a 3 x 3 neighbourhood (mtm_hit_neighbourhoods)
+POINT_DTYPE = np.dtype([("templ_idx", "<i4"), ("x", "<i4"), ("y", "<i4")])
 assert HIT_DTYPE.itemsize == ctypes.sizeof(MtmHit) == 24
 # mtm_templ as a numpy record: a whole template list is filled column-wise instead of field by field
 TEMPL_DTYPE = np.dtype([("px", "<u8"), ("mask", "<u8"), ("rows", "<i4"), ("cols", "<i4"), ("chans", "<i4"),
@@ -116,6 +118,8 @@ SYMBOLS = {
     "mtm_track_boxes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
+    "mtm_hit_neighbourhoods": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
                                              ctypes.c_int64, _P(ctypes.c_int64), ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
@@ -510,6 +514,19 @@ class Context(_RecordMemo):
         check(self._lib.mtm_track_boxes(self._h, ptrs, n, a0.shape[0], a0.shape[1], chans, _dtype_code(a0), stride,
                                         units.ctypes.data, nt, int(margin), int(use_min),
                                         float(min_score) if use_min else 0.0, out.ctypes.data), "mtm_track_boxes")
+        return out
+
+    def hit_neighbourhoods(self, image, points):
+        """The 3 x 3 score neighbourhoods of `points` (POINT_DTYPE records: a template of the current set and a window of
+        its map over `image`) in one native call (mtm_hit_neighbourhoods): a (len(points), 3, 3) float32 array, element
+        [k, 1 + dy, 1 + dx] the score at window (x + dx, y + dy), NaN outside the map."""
+        a, ptr, stride = _pixel_rows(image)
+        chans = 1 if a.ndim == 2 else a.shape[2]
+        points = np.ascontiguousarray(points, dtype=POINT_DTYPE)
+        n = len(points)
+        out = np.empty((n, 3, 3), dtype=np.float32)
+        check(self._lib.mtm_hit_neighbourhoods(self._h, ptr, a.shape[0], a.shape[1], chans, _dtype_code(a), stride,
+                                               points.ctypes.data, n, out.ctypes.data), "mtm_hit_neighbourhoods")
         return out
 
     def find_matches_batch(self, images, mode, score_threshold):

@@ -2,7 +2,7 @@
 // translation units share.  Units: mtm_context.hip (context, options, image upload), mtm_placement.hip (template sets ->
 // size classes, packs, constants), mtm_launch.hip (window statistics and score-map launches), mtm_api.hip
 // (mtm_find_matches and friends: peak extraction, hit lists), mtm_comm.hip (RCCL hit exchange), mtm_pyramid.hip (the
-// coarse-to-fine search), mtm_boxes.hip (many searchBoxes in one call).  Not part of the ABI.
+// coarse-to-fine search), mtm_boxes.hip (many searchBoxes in one call), mtm_subpixel.hip (hit neighbourhoods).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -386,6 +386,10 @@ struct mtm_ctx {
     // mtm_track_boxes (mtm_track.hip): the per-call track table (rewritten on the device every frame), tile table, extremum
     // keys and records.
     DevBuf trk_units, trk_tiles, trk_keys, trk_out;
+    // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
+    // template set sub_gen) and the per-call point table and scores.
+    uint64_t sub_gen = 0;
+    DevBuf sub_bytes, sub_wts, sub_td, sub_pts, sub_out;
 
     // RCCL
     void* rccl_lib = nullptr;

@@ -128,6 +128,7 @@ struct SizeClass {
     int r2 = 0;                 // multi-row MFMA variant (> 16 templates, w <= 64, one channel, methods 2..5): 2 or 3 consecutive
                                 // output rows x 16 templates per wave; packs of h + r2 - 1 rows per 16-template group (the
                                 // extra rows zero); 0 = off
+    int tail_split = 0;         // two-row variant: K steps before the tail screen (a multiple of 6; MfmaParams::tail_split), 0 = none
     long long mask_rm_off = -1; // masked class: row-multiplexed pack (1 "template" = the binary mask, R = 16) in apacks
     double mask_ones = 0.0;     // number of set mask pixels
     int n_pad = 0;              // members rounded up to a multiple of 16 (uint16 packs)
@@ -251,6 +252,8 @@ struct mtm_ctx {
     // statistics of the rows that became computable); the score kernel of a band waits for its event
     hipStream_t stats_stream = nullptr;     // non-null while a banded call queues its statistics launches
     int screen_l1 = 1;                      // MTM_SCREEN_L1: the hits-only screen starts with the per-lane bound (0: round 2's screen alone)
+    int tail_screen = 1;                    // MTM_TAIL_SCREEN: the two-row variant's hits-only K loop stops early where a bound on the
+                                            // template rows still missing rules out every candidate (MfmaParams::tail_split)
     int f32_mfma = 1;                       // MTM_F32_MFMA / MTM_OPT_F32_MFMA: unmasked float32 classes on the bf16 matrix cores:
                                             // 0 = float64 kernel, 1 = bf16 screen + exact float64 re-scoring of everything
                                             // that could be a peak (hit lists of the float64 kernel), 2 = bf16 scores as they are,
@@ -291,7 +294,8 @@ struct mtm_ctx {
     hipEvent_t slab_fork = nullptr;
     std::vector<hipEvent_t> band_ev;
     int banded_cls = -1;                    // the size class a banded call runs under the upload (banded_ok)
-    std::vector<double> upload_bands{0.25, 1.0};   // cumulative row fractions (MTM_UPLOAD_BANDS)
+    std::vector<double> upload_bands{0.25, 1.0};   // cumulative row fractions (MTM_UPLOAD_BANDS; 0.25 re-measured against
+                                                   // 0.15 .. 0.35 with the tail-screened score kernel: still the fastest)
     // MTM_HOST_TRACE=1: host time stamps at the phases of a fused call, averaged and printed when the context is destroyed
     bool host_trace = false;
     double trace_acc[24] = {0};

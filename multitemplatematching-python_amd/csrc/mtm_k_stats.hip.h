@@ -200,15 +200,18 @@ struct StatLayout {
                                             // kernel of a banded call does it instead of a fill command between two calls)
 };
 
+template <bool TAIL>
 __global__ __launch_bounds__(256) void stats_u8_kernel(const uint8_t* __restrict__ img, int pitch, int h, int w,
                                                        int oh, int ow, int owg, double inv_area, int num_type,
                                                        int want_sq, int want_t, int want_sum2, double* __restrict__ t0,
                                                        double* __restrict__ sum2, double* __restrict__ sq,
                                                        int st_pitch, double* __restrict__ rsq = nullptr,
                                                        int yb_off = 0, double* __restrict__ blk = nullptr,
-                                                       int blk_pitch = 0, StatLayout lay = StatLayout{}) {
+                                                       int blk_pitch = 0, StatLayout lay = StatLayout{},
+                                                       double* __restrict__ blkq = nullptr, int tail_s = 0) {
     __shared__ __attribute__((aligned(16))) uint32_t E1[kStatStrip + 4], E2[kStatStrip + 4];   // exclusive prefixes
-    __shared__ uint32_t wsum[2][4];
+    __shared__ uint32_t wsum[TAIL ? 4 : 2][4];
+    __shared__ __attribute__((aligned(16))) uint32_t EQ1[TAIL ? kStatStrip + 4 : 4], EQ2[TAIL ? kStatStrip + 4 : 4];   // ... of the tail boxes
     const int x0 = blockIdx.x * owg, y0 = ((int)blockIdx.y + yb_off) * kStatBand4;   // yb_off: banded launches
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (lay.zero16 != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && t == 0) {
@@ -245,6 +248,11 @@ __global__ __launch_bounds__(256) void stats_u8_kernel(const uint8_t* __restrict
     const bool ld = 4 * t < L && x0 + 4 * t + 3 < pitch;
     const uint8_t* base = img + (size_t)y0 * pitch + x0 + 4 * t;
     uint32_t c1[4] = {0, 0, 0, 0}, c2[4] = {0, 0, 0, 0};
+    // Tail boxes (TAIL; the two-row MFMA variant's tail screen, split s = tail_s, records into blkq): the window's template rows
+    // the score kernel has not accumulated after s K steps.  Its waves pair output rows (even y, y + 1): the even row's box
+    // is image rows y + s .. y + h - 1, the odd row's y + s .. y + h (|Q| = h - s and h - s + 1 rows).  y0 is even, so
+    // the column sums q1 / q2 of the box slide by one added row per output row and two removed ones after each odd row.
+    uint32_t q1[4] = {0, 0, 0, 0}, q2[4] = {0, 0, 0, 0};
     auto unpack = [](uint32_t v, uint32_t (&b)[4]) {
         b[0] = v & 255u;
         b[1] = (v >> 8) & 255u;
@@ -268,6 +276,13 @@ __global__ __launch_bounds__(256) void stats_u8_kernel(const uint8_t* __restrict
                     c1[k] += b[k];
                     c2[k] += b[k] * b[k];
                 }
+                if (TAIL && r0 + i >= tail_s) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        q1[k] += b[k];
+                        q2[k] += b[k] * b[k];
+                    }
+                }
             }
     }
     const int y1 = min(y0 + kStatBand4, oh);
@@ -276,25 +291,46 @@ __global__ __launch_bounds__(256) void stats_u8_kernel(const uint8_t* __restrict
     for (int y = y0; y < y1; ++y) {
         // request the two image rows of the slide at the end of this iteration now: their latency
         // hides behind the scan and the float64 statistics
-        uint32_t vn = 0, vo = 0;
+        uint32_t vn = 0, vo = 0, vq0 = 0, vq1 = 0;
+        const bool odd = ((y - y0) & 1) != 0;
         if (y + 1 < y1 && ld) {
             vn = *reinterpret_cast<const uint32_t*>(base + (size_t)(y - y0 + h) * pitch);
             vo = *reinterpret_cast<const uint32_t*>(base + (size_t)(y - y0) * pitch);
+            if (TAIL && odd) {          // the rows the tail box leaves behind on its way to the next (even) row
+                vq0 = *reinterpret_cast<const uint32_t*>(base + (size_t)(y - y0 + tail_s - 1) * pitch);
+                vq1 = *reinterpret_cast<const uint32_t*>(base + (size_t)(y - y0 + tail_s) * pitch);
+            }
         }
         // block-wide exclusive scan of the column sums (thread-local prefix, wave scan, cross-wave)
         const uint32_t a = c1[0] + c1[1] + c1[2] + c1[3], b = c2[0] + c2[1] + c2[2] + c2[3];
         const uint32_t sa = wave_inclusive_scan_u32(a), sb = wave_inclusive_scan_u32(b);
+        uint32_t aq = 0, bq = 0, saq = 0, sbq = 0;
+        if constexpr (TAIL) {
+            aq = q1[0] + q1[1] + q1[2] + q1[3];
+            bq = q2[0] + q2[1] + q2[2] + q2[3];
+            saq = wave_inclusive_scan_u32(aq);
+            sbq = wave_inclusive_scan_u32(bq);
+        }
         if (lane == 63) {
             wsum[0][wave] = sa;
             wsum[1][wave] = sb;
+            if constexpr (TAIL) {
+                wsum[2][wave] = saq;
+                wsum[3][wave] = sbq;
+            }
         }
         __syncthreads();                 // also: previous row's E reads are done
         uint32_t oa = sa - a, ob = sb - b;          // exclusive offset of this thread's first column
+        uint32_t oaq = saq - aq, obq = sbq - bq;
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (k < wave) {
                 oa += wsum[0][k];
                 ob += wsum[1][k];
+                if constexpr (TAIL) {
+                    oaq += wsum[2][k];
+                    obq += wsum[3][k];
+                }
             }
         const uint32_t e1[4] = {oa, oa + c1[0], oa + c1[0] + c1[1], oa + c1[0] + c1[1] + c1[2]};
         const uint32_t e2[4] = {ob, ob + c2[0], ob + c2[0] + c2[1], ob + c2[0] + c2[1] + c2[2]};
@@ -303,6 +339,16 @@ __global__ __launch_bounds__(256) void stats_u8_kernel(const uint8_t* __restrict
         if (t == 255) {                  // E[kStatStrip]: read when the strip is full width
             E1[kStatStrip] = oa + a;
             E2[kStatStrip] = ob + b;
+        }
+        const uint32_t eq1[4] = {oaq, oaq + q1[0], oaq + q1[0] + q1[1], oaq + q1[0] + q1[1] + q1[2]};
+        const uint32_t eq2[4] = {obq, obq + q2[0], obq + q2[0] + q2[1], obq + q2[0] + q2[1] + q2[2]};
+        if constexpr (TAIL) {
+            *reinterpret_cast<uint4*>(&EQ1[4 * t]) = make_uint4(eq1[0], eq1[1], eq1[2], eq1[3]);
+            *reinterpret_cast<uint4*>(&EQ2[4 * t]) = make_uint4(eq2[0], eq2[1], eq2[2], eq2[3]);
+            if (t == 255) {
+                EQ1[kStatStrip] = oaq + aq;
+                EQ2[kStatStrip] = obq + bq;
+            }
         }
         __syncthreads();
         double blk_s1[4] = {0.0, 0.0, 0.0, 0.0}, blk_sq[4] = {0.0, 0.0, 0.0, 0.0};
@@ -364,6 +410,37 @@ __global__ __launch_bounds__(256) void stats_u8_kernel(const uint8_t* __restrict
                 *reinterpret_cast<double2*>(o + 2) = make_double2(sm, 0.0);
             }
         }
+        if constexpr (TAIL) {
+            // the tail box's ranges over the same blocks: S1_Q min / max and the largest sqrt(V_Q).  |Q| S2_Q and S1_Q^2
+            // are integers below 2^53 (w h 255^2 < 2^32), so V' = |Q| S2_Q - S1_Q^2 = |Q| V_Q is exact, and so is its
+            // maximum over the block; sqrt(max V' * RN(1 / |Q|)) carries three roundings (<= 2.5 ulp) and is raised by 2^-49
+            // relative (16 ulp): never below the exact root of the block's largest V_Q (sqrt is monotonic)
+            const double nq = (double)((odd ? h - tail_s + 1 : h - tail_s) * w);
+            double lo = INFINITY, hi = 0.0, vm = 0.0;
+            if (out_on) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (xg + k < ow) {
+                        const uint32_t s1q = EQ1[4 * t + k + w] - eq1[k], s2q = EQ2[4 * t + k + w] - eq2[k];
+                        const double a1 = (double)s1q;
+                        lo = fmin(lo, a1);
+                        hi = fmax(hi, a1);
+                        vm = fmax(vm, nq * (double)s2q - a1 * a1);
+                    }
+            }
+#pragma unroll
+            for (int off = 1; off <= 2; off <<= 1) {
+                lo = fmin(lo, __shfl_xor(lo, off));
+                hi = fmax(hi, __shfl_xor(hi, off));
+                vm = fmax(vm, __shfl_xor(vm, off));
+            }
+            vm = sqrt(vm * (1.0 / nq)) * (1.0 + 0x1p-49);
+            if ((t & 3) == 0 && 4 * t < owg && (xg >> 4) < blk_pitch) {
+                double* o = blkq + ((size_t)y * blk_pitch + (xg >> 4)) * 4;
+                *reinterpret_cast<double2*>(o) = make_double2(lo == INFINITY ? 0.0 : lo, hi);
+                *reinterpret_cast<double2*>(o + 2) = make_double2(vm, 0.0);
+            }
+        }
         // slide the column sums one row down (zeros on the last row: nothing changes)
         uint32_t bn[4], bo[4];
         unpack(vn, bn);
@@ -372,6 +449,16 @@ __global__ __launch_bounds__(256) void stats_u8_kernel(const uint8_t* __restrict
         for (int k = 0; k < 4; ++k) {
             c1[k] += bn[k] - bo[k];
             c2[k] += bn[k] * bn[k] - bo[k] * bo[k];
+        }
+        if constexpr (TAIL) {
+            uint32_t b0[4], b1[4];
+            unpack(vq0, b0);
+            unpack(vq1, b1);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                q1[k] += bn[k] - b0[k] - b1[k];
+                q2[k] += bn[k] * bn[k] - b0[k] * b0[k] - b1[k] * b1[k];
+            }
         }
     }
 }

@@ -34,6 +34,10 @@ struct TemplDev {
     int map_pitch;          // floats per score-map row on the device (multiple of 4)
     int oh, ow;             // score-map size
     int cls;                // index of the template's size class
+    // tail screen of the two-row MFMA variant (ncc_mfma_kernel, MfmaParams::tail_split; written on the device by
+    // tail_consts_kernel): [0] the wave's first row (template rows 0 .. s - 1 accumulated), [1] its second (0 .. s - 2).
+    // K_P = 128 sum(T_P) - 16384 |P| (exact), d = mean(T_Q) - 128, g = sqrt(sum_Q (T - mean(T_Q))^2) rounded up.
+    double tail_k[2], tail_d[2], tail_g[2];
 };
 
 // Window statistics planes of one size class (all double, pitch = stat_pitch elements).
@@ -47,6 +51,9 @@ struct StatPlanes {
     // for a block right of the last output column
     int blk_pitch;
     const double* blk;
+    // the same blocks over the TAIL box of each output row (the template rows the two-row variant's K loop has not reached
+    // at MfmaParams::tail_split): [S1_Q min, S1_Q max, sqrt(V_Q) max (rounded up), -], V_Q = S2_Q - S1_Q^2 / |Q|; or nullptr
+    const double* blkq;
 };
 
 struct ImageDev {

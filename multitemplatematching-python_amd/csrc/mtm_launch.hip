@@ -103,6 +103,21 @@ int mfma_row_mux(MfmaParams& p, int R, int nt) {
     return rm_tile_rows(p.h, R);
 }
 
+// The tail screen's split for a launch of class `sc` on route R (MfmaParams::tail_split), 0 = off: hits-only candidate lists of
+// a two-row uint8 class in one K chunk, TM_CCOEFF_NORMED / TM_CCORR_NORMED, a non-negative threshold, neither the fused
+// extremum nor maps in memory - and a threshold the bound can get below.  After the split the tail term of a noise-like
+// window against a template whose structure is spread over its rows is about |Q| / n of the normaliser (|Q|: the odd row's
+// tail, the longer one); the screen is worth running where the threshold clears that by 0.1 (0.5 at 64 x 64: 0.14).
+int tail_split_for(const mtm_ctx* c, const CallRoute& R, const SizeClass& sc) {
+    if (!c->tail_screen || !c->screen_l1 || sc.tail_split <= 0 || sc.r2 != 2 || sc.masked || sc.kernel != MTM_KERNEL_MFMA) return 0;
+    if (!R.cand_on || !R.hits_only || R.ext || R.sparse || R.cand_min || c->chans != 1 || c->dtype != MTM_U8) return 0;
+    if (c->method != MTM_TM_CCOEFF_NORMED && c->method != MTM_TM_CCORR_NORMED) return 0;
+    if (sc.h + 1 > kMfChunkR2 || sc.w > 64) return 0;
+    const double thr_lo = (double)R.cand_thr - 1e-6 * std::max(1.0, std::fabs((double)R.cand_thr));
+    const double tail = (double)(sc.h - sc.tail_split + 1) / (double)sc.h;
+    return thr_lo >= 0.0 && thr_lo - tail >= 0.1 ? sc.tail_split : 0;
+}
+
 // the candidate list (mtm_ctx::cands: a 16-byte header, then the records) a score kernel appends to, `cap` records long
 template <class P>
 void wire_candidates(P& p, const mtm_ctx* c, const CallRoute& R, unsigned long long cap) {
@@ -280,12 +295,21 @@ int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out,
             rsq = c->stats_rsq.as<double>();
         }
         double* blk = nullptr;
+        double* blkq = nullptr;
+        int tail_s = 0;
         // statistic ranges per 16-pixel column block: the hits-only screens of the multi-row and row-multiplexed tilings
         if (c->chans == 1 && ((sc.r2 > 0 && normed) || (sc.rm_R > 0 && (normed || (masked_mfma && method == MTM_TM_CCORR_NORMED))))) {
             st.blk_pitch = (st.pitch + 15) / 16;
-            MTMC(c->stats_blk.ensure(sizeof(double) * 4 * (size_t)st.blk_pitch * oh));
+            // (the tail boxes' records, when the score launch screens its K loop, follow the window's in the same buffer)
+            const size_t nrec = 4 * (size_t)st.blk_pitch * oh;
+            tail_s = tail_split_for(c, R, sc);
+            MTMC(c->stats_blk.ensure(sizeof(double) * nrec * (tail_s ? 2 : 1)));
             blk = c->stats_blk.as<double>();
             st.blk = blk;
+            if (tail_s) {
+                blkq = blk + nrec;
+                st.blkq = blkq;
+            }
         }
         if (b1 > sb0) {
             const dim3 gs((ow + owg - 1) / owg, b1 - sb0);
@@ -308,9 +332,11 @@ int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out,
                 lay.zero16 = c->cands.as<unsigned long long>();
                 R.zero_pending = false;
             }
-            hipLaunchKernelGGL(stats_u8_kernel, gs, dim3(256), 0, c->stats_stream ? c->stats_stream : c->stream, src,
+            // (the tail boxes in an instantiation of their own: every other launch runs the kernel as it was)
+            hipLaunchKernelGGL(blkq ? stats_u8_kernel<true> : stats_u8_kernel<false>, gs, dim3(256), 0,
+                               c->stats_stream ? c->stats_stream : c->stream, src,
                                src_pitch, h, w, oh, ow, owg, inv_area, num_type, normed ? 1 : 0, want_t, want_sum2, tp[0],
-                               sum2, sq, st.pitch, rsq, sb0, blk, st.blk_pitch, lay);
+                               sum2, sq, st.pitch, rsq, sb0, blk, st.blk_pitch, lay, blkq, tail_s);
         }
     } else if (u8 && c->chans == 3 && w <= 768 && 3.0 * w * h * 65025.0 < 4294967296.0 && c->fuse_stats) {
         // RGB: the fused kernel with one scan per channel + one for the squares (sum2 always written:
@@ -792,7 +818,9 @@ static int launch_mfma(mtm_ctx* c, CallRoute& R, const SizeClass& sc, const Stat
     p.n_work = p.nseg * p.nyb * p.ntg;
     // statistics prefetch region: (channels + 2) planes per wave; none for the row-multiplexed tiling (it loads its
     // statistics directly), (mb + 1) / 2 KB per wave for the two-row one (differs by tiling; not decided here)
-    const size_t stat_bytes = rm ? 0 : r2 ? (size_t)kMfRows * ((mb + 1) / 2) * 1024
+    // (tail screen: the tail boxes' records and the templates' tail constants behind them)
+    p.tail_split = (r2 && st.blkq != nullptr && only_li < 0 && !p.seg_skip) ? tail_split_for(c, R, sc) : 0;
+    const size_t stat_bytes = rm ? 0 : r2 ? (size_t)kMfRows * ((mb + 1) / 2) * 1024 + (p.tail_split ? mf_tail_lds_bytes() : 0)
                                           : (size_t)kMfRows * mf_stat_bytes_per_wave(c->chans == 3 ? 3 : 1);
     const bool ext = R.ext;                          // plan_call checked the class
     const size_t lds = mfma_ext_or_staging(p, c, ext, mfma_lds_layout(p, tile_rows, kMfEpiBytesPerWave) + stat_bytes);

@@ -456,6 +456,24 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
         }
     }
 
+    // the tail screen's constants -> LDS behind the tail-box records (MfmaParams::tail_split; ordered like tcl above)
+    if constexpr (R2 && !EXT && (METHOD == MTM_TM_CCORR_NORMED || METHOD == MTM_TM_CCOEFF_NORMED)) {
+        if (mf_opaque_sgpr(p.tail_split) > 0 && tid_i < 16) {
+            MfTailConst* ttl = reinterpret_cast<MfTailConst*>(smem + p.st_off + kMfRows * ((MB + 1) / 2) * 1024 + kMfTailRecBytes);
+            const int li = tg * 16 + tid_i;
+            MfTailConst k;
+            if (li < p.n_list) {
+                const TemplDev& T = td[tlist[li]];
+#pragma unroll
+                for (int r = 0; r < 2; ++r) k.k[r] = T.tail_k[r], k.d[r] = T.tail_d[r], k.g[r] = T.tail_g[r];
+            } else {        // (zero-padded A rows: the bound is hugely negative whatever the statistics are)
+#pragma unroll
+                for (int r = 0; r < 2; ++r) k.k[r] = -1e300, k.d[r] = 0.0, k.g[r] = 0.0;
+            }
+            ttl[tid_i] = k;
+        }
+    }
+
     // window statistics of this wave's 256 pixels -> LDS (LDS-DMA, no registers; drained by the
     // staging barriers below, read back in the epilogue).  Lane L fetches pixels 4L..4L+3.
     constexpr bool kNeedSum2 = MASKED || METHOD == MTM_TM_SQDIFF || METHOD == MTM_TM_SQDIFF_NORMED;
@@ -479,6 +497,16 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
             const double* src = st.blk + ((size_t)yr * st.blk_pitch + bj) * 4 + 2 * (lane & 1);
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sbase + (r0 / 2) * 1024), 16, 0, 0);
         }
+        if (!EXT && mf_opaque_sgpr(p.tail_split) > 0) {
+            // the tail screen's records of the same blocks and rows (StatPlanes::blkq), kMfRows KiB further on
+#pragma unroll
+            for (int r0 = 0; r0 < MB; r0 += 2) {
+                const int yr = min(y0 + MB * wave + min(r0 + (lane >> 5), MB - 1), p.oh - 1);
+                const double* src = st.blkq + ((size_t)yr * st.blk_pitch + bj) * 4 + 2 * (lane & 1);
+                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sbase + kMfRows * ((MB + 1) / 2) * 1024 + (r0 / 2) * 1024),
+                                                 16, 0, 0);
+            }
+        }
     } else if constexpr (C1 && METHOD != kMfRaw && METHOD != kMfU16 && !RM && !R2) {
         typedef const __attribute__((address_space(1))) void* gptr_t;
         typedef __attribute__((address_space(3))) void* lptr_t;
@@ -499,6 +527,7 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
     }
 
     const uint8_t* apack_g = apack + slab_ap + (long long)tg * (R2 ? 1 : MB) * p.group_bytes + (size_t)lane * 16;
+    bool tail_out = false;      // R2: the tail screen ruled out every output of this wave (wave-uniform)
 
     for (int c = 0; c < p.chans; ++c) {
         const uint8_t* plane = p.img + slab_img + c * p.plane;
@@ -583,25 +612,101 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
                     mfma_step2(acc, QA, QB, ar_);                           \
                     __builtin_amdgcn_sched_barrier(0);                      \
                 }
+#define MTM_R2_STEP_LAST(QA, QB, ACUR, APREV)                               \
+                {                                                           \
+                    aptr += 1024;                                           \
+                    loff += p.lds_pitch;                                    \
+                    __builtin_amdgcn_sched_barrier(0);                      \
+                    const v4i ar_[2] = {ACUR, APREV};                       \
+                    mfma_step2(acc, QA, QB, ar_);                           \
+                    __builtin_amdgcn_sched_barrier(0);                      \
+                }
+#define MTM_R2_FIVE()                                                        \
+                MTM_R2_STEP(qx, qy, aA, aC, qx2, qy2, aB)                   \
+                MTM_R2_STEP(qx2, qy2, aB, aA, qx, qy, aC)                   \
+                MTM_R2_STEP(qx, qy, aC, aB, qx2, qy2, aA)                   \
+                MTM_R2_STEP(qx2, qy2, aA, aC, qx, qy, aB)                   \
+                MTM_R2_STEP(qx, qy, aB, aA, qx2, qy2, aC)
                 MTM_R2_LOAD(qx, qy, aA)           // step 0 of the chunk; aC = the step before it
                 int ks = 0;
-                for (; ks + 6 <= ch; ks += 6) {
-                    MTM_R2_STEP(qx, qy, aA, aC, qx2, qy2, aB)
-                    MTM_R2_STEP(qx2, qy2, aB, aA, qx, qy, aC)
-                    MTM_R2_STEP(qx, qy, aC, aB, qx2, qy2, aA)
-                    MTM_R2_STEP(qx2, qy2, aA, aC, qx, qy, aB)
-                    MTM_R2_STEP(qx, qy, aB, aA, qx2, qy2, aC)
-                    MTM_R2_STEP(qx2, qy2, aC, aB, qx, qy, aA)
+                // Tail screen (hits-only, one chunk: MfmaParams::tail_split, a multiple of 6).  After s = tail_split steps
+                // the first row of the wave holds template rows 0 .. s - 1, the second 0 .. s - 2, exactly.  Split the sum
+                // over the rows Q still missing as sum_Q I T = sum_Q (I - mu_Q)(T - tau_Q) + tau_Q S1_Q (mu_Q, tau_Q: their
+                // means over Q) and bound the first term by Cauchy-Schwarz:
+                //   num <= acc_P + K_P + m S1 + (tau_Q - 128) S1_Q + sqrt(V_Q) g_Q,   m = 128 - mean(T) (TM_CCOEFF_NORMED), 128,
+                // K_P = 128 sum(T_P) - 16384 |P|, V_Q = S2_Q - S1_Q^2 / |Q|, g_Q = sqrt(sum_Q (T - tau_Q)^2).  Per lane and
+                // template, over its 16 pixels: max(acc_P) (exact integers), the S1 / S1_Q ranges and the largest sqrt(V_Q)
+                // of the column block - level 1's bound below with the tail added, against level 1's right-hand side.
+                // Rigour: acc_P, S1, S1_Q, |Q| S2_Q - S1_Q^2 are exact integers; sqrt(V_Q) and g_Q are rounded up (stats_u8_kernel,
+                // tail_consts_kernel); the roundings of m, tau_Q - 128 and of the float64 products and sums are covered by
+                // the slack tail_consts_kernel adds to K_P (2^-46 of a bound on every term's magnitude, > 64 times their
+                // worst-case total).  The bound is therefore never below the exact numerator, and against it stands level
+                // 1's right-hand side, screen_hi templ_norm max(sqrt_min, sq_floor), lowered by 1e-6 relative below the
+                // candidate threshold: what that lowering leaves covers the epilogue's own rounding as for level 1.  An
+                // output ruled out scores below cand_thr_lo - the full loop would not have listed it - so the lists are
+                // those of the full loop.  A wave in which no lane passes skips its remaining steps and both screens.
+                const int split = (!EXT && kNormed) ? mf_opaque_sgpr(p.tail_split) : 0;
+                if (split > 0) {
+                    for (; ks + 6 < split; ks += 6) {
+                        MTM_R2_FIVE()
+                        MTM_R2_STEP(qx2, qy2, aC, aB, qx, qy, aA)
+                    }
+                    // the last six steps before the split: the sixth requests nothing ahead (the operands of step s are
+                    // not live across the screen; aC = the A operand of step s - 1, the second row's next one)
+                    MTM_R2_FIVE()
+                    MTM_R2_STEP_LAST(qx2, qy2, aC, aB)
+                    ks += 6;
+                    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+                    bool pass = false;
+                    const uint8_t* sbw = smem + p.st_off + wave * 1024 + j * 32;     // window records, row mb at + mb * 512
+                    const uint8_t* sbq = sbw + kMfRows * 1024;                       // tail-box records
+                    const MfTailConst* ttl = reinterpret_cast<const MfTailConst*>(smem + p.st_off + 2 * kMfRows * 1024);
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb) {
+                        int amax[4] = {INT_MIN, INT_MIN, INT_MIN, INT_MIN};
+#pragma unroll
+                        for (int c = 0; c < 16; ++c) {
+                            const v4i a = acc[mb][c];
+                            amax[0] = max(amax[0], a.x);
+                            amax[1] = max(amax[1], a.y);
+                            amax[2] = max(amax[2], a.z);
+                            amax[3] = max(amax[3], a.w);
+                        }
+                        const double2 s1 = *reinterpret_cast<const double2*>(sbw + mb * 512);
+                        const double sq_eff = fmax(*reinterpret_cast<const double*>(sbw + mb * 512 + 16), p.sq_floor);
+                        const double2 s1q = *reinterpret_cast<const double2*>(sbq + mb * 512);
+                        const double vq = *reinterpret_cast<const double*>(sbq + mb * 512 + 16);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const MfTemplConst& T = tcl[4 * q + e];       // (beyond the list: cannot pass)
+                            const MfTailConst& U = ttl[4 * q + e];
+                            const double m = METHOD == MTM_TM_CCOEFF_NORMED ? T.m128[0] : 128.0;
+                            const double dq = U.d[mb];
+                            const double bound = (((double)amax[e] + U.k[mb]) + fmax(m * s1.x, m * s1.y)) +
+                                                 fmax(dq * s1q.x, dq * s1q.y) + vq * U.g[mb];
+                            pass = pass || T.all_ones != 0 || bound > p.screen_hi * T.templ_norm * sq_eff;
+                        }
+                    }
+                    tail_out = __builtin_amdgcn_ballot_w64(pass) == 0ull;
+                    if (!tail_out) { MTM_R2_LOAD(qx, qy, aA) }        // step s, only now
                 }
-                // remainder (0..5 steps), same rotation; r2_prev = the operand of the chunk's last step
-                r2_prev = aC;
-                if (ks < ch) { MTM_R2_STEP(qx, qy, aA, aC, qx2, qy2, aB) r2_prev = aA; }
-                if (ks + 1 < ch) { MTM_R2_STEP(qx2, qy2, aB, aA, qx, qy, aC) r2_prev = aB; }
-                if (ks + 2 < ch) { MTM_R2_STEP(qx, qy, aC, aB, qx2, qy2, aA) r2_prev = aC; }
-                if (ks + 3 < ch) { MTM_R2_STEP(qx2, qy2, aA, aC, qx, qy, aB) r2_prev = aA; }
-                if (ks + 4 < ch) { MTM_R2_STEP(qx, qy, aB, aA, qx2, qy2, aC) r2_prev = aB; }
+                if (!tail_out) {
+                    for (; ks + 6 <= ch; ks += 6) {
+                        MTM_R2_FIVE()
+                        MTM_R2_STEP(qx2, qy2, aC, aB, qx, qy, aA)
+                    }
+                    // remainder (0..5 steps), same rotation; r2_prev = the operand of the chunk's last step
+                    r2_prev = aC;
+                    if (ks < ch) { MTM_R2_STEP(qx, qy, aA, aC, qx2, qy2, aB) r2_prev = aA; }
+                    if (ks + 1 < ch) { MTM_R2_STEP(qx2, qy2, aB, aA, qx, qy, aC) r2_prev = aB; }
+                    if (ks + 2 < ch) { MTM_R2_STEP(qx, qy, aC, aB, qx2, qy2, aA) r2_prev = aC; }
+                    if (ks + 3 < ch) { MTM_R2_STEP(qx2, qy2, aA, aC, qx, qy, aB) r2_prev = aA; }
+                    if (ks + 4 < ch) { MTM_R2_STEP(qx, qy, aB, aA, qx2, qy2, aC) r2_prev = aB; }
+                }
 #undef MTM_R2_LOAD
 #undef MTM_R2_STEP
+#undef MTM_R2_STEP_LAST
+#undef MTM_R2_FIVE
                 asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
                 __builtin_amdgcn_s_setprio(0);
             } else if constexpr (KP) {
@@ -1424,11 +1529,11 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
         //      operations per accumulator register.
         // Only if level 2 still sees a possible candidate does the wave run the full epilogue below, which
         // repeats the exact test.  Results are therefore those of the full epilogue.
-        bool wave_has_work = true;
+        bool wave_has_work = !tail_out;     // (ruled out by the tail screen: nothing more to test)
         if constexpr (CH == 1 && !MASKED && (METHOD == MTM_TM_CCORR_NORMED || METHOD == MTM_TM_CCOEFF_NORMED)) {
             // (quotients <= -1 saturate to -1 or 0, which can only be candidates below a negative threshold:
             // such calls skip the screen instead of tracking the minima as well)
-            if ((p.hits_only || (!EXT && p.seg_skip)) && (EXT || p.cand_thr_lo >= 0.0)) {
+            if (!tail_out && (p.hits_only || (!EXT && p.seg_skip)) && (EXT || p.cand_thr_lo >= 0.0)) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 const uint8_t* sw0 = smem + p.st_off + wave * (R2 ? MB * 4 * 1024 : mf_stat_bytes_per_wave(1));
                 bool pass1 = false;

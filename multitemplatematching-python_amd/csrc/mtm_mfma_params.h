@@ -137,6 +137,12 @@ struct MfmaParams {
     // ended, without a fetch kernel / copy command and its kernel boundary behind the score launch.  0 = off.
     mtm_hit* cand_pin;
     unsigned long long cand_pin_n;
+    // Tail screen (two-row variant, hits-only, one K chunk; 0 = off): after tail_split K steps every lane bounds the scores
+    // its outputs can still reach from the exact partial sums, the Q-box statistics (StatPlanes::blkq, in LDS at
+    // st_off + kMfRows * 1024) and the templates' tail constants (MfTailConst, behind them); a wave none of whose lanes can
+    // reach the threshold skips the rest of its K loop and both screens.  A multiple of 6 (the loop's operand rotation).
+    int tail_split;
+    int tail_pad_;
 };
 
 // one record of the candidate list: device list (slots below the capacity) + the host-visible window
@@ -159,6 +165,14 @@ struct MfTemplConst {
     unsigned ext_hi;         //   lowered by 1e-6 relative; high word of its key (0: none yet)
     int flag_base;           // first byte of this template's row-segment flags (MfmaParams::seg_flags)
 };
+// The tail screen's constants of a work item's 16 templates (TemplDev::tail_*; beyond the list: constants that cannot pass),
+// staged in LDS behind the tail-box records - only by launches with MfmaParams::tail_split > 0 (mf_tail_lds_bytes).
+struct MfTailConst {
+    double k[2], d[2], g[2];
+};
+// LDS of the tail screen per work-group: the tail-box records (kMfRows waves x 1 KiB) and 16 templates' constants
+constexpr int kMfTailRecBytes = kMfRows * 1024;
+constexpr int mf_tail_lds_bytes() { return kMfTailRecBytes + 16 * (int)sizeof(MfTailConst); }
 
 // One instantiation of ncc_mfma_kernel (defined in the mtm_mfma_*.hip units).
 using MfmaFn = void (*)(MfmaParams, const TemplDev*, const int*, const uint8_t*, StatPlanes, float*);

@@ -180,4 +180,52 @@ __global__ void gather_unit_kernel(const uint8_t* __restrict__ arena, UnitSrc u,
     if (mask != nullptr) mask[o] = u.moff >= 0 ? (uint8_t)unit_mask(arena, u, c, y, x) : 0;
 }
 
+// Tail constants of the two-row MFMA variant's tail screen (TemplDev::tail_*), from the class's packed A operands - the
+// same bytes the K loop multiplies, wherever the templates were packed.  One work-group of 64 per list position li of the
+// class (template tl[li]); thread r sums template row r.  Group layout (one channel, one 64-tap block, w <= 64):
+// byte ((dy * 64 + 16 (x / 16) + li % 16) * 16 + x % 16) of group li / 16 holds T[dy][x] ^ 0x80.  Integer sums are exact;
+// row [0]: the tail Q = template rows s .. h - 1 (the wave's first output row after s K steps), [1]: rows s - 1 .. h - 1.
+//   tail_k = K_P + slack, K_P = 128 sum(T_P) - 16384 |P|   (P: the rows accumulated; |P|, |Q| count taps)
+//   tail_d = sum(T_Q) / |Q| - 128
+//   tail_g = sqrt((|Q| sum(T_Q^2) - sum(T_Q)^2) / |Q|), rounded up
+// The slack (2^-46 of a bound on the magnitudes of every term of the kernel's float64 bound, far below one unit of the
+// integer sums) makes the computed bound an upper bound of the exact one despite its roundings (see ncc_mfma_kernel).
+constexpr int kTailMaxRows = 128;     // (the launcher takes h + 1 <= kMfChunkR2)
+__global__ __launch_bounds__(64) void tail_consts_kernel(const uint8_t* __restrict__ apack, long long group_bytes, int h, int w,
+                                                         int split, const int* __restrict__ tl, TemplDev* __restrict__ td) {
+    __shared__ long long rs[kTailMaxRows][2];
+    const int li = blockIdx.x, r = threadIdx.x;
+    const uint8_t* g = apack + (size_t)(li / 16) * group_bytes;
+    for (int y = r; y < h; y += 64) {
+        long long s = 0, s2 = 0;
+        for (int x = 0; x < w; ++x) {
+            const long long v = g[((size_t)y * 64 + 16 * (x / 16) + li % 16) * 16 + x % 16] ^ 0x80;
+            s += v;
+            s2 += v * v;
+        }
+        rs[y][0] = s;
+        rs[y][1] = s2;
+    }
+    __syncthreads();
+    if (r >= 2) return;
+    const int q0 = r == 0 ? split : split - 1;          // first tail row
+    long long sall = 0, sq = 0, s2q = 0;
+    for (int y = 0; y < h; ++y) {
+        sall += rs[y][0];
+        if (y >= q0) {
+            sq += rs[y][0];
+            s2q += rs[y][1];
+        }
+    }
+    const long long nq = (long long)(h - q0) * w, np = (long long)q0 * w, n = (long long)h * w;
+    const double kp = 128.0 * (double)(sall - sq) - 16384.0 * (double)np;
+    const double d = (double)sq / (double)nq - 128.0;
+    const double gg = sqrt((double)(nq * s2q - sq * sq) / (double)nq) * (1.0 + 0x1p-49);
+    const double mag = 4294967296.0 + fabs(kp) + 2.0 * 128.0 * 255.0 * (double)n + gg * 128.0 * sqrt((double)nq);
+    TemplDev& t = td[tl[li]];
+    t.tail_k[r] = kp + mag * 0x1p-46;
+    t.tail_d[r] = d;
+    t.tail_g[r] = gg;
+}
+
 }  // namespace mtm

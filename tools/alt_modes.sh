@@ -5,7 +5,7 @@
 # Exit status: 0 if every switch passed, 1 if some had failures; a run that timed out or died of a signal (abort,
 # segmentation fault, kill: 124, 134, 137, 139, ...) ends the script at once with its status - nothing more is started on
 # a GPU that may be in a bad state.
-DEFAULT_MODES="X=0 MTM_FUSE_LAYOUT=0 MTM_CAND_PINNED=0 MTM_SEG_SKIP=0 MTM_ROW_MUX=0 MTM_HITS_ONLY=0 MTM_EXACT_DIV=0 MTM_EXACT_DIV=2 MTM_FUSE_STATS=0 MTM_KERNEL=dot4 MTM_MFMA_R2=0 MTM_SCREEN_L1=0 MTM_F32_MFMA=2 MTM_F32_MFMA=3 MTM_F32_MFMA=0 MTM_TEMPL_ON_DEVICE=0 MTM_UPLOAD_BANDS=1 MTM_CLASS_LANES=1 MTM_CLASS_LANES=4 MTM_BAND_MIN_FILL=0 MTM_MASKSQ_FUSED=0 MTM_SPARSE_MAPS=0 MTM_NMS_DEVICE_MIN=-1"
+DEFAULT_MODES="X=0 MTM_FUSE_LAYOUT=0 MTM_CAND_PINNED=0 MTM_SEG_SKIP=0 MTM_ROW_MUX=0 MTM_HITS_ONLY=0 MTM_EXACT_DIV=0 MTM_EXACT_DIV=2 MTM_FUSE_STATS=0 MTM_KERNEL=dot4 MTM_MFMA_R2=0 MTM_SCREEN_L1=0 MTM_TAIL_SCREEN=0 MTM_F32_MFMA=2 MTM_F32_MFMA=3 MTM_F32_MFMA=0 MTM_TEMPL_ON_DEVICE=0 MTM_UPLOAD_BANDS=1 MTM_CLASS_LANES=1 MTM_CLASS_LANES=4 MTM_BAND_MIN_FILL=0 MTM_MASKSQ_FUSED=0 MTM_SPARSE_MAPS=0 MTM_NMS_DEVICE_MIN=-1"
 status=0
 # ALT_MODES: a subset of the switches (space separated) instead of all of them
 for e in ${ALT_MODES:-$DEFAULT_MODES}; do

@@ -30,8 +30,8 @@ extern "C" {
 #endif
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
- * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods - are new symbols only and left it at 9: a caller built against an older 9
- * finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd - are new symbols only and left
+ * it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -396,6 +396,17 @@ int mtm_find_matches_boxes(mtm_ctx* ctx, const void* px, int rows, int cols, int
 int mtm_track_boxes(mtm_ctx* ctx, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
                     int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min,
                     double min_score, mtm_hit* out);
+
+/* mtm_track_boxes with the 3 x 3 score neighbourhood of every record: the same arguments, checks, errors,
+ * records and afterwards-state, and nbhd[9 (f * n_tracks + k) + 3 (1 + dy) + (1 + dx)] = the score of track k's template
+ * at window (x + dx, y + dy) of frame f's own score map, (x, y) being the record out[f * n_tracks + k], NaN for a window
+ * outside that map - what mtm_hit_neighbourhoods returns for that record on frame f, bit for bit.  The neighbourhoods are
+ * scored while the frame is on the device: no frame crosses PCIe twice and the host still waits once.  They do not steer
+ * the tracks: the regions follow the records.  nbhd: 9 * n_frames * n_tracks floats, required when both counts are
+ * positive. */
+int mtm_track_boxes_nbhd(mtm_ctx* ctx, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                         int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min,
+                         double min_score, mtm_hit* out, float* nbhd);
 
 /* The 3 x 3 score neighbourhoods of n points in one call: out[9 k + 3 (1 + dy) + (1 + dx)] = the score of
  * template pts[k].templ_idx at window (x + dx, y + dy) of the image's score map, NaN for a window outside the map.  Image:

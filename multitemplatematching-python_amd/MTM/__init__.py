@@ -511,11 +511,11 @@ class TemplateMatcher:
             self._uploaded_for = (str(image.dtype), 1 if image.ndim == 2 else image.shape[2]) if uploaded else before
         return hits
 
-    def track(self, frames, tracks, margin: int, min_score=None) -> List[List[List[Hit]]]:
+    def track(self, frames, tracks, margin: int, min_score=None, *, refine: bool = False) -> List[List[List[Hit]]]:
         """
-        ``trackTemplates(listTemplates, frames, tracks, margin, method, min_score)`` with this matcher's list and method: the
-        same hits and exceptions, on this matcher's context with its templates resident across calls.  Scope as
-        trackTemplates', for every template of the list.
+        ``trackTemplates(listTemplates, frames, tracks, margin, method, min_score, refine=refine)`` with this matcher's list
+        and method: the same hits and exceptions, on this matcher's context with its templates resident across calls.
+        Scope as trackTemplates', for every template of the list.
         """
         from . import tracking
         self._not_streaming()
@@ -523,7 +523,7 @@ class TemplateMatcher:
             # as match_boxes: until the call returns, nothing is known to be resident
             before, self._uploaded_for = self._uploaded_for, None
             hits, f0, uploaded = tracking._track(self.listTemplates, frames, tracks, margin, self.method, min_score,
-                                                 self._ctx, True)
+                                                 self._ctx, True, refine)
             self._uploaded_for = (str(f0.dtype), 1 if f0.ndim == 2 else f0.shape[2]) if uploaded else before
         return hits
 

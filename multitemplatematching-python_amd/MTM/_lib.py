@@ -118,6 +118,9 @@ SYMBOLS = {
     "mtm_track_boxes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
+    "mtm_track_boxes_nbhd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_hit_neighbourhoods": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
@@ -499,9 +502,18 @@ class Context(_RecordMemo):
         """The current templates tracked through frames of one shape and dtype in one native call (mtm_track_boxes).
         `units`: BOX_UNIT_DTYPE records, each track's template and frame-0 region.  Returns the len(frames) * len(units)
         records, frame-major (frame coordinates, templ_idx = the track's template)."""
+        return self._track_boxes(frames, units, margin, min_score, False)[0]
+
+    def track_boxes_nbhd(self, frames, units, margin, min_score=None):
+        """track_boxes with every record's 3 x 3 score neighbourhood in its own frame's map, in the same native call
+        (mtm_track_boxes_nbhd): (records, (len(frames) * len(units), 3, 3) float32 array, element [i, 1 + dy, 1 + dx] the
+        score at window (x + dx, y + dy) of record i, NaN outside the map) - hit_neighbourhoods of each frame's records."""
+        return self._track_boxes(frames, units, margin, min_score, True)
+
+    def _track_boxes(self, frames, units, margin, min_score, with_nbhd):
         n, nt = len(frames), len(units)
         if n == 0 or nt == 0:
-            return np.zeros(0, dtype=HIT_DTYPE)
+            return np.zeros(0, dtype=HIT_DTYPE), (np.zeros((0, 3, 3), dtype=np.float32) if with_nbhd else None)
         rows = [_pixel_rows(a) for a in frames]
         if len({r[2] for r in rows}) > 1:       # (one row stride for every frame)
             rows = [_pixel_rows(np.ascontiguousarray(a)) for a in frames]
@@ -511,10 +523,14 @@ class Context(_RecordMemo):
         units = np.ascontiguousarray(units, dtype=BOX_UNIT_DTYPE)
         out = np.empty(n * nt, dtype=HIT_DTYPE)
         use_min = min_score is not None
-        check(self._lib.mtm_track_boxes(self._h, ptrs, n, a0.shape[0], a0.shape[1], chans, _dtype_code(a0), stride,
-                                        units.ctypes.data, nt, int(margin), int(use_min),
-                                        float(min_score) if use_min else 0.0, out.ctypes.data), "mtm_track_boxes")
-        return out
+        args = (self._h, ptrs, n, a0.shape[0], a0.shape[1], chans, _dtype_code(a0), stride, units.ctypes.data, nt,
+                int(margin), int(use_min), float(min_score) if use_min else 0.0, out.ctypes.data)
+        if not with_nbhd:
+            check(self._lib.mtm_track_boxes(*args), "mtm_track_boxes")
+            return out, None
+        nbhd = np.empty((n * nt, 3, 3), dtype=np.float32)
+        check(self._lib.mtm_track_boxes_nbhd(*args, nbhd.ctypes.data), "mtm_track_boxes_nbhd")
+        return out, nbhd
 
     def hit_neighbourhoods(self, image, points):
         """The 3 x 3 score neighbourhoods of `points` (POINT_DTYPE records: a template of the current set and a window of

@@ -11,6 +11,17 @@ with the same hits, labels, boxes, float32 score bits, exceptions and warnings, 
 (mtm_track_boxes): the frames go up in chunks, and the next frame's search boxes are computed on the GPU from
 this frame's hits, so the host waits once per call instead of twice per frame.
 
+``refine=True`` returns every hit at its sub-pixel position, element ``[f][k]`` being exactly
+
+    refineHits(listTemplates, frames[f], trackTemplates(..., refine=False)[f][k], method)
+
+- ``[(label, (x + ox, y + oy, w, h), score)]`` with float ``x + ox``, ``y + oy`` - from the same native call
+(mtm_track_boxes_nbhd): each frame's 3 x 3 score neighbourhoods are computed while the frame is on the device, and one
+``subpixel.fit_offsets`` call fits them all.  The hit's template is the track's own ``listTemplates[j]``.  The refined
+positions do not steer the tracks (the next box is ``next_box`` of the integer hit), a hit that fails ``min_score`` is
+refined like any other, and the exceptions and warnings are those of the unrefined call.  ``positions`` turns either kind
+of result into an (F, T, 2) array of trajectories.
+
 A track is a pair ``((x, y, w, h), j)``: template ``listTemplates[j]``, searched in that box in frame 0 and around its
 last hit afterwards (``next_box``).
 
@@ -25,10 +36,10 @@ from typing import List
 
 import numpy as np
 
-from . import _lib, boxes
+from . import _lib, boxes, subpixel
 from . import _MSG_MASK_UNSUPPORTED, Hit, TM_CCOEFF_NORMED
 
-__all__ = ["trackTemplates", "next_box"]
+__all__ = ["trackTemplates", "next_box", "positions"]
 
 
 def next_box(box, hit, margin, image_shape, method, min_score=None):
@@ -67,19 +78,21 @@ def _frames(frames):
     return fl
 
 
-def _check_args(margin, min_score):
+def _check_args(margin, min_score, refine=False):
     if not isinstance(margin, numbers.Integral) or isinstance(margin, bool) or margin < 0:
         raise ValueError("margin must be an integer >= 0 (got %r)" % (margin,))
     if min_score is not None and (not isinstance(min_score, numbers.Real) or isinstance(min_score, bool)):
         raise ValueError("min_score must be a number or None (got %r)" % (min_score,))
+    if not isinstance(refine, bool):
+        raise ValueError("refine must be True or False (got %r)" % (refine,))
 
 
-def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, resident):
+def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, resident, refine=False):
     """trackTemplates on `ctx`.  `resident`: the context holds every template of listTemplates in list order
     (TemplateMatcher); otherwise the templates the tracks use are set now.  Returns (hits per frame and track, the first
     frame or None, whether templates were set on the context)."""
     fl = _frames(frames)
-    _check_args(margin, min_score)
+    _check_args(margin, min_score, refine)
     regions = [(b, [j]) for b, j in tracks]         # (the loop's unpacking of the pairs, and its errors)
     if not fl:
         return [], None, False
@@ -107,23 +120,47 @@ def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, reside
     ctx = ctx or _lib.default_context()         # (only now: every argument error comes before "no GPU")
     with ctx.lock:
         ctx.set_templates(templates, method)
-        raw = ctx.track_boxes(fl, units, m, min_score)
+        if refine:
+            raw, nbhd = ctx.track_boxes_nbhd(fl, units, m, min_score)
+        else:
+            raw = ctx.track_boxes(fl, units, m, min_score)
     tidx = raw["templ_idx"] if used is None else used[raw["templ_idx"]]
     labels = boxes._labels(listTemplates)
     xywh = zip(raw["x"].tolist(), raw["y"].tolist(), raw["w"].tolist(), raw["h"].tolist())
     hits = list(zip(labels[tidx].tolist(), xywh, list(raw["score"])))
+    if refine:          # (one fit over every record: refineHits' numbers by construction)
+        hits = subpixel._refined(hits, nbhd, method)
     T = len(units)
     return [[[hits[f * T + k]] for k in range(T)] for f in range(len(fl))], f0, True
 
 
 def trackTemplates(listTemplates, frames, tracks, margin: int, method: int = TM_CCOEFF_NORMED, min_score=None, *,
-                   context=None) -> List[List[List[Hit]]]:
+                   refine: bool = False, context=None) -> List[List[List[Hit]]]:
     """
     Follow each track through ``frames`` (a sequence of arrays of one shape and dtype, or one ``(F, H, W[, C])`` array):
     element ``[f][k]`` is what ``findMatchesInBoxes(listTemplates, frames[f], ..., method, N_object=1)`` returns for track
     k - ``[hit]`` - in the loop of this module's docstring, where each frame's search box is ``next_box`` of the previous
     frame's hit.  ``tracks``: pairs ``((x, y, w, h), j)``, template ``listTemplates[j]`` starting from that box in frame
-    0.  ``min_score``: a hit that does not pass it (``next_box``) leaves its track's box where it was.  ``context``: the
-    _lib.Context to run on (default: the process's).
+    0.  ``min_score``: a hit that does not pass it (``next_box``) leaves its track's box where it was.  ``refine``
+    (True / False): every hit at its sub-pixel position, ``refineHits(listTemplates, frames[f], [hit], method)`` of the
+    unrefined call's hit, from the same native call (the module's docstring).  ``context``: the _lib.Context to run on
+    (default: the process's).
     """
-    return _track(listTemplates, frames, tracks, margin, method, min_score, context, False)[0]
+    return _track(listTemplates, frames, tracks, margin, method, min_score, context, False, refine)[0]
+
+
+def positions(result) -> np.ndarray:
+    """The trajectories of a trackTemplates / TemplateMatcher.track result, refined or not: an (F, T, 2) float64 array,
+    element ``[f, k]`` the ``(x, y)`` of track k's hit in frame f.  ValueError when some ``[f][k]`` does not hold exactly
+    one hit, or when the frames differ in their number of tracks."""
+    result = list(result)
+    n_tracks = len(result[0]) if result else 0
+    out = np.empty((len(result), n_tracks, 2), dtype=np.float64)
+    for f, row in enumerate(result):
+        if len(row) != n_tracks:
+            raise ValueError("positions: frame %d holds %d tracks, frame 0 holds %d" % (f, len(row), n_tracks))
+        for k, hits in enumerate(row):
+            if len(hits) != 1:
+                raise ValueError("positions: frame %d, track %d holds %d hits, not one" % (f, k, len(hits)))
+            out[f, k, 0], out[f, k, 1] = hits[0][1][0], hits[0][1][1]
+    return out

@@ -388,8 +388,8 @@ struct mtm_ctx {
     DevBuf box_td, box_units, box_tiles;
     int64_t boxes_max_floats = 1ll << 26;
     // mtm_track_boxes (mtm_track.hip): the per-call track table (rewritten on the device every frame), tile table, extremum
-    // keys and records.
-    DevBuf trk_units, trk_tiles, trk_keys, trk_out;
+    // keys and records; mtm_track_boxes_nbhd: the records' 3 x 3 neighbourhoods (nine floats per record).
+    DevBuf trk_units, trk_tiles, trk_keys, trk_out, trk_nbhd;
     // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
     // template set sub_gen) and the per-call point table and scores.
     uint64_t sub_gen = 0;

@@ -11,15 +11,12 @@
 //     mtm_score_map to rounding (1e-6 relative), not bit for bit; flat windows (normalisation guard) may differ outright.
 #include "mtm_ctx.h"
 #include "mtm_device_util.hip.h"
-#include "mtm_k_window.hip.h"
+#include "mtm_k_nbhd.hip.h"
 
 using namespace mtm;
 using namespace mtmi;
 
 namespace mtm {
-
-// Kinds of a launch: the image's pixel type and whether its templates carry masks.
-enum SubKind { kSubU8 = 0, kSubU8Mask = 1, kSubU16 = 2, kSubF32 = 3, kSubF32Mask = 4 };
 
 // A template as the neighbourhood kernel reads it: its epilogue constants and where its operands are.
 //   px_off: bytes in the byte arena - uint8: planar [C][h][w] of T (masked: T * M, M binary), uint16: the high-byte plane
@@ -35,33 +32,10 @@ struct SubPoint {
     int t, x, y;
 };
 
-constexpr int kSubR = kWinKR, kSubC = kWinKC;       // template chunk: rows x columns (one 4-pixel quad per thread)
-constexpr int kSubLdsW = (kSubC + 8) / 4;           // dwords per LDS image row: kSubC + 2 bytes and the alignbyte reach
-constexpr int kSubLdsR = kSubR + 2;                 // LDS image rows
 constexpr int kSubFW = kSubC + 2;                   // floats per LDS image row (float32)
 constexpr size_t kSubLaunchPoints = (size_t)1 << 22; // most work-groups (points) of one launch
-static_assert(kSubR * (kSubC / 4) == 256, "one template quad per thread and chunk");
 
-typedef uint32_t SubImageLds[kSubLdsR][kSubLdsW];
 typedef float SubImageLdsF[kSubLdsR][kSubFW];
-
-// Image rows y0 .. y0 + kSubLdsR - 1, columns x0 .. of one byte plane into LDS (zero outside rows x cols; y0 and x0 may be
-// -1); every byte XOR `bias`.
-__device__ __forceinline__ void sub_load_image(SubImageLds& Il, const uint8_t* __restrict__ ip, int pitch, int rows, int cols,
-                                               int y0, int x0, uint32_t bias, int tid) {
-    for (int k = tid; k < kSubLdsR * kSubLdsW; k += 256) {
-        const int i = k / kSubLdsW, j = (k % kSubLdsW) * 4;
-        const int y = y0 + i;
-        uint32_t v = 0u;
-        if (y >= 0 && y < rows)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int x = x0 + j + b;
-                if (x >= 0 && x < cols) v |= ((uint32_t)ip[(size_t)y * pitch + x] ^ bias) << (8 * b);
-            }
-        Il[i][j >> 2] = v;
-    }
-}
 
 __device__ __forceinline__ void sub_load_image_f(SubImageLdsF& Il, const float* __restrict__ ip, int pitch, int rows, int cols,
                                                  int y0, int x0, int tid) {
@@ -72,32 +46,10 @@ __device__ __forceinline__ void sub_load_image_f(SubImageLdsF& Il, const float* 
     }
 }
 
-// Bytes j + d .. j + d + 3 of LDS row `irow` (j a multiple of 4, d in 0..2), the bytes past the chunk's last template
-// column (nj) masked off.
-__device__ __forceinline__ uint32_t sub_quad(const uint32_t* irow, int j, int d, int nj) {
-    const int q = (j + d) >> 2;
-    uint32_t v = __builtin_amdgcn_alignbyte(irow[q + 1], irow[q], d);
-    if (nj - j < 4) v &= (1u << (8 * (nj - j))) - 1u;
-    return v;
-}
-
-// Wave-then-work-group sum of `v` in a fixed order (xor butterfly, then the four waves in order): identical run to run.
-// The result is valid in every thread.  `red` holds one slot per wave.
-template <typename T>
-__device__ __forceinline__ T sub_reduce(T v, T* red) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    const int tid = threadIdx.x;
-    __syncthreads();                    // the previous reduction's reads of `red` are done
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// Grid: one 256-thread work-group per point (launch slice).  Each chunk of kSubR x kSubC template pixels gives every thread
-// one 4-pixel quad (uint8 / uint16) or four pixels (float32) of it; the thread adds their products with the nine windows'
-// image pixels, staged in LDS as the chunk's (kSubR + 2) x (kSubC + 2) patch, to its own nine correlations and window sums.
-// Integer sums are exact in uint64; the work-group's sums are reduced in a fixed order and threads 0 .. 8 finish window
+// Grid: one 256-thread work-group per point (launch slice).  uint8 / uint16: sub_nbhd_int (mtm_k_nbhd.hip.h).  float32:
+// each chunk of kSubR x kSubC template pixels gives every thread four pixels of it; the thread adds their products with the
+// nine windows' image pixels, staged in LDS as the chunk's (kSubR + 2) x (kSubC + 2) patch, to its own nine correlations
+// and window sums in float64; the work-group's sums are reduced in a fixed order and threads 0 .. 8 finish window
 // (dy, dx) = (k / 3 - 1, k % 3 - 1).
 template <int CH, int KIND>
 __global__ __launch_bounds__(256) void sub_nbhd_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
@@ -105,86 +57,39 @@ __global__ __launch_bounds__(256) void sub_nbhd_kernel(ImageDev img, const uint8
                                                        const SubTempl* __restrict__ st, const SubPoint* __restrict__ pts,
                                                        float* __restrict__ out, int method) {
     constexpr bool kInt = KIND == kSubU8 || KIND == kSubU8Mask || KIND == kSubU16;
-    constexpr bool kMasked = KIND == kSubU8Mask || KIND == kSubF32Mask;
-    constexpr int kS1 = kMasked ? 0 : CH;       // window sums per channel (unmasked only)
-    using Acc = typename std::conditional<kInt, unsigned long long, double>::type;
-    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[KIND == kSubU8 ? 1 : kInt ? 2 : 1];
-    __shared__ __attribute__((aligned(16))) SubImageLds Il[KIND == kSubU16 ? 2 : 1];
-    __shared__ __attribute__((aligned(16))) SubImageLdsF If[1];
-    __shared__ Acc red[4];
     const SubPoint P = pts[blockIdx.x];
     const SubTempl S = st[P.t];
-    const int h = S.T.rows, w = S.T.cols;
     const int tid = threadIdx.x;
-    // the nine windows' correlations (masked: sum I T M^2), second sums (sum I^2, masked: sum I^2 M^2) and per-channel sums
-    Acc corr[9], s2[9], s1[9][kS1 > 0 ? kS1 : 1];
+    if constexpr (kInt) {
+        __shared__ __attribute__((aligned(16))) WinTemplLds Tl[KIND == kSubU8 ? 1 : 2];
+        __shared__ __attribute__((aligned(16))) SubImageLds Il[KIND == kSubU16 ? 2 : 1];
+        __shared__ unsigned long long red[4];
+        const float score = sub_nbhd_int<CH, KIND>(Tl, Il, red, img.u8, img.u8_plane, lo_b, img.u8_pitch, img.rows, img.cols,
+                                                   bytes + S.px_off, bytes + S.mk_off, S.T, P.x, P.y, method);
+        if (tid < 9) out[(size_t)blockIdx.x * 9 + tid] = score;
+    } else {
+        constexpr bool kMasked = KIND == kSubF32Mask;
+        constexpr int kS1 = kMasked ? 0 : CH;       // window sums per channel (unmasked only)
+        __shared__ __attribute__((aligned(16))) SubImageLdsF If[1];
+        __shared__ double red[4];
+        const int h = S.T.rows, w = S.T.cols;
+        // the nine windows' correlations (masked: sum I T M^2), second sums (sum I^2, masked: sum I^2 M^2) and per-channel
+        // sums
+        double corr[9], s2[9], s1[9][kS1 > 0 ? kS1 : 1];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        corr[k] = 0;
-        s2[k] = 0;
+        for (int k = 0; k < 9; ++k) {
+            corr[k] = 0;
+            s2[k] = 0;
 #pragma unroll
-        for (int c = 0; c < (kS1 > 0 ? kS1 : 1); ++c) s1[k][c] = 0;
-    }
-    const int oy = P.y - 1, ox = P.x - 1;       // image pixel of LDS patch (0, 0) for template pixel (r0, c0)
+            for (int c = 0; c < (kS1 > 0 ? kS1 : 1); ++c) s1[k][c] = 0;
+        }
+        const int oy = P.y - 1, ox = P.x - 1;       // image pixel of LDS patch (0, 0) for template pixel (r0, c0)
 #pragma unroll
-    for (int c = 0; c < CH; ++c) {
-        for (int r0 = 0; r0 < h; r0 += kSubR)
-            for (int c0 = 0; c0 < w; c0 += kSubC) {
-                const int ni = min(kSubR, h - r0), nj = min(kSubC, w - c0);
-                __syncthreads();                // the previous chunk's LDS reads are done
-                if constexpr (kInt) {
-                    const uint8_t* tp = bytes + S.px_off;
-                    if constexpr (KIND == kSubU16) {
-                        win_load_templ(Tl[0], tp, h, w, r0, c0, tid);
-                        win_load_templ(Tl[1], tp + (size_t)h * w, h, w, r0, c0, tid);
-                        sub_load_image(Il[0], img.u8, img.u8_pitch, img.rows, img.cols, oy + r0, ox + c0, 0u, tid);
-                        sub_load_image(Il[KIND == kSubU16 ? 1 : 0], lo_b, img.u8_pitch, img.rows, img.cols, oy + r0, ox + c0,
-                                       0x80u, tid);
-                    } else {
-                        win_load_templ(Tl[0], tp + (size_t)c * h * w, h, w, r0, c0, tid);
-                        if constexpr (KIND == kSubU8Mask)
-                            win_load_templ(Tl[1], bytes + S.mk_off + (size_t)c * h * w, h, w, r0, c0, tid);
-                        sub_load_image(Il[0], img.u8 + c * img.u8_plane, img.u8_pitch, img.rows, img.cols, oy + r0, ox + c0,
-                                       0u, tid);
-                    }
-                    __syncthreads();
-                    const int i = tid / (kSubC / 4), j = (tid % (kSubC / 4)) * 4;
-                    if (i < ni && j < nj) {
-                        const uint32_t t0 = Tl[0][i][j >> 2];
-                        const uint32_t t1 = Tl[KIND == kSubU8 ? 0 : 1][i][j >> 2];
-#pragma unroll
-                        for (int dy = 0; dy < 3; ++dy) {
-                            const uint32_t* r = &Il[0][i + dy][0];
-                            const uint32_t* rl = &Il[KIND == kSubU16 ? 1 : 0][i + dy][0];
-#pragma unroll
-                            for (int dx = 0; dx < 3; ++dx) {
-                                const int k = dy * 3 + dx;
-                                const uint32_t v = sub_quad(r, j, dx, nj);
-                                if constexpr (KIND == kSubU8) {
-                                    corr[k] += __builtin_amdgcn_udot4(v, t0, 0u, false);
-                                    s1[k][c < kS1 ? c : 0] += __builtin_amdgcn_udot4(v, 0x01010101u, 0u, false);
-                                    s2[k] += __builtin_amdgcn_udot4(v, v, 0u, false);
-                                } else if constexpr (KIND == kSubU8Mask) {
-                                    const uint32_t vm = v & t1;                 // I M (M binary: bytes 0xFF / 0x00)
-                                    corr[k] += __builtin_amdgcn_udot4(v, t0, 0u, false);
-                                    s2[k] += __builtin_amdgcn_udot4(vm, vm, 0u, false);
-                                } else {                                         // uint16: I = 256 Ih + Il, T = 256 Th + Tl
-                                    const uint32_t vl = sub_quad(rl, j, dx, nj);
-                                    const unsigned long long hh = __builtin_amdgcn_udot4(v, t0, 0u, false);
-                                    const unsigned long long hl = __builtin_amdgcn_udot4(v, t1, 0u, false);
-                                    const unsigned long long lh = __builtin_amdgcn_udot4(vl, t0, 0u, false);
-                                    const unsigned long long ll = __builtin_amdgcn_udot4(vl, t1, 0u, false);
-                                    corr[k] += (hh << 16) + ((hl + lh) << 8) + ll;
-                                    s1[k][0] += ((unsigned long long)__builtin_amdgcn_udot4(v, 0x01010101u, 0u, false) << 8) +
-                                                __builtin_amdgcn_udot4(vl, 0x01010101u, 0u, false);
-                                    s2[k] += ((unsigned long long)__builtin_amdgcn_udot4(v, v, 0u, false) << 16) +
-                                             ((unsigned long long)__builtin_amdgcn_udot4(v, vl, 0u, false) << 9) +
-                                             __builtin_amdgcn_udot4(vl, vl, 0u, false);
-                                }
-                            }
-                        }
-                    }
-                } else {
+        for (int c = 0; c < CH; ++c) {
+            for (int r0 = 0; r0 < h; r0 += kSubR)
+                for (int c0 = 0; c0 < w; c0 += kSubC) {
+                    const int ni = min(kSubR, h - r0), nj = min(kSubC, w - c0);
+                    __syncthreads();                // the previous chunk's LDS reads are done
                     sub_load_image_f(If[0], img.f32 + c * img.f32_plane, img.f32_pitch, img.rows, img.cols, oy + r0, ox + c0,
                                      tid);
                     __syncthreads();
@@ -212,52 +117,46 @@ __global__ __launch_bounds__(256) void sub_nbhd_kernel(ImageDev img, const uint8
                             }
                     }
                 }
+        }
+        // reduce; thread k < 9 keeps window k's sums
+        double rc = 0, r2 = 0, r1[kS1 > 0 ? kS1 : 1];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const double a = sub_reduce(corr[k], red);
+            const double b = sub_reduce(s2[k], red);
+            if (tid == k) {
+                rc = a;
+                r2 = b;
             }
-    }
-    // reduce; thread k < 9 keeps window k's sums
-    Acc rc = 0, r2 = 0, r1[kS1 > 0 ? kS1 : 1];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        const Acc a = sub_reduce(corr[k], red);
-        const Acc b = sub_reduce(s2[k], red);
-        if (tid == k) {
-            rc = a;
-            r2 = b;
+            for (int c = 0; c < kS1; ++c) {
+                const double s = sub_reduce(s1[k][c], red);
+                if (tid == k) r1[c] = s;
+            }
         }
+        if (tid >= 9) return;
+        const int dy = tid / 3 - 1, dx = tid % 3 - 1;
+        const int wy = P.y + dy, wx = P.x + dx;
+        float score = NAN;
+        if (wy >= 0 && wx >= 0 && wy <= img.rows - h && wx <= img.cols - w) {
+            if constexpr (kMasked) {
+                score = finish_masked(method, rc, r2, S.T);
+            } else {
+                // win_score's statistics from float64 sums
+                const bool centred = method == MTM_TM_CCOEFF || method == MTM_TM_CCOEFF_NORMED;
+                double mean2 = 0.0;
 #pragma unroll
-        for (int c = 0; c < kS1; ++c) {
-            const Acc s = sub_reduce(s1[k][c], red);
-            if (tid == k) r1[c] = s;
+                for (int c = 0; c < CH; ++c)
+                    if (centred) mean2 += r1[c] * r1[c];
+                const double inv_area = 1.0 / ((double)h * (double)w);
+                const double wnd_mean2 = mean2 * inv_area;
+                score = finish_unmasked_with(
+                    method, rc, [&](int c) { return c < CH ? r1[c < CH ? c : 0] : 0.0; }, [&]() { return r2; },
+                    [&]() { return window_norm(r2, wnd_mean2); }, S.T, CH);
+            }
         }
+        out[(size_t)blockIdx.x * 9 + tid] = score;
     }
-    if (tid >= 9) return;
-    const int dy = tid / 3 - 1, dx = tid % 3 - 1;
-    const int wy = P.y + dy, wx = P.x + dx;
-    float score = NAN;
-    if (wy >= 0 && wx >= 0 && wy <= img.rows - h && wx <= img.cols - w) {
-        if constexpr (kMasked) {
-            score = finish_masked(method, (double)rc, (double)r2, S.T);
-        } else if constexpr (kInt) {
-            const double inv_area = 1.0 / ((double)h * (double)w);
-            unsigned long long s1u[CH];
-#pragma unroll
-            for (int c = 0; c < CH; ++c) s1u[c] = r1[c];
-            score = win_score<CH>(method, S.T, inv_area, rc, s1u, r2);
-        } else {
-            // win_score's statistics from float64 sums
-            const bool centred = method == MTM_TM_CCOEFF || method == MTM_TM_CCOEFF_NORMED;
-            double mean2 = 0.0;
-#pragma unroll
-            for (int c = 0; c < CH; ++c)
-                if (centred) mean2 += r1[c] * r1[c];
-            const double inv_area = 1.0 / ((double)h * (double)w);
-            const double wnd_mean2 = mean2 * inv_area;
-            score = finish_unmasked_with(
-                method, rc, [&](int c) { return c < CH ? r1[c < CH ? c : 0] : 0.0; }, [&]() { return r2; },
-                [&]() { return window_norm(r2, wnd_mean2); }, S.T, CH);
-        }
-    }
-    out[(size_t)blockIdx.x * 9 + tid] = score;
 }
 
 }  // namespace mtm

@@ -2,9 +2,11 @@
 // track, the extremum of the track template's score map over the track's search box (what mtm_find_matches_boxes returns
 // for that unit in MTM_PEAKS_GLOBAL mode), then the next frame's box from that hit - both on the device, so that the host
 // waits once per call instead of twice per frame.  uint8 (1 or 3 channels) and single-channel uint16, unmasked templates
-// of one mtm_set_templates call.
+// of one mtm_set_templates call.  mtm_track_boxes_nbhd also scores the 3 x 3 neighbourhood of every record in its frame's
+// own map (track_nbhd_kernel) while the frame is on the device: what mtm_hit_neighbourhoods returns for it.
 #include "mtm_ctx.h"
 #include "mtm_device_util.hip.h"
+#include "mtm_k_nbhd.hip.h"
 #include "mtm_k_window.hip.h"
 
 using namespace mtm;
@@ -26,6 +28,7 @@ struct TrackTile {
     int k, ty0, tx0;
 };
 constexpr size_t kTrackLaunchTiles = (size_t)1 << 22;     // most work-groups (tiles) of one track_score_kernel launch
+constexpr size_t kTrackLaunchNbhd = (size_t)1 << 22;      // most work-groups (tracks) of one track_nbhd_kernel launch
 
 // Grid: one work-group per tile of the call's tile table.  The tile's windows are summed and scored exactly as
 // boxes_score_kernel does (win_tile_sums_u8 / win_tile_sums_u16, win_score: the same float32 bits), and instead of a map
@@ -107,6 +110,34 @@ __global__ __launch_bounds__(256) void track_update_kernel(TrackUnit* __restrict
     keys[k] = 0ull;
 }
 
+// Grid: one 256-thread work-group per track (launch slice), after the frame's track_update_kernel: the 3 x 3 neighbourhood
+// of the frame's record rec[k] - never of the track unit, which is the next frame's by now - in the frame's own map, into
+// out[9 k ..]: sub_nbhd_int's sums and win_score, mtm_hit_neighbourhoods' float32 bits.  `img` is the chunk's stack and
+// the frame its rows row_off .. row_off + rows - 1: the planes are entered at the frame's first row and bounded by the
+// frame's `rows`, so that windows and pixels outside the frame are NaN and zero whatever its neighbours in the stack hold.
+// A record whose own window is outside the frame's map (the decoded all-NaN key) gets nine NaNs and reads no pixel.
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void track_nbhd_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
+                                                         const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
+                                                         const TemplDev* __restrict__ td, const mtm_hit* __restrict__ rec,
+                                                         int row_off, int rows, int method, float* __restrict__ out) {
+    constexpr int kKind = U16 ? kSubU16 : kSubU8;
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
+    __shared__ __attribute__((aligned(16))) SubImageLds Il[U16 ? 2 : 1];
+    __shared__ unsigned long long red[4];
+    const mtm_hit R = rec[blockIdx.x];
+    const TemplDev T = td[R.templ_idx];
+    const int tid = threadIdx.x;
+    float score = NAN;
+    // (the same for the whole work-group: before any barrier)
+    if (R.x >= 0 && R.y >= 0 && R.x <= img.cols - T.cols && R.y <= rows - T.rows) {
+        const size_t base = (size_t)row_off * img.u8_pitch;
+        score = sub_nbhd_int<CH, kKind>(Tl, Il, red, img.u8 + base, img.u8_plane, lo_b + base, img.u8_pitch, rows, img.cols,
+                                        tpx + toff[R.templ_idx], nullptr, T, R.x, R.y, method);
+    }
+    if (tid < 9) out[(size_t)blockIdx.x * 9 + tid] = score;
+}
+
 }  // namespace mtm
 
 namespace {
@@ -121,16 +152,12 @@ int track_chunk_frames(const mtm_ctx* c, int rows, int cols, int chans) {
     return std::min(by_rows, by_mem);
 }
 
-}  // namespace
-
-extern "C" {
-
-int mtm_track_boxes(mtm_ctx* c, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
-                    int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min,
-                    double min_score, mtm_hit* out) {
-    const char* who = "mtm_track_boxes";
+// mtm_track_boxes (nbhd == nullptr, with_nbhd false) and mtm_track_boxes_nbhd (with_nbhd: `nbhd` is required).
+int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min, double min_score,
+                mtm_hit* out, float* nbhd, bool with_nbhd) {
     if (!c || n_frames < 0 || n_tracks < 0 || margin < 0 || (n_frames > 0 && !frames) ||
-        (n_tracks > 0 && !start) || (n_frames > 0 && n_tracks > 0 && !out)) {
+        (n_tracks > 0 && !start) || (n_frames > 0 && n_tracks > 0 && (!out || (with_nbhd && !nbhd)))) {
         set_error(std::string(who) + ": bad arguments");
         return MTM_E_INVALID;
     }
@@ -200,6 +227,7 @@ int mtm_track_boxes(mtm_ctx* c, const void* const* frames, int n_frames, int row
     MTMC(c->trk_tiles.ensure(sizeof(TrackTile) * tiles.size()));
     MTMC(c->trk_keys.ensure(sizeof(unsigned long long) * (size_t)n_tracks));
     MTMC(c->trk_out.ensure(sizeof(mtm_hit) * n_out));
+    if (nbhd) MTMC(c->trk_nbhd.ensure(sizeof(float) * 9 * n_out));
     HIPC(hipEventRecord(c->ev[0], c->stream));
     HIPC(hipMemcpyAsync(c->trk_units.p, tu.data(), sizeof(TrackUnit) * tu.size(), hipMemcpyHostToDevice, c->stream));
     HIPC(hipMemcpyAsync(c->trk_tiles.p, tiles.data(), sizeof(TrackTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
@@ -234,16 +262,50 @@ int mtm_track_boxes(mtm_ctx* c, const void* const* frames, int n_frames, int row
                                margin, use_min ? 1 : 0, min_score, rows, cols,
                                c->trk_out.as<mtm_hit>() + (size_t)(f0 + fl) * n_tracks);
             HIPC(hipGetLastError());
+            if (!nbhd) continue;
+            // the frame's neighbourhoods, from its records and its rows of the stack: no upload, no wait
+#define MTM_TRACK_NBHD(CH, U16)                                                                                              \
+    hipLaunchKernelGGL((track_nbhd_kernel<CH, U16>), dim3(nk), dim3(256), 0, c->stream, img, lo_b, c->win_tpx.as<uint8_t>(),  \
+                       c->win_toff.as<long long>(), c->box_td.as<TemplDev>(), c->trk_out.as<mtm_hit>() + r0 + k0, fl * rows, \
+                       rows, c->method, c->trk_nbhd.as<float>() + 9 * (r0 + k0))
+            const size_t r0 = (size_t)(f0 + fl) * n_tracks;
+            for (size_t k0 = 0; k0 < (size_t)n_tracks; k0 += kTrackLaunchNbhd) {
+                const unsigned nk = (unsigned)std::min(kTrackLaunchNbhd, (size_t)n_tracks - k0);
+                if (dtype == MTM_U16) MTM_TRACK_NBHD(1, true);
+                else if (chans == 1) MTM_TRACK_NBHD(1, false);
+                else MTM_TRACK_NBHD(3, false);
+                HIPC(hipGetLastError());
+            }
+#undef MTM_TRACK_NBHD
         }
     }
     HIPC(hipEventRecord(c->ev[1], c->stream));
     HIPC(hipMemcpyAsync(out, c->trk_out.p, sizeof(mtm_hit) * n_out, hipMemcpyDeviceToHost, c->stream));
+    if (nbhd) HIPC(hipMemcpyAsync(nbhd, c->trk_nbhd.p, sizeof(float) * 9 * n_out, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
     HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
     c->timing.n_hits = (int64_t)n_out;
     // the stack is none of the caller's frames: no current image, no published maps
     c->have_image = false;
     return MTM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtm_track_boxes(mtm_ctx* c, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                    int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min,
+                    double min_score, mtm_hit* out) {
+    return track_boxes(c, "mtm_track_boxes", frames, n_frames, rows, cols, chans, dtype, row_stride_bytes, start, n_tracks,
+                       margin, use_min, min_score, out, nullptr, false);
+}
+
+int mtm_track_boxes_nbhd(mtm_ctx* c, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                         int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min,
+                         double min_score, mtm_hit* out, float* nbhd) {
+    return track_boxes(c, "mtm_track_boxes_nbhd", frames, n_frames, rows, cols, chans, dtype, row_stride_bytes, start,
+                       n_tracks, margin, use_min, min_score, out, nbhd, true);
 }
 
 }  // extern "C"

@@ -8,12 +8,20 @@ JSON line per workload:
 The results of track and matcher are checked equal to loop_boxes' (labels, boxes, float32 score bits), and the fraction
 of (frame, track) hits at the true position is reported.
 
+--refine times sub-pixel tracking instead, one JSON line per workload:
+  track_refine   - MTM.trackTemplates(..., refine=True): the neighbourhoods scored inside the one native call
+  matcher_refine - TemplateMatcher(templates).track(..., refine=True)
+  track_then_refine - today's way: MTM.trackTemplates(...) followed by one MTM.refineHits call per frame
+  track, matcher - the unrefined calls, for the refined call's overhead per frame
+The results of track_refine and matcher_refine are checked equal to track_then_refine's (labels, float positions with ==,
+sizes, float32 score bits).
+
 Data: each frame is one of 8 synth.smooth_u8 backgrounds (uint16: 257 x that plus noise in the low byte) with each
 track's template - a crop of another smooth_u8 image - pasted at a position that moves up to margin / 2 pixels per frame
 in each direction.  Each method is warmed up first; the four are interleaved within a repetition; medians over the
 repetitions.
 
-Usage: tools/track_throughput.py [--reps 3] [--warmup 1] [--only T1|T2|T3]
+Usage: tools/track_throughput.py [--reps 3] [--warmup 1] [--only T1|T2|T3] [--refine]
 """
 import argparse
 import json
@@ -74,6 +82,66 @@ def _key(res):
     return [[(h[0][0], tuple(int(v) for v in h[0][1]), np.float32(h[0][2]).tobytes()) for h in fr] for fr in res]
 
 
+def _time(methods, reps, warmup):
+    """Each method warmed up, then the methods interleaved within a repetition: (last results, milliseconds per method)."""
+    results = {}
+    for k, fn in methods.items():
+        for _ in range(warmup):
+            results[k] = fn()
+    ms = {k: [] for k in methods}
+    for _ in range(reps):
+        for k, fn in methods.items():
+            t0 = time.perf_counter()
+            fn()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    return results, ms
+
+
+def _rkey(res):
+    return [[(h[0][0], tuple(h[0][1]), np.float32(h[0][2]).tobytes()) for h in fr] for fr in res]
+
+
+def run_refine(MTM, spec, reps, warmup):
+    name, n_frames, hw, chans, dtype, n_tracks, side, margin = spec
+    templs, frames, tracks, truth = workload(spec)
+    frame_list = list(frames)
+    method = MTM.TM_CCOEFF_NORMED
+    matcher = MTM.TemplateMatcher(templs, method)
+
+    def then_refine():
+        res = MTM.trackTemplates(templs, frames, tracks, margin, method)
+        return [[[h] for h in MTM.refineHits(templs, f, [c[0] for c in fr], method)] for f, fr in zip(frame_list, res)]
+
+    methods = {
+        "track_refine": lambda: MTM.trackTemplates(templs, frames, tracks, margin, method, refine=True),
+        "matcher_refine": lambda: matcher.track(frames, tracks, margin, refine=True),
+        "track_then_refine": then_refine,
+        "track": lambda: MTM.trackTemplates(templs, frames, tracks, margin, method),
+        "matcher": lambda: matcher.track(frames, tracks, margin),
+    }
+    results, ms = _time(methods, reps, max(1, warmup))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    ref = _rkey(results["track_then_refine"])
+    pos = MTM.tracking.positions(results["track_refine"])
+    methods["track_refine"]()                       # (the default context's timing: this call's, upload to last launch)
+    t = MTM._lib.default_context().timing()
+    return {
+        "workload": name, "mode": "refine", "frames": n_frames, "frame": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype),
+        "tracks": n_tracks, "template": "%dx%d" % (side, side), "margin": margin,
+        "ms_per_frame": {k: round(v / n_frames, 4) for k, v in med.items()},
+        "ms_per_frame_min": {k: round(min(v) / n_frames, 4) for k, v in ms.items()},
+        "ms_per_frame_max": {k: round(max(v) / n_frames, 4) for k, v in ms.items()},
+        "speedup_vs_track_then_refine": {k: round(med["track_then_refine"] / med[k], 2)
+                                         for k in ("track_refine", "matcher_refine")},
+        "refine_overhead_us_per_frame": {"track": round((med["track_refine"] - med["track"]) / n_frames * 1e3, 1),
+                                         "matcher": round((med["matcher_refine"] - med["matcher"]) / n_frames * 1e3, 1)},
+        "track_refine_device_ms": round(float(t["total_ms"]), 3),
+        "equal_to_track_then_refine": {k: _rkey(results[k]) == ref for k in ("track_refine", "matcher_refine")},
+        "mean_abs_offset": round(float(np.mean(np.abs(pos - np.round(pos)))), 4),
+        "reps": reps,
+    }
+
+
 def run(MTM, spec, reps, warmup):
     from MTM.tracking import next_box
     name, n_frames, hw, chans, dtype, n_tracks, side, margin = spec
@@ -97,16 +165,7 @@ def run(MTM, spec, reps, warmup):
         "loop_boxes": lambda: loop(lambda f, reg: MTM.findMatchesInBoxes(templs, f, reg, method, N_object=1)),
         "loop_matcher": lambda: loop(matcher1.match_boxes),
     }
-    results = {}
-    for k, fn in methods.items():
-        for _ in range(warmup):
-            results[k] = fn()
-    ms = {k: [] for k in methods}
-    for _ in range(reps):
-        for k, fn in methods.items():
-            t0 = time.perf_counter()
-            fn()
-            ms[k].append((time.perf_counter() - t0) * 1e3)
+    results, ms = _time(methods, reps, warmup)
     med = {k: statistics.median(v) for k, v in ms.items()}
     ref = _key(results["loop_boxes"])
     equal = {k: _key(results[k]) == ref for k in ("track", "matcher", "loop_matcher")}
@@ -119,6 +178,7 @@ def run(MTM, spec, reps, warmup):
         "template": "%dx%d" % (side, side), "margin": margin,
         "ms_per_frame": {k: round(v / n_frames, 4) for k, v in med.items()},
         "ms_per_frame_min": {k: round(min(v) / n_frames, 4) for k, v in ms.items()},
+        "ms_per_frame_max": {k: round(max(v) / n_frames, 4) for k, v in ms.items()},
         "speedup_vs_loop_boxes": {k: round(med["loop_boxes"] / med[k], 2) for k in ("track", "matcher", "loop_matcher")},
         "track_device_ms": round(float(t["total_ms"]), 3),
         "equal_to_loop_boxes": equal,
@@ -132,6 +192,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--only", default=None, help="run the one workload of this name (profiling runs)")
+    ap.add_argument("--refine", action="store_true", help="time sub-pixel tracking (refine=True) against today's way")
     args = ap.parse_args()
     import build as mtm_build
     mtm_build.build()
@@ -139,7 +200,7 @@ def main():
     for spec in WORKLOADS:
         if args.only and spec[0] != args.only:
             continue
-        print(json.dumps(run(MTM, spec, args.reps, args.warmup)), flush=True)
+        print(json.dumps((run_refine if args.refine else run)(MTM, spec, args.reps, args.warmup)), flush=True)
 
 
 if __name__ == "__main__":

@@ -222,6 +222,12 @@ int         mtm_debug_poison(mtm_ctx* ctx, int pattern_byte, int what);
  * bit (must be 0), cases that took the division, largest |num * rr - num / t| seen in ulp(double) (the bound in the
  * source is 6, the test's margin 32)}. */
 int         mtm_debug_quotient_check(mtm_ctx* ctx, uint64_t n_cases, uint64_t seed, uint64_t* out4);
+/* Test support (added under ABI 9; host only, needs no GPU).  The number of K steps after which the two-row score kernel
+ * of an h x w uint8 class screens its waves against the tail bound, as the library derives it from a call's candidate
+ * threshold thr: the smallest s in [6, h - 2] with thr - (h - s + 1) / h >= z sqrt(s / h) / sqrt(w h), or 0 where the call
+ * runs unscreened (no such s, a negative threshold, s / h above the measured cut-off).  The environment variable
+ * MTM_TAIL_SPLIT=<s> (read when a context is created) forces a split instead, clamped to [6, h - 2]. */
+int         mtm_debug_tail_split(int h, int w, double thr);
 /* Page-locked host memory for pixel buffers (optional).  The reference's caller hands over whatever numpy holds
  * (MTM/__init__.py:247 `image`) - pageable memory, which the runtime stages through its own pinned buffers while the
  * upload call blocks.  An image kept in memory from mtm_host_alloc crosses PCIe as a plain DMA transfer behind the call

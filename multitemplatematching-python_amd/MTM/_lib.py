@@ -84,6 +84,7 @@ SYMBOLS = {
     "mtm_get_option": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P(ctypes.c_int64)]),
     "mtm_debug_poison": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     "mtm_debug_quotient_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, _P(ctypes.c_uint64)]),
+    "mtm_debug_tail_split": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double]),
     "mtm_set_image": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
     "mtm_set_image_downscaled": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -358,6 +359,12 @@ _LIVE = weakref.WeakSet()          # contexts that exist right now (test support
 
 def live_contexts():
     return [c for c in list(_LIVE) if c._h]
+
+
+def debug_tail_split(h, w, thr):
+    """Test support (mtm_debug_tail_split; needs no GPU): the K steps after which the two-row score kernel of an h x w
+    class screens its waves at the candidate threshold `thr`, 0 = unscreened."""
+    return int(load().mtm_debug_tail_split(int(h), int(w), float(thr)))
 
 
 class Context(_RecordMemo):

@@ -328,6 +328,7 @@ int mtm_ctx_create(mtm_ctx** out, int device_id) {
     if (const char* v = std::getenv("MTM_NMS_DEVICE_MIN")) c->nms_device_min = std::atoll(v) < 0 ? (1ll << 60) : std::max(1, std::atoi(v));   // < 0: never
     if (const char* v = std::getenv("MTM_SCREEN_L1")) c->screen_l1 = std::atoi(v);
     if (const char* v = std::getenv("MTM_TAIL_SCREEN")) c->tail_screen = std::atoi(v) != 0;
+    if (const char* v = std::getenv("MTM_TAIL_SPLIT")) c->tail_split_force = std::max(0, std::atoi(v));
     if (const char* v = std::getenv("MTM_HOST_TRACE")) c->host_trace = std::atoi(v) != 0;
     if (const char* v = std::getenv("MTM_CLASS_LANES")) c->class_lanes = std::max(1, std::min(8, std::atoi(v)));
     if (const char* v = std::getenv("MTM_COMM_TIMEOUT_S")) c->comm_timeout_s = std::atof(v);

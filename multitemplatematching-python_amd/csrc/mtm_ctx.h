@@ -128,7 +128,9 @@ struct SizeClass {
     int r2 = 0;                 // multi-row MFMA variant (> 16 templates, w <= 64, one channel, methods 2..5): 2 or 3 consecutive
                                 // output rows x 16 templates per wave; packs of h + r2 - 1 rows per 16-template group (the
                                 // extra rows zero); 0 = off
-    int tail_split = 0;         // two-row variant: K steps before the tail screen (a multiple of 6; MfmaParams::tail_split), 0 = none
+    bool tail_ok = false;       // two-row variant in one K chunk, h >= 8: its hits-only launches can screen their K loop
+    int tail_split = 0;         // ... the split (MfmaParams::tail_split) the class's tail constants are computed for at placement:
+                                // tail_split_rule at the default threshold, or the forced one (mtm_ctx::tail_split_force); 0 = none
     long long mask_rm_off = -1; // masked class: row-multiplexed pack (1 "template" = the binary mask, R = 16) in apacks
     double mask_ones = 0.0;     // number of set mask pixels
     int n_pad = 0;              // members rounded up to a multiple of 16 (uint16 packs)
@@ -199,6 +201,10 @@ struct CallRoute {
     bool single_band = false;   // the banded upload is ONE band (banded_ok: a call too small for two score launches)
     int64_t cand_cap = 0;
     unsigned hash_mask = 0;
+    // the tail screen's split of the call (tail_split_for): the rule's value, computed once for the call's threshold and
+    // class shape - every statistics and score launch of every band then carries the same one
+    int tail_h = 0, tail_w = 0, tail_s = 0;
+    float tail_thr = 0.0f;
     NmsRequest nms;
     long long nms_raw_count = -1;   // >= 0: the device pruned the peak list; the count before that
     long long nms_sure = 0;         // ... and its first nms_sure hits are kept for certain (the neighbourhoods' best)
@@ -254,6 +260,10 @@ struct mtm_ctx {
     int screen_l1 = 1;                      // MTM_SCREEN_L1: the hits-only screen starts with the per-lane bound (0: round 2's screen alone)
     int tail_screen = 1;                    // MTM_TAIL_SCREEN: the two-row variant's hits-only K loop stops early where a bound on the
                                             // template rows still missing rules out every candidate (MfmaParams::tail_split)
+    int tail_split_force = 0;               // MTM_TAIL_SPLIT=<s>: that split (clamped to [6, h - 2]) wherever the route allows a
+                                            // screen, instead of tail_split_rule's (tests, measurements)
+    std::vector<int> tail_valid;            // per size class: the split TemplDev::tail_* on the device hold the constants of
+                                            // (ensure_tail_consts re-derives them when a call's split differs), 0 = none
     int f32_mfma = 1;                       // MTM_F32_MFMA / MTM_OPT_F32_MFMA: unmasked float32 classes on the bf16 matrix cores:
                                             // 0 = float64 kernel, 1 = bf16 screen + exact float64 re-scoring of everything
                                             // that could be a peak (hit lists of the float64 kernel), 2 = bf16 scores as they are,
@@ -565,6 +575,8 @@ int place_templates(mtm_ctx* c);
 // ---- mtm_launch.hip
 bool dot_variant_ok(int64_t v);
 int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out, int sb0 = 0, int sb1 = -1);
+// the tail constants of class `sc` for `split` (tail_consts_kernel -> TemplDev::tail_*), queued on `stream`
+int launch_tail_consts(mtm_ctx* c, const SizeClass& sc, int split, hipStream_t stream);
 int launch_ncc(mtm_ctx* c, CallRoute& R, const SizeClass& sc, int list_off, int n_list, const StatPlanes& st, int only_li = -1,
                int yb0 = 0, int yb1 = -1);
 int ensure_maps(mtm_ctx* c);

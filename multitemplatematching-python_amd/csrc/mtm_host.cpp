@@ -54,6 +54,25 @@ void u8_run_sums(const uint8_t* p, size_t n, unsigned long long* sum, unsigned l
     *sumsq += q;
 }
 
+// The tail screen's split (MfmaParams::tail_split: the K steps of the two-row MFMA variant ahead of its tail screen) for an
+// h x w class at the candidate threshold thr_lo.  After s steps a noise-like window's bound carries the tail term, about
+// (h - s + 1) / h of the normaliser for the longer of a wave's two tails, and a partial score whose standard deviation is
+// sigma_P = sqrt(s / h) / sqrt(w h); a wave leaves when all of its 8192 outputs (about 4 sigma_P) stay below the threshold
+// with what the screen's block-level ranges cost on top.  The split is the smallest s in [6, h - 2] with
+//   thr_lo - (h - s + 1) / h >= z sigma_P          (kTailSplitZ, measured: DESIGN 4.1 "Tail screen")
+// and 0 (no screen) where no s qualifies, the threshold is negative, or s / h is above kTailSplitMaxFrac, the fraction
+// beyond which a screened call - tail boxes in the statistics launch, the screen itself - no longer beats the full loop.
+// Any split is correct (the bound is rigorous for every s); the rule only decides how early the waves that can leave do.
+int tail_split_rule(int h, int w, double thr_lo) {
+    if (!(thr_lo >= 0.0) || h < 8 || w < 1) return 0;
+    for (int s = 6; s <= h - 2; ++s) {
+        const double tail = (double)(h - s + 1) / (double)h;
+        const double sigma = std::sqrt((double)s / (double)h) / std::sqrt((double)w * (double)h);
+        if (thr_lo - tail >= kTailSplitZ * sigma) return (double)s / (double)h <= kTailSplitMaxFrac ? s : 0;
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Template constants.  Follows OpenCV's common_matchTemplate (the arithmetic behind the
 // cv2.matchTemplate call at reference MTM/__init__.py:92) in the operation order that
@@ -498,6 +517,8 @@ extern "C" {
 const char* mtm_last_error(void) { return mtm::g_last_error.c_str(); }
 
 int mtm_abi_version(void) { return MTM_ABI_VERSION; }
+
+int mtm_debug_tail_split(int h, int w, double thr) { return mtm::tail_split_rule(h, w, thr); }
 
 int mtm_nms(const mtm_hit* hits, int64_t n, double score_threshold, int ascending,
             int64_t n_object, double max_overlap, int32_t* keep, int64_t* n_keep) {

@@ -35,6 +35,12 @@ TemplStats templ_stats_from_sums(const double* sum, const double* sumsq, double 
 
 // exact sum v / sum v^2 of n bytes, added to *sum / *sumsq
 void u8_run_sums(const uint8_t* p, size_t n, unsigned long long* sum, unsigned long long* sumsq);
+// The tail screen's split for an h x w class at the candidate threshold thr_lo (see the definition; 0 = no screen)
+int tail_split_rule(int h, int w, double thr_lo);
+// ... its measured constants, and the threshold whose split a class's tail constants are computed for at placement
+constexpr double kTailSplitZ = 6.5;
+constexpr double kTailSplitMaxFrac = 0.94;
+constexpr double kTailDefaultThr = 0.5;
 
 // scipy.signal.find_peaks(x, height=h)[0]
 std::vector<int> find_peaks_1d(const float* x, int n, int stride, float height, bool negate);

@@ -105,17 +105,39 @@ int mfma_row_mux(MfmaParams& p, int R, int nt) {
 
 // The tail screen's split for a launch of class `sc` on route R (MfmaParams::tail_split), 0 = off: hits-only candidate lists of
 // a two-row uint8 class in one K chunk, TM_CCOEFF_NORMED / TM_CCORR_NORMED, a non-negative threshold, neither the fused
-// extremum nor maps in memory - and a threshold the bound can get below.  After the split the tail term of a noise-like
-// window against a template whose structure is spread over its rows is about |Q| / n of the normaliser (|Q|: the odd row's
-// tail, the longer one); the screen is worth running where the threshold clears that by 0.1 (0.5 at 64 x 64: 0.14).
-int tail_split_for(const mtm_ctx* c, const CallRoute& R, const SizeClass& sc) {
-    if (!c->tail_screen || !c->screen_l1 || sc.tail_split <= 0 || sc.r2 != 2 || sc.masked || sc.kernel != MTM_KERNEL_MFMA) return 0;
+// extremum nor maps in memory - and a threshold the bound can get below early enough to pay.
+// The split itself follows the call's threshold (tail_split_rule, mtm_host.cpp), or is the forced one (MTM_TAIL_SPLIT).
+// The rule's value is computed once per call and kept in the route: every statistics and score launch of every band of the
+// call carries the same split (the route's other fields can change between a call's passes - they are tested every time).
+int tail_split_for(const mtm_ctx* c, CallRoute& R, const SizeClass& sc) {
+    if (!c->tail_screen || !c->screen_l1 || !sc.tail_ok || sc.r2 != 2 || sc.masked || sc.kernel != MTM_KERNEL_MFMA) return 0;
     if (!R.cand_on || !R.hits_only || R.ext || R.sparse || R.cand_min || c->chans != 1 || c->dtype != MTM_U8) return 0;
     if (c->method != MTM_TM_CCOEFF_NORMED && c->method != MTM_TM_CCORR_NORMED) return 0;
     if (sc.h + 1 > kMfChunkR2 || sc.w > 64) return 0;
     const double thr_lo = (double)R.cand_thr - 1e-6 * std::max(1.0, std::fabs((double)R.cand_thr));
-    const double tail = (double)(sc.h - sc.tail_split + 1) / (double)sc.h;
-    return thr_lo >= 0.0 && thr_lo - tail >= 0.1 ? sc.tail_split : 0;
+    if (!(thr_lo >= 0.0)) return 0;
+    if (c->tail_split_force > 0) return std::max(6, std::min(c->tail_split_force, sc.h - 2));
+    if (R.tail_h != sc.h || R.tail_w != sc.w || R.tail_thr != R.cand_thr) {
+        R.tail_s = tail_split_rule(sc.h, sc.w, thr_lo);
+        R.tail_h = sc.h;
+        R.tail_w = sc.w;
+        R.tail_thr = R.cand_thr;
+    }
+    return R.tail_s;
+}
+
+// The templates' tail constants (TemplDev::tail_*) hold for ONE split: a launch whose split is not the one they were last
+// computed for (mtm_ctx::tail_valid) re-derives them first - tail_consts_kernel, 64 threads per template, on the score
+// stream: ahead of the call's first score launch (launch_stats asks before the launch waits for its band, so the kernel
+// runs under band 0's copy) and behind the previous call's, never on the copy-side stream.
+static int ensure_tail_consts(mtm_ctx* c, const SizeClass& sc, int split) {
+    if (split <= 0 || sc.members.empty()) return MTM_OK;
+    const bool mine = !c->classes.empty() && &sc >= c->classes.data() && &sc < c->classes.data() + c->classes.size();
+    const size_t k = mine ? (size_t)(&sc - c->classes.data()) : 0;
+    if (mine && k < c->tail_valid.size() && c->tail_valid[k] == split) return MTM_OK;
+    MTMC(launch_tail_consts(c, sc, split, c->stream));
+    if (mine && k < c->tail_valid.size()) c->tail_valid[k] = split;
+    return MTM_OK;
 }
 
 // the candidate list (mtm_ctx::cands: a 16-byte header, then the records) a score kernel appends to, `cap` records long
@@ -303,6 +325,7 @@ int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out,
             // (the tail boxes' records, when the score launch screens its K loop, follow the window's in the same buffer)
             const size_t nrec = 4 * (size_t)st.blk_pitch * oh;
             tail_s = tail_split_for(c, R, sc);
+            MTMC(ensure_tail_consts(c, sc, tail_s));
             MTMC(c->stats_blk.ensure(sizeof(double) * nrec * (tail_s ? 2 : 1)));
             blk = c->stats_blk.as<double>();
             st.blk = blk;
@@ -820,6 +843,7 @@ static int launch_mfma(mtm_ctx* c, CallRoute& R, const SizeClass& sc, const Stat
     // statistics directly), (mb + 1) / 2 KB per wave for the two-row one (differs by tiling; not decided here)
     // (tail screen: the tail boxes' records and the templates' tail constants behind them)
     p.tail_split = (r2 && st.blkq != nullptr && only_li < 0 && !p.seg_skip) ? tail_split_for(c, R, sc) : 0;
+    MTMC(ensure_tail_consts(c, sc, p.tail_split));          // (launch_stats has seen to it: a no-op)
     const size_t stat_bytes = rm ? 0 : r2 ? (size_t)kMfRows * ((mb + 1) / 2) * 1024 + (p.tail_split ? mf_tail_lds_bytes() : 0)
                                           : (size_t)kMfRows * mf_stat_bytes_per_wave(c->chans == 3 ? 3 : 1);
     const bool ext = R.ext;                          // plan_call checked the class

@@ -629,7 +629,7 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
                 MTM_R2_STEP(qx, qy, aB, aA, qx2, qy2, aC)
                 MTM_R2_LOAD(qx, qy, aA)           // step 0 of the chunk; aC = the step before it
                 int ks = 0;
-                // Tail screen (hits-only, one chunk: MfmaParams::tail_split, a multiple of 6).  After s = tail_split steps
+                // Tail screen (hits-only, one chunk: MfmaParams::tail_split, any number of steps >= 1; the launcher gives 6 .. h - 2).  After s = tail_split steps
                 // the first row of the wave holds template rows 0 .. s - 1, the second 0 .. s - 2, exactly.  Split the sum
                 // over the rows Q still missing as sum_Q I T = sum_Q (I - mu_Q)(T - tau_Q) + tau_Q S1_Q (mu_Q, tau_Q: their
                 // means over Q) and bound the first term by Cauchy-Schwarz:
@@ -651,11 +651,22 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
                         MTM_R2_FIVE()
                         MTM_R2_STEP(qx2, qy2, aC, aB, qx, qy, aA)
                     }
-                    // the last six steps before the split: the sixth requests nothing ahead (the operands of step s are
-                    // not live across the screen; aC = the A operand of step s - 1, the second row's next one)
-                    MTM_R2_FIVE()
-                    MTM_R2_STEP_LAST(qx2, qy2, aC, aB)
-                    ks += 6;
+                    // the last 1 .. 6 steps before the split (any split >= 1; the trip counts are wave-uniform): single
+                    // steps in phase 0 of the rotation, the operand variables brought back to it by register moves (twelve
+                    // v_mov per step, at most five steps per wave), and then the last one, which requests nothing ahead -
+                    // the operands of step s are not live across the screen - and leaves its A operand, step s - 1's and
+                    // the second row's next one, in aC: where the loop below expects it when it starts again in phase 0
+#pragma nounroll
+                    for (; ks + 1 < split; ++ks) {
+                        MTM_R2_STEP(qx, qy, aA, aC, qx2, qy2, aB)
+                        aC = aA;
+                        aA = aB;
+                        qx = qx2;
+                        qy = qy2;
+                    }
+                    MTM_R2_STEP_LAST(qx, qy, aA, aC)
+                    aC = aA;
+                    ks = split;
                     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
                     bool pass = false;
                     const uint8_t* sbw = smem + p.st_off + wave * 1024 + j * 32;     // window records, row mb at + mb * 512

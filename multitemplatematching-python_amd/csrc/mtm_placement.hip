@@ -477,10 +477,21 @@ void choose_tiling(const mtm_ctx* c, SizeClass& sc) {
     else if (c->mfma_r2 && sc.rm_R == 0 && n_cls > 16 && sc.w <= 64 && c->chans == 1 && !sc.masked &&
              c->method >= MTM_TM_CCORR && c->fuse_stats)
         sc.r2 = 2;
-    // tail screen of the two-row variant (one K chunk): the split nearest 0.65 h on the loop's six-step rotation (42 for
-    // h = 64: 22 / 23 template rows left for the two rows of a wave), leaving at least two rows
-    if (sc.r2 == 2 && sc.h + 1 <= mtm::kMfChunkR2 && sc.h >= 8)
-        sc.tail_split = std::max(6, std::min(6 * (int)std::lround(0.65 * sc.h / 6.0), (sc.h - 2) / 6 * 6));
+    // tail screen of the two-row variant (one K chunk, splits 6 .. h - 2).  The split is a call's (tail_split_for); the
+    // constants computed here are those of the default threshold's, which a call at another one re-derives
+    if (sc.r2 == 2 && sc.h + 1 <= mtm::kMfChunkR2 && sc.h >= 8) {
+        sc.tail_ok = true;
+        sc.tail_split = c->tail_split_force > 0 ? std::max(6, std::min(c->tail_split_force, sc.h - 2))
+                                                : tail_split_rule(sc.h, sc.w, kTailDefaultThr - 1e-6);
+    }
+}
+
+int queue_tail_consts(mtm_ctx* c, const SizeClass& sc, int split, hipStream_t stream) {
+    hipLaunchKernelGGL(tail_consts_kernel, dim3((unsigned)sc.members.size()), dim3(64), 0, stream,
+                       c->apacks.as<uint8_t>() + sc.apack_off, sc.group_bytes, sc.h, sc.w, split,
+                       c->tlist.as<int>() + sc.tlist_off, c->td.as<TemplDev>());
+    HIPC(hipGetLastError());
+    return MTM_OK;
 }
 
 // A class's regions of the A arena (uint16: and of the tsum arena); returns the bytes of its A packs.  Fields of the
@@ -752,12 +763,8 @@ int upload_placement(mtm_ctx* c, Placement& P, HostArenas& H) {
         if (P.dev_pack[k]) MTMC(pack_class_on_device(c, P.classes[k]));
     // the tail screen's constants, from the packs just placed (host- or device-packed alike)
     for (const SizeClass& sc : P.classes)
-        if (sc.tail_split > 0 && sc.kernel == MTM_KERNEL_MFMA && !sc.members.empty()) {
-            hipLaunchKernelGGL(tail_consts_kernel, dim3((unsigned)sc.members.size()), dim3(64), 0, c->stream,
-                               c->apacks.as<uint8_t>() + sc.apack_off, sc.group_bytes, sc.h, sc.w, sc.tail_split,
-                               c->tlist.as<int>() + sc.tlist_off, c->td.as<TemplDev>());
-            HIPC(hipGetLastError());
-        }
+        if (sc.tail_split > 0 && sc.kernel == MTM_KERNEL_MFMA && !sc.members.empty())
+            MTMC(queue_tail_consts(c, sc, sc.tail_split, c->stream));
     // host staging vectors go out of scope; the tables that stay in the context (td, tlist) need no wait
     // (set_templates_device)
     const bool local_sources = P.any_host_pack || P.any_mbf || w_off || p_off || ts_off || new_units;
@@ -766,6 +773,11 @@ int upload_placement(mtm_ctx* c, Placement& P, HostArenas& H) {
     drain.armed = false;
     if (new_units) c->usrc_host.swap(P.units);
     c->classes.swap(P.classes);
+    c->tail_valid.assign(c->classes.size(), 0);
+    for (size_t k = 0; k < c->classes.size(); ++k) {
+        const SizeClass& sc = c->classes[k];
+        if (sc.tail_split > 0 && sc.kernel == MTM_KERNEL_MFMA && !sc.members.empty()) c->tail_valid[k] = sc.tail_split;
+    }
     c->td_host.swap(P.td);
     c->tlist_host.swap(P.tlist);
     c->list2d.swap(P.list2d);
@@ -778,6 +790,8 @@ int upload_placement(mtm_ctx* c, Placement& P, HostArenas& H) {
 }  // namespace
 
 namespace mtmi {
+
+int launch_tail_consts(mtm_ctx* c, const SizeClass& sc, int split, hipStream_t stream) { return queue_tail_consts(c, sc, split, stream); }
 
 int place_templates(mtm_ctx* c) {
     if (!c->have_image || !c->have_templ) {

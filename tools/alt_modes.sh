@@ -2,6 +2,8 @@
 # GPU parity suite under every alternative compute route of the library (GPU box).  Round 6: 20 MTM_* variables are left in
 # the native code (39 in round 5); the ones that select a route are all here, the rest is tuning / diagnostics
 # (MTM_CLASS_LANES, MTM_UPLOAD_BANDS, MTM_BAND_MIN_FILL, MTM_GROUP_SPIN_US, MTM_COMM_TIMEOUT_S, MTM_HOST_TRACE).
+# Known, not among the default modes: MTM_TAIL_SPLIT=<s> (the tail screen's split forced, e.g. ALT_MODES="MTM_TAIL_SPLIT=37";
+# any split gives the same records - tests/test_gpu_tail_split.py covers every residue of the K loop's rotation).
 # Exit status: 0 if every switch passed, 1 if some had failures; a run that timed out or died of a signal (abort,
 # segmentation fault, kill: 124, 134, 137, 139, ...) ends the script at once with its status - nothing more is started on
 # a GPU that may be in a bad state.

@@ -55,8 +55,8 @@ CallRoute plan_call(const mtm_ctx* c, int mode, float thr, bool banded) {
     R.cand_cap = std::min<int64_t>(c->hit_cap, kCandListMax);
     R.banded_u8 = banded && c->dtype == MTM_U8;
     // masked float32 classes: the bf16 screen needs the threshold - local extrema, or (mbf_global) the templates' best
-    // lower bounds and everything that reaches them; mtm_score_map keeps the float64 kernel.  What the peak pass compares
-    // with: the float32 threshold, on float32 scores.
+    // lower bounds and everything that reaches them; mtm_score_map (a route of its own, no threshold) keeps the float64
+    // kernel.  What the peak pass compares with: the float32 threshold, on float32 scores.
     R.mbf_thr_on = n > 0 && f32_refined(c);
     R.mbf_global = mode == MTM_PEAKS_GLOBAL;
     R.mbf_thr = thr;
@@ -387,8 +387,9 @@ int fetch_device_nms(mtm_ctx* c, const DeviceNms& qd, unsigned long long count, 
     return MTM_OK;
 }
 
-// ---- The fallback ladder.  An overflowing list moves the call one step down: each transition below lowers the route (a
-// slower route, or a longer list), keeps the context's back-off in step and re-runs what the lowered route needs.
+// ---- The fallback ladder.  An overflowing list moves the call one step down (ladder_next, mtm_host.cpp): each transition
+// below lowers the route (ladder_apply: a slower route, or a longer list), keeps the context's back-off in step and re-runs
+// what the lowered route needs.
 inline void back_off(int& counter, int& len) {      // the next `len` calls skip the route; the period doubles while they overflow
     counter = len;
     len = std::min(2 * len, 1024);
@@ -406,7 +407,7 @@ int rescore(mtm_ctx* c, CallRoute& R) {
 // float32 refinement, the ONE-PRODUCT screen listed more than the list holds: the same route with three piece products -
 // bounds 2^8 times tighter - before anything slower is tried (and the next calls start there)
 int to_three_products(mtm_ctx* c, CallRoute& R) {
-    R.bf16_np = 3;
+    ladder_apply(R, LadderStep::ThreeProducts);
     back_off(c->np1_backoff, c->np1_backoff_len);
     HIPC(hipMemsetAsync(c->cands.p, 0, 16, c->stream));
     if (R.ext) HIPC(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * 2 * std::max(1, R.n), c->stream));
@@ -420,9 +421,8 @@ int to_three_products(mtm_ctx* c, CallRoute& R) {
 // float32 refinement, the kernel candidates (everything above the threshold) overflowed: the potential peaks of a map scan
 // instead - far fewer
 int to_map_scan(mtm_ctx* c, CallRoute& R) {
+    ladder_apply(R, LadderStep::MapScan);
     back_off(c->fuse_backoff, c->backoff_len);
-    R.hits_only = false;
-    R.pp_mode = R.refine_scan = true;
     HIPC(hipMemsetAsync(c->cands.p, 0, 16, c->stream));
     return rescore(c, R);
 }
@@ -430,10 +430,9 @@ int to_map_scan(mtm_ctx* c, CallRoute& R) {
 // float32: the float64 kernel decides, on maps in memory (the refined lists overflowed, or a bound is too wide for the map
 // scan's tolerances)
 int to_float64(mtm_ctx* c, CallRoute& R) {
-    if (R.raw_rig) back_off(c->fuse_backoff, c->backoff_len);   // raw sums have no map-scan route: the next calls start here
-    R.raw_rig = R.refine = R.refine_scan = R.pp_mode = false;
-    R.fused = R.hits_only = R.ext = false;
-    R.f32_exact = true;
+    const bool raw_rig = R.raw_rig;
+    ladder_apply(R, LadderStep::Float64);
+    if (raw_rig) back_off(c->fuse_backoff, c->backoff_len);     // raw sums have no map-scan route: the next calls start here
     return rescore(c, R);
 }
 
@@ -441,21 +440,20 @@ int to_float64(mtm_ctx* c, CallRoute& R) {
 // full peak pass), this one takes the full peak pass.  (An overflow of the dense route's own list - row maxima only - is no
 // retry: the back-off it runs under keeps counting down.)
 int to_maps(mtm_ctx* c, CallRoute& R) {
-    R.fused = false;
+    const bool maps_in_memory = !R.hits_only;
+    ladder_apply(R, LadderStep::Maps);
     back_off(c->fuse_backoff, c->backoff_len);
-    if (!R.hits_only) return MTM_OK;
-    R.hits_only = false;                // no maps in memory: compute them (this call pays twice - the overflowed launch left early)
-    return rescore(c, R);
+    if (maps_in_memory) return MTM_OK;
+    return rescore(c, R);               // no maps in memory: compute them (this call pays twice - the overflowed launch left early)
 }
 
 // the per-segment lists of the flagged route are bounded in total: if growing them did not help, the full scan with its single
 // list takes over - the maps are complete unless the score pass left the unflagged segments out (then once more, in full:
 // the maps may be published)
 int leave_segments(mtm_ctx* c, CallRoute& R) {
-    R.sparse = false;
-    if (!R.seg_skip_used) return MTM_OK;
-    R.seg_skip_used = false;
-    return rescore(c, R);
+    const bool maps_complete = !R.seg_skip_used;
+    ladder_apply(R, LadderStep::GrowListLeaveSegments);
+    return maps_complete ? MTM_OK : rescore(c, R);
 }
 
 int ladder_exhausted() {
@@ -463,338 +461,353 @@ int ladder_exhausted() {
     return MTM_E_STATE;
 }
 
-// Synchronising half: waits for the stream, verifies / extracts the peaks, delivers the hits.
-int fm_end(mtm_ctx* c, CallRoute& R, mtm_hit* out, int64_t capacity, int64_t* n_out) {
-    HIPC(hipSetDevice(c->device));
-    const int mode = R.mode, n = R.n;
-    const float thr = R.thr;
-    const bool mode_min = R.mode_min;
-    const int64_t cand_cap = R.cand_cap;
-    const unsigned hash_mask = R.hash_mask;
-    std::vector<mtm_hit> hits;
-
-    if (mode == MTM_PEAKS_GLOBAL) {
-        std::vector<unsigned long long> best(2 * (size_t)std::max(1, n));
-        // passes: the first, then one per step down - three products, the float64 kernel (which lists nothing)
-        bool done = false;
-        for (int pass = 0; pass < 3 && !done; ++pass) {
-            if (!R.ext) {
-                MTMC(c->counters.ensure(sizeof(unsigned long long) * 2 * std::max(1, n)));
-                HIPC(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * 2 * std::max(1, n), c->stream));
-            }
-            if (n > 0 && !R.ext) {
-                const int nb = 256;
-                hipLaunchKernelGGL(extremum_kernel, dim3(nb, n), dim3(256), 0, c->stream, c->maps.as<float>(),
-                                   c->td.as<TemplDev>(), nb, c->counters.as<unsigned long long>());
-                HIPC(hipGetLastError());
-            }
-            HIPC(hipEventRecord(c->ev[2], c->stream));
-            HIPC(hipMemcpyAsync(best.data(), c->counters.p, sizeof(unsigned long long) * 2 * std::max(1, n),
-                                hipMemcpyDeviceToHost, c->stream));
-            unsigned long long nlisted = 0;
-            const bool refined = R.refine && R.ext;
-            if (refined)
-                HIPC(hipMemcpyAsync(&nlisted, c->cands.p, sizeof(nlisted), hipMemcpyDeviceToHost, c->stream));
-            HIPC(hipStreamSynchronize(c->stream));
-            if (!refined || (int64_t)nlisted <= cand_cap) {
-                if (refined && R.bf16_np == 1) c->np1_backoff_len = 16;
-                done = true;
-            } else if (R.bf16_np == 1) {
-                // (the one-product screen's bounds let more outputs reach their template's best than the list holds)
-                MTMC(to_three_products(c, R));
-            } else {
-                // more outputs within the margin of their template's best than the list holds (near-flat maps)
-                MTMC(to_float64(c, R));
-            }
-        }
-        if (!done) return ladder_exhausted();
-        for (int t = 0; t < n; ++t) {
-            const TemplDev& d = c->td_host[t];
-            hits.push_back(decode_extremum_key(best[2 * t + (mode_min ? 1 : 0)], mode_min, t, d.ow, d.cols, d.rows));
-        }
-    } else {
-        // ---- 2-D maps.  One device buffer holds [64-bit counter | per-template ints | hit records];
-        // the header and the first kHitPrefetch records come back in ONE copy.
-        // Fused path: the score-map kernel already appended every pixel above the threshold to the
-        // candidate list; verify_peaks_kernel keeps the 3x3 local maxima.  If the candidate list
-        // overflowed (dense maps), or on any non-MFMA class, the full peaks_kernel pass runs instead.
-        const int n2d = (int)c->list2d.size();
-        // [hit count | candidate count | spare word of the candidate header (float32 map mode: the "bound too wide" flag) | per-template ints]
-        const size_t hdr_bytes = round_up(3 * sizeof(unsigned long long) + sizeof(int) * (size_t)std::max(1, n), 16);
-        unsigned long long count = 0;
-        std::vector<int> tflags((size_t)std::max(1, n), 0);
-        std::vector<uint8_t> host_buf;
-        // Few candidates (the usual case): they come back in one copy and the 3x3 test runs on the host.
-        // Every pixel above the threshold is in the list (in both modes), so a neighbour that is not
-        // is <= threshold < candidate: the list alone decides.  Saves two kernels, three fills and a copy.
-        bool verified_on_host = false;
-        const float thr_q = mode_min ? -thr : thr;      // a hit's quality (score, or -score for minima) exceeds this
-        if (R.fused && n2d > 0 && !R.pp_mode) {
-            // the candidate list is already on its way into the pinned landing buffer (fm_begin: R.prefetched)
-            const size_t nfetch = R.cand_pin_n;
-            HIPC(hipStreamSynchronize(c->stream));
-            host_trace(c, 10);
-            uint8_t* land = static_cast<uint8_t*>(c->pinned);
-            unsigned long long ncand = 0;
-            if (R.pin_direct) {
-                // the window's slots fill from 0 upwards (every reserved slot below the capacity is written before the
-                // launch ends): the count is the first slot that still says "no record"
-                const mtm_hit* w = reinterpret_cast<const mtm_hit*>(land + 16);
-                while (ncand < nfetch && w[ncand].templ_idx >= 0) ++ncand;
-                if (ncand == nfetch) {      // window full: the list's real length is on the device (dense maps; rare)
-                    HIPC(hipMemcpyAsync(&ncand, c->cands.p, sizeof(ncand), hipMemcpyDeviceToHost, c->stream));
-                    HIPC(hipStreamSynchronize(c->stream));
-                }
-                std::memcpy(land, &ncand, sizeof(ncand));
-            }
-            std::memcpy(&ncand, land, sizeof(ncand));
-            std::memcpy(&c->timing.sclk_mhz, land + 8, sizeof(float));
-            if (ncand <= nfetch) {
-                // everything needed is on the host: clear the counter for the next call while this one finishes
-                // (unless this context's calls clear it in their own first kernel: banded uint8 calls)
-                if (!R.banded_u8 && hipMemsetAsync(c->cands.p, 0, 16, c->stream) == hipSuccess)
-                    c->cands_zeroed = c->cands.p;
-                const mtm_hit* cd = reinterpret_cast<const mtm_hit*>(land + 16);
-                // open-addressing table over the candidates (key -> index), kept in the context between calls
-                size_t tsize = 64;
-                while (tsize < 2 * (size_t)ncand + 8) tsize <<= 1;
-                std::vector<unsigned long long>& hk = c->vh_keys;
-                std::vector<int>& hv = c->vh_vals;
-                hk.assign(tsize, 0ull);
-                hv.resize(tsize);
-                const size_t tmask = tsize - 1;
-                auto key = [](int t, int y, int x) {
-                    return ((unsigned long long)(t + 1) << 42) | ((unsigned long long)y << 21) | (unsigned long long)x;
-                };
-                auto slot_of = [&](unsigned long long k) {
-                    size_t sidx = (size_t)((k * 0x9E3779B97F4A7C15ull) >> 20) & tmask;
-                    while (hk[sidx] != 0ull && hk[sidx] != k) sidx = (sidx + 1) & tmask;
-                    return sidx;
-                };
-                for (int i = 0; i < (int)ncand; ++i) {
-                    const unsigned long long k = key(cd[i].templ_idx, cd[i].y, cd[i].x);
-                    const size_t sidx = slot_of(k);
-                    if (hk[sidx] == 0ull) {         // (a pixel is listed once; keep the first if it ever were not)
-                        hk[sidx] = k;
-                        hv[sidx] = i;
-                    }
-                }
-                const float padv = (c->opt_border == MTM_BORDER_CONSTANT) ? 0.0f : -INFINITY;
-                for (int i = 0; i < (int)ncand; ++i) {
-                    const mtm_hit& h = cd[i];
-                    const TemplDev& d = c->td_host[h.templ_idx];
-                    const float v = mode_min ? -h.score : h.score;
-                    float mx = v;
-                    for (int dy = -1; dy <= 1; ++dy)
-                        for (int dx = -1; dx <= 1; ++dx) {
-                            if (!dy && !dx) continue;
-                            const int yy = h.y + dy, xx = h.x + dx;
-                            if (yy < 0 || yy >= d.oh || xx < 0 || xx >= d.ow) {
-                                mx = fmaxf(mx, padv);
-                                continue;
-                            }
-                            const size_t sidx = slot_of(key(h.templ_idx, yy, xx));
-                            if (hk[sidx] != 0ull) mx = fmaxf(mx, mode_min ? -cd[hv[sidx]].score : cd[hv[sidx]].score);
-                        }
-                    // (v > thr_q: every record the integer kernels list passes; the float32 screen lists with a margin)
-                    if (v == mx && v > thr_q) {
-                        hits.push_back(h);
-                        ++tflags[(size_t)h.templ_idx];
-                    }
-                }
-                count = hits.size();
-                verified_on_host = true;
-                if (R.refine && R.bf16_np == 1) c->np1_backoff_len = 16;
-            }
-        }
-        if (!verified_on_host && R.hits_only)
-            HIPC(hipMemsetAsync(c->chash.p, 0, ((size_t)hash_mask + 1) * sizeof(unsigned long long), c->stream));
-        if (R.pp_mode) R.fused = true;          // the potential peaks are in the candidate buffer, their neighbourhoods in the maps
-        DeviceNms dnms;                 // (the device's share of a suppression request, queued behind the flagged-segment peak pass)
-        // Passes: the first, then one per step down the ladder; no step is taken twice in a call.  Float32 refinement: three
-        // products, map scan, the float64 kernel or a grown list for the candidates (either ends them), a grown list for the
-        // full pass (it then holds every peak of the same maps) - 4 steps.  Integer candidates: the maps or a grown list, then
-        // the full pass's list - 2.  Flagged segments: their lists grown, left, the full pass's list grown - 3.  Hence at most
-        // 5 passes; a ladder that runs out is an internal error, never an empty list.
-        bool done = n2d == 0 || verified_on_host;
-        for (int attempt = 0; attempt < 5 && !done; ++attempt) {
-            dnms.queued = false;
-            MTMC(c->hits.ensure(hdr_bytes + sizeof(mtm_hit) * (size_t)c->hit_cap));
-            uint8_t* dbase = c->hits.as<uint8_t>();
-            HIPC(hipMemsetAsync(dbase, 0, hdr_bytes, c->stream));
-            unsigned long long* counter = reinterpret_cast<unsigned long long*>(dbase);
-            int* flags = reinterpret_cast<int*>(counter + 3);
-            mtm_hit* dhits = reinterpret_cast<mtm_hit*>(dbase + hdr_bytes);
-            if (R.fused) {
-                // counter[1] <- candidate count (for the overflow check on the host)
-                HIPC(hipMemcpyAsync(counter + 1, c->cands.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice,
-                                    c->stream));
-                const unsigned blocks = std::min((unsigned)((c->hit_cap + 255) / 256), 4096u);
-                const mtm_hit* dcands = reinterpret_cast<const mtm_hit*>(c->cands.as<uint8_t>() + 16);
-                if (R.hits_only) {
-                    unsigned long long* keys = c->chash.as<unsigned long long>();
-                    int* vals = reinterpret_cast<int*>(keys + (size_t)hash_mask + 1);
-                    hipLaunchKernelGGL(cand_hash_insert_kernel, dim3(blocks), dim3(256), 0, c->stream, dcands,
-                                       c->cands.as<unsigned long long>(), (unsigned long long)cand_cap, keys, vals,
-                                       hash_mask);
-                    hipLaunchKernelGGL(verify_hash_kernel, dim3(blocks), dim3(256), 0, c->stream, c->td.as<TemplDev>(),
-                                       mode_min ? 1 : 0, c->opt_border, dcands, c->cands.as<unsigned long long>(),
-                                       (unsigned long long)cand_cap, keys, vals, hash_mask, dhits,
-                                       (unsigned long long)c->hit_cap, counter, flags, thr_q);
-                } else {
-                    hipLaunchKernelGGL(verify_peaks_kernel, dim3(blocks), dim3(256), 0, c->stream,
-                                       c->maps.as<float>(), c->td.as<TemplDev>(), mode_min ? 1 : 0, c->opt_border,
-                                       dcands, c->cands.as<unsigned long long>(), (unsigned long long)cand_cap, dhits,
-                                       (unsigned long long)c->hit_cap, counter, flags, thr_q);
-                }
-            } else {
-                int max_oh = 0, max_ow = 0;
-                for (int t : c->list2d) {
-                    max_oh = std::max(max_oh, c->td_host[t].oh);
-                    max_ow = std::max(max_ow, c->td_host[t].ow);
-                }
-                const dim3 grd((max_ow + kPkCols - 1) / kPkCols, (max_oh + 4 * kPkRows - 1) / (4 * kPkRows), n2d);
-                if (R.sparse) {
-                    const dim3 grd((max_ow + kPkCols - 1) / kPkCols, (max_oh + 4 * kPkSparseRows - 1) / (4 * kPkSparseRows), n2d);
-                    // a list per (template, strip column) (at most 64 MB of them) + their counters, then one list for the host
-                    const unsigned long long n_lists = (unsigned long long)n2d * grd.x;
-                    const unsigned long long cap_t = std::max<unsigned long long>(
-                        256ull, std::min<unsigned long long>((unsigned long long)c->hit_cap / 8, (64ull << 20) / sizeof(mtm_hit) / n_lists));
-                    const size_t cnt_bytes = round_up(sizeof(unsigned long long) * (size_t)n_lists, 256);
-                    MTMC(c->hits_t.ensure(cnt_bytes + sizeof(mtm_hit) * (size_t)cap_t * (size_t)n_lists));
-                    unsigned long long* counts_t = c->hits_t.as<unsigned long long>();
-                    mtm_hit* hits_t = reinterpret_cast<mtm_hit*>(c->hits_t.as<uint8_t>() + cnt_bytes);
-                    HIPC(hipMemsetAsync(counts_t, 0, cnt_bytes, c->stream));
-                    hipLaunchKernelGGL(peaks_sparse_kernel, grd, dim3(256), 0, c->stream, c->maps.as<float>(),
-                                       c->td.as<TemplDev>(), c->tlist.as<int>() + c->list2d_off, mode_min ? 1 : 0, thr,
-                                       c->opt_border, hits_t, cap_t, counts_t, flags, c->seg_flags.as<uint8_t>(),
-                                       R.flag_tstride, R.flag_rstride, R.seg_skip_used ? 1 : 0);
-                    hipLaunchKernelGGL(compact_hits_kernel, dim3((unsigned)n_lists), dim3(256), 0, c->stream, hits_t, cap_t, counts_t,
-                                       (int)n_lists, dhits, (unsigned long long)c->hit_cap, counter);
-                    // a suppression request: its device share follows at once (it reads the list's length on the device)
-                    dnms = DeviceNms{};
-                    if (R.nms.on && R.nms.max_overlap >= 0.0)
-                        MTMC(queue_device_nms(c, R.nms, dhits, counter, mode_min, &dnms));
-                } else
-                    hipLaunchKernelGGL(peaks_kernel, grd, dim3(256), 0, c->stream, c->maps.as<float>(),
-                                       c->td.as<TemplDev>(), c->tlist.as<int>() + c->list2d_off, mode_min ? 1 : 0, thr,
-                                       c->opt_border, dhits, (unsigned long long)c->hit_cap, counter, flags);
-            }
-            HIPC(hipGetLastError());
-            HIPC(hipEventRecord(c->ev[2], c->stream));
-            const size_t first = std::min<size_t>(kHitPrefetch, (size_t)c->hit_cap);
-            host_buf.resize(hdr_bytes + sizeof(mtm_hit) * first);
-            HIPC(hipMemcpyAsync(host_buf.data(), dbase, host_buf.size(), hipMemcpyDeviceToHost, c->stream));
-            HIPC(hipStreamSynchronize(c->stream));
-            unsigned long long ncand = 0;
-            std::memcpy(&count, host_buf.data(), sizeof(count));
-            std::memcpy(&ncand, host_buf.data() + sizeof(count), sizeof(ncand));
-            std::memcpy(tflags.data(), host_buf.data() + 3 * sizeof(count), sizeof(int) * n);
-            unsigned int rig_wide = 0;
-            if (R.fused) std::memcpy(&rig_wide, host_buf.data() + 2 * sizeof(count), sizeof(rig_wide));
-            // float32 map mode: some output that could pass the threshold has an error bound beyond what the scan's
-            // tolerances cover (a low-contrast window beside a brightness step)
-            if (R.pp_mode && rig_wide != 0) {
-                MTMC(to_float64(c, R));
-                continue;
-            }
-            if (R.fused && (int64_t)ncand > cand_cap) {
-                if (!R.refine) MTMC(to_maps(c, R));
-                else if (!R.pp_mode && R.bf16_np == 1) MTMC(to_three_products(c, R));
-                else if (!R.pp_mode && !R.raw_rig) MTMC(to_map_scan(c, R));
-                else MTMC(to_float64(c, R));        // (the map scan's potential peaks overflowed too: plateau-rich maps)
-                continue;
-            }
-            if (R.fused && !R.pp_mode) c->backoff_len = 16;     // the candidates fitted
-            if (R.fused && !R.pp_mode && R.refine && R.bf16_np == 1) c->np1_backoff_len = 16;
-            if ((int64_t)count <= c->hit_cap) {
-                // thousands of peaks and a suppression request: decide on the device, fetch the kept ones
-                if (dnms.queued && R.sparse && !R.fused && (long long)count >= c->nms_device_min && count <= dnms.n_max) {
-                    bool trivial = false;       // (a map every pixel of which equals its local maximum loses its peaks below)
-                    for (int t : c->list2d) {
-                        const unsigned f = (unsigned)tflags[(size_t)t];
-                        trivial = trivial || ((f & 0xFFu) == 0 && !((f & 0xFF00u) != 0 && (f & 0xFF0000u) != 0));
-                    }
-                    if (!trivial) {
-                        MTMC(fetch_device_nms(c, dnms, count, hits, &R.nms_sure));
-                        R.nms_raw_count = (long long)count;
-                        done = true;
-                        break;
-                    }
-                }
-                hits.resize((size_t)count);
-                const size_t got = std::min<size_t>((size_t)count, first);
-                if (got) std::memcpy(hits.data(), host_buf.data() + hdr_bytes, sizeof(mtm_hit) * got);
-                if (count > got) {
-                    HIPC(hipMemcpyAsync(hits.data() + got, dhits + got, sizeof(mtm_hit) * ((size_t)count - got),
-                                        hipMemcpyDeviceToHost, c->stream));
-                    HIPC(hipStreamSynchronize(c->stream));
-                }
-                done = true;
-                break;
-            }
-            c->hit_cap = (int64_t)count + 1024;     // grow and rerun the compaction pass
-            R.fused = false;
-            if (R.sparse && attempt >= 1) MTMC(leave_segments(c, R));
-        }
-        if (!done) return ladder_exhausted();
-        if (n2d == 0) {
-            HIPC(hipEventRecord(c->ev[2], c->stream));
-            HIPC(hipStreamSynchronize(c->stream));
-        }
-        if (!hits.empty()) {
-            // skimage: a map in which every pixel equals its local maximum has no peaks at all.
-            // peaks_kernel: tflags[t] = "some pixel differs from its local max";
-            // fused path:   tflags[t] = number of peaks of t (all pixels <=> trivial).
-            hits.erase(std::remove_if(hits.begin(), hits.end(),
-                                      [&](const mtm_hit& h) {
-                                          const TemplDev& d = c->td_host[h.templ_idx];
-                                          if (d.oh <= 1 || d.ow <= 1) return true;   // 1-D / 1x1 maps: host path below
-                                          if (R.fused) return (long long)tflags[h.templ_idx] == (long long)d.oh * d.ow;
-                                          // (bytes 1 and 2: peaks_sparse_kernel - segments above and below the threshold exist)
-                                          const unsigned f = (unsigned)tflags[h.templ_idx];
-                                          return (f & 0xFFu) == 0 && !((f & 0xFF00u) != 0 && (f & 0xFF0000u) != 0);
-                                      }),
-                       hits.end());
-        }
-        // ---- 1x1 and 1-D maps (MTM/__init__.py:25-41) on the host
-        for (int t = 0; t < n; ++t) {
-            const TemplDev& d = c->td_host[t];
-            if (d.oh > 1 && d.ow > 1) continue;
-            const int len = std::max(d.oh, d.ow);
-            std::vector<float> line((size_t)len);
-            HIPC(hipMemcpy2DAsync(line.data(), sizeof(float) * (d.oh == 1 ? len : 1),
-                                  c->maps.as<float>() + d.map_off, sizeof(float) * d.map_pitch,
-                                  sizeof(float) * d.ow, d.oh, hipMemcpyDeviceToHost, c->stream));
-            HIPC(hipStreamSynchronize(c->stream));
-            line_map_peaks(line.data(), d.oh, d.ow, thr, mode_min, t, d.cols, d.rows, hits);
-        }
-        // deterministic order: template, then descending quality, then row-major position
-        host_trace(c, 11);
-        // (the device may have pruned the list already - queue_device_nms / fetch_device_nms -: the count of peaks is the one before that)
-        const int64_t n_raw = R.nms_raw_count >= 0 ? (int64_t)R.nms_raw_count : (int64_t)hits.size();
-        if (R.nms.on && n_raw > 1) {                    // MTM.NMS (a list of one hit is returned as it is: MTM/NMS.py:53-55)
-            const float thr_s = (float)(mode_min ? (1.0 - R.nms.score_threshold) : R.nms.score_threshold);
-            std::vector<int32_t> keep;
-            nms_select(hits.data(), (int64_t)hits.size(), mode_min ? 1 : 0, thr_s, (float)R.nms.max_overlap, keep,
-                       R.nms_raw_count >= 0 ? R.nms_sure : 0);
-            std::vector<mtm_hit> kept(keep.size());
-            for (size_t i = 0; i < keep.size(); ++i) kept[i] = hits[(size_t)keep[i]];
-            hits.swap(kept);
-        } else {
-            sort_hits(hits, mode_min);
-        }
-        if (R.nms.on && R.nms.n_object >= 0 && (long long)hits.size() > R.nms.n_object)
-            hits.resize((size_t)R.nms.n_object);                // MTM/NMS.py:81-82
-        c->timing.n_hits = n_raw;
-        host_trace(c, 12);
+// the step ladder_next named: its transition above, or - the pass found `count` peaks, more than the hit list holds - a list
+// with room for them
+int take_step(mtm_ctx* c, CallRoute& R, LadderStep step, unsigned long long count) {
+    switch (step) {
+        case LadderStep::Done: return MTM_OK;
+        case LadderStep::ThreeProducts: return to_three_products(c, R);
+        case LadderStep::MapScan: return to_map_scan(c, R);
+        case LadderStep::Float64: return to_float64(c, R);
+        case LadderStep::Maps: return to_maps(c, R);
+        case LadderStep::GrowList:
+        case LadderStep::GrowListLeaveSegments: break;
     }
-    HIPC(hipEventSynchronize(c->ev[2]));       // already complete: every path above synchronised the stream
+    c->hit_cap = (int64_t)count + 1024;     // grow and rerun the compaction pass
+    if (step == LadderStep::GrowListLeaveSegments) return leave_segments(c, R);
+    ladder_apply(R, step);
+    return MTM_OK;
+}
+
+// ---- fm_end, the synchronising half of a call, in stages.
+
+// MTM_PEAKS_GLOBAL: the per-template extremum keys (from the score kernels' epilogue, or extremum_kernel over the maps) ->
+// one record per template.  Passes: the first, then one per step down - three products, the float64 kernel (which lists
+// nothing).
+int collect_global_extremum(mtm_ctx* c, CallRoute& R, std::vector<mtm_hit>& hits) {
+    const int n = R.n;
+    const size_t key_bytes = sizeof(unsigned long long) * 2 * (size_t)std::max(1, n);
+    std::vector<unsigned long long> best(2 * (size_t)std::max(1, n));
+    bool done = false;
+    for (int pass = 0; pass < 3 && !done; ++pass) {
+        if (!R.ext) {
+            MTMC(c->counters.ensure(key_bytes));
+            HIPC(hipMemsetAsync(c->counters.p, 0, key_bytes, c->stream));
+        }
+        if (n > 0 && !R.ext) {
+            const int nb = 256;
+            hipLaunchKernelGGL(extremum_kernel, dim3(nb, n), dim3(256), 0, c->stream, c->maps.as<float>(),
+                               c->td.as<TemplDev>(), nb, c->counters.as<unsigned long long>());
+            HIPC(hipGetLastError());
+        }
+        HIPC(hipEventRecord(c->ev[2], c->stream));
+        HIPC(hipMemcpyAsync(best.data(), c->counters.p, key_bytes, hipMemcpyDeviceToHost, c->stream));
+        // refined: the outputs within the margin of their template's best are listed - more than the list holds?
+        unsigned long long nlisted = 0;
+        const bool refined = R.refine && R.ext;
+        if (refined) HIPC(hipMemcpyAsync(&nlisted, c->cands.p, sizeof(nlisted), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        const LadderStep step = ladder_next(R, PassOutcome{false, refined && (int64_t)nlisted > R.cand_cap, false}, pass);
+        if (step == LadderStep::Done) {
+            if (refined && R.bf16_np == 1) c->np1_backoff_len = 16;
+            done = true;
+        } else {
+            MTMC(take_step(c, R, step, 0));
+        }
+    }
+    if (!done) return ladder_exhausted();
+    for (int t = 0; t < n; ++t) {
+        const TemplDev& d = c->td_host[t];
+        hits.push_back(decode_extremum_key(best[2 * t + (R.mode_min ? 1 : 0)], R.mode_min, t, d.ow, d.cols, d.rows));
+    }
+    return MTM_OK;
+}
+
+// Few candidates (the usual case): they are in the pinned landing buffer when the stream is done (fm_begin: R.prefetched)
+// and the 3x3 test runs on the host (verify_candidates_3x3) - saves two kernels, three fills and a copy.  *verified: the
+// whole list was in the window; `hits` / `tflags` hold the result.
+int verify_on_host(mtm_ctx* c, CallRoute& R, std::vector<mtm_hit>& hits, int* tflags, bool* verified) {
+    const size_t nfetch = R.cand_pin_n;
+    HIPC(hipStreamSynchronize(c->stream));
+    host_trace(c, 10);
+    uint8_t* land = static_cast<uint8_t*>(c->pinned);
+    unsigned long long ncand = 0;
+    if (R.pin_direct) {
+        // the window's slots fill from 0 upwards (every reserved slot below the capacity is written before the
+        // launch ends): the count is the first slot that still says "no record"
+        const mtm_hit* w = reinterpret_cast<const mtm_hit*>(land + 16);
+        while (ncand < nfetch && w[ncand].templ_idx >= 0) ++ncand;
+        if (ncand == nfetch) {      // window full: the list's real length is on the device (dense maps; rare)
+            HIPC(hipMemcpyAsync(&ncand, c->cands.p, sizeof(ncand), hipMemcpyDeviceToHost, c->stream));
+            HIPC(hipStreamSynchronize(c->stream));
+        }
+        std::memcpy(land, &ncand, sizeof(ncand));
+    }
+    std::memcpy(&ncand, land, sizeof(ncand));
+    std::memcpy(&c->timing.sclk_mhz, land + 8, sizeof(float));
+    if (ncand > nfetch) return MTM_OK;
+    // everything needed is on the host: clear the counter for the next call while this one finishes
+    // (unless this context's calls clear it in their own first kernel: banded uint8 calls)
+    if (!R.banded_u8 && hipMemsetAsync(c->cands.p, 0, 16, c->stream) == hipSuccess) c->cands_zeroed = c->cands.p;
+    const TemplDev* td = c->td_host.data();
+    verify_candidates_3x3(reinterpret_cast<const mtm_hit*>(land + 16), (size_t)ncand, MapDims{&td->oh, &td->ow, sizeof(TemplDev)},
+                          R.mode_min, R.mode_min ? -R.thr : R.thr, c->opt_border == MTM_BORDER_CONSTANT ? 0.0f : -INFINITY,
+                          c->vh_keys, c->vh_vals, hits, tflags);
+    *verified = true;
+    if (R.refine && R.bf16_np == 1) c->np1_backoff_len = 16;
+    return MTM_OK;
+}
+
+// The hit buffer of a peak pass (mtm_ctx::hits), as the kernels read it: [hit count | candidate count | spare word of the
+// candidate header (float32 map mode: the "bound too wide" flag) | one int per template] [records].  The header and the
+// first kHitPrefetch records come back in ONE copy.
+struct HitBuffer {
+    size_t hdr_bytes;
+    uint8_t* base = nullptr;        // on the device
+    explicit HitBuffer(int n) : hdr_bytes(round_up(3 * sizeof(unsigned long long) + sizeof(int) * (size_t)std::max(1, n), 16)) {}
+    unsigned long long* count() const { return reinterpret_cast<unsigned long long*>(base); }
+    unsigned long long* cand_header() const { return count() + 1; }        // two words, as the candidate buffer starts
+    int* flags() const { return reinterpret_cast<int*>(count() + 3); }
+    mtm_hit* records() const { return reinterpret_cast<mtm_hit*>(base + hdr_bytes); }
+    // a host copy of the header
+    struct Header {
+        unsigned long long count, ncand;
+        unsigned rig_wide;
+    };
+    Header decode(const uint8_t* host, int n, int* tflags) const {
+        Header h{};
+        std::memcpy(&h.count, host, sizeof(h.count));
+        std::memcpy(&h.ncand, host + sizeof(h.count), sizeof(h.ncand));
+        std::memcpy(&h.rig_wide, host + 2 * sizeof(h.count), sizeof(h.rig_wide));
+        std::memcpy(tflags, host + 3 * sizeof(h.count), sizeof(int) * (size_t)n);
+        return h;
+    }
+    const uint8_t* host_records(const uint8_t* host) const { return host + hdr_bytes; }
+};
+
+// grid of the peak scans: strips of 4 * strip_rows rows x kPkCols columns over the largest 2-D map, one layer per map
+dim3 peak_grid(const mtm_ctx* c, int strip_rows) {
+    int max_oh = 0, max_ow = 0;
+    for (int t : c->list2d) {
+        max_oh = std::max(max_oh, c->td_host[t].oh);
+        max_ow = std::max(max_ow, c->td_host[t].ow);
+    }
+    return dim3((max_ow + kPkCols - 1) / kPkCols, (max_oh + 4 * strip_rows - 1) / (4 * strip_rows), (unsigned)c->list2d.size());
+}
+
+// One attempt of the device's peak pass, queued: the candidate list verified (against the hash table of its positions, or
+// the maps), else the maps scanned (the flagged segments, with compaction and the device's share of a suppression request,
+// or everything).
+int queue_peak_pass(mtm_ctx* c, const CallRoute& R, HitBuffer& hb, DeviceNms* dnms) {
+    *dnms = DeviceNms{};
+    const bool mode_min = R.mode_min;
+    const float thr_q = mode_min ? -R.thr : R.thr;      // a hit's quality (score, or -score for minima) exceeds this
+    const unsigned long long hit_cap = (unsigned long long)c->hit_cap;
+    MTMC(c->hits.ensure(hb.hdr_bytes + sizeof(mtm_hit) * (size_t)c->hit_cap));
+    hb.base = c->hits.as<uint8_t>();
+    HIPC(hipMemsetAsync(hb.base, 0, hb.hdr_bytes, c->stream));
+    if (R.fused) {
+        // the candidate count (for the overflow check on the host) and the spare word
+        HIPC(hipMemcpyAsync(hb.cand_header(), c->cands.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
+        const unsigned blocks = std::min((unsigned)((c->hit_cap + 255) / 256), 4096u);
+        const mtm_hit* dcands = reinterpret_cast<const mtm_hit*>(c->cands.as<uint8_t>() + 16);
+        if (R.hits_only) {
+            unsigned long long* keys = c->chash.as<unsigned long long>();
+            int* vals = reinterpret_cast<int*>(keys + (size_t)R.hash_mask + 1);
+            hipLaunchKernelGGL(cand_hash_insert_kernel, dim3(blocks), dim3(256), 0, c->stream, dcands,
+                               c->cands.as<unsigned long long>(), (unsigned long long)R.cand_cap, keys, vals, R.hash_mask);
+            hipLaunchKernelGGL(verify_hash_kernel, dim3(blocks), dim3(256), 0, c->stream, c->td.as<TemplDev>(),
+                               mode_min ? 1 : 0, c->opt_border, dcands, c->cands.as<unsigned long long>(),
+                               (unsigned long long)R.cand_cap, keys, vals, R.hash_mask, hb.records(), hit_cap, hb.count(),
+                               hb.flags(), thr_q);
+        } else {
+            hipLaunchKernelGGL(verify_peaks_kernel, dim3(blocks), dim3(256), 0, c->stream, c->maps.as<float>(),
+                               c->td.as<TemplDev>(), mode_min ? 1 : 0, c->opt_border, dcands, c->cands.as<unsigned long long>(),
+                               (unsigned long long)R.cand_cap, hb.records(), hit_cap, hb.count(), hb.flags(), thr_q);
+        }
+    } else if (R.sparse) {
+        const dim3 grd = peak_grid(c, kPkSparseRows);
+        // a list per (template, strip column) (at most 64 MB of them) + their counters, then one list for the host
+        const unsigned long long n_lists = (unsigned long long)grd.z * grd.x;
+        const unsigned long long cap_t = std::max<unsigned long long>(
+            256ull, std::min<unsigned long long>(hit_cap / 8, (64ull << 20) / sizeof(mtm_hit) / n_lists));
+        const size_t cnt_bytes = round_up(sizeof(unsigned long long) * (size_t)n_lists, 256);
+        MTMC(c->hits_t.ensure(cnt_bytes + sizeof(mtm_hit) * (size_t)cap_t * (size_t)n_lists));
+        unsigned long long* counts_t = c->hits_t.as<unsigned long long>();
+        mtm_hit* hits_t = reinterpret_cast<mtm_hit*>(c->hits_t.as<uint8_t>() + cnt_bytes);
+        HIPC(hipMemsetAsync(counts_t, 0, cnt_bytes, c->stream));
+        hipLaunchKernelGGL(peaks_sparse_kernel, grd, dim3(256), 0, c->stream, c->maps.as<float>(), c->td.as<TemplDev>(),
+                           c->tlist.as<int>() + c->list2d_off, mode_min ? 1 : 0, R.thr, c->opt_border, hits_t, cap_t, counts_t,
+                           hb.flags(), c->seg_flags.as<uint8_t>(), R.flag_tstride, R.flag_rstride, R.seg_skip_used ? 1 : 0);
+        hipLaunchKernelGGL(compact_hits_kernel, dim3((unsigned)n_lists), dim3(256), 0, c->stream, hits_t, cap_t, counts_t,
+                           (int)n_lists, hb.records(), hit_cap, hb.count());
+        // a suppression request: its device share follows at once (it reads the list's length on the device)
+        if (R.nms.on && R.nms.max_overlap >= 0.0) MTMC(queue_device_nms(c, R.nms, hb.records(), hb.count(), mode_min, dnms));
+    } else {
+        hipLaunchKernelGGL(peaks_kernel, peak_grid(c, kPkRows), dim3(256), 0, c->stream, c->maps.as<float>(),
+                           c->td.as<TemplDev>(), c->tlist.as<int>() + c->list2d_off, mode_min ? 1 : 0, R.thr, c->opt_border,
+                           hb.records(), hit_cap, hb.count(), hb.flags());
+    }
+    HIPC(hipGetLastError());
+    return MTM_OK;
+}
+
+// The one copy behind a peak pass - header + first kHitPrefetch records into host_buf - and what it says: the number of
+// peaks, the per-template ints, what overflowed.
+int fetch_pass_outcome(mtm_ctx* c, const CallRoute& R, const HitBuffer& hb, std::vector<uint8_t>& host_buf, int* tflags,
+                       unsigned long long* count, PassOutcome* o) {
+    HIPC(hipEventRecord(c->ev[2], c->stream));
+    host_buf.resize(hb.hdr_bytes + sizeof(mtm_hit) * std::min<size_t>(kHitPrefetch, (size_t)c->hit_cap));
+    HIPC(hipMemcpyAsync(host_buf.data(), hb.base, host_buf.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    const HitBuffer::Header h = hb.decode(host_buf.data(), R.n, tflags);
+    *count = h.count;
+    o->rig_wide = R.fused && h.rig_wide != 0;
+    o->cands_overflow = R.fused && (int64_t)h.ncand > R.cand_cap;
+    o->hits_overflow = (int64_t)h.count > c->hit_cap;
+    return MTM_OK;
+}
+
+// The `count` peaks of a pass whose lists held everything: from host_buf and, beyond the prefetched ones, the device.
+// Thousands of peaks and a suppression request: decided on the device, only the kept ones are fetched.
+int fetch_peak_list(mtm_ctx* c, CallRoute& R, const HitBuffer& hb, const std::vector<uint8_t>& host_buf, unsigned long long count,
+                    const int* tflags, const DeviceNms& dnms, std::vector<mtm_hit>& hits) {
+    if (dnms.queued && R.sparse && !R.fused && (long long)count >= c->nms_device_min && count <= dnms.n_max) {
+        bool trivial = false;       // (a map every pixel of which equals its local maximum loses its peaks: drop_trivial_maps)
+        for (int t : c->list2d) trivial = trivial || scan_flags_trivial((unsigned)tflags[(size_t)t]);
+        if (!trivial) {
+            MTMC(fetch_device_nms(c, dnms, count, hits, &R.nms_sure));
+            R.nms_raw_count = (long long)count;
+            return MTM_OK;
+        }
+    }
+    hits.resize((size_t)count);
+    const size_t got = std::min<size_t>((size_t)count, (host_buf.size() - hb.hdr_bytes) / sizeof(mtm_hit));
+    if (got) std::memcpy(hits.data(), hb.host_records(host_buf.data()), sizeof(mtm_hit) * got);
+    if (count > got) {
+        HIPC(hipMemcpyAsync(hits.data() + got, hb.records() + got, sizeof(mtm_hit) * ((size_t)count - got),
+                            hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+    }
+    return MTM_OK;
+}
+
+// skimage: a map in which every pixel equals its local maximum has no peaks at all (the scans' flag words, the candidate
+// routes' peak counts: mtm_internal.h).  1-D / 1x1 maps: append_line_map_peaks.  tflags[t] becomes "t's records go".
+void drop_trivial_maps(const mtm_ctx* c, const CallRoute& R, std::vector<int>& tflags, std::vector<mtm_hit>& hits) {
+    if (hits.empty()) return;
+    for (int t = 0; t < R.n; ++t) {
+        const TemplDev& d = c->td_host[t];
+        const int f = tflags[(size_t)t];
+        tflags[(size_t)t] = d.oh <= 1 || d.ow <= 1 || (R.fused ? fused_count_trivial(f, d.oh, d.ow) : scan_flags_trivial((unsigned)f));
+    }
+    hits.erase(std::remove_if(hits.begin(), hits.end(), [&](const mtm_hit& h) { return tflags[(size_t)h.templ_idx] != 0; }),
+               hits.end());
+}
+
+// 1x1 and 1-D maps (MTM/__init__.py:25-41) on the host.  The maps in memory are those of a stack of nb images of `rows`
+// rows each (one image: nb = 1, rows = its rows); image b's records go to per_img[b].
+int append_line_map_peaks(mtm_ctx* c, float thr, bool mode_min, int nb, int rows, std::vector<mtm_hit>* per_img) {
+    for (int t = 0; t < (int)c->templs.size(); ++t) {
+        const TemplDev& d = c->td_host[t];
+        const int oh_b = rows - d.rows + 1;
+        if (oh_b > 1 && d.ow > 1) continue;
+        std::vector<float> mp((size_t)d.oh * d.ow);
+        HIPC(hipMemcpy2DAsync(mp.data(), sizeof(float) * d.ow, c->maps.as<float>() + d.map_off, sizeof(float) * d.map_pitch,
+                              sizeof(float) * d.ow, d.oh, hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        for (int b = 0; b < nb; ++b)        // (a row, or a column of a one-column map)
+            line_map_peaks(mp.data() + (size_t)b * rows * d.ow, oh_b, d.ow, thr, mode_min, t, d.cols, d.rows, per_img[b]);
+    }
+    return MTM_OK;
+}
+
+// deterministic order: template, then descending quality, then row-major position - or, with a suppression request, MTM.NMS'
+// selection in its order; timing.n_hits = the peaks before that
+void order_and_suppress(mtm_ctx* c, const CallRoute& R, std::vector<mtm_hit>& hits) {
+    host_trace(c, 11);
+    const bool mode_min = R.mode_min;
+    // (the device may have pruned the list already - queue_device_nms / fetch_device_nms -: the count of peaks is the one before that)
+    const int64_t n_raw = R.nms_raw_count >= 0 ? (int64_t)R.nms_raw_count : (int64_t)hits.size();
+    if (R.nms.on && n_raw > 1) {                    // MTM.NMS (a list of one hit is returned as it is: MTM/NMS.py:53-55)
+        const float thr_s = (float)(mode_min ? (1.0 - R.nms.score_threshold) : R.nms.score_threshold);
+        std::vector<int32_t> keep;
+        nms_select(hits.data(), (int64_t)hits.size(), mode_min ? 1 : 0, thr_s, (float)R.nms.max_overlap, keep,
+                   R.nms_raw_count >= 0 ? R.nms_sure : 0);
+        std::vector<mtm_hit> kept(keep.size());
+        for (size_t i = 0; i < keep.size(); ++i) kept[i] = hits[(size_t)keep[i]];
+        hits.swap(kept);
+    } else {
+        sort_hits(hits, mode_min);
+    }
+    if (R.nms.on && R.nms.n_object >= 0 && (long long)hits.size() > R.nms.n_object)
+        hits.resize((size_t)R.nms.n_object);                // MTM/NMS.py:81-82
+    c->timing.n_hits = n_raw;
+    host_trace(c, 12);
+}
+
+// the call's GPU times from its three events (ev[2] is complete: every path synchronised the stream behind it)
+int finish_call_timing(mtm_ctx* c) {
+    HIPC(hipEventSynchronize(c->ev[2]));
     HIPC(hipEventElapsedTime(&c->timing.score_ms, c->ev[0], c->ev[1]));
     HIPC(hipEventElapsedTime(&c->timing.peaks_ms, c->ev[1], c->ev[2]));
     HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[2]));
-    MTMC(collect_ncc_time(c));
-    if (mode != MTM_PEAKS_LOCAL || !R.nms.on) c->timing.n_hits = (int64_t)hits.size();
+    return collect_ncc_time(c);
+}
+
+// Synchronising half: waits for the stream, verifies / extracts the peaks, delivers the hits.
+int fm_end(mtm_ctx* c, CallRoute& R, mtm_hit* out, int64_t capacity, int64_t* n_out) {
+    HIPC(hipSetDevice(c->device));
+    std::vector<mtm_hit> hits;
+    if (R.mode == MTM_PEAKS_GLOBAL) {
+        MTMC(collect_global_extremum(c, R, hits));
+    } else {
+        // ---- 2-D maps.  Fused path: the score kernels appended every pixel above the threshold to the candidate list; the
+        // 3x3 local maxima among them are hits.  If the list overflowed (dense maps), or on any class without candidates,
+        // the peak pass scans the maps instead.
+        const bool any2d = !c->list2d.empty();
+        std::vector<int> tflags((size_t)std::max(1, R.n), 0);
+        bool done = false;
+        if (R.fused && any2d && !R.pp_mode) MTMC(verify_on_host(c, R, hits, tflags.data(), &done));
+        if (!done && R.hits_only)
+            HIPC(hipMemsetAsync(c->chash.p, 0, ((size_t)R.hash_mask + 1) * sizeof(unsigned long long), c->stream));
+        if (R.pp_mode) R.fused = true;          // the potential peaks are in the candidate buffer, their neighbourhoods in the maps
+        done = done || !any2d;
+        HitBuffer hb(R.n);
+        std::vector<uint8_t> host_buf;
+        DeviceNms dnms;                 // (the device's share of a suppression request, queued behind the flagged-segment peak pass)
+        // Passes: the first, then one per step down the ladder (ladder_next; tests/native/sanitize_host.cpp walks every
+        // sequence the device can report: no step but a grown list twice, at most 5 passes).  A ladder that runs out is an
+        // internal error, never an empty list.
+        for (int attempt = 0; attempt < 5 && !done; ++attempt) {
+            unsigned long long count = 0;
+            PassOutcome outcome{};
+            MTMC(queue_peak_pass(c, R, hb, &dnms));
+            MTMC(fetch_pass_outcome(c, R, hb, host_buf, tflags.data(), &count, &outcome));
+            const LadderStep step = ladder_next(R, outcome, attempt);
+            const bool grow = step == LadderStep::GrowList || step == LadderStep::GrowListLeaveSegments;
+            if ((step == LadderStep::Done || grow) && R.fused && !R.pp_mode) {      // the candidates fitted
+                c->backoff_len = 16;
+                if (R.refine && R.bf16_np == 1) c->np1_backoff_len = 16;
+            }
+            if (step == LadderStep::Done) {
+                MTMC(fetch_peak_list(c, R, hb, host_buf, count, tflags.data(), dnms, hits));
+                done = true;
+            } else {
+                MTMC(take_step(c, R, step, count));
+            }
+        }
+        if (!done) return ladder_exhausted();
+        if (!any2d) {
+            HIPC(hipEventRecord(c->ev[2], c->stream));
+            HIPC(hipStreamSynchronize(c->stream));
+        }
+        drop_trivial_maps(c, R, tflags, hits);
+        MTMC(append_line_map_peaks(c, R.thr, R.mode_min, 1, c->rows, &hits));
+        order_and_suppress(c, R, hits);
+    }
+    MTMC(finish_call_timing(c));
+    if (R.mode != MTM_PEAKS_LOCAL || !R.nms.on) c->timing.n_hits = (int64_t)hits.size();
     // what the call's route came to
     c->timing.hits_only = R.sparse ? 2 : R.hits_only ? 1 : 0;
     c->timing.f32_route = R.mbf_used ? 4 : R.f32_exact ? 3 : !R.refine ? 0 : (R.refine_scan ? 2 : 1);
@@ -881,14 +894,9 @@ int batch_chunk(mtm_ctx* c, const void* const* px, int nb, int rows, int cols, i
         std::vector<int> nontriv((size_t)nb * std::max(1, n), 0);
         std::vector<mtm_hit> hits;
         if (n2d > 0) {
-            int max_oh = 0, max_ow = 0;
-            for (int t : c->list2d) {
-                max_oh = std::max(max_oh, c->td_host[t].oh);
-                max_ow = std::max(max_ow, c->td_host[t].ow);
-            }
             // [hit count | nontrivial flag per (image, template)] [records]
             const size_t hdr = round_up(sizeof(unsigned long long) + sizeof(int) * nontriv.size(), 16);
-            const dim3 grd((max_ow + kPkCols - 1) / kPkCols, (max_oh + 4 * kPkRows - 1) / (4 * kPkRows), n2d);
+            const dim3 grd = peak_grid(c, kPkRows);
             bool done = false;
             for (int pass = 0; pass < 2 && !done; ++pass) {         // (a list that overflowed: once more, large enough)
                 MTMC(c->hits.ensure(hdr + sizeof(mtm_hit) * (size_t)c->hit_cap));
@@ -928,25 +936,10 @@ int batch_chunk(mtm_ctx* c, const void* const* px, int nb, int rows, int cols, i
             r.y -= b * rows;
             per_img[b].push_back(r);
         }
-        // 1-D and 1x1 per-image maps (MTM/__init__.py:25-41) on the host, as fm_end does for one image
-        for (int t = 0; t < n; ++t) {
-            const TemplDev& d = c->td_host[t];
-            const int oh_b = rows - d.rows + 1;
-            if (oh_b > 1 && d.ow > 1) continue;
-            std::vector<float> mp((size_t)d.oh * d.ow);
-            HIPC(hipMemcpy2DAsync(mp.data(), sizeof(float) * d.ow, maps + d.map_off, sizeof(float) * d.map_pitch,
-                                  sizeof(float) * d.ow, d.oh, hipMemcpyDeviceToHost, c->stream));
-            HIPC(hipStreamSynchronize(c->stream));
-            for (int b = 0; b < nb; ++b)        // (a row, or a column of a one-column map)
-                line_map_peaks(mp.data() + (size_t)b * rows * d.ow, oh_b, d.ow, thr, mode_min, t, d.cols, d.rows, per_img[b]);
-        }
+        MTMC(append_line_map_peaks(c, thr, mode_min, nb, rows, per_img));
         for (int b = 0; b < nb; ++b) sort_hits(per_img[b], mode_min);
     }
-    HIPC(hipEventSynchronize(c->ev[2]));
-    HIPC(hipEventElapsedTime(&c->timing.score_ms, c->ev[0], c->ev[1]));
-    HIPC(hipEventElapsedTime(&c->timing.peaks_ms, c->ev[1], c->ev[2]));
-    HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[2]));
-    return collect_ncc_time(c);
+    return finish_call_timing(c);
 }
 
 }  // namespace

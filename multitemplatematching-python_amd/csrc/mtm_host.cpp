@@ -1,6 +1,7 @@
-// Host-only parts of libmtm_hip.so: error string, template statistics, 1-D peak finding and the
-// NMS.  Nothing here touches the GPU, so these entry points also work on a machine without one
-// (the CPU test-suite exercises mtm_nms through the C ABI).
+// Host-only parts of libmtm_hip.so: error string, template statistics, 1-D peak finding, the NMS,
+// and what fm_end decides without the device (the 3x3 test of the candidate list, the overflow
+// ladder).  Nothing here touches the GPU, so these entry points also work on a machine without one
+// (the CPU test-suite exercises mtm_nms through the C ABI, tests/native/sanitize_host.cpp the rest).
 #include <algorithm>
 #include <cmath>
 #include <cfloat>
@@ -257,6 +258,101 @@ int publish_hits(std::vector<mtm_hit>& hits, std::vector<mtm_hit>& last_hits, mt
                  int64_t* n_out, const std::string& msg) {
     last_hits.swap(hits);
     return copy_out_hits(last_hits, out, capacity, n_out, msg);
+}
+
+// ---------------------------------------------------------------------------------------------
+// mtm_find_matches' synchronising half (fm_end, mtm_api.hip): what needs no device.
+// ---------------------------------------------------------------------------------------------
+void verify_candidates_3x3(const mtm_hit* cd, size_t ncand, const MapDims& dims, bool mode_min, float thr_q, float padv,
+                           std::vector<unsigned long long>& hk, std::vector<int>& hv, std::vector<mtm_hit>& hits, int* tflags) {
+    // open-addressing table over the candidates (key -> index)
+    size_t tsize = 64;
+    while (tsize < 2 * ncand + 8) tsize <<= 1;
+    hk.assign(tsize, 0ull);
+    hv.resize(tsize);
+    const size_t tmask = tsize - 1;
+    auto key = [](int t, int y, int x) {
+        return ((unsigned long long)(t + 1) << 42) | ((unsigned long long)y << 21) | (unsigned long long)x;
+    };
+    auto slot_of = [&](unsigned long long k) {
+        size_t sidx = (size_t)((k * 0x9E3779B97F4A7C15ull) >> 20) & tmask;
+        while (hk[sidx] != 0ull && hk[sidx] != k) sidx = (sidx + 1) & tmask;
+        return sidx;
+    };
+    for (int i = 0; i < (int)ncand; ++i) {
+        const unsigned long long k = key(cd[i].templ_idx, cd[i].y, cd[i].x);
+        const size_t sidx = slot_of(k);
+        if (hk[sidx] == 0ull) {         // (a pixel is listed once; keep the first if it ever were not)
+            hk[sidx] = k;
+            hv[sidx] = i;
+        }
+    }
+    for (int i = 0; i < (int)ncand; ++i) {
+        const mtm_hit& h = cd[i];
+        const int oh = dims.oh(h.templ_idx), ow = dims.ow(h.templ_idx);
+        const float v = mode_min ? -h.score : h.score;
+        float mx = v;
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) {
+                if (!dy && !dx) continue;
+                const int yy = h.y + dy, xx = h.x + dx;
+                if (yy < 0 || yy >= oh || xx < 0 || xx >= ow) {
+                    mx = fmaxf(mx, padv);
+                    continue;
+                }
+                const size_t sidx = slot_of(key(h.templ_idx, yy, xx));
+                if (hk[sidx] != 0ull) mx = fmaxf(mx, mode_min ? -cd[hv[sidx]].score : cd[hv[sidx]].score);
+            }
+        // (v > thr_q: every record the integer kernels list passes; the float32 screen lists with a margin)
+        if (v == mx && v > thr_q) {
+            hits.push_back(h);
+            ++tflags[(size_t)h.templ_idx];
+        }
+    }
+}
+
+bool scan_flags_trivial(unsigned f) { return (f & 0xFFu) == 0 && !((f & 0xFF00u) != 0 && (f & 0xFF0000u) != 0); }
+bool fused_count_trivial(long long n_peaks, int oh, int ow) { return n_peaks == (long long)oh * ow; }
+
+LadderStep ladder_next(const mtmi::CallRoute& R, const PassOutcome& o, int attempt) {
+    if (R.mode == MTM_PEAKS_GLOBAL) {
+        if (!(R.refine && R.ext) || !o.cands_overflow) return LadderStep::Done;
+        // the one-product screen's bounds let more outputs reach their template's best than the list holds: three products;
+        // still more within the margin of their template's best (near-flat maps): the float64 kernel
+        return R.bf16_np == 1 ? LadderStep::ThreeProducts : LadderStep::Float64;
+    }
+    // float32 map mode: some output that could pass the threshold has an error bound beyond what the scan's
+    // tolerances cover (a low-contrast window beside a brightness step)
+    if (R.pp_mode && o.rig_wide) return LadderStep::Float64;
+    if (R.fused && o.cands_overflow) {
+        if (!R.refine) return LadderStep::Maps;
+        if (!R.pp_mode && R.bf16_np == 1) return LadderStep::ThreeProducts;
+        if (!R.pp_mode && !R.raw_rig) return LadderStep::MapScan;
+        return LadderStep::Float64;         // (the map scan's potential peaks overflowed too: plateau-rich maps)
+    }
+    if (!o.hits_overflow) return LadderStep::Done;
+    return R.sparse && attempt >= 1 ? LadderStep::GrowListLeaveSegments : LadderStep::GrowList;
+}
+
+void ladder_apply(mtmi::CallRoute& R, LadderStep s) {
+    switch (s) {
+        case LadderStep::Done: break;
+        case LadderStep::ThreeProducts: R.bf16_np = 3; break;
+        case LadderStep::MapScan:
+            R.hits_only = false;
+            R.pp_mode = R.refine_scan = true;
+            break;
+        case LadderStep::Float64:
+            R.raw_rig = R.refine = R.refine_scan = R.pp_mode = false;
+            R.fused = R.hits_only = R.ext = false;
+            R.f32_exact = true;
+            break;
+        case LadderStep::Maps: R.fused = R.hits_only = false; break;
+        case LadderStep::GrowListLeaveSegments:
+            R.sparse = R.seg_skip_used = false;
+            [[fallthrough]];
+        case LadderStep::GrowList: R.fused = false; break;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/mtm_hip.h"
+#include "mtm_route.h"
 
 namespace mtm {
 
@@ -67,6 +68,52 @@ mtm_hit decode_quality_key(unsigned long long key, bool mode_min, int templ_idx,
 int copy_out_hits(const std::vector<mtm_hit>& hits, mtm_hit* out, int64_t capacity, int64_t* n_out, const std::string& msg);
 int publish_hits(std::vector<mtm_hit>& hits, std::vector<mtm_hit>& last_hits, mtm_hit* out, int64_t capacity,
                  int64_t* n_out, const std::string& msg);
+
+// ---- mtm_find_matches' synchronising half (fm_end, mtm_api.hip): its host-only pieces
+
+// (oh, ow) of template t's map, read in place from any array of records that holds both (`stride` bytes apart)
+struct MapDims {
+    const int* oh0;
+    const int* ow0;
+    size_t stride;
+    int oh(int t) const { return *reinterpret_cast<const int*>(reinterpret_cast<const char*>(oh0) + stride * (size_t)t); }
+    int ow(int t) const { return *reinterpret_cast<const int*>(reinterpret_cast<const char*>(ow0) + stride * (size_t)t); }
+};
+// The 3x3 test of a complete candidate list `cd[0 .. ncand)`: every pixel whose quality (score, or -score with mode_min)
+// exceeds thr_q is in the list, so a neighbour that is not is <= thr_q < candidate - the list alone decides.  A candidate
+// is a hit when its quality exceeds thr_q and is no less than any listed neighbour's, nor than `padv` (0 for the constant
+// border, -INFINITY else) where a neighbour lies outside the map; of a duplicated record the first counts.  Hits are
+// appended to `hits` in list order and counted per template in tflags[t] (+= 1 each).  hk / hv: scratch the caller keeps
+// between calls (an open-addressing table, rebuilt here; they need not be cleared).
+void verify_candidates_3x3(const mtm_hit* cd, size_t ncand, const MapDims& dims, bool mode_min, float thr_q, float padv,
+                           std::vector<unsigned long long>& hk, std::vector<int>& hv, std::vector<mtm_hit>& hits, int* tflags);
+
+// skimage: a map in which every pixel equals its local maximum has no peaks at all.  The scans' per-template flag word:
+// byte 0 = "some pixel differs from its local maximum" (peaks_kernel), bytes 1 and 2 = "a segment above / below the
+// threshold exists" (peaks_sparse_kernel, which never looks at the unflagged ones).  The candidate routes count a template's
+// peaks instead: every pixel a peak <=> trivial.
+bool scan_flags_trivial(unsigned flags);
+bool fused_count_trivial(long long n_peaks, int oh, int ow);
+
+// The overflow ladder of fm_end.  A pass reports what overflowed; ladder_next names the step that follows (today's route
+// and the number of the pass decide it), ladder_apply makes the step's changes to the route.  The effects of a step -
+// re-running the score pass, clearing lists, the context's back-off counters, a longer hit list - are fm_end's.
+enum class LadderStep {
+    Done,                   // the pass's list is the result
+    ThreeProducts,          // float32 refinement, the one-product screen listed too much: three piece products
+    MapScan,                // ... the kernel candidates overflowed: the potential peaks of a map scan
+    Float64,                // ... those too, a bound too wide for the scan, raw sums, the global extremum: the float64 kernel
+    Maps,                   // integer candidates overflowed: maps in memory, full peak pass
+    GrowList,               // more peaks than the hit list holds: once more with room for all of them
+    GrowListLeaveSegments,  // ... and the flagged segments' bounded lists were the reason: the full scan's single list
+};
+struct PassOutcome {
+    bool rig_wide;          // map scan: a bound beyond its tolerances
+    bool cands_overflow;    // more candidates (global extremum: outputs within the margin of the best) than the list holds
+    bool hits_overflow;     // more peaks than the hit list holds
+};
+LadderStep ladder_next(const mtmi::CallRoute& R, const PassOutcome& o, int attempt);
+void ladder_apply(mtmi::CallRoute& R, LadderStep s);
 
 // float32-faithful restatement of cv2.dnn.NMSBoxes as called by MTM.NMS
 void nms_boxes(const mtm_hit* hits, int64_t n, const float* scores, float score_threshold,

@@ -485,8 +485,226 @@ static void test_host(std::mt19937& rng) {
     CHECK(mtm_nms(nullptr, 5, 0.5, 0, -1, 0.5, nullptr, &nk) == MTM_E_INVALID && std::strlen(mtm_last_error()) > 0);
 }
 
+// ---- the host-only pieces of fm_end (mtm_api.hip): the 3x3 test of the candidate list, the trivial-map rule, the ladder
+
+// one case of verify_candidates_3x3 against brute force over the maps: `maps[t]` the scores of an oh[t] x ow[t] map, the list
+// every pixel whose quality exceeds thr_q, shuffled; the scratch vectors come from the caller as they are
+static void verify_case(const std::vector<int>& oh, const std::vector<int>& ow, const std::vector<std::vector<float>>& maps,
+                        bool mode_min, float thr_q, float padv, std::mt19937& rng, std::vector<unsigned long long>& hk,
+                        std::vector<int>& hv) {
+    const int nt = (int)maps.size();
+    auto q = [&](int t, int y, int x) { return mode_min ? -maps[(size_t)t][(size_t)y * ow[(size_t)t] + x] : maps[(size_t)t][(size_t)y * ow[(size_t)t] + x]; };
+    std::vector<mtm_hit> list;
+    std::vector<std::tuple<int, int, int>> expect;
+    std::vector<int> expect_n((size_t)nt, 0);
+    for (int t = 0; t < nt; ++t)
+        for (int y = 0; y < oh[(size_t)t]; ++y)
+            for (int x = 0; x < ow[(size_t)t]; ++x) {
+                const float v = q(t, y, x);
+                if (!(v > thr_q)) continue;
+                mtm_hit h{t, x, y, 7 + t, 9 + t, maps[(size_t)t][(size_t)y * ow[(size_t)t] + x]};
+                list.push_back(h);
+                bool peak = true;
+                for (int dy = -1; dy <= 1; ++dy)
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        if (!dy && !dx) continue;
+                        const int yy = y + dy, xx = x + dx;
+                        const bool inside = yy >= 0 && yy < oh[(size_t)t] && xx >= 0 && xx < ow[(size_t)t];
+                        peak = peak && v >= (inside ? q(t, yy, xx) : padv);
+                    }
+                if (peak) {
+                    expect.emplace_back(t, y, x);
+                    ++expect_n[(size_t)t];
+                }
+            }
+    std::shuffle(list.begin(), list.end(), rng);
+    mtm_hit sentinel{};
+    sentinel.templ_idx = -7;
+    std::vector<mtm_hit> hits(1, sentinel);         // (hits are appended)
+    std::vector<int> tflags((size_t)nt, 0);
+    verify_candidates_3x3(list.data(), list.size(), MapDims{oh.data(), ow.data(), sizeof(int)}, mode_min, thr_q, padv, hk, hv, hits,
+                          tflags.data());
+    CHECK(hits[0].templ_idx == -7 && hits.size() == 1 + expect.size());
+    std::vector<std::tuple<int, int, int>> got;
+    for (size_t i = 1; i < hits.size(); ++i) {
+        const mtm_hit& h = hits[i];
+        CHECK(h.templ_idx >= 0 && h.templ_idx < nt && h.w == 7 + h.templ_idx && h.h == 9 + h.templ_idx);
+        CHECK(std::memcmp(&h.score, &maps[(size_t)h.templ_idx][(size_t)h.y * ow[(size_t)h.templ_idx] + h.x], 4) == 0);
+        got.emplace_back(h.templ_idx, h.y, h.x);
+    }
+    std::sort(got.begin(), got.end());
+    CHECK(got == expect);                           // (expect was built in (t, y, x) order)
+    for (int t = 0; t < nt; ++t) CHECK(tflags[(size_t)t] == expect_n[(size_t)t]);
+}
+
+static void test_verify_candidates(std::mt19937& rng) {
+    std::vector<unsigned long long> hk;             // one pair of scratch vectors through every case, never cleared here
+    std::vector<int> hv;
+    for (int rep = 0; rep < 400; ++rep) {
+        const int nt = 1 + (int)(rng() % 3);
+        std::vector<int> oh((size_t)nt), ow((size_t)nt);
+        std::vector<std::vector<float>> maps((size_t)nt);
+        for (int t = 0; t < nt; ++t) {
+            oh[(size_t)t] = 1 + (int)(rng() % 12);
+            ow[(size_t)t] = 1 + (int)(rng() % 12);
+            maps[(size_t)t].resize((size_t)oh[(size_t)t] * ow[(size_t)t]);
+            for (float& v : maps[(size_t)t]) v = 0.25f * (float)(rng() % 5);          // five levels: plateaus and ties
+        }
+        const bool mode_min = (rep & 1) != 0;
+        const float thr = 0.25f * (float)(rng() % 5) + (rng() % 3 == 0 ? -0.3f : 0.1f);
+        verify_case(oh, ow, maps, mode_min, mode_min ? -thr : thr, (rep & 2) ? 0.0f : -INFINITY, rng, hk, hv);
+    }
+    for (float padv : {0.0f, -INFINITY}) {
+        // the empty list
+        std::vector<mtm_hit> hits;
+        int flag = 0;
+        const int one = 5;
+        verify_candidates_3x3(nullptr, 0, MapDims{&one, &one, sizeof(int)}, false, 0.5f, padv, hk, hv, hits, &flag);
+        CHECK(hits.empty() && flag == 0);
+        // an all-equal map above the threshold: every pixel is returned, and the fused trivial predicate says "drop"
+        for (int oh : {1, 4, 12})
+            for (int ow : {1, 7}) {
+                std::vector<std::vector<float>> flat(1, std::vector<float>((size_t)oh * ow, 0.75f));
+                verify_case({oh}, {ow}, flat, false, 0.5f, padv, rng, hk, hv);
+                std::vector<mtm_hit> list;
+                for (int y = 0; y < oh; ++y)
+                    for (int x = 0; x < ow; ++x) list.push_back(mtm_hit{0, x, y, 3, 3, 0.75f});
+                hits.clear();
+                flag = 0;
+                verify_candidates_3x3(list.data(), list.size(), MapDims{&oh, &ow, sizeof(int)}, false, 0.5f, padv, hk, hv, hits, &flag);
+                CHECK((int)hits.size() == oh * ow && flag == oh * ow && fused_count_trivial(flag, oh, ow));
+                CHECK(!fused_count_trivial(flag - 1, oh, ow));
+            }
+        // a hit at each corner (quality above the constant border's 0)
+        {
+            const int oh = 5, ow = 6;
+            std::vector<std::vector<float>> m(1, std::vector<float>((size_t)oh * ow, 0.25f));
+            for (int y : {0, oh - 1})
+                for (int x : {0, ow - 1}) m[0][(size_t)y * ow + x] = 1.0f;
+            verify_case({oh}, {ow}, m, false, 0.5f, padv, rng, hk, hv);
+            hits.clear();
+            flag = 0;
+            const mtm_hit corners[4] = {{0, 0, 0, 2, 2, 1.0f}, {0, ow - 1, 0, 2, 2, 1.0f}, {0, 0, oh - 1, 2, 2, 1.0f}, {0, ow - 1, oh - 1, 2, 2, 1.0f}};
+            verify_candidates_3x3(corners, 4, MapDims{&oh, &ow, sizeof(int)}, false, 0.5f, padv, hk, hv, hits, &flag);
+            CHECK(hits.size() == 4 && flag == 4);
+        }
+        // one duplicated record: its first copy is what the neighbours see.  A = (1, 1) listed with 0.5, then again with 0.9;
+        // B = (2, 1) with 0.7 is a hit only against the first
+        {
+            const int oh = 3, ow = 4;
+            const mtm_hit list[3] = {{0, 1, 1, 2, 2, 0.5f}, {0, 2, 1, 2, 2, 0.7f}, {0, 1, 1, 2, 2, 0.9f}};
+            hits.clear();
+            flag = 0;
+            verify_candidates_3x3(list, 3, MapDims{&oh, &ow, sizeof(int)}, false, 0.25f, -INFINITY, hk, hv, hits, &flag);
+            bool b_hit = false, first_a_hit = false;
+            for (const mtm_hit& h : hits) {
+                b_hit = b_hit || (h.x == 2 && h.y == 1);
+                first_a_hit = first_a_hit || (h.x == 1 && h.score == 0.5f);
+            }
+            CHECK(b_hit && !first_a_hit && flag == (int)hits.size());
+        }
+    }
+    // the scans' flag word: bytes 0 / 1 / 2 zero or not, against the expression as fm_end had it; the top byte is not looked at
+    for (unsigned b0 : {0u, 1u, 0x80u})
+        for (unsigned b1 : {0u, 1u, 0xFFu})
+            for (unsigned b2 : {0u, 2u, 0x40u})
+                for (unsigned b3 : {0u, 0x7Fu}) {
+                    const unsigned f = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+                    CHECK(scan_flags_trivial(f) == ((f & 0xFFu) == 0 && !((f & 0xFF00u) != 0 && (f & 0xFF0000u) != 0)));
+                    CHECK(scan_flags_trivial(f) == (b0 == 0 && !(b1 != 0 && b2 != 0)));
+                }
+}
+
+// Every sequence of outcomes the device can report from `R` on: rig_wide only in pp_mode, cands_overflow only while fused,
+// hits_overflow only when not fused (a verified list is no longer than the candidate list, whose capacity never exceeds
+// hit_cap) and never right after the single list of a non-flagged full scan was grown (same maps, room for every peak).
+// Pass `attempt` is about to run: it must lie within `cap`; no step but a grown list is taken twice (`seen`).
+static void walk_ladder(const mtmi::CallRoute& R, int attempt, unsigned seen, bool list_holds_all, int cap, int* longest) {
+    CHECK(attempt < cap);
+    CHECK(!(R.refine && R.f32_exact));
+    const bool local = R.mode == MTM_PEAKS_LOCAL;
+    for (int rig = 0; rig <= (local && R.pp_mode ? 1 : 0); ++rig)
+        for (int co = 0; co <= ((local ? R.fused : (R.refine && R.ext)) ? 1 : 0); ++co)
+            for (int ho = 0; ho <= (local && !R.fused && !list_holds_all ? 1 : 0); ++ho) {
+                const LadderStep step = ladder_next(R, PassOutcome{rig != 0, co != 0, ho != 0}, attempt);
+                if (step == LadderStep::Done) {
+                    *longest = std::max(*longest, attempt + 1);
+                    continue;
+                }
+                CHECK(rig || co || ho);
+                const bool grow = step == LadderStep::GrowList || step == LadderStep::GrowListLeaveSegments;
+                const unsigned bit = 1u << (unsigned)step;
+                CHECK(grow || !(seen & bit));
+                mtmi::CallRoute next = R;
+                ladder_apply(next, step);
+                walk_ladder(next, attempt + 1, seen | bit, step == LadderStep::GrowList && !R.fused && !R.sparse, cap, longest);
+            }
+}
+
+static void test_ladder() {
+    std::vector<mtmi::CallRoute> starts;
+    mtmi::CallRoute base;
+    base.n = 3;
+    base.cand_cap = 16;
+    for (int ho = 0; ho < 2; ++ho) {
+        mtmi::CallRoute r = base;               // integer candidates
+        r.fused = true;
+        r.hits_only = ho != 0;
+        starts.push_back(r);
+        for (int np : {1, 3})
+            for (int raw = 0; raw < 2; ++raw) {
+                mtmi::CallRoute f = r;          // float32 refinement from kernel candidates
+                f.refine = true;
+                f.bf16_np = np;
+                f.raw_rig = raw != 0;
+                starts.push_back(f);
+            }
+    }
+    for (int np : {1, 3}) {
+        mtmi::CallRoute r = base;               // float32 refinement from a map scan, as fm_end enters its loop
+        r.refine = r.refine_scan = r.pp_mode = r.fused = true;
+        r.bf16_np = np;
+        starts.push_back(r);
+        mtmi::CallRoute g = base;               // the refined global extremum
+        g.mode = MTM_PEAKS_GLOBAL;
+        g.refine = g.ext = g.hits_only = true;
+        g.bf16_np = np;
+        starts.push_back(g);
+    }
+    for (int skip = 0; skip < 2; ++skip) {
+        mtmi::CallRoute r = base;               // flagged segments
+        r.sparse = true;
+        r.seg_skip_used = skip != 0;
+        starts.push_back(r);
+    }
+    starts.push_back(base);                     // the plain full scan
+    mtmi::CallRoute f64 = base;                 // ... on the float64 kernel's maps; the global extremum without a list
+    f64.f32_exact = true;
+    starts.push_back(f64);
+    f64.mode = MTM_PEAKS_GLOBAL;
+    starts.push_back(f64);
+    int worst_local = 0, worst_global = 0;
+    for (const mtmi::CallRoute& r : starts) {
+        const bool local = r.mode == MTM_PEAKS_LOCAL;
+        walk_ladder(r, 0, 0u, false, local ? 5 : 3, local ? &worst_local : &worst_global);
+    }
+    // one product -> three products -> map scan -> float64 kernel -> grown list; one product -> three products -> float64 kernel
+    CHECK(worst_local == 5 && worst_global == 3);
+    // a step's route: the flagged segments are left with complete maps asked for, the float64 kernel ends every refinement
+    mtmi::CallRoute r = base;
+    r.sparse = r.seg_skip_used = r.fused = true;
+    ladder_apply(r, LadderStep::GrowListLeaveSegments);
+    CHECK(!r.sparse && !r.seg_skip_used && !r.fused);
+    r = base;
+    r.refine = r.fused = r.hits_only = r.raw_rig = true;
+    ladder_apply(r, LadderStep::Float64);
+    CHECK(r.f32_exact && !r.refine && !r.fused && !r.hits_only && !r.raw_rig && !r.pp_mode && !r.ext);
+}
+
 int main() {
     std::mt19937 rng(12345);
+    test_verify_candidates(rng);
+    test_ladder();
     test_host(rng);
     test_group(rng);
     // two groups driven from two caller threads at once (each group is single-caller; the library must not share state)

@@ -228,6 +228,16 @@ int         mtm_debug_quotient_check(mtm_ctx* ctx, uint64_t n_cases, uint64_t se
  * runs unscreened (no such s, a negative threshold, s / h above the measured cut-off).  The environment variable
  * MTM_TAIL_SPLIT=<s> (read when a context is created) forces a split instead, clamped to [6, h - 2]. */
 int         mtm_debug_tail_split(int h, int w, double thr);
+/* Test support (added under ABI 9; launches nothing).  The tiling place_templates chose for every size class of the
+ * template set placed on the context (after a search, mtm_find_matches or mtm_score_map), in placement order:
+ * MTM_CLASS_TILING_FIELDS int32 per class - h, w, n_templates, kernel (MTM_KERNEL_*), rm_nt, rm_R (row-multiplexed: templates
+ * and output rows per MFMA group, 0 = not), kp_nseg (packed K: 16-tap segments per template row, 0 = not), r2 (2 = two-row
+ * tiling), tail_ok (the two-row class can screen its K loop), tail_split (the split the class's last score launch carried,
+ * 0 = it ran unscreened), n_slabs, slab_nt (slabs of a large-template class; templates per MFMA group of their
+ * row-multiplexed launches, 0 = plain launches).  Records of the first cap_classes classes go to `out`; returns the number
+ * of classes, or a negative MTM_E_* code (no template set placed). */
+#define MTM_CLASS_TILING_FIELDS 12
+int         mtm_debug_class_tilings(mtm_ctx* ctx, int32_t* out, int cap_classes);
 /* Page-locked host memory for pixel buffers (optional).  The reference's caller hands over whatever numpy holds
  * (MTM/__init__.py:247 `image`) - pageable memory, which the runtime stages through its own pinned buffers while the
  * upload call blocks.  An image kept in memory from mtm_host_alloc crosses PCIe as a plain DMA transfer behind the call

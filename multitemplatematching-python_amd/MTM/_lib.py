@@ -85,6 +85,7 @@ SYMBOLS = {
     "mtm_debug_poison": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     "mtm_debug_quotient_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, _P(ctypes.c_uint64)]),
     "mtm_debug_tail_split": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double]),
+    "mtm_debug_class_tilings": (ctypes.c_int, [ctypes.c_void_p, _P(ctypes.c_int32), ctypes.c_int]),
     "mtm_set_image": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
     "mtm_set_image_downscaled": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -361,6 +362,11 @@ def live_contexts():
     return [c for c in list(_LIVE) if c._h]
 
 
+# the fields of one mtm_debug_class_tilings record (MTM_CLASS_TILING_FIELDS of them)
+CLASS_TILING_FIELDS = ("h", "w", "n_templates", "kernel", "rm_nt", "rm_R", "kp_nseg", "r2", "tail_ok", "tail_split", "n_slabs",
+                       "slab_nt")
+
+
 def debug_tail_split(h, w, thr):
     """Test support (mtm_debug_tail_split; needs no GPU): the K steps after which the two-row score kernel of an h x w
     class screens its waves at the candidate threshold `thr`, 0 = unscreened."""
@@ -422,6 +428,17 @@ class Context(_RecordMemo):
         """Test support (mtm_debug_poison): a byte pattern into every wave slot's scratch memory (1), every CU's LDS (2) and
         the context's per-call work buffers (4) - memory no result may depend on."""
         check(self._lib.mtm_debug_poison(self._h, int(pattern), int(what)), "mtm_debug_poison")
+
+    def class_tilings(self):
+        """Test support (mtm_debug_class_tilings): the tiling placement chose for every size class of the template set
+        placed on the context, in placement order -> a list of dicts (CLASS_TILING_FIELDS; tail_split is the split of the
+        class's last score launch, 0 = unscreened)."""
+        nf = len(CLASS_TILING_FIELDS)
+        n = self._lib.mtm_debug_class_tilings(self._h, None, 0)
+        check(min(n, 0), "mtm_debug_class_tilings")
+        buf = (ctypes.c_int32 * (nf * max(n, 1)))()
+        check(min(self._lib.mtm_debug_class_tilings(self._h, buf, n), 0), "mtm_debug_class_tilings")
+        return [dict(zip(CLASS_TILING_FIELDS, buf[k * nf:(k + 1) * nf])) for k in range(n)]
 
     def debug_quotient_check(self, n_cases=1 << 28, seed=1):
         """Test support (mtm_debug_quotient_check): the epilogue's division-free quotient against the IEEE division on

@@ -553,6 +553,36 @@ int mtm_debug_poison(mtm_ctx* c, int pattern_byte, int what) {
     return MTM_OK;
 }
 
+// ---- test support: the tiling placement chose for every size class (mtm_debug_class_tilings) ---------------------------
+// Reads SizeClass as place_templates left it (and the split the class's last score launch carried); derives nothing,
+// launches nothing.
+int mtm_debug_class_tilings(mtm_ctx* c, int32_t* out, int cap_classes) {
+    if (!c || (!out && cap_classes > 0)) return MTM_E_INVALID;
+    MTM_NOT_IN_FLIGHT(c, "mtm_debug_class_tilings");
+    if (!c->placed) {
+        set_error("mtm_debug_class_tilings: no template set is placed (run a search first)");
+        return MTM_E_STATE;
+    }
+    const int n = (int)c->classes.size();
+    for (int k = 0; k < n && k < cap_classes; ++k) {
+        const mtm_ctx::SizeClass& sc = c->classes[(size_t)k];
+        int32_t* r = out + (size_t)k * MTM_CLASS_TILING_FIELDS;
+        r[0] = sc.h;
+        r[1] = sc.w;
+        r[2] = (int32_t)sc.members.size();
+        r[3] = sc.kernel;
+        r[4] = sc.rm_nt;
+        r[5] = sc.rm_R;
+        r[6] = sc.kp_nseg;
+        r[7] = sc.r2;
+        r[8] = sc.tail_ok ? 1 : 0;
+        r[9] = (size_t)k < c->tail_last.size() ? c->tail_last[(size_t)k] : 0;
+        r[10] = (int32_t)sc.slabs.size();
+        r[11] = sc.slab_nt;
+    }
+    return n;
+}
+
 // ---- test support: quotient_as_float against the IEEE division it replaces (mtm_debug_quotient_check) -------------------
 // Operands shaped like the epilogue's: sq = sqrt of an integer-valued window energy, templ_norm = sqrt of one, num an
 // integer-valued or fractional numerator with |num| <~ tt.  Even cases are plain random draws; odd cases are adversarial -

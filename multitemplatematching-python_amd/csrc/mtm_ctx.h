@@ -204,6 +204,8 @@ struct mtm_ctx {
                                             // screen, instead of tail_split_rule's (tests, measurements)
     std::vector<int> tail_valid;            // per size class: the split TemplDev::tail_* on the device hold the constants of
                                             // (ensure_tail_consts re-derives them when a call's split differs), 0 = none
+    std::vector<int> tail_last;             // per size class: the split its last score launch carried, 0 = unscreened
+                                            // (test support: mtm_debug_class_tilings)
     int f32_mfma = 1;                       // MTM_F32_MFMA / MTM_OPT_F32_MFMA: unmasked float32 classes on the bf16 matrix cores:
                                             // 0 = float64 kernel, 1 = bf16 screen + exact float64 re-scoring of everything
                                             // that could be a peak (hit lists of the float64 kernel), 2 = bf16 scores as they are,

@@ -844,6 +844,9 @@ static int launch_mfma(mtm_ctx* c, CallRoute& R, const SizeClass& sc, const Stat
     // (tail screen: the tail boxes' records and the templates' tail constants behind them)
     p.tail_split = (r2 && st.blkq != nullptr && only_li < 0 && !p.seg_skip) ? tail_split_for(c, R, sc) : 0;
     MTMC(ensure_tail_consts(c, sc, p.tail_split));          // (launch_stats has seen to it: a no-op)
+    if (!c->classes.empty() && &sc >= c->classes.data() && &sc < c->classes.data() + c->classes.size() &&
+        (size_t)(&sc - c->classes.data()) < c->tail_last.size())
+        c->tail_last[(size_t)(&sc - c->classes.data())] = p.tail_split;      // (what mtm_debug_class_tilings reports)
     const size_t stat_bytes = rm ? 0 : r2 ? (size_t)kMfRows * ((mb + 1) / 2) * 1024 + (p.tail_split ? mf_tail_lds_bytes() : 0)
                                           : (size_t)kMfRows * mf_stat_bytes_per_wave(c->chans == 3 ? 3 : 1);
     const bool ext = R.ext;                          // plan_call checked the class

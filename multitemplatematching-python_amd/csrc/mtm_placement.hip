@@ -160,11 +160,16 @@ void pack_class_rm(const mtm_ctx* c, const SizeClass& sc, uint8_t* out, size_t b
 }
 
 // uint16 image + uint16 templates, one channel, no mask: four uint8 byte-plane correlations on the int8
-// MFMA kernel (a raw pass over the high bytes, a finishing pass over the low bytes).  Same int32 accumulator bound
-// as the uint8 path.
+// MFMA kernel (a raw pass over the high bytes, a finishing pass over the low bytes).  The two middle correlations,
+// I_hi x T_lo + I_lo x T_hi, share ONE int32 accumulator (a_mid of the uint16 epilogue): up to 2 x 16384 w h where both
+// biased operands are -128 (zero bytes), which fits up to w h = 65535 - half the uint8 path's bound.  (The bound was the
+// uint8 one until tests/test_gpu_tilings.py ran 511 x 256: zero regions under zero templates wrapped a_mid.)  Larger
+// classes take the float64 kernel.
+constexpr long long kMfma16MaxArea = 65535;
+static_assert(2 * 16384 * kMfma16MaxArea <= 2147483647LL, "a_mid of the uint16 epilogue must fit an int32");
 bool mfma16_class_ok(const mtm_ctx* c, const SizeClass& sc) {
     return c->dtype == MTM_U16 && sc.all_u16 && c->chans == 1 && !sc.masked && sc.w <= kMfmaMaxW &&
-           (long long)sc.w * sc.h <= 131071;
+           (long long)sc.w * sc.h <= kMfma16MaxArea;
 }
 
 // float32 image + float32 templates, no mask: bfloat16 pieces on the bf16 matrix cores.  The normalised methods' outputs
@@ -774,6 +779,7 @@ int upload_placement(mtm_ctx* c, Placement& P, HostArenas& H) {
     if (new_units) c->usrc_host.swap(P.units);
     c->classes.swap(P.classes);
     c->tail_valid.assign(c->classes.size(), 0);
+    c->tail_last.assign(c->classes.size(), 0);
     for (size_t k = 0; k < c->classes.size(); ++k) {
         const SizeClass& sc = c->classes[k];
         if (sc.tail_split > 0 && sc.kernel == MTM_KERNEL_MFMA && !sc.members.empty()) c->tail_valid[k] = sc.tail_split;

@@ -34,6 +34,21 @@ def test_header_symbols_exported(lib):
     assert lib.load().mtm_abi_version() == lib.ABI_VERSION == 9
 
 
+def test_class_tilings_record_matches_the_header(lib):
+    """mtm_debug_class_tilings (test support): the binding's field list is as long as the header's record, in the header's
+    order, and the entry point refuses a null context without touching the output."""
+    hdr = open(os.path.join(ROOT, "include", "mtm_hip.h")).read()
+    n_fields = int(re.search(r"#define\s+MTM_CLASS_TILING_FIELDS\s+(\d+)", hdr).group(1))
+    assert len(lib.CLASS_TILING_FIELDS) == n_fields == 12
+    comment = hdr[:hdr.index("#define MTM_CLASS_TILING_FIELDS")]
+    comment = comment[comment.rindex("/*"):]
+    pos = [comment.index(f) for f in lib.CLASS_TILING_FIELDS]
+    assert pos == sorted(pos), list(zip(lib.CLASS_TILING_FIELDS, pos))
+    out = (ctypes.c_int32 * n_fields)(*([-7] * n_fields))
+    assert lib.load().mtm_debug_class_tilings(None, out, 1) < 0
+    assert list(out) == [-7] * n_fields
+
+
 def test_struct_layout(lib):
     assert ctypes.sizeof(lib.MtmHit) == 24
     assert ctypes.sizeof(lib.MtmTempl) == 48

@@ -3,7 +3,12 @@ where a Cauchy-Schwarz bound on the template rows still missing rules out every 
 hit records with it are identical to those of MTM_TAIL_SCREEN=0 - templates whose structure lies only in the rows after
 the split, noisy copies, flat tail boxes, constant templates, thresholds within 1e-3 of the best scores of those templates
 on both sides, partial row blocks and column segments, banded image uploads against single-band calls.  And on the
-default routes it does skip work: the score kernel of a screened call takes clearly less time."""
+default routes it does skip work: the score kernel of a screened call takes clearly less time.
+
+The screen only exists in the two-row tiling, which a normalised-method class takes at ceil(w / 16) % 4 == 0 alone: w in
+49 .. 64.  The 64 x 40 and 20 x 24 cases are packed-K classes (nseg 3 and 2): no screen is compiled into the launch they
+run, both contexts do the same thing - they stay as unscreened controls.  The cases where the screen runs say so through
+Context.class_tilings() (tail_ok), among them widths that leave the last 16-tap segment partly padded (56, 49)."""
 import os
 
 import numpy as np
@@ -49,9 +54,19 @@ def _templates(rng, img, h, w, n):
     return ts, kinds
 
 
-@pytest.mark.parametrize("shape,h,w", [((300, 700), 64, 64), ((203, 517), 64, 40), ((150, 333), 32, 64), ((97, 290), 20, 24)])
+def _screen_runs(h, w):
+    """The class is one whose hits-only launches can screen their K loop (choose_tiling): two-row tiling, one K chunk."""
+    return 49 <= w <= 64 and 8 <= h <= 71
+
+
+@pytest.mark.parametrize("shape,h,w", [((300, 700), 64, 64), ((203, 517), 64, 40), ((150, 333), 32, 64), ((97, 290), 20, 24),
+                                       ((203, 517), 64, 56), ((97, 290), 24, 49), ((150, 333), 71, 64)])
 def test_tail_screen_changes_nothing(monkeypatch, shape, h, w):
+    """Screened against MTM_TAIL_SCREEN=0.  The screen runs at 64 x 64, 32 x 64, 64 x 56, 24 x 49 and 71 x 64 (asserted:
+    tail_ok, and - where the candidate list cannot overflow - a split carried by the TM_CCOEFF_NORMED call at 0.7); 64 x 40
+    and 20 x 24 are packed-K classes, kept as unscreened controls (asserted too: no tail_ok there)."""
     _lib, plain, screened = _contexts(monkeypatch)
+    default = not any(os.environ.get(k) for k in _OTHER_ROUTES)
     rng = np.random.default_rng(20261016 + h * 7 + w)
     try:
         img = rng.integers(0, 256, shape).astype(np.uint8)
@@ -77,6 +92,14 @@ def test_tail_screen_changes_nothing(monkeypatch, shape, h, w):
                 thrs += [s - 4e-4, s + 4e-4]
             for thr in thrs:
                 a = screened.search(tl, img, method, _lib.PEAKS_LOCAL, thr)
+                if default:
+                    rec, = screened.class_tilings()
+                    assert bool(rec["tail_ok"]) == _screen_runs(h, w) and (rec["kp_nseg"] > 0) == (not _screen_runs(h, w)), rec
+                    # (a constant template scores 1 everywhere: at 300 x 700 the two of them alone put 2 x 237 x 637 outputs
+                    # into a candidate list of 2^18 records - every call there overflows and is repeated in map mode, the
+                    # comparison covers that fallback, not the screen)
+                    if _screen_runs(h, w) and method == 5 and thr == 0.7 and 2 * (shape[0] - h + 1) * (shape[1] - w + 1) < 1 << 18:
+                        assert rec["tail_split"] >= 6, rec
                 b = plain.search(tl, img, method, _lib.PEAKS_LOCAL, thr)
                 assert np.array_equal(a, b), (shape, h, w, method, thr, len(a), len(b))
                 n_rec += len(a)

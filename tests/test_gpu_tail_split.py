@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import synth
-from test_gpu_tail_screen import _OTHER_ROUTES, _templates
+from test_gpu_tail_screen import _OTHER_ROUTES, _screen_runs, _templates
 
 pytestmark = pytest.mark.gpu
 
@@ -53,8 +53,12 @@ def _scene(h, w):
     return img, [(t, None) for t in ts], kinds
 
 
-@pytest.mark.parametrize("h,w", [(64, 64), (32, 64), (20, 24)])
+@pytest.mark.parametrize("h,w", [(64, 64), (32, 64), (20, 24), (64, 56), (24, 49), (71, 64)])
 def test_any_split_changes_nothing(monkeypatch, h, w):
+    """The screen runs at 64 x 64, 32 x 64, 64 x 56, 24 x 49 (a partly padded last 16-tap segment) and 71 x 64 (the last
+    single-chunk height): asserted through Context.class_tilings() - tail_ok, and the forced split carried by the
+    TM_CCOEFF_NORMED call at 0.7.  20 x 24 is a packed-K class (nseg 2): no screen is compiled into its launch whatever
+    MTM_TAIL_SPLIT says; it stays as an unscreened control (asserted: no tail_ok)."""
     from MTM import _lib
     img, tl, kinds = _scene(h, w)
     plain = _ctx(monkeypatch, _lib, MTM_TAIL_SCREEN="0")
@@ -80,6 +84,11 @@ def test_any_split_changes_nothing(monkeypatch, h, w):
             try:
                 for (method, thr), b in ref.items():
                     a = forced.search(tl, img, method, _lib.PEAKS_LOCAL, thr)
+                    if not any(os.environ.get(k) for k in _OTHER_ROUTES):
+                        rec, = forced.class_tilings()
+                        assert bool(rec["tail_ok"]) == _screen_runs(h, w), rec
+                        if _screen_runs(h, w) and method == 5 and thr == 0.7:
+                            assert rec["tail_split"] == split, rec
                     assert np.array_equal(a, b), (h, w, split, method, thr, len(a), len(b))
             finally:
                 forced.close()

@@ -2665,47 +2665,10 @@ def test_4k_photograph_default_mode_hit_lists(mtm):
 
 # ---- round 5: the float32 route's listing decisions rest on a per-output error bound, not on empirical margins ----------
 def _bf16_bound_map(img, templ, method, pieces=3):
-    """numpy restatement of Bf16Params::rig's bound M(x, y) for a single-channel float32 image and one template:
-    rig_eps * sqrt(sum (I - mu)^2) / sq * (escale * sqrt(sum (T - mean)^2) / templ_norm), with mu the constant the
-    bf16 kernel's work item (128 columns x 4 rows of outputs) subtracts: the mean of an 8 x 8 sample grid over its patch."""
-    I = img.astype(np.float64)
-    T = templ.astype(np.float64)
-    rows, cols = I.shape
-    h, w = T.shape
-    oh, ow = rows - h + 1, cols - w + 1
-    A = float(h * w)
-    nkb = (w + 31) // 32
-    lds_cols = 128 + 32 * nkb
-    eps = 3.0518e-5 + 2.0 * 3.0 * h * nkb * 5.97e-8
-    if pieces == 1:         # the one-product screen (bf16_rig_eps(.., np = 1), the accumulation term not doubled)
-        eps = 2.0 ** -7 * (1.0 + 2.0 ** -9) + 2.0 * 1.0 * h * nkb * 5.97e-8
-    c1 = np.zeros((rows + 1, cols + 1))
-    c1[1:, 1:] = I.cumsum(0).cumsum(1)
-    c2 = np.zeros((rows + 1, cols + 1))
-    c2[1:, 1:] = (I * I).cumsum(0).cumsum(1)
-    box = lambda c: c[h:, w:] - c[:-h, w:] - c[h:, :-w] + c[:-h, :-w]     # noqa: E731
-    S1, S2 = box(c1), box(c2)
-    mu = np.zeros((oh, ow))
-    for y0 in range(0, oh, 4):
-        sr = np.minimum(y0 + (np.arange(8) * (h + 2)) // 7, rows - 1)
-        for x0 in range(0, ow, 128):
-            sc = np.minimum(x0 + (np.arange(8) * (lds_cols - 1)) // 7, cols - 1)
-            mu[y0:y0 + 4, x0:x0 + 128] = np.float32(img[np.ix_(sr, sc)].astype(np.float32).mean())
-    s2c = np.maximum(S2 - 2.0 * mu * S1 + A * mu * mu, 0.0) * 1.000001 + 1e-12 * (np.abs(S2) + A * mu * mu)
-    t2c = ((T - T.mean()) ** 2).sum()
-    if method == 5:
-        diff2 = np.maximum(S2 - S1 * S1 / A, 0.0)
-        tn = np.sqrt(t2c)
-        esc = 1.0
-    else:
-        diff2 = S2
-        tn = np.sqrt((T * T).sum())
-        esc = 2.0 if method == 1 else 1.0
-    flat = diff2 <= np.minimum(0.5, 10.0 * np.finfo(np.float32).eps * S2)
-    sq = np.where(flat, 0.0, np.sqrt(diff2))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        M = eps * np.sqrt(s2c) / sq * (esc * np.sqrt(t2c) / tn) + 3e-7
-    return np.where(sq > 0.0, M, 0.0), sq > 0.0
+    """Bf16Params::rig's bound M(x, y) as f32_model.bound_map restates it (any channel count), with the constant this test has
+    asserted since round 5: bf16_rig_eps BEFORE the whole was doubled (the kernel lists by twice that)."""
+    from f32_model import bound_map
+    return bound_map(img, templ, method, pieces, doubled=False)
 
 
 def _step_image(seed, shape=(300, 420), lo=0.0, hi=1.0, noise=2e-3):

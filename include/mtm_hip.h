@@ -30,8 +30,8 @@ extern "C" {
 #endif
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
- * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd - are new symbols only and left
- * it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
+ * mtm_debug_templ_stats - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -228,6 +228,12 @@ int         mtm_debug_quotient_check(mtm_ctx* ctx, uint64_t n_cases, uint64_t se
  * runs unscreened (no such s, a negative threshold, s / h above the measured cut-off).  The environment variable
  * MTM_TAIL_SPLIT=<s> (read when a context is created) forces a split instead, clamped to [6, h - 2]. */
 int         mtm_debug_tail_split(int h, int w, double thr);
+/* Test support (added under ABI 9; host only, needs no GPU).  The constants mtm_set_templates computes for an unmasked
+ * template under `method` (0..5): px = rows x cols pixels of `chans` interleaved channels (1..4), tightly packed, dtype
+ * MTM_U8, MTM_U16 or MTM_F32.  out7 = mean[0..3] (the channel means, zeroed where the method does not centre), templ_norm,
+ * templ_sum2, all_ones (1.0: TM_CCOEFF_NORMED with a constant template, whose map is 1 everywhere) - the record
+ * mtm_track_boxes_adapt returns per track in stats_out, computed there on the device by the same inline function. */
+int         mtm_debug_templ_stats(const void* px, int rows, int cols, int chans, int dtype, int method, double* out7);
 /* Test support (added under ABI 9; launches nothing).  The tiling place_templates chose for every size class of the
  * template set placed on the context (after a search, mtm_find_matches or mtm_score_map), in placement order:
  * MTM_CLASS_TILING_FIELDS int32 per class - h, w, n_templates, kernel (MTM_KERNEL_*), rm_nt, rm_R (row-multiplexed: templates
@@ -423,6 +429,24 @@ int mtm_track_boxes(mtm_ctx* ctx, const void* const* frames, int n_frames, int r
 int mtm_track_boxes_nbhd(mtm_ctx* ctx, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
                          int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min,
                          double min_score, mtm_hit* out, float* nbhd);
+
+/* mtm_track_boxes / mtm_track_boxes_nbhd with adaptive templates: the same arguments, checks, errors, records
+ * and afterwards-state, but every track owns a copy of its template - made on the device at the start of the call, in
+ * buffers of the call: the template set of the context is left as it is - and after each frame whose hit passes (use_min
+ * not set, or the score passes min_score: the rule that moves the region) every pixel of that copy becomes
+ *   (T * (256 - blend_a) + W * blend_a + 128) >> 8
+ * in integers, W being the frame's pixel under the hit; blend_a in 1 .. 256 (256: the window replaces the template).  The
+ * copy's constants are recomputed on the device from exact integer sums, in mtm_set_templates' operation order, so frame
+ * f + 1 is searched exactly as a mtm_find_matches_boxes call after mtm_set_templates of the blended template would search
+ * it.  Two tracks of one template diverge.  The adoption also follows the last frame.  One more launch per frame; the host
+ * still waits once.  nbhd: optional (NULL: records only); frame f's neighbourhoods are those of the template frame f was
+ * searched with.  templ_out: optional; every track's template after the last frame, track after track, each as
+ * mtm_set_templates takes it (interleaved channels, tightly packed, the frames' pixel type).  stats_out: optional; 7
+ * doubles per track, the constants of that template as mtm_debug_templ_stats lists them.  out[..].templ_idx = the track's
+ * template in the set, as mtm_track_boxes returns it. */
+int mtm_track_boxes_adapt(mtm_ctx* ctx, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                          int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min,
+                          double min_score, mtm_hit* out, float* nbhd, int blend_a, void* templ_out, double* stats_out);
 
 /* The 3 x 3 score neighbourhoods of n points in one call: out[9 k + 3 (1 + dy) + (1 + dx)] = the score of
  * template pts[k].templ_idx at window (x + dx, y + dy) of the image's score map, NaN for a window outside the map.  Image:

@@ -511,21 +511,23 @@ class TemplateMatcher:
             self._uploaded_for = (str(image.dtype), 1 if image.ndim == 2 else image.shape[2]) if uploaded else before
         return hits
 
-    def track(self, frames, tracks, margin: int, min_score=None, *, refine: bool = False) -> List[List[List[Hit]]]:
+    def track(self, frames, tracks, margin: int, min_score=None, *, refine: bool = False, update=None,
+              return_templates: bool = False):
         """
-        ``trackTemplates(listTemplates, frames, tracks, margin, method, min_score, refine=refine)`` with this matcher's list
-        and method: the same hits and exceptions, on this matcher's context with its templates resident across calls.
-        Scope as trackTemplates', for every template of the list.
+        ``trackTemplates(listTemplates, frames, tracks, margin, method, min_score, refine=refine, update=update,
+        return_templates=return_templates)`` with this matcher's list and method: the same hits and exceptions, on this
+        matcher's context with its templates resident across calls.  Scope as trackTemplates', for every template of the
+        list.  Adapted templates (``update``) live in buffers of the call: the resident ones stay as they are.
         """
         from . import tracking
         self._not_streaming()
         with self._ctx.lock:
             # as match_boxes: until the call returns, nothing is known to be resident
             before, self._uploaded_for = self._uploaded_for, None
-            hits, f0, uploaded = tracking._track(self.listTemplates, frames, tracks, margin, self.method, min_score,
-                                                 self._ctx, True, refine)
+            hits, f0, uploaded, last = tracking._track(self.listTemplates, frames, tracks, margin, self.method, min_score,
+                                                       self._ctx, True, refine, update, return_templates)
             self._uploaded_for = (str(f0.dtype), 1 if f0.ndim == 2 else f0.shape[2]) if uploaded else before
-        return hits
+        return (hits, last) if return_templates else hits
 
     def refine(self, image: np.ndarray, hits) -> List[tuple]:
         """

@@ -86,6 +86,8 @@ SYMBOLS = {
     "mtm_debug_quotient_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, _P(ctypes.c_uint64)]),
     "mtm_debug_tail_split": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double]),
     "mtm_debug_class_tilings": (ctypes.c_int, [ctypes.c_void_p, _P(ctypes.c_int32), ctypes.c_int]),
+    "mtm_debug_templ_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, _P(ctypes.c_double)]),
     "mtm_set_image": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
     "mtm_set_image_downscaled": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -123,6 +125,10 @@ SYMBOLS = {
     "mtm_track_boxes_nbhd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
+    "mtm_track_boxes_adapt": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_hit_neighbourhoods": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
@@ -373,6 +379,21 @@ def debug_tail_split(h, w, thr):
     return int(load().mtm_debug_tail_split(int(h), int(w), float(thr)))
 
 
+# the doubles of one mtm_debug_templ_stats / mtm_track_boxes_adapt statistics record
+TEMPL_STATS_FIELDS = ("mean0", "mean1", "mean2", "mean3", "templ_norm", "templ_sum2", "all_ones")
+
+
+def debug_templ_stats(template, method):
+    """Test support (mtm_debug_templ_stats; needs no GPU): the constants mtm_set_templates computes for an unmasked
+    template (H x W or H x W x C; uint8, uint16 or float32) under `method` - a float64 array of TEMPL_STATS_FIELDS."""
+    a = np.ascontiguousarray(template)
+    chans = 1 if a.ndim == 2 else a.shape[2]
+    out = (ctypes.c_double * len(TEMPL_STATS_FIELDS))()
+    check(load().mtm_debug_templ_stats(a.ctypes.data, a.shape[0], a.shape[1], chans, _dtype_code(a), int(method), out),
+          "mtm_debug_templ_stats")
+    return np.array(out[:], dtype=np.float64)
+
+
 class Context(_RecordMemo):
     """One GPU context (single caller: guarded by a lock)."""
 
@@ -555,6 +576,38 @@ class Context(_RecordMemo):
         nbhd = np.empty((n * nt, 3, 3), dtype=np.float32)
         check(self._lib.mtm_track_boxes_nbhd(*args, nbhd.ctypes.data), "mtm_track_boxes_nbhd")
         return out, nbhd
+
+    def track_boxes_adapt(self, frames, units, margin, min_score, blend_a, templates, with_nbhd=False):
+        """track_boxes / track_boxes_nbhd with a template per track that is blended with each passing hit's window
+        (mtm_track_boxes_adapt; the window's weight is blend_a / 256).  `templates`: the pixel arrays of the current
+        templates, in their order (for the shapes of the result).  Returns (records, neighbourhoods or None, every
+        track's template after the last frame, (len(units), 7) float64 array of their TEMPL_STATS_FIELDS)."""
+        n, nt = len(frames), len(units)
+        units = np.ascontiguousarray(units, dtype=BOX_UNIT_DTYPE)
+        like = [templates[j] for j in units["templ_idx"].tolist()]
+        if n == 0 or nt == 0:
+            return (np.zeros(0, dtype=HIT_DTYPE), (np.zeros((0, 3, 3), dtype=np.float32) if with_nbhd else None),
+                    [np.array(t) for t in like], np.zeros((nt, len(TEMPL_STATS_FIELDS))))
+        rows = [_pixel_rows(a) for a in frames]
+        if len({r[2] for r in rows}) > 1:       # (one row stride for every frame)
+            rows = [_pixel_rows(np.ascontiguousarray(a)) for a in frames]
+        a0, _, stride = rows[0]
+        chans = 1 if a0.ndim == 2 else a0.shape[2]
+        ptrs = (ctypes.c_void_p * n)(*[r[1] for r in rows])
+        out = np.empty(n * nt, dtype=HIT_DTYPE)
+        nbhd = np.empty((n * nt, 3, 3), dtype=np.float32) if with_nbhd else None
+        sizes = [int(np.prod(t.shape)) for t in like]          # (tightly packed, in the frames' pixel type)
+        packed = np.empty(sum(sizes), dtype=a0.dtype)
+        stats = np.empty((nt, len(TEMPL_STATS_FIELDS)), dtype=np.float64)
+        use_min = min_score is not None
+        check(self._lib.mtm_track_boxes_adapt(self._h, ptrs, n, a0.shape[0], a0.shape[1], chans, _dtype_code(a0), stride,
+                                              units.ctypes.data, nt, int(margin), int(use_min),
+                                              float(min_score) if use_min else 0.0, out.ctypes.data,
+                                              nbhd.ctypes.data if with_nbhd else None, int(blend_a), packed.ctypes.data,
+                                              stats.ctypes.data), "mtm_track_boxes_adapt")
+        ends = np.cumsum(sizes)
+        last = [packed[e - s:e].reshape(t.shape).copy() for s, e, t in zip(sizes, ends.tolist(), like)]
+        return out, nbhd, last, stats
 
     def hit_neighbourhoods(self, image, points):
         """The 3 x 3 score neighbourhoods of `points` (POINT_DTYPE records: a template of the current set and a window of

@@ -22,6 +22,27 @@ positions do not steer the tracks (the next box is ``next_box`` of the integer h
 refined like any other, and the exceptions and warnings are those of the unrefined call.  ``positions`` turns either kind
 of result into an (F, T, 2) array of trajectories.
 
+``update=rate`` (0 < rate <= 1) gives every track a template of its own that follows its object's appearance: after each
+frame whose hit passes (``next_box``' own rule), the track's template becomes ``blend_template(template, window, rate)``
+of the hit's window in that frame.  Element ``[f][k]`` is exactly what this loop returns,
+
+    cur, box = [listTemplates[j][1] for _, j in tracks], [b for b, _ in tracks]
+    for f in frames:
+        for k, (_, j) in enumerate(tracks):
+            r = findMatchesInBoxes([(listTemplates[j][0], cur[k])], f, [box[k]], method, N_object=1)[0]
+            hit = r[0]
+            if <the hit passes: no min_score, or next_box' comparison of the score with it; NaN never passes>:
+                x, y, w, h = hit[1]
+                cur[k] = blend_template(cur[k], f[y:y + h, x:x + w], rate)
+            box[k] = next_box(box[k], hit, margin, f.shape, method, min_score)
+
+from one native call (mtm_track_boxes_adapt): the blend and the new template's statistics are computed on the device
+between two frames' searches, in buffers of the call - the templates set on the context, a TemplateMatcher's resident
+ones included, are never touched.  Two tracks of one ``listTemplates[j]`` diverge.  With ``refine=True`` frame f's hit is
+refined with the template frame f was searched with.  ``return_templates=True`` returns ``(result, templates)``,
+``templates[k]`` being track k's template after the last frame (copies of the originals without ``update``): a video
+tracked in pieces carries on from them.
+
 A track is a pair ``((x, y, w, h), j)``: template ``listTemplates[j]``, searched in that box in frame 0 and around its
 last hit afterwards (``next_box``).
 
@@ -39,7 +60,7 @@ import numpy as np
 from . import _lib, boxes, subpixel
 from . import _MSG_MASK_UNSUPPORTED, Hit, TM_CCOEFF_NORMED
 
-__all__ = ["trackTemplates", "next_box", "positions"]
+__all__ = ["trackTemplates", "next_box", "blend_template", "positions"]
 
 
 def next_box(box, hit, margin, image_shape, method, min_score=None):
@@ -62,6 +83,34 @@ def next_box(box, hit, margin, image_shape, method, min_score=None):
     return (x0, y0, x1 - x0, y1 - y0)
 
 
+def _blend_weight(rate, name="update"):
+    """The window's weight in 256ths, a = round(256 rate), of a blend rate 0 < rate <= 1."""
+    if not isinstance(rate, numbers.Real) or isinstance(rate, bool) or not 0 < rate <= 1:
+        raise ValueError("%s must be a number in (0, 1] or None (got %r)" % (name, rate))
+    a = int(round(rate * 256))
+    if a == 0:
+        raise ValueError("%s = %r is below the smallest step, 1 / 256 (it rounds to a weight of 0)" % (name, rate))
+    return a
+
+
+def blend_template(template, window, rate):
+    """The template an adaptive track carries on with after a hit at ``window`` (the frame's pixels under the hit, of the
+    template's shape and dtype, uint8 or uint16): with a = round(256 rate), 0 < rate <= 1,
+
+        ((template * (256 - a) + window * a + 128) >> 8)
+
+    in integers per pixel - the rounded blend, ``rate=1`` the window itself.  This is the definition of what
+    ``trackTemplates(..., update=rate)`` computes on the device."""
+    template, window = np.asarray(template), np.asarray(window)
+    if template.dtype != window.dtype or template.dtype not in (np.uint8, np.uint16):
+        raise ValueError("blend_template: template and window must both be uint8 or both uint16 (got %s and %s)" % (
+            template.dtype, window.dtype))
+    if template.shape != window.shape:
+        raise ValueError("blend_template: template and window differ in shape (%s and %s)" % (template.shape, window.shape))
+    a = _blend_weight(rate, "rate")
+    return ((template.astype(np.int64) * (256 - a) + window.astype(np.int64) * a + 128) >> 8).astype(template.dtype)
+
+
 def _frames(frames):
     """frames -> a list of arrays of one shape and dtype (an (F, H, W[, C]) array is split along its first axis)."""
     if isinstance(frames, np.ndarray):
@@ -78,26 +127,34 @@ def _frames(frames):
     return fl
 
 
-def _check_args(margin, min_score, refine=False):
+def _check_args(margin, min_score, refine=False, update=None, return_templates=False):
     if not isinstance(margin, numbers.Integral) or isinstance(margin, bool) or margin < 0:
         raise ValueError("margin must be an integer >= 0 (got %r)" % (margin,))
     if min_score is not None and (not isinstance(min_score, numbers.Real) or isinstance(min_score, bool)):
         raise ValueError("min_score must be a number or None (got %r)" % (min_score,))
     if not isinstance(refine, bool):
         raise ValueError("refine must be True or False (got %r)" % (refine,))
+    if not isinstance(return_templates, bool):
+        raise ValueError("return_templates must be True or False (got %r)" % (return_templates,))
+    return None if update is None else _blend_weight(update)
 
 
-def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, resident, refine=False):
+def _originals(listTemplates, tracks):
+    return [np.array(listTemplates[j][1]) for _, j in tracks]
+
+
+def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, resident, refine=False, update=None,
+           return_templates=False):
     """trackTemplates on `ctx`.  `resident`: the context holds every template of listTemplates in list order
     (TemplateMatcher); otherwise the templates the tracks use are set now.  Returns (hits per frame and track, the first
-    frame or None, whether templates were set on the context)."""
+    frame or None, whether templates were set on the context, every track's last template or None)."""
     fl = _frames(frames)
-    _check_args(margin, min_score, refine)
+    a = _check_args(margin, min_score, refine, update, return_templates)
     regions = [(b, [j]) for b, j in tracks]         # (the loop's unpacking of the pairs, and its errors)
     if not fl:
-        return [], None, False
+        return [], None, False, (_originals(listTemplates, tracks) if return_templates else None)
     if not regions:
-        return [[] for _ in fl], fl[0], False
+        return [[] for _ in fl], fl[0], False, ([] if return_templates else None)
     f0 = fl[0]
     if resident and method in boxes._SCOPE_METHODS:       # every resident template is in scope
         boxes._check_scope(listTemplates, f0, range(len(listTemplates)), method, boxes._SCOPE_METHODS)
@@ -120,7 +177,10 @@ def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, reside
     ctx = ctx or _lib.default_context()         # (only now: every argument error comes before "no GPU")
     with ctx.lock:
         ctx.set_templates(templates, method)
-        if refine:
+        last = None
+        if a is not None:
+            raw, nbhd, last, _ = ctx.track_boxes_adapt(fl, units, m, min_score, a, [t[0] for t in templates], refine)
+        elif refine:
             raw, nbhd = ctx.track_boxes_nbhd(fl, units, m, min_score)
         else:
             raw = ctx.track_boxes(fl, units, m, min_score)
@@ -131,11 +191,13 @@ def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, reside
     if refine:          # (one fit over every record: refineHits' numbers by construction)
         hits = subpixel._refined(hits, nbhd, method)
     T = len(units)
-    return [[[hits[f * T + k]] for k in range(T)] for f in range(len(fl))], f0, True
+    if return_templates and last is None:
+        last = _originals(listTemplates, tracks)
+    return [[[hits[f * T + k]] for k in range(T)] for f in range(len(fl))], f0, True, (last if return_templates else None)
 
 
 def trackTemplates(listTemplates, frames, tracks, margin: int, method: int = TM_CCOEFF_NORMED, min_score=None, *,
-                   refine: bool = False, context=None) -> List[List[List[Hit]]]:
+                   refine: bool = False, update=None, return_templates: bool = False, context=None):
     """
     Follow each track through ``frames`` (a sequence of arrays of one shape and dtype, or one ``(F, H, W[, C])`` array):
     element ``[f][k]`` is what ``findMatchesInBoxes(listTemplates, frames[f], ..., method, N_object=1)`` returns for track
@@ -143,10 +205,13 @@ def trackTemplates(listTemplates, frames, tracks, margin: int, method: int = TM_
     frame's hit.  ``tracks``: pairs ``((x, y, w, h), j)``, template ``listTemplates[j]`` starting from that box in frame
     0.  ``min_score``: a hit that does not pass it (``next_box``) leaves its track's box where it was.  ``refine``
     (True / False): every hit at its sub-pixel position, ``refineHits(listTemplates, frames[f], [hit], method)`` of the
-    unrefined call's hit, from the same native call (the module's docstring).  ``context``: the _lib.Context to run on
-    (default: the process's).
+    unrefined call's hit, from the same native call (the module's docstring).  ``update`` (None, or a rate in (0, 1]):
+    every track adapts a template of its own, ``blend_template(template, hit's window, update)`` after each frame whose
+    hit passes (the module's docstring); ``return_templates=True`` returns ``(result, templates)`` with every track's
+    template after the last frame.  ``context``: the _lib.Context to run on (default: the process's).
     """
-    return _track(listTemplates, frames, tracks, margin, method, min_score, context, False, refine)[0]
+    r = _track(listTemplates, frames, tracks, margin, method, min_score, context, False, refine, update, return_templates)
+    return (r[0], r[3]) if return_templates else r[0]
 
 
 def positions(result) -> np.ndarray:

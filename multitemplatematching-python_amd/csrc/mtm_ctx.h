@@ -342,6 +342,11 @@ struct mtm_ctx {
     // mtm_track_boxes (mtm_track.hip): the per-call track table (rewritten on the device every frame), tile table, extremum
     // keys and records; mtm_track_boxes_nbhd: the records' 3 x 3 neighbourhoods (nine floats per record).
     DevBuf trk_units, trk_tiles, trk_keys, trk_out, trk_nbhd;
+    // mtm_track_boxes_adapt: the call's own templates, indexed by the track - byte planes (track k's at trk_toff[k] in
+    // trk_tpx, prepare_window_templates' layout), epilogue constants (trk_td) - and each track's pass flag of the frame.
+    // Copies of win_tpx / box_td made at the start of the call and rewritten by track_adopt_kernel: the template set's
+    // own tables and their generations are never touched.
+    DevBuf trk_tpx, trk_toff, trk_td, trk_pass;
     // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
     // template set sub_gen) and the per-call point table and scores.
     uint64_t sub_gen = 0;

@@ -118,48 +118,11 @@ TemplStats compute_templ_stats(const double* px, const double* mask, int rows, i
 }
 
 // The same from the per-channel sums (sum v, sum v^2) - or, masked, from sum (v*m)^2 alone: what the device
-// reduction over a template source delivers (exact integers for uint8 pixels).
+// reduction over a template source delivers (exact integers for uint8 pixels).  The arithmetic is
+// templ_stats_from_sums_inl's (mtm_templ_stats.h), which track_adopt_kernel calls on the device.
 TemplStats templ_stats_from_sums(const double* sum, const double* sumsq, double templ2_mask2_sum, bool masked, int rows,
                                  int cols, int chans, int method) {
-    TemplStats st;
-    const double n = (double)rows * (double)cols;
-    st.inv_area = 1.0 / ((double)rows * (double)cols);
-    if (masked) {
-        st.templ2_mask2_sum = templ2_mask2_sum;
-        return st;
-    }
-    double mean[4] = {0, 0, 0, 0}, sdv[4] = {0, 0, 0, 0};
-    for (int c = 0; c < chans && c < 4; ++c) {
-        mean[c] = sum[c] / n;
-        const double var = sumsq[c] / n - mean[c] * mean[c];
-        sdv[c] = std::sqrt(std::max(var, 0.0));
-        st.centred_sum2 += std::max(var, 0.0) * n + 1e-15 * sumsq[c];       // (+ the cancellation in sumsq / n - mean^2)
-    }
-    if (method == MTM_TM_CCORR) return st;
-    const int num_type = (method == MTM_TM_CCORR || method == MTM_TM_CCORR_NORMED) ? 0
-                       : (method == MTM_TM_CCOEFF || method == MTM_TM_CCOEFF_NORMED) ? 1 : 2;
-    for (int c = 0; c < 4; ++c) st.mean[c] = mean[c];
-    if (method != MTM_TM_CCOEFF) {
-        double templ_norm = 0.0;
-        for (int c = 0; c < chans && c < 4; ++c) templ_norm += sdv[c] * sdv[c];
-        if (templ_norm < DBL_EPSILON && method == MTM_TM_CCOEFF_NORMED) {
-            st.all_ones = 1;
-            return st;
-        }
-        double msum = 0.0;
-        for (int c = 0; c < chans && c < 4; ++c) msum += mean[c] * mean[c];
-        double templ_sum2 = templ_norm + msum;
-        if (num_type != 1) {
-            for (int c = 0; c < 4; ++c) st.mean[c] = 0.0;
-            templ_norm = templ_sum2;
-        }
-        templ_sum2 /= st.inv_area;
-        templ_norm = std::sqrt(templ_norm);
-        templ_norm /= std::sqrt(st.inv_area);
-        st.templ_norm = templ_norm;
-        st.templ_sum2 = templ_sum2;
-    }
-    return st;
+    return templ_stats_from_sums_inl(sum, sumsq, templ2_mask2_sum, masked, rows, cols, chans, method);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -615,6 +578,39 @@ const char* mtm_last_error(void) { return mtm::g_last_error.c_str(); }
 int mtm_abi_version(void) { return MTM_ABI_VERSION; }
 
 int mtm_debug_tail_split(int h, int w, double thr) { return mtm::tail_split_rule(h, w, thr); }
+
+int mtm_debug_templ_stats(const void* px, int rows, int cols, int chans, int dtype, int method, double* out7) {
+    if (!px || !out7 || rows < 1 || cols < 1 || chans < 1 || chans > 4 || method < MTM_TM_SQDIFF || method > MTM_TM_CCOEFF_NORMED ||
+        (dtype != MTM_U8 && dtype != MTM_U16 && dtype != MTM_F32)) {
+        mtm::set_error("mtm_debug_templ_stats: bad arguments");
+        return MTM_E_INVALID;
+    }
+    const size_t plane = (size_t)rows * cols;
+    std::vector<double> planar(plane * (size_t)chans);
+    for (size_t p = 0; p < plane; ++p)
+        for (int c = 0; c < chans; ++c) {
+            const size_t i = p * (size_t)chans + (size_t)c;
+            double v;
+            if (dtype == MTM_U8) {
+                v = (double)static_cast<const uint8_t*>(px)[i];
+            } else if (dtype == MTM_U16) {
+                uint16_t u;
+                std::memcpy(&u, static_cast<const uint8_t*>(px) + 2 * i, sizeof(u));
+                v = (double)u;
+            } else {
+                float f;
+                std::memcpy(&f, static_cast<const uint8_t*>(px) + 4 * i, sizeof(f));
+                v = (double)f;
+            }
+            planar[(size_t)c * plane + p] = v;
+        }
+    const mtm::TemplStats st = mtm::compute_templ_stats(planar.data(), nullptr, rows, cols, chans, method, dtype != MTM_F32);
+    for (int c = 0; c < 4; ++c) out7[c] = st.mean[c];
+    out7[4] = st.templ_norm;
+    out7[5] = st.templ_sum2;
+    out7[6] = (double)st.all_ones;
+    return MTM_OK;
+}
 
 int mtm_nms(const mtm_hit* hits, int64_t n, double score_threshold, int ascending,
             int64_t n_object, double max_overlap, int32_t* keep, int64_t* n_keep) {

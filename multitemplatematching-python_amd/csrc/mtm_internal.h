@@ -7,30 +7,18 @@
 
 #include "../../include/mtm_hip.h"
 #include "mtm_route.h"
+#include "mtm_templ_stats.h"       // TemplStats, templ_stats_from_sums_inl
 
 namespace mtm {
 
 void set_error(const std::string& msg);   // thread-local message behind mtm_last_error()
-
-// cv::meanStdDev + the template constants of OpenCV's common_matchTemplate, in the same
-// operation order as oracle/mtm_oracle.py::match_template (so that both sides round alike).
-struct TemplStats {
-    double mean[4] = {0, 0, 0, 0};   // templMean per channel (zeroed when numType != 1)
-    double templ_norm = 0;           // sqrt(templNorm) / sqrt(invArea)
-    double templ_sum2 = 0;           // templSum2 / invArea
-    double inv_area = 0;
-    int all_ones = 0;                // TM_CCOEFF_NORMED with a constant template: map == 1
-    double templ2_mask2_sum = 0;     // masked path: sum((T*M)^2)
-    double centred_sum2 = 0;         // sum over channels of sum (T - channel mean)^2, whatever the method (error bound of the
-                                     // refined raw-sum extremum of float32 classes, mtm_bf16.hip.h)
-};
 
 // px: planar float64 copies of the template (and mask weights, or nullptr), chans planes of
 // rows*cols each.  `integer` = values are exact integers (uint8 source).
 TemplStats compute_templ_stats(const double* px, const double* mask, int rows, int cols, int chans,
                                int method, bool integer);
 
-// the same from the per-channel sums (sum v, sum v^2), or - masked - from sum((v*m)^2) alone
+// the same from the per-channel sums (sum v, sum v^2), or - masked - from sum((v*m)^2) alone (templ_stats_from_sums_inl)
 TemplStats templ_stats_from_sums(const double* sum, const double* sumsq, double templ2_mask2_sum, bool masked, int rows,
                                  int cols, int chans, int method);
 

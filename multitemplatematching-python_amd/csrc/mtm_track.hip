@@ -4,10 +4,14 @@
 // waits once per call instead of twice per frame.  uint8 (1 or 3 channels) and single-channel uint16, unmasked templates
 // of one mtm_set_templates call.  mtm_track_boxes_nbhd also scores the 3 x 3 neighbourhood of every record in its frame's
 // own map (track_nbhd_kernel) while the frame is on the device: what mtm_hit_neighbourhoods returns for it.
+// mtm_track_boxes_adapt gives every track a template of its own - a copy of its list template in buffers of the call,
+// indexed by the track - and blends it with the window of every hit that passes (track_adopt_kernel), its statistics
+// recomputed on the device: the same score, update and neighbourhood kernels on per-track tables.
 #include "mtm_ctx.h"
 #include "mtm_device_util.hip.h"
 #include "mtm_k_nbhd.hip.h"
 #include "mtm_k_window.hip.h"
+#include "mtm_templ_stats.h"
 
 using namespace mtm;
 using namespace mtmi;
@@ -75,11 +79,12 @@ __global__ __launch_bounds__(256) void track_score_kernel(ImageDev img, const ui
 // One lane per track, after the frame's score launch: the frame's record of the track from its key (decode_quality_key,
 // mtm_host.cpp), in frame coordinates, into out[k]; the next frame's box (MTM.tracking.next_box: the hit widened by
 // `margin` on every side, clipped to the frame; kept when use_min is set and the score does not pass min_score - below it
-// for the difference methods, above it for the others, never when NaN); the key cleared for the next frame.
+// for the difference methods, above it for the others, never when NaN); the key cleared for the next frame.  `passed`
+// (or nullptr): passed[k] = whether the frame's hit moved the box, for track_adopt_kernel.
 __global__ __launch_bounds__(256) void track_update_kernel(TrackUnit* __restrict__ units, const TemplDev* __restrict__ td,
                                                            unsigned long long* __restrict__ keys, int n, int mode_min,
                                                            int margin, int use_min, double min_score, int rows, int cols,
-                                                           mtm_hit* __restrict__ out) {
+                                                           mtm_hit* __restrict__ out, uint8_t* __restrict__ passed) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     TrackUnit U = units[k];
@@ -97,6 +102,7 @@ __global__ __launch_bounds__(256) void track_update_kernel(TrackUnit* __restrict
     out[k] = r;
     const double s = (double)r.score;
     const bool pass = !use_min || (mode_min ? s < min_score : s > min_score);
+    if (passed) passed[k] = pass ? 1 : 0;
     if (pass) {
         const long long x0 = max(0ll, (long long)r.x - margin), y0 = max(0ll, (long long)r.y - margin);
         const long long x1 = min((long long)cols, (long long)r.x + w + margin);
@@ -138,6 +144,73 @@ __global__ __launch_bounds__(256) void track_nbhd_kernel(ImageDev img, const uin
     if (tid < 9) out[(size_t)blockIdx.x * 9 + tid] = score;
 }
 
+// Grid: one 256-thread work-group per track (launch slice), after the frame's track_update_kernel and, where there is
+// one, its track_nbhd_kernel: a track whose hit passed (passed[k]) adopts the hit's window.  Every pixel of its template
+// becomes (T (256 - a) + W a + 128) >> 8 in integers (MTM.tracking.blend_template), W the frame's pixel under the hit
+// rec[k] - uint8: plane c of the stack at img.u8 + c * plane; uint16: high << 8 | (lo_b ^ 0x80) -, in place in the
+// track's planes at tpx + toff[k] ([CH][h][w]; uint16: the high-byte plane, then the low-byte plane, unbiased).  The sums
+// of the new template's pixels and of their squares per channel are reduced in uint64 (exact: at most 2^21 uint16 pixels,
+// sum v^2 < 2^53) in a fixed order, and thread 0 writes the constants templ_stats_from_sums_inl gives for them - what
+// mtm_set_templates would compute for the new template - into td[k]; the fields the box kernels do not read stay.
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void track_adopt_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
+                                                          uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
+                                                          TemplDev* __restrict__ td, const mtm_hit* __restrict__ rec,
+                                                          const uint8_t* __restrict__ passed, int row_off, int rows,
+                                                          int method, int blend_a) {
+    __shared__ unsigned long long red[4];
+    const int k = blockIdx.x;
+    if (!passed[k]) return;                 // (the same for the whole work-group: before any barrier)
+    const mtm_hit R = rec[k];
+    const int h = td[k].rows, w = td[k].cols;
+    // (a record always lies inside its frame's map; a window that did not would be read out of bounds)
+    if (R.x < 0 || R.y < 0 || R.x > img.cols - w || R.y > rows - h) return;
+    const int tid = threadIdx.x;
+    const int n = h * w;
+    uint8_t* tp = tpx + toff[k];
+    const size_t base = (size_t)(row_off + R.y) * img.u8_pitch + (size_t)R.x;
+    const uint32_t a = (uint32_t)blend_a, b = 256u - (uint32_t)blend_a;
+    unsigned long long s1[CH], s2[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        s1[c] = 0ull;
+        s2[c] = 0ull;
+        for (int p = tid; p < n; p += 256) {
+            const size_t ip = base + (size_t)(p / w) * img.u8_pitch + (size_t)(p % w);
+            uint32_t v;
+            if constexpr (U16) {
+                const uint32_t wv = ((uint32_t)img.u8[ip] << 8) | ((uint32_t)lo_b[ip] ^ 0x80u);
+                const uint32_t tv = ((uint32_t)tp[p] << 8) | (uint32_t)tp[(size_t)n + p];
+                v = (tv * b + wv * a + 128u) >> 8;
+                tp[p] = (uint8_t)(v >> 8);
+                tp[(size_t)n + p] = (uint8_t)(v & 255u);
+            } else {
+                const uint32_t wv = img.u8[(size_t)c * img.u8_plane + ip];
+                const size_t tq = (size_t)c * n + p;
+                v = ((uint32_t)tp[tq] * b + wv * a + 128u) >> 8;
+                tp[tq] = (uint8_t)v;
+            }
+            s1[c] += v;
+            s2[c] += (unsigned long long)v * v;
+        }
+    }
+    double sum[kMaxChans] = {0.0, 0.0, 0.0, 0.0}, sumsq[kMaxChans] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        sum[c] = (double)sub_reduce(s1[c], red);
+        sumsq[c] = (double)sub_reduce(s2[c], red);
+    }
+    if (tid == 0) {
+        const TemplStats st = templ_stats_from_sums_inl(sum, sumsq, 0.0, false, h, w, CH, method);
+        TemplDev& T = td[k];
+#pragma unroll
+        for (int c = 0; c < kMaxChans; ++c) T.mean[c] = st.mean[c];
+        T.templ_norm = st.templ_norm;
+        T.templ_sum2 = st.templ_sum2;
+        T.all_ones = st.all_ones;
+    }
+}
+
 }  // namespace mtm
 
 namespace {
@@ -152,15 +225,41 @@ int track_chunk_frames(const mtm_ctx* c, int rows, int cols, int chans) {
     return std::min(by_rows, by_mem);
 }
 
-// mtm_track_boxes (nbhd == nullptr, with_nbhd false) and mtm_track_boxes_nbhd (with_nbhd: `nbhd` is required).
+// The templates of the tracks as the caller holds them - interleaved pixels, tightly packed, track after track - from
+// their planes `planar` (track k's at toff[k]: prepare_window_templates' layout).
+void unpack_track_templates(const std::vector<uint8_t>& planar, const std::vector<long long>& toff,
+                            const std::vector<BlobTempl>& tl, const mtm_box_unit* start, int n_tracks, uint8_t* dst) {
+    for (int k = 0; k < n_tracks; ++k) {
+        const BlobTempl& t = tl[(size_t)start[k].templ_idx];
+        const size_t plane = (size_t)t.rows * t.cols;
+        const uint8_t* src = planar.data() + toff[(size_t)k];
+        if (t.dtype == MTM_U16) {
+            for (size_t p = 0; p < plane; ++p) {
+                const uint16_t v = (uint16_t)((unsigned)src[p] << 8 | src[plane + p]);
+                std::memcpy(dst + 2 * p, &v, sizeof(v));
+            }
+            dst += 2 * plane;
+        } else {
+            for (size_t p = 0; p < plane; ++p)
+                for (int ch = 0; ch < t.chans; ++ch) dst[p * t.chans + ch] = src[(size_t)ch * plane + p];
+            dst += plane * t.chans;
+        }
+    }
+}
+
+// mtm_track_boxes (nbhd == nullptr, with_nbhd false), mtm_track_boxes_nbhd (with_nbhd: `nbhd` is required) and
+// mtm_track_boxes_adapt (blend_a > 0: per-track templates, adopted after every passing hit; nbhd, templ_out and stats_out
+// optional).
 int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
                 int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min, double min_score,
-                mtm_hit* out, float* nbhd, bool with_nbhd) {
+                mtm_hit* out, float* nbhd, bool with_nbhd, int blend_a = 0, void* templ_out = nullptr,
+                double* stats_out = nullptr) {
     if (!c || n_frames < 0 || n_tracks < 0 || margin < 0 || (n_frames > 0 && !frames) ||
         (n_tracks > 0 && !start) || (n_frames > 0 && n_tracks > 0 && (!out || (with_nbhd && !nbhd)))) {
         set_error(std::string(who) + ": bad arguments");
         return MTM_E_INVALID;
     }
+    const bool adapt = blend_a > 0;
     MTM_NOT_IN_FLIGHT(c, who);
     if (n_frames == 0 || n_tracks == 0) return MTM_OK;
     for (int f = 0; f < n_frames; ++f) MTMC(check_image_args(frames[f], rows, cols, chans, dtype, row_stride_bytes, who));
@@ -228,6 +327,45 @@ int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_fr
     MTMC(c->trk_keys.ensure(sizeof(unsigned long long) * (size_t)n_tracks));
     MTMC(c->trk_out.ensure(sizeof(mtm_hit) * n_out));
     if (nbhd) MTMC(c->trk_nbhd.ensure(sizeof(float) * 9 * n_out));
+    // the tables the kernels read: the template set's (indexed by the list), or the call's own copies (indexed by the track)
+    uint8_t* tpx = c->win_tpx.as<uint8_t>();
+    const long long* toff = c->win_toff.as<long long>();
+    TemplDev* td = c->box_td.as<TemplDev>();
+    uint8_t* passed = nullptr;
+    std::vector<long long> ktoff;
+    size_t kbytes = 0;
+    if (adapt) {
+        std::vector<long long> ltoff(tl.size());         // (prepare_window_templates' offsets)
+        long long at = 0;
+        for (size_t i = 0; i < tl.size(); ++i) {
+            ltoff[i] = at;
+            at += (long long)tl[i].rows * tl[i].cols * (tl[i].dtype == MTM_U16 ? 2 : tl[i].chans);
+        }
+        ktoff.resize((size_t)n_tracks);
+        for (int k = 0; k < n_tracks; ++k) {
+            const BlobTempl& t = tl[(size_t)start[k].templ_idx];
+            ktoff[(size_t)k] = (long long)kbytes;
+            kbytes += (size_t)t.rows * t.cols * (t.dtype == MTM_U16 ? 2 : t.chans);
+        }
+        MTMC(c->trk_tpx.ensure(kbytes));
+        MTMC(c->trk_toff.ensure(sizeof(long long) * (size_t)n_tracks));
+        MTMC(c->trk_td.ensure(sizeof(TemplDev) * (size_t)n_tracks));
+        MTMC(c->trk_pass.ensure((size_t)n_tracks));
+        for (int k = 0; k < n_tracks; ++k) {
+            const size_t j = (size_t)start[k].templ_idx;
+            const size_t bytes = (size_t)(k + 1 < n_tracks ? ktoff[(size_t)k + 1] : (long long)kbytes) - (size_t)ktoff[(size_t)k];
+            HIPC(hipMemcpyAsync(c->trk_tpx.as<uint8_t>() + ktoff[(size_t)k], tpx + ltoff[j], bytes, hipMemcpyDeviceToDevice,
+                                c->stream));
+            HIPC(hipMemcpyAsync(c->trk_td.as<TemplDev>() + k, td + j, sizeof(TemplDev), hipMemcpyDeviceToDevice, c->stream));
+            tu[(size_t)k].t = k;
+        }
+        HIPC(hipMemcpyAsync(c->trk_toff.p, ktoff.data(), sizeof(long long) * (size_t)n_tracks, hipMemcpyHostToDevice,
+                            c->stream));
+        tpx = c->trk_tpx.as<uint8_t>();
+        toff = c->trk_toff.as<long long>();
+        td = c->trk_td.as<TemplDev>();
+        passed = c->trk_pass.as<uint8_t>();
+    }
     HIPC(hipEventRecord(c->ev[0], c->stream));
     HIPC(hipMemcpyAsync(c->trk_units.p, tu.data(), sizeof(TrackUnit) * tu.size(), hipMemcpyHostToDevice, c->stream));
     HIPC(hipMemcpyAsync(c->trk_tiles.p, tiles.data(), sizeof(TrackTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
@@ -245,10 +383,9 @@ int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_fr
         const uint8_t* lo_b = c->slot[c->cur].u8b.as<uint8_t>() + img.u8_plane;     // uint16: [high ^ 0x80][low ^ 0x80]
         for (int fl = 0; fl < nb; ++fl) {
 #define MTM_TRACK_LAUNCH(CH, U16)                                                                                            \
-    hipLaunchKernelGGL((track_score_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, lo_b, c->win_tpx.as<uint8_t>(), \
-                       c->win_toff.as<long long>(), c->box_td.as<TemplDev>(), c->trk_units.as<TrackUnit>(),                  \
-                       c->trk_tiles.as<TrackTile>() + t0, fl * rows, c->method, mode_min ? 1 : 0,                            \
-                       c->trk_keys.as<unsigned long long>())
+    hipLaunchKernelGGL((track_score_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, lo_b, tpx, toff, td,            \
+                       c->trk_units.as<TrackUnit>(), c->trk_tiles.as<TrackTile>() + t0, fl * rows, c->method,                \
+                       mode_min ? 1 : 0, c->trk_keys.as<unsigned long long>())
             for (size_t t0 = 0; t0 < tiles.size(); t0 += kTrackLaunchTiles) {
                 const unsigned nt = (unsigned)std::min(kTrackLaunchTiles, tiles.size() - t0);
                 if (dtype == MTM_U16) MTM_TRACK_LAUNCH(1, true);
@@ -258,18 +395,17 @@ int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_fr
             }
 #undef MTM_TRACK_LAUNCH
             hipLaunchKernelGGL(track_update_kernel, dim3(ublocks), dim3(256), 0, c->stream, c->trk_units.as<TrackUnit>(),
-                               c->box_td.as<TemplDev>(), c->trk_keys.as<unsigned long long>(), n_tracks, mode_min ? 1 : 0,
-                               margin, use_min ? 1 : 0, min_score, rows, cols,
-                               c->trk_out.as<mtm_hit>() + (size_t)(f0 + fl) * n_tracks);
+                               td, c->trk_keys.as<unsigned long long>(), n_tracks, mode_min ? 1 : 0, margin,
+                               use_min ? 1 : 0, min_score, rows, cols,
+                               c->trk_out.as<mtm_hit>() + (size_t)(f0 + fl) * n_tracks, passed);
             HIPC(hipGetLastError());
-            if (!nbhd) continue;
+            const size_t r0 = (size_t)(f0 + fl) * n_tracks;
             // the frame's neighbourhoods, from its records and its rows of the stack: no upload, no wait
 #define MTM_TRACK_NBHD(CH, U16)                                                                                              \
-    hipLaunchKernelGGL((track_nbhd_kernel<CH, U16>), dim3(nk), dim3(256), 0, c->stream, img, lo_b, c->win_tpx.as<uint8_t>(),  \
-                       c->win_toff.as<long long>(), c->box_td.as<TemplDev>(), c->trk_out.as<mtm_hit>() + r0 + k0, fl * rows, \
-                       rows, c->method, c->trk_nbhd.as<float>() + 9 * (r0 + k0))
-            const size_t r0 = (size_t)(f0 + fl) * n_tracks;
-            for (size_t k0 = 0; k0 < (size_t)n_tracks; k0 += kTrackLaunchNbhd) {
+    hipLaunchKernelGGL((track_nbhd_kernel<CH, U16>), dim3(nk), dim3(256), 0, c->stream, img, lo_b, tpx, toff, td,             \
+                       c->trk_out.as<mtm_hit>() + r0 + k0, fl * rows, rows, c->method,                                       \
+                       c->trk_nbhd.as<float>() + 9 * (r0 + k0))
+            for (size_t k0 = 0; nbhd && k0 < (size_t)n_tracks; k0 += kTrackLaunchNbhd) {
                 const unsigned nk = (unsigned)std::min(kTrackLaunchNbhd, (size_t)n_tracks - k0);
                 if (dtype == MTM_U16) MTM_TRACK_NBHD(1, true);
                 else if (chans == 1) MTM_TRACK_NBHD(1, false);
@@ -277,14 +413,49 @@ int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_fr
                 HIPC(hipGetLastError());
             }
 #undef MTM_TRACK_NBHD
+            // the passing tracks adopt their hits' windows: the templates of the next frame's search
+#define MTM_TRACK_ADOPT(CH, U16)                                                                                             \
+    hipLaunchKernelGGL((track_adopt_kernel<CH, U16>), dim3(nk), dim3(256), 0, c->stream, img, lo_b, tpx, toff + k0, td + k0,  \
+                       c->trk_out.as<mtm_hit>() + r0 + k0, passed + k0, fl * rows, rows, c->method, blend_a)
+            for (size_t k0 = 0; adapt && k0 < (size_t)n_tracks; k0 += kTrackLaunchNbhd) {
+                const unsigned nk = (unsigned)std::min(kTrackLaunchNbhd, (size_t)n_tracks - k0);
+                if (dtype == MTM_U16) MTM_TRACK_ADOPT(1, true);
+                else if (chans == 1) MTM_TRACK_ADOPT(1, false);
+                else MTM_TRACK_ADOPT(3, false);
+                HIPC(hipGetLastError());
+            }
+#undef MTM_TRACK_ADOPT
         }
     }
     HIPC(hipEventRecord(c->ev[1], c->stream));
     HIPC(hipMemcpyAsync(out, c->trk_out.p, sizeof(mtm_hit) * n_out, hipMemcpyDeviceToHost, c->stream));
     if (nbhd) HIPC(hipMemcpyAsync(nbhd, c->trk_nbhd.p, sizeof(float) * 9 * n_out, hipMemcpyDeviceToHost, c->stream));
+    std::vector<uint8_t> kplanar;
+    std::vector<TemplDev> ktd;
+    if (adapt && templ_out) {
+        kplanar.resize(kbytes);
+        HIPC(hipMemcpyAsync(kplanar.data(), tpx, kbytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (adapt && stats_out) {
+        ktd.resize((size_t)n_tracks);
+        HIPC(hipMemcpyAsync(ktd.data(), td, sizeof(TemplDev) * (size_t)n_tracks, hipMemcpyDeviceToHost, c->stream));
+    }
     HIPC(hipStreamSynchronize(c->stream));
     HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
     c->timing.n_hits = (int64_t)n_out;
+    if (adapt) {
+        // the records name the track (the kernels' tables are the call's own): back to the list index
+        for (size_t i = 0; i < n_out; ++i) out[i].templ_idx = start[i % (size_t)n_tracks].templ_idx;
+        if (templ_out) unpack_track_templates(kplanar, ktoff, tl, start, n_tracks, static_cast<uint8_t*>(templ_out));
+        for (int k = 0; stats_out && k < n_tracks; ++k) {
+            const TemplDev& d = ktd[(size_t)k];
+            double* o = stats_out + 7 * (size_t)k;
+            for (int ch = 0; ch < 4; ++ch) o[ch] = d.mean[ch];
+            o[4] = d.templ_norm;
+            o[5] = d.templ_sum2;
+            o[6] = (double)d.all_ones;
+        }
+    }
     // the stack is none of the caller's frames: no current image, no published maps
     c->have_image = false;
     return MTM_OK;
@@ -306,6 +477,17 @@ int mtm_track_boxes_nbhd(mtm_ctx* c, const void* const* frames, int n_frames, in
                          double min_score, mtm_hit* out, float* nbhd) {
     return track_boxes(c, "mtm_track_boxes_nbhd", frames, n_frames, rows, cols, chans, dtype, row_stride_bytes, start,
                        n_tracks, margin, use_min, min_score, out, nbhd, true);
+}
+
+int mtm_track_boxes_adapt(mtm_ctx* c, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                          int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min,
+                          double min_score, mtm_hit* out, float* nbhd, int blend_a, void* templ_out, double* stats_out) {
+    if (blend_a < 1 || blend_a > 256) {
+        set_error("mtm_track_boxes_adapt: blend_a outside 1 .. 256");
+        return MTM_E_INVALID;
+    }
+    return track_boxes(c, "mtm_track_boxes_adapt", frames, n_frames, rows, cols, chans, dtype, row_stride_bytes, start,
+                       n_tracks, margin, use_min, min_score, out, nbhd, false, blend_a, templ_out, stats_out);
 }
 
 }  // extern "C"

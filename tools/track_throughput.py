@@ -16,12 +16,19 @@ of (frame, track) hits at the true position is reported.
 The results of track_refine and matcher_refine are checked equal to track_then_refine's (labels, float positions with ==,
 sizes, float32 score bits).
 
+--update RATE times adaptive templates (update=RATE) instead, one JSON line per workload:
+  track_update - MTM.trackTemplates(..., update=RATE): every track's template blended with its hit's window on the device
+  track        - the same call with update=None, for the adaptive call's overhead per frame
+  loop_update  - the loop the adaptive call replaces: per frame and track one findMatchesInBoxes call with the track's
+                 own template (a fresh mtm_set_templates each), next_box and MTM.tracking.blend_template
+The result of track_update is checked equal to loop_update's (labels, boxes, float32 score bits, last templates).
+
 Data: each frame is one of 8 synth.smooth_u8 backgrounds (uint16: 257 x that plus noise in the low byte) with each
 track's template - a crop of another smooth_u8 image - pasted at a position that moves up to margin / 2 pixels per frame
 in each direction.  Each method is warmed up first; the four are interleaved within a repetition; medians over the
 repetitions.
 
-Usage: tools/track_throughput.py [--reps 3] [--warmup 1] [--only T1|T2|T3] [--refine]
+Usage: tools/track_throughput.py [--reps 3] [--warmup 1] [--only T1|T2|T3] [--refine | --update RATE]
 """
 import argparse
 import json
@@ -142,6 +149,54 @@ def run_refine(MTM, spec, reps, warmup):
     }
 
 
+def run_update(MTM, spec, reps, warmup, rate):
+    from MTM.tracking import blend_template, next_box
+    name, n_frames, hw, chans, dtype, n_tracks, side, margin = spec
+    templs, frames, tracks, truth = workload(spec)
+    frame_list = list(frames)
+    method = MTM.TM_CCOEFF_NORMED
+
+    def loop():
+        cur, box, out = [templs[j][1] for _, j in tracks], [b for b, _ in tracks], []
+        for f in frame_list:
+            row = []
+            for k, (_, j) in enumerate(tracks):
+                r = MTM.findMatchesInBoxes([(templs[j][0], cur[k])], f, [box[k]], method, N_object=1)[0]
+                x, y, w, h = r[0][1]
+                cur[k] = blend_template(cur[k], f[y:y + h, x:x + w], rate)
+                box[k] = next_box(box[k], r[0], margin, f.shape, method)
+                row.append(r)
+            out.append(row)
+        return out, cur
+
+    methods = {
+        "track_update": lambda: MTM.trackTemplates(templs, frames, tracks, margin, method, update=rate, return_templates=True),
+        "track": lambda: MTM.trackTemplates(templs, frames, tracks, margin, method),
+        "loop_update": loop,
+    }
+    results, ms = _time(methods, reps, max(1, warmup))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    (got, last), (ref, ref_last) = results["track_update"], results["loop_update"]
+    equal = _key(got) == _key(ref) and all(np.array_equal(a, b) for a, b in zip(last, ref_last))
+    pos = np.array([[h[0][1][:2] for h in fr] for fr in got])
+    methods["track_update"]()                       # (the default context's timing: this call's, upload to last launch)
+    t = MTM._lib.default_context().timing()
+    return {
+        "workload": name, "mode": "update", "rate": rate, "frames": n_frames,
+        "frame": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype), "tracks": n_tracks, "template": "%dx%d" % (side, side),
+        "margin": margin,
+        "ms_per_frame": {k: round(v / n_frames, 4) for k, v in med.items()},
+        "ms_per_frame_min": {k: round(min(v) / n_frames, 4) for k, v in ms.items()},
+        "ms_per_frame_max": {k: round(max(v) / n_frames, 4) for k, v in ms.items()},
+        "speedup_vs_loop_update": round(med["loop_update"] / med["track_update"], 2),
+        "update_overhead_us_per_frame": round((med["track_update"] - med["track"]) / n_frames * 1e3, 1),
+        "track_update_device_ms": round(float(t["total_ms"]), 3),
+        "equal_to_loop_update": bool(equal),
+        "recovered": round(float(np.mean(np.all(pos == truth, axis=2))), 4),
+        "reps": reps,
+    }
+
+
 def run(MTM, spec, reps, warmup):
     from MTM.tracking import next_box
     name, n_frames, hw, chans, dtype, n_tracks, side, margin = spec
@@ -193,14 +248,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--only", default=None, help="run the one workload of this name (profiling runs)")
     ap.add_argument("--refine", action="store_true", help="time sub-pixel tracking (refine=True) against today's way")
+    ap.add_argument("--update", type=float, default=None, metavar="RATE",
+                    help="time adaptive templates (update=RATE) against the plain call and the loop they replace")
     args = ap.parse_args()
+    if args.refine and args.update is not None:
+        ap.error("--refine and --update are separate measurements")
     import build as mtm_build
     mtm_build.build()
     import MTM
     for spec in WORKLOADS:
         if args.only and spec[0] != args.only:
             continue
-        print(json.dumps((run_refine if args.refine else run)(MTM, spec, args.reps, args.warmup)), flush=True)
+        if args.update is not None:
+            rec = run_update(MTM, spec, args.reps, args.warmup, args.update)
+        else:
+            rec = (run_refine if args.refine else run)(MTM, spec, args.reps, args.warmup)
+        print(json.dumps(rec), flush=True)
 
 
 if __name__ == "__main__":

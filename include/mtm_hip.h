@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -447,6 +447,24 @@ int mtm_track_boxes_nbhd(mtm_ctx* ctx, const void* const* frames, int n_frames, 
 int mtm_track_boxes_adapt(mtm_ctx* ctx, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
                           int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min,
                           double min_score, mtm_hit* out, float* nbhd, int blend_a, void* templ_out, double* stats_out);
+
+/* mtm_track_boxes with lost tracks re-acquired by a whole-frame search: mtm_track_boxes_adapt's arguments,
+ * with blend_a = 0 meaning no adaptation (templ_out and stats_out are then ignored; otherwise blend_a in 1 .. 256) and
+ * nbhd == NULL meaning no neighbourhoods; the same checks, errors and afterwards-state.  use_min must be set
+ * (MTM_E_INVALID otherwise).  In every frame, a track whose hit in its region does not pass min_score (the rule that
+ * keeps the region) is searched again in the same frame over the whole frame - region (0, 0, cols, rows), which always
+ * holds the template - with the template the region was searched with: its record of that frame becomes the extremum of
+ * the template's whole-frame score map (ties: first in row-major order of that map; the same score bits as the region's
+ * map, which it contains).  If that record passes, the next frame's region is around it (and, with blend_a, the track
+ * adopts its window); if not, the region is kept and the next frame tries again.  The neighbourhoods are those of the
+ * final records.  The second search runs on the device for exactly the tracks that failed, after the frame's first
+ * search: the host does not learn which they are and still waits once, for the records.  Two more launches per frame,
+ * one of which leaves at once in a frame that lost no track.  A track whose whole-frame map has 2^32 outputs or more
+ * returns MTM_E_INVALID (the extremum's key carries a 32-bit index). */
+int mtm_track_boxes_reacquire(mtm_ctx* ctx, const void* const* frames, int n_frames, int rows, int cols, int chans,
+                              int dtype, int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin,
+                              int use_min, double min_score, mtm_hit* out, float* nbhd, int blend_a, void* templ_out,
+                              double* stats_out);
 
 /* The 3 x 3 score neighbourhoods of n points in one call: out[9 k + 3 (1 + dy) + (1 + dx)] = the score of
  * template pts[k].templ_idx at window (x + dx, y + dy) of the image's score map, NaN for a window outside the map.  Image:

@@ -512,10 +512,10 @@ class TemplateMatcher:
         return hits
 
     def track(self, frames, tracks, margin: int, min_score=None, *, refine: bool = False, update=None,
-              return_templates: bool = False):
+              return_templates: bool = False, reacquire: bool = False):
         """
         ``trackTemplates(listTemplates, frames, tracks, margin, method, min_score, refine=refine, update=update,
-        return_templates=return_templates)`` with this matcher's list and method: the same hits and exceptions, on this
+        return_templates=return_templates, reacquire=reacquire)`` with this matcher's list and method: the same hits and exceptions, on this
         matcher's context with its templates resident across calls.  Scope as trackTemplates', for every template of the
         list.  Adapted templates (``update``) live in buffers of the call: the resident ones stay as they are.
         """
@@ -525,7 +525,7 @@ class TemplateMatcher:
             # as match_boxes: until the call returns, nothing is known to be resident
             before, self._uploaded_for = self._uploaded_for, None
             hits, f0, uploaded, last = tracking._track(self.listTemplates, frames, tracks, margin, self.method, min_score,
-                                                       self._ctx, True, refine, update, return_templates)
+                                                       self._ctx, True, refine, update, return_templates, reacquire)
             self._uploaded_for = (str(f0.dtype), 1 if f0.ndim == 2 else f0.shape[2]) if uploaded else before
         return (hits, last) if return_templates else hits
 

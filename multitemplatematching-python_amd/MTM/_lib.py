@@ -129,6 +129,10 @@ SYMBOLS = {
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "mtm_track_boxes_reacquire": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_hit_neighbourhoods": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
@@ -582,12 +586,26 @@ class Context(_RecordMemo):
         (mtm_track_boxes_adapt; the window's weight is blend_a / 256).  `templates`: the pixel arrays of the current
         templates, in their order (for the shapes of the result).  Returns (records, neighbourhoods or None, every
         track's template after the last frame, (len(units), 7) float64 array of their TEMPL_STATS_FIELDS)."""
+        return self._track_boxes_adapt("mtm_track_boxes_adapt", frames, units, margin, min_score, blend_a, templates,
+                                       with_nbhd)
+
+    def track_boxes_reacquire(self, frames, units, margin, min_score, blend_a, templates, with_nbhd=False):
+        """track_boxes_adapt's arguments and result with lost tracks searched again over the whole frame, in the same
+        native call (mtm_track_boxes_reacquire): a track whose hit does not pass `min_score` (required) gets the
+        extremum of its template's whole-frame map as the frame's record.  blend_a == 0: no adaptation - the templates
+        and their statistics are then returned as None."""
+        return self._track_boxes_adapt("mtm_track_boxes_reacquire", frames, units, margin, min_score, blend_a, templates,
+                                       with_nbhd)
+
+    def _track_boxes_adapt(self, name, frames, units, margin, min_score, blend_a, templates, with_nbhd):
         n, nt = len(frames), len(units)
+        adapt = int(blend_a) != 0
         units = np.ascontiguousarray(units, dtype=BOX_UNIT_DTYPE)
         like = [templates[j] for j in units["templ_idx"].tolist()]
         if n == 0 or nt == 0:
             return (np.zeros(0, dtype=HIT_DTYPE), (np.zeros((0, 3, 3), dtype=np.float32) if with_nbhd else None),
-                    [np.array(t) for t in like], np.zeros((nt, len(TEMPL_STATS_FIELDS))))
+                    [np.array(t) for t in like] if adapt else None,
+                    np.zeros((nt, len(TEMPL_STATS_FIELDS))) if adapt else None)
         rows = [_pixel_rows(a) for a in frames]
         if len({r[2] for r in rows}) > 1:       # (one row stride for every frame)
             rows = [_pixel_rows(np.ascontiguousarray(a)) for a in frames]
@@ -597,14 +615,16 @@ class Context(_RecordMemo):
         out = np.empty(n * nt, dtype=HIT_DTYPE)
         nbhd = np.empty((n * nt, 3, 3), dtype=np.float32) if with_nbhd else None
         sizes = [int(np.prod(t.shape)) for t in like]          # (tightly packed, in the frames' pixel type)
-        packed = np.empty(sum(sizes), dtype=a0.dtype)
-        stats = np.empty((nt, len(TEMPL_STATS_FIELDS)), dtype=np.float64)
+        packed = np.empty(sum(sizes), dtype=a0.dtype) if adapt else None
+        stats = np.empty((nt, len(TEMPL_STATS_FIELDS)), dtype=np.float64) if adapt else None
         use_min = min_score is not None
-        check(self._lib.mtm_track_boxes_adapt(self._h, ptrs, n, a0.shape[0], a0.shape[1], chans, _dtype_code(a0), stride,
-                                              units.ctypes.data, nt, int(margin), int(use_min),
-                                              float(min_score) if use_min else 0.0, out.ctypes.data,
-                                              nbhd.ctypes.data if with_nbhd else None, int(blend_a), packed.ctypes.data,
-                                              stats.ctypes.data), "mtm_track_boxes_adapt")
+        check(getattr(self._lib, name)(self._h, ptrs, n, a0.shape[0], a0.shape[1], chans, _dtype_code(a0), stride,
+                                       units.ctypes.data, nt, int(margin), int(use_min),
+                                       float(min_score) if use_min else 0.0, out.ctypes.data,
+                                       nbhd.ctypes.data if with_nbhd else None, int(blend_a),
+                                       packed.ctypes.data if adapt else None, stats.ctypes.data if adapt else None), name)
+        if not adapt:
+            return out, nbhd, None, None
         ends = np.cumsum(sizes)
         last = [packed[e - s:e].reshape(t.shape).copy() for s, e, t in zip(sizes, ends.tolist(), like)]
         return out, nbhd, last, stats

@@ -43,6 +43,31 @@ refined with the template frame f was searched with.  ``return_templates=True`` 
 ``templates[k]`` being track k's template after the last frame (copies of the originals without ``update``): a video
 tracked in pieces carries on from them.
 
+``reacquire=True`` (needs ``min_score``) recovers a track whose object left its box - a stage jump, a dropped frame, drift
+during an occlusion: a hit that does not pass ``min_score`` is followed, in the same frame, by a search of the whole
+frame for that track's template, and that search's hit is the frame's record.  Element ``[f][k]`` is exactly what this
+loop returns,
+
+    box = [b for b, _ in tracks]
+    for f in frames:
+        H, W = f.shape[:2]
+        for k, (_, j) in enumerate(tracks):
+            hit = findMatchesInBoxes(listTemplates, f, [(box[k], [j])], method, N_object=1)[0][0]
+            if not <the hit passes min_score: next_box' comparison; NaN never passes>:
+                hit = findMatchesInBoxes(listTemplates, f, [((0, 0, W, H), [j])], method, N_object=1)[0][0]
+            out[f][k] = [hit]
+            box[k] = next_box(box[k], hit, margin, f.shape, method, min_score)
+
+from one native call (mtm_track_boxes_reacquire): the second search runs on the device for exactly the tracks that
+failed, and the host never learns which they are.  The whole-frame map contains the box's map with the same score bits,
+so a failed frame's record is the frame's global extremum for that template, the first in row-major order of the
+whole-frame map on ties; if it fails too, the box stays where it was and the next frame tries again (``lost`` marks
+those frames).  Frame 0 is a frame like any other: its errors and warnings are those of the loop's first call, the
+whole-frame box always holds the template, so the second search raises nothing, and it emits no mask warning of its own
+- the call warns as often as the call without ``reacquire``.  With ``refine=True`` the frame's final record is refined;
+with ``update=rate`` the whole frame is searched with the track's own adapted template, and the track adopts the window
+of its final record when that record passes.
+
 A track is a pair ``((x, y, w, h), j)``: template ``listTemplates[j]``, searched in that box in frame 0 and around its
 last hit afterwards (``next_box``).
 
@@ -60,7 +85,7 @@ import numpy as np
 from . import _lib, boxes, subpixel
 from . import _MSG_MASK_UNSUPPORTED, Hit, TM_CCOEFF_NORMED
 
-__all__ = ["trackTemplates", "next_box", "blend_template", "positions"]
+__all__ = ["trackTemplates", "next_box", "blend_template", "positions", "lost"]
 
 
 def next_box(box, hit, margin, image_shape, method, min_score=None):
@@ -127,7 +152,7 @@ def _frames(frames):
     return fl
 
 
-def _check_args(margin, min_score, refine=False, update=None, return_templates=False):
+def _check_args(margin, min_score, refine=False, update=None, return_templates=False, reacquire=False):
     if not isinstance(margin, numbers.Integral) or isinstance(margin, bool) or margin < 0:
         raise ValueError("margin must be an integer >= 0 (got %r)" % (margin,))
     if min_score is not None and (not isinstance(min_score, numbers.Real) or isinstance(min_score, bool)):
@@ -136,6 +161,10 @@ def _check_args(margin, min_score, refine=False, update=None, return_templates=F
         raise ValueError("refine must be True or False (got %r)" % (refine,))
     if not isinstance(return_templates, bool):
         raise ValueError("return_templates must be True or False (got %r)" % (return_templates,))
+    if not isinstance(reacquire, bool):
+        raise ValueError("reacquire must be True or False (got %r)" % (reacquire,))
+    if reacquire and min_score is None:
+        raise ValueError("reacquire=True needs min_score: a track is searched again where its hit does not pass it")
     return None if update is None else _blend_weight(update)
 
 
@@ -144,12 +173,12 @@ def _originals(listTemplates, tracks):
 
 
 def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, resident, refine=False, update=None,
-           return_templates=False):
+           return_templates=False, reacquire=False):
     """trackTemplates on `ctx`.  `resident`: the context holds every template of listTemplates in list order
     (TemplateMatcher); otherwise the templates the tracks use are set now.  Returns (hits per frame and track, the first
     frame or None, whether templates were set on the context, every track's last template or None)."""
     fl = _frames(frames)
-    a = _check_args(margin, min_score, refine, update, return_templates)
+    a = _check_args(margin, min_score, refine, update, return_templates, reacquire)
     regions = [(b, [j]) for b, j in tracks]         # (the loop's unpacking of the pairs, and its errors)
     if not fl:
         return [], None, False, (_originals(listTemplates, tracks) if return_templates else None)
@@ -178,7 +207,10 @@ def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, reside
     with ctx.lock:
         ctx.set_templates(templates, method)
         last = None
-        if a is not None:
+        if reacquire:       # (one binding method for every composition: a weight of 0 is no adaptation)
+            raw, nbhd, last, _ = ctx.track_boxes_reacquire(fl, units, m, min_score, a or 0, [t[0] for t in templates],
+                                                           refine)
+        elif a is not None:
             raw, nbhd, last, _ = ctx.track_boxes_adapt(fl, units, m, min_score, a, [t[0] for t in templates], refine)
         elif refine:
             raw, nbhd = ctx.track_boxes_nbhd(fl, units, m, min_score)
@@ -197,7 +229,8 @@ def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, reside
 
 
 def trackTemplates(listTemplates, frames, tracks, margin: int, method: int = TM_CCOEFF_NORMED, min_score=None, *,
-                   refine: bool = False, update=None, return_templates: bool = False, context=None):
+                   refine: bool = False, update=None, return_templates: bool = False, reacquire: bool = False,
+                   context=None):
     """
     Follow each track through ``frames`` (a sequence of arrays of one shape and dtype, or one ``(F, H, W[, C])`` array):
     element ``[f][k]`` is what ``findMatchesInBoxes(listTemplates, frames[f], ..., method, N_object=1)`` returns for track
@@ -208,9 +241,13 @@ def trackTemplates(listTemplates, frames, tracks, margin: int, method: int = TM_
     unrefined call's hit, from the same native call (the module's docstring).  ``update`` (None, or a rate in (0, 1]):
     every track adapts a template of its own, ``blend_template(template, hit's window, update)`` after each frame whose
     hit passes (the module's docstring); ``return_templates=True`` returns ``(result, templates)`` with every track's
-    template after the last frame.  ``context``: the _lib.Context to run on (default: the process's).
+    template after the last frame.  ``reacquire`` (True / False; True needs ``min_score``): a track whose hit does not
+    pass ``min_score`` is searched again in the same frame over the whole frame, and that search's hit is the frame's
+    record - and the track's new position when it passes (the module's docstring).  ``context``: the _lib.Context to run
+    on (default: the process's).
     """
-    r = _track(listTemplates, frames, tracks, margin, method, min_score, context, False, refine, update, return_templates)
+    r = _track(listTemplates, frames, tracks, margin, method, min_score, context, False, refine, update, return_templates,
+               reacquire)
     return (r[0], r[3]) if return_templates else r[0]
 
 
@@ -228,4 +265,27 @@ def positions(result) -> np.ndarray:
             if len(hits) != 1:
                 raise ValueError("positions: frame %d, track %d holds %d hits, not one" % (f, k, len(hits)))
             out[f, k, 0], out[f, k, 1] = hits[0][1][0], hits[0][1][1]
+    return out
+
+
+def lost(result, method, min_score) -> np.ndarray:
+    """Where a trackTemplates / TemplateMatcher.track result, refined or not, lost its object: an (F, T) bool array,
+    element ``[f, k]`` true where track k's hit in frame f does not pass ``min_score`` by ``next_box``' rule (methods 0
+    and 1 pass with score < min_score, the others with score > min_score, as Python floats; a NaN score never passes).
+    Without ``reacquire`` these are the frames whose box was kept; with ``reacquire=True`` they are the frames in which
+    the object was found nowhere in the frame.  ValueError as ``positions`` raises it."""
+    if not isinstance(min_score, numbers.Real) or isinstance(min_score, bool):
+        raise ValueError("min_score must be a number (got %r)" % (min_score,))
+    result = list(result)
+    n_tracks = len(result[0]) if result else 0
+    out = np.empty((len(result), n_tracks), dtype=bool)
+    m = float(min_score)
+    for f, row in enumerate(result):
+        if len(row) != n_tracks:
+            raise ValueError("lost: frame %d holds %d tracks, frame 0 holds %d" % (f, len(row), n_tracks))
+        for k, hits in enumerate(row):
+            if len(hits) != 1:
+                raise ValueError("lost: frame %d, track %d holds %d hits, not one" % (f, k, len(hits)))
+            s = float(hits[0][2])
+            out[f, k] = not (s < m if method in (0, 1) else s > m)
     return out

@@ -347,6 +347,10 @@ struct mtm_ctx {
     // Copies of win_tpx / box_td made at the start of the call and rewritten by track_adopt_kernel: the template set's
     // own tables and their generations are never touched.
     DevBuf trk_tpx, trk_toff, trk_td, trk_pass;
+    // mtm_track_boxes_reacquire: the state of a frame's whole-frame search - per track its whole-frame unit and its lost
+    // flag, the compacted list of the lost tracks and their count (TrackLostState, mtm_track.hip) - written by
+    // track_update_kernel, read by track_reacquire_kernel, cleared by track_reupdate_kernel.
+    DevBuf trk_lost;
     // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
     // template set sub_gen) and the per-call point table and scores.
     uint64_t sub_gen = 0;

@@ -7,6 +7,9 @@
 // mtm_track_boxes_adapt gives every track a template of its own - a copy of its list template in buffers of the call,
 // indexed by the track - and blends it with the window of every hit that passes (track_adopt_kernel), its statistics
 // recomputed on the device: the same score, update and neighbourhood kernels on per-track tables.
+// mtm_track_boxes_reacquire searches every track whose hit did not pass min_score again in the same frame, over the whole
+// frame (track_reacquire_kernel over the tracks track_update_kernel listed, then track_reupdate_kernel): the lost tracks
+// are found, searched and moved on the device, the host never learns which they are.
 #include "mtm_ctx.h"
 #include "mtm_device_util.hip.h"
 #include "mtm_k_nbhd.hip.h"
@@ -31,6 +34,16 @@ struct TrackUnit {
 struct TrackTile {
     int k, ty0, tx0;
 };
+// The state of a frame's whole-frame search (mtm_track_boxes_reacquire), in one buffer: wunits[k] = track k's whole-frame
+// unit and flags[k] != 0 while k is lost in the frame being processed; list[0 .. *n_lost - 1] = the lost tracks, in any
+// order.  Between two frames every flag and the count are 0.
+struct TrackLostState {
+    TrackUnit* wunits;
+    int* list;
+    int* n_lost;
+    uint8_t* flags;
+};
+constexpr unsigned kTrackReacquireGrid = 2048;            // work-groups of a track_reacquire_kernel launch: 8 per CU
 constexpr size_t kTrackLaunchTiles = (size_t)1 << 22;     // most work-groups (tiles) of one track_score_kernel launch
 constexpr size_t kTrackLaunchNbhd = (size_t)1 << 22;      // most work-groups (tracks) of one track_nbhd_kernel launch
 
@@ -76,20 +89,8 @@ __global__ __launch_bounds__(256) void track_score_kernel(ImageDev img, const ui
     if ((tid & 63) == 0 && key != 0ull) atomicMax(keys + K.k, key);
 }
 
-// One lane per track, after the frame's score launch: the frame's record of the track from its key (decode_quality_key,
-// mtm_host.cpp), in frame coordinates, into out[k]; the next frame's box (MTM.tracking.next_box: the hit widened by
-// `margin` on every side, clipped to the frame; kept when use_min is set and the score does not pass min_score - below it
-// for the difference methods, above it for the others, never when NaN); the key cleared for the next frame.  `passed`
-// (or nullptr): passed[k] = whether the frame's hit moved the box, for track_adopt_kernel.
-__global__ __launch_bounds__(256) void track_update_kernel(TrackUnit* __restrict__ units, const TemplDev* __restrict__ td,
-                                                           unsigned long long* __restrict__ keys, int n, int mode_min,
-                                                           int margin, int use_min, double min_score, int rows, int cols,
-                                                           mtm_hit* __restrict__ out, uint8_t* __restrict__ passed) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    TrackUnit U = units[k];
-    const unsigned long long key = keys[k];
-    const int w = td[U.t].cols, h = td[U.t].rows;
+// The record of a key (decode_quality_key, mtm_host.cpp) reduced over the map of unit U, in frame coordinates.
+__device__ __forceinline__ mtm_hit track_record(const TrackUnit& U, unsigned long long key, int w, int h, int mode_min) {
     const float q = mf_order_float((uint32_t)(key >> 32));
     const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull);
     mtm_hit r;
@@ -99,21 +100,134 @@ __global__ __launch_bounds__(256) void track_update_kernel(TrackUnit* __restrict
     r.w = w;
     r.h = h;
     r.score = key ? (mode_min ? -q : q) + 0.0f : __builtin_nanf("");
+    return r;
+}
+
+// U's map becomes that of the hit r widened by `margin` on every side and clipped to the frame (MTM.tracking.next_box).
+__device__ __forceinline__ void track_move_box(TrackUnit& U, const mtm_hit& r, int margin, int rows, int cols) {
+    const long long x0 = max(0ll, (long long)r.x - margin), y0 = max(0ll, (long long)r.y - margin);
+    const long long x1 = min((long long)cols, (long long)r.x + r.w + margin);
+    const long long y1 = min((long long)rows, (long long)r.y + r.h + margin);
+    U.x0 = (int)x0;
+    U.y0 = (int)y0;
+    U.ow = (int)(x1 - x0) - r.w + 1;
+    U.oh = (int)(y1 - y0) - r.h + 1;
+}
+
+// One lane per track, after the frame's score launch: the frame's record of the track from its key (decode_quality_key,
+// mtm_host.cpp), in frame coordinates, into out[k]; the next frame's box (MTM.tracking.next_box: the hit widened by
+// `margin` on every side, clipped to the frame; kept when use_min is set and the score does not pass min_score - below it
+// for the difference methods, above it for the others, never when NaN); the key cleared for the next frame.  `passed`
+// (or nullptr): passed[k] = whether the frame's hit moved the box, for track_adopt_kernel.  REACQ
+// (mtm_track_boxes_reacquire): a track whose hit did not pass is lost - its flag is set, its whole-frame unit (0, 0,
+// rows - h + 1, cols - w + 1) written and its index appended to the list, at the slot an atomic counter hands out: the
+// list's order differs from run to run, the results do not (each track's extremum is its own atomicMax key).
+template <bool REACQ>
+__global__ __launch_bounds__(256) void track_update_kernel(TrackUnit* __restrict__ units, const TemplDev* __restrict__ td,
+                                                           unsigned long long* __restrict__ keys, int n, int mode_min,
+                                                           int margin, int use_min, double min_score, int rows, int cols,
+                                                           mtm_hit* __restrict__ out, uint8_t* __restrict__ passed,
+                                                           TrackLostState L) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    TrackUnit U = units[k];
+    const int w = td[U.t].cols, h = td[U.t].rows;
+    const mtm_hit r = track_record(U, keys[k], w, h, mode_min);
     out[k] = r;
     const double s = (double)r.score;
     const bool pass = !use_min || (mode_min ? s < min_score : s > min_score);
     if (passed) passed[k] = pass ? 1 : 0;
     if (pass) {
-        const long long x0 = max(0ll, (long long)r.x - margin), y0 = max(0ll, (long long)r.y - margin);
-        const long long x1 = min((long long)cols, (long long)r.x + w + margin);
-        const long long y1 = min((long long)rows, (long long)r.y + h + margin);
-        U.x0 = (int)x0;
-        U.y0 = (int)y0;
-        U.ow = (int)(x1 - x0) - w + 1;
-        U.oh = (int)(y1 - y0) - h + 1;
+        track_move_box(U, r, margin, rows, cols);
+        units[k] = U;
+    } else if constexpr (REACQ) {
+        L.wunits[k] = TrackUnit{U.t, 0, 0, rows - h + 1, cols - w + 1};
+        L.flags[k] = 1;
+        L.list[atomicAdd(L.n_lost, 1)] = k;
+    }
+    keys[k] = 0ull;
+}
+
+// Grid: kTrackReacquireGrid work-groups, whatever the frame lost; after the frame's track_update_kernel<true> on the same
+// stream, so every work-group reads the finished list and none waits for another.  Items i = blockIdx.x, + gridDim.x, ..
+// below *n_lost * tiles_max: item i is tile i % tiles_max (row-major over the track's own map, 16 x 16 outputs) of the
+// lost track list[i / tiles_max]; tiles_max is the tile count of the call's largest whole-frame map, and a tile past
+// the track's own count is skipped.  Trip count and skip are the same for the whole work-group (the sums below hold
+// barriers); a frame that lost nothing costs each work-group one load.  A tile is scored as track_score_kernel scores it
+// - the same sums, win_score and key - over the whole-frame unit, with the template of the table the call uses; one
+// atomicMax per wave into keys[k], which the first update cleared.
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void track_reacquire_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
+                                                              const uint8_t* __restrict__ tpx,
+                                                              const long long* __restrict__ toff,
+                                                              const TemplDev* __restrict__ td, TrackLostState L,
+                                                              unsigned long long tiles_max, int row_off, int method,
+                                                              int mode_min, unsigned long long* __restrict__ keys) {
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
+    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
+    const int tid = threadIdx.x;
+    const unsigned long long items = (unsigned long long)*L.n_lost * tiles_max;
+    for (unsigned long long i = blockIdx.x; i < items; i += gridDim.x) {
+        const int k = L.list[i / tiles_max];
+        const unsigned long long tile = i % tiles_max;
+        const TrackUnit U = L.wunits[k];
+        const unsigned long long tiles_x = (unsigned long long)((U.ow + kWinTile - 1) / kWinTile);
+        const unsigned long long tiles_y = (unsigned long long)((U.oh + kWinTile - 1) / kWinTile);
+        if (tile >= tiles_x * tiles_y) continue;            // (the same for the whole work-group)
+        const int ty0 = (int)(tile / tiles_x) * kWinTile, tx0 = (int)(tile % tiles_x) * kWinTile;
+        const TemplDev T = td[U.t];
+        const int h = T.rows, w = T.cols;
+        const uint8_t* tp = tpx + toff[U.t];
+        const double inv_area = 1.0 / ((double)h * (double)w);
+        unsigned long long corr, s2, s1[CH];
+        if constexpr (U16)
+            win_tile_sums_u16(Tl[0], Tl[1], Il[0], Il[1], img.u8, lo_b, img.u8_pitch, img.rows, img.cols, tp, h, w,
+                              row_off + ty0, tx0, corr, s1[0], s2);
+        else
+            win_tile_sums_u8<CH>(Tl[0], Il[0], img.u8, img.u8_plane, img.u8_pitch, img.rows, img.cols, tp, h, w,
+                                 row_off + ty0, tx0, corr, s1, s2);
+        const int y = ty0 + tid / kWinTile, x = tx0 + tid % kWinTile;
+        unsigned long long key = 0ull;
+        if (y < U.oh && x < U.ow) {
+            const float s = win_score<CH>(method, T, inv_area, corr, s1, s2);
+            const float v = mode_min ? -s : s;
+            key = ((unsigned long long)mf_float_order(v) << 32) |
+                  (0xFFFFFFFFull - (unsigned long long)((long long)y * U.ow + x));
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const unsigned long long o = __shfl_xor(key, off);
+            key = o > key ? o : key;
+        }
+        if ((tid & 63) == 0 && key != 0ull) atomicMax(keys + k, key);
+    }
+}
+
+// One lane per track, after the frame's track_reacquire_kernel: a lost track's record becomes the one its key holds over
+// its whole-frame unit - out[k] overwritten, passed[k] (or nullptr) evaluated again, the box moved around the record if it
+// passes and kept if not -, its key and flag are cleared, and the count is reset for the next frame (by the first lane:
+// no lane of this kernel reads it).  A track that was not lost is not touched.
+__global__ __launch_bounds__(256) void track_reupdate_kernel(TrackUnit* __restrict__ units, const TemplDev* __restrict__ td,
+                                                             unsigned long long* __restrict__ keys, int n, int mode_min,
+                                                             int margin, double min_score, int rows, int cols,
+                                                             mtm_hit* __restrict__ out, uint8_t* __restrict__ passed,
+                                                             TrackLostState L) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k == 0) *L.n_lost = 0;
+    if (k >= n || !L.flags[k]) return;
+    const TrackUnit W = L.wunits[k];
+    const mtm_hit r = track_record(W, keys[k], td[W.t].cols, td[W.t].rows, mode_min);
+    out[k] = r;
+    const double s = (double)r.score;
+    const bool pass = mode_min ? s < min_score : s > min_score;
+    if (passed) passed[k] = pass ? 1 : 0;
+    if (pass) {
+        TrackUnit U = units[k];
+        track_move_box(U, r, margin, rows, cols);
         units[k] = U;
     }
     keys[k] = 0ull;
+    L.flags[k] = 0;
 }
 
 // Grid: one 256-thread work-group per track (launch slice), after the frame's track_update_kernel: the 3 x 3 neighbourhood
@@ -249,14 +363,19 @@ void unpack_track_templates(const std::vector<uint8_t>& planar, const std::vecto
 
 // mtm_track_boxes (nbhd == nullptr, with_nbhd false), mtm_track_boxes_nbhd (with_nbhd: `nbhd` is required) and
 // mtm_track_boxes_adapt (blend_a > 0: per-track templates, adopted after every passing hit; nbhd, templ_out and stats_out
-// optional).
+// optional), and mtm_track_boxes_reacquire (reacq: any of the above - blend_a >= 0, nbhd optional - with the lost
+// tracks of every frame searched again over the whole frame; use_min is required).
 int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
                 int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min, double min_score,
                 mtm_hit* out, float* nbhd, bool with_nbhd, int blend_a = 0, void* templ_out = nullptr,
-                double* stats_out = nullptr) {
+                double* stats_out = nullptr, bool reacq = false) {
     if (!c || n_frames < 0 || n_tracks < 0 || margin < 0 || (n_frames > 0 && !frames) ||
         (n_tracks > 0 && !start) || (n_frames > 0 && n_tracks > 0 && (!out || (with_nbhd && !nbhd)))) {
         set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    if (reacq && !use_min) {
+        set_error(std::string(who) + ": needs use_min (a track is searched again where its hit does not pass min_score)");
         return MTM_E_INVALID;
     }
     const bool adapt = blend_a > 0;
@@ -277,6 +396,7 @@ int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_fr
     // (2 margin + 1) outputs per side (a box is the hit widened by the margin), neither larger than the frame's own map
     std::vector<TrackUnit> tu((size_t)n_tracks);
     std::vector<TrackTile> tiles;
+    unsigned long long tiles_max = 0;           // (reacq) the tiles of the largest whole-frame map
     for (int k = 0; k < n_tracks; ++k) {
         const mtm_box_unit& s = start[k];
         const std::string where = std::string(who) + ": track " + std::to_string(k);
@@ -300,6 +420,15 @@ int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_fr
         if (dtype == MTM_U16 && (long long)t.rows * t.cols > (1ll << 21)) {
             set_error(where + ": uint16 template of more than 2^21 pixels");
             return MTM_E_INVALID;
+        }
+        if (reacq) {
+            const long long wh = rows - t.rows + 1, ww = cols - t.cols + 1;
+            if (wh * ww >= (1ll << 32)) {
+                set_error(where + ": whole-frame map of 2^32 outputs or more");
+                return MTM_E_INVALID;
+            }
+            tiles_max = std::max(tiles_max, (unsigned long long)((wh + kWinTile - 1) / kWinTile) *
+                                                (unsigned long long)((ww + kWinTile - 1) / kWinTile));
         }
         TrackUnit& u = tu[(size_t)k];
         u.t = s.templ_idx;
@@ -327,6 +456,18 @@ int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_fr
     MTMC(c->trk_keys.ensure(sizeof(unsigned long long) * (size_t)n_tracks));
     MTMC(c->trk_out.ensure(sizeof(mtm_hit) * n_out));
     if (nbhd) MTMC(c->trk_nbhd.ensure(sizeof(float) * 9 * n_out));
+    // (reacq) the lost state, all zero between frames: [wunits | list | n_lost | flags]
+    TrackLostState lost{nullptr, nullptr, nullptr, nullptr};
+    if (reacq) {
+        const size_t o_list = round_up(sizeof(TrackUnit) * (size_t)n_tracks, 16);
+        const size_t o_count = o_list + round_up(sizeof(int) * (size_t)n_tracks, 16);
+        const size_t o_flags = o_count + 16, bytes = o_flags + (size_t)n_tracks;
+        MTMC(c->trk_lost.ensure(bytes));
+        uint8_t* base = c->trk_lost.as<uint8_t>();
+        lost = TrackLostState{reinterpret_cast<TrackUnit*>(base), reinterpret_cast<int*>(base + o_list),
+                              reinterpret_cast<int*>(base + o_count), base + o_flags};
+        HIPC(hipMemsetAsync(base, 0, bytes, c->stream));
+    }
     // the tables the kernels read: the template set's (indexed by the list), or the call's own copies (indexed by the track)
     uint8_t* tpx = c->win_tpx.as<uint8_t>();
     const long long* toff = c->win_toff.as<long long>();
@@ -394,12 +535,33 @@ int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_fr
                 HIPC(hipGetLastError());
             }
 #undef MTM_TRACK_LAUNCH
-            hipLaunchKernelGGL(track_update_kernel, dim3(ublocks), dim3(256), 0, c->stream, c->trk_units.as<TrackUnit>(),
-                               td, c->trk_keys.as<unsigned long long>(), n_tracks, mode_min ? 1 : 0, margin,
-                               use_min ? 1 : 0, min_score, rows, cols,
-                               c->trk_out.as<mtm_hit>() + (size_t)(f0 + fl) * n_tracks, passed);
+#define MTM_TRACK_UPDATE(REACQ)                                                                                               \
+    hipLaunchKernelGGL(track_update_kernel<REACQ>, dim3(ublocks), dim3(256), 0, c->stream, c->trk_units.as<TrackUnit>(), td,  \
+                       c->trk_keys.as<unsigned long long>(), n_tracks, mode_min ? 1 : 0, margin, use_min ? 1 : 0, min_score, \
+                       rows, cols, c->trk_out.as<mtm_hit>() + (size_t)(f0 + fl) * n_tracks, passed, lost)
+            if (reacq) MTM_TRACK_UPDATE(true);
+            else MTM_TRACK_UPDATE(false);
+#undef MTM_TRACK_UPDATE
             HIPC(hipGetLastError());
             const size_t r0 = (size_t)(f0 + fl) * n_tracks;
+            // the frame's lost tracks over the whole frame, then their records and boxes from that search: a fixed grid
+            // that finds the list on the device, no wait
+#define MTM_TRACK_REACQUIRE(CH, U16)                                                                                         \
+    hipLaunchKernelGGL((track_reacquire_kernel<CH, U16>), dim3(kTrackReacquireGrid), dim3(256), 0, c->stream, img, lo_b, tpx, \
+                       toff, td, lost, tiles_max, fl * rows, c->method, mode_min ? 1 : 0,                                     \
+                       c->trk_keys.as<unsigned long long>())
+            if (reacq) {
+                if (dtype == MTM_U16) MTM_TRACK_REACQUIRE(1, true);
+                else if (chans == 1) MTM_TRACK_REACQUIRE(1, false);
+                else MTM_TRACK_REACQUIRE(3, false);
+                HIPC(hipGetLastError());
+                hipLaunchKernelGGL(track_reupdate_kernel, dim3(ublocks), dim3(256), 0, c->stream,
+                                   c->trk_units.as<TrackUnit>(), td, c->trk_keys.as<unsigned long long>(), n_tracks,
+                                   mode_min ? 1 : 0, margin, min_score, rows, cols, c->trk_out.as<mtm_hit>() + r0, passed,
+                                   lost);
+                HIPC(hipGetLastError());
+            }
+#undef MTM_TRACK_REACQUIRE
             // the frame's neighbourhoods, from its records and its rows of the stack: no upload, no wait
 #define MTM_TRACK_NBHD(CH, U16)                                                                                              \
     hipLaunchKernelGGL((track_nbhd_kernel<CH, U16>), dim3(nk), dim3(256), 0, c->stream, img, lo_b, tpx, toff, td,             \
@@ -488,6 +650,17 @@ int mtm_track_boxes_adapt(mtm_ctx* c, const void* const* frames, int n_frames, i
     }
     return track_boxes(c, "mtm_track_boxes_adapt", frames, n_frames, rows, cols, chans, dtype, row_stride_bytes, start,
                        n_tracks, margin, use_min, min_score, out, nbhd, false, blend_a, templ_out, stats_out);
+}
+
+int mtm_track_boxes_reacquire(mtm_ctx* c, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                              int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin, int use_min,
+                              double min_score, mtm_hit* out, float* nbhd, int blend_a, void* templ_out, double* stats_out) {
+    if (blend_a < 0 || blend_a > 256) {
+        set_error("mtm_track_boxes_reacquire: blend_a outside 0 .. 256");
+        return MTM_E_INVALID;
+    }
+    return track_boxes(c, "mtm_track_boxes_reacquire", frames, n_frames, rows, cols, chans, dtype, row_stride_bytes, start,
+                       n_tracks, margin, use_min, min_score, out, nbhd, false, blend_a, templ_out, stats_out, true);
 }
 
 }  // extern "C"

@@ -23,12 +23,27 @@ sizes, float32 score bits).
                  own template (a fresh mtm_set_templates each), next_box and MTM.tracking.blend_template
 The result of track_update is checked equal to loop_update's (labels, boxes, float32 score bits, last templates).
 
+--reacquire times the re-acquisition of lost tracks (reacquire=True, min_score 0.9) instead, one JSON line per workload,
+on a variant of the workload in which one track in eight jumps to a random place, outside its box, after every 10th
+frame:
+  track_reacquire - MTM.trackTemplates(..., min_score, reacquire=True): lost tracks searched over the whole frame on the
+                    device
+  track           - the same call with reacquire=False (the jumped tracks stay lost), for the cost of the second searches
+  loop_reacquire  - the loop the call replaces: findMatchesInBoxes per frame, a whole-frame findMatchesInBoxes for every
+                    hit that fails, next_box
+  match_whole     - for comparison, per jump frame one exhaustive matchTemplates(N_object=1) over the jumped tracks'
+                    templates (milliseconds per such frame)
+and on the unmodified workload with min_score -1, which every hit passes, so that nothing is ever lost (at 0.9 the
+unmodified T1 and T2 lose tracks too: their pasted copies overlap at times):
+  idle_reacquire, idle_track - reacquire=True and reacquire=False: the cost of the option when it has nothing to do
+The result of track_reacquire is checked equal to loop_reacquire's (labels, boxes, float32 score bits).
+
 Data: each frame is one of 8 synth.smooth_u8 backgrounds (uint16: 257 x that plus noise in the low byte) with each
 track's template - a crop of another smooth_u8 image - pasted at a position that moves up to margin / 2 pixels per frame
 in each direction.  Each method is warmed up first; the four are interleaved within a repetition; medians over the
 repetitions.
 
-Usage: tools/track_throughput.py [--reps 3] [--warmup 1] [--only T1|T2|T3] [--refine | --update RATE]
+Usage: tools/track_throughput.py [--reps 3] [--warmup 1] [--only T1|T2|T3] [--refine | --update RATE | --reacquire]
 """
 import argparse
 import json
@@ -60,7 +75,7 @@ def _image(seed, hw, chans, dtype, rng):
     return img
 
 
-def workload(spec, seed=0):
+def workload(spec, seed=0, jumps=False):
     name, n_frames, hw, chans, dtype, n_tracks, side, margin = spec
     rng = np.random.default_rng(seed)
     backs = [_image(seed + 1 + b, hw, chans, dtype, rng) for b in range(N_BACKGROUNDS)]
@@ -80,6 +95,10 @@ def workload(spec, seed=0):
         truth[f] = pos
         step = rng.integers(-(margin // 2), margin // 2 + 1, size=pos.shape)
         pos = np.clip(pos + step, 0, [hw[1] - side, hw[0] - side])
+        if jumps and f % 10 == 9:           # one track in eight jumps to a random place (from a generator of its own)
+            jr = np.random.default_rng(seed + 7919 * f)
+            for k in range(0, n_tracks, 8):
+                pos[k] = (int(jr.integers(0, hw[1] - side)), int(jr.integers(0, hw[0] - side)))
     tracks = [((max(0, int(x) - margin), max(0, int(y) - margin), side + 2 * margin, side + 2 * margin), k)
               for k, (x, y) in enumerate(truth[0])]
     return templs, frames, tracks, truth
@@ -197,6 +216,83 @@ def run_update(MTM, spec, reps, warmup, rate):
     }
 
 
+def run_reacquire(MTM, spec, reps, warmup, min_score=0.9):
+    from MTM.tracking import lost, next_box
+    name, n_frames, hw, chans, dtype, n_tracks, side, margin = spec
+    templs, frames, tracks, truth = workload(spec, jumps=True)
+    _, idle_frames, idle_tracks, _ = workload(spec)
+    frame_list = list(frames)
+    method = MTM.TM_CCOEFF_NORMED
+    whole = (0, 0, hw[1], hw[0])
+
+    def loop():
+        out, box, n_again = [], [b for b, _ in tracks], 0
+        for f in frame_list:
+            r = MTM.findMatchesInBoxes(templs, f, [(b, [j]) for b, (_, j) in zip(box, tracks)], method, N_object=1)
+            again = [k for k, ri in enumerate(r) if not float(ri[0][2]) > min_score]
+            if again:       # (one call for the frame's failed hits: kinder to the loop than one call per track)
+                r2 = MTM.findMatchesInBoxes(templs, f, [(whole, [tracks[k][1]]) for k in again], method, N_object=1)
+                for k, ri in zip(again, r2):
+                    r[k] = ri
+                n_again += len(again)
+            out.append(r)
+            box = [next_box(b, ri[0], margin, f.shape, method, min_score) for b, ri in zip(box, r)]
+        return out, n_again
+
+    jumped = [templs[j] for (_, j) in tracks[::8]]
+    jump_frames = [f for i, f in enumerate(frame_list) if i % 10 == 0 and i > 0]
+
+    def match_whole():
+        return [MTM.matchTemplates(jumped, f, method, 1) for f in jump_frames]
+
+    methods = {
+        "track_reacquire": lambda: MTM.trackTemplates(templs, frames, tracks, margin, method, min_score, reacquire=True),
+        "track": lambda: MTM.trackTemplates(templs, frames, tracks, margin, method, min_score),
+        "loop_reacquire": loop,
+        "idle_reacquire": lambda: MTM.trackTemplates(templs, idle_frames, idle_tracks, margin, method, -1.0,
+                                                     reacquire=True),
+        "idle_track": lambda: MTM.trackTemplates(templs, idle_frames, idle_tracks, margin, method, -1.0),
+        "match_whole": match_whole,
+    }
+    results, ms = _time(methods, reps, max(1, warmup))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    got, (ref, n_again) = results["track_reacquire"], results["loop_reacquire"]
+
+    def recovered(res):
+        return round(float(np.mean(np.all(np.array([[h[0][1][:2] for h in fr] for fr in res]) == truth, axis=2))), 4)
+
+    per = {k: v / n_frames for k, v in med.items() if k != "match_whole"}
+    methods["track_reacquire"]()                    # (the default context's timing: this call's, upload to last launch)
+    t_re = float(MTM._lib.default_context().timing()["total_ms"])
+    methods["track"]()
+    t_plain = float(MTM._lib.default_context().timing()["total_ms"])
+    methods["idle_reacquire"]()
+    t_idle_re = float(MTM._lib.default_context().timing()["total_ms"])
+    methods["idle_track"]()
+    t_idle = float(MTM._lib.default_context().timing()["total_ms"])
+    return {
+        "workload": name, "mode": "reacquire", "min_score": min_score, "frames": n_frames,
+        "frame": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype), "tracks": n_tracks, "template": "%dx%d" % (side, side),
+        "margin": margin, "second_searches": n_again,
+        "ms_per_frame": {k: round(v, 4) for k, v in per.items()},
+        "ms_per_frame_min": {k: round(min(v) / n_frames, 4) for k, v in ms.items() if k != "match_whole"},
+        "ms_per_frame_max": {k: round(max(v) / n_frames, 4) for k, v in ms.items() if k != "match_whole"},
+        "speedup_vs_loop_reacquire": round(med["loop_reacquire"] / med["track_reacquire"], 2),
+        "ms_per_second_search": round((med["track_reacquire"] - med["track"]) / max(1, n_again), 4),
+        "device_ms_per_second_search": round((t_re - t_plain) / max(1, n_again), 4),
+        "match_whole_ms_per_jump_frame": round(med["match_whole"] / max(1, len(jump_frames)), 4),
+        "idle_overhead_us_per_frame": round((per["idle_reacquire"] - per["idle_track"]) * 1e3, 1),
+        "idle_device_overhead_us_per_frame": round((t_idle_re - t_idle) / n_frames * 1e3, 1),
+        "idle_still_lost": int(lost(results["idle_reacquire"], method, -1.0).sum()),
+        "track_reacquire_device_ms": round(t_re, 3), "track_device_ms": round(t_plain, 3),
+        "equal_to_loop_reacquire": _key(got) == _key(ref),
+        "idle_equal": _key(results["idle_reacquire"]) == _key(results["idle_track"]),
+        "recovered": {"track_reacquire": recovered(got), "track": recovered(results["track"])},
+        "still_lost": int(lost(got, method, min_score).sum()),
+        "reps": reps,
+    }
+
+
 def run(MTM, spec, reps, warmup):
     from MTM.tracking import next_box
     name, n_frames, hw, chans, dtype, n_tracks, side, margin = spec
@@ -250,16 +346,20 @@ def main():
     ap.add_argument("--refine", action="store_true", help="time sub-pixel tracking (refine=True) against today's way")
     ap.add_argument("--update", type=float, default=None, metavar="RATE",
                     help="time adaptive templates (update=RATE) against the plain call and the loop they replace")
+    ap.add_argument("--reacquire", action="store_true",
+                    help="time the re-acquisition of lost tracks (reacquire=True) against the plain call and the loop")
     args = ap.parse_args()
-    if args.refine and args.update is not None:
-        ap.error("--refine and --update are separate measurements")
+    if args.refine + (args.update is not None) + args.reacquire > 1:
+        ap.error("--refine, --update and --reacquire are separate measurements")
     import build as mtm_build
     mtm_build.build()
     import MTM
     for spec in WORKLOADS:
         if args.only and spec[0] != args.only:
             continue
-        if args.update is not None:
+        if args.reacquire:
+            rec = run_reacquire(MTM, spec, args.reps, args.warmup)
+        elif args.update is not None:
             rec = run_update(MTM, spec, args.reps, args.warmup, args.update)
         else:
             rec = (run_refine if args.refine else run)(MTM, spec, args.reps, args.warmup)

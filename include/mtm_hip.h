@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -465,6 +465,22 @@ int mtm_track_boxes_reacquire(mtm_ctx* ctx, const void* const* frames, int n_fra
                               int dtype, int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, int margin,
                               int use_min, double min_score, mtm_hit* out, float* nbhd, int blend_a, void* templ_out,
                               double* stats_out);
+
+/* mtm_track_boxes for tracks that carry a set of templates: track k follows the templates
+ * set_idx[set_off[k] .. set_off[k + 1] - 1] of the current set, all of one (rows, cols); set_off has n_tracks + 1
+ * ascending entries, set_off[0] = 0.  start[k] is the frame-0 region, and start[k].templ_idx must equal
+ * set_idx[set_off[k]].  In every frame every template of the set is searched in the track's region; the frame's record
+ * is that of the template with the best extremum - the first in set order on ties, compared as float32 scores (a NaN
+ * never replaces an earlier one) - and out[f * n_tracks + k].templ_idx names it.  The next frame's region is derived from
+ * that record by mtm_track_boxes' rule.  reacquire != 0 (needs use_min): a record that does not pass min_score is followed
+ * by a whole-frame search of every template of the set, reduced the same way, as mtm_track_boxes_reacquire does for one
+ * template.  nbhd: optional (NULL: records only), the 3 x 3 neighbourhoods of the final records in the map of the
+ * winning template, as mtm_track_boxes_nbhd returns them.  Checks as mtm_track_boxes', per template; an empty set, a set
+ * of templates that differ in shape and reacquire without use_min return MTM_E_INVALID.  One host wait per call. */
+int mtm_track_boxes_sets(mtm_ctx* ctx, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                         int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, const int32_t* set_off,
+                         const int32_t* set_idx, int margin, int use_min, double min_score, int reacquire, mtm_hit* out,
+                         float* nbhd);
 
 /* The 3 x 3 score neighbourhoods of n points in one call: out[9 k + 3 (1 + dy) + (1 + dx)] = the score of
  * template pts[k].templ_idx at window (x + dx, y + dy) of the image's score map, NaN for a window outside the map.  Image:

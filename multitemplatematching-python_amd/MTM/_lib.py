@@ -133,6 +133,10 @@ SYMBOLS = {
                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
                                                  ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
                                                  ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "mtm_track_boxes_sets": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_hit_neighbourhoods": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
@@ -628,6 +632,35 @@ class Context(_RecordMemo):
         ends = np.cumsum(sizes)
         last = [packed[e - s:e].reshape(t.shape).copy() for s, e, t in zip(sizes, ends.tolist(), like)]
         return out, nbhd, last, stats
+
+    def track_boxes_sets(self, frames, start, set_off, set_idx, margin, min_score=None, reacquire=False, with_nbhd=False):
+        """track_boxes / track_boxes_nbhd / track_boxes_reacquire for tracks that carry a set of templates of one shape, in
+        one native call (mtm_track_boxes_sets).  `start`: BOX_UNIT_DTYPE records, each track's frame-0 region and the first
+        template of its set; track k's set is set_idx[set_off[k]:set_off[k + 1]] (int32 arrays, len(start) + 1 offsets).
+        Returns (records, neighbourhoods or None): a record's templ_idx is the template of the set that won its frame."""
+        n, nt = len(frames), len(start)
+        if n == 0 or nt == 0:
+            return np.zeros(0, dtype=HIT_DTYPE), (np.zeros((0, 3, 3), dtype=np.float32) if with_nbhd else None)
+        rows = [_pixel_rows(a) for a in frames]
+        if len({r[2] for r in rows}) > 1:       # (one row stride for every frame)
+            rows = [_pixel_rows(np.ascontiguousarray(a)) for a in frames]
+        a0, _, stride = rows[0]
+        chans = 1 if a0.ndim == 2 else a0.shape[2]
+        ptrs = (ctypes.c_void_p * n)(*[r[1] for r in rows])
+        start = np.ascontiguousarray(start, dtype=BOX_UNIT_DTYPE)
+        set_off = np.ascontiguousarray(set_off, dtype=np.int32)
+        set_idx = np.ascontiguousarray(set_idx, dtype=np.int32)
+        if len(set_off) != nt + 1 or len(set_idx) != int(set_off[-1]):
+            raise ValueError("track_boxes_sets: set_off holds len(start) + 1 offsets into set_idx")
+        out = np.empty(n * nt, dtype=HIT_DTYPE)
+        nbhd = np.empty((n * nt, 3, 3), dtype=np.float32) if with_nbhd else None
+        use_min = min_score is not None
+        check(self._lib.mtm_track_boxes_sets(self._h, ptrs, n, a0.shape[0], a0.shape[1], chans, _dtype_code(a0), stride,
+                                             start.ctypes.data, nt, set_off.ctypes.data, set_idx.ctypes.data, int(margin),
+                                             int(use_min), float(min_score) if use_min else 0.0, int(bool(reacquire)),
+                                             out.ctypes.data, nbhd.ctypes.data if with_nbhd else None),
+              "mtm_track_boxes_sets")
+        return out, nbhd
 
     def hit_neighbourhoods(self, image, points):
         """The 3 x 3 score neighbourhoods of `points` (POINT_DTYPE records: a template of the current set and a window of

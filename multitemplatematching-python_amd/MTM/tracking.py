@@ -71,6 +71,28 @@ of its final record when that record passes.
 A track is a pair ``((x, y, w, h), j)``: template ``listTemplates[j]``, searched in that box in frame 0 and around its
 last hit afterwards (``next_box``).
 
+A track may carry a *set* of templates instead - ``((x, y, w, h), js)`` with ``js`` a list, a tuple or a 1-D integer array
+of indices into ``listTemplates`` (negative ones count from the end, duplicates are allowed): the appearances of one
+object - rotations, flips, focus states -, all of one ``(h, w)``.  Every frame searches the whole set in the track's box,
+and the frame's record is the best variant's, so its label says which appearance the object had.  Element ``[f][k]`` is
+exactly what this loop returns,
+
+    box = [b for b, _ in tracks]
+    for f in frames:
+        for k, (_, js) in enumerate(tracks):
+            hits = findMatchesInBoxes(listTemplates, f, [(box[k], list(js))], method, N_object=1)[0]   # one per variant
+            hit = (min if method in (0, 1) else max)(hits, key=lambda h: h[2])        # the first extreme one on ties
+            out[f][k] = [hit]
+            box[k] = next_box(box[k], hit, margin, f.shape, method, min_score)
+
+from one native call (mtm_track_boxes_sets): the variants of a set share the box, so the kernel stages each tile's image
+rows and forms the window sums once per group of variants.  An integer ``j`` is the set ``(j,)``, and both kinds of
+track may be mixed in one call; a call without a set takes the code paths it took before sets existed.  With
+``reacquire=True`` a winner that does not pass ``min_score`` is followed by the whole-frame search of the whole set,
+reduced the same way; with ``refine=True`` the frame's final record is refined with the winner's template.  An empty
+set, a set whose templates differ in ``(h, w)`` (the next box is derived from the winner's size) and ``update`` or
+``return_templates=True`` together with a set raise ValueError after frame 0's own checks: adaptive sets are not built.
+
 Scope (anything else raises before any native call): findMatchesInBoxes' scope with N_object=1 - uint8 frames with 1 or 3
 channels or single-channel uint16 ones, methods 0..5, no masks for methods 0 and 3 - and frames of one shape and dtype,
 ``margin`` an integer >= 0.  Frame 0's boxes raise what the loop's first call raises; later boxes always hold their
@@ -172,6 +194,48 @@ def _originals(listTemplates, tracks):
     return [np.array(listTemplates[j][1]) for _, j in tracks]
 
 
+_MSG_ADAPTIVE_SETS = "update and return_templates are not supported for tracks that carry a set of templates"
+
+
+def _regions(tracks):
+    """tracks -> (the regions the loop's findMatchesInBoxes calls take, whether some track carries a set, the first
+    track whose set is an array that is not 1-D or None: its members reach the loop's checks flattened, and the track
+    raises after them)."""
+    regions, any_set, not_1d = [], False, None
+    for b, j in tracks:                 # (the loop's unpacking of the pairs, and its errors)
+        if isinstance(j, (list, tuple)) or (isinstance(j, np.ndarray) and j.ndim > 0):
+            if isinstance(j, np.ndarray) and j.ndim != 1:
+                if not_1d is None:
+                    not_1d = len(regions)
+                j = j.reshape(-1)
+            regions.append((b, list(j)))
+            any_set = True
+        else:
+            regions.append((b, [j]))
+    return regions, any_set, not_1d
+
+
+def _check_sets(listTemplates, tracks, reg, units, n_tracks, adaptive, not_1d):
+    """The rules of set tracks, after the loop's own checks: (n_tracks + 1 offsets of the tracks' units) or ValueError."""
+    if not_1d is not None:
+        raise ValueError("tracks[%d]: a set of templates is a list, a tuple or a 1-D array of indices (got an array of "
+                         "shape %s)" % (not_1d, tracks[not_1d][1].shape))
+    counts = np.bincount(reg.u_region, minlength=n_tracks)
+    if (counts == 0).any():
+        raise ValueError("tracks[%d]: an empty set of templates" % int(np.argmax(counts == 0)))
+    set_off = np.concatenate(([0], np.cumsum(counts))).astype(np.int32)
+    shp = np.array([listTemplates[j][1].shape[:2] for j in units["templ_idx"].tolist()], dtype=np.int64)
+    differs = (shp != shp[np.repeat(set_off[:-1], counts)]).any(axis=1)
+    if differs.any():
+        u = int(np.argmax(differs))
+        raise ValueError("tracks[%d]: the templates of a set must be of one (h, w) (template '%s' is %s, the set's first %s)"
+                         % (int(reg.u_region[u]), listTemplates[int(units["templ_idx"][u])][0], tuple(shp[u].tolist()),
+                            tuple(shp[set_off[reg.u_region[u]]].tolist())))
+    if adaptive:
+        raise ValueError(_MSG_ADAPTIVE_SETS)
+    return set_off
+
+
 def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, resident, refine=False, update=None,
            return_templates=False, reacquire=False):
     """trackTemplates on `ctx`.  `resident`: the context holds every template of listTemplates in list order
@@ -179,8 +243,10 @@ def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, reside
     frame or None, whether templates were set on the context, every track's last template or None)."""
     fl = _frames(frames)
     a = _check_args(margin, min_score, refine, update, return_templates, reacquire)
-    regions = [(b, [j]) for b, j in tracks]         # (the loop's unpacking of the pairs, and its errors)
+    regions, any_set, not_1d = _regions(tracks)
     if not fl:
+        if any_set and (a is not None or return_templates):
+            raise ValueError(_MSG_ADAPTIVE_SETS)
         return [], None, False, (_originals(listTemplates, tracks) if return_templates else None)
     if not regions:
         return [[] for _ in fl], fl[0], False, ([] if return_templates else None)
@@ -188,7 +254,11 @@ def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, reside
     if resident and method in boxes._SCOPE_METHODS:       # every resident template is in scope
         boxes._check_scope(listTemplates, f0, range(len(listTemplates)), method, boxes._SCOPE_METHODS)
     # frame 0's errors and warnings, as the loop's first call raises and emits them
-    _, units = boxes._plan(listTemplates, f0, regions, method, 1, boxes._SCOPE_METHODS)
+    reg, units = boxes._plan(listTemplates, f0, regions, method, 1, boxes._SCOPE_METHODS)
+    set_off = None
+    if any_set:
+        set_off = _check_sets(listTemplates, tracks, reg, units, len(regions), a is not None or return_templates,
+                              not_1d)
     if method not in (0, 3) and len(fl) > 1:        # the mask warnings of the loop's later calls
         n_warn = sum(1 for j in units["templ_idx"].tolist() if len(listTemplates[j]) >= 3)
         for _ in range(n_warn * (len(fl) - 1)):
@@ -207,7 +277,10 @@ def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, reside
     with ctx.lock:
         ctx.set_templates(templates, method)
         last = None
-        if reacquire:       # (one binding method for every composition: a weight of 0 is no adaptation)
+        if any_set:         # (one unit per track and variant; the record names the variant that won its frame)
+            raw, nbhd = ctx.track_boxes_sets(fl, units[set_off[:-1]], set_off, units["templ_idx"], m, min_score, reacquire,
+                                             refine)
+        elif reacquire:       # (one binding method for every composition: a weight of 0 is no adaptation)
             raw, nbhd, last, _ = ctx.track_boxes_reacquire(fl, units, m, min_score, a or 0, [t[0] for t in templates],
                                                            refine)
         elif a is not None:
@@ -222,7 +295,7 @@ def _track(listTemplates, frames, tracks, margin, method, min_score, ctx, reside
     hits = list(zip(labels[tidx].tolist(), xywh, list(raw["score"])))
     if refine:          # (one fit over every record: refineHits' numbers by construction)
         hits = subpixel._refined(hits, nbhd, method)
-    T = len(units)
+    T = len(regions)
     if return_templates and last is None:
         last = _originals(listTemplates, tracks)
     return [[[hits[f * T + k]] for k in range(T)] for f in range(len(fl))], f0, True, (last if return_templates else None)
@@ -236,7 +309,8 @@ def trackTemplates(listTemplates, frames, tracks, margin: int, method: int = TM_
     element ``[f][k]`` is what ``findMatchesInBoxes(listTemplates, frames[f], ..., method, N_object=1)`` returns for track
     k - ``[hit]`` - in the loop of this module's docstring, where each frame's search box is ``next_box`` of the previous
     frame's hit.  ``tracks``: pairs ``((x, y, w, h), j)``, template ``listTemplates[j]`` starting from that box in frame
-    0.  ``min_score``: a hit that does not pass it (``next_box``) leaves its track's box where it was.  ``refine``
+    0, or ``((x, y, w, h), js)`` with a set of same-shape templates ``[listTemplates[j] for j in js]``, of which each frame's
+    best one gives the record and its label (the module's docstring).  ``min_score``: a hit that does not pass it (``next_box``) leaves its track's box where it was.  ``refine``
     (True / False): every hit at its sub-pixel position, ``refineHits(listTemplates, frames[f], [hit], method)`` of the
     unrefined call's hit, from the same native call (the module's docstring).  ``update`` (None, or a rate in (0, 1]):
     every track adapts a template of its own, ``blend_template(template, hit's window, update)`` after each frame whose

@@ -369,7 +369,7 @@ void mtm_ctx_destroy(mtm_ctx* c) {
     if (c->pyr_sub) mtm_ctx_destroy(c->pyr_sub);
     for (DevBuf* b : {&c->win_tpx, &c->win_toff, &c->win_buf, &c->win_hits, &c->win_flags, &c->pyr_wins, &c->box_td,
                       &c->box_units, &c->box_tiles, &c->trk_units, &c->trk_tiles, &c->trk_keys, &c->trk_out,
-                      &c->trk_nbhd, &c->trk_tpx, &c->trk_toff, &c->trk_td, &c->trk_pass, &c->trk_lost})
+                      &c->trk_nbhd, &c->trk_tpx, &c->trk_toff, &c->trk_td, &c->trk_pass, &c->trk_lost, &c->trk_sets})
         b->release();
     for (auto& sl : c->slot)
         for (DevBuf* b : {&sl.raw, &sl.u8, &sl.u8b, &sl.f32}) b->release();
@@ -540,7 +540,7 @@ int mtm_debug_poison(mtm_ctx* c, int pattern_byte, int what) {
         for (mtm_ctx::DevBuf* d : {&c->stats, &c->stats_rsq, &c->stats_blk, &c->hs1, &c->hs2, &c->raw16, &c->slab_raw,
                                    &c->stats_hi, &c->maps, &c->sq_planes, &c->mbf_maps, &c->f32_sq, &c->mbf_stats, &c->mbf_mu,
                                    &c->trk_units, &c->trk_keys, &c->trk_out, &c->trk_nbhd, &c->trk_tpx, &c->trk_toff, &c->trk_td,
-                                   &c->trk_pass, &c->trk_lost, &c->sub_pts, &c->sub_out})
+                                   &c->trk_pass, &c->trk_lost, &c->trk_sets, &c->sub_pts, &c->sub_out})
             MTMC(fill(*d));
         for (auto& ln : c->lanes)
             for (mtm_ctx::DevBuf* d : {&ln.stats, &ln.stats_rsq, &ln.stats_blk, &ln.hs1, &ln.hs2, &ln.raw16, &ln.slab_raw, &ln.stats_hi})

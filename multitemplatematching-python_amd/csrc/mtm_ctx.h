@@ -351,6 +351,8 @@ struct mtm_ctx {
     // flag, the compacted list of the lost tracks and their count (TrackLostState, mtm_track.hip) - written by
     // track_update_kernel, read by track_reacquire_kernel, cleared by track_reupdate_kernel.
     DevBuf trk_lost;
+    // mtm_track_boxes_sets: the first unit of every track's set in trk_units (n_tracks + 1 offsets).
+    DevBuf trk_sets;
     // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
     // template set sub_gen) and the per-call point table and scores.
     uint64_t sub_gen = 0;

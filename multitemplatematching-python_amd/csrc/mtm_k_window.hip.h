@@ -145,6 +145,150 @@ __device__ __forceinline__ void win_tile_sums_u16(WinTemplLds& Th, WinTemplLds& 
         }
 }
 
+// ---- a set of templates of one shape over one tile (track_score_sets_kernel, mtm_track.hip) ----------------------------
+// nv <= NV templates of one h x w share the tile's image rows and both window sums: per chunk the image rows are staged
+// once, S1 and S2 are accumulated once, and only the correlation stream runs per template - 2 + nv v_dot4 streams where nv
+// calls of win_tile_sums_u8 issue 3 nv (uint16: 5 + 4 nv against 9 nv).  Every sum is the exact integer the single-template
+// functions above form, so win_score gives each template the same bits.  nv is the same for the whole work-group.
+
+// The dot products of one staged chunk for exactly N templates: the inner loop holds no branch on the set's size.
+template <int N, int NV>
+__device__ __forceinline__ void win_set_dots_u8(const WinTemplLds (&Tl)[NV], const WinImageLds& Il, int ly, int lx, int ni,
+                                                int nj, unsigned long long (&corr)[NV], unsigned long long& s1,
+                                                unsigned long long& s2) {
+    uint32_t a_corr[N], a_s1 = 0u, a_s2 = 0u;
+#pragma unroll
+    for (int n = 0; n < N; ++n) a_corr[n] = 0u;
+    for (int i = 0; i < ni; ++i) {
+        const uint32_t* irow = &Il[ly + i][0];
+        for (int j = 0; j < nj; j += 4) {
+            const uint32_t v = win_image_quad(irow, lx, j, nj);
+#pragma unroll
+            for (int n = 0; n < N; ++n) a_corr[n] = __builtin_amdgcn_udot4(v, Tl[n][i][j >> 2], a_corr[n], false);
+            a_s1 = __builtin_amdgcn_udot4(v, 0x01010101u, a_s1, false);
+            a_s2 = __builtin_amdgcn_udot4(v, v, a_s2, false);
+        }
+    }
+#pragma unroll
+    for (int n = 0; n < N; ++n) corr[n] += a_corr[n];
+    s1 += a_s1;
+    s2 += a_s2;
+}
+
+template <int N, int NV>
+__device__ __forceinline__ void win_set_dispatch_u8(int nv, const WinTemplLds (&Tl)[NV], const WinImageLds& Il, int ly, int lx,
+                                                    int ni, int nj, unsigned long long (&corr)[NV], unsigned long long& s1,
+                                                    unsigned long long& s2) {
+    if (nv == N) win_set_dots_u8<N, NV>(Tl, Il, ly, lx, ni, nj, corr, s1, s2);
+    else if constexpr (N > 1) win_set_dispatch_u8<N - 1, NV>(nv, Tl, Il, ly, lx, ni, nj, corr, s1, s2);
+}
+
+// win_tile_sums_u8 for templates tp[0 .. nv - 1] (1 <= nv <= NV), all h x w with CH planes: corr[n] = sum I T_n; s1 and s2
+// as there.  corr[n] for n >= nv is 0.
+template <int CH, int NV>
+__device__ __forceinline__ void win_tile_sums_u8_set(WinTemplLds (&Tl)[NV], WinImageLds& Il, const uint8_t* __restrict__ ip,
+                                                     long long plane, int pitch, int rows, int cols,
+                                                     const uint8_t* const (&tp)[NV], int nv, int h, int w, int oy0, int ox0,
+                                                     unsigned long long (&corr)[NV], unsigned long long (&s1)[CH],
+                                                     unsigned long long& s2) {
+    const int tid = threadIdx.x, ly = tid / kWinTile, lx = tid % kWinTile;
+#pragma unroll
+    for (int n = 0; n < NV; ++n) corr[n] = 0ull;
+    s2 = 0ull;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        s1[c] = 0ull;
+        const uint8_t* ipc = ip + c * plane;
+        for (int r0 = 0; r0 < h; r0 += kWinKR)
+            for (int c0 = 0; c0 < w; c0 += kWinKC) {
+                __syncthreads();            // the previous chunk's LDS reads are done
+#pragma unroll
+                for (int n = 0; n < NV; ++n)
+                    if (n < nv) win_load_templ(Tl[n], tp[n] + (size_t)c * h * w, h, w, r0, c0, tid);
+                win_load_image(Il, ipc, pitch, rows, cols, oy0 + r0, ox0 + c0, 0u, tid);
+                __syncthreads();
+                const int ni = min(kWinKR, h - r0), nj = min(kWinKC, w - c0);
+                win_set_dispatch_u8<NV, NV>(nv, Tl, Il, ly, lx, ni, nj, corr, s1[c], s2);
+            }
+    }
+}
+
+// The uint16 counterpart (win_tile_sums_u16's byte planes): five streams for S1 and S2 once, four per template.
+template <int N, int NV>
+__device__ __forceinline__ void win_set_dots_u16(const WinTemplLds (&Th)[NV], const WinTemplLds (&Tlo)[NV],
+                                                 const WinImageLds& Ih, const WinImageLds& Ilo, int ly, int lx, int ni, int nj,
+                                                 unsigned long long (&corr)[NV], unsigned long long& s1,
+                                                 unsigned long long& s2) {
+    uint32_t hh[N], hl[N], lh[N], ll[N], s1h = 0u, s1l = 0u, s2hh = 0u, s2hl = 0u, s2ll = 0u;
+#pragma unroll
+    for (int n = 0; n < N; ++n) hh[n] = hl[n] = lh[n] = ll[n] = 0u;
+    for (int i = 0; i < ni; ++i) {
+        const uint32_t* rh = &Ih[ly + i][0];
+        const uint32_t* rl = &Ilo[ly + i][0];
+        for (int j = 0; j < nj; j += 4) {
+            const uint32_t vh = win_image_quad(rh, lx, j, nj), vl = win_image_quad(rl, lx, j, nj);
+#pragma unroll
+            for (int n = 0; n < N; ++n) {
+                const uint32_t th = Th[n][i][j >> 2], tl = Tlo[n][i][j >> 2];
+                hh[n] = __builtin_amdgcn_udot4(vh, th, hh[n], false);
+                hl[n] = __builtin_amdgcn_udot4(vh, tl, hl[n], false);
+                lh[n] = __builtin_amdgcn_udot4(vl, th, lh[n], false);
+                ll[n] = __builtin_amdgcn_udot4(vl, tl, ll[n], false);
+            }
+            s1h = __builtin_amdgcn_udot4(vh, 0x01010101u, s1h, false);
+            s1l = __builtin_amdgcn_udot4(vl, 0x01010101u, s1l, false);
+            s2hh = __builtin_amdgcn_udot4(vh, vh, s2hh, false);
+            s2hl = __builtin_amdgcn_udot4(vh, vl, s2hl, false);
+            s2ll = __builtin_amdgcn_udot4(vl, vl, s2ll, false);
+        }
+    }
+#pragma unroll
+    for (int n = 0; n < N; ++n)
+        corr[n] += ((unsigned long long)hh[n] << 16) + (((unsigned long long)hl[n] + lh[n]) << 8) + ll[n];
+    s1 += ((unsigned long long)s1h << 8) + s1l;
+    s2 += ((unsigned long long)s2hh << 16) + ((unsigned long long)s2hl << 9) + s2ll;
+}
+
+template <int N, int NV>
+__device__ __forceinline__ void win_set_dispatch_u16(int nv, const WinTemplLds (&Th)[NV], const WinTemplLds (&Tlo)[NV],
+                                                     const WinImageLds& Ih, const WinImageLds& Ilo, int ly, int lx, int ni,
+                                                     int nj, unsigned long long (&corr)[NV], unsigned long long& s1,
+                                                     unsigned long long& s2) {
+    if (nv == N) win_set_dots_u16<N, NV>(Th, Tlo, Ih, Ilo, ly, lx, ni, nj, corr, s1, s2);
+    else if constexpr (N > 1) win_set_dispatch_u16<N - 1, NV>(nv, Th, Tlo, Ih, Ilo, ly, lx, ni, nj, corr, s1, s2);
+}
+
+// win_tile_sums_u16 for templates tp[0 .. nv - 1] (1 <= nv <= NV), all h x w: high bytes at tp[n], low bytes at
+// tp[n] + h * w.  corr[n] for n >= nv is 0.
+template <int NV>
+__device__ __forceinline__ void win_tile_sums_u16_set(WinTemplLds (&Th)[NV], WinTemplLds (&Tlo)[NV], WinImageLds& Ih,
+                                                      WinImageLds& Ilo, const uint8_t* __restrict__ hi,
+                                                      const uint8_t* __restrict__ lo_b, int pitch, int rows, int cols,
+                                                      const uint8_t* const (&tp)[NV], int nv, int h, int w, int oy0, int ox0,
+                                                      unsigned long long (&corr)[NV], unsigned long long& s1,
+                                                      unsigned long long& s2) {
+    const int tid = threadIdx.x, ly = tid / kWinTile, lx = tid % kWinTile;
+#pragma unroll
+    for (int n = 0; n < NV; ++n) corr[n] = 0ull;
+    s1 = s2 = 0ull;
+    const size_t lo_off = (size_t)h * w;
+    for (int r0 = 0; r0 < h; r0 += kWinKR)
+        for (int c0 = 0; c0 < w; c0 += kWinKC) {
+            __syncthreads();
+#pragma unroll
+            for (int n = 0; n < NV; ++n)
+                if (n < nv) {
+                    win_load_templ(Th[n], tp[n], h, w, r0, c0, tid);
+                    win_load_templ(Tlo[n], tp[n] + lo_off, h, w, r0, c0, tid);
+                }
+            win_load_image(Ih, hi, pitch, rows, cols, oy0 + r0, ox0 + c0, 0u, tid);
+            win_load_image(Ilo, lo_b, pitch, rows, cols, oy0 + r0, ox0 + c0, 0x80u, tid);
+            __syncthreads();
+            const int ni = min(kWinKR, h - r0), nj = min(kWinKC, w - c0);
+            win_set_dispatch_u16<NV, NV>(nv, Th, Tlo, Ih, Ilo, ly, lx, ni, nj, corr, s1, s2);
+        }
+}
+
 // The float32 score of a window from its exact sums: the statistics of stats_u8_kernel / stats_u8_mc_kernel /
 // stats_u16_kernel / vsum_stats_kernel (exact sums, S1^2 summed over the channels, times 1 / area) and the epilogue of every
 // score kernel (window_norm, finish_unmasked_with) - the exhaustive map's value bit for bit.

@@ -10,6 +10,9 @@
 // mtm_track_boxes_reacquire searches every track whose hit did not pass min_score again in the same frame, over the whole
 // frame (track_reacquire_kernel over the tracks track_update_kernel listed, then track_reupdate_kernel): the lost tracks
 // are found, searched and moved on the device, the host never learns which they are.
+// mtm_track_boxes_sets gives every track a set of templates of one shape: one unit per (track, template), groups of up to
+// kTrackNV units scored by one work-group that shares the tile's image rows and window sums (track_score_sets_kernel), and
+// the frame's record the best unit's, the first in set order on ties (track_update_sets_kernel).
 #include "mtm_ctx.h"
 #include "mtm_device_util.hip.h"
 #include "mtm_k_nbhd.hip.h"
@@ -325,6 +328,207 @@ __global__ __launch_bounds__(256) void track_adopt_kernel(ImageDev img, const ui
     }
 }
 
+// ---- tracks that carry a set of templates (mtm_track_boxes_sets) -----------------------------------------------------
+// The unit table holds one TrackUnit per (track, template of its set), track after track in set order; track k's units
+// are set_off[k] .. set_off[k + 1] - 1.  The templates of a set are of one shape and share the track's box, so the units
+// of a track differ in `t` alone, and a group of up to kTrackNV of them is scored by one work-group that stages the
+// tile's image rows and forms both window sums once (win_tile_sums_u8_set / win_tile_sums_u16_set).
+constexpr int kTrackNV = 4;         // templates per group: 0 B scratch in every instantiation
+
+// One 16 x 16 tile of outputs of the units u0 .. u0 + nv - 1 (one group of one track), first output (ty0, tx0).
+struct TrackSetTile {
+    int u0, nv, ty0, tx0;
+};
+
+// The tile (ty0, tx0) of map U for the nv templates gu[0 .. nv - 1].t (nv the same for the whole work-group): the fused
+// sums, then per template win_score and the key of track_score_kernel, one atomicMax per wave and template into gkeys[n].
+template <int CH, bool U16>
+__device__ __forceinline__ void track_set_tile(WinTemplLds (&Th)[kTrackNV], WinTemplLds (&Tlo)[U16 ? kTrackNV : 1],
+                                               WinImageLds (&Il)[U16 ? 2 : 1], const ImageDev& img,
+                                               const uint8_t* __restrict__ lo_b, const uint8_t* __restrict__ tpx,
+                                               const long long* __restrict__ toff, const TemplDev* __restrict__ td,
+                                               const TrackUnit* __restrict__ gu, int nv, const TrackUnit& U, int ty0, int tx0,
+                                               int row_off, int method, int mode_min,
+                                               unsigned long long* __restrict__ gkeys) {
+    const int tid = threadIdx.x;
+    int t[kTrackNV];
+    const uint8_t* tp[kTrackNV];
+#pragma unroll
+    for (int n = 0; n < kTrackNV; ++n) {
+        t[n] = gu[n < nv ? n : 0].t;
+        tp[n] = tpx + toff[t[n]];
+    }
+    const int h = td[t[0]].rows, w = td[t[0]].cols;
+    const double inv_area = 1.0 / ((double)h * (double)w);
+    unsigned long long corr[kTrackNV], s2, s1[CH];
+    if constexpr (U16)
+        win_tile_sums_u16_set<kTrackNV>(Th, Tlo, Il[0], Il[1], img.u8, lo_b, img.u8_pitch, img.rows, img.cols, tp, nv, h, w,
+                                        row_off + U.y0 + ty0, U.x0 + tx0, corr, s1[0], s2);
+    else
+        win_tile_sums_u8_set<CH, kTrackNV>(Th, Il[0], img.u8, img.u8_plane, img.u8_pitch, img.rows, img.cols, tp, nv, h, w,
+                                           row_off + U.y0 + ty0, U.x0 + tx0, corr, s1, s2);
+    const int y = ty0 + tid / kWinTile, x = tx0 + tid % kWinTile;
+    const bool inside = y < U.oh && x < U.ow;
+    const unsigned long long pos = 0xFFFFFFFFull - (unsigned long long)((long long)y * U.ow + x);
+#pragma unroll
+    for (int n = 0; n < kTrackNV; ++n) {
+        if (n >= nv) break;             // (the same for the whole work-group)
+        unsigned long long key = 0ull;
+        if (inside) {
+            const float s = win_score<CH>(method, td[t[n]], inv_area, corr[n], s1, s2);
+            const float v = mode_min ? -s : s;
+            key = ((unsigned long long)mf_float_order(v) << 32) | pos;
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const unsigned long long o = __shfl_xor(key, off);
+            key = o > key ? o : key;
+        }
+        if ((tid & 63) == 0 && key != 0ull) atomicMax(gkeys + n, key);
+    }
+}
+
+// Grid: one work-group per entry of the call's (track, group, tile) table; track_score_kernel for a group of units.
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void track_score_sets_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
+                                                               const uint8_t* __restrict__ tpx,
+                                                               const long long* __restrict__ toff,
+                                                               const TemplDev* __restrict__ td,
+                                                               const TrackUnit* __restrict__ units,
+                                                               const TrackSetTile* __restrict__ tiles, int row_off, int method,
+                                                               int mode_min, unsigned long long* __restrict__ keys) {
+    __shared__ __attribute__((aligned(16))) WinTemplLds Th[kTrackNV];
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tlo[U16 ? kTrackNV : 1];
+    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
+    const TrackSetTile K = tiles[blockIdx.x];
+    const TrackUnit U = units[K.u0];
+    if (K.ty0 >= U.oh || K.tx0 >= U.ow) return;         // (the same for the whole work-group: before any barrier)
+    track_set_tile<CH, U16>(Th, Tlo, Il, img, lo_b, tpx, toff, td, units + K.u0, K.nv, U, K.ty0, K.tx0, row_off, method,
+                            mode_min, keys + K.u0);
+}
+
+// The unit of keys[u0 .. u1 - 1] that python's max() over the units' scores (min() for the difference methods) returns: the
+// first whose quality no later one exceeds, compared as float32 - the position word of a key orders outputs within one
+// unit's map and takes no part; -0 equals +0 (mf_float_order stores +0) and a NaN never replaces an earlier unit.
+// (Deliberately not a comparison of the keys' raw high words, as the feature was first specified: the raw word ranks a NaN
+// above every number, python's max() / min() - the contract - never let a NaN replace an earlier hit.)
+__device__ __forceinline__ int track_set_winner(const unsigned long long* __restrict__ keys, int u0, int u1) {
+    int best = u0;
+    unsigned long long kb = keys[u0];
+    float qb = kb ? mf_order_float((uint32_t)(kb >> 32)) : __builtin_nanf("");
+    for (int u = u0 + 1; u < u1; ++u) {
+        const unsigned long long ku = keys[u];
+        const float q = ku ? mf_order_float((uint32_t)(ku >> 32)) : __builtin_nanf("");
+        if (q > qb) {
+            best = u;
+            qb = q;
+        }
+    }
+    return best;
+}
+
+// One lane per track, after the frame's score launches: track_update_kernel over the track's units - the record is the
+// winning unit's (track_set_winner), its templ_idx the winner's template; a passing record moves the box of every unit of
+// the track; every key of the track is cleared.  REACQ: a failing track is listed once, with the whole-frame unit its
+// set's shape gives (L.wunits[k]; the templates are those of the track's units).
+// (Deliberately one list entry and one whole-frame unit per lost track, capacity the track count, where the feature was
+// first specified with an entry per unit and capacity the unit count: the units of a track share shape and box, so their
+// whole-frame units would be copies of each other, and the item walk derives the groups from set_off.)
+template <bool REACQ>
+__global__ __launch_bounds__(256) void track_update_sets_kernel(TrackUnit* __restrict__ units, const int* __restrict__ set_off,
+                                                                const TemplDev* __restrict__ td,
+                                                                unsigned long long* __restrict__ keys, int n, int mode_min,
+                                                                int margin, int use_min, double min_score, int rows, int cols,
+                                                                mtm_hit* __restrict__ out, TrackLostState L) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int u0 = set_off[k], u1 = set_off[k + 1];
+    const int b = track_set_winner(keys, u0, u1);
+    TrackUnit U = units[b];
+    const int w = td[U.t].cols, h = td[U.t].rows;
+    const mtm_hit r = track_record(U, keys[b], w, h, mode_min);
+    out[k] = r;
+    const double s = (double)r.score;
+    const bool pass = !use_min || (mode_min ? s < min_score : s > min_score);
+    if (pass) {
+        track_move_box(U, r, margin, rows, cols);
+        for (int u = u0; u < u1; ++u) {
+            U.t = units[u].t;
+            units[u] = U;
+        }
+    } else if constexpr (REACQ) {
+        L.wunits[k] = TrackUnit{U.t, 0, 0, rows - h + 1, cols - w + 1};
+        L.flags[k] = 1;
+        L.list[atomicAdd(L.n_lost, 1)] = k;
+    }
+    for (int u = u0; u < u1; ++u) keys[u] = 0ull;
+}
+
+// track_reacquire_kernel over sets: items i = blockIdx.x, + gridDim.x, .. below *n_lost * groups_max * tiles_max; item i is
+// tile i % tiles_max of group (i / tiles_max) % groups_max of the lost track list[i / (tiles_max * groups_max)], scored
+// over the track's whole-frame unit by the fused sums.  A group or a tile past the track's own count is skipped, the same
+// for the whole work-group.
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void track_reacquire_sets_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
+                                                                   const uint8_t* __restrict__ tpx,
+                                                                   const long long* __restrict__ toff,
+                                                                   const TemplDev* __restrict__ td,
+                                                                   const TrackUnit* __restrict__ units,
+                                                                   const int* __restrict__ set_off, TrackLostState L,
+                                                                   unsigned long long groups_max, unsigned long long tiles_max,
+                                                                   int row_off, int method, int mode_min,
+                                                                   unsigned long long* __restrict__ keys) {
+    __shared__ __attribute__((aligned(16))) WinTemplLds Th[kTrackNV];
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tlo[U16 ? kTrackNV : 1];
+    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
+    const unsigned long long per_track = groups_max * tiles_max;
+    const unsigned long long items = (unsigned long long)*L.n_lost * per_track;
+    for (unsigned long long i = blockIdx.x; i < items; i += gridDim.x) {
+        const int k = L.list[i / per_track];
+        const unsigned long long g = (i % per_track) / tiles_max, tile = i % tiles_max;
+        const int u1 = set_off[k + 1];
+        if (g * kTrackNV >= (unsigned long long)(u1 - set_off[k])) continue;        // (the same for the whole work-group)
+        const int u0 = set_off[k] + (int)g * kTrackNV;
+        const TrackUnit W = L.wunits[k];
+        const unsigned long long tiles_x = (unsigned long long)((W.ow + kWinTile - 1) / kWinTile);
+        const unsigned long long tiles_y = (unsigned long long)((W.oh + kWinTile - 1) / kWinTile);
+        if (tile >= tiles_x * tiles_y) continue;
+        track_set_tile<CH, U16>(Th, Tlo, Il, img, lo_b, tpx, toff, td, units + u0, min(kTrackNV, u1 - u0), W,
+                                (int)(tile / tiles_x) * kWinTile, (int)(tile % tiles_x) * kWinTile, row_off, method, mode_min,
+                                keys + u0);
+    }
+}
+
+// track_reupdate_kernel over sets: a lost track's record becomes the winning unit's over the whole-frame keys; a passing
+// one moves every unit of the track.  A track that was not lost is not touched; flags and count are zero afterwards.
+__global__ __launch_bounds__(256) void track_reupdate_sets_kernel(TrackUnit* __restrict__ units,
+                                                                  const int* __restrict__ set_off,
+                                                                  const TemplDev* __restrict__ td,
+                                                                  unsigned long long* __restrict__ keys, int n, int mode_min,
+                                                                  int margin, double min_score, int rows, int cols,
+                                                                  mtm_hit* __restrict__ out, TrackLostState L) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k == 0) *L.n_lost = 0;
+    if (k >= n || !L.flags[k]) return;
+    const int u0 = set_off[k], u1 = set_off[k + 1];
+    const int b = track_set_winner(keys, u0, u1);
+    TrackUnit W = L.wunits[k];
+    W.t = units[b].t;
+    const mtm_hit r = track_record(W, keys[b], td[W.t].cols, td[W.t].rows, mode_min);
+    out[k] = r;
+    const double s = (double)r.score;
+    if (mode_min ? s < min_score : s > min_score) {
+        TrackUnit U = units[u0];
+        track_move_box(U, r, margin, rows, cols);
+        for (int u = u0; u < u1; ++u) {
+            U.t = units[u].t;
+            units[u] = U;
+        }
+    }
+    for (int u = u0; u < u1; ++u) keys[u] = 0ull;
+    L.flags[k] = 0;
+}
+
 }  // namespace mtm
 
 namespace {
@@ -359,6 +563,39 @@ void unpack_track_templates(const std::vector<uint8_t>& planar, const std::vecto
             dst += plane * t.chans;
         }
     }
+}
+
+// The lost state of a reacquiring call for n_tracks tracks, in c->trk_lost and zeroed on the stream (all zero between
+// frames): [wunits | list | n_lost | flags].
+int track_lost_state(mtm_ctx* c, int n_tracks, TrackLostState& lost) {
+    const size_t o_list = round_up(sizeof(TrackUnit) * (size_t)n_tracks, 16);
+    const size_t o_count = o_list + round_up(sizeof(int) * (size_t)n_tracks, 16);
+    const size_t o_flags = o_count + 16, bytes = o_flags + (size_t)n_tracks;
+    MTMC(c->trk_lost.ensure(bytes));
+    uint8_t* base = c->trk_lost.as<uint8_t>();
+    lost = TrackLostState{reinterpret_cast<TrackUnit*>(base), reinterpret_cast<int*>(base + o_list),
+                          reinterpret_cast<int*>(base + o_count), base + o_flags};
+    HIPC(hipMemsetAsync(base, 0, bytes, c->stream));
+    return MTM_OK;
+}
+
+// A frame's neighbourhoods, from its records c->trk_out[r0 .. r0 + n_tracks - 1] and its rows of the stack, into
+// c->trk_nbhd: no upload, no wait.
+int track_launch_nbhd(mtm_ctx* c, const ImageDev& img, const uint8_t* lo_b, const uint8_t* tpx, const long long* toff,
+                      const TemplDev* td, size_t r0, int n_tracks, int row_off, int rows, int chans, int dtype) {
+#define MTM_TRACK_NBHD(CH, U16)                                                                                              \
+    hipLaunchKernelGGL((track_nbhd_kernel<CH, U16>), dim3(nk), dim3(256), 0, c->stream, img, lo_b, tpx, toff, td,             \
+                       c->trk_out.as<mtm_hit>() + r0 + k0, row_off, rows, c->method,                                         \
+                       c->trk_nbhd.as<float>() + 9 * (r0 + k0))
+    for (size_t k0 = 0; k0 < (size_t)n_tracks; k0 += kTrackLaunchNbhd) {
+        const unsigned nk = (unsigned)std::min(kTrackLaunchNbhd, (size_t)n_tracks - k0);
+        if (dtype == MTM_U16) MTM_TRACK_NBHD(1, true);
+        else if (chans == 1) MTM_TRACK_NBHD(1, false);
+        else MTM_TRACK_NBHD(3, false);
+        HIPC(hipGetLastError());
+    }
+#undef MTM_TRACK_NBHD
+    return MTM_OK;
 }
 
 // mtm_track_boxes (nbhd == nullptr, with_nbhd false), mtm_track_boxes_nbhd (with_nbhd: `nbhd` is required) and
@@ -458,16 +695,7 @@ int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_fr
     if (nbhd) MTMC(c->trk_nbhd.ensure(sizeof(float) * 9 * n_out));
     // (reacq) the lost state, all zero between frames: [wunits | list | n_lost | flags]
     TrackLostState lost{nullptr, nullptr, nullptr, nullptr};
-    if (reacq) {
-        const size_t o_list = round_up(sizeof(TrackUnit) * (size_t)n_tracks, 16);
-        const size_t o_count = o_list + round_up(sizeof(int) * (size_t)n_tracks, 16);
-        const size_t o_flags = o_count + 16, bytes = o_flags + (size_t)n_tracks;
-        MTMC(c->trk_lost.ensure(bytes));
-        uint8_t* base = c->trk_lost.as<uint8_t>();
-        lost = TrackLostState{reinterpret_cast<TrackUnit*>(base), reinterpret_cast<int*>(base + o_list),
-                              reinterpret_cast<int*>(base + o_count), base + o_flags};
-        HIPC(hipMemsetAsync(base, 0, bytes, c->stream));
-    }
+    if (reacq) MTMC(track_lost_state(c, n_tracks, lost));
     // the tables the kernels read: the template set's (indexed by the list), or the call's own copies (indexed by the track)
     uint8_t* tpx = c->win_tpx.as<uint8_t>();
     const long long* toff = c->win_toff.as<long long>();
@@ -563,18 +791,7 @@ int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_fr
             }
 #undef MTM_TRACK_REACQUIRE
             // the frame's neighbourhoods, from its records and its rows of the stack: no upload, no wait
-#define MTM_TRACK_NBHD(CH, U16)                                                                                              \
-    hipLaunchKernelGGL((track_nbhd_kernel<CH, U16>), dim3(nk), dim3(256), 0, c->stream, img, lo_b, tpx, toff, td,             \
-                       c->trk_out.as<mtm_hit>() + r0 + k0, fl * rows, rows, c->method,                                       \
-                       c->trk_nbhd.as<float>() + 9 * (r0 + k0))
-            for (size_t k0 = 0; nbhd && k0 < (size_t)n_tracks; k0 += kTrackLaunchNbhd) {
-                const unsigned nk = (unsigned)std::min(kTrackLaunchNbhd, (size_t)n_tracks - k0);
-                if (dtype == MTM_U16) MTM_TRACK_NBHD(1, true);
-                else if (chans == 1) MTM_TRACK_NBHD(1, false);
-                else MTM_TRACK_NBHD(3, false);
-                HIPC(hipGetLastError());
-            }
-#undef MTM_TRACK_NBHD
+            if (nbhd) MTMC(track_launch_nbhd(c, img, lo_b, tpx, toff, td, r0, n_tracks, fl * rows, rows, chans, dtype));
             // the passing tracks adopt their hits' windows: the templates of the next frame's search
 #define MTM_TRACK_ADOPT(CH, U16)                                                                                             \
     hipLaunchKernelGGL((track_adopt_kernel<CH, U16>), dim3(nk), dim3(256), 0, c->stream, img, lo_b, tpx, toff + k0, td + k0,  \
@@ -623,6 +840,193 @@ int track_boxes(mtm_ctx* c, const char* who, const void* const* frames, int n_fr
     return MTM_OK;
 }
 
+// mtm_track_boxes_sets: track_boxes' chunks, stream order and single wait, over the unit table of the tracks' sets.
+int track_boxes_sets(mtm_ctx* c, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                     int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, const int32_t* set_off,
+                     const int32_t* set_idx, int margin, int use_min, double min_score, bool reacq, mtm_hit* out, float* nbhd) {
+    const char* who = "mtm_track_boxes_sets";
+    if (!c || n_frames < 0 || n_tracks < 0 || margin < 0 || (n_frames > 0 && !frames) ||
+        (n_tracks > 0 && (!start || !set_off || !set_idx)) || (n_frames > 0 && n_tracks > 0 && !out)) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    if (reacq && !use_min) {
+        set_error(std::string(who) + ": reacquire needs use_min (a track is searched again where its hit does not pass min_score)");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    if (n_frames == 0 || n_tracks == 0) return MTM_OK;
+    for (int f = 0; f < n_frames; ++f) MTMC(check_image_args(frames[f], rows, cols, chans, dtype, row_stride_bytes, who));
+    if (!((dtype == MTM_U8 && (chans == 1 || chans == 3)) || (dtype == MTM_U16 && chans == 1))) {
+        set_error(std::string(who) + ": takes uint8 frames with 1 or 3 channels and single-channel uint16 frames");
+        return MTM_E_INVALID;
+    }
+    if (!c->have_templ) {
+        set_error(std::string(who) + ": no templates set");
+        return MTM_E_STATE;
+    }
+    std::vector<BlobTempl> tl;
+    MTMC(parse_templ_blob(c->templ_blob, tl, who, true));
+    if (set_off[0] != 0) {
+        set_error(std::string(who) + ": set_off[0] must be 0");
+        return MTM_E_INVALID;
+    }
+    // the unit table (track after track, set order) and the (track, group, tile) table over the largest map a track can
+    // have during the call, as track_boxes sizes it
+    std::vector<TrackUnit> tu;
+    std::vector<TrackSetTile> tiles;
+    unsigned long long tiles_max = 0, groups_max = 0;       // (reacq) of the largest whole-frame map / the largest set
+    for (int k = 0; k < n_tracks; ++k) {
+        const mtm_box_unit& s = start[k];
+        const std::string where = std::string(who) + ": track " + std::to_string(k);
+        const long long n_set = (long long)set_off[k + 1] - set_off[k];
+        if (n_set < 1) {
+            set_error(where + (n_set == 0 ? ": empty set" : ": set_off is not ascending"));
+            return MTM_E_INVALID;
+        }
+        if (s.templ_idx != set_idx[set_off[k]]) {
+            set_error(where + ": start's template is not the first of its set");
+            return MTM_E_INVALID;
+        }
+        if (s.y0 < 0 || s.x0 < 0 || s.rows < 1 || s.cols < 1 || s.rows > rows - s.y0 || s.cols > cols - s.x0) {
+            set_error(where + ": box outside the frame");
+            return MTM_E_INVALID;
+        }
+        for (int i = set_off[k]; i < set_off[k + 1]; ++i) {
+            if (set_idx[i] < 0 || set_idx[i] >= (int)tl.size()) {
+                set_error(where + ": template index out of range");
+                return MTM_E_INVALID;
+            }
+            const BlobTempl& t = tl[(size_t)set_idx[i]];
+            if (t.dtype != dtype || t.chans != chans) {
+                set_error(where + ": template and frames differ in pixel type or channel count");
+                return MTM_E_INVALID;
+            }
+            if (t.rows != tl[(size_t)s.templ_idx].rows || t.cols != tl[(size_t)s.templ_idx].cols) {
+                set_error(where + ": the templates of a set must be of one shape");
+                return MTM_E_INVALID;
+            }
+        }
+        const BlobTempl& t = tl[(size_t)s.templ_idx];
+        if (t.rows > s.rows || t.cols > s.cols) {
+            set_error(where + ": template larger than the box");
+            return MTM_E_INVALID;
+        }
+        if (dtype == MTM_U16 && (long long)t.rows * t.cols > (1ll << 21)) {
+            set_error(where + ": uint16 template of more than 2^21 pixels");
+            return MTM_E_INVALID;
+        }
+        const unsigned long long groups = (unsigned long long)((n_set + kTrackNV - 1) / kTrackNV);
+        if (reacq) {
+            const long long wh = rows - t.rows + 1, ww = cols - t.cols + 1;
+            if (wh * ww >= (1ll << 32)) {
+                set_error(where + ": whole-frame map of 2^32 outputs or more");
+                return MTM_E_INVALID;
+            }
+            tiles_max = std::max(tiles_max, (unsigned long long)((wh + kWinTile - 1) / kWinTile) *
+                                                (unsigned long long)((ww + kWinTile - 1) / kWinTile));
+            groups_max = std::max(groups_max, groups);
+        }
+        const int oh = s.rows - t.rows + 1, ow = s.cols - t.cols + 1;
+        for (int i = set_off[k]; i < set_off[k + 1]; ++i) tu.push_back(TrackUnit{set_idx[i], s.y0, s.x0, oh, ow});
+        const long long side = 2ll * margin + 1;
+        const int th = (int)std::min<long long>(std::max<long long>(oh, side), rows - t.rows + 1);
+        const int tw = (int)std::min<long long>(std::max<long long>(ow, side), cols - t.cols + 1);
+        for (int u0 = set_off[k]; u0 < set_off[k + 1]; u0 += kTrackNV)
+            for (int ty = 0; ty < th; ty += kWinTile)
+                for (int tx = 0; tx < tw; tx += kWinTile)
+                    tiles.push_back(TrackSetTile{u0, std::min(kTrackNV, set_off[k + 1] - u0), ty, tx});
+    }
+    const size_t n_units = tu.size();
+    HIPC(hipSetDevice(c->device));
+    MTMC(prepare_window_templates(c, tl));
+    MTMC(prepare_box_td(c, tl));
+
+    c->timing = mtm_timing{};
+    c->maps_valid = false;
+    c->last_hits.clear();
+    const bool mode_min = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_SQDIFF_NORMED;
+    const size_t n_out = (size_t)n_frames * n_tracks;
+    MTMC(c->trk_units.ensure(sizeof(TrackUnit) * n_units));
+    MTMC(c->trk_tiles.ensure(sizeof(TrackSetTile) * tiles.size()));
+    MTMC(c->trk_keys.ensure(sizeof(unsigned long long) * n_units));
+    MTMC(c->trk_sets.ensure(sizeof(int) * ((size_t)n_tracks + 1)));
+    MTMC(c->trk_out.ensure(sizeof(mtm_hit) * n_out));
+    if (nbhd) MTMC(c->trk_nbhd.ensure(sizeof(float) * 9 * n_out));
+    // (reacq) the lost state per track, all zero between frames: [wunits | list | n_lost | flags]
+    TrackLostState lost{nullptr, nullptr, nullptr, nullptr};
+    if (reacq) MTMC(track_lost_state(c, n_tracks, lost));
+    const uint8_t* tpx = c->win_tpx.as<uint8_t>();
+    const long long* toff = c->win_toff.as<long long>();
+    const TemplDev* td = c->box_td.as<TemplDev>();
+    TrackUnit* d_units = c->trk_units.as<TrackUnit>();
+    const int* d_sets = c->trk_sets.as<int>();
+    unsigned long long* d_keys = c->trk_keys.as<unsigned long long>();
+    HIPC(hipEventRecord(c->ev[0], c->stream));
+    HIPC(hipMemcpyAsync(c->trk_units.p, tu.data(), sizeof(TrackUnit) * n_units, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->trk_tiles.p, tiles.data(), sizeof(TrackSetTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->trk_sets.p, set_off, sizeof(int) * ((size_t)n_tracks + 1), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemsetAsync(c->trk_keys.p, 0, sizeof(unsigned long long) * n_units, c->stream));
+
+    const int per_chunk = track_chunk_frames(c, rows, cols, chans);
+    const int ublocks = (n_tracks + 255) / 256;
+    for (int f0 = 0; f0 < n_frames; f0 += per_chunk) {
+        const int nb = std::min(per_chunk, n_frames - f0);
+        adopt_image(c, nb * rows, cols, chans, dtype);
+        MTMC(upload_image_stack(c, c->slot[c->cur], frames + f0, nb, row_stride_bytes, rows, cols, chans, dtype, c->stream));
+        const ImageDev img = image_dev(c);
+        const uint8_t* lo_b = c->slot[c->cur].u8b.as<uint8_t>() + img.u8_plane;     // uint16: [high ^ 0x80][low ^ 0x80]
+        for (int fl = 0; fl < nb; ++fl) {
+            const size_t r0 = (size_t)(f0 + fl) * n_tracks;
+#define MTM_TRACK_LAUNCH(CH, U16)                                                                                            \
+    hipLaunchKernelGGL((track_score_sets_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, lo_b, tpx, toff, td,       \
+                       d_units, c->trk_tiles.as<TrackSetTile>() + t0, fl * rows, c->method, mode_min ? 1 : 0, d_keys)
+            for (size_t t0 = 0; t0 < tiles.size(); t0 += kTrackLaunchTiles) {
+                const unsigned nt = (unsigned)std::min(kTrackLaunchTiles, tiles.size() - t0);
+                if (dtype == MTM_U16) MTM_TRACK_LAUNCH(1, true);
+                else if (chans == 1) MTM_TRACK_LAUNCH(1, false);
+                else MTM_TRACK_LAUNCH(3, false);
+                HIPC(hipGetLastError());
+            }
+#undef MTM_TRACK_LAUNCH
+#define MTM_TRACK_UPDATE(REACQ)                                                                                               \
+    hipLaunchKernelGGL(track_update_sets_kernel<REACQ>, dim3(ublocks), dim3(256), 0, c->stream, d_units, d_sets, td, d_keys,  \
+                       n_tracks, mode_min ? 1 : 0, margin, use_min ? 1 : 0, min_score, rows, cols,                           \
+                       c->trk_out.as<mtm_hit>() + r0, lost)
+            if (reacq) MTM_TRACK_UPDATE(true);
+            else MTM_TRACK_UPDATE(false);
+#undef MTM_TRACK_UPDATE
+            HIPC(hipGetLastError());
+#define MTM_TRACK_REACQUIRE(CH, U16)                                                                                         \
+    hipLaunchKernelGGL((track_reacquire_sets_kernel<CH, U16>), dim3(kTrackReacquireGrid), dim3(256), 0, c->stream, img, lo_b, \
+                       tpx, toff, td, d_units, d_sets, lost, groups_max, tiles_max, fl * rows, c->method, mode_min ? 1 : 0,   \
+                       d_keys)
+            if (reacq) {
+                if (dtype == MTM_U16) MTM_TRACK_REACQUIRE(1, true);
+                else if (chans == 1) MTM_TRACK_REACQUIRE(1, false);
+                else MTM_TRACK_REACQUIRE(3, false);
+                HIPC(hipGetLastError());
+                hipLaunchKernelGGL(track_reupdate_sets_kernel, dim3(ublocks), dim3(256), 0, c->stream, d_units, d_sets, td,
+                                   d_keys, n_tracks, mode_min ? 1 : 0, margin, min_score, rows, cols,
+                                   c->trk_out.as<mtm_hit>() + r0, lost);
+                HIPC(hipGetLastError());
+            }
+#undef MTM_TRACK_REACQUIRE
+            // the frame's neighbourhoods: track_nbhd_kernel as it is - it reads the winner's template from the record
+            if (nbhd) MTMC(track_launch_nbhd(c, img, lo_b, tpx, toff, td, r0, n_tracks, fl * rows, rows, chans, dtype));
+        }
+    }
+    HIPC(hipEventRecord(c->ev[1], c->stream));
+    HIPC(hipMemcpyAsync(out, c->trk_out.p, sizeof(mtm_hit) * n_out, hipMemcpyDeviceToHost, c->stream));
+    if (nbhd) HIPC(hipMemcpyAsync(nbhd, c->trk_nbhd.p, sizeof(float) * 9 * n_out, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
+    c->timing.n_hits = (int64_t)n_out;
+    // the stack is none of the caller's frames: no current image, no published maps
+    c->have_image = false;
+    return MTM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -661,6 +1065,14 @@ int mtm_track_boxes_reacquire(mtm_ctx* c, const void* const* frames, int n_frame
     }
     return track_boxes(c, "mtm_track_boxes_reacquire", frames, n_frames, rows, cols, chans, dtype, row_stride_bytes, start,
                        n_tracks, margin, use_min, min_score, out, nbhd, false, blend_a, templ_out, stats_out, true);
+}
+
+int mtm_track_boxes_sets(mtm_ctx* c, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                         int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, const int32_t* set_off,
+                         const int32_t* set_idx, int margin, int use_min, double min_score, int reacquire, mtm_hit* out,
+                         float* nbhd) {
+    return track_boxes_sets(c, frames, n_frames, rows, cols, chans, dtype, row_stride_bytes, start, n_tracks, set_off, set_idx,
+                            margin, use_min, min_score, reacquire != 0, out, nbhd);
 }
 
 }  // extern "C"

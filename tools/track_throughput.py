@@ -38,12 +38,23 @@ unmodified T1 and T2 lose tracks too: their pasted copies overlap at times):
   idle_reacquire, idle_track - reacquire=True and reacquire=False: the cost of the option when it has nothing to do
 The result of track_reacquire is checked equal to loop_reacquire's (labels, boxes, float32 score bits).
 
+--sets V (1 <= V <= 4) times tracks that carry a set of V same-shape variants - the template, its two flips and its 180
+degree rotation - instead, one JSON line per workload, on a variant of the workload in which each object shows variant
+(frame + track) % V of its set:
+  track_sets     - MTM.trackTemplates(...) with tracks ((x, y, w, h), [j0 .. jV-1]): one unit per track and variant, the
+                   variants of a set scored by one work-group per tile
+  track_separate - the same variants as V separate single-template tracks each (V times the tracks; every one follows its
+                   own maximum, so this is the cost of the search alone, not the set's result)
+  loop_sets      - the loop the set call replaces: per frame one findMatchesInBoxes call over (box, set) regions, the best
+                   hit of each region on the host, next_box
+The result of track_sets is checked equal to loop_sets' (labels, boxes, float32 score bits).
+
 Data: each frame is one of 8 synth.smooth_u8 backgrounds (uint16: 257 x that plus noise in the low byte) with each
 track's template - a crop of another smooth_u8 image - pasted at a position that moves up to margin / 2 pixels per frame
 in each direction.  Each method is warmed up first; the four are interleaved within a repetition; medians over the
 repetitions.
 
-Usage: tools/track_throughput.py [--reps 3] [--warmup 1] [--only T1|T2|T3] [--refine | --update RATE | --reacquire]
+Usage: tools/track_throughput.py [--reps 3] [--warmup 1] [--only T1|T2|T3] [--refine | --update RATE | --reacquire | --sets V]
 """
 import argparse
 import json
@@ -293,6 +304,67 @@ def run_reacquire(MTM, spec, reps, warmup, min_score=0.9):
     }
 
 
+def run_sets(MTM, spec, reps, warmup, n_var):
+    from MTM.tracking import next_box
+    name, n_frames, hw, chans, dtype, n_tracks, side, margin = spec
+    base, frames, tracks, truth = workload(spec)
+    templs, sets = [], []
+    for k, (label, t) in enumerate(base):
+        variants = [t, t[:, ::-1], t[::-1], t[::-1, ::-1]][:n_var]
+        sets.append(list(range(len(templs), len(templs) + n_var)))
+        templs += [("%s.%d" % (label, v), np.ascontiguousarray(a)) for v, a in enumerate(variants)]
+    shown = np.empty((n_frames, n_tracks), np.int64)
+    for f in range(n_frames):               # (in track order, as workload pasted the originals)
+        for k in range(n_tracks):
+            x, y = truth[f, k]
+            shown[f, k] = sets[k][(f + k) % n_var]
+            frames[f, y:y + side, x:x + side] = templs[shown[f, k]][1]
+    frame_list = list(frames)
+    method = MTM.TM_CCOEFF_NORMED
+    set_tracks = [(b, sets[k]) for k, (b, _) in enumerate(tracks)]
+    separate = [(b, j) for k, (b, _) in enumerate(tracks) for j in sets[k]]
+
+    def loop():
+        out, box = [], [b for b, _ in set_tracks]
+        for f in frame_list:
+            r = MTM.findMatchesInBoxes(templs, f, [(b, js) for b, (_, js) in zip(box, set_tracks)], method, N_object=1)
+            row = [[max(hits, key=lambda h: h[2])] for hits in r]
+            out.append(row)
+            box = [next_box(b, ri[0], margin, f.shape, method) for b, ri in zip(box, row)]
+        return out
+
+    methods = {
+        "track_sets": lambda: MTM.trackTemplates(templs, frames, set_tracks, margin, method),
+        "track_separate": lambda: MTM.trackTemplates(templs, frames, separate, margin, method),
+        "loop_sets": loop,
+    }
+    results, ms = _time(methods, reps, max(1, warmup))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    got = results["track_sets"]
+    pos = np.array([[h[0][1][:2] for h in fr] for fr in got])
+    labels = np.array([[h[0][0] for h in fr] for fr in got])
+    want = np.array([[templs[j][0] for j in row] for row in shown])
+    methods["track_sets"]()                         # (the default context's timing: this call's, upload to last launch)
+    t_sets = float(MTM._lib.default_context().timing()["total_ms"])
+    methods["track_separate"]()
+    t_sep = float(MTM._lib.default_context().timing()["total_ms"])
+    return {
+        "workload": name, "mode": "sets", "variants": n_var, "frames": n_frames,
+        "frame": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype), "tracks": n_tracks, "template": "%dx%d" % (side, side),
+        "margin": margin,
+        "ms_per_frame": {k: round(v / n_frames, 4) for k, v in med.items()},
+        "ms_per_frame_min": {k: round(min(v) / n_frames, 4) for k, v in ms.items()},
+        "ms_per_frame_max": {k: round(max(v) / n_frames, 4) for k, v in ms.items()},
+        "speedup_vs_loop_sets": round(med["loop_sets"] / med["track_sets"], 2),
+        "speedup_vs_track_separate": round(med["track_separate"] / med["track_sets"], 2),
+        "track_sets_device_ms": round(t_sets, 3), "track_separate_device_ms": round(t_sep, 3),
+        "equal_to_loop_sets": _key(got) == _key(results["loop_sets"]),
+        "recovered": round(float(np.mean(np.all(pos == truth, axis=2))), 4),
+        "variant_named": round(float(np.mean(labels == want)), 4),
+        "reps": reps,
+    }
+
+
 def run(MTM, spec, reps, warmup):
     from MTM.tracking import next_box
     name, n_frames, hw, chans, dtype, n_tracks, side, margin = spec
@@ -348,16 +420,22 @@ def main():
                     help="time adaptive templates (update=RATE) against the plain call and the loop they replace")
     ap.add_argument("--reacquire", action="store_true",
                     help="time the re-acquisition of lost tracks (reacquire=True) against the plain call and the loop")
+    ap.add_argument("--sets", type=int, default=None, metavar="V",
+                    help="time tracks that carry V same-shape variants (1..4) against separate tracks and the loop")
     args = ap.parse_args()
-    if args.refine + (args.update is not None) + args.reacquire > 1:
-        ap.error("--refine, --update and --reacquire are separate measurements")
+    if args.refine + (args.update is not None) + args.reacquire + (args.sets is not None) > 1:
+        ap.error("--refine, --update, --reacquire and --sets are separate measurements")
+    if args.sets is not None and not 1 <= args.sets <= 4:
+        ap.error("--sets takes 1 to 4 variants (the template, its flips and its 180 degree rotation)")
     import build as mtm_build
     mtm_build.build()
     import MTM
     for spec in WORKLOADS:
         if args.only and spec[0] != args.only:
             continue
-        if args.reacquire:
+        if args.sets is not None:
+            rec = run_sets(MTM, spec, args.reps, args.warmup, args.sets)
+        elif args.reacquire:
             rec = run_reacquire(MTM, spec, args.reps, args.warmup)
         elif args.update is not None:
             rec = run_update(MTM, spec, args.reps, args.warmup, args.update)

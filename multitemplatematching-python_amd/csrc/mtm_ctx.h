@@ -339,19 +339,21 @@ struct mtm_ctx {
     uint64_t box_gen = 0;
     DevBuf box_td, box_units, box_tiles;
     int64_t boxes_max_floats = 1ll << 26;
-    // mtm_track_boxes (mtm_track.hip): the per-call track table (rewritten on the device every frame), tile table, extremum
-    // keys and records; mtm_track_boxes_nbhd: the records' 3 x 3 neighbourhoods (nine floats per record).
+    // mtm_track_boxes* (mtm_track.hip, stage_tables): the per-call unit table (TrackPlan::units, rewritten on the device
+    // every frame), tile table (TrackPlan::tiles), one extremum key per unit and the records; the records' 3 x 3
+    // neighbourhoods where a call returns them (nine floats per record).
     DevBuf trk_units, trk_tiles, trk_keys, trk_out, trk_nbhd;
-    // mtm_track_boxes_adapt: the call's own templates, indexed by the track - byte planes (track k's at trk_toff[k] in
-    // trk_tpx, prepare_window_templates' layout), epilogue constants (trk_td) - and each track's pass flag of the frame.
-    // Copies of win_tpx / box_td made at the start of the call and rewritten by track_adopt_kernel: the template set's
-    // own tables and their generations are never touched.
+    // mtm_track_boxes_adapt (stage_track_templates): the call's own templates, indexed by the track - byte planes (track
+    // k's at trk_toff[k] in trk_tpx, prepare_window_templates' layout), epilogue constants (trk_td) - and each track's pass
+    // flag of the frame.  Copies of win_tpx / box_td made at the start of the call and rewritten by track_adopt_kernel:
+    // the template set's own tables and their generations are never touched.
     DevBuf trk_tpx, trk_toff, trk_td, trk_pass;
     // mtm_track_boxes_reacquire: the state of a frame's whole-frame search - per track its whole-frame unit and its lost
     // flag, the compacted list of the lost tracks and their count (TrackLostState, mtm_track.hip) - written by
     // track_update_kernel, read by track_reacquire_kernel, cleared by track_reupdate_kernel.
     DevBuf trk_lost;
-    // mtm_track_boxes_sets: the first unit of every track's set in trk_units (n_tracks + 1 offsets).
+    // mtm_track_boxes_sets: the first unit of every track's set in trk_units (TrackPlan::set_off, n_tracks + 1 offsets);
+    // the other entry points hand the update kernels no offsets (track k is unit k).
     DevBuf trk_sets;
     // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
     // template set sub_gen) and the per-call point table and scores.
@@ -489,13 +491,7 @@ int upload_image(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* src, int64_t sr
 int upload_image_stack(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* const* px, int n, int64_t src_stride, int rows,
                        int cols, int chans, int dtype, hipStream_t stream);
 void adopt_image(mtm_ctx* c, int rows, int cols, int chans, int dtype);
-// One template of the last mtm_set_templates as its bytes in mtm_ctx::templ_blob (interleaved, tightly packed rows of
-// `dtype` pixels); parse_templ_blob (mtm_placement.hip) lists them - unmasked uint8 templates, with `u16_ok` also unmasked
-// single-channel uint16 ones - for mtm_find_matches_pyramid and mtm_find_matches_boxes.
-struct BlobTempl {
-    int rows, cols, chans, dtype;
-    const uint8_t* px;
-};
+// (BlobTempl: mtm_internal.h)
 int parse_templ_blob(const std::vector<uint8_t>& b, std::vector<BlobTempl>& out, const char* who, bool u16_ok);
 int prepare_window_templates(mtm_ctx* c, const std::vector<BlobTempl>& tl);
 // The templates' epilogue constants (TemplDev, statistics of the last mtm_set_templates and the sizes of `tl`) in

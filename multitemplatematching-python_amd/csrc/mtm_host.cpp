@@ -569,6 +569,70 @@ static void nms_greedy(const mtm_hit* hits, const std::vector<int32_t>& cand, fl
     }
 }
 
+// ---- the host plan of a tracking call (mtm_track.hip)
+int plan_tracks(const std::vector<BlobTempl>& tl, int rows, int cols, int chans, int dtype, const mtm_box_unit* start,
+                int n_tracks, int margin, bool reacq, const int32_t* set_off, const int32_t* set_idx, const char* who,
+                TrackPlan& P) {
+    P = TrackPlan{};
+    const bool sets = set_off != nullptr;
+    if (sets && set_off[0] != 0) {
+        set_error(std::string(who) + ": set_off[0] must be 0");
+        return MTM_E_INVALID;
+    }
+    P.set_off.assign(1, 0);
+    for (int k = 0; k < n_tracks; ++k) {
+        const mtm_box_unit& s = start[k];
+        auto fail = [&](const char* what) {
+            set_error(std::string(who) + ": track " + std::to_string(k) + what);
+            return MTM_E_INVALID;
+        };
+        const auto listed = [&](int j) { return j >= 0 && j < (int)tl.size(); };
+        const long long n_set = sets ? (long long)set_off[k + 1] - set_off[k] : 1;
+        if (n_set < 1) return fail(n_set == 0 ? ": empty set" : ": set_off is not ascending");
+        const int32_t* js = sets ? set_idx + set_off[k] : &s.templ_idx;
+        if (s.templ_idx != js[0]) return fail(": start's template is not the first of its set");
+        // (a plain track's index is checked ahead of its box, a set's behind it: the order each entry point reports in)
+        if (!sets && !listed(s.templ_idx)) return fail(": template index out of range");
+        if (s.y0 < 0 || s.x0 < 0 || s.rows < 1 || s.cols < 1 || s.rows > rows - s.y0 || s.cols > cols - s.x0)
+            return fail(": box outside the frame");
+        for (long long i = 0; i < n_set; ++i) {
+            if (!listed(js[i])) return fail(": template index out of range");
+            const BlobTempl& v = tl[(size_t)js[i]];
+            if (v.dtype != dtype || v.chans != chans)
+                return fail(": template and frames differ in pixel type or channel count");
+            if (v.rows != tl[(size_t)js[0]].rows || v.cols != tl[(size_t)js[0]].cols)
+                return fail(": the templates of a set must be of one shape");
+        }
+        const BlobTempl& t = tl[(size_t)s.templ_idx];
+        if (t.rows > s.rows || t.cols > s.cols) return fail(": template larger than the box");
+        if (dtype == MTM_U16 && (long long)t.rows * t.cols > (1ll << 21))
+            return fail(": uint16 template of more than 2^21 pixels");
+        const long long wh = rows - t.rows + 1, ww = cols - t.cols + 1;         // the whole-frame map
+        if (reacq) {
+            if (wh * ww >= (1ll << 32)) return fail(": whole-frame map of 2^32 outputs or more");
+            P.tiles_max = std::max(P.tiles_max, (unsigned long long)((wh + kTrackTile - 1) / kTrackTile) *
+                                                    (unsigned long long)((ww + kTrackTile - 1) / kTrackTile));
+            P.groups_max = std::max(P.groups_max, (unsigned long long)((n_set + kTrackNV - 1) / kTrackNV));
+        }
+        const int u0 = (int)P.units.size(), u1 = u0 + (int)n_set;
+        const int oh = s.rows - t.rows + 1, ow = s.cols - t.cols + 1;
+        for (long long i = 0; i < n_set; ++i) P.units.push_back(TrackUnit{js[i], s.y0, s.x0, oh, ow});
+        P.set_off.push_back(u1);
+        P.templ_bytes.push_back((size_t)t.rows * t.cols * (t.dtype == MTM_U16 ? 2 : t.chans));
+        // the tiles cover every map the track can have during the call: the frame-0 map, or one of at most 2 margin + 1
+        // outputs per side (a box is the hit widened by the margin), neither larger than the whole-frame map
+        const long long side = 2ll * margin + 1;
+        const int th = (int)std::min<long long>(std::max<long long>(oh, side), wh);
+        const int tw = (int)std::min<long long>(std::max<long long>(ow, side), ww);
+        for (int g0 = u0; g0 < u1; g0 += kTrackNV)
+            for (int ty = 0; ty < th; ty += kTrackTile)
+                for (int tx = 0; tx < tw; tx += kTrackTile)
+                    P.tiles.push_back(TrackTile{g0, std::min(kTrackNV, u1 - g0), ty, tx});
+    }
+    P.n_units = P.units.size();
+    return MTM_OK;
+}
+
 }  // namespace mtm
 
 extern "C" {

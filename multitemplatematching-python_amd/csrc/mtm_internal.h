@@ -103,6 +103,46 @@ struct PassOutcome {
 LadderStep ladder_next(const mtmi::CallRoute& R, const PassOutcome& o, int attempt);
 void ladder_apply(mtmi::CallRoute& R, LadderStep s);
 
+// ---- the host plan of a tracking call (mtm_track_boxes*, mtm_track.hip)
+
+// One template of the last mtm_set_templates as its bytes in mtm_ctx::templ_blob (interleaved, tightly packed rows of
+// `dtype` pixels); parse_templ_blob (mtm_placement.hip) lists them - unmasked uint8 templates, with `u16_ok` also unmasked
+// single-channel uint16 ones - for mtm_find_matches_pyramid, mtm_find_matches_boxes and the tracking calls.
+struct BlobTempl {
+    int rows, cols, chans, dtype;
+    const uint8_t* px;
+};
+constexpr int kTrackTile = 16;      // a tile of 16 x 16 outputs: the window kernels' kWinTile (mtm_track.hip asserts it)
+constexpr int kTrackNV = 4;         // templates of a set that one work-group scores together (a group)
+// A unit as the kernels see it: its template, the frame pixel of its map's output (0, 0) and the map's size.  Frame
+// coordinates: the score kernels add the frame's row offset in the chunk's stack.
+struct TrackUnit {
+    int t;
+    int y0, x0;
+    int oh, ow;
+};
+// One 16 x 16 tile of outputs of the units u0 .. u0 + nv - 1 (one group of one track), first output (ty0, tx0) of their map.
+struct TrackTile {
+    int u0, nv, ty0, tx0;
+};
+struct TrackPlan {
+    std::vector<TrackUnit> units;           // one per (track, template of its set), track after track in set order
+    std::vector<int> set_off;               // track k's units: set_off[k] .. set_off[k + 1] - 1
+    std::vector<TrackTile> tiles;           // per track and group, row-major over the largest map the track can have
+    unsigned long long tiles_max = 0;       // (reacq) the tiles of the call's largest whole-frame map
+    unsigned long long groups_max = 0;      // (reacq) the groups of the call's largest set
+    size_t n_units = 0;
+    std::vector<size_t> templ_bytes;        // the bytes of each track's template planes (the start template's)
+};
+// The tracks of a call checked and laid out: templates `tl`, frames of rows x cols x chans `dtype` pixels, frame-0 boxes
+// and templates start[0 .. n_tracks - 1]; track k's set is set_idx[set_off[k] .. set_off[k + 1] - 1], or - set_off ==
+// nullptr - its start template alone.  A track's tiles cover every map it can have during the call: the frame-0 map, or
+// one of 2 margin + 1 outputs per side, clipped to the whole-frame map.  MTM_OK, or the code and message (set_error,
+// prefixed `who`) of the first track that is not valid.
+int plan_tracks(const std::vector<BlobTempl>& tl, int rows, int cols, int chans, int dtype, const mtm_box_unit* start,
+                int n_tracks, int margin, bool reacq, const int32_t* set_off, const int32_t* set_idx, const char* who,
+                TrackPlan& plan);
+
 // float32-faithful restatement of cv2.dnn.NMSBoxes as called by MTM.NMS
 void nms_boxes(const mtm_hit* hits, int64_t n, const float* scores, float score_threshold,
                float nms_threshold, std::vector<int32_t>& keep);

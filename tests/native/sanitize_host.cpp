@@ -1,5 +1,6 @@
 // Sanitizer driver for the host-only C++ of libmtm_hip.so (no GPU, no HIP): mtm_host.cpp (NMS, 1-D peaks, hit
-// sorting, extremum-key decoding, result hand-over, template statistics) and mtm_group.cpp (worker threads, generation counter, LPT shards, host merge) are
+// sorting, extremum-key decoding, result hand-over, template statistics, the plan of a tracking call) and mtm_group.cpp
+// (worker threads, generation counter, LPT shards, host merge) are
 // compiled as they are, with -fsanitize=address,undefined and again with -fsanitize=thread; the per-device context
 // API the group drives (mtm_ctx_create, mtm_set_templates, mtm_find_matches_image, ...) is replaced by a fake that
 // returns deterministic hits - so the group's threading protocol runs thousands of jobs under the sanitizers.
@@ -701,10 +702,186 @@ static void test_ladder() {
     CHECK(r.f32_exact && !r.refine && !r.fused && !r.hits_only && !r.raw_rig && !r.pp_mode && !r.ext);
 }
 
+// ---- the host plan of a tracking call (plan_tracks, mtm_host.cpp): the tile tables against brute force, every error path
+static int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// What plan_tracks must have laid out for valid tracks: units in set order, groups that partition each set, per group a
+// row-major grid of distinct 16-aligned tiles that holds the frame-0 map and the next_box map of every possible hit.
+static void check_plan(const TrackPlan& P, const std::vector<BlobTempl>& tl, int rows, int cols,
+                       const std::vector<mtm_box_unit>& start, const std::vector<int32_t>& off, const std::vector<int32_t>& idx,
+                       int margin, bool reacq) {
+    const int n = (int)start.size();
+    CHECK(P.n_units == idx.size() && P.units.size() == idx.size() && P.set_off.size() == off.size());
+    CHECK(std::equal(off.begin(), off.end(), P.set_off.begin()));
+    CHECK((int)P.templ_bytes.size() == n);
+    size_t at = 0;              // the next tile of the table
+    unsigned long long tiles_max = 0, groups_max = 0;
+    for (int k = 0; k < n; ++k) {
+        const mtm_box_unit& s = start[(size_t)k];
+        const BlobTempl& t = tl[(size_t)s.templ_idx];
+        const int h = t.rows, w = t.cols, oh0 = s.rows - h + 1, ow0 = s.cols - w + 1;
+        CHECK(P.templ_bytes[(size_t)k] == (size_t)h * w * (t.dtype == MTM_U16 ? 2 : t.chans));
+        for (int u = off[(size_t)k]; u < off[(size_t)k + 1]; ++u) {
+            const TrackUnit& U = P.units[(size_t)u];
+            CHECK(U.t == idx[(size_t)u] && U.y0 == s.y0 && U.x0 == s.x0 && U.oh == oh0 && U.ow == ow0);
+        }
+        // the largest map of the call, by brute force: frame 0's, and MTM.tracking.next_box around every hit of the frame
+        int need_h = oh0, need_w = ow0;
+        for (int y = 0; y <= rows - h; ++y)
+            need_h = std::max(need_h, std::min(rows, y + h + margin) - std::max(0, y - margin) - h + 1);
+        for (int x = 0; x <= cols - w; ++x)
+            need_w = std::max(need_w, std::min(cols, x + w + margin) - std::max(0, x - margin) - w + 1);
+        const int ty_n = cdiv(need_h, 16), tx_n = cdiv(need_w, 16);
+        int u_next = off[(size_t)k];
+        while (u_next < off[(size_t)k + 1]) {           // one group: its tiles are a ty_n x tx_n grid, row-major
+            CHECK(at < P.tiles.size());
+            const int u0 = P.tiles[at].u0, nv = P.tiles[at].nv;
+            CHECK(u0 == u_next && nv >= 1 && nv <= kTrackNV && nv == std::min(kTrackNV, off[(size_t)k + 1] - u0));
+            for (int ty = 0; ty < ty_n; ++ty)
+                for (int tx = 0; tx < tx_n; ++tx, ++at) {
+                    CHECK(at < P.tiles.size());
+                    const TrackTile& K = P.tiles[at];
+                    CHECK(K.u0 == u0 && K.nv == nv && K.ty0 == 16 * ty && K.tx0 == 16 * tx);
+                }
+            u_next += nv;
+        }
+        CHECK(u_next == off[(size_t)k + 1]);
+        tiles_max = std::max(tiles_max,
+                             (unsigned long long)cdiv(rows - h + 1, 16) * (unsigned long long)cdiv(cols - w + 1, 16));
+        groups_max = std::max(groups_max, (unsigned long long)cdiv(off[(size_t)k + 1] - off[(size_t)k], kTrackNV));
+    }
+    CHECK(at == P.tiles.size());
+    CHECK(P.tiles_max == (reacq ? tiles_max : 0ull) && P.groups_max == (reacq ? groups_max : 0ull));
+}
+
+static void test_track_plan() {
+    const int rows = 40, cols = 50;
+    const int shapes[4][2] = {{1, 1}, {7, 9}, {17, 33}, {40, 50}};
+    const int set_sizes[5] = {1, 2, 4, 5, 9};
+    const int kinds[3][2] = {{MTM_U8, 1}, {MTM_U8, 3}, {MTM_U16, 1}};
+    for (const auto& kind : kinds) {
+        // nine templates of every shape in the kind, then one of another kind
+        std::vector<BlobTempl> tl;
+        for (const auto& sh : shapes)
+            for (int v = 0; v < 9; ++v) tl.push_back(BlobTempl{sh[0], sh[1], kind[1], kind[0], nullptr});
+        tl.push_back(BlobTempl{7, 9, kind[1] == 3 ? 1 : 3, MTM_U8, nullptr});
+        for (int margin : {0, 1, 3, 8, 60})
+            for (int reacq = 0; reacq < 2; ++reacq) {
+                std::vector<mtm_box_unit> start;
+                std::vector<int32_t> off(1, 0), idx;
+                int ns = 0;
+                for (int si = 0; si < 4; ++si) {
+                    const int h = shapes[si][0], w = shapes[si][1];
+                    const int bh = std::min(rows, h + 5), bw = std::min(cols, w + 6);
+                    // the four corners, a box equal to the template, the whole frame
+                    const int boxes[6][4] = {{0, 0, bh, bw}, {0, cols - bw, bh, bw}, {rows - bh, 0, bh, bw},
+                                             {rows - bh, cols - bw, bh, bw}, {(rows - h) / 2, (cols - w) / 2, h, w},
+                                             {0, 0, rows, cols}};
+                    for (const auto& b : boxes) {
+                        const int n_set = set_sizes[ns++ % 5];
+                        for (int v = 0; v < n_set; ++v) idx.push_back(9 * si + (v * 4 + ns) % 9);   // (with repeats)
+                        start.push_back(mtm_box_unit{idx[(size_t)off.back()], b[0], b[1], b[2], b[3]});
+                        off.push_back((int32_t)idx.size());
+                    }
+                }
+                const int n = (int)start.size();
+                TrackPlan P;
+                CHECK(plan_tracks(tl, rows, cols, kind[1], kind[0], start.data(), n, margin, reacq != 0, off.data(), idx.data(),
+                                  "mtm_track_boxes_sets", P) == MTM_OK);
+                check_plan(P, tl, rows, cols, start, off, idx, margin, reacq != 0);
+                // without sets: what singleton sets give
+                std::vector<int32_t> off1((size_t)n + 1), idx1((size_t)n);
+                for (int k = 0; k <= n; ++k) off1[(size_t)k] = k;
+                for (int k = 0; k < n; ++k) idx1[(size_t)k] = start[(size_t)k].templ_idx;
+                TrackPlan A, B;
+                CHECK(plan_tracks(tl, rows, cols, kind[1], kind[0], start.data(), n, margin, reacq != 0, nullptr, nullptr,
+                                  "mtm_track_boxes", A) == MTM_OK);
+                CHECK(plan_tracks(tl, rows, cols, kind[1], kind[0], start.data(), n, margin, reacq != 0, off1.data(),
+                                  idx1.data(), "mtm_track_boxes_sets", B) == MTM_OK);
+                check_plan(A, tl, rows, cols, start, off1, idx1, margin, reacq != 0);
+                CHECK(A.units.size() == B.units.size() && A.tiles.size() == B.tiles.size() && A.set_off == B.set_off &&
+                      A.templ_bytes == B.templ_bytes && A.tiles_max == B.tiles_max && A.groups_max == B.groups_max);
+                CHECK(std::memcmp(A.units.data(), B.units.data(), sizeof(TrackUnit) * A.units.size()) == 0);
+                CHECK(std::memcmp(A.tiles.data(), B.tiles.data(), sizeof(TrackTile) * A.tiles.size()) == 0);
+            }
+    }
+    // ---- every error path: the code and the message of the entry points
+    std::vector<BlobTempl> tl = {{7, 9, 1, MTM_U8, nullptr},  {7, 9, 1, MTM_U8, nullptr},  {5, 9, 1, MTM_U8, nullptr},
+                                 {7, 9, 3, MTM_U8, nullptr},  {7, 9, 1, MTM_U16, nullptr}, {2048, 1025, 1, MTM_U16, nullptr},
+                                 {2048, 1024, 1, MTM_U16, nullptr}, {1, 1, 1, MTM_U8, nullptr}};
+    struct Bad {
+        int rows, cols, dtype;
+        std::vector<mtm_box_unit> start;
+        std::vector<int32_t> off, idx;      // (off empty: without sets)
+        bool reacq;
+        std::string msg;
+    };
+    const mtm_box_unit ok = {0, 2, 3, 12, 14};
+    const std::vector<Bad> bad = {
+        {40, 50, MTM_U8, {ok, {8, 2, 3, 12, 14}}, {}, {}, false, "mtm_track_boxes: track 1: template index out of range"},
+        {40, 50, MTM_U8, {ok, {-1, 2, 3, 12, 14}}, {}, {}, false, "mtm_track_boxes: track 1: template index out of range"},
+        {40, 50, MTM_U8, {ok, ok}, {0, 1, 3}, {0, 0, 8}, false, "mtm_track_boxes_sets: track 1: template index out of range"},
+        {40, 50, MTM_U8, {{0, 30, 3, 12, 14}}, {}, {}, false, "mtm_track_boxes: track 0: box outside the frame"},
+        {40, 50, MTM_U8, {{0, 2, 40, 12, 14}}, {0, 1}, {0}, false, "mtm_track_boxes_sets: track 0: box outside the frame"},
+        {40, 50, MTM_U8, {{0, -1, 3, 12, 14}}, {}, {}, false, "mtm_track_boxes: track 0: box outside the frame"},
+        {40, 50, MTM_U8, {{0, 2, 3, 0, 14}}, {}, {}, false, "mtm_track_boxes: track 0: box outside the frame"},
+        // (both an index out of range and a box outside: a plain track reports the index, a set the box)
+        {40, 50, MTM_U8, {{8, 30, 3, 12, 14}}, {}, {}, false, "mtm_track_boxes: track 0: template index out of range"},
+        {40, 50, MTM_U8, {{8, 30, 3, 12, 14}}, {0, 1}, {8}, false, "mtm_track_boxes_sets: track 0: box outside the frame"},
+        {40, 50, MTM_U8, {{3, 2, 3, 12, 14}}, {}, {}, false,
+         "mtm_track_boxes_nbhd: track 0: template and frames differ in pixel type or channel count"},
+        {40, 50, MTM_U8, {{4, 2, 3, 12, 14}}, {}, {}, false,
+         "mtm_track_boxes_nbhd: track 0: template and frames differ in pixel type or channel count"},
+        {40, 50, MTM_U8, {ok}, {0, 2}, {0, 3}, false,
+         "mtm_track_boxes_sets: track 0: template and frames differ in pixel type or channel count"},
+        {40, 50, MTM_U8, {{0, 2, 3, 6, 14}}, {}, {}, false, "mtm_track_boxes_adapt: track 0: template larger than the box"},
+        {40, 50, MTM_U8, {{0, 2, 3, 12, 8}}, {0, 2}, {0, 1}, false,
+         "mtm_track_boxes_sets: track 0: template larger than the box"},
+        {2048, 1025, MTM_U16, {{5, 0, 0, 2048, 1025}}, {}, {}, false,
+         "mtm_track_boxes: track 0: uint16 template of more than 2^21 pixels"},
+        {2048, 1025, MTM_U16, {{5, 0, 0, 2048, 1025}}, {0, 1}, {5}, false,
+         "mtm_track_boxes_sets: track 0: uint16 template of more than 2^21 pixels"},
+        {65536, 65537, MTM_U8, {{7, 0, 0, 4, 4}}, {}, {}, true,
+         "mtm_track_boxes_reacquire: track 0: whole-frame map of 2^32 outputs or more"},
+        {65536, 65537, MTM_U8, {{7, 0, 0, 4, 4}}, {0, 1}, {7}, true,
+         "mtm_track_boxes_sets: track 0: whole-frame map of 2^32 outputs or more"},
+        {40, 50, MTM_U8, {ok}, {1, 2}, {0, 0}, false, "mtm_track_boxes_sets: set_off[0] must be 0"},
+        {40, 50, MTM_U8, {ok, ok}, {0, 1, 1}, {0}, false, "mtm_track_boxes_sets: track 1: empty set"},
+        {40, 50, MTM_U8, {ok, ok}, {0, 2, 1}, {0, 1}, false, "mtm_track_boxes_sets: track 1: set_off is not ascending"},
+        {40, 50, MTM_U8, {ok}, {0, 2}, {1, 0}, false,
+         "mtm_track_boxes_sets: track 0: start's template is not the first of its set"},
+        {40, 50, MTM_U8, {ok}, {0, 3}, {0, 1, 2}, false,
+         "mtm_track_boxes_sets: track 0: the templates of a set must be of one shape"},
+        // two invalid tracks: the first is reported
+        {40, 50, MTM_U8, {ok, {0, 2, 3, 6, 14}, {9, 2, 3, 12, 14}}, {}, {}, false,
+         "mtm_track_boxes: track 1: template larger than the box"},
+        {40, 50, MTM_U8, {ok, ok, ok}, {0, 1, 1, 0}, {0}, false, "mtm_track_boxes_sets: track 1: empty set"},
+    };
+    for (const Bad& b : bad) {
+        const std::string who = b.msg.substr(0, b.msg.find(':'));
+        TrackPlan P;
+        set_error("");
+        const int rc = plan_tracks(tl, b.rows, b.cols, 1, b.dtype, b.start.data(), (int)b.start.size(), 2, b.reacq,
+                                   b.off.empty() ? nullptr : b.off.data(), b.idx.data(), who.c_str(), P);
+        if (rc != MTM_E_INVALID || b.msg != mtm_last_error())
+            std::fprintf(stderr, "plan_tracks: %d '%s', expected '%s'\n", rc, mtm_last_error(), b.msg.c_str());
+        CHECK(rc == MTM_E_INVALID && b.msg == mtm_last_error());
+    }
+    // the last sizes that pass: a uint16 template of exactly 2^21 pixels, a whole-frame map of 2^32 - 2^16 outputs
+    TrackPlan P;
+    const mtm_box_unit big = {6, 0, 0, 2048, 1024}, dot = {7, 0, 0, 4, 4};
+    CHECK(plan_tracks(tl, 2048, 1025, 1, MTM_U16, &big, 1, 0, false, nullptr, nullptr, "mtm_track_boxes", P) == MTM_OK);
+    CHECK(P.tiles.size() == 1 && P.templ_bytes[0] == (size_t)2 << 21);
+    CHECK(plan_tracks(tl, 65536, 65535, 1, MTM_U8, &dot, 1, 0, true, nullptr, nullptr, "mtm_track_boxes_reacquire", P) ==
+          MTM_OK);
+    CHECK(P.tiles_max == 4096ull * 4096ull && P.groups_max == 1 && P.tiles.size() == 1);
+}
+
 int main() {
     std::mt19937 rng(12345);
     test_verify_candidates(rng);
     test_ladder();
+    test_track_plan();
     test_host(rng);
     test_group(rng);
     // two groups driven from two caller threads at once (each group is single-caller; the library must not share state)

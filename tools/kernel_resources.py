@@ -96,5 +96,5 @@ if __name__ == "__main__":
     flt = sys.argv[-1] if len(sys.argv) > 1 and not os.path.exists(sys.argv[-1]) else ""
     ks = [k for k in kernels(so) if flt in k["name"]]
     for k in sorted(ks, key=lambda k: -k["scratch"])[:400]:
-        print("%4d vgpr %4d sgpr %5d B scratch  %s" % (k["vgpr"], k["sgpr"], k["scratch"], k["name"][:150]))
+        print("%4d vgpr %4d sgpr %5d B scratch %6d B lds  %s" % (k["vgpr"], k["sgpr"], k["scratch"], k["lds"], k["name"][:150]))
     print("%d kernels; max scratch %d B" % (len(ks), max(k["scratch"] for k in ks)))

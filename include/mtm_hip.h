@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -244,6 +244,21 @@ int         mtm_debug_templ_stats(const void* px, int rows, int cols, int chans,
  * of classes, or a negative MTM_E_* code (no template set placed). */
 #define MTM_CLASS_TILING_FIELDS 12
 int         mtm_debug_class_tilings(mtm_ctx* ctx, int32_t* out, int cap_classes);
+/* Test support (added under ABI 9; needs no image and no templates on the context).  The device's share of the non-maxima
+ * suppression of mtm_find_matches_image_nms - the counting sort by grid cell, the champion pass, the prune pass - on a hit
+ * list the caller hands over: the n records of `hits` and the count n go to device memory, the grid is the one a
+ * rows x cols image with boxes of at most max_side a side gets (cell = max(32, max_side), cols / cell + 3 by rows / cell + 3
+ * cells), and the very chain the search call queues behind its peak pass runs on them: n_min plays the part of the
+ * context's device-NMS minimum, n_max that of min(hit capacity, 2^18) - it sizes the work buffers and the launches (1 ..
+ * 2^18).  score_threshold, ascending and max_overlap (>= 0) are those of mtm_nms.  out = the champions (hits no earlier hit
+ * overlaps beyond max_overlap: kept for certain), then the undecided hits (neither champions nor overlapped by one), in no
+ * particular order inside either part; what a champion overlaps is not returned.  mtm_nms' selection from `out` is its
+ * selection from `hits`.  A list shorter than n_min or longer than n_max is left alone, as in the search call: both counts
+ * 0, `out` untouched.  capacity >= n for a list inside [n_min, n_max].  The hits' boxes are expected inside the image; a
+ * box elsewhere is filed in the nearest cell. */
+int         mtm_debug_device_nms(mtm_ctx* ctx, const mtm_hit* hits, int64_t n, int rows, int cols, int max_side,
+                                 double score_threshold, int ascending, double max_overlap, int64_t n_min, int64_t n_max,
+                                 mtm_hit* out, int64_t capacity, int64_t* n_champions, int64_t* n_undecided);
 /* Page-locked host memory for pixel buffers (optional).  The reference's caller hands over whatever numpy holds
  * (MTM/__init__.py:247 `image`) - pageable memory, which the runtime stages through its own pinned buffers while the
  * upload call blocks.  An image kept in memory from mtm_host_alloc crosses PCIe as a plain DMA transfer behind the call

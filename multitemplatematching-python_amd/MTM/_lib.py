@@ -88,6 +88,10 @@ SYMBOLS = {
     "mtm_debug_class_tilings": (ctypes.c_int, [ctypes.c_void_p, _P(ctypes.c_int32), ctypes.c_int]),
     "mtm_debug_templ_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_int, _P(ctypes.c_double)]),
+    "mtm_debug_device_nms": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, _P(ctypes.c_int64),
+                                            _P(ctypes.c_int64)]),
     "mtm_set_image": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
     "mtm_set_image_downscaled": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -475,6 +479,25 @@ class Context(_RecordMemo):
         out = (ctypes.c_uint64 * 4)()
         check(self._lib.mtm_debug_quotient_check(self._h, int(n_cases), int(seed), out), "mtm_debug_quotient_check")
         return {"cases": int(out[0]), "mismatches": int(out[1]), "took_division": int(out[2]), "max_ulp_distance": int(out[3])}
+
+    def debug_device_nms(self, hits, rows, cols, max_side, score_threshold, max_overlap, ascending=False, n_min=0,
+                         n_max=1 << 18, out=None):
+        """Test support (mtm_debug_device_nms): the device's share of the suppression - counting sort by grid cell, champion
+        pass, prune pass - on the hit list `hits`, on the grid of a rows x cols image with boxes of at most max_side a side
+        -> (champions, undecided): the hits kept for certain and the ones the host's pass still has to decide about (views
+        of `out`, a HIT_DTYPE array of at least len(hits) records, when one is given).  A list shorter than n_min or longer
+        than n_max returns two empty arrays and leaves `out` as it is."""
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        n = len(hits)
+        if out is None:
+            out = np.empty(max(n, 1), dtype=HIT_DTYPE)
+        assert out.dtype == HIT_DTYPE and out.flags.c_contiguous
+        nc, nu = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(self._lib.mtm_debug_device_nms(self._h, hits.ctypes.data, n, int(rows), int(cols), int(max_side),
+                                             float(score_threshold), int(bool(ascending)), float(max_overlap), int(n_min),
+                                             int(n_max), out.ctypes.data, len(out), ctypes.byref(nc), ctypes.byref(nu)),
+              "mtm_debug_device_nms")
+        return out[:nc.value], out[nc.value:nc.value + nu.value]
 
     def set_image(self, image, downscale=1):
         """Upload the search image; `downscale` > 1 area-averages it by that integer factor on the

@@ -313,25 +313,22 @@ struct DeviceNms {
     const mtm_hit* out = nullptr;
 };
 
-int queue_device_nms(mtm_ctx* c, const NmsRequest& req, const mtm_hit* dhits, const unsigned long long* dcount, bool ascending, DeviceNms* q) {
-    // (a cell larger than the largest box side is still correct - the 3x3 cell neighbourhood covers every partner - and
-    // small templates on a large image would otherwise make millions of cells to clear and scan on every attempt)
-    int cell = 32;
-    for (const TemplDev& d : c->td_host) cell = std::max(cell, std::max(d.rows, d.cols));
-    const size_t n_max = (size_t)std::min<int64_t>(c->hit_cap, 1ll << 18);
+// Lays out nms_buf and queues the chain - two memsets, the five launches, the copy of the two counters - for the list of
+// *dcount records at `dhits` (both on the device); reads nothing else of the call from the context.  n_max sizes the buffers
+// and the launches; a count outside [n_min, n_max] makes every kernel return at once.
+int queue_nms_chain(mtm_ctx* c, const mtm_hit* dhits, const unsigned long long* dcount, unsigned n_min, size_t n_max, bool ascending,
+                    float thr_score, float thr_overlap, const NmsGrid& g, DeviceNms* q) {
     NmsParams p{};
     p.hits = dhits;
     p.n_ptr = dcount;
-    p.n_min = (unsigned)std::min<long long>(c->nms_device_min, 1ll << 30);
+    p.n_min = n_min;
     p.n_max = (unsigned)n_max;
     p.ascending = ascending ? 1 : 0;
-    // MTM/NMS.py:73-78: the scores are float32 (1 - score for the difference methods), the threshold a python float
-    // transformed in double and narrowed by the cv2 binding
-    p.thr_score = (float)(ascending ? (1.0 - req.score_threshold) : req.score_threshold);
-    p.thr_overlap = (float)req.max_overlap;
-    p.cell = cell;
-    p.gw = c->cols / cell + 3;
-    p.gh = c->rows / cell + 3;
+    p.thr_score = thr_score;
+    p.thr_overlap = thr_overlap;
+    p.cell = g.cell;
+    p.gw = g.gw;
+    p.gh = g.gh;
     const size_t n_cells = (size_t)p.gw * p.gh;
     const size_t off_rank = round_up(sizeof(unsigned) * (n_cells + 1), 256), off_status = off_rank + round_up(sizeof(unsigned) * n_max, 256);
     const size_t off_sorted = off_status + round_up(sizeof(int) * n_max, 256);
@@ -362,6 +359,19 @@ int queue_device_nms(mtm_ctx* c, const NmsRequest& req, const mtm_hit* dhits, co
     q->n_max = (unsigned)n_max;
     q->out = p.out;
     return MTM_OK;
+}
+
+// the production call: the grid of the context's image and templates (mtm_nms_core.h: nms_grid), lists of nms_device_min ..
+// min(hit capacity, 2^18) peaks
+int queue_device_nms(mtm_ctx* c, const NmsRequest& req, const mtm_hit* dhits, const unsigned long long* dcount, bool ascending, DeviceNms* q) {
+    int max_side = 0;
+    for (const TemplDev& d : c->td_host) max_side = std::max(max_side, std::max(d.rows, d.cols));
+    const size_t n_max = (size_t)std::min<int64_t>(c->hit_cap, 1ll << 18);
+    // MTM/NMS.py:73-78: the scores are float32 (1 - score for the difference methods), the threshold a python float
+    // transformed in double and narrowed by the cv2 binding
+    const float thr_score = (float)(ascending ? (1.0 - req.score_threshold) : req.score_threshold);
+    return queue_nms_chain(c, dhits, dcount, (unsigned)std::min<long long>(c->nms_device_min, 1ll << 30), n_max, ascending, thr_score,
+                           (float)req.max_overlap, nms_grid(c->rows, c->cols, max_side), q);
 }
 
 // after the stream was synchronised (q.cnt has landed): the pruned list of `count` peaks -> `rest`, *n_sure = champions
@@ -1058,6 +1068,52 @@ int mtm_find_matches_image_nms(mtm_ctx* c, const void* px, int rows, int cols, i
     const int rc = find_matches_impl(c, MTM_PEAKS_LOCAL, score_threshold, out, capacity, n_out, nullptr, &up, &nms);
     host_trace(c, 15);
     return rc;
+}
+
+// Test support: the chain of queue_nms_chain on a list the caller hands over (tests/test_gpu_device_nms.py).
+int mtm_debug_device_nms(mtm_ctx* c, const mtm_hit* hits, int64_t n, int rows, int cols, int max_side, double score_threshold,
+                         int ascending, double max_overlap, int64_t n_min, int64_t n_max, mtm_hit* out, int64_t capacity,
+                         int64_t* n_champions, int64_t* n_undecided) {
+    if (!c) {
+        set_error("mtm_debug_device_nms: null context");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, "mtm_debug_device_nms");
+    const bool gate = n >= n_min && n <= n_max;
+    if (n < 0 || (n > 0 && !hits) || rows < 1 || cols < 1 || max_side < 0 || !(max_overlap >= 0.0) || n_min < 0 || n_max < 1 ||
+        n_max > (1ll << 18) || capacity < 0 || !n_champions || !n_undecided || (gate && (capacity < n || (n > 0 && !out)))) {
+        set_error("mtm_debug_device_nms: bad arguments (negative sizes, max_overlap < 0, n_max outside 1 .. 2^18, or a capacity "
+                  "below the length of a list inside [n_min, n_max])");
+        return MTM_E_INVALID;
+    }
+    const NmsGrid g = nms_grid(rows, cols, max_side);
+    if ((long long)g.gw * g.gh > (1ll << 24)) {
+        set_error("mtm_debug_device_nms: more than 2^24 grid cells");
+        return MTM_E_INVALID;
+    }
+    HIPC(hipSetDevice(c->device));
+    // [the count][the records]
+    MTMC(c->nms_dbg.ensure(256 + sizeof(mtm_hit) * (size_t)std::max<int64_t>(n, 1)));
+    uint8_t* d = c->nms_dbg.as<uint8_t>();
+    const unsigned long long count = (unsigned long long)n;
+    HIPC(hipMemcpyAsync(d, &count, sizeof(count), hipMemcpyHostToDevice, c->stream));
+    if (n) HIPC(hipMemcpyAsync(d + 256, hits, sizeof(mtm_hit) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    DeviceNms q;
+    MTMC(queue_nms_chain(c, reinterpret_cast<const mtm_hit*>(d + 256), reinterpret_cast<const unsigned long long*>(d),
+                         (unsigned)std::min<int64_t>(n_min, 1ll << 30), (size_t)n_max, ascending != 0,
+                         (float)(ascending ? (1.0 - score_threshold) : score_threshold), (float)max_overlap, g, &q));
+    HIPC(hipStreamSynchronize(c->stream));
+    std::vector<mtm_hit> rest;
+    long long n_sure = 0;
+    MTMC(fetch_device_nms(c, q, count, rest, &n_sure));
+    if (!gate && !rest.empty()) {
+        set_error("mtm_debug_device_nms: internal state (a list outside [n_min, n_max] produced records)");
+        return MTM_E_STATE;
+    }
+    if (!rest.empty()) std::memcpy(out, rest.data(), sizeof(mtm_hit) * rest.size());
+    *n_champions = (int64_t)n_sure;
+    *n_undecided = (int64_t)rest.size() - (int64_t)n_sure;
+    return MTM_OK;
 }
 
 // One step of the process-per-GPU form in ONE native call (round 5): this rank's shard is searched, its hits get their list

@@ -188,6 +188,7 @@ struct mtm_ctx {
     hipStream_t copy_stream = nullptr;
     long long nms_device_min = 4096;        // CallRoute::nms: fewer peaks than this are pruned on the host (as fast)
     DevBuf nms_buf;
+    DevBuf nms_dbg;             // mtm_debug_device_nms: [the count][the records] of the list under test
     // segment flags (MTM_SPARSE_MAPS, default 1): the route of a call on dense maps (candidate list overflowed recently)
     // when every class runs the lean MFMA epilogue - maps in memory, one flag per row segment that holds something above the
     // threshold, peaks_sparse_kernel over the flagged segments instead of the full scan (MfmaParams::seg_flags)

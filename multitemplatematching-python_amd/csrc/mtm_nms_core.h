@@ -44,4 +44,20 @@ MTM_HD inline float nms_rect_overlap(const mtm_hit& a, const mtm_hit& b) {
     return 1.0f - (float)dist;
 }
 
+// The grid the device's counting sort files the hits of a rows x cols image in, by the top-left corner of their box
+// (mtm_k_nms.hip.h; max_side = the largest side of any box):
+//     cell = max(32, max_side),   gw = cols / cell + 3,   gh = rows / cell + 3      (integer divisions)
+// A hit at (x, y) goes to column min(max(x / cell, 0), gw - 3) + 1 and the row formed likewise: one ring of empty cells
+// around the cells in use, one more column / row for the run cell_cnt[c - 1] .. cell_cnt[c + 2] the kernels read per grid
+// row.  Boxes that intersect are less than a side apart, so their cells are at most one apart in each axis.  (A cell larger
+// than the largest side is still correct, and small templates on a large image would otherwise make millions of cells to
+// clear and scan on every call: hence the floor of 32.)
+struct NmsGrid {
+    int cell, gw, gh;
+};
+inline NmsGrid nms_grid(int rows, int cols, int max_side) {
+    const int cell = max_side > 32 ? max_side : 32;
+    return NmsGrid{cell, cols / cell + 3, rows / cell + 3};
+}
+
 }  // namespace mtm

@@ -486,6 +486,62 @@ static void test_host(std::mt19937& rng) {
     CHECK(mtm_nms(nullptr, 5, 0.5, 0, -1, 0.5, nullptr, &nk) == MTM_E_INVALID && std::strlen(mtm_last_error()) > 0);
 }
 
+// ---- the grid of the device's NMS (mtm_nms_core.h: nms_grid; the cell rule as nms_cell_of, mtm_k_nms.hip.h, applies it) ----
+// Boxes inside the image with sides <= max_side: any two that intersect are filed at most one cell apart in each axis (the
+// 3 x 3 neighbourhood holds every partner), and every index the kernels form - cell_cnt[c + dy * gw - 1] and
+// cell_cnt[c + dy * gw + 2], dy = -1 .. 1 - lies in [0, gw * gh] (cell_cnt has gw * gh + 1 words).
+static void test_nms_grid(std::mt19937& rng) {
+    const auto cell_xy = [](const NmsGrid& g, const mtm_hit& h, int* cx, int* cy) {
+        *cx = std::min(std::max(h.x / g.cell, 0), g.gw - 3) + 1;
+        *cy = std::min(std::max(h.y / g.cell, 0), g.gh - 3) + 1;
+    };
+    CHECK(nms_grid(300, 640, 0).cell == 32 && nms_grid(300, 640, 32).gw == 23 && nms_grid(300, 640, 32).gh == 12);
+    CHECK(nms_grid(300, 640, 48).cell == 48 && nms_grid(300, 640, 48).gw == 16 && nms_grid(300, 640, 48).gh == 9);
+    for (int rep = 0; rep < 400; ++rep) {
+        const int max_side = rep % 7 == 0 ? 1 + (int)(rng() % 31) : 1 + (int)(rng() % 300);
+        // (images narrower than a cell, sides at and next to multiples of the cell)
+        int rows = 1 + (int)(rng() % 2000), cols = 1 + (int)(rng() % 2000);
+        const int cell0 = std::max(32, max_side);
+        if (rep % 5 == 1) cols = cell0 * (1 + (int)(rng() % 6)) + (int)(rng() % 3) - 1;
+        if (rep % 5 == 2) rows = cell0 * (1 + (int)(rng() % 6)) + (int)(rng() % 3) - 1;
+        const NmsGrid g = nms_grid(rows, cols, max_side);
+        CHECK(g.cell == cell0 && g.gw == cols / g.cell + 3 && g.gh == rows / g.cell + 3);
+        std::vector<mtm_hit> hits(64);
+        for (size_t i = 0; i < hits.size(); ++i) {
+            mtm_hit& h = hits[i];
+            h.w = 1 + (int)(rng() % (unsigned)std::min(max_side, cols));
+            h.h = 1 + (int)(rng() % (unsigned)std::min(max_side, rows));
+            if (i % 4 == 0) h.w = std::min(max_side, cols);
+            if (i % 8 == 0) h.h = std::min(max_side, rows);
+            // around one place (so that pairs intersect), or at the image's edges
+            const int ax = (int)(rng() % (unsigned)cols), ay = (int)(rng() % (unsigned)rows);
+            h.x = i < 40 ? (int)(hits[0].x * (i > 0) + (i ? (int)(rng() % (unsigned)(2 * g.cell)) - g.cell : ax)) : (i % 2 ? 0 : cols);
+            h.y = i < 40 ? (int)(hits[0].y * (i > 0) + (i ? (int)(rng() % (unsigned)(2 * g.cell)) - g.cell : ay)) : (i % 3 ? 0 : rows);
+            h.x = std::min(std::max(h.x, 0), cols - h.w);
+            h.y = std::min(std::max(h.y, 0), rows - h.h);
+            h.templ_idx = 0;
+            h.score = 1.0f;
+        }
+        int pairs = 0;
+        for (const mtm_hit& a : hits) {
+            int ax, ay;
+            cell_xy(g, a, &ax, &ay);
+            CHECK(ax >= 1 && ax <= g.gw - 2 && ay >= 1 && ay <= g.gh - 2);
+            const int c = ay * g.gw + ax;
+            for (int dy = -1; dy <= 1; ++dy)
+                CHECK(c + dy * g.gw - 1 >= 0 && c + dy * g.gw + 2 <= g.gw * g.gh);
+            for (const mtm_hit& b : hits) {
+                if (nms_rect_overlap(a, b) <= 0.0f) continue;
+                int bx, by;
+                cell_xy(g, b, &bx, &by);
+                CHECK(std::abs(ax - bx) <= 1 && std::abs(ay - by) <= 1);
+                ++pairs;
+            }
+        }
+        CHECK(pairs > (int)hits.size());        // (more than every box with itself)
+    }
+}
+
 // ---- the host-only pieces of fm_end (mtm_api.hip): the 3x3 test of the candidate list, the trivial-map rule, the ladder
 
 // one case of verify_candidates_3x3 against brute force over the maps: `maps[t]` the scores of an oh[t] x ow[t] map, the list
@@ -882,6 +938,7 @@ int main() {
     test_verify_candidates(rng);
     test_ladder();
     test_track_plan();
+    test_nms_grid(rng);
     test_host(rng);
     test_group(rng);
     // two groups driven from two caller threads at once (each group is single-caller; the library must not share state)

@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -259,6 +259,66 @@ int         mtm_debug_class_tilings(mtm_ctx* ctx, int32_t* out, int cap_classes)
 int         mtm_debug_device_nms(mtm_ctx* ctx, const mtm_hit* hits, int64_t n, int rows, int cols, int max_side,
                                  double score_threshold, int ascending, double max_overlap, int64_t n_min, int64_t n_max,
                                  mtm_hit* out, int64_t capacity, int64_t* n_champions, int64_t* n_undecided);
+/* Test support (added under ABI 9; needs no image and no templates on the context, leaves a placed template set and the
+ * options as they are).  The peak pass of the search calls on score maps the caller hands over: the n_maps maps (dims: oh, ow
+ * and the template's h, w per map - the last two only fill the records -, maps: their oh * ow float32 values, tightly packed,
+ * map after map) go to a map arena laid out as placement lays it out (pitch = ow rounded up to 4, map after map) that was
+ * filled with pattern_byte first - the pitch padding and, under `holes`, whatever the caller leaves out -, and the very
+ * kernels of `route` run on them with the grids and capacities the search call derives (csrc/mtm_peak_sizing.h):
+ *   MTM_PEAK_SCAN            peaks_kernel
+ *   MTM_PEAK_SCAN_BATCH      peaks_batch_kernel: every map is that of a stack of (oh + h - 1) / img_rows images of img_rows
+ *                            rows (the same number for every map, img_rows - h >= 1)
+ *   MTM_PEAK_SEGMENTS        peaks_sparse_kernel + compact_hits_kernel: flags = one byte per (map, row, strip column of 256),
+ *                            n_maps x max oh x ceil(max ow / 256) bytes; holes = 1: the rows of unflagged segments are not
+ *                            copied (they keep pattern_byte) and the kernel is told so
+ *   MTM_PEAK_VERIFY_MAPS     verify_peaks_kernel on the candidate list cands[0 .. n_cands)
+ *   MTM_PEAK_VERIFY_HASH     cand_hash_insert_kernel + verify_hash_kernel on that list
+ *   MTM_PEAK_EXTREMUM        extremum_kernel
+ *   MTM_PEAK_EXTREMUM_BATCH  extremum_batch_kernel (img_rows as above)
+ * thr is the call's threshold on the score (a hit's quality - score, or -score with mode_min - exceeds thr, or -thr), border
+ * an MTM_BORDER_* value, hit_cap the hit capacity (>= 1).  The verify routes: cand_count is the list's length as the device
+ * counter holds it (it may exceed cand_cap; the first min(cand_count, cand_cap) <= n_cands records are judged, every one of
+ * them inside its map), thr_q the quality a hit must exceed; their launch covers max(hit_cap, cand_cap) candidates (the
+ * search call always has cand_cap <= hit_cap).
+ * Results: `records` (capacity >= hit_cap records) is copied to the device's record list before the launches and back after
+ * them - what the kernels did not write is what the caller put there; *count = the device's count, as it reports it;
+ * raw[n_ints] = the per-map int (the scans' flag word - per (image, map), image-major, for the batch scan -, the verifiers'
+ * peak count), trivial[n_ints] = the host's reading of it (scan_flags_trivial / fused_count_trivial; per image:
+ * raw == 0); the extremum routes: keys[2 * n_ints] = the (max, min) key pairs, ext_hits[2 * n_ints] = their records
+ * (decode_extremum_key); MTM_PEAK_SEGMENTS: list_counts[n_lists] = the per-(map, strip column) counters before compaction
+ * (list = map * strip columns + strip column).  info[8] = {grid x, grid y, grid z, records per list (SEGMENTS), lists,
+ * verifier work-groups, hash slots, work-groups per map of the extremum launch}.  Pointers of routes not taken may be
+ * NULL; n_ints and list_cap are the lengths of raw / trivial (keys, ext_hits: twice that) and of list_counts. */
+#define MTM_PEAK_SCAN           0
+#define MTM_PEAK_SCAN_BATCH     1
+#define MTM_PEAK_SEGMENTS       2
+#define MTM_PEAK_VERIFY_MAPS    3
+#define MTM_PEAK_VERIFY_HASH    4
+#define MTM_PEAK_EXTREMUM       5
+#define MTM_PEAK_EXTREMUM_BATCH 6
+typedef struct mtm_peak_pass {
+    int32_t        n_maps, route, mode_min, border;
+    float          thr, thr_q;
+    int32_t        img_rows, holes, pattern_byte, reserved;
+    int64_t        hit_cap;
+    const int32_t* dims;
+    const float*   maps;
+    const uint8_t* flags;
+    const mtm_hit* cands;
+    int64_t        n_cands, cand_count, cand_cap;
+    mtm_hit*       records;
+    int64_t        capacity;
+    uint64_t*      count;
+    int32_t*       raw;
+    int32_t*       trivial;
+    int64_t        n_ints;
+    uint64_t*      keys;
+    mtm_hit*       ext_hits;
+    uint64_t*      list_counts;
+    int64_t        list_cap;
+    int64_t*       info;
+} mtm_peak_pass;
+int         mtm_debug_peak_pass(mtm_ctx* ctx, const mtm_peak_pass* args);
 /* Page-locked host memory for pixel buffers (optional).  The reference's caller hands over whatever numpy holds
  * (MTM/__init__.py:247 `image`) - pageable memory, which the runtime stages through its own pinned buffers while the
  * upload call blocks.  An image kept in memory from mtm_host_alloc crosses PCIe as a plain DMA transfer behind the call

@@ -72,6 +72,24 @@ assert TEMPL_DTYPE.itemsize == ctypes.sizeof(MtmTempl) == 48
 VARIANT_DTYPE = np.dtype([("rot90", "<i4"), ("flip_lr", "<i4"), ("flip_ud", "<i4"), ("rows", "<i4"), ("cols", "<i4"),
                           ("down", "<i4")])
 
+# mtm_debug_peak_pass: the routes of the peak pass, and its argument block (mtm_peak_pass)
+PEAK_SCAN, PEAK_SCAN_BATCH, PEAK_SEGMENTS, PEAK_VERIFY_MAPS, PEAK_VERIFY_HASH, PEAK_EXTREMUM, PEAK_EXTREMUM_BATCH = range(7)
+PEAK_INFO_FIELDS = ("grid_x", "grid_y", "grid_z", "list_cap", "n_lists", "verify_blocks", "hash_slots", "extremum_blocks")
+
+
+class MtmPeakPass(ctypes.Structure):
+    _fields_ = [("n_maps", ctypes.c_int32), ("route", ctypes.c_int32), ("mode_min", ctypes.c_int32), ("border", ctypes.c_int32),
+                ("thr", ctypes.c_float), ("thr_q", ctypes.c_float),
+                ("img_rows", ctypes.c_int32), ("holes", ctypes.c_int32), ("pattern_byte", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("hit_cap", ctypes.c_int64),
+                ("dims", ctypes.c_void_p), ("maps", ctypes.c_void_p), ("flags", ctypes.c_void_p), ("cands", ctypes.c_void_p),
+                ("n_cands", ctypes.c_int64), ("cand_count", ctypes.c_int64), ("cand_cap", ctypes.c_int64),
+                ("records", ctypes.c_void_p), ("capacity", ctypes.c_int64), ("count", ctypes.c_void_p),
+                ("raw", ctypes.c_void_p), ("trivial", ctypes.c_void_p), ("n_ints", ctypes.c_int64),
+                ("keys", ctypes.c_void_p), ("ext_hits", ctypes.c_void_p), ("list_counts", ctypes.c_void_p),
+                ("list_cap", ctypes.c_int64), ("info", ctypes.c_void_p)]
+
+
 # every symbol include/mtm_hip.h declares: (restype, argtypes)
 _P = ctypes.POINTER
 SYMBOLS = {
@@ -92,6 +110,7 @@ SYMBOLS = {
                                             ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int64,
                                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, _P(ctypes.c_int64),
                                             _P(ctypes.c_int64)]),
+    "mtm_debug_peak_pass": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_set_image": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
     "mtm_set_image_downscaled": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -498,6 +517,63 @@ class Context(_RecordMemo):
                                              int(n_max), out.ctypes.data, len(out), ctypes.byref(nc), ctypes.byref(nu)),
               "mtm_debug_device_nms")
         return out[:nc.value], out[nc.value:nc.value + nu.value]
+
+    def debug_peak_pass(self, maps, route, thr, mode_min=False, border=BORDER_NEAREST, hit_cap=4096, templ_hw=None, img_rows=0,
+                        flags=None, holes=False, cands=None, cand_count=None, cand_cap=None, thr_q=None, pattern=0xFF,
+                        records=None):
+        """Test support (mtm_debug_peak_pass): the peak pass of the search calls - the kernels of `route` (PEAK_*), with the
+        grids and capacities the search call derives - on the float32 score maps `maps` (a list of 2-D arrays; templ_hw: the
+        (h, w) of each map's template, (1, 1) by default).  flags (PEAK_SEGMENTS): uint8 [map][row][strip column of 256],
+        padded to the largest map.  cands (the verify routes): HIT_DTYPE records, cand_count the length the device counter
+        holds (len(cands) by default), cand_cap the list's capacity (max(len, 1) by default), thr_q the quality a hit exceeds
+        (the threshold's by default).  records: a HIT_DTYPE array of at least hit_cap records that the device's list starts
+        from (what the kernels do not write stays) - it comes back as 'records'.
+        -> dict(records, count, raw, trivial, keys, ext_hits, list_counts, info); raw / trivial / keys are per (image, map) for
+        the batch routes."""
+        maps = [np.ascontiguousarray(m, dtype=np.float32) for m in maps]
+        n = len(maps)
+        assert n >= 1 and all(m.ndim == 2 for m in maps)
+        templ_hw = [(1, 1)] * n if templ_hw is None else list(templ_hw)
+        dims = np.array([[m.shape[0], m.shape[1], hw[0], hw[1]] for m, hw in zip(maps, templ_hw)], dtype=np.int32)
+        packed = np.concatenate([m.ravel() for m in maps])
+        batch = route in (PEAK_SCAN_BATCH, PEAK_EXTREMUM_BATCH)
+        n_img = (int(dims[0, 0]) + int(dims[0, 2]) - 1) // int(img_rows) if batch and img_rows > 0 else 1
+        n_ints = n * max(n_img, 1)
+        max_oh, max_ow = int(dims[:, 0].max()), int(dims[:, 1].max())
+        n_sx = (max_ow + 255) // 256
+        a = MtmPeakPass()
+        a.n_maps, a.route, a.mode_min, a.border = n, int(route), int(bool(mode_min)), int(border)
+        a.thr = float(thr)
+        a.thr_q = float(thr_q) if thr_q is not None else float(np.float32(-np.float32(thr)) if mode_min else np.float32(thr))
+        a.img_rows, a.holes, a.pattern_byte, a.hit_cap = int(img_rows), int(bool(holes)), int(pattern), int(hit_cap)
+        a.dims, a.maps = dims.ctypes.data, packed.ctypes.data
+        if flags is not None:
+            flags = np.ascontiguousarray(flags, dtype=np.uint8)
+            assert flags.shape == (n, max_oh, n_sx), (flags.shape, (n, max_oh, n_sx))
+            a.flags = flags.ctypes.data
+        if cands is not None:
+            cands = np.ascontiguousarray(cands, dtype=HIT_DTYPE)
+            a.cands = cands.ctypes.data if len(cands) else None
+            a.n_cands = len(cands)
+            a.cand_count = len(cands) if cand_count is None else int(cand_count)
+            a.cand_cap = max(len(cands), 1) if cand_cap is None else int(cand_cap)
+        if records is None:
+            records = np.zeros(int(hit_cap), dtype=HIT_DTYPE)
+        assert records.dtype == HIT_DTYPE and records.flags.c_contiguous and records.flags.writeable
+        count = np.zeros(1, dtype=np.uint64)
+        raw, trivial = np.zeros(n_ints, dtype=np.int32), np.zeros(n_ints, dtype=np.int32)
+        keys, ext_hits = np.zeros(2 * n_ints, dtype=np.uint64), np.zeros(2 * n_ints, dtype=HIT_DTYPE)
+        list_counts = np.zeros(n * n_sx, dtype=np.uint64)
+        info = np.zeros(8, dtype=np.int64)
+        a.records, a.capacity, a.count = records.ctypes.data, len(records), count.ctypes.data
+        a.raw, a.trivial, a.n_ints = raw.ctypes.data, trivial.ctypes.data, n_ints
+        a.keys, a.ext_hits = keys.ctypes.data, ext_hits.ctypes.data
+        a.list_counts, a.list_cap, a.info = list_counts.ctypes.data, len(list_counts), info.ctypes.data
+        check(self._lib.mtm_debug_peak_pass(self._h, ctypes.byref(a)), "mtm_debug_peak_pass")
+        shape = (n_img, n) if batch else (n,)
+        return {"records": records, "count": int(count[0]), "raw": raw.reshape(shape), "trivial": trivial.reshape(shape),
+                "keys": keys.reshape(shape + (2,)), "ext_hits": ext_hits.reshape(shape + (2,)), "list_counts": list_counts,
+                "info": dict(zip(PEAK_INFO_FIELDS, (int(v) for v in info)))}
 
     def set_image(self, image, downscale=1):
         """Upload the search image; `downscale` > 1 area-averages it by that integer factor on the

@@ -170,9 +170,7 @@ CallRoute plan_call(const mtm_ctx* c, int mode, float thr, bool banded) {
     // hash table of the candidate positions (hits-only verification on the device: only when the
     // candidates are too many to be checked on the host, see fm_end)
     if (R.hits_only && !R.ext) {
-        size_t hsz = 1024;
-        while (hsz < 2 * (size_t)R.cand_cap) hsz <<= 1;
-        R.hash_mask = (unsigned)(hsz - 1);
+        R.hash_mask = (unsigned)(cand_hash_slots(R.cand_cap) - 1);
     }
     // The landing buffer of the candidate list (pinned).  Round 5: when every class of the call runs ncc_mfma_kernel's own
     // epilogue, the waves that fill the first slots of the list write them there as well (MfmaParams::cand_pin) and the
@@ -248,7 +246,7 @@ int fm_begin(mtm_ctx* c, int mode, double score_threshold, NextImage* next, Call
         if (!R.zero_pending && c->cands.p != c->cands_zeroed) HIPC(hipMemsetAsync(c->cands.p, 0, 16, c->stream));
         c->cands_zeroed = nullptr;
     }
-    if (R.hash_mask) MTMC(c->chash.ensure(((size_t)R.hash_mask + 1) * (sizeof(unsigned long long) + sizeof(int))));
+    if (R.hash_mask) MTMC(c->chash.ensure(cand_hash_bytes(R.hash_mask)));
     if (R.prefetched) {
         const size_t fetch_bytes = 16 + sizeof(mtm_hit) * R.cand_pin_n;
         if (c->pinned_cap < fetch_bytes) {
@@ -421,7 +419,7 @@ int to_three_products(mtm_ctx* c, CallRoute& R) {
     back_off(c->np1_backoff, c->np1_backoff_len);
     HIPC(hipMemsetAsync(c->cands.p, 0, 16, c->stream));
     if (R.ext) HIPC(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * 2 * std::max(1, R.n), c->stream));
-    else if (R.hits_only) HIPC(hipMemsetAsync(c->chash.p, 0, ((size_t)R.hash_mask + 1) * sizeof(unsigned long long), c->stream));
+    else if (R.hits_only) HIPC(hipMemsetAsync(c->chash.p, 0, cand_hash_key_bytes(R.hash_mask), c->stream));
     R.cand_on = true;
     MTMC(rescore(c, R));
     R.cand_on = false;
@@ -505,7 +503,7 @@ int collect_global_extremum(mtm_ctx* c, CallRoute& R, std::vector<mtm_hit>& hits
             HIPC(hipMemsetAsync(c->counters.p, 0, key_bytes, c->stream));
         }
         if (n > 0 && !R.ext) {
-            const int nb = 256;
+            const int nb = extremum_blocks();
             hipLaunchKernelGGL(extremum_kernel, dim3(nb, n), dim3(256), 0, c->stream, c->maps.as<float>(),
                                c->td.as<TemplDev>(), nb, c->counters.as<unsigned long long>());
             HIPC(hipGetLastError());
@@ -602,7 +600,8 @@ dim3 peak_grid(const mtm_ctx* c, int strip_rows) {
         max_oh = std::max(max_oh, c->td_host[t].oh);
         max_ow = std::max(max_ow, c->td_host[t].ow);
     }
-    return dim3((max_ow + kPkCols - 1) / kPkCols, (max_oh + 4 * strip_rows - 1) / (4 * strip_rows), (unsigned)c->list2d.size());
+    const PeakGrid g = peak_grid_dims(max_oh, max_ow, (int)c->list2d.size(), strip_rows);
+    return dim3(g.x, g.y, g.z);
 }
 
 // One attempt of the device's peak pass, queued: the candidate list verified (against the hash table of its positions, or
@@ -619,7 +618,7 @@ int queue_peak_pass(mtm_ctx* c, const CallRoute& R, HitBuffer& hb, DeviceNms* dn
     if (R.fused) {
         // the candidate count (for the overflow check on the host) and the spare word
         HIPC(hipMemcpyAsync(hb.cand_header(), c->cands.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
-        const unsigned blocks = std::min((unsigned)((c->hit_cap + 255) / 256), 4096u);
+        const unsigned blocks = verify_blocks(c->hit_cap);
         const mtm_hit* dcands = reinterpret_cast<const mtm_hit*>(c->cands.as<uint8_t>() + 16);
         if (R.hits_only) {
             unsigned long long* keys = c->chash.as<unsigned long long>();
@@ -639,8 +638,7 @@ int queue_peak_pass(mtm_ctx* c, const CallRoute& R, HitBuffer& hb, DeviceNms* dn
         const dim3 grd = peak_grid(c, kPkSparseRows);
         // a list per (template, strip column) (at most 64 MB of them) + their counters, then one list for the host
         const unsigned long long n_lists = (unsigned long long)grd.z * grd.x;
-        const unsigned long long cap_t = std::max<unsigned long long>(
-            256ull, std::min<unsigned long long>(hit_cap / 8, (64ull << 20) / sizeof(mtm_hit) / n_lists));
+        const unsigned long long cap_t = peak_list_cap(hit_cap, n_lists);
         const size_t cnt_bytes = round_up(sizeof(unsigned long long) * (size_t)n_lists, 256);
         MTMC(c->hits_t.ensure(cnt_bytes + sizeof(mtm_hit) * (size_t)cap_t * (size_t)n_lists));
         unsigned long long* counts_t = c->hits_t.as<unsigned long long>();
@@ -780,7 +778,7 @@ int fm_end(mtm_ctx* c, CallRoute& R, mtm_hit* out, int64_t capacity, int64_t* n_
         bool done = false;
         if (R.fused && any2d && !R.pp_mode) MTMC(verify_on_host(c, R, hits, tflags.data(), &done));
         if (!done && R.hits_only)
-            HIPC(hipMemsetAsync(c->chash.p, 0, ((size_t)R.hash_mask + 1) * sizeof(unsigned long long), c->stream));
+            HIPC(hipMemsetAsync(c->chash.p, 0, cand_hash_key_bytes(R.hash_mask), c->stream));
         if (R.pp_mode) R.fused = true;          // the potential peaks are in the candidate buffer, their neighbourhoods in the maps
         done = done || !any2d;
         HitBuffer hb(R.n);
@@ -885,7 +883,7 @@ int batch_chunk(mtm_ctx* c, const void* const* px, int nb, int rows, int cols, i
         MTMC(c->counters.ensure(sizeof(unsigned long long) * best.size()));
         HIPC(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * best.size(), c->stream));
         if (n > 0) {
-            const int nbk = (int)std::min<long long>(256, (max_px + 4095) / 4096);
+            const int nbk = extremum_batch_blocks(max_px);
             hipLaunchKernelGGL(extremum_batch_kernel, dim3(nbk, n, nb), dim3(256), 0, c->stream, maps, c->td.as<TemplDev>(), rows,
                                nbk, c->counters.as<unsigned long long>());
             HIPC(hipGetLastError());
@@ -1113,6 +1111,220 @@ int mtm_debug_device_nms(mtm_ctx* c, const mtm_hit* hits, int64_t n, int rows, i
     if (!rest.empty()) std::memcpy(out, rest.data(), sizeof(mtm_hit) * rest.size());
     *n_champions = (int64_t)n_sure;
     *n_undecided = (int64_t)rest.size() - (int64_t)n_sure;
+    return MTM_OK;
+}
+
+// Test support: the peak pass on maps the caller hands over (tests/test_gpu_peaks.py).  Everything lives in peak_dbg - the
+// TemplDev table, the map arena, flags, lists, counters -, laid out per call; nothing of the context's placement or options is
+// read or written.  The grids and capacities are those of queue_peak_pass / collect_global_extremum / batch_chunk
+// (mtm_peak_sizing.h).
+int mtm_debug_peak_pass(mtm_ctx* c, const mtm_peak_pass* a) {
+    if (!c || !a) {
+        set_error("mtm_debug_peak_pass: null context or arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, "mtm_debug_peak_pass");
+    const auto bad = [](const char* what) {
+        set_error(std::string("mtm_debug_peak_pass: ") + what);
+        return MTM_E_INVALID;
+    };
+    const int n = a->n_maps, route = a->route;
+    if (n < 1 || n > 4096 || route < MTM_PEAK_SCAN || route > MTM_PEAK_EXTREMUM_BATCH || !a->dims || !a->maps || !a->info ||
+        (a->border != MTM_BORDER_CONSTANT && a->border != MTM_BORDER_NEAREST) || a->hit_cap < 1 || a->hit_cap > (1ll << 24) ||
+        a->pattern_byte < 0 || a->pattern_byte > 255 || a->capacity < 0 || a->n_ints < 0 || a->list_cap < 0)
+        return bad("bad arguments (1 .. 4096 maps, a route, a border rule, hit_cap in 1 .. 2^24, a pattern byte)");
+    const bool batch = route == MTM_PEAK_SCAN_BATCH || route == MTM_PEAK_EXTREMUM_BATCH;
+    const bool ext = route == MTM_PEAK_EXTREMUM || route == MTM_PEAK_EXTREMUM_BATCH;
+    const bool verify = route == MTM_PEAK_VERIFY_MAPS || route == MTM_PEAK_VERIFY_HASH;
+    const bool mode_min = a->mode_min != 0;
+    // the table, as plan_placement fills the fields the peak kernels read
+    std::vector<TemplDev> td((size_t)n, TemplDev{});
+    std::vector<size_t> src_off((size_t)n);
+    size_t arena = 0, src = 0;
+    int max_oh = 0, max_ow = 0, n_img = 1;
+    long long max_px = 1;
+    for (int t = 0; t < n; ++t) {
+        const int oh = a->dims[4 * t], ow = a->dims[4 * t + 1], h = a->dims[4 * t + 2], w = a->dims[4 * t + 3];
+        const int least = ext ? 1 : 2;          // (the scans and verifiers only ever see 2-D maps: mtm_ctx::list2d)
+        if (oh < least || ow < least || oh > kBatchMaxRows || ow > 65535 || h < 1 || w < 1) return bad("a map's size");
+        TemplDev& d = td[(size_t)t];
+        d.rows = h;
+        d.cols = w;
+        d.oh = oh;
+        d.ow = ow;
+        d.map_pitch = map_pitch_of(ow);
+        d.map_off = (long long)arena;
+        d.k1_off = d.k2_off = d.pack_off = -1;
+        arena += (size_t)d.map_pitch * oh;
+        src_off[(size_t)t] = src;
+        src += (size_t)oh * ow;
+        max_oh = std::max(max_oh, oh);
+        max_ow = std::max(max_ow, ow);
+        if (batch) {
+            if (a->img_rows < 2 || h > a->img_rows - 1 || (oh + h - 1) % a->img_rows != 0) return bad("img_rows does not fit a map");
+            const int nbt = (oh + h - 1) / a->img_rows;
+            if (t > 0 && nbt != n_img) return bad("the maps' stacks differ in their number of images");
+            n_img = nbt;
+            max_px = std::max(max_px, (long long)(a->img_rows - h + 1) * ow);
+        }
+    }
+    if (arena > (64ull << 20)) return bad("more than 2^26 floats of maps");
+    const size_t n_ints = (size_t)n * (size_t)n_img;
+    const size_t capacity = (size_t)a->capacity;
+    if (ext) {
+        if (!a->keys || !a->ext_hits || (size_t)a->n_ints < n_ints) return bad("the extremum routes need keys and ext_hits of 2 * n_ints");
+    } else if (!a->records || !a->count || !a->raw || !a->trivial || (size_t)a->n_ints < n_ints || a->capacity < a->hit_cap) {
+        return bad("records (capacity >= hit_cap), count, raw and trivial (n_ints each) are needed");
+    }
+    // the grids and capacities of the route
+    const PeakGrid grd = peak_grid_dims(max_oh, max_ow, n, route == MTM_PEAK_SEGMENTS ? kPkSparseRows : kPkRows);
+    const unsigned long long hit_cap = (unsigned long long)a->hit_cap;
+    unsigned long long n_lists = 0, cap_t = 0;
+    size_t flag_rstride = 0, flag_tstride = 0;
+    if (route == MTM_PEAK_SEGMENTS) {
+        n_lists = (unsigned long long)grd.z * grd.x;
+        cap_t = peak_list_cap(hit_cap, n_lists);
+        flag_rstride = grd.x;
+        flag_tstride = (size_t)max_oh * grd.x;
+        if (!a->flags || !a->list_counts || (unsigned long long)a->list_cap < n_lists) return bad("flags and list_counts (one per list) are needed");
+    }
+    unsigned blocks = 0, hash_mask = 0;
+    size_t n_judged = 0;
+    if (verify) {
+        if (a->cand_cap < 1 || a->cand_cap > kCandListMax || a->cand_count < 0 || a->n_cands < 0 || (a->n_cands > 0 && !a->cands))
+            return bad("the candidate list (cand_cap in 1 .. 2^20)");
+        n_judged = (size_t)std::min(a->cand_count, a->cand_cap);
+        if ((size_t)a->n_cands < n_judged) return bad("fewer candidate records than min(cand_count, cand_cap)");
+        for (size_t i = 0; i < n_judged; ++i) {
+            const mtm_hit& h = a->cands[i];
+            if (h.templ_idx < 0 || h.templ_idx >= n || h.x < 0 || h.y < 0 || h.x >= td[(size_t)h.templ_idx].ow ||
+                h.y >= td[(size_t)h.templ_idx].oh)
+                return bad("a candidate outside its map");
+        }
+        blocks = verify_blocks(std::max<long long>(a->hit_cap, a->cand_cap));
+        if (route == MTM_PEAK_VERIFY_HASH) hash_mask = (unsigned)(cand_hash_slots(a->cand_cap) - 1);
+    }
+    const int nbk = route == MTM_PEAK_EXTREMUM ? extremum_blocks() : route == MTM_PEAK_EXTREMUM_BATCH ? extremum_batch_blocks(max_px) : 0;
+    // peak_dbg: [table][map list][count | per-map ints][records][maps][flags][candidates][hash][list counters][lists][keys]
+    size_t total = 0;
+    const auto take = [&](size_t bytes) {
+        const size_t off = total;
+        total += round_up(std::max<size_t>(bytes, 16), 256);
+        return off;
+    };
+    const size_t o_td = take(sizeof(TemplDev) * (size_t)n), o_tl = take(sizeof(int) * (size_t)n);
+    const size_t hdr_bytes = 16 + sizeof(int) * n_ints;
+    const size_t o_hdr = take(hdr_bytes), o_rec = take(sizeof(mtm_hit) * capacity), o_maps = take(sizeof(float) * arena);
+    const size_t flag_bytes = (size_t)n * flag_tstride;
+    const size_t o_flags = take(flag_bytes);
+    const size_t o_cand = take(16 + sizeof(mtm_hit) * (size_t)std::max<int64_t>(verify ? a->cand_cap : 0, 1));
+    const size_t o_hash = take(hash_mask ? cand_hash_bytes(hash_mask) : 0);
+    const size_t cnt_bytes = sizeof(unsigned long long) * (size_t)n_lists;
+    const size_t o_cnt = take(cnt_bytes), o_lists = take(sizeof(mtm_hit) * (size_t)cap_t * (size_t)n_lists);
+    const size_t key_bytes = sizeof(unsigned long long) * 2 * n_ints;
+    const size_t o_keys = take(key_bytes);
+    HIPC(hipSetDevice(c->device));
+    MTMC(c->peak_dbg.ensure(total));
+    uint8_t* b = c->peak_dbg.as<uint8_t>();
+    // the arena as the device will hold it: the pattern, then the maps row by row (holes: flagged segments only)
+    std::vector<uint8_t> stage(sizeof(float) * arena, (uint8_t)a->pattern_byte);
+    for (int t = 0; t < n; ++t) {
+        const TemplDev& d = td[(size_t)t];
+        for (int y = 0; y < d.oh; ++y) {
+            const float* from = a->maps + src_off[(size_t)t] + (size_t)y * d.ow;
+            uint8_t* to = stage.data() + sizeof(float) * ((size_t)d.map_off + (size_t)y * d.map_pitch);
+            if (route == MTM_PEAK_SEGMENTS && a->holes) {
+                for (int sx = 0; sx * kPkCols < d.ow; ++sx)
+                    if (a->flags[(size_t)t * flag_tstride + (size_t)y * flag_rstride + (size_t)sx])
+                        std::memcpy(to + sizeof(float) * (size_t)sx * kPkCols, from + (size_t)sx * kPkCols,
+                                    sizeof(float) * (size_t)std::min(kPkCols, d.ow - sx * kPkCols));
+            } else {
+                std::memcpy(to, from, sizeof(float) * (size_t)d.ow);
+            }
+        }
+    }
+    std::vector<int> tl((size_t)n);
+    for (int t = 0; t < n; ++t) tl[(size_t)t] = t;
+    HIPC(hipMemcpyAsync(b + o_td, td.data(), sizeof(TemplDev) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(b + o_tl, tl.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemsetAsync(b + o_hdr, 0, hdr_bytes, c->stream));
+    if (!ext && capacity) HIPC(hipMemcpyAsync(b + o_rec, a->records, sizeof(mtm_hit) * capacity, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(b + o_maps, stage.data(), stage.size(), hipMemcpyHostToDevice, c->stream));
+    const TemplDev* dtd = reinterpret_cast<const TemplDev*>(b + o_td);
+    const int* dtl = reinterpret_cast<const int*>(b + o_tl);
+    const float* dmaps = reinterpret_cast<const float*>(b + o_maps);
+    unsigned long long* dcount = reinterpret_cast<unsigned long long*>(b + o_hdr);
+    int* dints = reinterpret_cast<int*>(b + o_hdr + 16);
+    mtm_hit* drec = reinterpret_cast<mtm_hit*>(b + o_rec);
+    unsigned long long* dkeys = reinterpret_cast<unsigned long long*>(b + o_keys);
+    const dim3 grid(grd.x, grd.y, grd.z);
+    if (route == MTM_PEAK_SCAN) {
+        hipLaunchKernelGGL(peaks_kernel, grid, dim3(256), 0, c->stream, dmaps, dtd, dtl, mode_min ? 1 : 0, a->thr, a->border, drec,
+                           hit_cap, dcount, dints);
+    } else if (route == MTM_PEAK_SCAN_BATCH) {
+        hipLaunchKernelGGL(peaks_batch_kernel, grid, dim3(256), 0, c->stream, dmaps, dtd, dtl, mode_min ? 1 : 0, a->thr, a->border,
+                           drec, hit_cap, dcount, dints, a->img_rows, n);
+    } else if (route == MTM_PEAK_SEGMENTS) {
+        unsigned long long* counts_t = reinterpret_cast<unsigned long long*>(b + o_cnt);
+        mtm_hit* hits_t = reinterpret_cast<mtm_hit*>(b + o_lists);
+        HIPC(hipMemcpyAsync(b + o_flags, a->flags, flag_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPC(hipMemsetAsync(counts_t, 0, round_up(cnt_bytes, 256), c->stream));
+        hipLaunchKernelGGL(peaks_sparse_kernel, grid, dim3(256), 0, c->stream, dmaps, dtd, dtl, mode_min ? 1 : 0, a->thr, a->border,
+                           hits_t, cap_t, counts_t, dints, b + o_flags, (int)flag_tstride, (int)flag_rstride, a->holes ? 1 : 0);
+        hipLaunchKernelGGL(compact_hits_kernel, dim3((unsigned)n_lists), dim3(256), 0, c->stream, hits_t, cap_t, counts_t,
+                           (int)n_lists, drec, hit_cap, dcount);
+    } else if (verify) {
+        const unsigned long long cc[2] = {(unsigned long long)a->cand_count, 0ull};
+        unsigned long long* dcc = reinterpret_cast<unsigned long long*>(b + o_cand);
+        const mtm_hit* dcands = reinterpret_cast<const mtm_hit*>(b + o_cand + 16);
+        HIPC(hipMemcpyAsync(dcc, cc, sizeof(cc), hipMemcpyHostToDevice, c->stream));
+        if (n_judged) HIPC(hipMemcpyAsync(b + o_cand + 16, a->cands, sizeof(mtm_hit) * n_judged, hipMemcpyHostToDevice, c->stream));
+        if (route == MTM_PEAK_VERIFY_HASH) {
+            unsigned long long* keys = reinterpret_cast<unsigned long long*>(b + o_hash);
+            int* vals = reinterpret_cast<int*>(keys + (size_t)hash_mask + 1);
+            HIPC(hipMemsetAsync(keys, 0, cand_hash_key_bytes(hash_mask), c->stream));
+            hipLaunchKernelGGL(cand_hash_insert_kernel, dim3(blocks), dim3(256), 0, c->stream, dcands, dcc,
+                               (unsigned long long)a->cand_cap, keys, vals, hash_mask);
+            hipLaunchKernelGGL(verify_hash_kernel, dim3(blocks), dim3(256), 0, c->stream, dtd, mode_min ? 1 : 0, a->border, dcands, dcc,
+                               (unsigned long long)a->cand_cap, keys, vals, hash_mask, drec, hit_cap, dcount, dints, a->thr_q);
+        } else {
+            hipLaunchKernelGGL(verify_peaks_kernel, dim3(blocks), dim3(256), 0, c->stream, dmaps, dtd, mode_min ? 1 : 0, a->border,
+                               dcands, dcc, (unsigned long long)a->cand_cap, drec, hit_cap, dcount, dints, a->thr_q);
+        }
+    } else {
+        HIPC(hipMemsetAsync(dkeys, 0, key_bytes, c->stream));
+        if (route == MTM_PEAK_EXTREMUM)
+            hipLaunchKernelGGL(extremum_kernel, dim3(nbk, n), dim3(256), 0, c->stream, dmaps, dtd, nbk, dkeys);
+        else
+            hipLaunchKernelGGL(extremum_batch_kernel, dim3(nbk, n, n_img), dim3(256), 0, c->stream, dmaps, dtd, a->img_rows, nbk, dkeys);
+    }
+    HIPC(hipGetLastError());
+    std::vector<uint8_t> hdr(hdr_bytes);
+    HIPC(hipMemcpyAsync(hdr.data(), b + o_hdr, hdr_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (!ext && capacity) HIPC(hipMemcpyAsync(a->records, b + o_rec, sizeof(mtm_hit) * capacity, hipMemcpyDeviceToHost, c->stream));
+    if (n_lists) HIPC(hipMemcpyAsync(a->list_counts, b + o_cnt, cnt_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (ext) HIPC(hipMemcpyAsync(a->keys, dkeys, key_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    if (ext) {
+        for (size_t i = 0; i < n_ints; ++i) {
+            const TemplDev& d = td[i % (size_t)n];
+            a->ext_hits[2 * i] = decode_extremum_key(a->keys[2 * i], false, (int)(i % (size_t)n), d.ow, d.cols, d.rows);
+            a->ext_hits[2 * i + 1] = decode_extremum_key(a->keys[2 * i + 1], true, (int)(i % (size_t)n), d.ow, d.cols, d.rows);
+        }
+    } else {
+        unsigned long long count = 0;
+        std::memcpy(&count, hdr.data(), sizeof(count));
+        *a->count = count;
+        std::memcpy(a->raw, hdr.data() + 16, sizeof(int) * n_ints);
+        for (size_t i = 0; i < n_ints; ++i) {
+            const TemplDev& d = td[i % (size_t)n];
+            const int f = a->raw[i];
+            a->trivial[i] = verify ? fused_count_trivial(f, d.oh, d.ow) : batch ? f == 0 : scan_flags_trivial((unsigned)f);
+        }
+    }
+    const int64_t info[8] = {(int64_t)grd.x, (int64_t)grd.y, (int64_t)grd.z, (int64_t)cap_t, (int64_t)n_lists, (int64_t)blocks,
+                             hash_mask ? (int64_t)hash_mask + 1 : 0, (int64_t)nbk};
+    std::memcpy(a->info, info, sizeof(info));
     return MTM_OK;
 }
 

@@ -25,6 +25,7 @@
 #include "mtm_templates_params.h"
 #include "mtm_internal.h"
 #include "mtm_route.h"
+#include "mtm_peak_sizing.h"
 
 struct ncclComm;
 
@@ -189,6 +190,7 @@ struct mtm_ctx {
     long long nms_device_min = 4096;        // CallRoute::nms: fewer peaks than this are pruned on the host (as fast)
     DevBuf nms_buf;
     DevBuf nms_dbg;             // mtm_debug_device_nms: [the count][the records] of the list under test
+    DevBuf peak_dbg;            // mtm_debug_peak_pass: the table, maps, flags, lists and counters of the maps under test
     // segment flags (MTM_SPARSE_MAPS, default 1): the route of a call on dense maps (candidate list overflowed recently)
     // when every class runs the lean MFMA epilogue - maps in memory, one flag per row segment that holds something above the
     // threshold, peaks_sparse_kernel over the flagged segments instead of the full scan (MfmaParams::seg_flags)

@@ -7,6 +7,7 @@
 
 #include "mtm_kernels.h"
 #include "../../include/mtm_hip.h"
+#include "mtm_peak_sizing.h"
 
 namespace mtm {
 
@@ -106,8 +107,7 @@ __device__ __forceinline__ float mf_order_float(uint32_t o) {
     return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
 }
 
-// rows of a score map for the 3x3 scans (peaks_kernel, refine_scan_kernel)
-constexpr int kPkCols = 256, kPkRows = 32;
+// rows of a score map for the 3x3 scans (peaks_kernel, refine_scan_kernel); kPkCols, kPkRows: mtm_peak_sizing.h
 
 __device__ __forceinline__ void peaks_load_row(const float* __restrict__ m, int pitch, int oh, int ow, int y, int xb,
                                                int lane, bool mode_min, float padv, float (&v)[4], float& hl,

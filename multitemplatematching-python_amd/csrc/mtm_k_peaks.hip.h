@@ -157,7 +157,7 @@ constexpr int kPkStage = 64;        // records staged per wave
 // rows per wave: flagged rows cluster (bright regions), and a wave works through its flagged rows one memory latency after
 // the other - with the 32-row strips of the full scan the pass took as long as the fully flagged strips did, four
 // generations of them: 0.30 ms; the rows of the next flagged row are requested before the current one is evaluated
-constexpr int kPkSparseRows = 8;
+// (kPkSparseRows = 8: mtm_peak_sizing.h)
 __global__ __launch_bounds__(256) void peaks_sparse_kernel(const float* __restrict__ maps, const TemplDev* __restrict__ td,
                                                            const int* __restrict__ tlist, int mode_min, float thr, int border,
                                                            mtm_hit* __restrict__ hits_t, unsigned long long cap_t,

@@ -597,7 +597,7 @@ int plan_placement(const mtm_ctx* c, Placement& P) {
         d.cls = t.cls;
         d.oh = c->rows - t.rows + 1;
         d.ow = c->cols - t.cols + 1;
-        d.map_pitch = (int)round_up((size_t)d.ow, 4);
+        d.map_pitch = map_pitch_of(d.ow);
         d.map_off = P.maps.take((size_t)d.map_pitch * d.oh);
         // float64 weights: the float64 / naive kernels, and the exact re-scoring behind the bf16 kernel
         const size_t plane = (size_t)t.chans * t.rows * t.cols;

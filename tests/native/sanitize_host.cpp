@@ -19,6 +19,7 @@
 
 #include "../../multitemplatematching-python_amd/csrc/mtm_internal.h"
 #include "../../multitemplatematching-python_amd/csrc/mtm_nms_core.h"
+#include "../../multitemplatematching-python_amd/csrc/mtm_peak_sizing.h"
 
 using namespace mtm;
 
@@ -542,6 +543,47 @@ static void test_nms_grid(std::mt19937& rng) {
     }
 }
 
+// ---- the sizing rules of the peak pass (mtm_peak_sizing.h), one check per rule --------------------------------------------
+static void test_peak_sizing(std::mt19937& rng) {
+    CHECK(map_pitch_of(1) == 4 && map_pitch_of(4) == 4 && map_pitch_of(5) == 8 && map_pitch_of(513) == 516);
+    CHECK(peak_grid_dims(130, 513, 33, kPkRows).x == 3 && peak_grid_dims(130, 513, 33, kPkRows).y == 2 &&
+          peak_grid_dims(130, 513, 33, kPkRows).z == 33 && peak_grid_dims(130, 513, 33, kPkSparseRows).y == 5);
+    CHECK(peak_list_cap(2048, 4) == 256 && peak_list_cap(1 << 20, 4) == (1 << 17) && verify_blocks(1) == 1 && verify_blocks(257) == 2);
+    CHECK(cand_hash_slots(1) == 1024 && cand_hash_slots(512) == 1024 && cand_hash_slots(513) == 2048);
+    CHECK(extremum_blocks() == 256 && extremum_batch_blocks(1) == 1 && extremum_batch_blocks(4097) == 2);
+    for (int rep = 0; rep < 2000; ++rep) {
+        // the grid covers every pixel of the largest map: the last strip holds its last row and column, no strip is empty
+        const int max_oh = 1 + (int)(rng() % (rep % 3 ? 300u : 65535u)), max_ow = 1 + (int)(rng() % (rep % 3 ? 1100u : 65535u));
+        const int n_maps = 1 + (int)(rng() % 4096u);
+        for (int strip_rows : {kPkRows, kPkSparseRows}) {
+            const PeakGrid g = peak_grid_dims(max_oh, max_ow, n_maps, strip_rows);
+            CHECK((long long)g.x * kPkCols >= max_ow && (long long)(g.x - 1) * kPkCols < max_ow);
+            CHECK((long long)g.y * 4 * strip_rows >= max_oh && (long long)(g.y - 1) * 4 * strip_rows < max_oh);
+            CHECK(g.z == (unsigned)n_maps && g.y <= 65535u && g.z <= 65535u);
+        }
+        // the lists: within 64 MB all together, or at the floor of 256 records; never more than an eighth of the capacity
+        // unless at the floor
+        const unsigned long long hit_cap = rep % 4 == 0 ? 1 + rng() % 4096u : 1 + (((unsigned long long)rng() << 8) % (1ull << 26));
+        const unsigned long long n_lists = 1 + rng() % (rep % 5 == 0 ? 4096u : 200u);
+        const unsigned long long cap_t = peak_list_cap(hit_cap, n_lists);
+        CHECK(cap_t >= 256 && (cap_t == 256 || (cap_t * n_lists * sizeof(mtm_hit) <= (64ull << 20) && cap_t <= hit_cap / 8)));
+        CHECK(cap_t == 256 || cap_t == hit_cap / 8 || cap_t == (64ull << 20) / sizeof(mtm_hit) / n_lists);
+        // the verifiers: one thread per record of a candidate list of min(hit_cap, 4096 * 256) records
+        const long long hc = (long long)hit_cap, cand_cap = std::min<long long>(hc, 4096ll * 256);
+        CHECK((long long)verify_blocks(hc) * 256 >= cand_cap && verify_blocks(hc) <= 4096u && verify_blocks(hc) >= 1u);
+        CHECK(((long long)verify_blocks(hc) - 1) * 256 < hc);
+        // the table: a power of two, at least 1024 slots and twice the list; the keys are what is cleared, the values follow
+        const size_t hsz = cand_hash_slots(cand_cap);
+        CHECK((hsz & (hsz - 1)) == 0 && hsz >= 1024 && hsz >= 2 * (size_t)cand_cap && (hsz == 1024 || hsz / 2 < 2 * (size_t)cand_cap));
+        const unsigned mask = (unsigned)(hsz - 1);
+        CHECK(cand_hash_key_bytes(mask) == hsz * 8 && cand_hash_bytes(mask) == hsz * 12);
+        // the extremum launches: at least one work-group, at most 256, one pixel per thread until then
+        const long long px = 1 + (long long)(rng() % (rep % 2 ? 5000u : 4000000u));
+        const int nb = extremum_batch_blocks(px);
+        CHECK(nb >= 1 && nb <= 256 && (nb == 256 || (long long)nb * 4096 >= px));
+    }
+}
+
 // ---- the host-only pieces of fm_end (mtm_api.hip): the 3x3 test of the candidate list, the trivial-map rule, the ladder
 
 // one case of verify_candidates_3x3 against brute force over the maps: `maps[t]` the scores of an oh[t] x ow[t] map, the list
@@ -611,6 +653,24 @@ static void test_verify_candidates(std::mt19937& rng) {
         const float thr = 0.25f * (float)(rng() % 5) + (rng() % 3 == 0 ? -0.3f : 0.1f);
         verify_case(oh, ow, maps, mode_min, mode_min ? -thr : thr, (rep & 2) ? 0.0f : -INFINITY, rng, hk, hv);
     }
+    // NaN: a NaN candidate is never a hit and never beats a neighbour (the rule of peaks_kernel: fmaxf ignores it), and it
+    // keeps the template's count below oh * ow - the map is not trivial
+    for (float padv : {0.0f, -INFINITY})
+        for (int mode_min = 0; mode_min < 2; ++mode_min) {
+            const int oh = 3, ow = 4;
+            const float s = mode_min ? -1.0f : 1.0f;
+            std::vector<mtm_hit> list;
+            for (int y = 0; y < oh; ++y)
+                for (int x = 0; x < ow; ++x) list.push_back(mtm_hit{0, x, y, 2, 2, s * 0.75f});
+            list[5].score = NAN;                     // (1, 1): every other pixel has it as a neighbour or lies beside one that has
+            list[0].score = s * 0.875f;              // (0, 0) beats (0, 1) and (1, 0); its NaN neighbour does not beat it
+            std::shuffle(list.begin(), list.end(), rng);
+            std::vector<mtm_hit> hits;
+            int flag = 0;
+            verify_candidates_3x3(list.data(), list.size(), MapDims{&oh, &ow, sizeof(int)}, mode_min != 0, 0.5f, padv, hk, hv, hits, &flag);
+            CHECK((int)hits.size() == oh * ow - 3 && flag == oh * ow - 3 && !fused_count_trivial(flag, oh, ow));
+            for (const mtm_hit& h : hits) CHECK(h.score == h.score && !(h.x == 1 && h.y == 0) && !(h.x == 0 && h.y == 1));
+        }
     for (float padv : {0.0f, -INFINITY}) {
         // the empty list
         std::vector<mtm_hit> hits;
@@ -939,6 +999,7 @@ int main() {
     test_ladder();
     test_track_plan();
     test_nms_grid(rng);
+    test_peak_sizing(rng);
     test_host(rng);
     test_group(rng);
     // two groups driven from two caller threads at once (each group is single-caller; the library must not share state)

@@ -49,6 +49,22 @@ def test_class_tilings_record_matches_the_header(lib):
     assert list(out) == [-7] * n_fields
 
 
+def test_peak_pass_block_matches_the_header(lib):
+    """mtm_debug_peak_pass (test support): the binding's argument block has the header's fields in the header's order, the
+    routes carry the header's numbers, and the entry point refuses null arguments."""
+    hdr = open(os.path.join(ROOT, "include", "mtm_hip.h")).read()
+    body = hdr[hdr.index("typedef struct mtm_peak_pass {"):hdr.index("} mtm_peak_pass;")]
+    fields = [f for line in body.splitlines()[1:] for f in re.findall(r"\b([a-z_]+)\s*[,;]", line)]
+    assert fields == [f[0] for f in lib.MtmPeakPass._fields_], fields
+    assert ctypes.sizeof(lib.MtmPeakPass) == 10 * 4 + 19 * 8 == 192          # (no padding: ten 4-byte fields, then 8-byte ones)
+    for k, name in enumerate(("SCAN", "SCAN_BATCH", "SEGMENTS", "VERIFY_MAPS", "VERIFY_HASH", "EXTREMUM", "EXTREMUM_BATCH")):
+        assert int(re.search(r"#define\s+MTM_PEAK_%s\s+(\d+)" % name, hdr).group(1)) == getattr(lib, "PEAK_" + name) == k
+    assert len(lib.PEAK_INFO_FIELDS) == 8 and "info[8]" in hdr
+    assert lib.load().mtm_debug_peak_pass(None, None) == -1
+    a = lib.MtmPeakPass()
+    assert lib.load().mtm_debug_peak_pass(None, ctypes.byref(a)) == -1 and b"mtm_debug_peak_pass" in lib.load().mtm_last_error()
+
+
 def test_struct_layout(lib):
     assert ctypes.sizeof(lib.MtmHit) == 24
     assert ctypes.sizeof(lib.MtmTempl) == 48

@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -319,6 +319,40 @@ typedef struct mtm_peak_pass {
     int64_t*       info;
 } mtm_peak_pass;
 int         mtm_debug_peak_pass(mtm_ctx* ctx, const mtm_peak_pass* args);
+/* Test support (added under ABI 9; needs no templates on the context and leaves its image, template set and options as
+ * they are).  The fused window statistics of single-channel uint8 images (stats_u8_kernel) on an image the caller hands
+ * over, through the very function the search calls launch it with: window h x w (w <= 768, w h 255^2 < 2^32) over the
+ * rows x cols pixels of `image` (tightly packed), num_type 0 / 1 / 2 (1: the window's mean is taken out - the TM_CCOEFF
+ * methods), row units [sb0, sb1) of 8 output rows each (sb1 < 0 or beyond the last unit: up to the last), in form `form`
+ * (output rows per work-group: 1 = 8 rows, 2 = 4 rows - MTM_STATS_FORMS of them; 0 = the launcher's choice
+ * for this launch).  Everything lives in a buffer of the entry's own that is filled with pattern_byte first: the image
+ * plane as the context holds it (pitch = cols + 512 rounded up to 64, zero padding), the raw copy of the image, the
+ * statistics planes (pitch = ow rounded up to 4, oh rows) and the block records (4 doubles per 16 output columns and row).
+ * lay_r1 > lay_r0 (cols a multiple of 4): the launch reads the raw copy instead and converts image rows [lay_r0, lay_r1)
+ * into the uint8 plane and its int8 view on the way, as the banded upload has it do - both planes then start out as
+ * pattern_byte.  tail_s in 1 .. h - 1 (needs blk and blkq): the tail boxes of split tail_s.  zero_header != 0: the launch
+ * clears the 16-byte header, which starts out as pattern_byte too.
+ * Results, each optional (NULL = not wanted, and for t0 / sum2 / sq / rsq / blk the kernel is told so): t0, sum2, sq, rsq -
+ * st_pitch * oh doubles; blk, blkq - 4 * blk_pitch * oh doubles; u8, u8b - rows * pitch bytes of the two planes; header - 2
+ * words; info[8] = {st_pitch, blk_pitch, plane pitch, the form that ran, grid x, grid y, the device's compute units (what the launcher's choice goes by), the
+ * launch's time in nanoseconds between two events}. */
+#define MTM_STATS_FORMS 2
+typedef struct mtm_window_stats {
+    int32_t        rows, cols, h, w, num_type, form;
+    int32_t        tail_s, sb0, sb1, lay_r0, lay_r1, pattern_byte, zero_header, reserved;
+    const uint8_t* image;
+    double*        t0;
+    double*        sum2;
+    double*        sq;
+    double*        rsq;
+    double*        blk;
+    double*        blkq;
+    uint8_t*       u8;
+    uint8_t*       u8b;
+    uint64_t*      header;
+    int64_t*       info;
+} mtm_window_stats;
+int         mtm_debug_window_stats(mtm_ctx* ctx, const mtm_window_stats* args);
 /* Page-locked host memory for pixel buffers (optional).  The reference's caller hands over whatever numpy holds
  * (MTM/__init__.py:247 `image`) - pageable memory, which the runtime stages through its own pinned buffers while the
  * upload call blocks.  An image kept in memory from mtm_host_alloc crosses PCIe as a plain DMA transfer behind the call

@@ -90,6 +90,22 @@ class MtmPeakPass(ctypes.Structure):
                 ("list_cap", ctypes.c_int64), ("info", ctypes.c_void_p)]
 
 
+# mtm_debug_window_stats: the forms of the fused uint8 statistics kernel (output rows per work-group; numbered from 1) and the argument block (mtm_window_stats)
+STATS_FORMS = (8, 4)
+STATS_INFO_FIELDS = ("st_pitch", "blk_pitch", "pitch", "form", "grid_x", "grid_y", "n_cus", "kernel_ns")
+
+
+class MtmWindowStats(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("num_type", ctypes.c_int32), ("form", ctypes.c_int32),
+                ("tail_s", ctypes.c_int32), ("sb0", ctypes.c_int32), ("sb1", ctypes.c_int32), ("lay_r0", ctypes.c_int32),
+                ("lay_r1", ctypes.c_int32), ("pattern_byte", ctypes.c_int32), ("zero_header", ctypes.c_int32),
+                ("reserved", ctypes.c_int32),
+                ("image", ctypes.c_void_p), ("t0", ctypes.c_void_p), ("sum2", ctypes.c_void_p), ("sq", ctypes.c_void_p),
+                ("rsq", ctypes.c_void_p), ("blk", ctypes.c_void_p), ("blkq", ctypes.c_void_p), ("u8", ctypes.c_void_p),
+                ("u8b", ctypes.c_void_p), ("header", ctypes.c_void_p), ("info", ctypes.c_void_p)]
+
+
 # every symbol include/mtm_hip.h declares: (restype, argtypes)
 _P = ctypes.POINTER
 SYMBOLS = {
@@ -111,6 +127,7 @@ SYMBOLS = {
                                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, _P(ctypes.c_int64),
                                             _P(ctypes.c_int64)]),
     "mtm_debug_peak_pass": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "mtm_debug_window_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_set_image": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
     "mtm_set_image_downscaled": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -574,6 +591,43 @@ class Context(_RecordMemo):
         return {"records": records, "count": int(count[0]), "raw": raw.reshape(shape), "trivial": trivial.reshape(shape),
                 "keys": keys.reshape(shape + (2,)), "ext_hits": ext_hits.reshape(shape + (2,)), "list_counts": list_counts,
                 "info": dict(zip(PEAK_INFO_FIELDS, (int(v) for v in info)))}
+
+    def debug_window_stats(self, image, h, w, num_type, form=0, planes=("t0", "sum2", "sq", "rsq", "blk"), tail_s=0, units=None,
+                           convert_rows=None, zero_header=True, pattern=0xA5):
+        """Test support (mtm_debug_window_stats): the fused window statistics of single-channel uint8 images on the 2-D uint8
+        array `image`, window h x w, num_type 0 / 1 / 2, launched the way the search calls launch them - in form `form` (1 ..
+        len(STATS_FORMS); 0: the launcher's choice).  planes: which of t0, sum2, sq, rsq, blk the kernel is asked for (tail_s
+        > 0 adds blkq, the tail boxes of that split); units: the (first, end) range of 8-row units, all by default;
+        convert_rows: (r0, r1) image rows the launch converts from the raw copy on the way.  Every buffer starts out as the
+        byte `pattern`.
+        -> dict: the wanted planes ((oh, st_pitch) float64; blk / blkq (oh, blk_pitch, 4)), u8 / u8b ((rows, pitch) uint8),
+        header (2 uint64), info (STATS_INFO_FIELDS)."""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        assert image.ndim == 2
+        rows, cols = image.shape
+        oh, ow = rows - h + 1, cols - w + 1
+        st_pitch = (ow + 3) // 4 * 4
+        blk_pitch = (st_pitch + 15) // 16
+        pitch = (cols + 512 + 63) // 64 * 64
+        a = MtmWindowStats()
+        a.rows, a.cols, a.h, a.w, a.num_type, a.form = rows, cols, int(h), int(w), int(num_type), int(form)
+        a.tail_s, a.pattern_byte, a.zero_header = int(tail_s), int(pattern), int(bool(zero_header))
+        a.sb0, a.sb1 = (0, -1) if units is None else (int(units[0]), int(units[1]))
+        a.lay_r0, a.lay_r1 = (0, 0) if convert_rows is None else (int(convert_rows[0]), int(convert_rows[1]))
+        a.image = image.ctypes.data
+        out = {}
+        for name in tuple(planes) + (("blkq",) if tail_s else ()):
+            shape = (max(oh, 0), blk_pitch, 4) if name in ("blk", "blkq") else (max(oh, 0), st_pitch)
+            out[name] = np.zeros(shape, dtype=np.float64)
+            setattr(a, name, out[name].ctypes.data)
+        out["u8"], out["u8b"] = np.zeros((rows, pitch), dtype=np.uint8), np.zeros((rows, pitch), dtype=np.uint8)
+        out["header"] = np.zeros(2, dtype=np.uint64)
+        info = np.zeros(8, dtype=np.int64)
+        a.u8, a.u8b, a.header, a.info = out["u8"].ctypes.data, out["u8b"].ctypes.data, out["header"].ctypes.data, info.ctypes.data
+        check(self._lib.mtm_debug_window_stats(self._h, ctypes.byref(a)), "mtm_debug_window_stats")
+        out["info"] = dict(zip(STATS_INFO_FIELDS, (int(v) for v in info)))
+        assert (out["info"]["st_pitch"], out["info"]["blk_pitch"], out["info"]["pitch"]) == (st_pitch, blk_pitch, pitch)
+        return out
 
     def set_image(self, image, downscale=1):
         """Upload the search image; `downscale` > 1 area-averages it by that integer factor on the

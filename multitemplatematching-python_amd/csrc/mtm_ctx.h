@@ -191,6 +191,7 @@ struct mtm_ctx {
     DevBuf nms_buf;
     DevBuf nms_dbg;             // mtm_debug_device_nms: [the count][the records] of the list under test
     DevBuf peak_dbg;            // mtm_debug_peak_pass: the table, maps, flags, lists and counters of the maps under test
+    DevBuf stats_dbg;           // mtm_debug_window_stats: the image, its planes, the statistics planes and records under test
     // segment flags (MTM_SPARSE_MAPS, default 1): the route of a call on dense maps (candidate list overflowed recently)
     // when every class runs the lean MFMA epilogue - maps in memory, one flag per row segment that holds something above the
     // threshold, peaks_sparse_kernel over the flagged segments instead of the full scan (MfmaParams::seg_flags)

@@ -1,6 +1,7 @@
 // Window statistics kernels (exact box sums and the template-independent part of the normalisation per output pixel) and the sum I^2 M helpers of masked classes.  Launched by mtm_launch.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cfloat>
 #include <cstdint>
 
@@ -108,6 +109,17 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan_u32(uint32_t x) {
     return s;
 }
 
+// The value of the lane D (1 or 2) away in this lane's quad: what a min / max reduction over a quad needs - one DPP move
+// (quad_perm) instead of a trip through the LDS crossbar.  All lanes active.
+__device__ __forceinline__ uint32_t lane_group_xchg_u32(uint32_t x, int D) {
+    return D == 1 ? (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xf, 0xf, false)      // quad_perm:[1,0,3,2]
+                  : (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xf, 0xf, false);     // quad_perm:[2,3,0,1]
+}
+__device__ __forceinline__ double lane_group_xchg_f64(double x, int D) {
+    const uint32_t lo = lane_group_xchg_u32((uint32_t)__double2loint(x), D), hi = lane_group_xchg_u32((uint32_t)__double2hiint(x), D);
+    return __hiloint2double((int)hi, (int)lo);
+}
+
 // Horizontal box sums of one uint8 image row per work-group, through inclusive prefix sums held in
 // LDS (uint32, exact): fully coalesced global reads and writes.  Element i of the row is owned by
 // thread i % 256 in round i / 256; each round is a 256-wide block scan (wave shuffles + one LDS
@@ -166,21 +178,25 @@ __global__ __launch_bounds__(256) void hsum_u8_kernel(const uint8_t* __restrict_
 // ---------------------------------------------------------------------------------------------
 // Fused window statistics for single-channel uint8 images: one kernel, no intermediate planes.
 // A work-group owns a strip of `owg` output columns (owg + w - 1 <= 1024 image columns) x
-// kStatBand4 output rows; a thread owns FOUR adjacent image columns: one aligned dword load per
-// image row, four 8-byte statistics per plane and output row (two 16-byte stores).  Column sums over
-// the template height (C1 = sum I, C2 = sum I^2 per image column) are kept in registers and slid down
-// one row at a time (two dword loads per output row, requested one iteration ahead); the window
-// sums are differences of the exclusive prefix scan of the column sums over the strip, held in LDS
-// (uint32, exact: differences are taken modulo 2^32 and the true window sums fit).  One block scan
-// (thread-local prefix, DPP wave scan, one LDS exchange) and two barriers serve 4 x 256 columns.
+// `rows_wg` output rows (the launcher hands out ranges of row units of kStatBand4 rows); a thread owns FOUR adjacent image
+// columns: one aligned dword load per image row, four
+// 8-byte statistics per plane and output row.  Column sums over the template height (C1 = sum I,
+// C2 = sum I^2 per image column) are kept in registers and slid down one row at a time (two loads
+// per output row, requested one iteration ahead); the window sums are differences of the exclusive
+// prefix scan of the column sums over the strip, held in LDS (uint32, exact: differences are taken
+// modulo 2^32 and the true window sums fit).  One block scan (thread-local prefix, DPP wave scan,
+// one LDS exchange of the waves' partials) and two barriers serve the strip's 1024 columns.
 // The launcher uses it for w <= 768 and w * h * 255^2 < 2^32; everything else takes hsum_* +
 // vsum_stats_kernel.
+//
+// The form of a launch (output rows per work-group) changes how the work is spread, never a byte of what is written;
+// stats_u8_form() is the launcher's rule.
 // ---------------------------------------------------------------------------------------------
 #ifndef MTM_STAT_BAND4
 #define MTM_STAT_BAND4 8
 #endif
-constexpr int kStatBand4 = MTM_STAT_BAND4;    // stats_u8_kernel: output rows per work-group
-constexpr int kStatStrip = 1024;               // image columns per work-group (4 per thread)
+constexpr int kStatBand4 = MTM_STAT_BAND4;    // fused statistics kernels: output rows per row unit (the unit of [sb0, sb1) ranges)
+constexpr int kStatStrip = 1024;               // image columns per work-group
 #ifndef MTM_STAT_PRO_BATCH
 #define MTM_STAT_PRO_BATCH 32
 #endif
@@ -200,20 +216,68 @@ struct StatLayout {
                                             // kernel of a banded call does it instead of a fill command between two calls)
 };
 
-template <bool TAIL>
-__global__ __launch_bounds__(256) void stats_u8_kernel(const uint8_t* __restrict__ img, int pitch, int h, int w,
-                                                       int oh, int ow, int owg, double inv_area, int num_type,
-                                                       int want_sq, int want_t, int want_sum2, double* __restrict__ t0,
-                                                       double* __restrict__ sum2, double* __restrict__ sq,
-                                                       int st_pitch, double* __restrict__ rsq = nullptr,
-                                                       int yb_off = 0, double* __restrict__ blk = nullptr,
-                                                       int blk_pitch = 0, StatLayout lay = StatLayout{},
-                                                       double* __restrict__ blkq = nullptr, int tail_s = 0) {
+// The forms of stats_u8_kernel: output rows per work-group (even; the last work-group of a launch may have fewer), numbered
+// from 1 (0 = the launcher's choice: mtm_debug_window_stats).  A form changes how the work is spread, never a byte.
+constexpr int kStatFormRows[] = {kStatBand4, 4};
+constexpr int kStatFormCount = (int)(sizeof(kStatFormRows) / sizeof(kStatFormRows[0]));
+
+// The launcher's rule, from the work-groups a launch has at kStatBand4 rows each (`strips` x `units`) against the chip's
+// compute units (measured: profiles/stats_kernel/forms.md).  A work-group is one chain - the h-row column-sum prologue, then
+// its output rows one after the other - and a launch that gives a compute unit no more than two of them lasts as long as
+// that chain: four rows per work-group shorten it, at the price of one more prologue per eight rows, which a launch that
+// fills the chip several times over cannot afford.  (More rows per work-group and fewer columns per thread were measured
+// too and lose at every size: not kept.)
+inline int stats_u8_form(int strips, int units, int n_cus) {
+    return (long long)strips * units <= 2ll * n_cus ? 2 : 1;
+}
+
+// Work-groups in y of a launch over the row units [sb0, sb1) at rows_wg rows each: counted from the output rows the units
+// really hold (the last unit of an image may be partial), so that every work-group has a first row inside the image - its
+// prologue reads the h image rows from there on, and the raw upload buffer ends with the image.
+inline int stats_u8_grid_y(int sb0, int sb1, int oh, int rows_wg) {
+    const int rows = std::min(sb1 * kStatBand4, oh) - sb0 * kStatBand4;
+    return rows > 0 ? (rows + rows_wg - 1) / rows_wg : 0;
+}
+
+// what a stats_u8_kernel launch takes (launch_stats_u8 fills the last block)
+struct StatU8Args {
+    const uint8_t* img = nullptr;   // the padded uint8 plane - or, with lay.u8b, the raw upload buffer
+    int pitch = 0;                  // its row length (a multiple of 4)
+    int h = 0, w = 0, oh = 0, ow = 0;
+    int num_type = 0, want_sq = 0, want_t = 0, want_sum2 = 0;
+    double* t0 = nullptr;
+    double* sum2 = nullptr;
+    double* sq = nullptr;
+    double* rsq = nullptr;          // 1 / sq (0 where sq is 0): row-multiplexed MFMA classes
+    int st_pitch = 0;
+    double* blk = nullptr;          // ranges per 16-pixel column block
+    double* blkq = nullptr;         // ... of the tail boxes (split tail_s)
+    int blk_pitch = 0, tail_s = 0;
+    int sb0 = 0, sb1 = 0;           // row units to compute
+    StatLayout lay;
+    // derived
+    int owg = 0, rows_wg = kStatBand4;
+    double inv_area = 0.0;
+    double inv_nq[2] = {0.0, 0.0};  // 1 / (rows x columns of the tail box) of even and of odd output rows
+};
+
+template <bool TAIL, bool RSQ>
+__global__ __launch_bounds__(kStatStrip / 4) void stats_u8_kernel(const StatU8Args a) {
+    constexpr int CPT = 4;                   // image columns per thread
+    constexpr int NT = kStatStrip / CPT;     // threads
+    constexpr int NW = NT / 64;              // waves: partials of the block scan
+    constexpr int BL = 16 / CPT;             // lanes per 16-pixel column block
     __shared__ __attribute__((aligned(16))) uint32_t E1[kStatStrip + 4], E2[kStatStrip + 4];   // exclusive prefixes
-    __shared__ uint32_t wsum[TAIL ? 4 : 2][4];
+    constexpr int NS = TAIL ? 4 : 2;         // scans per output row: C1, C2 (, Q1, Q2)
+    __shared__ __attribute__((aligned(16))) uint32_t wsum[NW][NS];
     __shared__ __attribute__((aligned(16))) uint32_t EQ1[TAIL ? kStatStrip + 4 : 4], EQ2[TAIL ? kStatStrip + 4 : 4];   // ... of the tail boxes
-    const int x0 = blockIdx.x * owg, y0 = ((int)blockIdx.y + yb_off) * kStatBand4;   // yb_off: banded launches
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint8_t* __restrict__ img = a.img;
+    const int pitch = a.pitch, h = a.h, w = a.w, ow = a.ow, owg = a.owg, st_pitch = a.st_pitch, tail_s = a.tail_s;
+    // the work-group's output rows: a.rows_wg from the first row of unit sb0 on, the last work-group of the launch takes what
+    // is left.  Its first row is even (rows_wg is), which the tail boxes rely on.
+    const int x0 = blockIdx.x * owg, y0 = a.sb0 * kStatBand4 + (int)blockIdx.y * a.rows_wg;
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const StatLayout& lay = a.lay;
     if (lay.zero16 != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && t == 0) {
         lay.zero16[0] = 0ull;
         lay.zero16[1] = 0ull;
@@ -243,170 +307,180 @@ __global__ __launch_bounds__(256) void stats_u8_kernel(const uint8_t* __restrict
             }
         }
     }
+    const int y1 = min(min(a.sb1 * kStatBand4, a.oh), y0 + a.rows_wg);
+    if (y0 >= y1) return;                            // (stats_u8_grid_y launches none such; uniform, ahead of every barrier)
     const int L = owg + w - 1;                       // image columns of this strip (<= kStatStrip)
-    // the image is padded by kPadCols columns only: quads further right (beyond every valid window) read 0
-    const bool ld = 4 * t < L && x0 + 4 * t + 3 < pitch;
-    const uint8_t* base = img + (size_t)y0 * pitch + x0 + 4 * t;
-    uint32_t c1[4] = {0, 0, 0, 0}, c2[4] = {0, 0, 0, 0};
+    const int tc = CPT * t;                          // first of this thread's columns in the strip
+    // the image is padded by kPadCols columns only: aligned quads further right (beyond every valid window) read 0
+    const bool ld = (tc & ~3) < L && x0 + (tc | 3) < pitch;
+    const uint8_t* base = img + (size_t)y0 * pitch + x0 + tc;
+    auto load = [](const uint8_t* p) { return *reinterpret_cast<const uint32_t*>(p); };   // this thread's four pixels of a row
+    auto unpack = [](uint32_t v, uint32_t (&b)[CPT]) {
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) b[k] = k == 3 ? v >> 24 : (v >> (8 * k)) & 255u;
+    };
+    uint32_t c1[CPT], c2[CPT];
     // Tail boxes (TAIL; the two-row MFMA variant's tail screen, split s = tail_s, records into blkq): the window's template rows
     // the score kernel has not accumulated after s K steps.  Its waves pair output rows (even y, y + 1): the even row's box
     // is image rows y + s .. y + h - 1, the odd row's y + s .. y + h (|Q| = h - s and h - s + 1 rows).  y0 is even, so
     // the column sums q1 / q2 of the box slide by one added row per output row and two removed ones after each odd row.
-    uint32_t q1[4] = {0, 0, 0, 0}, q2[4] = {0, 0, 0, 0};
-    auto unpack = [](uint32_t v, uint32_t (&b)[4]) {
-        b[0] = v & 255u;
-        b[1] = (v >> 8) & 255u;
-        b[2] = (v >> 16) & 255u;
-        b[3] = v >> 24;
-    };
+    uint32_t q1[CPT], q2[CPT];
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) c1[k] = c2[k] = q1[k] = q2[k] = 0u;
     // kStatProBatch rows per batch: the loads of a batch are all in flight before the first add needs one.  (Round 5: 32
     // instead of 8 - the kernel is a chain of memory latencies, a 64-row window was eight of them before the first output row.)
     for (int r0 = 0; r0 < h; r0 += kStatProBatch) {
         uint32_t v[kStatProBatch];
 #pragma unroll
-        for (int i = 0; i < kStatProBatch; ++i)
-            v[i] = ld ? *reinterpret_cast<const uint32_t*>(base + (size_t)min(r0 + i, h - 1) * pitch) : 0u;
+        for (int i = 0; i < kStatProBatch; ++i) v[i] = ld ? load(base + (size_t)min(r0 + i, h - 1) * pitch) : 0u;
 #pragma unroll
         for (int i = 0; i < kStatProBatch; ++i)
             if (r0 + i < h) {
-                uint32_t b[4];
+                uint32_t b[CPT];
                 unpack(v[i], b);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
+                for (int k = 0; k < CPT; ++k) {
                     c1[k] += b[k];
                     c2[k] += b[k] * b[k];
                 }
                 if (TAIL && r0 + i >= tail_s) {
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
+                    for (int k = 0; k < CPT; ++k) {
                         q1[k] += b[k];
                         q2[k] += b[k] * b[k];
                     }
                 }
             }
     }
-    const int y1 = min(y0 + kStatBand4, oh);
-    const int xg = x0 + 4 * t;                       // first of this thread's four output columns
-    const bool out_on = 4 * t < owg && xg < st_pitch;   // st_pitch is a multiple of 4: xg + 3 < st_pitch too
+    const int xg = x0 + tc;                          // first of this thread's output columns
+    const bool out_on = tc < owg && xg < st_pitch;   // st_pitch is a multiple of 4, owg of 16: whole quads are on or off
+    const bool blk_on = (t & (BL - 1)) == 0 && tc < owg && (xg >> 4) < a.blk_pitch;     // the lane that writes a block's record
     for (int y = y0; y < y1; ++y) {
         // request the two image rows of the slide at the end of this iteration now: their latency
         // hides behind the scan and the float64 statistics
         uint32_t vn = 0, vo = 0, vq0 = 0, vq1 = 0;
         const bool odd = ((y - y0) & 1) != 0;
         if (y + 1 < y1 && ld) {
-            vn = *reinterpret_cast<const uint32_t*>(base + (size_t)(y - y0 + h) * pitch);
-            vo = *reinterpret_cast<const uint32_t*>(base + (size_t)(y - y0) * pitch);
+            vn = load(base + (size_t)(y - y0 + h) * pitch);
+            vo = load(base + (size_t)(y - y0) * pitch);
             if (TAIL && odd) {          // the rows the tail box leaves behind on its way to the next (even) row
-                vq0 = *reinterpret_cast<const uint32_t*>(base + (size_t)(y - y0 + tail_s - 1) * pitch);
-                vq1 = *reinterpret_cast<const uint32_t*>(base + (size_t)(y - y0 + tail_s) * pitch);
+                vq0 = load(base + (size_t)(y - y0 + tail_s - 1) * pitch);
+                vq1 = load(base + (size_t)(y - y0 + tail_s) * pitch);
             }
         }
         // block-wide exclusive scan of the column sums (thread-local prefix, wave scan, cross-wave)
-        const uint32_t a = c1[0] + c1[1] + c1[2] + c1[3], b = c2[0] + c2[1] + c2[2] + c2[3];
-        const uint32_t sa = wave_inclusive_scan_u32(a), sb = wave_inclusive_scan_u32(b);
-        uint32_t aq = 0, bq = 0, saq = 0, sbq = 0;
-        if constexpr (TAIL) {
-            aq = q1[0] + q1[1] + q1[2] + q1[3];
-            bq = q2[0] + q2[1] + q2[2] + q2[3];
-            saq = wave_inclusive_scan_u32(aq);
-            sbq = wave_inclusive_scan_u32(bq);
+        uint32_t s[NS], ws[NS];          // this thread's totals and their wave scans
+        s[0] = s[1] = 0u;
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) {
+            s[0] += c1[k];
+            s[1] += c2[k];
         }
-        if (lane == 63) {
-            wsum[0][wave] = sa;
-            wsum[1][wave] = sb;
-            if constexpr (TAIL) {
-                wsum[2][wave] = saq;
-                wsum[3][wave] = sbq;
+        if constexpr (TAIL) {
+            s[2] = s[3] = 0u;
+#pragma unroll
+            for (int k = 0; k < CPT; ++k) {
+                s[2] += q1[k];
+                s[3] += q2[k];
             }
+        }
+#pragma unroll
+        for (int j = 0; j < NS; ++j) ws[j] = wave_inclusive_scan_u32(s[j]);
+        if (lane == 63) {
+#pragma unroll
+            for (int j = 0; j < NS; ++j) wsum[wave][j] = ws[j];
         }
         __syncthreads();                 // also: previous row's E reads are done
-        uint32_t oa = sa - a, ob = sb - b;          // exclusive offset of this thread's first column
-        uint32_t oaq = saq - aq, obq = sbq - bq;
+        uint32_t off[NS];                // exclusive offset of this thread's first column: every earlier wave's partial
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
+        for (int j = 0; j < NS; ++j) off[j] = ws[j] - s[j];
+#pragma unroll
+        for (int k = 0; k < NW - 1; ++k)
             if (k < wave) {
-                oa += wsum[0][k];
-                ob += wsum[1][k];
-                if constexpr (TAIL) {
-                    oaq += wsum[2][k];
-                    obq += wsum[3][k];
-                }
+#pragma unroll
+                for (int j = 0; j < NS; ++j) off[j] += wsum[k][j];
             }
-        const uint32_t e1[4] = {oa, oa + c1[0], oa + c1[0] + c1[1], oa + c1[0] + c1[1] + c1[2]};
-        const uint32_t e2[4] = {ob, ob + c2[0], ob + c2[0] + c2[1], ob + c2[0] + c2[1] + c2[2]};
-        *reinterpret_cast<uint4*>(&E1[4 * t]) = make_uint4(e1[0], e1[1], e1[2], e1[3]);
-        *reinterpret_cast<uint4*>(&E2[4 * t]) = make_uint4(e2[0], e2[1], e2[2], e2[3]);
-        if (t == 255) {                  // E[kStatStrip]: read when the strip is full width
-            E1[kStatStrip] = oa + a;
-            E2[kStatStrip] = ob + b;
+        uint32_t e1[CPT], e2[CPT], eq1[CPT], eq2[CPT];
+        e1[0] = off[0];
+        e2[0] = off[1];
+#pragma unroll
+        for (int k = 1; k < CPT; ++k) {
+            e1[k] = e1[k - 1] + c1[k - 1];
+            e2[k] = e2[k - 1] + c2[k - 1];
         }
-        const uint32_t eq1[4] = {oaq, oaq + q1[0], oaq + q1[0] + q1[1], oaq + q1[0] + q1[1] + q1[2]};
-        const uint32_t eq2[4] = {obq, obq + q2[0], obq + q2[0] + q2[1], obq + q2[0] + q2[1] + q2[2]};
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) {
+            E1[tc + k] = e1[k];
+            E2[tc + k] = e2[k];
+        }
+        if (t == NT - 1) {               // E[kStatStrip]: read when the strip is full width
+            E1[kStatStrip] = off[0] + s[0];
+            E2[kStatStrip] = off[1] + s[1];
+        }
         if constexpr (TAIL) {
-            *reinterpret_cast<uint4*>(&EQ1[4 * t]) = make_uint4(eq1[0], eq1[1], eq1[2], eq1[3]);
-            *reinterpret_cast<uint4*>(&EQ2[4 * t]) = make_uint4(eq2[0], eq2[1], eq2[2], eq2[3]);
-            if (t == 255) {
-                EQ1[kStatStrip] = oaq + aq;
-                EQ2[kStatStrip] = obq + bq;
+            eq1[0] = off[2];
+            eq2[0] = off[3];
+#pragma unroll
+            for (int k = 1; k < CPT; ++k) {
+                eq1[k] = eq1[k - 1] + q1[k - 1];
+                eq2[k] = eq2[k - 1] + q2[k - 1];
+            }
+#pragma unroll
+            for (int k = 0; k < CPT; ++k) {
+                EQ1[tc + k] = eq1[k];
+                EQ2[tc + k] = eq2[k];
+            }
+            if (t == NT - 1) {
+                EQ1[kStatStrip] = off[2] + s[2];
+                EQ2[kStatStrip] = off[3] + s[3];
             }
         }
         __syncthreads();
-        double blk_s1[4] = {0.0, 0.0, 0.0, 0.0}, blk_sq[4] = {0.0, 0.0, 0.0, 0.0};
+        // ranges over the 16-pixel column block this thread's BL lanes cover (the hits-only screen of the multi-row MFMA
+        // variants bounds a lane's 16 outputs with them): S1 min / max (exact integers: taken as uint32, converted once)
+        // and the smallest sqrt over the block's output columns (x < ow); a block without any gets sqrt = +inf - no
+        // candidate can pass that
+        uint32_t lo = 0xffffffffu, hi = 0u;     // (a window sum is below 2^32 / 255: never the empty block's mark)
+        double sm = INFINITY;
         if (out_on) {
-            double tt[4], ws2[4], sqv[4], rs[4];
+            double tt[CPT], ws2[CPT], sqv[CPT], rs[CPT];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t s1 = E1[4 * t + k + w] - e1[k], s2 = E2[4 * t + k + w] - e2[k];
+            for (int k = 0; k < CPT; ++k) {
+                const uint32_t s1 = E1[tc + k + w] - e1[k], s2 = E2[tc + k + w] - e2[k];
                 tt[k] = (double)s1;
                 ws2[k] = (double)s2;
                 double wnd_mean2 = 0.0;
-                if (num_type == 1) wnd_mean2 = (tt[k] * tt[k]) * inv_area;
+                if (a.num_type == 1) wnd_mean2 = (tt[k] * tt[k]) * a.inv_area;
                 sqv[k] = window_norm(ws2[k], wnd_mean2);
-                rs[k] = sqv[k] > 0.0 ? 1.0 / sqv[k] : 0.0;
-                blk_s1[k] = tt[k];
-                blk_sq[k] = sqv[k];
-            }
-            const size_t o = (size_t)y * st_pitch + xg;
-            if (want_t) {
-                *reinterpret_cast<double2*>(t0 + o) = make_double2(tt[0], tt[1]);
-                *reinterpret_cast<double2*>(t0 + o + 2) = make_double2(tt[2], tt[3]);
-            }
-            if (want_sum2) {
-                *reinterpret_cast<double2*>(sum2 + o) = make_double2(ws2[0], ws2[1]);
-                *reinterpret_cast<double2*>(sum2 + o + 2) = make_double2(ws2[2], ws2[3]);
-            }
-            if (want_sq) {
-                *reinterpret_cast<double2*>(sq + o) = make_double2(sqv[0], sqv[1]);
-                *reinterpret_cast<double2*>(sq + o + 2) = make_double2(sqv[2], sqv[3]);
-                if (rsq != nullptr) {                // row-multiplexed MFMA classes
-                    *reinterpret_cast<double2*>(rsq + o) = make_double2(rs[0], rs[1]);
-                    *reinterpret_cast<double2*>(rsq + o + 2) = make_double2(rs[2], rs[3]);
+                if constexpr (RSQ) rs[k] = sqv[k] > 0.0 ? 1.0 / sqv[k] : 0.0;
+                if (xg + k < ow) {
+                    lo = min(lo, s1);
+                    hi = max(hi, s1);
+                    sm = fmin(sm, sqv[k]);
                 }
             }
+            const size_t o = (size_t)y * st_pitch + xg;
+            auto store = [&](double* plane, const double (&v)[CPT]) {
+#pragma unroll
+                for (int k = 0; k < CPT; k += 2) *reinterpret_cast<double2*>(plane + o + k) = make_double2(v[k], v[k + 1]);
+            };
+            if (a.want_t) store(a.t0, tt);
+            if (a.want_sum2) store(a.sum2, ws2);
+            if (a.want_sq) {
+                store(a.sq, sqv);
+                if constexpr (RSQ) store(a.rsq, rs);                // row-multiplexed MFMA classes
+            }
         }
-        if (blk != nullptr) {
-            // ranges over the 16-pixel column block this thread's quad of threads covers (the hits-only screen of the
-            // multi-row MFMA variants bounds a lane's 16 outputs with them): S1 min / max and the smallest sqrt over the
-            // block's output columns (x < ow); a block without any gets sqrt = +inf - no candidate can pass that
-            double lo = INFINITY, hi = 0.0, sm = INFINITY;
-            if (out_on) {
+        if (a.blk != nullptr) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (xg + k < ow) {
-                        lo = fmin(lo, blk_s1[k]);
-                        hi = fmax(hi, blk_s1[k]);
-                        sm = fmin(sm, blk_sq[k]);
-                    }
+            for (int d = 1; d < BL; d <<= 1) {
+                lo = min(lo, lane_group_xchg_u32(lo, d));
+                hi = max(hi, lane_group_xchg_u32(hi, d));
+                sm = fmin(sm, lane_group_xchg_f64(sm, d));
             }
-#pragma unroll
-            for (int off = 1; off <= 2; off <<= 1) {
-                lo = fmin(lo, __shfl_xor(lo, off));
-                hi = fmax(hi, __shfl_xor(hi, off));
-                sm = fmin(sm, __shfl_xor(sm, off));
-            }
-            if ((t & 3) == 0 && 4 * t < owg && (xg >> 4) < blk_pitch) {
-                double* o = blk + ((size_t)y * blk_pitch + (xg >> 4)) * 4;
-                *reinterpret_cast<double2*>(o) = make_double2(lo == INFINITY ? 0.0 : lo, hi);
+            if (blk_on) {
+                double* o = a.blk + ((size_t)y * a.blk_pitch + (xg >> 4)) * 4;
+                *reinterpret_cast<double2*>(o) = make_double2(lo == 0xffffffffu ? 0.0 : (double)lo, (double)hi);
                 *reinterpret_cast<double2*>(o + 2) = make_double2(sm, 0.0);
             }
         }
@@ -414,48 +488,51 @@ __global__ __launch_bounds__(256) void stats_u8_kernel(const uint8_t* __restrict
             // the tail box's ranges over the same blocks: S1_Q min / max and the largest sqrt(V_Q).  |Q| S2_Q and S1_Q^2
             // are integers below 2^53 (w h 255^2 < 2^32), so V' = |Q| S2_Q - S1_Q^2 = |Q| V_Q is exact, and so is its
             // maximum over the block; sqrt(max V' * RN(1 / |Q|)) carries three roundings (<= 2.5 ulp) and is raised by 2^-49
-            // relative (16 ulp): never below the exact root of the block's largest V_Q (sqrt is monotonic)
+            // relative (16 ulp): never below the exact root of the block's largest V_Q (sqrt is monotonic).  RN(1 / |Q|)
+            // comes from the host (IEEE division there as here), one for even and one for odd rows.
             const double nq = (double)((odd ? h - tail_s + 1 : h - tail_s) * w);
-            double lo = INFINITY, hi = 0.0, vm = 0.0;
+            uint32_t loq = 0xffffffffu, hiq = 0u;
+            double vm = 0.0;
             if (out_on) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k)
+                for (int k = 0; k < CPT; ++k)
                     if (xg + k < ow) {
-                        const uint32_t s1q = EQ1[4 * t + k + w] - eq1[k], s2q = EQ2[4 * t + k + w] - eq2[k];
+                        const uint32_t s1q = EQ1[tc + k + w] - eq1[k], s2q = EQ2[tc + k + w] - eq2[k];
                         const double a1 = (double)s1q;
-                        lo = fmin(lo, a1);
-                        hi = fmax(hi, a1);
+                        loq = min(loq, s1q);
+                        hiq = max(hiq, s1q);
                         vm = fmax(vm, nq * (double)s2q - a1 * a1);
                     }
             }
 #pragma unroll
-            for (int off = 1; off <= 2; off <<= 1) {
-                lo = fmin(lo, __shfl_xor(lo, off));
-                hi = fmax(hi, __shfl_xor(hi, off));
-                vm = fmax(vm, __shfl_xor(vm, off));
+            for (int d = 1; d < BL; d <<= 1) {
+                loq = min(loq, lane_group_xchg_u32(loq, d));
+                hiq = max(hiq, lane_group_xchg_u32(hiq, d));
+                vm = fmax(vm, lane_group_xchg_f64(vm, d));
             }
-            vm = sqrt(vm * (1.0 / nq)) * (1.0 + 0x1p-49);
-            if ((t & 3) == 0 && 4 * t < owg && (xg >> 4) < blk_pitch) {
-                double* o = blkq + ((size_t)y * blk_pitch + (xg >> 4)) * 4;
-                *reinterpret_cast<double2*>(o) = make_double2(lo == INFINITY ? 0.0 : lo, hi);
+            if (blk_on) {
+                vm = sqrt(vm * a.inv_nq[odd ? 1 : 0]) * (1.0 + 0x1p-49);
+                double* o = a.blkq + ((size_t)y * a.blk_pitch + (xg >> 4)) * 4;
+                *reinterpret_cast<double2*>(o) = make_double2(loq == 0xffffffffu ? 0.0 : (double)loq, (double)hiq);
                 *reinterpret_cast<double2*>(o + 2) = make_double2(vm, 0.0);
             }
         }
-        // slide the column sums one row down (zeros on the last row: nothing changes)
-        uint32_t bn[4], bo[4];
+        // slide the column sums one row down (zeros on the last row: nothing changes); squares as (n - o)(n + o), a
+        // 24-bit product
+        uint32_t bn[CPT], bo[CPT];
         unpack(vn, bn);
         unpack(vo, bo);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < CPT; ++k) {
             c1[k] += bn[k] - bo[k];
-            c2[k] += bn[k] * bn[k] - bo[k] * bo[k];
+            c2[k] += (uint32_t)__mul24((int)bn[k] - (int)bo[k], (int)(bn[k] + bo[k]));
         }
         if constexpr (TAIL) {
-            uint32_t b0[4], b1[4];
+            uint32_t b0[CPT], b1[CPT];
             unpack(vq0, b0);
             unpack(vq1, b1);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
+            for (int k = 0; k < CPT; ++k) {
                 q1[k] += bn[k] - b0[k] - b1[k];
                 q2[k] += bn[k] * bn[k] - b0[k] * b0[k] - b1[k] * b1[k];
             }

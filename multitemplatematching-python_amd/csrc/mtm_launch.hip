@@ -265,6 +265,35 @@ int ensure_square_planes(mtm_ctx* c) {
 
 static int launch_masked_sumsq(mtm_ctx* c, const SizeClass& sc, bool fused_stats, const StatPlanes& st, double* sum2);
 
+// One stats_u8_kernel launch: the row units [a.sb0, a.sb1) of the fused single-channel uint8 statistics, in form `form`
+// (kStatForms, from 1; 0 = stats_u8_form's choice).  Fills the derived fields of `a`.  launch_stats and the test-support
+// entry mtm_debug_window_stats both come through here.
+int launch_stats_u8(hipStream_t stream, StatU8Args a, int form, int n_cus) {
+    if (a.sb1 <= a.sb0) return MTM_OK;
+    a.owg = stats_u8_owg(a.w);
+    const int strips = (a.ow + a.owg - 1) / a.owg;
+    if (form == 0) form = stats_u8_form(strips, a.sb1 - a.sb0, n_cus);
+    if (form < 1 || form > kStatFormCount) {
+        set_error("launch_stats_u8: no such form");
+        return MTM_E_INVALID;
+    }
+    a.rows_wg = kStatFormRows[form - 1];
+    a.inv_area = 1.0 / ((double)a.h * (double)a.w);
+    const bool tail = a.blkq != nullptr;
+    if (tail) {
+        a.inv_nq[0] = 1.0 / (double)((a.h - a.tail_s) * a.w);
+        a.inv_nq[1] = 1.0 / (double)((a.h - a.tail_s + 1) * a.w);
+    }
+    const dim3 grid(strips, stats_u8_grid_y(a.sb0, a.sb1, a.oh, a.rows_wg)), block(kStatStrip / 4);
+    if (grid.y == 0) return MTM_OK;
+    // (the tail boxes and the reciprocal plane in instantiations of their own: a launch without them pays nothing for them)
+    auto* kernel = tail ? (a.rsq ? stats_u8_kernel<true, true> : stats_u8_kernel<true, false>)
+                        : (a.rsq ? stats_u8_kernel<false, true> : stats_u8_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
+    HIPC(hipGetLastError());
+    return MTM_OK;
+}
+
 // Window statistics of one size class (two kernels), into c->stats.  Returns the plane table.
 // `sb0`, `sb1`: range of kStatBand4-row output blocks to compute (banded image upload; fused single-channel
 // kernel only), sb1 < 0 = all.
@@ -308,7 +337,6 @@ int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out,
     if (fused_stats) {
         // (masked classes on the matrix cores: the sum2 plane is written by the sum I^2 M pass below, not here)
         const int want_sum2 = (!masked_mfma && (num_type == 2 || (normed && num_type != 1) || !want_t_always)) ? 1 : 0;
-        const int owg = stats_u8_owg(w);
         const int nsb = (oh + kStatBand4 - 1) / kStatBand4;
         const int b1 = sb1 < 0 ? nsb : std::min(sb1, nsb);
         double* rsq = nullptr;
@@ -335,7 +363,6 @@ int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out,
             }
         }
         if (b1 > sb0) {
-            const dim3 gs((ow + owg - 1) / owg, b1 - sb0);
             // banded upload with the layout conversion of the band's rows on this launch (run_score_banded): the kernel reads
             // the raw upload buffer (every row that has arrived so far is there) and writes the planes of the new rows
             StatLayout lay{};
@@ -355,11 +382,16 @@ int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out,
                 lay.zero16 = c->cands.as<unsigned long long>();
                 R.zero_pending = false;
             }
-            // (the tail boxes in an instantiation of their own: every other launch runs the kernel as it was)
-            hipLaunchKernelGGL(blkq ? stats_u8_kernel<true> : stats_u8_kernel<false>, gs, dim3(256), 0,
-                               c->stats_stream ? c->stats_stream : c->stream, src,
-                               src_pitch, h, w, oh, ow, owg, inv_area, num_type, normed ? 1 : 0, want_t, want_sum2, tp[0],
-                               sum2, sq, st.pitch, rsq, sb0, blk, st.blk_pitch, lay, blkq, tail_s);
+            StatU8Args a{};
+            a.img = src;
+            a.pitch = src_pitch;
+            a.h = h, a.w = w, a.oh = oh, a.ow = ow;
+            a.num_type = num_type, a.want_sq = normed ? 1 : 0, a.want_t = want_t, a.want_sum2 = want_sum2;
+            a.t0 = tp[0], a.sum2 = sum2, a.sq = sq, a.rsq = rsq, a.st_pitch = st.pitch;
+            a.blk = blk, a.blkq = blkq, a.blk_pitch = st.blk_pitch, a.tail_s = blkq ? tail_s : 0;
+            a.sb0 = sb0, a.sb1 = b1;
+            a.lay = lay;
+            MTMC(launch_stats_u8(c->stats_stream ? c->stats_stream : c->stream, a, 0, c->n_cus > 0 ? c->n_cus : 256));
         }
     } else if (u8 && c->chans == 3 && w <= 768 && 3.0 * w * h * 65025.0 < 4294967296.0 && c->fuse_stats) {
         // RGB: the fused kernel with one scan per channel + one for the squares (sum2 always written:
@@ -1542,3 +1574,113 @@ int run_score_banded(mtm_ctx* c, CallRoute& R, const ImageArgs& a) {
 }
 
 }  // namespace mtmi
+
+extern "C" {
+
+// Test support: stats_u8_kernel on an image the caller hands over (tests/test_gpu_window_stats.py), launched by
+// launch_stats_u8 like every statistics launch of a search call.  Everything lives in stats_dbg, laid out per call and
+// filled with the caller's pattern first; nothing of the context's image, placement or options is read or written.
+int mtm_debug_window_stats(mtm_ctx* c, const mtm_window_stats* a) {
+    if (!c || !a) {
+        set_error("mtm_debug_window_stats: null context or arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, "mtm_debug_window_stats");
+    const auto bad = [](const char* what) {
+        set_error(std::string("mtm_debug_window_stats: ") + what);
+        return MTM_E_INVALID;
+    };
+    const int rows = a->rows, cols = a->cols, h = a->h, w = a->w;
+    if (!a->image || !a->info || rows < 1 || cols < 1 || rows > 16384 || cols > 16384 || h < 1 || w < 1 || h > rows || w > cols)
+        return bad("an image of 1 .. 16384 rows and columns and a window inside it are needed");
+    if (w > 768 || (double)w * h * 65025.0 >= 4294967296.0) return bad("the fused kernel takes w <= 768 and w h 255^2 < 2^32");
+    if (a->num_type < 0 || a->num_type > 2 || a->form < 0 || a->form > kStatFormCount || a->pattern_byte < 0 || a->pattern_byte > 255)
+        return bad("num_type 0 .. 2, a form and a pattern byte");
+    const int oh = rows - h + 1, ow = cols - w + 1, nsb = (oh + kStatBand4 - 1) / kStatBand4;
+    const int sb0 = a->sb0, sb1 = a->sb1 < 0 ? nsb : std::min(a->sb1, nsb);
+    if (sb0 < 0 || sb0 >= sb1) return bad("an empty range of row units");
+    const bool conv = a->lay_r1 > a->lay_r0;
+    if (conv && (cols % 4 != 0 || a->lay_r0 < 0 || a->lay_r1 > rows)) return bad("the conversion needs cols % 4 == 0 and rows inside the image");
+    const bool tail = a->tail_s != 0;
+    if (tail && (a->tail_s < 1 || a->tail_s > h - 1 || !a->blk || !a->blkq)) return bad("tail_s in 1 .. h - 1, with blk and blkq");
+    if (!tail && a->blkq) return bad("blkq without tail_s");
+    if (a->rsq && !a->sq) return bad("rsq without sq");
+    const int st_pitch = (int)round_up((size_t)ow, 4), blk_pitch = (st_pitch + 15) / 16;
+    const int pitch = (int)round_up((size_t)cols + kPadCols, 64), rows_alloc = rows + kPadRows;
+    // stats_dbg: [header][raw image][uint8 plane][int8 view][t0][sum2][sq][rsq][blk][blkq]
+    size_t total = 0;
+    const auto take = [&](size_t bytes) {
+        const size_t off = total;
+        total += round_up(std::max<size_t>(bytes, 16), 256);
+        return off;
+    };
+    const size_t plane_bytes = (size_t)pitch * rows_alloc, st_bytes = sizeof(double) * (size_t)st_pitch * oh;
+    const size_t rec_bytes = sizeof(double) * 4 * (size_t)blk_pitch * oh;
+    const size_t o_hdr = take(16), o_raw = take((size_t)rows * cols), o_u8 = take(plane_bytes), o_u8b = take(plane_bytes);
+    const size_t o_t0 = take(st_bytes), o_sum2 = take(st_bytes), o_sq = take(st_bytes), o_rsq = take(st_bytes);
+    const size_t o_blk = take(rec_bytes), o_blkq = take(rec_bytes);
+    HIPC(hipSetDevice(c->device));
+    MTMC(c->stats_dbg.ensure(total));
+    uint8_t* b = c->stats_dbg.as<uint8_t>();
+    HIPC(hipMemsetAsync(b, a->pattern_byte, total, c->stream));
+    HIPC(hipMemcpyAsync(b + o_raw, a->image, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
+    if (!conv) {        // the plane as an upload leaves it: the image, zero padding
+        HIPC(hipMemsetAsync(b + o_u8, 0, plane_bytes, c->stream));
+        HIPC(hipMemcpy2DAsync(b + o_u8, (size_t)pitch, a->image, (size_t)cols, (size_t)cols, (size_t)rows, hipMemcpyHostToDevice,
+                              c->stream));
+    }
+    StatU8Args k{};
+    k.img = conv ? b + o_raw : b + o_u8;
+    k.pitch = conv ? cols : pitch;
+    k.h = h, k.w = w, k.oh = oh, k.ow = ow;
+    k.num_type = a->num_type, k.want_sq = a->sq ? 1 : 0, k.want_t = a->t0 ? 1 : 0, k.want_sum2 = a->sum2 ? 1 : 0;
+    k.t0 = reinterpret_cast<double*>(b + o_t0), k.sum2 = reinterpret_cast<double*>(b + o_sum2);
+    k.sq = reinterpret_cast<double*>(b + o_sq), k.rsq = a->rsq ? reinterpret_cast<double*>(b + o_rsq) : nullptr;
+    k.st_pitch = st_pitch;
+    k.blk = a->blk ? reinterpret_cast<double*>(b + o_blk) : nullptr;
+    k.blkq = tail ? reinterpret_cast<double*>(b + o_blkq) : nullptr;
+    k.blk_pitch = a->blk ? blk_pitch : 0, k.tail_s = a->tail_s;
+    k.sb0 = sb0, k.sb1 = sb1;
+    if (conv) {
+        k.lay.u8 = b + o_u8, k.lay.u8b = b + o_u8b, k.lay.pitch = pitch;
+        k.lay.r0 = a->lay_r0, k.lay.r1 = a->lay_r1;
+    }
+    if (a->zero_header) k.lay.zero16 = reinterpret_cast<unsigned long long*>(b + o_hdr);
+    const int n_cus = c->n_cus > 0 ? c->n_cus : 256;
+    const int strips = (ow + stats_u8_owg(w) - 1) / stats_u8_owg(w);
+    const int form = a->form ? a->form : stats_u8_form(strips, sb1 - sb0, n_cus);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int rc = MTM_OK;
+    float ms = 0.0f;
+    hipError_t e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
+    if (e == hipSuccess) rc = launch_stats_u8(c->stream, k, form, n_cus);
+    if (e == hipSuccess && rc == MTM_OK) e = hipEventRecord(ev[1], c->stream);
+    if (e == hipSuccess && rc == MTM_OK) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && rc == MTM_OK) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    for (hipEvent_t v : ev)
+        if (v) (void)hipEventDestroy(v);
+    MTMC(rc);
+    HIPC(e);
+    const auto fetch = [&](void* to, size_t off, size_t bytes) -> int {
+        if (to) HIPC(hipMemcpy(to, b + off, bytes, hipMemcpyDeviceToHost));
+        return MTM_OK;
+    };
+    MTMC(fetch(a->t0, o_t0, st_bytes));
+    MTMC(fetch(a->sum2, o_sum2, st_bytes));
+    MTMC(fetch(a->sq, o_sq, st_bytes));
+    MTMC(fetch(a->rsq, o_rsq, st_bytes));
+    MTMC(fetch(a->blk, o_blk, rec_bytes));
+    MTMC(fetch(a->blkq, o_blkq, rec_bytes));
+    MTMC(fetch(a->u8, o_u8, (size_t)rows * pitch));
+    MTMC(fetch(a->u8b, o_u8b, (size_t)rows * pitch));
+    MTMC(fetch(a->header, o_hdr, 16));
+    const int rows_wg = kStatFormRows[form - 1];
+    const int64_t info[8] = {st_pitch, blk_pitch, pitch, form, strips, stats_u8_grid_y(sb0, sb1, oh, rows_wg), n_cus,
+                             (int64_t)llround((double)ms * 1e6)};
+    std::memcpy(a->info, info, sizeof(info));
+    return MTM_OK;
+}
+
+}  // extern "C"

@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -590,6 +590,37 @@ int mtm_track_boxes_sets(mtm_ctx* ctx, const void* const* frames, int n_frames, 
                          int64_t row_stride_bytes, const mtm_box_unit* start, int n_tracks, const int32_t* set_off,
                          const int32_t* set_idx, int margin, int use_min, double min_score, int reacquire, mtm_hit* out,
                          float* nbhd);
+
+/* One block of mtm_match_blocks: columns x .. x + w - 1 and rows y .. y + h - 1 of the reference image. */
+typedef struct mtm_block {
+    int32_t x, y, w, h;
+} mtm_block;
+
+/* Block matching between two images of one shape in one call: block k of `reference` is the template, and
+ * its search box in `image` is the block's own box widened by `margin` pixels on every side and clipped to the image.
+ * out[k] = the extremum of that template's score map over the box - what mtm_find_matches_boxes returns in
+ * MTM_PEAKS_GLOBAL mode for the block's pixels set as a template and the box as its region: image coordinates, the same
+ * float32 score bits, the first output in row-major order of the box's map on ties - with templ_idx = k.  The templates
+ * never exist on the host: a kernel cuts them out of the uploaded reference and computes their constants on the device.
+ * uint8 images with 1 or 3 channels or single-channel uint16 ones, each with a row stride of its own; method: MTM_TM_*.
+ * nbhd: optional (NULL: records only), 9 n floats - nbhd[9 k + 3 (1 + dy) + (1 + dx)] = the score of block k at window
+ * (x + dx, y + dy) of the WHOLE image's map around out[k], NaN outside that map: what mtm_hit_neighbourhoods returns for
+ * it, bit for bit.  A block outside the reference or with w < 1 or h < 1, a uint16 block of more than 2^21 pixels and a
+ * block of 2^31 pixels or more return MTM_E_INVALID and name the block.  The templates set on the context, their caches
+ * and the method they were set with are neither read nor changed; the context has no current image afterwards.  Blocks run
+ * in chunks whose template bytes fit 4 * MTM_OPT_BOXES_MAX_FLOATS; one host wait per call. */
+int mtm_match_blocks(mtm_ctx* ctx, const void* reference, int64_t reference_stride_bytes, const void* image,
+                     int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
+                     int n_blocks, int margin, int method, mtm_hit* out, float* nbhd);
+
+/* Test support: the host plan of a mtm_match_blocks call (no context, no GPU) - its checks, tile table and chunk split
+ * for a template budget of `budget_bytes`.  tiles: 3 int32 per tile (block, first output row, first output column of a
+ * 16 x 16 tile of the block's map), at most tile_cap tiles are written and *n_tiles is their full number; chunk_of[k] =
+ * the chunk block k runs in; toff[k] = the byte offset of its template planes in that chunk's buffer; maps: 4 int32 per
+ * block (x0, y0 of its search box, ow, oh of its map).  Any output may be NULL. */
+int mtm_debug_plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* blocks, int n_blocks, int margin,
+                          int64_t budget_bytes, int32_t* tiles, int64_t tile_cap, int64_t* n_tiles, int32_t* chunk_of,
+                          int64_t* toff, int32_t* maps);
 
 /* The 3 x 3 score neighbourhoods of n points in one call: out[9 k + 3 (1 + dy) + (1 + dx)] = the score of
  * template pts[k].templ_idx at window (x + dx, y + dy) of the image's score map, NaN for a window outside the map.  Image:

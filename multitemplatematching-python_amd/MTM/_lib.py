@@ -62,6 +62,8 @@ HIT_DTYPE = np.dtype([("templ_idx", "<i4"), ("x", "<i4"), ("y", "<i4"), ("w", "<
 # mtm_box_unit: a template index and the region (y0, x0, rows, cols) it is searched in
 BOX_UNIT_DTYPE = np.dtype([("templ_idx", "<i4"), ("y0", "<i4"), ("x0", "<i4"), ("rows", "<i4"), ("cols", "<i4")])
 # mtm_point: a template index and the window (x, y) at the centre of a 3 x 3 neighbourhood (mtm_hit_neighbourhoods)
+# one mtm_block of mtm_match_blocks: a block (x, y, w, h) of the reference image
+BLOCK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4")])
 POINT_DTYPE = np.dtype([("templ_idx", "<i4"), ("x", "<i4"), ("y", "<i4")])
 assert HIT_DTYPE.itemsize == ctypes.sizeof(MtmHit) == 24
 # mtm_templ as a numpy record: a whole template list is filled column-wise instead of field by field
@@ -177,6 +179,12 @@ SYMBOLS = {
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "mtm_match_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "mtm_debug_plan_blocks": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                             _P(ctypes.c_int64), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_hit_neighbourhoods": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
@@ -429,6 +437,37 @@ def debug_tail_split(h, w, thr):
 
 # the doubles of one mtm_debug_templ_stats / mtm_track_boxes_adapt statistics record
 TEMPL_STATS_FIELDS = ("mean0", "mean1", "mean2", "mean3", "templ_norm", "templ_sum2", "all_ones")
+
+
+def block_records(blocks):
+    """BLOCK_DTYPE records from such records or from an (N, 4) integer array of (x, y, w, h)."""
+    b = np.asarray(blocks)
+    if b.dtype == BLOCK_DTYPE:
+        return np.ascontiguousarray(b)
+    b = b.reshape(-1, 4)
+    rec = np.empty(len(b), dtype=BLOCK_DTYPE)
+    rec["x"], rec["y"], rec["w"], rec["h"] = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+    return rec
+
+
+def debug_plan_blocks(shape, chans, dtype, blocks, margin, budget_bytes):
+    """The host plan of a mtm_match_blocks call for images of `shape` (rows, cols), no GPU needed (mtm_debug_plan_blocks):
+    (tiles (n, 3) int32 of (block, ty0, tx0); chunk_of (N,) int32; toff (N,) int64; maps (N, 4) int32 of (x0, y0, ow, oh))."""
+    lib = load()
+    blocks = block_records(blocks)
+    n = len(blocks)
+    code = _DT_CODES[np.dtype(dtype)]
+    n_tiles = ctypes.c_int64(0)
+    chunk_of = np.zeros(n, dtype=np.int32)
+    toff = np.zeros(n, dtype=np.int64)
+    maps = np.zeros((n, 4), dtype=np.int32)
+    args = (int(shape[0]), int(shape[1]), int(chans), code, blocks.ctypes.data, n, int(margin), int(budget_bytes))
+    check(lib.mtm_debug_plan_blocks(*args, None, 0, ctypes.byref(n_tiles), chunk_of.ctypes.data, toff.ctypes.data,
+                                    maps.ctypes.data), "mtm_debug_plan_blocks")
+    tiles = np.zeros((n_tiles.value, 3), dtype=np.int32)
+    check(lib.mtm_debug_plan_blocks(*args, tiles.ctypes.data, n_tiles.value, ctypes.byref(n_tiles), None, None, None),
+          "mtm_debug_plan_blocks")
+    return tiles, chunk_of, toff, maps
 
 
 def debug_templ_stats(template, method):
@@ -813,6 +852,26 @@ class Context(_RecordMemo):
                                              int(use_min), float(min_score) if use_min else 0.0, int(bool(reacquire)),
                                              out.ctypes.data, nbhd.ctypes.data if with_nbhd else None),
               "mtm_track_boxes_sets")
+        return out, nbhd
+
+    def match_blocks(self, reference, image, blocks, margin, method, with_nbhd=False):
+        """Every block of `reference` (BLOCK_DTYPE records) searched in `image` - same shape and pixel type, row strides of
+        their own - inside its box widened by `margin`, in one native call (mtm_match_blocks).  Returns (records, one per
+        block with templ_idx = the block's index, image coordinates; (len(blocks), 3, 3) float32 neighbourhoods of the
+        records in the whole image's map - hit_neighbourhoods' values -, or None).  The templates set on the context are
+        not touched."""
+        blocks = block_records(blocks)
+        n = len(blocks)
+        out = np.empty(n, dtype=HIT_DTYPE)
+        nbhd = np.empty((n, 3, 3), dtype=np.float32) if with_nbhd else None
+        if n == 0:
+            return out, nbhd
+        r, rptr, rstride = _pixel_rows(reference)
+        a, aptr, astride = _pixel_rows(image)
+        chans = 1 if a.ndim == 2 else a.shape[2]
+        check(self._lib.mtm_match_blocks(self._h, rptr, rstride, aptr, astride, a.shape[0], a.shape[1], chans, _dtype_code(a),
+                                         blocks.ctypes.data, n, int(margin), int(method), out.ctypes.data,
+                                         nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks")
         return out, nbhd
 
     def hit_neighbourhoods(self, image, points):

@@ -1,0 +1,186 @@
+"""
+Block matching between two images in one engine call: the displacement of every block of ``reference`` in ``image`` -
+drift and stage-shift estimation, registration of stitching overlaps, PIV-style displacement fields, "where did every
+patch of frame n go in frame n + 1".  The loop a user writes today,
+
+    for k, (x, y, w, h) in enumerate(blocks):
+        hit, = findMatchesInBoxes([("b", reference[y:y + h, x:x + w])], image, [search_box((x, y, w, h), margin, image.shape)],
+                                  method, N_object=1)[0]
+        positions[k], scores[k] = hit[1][:2], hit[2]
+
+with the same positions and float32 score bits, computed by one native call (mtm_match_blocks): both images
+are uploaded once, and the templates never exist on the host - a kernel cuts every block out of the uploaded reference
+and computes its constants on the device.  The search box of a block is the block's own box widened by ``margin`` pixels
+on every side and clipped to the image (``search_box``; ``MTM.tracking.next_box`` of the block taken as a hit).  Ties go
+to the first output in row-major order of the box's map; a flat block under TM_CCOEFF_NORMED scores 1.0 everywhere and
+lands on the box's first output; ``margin=0`` gives a 1 x 1 map.
+
+``refine=True`` returns float64 positions, element k being exactly
+
+    refineHits([("b", reference[y:y + h, x:x + w])], image, [hit_k], method)[0][1][:2]
+
+from the same native call: the 3 x 3 neighbourhood of every hit in the whole image's score map (NaN outside it), fitted
+by one ``subpixel.fit_offsets`` call for all blocks.  The scores stay the unrefined ones.
+
+Results are numpy arrays, not hit tuples.  The call leaves the templates set on its context - a TemplateMatcher's resident
+ones included - exactly as it found them.
+
+Scope (anything else raises ValueError / TypeError before any native call): two images of one shape, dtype and channel
+count - uint8 with 1 or 3 channels or single-channel uint16, at most 32767 rows -, methods 0..5, blocks wholly inside the
+reference, uint16 blocks of at most 2^21 pixels, ``margin`` an integer >= 0.
+"""
+import numbers
+
+import numpy as np
+
+from . import _lib, subpixel
+from . import TM_CCOEFF_NORMED
+
+__all__ = ["matchBlocks", "grid", "search_box", "displacements"]
+
+_I64 = np.dtype(np.int64)
+_U16_MAX_PIXELS = 1 << 21       # mtm_match_blocks: uint16 correlations stay below 2^53, exact in float64
+_MAX_ROWS = 32767               # the two images are uploaded as one stack of at most 65535 rows
+
+
+def _is_int(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, (bool, np.bool_))
+
+
+def search_box(block, margin, shape):
+    """The search box ``(x0, y0, bw, bh)`` of ``block = (x, y, w, h)`` in an image of shape ``shape``: the block's box
+    widened by ``margin`` pixels on every side and clipped to the image -
+    ``MTM.tracking.next_box(None, (None, block, 0), margin, shape, method)``."""
+    x, y, w, h = (int(v) for v in block)
+    H, W = int(shape[0]), int(shape[1])
+    x0, y0 = max(0, x - margin), max(0, y - margin)
+    x1, y1 = min(W, x + w + margin), min(H, y + h + margin)
+    return (x0, y0, x1 - x0, y1 - y0)
+
+
+def grid(shape, block, step=None):
+    """Every block of size ``block`` (an int, or ``(w, h)``) at stride ``step`` (an int or ``(sx, sy)``; default: the
+    block size) that lies wholly inside an image of shape ``shape``, in row-major order: an (N, 4) int64 array of
+    ``(x, y, w, h)``."""
+    def pair(v, what):
+        try:
+            p = (v, v) if _is_int(v) else tuple(v)
+        except TypeError:
+            p = ()
+        if len(p) != 2 or not all(_is_int(q) for q in p) or min(p) < 1:
+            raise ValueError("grid: %s must be a positive integer or a pair of them (got %r)" % (what, v))
+        return int(p[0]), int(p[1])
+
+    w, h = pair(block, "block")
+    sx, sy = (w, h) if step is None else pair(step, "step")
+    H, W = int(shape[0]), int(shape[1])
+    xs = np.arange(0, W - w + 1, sx, dtype=_I64) if W >= w else np.zeros(0, _I64)
+    ys = np.arange(0, H - h + 1, sy, dtype=_I64) if H >= h else np.zeros(0, _I64)
+    out = np.empty((len(ys) * len(xs), 4), dtype=_I64)
+    out[:, 0] = np.tile(xs, len(ys))
+    out[:, 1] = np.repeat(ys, len(xs))
+    out[:, 2] = w
+    out[:, 3] = h
+    return out
+
+
+def displacements(blocks, positions):
+    """``positions - blocks[:, :2]``: where every block of ``blocks`` moved to, as (dx, dy) - int64 for matchBlocks'
+    integer positions, float64 for refined ones."""
+    b = np.asarray(blocks).reshape(-1, 4)
+    p = np.asarray(positions).reshape(-1, 2)
+    if len(b) != len(p):
+        raise ValueError("displacements: %d blocks and %d positions" % (len(b), len(p)))
+    return p - b[:, :2]
+
+
+def _check_images(reference, image):
+    for name, a in (("reference", reference), ("image", image)):
+        if not isinstance(a, np.ndarray):
+            raise TypeError("%s must be a numpy array (got %s)" % (name, type(a).__name__))
+    ok = (image.dtype == np.uint8 and (image.ndim == 2 or (image.ndim == 3 and image.shape[2] in (1, 3)))) or \
+        (image.dtype == np.uint16 and (image.ndim == 2 or (image.ndim == 3 and image.shape[2] == 1)))
+    if reference.shape != image.shape or reference.dtype != image.dtype:
+        raise ValueError("reference and image differ in shape, dtype or channel count (%s %s and %s %s)" % (
+            reference.shape, reference.dtype, image.shape, image.dtype))
+    if not ok:
+        raise ValueError("matchBlocks takes uint8 images with 1 or 3 channels and single-channel uint16 images (got %s "
+                         "images of shape %s)" % (image.dtype, image.shape))
+    if image.shape[0] == 0 or image.shape[1] == 0:
+        raise ValueError("matchBlocks: the images are empty (shape %s)" % (image.shape,))
+    if image.shape[0] > _MAX_ROWS:
+        raise ValueError("matchBlocks takes images of at most %d rows (got %d)" % (_MAX_ROWS, image.shape[0]))
+
+
+def _check_blocks(blocks, reference):
+    """blocks -> (N, 4) int64 array; TypeError / ValueError naming the first offending block."""
+    try:
+        b = np.asarray(blocks)
+    except (ValueError, TypeError):
+        b = None
+    if b is not None and b.size == 0 and b.ndim <= 2 and (b.ndim < 2 or b.shape[1] in (0, 4)):
+        return np.zeros((0, 4), _I64)
+    if b is None or b.ndim != 2 or b.shape[1] != 4:
+        raise ValueError("blocks must be a sequence or an (N, 4) array of (x, y, w, h)")
+    if b.dtype.kind not in "iu":
+        for k, v in enumerate(np.asarray(blocks, dtype=object).reshape(-1)):
+            if not _is_int(v):
+                raise TypeError("blocks[%d]: (x, y, w, h) must be integers (got %r)" % (k // 4, v))
+        b = np.array(b.tolist(), dtype=_I64)       # (an object array of Python integers)
+    b = b.astype(_I64)
+    H, W = reference.shape[0], reference.shape[1]
+    x, y, w, h = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+    empty = (w < 1) | (h < 1)
+    outside = (x < 0) | (y < 0) | (w > W - x) | (h > H - y)
+    large = (w * h > _U16_MAX_PIXELS) if reference.dtype == np.uint16 else np.zeros(len(b), bool)
+    bad = empty | outside | large
+    if bad.any():
+        k = int(np.argmax(bad))
+        blk = tuple(int(v) for v in b[k])
+        if empty[k]:
+            raise ValueError("blocks[%d]: a block needs w >= 1 and h >= 1 (got %r)" % (k, blk))
+        if outside[k]:
+            raise ValueError("blocks[%d]: block %r is not inside the %d x %d reference" % (k, blk, H, W))
+        raise ValueError("blocks[%d]: uint16 blocks of more than 2^21 pixels are not supported (their exact correlations "
+                         "would pass 2^53)" % k)
+    return b
+
+
+def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, method: int = TM_CCOEFF_NORMED, *,
+                refine: bool = False, context=None):
+    """
+    Where every block of ``reference`` is in ``image``: ``(positions, scores)``, ``positions[k]`` the int64 ``[x, y]``
+    (image coordinates) and ``scores[k]`` the float32 score of the single hit of
+
+        findMatchesInBoxes([("b", reference[y:y + h, x:x + w])], image, [search_box(blocks[k], margin, image.shape)],
+                           method, N_object=1)[0]
+
+    in one native call.  ``blocks``: a sequence or an (N, 4) integer array of ``(x, y, w, h)``, each inside the reference
+    (``grid`` makes regular ones).  ``refine=True``: float64 positions, ``refineHits``' of each hit (the module's
+    docstring).  ``context``: the _lib.Context to run on (default: the process's); its templates are not touched.
+    ``displacements(blocks, positions)`` gives the displacement field.
+    """
+    _check_images(reference, image)
+    if not _is_int(method) or method not in (0, 1, 2, 3, 4, 5):
+        raise ValueError("matchBlocks takes methods 0..5 (got %r)" % (method,))
+    if not _is_int(margin) or margin < 0:
+        raise ValueError("margin must be an integer >= 0 (got %r)" % (margin,))
+    if not isinstance(refine, bool):
+        raise ValueError("refine must be True or False (got %r)" % (refine,))
+    b = _check_blocks(blocks, reference)
+    n = len(b)
+    if n == 0:
+        return np.zeros((0, 2), dtype=np.float64 if refine else _I64), np.zeros(0, dtype=np.float32)
+    rec = np.empty(n, dtype=_lib.BLOCK_DTYPE)
+    rec["x"], rec["y"], rec["w"], rec["h"] = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+    # (a margin past the images' larger side clips to the whole image, as a margin of that side does)
+    m = int(min(margin, max(image.shape[0], image.shape[1])))
+    ctx = context or _lib.default_context()     # (only now: every argument error comes before "no GPU")
+    with ctx.lock:
+        raw, nbhd = ctx.match_blocks(reference, image, rec, m, int(method), refine)
+    positions = np.stack((raw["x"], raw["y"]), axis=1).astype(_I64)
+    scores = raw["score"].astype(np.float32)
+    if refine:          # (one fit over every block: refineHits' numbers by construction)
+        ox, oy = subpixel.fit_offsets(nbhd, method)
+        positions = positions.astype(np.float64) + np.stack((ox, oy), axis=1)
+    return positions, scores

@@ -1,0 +1,294 @@
+// libmtm_hip.so - block matching between two images of one shape in one call (mtm_match_blocks): every block
+// of the reference image is a template, searched in the other image inside the block's own box widened by a margin - what
+// mtm_find_matches_boxes returns in MTM_PEAKS_GLOBAL mode for the block's pixels set as a template.  The templates never
+// exist on the host: both images go up as one stack of two (the reference in rows 0 .., the image below it),
+// blocks_gather_kernel cuts every block out of the reference's planes into planes of the call's own - the layout
+// prepare_window_templates gives a template set - and computes the constants mtm_set_templates would give it
+// (templ_stats_from_sums_inl, the single source of host and device); blocks_score_kernel scores the tiles of every block's
+// map with the window kernels' exact sums (win_tile_sums_u8 / win_tile_sums_u16, win_score: the exhaustive map's float32
+// bits) and keeps each block's extremum in a key, no map is written; blocks_nbhd_kernel, where asked for, decodes the keys
+// and scores the 3 x 3 neighbourhoods in the whole image's map.  plan_blocks (mtm_host.cpp) checks the blocks and lays out
+// the unit and tile tables and the chunks; the host waits once per call.  uint8 (1 or 3 channels) and single-channel
+// uint16.  The template set of the context is neither read nor written.
+#include <type_traits>
+
+#include "mtm_ctx.h"
+#include "mtm_device_util.hip.h"
+#include "mtm_k_nbhd.hip.h"
+#include "mtm_k_window.hip.h"
+#include "mtm_templ_stats.h"
+
+using namespace mtm;
+using namespace mtmi;
+
+namespace mtm {
+
+static_assert(kTrackTile == kWinTile, "plan_blocks tiles the maps as the window kernels walk them");
+
+constexpr size_t kBlockLaunchGroups = (size_t)1 << 22;      // most work-groups of one blocks_* launch
+
+// Grid: one 256-thread work-group per block (launch slice; block k = k0 + blockIdx.x).  `ref` is the reference image - the
+// stack's planes entered at its first row and bounded by its own `rows` -: uint8, plane c at ref.u8 + c * u8_plane;
+// uint16, the high-byte plane with `lo_b` the low-byte plane XOR 0x80.  The block's window is copied into the call's
+// template planes at tpx + toff[k] - uint8: [CH][h][w], tightly packed; uint16: the high-byte plane, then the low-byte
+// plane, unbiased - and the sums of its pixels and of their squares per channel are reduced in uint64 (exact: at most 2^21
+// uint16 pixels, sum v^2 < 2^53) in a fixed order; thread 0 writes the constants templ_stats_from_sums_inl gives for them -
+// what mtm_set_templates would compute for the block set as a template - and the block's size into td[k] (the fields
+// prepare_box_td fills; the others are zero).  A block that is not inside the reference is left alone (plan_blocks
+// refuses it: a window that did not lie inside would be read out of bounds).
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void blocks_gather_kernel(ImageDev ref, const uint8_t* __restrict__ lo_b,
+                                                            const mtm_block* __restrict__ blocks, int k0,
+                                                            uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
+                                                            TemplDev* __restrict__ td, int method) {
+    __shared__ unsigned long long red[4];
+    const int k = k0 + (int)blockIdx.x;
+    const mtm_block B = blocks[k];
+    const int h = B.h, w = B.w;
+    // (the same for the whole work-group: before any barrier)
+    if (w < 1 || h < 1 || B.x < 0 || B.y < 0 || B.x > ref.cols - w || B.y > ref.rows - h) return;
+    const int tid = threadIdx.x;
+    const uint32_t n = (uint32_t)h * (uint32_t)w;           // (< 2^31: plan_blocks)
+    uint8_t* tp = tpx + toff[k];
+    const size_t base = (size_t)B.y * ref.u8_pitch + (size_t)B.x;
+    unsigned long long s1[CH], s2[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        s1[c] = 0ull;
+        s2[c] = 0ull;
+        for (uint32_t p = (uint32_t)tid; p < n; p += 256u) {
+            const size_t ip = base + (size_t)(p / (uint32_t)w) * ref.u8_pitch + (size_t)(p % (uint32_t)w);
+            uint32_t v;
+            if constexpr (U16) {
+                const uint32_t hi = ref.u8[ip], lo = (uint32_t)lo_b[ip] ^ 0x80u;
+                tp[p] = (uint8_t)hi;
+                tp[(size_t)n + p] = (uint8_t)lo;
+                v = (hi << 8) | lo;
+            } else {
+                v = ref.u8[(size_t)c * ref.u8_plane + ip];
+                tp[(size_t)c * n + p] = (uint8_t)v;
+            }
+            s1[c] += v;
+            s2[c] += (unsigned long long)v * v;
+        }
+    }
+    double sum[kMaxChans] = {0.0, 0.0, 0.0, 0.0}, sumsq[kMaxChans] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        sum[c] = (double)sub_reduce(s1[c], red);
+        sumsq[c] = (double)sub_reduce(s2[c], red);
+    }
+    if (tid == 0) {
+        const TemplStats st = templ_stats_from_sums_inl(sum, sumsq, 0.0, false, h, w, CH, method);
+        TemplDev T{};
+#pragma unroll
+        for (int c = 0; c < kMaxChans; ++c) T.mean[c] = st.mean[c];
+        T.templ_norm = st.templ_norm;
+        T.templ_sum2 = st.templ_sum2;
+        T.all_ones = st.all_ones;
+        T.rows = h;
+        T.cols = w;
+        td[k] = T;
+    }
+}
+
+// Grid: one work-group per tile of the chunk's part of the tile table (launch slice).  `img` is the searched image, entered
+// and bounded as `ref` above: no row of the reference is read.  The windows of tile (ty0, tx0) of block u0's map are summed
+// and scored exactly as boxes_score_kernel does - the same float32 bits -, with the gathered template of the block, and
+// instead of a map the tile's best output goes into keys[u0] (track_merge_key): order(quality) << 32 | ~index, one
+// atomicMax per wave.  Every tile of the table lies inside its map (plan_blocks); a (2 margin + 1)^2 map fills only part of
+// its tiles.
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void blocks_score_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
+                                                           const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
+                                                           const TemplDev* __restrict__ td, const TrackUnit* __restrict__ units,
+                                                           const TrackTile* __restrict__ tiles, int method, int mode_min,
+                                                           unsigned long long* __restrict__ keys) {
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
+    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
+    const TrackTile K = tiles[blockIdx.x];
+    const TrackUnit U = units[K.u0];
+    const TemplDev T = td[K.u0];
+    const int h = T.rows, w = T.cols;
+    const uint8_t* tp = tpx + toff[K.u0];
+    const int tid = threadIdx.x;
+    const double inv_area = 1.0 / ((double)h * (double)w);
+    unsigned long long corr, s2, s1[CH];
+    if constexpr (U16)
+        win_tile_sums_u16(Tl[0], Tl[1], Il[0], Il[1], img.u8, lo_b, img.u8_pitch, img.rows, img.cols, tp, h, w, U.y0 + K.ty0,
+                          U.x0 + K.tx0, corr, s1[0], s2);
+    else
+        win_tile_sums_u8<CH>(Tl[0], Il[0], img.u8, img.u8_plane, img.u8_pitch, img.rows, img.cols, tp, h, w, U.y0 + K.ty0,
+                             U.x0 + K.tx0, corr, s1, s2);
+    const int y = K.ty0 + tid / kWinTile, x = K.tx0 + tid % kWinTile;
+    track_merge_key(y < U.oh && x < U.ow, 0xFFFFFFFFull - (unsigned long long)((long long)y * U.ow + x), mode_min,
+                    [&] { return win_score<CH>(method, T, inv_area, corr, s1, s2); }, keys + K.u0);
+}
+
+// Grid: one 256-thread work-group per block (launch slice; block k = k0 + blockIdx.x), after the chunk's score launches:
+// the key of the block is decoded (decode_quality_key, mtm_host.cpp: the extremum's index in the block's map, moved by the
+// map's origin into image coordinates) and the 3 x 3 neighbourhood of that window in the WHOLE image's map goes into
+// out[9 k ..]: sub_nbhd_int's sums and win_score, mtm_hit_neighbourhoods' float32 bits, NaN outside the map.  A block
+// without a key (no output scored) gets nine NaNs and reads no pixel.
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void blocks_nbhd_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
+                                                          const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
+                                                          const TemplDev* __restrict__ td, const TrackUnit* __restrict__ units,
+                                                          const unsigned long long* __restrict__ keys, int k0, int method,
+                                                          float* __restrict__ out) {
+    constexpr int kKind = U16 ? kSubU16 : kSubU8;
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
+    __shared__ __attribute__((aligned(16))) SubImageLds Il[U16 ? 2 : 1];
+    __shared__ unsigned long long red[4];
+    const int k = k0 + (int)blockIdx.x;
+    const TrackUnit U = units[k];
+    const TemplDev T = td[k];
+    const unsigned long long key = keys[k];
+    const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull);
+    const int px = U.x0 + (int)(idx % (uint32_t)U.ow), py = U.y0 + (int)(idx / (uint32_t)U.ow);
+    const int tid = threadIdx.x;
+    float score = NAN;
+    // (the same for the whole work-group: before any barrier)
+    if (key != 0ull && px >= 0 && py >= 0 && px <= img.cols - T.cols && py <= img.rows - T.rows)
+        score = sub_nbhd_int<CH, kKind>(Tl, Il, red, img.u8, img.u8_plane, lo_b, img.u8_pitch, img.rows, img.cols,
+                                        tpx + toff[k], nullptr, T, px, py, method);
+    if (tid < 9) out[(size_t)k * 9 + tid] = score;
+}
+
+}  // namespace mtm
+
+namespace {
+
+// f(ch, u16) with the images' pixel kind as compile-time constants, the kernels' <CH, U16>.
+template <class F>
+int blocks_dispatch(int dtype, int chans, F&& f) {
+    if (dtype == MTM_U16) return f(std::integral_constant<int, 1>{}, std::true_type{});
+    if (chans == 1) return f(std::integral_constant<int, 1>{}, std::false_type{});
+    return f(std::integral_constant<int, 3>{}, std::false_type{});
+}
+
+// The image of rows row_off .. row_off + rows - 1 of the stack `st`: its planes entered at that row and bounded by `rows`,
+// so that pixels below it read as zero whatever the stack holds there.
+ImageDev stack_view(const ImageDev& st, int row_off, int rows) {
+    ImageDev v = st;
+    v.u8 = st.u8 + (size_t)row_off * st.u8_pitch;
+    v.f32 = nullptr;
+    v.rows = rows;
+    return v;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mtm_match_blocks(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                     int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
+                     int n_blocks, int margin, int method, mtm_hit* out, float* nbhd) {
+    const char* who = "mtm_match_blocks";
+    if (!c || n_blocks < 0 || margin < 0 || (n_blocks > 0 && (!blocks || !out)) || method < MTM_TM_SQDIFF ||
+        method > MTM_TM_CCOEFF_NORMED) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    MTMC(check_image_args(reference, rows, cols, chans, dtype, reference_stride_bytes, who));
+    MTMC(check_image_args(image, rows, cols, chans, dtype, image_stride_bytes, who));
+    if (!((dtype == MTM_U8 && (chans == 1 || chans == 3)) || (dtype == MTM_U16 && chans == 1))) {
+        set_error(std::string(who) + ": takes uint8 images with 1 or 3 channels and single-channel uint16 images");
+        return MTM_E_INVALID;
+    }
+    // (the two images are one stack: its rows stay within what a layout launch's grid holds)
+    if (2ll * rows > kBatchMaxRows) {
+        set_error(std::string(who) + ": images of more than " + std::to_string(kBatchMaxRows / 2) + " rows");
+        return MTM_E_INVALID;
+    }
+    BlockPlan P;
+    MTMC(plan_blocks(rows, cols, chans, dtype, blocks, n_blocks, margin, 4 * (long long)c->boxes_max_floats, who, P));
+    if (n_blocks == 0) return MTM_OK;
+
+    HIPC(hipSetDevice(c->device));
+    c->timing = mtm_timing{};
+    c->maps_valid = false;
+    c->last_hits.clear();
+    const size_t n = (size_t)n_blocks;
+    MTMC(c->blk_tpx.ensure(P.max_bytes));
+    MTMC(c->blk_toff.ensure(sizeof(long long) * n));
+    MTMC(c->blk_td.ensure(sizeof(TemplDev) * n));
+    MTMC(c->blk_blocks.ensure(sizeof(mtm_block) * n));
+    MTMC(c->blk_units.ensure(sizeof(TrackUnit) * n));
+    MTMC(c->blk_tiles.ensure(sizeof(TrackTile) * P.tiles.size()));
+    MTMC(c->blk_keys.ensure(sizeof(unsigned long long) * n));
+    if (nbhd) MTMC(c->blk_nbhd.ensure(sizeof(float) * 9 * n));
+
+    // ONE upload of each image: the stack's rows 0 .. rows - 1 are the reference, rows .. 2 rows - 1 the image
+    adopt_image(c, 2 * rows, cols, chans, dtype);
+    MTMC(upload_image_pair(c, c->slot[c->cur], reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans,
+                           dtype, c->stream));
+    const ImageDev st = image_dev(c);
+    const uint8_t* st_lo = c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane;        // uint16: [high ^ 0x80][low ^ 0x80]
+    const ImageDev ref = stack_view(st, 0, rows), img = stack_view(st, rows, rows);
+    const uint8_t* ref_lo = st_lo;
+    const uint8_t* img_lo = st_lo + (size_t)rows * st.u8_pitch;
+
+    HIPC(hipEventRecord(c->ev[0], c->stream));
+    HIPC(hipMemcpyAsync(c->blk_blocks.p, blocks, sizeof(mtm_block) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_toff.p, P.toff.data(), sizeof(long long) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_units.p, P.units.data(), sizeof(TrackUnit) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_tiles.p, P.tiles.data(), sizeof(TrackTile) * P.tiles.size(), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemsetAsync(c->blk_keys.p, 0, sizeof(unsigned long long) * n, c->stream));
+
+    const int mode_min = method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED ? 1 : 0;
+    uint8_t* tpx = c->blk_tpx.as<uint8_t>();
+    const long long* toff = c->blk_toff.as<long long>();
+    TemplDev* td = c->blk_td.as<TemplDev>();
+    const TrackUnit* units = c->blk_units.as<TrackUnit>();
+    unsigned long long* keys = c->blk_keys.as<unsigned long long>();
+    // a chunk's launch chain - gather, score, [neighbourhoods] - in stream order: the next chunk's gather overwrites the
+    // template planes behind this chunk's last reader, and the host waits for none of them
+    MTMC(blocks_dispatch(dtype, chans, [&](auto ch, auto u16) -> int {
+        constexpr int CH = decltype(ch)::value;
+        constexpr bool U16 = decltype(u16)::value;
+        for (const BlockChunk& C : P.chunks) {
+            for (size_t b0 = (size_t)C.b0; b0 < (size_t)C.b1; b0 += kBlockLaunchGroups) {
+                const unsigned nb = (unsigned)std::min(kBlockLaunchGroups, (size_t)C.b1 - b0);
+                hipLaunchKernelGGL((blocks_gather_kernel<CH, U16>), dim3(nb), dim3(256), 0, c->stream, ref, ref_lo,
+                                   c->blk_blocks.as<mtm_block>(), (int)b0, tpx, toff, td, method);
+                HIPC(hipGetLastError());
+            }
+            for (size_t t0 = C.t0; t0 < C.t1; t0 += kBlockLaunchGroups) {
+                const unsigned nt = (unsigned)std::min(kBlockLaunchGroups, C.t1 - t0);
+                hipLaunchKernelGGL((blocks_score_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo, tpx, toff, td,
+                                   units, c->blk_tiles.as<TrackTile>() + t0, method, mode_min, keys);
+                HIPC(hipGetLastError());
+            }
+            for (size_t b0 = (size_t)C.b0; nbhd && b0 < (size_t)C.b1; b0 += kBlockLaunchGroups) {
+                const unsigned nb = (unsigned)std::min(kBlockLaunchGroups, (size_t)C.b1 - b0);
+                hipLaunchKernelGGL((blocks_nbhd_kernel<CH, U16>), dim3(nb), dim3(256), 0, c->stream, img, img_lo, tpx, toff, td,
+                                   units, keys, (int)b0, method, c->blk_nbhd.as<float>());
+                HIPC(hipGetLastError());
+            }
+        }
+        return MTM_OK;
+    }));
+
+    // the keys (and neighbourhoods) come back behind the call's single wait
+    std::vector<unsigned long long> hkeys(n);
+    HIPC(hipEventRecord(c->ev[1], c->stream));
+    HIPC(hipMemcpyAsync(hkeys.data(), keys, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
+    if (nbhd) HIPC(hipMemcpyAsync(nbhd, c->blk_nbhd.p, sizeof(float) * 9 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
+    c->timing.n_hits = (int64_t)n;
+    for (size_t k = 0; k < n; ++k) {
+        const TrackUnit& u = P.units[k];
+        mtm_hit r = decode_quality_key(hkeys[k], mode_min != 0, (int)k, u.ow, blocks[k].w, blocks[k].h);
+        r.x += u.x0;
+        r.y += u.y0;
+        out[k] = r;
+    }
+    // the stack is none of the caller's images: no current image, no published maps
+    c->have_image = false;
+    return MTM_OK;
+}
+
+}  // extern "C"

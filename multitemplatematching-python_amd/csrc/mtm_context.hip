@@ -186,6 +186,17 @@ int upload_image_stack(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* const* px
     return convert_raw(sl, g, cols, chans, dtype, stream, 1);
 }
 
+int upload_image_pair(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* px0, int64_t stride0, const void* px1, int64_t stride1,
+                      int rows, int cols, int chans, int dtype, hipStream_t stream) {
+    SlotGeom g{};
+    MTMC(prepare_slot(c, sl, 2 * rows, cols, chans, dtype, stream, 1, &g));
+    const size_t tight = (size_t)cols * chans * elem_size(dtype);
+    HIPC(hipMemcpy2DAsync(sl.raw.p, tight, px0, (size_t)stride0, tight, rows, hipMemcpyHostToDevice, stream));
+    HIPC(hipMemcpy2DAsync(sl.raw.as<uint8_t>() + (size_t)rows * tight, tight, px1, (size_t)stride1, tight, rows,
+                          hipMemcpyHostToDevice, stream));
+    return convert_raw(sl, g, cols, chans, dtype, stream, 1);
+}
+
 int derive_downscaled_u8(mtm_ctx* dst, const mtm_ctx::ImageSlot& src, int src_rows, int src_cols, int chans, int factor,
                          hipStream_t stream) {
     mtm_ctx::ImageSlot& sl = dst->slot[dst->cur];
@@ -369,7 +380,9 @@ void mtm_ctx_destroy(mtm_ctx* c) {
     if (c->pyr_sub) mtm_ctx_destroy(c->pyr_sub);
     for (DevBuf* b : {&c->win_tpx, &c->win_toff, &c->win_buf, &c->win_hits, &c->win_flags, &c->pyr_wins, &c->box_td,
                       &c->box_units, &c->box_tiles, &c->trk_units, &c->trk_tiles, &c->trk_keys, &c->trk_out,
-                      &c->trk_nbhd, &c->trk_tpx, &c->trk_toff, &c->trk_td, &c->trk_pass, &c->trk_lost, &c->trk_sets})
+                      &c->trk_nbhd, &c->trk_tpx, &c->trk_toff, &c->trk_td, &c->trk_pass, &c->trk_lost, &c->trk_sets,
+                      &c->blk_tpx, &c->blk_toff, &c->blk_td, &c->blk_blocks, &c->blk_units, &c->blk_tiles, &c->blk_keys,
+                      &c->blk_nbhd})
         b->release();
     for (auto& sl : c->slot)
         for (DevBuf* b : {&sl.raw, &sl.u8, &sl.u8b, &sl.f32}) b->release();
@@ -542,7 +555,8 @@ int mtm_debug_poison(mtm_ctx* c, int pattern_byte, int what) {
         for (mtm_ctx::DevBuf* d : {&c->stats, &c->stats_rsq, &c->stats_blk, &c->hs1, &c->hs2, &c->raw16, &c->slab_raw,
                                    &c->stats_hi, &c->maps, &c->sq_planes, &c->mbf_maps, &c->f32_sq, &c->mbf_stats, &c->mbf_mu,
                                    &c->trk_units, &c->trk_keys, &c->trk_out, &c->trk_nbhd, &c->trk_tpx, &c->trk_toff, &c->trk_td,
-                                   &c->trk_pass, &c->trk_lost, &c->trk_sets, &c->sub_pts, &c->sub_out, &c->nms_buf, &c->peak_dbg, &c->stats_dbg})
+                                   &c->trk_pass, &c->trk_lost, &c->trk_sets, &c->blk_tpx, &c->blk_toff, &c->blk_td, &c->blk_blocks, &c->blk_units,
+                                   &c->blk_tiles, &c->blk_keys, &c->blk_nbhd, &c->sub_pts, &c->sub_out, &c->nms_buf, &c->peak_dbg, &c->stats_dbg})
             MTMC(fill(*d));
         for (auto& ln : c->lanes)
             for (mtm_ctx::DevBuf* d : {&ln.stats, &ln.stats_rsq, &ln.stats_blk, &ln.hs1, &ln.hs2, &ln.raw16, &ln.slab_raw, &ln.stats_hi})

@@ -2,7 +2,8 @@
 // translation units share.  Units: mtm_context.hip (context, options, image upload), mtm_placement.hip (template sets ->
 // size classes, packs, constants), mtm_launch.hip (window statistics and score-map launches), mtm_api.hip
 // (mtm_find_matches and friends: peak extraction, hit lists), mtm_comm.hip (RCCL hit exchange), mtm_pyramid.hip (the
-// coarse-to-fine search), mtm_boxes.hip (many searchBoxes in one call), mtm_subpixel.hip (hit neighbourhoods).  Not part of the ABI.
+// coarse-to-fine search), mtm_boxes.hip (many searchBoxes in one call), mtm_subpixel.hip (hit neighbourhoods), mtm_blocks.hip (block matching
+// between two images).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -359,6 +360,12 @@ struct mtm_ctx {
     // mtm_track_boxes_sets: the first unit of every track's set in trk_units (TrackPlan::set_off, n_tracks + 1 offsets);
     // the other entry points hand the update kernels no offsets (track k is unit k).
     DevBuf trk_sets;
+    // mtm_match_blocks (mtm_blocks.hip): the call's own templates - byte planes gathered from the reference image (block k's
+    // at blk_toff[k] in blk_tpx, prepare_window_templates' layout, one chunk of blocks at a time) and the constants
+    // blocks_gather_kernel computes for them (blk_td) -, the block records, the unit and tile tables (BlockPlan), one
+    // extremum key per block and the records' 3 x 3 neighbourhoods.  The template set's tables (win_tpx, win_toff, box_td)
+    // and their generations are never touched.
+    DevBuf blk_tpx, blk_toff, blk_td, blk_blocks, blk_units, blk_tiles, blk_keys, blk_nbhd;
     // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
     // template set sub_gen) and the per-call point table and scores.
     uint64_t sub_gen = 0;
@@ -494,6 +501,9 @@ int upload_image(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* src, int64_t sr
                  int chans, int dtype, hipStream_t stream, int factor = 1);
 int upload_image_stack(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* const* px, int n, int64_t src_stride, int rows,
                        int cols, int chans, int dtype, hipStream_t stream);
+// Two images of one shape as one image of 2 * rows rows, each copied from its own rows and stride (mtm_match_blocks).
+int upload_image_pair(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* px0, int64_t stride0, const void* px1, int64_t stride1,
+                      int rows, int cols, int chans, int dtype, hipStream_t stream);
 void adopt_image(mtm_ctx* c, int rows, int cols, int chans, int dtype);
 // (BlobTempl: mtm_internal.h)
 int parse_templ_blob(const std::vector<uint8_t>& b, std::vector<BlobTempl>& out, const char* who, bool u16_ok);

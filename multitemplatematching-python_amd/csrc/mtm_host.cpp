@@ -633,6 +633,53 @@ int plan_tracks(const std::vector<BlobTempl>& tl, int rows, int cols, int chans,
     return MTM_OK;
 }
 
+// ---- the host plan of a block-matching call (mtm_blocks.hip)
+int plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* blocks, int n_blocks, int margin,
+                long long budget_bytes, const char* who, BlockPlan& P) {
+    P = BlockPlan{};
+    P.units.reserve((size_t)n_blocks);
+    P.toff.reserve((size_t)n_blocks);
+    BlockChunk cur{0, 0, 0, 0, 0};
+    for (int k = 0; k < n_blocks; ++k) {
+        const mtm_block& b = blocks[k];
+        auto fail = [&](const char* what) {
+            set_error(std::string(who) + ": block " + std::to_string(k) + what);
+            return MTM_E_INVALID;
+        };
+        if (b.w < 1 || b.h < 1) return fail(": empty block");
+        if (b.x < 0 || b.y < 0 || b.w > cols - b.x || b.h > rows - b.y) return fail(": block outside the reference");
+        const long long area = (long long)b.w * b.h;
+        // (uint16: correlations of up to 2^21 pixels stay below 2^53, exact in float64 as the exhaustive kernels need)
+        if (dtype == MTM_U16 && area > (1ll << 21)) return fail(": uint16 block of more than 2^21 pixels");
+        if (area >= (1ll << 31)) return fail(": block of 2^31 pixels or more");       // (the gather kernel's pixel index)
+        // the search box (MTM.blocks.search_box) and the block's map over it
+        const long long x0 = std::max(0ll, (long long)b.x - margin), y0 = std::max(0ll, (long long)b.y - margin);
+        const long long x1 = std::min((long long)cols, (long long)b.x + b.w + margin);
+        const long long y1 = std::min((long long)rows, (long long)b.y + b.h + margin);
+        const long long oh = y1 - y0 - b.h + 1, ow = x1 - x0 - b.w + 1;
+        if (oh * ow >= (1ll << 32)) return fail(": map of 2^32 outputs or more");
+        const size_t bytes = (size_t)area * (size_t)(dtype == MTM_U16 ? 2 : chans);
+        if (k > cur.b0 && (long long)(cur.bytes + bytes) > budget_bytes) {
+            cur.b1 = k;
+            cur.t1 = P.tiles.size();
+            P.chunks.push_back(cur);
+            cur = BlockChunk{k, k, P.tiles.size(), P.tiles.size(), 0};
+        }
+        P.units.push_back(TrackUnit{k, (int)y0, (int)x0, (int)oh, (int)ow});
+        P.toff.push_back((long long)cur.bytes);
+        cur.bytes += bytes;
+        P.max_bytes = std::max(P.max_bytes, cur.bytes);
+        for (int ty = 0; ty < (int)oh; ty += kTrackTile)
+            for (int tx = 0; tx < (int)ow; tx += kTrackTile) P.tiles.push_back(TrackTile{k, 1, ty, tx});
+    }
+    if (n_blocks > 0) {
+        cur.b1 = n_blocks;
+        cur.t1 = P.tiles.size();
+        P.chunks.push_back(cur);
+    }
+    return MTM_OK;
+}
+
 }  // namespace mtm
 
 extern "C" {
@@ -673,6 +720,38 @@ int mtm_debug_templ_stats(const void* px, int rows, int cols, int chans, int dty
     out7[4] = st.templ_norm;
     out7[5] = st.templ_sum2;
     out7[6] = (double)st.all_ones;
+    return MTM_OK;
+}
+
+int mtm_debug_plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* blocks, int n_blocks, int margin,
+                          int64_t budget_bytes, int32_t* tiles, int64_t tile_cap, int64_t* n_tiles, int32_t* chunk_of,
+                          int64_t* toff, int32_t* maps) {
+    if (rows < 1 || cols < 1 || n_blocks < 0 || (n_blocks > 0 && !blocks) || margin < 0 || tile_cap < 0 ||
+        !((dtype == MTM_U8 && (chans == 1 || chans == 3)) || (dtype == MTM_U16 && chans == 1))) {
+        mtm::set_error("mtm_debug_plan_blocks: bad arguments");
+        return MTM_E_INVALID;
+    }
+    mtm::BlockPlan P;
+    const int rc = mtm::plan_blocks(rows, cols, chans, dtype, blocks, n_blocks, margin, budget_bytes, "mtm_debug_plan_blocks", P);
+    if (rc != MTM_OK) return rc;
+    if (n_tiles) *n_tiles = (int64_t)P.tiles.size();
+    for (size_t i = 0; tiles && i < P.tiles.size() && (int64_t)i < tile_cap; ++i) {
+        tiles[3 * i] = P.tiles[i].u0;
+        tiles[3 * i + 1] = P.tiles[i].ty0;
+        tiles[3 * i + 2] = P.tiles[i].tx0;
+    }
+    for (size_t ci = 0; chunk_of && ci < P.chunks.size(); ++ci)
+        for (int k = P.chunks[ci].b0; k < P.chunks[ci].b1; ++k) chunk_of[k] = (int32_t)ci;
+    for (int k = 0; k < n_blocks; ++k) {
+        if (toff) toff[k] = P.toff[(size_t)k];
+        if (maps) {
+            const mtm::TrackUnit& u = P.units[(size_t)k];
+            maps[4 * k] = u.x0;
+            maps[4 * k + 1] = u.y0;
+            maps[4 * k + 2] = u.ow;
+            maps[4 * k + 3] = u.oh;
+        }
+    }
     return MTM_OK;
 }
 

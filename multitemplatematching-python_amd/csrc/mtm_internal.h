@@ -143,6 +143,28 @@ int plan_tracks(const std::vector<BlobTempl>& tl, int rows, int cols, int chans,
                 int n_tracks, int margin, bool reacq, const int32_t* set_off, const int32_t* set_idx, const char* who,
                 TrackPlan& plan);
 
+// ---- the host plan of a block-matching call (mtm_match_blocks, mtm_blocks.hip)
+
+// Blocks b0 .. b1 - 1 run together: their tiles are tiles[t0 .. t1 - 1], their gathered template planes fill `bytes`.
+struct BlockChunk {
+    int b0, b1;
+    size_t t0, t1;
+    size_t bytes;
+};
+struct BlockPlan {
+    std::vector<TrackUnit> units;           // block k: t = k, the image pixel of its map's output (0, 0), the map's size
+    std::vector<long long> toff;            // byte offset of block k's template planes in its chunk's buffer
+    std::vector<TrackTile> tiles;           // {k, 1, ty0, tx0}: block after block, row-major over each block's map
+    std::vector<BlockChunk> chunks;         // whole blocks, in order, each within the budget (a single block may pass it)
+    size_t max_bytes = 0;                   // the largest chunk's template bytes
+};
+// The blocks of a call checked and laid out: images of rows x cols x chans `dtype` pixels; block k's search box is its own
+// box widened by `margin` on every side and clipped to the image (MTM.blocks.search_box), its map that of a template of
+// the block's size over the box.  Chunks hold whole blocks while their template bytes - w h chans, uint16: 2 w h - stay
+// within budget_bytes.  MTM_OK, or the code and message (set_error, prefixed `who`) of the first block that is not valid.
+int plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* blocks, int n_blocks, int margin,
+                long long budget_bytes, const char* who, BlockPlan& plan);
+
 // float32-faithful restatement of cv2.dnn.NMSBoxes as called by MTM.NMS
 void nms_boxes(const mtm_hit* hits, int64_t n, const float* scores, float score_threshold,
                float nms_threshold, std::vector<int32_t>& keep);

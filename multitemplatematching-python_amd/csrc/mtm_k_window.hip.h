@@ -310,4 +310,25 @@ __device__ __forceinline__ float win_score(int method, const TemplDev& T, double
         [&]() { return window_norm(sum2, wnd_mean2); }, T, CH);
 }
 
+// The key of this lane's output - order(quality) << 32 | pos, pos = ~(index in the unit's current map), quality score()
+// or its negative for the difference methods; 0 for a lane outside the map, which never calls score() -, reduced per
+// wave and merged into *slot with one atomicMax per wave, as boxes_peaks_kernel keys a unit's extremum in global mode.
+// (The tracking score kernels, mtm_track.hip, and blocks_score_kernel, mtm_blocks.hip.)
+template <class Score>
+__device__ __forceinline__ void track_merge_key(bool inside, unsigned long long pos, int mode_min, Score&& score,
+                                                unsigned long long* __restrict__ slot) {
+    unsigned long long key = 0ull;
+    if (inside) {
+        const float s = score();
+        const float v = mode_min ? -s : s;
+        key = ((unsigned long long)mf_float_order(v) << 32) | pos;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = __shfl_xor(key, off);
+        key = o > key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0 && key != 0ull) atomicMax(slot, key);
+}
+
 }  // namespace mtm

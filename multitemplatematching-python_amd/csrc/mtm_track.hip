@@ -48,26 +48,6 @@ constexpr unsigned kTrackReacquireGrid = 2048;            // work-groups of a tr
 constexpr size_t kTrackLaunchTiles = (size_t)1 << 22;     // most work-groups (tiles) of one track_score_kernel launch
 constexpr size_t kTrackLaunchNbhd = (size_t)1 << 22;      // most work-groups (tracks) of one track_nbhd_kernel launch
 
-// The key of this lane's output - order(quality) << 32 | pos, pos = ~(index in the unit's current map), quality score()
-// or its negative for the difference methods; 0 for a lane outside the map, which never calls score() -, reduced per
-// wave and merged into *slot with one atomicMax per wave, as boxes_peaks_kernel keys a unit's extremum in global mode.
-template <class Score>
-__device__ __forceinline__ void track_merge_key(bool inside, unsigned long long pos, int mode_min, Score&& score,
-                                                unsigned long long* __restrict__ slot) {
-    unsigned long long key = 0ull;
-    if (inside) {
-        const float s = score();
-        const float v = mode_min ? -s : s;
-        key = ((unsigned long long)mf_float_order(v) << 32) | pos;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off);
-        key = o > key ? o : key;
-    }
-    if ((threadIdx.x & 63) == 0 && key != 0ull) atomicMax(slot, key);
-}
-
 // The tile (ty0, tx0) of unit U's map: the windows are summed and scored exactly as boxes_score_kernel does
 // (win_tile_sums_u8 / win_tile_sums_u16, win_score: the same float32 bits), and instead of a map the tile's best output
 // goes into *slot (track_merge_key).  A whole-frame unit has y0 = x0 = 0.

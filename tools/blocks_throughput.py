@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Milliseconds per call, from numpy arrays to numpy arrays, of three ways to get the displacement of every block of a
+grid between two images, one JSON line per workload:
+  blocks        - matchBlocks(reference, image, grid, margin)
+  blocks_refine - matchBlocks(..., refine=True): the same with sub-pixel positions
+  loop          - what a user writes without the call: the blocks cut out of the reference on the host as templates, each
+                  with its search box as a region, through one findMatchesInBoxes(..., N_object=1) - template cutting,
+                  region building and the conversion of the hit lists to arrays included
+The call's positions and float32 score bits are checked equal to the loop's (``equal_to_loop``), the refined positions
+equal to refineHits' of the loop's hits (``refine_equal``, outside the timed part).
+
+Data from synth.py: a photograph-like reference (smooth_u8; uint16 = 257 x that plus noise in the low byte) and, as the
+image, the reference moved by a few pixels (wrapping around) with a little noise.  Each method is warmed up first; the
+three calls are interleaved within a repetition; medians over the repetitions.
+
+Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "multitemplatematching-python_amd"))
+
+# name, (rows, cols), channels, dtype, block side (= step), margin
+WORKLOADS = [
+    ("K1", (1080, 1920), 1, "uint8", 32, 8),
+    ("K2", (2048, 2048), 1, "uint16", 48, 12),
+    ("K3", (2160, 3840), 3, "uint8", 64, 16),
+]
+
+
+def workload(spec, seed=0, shift=(3, -2)):
+    import synth
+    name, hw, chans, dtype, side, margin = spec
+    planes = [synth.smooth_u8(seed + c, hw) for c in range(chans)]
+    ref = planes[0] if chans == 1 else np.ascontiguousarray(np.stack(planes, axis=2))
+    rng = np.random.default_rng(seed + 10)
+    top = 255
+    if dtype == "uint16":
+        ref = (ref.astype(np.uint16) * 257 + rng.integers(0, 64, size=ref.shape, dtype=np.uint16)).astype(np.uint16)
+        top = 65535
+    img = np.roll(ref, (shift[1], shift[0]), axis=(0, 1)).astype(np.int64) + rng.integers(-2, 3, size=ref.shape)
+    return ref, np.clip(img, 0, top).astype(ref.dtype)
+
+
+def run(MTM, spec, reps, warmup):
+    from MTM import blocks as B
+    name, hw, chans, dtype, side, margin = spec
+    ref, img = workload(spec)
+    grid = B.grid(ref.shape, side)
+    method = MTM.TM_CCOEFF_NORMED
+
+    def loop(keep=None):
+        templs = [("b%d" % k, ref[y:y + h, x:x + w]) for k, (x, y, w, h) in enumerate(grid.tolist())]
+        regions = [(B.search_box(b, margin, img.shape), [k]) for k, b in enumerate(grid.tolist())]
+        res = MTM.findMatchesInBoxes(templs, img, regions, method, N_object=1)
+        if keep is not None:
+            keep.extend([templs, [r[0] for r in res]])
+        pos = np.array([r[0][1][:2] for r in res], dtype=np.int64)
+        return pos, np.array([r[0][2] for r in res], dtype=np.float32)
+
+    methods = {
+        "blocks": lambda: MTM.matchBlocks(ref, img, grid, margin, method),
+        "blocks_refine": lambda: MTM.matchBlocks(ref, img, grid, margin, method, refine=True),
+        "loop": loop,
+    }
+    results = {}
+    for k, fn in methods.items():
+        for _ in range(warmup):
+            results[k] = fn()
+    ms = {k: [] for k in methods}
+    for _ in range(reps):
+        for k, fn in methods.items():
+            t0 = time.perf_counter()
+            fn()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    (pos, sc), (lpos, lsc) = results["blocks"], results["loop"]
+    equal = bool((pos == lpos).all() and sc.tobytes() == lsc.tobytes() and
+                 results["blocks_refine"][1].tobytes() == lsc.tobytes())
+    keep = []
+    loop(keep)
+    fine = np.array([h[1][:2] for h in MTM.refineHits(keep[0], img, keep[1], method)], dtype=np.float64)
+    d = B.displacements(grid, pos)
+    return {
+        "workload": name, "image": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype), "blocks": int(len(grid)), "block": side,
+        "margin": margin, "map": "%dx%d" % (2 * margin + 1, 2 * margin + 1),
+        "ms": {k: round(v, 3) for k, v in med.items()},
+        "ms_min": {k: round(min(v), 3) for k, v in ms.items()},
+        "speedup_vs_loop": {k: round(med["loop"] / med[k], 2) for k in ("blocks", "blocks_refine")},
+        "equal_to_loop": equal,
+        "refine_equal": bool((results["blocks_refine"][0] == fine).all()),
+        "found_shift": float(np.mean((d == (3, -2)).all(axis=1))),
+        "reps": reps,
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--only", default=None, help="run the one workload of this name (profiling runs)")
+    args = ap.parse_args()
+    import build as mtm_build
+    mtm_build.build()
+    import MTM
+    for spec in WORKLOADS:
+        if args.only and spec[0] != args.only:
+            continue
+        print(json.dumps(run(MTM, spec, args.reps, args.warmup)), flush=True)
+
+
+if __name__ == "__main__":
+    main()

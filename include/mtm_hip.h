@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -621,6 +621,38 @@ int mtm_match_blocks(mtm_ctx* ctx, const void* reference, int64_t reference_stri
 int mtm_debug_plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* blocks, int n_blocks, int margin,
                           int64_t budget_bytes, int32_t* tiles, int64_t tile_cap, int64_t* n_tiles, int32_t* chunk_of,
                           int64_t* toff, int32_t* maps);
+
+/* mtm_match_blocks_stack: the reference of pair p. */
+#define MTM_BLOCKS_REF_PREVIOUS 0 /* frames[p] */
+#define MTM_BLOCKS_REF_FIRST 1    /* frames[0] */
+
+/* Block matching over a stack of n_frames frames of one shape in one call: pair p (0 .. n_frames - 2)
+ * searches frames[p + 1] for the blocks of its reference - frames[p] (MTM_BLOCKS_REF_PREVIOUS) or frames[0]
+ * (MTM_BLOCKS_REF_FIRST) - exactly as mtm_match_blocks(reference, frames[p + 1], ...) does.  Frames as mtm_track_boxes
+ * takes them: n_frames pointers, one row stride.
+ * Per-pair results (planes == NULL): out_hits[p n_blocks + k] = mtm_match_blocks' out[k] of pair p, bit for bit; nbhd:
+ * optional, 9 floats per record in the same order, mtm_match_blocks' nbhd of the pair.
+ * Ensemble planes (planes != NULL; out_hits and nbhd are ignored): S = 2 margin + 1, planes[(k S + margin + dy) S +
+ * margin + dx] = the mean over the pairs of block k's score at displacement (dx, dy): the float32 rounding of
+ * (((s_0 + s_1) + ...) + s_{P-1}) / P in float64, s_p the pair's float32 score; NaN where the clipped search box has no
+ * output at that displacement.  n_blocks S^2 above MTM_OPT_BOXES_MAX_FLOATS returns MTM_E_INVALID and names both numbers.
+ * Frames go up in stacks of at most MTM_OPT_BATCH_MAX_ROWS rows (never fewer than two frames: frames of at most 32767
+ * rows), each frame once plus the frame that carries the reference into a stack; no kernel reads across frames.  Checks,
+ * block chunks and the context's state afterwards as mtm_match_blocks'; n_frames < 2 with n_blocks > 0 returns
+ * MTM_E_INVALID.  One host wait per call. */
+int mtm_match_blocks_stack(mtm_ctx* ctx, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                           int64_t row_stride_bytes, const mtm_block* blocks, int n_blocks, int margin, int method, int mode,
+                           mtm_hit* out_hits, float* nbhd, float* planes);
+
+/* Test support: the host plan of a mtm_match_blocks_stack call (no context, no GPU).  chunks: 4 int32 per frame chunk -
+ * (f0, nf, carried, p0): the chunk uploads the stack [frame carried, frames f0 .. f0 + nf - 1] and runs the pairs p0 ..
+ * p0 + nf - 1 -, at most chunk_cap chunks are written and *n_chunks is their full number.  With blocks and clip != NULL:
+ * clip[2 k], clip[2 k + 1] = (ox, oy) of block k, how far its search box was clipped at the left and at the top (output
+ * (y, x) of its map is cell (y + oy, x + ox) of its plane); rows .. dtype describe the frames as for
+ * mtm_debug_plan_blocks. */
+int mtm_debug_plan_blocks_stack(int n_frames, int frames_per_chunk, int mode, int32_t* chunks, int64_t chunk_cap,
+                                int64_t* n_chunks, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
+                                int n_blocks, int margin, int32_t* clip);
 
 /* The 3 x 3 score neighbourhoods of n points in one call: out[9 k + 3 (1 + dy) + (1 + dx)] = the score of
  * template pts[k].templ_idx at window (x + dx, y + dy) of the image's score map, NaN for a window outside the map.  Image:

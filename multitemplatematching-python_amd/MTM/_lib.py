@@ -185,6 +185,13 @@ SYMBOLS = {
     "mtm_debug_plan_blocks": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                              _P(ctypes.c_int64), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mtm_match_blocks_stack": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p]),
+    "mtm_debug_plan_blocks_stack": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                                   _P(ctypes.c_int64), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "mtm_hit_neighbourhoods": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
@@ -468,6 +475,32 @@ def debug_plan_blocks(shape, chans, dtype, blocks, margin, budget_bytes):
     check(lib.mtm_debug_plan_blocks(*args, tiles.ctypes.data, n_tiles.value, ctypes.byref(n_tiles), None, None, None),
           "mtm_debug_plan_blocks")
     return tiles, chunk_of, toff, maps
+
+
+# mtm_match_blocks_stack: the reference of pair p is frames[p] / frames[0]
+BLOCKS_REF_PREVIOUS, BLOCKS_REF_FIRST = 0, 1
+
+
+def debug_plan_blocks_stack(n_frames, frames_per_chunk, mode, shape=None, chans=1, dtype=np.uint8, blocks=None, margin=0):
+    """The host plan of a mtm_match_blocks_stack call, no GPU needed (mtm_debug_plan_blocks_stack): (chunks (n, 4) int32 of
+    (f0, nf, carried, p0) - a chunk uploads the stack [frame carried, frames f0 .. f0 + nf - 1] and runs the pairs p0 ..
+    p0 + nf - 1 -; clip (N, 2) int32 of every block's (ox, oy), how far its search box in frames of `shape` was clipped at
+    the left and at the top, or None without blocks)."""
+    lib = load()
+    n_chunks = ctypes.c_int64(0)
+    head = (int(n_frames), int(frames_per_chunk), int(mode))
+    none = (1, 1, 1, MTM_U8, None, 0, 0, None)
+    check(lib.mtm_debug_plan_blocks_stack(*head, None, 0, ctypes.byref(n_chunks), *none), "mtm_debug_plan_blocks_stack")
+    chunks = np.zeros((n_chunks.value, 4), dtype=np.int32)
+    clip, tail = None, none
+    if blocks is not None:
+        blocks = block_records(blocks)
+        clip = np.zeros((len(blocks), 2), dtype=np.int32)
+        tail = (int(shape[0]), int(shape[1]), int(chans), _DT_CODES[np.dtype(dtype)], blocks.ctypes.data, len(blocks),
+                int(margin), clip.ctypes.data)
+    check(lib.mtm_debug_plan_blocks_stack(*head, chunks.ctypes.data, n_chunks.value, ctypes.byref(n_chunks), *tail),
+          "mtm_debug_plan_blocks_stack")
+    return chunks, clip
 
 
 def debug_templ_stats(template, method):
@@ -872,6 +905,41 @@ class Context(_RecordMemo):
         check(self._lib.mtm_match_blocks(self._h, rptr, rstride, aptr, astride, a.shape[0], a.shape[1], chans, _dtype_code(a),
                                          blocks.ctypes.data, n, int(margin), int(method), out.ctypes.data,
                                          nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks")
+        return out, nbhd
+
+    def match_blocks_stack(self, frames, blocks, margin, method, mode, with_nbhd=False, planes=False):
+        """matchBlocks over the pairs of a frame stack in one native call (mtm_match_blocks_stack): pair p searches
+        frames[p + 1] for the blocks (BLOCK_DTYPE records) of frames[p] (`mode` BLOCKS_REF_PREVIOUS) or frames[0]
+        (BLOCKS_REF_FIRST).  Frames of one shape and pixel type as track_boxes takes them.  Returns (records, pair-major:
+        (len(frames) - 1) * len(blocks); neighbourhoods as match_blocks' in the same order, or None) or, `planes`, the
+        (len(blocks), 2 margin + 1, 2 margin + 1) float32 array of every block's score plane averaged over the pairs, NaN
+        where the clipped search box has no output.  The templates set on the context are not touched."""
+        blocks = block_records(blocks)
+        n, npairs, side = len(blocks), len(frames) - 1, 2 * int(margin) + 1
+        if planes:
+            if npairs < 1:
+                raise ValueError("match_blocks_stack: planes need at least two frames")
+            out = np.empty((n, side, side), dtype=np.float32)
+            if n == 0:
+                return out
+        else:
+            out = np.empty(max(npairs, 0) * n, dtype=HIT_DTYPE)
+            nbhd = np.empty((len(out), 3, 3), dtype=np.float32) if with_nbhd else None
+            if len(out) == 0:
+                return out, nbhd
+        rows = [_pixel_rows(a) for a in frames]
+        if len({r[2] for r in rows}) > 1:       # (one row stride for every frame)
+            rows = [_pixel_rows(np.ascontiguousarray(a)) for a in frames]
+        a0, _, stride = rows[0]
+        chans = 1 if a0.ndim == 2 else a0.shape[2]
+        ptrs = (ctypes.c_void_p * len(rows))(*[r[1] for r in rows])
+        args = (self._h, ptrs, len(rows), a0.shape[0], a0.shape[1], chans, _dtype_code(a0), stride, blocks.ctypes.data, n,
+                int(margin), int(method), int(mode))
+        if planes:
+            check(self._lib.mtm_match_blocks_stack(*args, None, None, out.ctypes.data), "mtm_match_blocks_stack")
+            return out
+        check(self._lib.mtm_match_blocks_stack(*args, out.ctypes.data, nbhd.ctypes.data if with_nbhd else None, None),
+              "mtm_match_blocks_stack")
         return out, nbhd
 
     def hit_neighbourhoods(self, image, points):

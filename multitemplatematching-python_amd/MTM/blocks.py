@@ -28,6 +28,11 @@ ones included - exactly as it found them.
 Scope (anything else raises ValueError / TypeError before any native call): two images of one shape, dtype and channel
 count - uint8 with 1 or 3 channels or single-channel uint16, at most 32767 rows -, methods 0..5, blocks wholly inside the
 reference, uint16 blocks of at most 2^21 pixels, ``margin`` an integer >= 0.
+
+``matchBlocksStack`` is the movie form: the pairs of a stack of frames - each frame against the previous or against the
+first - in one native call (mtm_match_blocks_stack), every frame uploaded once; per pair the very results of
+``matchBlocks``, or (``ensemble=True``) every block's correlation plane averaged over the pairs and its peak
+(``plane_peaks``): ensemble correlation, for movies whose single pairs are too noisy to peak.
 """
 import numbers
 
@@ -36,7 +41,7 @@ import numpy as np
 from . import _lib, subpixel
 from . import TM_CCOEFF_NORMED
 
-__all__ = ["matchBlocks", "grid", "search_box", "displacements"]
+__all__ = ["matchBlocks", "matchBlocksStack", "plane_peaks", "grid", "search_box", "displacements"]
 
 _I64 = np.dtype(np.int64)
 _U16_MAX_PIXELS = 1 << 21       # mtm_match_blocks: uint16 correlations stay below 2^53, exact in float64
@@ -183,4 +188,155 @@ def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, m
     if refine:          # (one fit over every block: refineHits' numbers by construction)
         ox, oy = subpixel.fit_offsets(nbhd, method)
         positions = positions.astype(np.float64) + np.stack((ox, oy), axis=1)
+    return positions, scores
+
+
+_REFERENCE_MODES = {"previous": _lib.BLOCKS_REF_PREVIOUS, "first": _lib.BLOCKS_REF_FIRST}
+
+
+def _check_frames(frames):
+    """frames -> a list of arrays of one shape and dtype in matchBlocks' scope (an (F, H, W[, C]) array is split along
+    its first axis); TypeError / ValueError naming the first offending frame."""
+    if isinstance(frames, np.ndarray):
+        if frames.ndim not in (3, 4):
+            raise ValueError("frames: an array of frames has the shape (F, H, W) or (F, H, W, C) (got %s)" % (frames.shape,))
+        fl = list(frames)
+    else:
+        try:
+            fl = list(frames)
+        except TypeError:
+            raise TypeError("frames must be a sequence of numpy arrays or one array with a leading frame axis (got %s)"
+                            % type(frames).__name__) from None
+    if not fl:
+        raise ValueError("frames is empty")
+    for i, f in enumerate(fl):
+        if not isinstance(f, np.ndarray):
+            raise TypeError("frames[%d] must be a numpy array (got %s)" % (i, type(f).__name__))
+        if f.shape != fl[0].shape or f.dtype != fl[0].dtype:
+            raise ValueError("frames[%d] differs from frames[0] in shape, dtype or channel count (%s %s, frames[0] %s %s)" % (
+                i, f.shape, f.dtype, fl[0].shape, fl[0].dtype))
+    a = fl[0]
+    ok = (a.dtype == np.uint8 and (a.ndim == 2 or (a.ndim == 3 and a.shape[2] in (1, 3)))) or \
+        (a.dtype == np.uint16 and (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 1)))
+    if not ok:
+        raise ValueError("matchBlocksStack takes uint8 frames with 1 or 3 channels and single-channel uint16 frames (got "
+                         "frames[0] %s of shape %s)" % (a.dtype, a.shape))
+    if a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError("matchBlocksStack: the frames are empty (shape %s)" % (a.shape,))
+    if a.shape[0] > _MAX_ROWS:
+        raise ValueError("matchBlocksStack takes frames of at most %d rows (got %d)" % (_MAX_ROWS, a.shape[0]))
+    return fl
+
+
+def plane_peaks(planes, blocks, method, refine=False):
+    """
+    The peak of every block's score plane: ``(positions, scores)``.  ``planes``: an (N, 2m+1, 2m+1) float array,
+    ``planes[k, m + dy, m + dx]`` block k's score at displacement (dx, dy), NaN where there is none (``matchBlocksStack``'s
+    ensemble planes, or a combination of the planes of several calls).  Per plane the maximum over the cells that are not
+    NaN - the minimum for methods 0 and 1 -, the first such cell in row-major order on ties: ``positions[k]`` is the int64
+    ``(x_k + dx, y_k + dy)``, ``scores[k]`` the plane's value as float32.  ``refine=True``: float64 positions, the peak plus
+    ``subpixel.fit_offsets`` of the plane's 3 x 3 cells around it (cells outside the plane count as NaN: no offset along
+    an axis whose three cells are not all numbers).  Host numpy; a plane without a number raises ValueError.
+    """
+    if not _is_int(method) or method not in (0, 1, 2, 3, 4, 5):
+        raise ValueError("plane_peaks takes methods 0..5 (got %r)" % (method,))
+    if not isinstance(refine, bool):
+        raise ValueError("refine must be True or False (got %r)" % (refine,))
+    p = np.asarray(planes)
+    if p.ndim != 3 or p.shape[1] != p.shape[2] or p.shape[1] % 2 != 1 or p.dtype.kind != "f":
+        raise ValueError("planes must be an (N, 2m+1, 2m+1) float array (got %s %s)" % (p.dtype, p.shape))
+    p = p.astype(np.float32, copy=False)
+    b = np.asarray(blocks)
+    if b.size == 0 and len(p) == 0:
+        b = np.zeros((0, 4), _I64)
+    if b.ndim != 2 or b.shape[1] != 4 or b.dtype.kind not in "iu" or len(b) != len(p):
+        raise ValueError("blocks must be an (N, 4) integer array of (x, y, w, h), one block per plane (got %s for %d planes)"
+                         % (b.shape, len(p)))
+    n, side = len(p), p.shape[1]
+    m = side // 2
+    flat = p.reshape(n, side * side)
+    nan = np.isnan(flat)
+    if nan.all(axis=1).any():
+        raise ValueError("planes[%d] holds no number" % int(np.argmax(nan.all(axis=1))))
+    if method in (0, 1):
+        at = np.argmin(np.where(nan, np.float32(np.inf), flat), axis=1)
+    else:
+        at = np.argmax(np.where(nan, np.float32(-np.inf), flat), axis=1)
+    stray = nan[np.arange(n), at]           # (every number of the plane is the infinity that stood in for NaN)
+    at[stray] = np.argmin(nan[stray], axis=1)
+    cy, cx = at // side, at % side
+    scores = flat[np.arange(n), at].astype(np.float32)
+    positions = b[:, :2].astype(_I64) + np.stack((cx - m, cy - m), axis=1).astype(_I64)
+    if refine:
+        padded = np.full((n, side + 2, side + 2), np.nan, dtype=np.float32)
+        padded[:, 1:-1, 1:-1] = p
+        rows = (cy[:, None] + np.arange(3)[None, :])[:, :, None]
+        cols = (cx[:, None] + np.arange(3)[None, :])[:, None, :]
+        nbhd = padded[np.arange(n)[:, None, None], rows, cols]
+        ox, oy = subpixel.fit_offsets(nbhd, method)
+        positions = positions.astype(np.float64) + np.stack((ox, oy), axis=1)
+    return positions, scores
+
+
+def matchBlocksStack(frames, blocks, margin: int, method: int = TM_CCOEFF_NORMED, *, reference: str = "previous",
+                     refine: bool = False, ensemble: bool = False, context=None):
+    """
+    ``matchBlocks`` over a stack of F frames in one native call.  ``frames``: a sequence of F arrays of one shape and dtype
+    or one array with a leading frame axis.  Pair p (0 .. F - 2) searches ``frames[p + 1]``; its reference is ``frames[p]``
+    (``reference="previous"``) or ``frames[0]`` (``"first"``).
+
+    ``ensemble=False``: ``(positions, scores)`` of shapes (F - 1, N, 2) and (F - 1, N), ``positions[p], scores[p]`` being
+    exactly ``matchBlocks(ref_p, frames[p + 1], blocks, margin, method, refine=refine)``.  One frame gives empty arrays.
+
+    ``ensemble=True``: ``(positions, scores, planes)``; ``planes`` is an (N, 2m+1, 2m+1) float32 array (m: the margin,
+    clipped to the frames' larger side), ``planes[k, m + dy, m + dx]`` the mean over the pairs of block k's score at
+    displacement (dx, dy) - the float32 rounding of the pairs' float32 scores summed in float64 in pair order and divided
+    by their number -, NaN where the block's clipped search box has no such displacement.  ``positions`` (N, 2) and
+    ``scores`` (N,) are ``plane_peaks(planes, blocks, method, refine)``.  Needs two frames at least, and planes of at
+    most OPT_BOXES_MAX_FLOATS cells in all.
+    """
+    fl = _check_frames(frames)
+    if not _is_int(method) or method not in (0, 1, 2, 3, 4, 5):
+        raise ValueError("matchBlocksStack takes methods 0..5 (got %r)" % (method,))
+    if not _is_int(margin) or margin < 0:
+        raise ValueError("margin must be an integer >= 0 (got %r)" % (margin,))
+    if not isinstance(reference, str) or reference not in _REFERENCE_MODES:
+        raise ValueError('reference must be "previous" or "first" (got %r)' % (reference,))
+    if not isinstance(refine, bool):
+        raise ValueError("refine must be True or False (got %r)" % (refine,))
+    if not isinstance(ensemble, bool):
+        raise ValueError("ensemble must be True or False (got %r)" % (ensemble,))
+    b = _check_blocks(blocks, fl[0])
+    n, pairs = len(b), len(fl) - 1
+    if ensemble and pairs < 1:
+        raise ValueError("ensemble=True needs two frames at least: there is no pair to average")
+    # (a margin past the frames' larger side clips to the whole frame, as a margin of that side does)
+    m = int(min(margin, max(fl[0].shape[0], fl[0].shape[1])))
+    side = 2 * m + 1
+    ptype = np.float64 if refine else _I64
+    if ensemble and n == 0:
+        return np.zeros((0, 2), dtype=ptype), np.zeros(0, dtype=np.float32), np.zeros((0, side, side), dtype=np.float32)
+    if not ensemble and (n == 0 or pairs == 0):
+        return np.zeros((pairs, n, 2), dtype=ptype), np.zeros((pairs, n), dtype=np.float32)
+    rec = np.empty(n, dtype=_lib.BLOCK_DTYPE)
+    rec["x"], rec["y"], rec["w"], rec["h"] = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+    ctx = context or _lib.default_context()     # (only now: every argument error above comes before "no GPU")
+    mode = _REFERENCE_MODES[reference]
+    with ctx.lock:
+        if ensemble:
+            budget = int(ctx.get_option(_lib.OPT_BOXES_MAX_FLOATS))
+            if n * side * side > budget:
+                raise ValueError("ensemble=True: the planes of %d blocks at margin %d hold %d floats, more than the "
+                                 "context's OPT_BOXES_MAX_FLOATS = %d" % (n, m, n * side * side, budget))
+            planes = ctx.match_blocks_stack(fl, rec, m, int(method), mode, planes=True)
+        else:
+            raw, nbhd = ctx.match_blocks_stack(fl, rec, m, int(method), mode, with_nbhd=refine)
+    if ensemble:
+        positions, scores = plane_peaks(planes, b, int(method), refine)
+        return positions, scores, planes
+    positions = np.stack((raw["x"], raw["y"]), axis=1).astype(_I64).reshape(pairs, n, 2)
+    scores = raw["score"].astype(np.float32).reshape(pairs, n)
+    if refine:          # (one fit over every pair and block: matchBlocks' numbers by construction)
+        ox, oy = subpixel.fit_offsets(nbhd, method)
+        positions = positions.astype(np.float64) + np.stack((ox, oy), axis=1).reshape(pairs, n, 2)
     return positions, scores

@@ -10,6 +10,10 @@
 // and scores the 3 x 3 neighbourhoods in the whole image's map.  plan_blocks (mtm_host.cpp) checks the blocks and lays out
 // the unit and tile tables and the chunks; the host waits once per call.  uint8 (1 or 3 channels) and single-channel
 // uint16.  The template set of the context is neither read nor written.
+// mtm_match_blocks_stack runs the same chain for every pair of a frame stack: the frames go up in stacked
+// chunks (plan_blocks_stack, mtm_host.cpp), every pair has a row of keys of its own, and - ensemble planes - blocks_plane_kernel
+// adds every output's score to the block's plane of float64 sums instead of keeping an extremum.
+#include <climits>
 #include <type_traits>
 
 #include "mtm_ctx.h"
@@ -123,6 +127,45 @@ __global__ __launch_bounds__(256) void blocks_score_kernel(ImageDev img, const u
     const int y = K.ty0 + tid / kWinTile, x = K.tx0 + tid % kWinTile;
     track_merge_key(y < U.oh && x < U.ow, 0xFFFFFFFFull - (unsigned long long)((long long)y * U.ow + x), mode_min,
                     [&] { return win_score<CH>(method, T, inv_area, corr, s1, s2); }, keys + K.u0);
+}
+
+// blocks_score_kernel's sibling for the ensemble planes of mtm_match_blocks_stack: the same tile, sums and float32 score
+// (win_tile_sums_*, win_score), and instead of merging a key every output (y, x) of the map adds its score, widened to
+// float64, to its cell of block u0's side x side plane of sums: acc[(u0 side + y + oy) side + x + ox], (ox, oy) =
+// clip[2 u0], clip[2 u0 + 1] the block's clip offsets (BlockPlan::clip: y + oy, x + ox < side).  A plain read-modify-write:
+// the tile table partitions every map, so a cell has one writer per launch, and the launches of successive pairs are
+// ordered by the call's one stream - the sums are those of the pairs in order, bit for bit.  `first` (the call's first
+// pair) stores instead of adding: the sum starts from s_0 itself, a -0.0 included.
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void blocks_plane_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
+                                                           const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
+                                                           const TemplDev* __restrict__ td, const TrackUnit* __restrict__ units,
+                                                           const TrackTile* __restrict__ tiles, int method,
+                                                           const int32_t* __restrict__ clip, int side, int first,
+                                                           double* __restrict__ acc) {
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
+    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
+    const TrackTile K = tiles[blockIdx.x];
+    const TrackUnit U = units[K.u0];
+    const TemplDev T = td[K.u0];
+    const int h = T.rows, w = T.cols;
+    const uint8_t* tp = tpx + toff[K.u0];
+    const int tid = threadIdx.x;
+    const double inv_area = 1.0 / ((double)h * (double)w);
+    unsigned long long corr, s2, s1[CH];
+    if constexpr (U16)
+        win_tile_sums_u16(Tl[0], Tl[1], Il[0], Il[1], img.u8, lo_b, img.u8_pitch, img.rows, img.cols, tp, h, w, U.y0 + K.ty0,
+                          U.x0 + K.tx0, corr, s1[0], s2);
+    else
+        win_tile_sums_u8<CH>(Tl[0], Il[0], img.u8, img.u8_plane, img.u8_pitch, img.rows, img.cols, tp, h, w, U.y0 + K.ty0,
+                             U.x0 + K.tx0, corr, s1, s2);
+    const int y = K.ty0 + tid / kWinTile, x = K.tx0 + tid % kWinTile;
+    const int cy = y + clip[2 * K.u0 + 1], cx = x + clip[2 * K.u0];
+    if (y < U.oh && x < U.ow && cy < side && cx < side) {
+        const float s = win_score<CH>(method, T, inv_area, corr, s1, s2);
+        double* cell = acc + ((size_t)K.u0 * (size_t)side + (size_t)cy) * (size_t)side + (size_t)cx;
+        *cell = first ? (double)s : *cell + (double)s;
+    }
 }
 
 // Grid: one 256-thread work-group per block (launch slice; block k = k0 + blockIdx.x), after the chunk's score launches:
@@ -287,6 +330,176 @@ int mtm_match_blocks(mtm_ctx* c, const void* reference, int64_t reference_stride
         out[k] = r;
     }
     // the stack is none of the caller's images: no current image, no published maps
+    c->have_image = false;
+    return MTM_OK;
+}
+
+int mtm_match_blocks_stack(mtm_ctx* c, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                           int64_t row_stride_bytes, const mtm_block* blocks, int n_blocks, int margin, int method, int mode,
+                           mtm_hit* out_hits, float* nbhd, float* planes) {
+    const char* who = "mtm_match_blocks_stack";
+    if (!c || n_frames < 0 || n_blocks < 0 || margin < 0 || (n_frames > 0 && !frames) ||
+        (n_blocks > 0 && (!blocks || n_frames < 2 || (!out_hits && !planes))) || method < MTM_TM_SQDIFF ||
+        method > MTM_TM_CCOEFF_NORMED || (mode != MTM_BLOCKS_REF_PREVIOUS && mode != MTM_BLOCKS_REF_FIRST)) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    for (int f = 0; f < n_frames; ++f) MTMC(check_image_args(frames[f], rows, cols, chans, dtype, row_stride_bytes, who));
+    if (!((dtype == MTM_U8 && (chans == 1 || chans == 3)) || (dtype == MTM_U16 && chans == 1))) {
+        set_error(std::string(who) + ": takes uint8 frames with 1 or 3 channels and single-channel uint16 frames");
+        return MTM_E_INVALID;
+    }
+    // (a pair's two frames are one stack: its rows stay within what a layout launch's grid holds)
+    if (2ll * rows > kBatchMaxRows) {
+        set_error(std::string(who) + ": frames of more than " + std::to_string(kBatchMaxRows / 2) + " rows");
+        return MTM_E_INVALID;
+    }
+    BlockPlan P;
+    MTMC(plan_blocks(rows, cols, chans, dtype, blocks, n_blocks, margin, 4 * (long long)c->boxes_max_floats, who, P));
+    if (n_blocks == 0) return MTM_OK;
+    const bool ens = planes != nullptr;
+    if (ens) nbhd = nullptr;
+    const size_t n = (size_t)n_blocks, np = (size_t)n_frames - 1;
+    const unsigned __int128 side = 2 * (unsigned __int128)margin + 1, cells128 = (unsigned __int128)n * side * side;
+    if (ens && (cells128 > (unsigned __int128)c->boxes_max_floats || side > (unsigned __int128)INT_MAX)) {
+        const std::string cells_s = cells128 >> 63 ? std::string("2^63 or more") : std::to_string((long long)cells128);
+        set_error(std::string(who) + ": the planes of " + std::to_string(n_blocks) + " blocks at margin " +
+                  std::to_string(margin) + " hold " + cells_s + " floats, more than MTM_OPT_BOXES_MAX_FLOATS = " +
+                  std::to_string((long long)c->boxes_max_floats));
+        return MTM_E_INVALID;
+    }
+    const size_t cells = ens ? (size_t)cells128 : 0;
+
+    HIPC(hipSetDevice(c->device));
+    c->timing = mtm_timing{};
+    c->maps_valid = false;
+    c->last_hits.clear();
+    MTMC(c->blk_tpx.ensure(P.max_bytes));
+    MTMC(c->blk_toff.ensure(sizeof(long long) * n));
+    MTMC(c->blk_td.ensure(sizeof(TemplDev) * n));
+    MTMC(c->blk_blocks.ensure(sizeof(mtm_block) * n));
+    MTMC(c->blk_units.ensure(sizeof(TrackUnit) * n));
+    MTMC(c->blk_tiles.ensure(sizeof(TrackTile) * P.tiles.size()));
+    if (ens) {
+        MTMC(c->blk_clip.ensure(sizeof(int32_t) * 2 * n));
+        MTMC(c->blk_acc.ensure(sizeof(double) * cells));
+    } else {
+        MTMC(c->blk_keys.ensure(sizeof(unsigned long long) * np * n));
+        if (nbhd) MTMC(c->blk_nbhd.ensure(sizeof(float) * 9 * np * n));
+    }
+
+    HIPC(hipEventRecord(c->ev[0], c->stream));
+    HIPC(hipMemcpyAsync(c->blk_blocks.p, blocks, sizeof(mtm_block) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_toff.p, P.toff.data(), sizeof(long long) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_units.p, P.units.data(), sizeof(TrackUnit) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_tiles.p, P.tiles.data(), sizeof(TrackTile) * P.tiles.size(), hipMemcpyHostToDevice, c->stream));
+    if (ens) {
+        HIPC(hipMemcpyAsync(c->blk_clip.p, P.clip.data(), sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
+        HIPC(hipMemsetAsync(c->blk_acc.p, 0, sizeof(double) * cells, c->stream));
+    } else {
+        HIPC(hipMemsetAsync(c->blk_keys.p, 0, sizeof(unsigned long long) * np * n, c->stream));
+    }
+
+    const int mode_min = method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED ? 1 : 0;
+    uint8_t* tpx = c->blk_tpx.as<uint8_t>();
+    const long long* toff = c->blk_toff.as<long long>();
+    TemplDev* td = c->blk_td.as<TemplDev>();
+    const TrackUnit* units = c->blk_units.as<TrackUnit>();
+    // mode "first" with every block in one chunk: the gathered templates outlive the pairs of a frame chunk
+    const bool gather_once = mode == MTM_BLOCKS_REF_FIRST && P.chunks.size() == 1;
+    std::vector<const void*> px;
+    // frame chunks sized as a tracking call's, never below two frames (plan_blocks_stack: a pair's reference and image lie
+    // in one stack); a frame chunk's upload, then per pair and block chunk the launch chain - gather, score, [neighbourhoods] - in stream
+    // order: the next upload overwrites the stack behind this chunk's last reader, and the host waits for none of them
+    for (const StackChunk& S : plan_blocks_stack(n_frames, track_chunk_frames(c, rows, cols, chans), mode)) {
+        px.assign(1, frames[S.carried]);
+        px.insert(px.end(), frames + S.f0, frames + S.f0 + S.nf);
+        adopt_image(c, (S.nf + 1) * rows, cols, chans, dtype);
+        MTMC(upload_image_stack(c, c->slot[c->cur], px.data(), S.nf + 1, row_stride_bytes, rows, cols, chans, dtype, c->stream));
+        const ImageDev st = image_dev(c);
+        const uint8_t* st_lo = c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane;    // uint16: [high ^ 0x80][low ^ 0x80]
+        bool gathered = false;
+        for (int i = 0; i < S.nf; ++i) {
+            const int r_slot = mode == MTM_BLOCKS_REF_FIRST ? 0 : i, i_slot = i + 1;
+            const ImageDev ref = stack_view(st, r_slot * rows, rows), img = stack_view(st, i_slot * rows, rows);
+            const uint8_t* ref_lo = st_lo + (size_t)r_slot * rows * st.u8_pitch;
+            const uint8_t* img_lo = st_lo + (size_t)i_slot * rows * st.u8_pitch;
+            unsigned long long* keys = ens ? nullptr : c->blk_keys.as<unsigned long long>() + (size_t)(S.p0 + i) * n;
+            float* nb_out = nbhd ? c->blk_nbhd.as<float>() + 9 * (size_t)(S.p0 + i) * n : nullptr;
+            MTMC(blocks_dispatch(dtype, chans, [&](auto ch, auto u16) -> int {
+                constexpr int CH = decltype(ch)::value;
+                constexpr bool U16 = decltype(u16)::value;
+                for (const BlockChunk& C : P.chunks) {
+                    for (size_t b0 = (size_t)C.b0; !(gather_once && gathered) && b0 < (size_t)C.b1; b0 += kBlockLaunchGroups) {
+                        const unsigned nb = (unsigned)std::min(kBlockLaunchGroups, (size_t)C.b1 - b0);
+                        hipLaunchKernelGGL((blocks_gather_kernel<CH, U16>), dim3(nb), dim3(256), 0, c->stream, ref, ref_lo,
+                                           c->blk_blocks.as<mtm_block>(), (int)b0, tpx, toff, td, method);
+                        HIPC(hipGetLastError());
+                    }
+                    for (size_t t0 = C.t0; t0 < C.t1; t0 += kBlockLaunchGroups) {
+                        const unsigned nt = (unsigned)std::min(kBlockLaunchGroups, C.t1 - t0);
+                        if (ens)
+                            hipLaunchKernelGGL((blocks_plane_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo,
+                                               tpx, toff, td, units, c->blk_tiles.as<TrackTile>() + t0, method,
+                                               c->blk_clip.as<int32_t>(), (int)side, S.p0 + i == 0 ? 1 : 0,
+                                               c->blk_acc.as<double>());
+                        else
+                            hipLaunchKernelGGL((blocks_score_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo,
+                                               tpx, toff, td, units, c->blk_tiles.as<TrackTile>() + t0, method, mode_min, keys);
+                        HIPC(hipGetLastError());
+                    }
+                    for (size_t b0 = (size_t)C.b0; nb_out && b0 < (size_t)C.b1; b0 += kBlockLaunchGroups) {
+                        const unsigned nb = (unsigned)std::min(kBlockLaunchGroups, (size_t)C.b1 - b0);
+                        hipLaunchKernelGGL((blocks_nbhd_kernel<CH, U16>), dim3(nb), dim3(256), 0, c->stream, img, img_lo, tpx,
+                                           toff, td, units, keys, (int)b0, method, nb_out);
+                        HIPC(hipGetLastError());
+                    }
+                }
+                return MTM_OK;
+            }));
+            gathered = true;
+        }
+    }
+
+    // the keys (and neighbourhoods), or the planes' sums, come back behind the call's single wait
+    std::vector<unsigned long long> hkeys(ens ? 0 : np * n);
+    std::vector<double> hacc(cells);
+    HIPC(hipEventRecord(c->ev[1], c->stream));
+    if (ens) {
+        HIPC(hipMemcpyAsync(hacc.data(), c->blk_acc.p, sizeof(double) * cells, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        HIPC(hipMemcpyAsync(hkeys.data(), c->blk_keys.p, sizeof(unsigned long long) * np * n, hipMemcpyDeviceToHost, c->stream));
+        if (nbhd) HIPC(hipMemcpyAsync(nbhd, c->blk_nbhd.p, sizeof(float) * 9 * np * n, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPC(hipStreamSynchronize(c->stream));
+    HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
+    c->timing.n_hits = (int64_t)(ens ? n : np * n);
+    if (ens) {
+        // the mean of the pairs in float64, rounded to float32; NaN where the clipped box has no output
+        const size_t sd = (size_t)side;
+        const double pairs = (double)np;
+        for (size_t k = 0; k < n; ++k) {
+            const TrackUnit& u = P.units[k];
+            const size_t ox = (size_t)P.clip[2 * k], oy = (size_t)P.clip[2 * k + 1];
+            for (size_t cy = 0; cy < sd; ++cy)
+                for (size_t cx = 0; cx < sd; ++cx) {
+                    const size_t i = (k * sd + cy) * sd + cx;
+                    const bool in = cy >= oy && cy - oy < (size_t)u.oh && cx >= ox && cx - ox < (size_t)u.ow;
+                    planes[i] = in ? (float)(hacc[i] / pairs) : NAN;
+                }
+        }
+    } else {
+        for (size_t p = 0; p < np; ++p)
+            for (size_t k = 0; k < n; ++k) {
+                const TrackUnit& u = P.units[k];
+                mtm_hit r = decode_quality_key(hkeys[p * n + k], mode_min != 0, (int)k, u.ow, blocks[k].w, blocks[k].h);
+                r.x += u.x0;
+                r.y += u.y0;
+                out_hits[p * n + k] = r;
+            }
+    }
+    // the stacks are none of the caller's images: no current image, no published maps
     c->have_image = false;
     return MTM_OK;
 }

@@ -364,8 +364,10 @@ struct mtm_ctx {
     // at blk_toff[k] in blk_tpx, prepare_window_templates' layout, one chunk of blocks at a time) and the constants
     // blocks_gather_kernel computes for them (blk_td) -, the block records, the unit and tile tables (BlockPlan), one
     // extremum key per block and the records' 3 x 3 neighbourhoods.  The template set's tables (win_tpx, win_toff, box_td)
-    // and their generations are never touched.
-    DevBuf blk_tpx, blk_toff, blk_td, blk_blocks, blk_units, blk_tiles, blk_keys, blk_nbhd;
+    // and their generations are never touched.  mtm_match_blocks_stack: one row of keys and neighbourhoods per pair, the
+    // blocks' clip offsets (BlockPlan::clip) and the float64 sums of the ensemble planes (blk_acc: zeroed at the start of
+    // a call, one writer per cell and launch).
+    DevBuf blk_tpx, blk_toff, blk_td, blk_blocks, blk_units, blk_tiles, blk_keys, blk_nbhd, blk_clip, blk_acc;
     // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
     // template set sub_gen) and the per-call point table and scores.
     uint64_t sub_gen = 0;
@@ -505,6 +507,9 @@ int upload_image_stack(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* const* px
 int upload_image_pair(mtm_ctx* c, mtm_ctx::ImageSlot& sl, const void* px0, int64_t stride0, const void* px1, int64_t stride1,
                       int rows, int cols, int chans, int dtype, hipStream_t stream);
 void adopt_image(mtm_ctx* c, int rows, int cols, int chans, int dtype);
+// Frames of rows x cols x chans pixels per stacked chunk of a tracking call (mtm_track.hip; mtm_match_blocks_stack sizes
+// its chunks with it): MTM_OPT_BATCH_MAX_ROWS and the device memory of the stack's planes, at least one.
+int track_chunk_frames(const mtm_ctx* c, int rows, int cols, int chans);
 // (BlobTempl: mtm_internal.h)
 int parse_templ_blob(const std::vector<uint8_t>& b, std::vector<BlobTempl>& out, const char* who, bool u16_ok);
 int prepare_window_templates(mtm_ctx* c, const std::vector<BlobTempl>& tl);

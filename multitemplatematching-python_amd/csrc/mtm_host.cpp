@@ -639,6 +639,7 @@ int plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* block
     P = BlockPlan{};
     P.units.reserve((size_t)n_blocks);
     P.toff.reserve((size_t)n_blocks);
+    P.clip.reserve(2 * (size_t)n_blocks);
     BlockChunk cur{0, 0, 0, 0, 0};
     for (int k = 0; k < n_blocks; ++k) {
         const mtm_block& b = blocks[k];
@@ -667,6 +668,8 @@ int plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* block
         }
         P.units.push_back(TrackUnit{k, (int)y0, (int)x0, (int)oh, (int)ow});
         P.toff.push_back((long long)cur.bytes);
+        P.clip.push_back((int32_t)((long long)margin - (b.x - x0)));
+        P.clip.push_back((int32_t)((long long)margin - (b.y - y0)));
         cur.bytes += bytes;
         P.max_bytes = std::max(P.max_bytes, cur.bytes);
         for (int ty = 0; ty < (int)oh; ty += kTrackTile)
@@ -678,6 +681,15 @@ int plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* block
         P.chunks.push_back(cur);
     }
     return MTM_OK;
+}
+
+// ---- the frame chunks of a block-matching call over a frame stack (mtm_blocks.hip)
+std::vector<StackChunk> plan_blocks_stack(int n_frames, int frames_per_chunk, int mode) {
+    std::vector<StackChunk> chunks;
+    const int per = std::max(2, frames_per_chunk) - 1;         // new frames of a chunk, behind its carried frame
+    for (int f0 = 1; f0 < n_frames; f0 += per)
+        chunks.push_back(StackChunk{f0, std::min(per, n_frames - f0), mode == MTM_BLOCKS_REF_FIRST ? 0 : f0 - 1, f0 - 1});
+    return chunks;
 }
 
 }  // namespace mtm
@@ -751,6 +763,36 @@ int mtm_debug_plan_blocks(int rows, int cols, int chans, int dtype, const mtm_bl
             maps[4 * k + 2] = u.ow;
             maps[4 * k + 3] = u.oh;
         }
+    }
+    return MTM_OK;
+}
+
+int mtm_debug_plan_blocks_stack(int n_frames, int frames_per_chunk, int mode, int32_t* chunks, int64_t chunk_cap,
+                                int64_t* n_chunks, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
+                                int n_blocks, int margin, int32_t* clip) {
+    if (n_frames < 2 || frames_per_chunk < 2 || (mode != MTM_BLOCKS_REF_PREVIOUS && mode != MTM_BLOCKS_REF_FIRST) ||
+        chunk_cap < 0 || n_blocks < 0 || margin < 0 || (n_blocks > 0 && !blocks)) {
+        mtm::set_error("mtm_debug_plan_blocks_stack: bad arguments");
+        return MTM_E_INVALID;
+    }
+    const std::vector<mtm::StackChunk> C = mtm::plan_blocks_stack(n_frames, frames_per_chunk, mode);
+    if (n_chunks) *n_chunks = (int64_t)C.size();
+    for (size_t i = 0; chunks && i < C.size() && (int64_t)i < chunk_cap; ++i) {
+        chunks[4 * i] = C[i].f0;
+        chunks[4 * i + 1] = C[i].nf;
+        chunks[4 * i + 2] = C[i].carried;
+        chunks[4 * i + 3] = C[i].p0;
+    }
+    if (n_blocks > 0 && clip) {
+        if (rows < 1 || cols < 1 || !((dtype == MTM_U8 && (chans == 1 || chans == 3)) || (dtype == MTM_U16 && chans == 1))) {
+            mtm::set_error("mtm_debug_plan_blocks_stack: bad arguments");
+            return MTM_E_INVALID;
+        }
+        mtm::BlockPlan P;
+        const int rc = mtm::plan_blocks(rows, cols, chans, dtype, blocks, n_blocks, margin, 1ll << 62,
+                                        "mtm_debug_plan_blocks_stack", P);
+        if (rc != MTM_OK) return rc;
+        std::copy(P.clip.begin(), P.clip.end(), clip);
     }
     return MTM_OK;
 }

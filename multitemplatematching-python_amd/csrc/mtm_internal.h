@@ -157,6 +157,9 @@ struct BlockPlan {
     std::vector<TrackTile> tiles;           // {k, 1, ty0, tx0}: block after block, row-major over each block's map
     std::vector<BlockChunk> chunks;         // whole blocks, in order, each within the budget (a single block may pass it)
     size_t max_bytes = 0;                   // the largest chunk's template bytes
+    // block k: (ox, oy) = clip[2 k], clip[2 k + 1], how far its box was clipped at the left and at the top - output (y, x)
+    // of its map is displacement (x + ox - margin, y + oy - margin), cell (y + oy, x + ox) of its (2 margin + 1)^2 plane
+    std::vector<int32_t> clip;
 };
 // The blocks of a call checked and laid out: images of rows x cols x chans `dtype` pixels; block k's search box is its own
 // box widened by `margin` on every side and clipped to the image (MTM.blocks.search_box), its map that of a template of
@@ -164,6 +167,18 @@ struct BlockPlan {
 // within budget_bytes.  MTM_OK, or the code and message (set_error, prefixed `who`) of the first block that is not valid.
 int plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* blocks, int n_blocks, int margin,
                 long long budget_bytes, const char* who, BlockPlan& plan);
+
+// ---- the frame chunks of a block-matching call over a frame stack (mtm_match_blocks_stack, mtm_blocks.hip)
+
+// One upload: the stack [frame `carried`, frames f0 .. f0 + nf - 1] - the carried frame brings the reference into the
+// chunk - and the pairs p0 .. p0 + nf - 1 it runs: pair p searches frame p + 1 (stack slot p + 2 - f0); its reference is
+// frame p (slot p + 1 - f0; slot 0 for p = p0) or, mode "first", frame 0 (slot 0).
+struct StackChunk {
+    int f0, nf, carried, p0;
+};
+// n_frames >= 2 frames in stacks of at most frames_per_chunk >= 2 frames each; mode: MTM_BLOCKS_REF_PREVIOUS / _FIRST.
+// Frame 0 is the first chunk's carried frame: every frame is uploaded once, plus one carried frame per later chunk.
+std::vector<StackChunk> plan_blocks_stack(int n_frames, int frames_per_chunk, int mode);
 
 // float32-faithful restatement of cv2.dnn.NMSBoxes as called by MTM.NMS
 void nms_boxes(const mtm_hit* hits, int64_t n, const float* scores, float score_threshold,

@@ -452,7 +452,7 @@ __global__ __launch_bounds__(256) void track_reacquire_sets_kernel(ImageDev img,
 
 }  // namespace mtm
 
-namespace {
+namespace mtmi {
 
 // Frames per chunk: the row bound of the stacked image (MTM_OPT_BATCH_MAX_ROWS) and the device memory of its planes (raw
 // copy, uint8 / byte / float32 planes: at most 10 bytes per pixel and channel); no score maps are held.
@@ -463,6 +463,10 @@ int track_chunk_frames(const mtm_ctx* c, int rows, int cols, int chans) {
     const int by_mem = (int)std::max(1.0, std::min(1e9, kBatchChunkBytes / per_frame));
     return std::min(by_rows, by_mem);
 }
+
+}  // namespace mtmi
+
+namespace {
 
 // The templates of the tracks as the caller holds them - interleaved pixels, tightly packed, track after track - from
 // their planes `planar` (track k's at toff[k]: prepare_window_templates' layout).

@@ -13,7 +13,17 @@ Data from synth.py: a photograph-like reference (smooth_u8; uint16 = 257 x that 
 image, the reference moved by a few pixels (wrapping around) with a little noise.  Each method is warmed up first; the
 three calls are interleaved within a repetition; medians over the repetitions.
 
-Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3]
+--stack F: the movie form instead - F frames of the same shapes and block grids (frame f = the reference moved by f times
+the shift, with noise), milliseconds per PAIR of
+  stack_previous / stack_first - matchBlocksStack(frames, grid, margin, reference=...)
+  stack_ensemble               - matchBlocksStack(..., ensemble=True): the averaged planes and their peaks
+  loop                         - matchBlocks over the F - 1 pairs ("previous"), what a user writes without the call
+with ``equal_to_loop`` (both reference modes against their loops, positions and score bits) and, on a movie of at most 8
+frames of noise around a weak pattern that moves by (2, 1) a frame (``noisy_movie``: a single pair's peak about 2.5 standard
+deviations above the correlation noise of a block), the fraction of blocks found at that step by the pairs' own peaks
+(``noisy_found_pairs``, mean over the pairs) and by the ensemble peak (``noisy_found_ensemble``).
+
+Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F]
 """
 import argparse
 import json
@@ -101,11 +111,99 @@ def run(MTM, spec, reps, warmup):
     }
 
 
+def movie(spec, n, seed=0, shift=(3, -2)):
+    ref, _ = workload(spec, seed, shift)
+    rng = np.random.default_rng(seed + 20)
+    top = 65535 if ref.dtype == np.uint16 else 255
+    frames = [ref]
+    for f in range(1, n):
+        a = np.roll(ref, (f * shift[1], f * shift[0]), axis=(0, 1)).astype(np.int32)
+        a += rng.integers(-2, 3, size=ref.shape, dtype=np.int32)
+        frames.append(np.clip(a, 0, top).astype(ref.dtype))
+    return frames
+
+
+def noisy_movie(spec, n, seed=0, step=(2, 1), sigma=22.0, z=2.5):
+    """n frames of noise (standard deviation `sigma` grey levels) around a weak random pattern that moves by `step` a
+    frame.  The pattern's amplitude is set from the block size: two frames' matching blocks correlate with rho = the
+    pattern's share of a frame's variance, the correlation of unrelated blocks of n_pix values scatters by about
+    1 / sqrt(n_pix), and rho is chosen `z` such standard deviations high - a single pair's peak is marginal at any block
+    size, the mean of P planes stands sqrt(P) times higher."""
+    name, hw, chans, dtype, side, margin = spec
+    ref, _ = workload(spec, seed)
+    rng = np.random.default_rng(seed + 30)
+    scale = 257.0 if ref.dtype == np.uint16 else 1.0
+    base = rng.integers(0, 256, size=ref.shape).astype(np.float32) - 127.5
+    rho = z / np.sqrt(side * side * chans)
+    amp = np.sqrt(rho / (1.0 - rho)) * sigma / float(base.std())
+    frames = []
+    for f in range(n):
+        a = 128 + amp * np.roll(base, (f * step[1], f * step[0]), axis=(0, 1))
+        a += sigma * rng.standard_normal(size=ref.shape, dtype=np.float32)
+        frames.append((np.clip(a, 0, 255) * scale).astype(ref.dtype))
+    return frames
+
+
+def run_stack(MTM, spec, n_frames, reps, warmup):
+    from MTM import blocks as B
+    name, hw, chans, dtype, side, margin = spec
+    frames = movie(spec, n_frames)
+    grid = B.grid(frames[0].shape, side)
+    method = MTM.TM_CCOEFF_NORMED
+    pairs = n_frames - 1
+
+    def loop(first=False):
+        res = [MTM.matchBlocks(frames[0 if first else p], frames[p + 1], grid, margin, method) for p in range(pairs)]
+        return np.stack([r[0] for r in res]), np.stack([r[1] for r in res])
+
+    methods = {
+        "stack_previous": lambda: MTM.matchBlocksStack(frames, grid, margin, method),
+        "stack_first": lambda: MTM.matchBlocksStack(frames, grid, margin, method, reference="first"),
+        "stack_ensemble": lambda: MTM.matchBlocksStack(frames, grid, margin, method, ensemble=True),
+        "loop": loop,
+    }
+    results = {}
+    for k, fn in methods.items():
+        for _ in range(warmup):
+            results[k] = fn()
+    ms = {k: [] for k in methods}
+    for _ in range(reps):
+        for k, fn in methods.items():
+            t0 = time.perf_counter()
+            fn()
+            ms[k].append((time.perf_counter() - t0) * 1e3 / pairs)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+
+    def same(a, b):
+        return bool((a[0] == b[0]).all() and a[1].tobytes() == b[1].tobytes())
+
+    equal = same(results["stack_previous"], results["loop"]) and same(results["stack_first"], loop(first=True))
+    noisy = noisy_movie(spec, min(n_frames, 8))
+    step = (2, 1)
+    ppos, _ = MTM.matchBlocksStack(noisy, grid, margin, method)
+    epos, _, _ = MTM.matchBlocksStack(noisy, grid, margin, method, ensemble=True)
+    found = lambda pos: float(np.mean((B.displacements(grid, pos) == step).all(axis=1)))     # noqa: E731
+    return {
+        "workload": name, "image": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype), "frames": n_frames, "pairs": pairs,
+        "blocks": int(len(grid)), "block": side, "margin": margin, "map": "%dx%d" % (2 * margin + 1, 2 * margin + 1),
+        "ms_per_pair": {k: round(v, 3) for k, v in med.items()},
+        "ms_per_pair_min": {k: round(min(v), 3) for k, v in ms.items()},
+        "speedup_vs_loop": {k: round(med["loop"] / med[k], 2) for k in ("stack_previous", "stack_first", "stack_ensemble")},
+        "equal_to_loop": equal,
+        "found_shift": float(np.mean((B.displacements(grid, results["stack_previous"][0][0]) == (3, -2)).all(axis=1))),
+        "noisy_frames": len(noisy),
+        "noisy_found_pairs": round(float(np.mean([found(p) for p in ppos])), 4),
+        "noisy_found_ensemble": round(found(epos), 4),
+        "reps": reps,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--only", default=None, help="run the one workload of this name (profiling runs)")
+    ap.add_argument("--stack", type=int, default=0, metavar="F", help="the movie form: matchBlocksStack over F frames")
     args = ap.parse_args()
     import build as mtm_build
     mtm_build.build()
@@ -113,7 +211,12 @@ def main():
     for spec in WORKLOADS:
         if args.only and spec[0] != args.only:
             continue
-        print(json.dumps(run(MTM, spec, args.reps, args.warmup)), flush=True)
+        if args.stack:
+            if args.stack < 2:
+                ap.error("--stack needs two frames at least")
+            print(json.dumps(run_stack(MTM, spec, args.stack, args.reps, args.warmup)), flush=True)
+        else:
+            print(json.dumps(run(MTM, spec, args.reps, args.warmup)), flush=True)
 
 
 if __name__ == "__main__":

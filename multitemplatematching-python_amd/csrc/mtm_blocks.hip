@@ -5,14 +5,16 @@
 // blocks_gather_kernel cuts every block out of the reference's planes into planes of the call's own - the layout
 // prepare_window_templates gives a template set - and computes the constants mtm_set_templates would give it
 // (templ_stats_from_sums_inl, the single source of host and device); blocks_score_kernel scores the tiles of every block's
-// map with the window kernels' exact sums (win_tile_sums_u8 / win_tile_sums_u16, win_score: the exhaustive map's float32
-// bits) and keeps each block's extremum in a key, no map is written; blocks_nbhd_kernel, where asked for, decodes the keys
-// and scores the 3 x 3 neighbourhoods in the whole image's map.  plan_blocks (mtm_host.cpp) checks the blocks and lays out
+// map with the window kernels' tile scorer (win_score_tile, mtm_k_window.hip.h: the exhaustive map's float32 bits) and
+// keeps each block's extremum in a key, no map is written; blocks_nbhd_kernel, where asked for, decodes the keys and
+// scores the 3 x 3 neighbourhoods in the whole image's map.  plan_blocks (mtm_host.cpp) checks the blocks and lays out
 // the unit and tile tables and the chunks; the host waits once per call.  uint8 (1 or 3 channels) and single-channel
 // uint16.  The template set of the context is neither read nor written.
 // mtm_match_blocks_stack runs the same chain for every pair of a frame stack: the frames go up in stacked
 // chunks (plan_blocks_stack, mtm_host.cpp), every pair has a row of keys of its own, and - ensemble planes - blocks_plane_kernel
 // adds every output's score to the block's plane of float64 sums instead of keeping an extremum.
+// Both entry points are compositions of the same host steps: check_block_images, stage_block_tables, blocks_pair (a
+// pair's launch chain, the one place the kernels are launched) and decode_block_keys.
 #include <climits>
 #include <type_traits>
 
@@ -28,8 +30,6 @@ using namespace mtmi;
 namespace mtm {
 
 static_assert(kTrackTile == kWinTile, "plan_blocks tiles the maps as the window kernels walk them");
-
-constexpr size_t kBlockLaunchGroups = (size_t)1 << 22;      // most work-groups of one blocks_* launch
 
 // Grid: one 256-thread work-group per block (launch slice; block k = k0 + blockIdx.x).  `ref` is the reference image - the
 // stack's planes entered at its first row and bounded by its own `rows` -: uint8, plane c at ref.u8 + c * u8_plane;
@@ -98,8 +98,8 @@ __global__ __launch_bounds__(256) void blocks_gather_kernel(ImageDev ref, const 
 
 // Grid: one work-group per tile of the chunk's part of the tile table (launch slice).  `img` is the searched image, entered
 // and bounded as `ref` above: no row of the reference is read.  The windows of tile (ty0, tx0) of block u0's map are summed
-// and scored exactly as boxes_score_kernel does - the same float32 bits -, with the gathered template of the block, and
-// instead of a map the tile's best output goes into keys[u0] (track_merge_key): order(quality) << 32 | ~index, one
+// and scored by win_score_tile - boxes_score_kernel's float32 bits, the same function -, with the gathered template of the
+// block, and instead of a map the tile's best output goes into keys[u0] (win_merge_key): order(quality) << 32 | ~index, one
 // atomicMax per wave.  Every tile of the table lies inside its map (plan_blocks); a (2 margin + 1)^2 map fills only part of
 // its tiles.
 template <int CH, bool U16>
@@ -113,26 +113,16 @@ __global__ __launch_bounds__(256) void blocks_score_kernel(ImageDev img, const u
     const TrackTile K = tiles[blockIdx.x];
     const TrackUnit U = units[K.u0];
     const TemplDev T = td[K.u0];
-    const int h = T.rows, w = T.cols;
-    const uint8_t* tp = tpx + toff[K.u0];
-    const int tid = threadIdx.x;
-    const double inv_area = 1.0 / ((double)h * (double)w);
-    unsigned long long corr, s2, s1[CH];
-    if constexpr (U16)
-        win_tile_sums_u16(Tl[0], Tl[1], Il[0], Il[1], img.u8, lo_b, img.u8_pitch, img.rows, img.cols, tp, h, w, U.y0 + K.ty0,
-                          U.x0 + K.tx0, corr, s1[0], s2);
-    else
-        win_tile_sums_u8<CH>(Tl[0], Il[0], img.u8, img.u8_plane, img.u8_pitch, img.rows, img.cols, tp, h, w, U.y0 + K.ty0,
-                             U.x0 + K.tx0, corr, s1, s2);
-    const int y = K.ty0 + tid / kWinTile, x = K.tx0 + tid % kWinTile;
-    track_merge_key(y < U.oh && x < U.ow, 0xFFFFFFFFull - (unsigned long long)((long long)y * U.ow + x), mode_min,
-                    [&] { return win_score<CH>(method, T, inv_area, corr, s1, s2); }, keys + K.u0);
+    win_score_tile<CH, U16>(Tl, Il, img, lo_b, tpx + toff[K.u0], T, U.y0 + K.ty0, U.x0 + K.tx0, K.ty0, K.tx0, U.oh, U.ow, method,
+                            [&](bool inside, int y, int x, auto&& score) {
+                                win_merge_key(inside, win_pos_word(y, x, U.ow), mode_min, score, keys + K.u0);
+                            });
 }
 
-// blocks_score_kernel's sibling for the ensemble planes of mtm_match_blocks_stack: the same tile, sums and float32 score
-// (win_tile_sums_*, win_score), and instead of merging a key every output (y, x) of the map adds its score, widened to
-// float64, to its cell of block u0's side x side plane of sums: acc[(u0 side + y + oy) side + x + ox], (ox, oy) =
-// clip[2 u0], clip[2 u0 + 1] the block's clip offsets (BlockPlan::clip: y + oy, x + ox < side).  A plain read-modify-write:
+// blocks_score_kernel's sibling for the ensemble planes of mtm_match_blocks_stack: the same tile and float32 score
+// (win_score_tile), and instead of merging a key every output (y, x) of the map adds its score, widened to float64, to its
+// cell of block u0's side x side plane of sums: acc[(u0 side + y + oy) side + x + ox], (ox, oy) = clip[2 u0],
+// clip[2 u0 + 1] the block's clip offsets (BlockPlan::clip: y + oy, x + ox < side).  A plain read-modify-write:
 // the tile table partitions every map, so a cell has one writer per launch, and the launches of successive pairs are
 // ordered by the call's one stream - the sums are those of the pairs in order, bit for bit.  `first` (the call's first
 // pair) stores instead of adding: the sum starts from s_0 itself, a -0.0 included.
@@ -148,24 +138,15 @@ __global__ __launch_bounds__(256) void blocks_plane_kernel(ImageDev img, const u
     const TrackTile K = tiles[blockIdx.x];
     const TrackUnit U = units[K.u0];
     const TemplDev T = td[K.u0];
-    const int h = T.rows, w = T.cols;
-    const uint8_t* tp = tpx + toff[K.u0];
-    const int tid = threadIdx.x;
-    const double inv_area = 1.0 / ((double)h * (double)w);
-    unsigned long long corr, s2, s1[CH];
-    if constexpr (U16)
-        win_tile_sums_u16(Tl[0], Tl[1], Il[0], Il[1], img.u8, lo_b, img.u8_pitch, img.rows, img.cols, tp, h, w, U.y0 + K.ty0,
-                          U.x0 + K.tx0, corr, s1[0], s2);
-    else
-        win_tile_sums_u8<CH>(Tl[0], Il[0], img.u8, img.u8_plane, img.u8_pitch, img.rows, img.cols, tp, h, w, U.y0 + K.ty0,
-                             U.x0 + K.tx0, corr, s1, s2);
-    const int y = K.ty0 + tid / kWinTile, x = K.tx0 + tid % kWinTile;
-    const int cy = y + clip[2 * K.u0 + 1], cx = x + clip[2 * K.u0];
-    if (y < U.oh && x < U.ow && cy < side && cx < side) {
-        const float s = win_score<CH>(method, T, inv_area, corr, s1, s2);
-        double* cell = acc + ((size_t)K.u0 * (size_t)side + (size_t)cy) * (size_t)side + (size_t)cx;
-        *cell = first ? (double)s : *cell + (double)s;
-    }
+    win_score_tile<CH, U16>(Tl, Il, img, lo_b, tpx + toff[K.u0], T, U.y0 + K.ty0, U.x0 + K.tx0, K.ty0, K.tx0, U.oh, U.ow, method,
+                            [&](bool inside, int y, int x, auto&& score) {
+                                const int cy = y + clip[2 * K.u0 + 1], cx = x + clip[2 * K.u0];
+                                if (inside && cy < side && cx < side) {
+                                    const float s = score();
+                                    double* cell = acc + ((size_t)K.u0 * (size_t)side + (size_t)cy) * (size_t)side + (size_t)cx;
+                                    *cell = first ? (double)s : *cell + (double)s;
+                                }
+                            });
 }
 
 // Grid: one 256-thread work-group per block (launch slice; block k = k0 + blockIdx.x), after the chunk's score launches:
@@ -220,6 +201,130 @@ ImageDev stack_view(const ImageDev& st, int row_off, int rows) {
     return v;
 }
 
+// What both entry points check of their images behind check_image_args: the pixel kind, and that a pair's two images -
+// one stack - stay within the rows a layout launch's grid holds.  `noun`: "images" / "frames", as the entry names them.
+int check_block_images(const char* who, const std::string& noun, int rows, int chans, int dtype) {
+    if (!((dtype == MTM_U8 && (chans == 1 || chans == 3)) || (dtype == MTM_U16 && chans == 1))) {
+        set_error(std::string(who) + ": takes uint8 " + noun + " with 1 or 3 channels and single-channel uint16 " + noun);
+        return MTM_E_INVALID;
+    }
+    if (2ll * rows > kBatchMaxRows) {
+        set_error(std::string(who) + ": " + noun + " of more than " + std::to_string(kBatchMaxRows / 2) + " rows");
+        return MTM_E_INVALID;
+    }
+    return MTM_OK;
+}
+
+// The call's buffers, sized by the plan - template planes, the block, offset, constant, unit and tile tables, then either
+// `cells` float64 sums with the clip table (ensemble planes: cells > 0) or n_pairs rows of keys (and of neighbourhoods,
+// want_nbhd) -, then before() - what the entry enqueues ahead of the call's clock -, the event the call's time counts
+// from, and the tables and zeroed results on the stream.
+template <class Before>
+int stage_block_tables(mtm_ctx* c, const mtm_block* blocks, const BlockPlan& P, size_t n_pairs, bool want_nbhd, size_t cells,
+                       Before&& before) {
+    const size_t n = P.units.size();
+    HIPC(hipSetDevice(c->device));
+    c->timing = mtm_timing{};
+    c->maps_valid = false;
+    c->last_hits.clear();
+    MTMC(c->blk_tpx.ensure(P.max_bytes));
+    MTMC(c->blk_toff.ensure(sizeof(long long) * n));
+    MTMC(c->blk_td.ensure(sizeof(TemplDev) * n));
+    MTMC(c->blk_blocks.ensure(sizeof(mtm_block) * n));
+    MTMC(c->blk_units.ensure(sizeof(TrackUnit) * n));
+    MTMC(c->blk_tiles.ensure(sizeof(TrackTile) * P.tiles.size()));
+    if (cells) {
+        MTMC(c->blk_clip.ensure(sizeof(int32_t) * 2 * n));
+        MTMC(c->blk_acc.ensure(sizeof(double) * cells));
+    } else {
+        MTMC(c->blk_keys.ensure(sizeof(unsigned long long) * n_pairs * n));
+        if (want_nbhd) MTMC(c->blk_nbhd.ensure(sizeof(float) * 9 * n_pairs * n));
+    }
+    MTMC(before());
+    HIPC(hipEventRecord(c->ev[0], c->stream));
+    HIPC(hipMemcpyAsync(c->blk_blocks.p, blocks, sizeof(mtm_block) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_toff.p, P.toff.data(), sizeof(long long) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_units.p, P.units.data(), sizeof(TrackUnit) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_tiles.p, P.tiles.data(), sizeof(TrackTile) * P.tiles.size(), hipMemcpyHostToDevice, c->stream));
+    if (cells) {
+        HIPC(hipMemcpyAsync(c->blk_clip.p, P.clip.data(), sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
+        HIPC(hipMemsetAsync(c->blk_acc.p, 0, sizeof(double) * cells, c->stream));
+    } else {
+        HIPC(hipMemsetAsync(c->blk_keys.p, 0, sizeof(unsigned long long) * n_pairs * n, c->stream));
+    }
+    return MTM_OK;
+}
+
+// What a pair's chain writes: a row of keys (and of neighbourhoods, or nullptr), or - side > 0, ensemble planes - the
+// call's planes of sums, which the call's first pair starts.
+struct BlockSink {
+    unsigned long long* keys;
+    float* nbhd;
+    int side, first;
+};
+
+// One pair's launch chain for every block chunk - gather (unless the templates are already there), score or plane,
+// [neighbourhoods] - in stream order: the next chunk's gather overwrites the template planes behind this chunk's last
+// reader, and the host waits for none of them.  The pair is the stack's current image: the reference its rows
+// r_slot * rows .., the searched image its rows i_slot * rows ...
+int blocks_pair(mtm_ctx* c, const BlockPlan& P, int rows, int chans, int dtype, int method, int r_slot, int i_slot, bool gather,
+                const BlockSink& S) {
+    const ImageDev st = image_dev(c);
+    const uint8_t* st_lo = c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane;        // uint16: [high ^ 0x80][low ^ 0x80]
+    const ImageDev ref = stack_view(st, r_slot * rows, rows), img = stack_view(st, i_slot * rows, rows);
+    const uint8_t* ref_lo = st_lo + (size_t)r_slot * rows * st.u8_pitch;
+    const uint8_t* img_lo = st_lo + (size_t)i_slot * rows * st.u8_pitch;
+    const int mode_min = method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED ? 1 : 0;
+    uint8_t* tpx = c->blk_tpx.as<uint8_t>();
+    const long long* toff = c->blk_toff.as<long long>();
+    TemplDev* td = c->blk_td.as<TemplDev>();
+    const TrackUnit* units = c->blk_units.as<TrackUnit>();
+    return blocks_dispatch(dtype, chans, [&](auto ch, auto u16) -> int {
+        constexpr int CH = decltype(ch)::value;
+        constexpr bool U16 = decltype(u16)::value;
+        for (const BlockChunk& C : P.chunks) {
+            if (gather)
+                MTMC(for_launch_slices((size_t)C.b0, (size_t)C.b1, [&](size_t b0, unsigned nb) -> int {
+                    hipLaunchKernelGGL((blocks_gather_kernel<CH, U16>), dim3(nb), dim3(256), 0, c->stream, ref, ref_lo,
+                                       c->blk_blocks.as<mtm_block>(), (int)b0, tpx, toff, td, method);
+                    HIPC(hipGetLastError());
+                    return MTM_OK;
+                }));
+            MTMC(for_launch_slices(C.t0, C.t1, [&](size_t t0, unsigned nt) -> int {
+                if (S.side > 0)
+                    hipLaunchKernelGGL((blocks_plane_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo, tpx, toff,
+                                       td, units, c->blk_tiles.as<TrackTile>() + t0, method, c->blk_clip.as<int32_t>(), S.side,
+                                       S.first, c->blk_acc.as<double>());
+                else
+                    hipLaunchKernelGGL((blocks_score_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo, tpx, toff,
+                                       td, units, c->blk_tiles.as<TrackTile>() + t0, method, mode_min, S.keys);
+                HIPC(hipGetLastError());
+                return MTM_OK;
+            }));
+            if (S.nbhd)
+                MTMC(for_launch_slices((size_t)C.b0, (size_t)C.b1, [&](size_t b0, unsigned nb) -> int {
+                    hipLaunchKernelGGL((blocks_nbhd_kernel<CH, U16>), dim3(nb), dim3(256), 0, c->stream, img, img_lo, tpx, toff,
+                                       td, units, S.keys, (int)b0, method, S.nbhd);
+                    HIPC(hipGetLastError());
+                    return MTM_OK;
+                }));
+        }
+        return MTM_OK;
+    });
+}
+
+// A pair's row of keys as hits: each block's extremum in its own map, moved by the map's origin into image coordinates.
+void decode_block_keys(const BlockPlan& P, const mtm_block* blocks, const unsigned long long* hkeys, int method, mtm_hit* out) {
+    const bool mode_min = method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED;
+    for (size_t k = 0; k < P.units.size(); ++k) {
+        const TrackUnit& u = P.units[k];
+        mtm_hit r = decode_quality_key(hkeys[k], mode_min, (int)k, u.ow, blocks[k].w, blocks[k].h);
+        r.x += u.x0;
+        r.y += u.y0;
+        out[k] = r;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -236,83 +341,21 @@ int mtm_match_blocks(mtm_ctx* c, const void* reference, int64_t reference_stride
     MTM_NOT_IN_FLIGHT(c, who);
     MTMC(check_image_args(reference, rows, cols, chans, dtype, reference_stride_bytes, who));
     MTMC(check_image_args(image, rows, cols, chans, dtype, image_stride_bytes, who));
-    if (!((dtype == MTM_U8 && (chans == 1 || chans == 3)) || (dtype == MTM_U16 && chans == 1))) {
-        set_error(std::string(who) + ": takes uint8 images with 1 or 3 channels and single-channel uint16 images");
-        return MTM_E_INVALID;
-    }
-    // (the two images are one stack: its rows stay within what a layout launch's grid holds)
-    if (2ll * rows > kBatchMaxRows) {
-        set_error(std::string(who) + ": images of more than " + std::to_string(kBatchMaxRows / 2) + " rows");
-        return MTM_E_INVALID;
-    }
+    MTMC(check_block_images(who, "images", rows, chans, dtype));
     BlockPlan P;
     MTMC(plan_blocks(rows, cols, chans, dtype, blocks, n_blocks, margin, 4 * (long long)c->boxes_max_floats, who, P));
     if (n_blocks == 0) return MTM_OK;
-
-    HIPC(hipSetDevice(c->device));
-    c->timing = mtm_timing{};
-    c->maps_valid = false;
-    c->last_hits.clear();
     const size_t n = (size_t)n_blocks;
-    MTMC(c->blk_tpx.ensure(P.max_bytes));
-    MTMC(c->blk_toff.ensure(sizeof(long long) * n));
-    MTMC(c->blk_td.ensure(sizeof(TemplDev) * n));
-    MTMC(c->blk_blocks.ensure(sizeof(mtm_block) * n));
-    MTMC(c->blk_units.ensure(sizeof(TrackUnit) * n));
-    MTMC(c->blk_tiles.ensure(sizeof(TrackTile) * P.tiles.size()));
-    MTMC(c->blk_keys.ensure(sizeof(unsigned long long) * n));
-    if (nbhd) MTMC(c->blk_nbhd.ensure(sizeof(float) * 9 * n));
 
-    // ONE upload of each image: the stack's rows 0 .. rows - 1 are the reference, rows .. 2 rows - 1 the image
-    adopt_image(c, 2 * rows, cols, chans, dtype);
-    MTMC(upload_image_pair(c, c->slot[c->cur], reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans,
-                           dtype, c->stream));
-    const ImageDev st = image_dev(c);
-    const uint8_t* st_lo = c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane;        // uint16: [high ^ 0x80][low ^ 0x80]
-    const ImageDev ref = stack_view(st, 0, rows), img = stack_view(st, rows, rows);
-    const uint8_t* ref_lo = st_lo;
-    const uint8_t* img_lo = st_lo + (size_t)rows * st.u8_pitch;
-
-    HIPC(hipEventRecord(c->ev[0], c->stream));
-    HIPC(hipMemcpyAsync(c->blk_blocks.p, blocks, sizeof(mtm_block) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_toff.p, P.toff.data(), sizeof(long long) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_units.p, P.units.data(), sizeof(TrackUnit) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_tiles.p, P.tiles.data(), sizeof(TrackTile) * P.tiles.size(), hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemsetAsync(c->blk_keys.p, 0, sizeof(unsigned long long) * n, c->stream));
-
-    const int mode_min = method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED ? 1 : 0;
-    uint8_t* tpx = c->blk_tpx.as<uint8_t>();
-    const long long* toff = c->blk_toff.as<long long>();
-    TemplDev* td = c->blk_td.as<TemplDev>();
-    const TrackUnit* units = c->blk_units.as<TrackUnit>();
-    unsigned long long* keys = c->blk_keys.as<unsigned long long>();
-    // a chunk's launch chain - gather, score, [neighbourhoods] - in stream order: the next chunk's gather overwrites the
-    // template planes behind this chunk's last reader, and the host waits for none of them
-    MTMC(blocks_dispatch(dtype, chans, [&](auto ch, auto u16) -> int {
-        constexpr int CH = decltype(ch)::value;
-        constexpr bool U16 = decltype(u16)::value;
-        for (const BlockChunk& C : P.chunks) {
-            for (size_t b0 = (size_t)C.b0; b0 < (size_t)C.b1; b0 += kBlockLaunchGroups) {
-                const unsigned nb = (unsigned)std::min(kBlockLaunchGroups, (size_t)C.b1 - b0);
-                hipLaunchKernelGGL((blocks_gather_kernel<CH, U16>), dim3(nb), dim3(256), 0, c->stream, ref, ref_lo,
-                                   c->blk_blocks.as<mtm_block>(), (int)b0, tpx, toff, td, method);
-                HIPC(hipGetLastError());
-            }
-            for (size_t t0 = C.t0; t0 < C.t1; t0 += kBlockLaunchGroups) {
-                const unsigned nt = (unsigned)std::min(kBlockLaunchGroups, C.t1 - t0);
-                hipLaunchKernelGGL((blocks_score_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo, tpx, toff, td,
-                                   units, c->blk_tiles.as<TrackTile>() + t0, method, mode_min, keys);
-                HIPC(hipGetLastError());
-            }
-            for (size_t b0 = (size_t)C.b0; nbhd && b0 < (size_t)C.b1; b0 += kBlockLaunchGroups) {
-                const unsigned nb = (unsigned)std::min(kBlockLaunchGroups, (size_t)C.b1 - b0);
-                hipLaunchKernelGGL((blocks_nbhd_kernel<CH, U16>), dim3(nb), dim3(256), 0, c->stream, img, img_lo, tpx, toff, td,
-                                   units, keys, (int)b0, method, c->blk_nbhd.as<float>());
-                HIPC(hipGetLastError());
-            }
-        }
-        return MTM_OK;
+    // ONE upload of each image, ahead of the call's clock: the stack's rows 0 .. rows - 1 are the reference, rows ..
+    // 2 rows - 1 the image
+    MTMC(stage_block_tables(c, blocks, P, 1, nbhd != nullptr, 0, [&]() -> int {
+        adopt_image(c, 2 * rows, cols, chans, dtype);
+        return upload_image_pair(c, c->slot[c->cur], reference, reference_stride_bytes, image, image_stride_bytes, rows, cols,
+                                 chans, dtype, c->stream);
     }));
+    unsigned long long* keys = c->blk_keys.as<unsigned long long>();
+    MTMC(blocks_pair(c, P, rows, chans, dtype, method, 0, 1, true, BlockSink{keys, nbhd ? c->blk_nbhd.as<float>() : nullptr, 0, 0}));
 
     // the keys (and neighbourhoods) come back behind the call's single wait
     std::vector<unsigned long long> hkeys(n);
@@ -322,13 +365,7 @@ int mtm_match_blocks(mtm_ctx* c, const void* reference, int64_t reference_stride
     HIPC(hipStreamSynchronize(c->stream));
     HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
     c->timing.n_hits = (int64_t)n;
-    for (size_t k = 0; k < n; ++k) {
-        const TrackUnit& u = P.units[k];
-        mtm_hit r = decode_quality_key(hkeys[k], mode_min != 0, (int)k, u.ow, blocks[k].w, blocks[k].h);
-        r.x += u.x0;
-        r.y += u.y0;
-        out[k] = r;
-    }
+    decode_block_keys(P, blocks, hkeys.data(), method, out);
     // the stack is none of the caller's images: no current image, no published maps
     c->have_image = false;
     return MTM_OK;
@@ -346,15 +383,7 @@ int mtm_match_blocks_stack(mtm_ctx* c, const void* const* frames, int n_frames, 
     }
     MTM_NOT_IN_FLIGHT(c, who);
     for (int f = 0; f < n_frames; ++f) MTMC(check_image_args(frames[f], rows, cols, chans, dtype, row_stride_bytes, who));
-    if (!((dtype == MTM_U8 && (chans == 1 || chans == 3)) || (dtype == MTM_U16 && chans == 1))) {
-        set_error(std::string(who) + ": takes uint8 frames with 1 or 3 channels and single-channel uint16 frames");
-        return MTM_E_INVALID;
-    }
-    // (a pair's two frames are one stack: its rows stay within what a layout launch's grid holds)
-    if (2ll * rows > kBatchMaxRows) {
-        set_error(std::string(who) + ": frames of more than " + std::to_string(kBatchMaxRows / 2) + " rows");
-        return MTM_E_INVALID;
-    }
+    MTMC(check_block_images(who, "frames", rows, chans, dtype));
     BlockPlan P;
     MTMC(plan_blocks(rows, cols, chans, dtype, blocks, n_blocks, margin, 4 * (long long)c->boxes_max_floats, who, P));
     if (n_blocks == 0) return MTM_OK;
@@ -371,94 +400,26 @@ int mtm_match_blocks_stack(mtm_ctx* c, const void* const* frames, int n_frames, 
     }
     const size_t cells = ens ? (size_t)cells128 : 0;
 
-    HIPC(hipSetDevice(c->device));
-    c->timing = mtm_timing{};
-    c->maps_valid = false;
-    c->last_hits.clear();
-    MTMC(c->blk_tpx.ensure(P.max_bytes));
-    MTMC(c->blk_toff.ensure(sizeof(long long) * n));
-    MTMC(c->blk_td.ensure(sizeof(TemplDev) * n));
-    MTMC(c->blk_blocks.ensure(sizeof(mtm_block) * n));
-    MTMC(c->blk_units.ensure(sizeof(TrackUnit) * n));
-    MTMC(c->blk_tiles.ensure(sizeof(TrackTile) * P.tiles.size()));
-    if (ens) {
-        MTMC(c->blk_clip.ensure(sizeof(int32_t) * 2 * n));
-        MTMC(c->blk_acc.ensure(sizeof(double) * cells));
-    } else {
-        MTMC(c->blk_keys.ensure(sizeof(unsigned long long) * np * n));
-        if (nbhd) MTMC(c->blk_nbhd.ensure(sizeof(float) * 9 * np * n));
-    }
+    // the call's clock starts ahead of the uploads: the frames go up chunk by chunk between the pairs' chains
+    MTMC(stage_block_tables(c, blocks, P, np, nbhd != nullptr, cells, [] { return MTM_OK; }));
 
-    HIPC(hipEventRecord(c->ev[0], c->stream));
-    HIPC(hipMemcpyAsync(c->blk_blocks.p, blocks, sizeof(mtm_block) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_toff.p, P.toff.data(), sizeof(long long) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_units.p, P.units.data(), sizeof(TrackUnit) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_tiles.p, P.tiles.data(), sizeof(TrackTile) * P.tiles.size(), hipMemcpyHostToDevice, c->stream));
-    if (ens) {
-        HIPC(hipMemcpyAsync(c->blk_clip.p, P.clip.data(), sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
-        HIPC(hipMemsetAsync(c->blk_acc.p, 0, sizeof(double) * cells, c->stream));
-    } else {
-        HIPC(hipMemsetAsync(c->blk_keys.p, 0, sizeof(unsigned long long) * np * n, c->stream));
-    }
-
-    const int mode_min = method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED ? 1 : 0;
-    uint8_t* tpx = c->blk_tpx.as<uint8_t>();
-    const long long* toff = c->blk_toff.as<long long>();
-    TemplDev* td = c->blk_td.as<TemplDev>();
-    const TrackUnit* units = c->blk_units.as<TrackUnit>();
     // mode "first" with every block in one chunk: the gathered templates outlive the pairs of a frame chunk
     const bool gather_once = mode == MTM_BLOCKS_REF_FIRST && P.chunks.size() == 1;
     std::vector<const void*> px;
     // frame chunks sized as a tracking call's, never below two frames (plan_blocks_stack: a pair's reference and image lie
-    // in one stack); a frame chunk's upload, then per pair and block chunk the launch chain - gather, score, [neighbourhoods] - in stream
-    // order: the next upload overwrites the stack behind this chunk's last reader, and the host waits for none of them
+    // in one stack); a frame chunk's upload, then every pair's chain (blocks_pair) in stream order: the next upload
+    // overwrites the stack behind this chunk's last reader, and the host waits for none of them
     for (const StackChunk& S : plan_blocks_stack(n_frames, track_chunk_frames(c, rows, cols, chans), mode)) {
         px.assign(1, frames[S.carried]);
         px.insert(px.end(), frames + S.f0, frames + S.f0 + S.nf);
         adopt_image(c, (S.nf + 1) * rows, cols, chans, dtype);
         MTMC(upload_image_stack(c, c->slot[c->cur], px.data(), S.nf + 1, row_stride_bytes, rows, cols, chans, dtype, c->stream));
-        const ImageDev st = image_dev(c);
-        const uint8_t* st_lo = c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane;    // uint16: [high ^ 0x80][low ^ 0x80]
-        bool gathered = false;
         for (int i = 0; i < S.nf; ++i) {
-            const int r_slot = mode == MTM_BLOCKS_REF_FIRST ? 0 : i, i_slot = i + 1;
-            const ImageDev ref = stack_view(st, r_slot * rows, rows), img = stack_view(st, i_slot * rows, rows);
-            const uint8_t* ref_lo = st_lo + (size_t)r_slot * rows * st.u8_pitch;
-            const uint8_t* img_lo = st_lo + (size_t)i_slot * rows * st.u8_pitch;
-            unsigned long long* keys = ens ? nullptr : c->blk_keys.as<unsigned long long>() + (size_t)(S.p0 + i) * n;
-            float* nb_out = nbhd ? c->blk_nbhd.as<float>() + 9 * (size_t)(S.p0 + i) * n : nullptr;
-            MTMC(blocks_dispatch(dtype, chans, [&](auto ch, auto u16) -> int {
-                constexpr int CH = decltype(ch)::value;
-                constexpr bool U16 = decltype(u16)::value;
-                for (const BlockChunk& C : P.chunks) {
-                    for (size_t b0 = (size_t)C.b0; !(gather_once && gathered) && b0 < (size_t)C.b1; b0 += kBlockLaunchGroups) {
-                        const unsigned nb = (unsigned)std::min(kBlockLaunchGroups, (size_t)C.b1 - b0);
-                        hipLaunchKernelGGL((blocks_gather_kernel<CH, U16>), dim3(nb), dim3(256), 0, c->stream, ref, ref_lo,
-                                           c->blk_blocks.as<mtm_block>(), (int)b0, tpx, toff, td, method);
-                        HIPC(hipGetLastError());
-                    }
-                    for (size_t t0 = C.t0; t0 < C.t1; t0 += kBlockLaunchGroups) {
-                        const unsigned nt = (unsigned)std::min(kBlockLaunchGroups, C.t1 - t0);
-                        if (ens)
-                            hipLaunchKernelGGL((blocks_plane_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo,
-                                               tpx, toff, td, units, c->blk_tiles.as<TrackTile>() + t0, method,
-                                               c->blk_clip.as<int32_t>(), (int)side, S.p0 + i == 0 ? 1 : 0,
-                                               c->blk_acc.as<double>());
-                        else
-                            hipLaunchKernelGGL((blocks_score_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo,
-                                               tpx, toff, td, units, c->blk_tiles.as<TrackTile>() + t0, method, mode_min, keys);
-                        HIPC(hipGetLastError());
-                    }
-                    for (size_t b0 = (size_t)C.b0; nb_out && b0 < (size_t)C.b1; b0 += kBlockLaunchGroups) {
-                        const unsigned nb = (unsigned)std::min(kBlockLaunchGroups, (size_t)C.b1 - b0);
-                        hipLaunchKernelGGL((blocks_nbhd_kernel<CH, U16>), dim3(nb), dim3(256), 0, c->stream, img, img_lo, tpx,
-                                           toff, td, units, keys, (int)b0, method, nb_out);
-                        HIPC(hipGetLastError());
-                    }
-                }
-                return MTM_OK;
-            }));
-            gathered = true;
+            const size_t p = (size_t)(S.p0 + i);
+            const BlockSink sink{ens ? nullptr : c->blk_keys.as<unsigned long long>() + p * n,
+                                 nbhd ? c->blk_nbhd.as<float>() + 9 * p * n : nullptr, ens ? (int)side : 0, p == 0 ? 1 : 0};
+            MTMC(blocks_pair(c, P, rows, chans, dtype, method, mode == MTM_BLOCKS_REF_FIRST ? 0 : i, i + 1,
+                             !(gather_once && i > 0), sink));
         }
     }
 
@@ -490,14 +451,7 @@ int mtm_match_blocks_stack(mtm_ctx* c, const void* const* frames, int n_frames, 
                 }
         }
     } else {
-        for (size_t p = 0; p < np; ++p)
-            for (size_t k = 0; k < n; ++k) {
-                const TrackUnit& u = P.units[k];
-                mtm_hit r = decode_quality_key(hkeys[p * n + k], mode_min != 0, (int)k, u.ow, blocks[k].w, blocks[k].h);
-                r.x += u.x0;
-                r.y += u.y0;
-                out_hits[p * n + k] = r;
-            }
+        for (size_t p = 0; p < np; ++p) decode_block_keys(P, blocks, hkeys.data() + p * n, method, out_hits + p * n);
     }
     // the stacks are none of the caller's images: no current image, no published maps
     c->have_image = false;

@@ -1,6 +1,6 @@
 // libmtm_hip.so - many searchBoxes of one image in one call (mtm_find_matches_boxes): every (region, template)
 // pair - a unit - gets the score map of its crop, computed tile by tile over the whole chip with the exact integer sums and
-// the epilogue of every other score kernel (boxes_score_kernel), and the peak rules of mtm_find_matches applied to that map
+// the epilogue of every other score kernel (boxes_score_kernel: win_score_tile, mtm_k_window.hip.h), and the peak rules of mtm_find_matches applied to that map
 // alone (boxes_peaks_kernel; 1-D and 1x1 maps on the host, as mtm_find_matches treats them).  uint8 (1 or 3 channels) and
 // single-channel uint16, unmasked templates of one mtm_set_templates call.
 #include "mtm_ctx.h"
@@ -25,11 +25,10 @@ struct BoxUnit {
 struct BoxTile {
     int u, ty0, tx0;
 };
-constexpr size_t kBoxLaunchTiles = (size_t)1 << 22;     // most work-groups (tiles) of one boxes_* launch
 
 // Grid: one work-group per tile of the chunk's tile table, so that a large region spreads over the chip and many small
-// ones fill it together.  The tile's windows are summed by win_tile_sums_u8 / win_tile_sums_u16 straight from the image's
-// planes (a unit's outputs only read pixels of its region) and finished by win_score: the exhaustive map's float32 values.
+// ones fill it together.  win_score_tile sums the tile's windows straight from the image's planes (a unit's outputs only
+// read pixels of its region) and finishes them: the exhaustive map's float32 values, stored into the unit's map.
 template <int CH, bool U16>
 __global__ __launch_bounds__(256) void boxes_score_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
                                                           const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
@@ -41,19 +40,10 @@ __global__ __launch_bounds__(256) void boxes_score_kernel(ImageDev img, const ui
     const BoxTile K = tiles[blockIdx.x];
     const BoxUnit U = units[K.u];
     const TemplDev T = td[U.t];
-    const int h = T.rows, w = T.cols;
-    const uint8_t* tp = tpx + toff[U.t];
-    const int tid = threadIdx.x;
-    const double inv_area = 1.0 / ((double)h * (double)w);
-    unsigned long long corr, s2, s1[CH];
-    if constexpr (U16)
-        win_tile_sums_u16(Tl[0], Tl[1], Il[0], Il[1], img.u8, lo_b, img.u8_pitch, img.rows, img.cols, tp, h, w,
-                          U.y0 + K.ty0, U.x0 + K.tx0, corr, s1[0], s2);
-    else
-        win_tile_sums_u8<CH>(Tl[0], Il[0], img.u8, img.u8_plane, img.u8_pitch, img.rows, img.cols, tp, h, w, U.y0 + K.ty0,
-                             U.x0 + K.tx0, corr, s1, s2);
-    const int y = K.ty0 + tid / kWinTile, x = K.tx0 + tid % kWinTile;
-    if (y < U.oh && x < U.ow) buf[U.buf_off + (long long)y * U.ow + x] = win_score<CH>(method, T, inv_area, corr, s1, s2);
+    win_score_tile<CH, U16>(Tl, Il, img, lo_b, tpx + toff[U.t], T, U.y0 + K.ty0, U.x0 + K.tx0, K.ty0, K.tx0, U.oh, U.ow, method,
+                            [&](bool inside, int y, int x, auto&& score) {
+                                if (inside) buf[U.buf_off + (long long)y * U.ow + x] = score();
+                            });
 }
 
 // Grid: the tiles again (local mode: only those of units with 2-D maps).  Per output of the unit's own map:
@@ -198,20 +188,19 @@ int boxes_chunk(mtm_ctx* c, const mtm_box_unit* units, const std::vector<BlobTem
 
     const ImageDev img = image_dev(c);
     const uint8_t* lo_b = c->slot[c->cur].u8b.as<uint8_t>() + img.u8_plane;     // uint16: [high ^ 0x80][low ^ 0x80]
-    // (both kernels run over the tile table in slices of at most kBoxLaunchTiles work-groups: one dispatch stays far below
-    // 2^32 work items however many tiles a chunk or a single unit has)
-#define MTM_BOX_LAUNCH(CH, U16)                                                                                              \
-    hipLaunchKernelGGL((boxes_score_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, lo_b,                          \
-                       c->win_tpx.as<uint8_t>(), c->win_toff.as<long long>(), c->box_td.as<TemplDev>(),                      \
-                       c->box_units.as<BoxUnit>(), c->box_tiles.as<BoxTile>() + t0, c->win_buf.as<float>(), c->method)
-    for (size_t t0 = 0; t0 < tiles.size(); t0 += kBoxLaunchTiles) {
-        const unsigned nt = (unsigned)std::min(kBoxLaunchTiles, tiles.size() - t0);
-        if (dtype == MTM_U16) MTM_BOX_LAUNCH(1, true);
-        else if (chans == 1) MTM_BOX_LAUNCH(1, false);
-        else MTM_BOX_LAUNCH(3, false);
+    // (both kernels run over the tile table in launch slices, for_launch_slices)
+    MTMC(for_launch_slices(0, tiles.size(), [&](size_t t0, unsigned nt) -> int {
+        const auto launch_score = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(nt), dim3(256), 0, c->stream, img, lo_b, c->win_tpx.as<uint8_t>(),
+                               c->win_toff.as<long long>(), c->box_td.as<TemplDev>(), c->box_units.as<BoxUnit>(),
+                               c->box_tiles.as<BoxTile>() + t0, c->win_buf.as<float>(), c->method);
+        };
+        if (dtype == MTM_U16) launch_score(boxes_score_kernel<1, true>);
+        else if (chans == 1) launch_score(boxes_score_kernel<1, false>);
+        else launch_score(boxes_score_kernel<3, false>);
         HIPC(hipGetLastError());
-    }
-#undef MTM_BOX_LAUNCH
+        return MTM_OK;
+    }));
 
     std::vector<float> maps1d(global ? 0 : (size_t)n1d_floats);
     const size_t peak_tiles = global ? tiles.size() : n_tiles_2d;
@@ -219,14 +208,14 @@ int boxes_chunk(mtm_ctx* c, const mtm_box_unit* units, const std::vector<BlobTem
     std::vector<mtm_hit> ch;            // this chunk's records, templ_idx = the unit's index in the chunk, unit coordinates
     auto launch = [&](mtm_hit* dhits, unsigned long long cap, unsigned long long* counter, unsigned long long* best,
                       int* nontrivial) -> int {
-        for (size_t t0 = 0; t0 < peak_tiles; t0 += kBoxLaunchTiles) {
-            const unsigned nt = (unsigned)std::min(kBoxLaunchTiles, peak_tiles - t0);
+        MTMC(for_launch_slices(0, peak_tiles, [&](size_t t0, unsigned nt) -> int {
             hipLaunchKernelGGL(boxes_peaks_kernel, dim3(nt), dim3(256), 0, c->stream, c->box_units.as<BoxUnit>(),
                                c->box_tiles.as<BoxTile>() + t0, c->win_buf.as<float>(), c->box_td.as<TemplDev>(),
                                mode_min ? 1 : 0, global ? 1 : 0, mode_min ? -thr : thr, c->opt_border, dhits, cap, counter,
                                best, nontrivial);
             HIPC(hipGetLastError());
-        }
+            return MTM_OK;
+        }));
         if (first && !maps1d.empty())
             HIPC(hipMemcpyAsync(maps1d.data(), c->win_buf.as<float>() + off1d, sizeof(float) * maps1d.size(),
                                 hipMemcpyDeviceToHost, c->stream));

@@ -61,6 +61,17 @@ using namespace mtm;
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The window units (boxes, tracking, blocks) launch one work-group per entry of a table; a launch takes at most this many,
+// so that one dispatch stays far below 2^32 work-items however long the table is.
+constexpr size_t kLaunchGroups = (size_t)1 << 22;
+// launch(first, count) for [begin, end) in slices of at most kLaunchGroups entries, in order; the first status that is
+// not MTM_OK ends the walk and is returned.
+template <class Launch>
+int for_launch_slices(size_t begin, size_t end, Launch&& launch) {
+    for (size_t at = begin; at < end; at += kLaunchGroups) MTMC(launch(at, (unsigned)std::min(kLaunchGroups, end - at)));
+    return MTM_OK;
+}
+
 // mtm_find_matches_batch stacks its images into one tall image.  The rows of one chunk are bounded by the tightest packing a
 // tall map can reach: launches with one grid row per map row (masksq_combine_kernel, slab_combine_kernel, the
 // masked float32 kernels: grid.y = oh) stay within 16 bits.  Looser ones: the candidate key (cand_key, the host's 3x3 table)

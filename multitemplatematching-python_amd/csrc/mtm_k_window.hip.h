@@ -1,10 +1,17 @@
-// Exact window sums of one 16 x 16 tile of score-map outputs, for the kernels that score arbitrary regions of a map
-// (pyr_window_kernel, mtm_pyramid.hip; boxes_score_kernel, mtm_boxes.hip): the template streams through LDS in chunks of
-// kWinKR x kWinKC pixels next to the image rows the tile's windows cover, and v_dot4_u32_u8 forms the correlation and the
-// window sums S1 (per channel) and S2 of the chunk in uint32; they are flushed to uint64 after every chunk, so the
-// template's size is bounded by neither LDS nor the uint32 range.  Thread (ly, lx) = (tid / 16, tid % 16) of a 256-thread
-// work-group owns output (oy0 + ly, ox0 + lx), whose window's top-left pixel is image pixel (oy0 + ly, ox0 + lx).
-// Image pixels outside `rows` x `cols` read as zero: only outputs outside the map read them, and those are never stored.
+// Exact window sums of one 16 x 16 tile of score-map outputs, for the kernels that score arbitrary regions of a map: the
+// template streams through LDS in chunks of kWinKR x kWinKC pixels next to the image rows the tile's windows cover, and
+// v_dot4_u32_u8 forms the correlation and the window sums S1 (per channel) and S2 of the chunk in uint32; they are flushed
+// to uint64 after every chunk, so the template's size is bounded by neither LDS nor the uint32 range.  Thread (ly, lx) =
+// (tid / 16, tid % 16) of a 256-thread work-group owns output (oy0 + ly, ox0 + lx), whose window's top-left pixel is image
+// pixel (oy0 + ly, ox0 + lx).  Image pixels outside `rows` x `cols` read as zero: only outputs outside the map read them,
+// and those are never scored.
+// win_score_tile is the one body of the kernels that score a tile of a unit's map for one template - boxes_score_kernel
+// (mtm_boxes.hip), track_score_kernel and track_reacquire_kernel (mtm_track.hip), blocks_score_kernel and
+// blocks_plane_kernel (mtm_blocks.hip): the sums, the lane's output and whether it lies in the map, and the float32 score
+// (win_score) handed to the kernel's sink, which stores it, merges it into a key (win_merge_key) or adds it to a plane.
+// That these kernels give the same float32 bits rests on this one function.  pyr_window_kernel (mtm_pyramid.hip, uint8
+// only) calls win_tile_sums_u8 and win_score itself inside its tile loop: with win_score_tile as the loop's body its
+// 414 x 400 template case ran 6 % longer on the device (profiles/window_tile/summary.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -310,13 +317,19 @@ __device__ __forceinline__ float win_score(int method, const TemplDev& T, double
         [&]() { return window_norm(sum2, wnd_mean2); }, T, CH);
 }
 
-// The key of this lane's output - order(quality) << 32 | pos, pos = ~(index in the unit's current map), quality score()
-// or its negative for the difference methods; 0 for a lane outside the map, which never calls score() -, reduced per
-// wave and merged into *slot with one atomicMax per wave, as boxes_peaks_kernel keys a unit's extremum in global mode.
-// (The tracking score kernels, mtm_track.hip, and blocks_score_kernel, mtm_blocks.hip.)
+// The position word of output (y, x) of a map ow wide in a quality key: ~(row-major index), so that among equal
+// qualities the first output in row-major order has the largest key.
+__device__ __forceinline__ unsigned long long win_pos_word(int y, int x, int ow) {
+    return 0xFFFFFFFFull - (unsigned long long)((long long)y * ow + x);
+}
+
+// The key of this lane's output - order(quality) << 32 | pos (win_pos_word), quality score() or its negative for the
+// difference methods; 0 for a lane outside the map, which never calls score() -, reduced per wave and merged into *slot
+// with one atomicMax per wave, as boxes_peaks_kernel keys a unit's extremum in global mode.  Every lane of the wave calls
+// it (the shuffles).  (The tracking score kernels, mtm_track.hip, and blocks_score_kernel, mtm_blocks.hip.)
 template <class Score>
-__device__ __forceinline__ void track_merge_key(bool inside, unsigned long long pos, int mode_min, Score&& score,
-                                                unsigned long long* __restrict__ slot) {
+__device__ __forceinline__ void win_merge_key(bool inside, unsigned long long pos, int mode_min, Score&& score,
+                                              unsigned long long* __restrict__ slot) {
     unsigned long long key = 0ull;
     if (inside) {
         const float s = score();
@@ -329,6 +342,33 @@ __device__ __forceinline__ void track_merge_key(bool inside, unsigned long long 
         key = o > key ? o : key;
     }
     if ((threadIdx.x & 63) == 0 && key != 0ull) atomicMax(slot, key);
+}
+
+// One tile of a map scored for one template: the tile's first output is (ty0, tx0) of a map of oh x ow outputs, and the
+// window of that output has its top-left pixel at image pixel (py0, px0).  `img` holds the planes as the sums read them
+// (uint8: plane c at img.u8 + c * img.u8_plane; uint16: img.u8 the high-byte plane, lo_b the low-byte plane XOR 0x80), tp
+// the template's planes (win_tile_sums_*) and T its constants.  The sums run once, every lane through their barriers; then
+// every lane calls sink(inside, y, x, score) exactly once: (y, x) the lane's output, inside = it lies in the map, score() the
+// float32 value of win_score - the exhaustive map's bits.  The sink calls score() only where it needs the value and never
+// for a lane that is not inside (such a lane's windows read pixels as zero).  Called by the whole work-group, outside
+// divergent control flow.
+template <int CH, bool U16, class Sink>
+__device__ __forceinline__ void win_score_tile(WinTemplLds (&Tl)[U16 ? 2 : 1], WinImageLds (&Il)[U16 ? 2 : 1],
+                                               const ImageDev& img, const uint8_t* __restrict__ lo_b,
+                                               const uint8_t* __restrict__ tp, const TemplDev& T, int py0, int px0, int ty0,
+                                               int tx0, int oh, int ow, int method, Sink&& sink) {
+    const int h = T.rows, w = T.cols;
+    const int tid = threadIdx.x;
+    const double inv_area = 1.0 / ((double)h * (double)w);
+    unsigned long long corr, s2, s1[CH];
+    if constexpr (U16)
+        win_tile_sums_u16(Tl[0], Tl[1], Il[0], Il[1], img.u8, lo_b, img.u8_pitch, img.rows, img.cols, tp, h, w, py0, px0, corr,
+                          s1[0], s2);
+    else
+        win_tile_sums_u8<CH>(Tl[0], Il[0], img.u8, img.u8_plane, img.u8_pitch, img.rows, img.cols, tp, h, w, py0, px0, corr, s1,
+                             s2);
+    const int y = ty0 + tid / kWinTile, x = tx0 + tid % kWinTile;
+    sink(y < oh && x < ow, y, x, [&] { return win_score<CH>(method, T, inv_area, corr, s1, s2); });
 }
 
 }  // namespace mtm

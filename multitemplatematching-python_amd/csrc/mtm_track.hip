@@ -1,7 +1,8 @@
 // libmtm_hip.so - templates tracked through a stack of frames in one call (mtm_track_boxes): per frame and
 // track, the extremum of the track template's score map over the track's search box (what mtm_find_matches_boxes returns
-// for that unit in MTM_PEAKS_GLOBAL mode), then the next frame's box from that hit - both on the device, so that the host
-// waits once per call instead of twice per frame.  uint8 (1 or 3 channels) and single-channel uint16, unmasked templates
+// for that unit in MTM_PEAKS_GLOBAL mode: the scores are win_score_tile's, mtm_k_window.hip.h, the function that kernel
+// calls), then the next frame's box from that hit - both on the device, so that the host waits once per call instead of
+// twice per frame.  uint8 (1 or 3 channels) and single-channel uint16, unmasked templates
 // of one mtm_set_templates call.  The five entry points are one host function, track_boxes: plan_tracks (mtm_host.cpp)
 // checks the tracks and lays out the unit and tile tables, stage_tables puts them on the device, track_frame enqueues a
 // frame's kernels, finish_track_call reads the results back behind the call's only wait.
@@ -45,12 +46,10 @@ struct TrackLostState {
     uint8_t* flags;
 };
 constexpr unsigned kTrackReacquireGrid = 2048;            // work-groups of a track_reacquire_kernel launch: 8 per CU
-constexpr size_t kTrackLaunchTiles = (size_t)1 << 22;     // most work-groups (tiles) of one track_score_kernel launch
-constexpr size_t kTrackLaunchNbhd = (size_t)1 << 22;      // most work-groups (tracks) of one track_nbhd_kernel launch
 
-// The tile (ty0, tx0) of unit U's map: the windows are summed and scored exactly as boxes_score_kernel does
-// (win_tile_sums_u8 / win_tile_sums_u16, win_score: the same float32 bits), and instead of a map the tile's best output
-// goes into *slot (track_merge_key).  A whole-frame unit has y0 = x0 = 0.
+// The tile (ty0, tx0) of unit U's map in the frame at rows row_off .. of the stack: win_score_tile's sums and float32
+// scores - boxes_score_kernel's bits, the same function -, and instead of a map the tile's best output goes into *slot
+// (win_merge_key).  A whole-frame unit has y0 = x0 = 0.
 template <int CH, bool U16>
 __device__ __forceinline__ void track_score_tile(WinTemplLds (&Tl)[U16 ? 2 : 1], WinImageLds (&Il)[U16 ? 2 : 1],
                                                  const ImageDev& img, const uint8_t* __restrict__ lo_b,
@@ -59,20 +58,10 @@ __device__ __forceinline__ void track_score_tile(WinTemplLds (&Tl)[U16 ? 2 : 1],
                                                  int row_off, int method, int mode_min,
                                                  unsigned long long* __restrict__ slot) {
     const TemplDev T = td[U.t];
-    const int h = T.rows, w = T.cols;
-    const uint8_t* tp = tpx + toff[U.t];
-    const int tid = threadIdx.x;
-    const double inv_area = 1.0 / ((double)h * (double)w);
-    unsigned long long corr, s2, s1[CH];
-    if constexpr (U16)
-        win_tile_sums_u16(Tl[0], Tl[1], Il[0], Il[1], img.u8, lo_b, img.u8_pitch, img.rows, img.cols, tp, h, w,
-                          row_off + U.y0 + ty0, U.x0 + tx0, corr, s1[0], s2);
-    else
-        win_tile_sums_u8<CH>(Tl[0], Il[0], img.u8, img.u8_plane, img.u8_pitch, img.rows, img.cols, tp, h, w,
-                             row_off + U.y0 + ty0, U.x0 + tx0, corr, s1, s2);
-    const int y = ty0 + tid / kWinTile, x = tx0 + tid % kWinTile;
-    track_merge_key(y < U.oh && x < U.ow, 0xFFFFFFFFull - (unsigned long long)((long long)y * U.ow + x), mode_min,
-                    [&] { return win_score<CH>(method, T, inv_area, corr, s1, s2); }, slot);
+    win_score_tile<CH, U16>(Tl, Il, img, lo_b, tpx + toff[U.t], T, row_off + U.y0 + ty0, U.x0 + tx0, ty0, tx0, U.oh, U.ow,
+                            method, [&](bool inside, int y, int x, auto&& score) {
+                                win_merge_key(inside, win_pos_word(y, x, U.ow), mode_min, score, slot);
+                            });
 }
 
 // Grid: one work-group per tile of the call's tile table (plain tracks: u0 = the track, nv = 1): the tile's best output
@@ -386,13 +375,13 @@ __device__ __forceinline__ void track_set_tile(WinTemplLds (&Th)[kTrackNV], WinT
                                            row_off + U.y0 + ty0, U.x0 + tx0, corr, s1, s2);
     const int y = ty0 + tid / kWinTile, x = tx0 + tid % kWinTile;
     const bool inside = y < U.oh && x < U.ow;
-    const unsigned long long pos = 0xFFFFFFFFull - (unsigned long long)((long long)y * U.ow + x);
+    const unsigned long long pos = win_pos_word(y, x, U.ow);
 #pragma unroll
     for (int n = 0; n < kTrackNV; ++n) {
         if (n >= nv) break;             // (the same for the whole work-group)
         const TemplDev& Tn = td[t[n]];
         const unsigned long long cn = corr[n];          // (a scalar: capturing the array costs 8 VGPRs)
-        track_merge_key(inside, pos, mode_min, [&] { return win_score<CH>(method, Tn, inv_area, cn, s1, s2); }, gkeys + n);
+        win_merge_key(inside, pos, mode_min, [&] { return win_score<CH>(method, Tn, inv_area, cn, s1, s2); }, gkeys + n);
     }
 }
 
@@ -669,12 +658,12 @@ int track_frame(mtm_ctx* c, const TrackArgs& A, const TrackPlan& P, const TrackT
         constexpr int CH = decltype(ch)::value;
         constexpr bool U16 = decltype(u16)::value;
         const auto score = A.sets ? track_score_sets_kernel<CH, U16> : track_score_kernel<CH, U16>;
-        for (size_t t0 = 0; t0 < P.tiles.size(); t0 += kTrackLaunchTiles) {
-            const unsigned nt = (unsigned)std::min(kTrackLaunchTiles, P.tiles.size() - t0);
+        MTMC(for_launch_slices(0, P.tiles.size(), [&](size_t t0, unsigned nt) -> int {
             hipLaunchKernelGGL(score, dim3(nt), dim3(256), 0, c->stream, img, lo_b, T.tpx, T.toff, T.td, T.units,
                                T.tiles + t0, row_off, c->method, mode_min, T.keys);
             HIPC(hipGetLastError());
-        }
+            return MTM_OK;
+        }));
         const auto update = A.reacq ? track_update_kernel<true> : track_update_kernel<false>;
         hipLaunchKernelGGL(update, dim3(ublocks), dim3(256), 0, c->stream, T.units, T.set_off, T.td, T.keys, n, mode_min,
                            A.margin, A.use_min ? 1 : 0, A.min_score, A.rows, A.cols, T.out + r0, T.passed, T.lost);
@@ -695,19 +684,22 @@ int track_frame(mtm_ctx* c, const TrackArgs& A, const TrackPlan& P, const TrackT
             HIPC(hipGetLastError());
         }
         // the frame's neighbourhoods, from its records (a set's winner names its template there) and its rows of the stack
-        for (size_t k0 = 0; T.nbhd && k0 < (size_t)n; k0 += kTrackLaunchNbhd) {
-            const unsigned nk = (unsigned)std::min(kTrackLaunchNbhd, (size_t)n - k0);
-            hipLaunchKernelGGL((track_nbhd_kernel<CH, U16>), dim3(nk), dim3(256), 0, c->stream, img, lo_b, T.tpx, T.toff, T.td,
-                               T.out + r0 + k0, row_off, A.rows, c->method, T.nbhd + 9 * (r0 + k0));
-            HIPC(hipGetLastError());
-        }
+        if (T.nbhd)
+            MTMC(for_launch_slices(0, (size_t)n, [&](size_t k0, unsigned nk) -> int {
+                hipLaunchKernelGGL((track_nbhd_kernel<CH, U16>), dim3(nk), dim3(256), 0, c->stream, img, lo_b, T.tpx, T.toff,
+                                   T.td, T.out + r0 + k0, row_off, A.rows, c->method, T.nbhd + 9 * (r0 + k0));
+                HIPC(hipGetLastError());
+                return MTM_OK;
+            }));
         // the passing tracks adopt their hits' windows: the templates of the next frame's search
-        for (size_t k0 = 0; A.blend_a > 0 && k0 < (size_t)n; k0 += kTrackLaunchNbhd) {
-            const unsigned nk = (unsigned)std::min(kTrackLaunchNbhd, (size_t)n - k0);
-            hipLaunchKernelGGL((track_adopt_kernel<CH, U16>), dim3(nk), dim3(256), 0, c->stream, img, lo_b, T.tpx, T.toff + k0,
-                               T.td + k0, T.out + r0 + k0, T.passed + k0, row_off, A.rows, c->method, A.blend_a);
-            HIPC(hipGetLastError());
-        }
+        if (A.blend_a > 0)
+            MTMC(for_launch_slices(0, (size_t)n, [&](size_t k0, unsigned nk) -> int {
+                hipLaunchKernelGGL((track_adopt_kernel<CH, U16>), dim3(nk), dim3(256), 0, c->stream, img, lo_b, T.tpx,
+                                   T.toff + k0, T.td + k0, T.out + r0 + k0, T.passed + k0, row_off, A.rows, c->method,
+                                   A.blend_a);
+                HIPC(hipGetLastError());
+                return MTM_OK;
+            }));
         return MTM_OK;
     });
 }

@@ -1,5 +1,6 @@
 """MTM.matchBlocksStack on the GPU.  Per pair every case equals the loop of MTM.matchBlocks over the pairs (itself pinned
-against findMatchesInBoxes and the oracle by test_gpu_blocks.py) in positions (``==``) and float32 score bits; the ensemble
+against findMatchesInBoxes and the oracle by test_gpu_blocks.py) in positions (``==``) and float32 score bits, and - the two
+calls share their chain of launches - one test pins the stack call itself against the findMatchesInBoxes loop; the ensemble
 planes equal, bit for bit, a restatement from MTM.computeScoreMap of host-cut blocks on host-cut search-box crops
 (tests/blocks_stack_model.py), and their peaks the restated peak rule; frame and block chunking change no byte."""
 import warnings
@@ -11,6 +12,7 @@ import MTM
 import blocks_stack_model as M
 from MTM import _lib
 from MTM import blocks as B
+from test_gpu_blocks import _loop as _boxes_loop
 
 pytestmark = pytest.mark.gpu
 
@@ -99,6 +101,39 @@ def test_pairs_equal_the_loop(kind, method, reference, refine):
         got = _call(frames, _EDGE_BLOCKS, margin, method, reference=reference, refine=refine)
         assert got[0].shape == (3, len(_EDGE_BLOCKS), 2) and got[0].dtype == (np.float64 if refine else np.int64)
         _same(got, _loop(frames, _EDGE_BLOCKS, margin, method, reference, refine))
+
+
+# ---- per pair: the loop of findMatchesInBoxes on host-cut templates, another kernel family and host path -------------------
+# 3 frames of 48 x 96; margin 9: an interior block's 19 x 19 map has four tiles, three of them partial
+_ANCHOR_HW, _ANCHOR_MARGIN = (48, 96), 9
+_ANCHOR_BLOCKS = [(10, 20, 70, 5),      # 5 x 70: crosses the 64-column template chunk
+                  (50, 12, 4, 17),      # 17 x 4: crosses the 16-row template chunk
+                  (90, 44, 6, 4),       # the bottom right corner: its box is clipped on two sides
+                  (40, 30, 1, 1)]       # (x, y, w, h)
+
+
+@pytest.mark.parametrize("method", [1, 5])
+@pytest.mark.parametrize("refine", [False, True])
+@pytest.mark.parametrize("reference", ["previous", "first"])
+@pytest.mark.parametrize("kind", ["u8", "rgb", "u16"])
+def test_pairs_equal_the_boxes_loop(kind, reference, refine, method):
+    """matchBlocksStack against findMatchesInBoxes (and refineHits) per pair, bit for bit: test_pairs_equal_the_loop
+    compares two calls that run one chain of launches, this one does not.  Once with every block in one chunk ("first"
+    gathers once), once with a chunk per block."""
+    frames = _movie(390 + method, 3, kind, hw=_ANCHOR_HW)
+    blocks, margin, n = _ANCHOR_BLOCKS, _ANCHOR_MARGIN, len(_ANCHOR_BLOCKS)
+    chans, dtype = (3 if kind == "rgb" else 1), frames[0].dtype
+    budget = 4 * int(_lib.default_context().get_option(_lib.OPT_BOXES_MAX_FLOATS))
+    tiles, chunk_of, _, maps = _lib.debug_plan_blocks(_ANCHOR_HW, chans, dtype, blocks, margin, budget)
+    assert (chunk_of == 0).all() and maps[0].tolist() == [1, 11, 19, 19] and maps[2, 2:].tolist() == [10, 10]
+    assert tiles[tiles[:, 0] == 0, 1:].tolist() == [[0, 0], [0, 16], [16, 0], [16, 16]]
+    assert (_lib.debug_plan_blocks(_ANCHOR_HW, chans, dtype, blocks, margin, 4)[1] == np.arange(n)).all()
+    mode = M.FIRST if reference == "first" else M.PREVIOUS
+    per_pair = [_boxes_loop(frames[r], frames[s], blocks, margin, method, refine) for r, s in M.pair_frames(3, mode)]
+    exp = np.stack([fine if refine else pos for pos, _, fine in per_pair]), np.stack([sc for _, sc, _ in per_pair])
+    _same(_call(frames, blocks, margin, method, reference=reference, refine=refine), exp)
+    with _Opt(_lib.OPT_BOXES_MAX_FLOATS, 1):            # 4 bytes of templates: every block is a chunk of its own
+        _same(_call(frames, blocks, margin, method, reference=reference, refine=refine), exp)
 
 
 @pytest.mark.parametrize("kind", ["u8", "rgb", "u16"])

@@ -248,7 +248,7 @@ int         mtm_debug_class_tilings(mtm_ctx* ctx, int32_t* out, int cap_classes)
  * suppression of mtm_find_matches_image_nms - the counting sort by grid cell, the champion pass, the prune pass - on a hit
  * list the caller hands over: the n records of `hits` and the count n go to device memory, the grid is the one a
  * rows x cols image with boxes of at most max_side a side gets (cell = max(32, max_side), cols / cell + 3 by rows / cell + 3
- * cells), and the very chain the search call queues behind its peak pass runs on them: n_min plays the part of the
+ * cells), and the very chain the search call queues behind its peak pass (queue_nms_chain, csrc/mtm_peaks.hip) runs on them: n_min plays the part of the
  * context's device-NMS minimum, n_max that of min(hit capacity, 2^18) - it sizes the work buffers and the launches (1 ..
  * 2^18).  score_threshold, ascending and max_overlap (>= 0) are those of mtm_nms.  out = the champions (hits no earlier hit
  * overlaps beyond max_overlap: kept for certain), then the undecided hits (neither champions nor overlapped by one), in no
@@ -263,8 +263,9 @@ int         mtm_debug_device_nms(mtm_ctx* ctx, const mtm_hit* hits, int64_t n, i
  * options as they are).  The peak pass of the search calls on score maps the caller hands over: the n_maps maps (dims: oh, ow
  * and the template's h, w per map - the last two only fill the records -, maps: their oh * ow float32 values, tightly packed,
  * map after map) go to a map arena laid out as placement lays it out (pitch = ow rounded up to 4, map after map) that was
- * filled with pattern_byte first - the pitch padding and, under `holes`, whatever the caller leaves out -, and the very
- * kernels of `route` run on them with the grids and capacities the search call derives (csrc/mtm_peak_sizing.h):
+ * filled with pattern_byte first - the pitch padding and, under `holes`, whatever the caller leaves out -, and the
+ * kernels of `route` run on them through the launchers the search calls go through (csrc/mtm_peaks.hip: one launch site per
+ * kernel, grids and capacities from csrc/mtm_peak_sizing.h):
  *   MTM_PEAK_SCAN            peaks_kernel
  *   MTM_PEAK_SCAN_BATCH      peaks_batch_kernel: every map is that of a stack of (oh + h - 1) / img_rows images of img_rows
  *                            rows (the same number for every map, img_rows - h >= 1)

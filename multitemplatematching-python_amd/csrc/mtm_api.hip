@@ -1,11 +1,10 @@
-// libmtm_hip.so - the search entry points: mtm_find_matches and its variants (score pass, peak extraction or
-// verification of the kernels' candidates, float32 refinement routes, hit lists), score maps, timing.
+// libmtm_hip.so - the search entry points: mtm_find_matches and its variants (the route of a call, its score pass, the
+// fallback ladder around the peak pass of mtm_peaks.hip, host verification of the kernels' candidates, hit lists), score
+// maps, timing.  Launches no kernel itself.
 #include "mtm_ctx.h"
 
 using namespace mtm;
 using namespace mtmi;
-#include "mtm_k_peaks.hip.h"
-#include "mtm_k_nms.hip.h"
 
 namespace {
 
@@ -39,8 +38,6 @@ int stage_next_image(mtm_ctx* c, NextImage* nx) {
 
 int find_matches_impl(mtm_ctx* c, int mode, double score_threshold, mtm_hit* out, int64_t capacity,
                       int64_t* n_out, NextImage* next, const ImageArgs* up = nullptr, const NmsRequest* nms = nullptr);
-
-constexpr size_t kHitPrefetch = 1024;       // candidate / hit records fetched together with the counters
 
 // The route of a call on the placed templates and the current image (`banded`: it arrives in row bands), decided from the
 // context's switches and back-off counters.  No HIP call, no change to the context: fm_begin acts on what it returns.
@@ -290,108 +287,9 @@ int fm_begin(mtm_ctx* c, int mode, double score_threshold, NextImage* next, Call
     if (R.prefetched) {
         // Few candidates (the usual case): they are in the pinned landing buffer when the stream is done and the 3x3 test
         // runs on the host (fm_end) - written there by the score kernel itself (pin_direct), else by a one-group kernel
-        if (!R.pin_direct) {
-            hipLaunchKernelGGL(fetch_cands_kernel, dim3(1), dim3(256), 0, c->stream, c->cands.as<uint4>(),
-                               static_cast<uint4*>(c->pinned), (unsigned long long)R.cand_pin_n);
-            HIPC(hipGetLastError());
-        }
+        if (!R.pin_direct) MTMC(queue_cand_fetch(c->stream, c->cands.p, c->pinned, R.cand_pin_n));
         HIPC(hipEventRecord(c->ev[2], c->stream));
     }
-    return MTM_OK;
-}
-
-// The device's share of the non-maxima suppression (mtm_k_nms.hip.h), queued right behind the peak pass: the length of the
-// peak list at `dhits` is still on the device (`dcount`), the launches read it there and do nothing unless it lies in
-// [nms_device_min, n_max].  What a neighbourhood's best hit suppresses stays on the device; fetch_device_nms() brings the
-// rest: first the hits that are certainly kept (nothing earlier overlaps them), then the undecided ones.
-struct DeviceNms {
-    bool queued = false;
-    unsigned n_max = 0;
-    const unsigned long long* cnt_pin = nullptr;   // landing buffer of the two counters (champions, undecided), page-locked
-    const mtm_hit* out = nullptr;
-};
-
-// Lays out nms_buf and queues the chain - two memsets, the five launches, the copy of the two counters - for the list of
-// *dcount records at `dhits` (both on the device); reads nothing else of the call from the context.  n_max sizes the buffers
-// and the launches; a count outside [n_min, n_max] makes every kernel return at once.
-int queue_nms_chain(mtm_ctx* c, const mtm_hit* dhits, const unsigned long long* dcount, unsigned n_min, size_t n_max, bool ascending,
-                    float thr_score, float thr_overlap, const NmsGrid& g, DeviceNms* q) {
-    NmsParams p{};
-    p.hits = dhits;
-    p.n_ptr = dcount;
-    p.n_min = n_min;
-    p.n_max = (unsigned)n_max;
-    p.ascending = ascending ? 1 : 0;
-    p.thr_score = thr_score;
-    p.thr_overlap = thr_overlap;
-    p.cell = g.cell;
-    p.gw = g.gw;
-    p.gh = g.gh;
-    const size_t n_cells = (size_t)p.gw * p.gh;
-    const size_t off_rank = round_up(sizeof(unsigned) * (n_cells + 1), 256), off_status = off_rank + round_up(sizeof(unsigned) * n_max, 256);
-    const size_t off_sorted = off_status + round_up(sizeof(int) * n_max, 256);
-    const size_t off_hdr = off_sorted + round_up(sizeof(mtm_hit) * n_max, 256), off_out = off_hdr + 256;
-    MTMC(c->nms_buf.ensure(off_out + sizeof(mtm_hit) * n_max));
-    uint8_t* b = c->nms_buf.as<uint8_t>();
-    p.cell_cnt = reinterpret_cast<unsigned*>(b);
-    p.rank = reinterpret_cast<unsigned*>(b + off_rank);
-    p.status = reinterpret_cast<int*>(b + off_status);
-    p.sorted = reinterpret_cast<mtm_hit*>(b + off_sorted);
-    p.out_count = reinterpret_cast<unsigned long long*>(b + off_hdr);
-    p.out = reinterpret_cast<mtm_hit*>(b + off_out);
-    HIPC(hipMemsetAsync(p.cell_cnt, 0, sizeof(unsigned) * (n_cells + 1), c->stream));
-    HIPC(hipMemsetAsync(b + off_hdr, 0, 16, c->stream));
-    const unsigned blocks = (unsigned)((n_max + 255) / 256);
-    hipLaunchKernelGGL(nms_count_kernel, dim3(blocks), dim3(256), 0, c->stream, p);
-    hipLaunchKernelGGL(nms_offsets_kernel, dim3(1), dim3(1024), 0, c->stream, p);
-    hipLaunchKernelGGL(nms_scatter_kernel, dim3(blocks), dim3(256), 0, c->stream, p);
-    hipLaunchKernelGGL(nms_champion_kernel, dim3(blocks), dim3(256), 0, c->stream, p);
-    hipLaunchKernelGGL(nms_prune_kernel, dim3(blocks), dim3(256), 0, c->stream, p);
-    HIPC(hipGetLastError());
-    // (into page-locked memory: a device-to-host copy into a pageable stack slot may hold the host until the whole peak pass
-    // is done - the round trip this queueing exists to avoid)
-    if (!c->pin_small) HIPC(hipHostMalloc(&c->pin_small, 64, hipHostMallocDefault));
-    q->cnt_pin = static_cast<unsigned long long*>(c->pin_small);
-    HIPC(hipMemcpyAsync(c->pin_small, b + off_hdr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    q->queued = true;
-    q->n_max = (unsigned)n_max;
-    q->out = p.out;
-    return MTM_OK;
-}
-
-// the production call: the grid of the context's image and templates (mtm_nms_core.h: nms_grid), lists of nms_device_min ..
-// min(hit capacity, 2^18) peaks
-int queue_device_nms(mtm_ctx* c, const NmsRequest& req, const mtm_hit* dhits, const unsigned long long* dcount, bool ascending, DeviceNms* q) {
-    int max_side = 0;
-    for (const TemplDev& d : c->td_host) max_side = std::max(max_side, std::max(d.rows, d.cols));
-    const size_t n_max = (size_t)std::min<int64_t>(c->hit_cap, 1ll << 18);
-    // MTM/NMS.py:73-78: the scores are float32 (1 - score for the difference methods), the threshold a python float
-    // transformed in double and narrowed by the cv2 binding
-    const float thr_score = (float)(ascending ? (1.0 - req.score_threshold) : req.score_threshold);
-    return queue_nms_chain(c, dhits, dcount, (unsigned)std::min<long long>(c->nms_device_min, 1ll << 30), n_max, ascending, thr_score,
-                           (float)req.max_overlap, nms_grid(c->rows, c->cols, max_side), q);
-}
-
-// after the stream was synchronised (q.cnt has landed): the pruned list of `count` peaks -> `rest`, *n_sure = champions
-int fetch_device_nms(mtm_ctx* c, const DeviceNms& qd, unsigned long long count, std::vector<mtm_hit>& rest, long long* n_sure) {
-    struct {
-        unsigned long long cnt[2];
-        const mtm_hit* out;
-    } q{{qd.cnt_pin ? qd.cnt_pin[0] : 0ull, qd.cnt_pin ? qd.cnt_pin[1] : 0ull}, qd.out};
-    if (q.cnt[0] + q.cnt[1] > count) {
-        set_error("mtm_find_matches_image_nms: internal state (pruned list longer than the peak list)");
-        return MTM_E_STATE;
-    }
-    if (c->host_trace && c->trace_calls <= 12)
-        std::fprintf(stderr, "[mtm host trace] device NMS: %llu peaks -> %llu champions + %llu for the host's pass\n", count,
-                     q.cnt[0], q.cnt[1]);
-    rest.resize((size_t)(q.cnt[0] + q.cnt[1]));
-    if (q.cnt[0]) HIPC(hipMemcpyAsync(rest.data(), q.out, sizeof(mtm_hit) * (size_t)q.cnt[0], hipMemcpyDeviceToHost, c->stream));
-    if (q.cnt[1])
-        HIPC(hipMemcpyAsync(rest.data() + q.cnt[0], q.out + (count - q.cnt[1]), sizeof(mtm_hit) * (size_t)q.cnt[1],
-                            hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    *n_sure = (long long)q.cnt[0];
     return MTM_OK;
 }
 
@@ -464,11 +362,6 @@ int leave_segments(mtm_ctx* c, CallRoute& R) {
     return maps_complete ? MTM_OK : rescore(c, R);
 }
 
-int ladder_exhausted() {
-    set_error("mtm_find_matches: internal state (the overflow fallbacks ran out of passes)");
-    return MTM_E_STATE;
-}
-
 // the step ladder_next named: its transition above, or - the pass found `count` peaks, more than the hit list holds - a list
 // with room for them
 int take_step(mtm_ctx* c, CallRoute& R, LadderStep step, unsigned long long count) {
@@ -498,16 +391,7 @@ int collect_global_extremum(mtm_ctx* c, CallRoute& R, std::vector<mtm_hit>& hits
     std::vector<unsigned long long> best(2 * (size_t)std::max(1, n));
     bool done = false;
     for (int pass = 0; pass < 3 && !done; ++pass) {
-        if (!R.ext) {
-            MTMC(c->counters.ensure(key_bytes));
-            HIPC(hipMemsetAsync(c->counters.p, 0, key_bytes, c->stream));
-        }
-        if (n > 0 && !R.ext) {
-            const int nb = extremum_blocks();
-            hipLaunchKernelGGL(extremum_kernel, dim3(nb, n), dim3(256), 0, c->stream, c->maps.as<float>(),
-                               c->td.as<TemplDev>(), nb, c->counters.as<unsigned long long>());
-            HIPC(hipGetLastError());
-        }
+        MTMC(queue_extremum_pass(c, R));
         HIPC(hipEventRecord(c->ev[2], c->stream));
         HIPC(hipMemcpyAsync(best.data(), c->counters.p, key_bytes, hipMemcpyDeviceToHost, c->stream));
         // refined: the outputs within the margin of their template's best are listed - more than the list holds?
@@ -563,140 +447,6 @@ int verify_on_host(mtm_ctx* c, CallRoute& R, std::vector<mtm_hit>& hits, int* tf
                           c->vh_keys, c->vh_vals, hits, tflags);
     *verified = true;
     if (R.refine && R.bf16_np == 1) c->np1_backoff_len = 16;
-    return MTM_OK;
-}
-
-// The hit buffer of a peak pass (mtm_ctx::hits), as the kernels read it: [hit count | candidate count | spare word of the
-// candidate header (float32 map mode: the "bound too wide" flag) | one int per template] [records].  The header and the
-// first kHitPrefetch records come back in ONE copy.
-struct HitBuffer {
-    size_t hdr_bytes;
-    uint8_t* base = nullptr;        // on the device
-    explicit HitBuffer(int n) : hdr_bytes(round_up(3 * sizeof(unsigned long long) + sizeof(int) * (size_t)std::max(1, n), 16)) {}
-    unsigned long long* count() const { return reinterpret_cast<unsigned long long*>(base); }
-    unsigned long long* cand_header() const { return count() + 1; }        // two words, as the candidate buffer starts
-    int* flags() const { return reinterpret_cast<int*>(count() + 3); }
-    mtm_hit* records() const { return reinterpret_cast<mtm_hit*>(base + hdr_bytes); }
-    // a host copy of the header
-    struct Header {
-        unsigned long long count, ncand;
-        unsigned rig_wide;
-    };
-    Header decode(const uint8_t* host, int n, int* tflags) const {
-        Header h{};
-        std::memcpy(&h.count, host, sizeof(h.count));
-        std::memcpy(&h.ncand, host + sizeof(h.count), sizeof(h.ncand));
-        std::memcpy(&h.rig_wide, host + 2 * sizeof(h.count), sizeof(h.rig_wide));
-        std::memcpy(tflags, host + 3 * sizeof(h.count), sizeof(int) * (size_t)n);
-        return h;
-    }
-    const uint8_t* host_records(const uint8_t* host) const { return host + hdr_bytes; }
-};
-
-// grid of the peak scans: strips of 4 * strip_rows rows x kPkCols columns over the largest 2-D map, one layer per map
-dim3 peak_grid(const mtm_ctx* c, int strip_rows) {
-    int max_oh = 0, max_ow = 0;
-    for (int t : c->list2d) {
-        max_oh = std::max(max_oh, c->td_host[t].oh);
-        max_ow = std::max(max_ow, c->td_host[t].ow);
-    }
-    const PeakGrid g = peak_grid_dims(max_oh, max_ow, (int)c->list2d.size(), strip_rows);
-    return dim3(g.x, g.y, g.z);
-}
-
-// One attempt of the device's peak pass, queued: the candidate list verified (against the hash table of its positions, or
-// the maps), else the maps scanned (the flagged segments, with compaction and the device's share of a suppression request,
-// or everything).
-int queue_peak_pass(mtm_ctx* c, const CallRoute& R, HitBuffer& hb, DeviceNms* dnms) {
-    *dnms = DeviceNms{};
-    const bool mode_min = R.mode_min;
-    const float thr_q = mode_min ? -R.thr : R.thr;      // a hit's quality (score, or -score for minima) exceeds this
-    const unsigned long long hit_cap = (unsigned long long)c->hit_cap;
-    MTMC(c->hits.ensure(hb.hdr_bytes + sizeof(mtm_hit) * (size_t)c->hit_cap));
-    hb.base = c->hits.as<uint8_t>();
-    HIPC(hipMemsetAsync(hb.base, 0, hb.hdr_bytes, c->stream));
-    if (R.fused) {
-        // the candidate count (for the overflow check on the host) and the spare word
-        HIPC(hipMemcpyAsync(hb.cand_header(), c->cands.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
-        const unsigned blocks = verify_blocks(c->hit_cap);
-        const mtm_hit* dcands = reinterpret_cast<const mtm_hit*>(c->cands.as<uint8_t>() + 16);
-        if (R.hits_only) {
-            unsigned long long* keys = c->chash.as<unsigned long long>();
-            int* vals = reinterpret_cast<int*>(keys + (size_t)R.hash_mask + 1);
-            hipLaunchKernelGGL(cand_hash_insert_kernel, dim3(blocks), dim3(256), 0, c->stream, dcands,
-                               c->cands.as<unsigned long long>(), (unsigned long long)R.cand_cap, keys, vals, R.hash_mask);
-            hipLaunchKernelGGL(verify_hash_kernel, dim3(blocks), dim3(256), 0, c->stream, c->td.as<TemplDev>(),
-                               mode_min ? 1 : 0, c->opt_border, dcands, c->cands.as<unsigned long long>(),
-                               (unsigned long long)R.cand_cap, keys, vals, R.hash_mask, hb.records(), hit_cap, hb.count(),
-                               hb.flags(), thr_q);
-        } else {
-            hipLaunchKernelGGL(verify_peaks_kernel, dim3(blocks), dim3(256), 0, c->stream, c->maps.as<float>(),
-                               c->td.as<TemplDev>(), mode_min ? 1 : 0, c->opt_border, dcands, c->cands.as<unsigned long long>(),
-                               (unsigned long long)R.cand_cap, hb.records(), hit_cap, hb.count(), hb.flags(), thr_q);
-        }
-    } else if (R.sparse) {
-        const dim3 grd = peak_grid(c, kPkSparseRows);
-        // a list per (template, strip column) (at most 64 MB of them) + their counters, then one list for the host
-        const unsigned long long n_lists = (unsigned long long)grd.z * grd.x;
-        const unsigned long long cap_t = peak_list_cap(hit_cap, n_lists);
-        const size_t cnt_bytes = round_up(sizeof(unsigned long long) * (size_t)n_lists, 256);
-        MTMC(c->hits_t.ensure(cnt_bytes + sizeof(mtm_hit) * (size_t)cap_t * (size_t)n_lists));
-        unsigned long long* counts_t = c->hits_t.as<unsigned long long>();
-        mtm_hit* hits_t = reinterpret_cast<mtm_hit*>(c->hits_t.as<uint8_t>() + cnt_bytes);
-        HIPC(hipMemsetAsync(counts_t, 0, cnt_bytes, c->stream));
-        hipLaunchKernelGGL(peaks_sparse_kernel, grd, dim3(256), 0, c->stream, c->maps.as<float>(), c->td.as<TemplDev>(),
-                           c->tlist.as<int>() + c->list2d_off, mode_min ? 1 : 0, R.thr, c->opt_border, hits_t, cap_t, counts_t,
-                           hb.flags(), c->seg_flags.as<uint8_t>(), R.flag_tstride, R.flag_rstride, R.seg_skip_used ? 1 : 0);
-        hipLaunchKernelGGL(compact_hits_kernel, dim3((unsigned)n_lists), dim3(256), 0, c->stream, hits_t, cap_t, counts_t,
-                           (int)n_lists, hb.records(), hit_cap, hb.count());
-        // a suppression request: its device share follows at once (it reads the list's length on the device)
-        if (R.nms.on && R.nms.max_overlap >= 0.0) MTMC(queue_device_nms(c, R.nms, hb.records(), hb.count(), mode_min, dnms));
-    } else {
-        hipLaunchKernelGGL(peaks_kernel, peak_grid(c, kPkRows), dim3(256), 0, c->stream, c->maps.as<float>(),
-                           c->td.as<TemplDev>(), c->tlist.as<int>() + c->list2d_off, mode_min ? 1 : 0, R.thr, c->opt_border,
-                           hb.records(), hit_cap, hb.count(), hb.flags());
-    }
-    HIPC(hipGetLastError());
-    return MTM_OK;
-}
-
-// The one copy behind a peak pass - header + first kHitPrefetch records into host_buf - and what it says: the number of
-// peaks, the per-template ints, what overflowed.
-int fetch_pass_outcome(mtm_ctx* c, const CallRoute& R, const HitBuffer& hb, std::vector<uint8_t>& host_buf, int* tflags,
-                       unsigned long long* count, PassOutcome* o) {
-    HIPC(hipEventRecord(c->ev[2], c->stream));
-    host_buf.resize(hb.hdr_bytes + sizeof(mtm_hit) * std::min<size_t>(kHitPrefetch, (size_t)c->hit_cap));
-    HIPC(hipMemcpyAsync(host_buf.data(), hb.base, host_buf.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    const HitBuffer::Header h = hb.decode(host_buf.data(), R.n, tflags);
-    *count = h.count;
-    o->rig_wide = R.fused && h.rig_wide != 0;
-    o->cands_overflow = R.fused && (int64_t)h.ncand > R.cand_cap;
-    o->hits_overflow = (int64_t)h.count > c->hit_cap;
-    return MTM_OK;
-}
-
-// The `count` peaks of a pass whose lists held everything: from host_buf and, beyond the prefetched ones, the device.
-// Thousands of peaks and a suppression request: decided on the device, only the kept ones are fetched.
-int fetch_peak_list(mtm_ctx* c, CallRoute& R, const HitBuffer& hb, const std::vector<uint8_t>& host_buf, unsigned long long count,
-                    const int* tflags, const DeviceNms& dnms, std::vector<mtm_hit>& hits) {
-    if (dnms.queued && R.sparse && !R.fused && (long long)count >= c->nms_device_min && count <= dnms.n_max) {
-        bool trivial = false;       // (a map every pixel of which equals its local maximum loses its peaks: drop_trivial_maps)
-        for (int t : c->list2d) trivial = trivial || scan_flags_trivial((unsigned)tflags[(size_t)t]);
-        if (!trivial) {
-            MTMC(fetch_device_nms(c, dnms, count, hits, &R.nms_sure));
-            R.nms_raw_count = (long long)count;
-            return MTM_OK;
-        }
-    }
-    hits.resize((size_t)count);
-    const size_t got = std::min<size_t>((size_t)count, (host_buf.size() - hb.hdr_bytes) / sizeof(mtm_hit));
-    if (got) std::memcpy(hits.data(), hb.host_records(host_buf.data()), sizeof(mtm_hit) * got);
-    if (count > got) {
-        HIPC(hipMemcpyAsync(hits.data() + got, hb.records() + got, sizeof(mtm_hit) * ((size_t)count - got),
-                            hipMemcpyDeviceToHost, c->stream));
-        HIPC(hipStreamSynchronize(c->stream));
-    }
     return MTM_OK;
 }
 
@@ -875,75 +625,9 @@ int batch_chunk(mtm_ctx* c, const void* const* px, int nb, int rows, int cols, i
     HIPC(hipEventRecord(c->ev[0], c->stream));
     MTMC(run_score_all(c, R));
     HIPC(hipEventRecord(c->ev[1], c->stream));
-    const float* maps = c->maps.as<float>();
-    if (mode == MTM_PEAKS_GLOBAL) {
-        std::vector<unsigned long long> best(2 * (size_t)nb * std::max(1, n), 0ull);
-        long long max_px = 1;
-        for (const TemplDev& d : c->td_host) max_px = std::max(max_px, (long long)(rows - d.rows + 1) * d.ow);
-        MTMC(c->counters.ensure(sizeof(unsigned long long) * best.size()));
-        HIPC(hipMemsetAsync(c->counters.p, 0, sizeof(unsigned long long) * best.size(), c->stream));
-        if (n > 0) {
-            const int nbk = extremum_batch_blocks(max_px);
-            hipLaunchKernelGGL(extremum_batch_kernel, dim3(nbk, n, nb), dim3(256), 0, c->stream, maps, c->td.as<TemplDev>(), rows,
-                               nbk, c->counters.as<unsigned long long>());
-            HIPC(hipGetLastError());
-        }
-        HIPC(hipEventRecord(c->ev[2], c->stream));
-        HIPC(hipMemcpyAsync(best.data(), c->counters.p, sizeof(unsigned long long) * best.size(), hipMemcpyDeviceToHost, c->stream));
-        HIPC(hipStreamSynchronize(c->stream));
-        for (int b = 0; b < nb; ++b)
-            for (int t = 0; t < n; ++t) {           // (fm_end's decoding, on the image's own index)
-                const TemplDev& d = c->td_host[t];
-                per_img[b].push_back(decode_extremum_key(best[2 * ((size_t)b * n + t) + (mode_min ? 1 : 0)], mode_min, t,
-                                                         d.ow, d.cols, d.rows));
-            }
-    } else {
-        const int n2d = (int)c->list2d.size();
-        std::vector<int> nontriv((size_t)nb * std::max(1, n), 0);
-        std::vector<mtm_hit> hits;
-        if (n2d > 0) {
-            // [hit count | nontrivial flag per (image, template)] [records]
-            const size_t hdr = round_up(sizeof(unsigned long long) + sizeof(int) * nontriv.size(), 16);
-            const dim3 grd = peak_grid(c, kPkRows);
-            bool done = false;
-            for (int pass = 0; pass < 2 && !done; ++pass) {         // (a list that overflowed: once more, large enough)
-                MTMC(c->hits.ensure(hdr + sizeof(mtm_hit) * (size_t)c->hit_cap));
-                uint8_t* dbase = c->hits.as<uint8_t>();
-                unsigned long long* counter = reinterpret_cast<unsigned long long*>(dbase);
-                mtm_hit* dhits = reinterpret_cast<mtm_hit*>(dbase + hdr);
-                HIPC(hipMemsetAsync(dbase, 0, hdr, c->stream));
-                hipLaunchKernelGGL(peaks_batch_kernel, grd, dim3(256), 0, c->stream, maps, c->td.as<TemplDev>(),
-                                   c->tlist.as<int>() + c->list2d_off, mode_min ? 1 : 0, thr, c->opt_border, dhits,
-                                   (unsigned long long)c->hit_cap, counter, reinterpret_cast<int*>(counter + 1), rows, n);
-                HIPC(hipGetLastError());
-                std::vector<uint8_t> hb(hdr);
-                HIPC(hipMemcpyAsync(hb.data(), dbase, hdr, hipMemcpyDeviceToHost, c->stream));
-                HIPC(hipStreamSynchronize(c->stream));
-                unsigned long long count = 0;
-                std::memcpy(&count, hb.data(), sizeof(count));
-                std::memcpy(nontriv.data(), hb.data() + sizeof(count), sizeof(int) * nontriv.size());
-                if ((int64_t)count <= c->hit_cap) {
-                    hits.resize((size_t)count);
-                    if (count) {
-                        HIPC(hipMemcpyAsync(hits.data(), dhits, sizeof(mtm_hit) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
-                        HIPC(hipStreamSynchronize(c->stream));
-                    }
-                    done = true;
-                } else {
-                    c->hit_cap = (int64_t)count + 1024;
-                }
-            }
-            if (!done) return ladder_exhausted();
-        }
-        HIPC(hipEventRecord(c->ev[2], c->stream));
-        // stack rows -> (image, row); skimage: a map in which every pixel equals its local maximum has no peaks at all
-        for (const mtm_hit& h : hits) {
-            const int b = h.y / rows;
-            if (!nontriv[(size_t)b * n + h.templ_idx]) continue;
-            mtm_hit r = h;
-            r.y -= b * rows;
-            per_img[b].push_back(r);
-        }
+    // the maps are in memory: the peak pass (mtm_peaks.hip) -> per-image records
+    MTMC(batch_peak_pass(c, mode, thr, mode_min, nb, rows, per_img));
+    if (mode != MTM_PEAKS_GLOBAL) {
         MTMC(append_line_map_peaks(c, thr, mode_min, nb, rows, per_img));
         for (int b = 0; b < nb; ++b) sort_hits(per_img[b], mode_min);
     }
@@ -954,40 +638,9 @@ int batch_chunk(mtm_ctx* c, const void* const* px, int nb, int rows, int cols, i
 
 namespace mtmi {
 
-int window_peak_pass(mtm_ctx* c, int n, bool global, const WindowPeakLaunch& launch, std::vector<unsigned long long>& best,
-                     std::vector<mtm_hit>& recs, const char* who) {
-    const size_t flag_bytes = sizeof(unsigned long long) * (1 + (size_t)n) + sizeof(int) * (size_t)n;
-    MTMC(c->win_flags.ensure(flag_bytes));
-    std::vector<uint8_t> fl(flag_bytes);
-    unsigned long long cap = (unsigned long long)std::max<int64_t>(1, c->hit_cap), count = 0;
-    for (int pass = 0; pass < 2; ++pass) {          // (a list that overflowed: once more, large enough)
-        MTMC(c->win_hits.ensure(sizeof(mtm_hit) * (size_t)cap));
-        HIPC(hipMemsetAsync(c->win_flags.p, 0, flag_bytes, c->stream));
-        unsigned long long* counter = c->win_flags.as<unsigned long long>();
-        MTMC(launch(c->win_hits.as<mtm_hit>(), cap, counter, counter + 1, reinterpret_cast<int*>(counter + 1 + n)));
-        HIPC(hipMemcpyAsync(fl.data(), c->win_flags.p, flag_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPC(hipStreamSynchronize(c->stream));
-        std::memcpy(&count, fl.data(), sizeof(count));
-        if (count <= cap) break;
-        if (pass == 1) {            // (cannot happen: the second pass runs with room for every record of the first)
-            set_error(std::string(who) + ": hit list overflowed twice");
-            return MTM_E_HIP;
-        }
-        cap = count + 1024;
-    }
-    if (global) {
-        best.resize((size_t)n);
-        if (n > 0) std::memcpy(best.data(), fl.data() + sizeof(unsigned long long), sizeof(unsigned long long) * (size_t)n);
-        return MTM_OK;
-    }
-    std::vector<mtm_hit> raw((size_t)count);
-    if (count > 0) HIPC(hipMemcpy(raw.data(), c->win_hits.p, sizeof(mtm_hit) * (size_t)count, hipMemcpyDeviceToHost));
-    std::vector<int> nontrivial((size_t)n);
-    if (n > 0) std::memcpy(nontrivial.data(), fl.data() + sizeof(unsigned long long) * (1 + (size_t)n), sizeof(int) * (size_t)n);
-    for (const mtm_hit& r : raw)
-        if (nontrivial[(size_t)r.templ_idx]) recs.push_back(r);     // a slot with no output that differs from its
-                                                                    // neighbourhood's max has no peaks
-    return MTM_OK;
+int ladder_exhausted() {
+    set_error("mtm_find_matches: internal state (the overflow fallbacks ran out of passes)");
+    return MTM_E_STATE;
 }
 
 }  // namespace mtmi
@@ -1066,266 +719,6 @@ int mtm_find_matches_image_nms(mtm_ctx* c, const void* px, int rows, int cols, i
     const int rc = find_matches_impl(c, MTM_PEAKS_LOCAL, score_threshold, out, capacity, n_out, nullptr, &up, &nms);
     host_trace(c, 15);
     return rc;
-}
-
-// Test support: the chain of queue_nms_chain on a list the caller hands over (tests/test_gpu_device_nms.py).
-int mtm_debug_device_nms(mtm_ctx* c, const mtm_hit* hits, int64_t n, int rows, int cols, int max_side, double score_threshold,
-                         int ascending, double max_overlap, int64_t n_min, int64_t n_max, mtm_hit* out, int64_t capacity,
-                         int64_t* n_champions, int64_t* n_undecided) {
-    if (!c) {
-        set_error("mtm_debug_device_nms: null context");
-        return MTM_E_INVALID;
-    }
-    MTM_NOT_IN_FLIGHT(c, "mtm_debug_device_nms");
-    const bool gate = n >= n_min && n <= n_max;
-    if (n < 0 || (n > 0 && !hits) || rows < 1 || cols < 1 || max_side < 0 || !(max_overlap >= 0.0) || n_min < 0 || n_max < 1 ||
-        n_max > (1ll << 18) || capacity < 0 || !n_champions || !n_undecided || (gate && (capacity < n || (n > 0 && !out)))) {
-        set_error("mtm_debug_device_nms: bad arguments (negative sizes, max_overlap < 0, n_max outside 1 .. 2^18, or a capacity "
-                  "below the length of a list inside [n_min, n_max])");
-        return MTM_E_INVALID;
-    }
-    const NmsGrid g = nms_grid(rows, cols, max_side);
-    if ((long long)g.gw * g.gh > (1ll << 24)) {
-        set_error("mtm_debug_device_nms: more than 2^24 grid cells");
-        return MTM_E_INVALID;
-    }
-    HIPC(hipSetDevice(c->device));
-    // [the count][the records]
-    MTMC(c->nms_dbg.ensure(256 + sizeof(mtm_hit) * (size_t)std::max<int64_t>(n, 1)));
-    uint8_t* d = c->nms_dbg.as<uint8_t>();
-    const unsigned long long count = (unsigned long long)n;
-    HIPC(hipMemcpyAsync(d, &count, sizeof(count), hipMemcpyHostToDevice, c->stream));
-    if (n) HIPC(hipMemcpyAsync(d + 256, hits, sizeof(mtm_hit) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    DeviceNms q;
-    MTMC(queue_nms_chain(c, reinterpret_cast<const mtm_hit*>(d + 256), reinterpret_cast<const unsigned long long*>(d),
-                         (unsigned)std::min<int64_t>(n_min, 1ll << 30), (size_t)n_max, ascending != 0,
-                         (float)(ascending ? (1.0 - score_threshold) : score_threshold), (float)max_overlap, g, &q));
-    HIPC(hipStreamSynchronize(c->stream));
-    std::vector<mtm_hit> rest;
-    long long n_sure = 0;
-    MTMC(fetch_device_nms(c, q, count, rest, &n_sure));
-    if (!gate && !rest.empty()) {
-        set_error("mtm_debug_device_nms: internal state (a list outside [n_min, n_max] produced records)");
-        return MTM_E_STATE;
-    }
-    if (!rest.empty()) std::memcpy(out, rest.data(), sizeof(mtm_hit) * rest.size());
-    *n_champions = (int64_t)n_sure;
-    *n_undecided = (int64_t)rest.size() - (int64_t)n_sure;
-    return MTM_OK;
-}
-
-// Test support: the peak pass on maps the caller hands over (tests/test_gpu_peaks.py).  Everything lives in peak_dbg - the
-// TemplDev table, the map arena, flags, lists, counters -, laid out per call; nothing of the context's placement or options is
-// read or written.  The grids and capacities are those of queue_peak_pass / collect_global_extremum / batch_chunk
-// (mtm_peak_sizing.h).
-int mtm_debug_peak_pass(mtm_ctx* c, const mtm_peak_pass* a) {
-    if (!c || !a) {
-        set_error("mtm_debug_peak_pass: null context or arguments");
-        return MTM_E_INVALID;
-    }
-    MTM_NOT_IN_FLIGHT(c, "mtm_debug_peak_pass");
-    const auto bad = [](const char* what) {
-        set_error(std::string("mtm_debug_peak_pass: ") + what);
-        return MTM_E_INVALID;
-    };
-    const int n = a->n_maps, route = a->route;
-    if (n < 1 || n > 4096 || route < MTM_PEAK_SCAN || route > MTM_PEAK_EXTREMUM_BATCH || !a->dims || !a->maps || !a->info ||
-        (a->border != MTM_BORDER_CONSTANT && a->border != MTM_BORDER_NEAREST) || a->hit_cap < 1 || a->hit_cap > (1ll << 24) ||
-        a->pattern_byte < 0 || a->pattern_byte > 255 || a->capacity < 0 || a->n_ints < 0 || a->list_cap < 0)
-        return bad("bad arguments (1 .. 4096 maps, a route, a border rule, hit_cap in 1 .. 2^24, a pattern byte)");
-    const bool batch = route == MTM_PEAK_SCAN_BATCH || route == MTM_PEAK_EXTREMUM_BATCH;
-    const bool ext = route == MTM_PEAK_EXTREMUM || route == MTM_PEAK_EXTREMUM_BATCH;
-    const bool verify = route == MTM_PEAK_VERIFY_MAPS || route == MTM_PEAK_VERIFY_HASH;
-    const bool mode_min = a->mode_min != 0;
-    // the table, as plan_placement fills the fields the peak kernels read
-    std::vector<TemplDev> td((size_t)n, TemplDev{});
-    std::vector<size_t> src_off((size_t)n);
-    size_t arena = 0, src = 0;
-    int max_oh = 0, max_ow = 0, n_img = 1;
-    long long max_px = 1;
-    for (int t = 0; t < n; ++t) {
-        const int oh = a->dims[4 * t], ow = a->dims[4 * t + 1], h = a->dims[4 * t + 2], w = a->dims[4 * t + 3];
-        const int least = ext ? 1 : 2;          // (the scans and verifiers only ever see 2-D maps: mtm_ctx::list2d)
-        if (oh < least || ow < least || oh > kBatchMaxRows || ow > 65535 || h < 1 || w < 1) return bad("a map's size");
-        TemplDev& d = td[(size_t)t];
-        d.rows = h;
-        d.cols = w;
-        d.oh = oh;
-        d.ow = ow;
-        d.map_pitch = map_pitch_of(ow);
-        d.map_off = (long long)arena;
-        d.k1_off = d.k2_off = d.pack_off = -1;
-        arena += (size_t)d.map_pitch * oh;
-        src_off[(size_t)t] = src;
-        src += (size_t)oh * ow;
-        max_oh = std::max(max_oh, oh);
-        max_ow = std::max(max_ow, ow);
-        if (batch) {
-            if (a->img_rows < 2 || h > a->img_rows - 1 || (oh + h - 1) % a->img_rows != 0) return bad("img_rows does not fit a map");
-            const int nbt = (oh + h - 1) / a->img_rows;
-            if (t > 0 && nbt != n_img) return bad("the maps' stacks differ in their number of images");
-            n_img = nbt;
-            max_px = std::max(max_px, (long long)(a->img_rows - h + 1) * ow);
-        }
-    }
-    if (arena > (64ull << 20)) return bad("more than 2^26 floats of maps");
-    const size_t n_ints = (size_t)n * (size_t)n_img;
-    const size_t capacity = (size_t)a->capacity;
-    if (ext) {
-        if (!a->keys || !a->ext_hits || (size_t)a->n_ints < n_ints) return bad("the extremum routes need keys and ext_hits of 2 * n_ints");
-    } else if (!a->records || !a->count || !a->raw || !a->trivial || (size_t)a->n_ints < n_ints || a->capacity < a->hit_cap) {
-        return bad("records (capacity >= hit_cap), count, raw and trivial (n_ints each) are needed");
-    }
-    // the grids and capacities of the route
-    const PeakGrid grd = peak_grid_dims(max_oh, max_ow, n, route == MTM_PEAK_SEGMENTS ? kPkSparseRows : kPkRows);
-    const unsigned long long hit_cap = (unsigned long long)a->hit_cap;
-    unsigned long long n_lists = 0, cap_t = 0;
-    size_t flag_rstride = 0, flag_tstride = 0;
-    if (route == MTM_PEAK_SEGMENTS) {
-        n_lists = (unsigned long long)grd.z * grd.x;
-        cap_t = peak_list_cap(hit_cap, n_lists);
-        flag_rstride = grd.x;
-        flag_tstride = (size_t)max_oh * grd.x;
-        if (!a->flags || !a->list_counts || (unsigned long long)a->list_cap < n_lists) return bad("flags and list_counts (one per list) are needed");
-    }
-    unsigned blocks = 0, hash_mask = 0;
-    size_t n_judged = 0;
-    if (verify) {
-        if (a->cand_cap < 1 || a->cand_cap > kCandListMax || a->cand_count < 0 || a->n_cands < 0 || (a->n_cands > 0 && !a->cands))
-            return bad("the candidate list (cand_cap in 1 .. 2^20)");
-        n_judged = (size_t)std::min(a->cand_count, a->cand_cap);
-        if ((size_t)a->n_cands < n_judged) return bad("fewer candidate records than min(cand_count, cand_cap)");
-        for (size_t i = 0; i < n_judged; ++i) {
-            const mtm_hit& h = a->cands[i];
-            if (h.templ_idx < 0 || h.templ_idx >= n || h.x < 0 || h.y < 0 || h.x >= td[(size_t)h.templ_idx].ow ||
-                h.y >= td[(size_t)h.templ_idx].oh)
-                return bad("a candidate outside its map");
-        }
-        blocks = verify_blocks(std::max<long long>(a->hit_cap, a->cand_cap));
-        if (route == MTM_PEAK_VERIFY_HASH) hash_mask = (unsigned)(cand_hash_slots(a->cand_cap) - 1);
-    }
-    const int nbk = route == MTM_PEAK_EXTREMUM ? extremum_blocks() : route == MTM_PEAK_EXTREMUM_BATCH ? extremum_batch_blocks(max_px) : 0;
-    // peak_dbg: [table][map list][count | per-map ints][records][maps][flags][candidates][hash][list counters][lists][keys]
-    size_t total = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t off = total;
-        total += round_up(std::max<size_t>(bytes, 16), 256);
-        return off;
-    };
-    const size_t o_td = take(sizeof(TemplDev) * (size_t)n), o_tl = take(sizeof(int) * (size_t)n);
-    const size_t hdr_bytes = 16 + sizeof(int) * n_ints;
-    const size_t o_hdr = take(hdr_bytes), o_rec = take(sizeof(mtm_hit) * capacity), o_maps = take(sizeof(float) * arena);
-    const size_t flag_bytes = (size_t)n * flag_tstride;
-    const size_t o_flags = take(flag_bytes);
-    const size_t o_cand = take(16 + sizeof(mtm_hit) * (size_t)std::max<int64_t>(verify ? a->cand_cap : 0, 1));
-    const size_t o_hash = take(hash_mask ? cand_hash_bytes(hash_mask) : 0);
-    const size_t cnt_bytes = sizeof(unsigned long long) * (size_t)n_lists;
-    const size_t o_cnt = take(cnt_bytes), o_lists = take(sizeof(mtm_hit) * (size_t)cap_t * (size_t)n_lists);
-    const size_t key_bytes = sizeof(unsigned long long) * 2 * n_ints;
-    const size_t o_keys = take(key_bytes);
-    HIPC(hipSetDevice(c->device));
-    MTMC(c->peak_dbg.ensure(total));
-    uint8_t* b = c->peak_dbg.as<uint8_t>();
-    // the arena as the device will hold it: the pattern, then the maps row by row (holes: flagged segments only)
-    std::vector<uint8_t> stage(sizeof(float) * arena, (uint8_t)a->pattern_byte);
-    for (int t = 0; t < n; ++t) {
-        const TemplDev& d = td[(size_t)t];
-        for (int y = 0; y < d.oh; ++y) {
-            const float* from = a->maps + src_off[(size_t)t] + (size_t)y * d.ow;
-            uint8_t* to = stage.data() + sizeof(float) * ((size_t)d.map_off + (size_t)y * d.map_pitch);
-            if (route == MTM_PEAK_SEGMENTS && a->holes) {
-                for (int sx = 0; sx * kPkCols < d.ow; ++sx)
-                    if (a->flags[(size_t)t * flag_tstride + (size_t)y * flag_rstride + (size_t)sx])
-                        std::memcpy(to + sizeof(float) * (size_t)sx * kPkCols, from + (size_t)sx * kPkCols,
-                                    sizeof(float) * (size_t)std::min(kPkCols, d.ow - sx * kPkCols));
-            } else {
-                std::memcpy(to, from, sizeof(float) * (size_t)d.ow);
-            }
-        }
-    }
-    std::vector<int> tl((size_t)n);
-    for (int t = 0; t < n; ++t) tl[(size_t)t] = t;
-    HIPC(hipMemcpyAsync(b + o_td, td.data(), sizeof(TemplDev) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(b + o_tl, tl.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemsetAsync(b + o_hdr, 0, hdr_bytes, c->stream));
-    if (!ext && capacity) HIPC(hipMemcpyAsync(b + o_rec, a->records, sizeof(mtm_hit) * capacity, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(b + o_maps, stage.data(), stage.size(), hipMemcpyHostToDevice, c->stream));
-    const TemplDev* dtd = reinterpret_cast<const TemplDev*>(b + o_td);
-    const int* dtl = reinterpret_cast<const int*>(b + o_tl);
-    const float* dmaps = reinterpret_cast<const float*>(b + o_maps);
-    unsigned long long* dcount = reinterpret_cast<unsigned long long*>(b + o_hdr);
-    int* dints = reinterpret_cast<int*>(b + o_hdr + 16);
-    mtm_hit* drec = reinterpret_cast<mtm_hit*>(b + o_rec);
-    unsigned long long* dkeys = reinterpret_cast<unsigned long long*>(b + o_keys);
-    const dim3 grid(grd.x, grd.y, grd.z);
-    if (route == MTM_PEAK_SCAN) {
-        hipLaunchKernelGGL(peaks_kernel, grid, dim3(256), 0, c->stream, dmaps, dtd, dtl, mode_min ? 1 : 0, a->thr, a->border, drec,
-                           hit_cap, dcount, dints);
-    } else if (route == MTM_PEAK_SCAN_BATCH) {
-        hipLaunchKernelGGL(peaks_batch_kernel, grid, dim3(256), 0, c->stream, dmaps, dtd, dtl, mode_min ? 1 : 0, a->thr, a->border,
-                           drec, hit_cap, dcount, dints, a->img_rows, n);
-    } else if (route == MTM_PEAK_SEGMENTS) {
-        unsigned long long* counts_t = reinterpret_cast<unsigned long long*>(b + o_cnt);
-        mtm_hit* hits_t = reinterpret_cast<mtm_hit*>(b + o_lists);
-        HIPC(hipMemcpyAsync(b + o_flags, a->flags, flag_bytes, hipMemcpyHostToDevice, c->stream));
-        HIPC(hipMemsetAsync(counts_t, 0, round_up(cnt_bytes, 256), c->stream));
-        hipLaunchKernelGGL(peaks_sparse_kernel, grid, dim3(256), 0, c->stream, dmaps, dtd, dtl, mode_min ? 1 : 0, a->thr, a->border,
-                           hits_t, cap_t, counts_t, dints, b + o_flags, (int)flag_tstride, (int)flag_rstride, a->holes ? 1 : 0);
-        hipLaunchKernelGGL(compact_hits_kernel, dim3((unsigned)n_lists), dim3(256), 0, c->stream, hits_t, cap_t, counts_t,
-                           (int)n_lists, drec, hit_cap, dcount);
-    } else if (verify) {
-        const unsigned long long cc[2] = {(unsigned long long)a->cand_count, 0ull};
-        unsigned long long* dcc = reinterpret_cast<unsigned long long*>(b + o_cand);
-        const mtm_hit* dcands = reinterpret_cast<const mtm_hit*>(b + o_cand + 16);
-        HIPC(hipMemcpyAsync(dcc, cc, sizeof(cc), hipMemcpyHostToDevice, c->stream));
-        if (n_judged) HIPC(hipMemcpyAsync(b + o_cand + 16, a->cands, sizeof(mtm_hit) * n_judged, hipMemcpyHostToDevice, c->stream));
-        if (route == MTM_PEAK_VERIFY_HASH) {
-            unsigned long long* keys = reinterpret_cast<unsigned long long*>(b + o_hash);
-            int* vals = reinterpret_cast<int*>(keys + (size_t)hash_mask + 1);
-            HIPC(hipMemsetAsync(keys, 0, cand_hash_key_bytes(hash_mask), c->stream));
-            hipLaunchKernelGGL(cand_hash_insert_kernel, dim3(blocks), dim3(256), 0, c->stream, dcands, dcc,
-                               (unsigned long long)a->cand_cap, keys, vals, hash_mask);
-            hipLaunchKernelGGL(verify_hash_kernel, dim3(blocks), dim3(256), 0, c->stream, dtd, mode_min ? 1 : 0, a->border, dcands, dcc,
-                               (unsigned long long)a->cand_cap, keys, vals, hash_mask, drec, hit_cap, dcount, dints, a->thr_q);
-        } else {
-            hipLaunchKernelGGL(verify_peaks_kernel, dim3(blocks), dim3(256), 0, c->stream, dmaps, dtd, mode_min ? 1 : 0, a->border,
-                               dcands, dcc, (unsigned long long)a->cand_cap, drec, hit_cap, dcount, dints, a->thr_q);
-        }
-    } else {
-        HIPC(hipMemsetAsync(dkeys, 0, key_bytes, c->stream));
-        if (route == MTM_PEAK_EXTREMUM)
-            hipLaunchKernelGGL(extremum_kernel, dim3(nbk, n), dim3(256), 0, c->stream, dmaps, dtd, nbk, dkeys);
-        else
-            hipLaunchKernelGGL(extremum_batch_kernel, dim3(nbk, n, n_img), dim3(256), 0, c->stream, dmaps, dtd, a->img_rows, nbk, dkeys);
-    }
-    HIPC(hipGetLastError());
-    std::vector<uint8_t> hdr(hdr_bytes);
-    HIPC(hipMemcpyAsync(hdr.data(), b + o_hdr, hdr_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (!ext && capacity) HIPC(hipMemcpyAsync(a->records, b + o_rec, sizeof(mtm_hit) * capacity, hipMemcpyDeviceToHost, c->stream));
-    if (n_lists) HIPC(hipMemcpyAsync(a->list_counts, b + o_cnt, cnt_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (ext) HIPC(hipMemcpyAsync(a->keys, dkeys, key_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    if (ext) {
-        for (size_t i = 0; i < n_ints; ++i) {
-            const TemplDev& d = td[i % (size_t)n];
-            a->ext_hits[2 * i] = decode_extremum_key(a->keys[2 * i], false, (int)(i % (size_t)n), d.ow, d.cols, d.rows);
-            a->ext_hits[2 * i + 1] = decode_extremum_key(a->keys[2 * i + 1], true, (int)(i % (size_t)n), d.ow, d.cols, d.rows);
-        }
-    } else {
-        unsigned long long count = 0;
-        std::memcpy(&count, hdr.data(), sizeof(count));
-        *a->count = count;
-        std::memcpy(a->raw, hdr.data() + 16, sizeof(int) * n_ints);
-        for (size_t i = 0; i < n_ints; ++i) {
-            const TemplDev& d = td[i % (size_t)n];
-            const int f = a->raw[i];
-            a->trivial[i] = verify ? fused_count_trivial(f, d.oh, d.ow) : batch ? f == 0 : scan_flags_trivial((unsigned)f);
-        }
-    }
-    const int64_t info[8] = {(int64_t)grd.x, (int64_t)grd.y, (int64_t)grd.z, (int64_t)cap_t, (int64_t)n_lists, (int64_t)blocks,
-                             hash_mask ? (int64_t)hash_mask + 1 : 0, (int64_t)nbk};
-    std::memcpy(a->info, info, sizeof(info));
-    return MTM_OK;
 }
 
 // One step of the process-per-GPU form in ONE native call (round 5): this rank's shard is searched, its hits get their list

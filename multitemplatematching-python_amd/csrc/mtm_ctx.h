@@ -1,7 +1,8 @@
 // Internal header of libmtm_hip.so's GPU side: the context, the size classes of a template set, and the functions the
 // translation units share.  Units: mtm_context.hip (context, options, image upload), mtm_placement.hip (template sets ->
 // size classes, packs, constants), mtm_launch.hip (window statistics and score-map launches), mtm_api.hip
-// (mtm_find_matches and friends: peak extraction, hit lists), mtm_comm.hip (RCCL hit exchange), mtm_pyramid.hip (the
+// (mtm_find_matches and friends: a call's route, its ladder, hit lists), mtm_peaks.hip (the peak pass: its launchers and
+// fetches, the device's share of the NMS), mtm_comm.hip (RCCL hit exchange), mtm_pyramid.hip (the
 // coarse-to-fine search), mtm_boxes.hip (many searchBoxes in one call), mtm_subpixel.hip (hit neighbourhoods), mtm_blocks.hip (block matching
 // between two images).  Not part of the ABI.
 #pragma once
@@ -527,16 +528,6 @@ int prepare_window_templates(mtm_ctx* c, const std::vector<BlobTempl>& tl);
 // The templates' epilogue constants (TemplDev, statistics of the last mtm_set_templates and the sizes of `tl`) in
 // mtm_ctx::box_td, uploaded once per template set (mtm_boxes.hip; the boxes and tracking searches).
 int prepare_box_td(mtm_ctx* c, const std::vector<BlobTempl>& tl);
-// The peak pass of the window searches (mtm_api.hip) over n slots (pyramid: templates, boxes: units).  Flags laid out as
-// [u64 record count][u64 best key x n][int nontrivial x n] are zeroed, `launch` enqueues the peak kernels (and anything that
-// must follow them before the read-back) writing records to (hits, cap), the flags come back in one copy; a list that
-// overflowed runs once more with room for every record.  Global mode: the best key per slot into `best`.  Local mode: the
-// records of the slots flagged nontrivial, unsorted, appended to `recs`.  The list starts at mtm_ctx::hit_cap records and
-// grows for this call only: hit_cap is left as it is (later mtm_find_matches routes size candidate lists by it).
-using WindowPeakLaunch = std::function<int(mtm_hit* hits, unsigned long long cap, unsigned long long* counter,
-                                           unsigned long long* best, int* nontrivial)>;
-int window_peak_pass(mtm_ctx* c, int n, bool global, const WindowPeakLaunch& launch, std::vector<unsigned long long>& best,
-                     std::vector<mtm_hit>& recs, const char* who);
 // The planes of `dst`'s current slot from the raw uint8 image already in `src` (src_rows x src_cols, tightly packed),
 // area-downscaled by `factor` on `stream`; `dst` adopts the downscaled image (mtm_find_matches_pyramid's coarse level).
 int derive_downscaled_u8(mtm_ctx* dst, const mtm_ctx::ImageSlot& src, int src_rows, int src_cols, int chans, int factor,
@@ -563,5 +554,76 @@ int run_score_all(mtm_ctx* c, CallRoute& R);
 bool banded_ok(mtm_ctx* c, const ImageArgs& a, bool* single_band);
 int run_score_banded(mtm_ctx* c, CallRoute& R, const ImageArgs& a);
 int collect_ncc_time(mtm_ctx* c);
+
+// ---- mtm_peaks.hip: the host side of the peak pass (the only unit that launches mtm_k_peaks.hip.h and mtm_k_nms.hip.h)
+constexpr size_t kHitPrefetch = 1024;       // candidate / hit records fetched together with the counters
+// The hit buffer of a peak pass (mtm_ctx::hits), as the kernels read it: [hit count | candidate count | spare word of the
+// candidate header (float32 map mode: the "bound too wide" flag) | one int per template] [records].  The header and the
+// first kHitPrefetch records come back in ONE copy.
+struct HitBuffer {
+    size_t hdr_bytes;
+    uint8_t* base = nullptr;        // on the device
+    explicit HitBuffer(int n) : hdr_bytes(round_up(3 * sizeof(unsigned long long) + sizeof(int) * (size_t)std::max(1, n), 16)) {}
+    unsigned long long* count() const { return reinterpret_cast<unsigned long long*>(base); }
+    unsigned long long* cand_header() const { return count() + 1; }        // two words, as the candidate buffer starts
+    int* flags() const { return reinterpret_cast<int*>(count() + 3); }
+    mtm_hit* records() const { return reinterpret_cast<mtm_hit*>(base + hdr_bytes); }
+    // a host copy of the header
+    struct Header {
+        unsigned long long count, ncand;
+        unsigned rig_wide;
+    };
+    Header decode(const uint8_t* host, int n, int* tflags) const {
+        Header h{};
+        std::memcpy(&h.count, host, sizeof(h.count));
+        std::memcpy(&h.ncand, host + sizeof(h.count), sizeof(h.ncand));
+        std::memcpy(&h.rig_wide, host + 2 * sizeof(h.count), sizeof(h.rig_wide));
+        std::memcpy(tflags, host + 3 * sizeof(h.count), sizeof(int) * (size_t)n);
+        return h;
+    }
+    const uint8_t* host_records(const uint8_t* host) const { return host + hdr_bytes; }
+};
+// The device's share of the non-maxima suppression (mtm_k_nms.hip.h), queued right behind the peak pass: the length of the
+// peak list is still on the device, the launches read it there and do nothing unless it lies in [nms_device_min, n_max].
+// What a neighbourhood's best hit suppresses stays on the device; fetch_peak_list brings the rest: first the hits that are
+// certainly kept (nothing earlier overlaps them), then the undecided ones.
+struct DeviceNms {
+    bool queued = false;
+    unsigned n_max = 0;
+    const unsigned long long* cnt_pin = nullptr;   // landing buffer of the two counters (champions, undecided), page-locked
+    const mtm_hit* out = nullptr;
+};
+// fm_begin: the first max_records records of the candidate buffer `cands` and its header -> the pinned landing buffer
+int queue_cand_fetch(hipStream_t stream, const void* cands, void* pinned, size_t max_records);
+// One attempt of the device's peak pass, queued: the candidate list verified (against the hash table of its positions, or
+// the maps), else the maps scanned (the flagged segments, with compaction and the device's share of a suppression request,
+// or everything).
+int queue_peak_pass(mtm_ctx* c, const CallRoute& R, HitBuffer& hb, DeviceNms* dnms);
+// The one copy behind a peak pass - header + first kHitPrefetch records into host_buf - and what it says: the number of
+// peaks, the per-template ints, what overflowed.  Records ev[2].
+int fetch_pass_outcome(mtm_ctx* c, const CallRoute& R, const HitBuffer& hb, std::vector<uint8_t>& host_buf, int* tflags,
+                       unsigned long long* count, PassOutcome* o);
+// The `count` peaks of a pass whose lists held everything: from host_buf and, beyond the prefetched ones, the device.
+// Thousands of peaks and a suppression request: decided on the device, only the kept ones are fetched.
+int fetch_peak_list(mtm_ctx* c, CallRoute& R, const HitBuffer& hb, const std::vector<uint8_t>& host_buf, unsigned long long count,
+                    const int* tflags, const DeviceNms& dnms, std::vector<mtm_hit>& hits);
+// MTM_PEAKS_GLOBAL without the fused extremum (R.ext: nothing to do): mtm_ctx::counters cleared, extremum_kernel over the maps
+int queue_extremum_pass(mtm_ctx* c, const CallRoute& R);
+// mtm_find_matches_batch, the maps of a stack of nb images of `rows` rows in memory: the per-image extremum, or the
+// seam-aware scan (a list that overflows grows mtm_ctx::hit_cap and runs once more) -> image b's records, unsorted, appended
+// to per_img[b].  Records ev[2].
+int batch_peak_pass(mtm_ctx* c, int mode, float thr, bool mode_min, int nb, int rows, std::vector<mtm_hit>* per_img);
+// The peak pass of the window searches over n slots (pyramid: templates, boxes: units).  Flags laid out as
+// [u64 record count][u64 best key x n][int nontrivial x n] are zeroed, `launch` enqueues the peak kernels (and anything that
+// must follow them before the read-back) writing records to (hits, cap), the flags come back in one copy; a list that
+// overflowed runs once more with room for every record.  Global mode: the best key per slot into `best`.  Local mode: the
+// records of the slots flagged nontrivial, unsorted, appended to `recs`.  The list starts at mtm_ctx::hit_cap records and
+// grows for this call only: hit_cap is left as it is (later mtm_find_matches routes size candidate lists by it).
+using WindowPeakLaunch = std::function<int(mtm_hit* hits, unsigned long long cap, unsigned long long* counter,
+                                           unsigned long long* best, int* nontrivial)>;
+int window_peak_pass(mtm_ctx* c, int n, bool global, const WindowPeakLaunch& launch, std::vector<unsigned long long>& best,
+                     std::vector<mtm_hit>& recs, const char* who);
+// ---- mtm_api.hip
+int ladder_exhausted();        // the error of a call whose overflow fallbacks ran out of passes
 
 }  // namespace mtmi

@@ -224,7 +224,7 @@ int publish_hits(std::vector<mtm_hit>& hits, std::vector<mtm_hit>& last_hits, mt
 }
 
 // ---------------------------------------------------------------------------------------------
-// mtm_find_matches' synchronising half (fm_end, mtm_api.hip): what needs no device.
+// mtm_find_matches' synchronising half (fm_end, mtm_api.hip; its peak pass: mtm_peaks.hip): what needs no device.
 // ---------------------------------------------------------------------------------------------
 void verify_candidates_3x3(const mtm_hit* cd, size_t ncand, const MapDims& dims, bool mode_min, float thr_q, float padv,
                            std::vector<unsigned long long>& hk, std::vector<int>& hv, std::vector<mtm_hit>& hits, int* tflags) {

@@ -57,7 +57,7 @@ int copy_out_hits(const std::vector<mtm_hit>& hits, mtm_hit* out, int64_t capaci
 int publish_hits(std::vector<mtm_hit>& hits, std::vector<mtm_hit>& last_hits, mtm_hit* out, int64_t capacity,
                  int64_t* n_out, const std::string& msg);
 
-// ---- mtm_find_matches' synchronising half (fm_end, mtm_api.hip): its host-only pieces
+// ---- mtm_find_matches' synchronising half (fm_end, mtm_api.hip; its peak pass: mtm_peaks.hip): its host-only pieces
 
 // (oh, ow) of template t's map, read in place from any array of records that holds both (`stride` bytes apart)
 struct MapDims {

@@ -8,7 +8,7 @@
 // Hits only interact within a box side of each other: every hit looks at the hits of the 3 x 3 grid cells around its
 // corner (cell = the largest box side), the hits sorted by cell.  (A first version decided everything on the device, every thread waiting for the
 // earlier hits it depends on: correct, but in dense fields a hit has hundreds of earlier neighbours and the waiting
-// scans took 1 ms - twice the host's pass.)  Launched by mtm_api.hip only.
+// scans took 1 ms - twice the host's pass.)  Launched by mtm_peaks.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -1,4 +1,4 @@
-// Peak extraction kernels: full 3x3 scan, verification of kernel candidates (against maps / by hash), global extremum.  Launched by mtm_api.hip only.
+// Peak extraction kernels: full 3x3 scan, verification of kernel candidates (against maps / by hash), global extremum.  Launched by mtm_peaks.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cfloat>

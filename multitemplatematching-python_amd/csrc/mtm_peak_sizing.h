@@ -1,6 +1,6 @@
-// The sizing rules of the peak pass (mtm_k_peaks.hip.h), written once for the search calls (queue_peak_pass, fm_begin,
-// collect_global_extremum, batch_chunk), the test-support entry mtm_debug_peak_pass and the host checks
-// (tests/native/sanitize_host.cpp).  Plain C++: no HIP type, no context.
+// The sizing rules of the peak pass (mtm_k_peaks.hip.h), written once: the launchers of mtm_peaks.hip apply them - for the
+// search calls and the test-support entry mtm_debug_peak_pass alike -, plan_call and fm_begin size the candidate hash
+// table with them, and the host checks (tests/native/sanitize_host.cpp) walk every rule.  Plain C++: no HIP type, no context.
 #pragma once
 #include <cstddef>
 #include <cstdint>

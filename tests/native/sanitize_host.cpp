@@ -584,7 +584,7 @@ static void test_peak_sizing(std::mt19937& rng) {
     }
 }
 
-// ---- the host-only pieces of fm_end (mtm_api.hip): the 3x3 test of the candidate list, the trivial-map rule, the ladder
+// ---- the host-only pieces of fm_end (mtm_api.hip; its peak pass: mtm_peaks.hip): the 3x3 test of the candidate list, the trivial-map rule, the ladder
 
 // one case of verify_candidates_3x3 against brute force over the maps: `maps[t]` the scores of an oh[t] x ow[t] map, the list
 // every pixel whose quality exceeds thr_q, shuffled; the scratch vectors come from the caller as they are

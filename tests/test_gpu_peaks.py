@@ -4,8 +4,8 @@ cand_hash_insert_kernel + verify_hash_kernel, extremum_kernel, extremum_batch_ke
 score maps, against the plain 3x3 reference of tests/peaks_model.py (-m gpu).
 
 Through a search the kernels only see what the score kernel produced from an image: nobody chooses where a plateau, a tie or
-a NaN falls.  Context.debug_peak_pass (mtm_debug_peak_pass) hands the very kernels, with the grids and capacities the search
-call derives (csrc/mtm_peak_sizing.h), maps of the test's choosing: the table of tests/peaks_model.py (validated on the CPU
+a NaN falls.  Context.debug_peak_pass (mtm_debug_peak_pass) hands the very kernels, through the launchers a search call goes
+through (csrc/mtm_peaks.hip; grids and capacities from csrc/mtm_peak_sizing.h), maps of the test's choosing: the table of tests/peaks_model.py (validated on the CPU
 by tests/test_peaks_model_cpu.py) - map widths 2 .. 8, 252 .. 260, 511 .. 513 and heights 2 .. 130 in lists of 1, 2 and 33
 maps of mixed sizes; single peaks, equal and greater pairs, plateaus on and across the seams of the 256-column by 32-row (8-row)
 strips; negative qualities at the border under both border rules; thresholds at a pixel's value and one float32 below; trivial

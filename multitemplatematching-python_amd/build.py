@@ -26,7 +26,7 @@ STAMP = LIB + ".stamp"
 SOURCES = ["mtm_context.hip", "mtm_placement.hip", "mtm_launch.hip", "mtm_api.hip", "mtm_peaks.hip", "mtm_comm.hip", "mtm_mfma_plain.hip", "mtm_mfma_rm.hip", "mtm_mfma_ext.hip", "mtm_mfma_kp.hip", "mtm_mfma_rows.hip", "mtm_bf16.hip", "mtm_pyramid.hip", "mtm_boxes.hip", "mtm_track.hip", "mtm_subpixel.hip", "mtm_blocks.hip",
            "mtm_host.cpp", "mtm_group.cpp"]
 HEADERS = ["mtm_ctx.h", "mtm_k_image.hip.h", "mtm_k_stats.hip.h", "mtm_k_score.hip.h", "mtm_k_peaks.hip.h", "mtm_score_params.h",
-           "mtm_templates_params.h", "mtm_device_util.hip.h", "mtm_mfma.hip.h", "mtm_mfma_params.h", "mtm_templates.hip.h",
+           "mtm_templates_params.h", "mtm_device_util.hip.h", "mtm_mfma.hip.h", "mtm_mfma_kloop.hip.h", "mtm_mfma_epilogue.hip.h", "mtm_mfma_finish.hip.h", "mtm_mfma_params.h", "mtm_templates.hip.h",
            "mtm_bf16.hip.h", "mtm_bf16_params.h", "mtm_refine.hip.h", "mtm_mfma_step_asm.inc", "mtm_kernels.h", "mtm_internal.h",
            "mtm_k_nms.hip.h", "mtm_nms_core.h", "mtm_peak_sizing.h", "mtm_k_window.hip.h", "mtm_k_nbhd.hip.h", "mtm_route.h", "mtm_templ_stats.h",
            os.path.join("..", "..", "include", "mtm_hip.h")]

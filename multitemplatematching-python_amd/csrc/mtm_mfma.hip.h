@@ -26,6 +26,16 @@
 //   * epilogue: accumulators go through LDS (transposed) so that consecutive lanes own consecutive
 //     output columns - coalesced statistics loads and score-map stores - then the float64
 //     normalisation shared with the other kernels (finish_unmasked).
+//
+// Layout.  This header: the instantiation's configuration (MfCfg), the work item (MfItem, mf_item_live, mf_item_decode) and
+// the __global__ template.  mtm_mfma_kloop.hip.h: the K step, the operand macros of the three K loops, tile staging
+// (mf_stage_tile) and the packed-K and plain / row-multiplexed loops (mf_kloop_kp, mf_kloop_plain).
+// mtm_mfma_finish.hip.h: the float64 normalisations.  Every piece is a __forceinline__ template on the configuration: an
+// instantiation is still ONE function to the register allocator, exactly as when it was one body.
+// Still in the kernel's body, because as functions they changed the code of some instantiation (register counts, LDS reads;
+// profiles/mfma_split/summary.txt): the per-template constants, the statistics prefetch, the two-row K loop with its tail
+// screen, and the epilogue - six families in one `if constexpr` chain, joined by the [&] lambdas put / emit_at /
+// ext_update / store4.
 #pragma once
 #include "mtm_device_util.hip.h"
 #include "mtm_mfma_params.h"
@@ -40,256 +50,6 @@ __device__ __forceinline__ int mf_opaque_sgpr(int v) {
     asm volatile("" : "+s"(v));
     return v;
 }
-// finish_unmasked on values already in registers (same arithmetic, same order).  METHOD >= 0 fixes
-// the matching method at compile time: the per-output code is then branch-free apart from the
-// data-dependent normalisation cases (the runtime-method version spends most of its time in
-// wave-uniform scalar branches).
-template <int METHOD>
-__device__ __forceinline__ float finish_vals(int method_rt, double corr, const double (&t)[kMaxChans], double sum2,
-                                             double sq, const MfTemplConst& T, int chans) {
-    const int method = METHOD >= 0 ? METHOD : method_rt;
-    if (T.all_ones) return 1.0f;
-    if (method == MTM_TM_CCORR) return (float)corr;
-    const int num_type = (method == MTM_TM_CCORR_NORMED) ? 0
-                       : (method == MTM_TM_CCOEFF || method == MTM_TM_CCOEFF_NORMED) ? 1 : 2;
-    const bool normed = (method == MTM_TM_SQDIFF_NORMED) || (method == MTM_TM_CCORR_NORMED) ||
-                        (method == MTM_TM_CCOEFF_NORMED);
-    double num = corr;
-    if (num_type == 1) {
-#pragma unroll
-        for (int c = 0; c < kMaxChans; ++c)
-            if (c < chans) num -= t[c] * T.mean[c];
-    } else if (num_type == 2) {
-        num = sum2 - 2.0 * num + T.templ_sum2;
-        num = fmax(num, 0.0);
-    }
-    if (normed) {
-        const double tt = sq * T.templ_norm;
-        const double an = fabs(num);
-        const double other = (method == MTM_TM_SQDIFF_NORMED) ? 1.0 : 0.0;
-        const double sat = (an < tt * 1.125) ? ((num > 0.0) ? 1.0 : -1.0) : other;
-        num = (an < tt) ? num / tt : sat;
-    }
-    return (float)num;
-}
-
-// Lean single-channel epilogue with the method fixed at compile time.  Same quantities and the same
-// case analysis as finish_unmasked / OpenCV's common_matchTemplate; the exact integer correlation is
-// rebuilt from the biased MFMA accumulator (a32 + 128*S1 + K, all exact in float64).  EXACT_DIV keeps
-// the IEEE division num / t (bit-identical to the other kernels and to the oracle); otherwise the
-// quotient is num * (1/sq) * (1/templ_norm) with both reciprocals correctly rounded: <= 2 ulp(double)
-// from the exact quotient, i.e. the float32 result differs in the last bit for ~1e-8 of the pixels.
-template <int METHOD, bool EXACT_DIV>
-__device__ __forceinline__ float finish_lean(int a32, double s1, double p1, double sum2, double sq, double rsq,
-                                             const MfTemplConst& T) {
-    constexpr bool normed = METHOD == MTM_TM_SQDIFF_NORMED || METHOD == MTM_TM_CCORR_NORMED ||
-                            METHOD == MTM_TM_CCOEFF_NORMED;
-    const double corr = (double)a32 + (p1 + T.mfma_k);
-    double num = corr;
-    if (METHOD == MTM_TM_CCOEFF || METHOD == MTM_TM_CCOEFF_NORMED) num = corr - s1 * T.mean[0];
-    if (METHOD == MTM_TM_SQDIFF || METHOD == MTM_TM_SQDIFF_NORMED) num = fmax(sum2 - 2.0 * corr + T.templ_sum2, 0.0);
-    if (!normed) return (float)num;
-    const double tt = sq * T.templ_norm;
-    const double an = fabs(num);
-    const float qf = EXACT_DIV ? (float)(num / tt) : (float)(num * (rsq * T.rtempl_norm));
-    const float satf = (num > 0.0) ? 1.0f : -1.0f;
-    const float other = (METHOD == MTM_TM_SQDIFF_NORMED) ? 1.0f : 0.0f;
-    return (an < tt) ? qf : ((an < tt * 1.125) ? satf : other);
-}
-
-// (quotient_as_float: mtm_device_util.hip.h)
-// finish_lean with the quotient computed unconditionally (the empty asm keeps the compiler from
-// sinking it into a divergent branch): straight-line code, the four pixels of a lane interleave.
-// Same operations in the same order as finish_lean: bit-identical results.
-// DEFER (IEEE-division builds, one channel): the quotient is quotient_as_float's reciprocal product and *redo says whether
-// it sits next to a float32 rounding boundary - the caller repeats those through the division behind ONE wave-uniform
-// branch for the lane's four pixels (as a per-lane `if` the compiler turned the division into a select and computed both).
-template <int METHOD, bool EXACT_DIV, int CH = 1, bool DEFER = false>
-__device__ __forceinline__ float finish_fast(int a32, const double (&s1)[CH], double p1, double sum2, double sq,
-                                             double rsq, const MfTemplConst& T, bool* redo = nullptr, bool* sat = nullptr) {
-    constexpr bool normed = METHOD == MTM_TM_SQDIFF_NORMED || METHOD == MTM_TM_CCORR_NORMED ||
-                            METHOD == MTM_TM_CCOEFF_NORMED;
-    if constexpr (!EXACT_DIV && (METHOD == MTM_TM_CCORR_NORMED || METHOD == MTM_TM_CCOEFF_NORMED)) {
-        // Default (reciprocal) mode of the two north-star methods: 5-6 float64 operations per output.
-        //   num = a32 + K + 128 S1 [- mean S1]  as one fma on the biased accumulator,
-        //   q   = num * (1/sq) * (1/templ_norm)   (both reciprocals correctly rounded; 0 for a flat
-        //         window or a constant template, which yields the 0 OpenCV returns for t == 0),
-        //   |q| < 1 -> q,  |q| < 1.125 -> +-1,  else 0: the case analysis of common_matchTemplate
-        //   evaluated on the float32 quotient (it only differs from the float64 comparison when q is
-        //   within one float64 rounding of 1.125; at 1 both give +-1.0f).
-        double num = (double)a32 + T.mfma_k;
-#pragma unroll
-        for (int cc = 0; cc < CH; ++cc) num = fma(s1[cc], METHOD == MTM_TM_CCOEFF_NORMED ? T.m128[cc] : 128.0, num);
-        const float qf = (float)(num * (rsq * T.rtempl_norm));
-        const float aq = fabsf(qf);
-        const float sat = (aq < 1.125f) ? copysignf(1.0f, qf) : 0.0f;
-        return (aq < 1.0f) ? qf : sat;
-    }
-    const double corr = (double)a32 + (p1 + T.mfma_k);
-    double num = corr;
-    if (METHOD == MTM_TM_CCOEFF || METHOD == MTM_TM_CCOEFF_NORMED) {
-#pragma unroll
-        for (int cc = 0; cc < CH; ++cc) num -= s1[cc] * T.mean[cc];      // same order as finish_unmasked
-    }
-    if (METHOD == MTM_TM_SQDIFF || METHOD == MTM_TM_SQDIFF_NORMED) num = fmax(sum2 - 2.0 * corr + T.templ_sum2, 0.0);
-    if (!normed) return (float)num;
-    const double tt = sq * T.templ_norm;
-    // (IEEE-division builds of the normalised methods defer; three channels with the function's general form - 16-44 B more
-    // scratch in eight of those instantiations, RGB map-mode kernel 2.83 -> 2.68 ms at 4K x 32)
-    float qf;
-    if constexpr (EXACT_DIV && DEFER) {
-        // |num| >= t (a flat window, a saturated quotient: the rules' constants, finish_saturated) is the caller's second
-        // wave-uniform branch - the comparison with 1.125 t and the selects leave the common path as well
-        const double q0 = num * (rsq * T.rtempl_norm);
-        *redo = quotient_needs_division<(CH > 1)>(q0);   // (one channel: no tiny quotients from these operands, mtm_device_util.hip.h)
-        *sat = !(fabs(num) < tt);
-        return (float)q0;
-    } else {
-        qf = EXACT_DIV ? (float)(num / tt) : (float)(num * (rsq * T.rtempl_norm));
-    }
-    asm volatile("" : "+v"(qf));
-    const double an = fabs(num);
-    const float satf = (num > 0.0) ? 1.0f : -1.0f;
-    const float other = (METHOD == MTM_TM_SQDIFF_NORMED) ? 1.0f : 0.0f;
-    const float r2 = (an < tt * 1.125) ? satf : other;
-    return (an < tt) ? qf : r2;
-}
-
-// What finish_fast returns where |num| >= t (same quantities, same order): +-1 below 1.125 t, else the rules' constant.
-template <int METHOD, int CH = 1>
-__device__ __forceinline__ float finish_saturated(int a32, const double (&s1)[CH], double p1, double sum2, double sq,
-                                                  const MfTemplConst& T) {
-    const double corr = (double)a32 + (p1 + T.mfma_k);
-    double num = corr;
-    if (METHOD == MTM_TM_CCOEFF || METHOD == MTM_TM_CCOEFF_NORMED) {
-#pragma unroll
-        for (int cc = 0; cc < CH; ++cc) num -= s1[cc] * T.mean[cc];
-    }
-    if (METHOD == MTM_TM_SQDIFF || METHOD == MTM_TM_SQDIFF_NORMED) num = fmax(sum2 - 2.0 * corr + T.templ_sum2, 0.0);
-    const double tt = sq * T.templ_norm;
-    const float satf = (num > 0.0) ? 1.0f : -1.0f;
-    const float other = (METHOD == MTM_TM_SQDIFF_NORMED) ? 1.0f : 0.0f;
-    return (fabs(num) < tt * 1.125) ? satf : other;
-}
-
-// finish_lean with the method chosen at run time (one channel): `corr` is the exact correlation.
-template <bool EXACT_DIV>
-__device__ __forceinline__ float finish_rt(int method, double corr, double s1, double sum2, double sq, double rsq,
-                                           const MfTemplConst& T) {
-    const bool normed = method == MTM_TM_SQDIFF_NORMED || method == MTM_TM_CCORR_NORMED || method == MTM_TM_CCOEFF_NORMED;
-    double num = corr;
-    if (method == MTM_TM_CCOEFF || method == MTM_TM_CCOEFF_NORMED) num = corr - s1 * T.mean[0];
-    if (method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED) num = fmax(sum2 - 2.0 * corr + T.templ_sum2, 0.0);
-    if (!normed) return (float)num;
-    const double tt = sq * T.templ_norm;
-    float qf = EXACT_DIV ? (float)(num / tt) : (float)(num * (rsq * T.rtempl_norm));
-    asm volatile("" : "+v"(qf));
-    const double an = fabs(num);
-    const float satf = (num > 0.0) ? 1.0f : -1.0f;
-    const float other = (method == MTM_TM_SQDIFF_NORMED) ? 1.0f : 0.0f;
-    const float r2 = (an < tt * 1.125) ? satf : other;
-    return (an < tt) ? qf : r2;
-}
-
-// Masked templates (OpenCV's matchTemplateMask, binary uint8 mask, reference MTM/__init__.py:78,:216):
-// c1 = sum I*(T*M) comes from the MFMA accumulator exactly like an unmasked correlation (the packed
-// template is T*M), c2 = sum I^2*M from the class's raw row-multiplexed pass (MfmaParams::sq_fused; MTM_ROW_MUX=0: the MASKSQ dot4 pass).  No guards, as in OpenCV: 0/0 is NaN.
-// DEFER (IEEE builds, round 6): the float32 value of num / sqrt(tms c2) from num * (RN(1 / sqrt(c2)) * RN(1 / sqrt(tms))) - six
-// roundings against the reference's three, <= 9 ulp(double) apart - with quotient_needs_division's general form; a quotient
-// that is not finite (c2 == 0: inf or the 0 / 0 NaN of OpenCV) takes the reference sequence as well, so that even the NaN's bits
-// are the division's.  *redo: the caller repeats those behind one wave-uniform branch (see finish_fast).
-template <int METHOD, bool EXACT_DIV, bool DEFER = false>
-__device__ __forceinline__ float finish_lean_masked(int a32, double p1, double c2, double rsqrt_c2,
-                                                    const MfTemplConst& T, bool* redo = nullptr) {
-    const double c1 = (double)a32 + (p1 + T.mfma_k);
-    if (METHOD == MTM_TM_CCORR) return (float)c1;
-    if (METHOD == MTM_TM_SQDIFF) return (float)(-2.0 * c1 + c2 + T.tms);
-    const double num = (METHOD == MTM_TM_SQDIFF_NORMED) ? (-2.0 * c1 + c2 + T.tms) : c1;
-    if constexpr (EXACT_DIV && DEFER) {
-        const double q0 = num * (rsqrt_c2 * T.rsqrt_tms);
-        const bool finite = ((uint32_t)__double2hiint(q0) & 0x7ff00000u) != 0x7ff00000u;
-        *redo = quotient_needs_division<true>(q0) || !finite;
-        return (float)q0;
-    }
-    return EXACT_DIV ? (float)(num / sqrt(T.tms * c2)) : (float)(num * (rsqrt_c2 * T.rsqrt_tms));
-}
-
-// One K step: 16 phases x MB template groups, operands already in registers.
-template <int MB>
-__device__ __forceinline__ void mfma_step(v4i (&acc)[MB][16], const v4i qa, const v4i qb, const v4i (&a)[MB]) {
-    const int W[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-    // phases with a whole-dword shift: no VALU work
-#pragma unroll
-    for (int cq = 0; cq < 4; ++cq) {
-        const v4i bv = {W[cq], W[cq + 1], W[cq + 2], W[cq + 3]};
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-            acc[mb][4 * cq] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[mb], bv, acc[mb][4 * cq], 0, 0, 0);
-    }
-    // byte shifts 1..3: 7 v_alignbyte_b32 serve four phases each
-#pragma unroll
-    for (int cr = 1; cr < 4; ++cr) {
-        int E[7];
-#pragma unroll
-        for (int m = 0; m < 7; ++m) E[m] = (int)__builtin_amdgcn_alignbyte((uint32_t)W[m + 1], (uint32_t)W[m], cr);
-#pragma unroll
-        for (int cq = 0; cq < 4; ++cq) {
-            const v4i bv = {E[cq], E[cq + 1], E[cq + 2], E[cq + 3]};
-#pragma unroll
-            for (int mb = 0; mb < MB; ++mb)
-                acc[mb][4 * cq + cr] =
-                    __builtin_amdgcn_mfma_i32_16x16x64_i8(a[mb], bv, acc[mb][4 * cq + cr], 0, 0, 0);
-        }
-    }
-}
-
-#ifndef MTM_MFMA_NO_ASM
-#include "mtm_mfma_step_asm.inc"
-#else
-__device__ __forceinline__ void mfma_step_one_set(v4i (&acc)[2][16], const v4i qa, const v4i qb, const v4i (&a)[2]) {
-    mfma_step<2>(acc, qa, qb, a);
-}
-#endif
-// The K step of two MFMA groups.  MTM_STEP_VARIANT (build-time experiment switch): 2 = the whole step as ONE asm
-// statement with the odd-offset windows computed from the operand (default; 44 VALU), 1 = one statement with the odd-offset
-// windows copied from the even ones (47 VALU), 0 = round 2's four statements.  Measured on one box, 4K x 32 templates,
-// kernel per step banded / single launch (profiles/r04a/lib_ab.txt): 0: 0.6636 / 0.6262 ms at 1943 / 2036 MHz,
-// 1: 0.6499 / 0.6131 at 1893 / 1982, 2: 0.6490 / 0.6116 at 1873 / 1967 - 6 % fewer cycles, 2.3 % less time (the chip
-// clocks to its power budget); register-only step: 17.4 -> 16.2 cycles per MFMA (tools/ubench/step).
-#ifndef MTM_STEP_VARIANT
-#define MTM_STEP_VARIANT 2
-#endif
-__device__ __forceinline__ void mfma_step2(v4i (&acc)[2][16], const v4i qa, const v4i qb, const v4i (&a)[2]) {
-#if defined(MTM_MFMA_NO_ASM) || MTM_STEP_VARIANT == 0
-    mfma_step<2>(acc, qa, qb, a);
-#elif MTM_STEP_VARIANT == 2
-    mfma_step2_fused_b(acc, qa, qb, a);
-#else
-    mfma_step2_fused(acc, qa, qb, a);
-#endif
-}
-// The K step of the row-multiplexed tilings: both groups, or - edge steps, see the generic K loop - only one of them
-// (mode 1: group 0, 2: group 1).  One asm statement with three paths (tools/gen_mfma_step.py says why).
-__device__ __forceinline__ void mfma_step2_rm(v4i (&acc)[2][16], const v4i qa, const v4i qb, const v4i (&a)[2], const int mode) {
-#if defined(MTM_MFMA_NO_ASM) || MTM_STEP_VARIANT == 0
-    if (mode == 0) {
-        mfma_step<2>(acc, qa, qb, a);
-    } else {
-        v4i (&acc1)[1][16] = reinterpret_cast<v4i (&)[1][16]>(acc[mode - 1]);
-        const v4i a1[1] = {a[mode - 1]};
-        mfma_step<1>(acc1, qa, qb, a1);
-    }
-#else
-    mfma_step2_edges(acc, qa, qb, a, mode);
-#endif
-}
-// the K step of an instantiation: the uint16 kernel (three accumulator sets) takes the one-scratch-set form
-template <int METHOD_, int MB>
-__device__ __forceinline__ void mfma_kstep(v4i (&acc)[MB][16], const v4i qa, const v4i qb, const v4i (&a)[MB]) {
-    if constexpr (METHOD_ == 7 && MB == 2) mfma_step_one_set(acc, qa, qb, a);       // kMfU16
-    else if constexpr (MB == 2) mfma_step2(acc, qa, qb, a);
-    else mfma_step<MB>(acc, qa, qb, a);
-}
 
 // METHOD >= 0: single-channel image, method fixed at compile time.  METHOD < 0: generic (any channel
 // count, runtime method).
@@ -299,13 +59,11 @@ __device__ __forceinline__ void mfma_kstep(v4i (&acc)[MB][16], const v4i qa, con
 // is the one the first group used one step earlier: it stays in registers.  A K step then needs ONE 1 KiB template
 // load instead of two (the B operand and its byte shifts were shared already); a wave walks h + 1 image rows (the
 // first / last step use a zero operand for one of the rows) and a work-group covers 8 output rows.
-template <int MB, int METHOD, bool EXACT_DIV, bool MASKED = false, bool RM = false, int CH = 1, bool EXT = false,
-          bool R2 = false, bool KP = false>
-__global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const TemplDev* __restrict__ td,
-                                                          const int* __restrict__ tlist,
-                                                          const uint8_t* __restrict__ apack,
-                                                          StatPlanes st, float* __restrict__ maps) {
-    constexpr bool C1 = METHOD >= 0;         // compile-time method: CH (1 or 3) channels, lean epilogue
+template <int MB_, int METHOD_, bool EXACT_DIV_, bool MASKED_, bool RM_, int CH_, bool EXT_, bool R2_, bool KP_>
+struct MfCfg {
+    static constexpr int MB = MB_, METHOD = METHOD_, CH = CH_;
+    static constexpr bool EXACT_DIV = EXACT_DIV_, MASKED = MASKED_, RM = RM_, EXT = EXT_, R2 = R2_, KP = KP_;
+    static constexpr bool C1 = METHOD >= 0;         // compile-time method: CH (1 or 3) channels, lean epilogue
     static_assert(CH == 1 || !MASKED, "multi-channel: unmasked paths only");
     static_assert(!EXT || (METHOD >= 0 && METHOD != kMfRaw), "fused extremum: compile-time-method paths");
     static_assert(METHOD != kMfU16 || (MB == 2 && !MASKED && !RM && CH == 1 && !R2), "uint16 finishing pass");
@@ -316,6 +74,80 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
     // cycles, 2.4 % less clock, no gain, and the only uint8 instantiations with hundreds of bytes of spills; removed in round 6)
     static_assert(!R2 || (MB == 2 && METHOD >= 2 && METHOD <= 5 && !MASKED && !RM && CH == 1), "two-row variant");
     static_assert(MB <= 2, "at most two MFMA groups per wave");
+    static constexpr int kTG = R2 ? 16 : 16 * MB;              // templates per work item
+    static constexpr int kTGc = METHOD == kMfU16 ? 16 : kTG;   // templates with constants (uint16: both groups are the same 16)
+    static constexpr bool kNeedSum2 = MASKED || METHOD == MTM_TM_SQDIFF || METHOD == MTM_TM_SQDIFF_NORMED;
+    static constexpr bool kNormed = !MASKED && (METHOD == MTM_TM_SQDIFF_NORMED || METHOD == MTM_TM_CCORR_NORMED ||
+                                                METHOD == MTM_TM_CCOEFF_NORMED);
+    static constexpr bool kMaskedNormed = MASKED && (METHOD == MTM_TM_SQDIFF_NORMED || METHOD == MTM_TM_CCORR_NORMED);
+    static constexpr int kChunk = R2 ? kMfChunkR2 : kMfChunkH;
+    static constexpr bool kRmEdges = RM && MB == 2 && METHOD != kMfU16;     // (see mf_kloop_plain)
+};
+
+// One work item: which template group, which 256-pixel segment, which block of rows - and, with several slabs in one launch
+// (MfmaParams::n_slab), which slab: where its image window, A pack and raw maps are.
+struct MfItem {
+    int tg, seg, yb, x0, y0;
+    int wave_rows;              // output rows per wave = tile-row stride between waves
+    long long slab_img, slab_ap, slab_raw;
+};
+
+}  // namespace mtm
+
+#include "mtm_mfma_kloop.hip.h"
+#include "mtm_mfma_finish.hip.h"
+
+namespace mtm {
+
+// Is there an item for this work-group, and is it still worth computing?
+template <class Cfg>
+__device__ __forceinline__ bool mf_item_live(const MfmaParams& p, int wid, int* s_item) {
+    if (wid >= p.n_work) return false;
+    if (!Cfg::EXT && Cfg::METHOD != kMfRaw && p.hits_only) {
+        // hits-only launch whose candidate list overflowed: the call will be repeated with the maps in memory
+        // (dense maps), nothing this launch still computes is used - leave (work-group-uniform decision)
+        if (threadIdx.x == 0)
+            s_item[2] = __hip_atomic_load(p.cand_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > p.cand_cap ? 1 : 0;
+        __syncthreads();
+        if (s_item[2]) return false;
+    }
+    return true;
+}
+
+template <class Cfg>
+__device__ __forceinline__ MfItem mf_item_decode(const MfmaParams& p, int wid) {
+    MfItem it;
+    it.tg = wid % p.ntg;
+    const int rest = wid / p.ntg;
+    it.seg = rest % p.nseg;
+    it.yb = rest / p.nseg;
+    // several slabs in one launch (MfmaParams::n_slab): which slab, where its image window, A pack and raw maps are
+    it.slab_img = 0, it.slab_ap = 0, it.slab_raw = 0;
+    if constexpr (Cfg::RM && Cfg::METHOD == kMfRaw && !Cfg::KP) {
+        if (p.n_slab > 1) {
+            const int k = it.yb / p.nyb;
+            it.yb -= k * p.nyb;
+            const int cb = k % p.slab_ncb, rbk = k / p.slab_ncb;
+            const int rb = rbk % p.slab_nrb, ch = rbk / p.slab_nrb;
+            it.slab_img = (long long)ch * p.plane + (long long)rb * p.slab_rh * p.pitch + (long long)cb * p.slab_cw;
+            it.slab_ap = (long long)k * p.slab_ap_step;
+            it.slab_raw = (long long)k * p.slab_raw_step;
+        }
+    }
+    it.x0 = it.seg * kMfSeg;
+    it.y0 = (it.yb + p.yb0) * (Cfg::RM ? 8 * p.rm_R : (Cfg::R2 ? Cfg::MB * kMfRows : kMfRows));
+    it.wave_rows = Cfg::RM ? 2 * p.rm_R : (Cfg::R2 ? Cfg::MB : 1);
+    return it;
+}
+
+template <int MB, int METHOD, bool EXACT_DIV, bool MASKED = false, bool RM = false, int CH = 1, bool EXT = false,
+          bool R2 = false, bool KP = false>
+__global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const TemplDev* __restrict__ td,
+                                                          const int* __restrict__ tlist,
+                                                          const uint8_t* __restrict__ apack,
+                                                          StatPlanes st, float* __restrict__ maps) {
+    using Cfg = MfCfg<MB, METHOD, EXACT_DIV, MASKED, RM, CH, EXT, R2, KP>;
+    constexpr bool C1 = Cfg::C1;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
     // One work item per work-group; the block index orders the items so that the rows of the image an XCD reads stay in
@@ -336,33 +168,10 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
     const int per_xcd = (p.n_work + 7) >> 3;
     do {        // (a scope to leave: `continue` / `break` below = this wave is done with the item)
     const int wid = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if (wid >= p.n_work) break;
-    if (!EXT && METHOD != kMfRaw && p.hits_only) {
-        // hits-only launch whose candidate list overflowed: the call will be repeated with the maps in memory
-        // (dense maps), nothing this launch still computes is used - leave (work-group-uniform decision)
-        if (threadIdx.x == 0)
-            s_item[2] = __hip_atomic_load(p.cand_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > p.cand_cap ? 1 : 0;
-        __syncthreads();
-        if (s_item[2]) break;
-    }
-    const int tg = wid % p.ntg;
-    const int rest = wid / p.ntg;
-    const int seg = rest % p.nseg;
-    int yb = rest / p.nseg;
-    // several slabs in one launch (MfmaParams::n_slab): which slab, where its image window, A pack and raw maps are
-    long long slab_img = 0, slab_ap = 0, slab_raw = 0;
-    if constexpr (RM && METHOD == kMfRaw && !KP) {
-        if (p.n_slab > 1) {
-            const int k = yb / p.nyb;
-            yb -= k * p.nyb;
-            const int cb = k % p.slab_ncb, rbk = k / p.slab_ncb;
-            const int rb = rbk % p.slab_nrb, ch = rbk / p.slab_nrb;
-            slab_img = (long long)ch * p.plane + (long long)rb * p.slab_rh * p.pitch + (long long)cb * p.slab_cw;
-            slab_ap = (long long)k * p.slab_ap_step;
-            slab_raw = (long long)k * p.slab_raw_step;
-        }
-    }
-    const int x0 = seg * kMfSeg, y0 = (yb + p.yb0) * (RM ? 8 * p.rm_R : (R2 ? MB * kMfRows : kMfRows));
+    if (!mf_item_live<Cfg>(p, wid, s_item)) break;
+    const MfItem it = mf_item_decode<Cfg>(p, wid);
+    const int tg = it.tg, x0 = it.x0, y0 = it.y0, wave_rows = it.wave_rows;      // (the body's names for them)
+    const long long slab_img = it.slab_img, slab_ap = it.slab_ap, slab_raw = it.slab_raw;
     // Lane coordinates of this work item, derived from an opaque copy of the thread index: whatever the prologue
     // computes from them is then computed HERE, per item, instead of once ahead of the item loop - where it stayed
     // live across the K loop (which owns every register) and was spilled to scratch memory.
@@ -370,8 +179,7 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
     asm volatile("" : "+v"(tid_i));
     const int wave = __builtin_amdgcn_readfirstlane(tid_i >> 6), lane = tid_i & 63;
     const int j = lane & 15, q = lane >> 4;
-    const int wave_rows = RM ? 2 * p.rm_R : (R2 ? MB : 1);   // output rows per wave = tile-row stride between waves
-    constexpr int kTG = R2 ? 16 : 16 * MB;              // templates per work item
+    constexpr int kTG = Cfg::kTG;
 
     v4i acc[MB][16];
 #pragma unroll
@@ -387,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
 
     // per-template constants -> LDS (read back in the epilogue; the staging barriers below order it)
     MfTemplConst* tcl = reinterpret_cast<MfTemplConst*>(smem + p.tc_off);
-    constexpr int kTGc = METHOD == kMfU16 ? 16 : kTG;   // templates with constants (uint16: both groups are the same 16)
+    constexpr int kTGc = Cfg::kTGc;
     if (METHOD != kMfRaw && tid_i < (RM ? p.rm_nt : kTGc)) {
         const int li = tg * kTGc + tid_i;
         if (li < p.n_list) {
@@ -476,10 +284,7 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
 
     // window statistics of this wave's 256 pixels -> LDS (LDS-DMA, no registers; drained by the
     // staging barriers below, read back in the epilogue).  Lane L fetches pixels 4L..4L+3.
-    constexpr bool kNeedSum2 = MASKED || METHOD == MTM_TM_SQDIFF || METHOD == MTM_TM_SQDIFF_NORMED;
-    constexpr bool kNormed = !MASKED && (METHOD == MTM_TM_SQDIFF_NORMED || METHOD == MTM_TM_CCORR_NORMED ||
-                                         METHOD == MTM_TM_CCOEFF_NORMED);
-    constexpr bool kMaskedNormed = MASKED && (METHOD == MTM_TM_SQDIFF_NORMED || METHOD == MTM_TM_CCORR_NORMED);
+    constexpr bool kNeedSum2 = Cfg::kNeedSum2, kNormed = Cfg::kNormed, kMaskedNormed = Cfg::kMaskedNormed;
     if constexpr (R2 && kNormed) {
         // MB rows per wave.  Only the hits-only screen's first level is on every item's path, and all it needs of the
         // statistics are their ranges over each 16-pixel column block (StatPlanes::blk, written by stats_u8_kernel:
@@ -555,38 +360,11 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
             }
         }
         const int krows = RM ? p.rm_steps : (R2 ? p.h + MB - 1 : p.h);        // image rows a wave walks (K steps / nb)
-        constexpr int kChunk = R2 ? kMfChunkR2 : kMfChunkH;
+        constexpr int kChunk = Cfg::kChunk;
         v4i r2_prev = v4i{0, 0, 0, 0};      // R2: the A operand of the previous step (the int8 zero before template row 0)
         for (int cy0 = 0; cy0 < krows; cy0 += kChunk) {
             const int ch = min(kChunk, krows - cy0);
-            // ---- stage (ch + 3) rows of the int8 image plane by LDS-DMA: the tile is one linear
-            // array of 16-byte chunks [row][cpr]; wave-instruction k of the work-group fills chunks
-            // 64 k .. 64 k + 63 (LDS destination = wave-uniform base + lane * 16), each lane
-            // supplying the global address of its chunk.  No registers, no VALU conversion.
-            __syncthreads();
-            {
-                typedef const __attribute__((address_space(1))) void* gptr_t;
-                typedef __attribute__((address_space(3))) void* lptr_t;
-                const int nchunk = (ch + (kMfRows - 1) * wave_rows) * p.cpr;
-                int ci = tid_i;
-                int r = (ci * p.cpr_magic) >> 16, d = ci - r * p.cpr;     // ci / cpr for ci < 256 (cpr <= 33), without a division
-                const uint8_t* grow = plane + (size_t)(y0 + cy0) * p.pitch + x0;
-                uint8_t* lbase_w = smem + wave * 1024;
-                for (; ci - lane < nchunk; ci += 256) {
-                    if (ci < nchunk)
-                        __builtin_amdgcn_global_load_lds((gptr_t)(grow + (size_t)r * p.pitch + 16 * d), (lptr_t)lbase_w,
-                                                         16, 0, 0);
-                    lbase_w += 4096;
-                    r += p.cpr_rstep;
-                    d += p.cpr_dstep;
-                    if (d >= p.cpr) {
-                        d -= p.cpr;
-                        ++r;
-                    }
-                }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            __syncthreads();
+            mf_stage_tile<Cfg>(p, smem, plane, it, cy0, ch, tid_i, wave, lane);
             if constexpr (R2) {
                 // ---- K loop of the two-row variant (nb == 1: one step per image row).  B operands alternate between
                 // two register sets, A operands rotate through three (this step's, the previous step's - the second
@@ -598,35 +376,6 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
                 int loff = 0;
                 v4i qx, qy, qx2, qy2, aA, aB, aC = r2_prev;
                 if (mf_opaque_sgpr(p.hits_only)) __builtin_amdgcn_s_setprio(3);
-#define MTM_R2_LOAD(QA, QB, A)                                              \
-                QA = *reinterpret_cast<const v4i*>(lbase + loff);           \
-                QB = *reinterpret_cast<const v4i*>(lbase + loff + 16);      \
-                A = *reinterpret_cast<const v4i*>(aptr);
-#define MTM_R2_STEP(QA, QB, ACUR, APREV, QA2, QB2, ANEXT)                   \
-                {                                                           \
-                    aptr += 1024;                                           \
-                    loff += p.lds_pitch;                                    \
-                    MTM_R2_LOAD(QA2, QB2, ANEXT)                            \
-                    __builtin_amdgcn_sched_barrier(0);                      \
-                    const v4i ar_[2] = {ACUR, APREV};                       \
-                    mfma_step2(acc, QA, QB, ar_);                           \
-                    __builtin_amdgcn_sched_barrier(0);                      \
-                }
-#define MTM_R2_STEP_LAST(QA, QB, ACUR, APREV)                               \
-                {                                                           \
-                    aptr += 1024;                                           \
-                    loff += p.lds_pitch;                                    \
-                    __builtin_amdgcn_sched_barrier(0);                      \
-                    const v4i ar_[2] = {ACUR, APREV};                       \
-                    mfma_step2(acc, QA, QB, ar_);                           \
-                    __builtin_amdgcn_sched_barrier(0);                      \
-                }
-#define MTM_R2_FIVE()                                                        \
-                MTM_R2_STEP(qx, qy, aA, aC, qx2, qy2, aB)                   \
-                MTM_R2_STEP(qx2, qy2, aB, aA, qx, qy, aC)                   \
-                MTM_R2_STEP(qx, qy, aC, aB, qx2, qy2, aA)                   \
-                MTM_R2_STEP(qx2, qy2, aA, aC, qx, qy, aB)                   \
-                MTM_R2_STEP(qx, qy, aB, aA, qx2, qy2, aC)
                 MTM_R2_LOAD(qx, qy, aA)           // step 0 of the chunk; aC = the step before it
                 int ks = 0;
                 // Tail screen (hits-only, one chunk: MfmaParams::tail_split, any number of steps >= 1; the launcher gives 6 .. h - 2).  After s = tail_split steps
@@ -714,139 +463,13 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
                     if (ks + 3 < ch) { MTM_R2_STEP(qx2, qy2, aA, aC, qx, qy, aB) r2_prev = aA; }
                     if (ks + 4 < ch) { MTM_R2_STEP(qx, qy, aB, aA, qx2, qy2, aC) r2_prev = aB; }
                 }
-#undef MTM_R2_LOAD
-#undef MTM_R2_STEP
-#undef MTM_R2_STEP_LAST
-#undef MTM_R2_FIVE
                 asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
                 __builtin_amdgcn_s_setprio(0);
             } else if constexpr (KP) {
-            // ---- K loop over the segment stream (packed K, see MfmaParams): as below, but every lane group q walks
-            // its own (row, segment) position - five VALU instructions of bookkeeping per step instead of scalar ones
-            const int nseg = p.kp_nseg;
-            const uint8_t* aptr = apack_g + (RM ? (size_t)cpk * p.rm_cstride : (size_t)cpk * p.kp_blocks * 1024) +
-                                  (size_t)((cy0 * nseg) >> 2) * 1024;           // cy0 is a multiple of 64
-            const uint8_t* lbase = smem + wave * wave_rows * p.lds_pitch + j * 16;
-            const int nsteps = (ch * nseg + 3) >> 2;
-            const int drow = 4 / nseg, dseg = 4 - drow * nseg;                 // uniform: stream advance of one step
-            const int adv = drow * p.lds_pitch + dseg * 16, wrapfix = p.lds_pitch - nseg * 16;
-            int seg = q % nseg;                                                 // this lane group's segment of step 0
-            int loff = (q / nseg) * p.lds_pitch + seg * 16;
-            v4i qa0, qb0, qa1, qb1, a0[MB], a1[MB];
-#define MTM_KP_ADVANCE()                                            \
-            {                                                       \
-                aptr += 1024;                                       \
-                seg += dseg;                                        \
-                const bool wrap_ = seg >= nseg;                     \
-                seg -= wrap_ ? nseg : 0;                            \
-                loff += adv + (wrap_ ? wrapfix : 0);                \
-            }
-#define MTM_KP_LOAD(QA, QB, A)                                                          \
-            QA = *reinterpret_cast<const v4i*>(lbase + loff);                           \
-            QB = *reinterpret_cast<const v4i*>(lbase + loff + 16);                      \
-            _Pragma("unroll") for (int mb = 0; mb < MB; ++mb)                           \
-                A[mb] = *reinterpret_cast<const v4i*>(aptr + mb * p.group_bytes);
-            if (mf_opaque_sgpr(p.hits_only)) __builtin_amdgcn_s_setprio(3);
-            MTM_KP_LOAD(qa0, qb0, a0)            // step 0
-            int ks = 0;
-            for (; ks + 2 <= nsteps; ks += 2) {
-                MTM_KP_ADVANCE()
-                MTM_KP_LOAD(qa1, qb1, a1)
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_kstep<METHOD, MB>(acc, qa0, qb0, a0);
-                __builtin_amdgcn_sched_barrier(0);
-                MTM_KP_ADVANCE()
-                MTM_KP_LOAD(qa0, qb0, a0)
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_kstep<METHOD, MB>(acc, qa1, qb1, a1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (ks < nsteps) {
-                mfma_kstep<METHOD, MB>(acc, qa0, qb0, a0);
-            }
-#undef MTM_KP_ADVANCE
-#undef MTM_KP_LOAD
-            asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-            __builtin_amdgcn_s_setprio(0);
+                mf_kloop_kp<Cfg>(p, acc, smem, it, apack_g, cpk, cy0, ch, wave, j, q);
             } else {
-            // ---- K loop: template rows of this chunk x 64-tap blocks, software pipelined with two
-            // register sets: the operands of the next step (2 LDS chunks + MB packed template rows)
-            // are requested before the 16*MB MFMAs of the current step issue.  sched_barrier keeps
-            // the compiler from sinking the requests below the MFMAs.
-            const uint8_t* aptr = apack_g + (RM ? (size_t)cpk * p.rm_cstride + (size_t)cy0 * p.nb * 1024     // + ks * 1024
-                                               : ((size_t)(cpk * p.h + cy0) * p.nb) * 1024);
-            const uint8_t* lbase = smem + wave * wave_rows * p.lds_pitch + (j + q) * 16;
-            const int nsteps = ch * p.nb;
-            int nb_i = 0;                       // 64-tap block of the step last requested
-            int loff = 0;                       // its LDS offset: dy * lds_pitch + b * 64
-            const int row_adv = p.lds_pitch - (p.nb - 1) * 64;
-            v4i qa0, qb0, qa1, qb1, a0[MB], a1[MB];
-            // The loop body is branch-free: the bookkeeping of the next step is scalar selects, and the
-            // requests run up to two steps past the end of the chunk (the pack arena has slack, LDS reads
-            // past the tile stay inside the allocation; nothing of it is used).  Taken scalar branches
-            // cost more than the loads they would save.
-#define MTM_MF_ADVANCE()                                            \
-            {                                                       \
-                MTM_MF_APTR_STEP                                    \
-                const bool wrap_ = nb_i + 1 == p.nb;                \
-                loff += wrap_ ? row_adv : 64;                       \
-                nb_i = wrap_ ? 0 : nb_i + 1;                        \
+                mf_kloop_plain<Cfg>(p, acc, smem, it, apack_g, cpk, cy0, ch, wave, j, q);
             }
-#define MTM_MF_APTR_STEP aptr += 1024;
-#define MTM_MF_LOAD(QA, QB, A)                                                          \
-            QA = *reinterpret_cast<const v4i*>(lbase + loff);                           \
-            QB = *reinterpret_cast<const v4i*>(lbase + loff + 16);                      \
-            _Pragma("unroll") for (int mb = 0; mb < MB; ++mb)                           \
-                A[mb] = *reinterpret_cast<const v4i*>(aptr + mb * p.group_bytes);
-#define MTM_MF_LOAD_LOOP(QA, QB, A) MTM_MF_LOAD(QA, QB, A)
-            // Row-multiplexed tilings (round 4): a wave's two MFMA groups are output rows [0, R) and [R, 2 R) of the same
-            // templates, and image row s of the wave's h + 2 R - 1 holds template rows of group 0 only for s < h + R - 1 and
-            // of group 1 only for s >= R - outside, the group's A operand is all zero.  Those edge steps run the
-            // one-group step (16 MFMAs instead of 32): 2 R of the h + 2 R - 1 steps, i.e. for ONE template or mask
-            // (R = 16, h = 64) 79 step-equivalents instead of 95.
-            constexpr bool kRmEdges = RM && MB == 2 && METHOD != kMfU16;
-            int srow = cy0, sblk = 0;                       // image row / 64-tap block of the step being executed
-            const int edge_lo = RM ? p.rm_R : 0, edge_hi = RM ? p.h + p.rm_R - 1 : 0x7fffffff;
-#define MTM_MF_STEP(QA, QB, A, K)                                                       \
-            if constexpr (kRmEdges) {                                                   \
-                const int mode_ = srow < edge_lo ? 1 : srow >= edge_hi ? 2 : 0; \
-                mfma_step2_rm(acc, QA, QB, A, __builtin_amdgcn_readfirstlane(mode_));   \
-                const bool last_ = sblk + 1 == p.nb;                                    \
-                srow += last_ ? 1 : 0;                                                  \
-                sblk = last_ ? 0 : sblk + 1;                                            \
-            } else {                                                                    \
-                mfma_kstep<METHOD, MB>(acc, QA, QB, A);                                 \
-            }
-            // hits-only launches: the MFMA main loop outranks the (short) epilogue of the co-resident work-group
-            // (-0.9 % kernel time; with the maps written the long epilogue is the one that must not starve: +1 %)
-            if (mf_opaque_sgpr(p.hits_only)) __builtin_amdgcn_s_setprio(3);
-            MTM_MF_LOAD(qa0, qb0, a0)            // step 0
-            int ks = 0;
-            for (; ks + 2 <= nsteps; ks += 2) {
-                MTM_MF_ADVANCE()
-                MTM_MF_LOAD_LOOP(qa1, qb1, a1)    // step ks + 1
-                __builtin_amdgcn_sched_barrier(0);
-                MTM_MF_STEP(qa0, qb0, a0, 0)
-                __builtin_amdgcn_sched_barrier(0);
-                MTM_MF_ADVANCE()
-                MTM_MF_LOAD_LOOP(qa0, qb0, a0)    // step ks + 2 (one past the end in the last iteration)
-                __builtin_amdgcn_sched_barrier(0);
-                MTM_MF_STEP(qa1, qb1, a1, 1)
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (ks < nsteps) {                    // odd number of steps: the last one is already in set 0
-                MTM_MF_STEP(qa0, qb0, a0, 0)
-            }
-#undef MTM_MF_ADVANCE
-#undef MTM_MF_APTR_STEP
-#undef MTM_MF_LOAD
-#undef MTM_MF_LOAD_LOOP
-#undef MTM_MF_STEP
-            // the last MFMAs may have been issued from inline asm: give their results time to land
-            // before compiler-generated code reads the accumulators (hipcc does not see asm MFMAs)
-            asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-            __builtin_amdgcn_s_setprio(0);
-            }   // !R2
         }
     }
 
@@ -1966,5 +1589,17 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
         if (dr > 0) *p.clk_out = (float)((double)dt * 100.0 / (double)dr);
     }
 }
+
+#undef MTM_R2_LOAD
+#undef MTM_R2_STEP
+#undef MTM_R2_STEP_LAST
+#undef MTM_R2_FIVE
+#undef MTM_KP_ADVANCE
+#undef MTM_KP_LOAD
+#undef MTM_MF_ADVANCE
+#undef MTM_MF_APTR_STEP
+#undef MTM_MF_LOAD
+#undef MTM_MF_LOAD_LOOP
+#undef MTM_MF_STEP
 
 }  // namespace mtm

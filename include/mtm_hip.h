@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -354,6 +354,45 @@ typedef struct mtm_window_stats {
     int64_t*       info;
 } mtm_window_stats;
 int         mtm_debug_window_stats(mtm_ctx* ctx, const mtm_window_stats* args);
+/* Test support (added under ABI 9; as above).  The window statistics on the six OTHER kernel chains the library chooses
+ * from (csrc/mtm_stats_route.h: stats_route), each through the launcher the search calls use: window h x w over the rows x
+ * cols x chans pixels of `image` (interleaved, tightly packed; dtype MTM_U8 / MTM_U16 / MTM_F32), num_type 0 / 1 / 2.
+ * route: 0 = the one stats_route gives this image and window (refused where that is the fused single-channel uint8 kernel:
+ * mtm_debug_window_stats), else MTM_STATS_ROUTE_*, forced - refused with MTM_E_INVALID where the route's kernels are not
+ * built for the image or window.  The two float64 routes take images of any dtype (they read the float32 plane).
+ * want: bits 1 = the window sums t, 2 = sum2, 4 = sq, 8 = blk (MTM_STATS_ROUTE_U16 only: the records per 16 output columns),
+ * 16 = hand the kernels NULL for the planes not wanted instead of a plane with its flag off.  The two-pass chains (routes
+ * 3 .. 6) write sum2 whatever is asked.  sb0, sb1: row units of 8 output rows as above - MTM_STATS_ROUTE_U16, and
+ * MTM_STATS_ROUTE_F64_LDS with lay_r1 > lay_r0: the launch of a band of a banded upload, row sums of image rows [lay_r0,
+ * lay_r1) only, then the windows of the units (sb0 * 8 a multiple of 32, lay_r0 <= sb0 * 8, lay_r1 >= the last window's
+ * last row + 1).  Everything lives in the buffer of mtm_debug_window_stats, filled with pattern_byte first; the image
+ * planes are laid out by the host as an upload leaves them (pitch = cols + 512 rounded up to 64, zero padding, 0x80 in the
+ * biased byte planes of a uint16 image); a call that would need more than 256 MB of it is refused.
+ * Results, each optional and copied back whether wanted or not (a plane that was not wanted holds pattern_byte): t0 .. t3,
+ * sum2, sq - st_pitch * oh doubles; blk - 4 * blk_pitch * oh doubles; info[12] = {the route that ran, st_pitch, blk_pitch,
+ * plane pitch, the first kernel's grid x, y, z, the second kernel's grid x, y (0: a fused route), the row sums' pitch, the
+ * first kernel's dynamic LDS bytes, the chain's time in nanoseconds between two events}. */
+#define MTM_STATS_ROUTE_U8         0
+#define MTM_STATS_ROUTE_U8MC       1
+#define MTM_STATS_ROUTE_U16        2
+#define MTM_STATS_ROUTE_U8_2P      3
+#define MTM_STATS_ROUTE_U8_2P_WIDE 4
+#define MTM_STATS_ROUTE_F64_LDS    5
+#define MTM_STATS_ROUTE_F64        6
+typedef struct mtm_window_stats_route {
+    int32_t        rows, cols, chans, dtype, h, w, num_type, route;
+    int32_t        want, sb0, sb1, lay_r0, lay_r1, pattern_byte;
+    const void*    image;
+    double*        t0;
+    double*        t1;
+    double*        t2;
+    double*        t3;
+    double*        sum2;
+    double*        sq;
+    double*        blk;
+    int64_t*       info;
+} mtm_window_stats_route;
+int         mtm_debug_window_stats_route(mtm_ctx* ctx, const mtm_window_stats_route* args);
 /* Page-locked host memory for pixel buffers (optional).  The reference's caller hands over whatever numpy holds
  * (MTM/__init__.py:247 `image`) - pageable memory, which the runtime stages through its own pinned buffers while the
  * upload call blocks.  An image kept in memory from mtm_host_alloc crosses PCIe as a plain DMA transfer behind the call

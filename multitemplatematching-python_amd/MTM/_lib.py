@@ -108,6 +108,24 @@ class MtmWindowStats(ctypes.Structure):
                 ("u8b", ctypes.c_void_p), ("header", ctypes.c_void_p), ("info", ctypes.c_void_p)]
 
 
+# mtm_debug_window_stats_route: the kernel chains of csrc/mtm_stats_route.h (MTM_STATS_ROUTE_*), the bits of `want` and the
+# argument block (mtm_window_stats_route)
+STATS_ROUTES = ("U8", "U8MC", "U16", "U8_2P", "U8_2P_WIDE", "F64_LDS", "F64")
+STATS_ROUTE_WANT = {"t": 1, "sum2": 2, "sq": 4, "blk": 8, "nulls": 16}
+STATS_ROUTE_INFO_FIELDS = ("route", "st_pitch", "blk_pitch", "pitch", "grid1_x", "grid1_y", "grid1_z", "grid2_x", "grid2_y",
+                           "hs_pitch", "lds_bytes", "kernel_ns")
+
+
+class MtmWindowStatsRoute(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("chans", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("num_type", ctypes.c_int32), ("route", ctypes.c_int32),
+                ("want", ctypes.c_int32), ("sb0", ctypes.c_int32), ("sb1", ctypes.c_int32), ("lay_r0", ctypes.c_int32),
+                ("lay_r1", ctypes.c_int32), ("pattern_byte", ctypes.c_int32),
+                ("image", ctypes.c_void_p), ("t0", ctypes.c_void_p), ("t1", ctypes.c_void_p), ("t2", ctypes.c_void_p),
+                ("t3", ctypes.c_void_p), ("sum2", ctypes.c_void_p), ("sq", ctypes.c_void_p), ("blk", ctypes.c_void_p),
+                ("info", ctypes.c_void_p)]
+
+
 # every symbol include/mtm_hip.h declares: (restype, argtypes)
 _P = ctypes.POINTER
 SYMBOLS = {
@@ -130,6 +148,7 @@ SYMBOLS = {
                                             _P(ctypes.c_int64)]),
     "mtm_debug_peak_pass": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_debug_window_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "mtm_debug_window_stats_route": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_set_image": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
     "mtm_set_image_downscaled": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -699,6 +718,44 @@ class Context(_RecordMemo):
         check(self._lib.mtm_debug_window_stats(self._h, ctypes.byref(a)), "mtm_debug_window_stats")
         out["info"] = dict(zip(STATS_INFO_FIELDS, (int(v) for v in info)))
         assert (out["info"]["st_pitch"], out["info"]["blk_pitch"], out["info"]["pitch"]) == (st_pitch, blk_pitch, pitch)
+        return out
+
+    def debug_window_stats_route(self, image, h, w, num_type, route=0, want=("t", "sum2", "sq"), units=None, rows_in=None,
+                                 pattern=0xA5):
+        """Test support (mtm_debug_window_stats_route): the window statistics of `image` ((rows, cols) or (rows, cols, chans);
+        uint8, uint16 or float32) on one of the kernel chains of STATS_ROUTES - route 0: the one the library's rule gives
+        it, else its index, forced.  want: which of t, sum2, sq, blk the kernels are asked for ("nulls": planes not wanted
+        are handed over as NULL); units: the (first, end) range of 8-row units (U16, or F64_LDS with rows_in: the (r0, r1)
+        image rows whose row sums the launch makes).  Every buffer starts out as the byte `pattern`.
+        -> dict: t (chans planes), sum2, sq ((oh, st_pitch) float64), blk ((oh, blk_pitch, 4)) - all of them, wanted or not -
+        and info (STATS_ROUTE_INFO_FIELDS)."""
+        image = np.ascontiguousarray(image)
+        code = _dtype_code(image)
+        assert image.ndim in (2, 3)
+        rows, cols = image.shape[:2]
+        chans = 1 if image.ndim == 2 else image.shape[2]
+        oh, ow = rows - h + 1, cols - w + 1
+        st_pitch = (ow + 3) // 4 * 4
+        blk_pitch = (st_pitch + 15) // 16
+        a = MtmWindowStatsRoute()
+        a.rows, a.cols, a.chans, a.dtype, a.h, a.w = rows, cols, chans, code, int(h), int(w)
+        a.num_type, a.route, a.pattern_byte = int(num_type), int(route), int(pattern)
+        a.want = sum(STATS_ROUTE_WANT[k] for k in want)
+        a.sb0, a.sb1 = (0, -1) if units is None else (int(units[0]), int(units[1]))
+        a.lay_r0, a.lay_r1 = (0, 0) if rows_in is None else (int(rows_in[0]), int(rows_in[1]))
+        a.image = image.ctypes.data
+        out = {"t": np.zeros((4, max(oh, 0), max(st_pitch, 0)), dtype=np.float64)}
+        for k in range(4):
+            setattr(a, "t%d" % k, out["t"][k].ctypes.data)
+        for name in ("sum2", "sq", "blk"):
+            shape = (max(oh, 0), max(blk_pitch, 0), 4) if name == "blk" else (max(oh, 0), max(st_pitch, 0))
+            out[name] = np.zeros(shape, dtype=np.float64)
+            setattr(a, name, out[name].ctypes.data)
+        info = np.zeros(len(STATS_ROUTE_INFO_FIELDS), dtype=np.int64)
+        a.info = info.ctypes.data
+        check(self._lib.mtm_debug_window_stats_route(self._h, ctypes.byref(a)), "mtm_debug_window_stats_route")
+        out["info"] = dict(zip(STATS_ROUTE_INFO_FIELDS, (int(v) for v in info)))
+        assert (out["info"]["st_pitch"], out["info"]["blk_pitch"]) == (st_pitch, blk_pitch)
         return out
 
     def set_image(self, image, downscale=1):

@@ -28,6 +28,7 @@
 #include "mtm_internal.h"
 #include "mtm_route.h"
 #include "mtm_peak_sizing.h"
+#include "mtm_stats_route.h"
 
 struct ncclComm;
 

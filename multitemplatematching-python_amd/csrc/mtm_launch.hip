@@ -294,6 +294,122 @@ int launch_stats_u8(hipStream_t stream, StatU8Args a, int form, int n_cus) {
     return MTM_OK;
 }
 
+// ---- one launcher per route of stats_route (mtm_stats_route.h) but the first, which launch_stats_u8 above is: a stream,
+// explicit device pointers and geometry, nothing of a context.  launch_stats, launch_masked_bf16 and the test-support entry
+// mtm_debug_window_stats_route all come through them.
+struct StatGeom {           // an h x w window over `chans` planes of rows x cols pixels
+    int rows, cols, chans, h, w, oh, ow;
+    double inv_area;
+};
+static StatGeom stat_geom(int rows, int cols, int chans, int h, int w) {
+    return StatGeom{rows, cols, chans, h, w, rows - h + 1, cols - w + 1, 1.0 / ((double)h * (double)w)};
+}
+struct StatScratch {        // the row sums between the two passes: `chans` planes of rows x pitch (uint32 or double) each
+    void* hs1;
+    void* hs2;
+    int pitch;
+    long long plane;
+};
+struct StatOut {            // the planes to write (st_pitch doubles a row, oh rows); a null plane goes with its flag off
+    int num_type = 0, want_sq = 0, want_t = 0, want_sum2 = 1;       // (the two-pass chains write sum2 whatever is asked)
+    double* t[kMaxChans] = {nullptr, nullptr, nullptr, nullptr};
+    long long t_plane = 0;  // the fused RGB kernel: doubles from t[0] to t[1] to t[2]
+    double* sum2 = nullptr;
+    double* sq = nullptr;
+    int st_pitch = 0;
+};
+
+// (every launcher: the planes' rows hold the output row - the fused kernels store whole quads)
+static int stat_out_check(const StatGeom& g, const StatOut& o) {
+    if (o.st_pitch >= g.ow && o.st_pitch % 4 == 0) return MTM_OK;
+    set_error("statistics launch: a plane pitch below the output width, or no multiple of 4");
+    return MTM_E_INVALID;
+}
+
+// U8MC: stats_u8_mc_kernel<3> over the three uint8 planes
+static int launch_stats_u8mc(hipStream_t stream, const uint8_t* u8, int pitch, long long plane, const StatGeom& g, const StatOut& o) {
+    MTMC(stat_out_check(g, o));
+    const int owg = stats_u8_owg(g.w);
+    const dim3 gs((g.ow + owg - 1) / owg, (g.oh + kStatBand4 - 1) / kStatBand4);
+    hipLaunchKernelGGL(stats_u8_mc_kernel<3>, gs, dim3(256), 0, stream, u8, pitch, plane, g.h, g.w, g.oh, g.ow, owg, g.inv_area,
+                       o.num_type, o.want_sq, o.want_t, o.want_sum2, o.t[0], o.t_plane, o.sum2, o.sq, o.st_pitch);
+    HIPC(hipGetLastError());
+    return MTM_OK;
+}
+
+// U16: stats_u16_kernel over the two biased byte planes, row units [sb0, sb1) of kStatBand4 output rows; blk: the records
+// per 16-column block (null: none)
+static int launch_stats_u16(hipStream_t stream, const uint8_t* hib, const uint8_t* lob, int pitch, const StatGeom& g,
+                            const StatOut& o, double* blk, int blk_pitch, int sb0, int sb1) {
+    MTMC(stat_out_check(g, o));
+    if (sb1 <= sb0) return MTM_OK;
+    const int owg = stats_u8_owg(g.w);
+    const dim3 gs((g.ow + owg - 1) / owg, sb1 - sb0);
+    hipLaunchKernelGGL(stats_u16_kernel, gs, dim3(256), 0, stream, hib, lob, pitch, g.h, g.w, g.oh, g.ow, owg, g.inv_area,
+                       o.num_type, o.want_sq, o.want_t, o.want_sum2, o.t[0], o.sum2, o.sq, o.st_pitch, blk, blk_pitch, sb0);
+    HIPC(hipGetLastError());
+    return MTM_OK;
+}
+
+// the second pass of the two-pass chains: output rows [o0, o1), o0 a multiple of kVsumBand (a band restarts its column sums)
+template <typename AccT, typename SumT>
+static int launch_vsum(hipStream_t stream, const StatGeom& g, const StatScratch& s, const StatOut& o, int o0, int o1) {
+    MTMC(stat_out_check(g, o));
+    if (o1 <= o0) return MTM_OK;
+    if (o0 % kVsumBand != 0) {
+        set_error("launch_vsum: a launch starts on a whole band of output rows");
+        return MTM_E_INVALID;
+    }
+    const dim3 g2((g.ow + 255) / 256, (o1 - o0 + kVsumBand - 1) / kVsumBand);
+    hipLaunchKernelGGL((vsum_stats_kernel<AccT, SumT>), g2, dim3(256), 0, stream, static_cast<const AccT*>(s.hs1),
+                       static_cast<const AccT*>(s.hs2), s.pitch, s.plane, g.chans, g.h, g.oh, g.ow, g.inv_area, o.num_type,
+                       o.want_sq, o.want_t, o.t[0], o.t[1], o.t[2], o.t[3], o.sum2, o.sq, o.st_pitch, o0 / kVsumBand);
+    HIPC(hipGetLastError());
+    return MTM_OK;
+}
+
+// U8_2P: hsum_u8_kernel (a row's two prefix sums in LDS: cols <= kStatsHsumU8MaxCols) + vsum over uint32 row sums
+static int launch_stats_u8_2p(hipStream_t stream, const uint8_t* u8, int pitch, long long plane, const StatGeom& g,
+                              const StatScratch& s, const StatOut& o) {
+    hipLaunchKernelGGL(hsum_u8_kernel, dim3(g.rows, g.chans), dim3(256), sizeof(uint32_t) * 2 * (g.cols + 1), stream, u8, pitch,
+                       plane, g.cols, g.w, g.ow, static_cast<uint32_t*>(s.hs1), static_cast<uint32_t*>(s.hs2), s.pitch, s.plane);
+    HIPC(hipGetLastError());
+    return launch_vsum<uint32_t, unsigned long long>(stream, g, s, o, 0, g.oh);
+}
+
+// U8_2P_WIDE: the generic hsum_kernel on the float32 plane of a uint8 image (uint32 row sums: exact) + the same vsum
+static int launch_stats_u8_2p_wide(hipStream_t stream, const float* f32, int pitch, long long plane, const StatGeom& g,
+                                   const StatScratch& s, const StatOut& o) {
+    const dim3 g1((g.ow + 256 * kHsumSeg - 1) / (256 * kHsumSeg), g.rows, g.chans);
+    hipLaunchKernelGGL(hsum_kernel<uint32_t>, g1, dim3(256), 0, stream, f32, pitch, plane, g.rows, g.w, g.ow,
+                       static_cast<uint32_t*>(s.hs1), static_cast<uint32_t*>(s.hs2), s.pitch, s.plane);
+    HIPC(hipGetLastError());
+    return launch_vsum<uint32_t, unsigned long long>(stream, g, s, o, 0, g.oh);
+}
+
+// F64_LDS: hsum_lds_kernel (w <= kStatsHsumLdsMaxW) over the image rows [r0, r1) + vsum over the output rows [o0, o1) - the
+// whole image, or the rows a band of a banded upload brought and the windows they complete
+static int launch_stats_f64_lds(hipStream_t stream, const float* f32, int pitch, long long plane, const StatGeom& g,
+                                const StatScratch& s, const StatOut& o, int r0, int r1, int o0, int o1) {
+    if (r1 > r0) {
+        const dim3 g1((g.ow + 256 * kHsumSeg - 1) / (256 * kHsumSeg), r1 - r0, g.chans);
+        hipLaunchKernelGGL(hsum_lds_kernel, g1, dim3(256), hsum_lds_bytes(g.w), stream, f32, pitch, plane, g.rows, g.w, g.ow,
+                           static_cast<double*>(s.hs1), static_cast<double*>(s.hs2), s.pitch, s.plane, r0);
+        HIPC(hipGetLastError());
+    }
+    return launch_vsum<double, double>(stream, g, s, o, o0, o1);
+}
+
+// F64: the generic hsum_kernel<double> (any window width) + the same vsum, whole image
+static int launch_stats_f64(hipStream_t stream, const float* f32, int pitch, long long plane, const StatGeom& g,
+                            const StatScratch& s, const StatOut& o) {
+    const dim3 g1((g.ow + 256 * kHsumSeg - 1) / (256 * kHsumSeg), g.rows, g.chans);
+    hipLaunchKernelGGL(hsum_kernel<double>, g1, dim3(256), 0, stream, f32, pitch, plane, g.rows, g.w, g.ow,
+                       static_cast<double*>(s.hs1), static_cast<double*>(s.hs2), s.pitch, s.plane);
+    HIPC(hipGetLastError());
+    return launch_vsum<double, double>(stream, g, s, o, 0, g.oh);
+}
+
 // Window statistics of one size class (two kernels), into c->stats.  Returns the plane table.
 // `sb0`, `sb1`: range of kStatBand4-row output blocks to compute (banded image upload; fused single-channel
 // kernel only), sb1 < 0 = all.
@@ -327,13 +443,17 @@ int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out,
     MTMC(c->hs1.ensure(esz * hs_plane * c->chans));
     MTMC(c->hs2.ensure(esz * hs_plane * c->chans));
     const ImageDev img = image_dev(c);
-    const dim3 g1((ow + 256 * kHsumSeg - 1) / (256 * kHsumSeg), c->rows, c->chans);
-    const dim3 g2((ow + 255) / 256, (oh + kVsumBand - 1) / kVsumBand);
     const int want_t = (num_type == 1 || want_t_always) ? 1 : 0;
-    const double inv_area = 1.0 / ((double)h * (double)w);
+    // what every launcher but the fused single-channel one takes: the window, the row-sum planes, the planes to write
+    const StatGeom g = stat_geom(c->rows, c->cols, c->chans, h, w);
+    const StatScratch hs{c->hs1.p, c->hs2.p, hs_pitch, hs_plane};
+    StatOut o{};
+    o.num_type = num_type, o.want_sq = normed ? 1 : 0, o.want_t = want_t, o.want_sum2 = 1;
+    for (int k = 0; k < kMaxChans; ++k) o.t[k] = tp[k];
+    o.t_plane = (long long)plane, o.sum2 = sum2, o.sq = sq, o.st_pitch = st.pitch;
+    const StatsRoute route = stats_route(c->dtype, c->chans, h, w, c->cols, c->fuse_stats != 0);
     // fused single-kernel statistics for the common case
-    const bool fused_stats = u8 && c->chans == 1 && w <= 768 && (double)w * h * 65025.0 < 4294967296.0 &&
-                             c->fuse_stats;
+    const bool fused_stats = route == kStatsRouteU8;
     if (fused_stats) {
         // (masked classes on the matrix cores: the sum2 plane is written by the sum I^2 M pass below, not here)
         const int want_sum2 = (!masked_mfma && (num_type == 2 || (normed && num_type != 1) || !want_t_always)) ? 1 : 0;
@@ -393,32 +513,17 @@ int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out,
             a.lay = lay;
             MTMC(launch_stats_u8(c->stats_stream ? c->stats_stream : c->stream, a, 0, c->n_cus > 0 ? c->n_cus : 256));
         }
-    } else if (u8 && c->chans == 3 && w <= 768 && 3.0 * w * h * 65025.0 < 4294967296.0 && c->fuse_stats) {
+    } else if (route == kStatsRouteU8MC) {
         // RGB: the fused kernel with one scan per channel + one for the squares (sum2 always written:
         // vsum_stats_kernel does)
-        const int owg = stats_u8_owg(w);
-        const dim3 gs((ow + owg - 1) / owg, (oh + kStatBand4 - 1) / kStatBand4);
-        hipLaunchKernelGGL(stats_u8_mc_kernel<3>, gs, dim3(256), 0, c->stream, img.u8, img.u8_pitch, img.u8_plane, h, w, oh,
-                           ow, owg, inv_area, num_type, normed ? 1 : 0, want_t, 1, tp[0], (long long)plane, sum2, sq,
-                           st.pitch);
-    } else if (u8) {
-        if (c->cols <= 8191)
-            hipLaunchKernelGGL(hsum_u8_kernel, dim3(c->rows, c->chans), dim3(256), sizeof(uint32_t) * 2 * (c->cols + 1),
-                               c->stream, img.u8, img.u8_pitch, img.u8_plane, c->cols, w, ow, c->hs1.as<uint32_t>(),
-                               c->hs2.as<uint32_t>(), hs_pitch, hs_plane);
-        else {
-            MTMC(ensure_f32_plane(c));
-            hipLaunchKernelGGL(hsum_kernel<uint32_t>, g1, dim3(256), 0, c->stream, img.f32, img.f32_pitch,
-                               img.f32_plane, c->rows, w, ow, c->hs1.as<uint32_t>(), c->hs2.as<uint32_t>(),
-                               hs_pitch, hs_plane);
-        }
-        hipLaunchKernelGGL((vsum_stats_kernel<uint32_t, unsigned long long>), g2, dim3(256), 0, c->stream,
-                           c->hs1.as<uint32_t>(), c->hs2.as<uint32_t>(), hs_pitch, hs_plane, c->chans, h, oh,
-                           ow, inv_area, num_type, normed ? 1 : 0, want_t, tp[0], tp[1], tp[2], tp[3], sum2, sq,
-                           st.pitch, 0);
-    } else if (c->dtype == MTM_U16 && c->chans == 1 && w <= 768 && (double)w * h * 65535.0 < 4294967296.0 && c->fuse_stats) {
+        MTMC(launch_stats_u8mc(c->stream, img.u8, img.u8_pitch, img.u8_plane, g, o));
+    } else if (route == kStatsRouteU8TwoPass) {
+        MTMC(launch_stats_u8_2p(c->stream, img.u8, img.u8_pitch, img.u8_plane, g, hs, o));
+    } else if (route == kStatsRouteU8TwoPassWide) {
+        MTMC(ensure_f32_plane(c));
+        MTMC(launch_stats_u8_2p_wide(c->stream, img.f32, img.f32_pitch, img.f32_plane, g, hs, o));
+    } else if (route == kStatsRouteU16) {
         // single-channel uint16: the fused kernel over the two byte planes (the ones the MFMA kernel reads)
-        const int owg = stats_u8_owg(w);
         const int nsb = (oh + kStatBand4 - 1) / kStatBand4;
         const int b1 = sb1 < 0 ? nsb : std::min(sb1, nsb);
         const uint8_t* hib = c->slot[c->cur].u8b.as<uint8_t>();
@@ -429,36 +534,21 @@ int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out,
             blk = c->stats_blk.as<double>();
             st.blk = blk;
         }
-        if (b1 > sb0) {
-            const dim3 gs((ow + owg - 1) / owg, b1 - sb0);
-            hipLaunchKernelGGL(stats_u16_kernel, gs, dim3(256), 0, c->stats_stream ? c->stats_stream : c->stream, hib,
-                               hib + img.u8_plane, img.u8_pitch, h, w, oh, ow, owg, inv_area, num_type, normed ? 1 : 0, want_t, 1,
-                               tp[0], sum2, sq, st.pitch, blk, st.blk_pitch, sb0);
-        }
+        MTMC(launch_stats_u16(c->stats_stream ? c->stats_stream : c->stream, hib, hib + img.u8_plane, img.u8_pitch, g, o, blk,
+                              st.blk_pitch, sb0, b1));
     } else {
         // Round 6, banded float32 uploads (run_score_banded): c->lay_r0 .. lay_r1 are the image rows that have just arrived
         // (their horizontal sums), sb0 .. sb1 the output rows whose windows they complete, in blocks of kStatBand4 rows that
         // make whole vsum bands (a band restarts its column sums: the planes are bit for bit those of one launch)
-        const bool part = c->lay_r1 > c->lay_r0 && w <= 1024;
+        const bool part = c->lay_r1 > c->lay_r0 && route == kStatsRouteF64Lds;
         const hipStream_t ss = c->stats_stream ? c->stats_stream : c->stream;
         if (!part) MTMC(ensure_f32_plane(c));
-        if (w <= 1024) {    // (the same sums in the same order, the row staged through LDS: mtm_k_stats.hip.h)
-            const dim3 g1p(g1.x, part ? c->lay_r1 - c->lay_r0 : c->rows, c->chans);
-            hipLaunchKernelGGL(hsum_lds_kernel, g1p, dim3(256), hsum_lds_bytes(w), ss, img.f32, img.f32_pitch,
-                               img.f32_plane, c->rows, w, ow, c->hs1.as<double>(), c->hs2.as<double>(), hs_pitch,
-                               hs_plane, part ? c->lay_r0 : 0);
-        } else
-            hipLaunchKernelGGL(hsum_kernel<double>, g1, dim3(256), 0, ss, img.f32, img.f32_pitch,
-                               img.f32_plane, c->rows, w, ow, c->hs1.as<double>(), c->hs2.as<double>(), hs_pitch,
-                               hs_plane);
         const int o0 = part ? sb0 * kStatBand4 : 0, o1 = part && sb1 >= 0 ? std::min(oh, sb1 * kStatBand4) : oh;
-        if (o1 > o0) {
-            const dim3 g2p(g2.x, (o1 - o0 + kVsumBand - 1) / kVsumBand);
-            hipLaunchKernelGGL((vsum_stats_kernel<double, double>), g2p, dim3(256), 0, ss,
-                               c->hs1.as<double>(), c->hs2.as<double>(), hs_pitch, hs_plane, c->chans, h, oh, ow,
-                               inv_area, num_type, normed ? 1 : 0, want_t, tp[0], tp[1], tp[2], tp[3], sum2, sq, st.pitch,
-                               o0 / kVsumBand);
-        }
+        if (route == kStatsRouteF64Lds)     // (the same sums in the same order, the row staged through LDS: mtm_k_stats.hip.h)
+            MTMC(launch_stats_f64_lds(ss, img.f32, img.f32_pitch, img.f32_plane, g, hs, o, part ? c->lay_r0 : 0,
+                                      part ? c->lay_r1 : c->rows, o0, o1));
+        else
+            MTMC(launch_stats_f64(ss, img.f32, img.f32_pitch, img.f32_plane, g, hs, o));
     }
     HIPC(hipGetLastError());
     for (int k = 0; k < kMaxChans; ++k) st.t[k] = tp[k];
@@ -573,16 +663,13 @@ static int launch_masked_bf16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, flo
         const size_t hs_plane = (size_t)hs_pitch * c->rows;
         MTMC(c->hs1.ensure(sizeof(double) * hs_plane));
         MTMC(c->hs2.ensure(sizeof(double) * hs_plane));
-        const dim3 g1((ow + 256 * kHsumSeg - 1) / (256 * kHsumSeg), c->rows, 1);
-        const dim3 g2((ow + 255) / 256, (oh + kVsumBand - 1) / kVsumBand);
+        const StatGeom g = stat_geom(c->rows, c->cols, 1, h, w);
+        const StatScratch hs{c->hs1.p, c->hs2.p, hs_pitch, (long long)hs_plane};
         for (int pl = 0; pl < 2; ++pl) {
             const float* src = pl == 0 ? img.f32 : c->f32_sq.as<float>();
-            hipLaunchKernelGGL(hsum_lds_kernel, g1, dim3(256), hsum_lds_bytes(w), c->stream, src, img.f32_pitch, img.f32_plane, c->rows,
-                               w, ow, c->hs1.as<double>(), c->hs2.as<double>(), hs_pitch, (long long)hs_plane, 0);
-            hipLaunchKernelGGL((vsum_stats_kernel<double, double>), g2, dim3(256), 0, c->stream, c->hs1.as<double>(),
-                               c->hs2.as<double>(), hs_pitch, (long long)hs_plane, 1, h, oh, ow, 1.0 / ((double)h * w), 0, 0, 1,
-                               pl == 0 ? s1i : s1j, (double*)nullptr, (double*)nullptr, (double*)nullptr, pl == 0 ? s2i : s2j,
-                               (double*)nullptr, st_pitch, 0);
+            StatOut o{};                    // sums only: num_type 0, no sqrt plane
+            o.want_t = 1, o.t[0] = pl == 0 ? s1i : s1j, o.sum2 = pl == 0 ? s2i : s2j, o.st_pitch = st_pitch;
+            MTMC(launch_stats_f64_lds(c->stream, src, img.f32_pitch, img.f32_plane, g, hs, o, 0, c->rows, 0, oh));
         }
     }
     // the two raw launches
@@ -1209,12 +1296,8 @@ struct LaneScope {
 // statistics)?  A banded uint8 upload leaves that plane out (ensure_f32_plane rebuilds it on demand).
 static bool class_reads_f32(const mtm_ctx* c, const SizeClass& sc) {
     if (sc.kernel == MTM_KERNEL_NAIVE || sc.kernel == MTM_KERNEL_AUTO) return true;     // ncc_naive_kernel / ncc_f64_kernel
-    if (c->dtype == MTM_U8) {
-        const bool fused1 = c->chans == 1 && sc.w <= 768 && (double)sc.w * sc.h * 65025.0 < 4294967296.0 && c->fuse_stats;
-        const bool fused3 = c->chans == 3 && sc.w <= 768 && 3.0 * sc.w * sc.h * 65025.0 < 4294967296.0 && c->fuse_stats;
-        return !fused1 && !fused3 && c->cols > 8191;                                 // hsum_kernel on the float32 plane
-    }
-    return false;       // uint16 / float32 images are uploaded with their float32 plane
+    // hsum_kernel on the float32 plane of a uint8 image (uint16 / float32 images are uploaded with their float32 plane)
+    return stats_route(c->dtype, c->chans, sc.h, sc.w, c->cols, c->fuse_stats != 0) == kStatsRouteU8TwoPassWide;
 }
 
 // Statistics + score launches of every size class but `skip` (the class a banded call has already queued; -1: none).
@@ -1381,7 +1464,8 @@ static bool class_bandable(const mtm_ctx* c, const ImageArgs& a, const SizeClass
     if (c->upload_bands.size() < 2 || (a.dtype != MTM_U8 && !u16) || a.chans != 1) return false;
     if (sc.masked || !c->fuse_stats || !sc.slabs.empty() || sc.kernel != (u16 ? MTM_KERNEL_MFMA16 : MTM_KERNEL_MFMA))
         return false;
-    if (!(sc.w <= 768 && (double)sc.w * sc.h * (u16 ? 65535.0 : 65025.0) < 4294967296.0)) return false;   // the fused statistics
+    const StatsRoute route = stats_route(a.dtype, 1, sc.h, sc.w, a.cols, true);
+    if (route != kStatsRouteU8 && route != kStatsRouteU16) return false;                                   // the fused statistics
     if (!any_fill && !((size_t)a.rows * a.cols >= ((size_t)1 << 20) && a.rows - sc.h + 1 >= 256)) return false;
     if (any_fill) return true;
     // A band's score launch must still fill the chip: two work-groups per CU are resident, and a launch of fewer than a
@@ -1593,7 +1677,7 @@ int mtm_debug_window_stats(mtm_ctx* c, const mtm_window_stats* a) {
     const int rows = a->rows, cols = a->cols, h = a->h, w = a->w;
     if (!a->image || !a->info || rows < 1 || cols < 1 || rows > 16384 || cols > 16384 || h < 1 || w < 1 || h > rows || w > cols)
         return bad("an image of 1 .. 16384 rows and columns and a window inside it are needed");
-    if (w > 768 || (double)w * h * 65025.0 >= 4294967296.0) return bad("the fused kernel takes w <= 768 and w h 255^2 < 2^32");
+    if (stats_route(MTM_U8, 1, h, w, cols, true) != kStatsRouteU8) return bad("the fused kernel takes w <= 768 and w h 255^2 < 2^32");
     if (a->num_type < 0 || a->num_type > 2 || a->form < 0 || a->form > kStatFormCount || a->pattern_byte < 0 || a->pattern_byte > 255)
         return bad("num_type 0 .. 2, a form and a pattern byte");
     const int oh = rows - h + 1, ow = cols - w + 1, nsb = (oh + kStatBand4 - 1) / kStatBand4;
@@ -1679,6 +1763,166 @@ int mtm_debug_window_stats(mtm_ctx* c, const mtm_window_stats* a) {
     const int rows_wg = kStatFormRows[form - 1];
     const int64_t info[8] = {st_pitch, blk_pitch, pitch, form, strips, stats_u8_grid_y(sb0, sb1, oh, rows_wg), n_cus,
                              (int64_t)llround((double)ms * 1e6)};
+    std::memcpy(a->info, info, sizeof(info));
+    return MTM_OK;
+}
+
+// Test support: the six other routes of stats_route (tests/test_gpu_stats_routes.py), each through the launcher launch_stats
+// uses.  Everything lives in stats_dbg, filled with the caller's pattern first.  The image planes are laid out on the HOST
+// exactly as an upload of that dtype leaves them (pitch = cols + 512 rounded up to 64, rows + kPadRows rows a plane, zero
+// padding - 0x80 in the biased byte planes) and copied in one piece: the conversion kernels are not what is under test.
+int mtm_debug_window_stats_route(mtm_ctx* c, const mtm_window_stats_route* a) {
+    if (!c || !a) {
+        set_error("mtm_debug_window_stats_route: null context or arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, "mtm_debug_window_stats_route");
+    const auto bad = [](const char* what) {
+        set_error(std::string("mtm_debug_window_stats_route: ") + what);
+        return MTM_E_INVALID;
+    };
+    const int rows = a->rows, cols = a->cols, chans = a->chans, h = a->h, w = a->w, dtype = a->dtype;
+    if (!a->image || !a->info || rows < 1 || cols < 1 || rows > 16384 || cols > 16384 || h < 1 || w < 1 || h > rows || w > cols)
+        return bad("an image of 1 .. 16384 rows and columns and a window inside it are needed");
+    if (chans < 1 || chans > kMaxChans || (dtype != MTM_U8 && dtype != MTM_U16 && dtype != MTM_F32))
+        return bad("1 .. 4 channels of uint8, uint16 or float32");
+    if (a->num_type < 0 || a->num_type > 2 || a->pattern_byte < 0 || a->pattern_byte > 255 || a->route < 0 ||
+        a->route >= kStatsRouteCount || (a->want & ~31) != 0)
+        return bad("num_type 0 .. 2, a route, the planes wanted and a pattern byte");
+    const int route = a->route ? a->route : (int)stats_route(dtype, chans, h, w, cols, true);
+    if (route == kStatsRouteU8) return bad("the fused single-channel uint8 kernel is mtm_debug_window_stats's");
+    if (const char* why = stats_route_refusal(route, dtype, chans, h, w, cols)) return bad(why);
+    const StatGeom g = stat_geom(rows, cols, chans, h, w);
+    const int oh = g.oh, ow = g.ow, nsb = (oh + kStatBand4 - 1) / kStatBand4;
+    const int sb0 = a->sb0, sb1 = a->sb1 < 0 ? nsb : std::min(a->sb1, nsb);
+    if (sb0 < 0 || sb0 >= sb1) return bad("an empty range of row units");
+    const bool part = a->lay_r1 > a->lay_r0;
+    const bool ranged = route == kStatsRouteU16 || (route == kStatsRouteF64Lds && part);
+    if (part && route != kStatsRouteF64Lds) return bad("image rows lay_r0 .. lay_r1: the F64_LDS route only");
+    if (!ranged && (sb0 != 0 || sb1 != nsb)) return bad("a range of row units: the U16 route or a partial F64_LDS launch only");
+    const int o0 = sb0 * kStatBand4, o1 = std::min(oh, sb1 * kStatBand4);
+    if (part) {
+        if (o0 % kVsumBand != 0) return bad("a partial F64_LDS launch starts on a whole band: sb0 * 8 a multiple of 32");
+        if (a->lay_r0 < 0 || a->lay_r1 > rows || a->lay_r0 > o0) return bad("lay_r0 .. lay_r1 inside the image, lay_r0 <= sb0 * 8");
+        if (a->lay_r1 < o1 + h - 1) return bad("lay_r1 < min(oh, sb1 * 8) + h - 1: the windows' last rows have no sums");
+    }
+    const bool want_t = a->want & 1, want_sum2 = a->want & 2, want_sq = a->want & 4, want_blk = a->want & 8, nulls = a->want & 16;
+    const bool two_pass = route != kStatsRouteU8MC && route != kStatsRouteU16;
+    if (want_blk && route != kStatsRouteU16) return bad("blk: the U16 route only");
+    if (two_pass && nulls && !want_sum2) return bad("the two-pass chains write sum2 whatever is asked: it cannot be null");
+    const int st_pitch = (int)round_up((size_t)ow, 4), blk_pitch = (st_pitch + 15) / 16;
+    const int pitch = (int)round_up((size_t)cols + kPadCols, 64), rows_alloc = rows + kPadRows;
+    // stats_dbg: [image planes][hs1][hs2][t0 .. t3][sum2][sq][blk]
+    size_t total = 0;
+    const auto take = [&](size_t bytes) {
+        const size_t off = total;
+        total += round_up(std::max<size_t>(bytes, 16), 256);
+        return off;
+    };
+    const bool bytes_in = route == kStatsRouteU8MC || route == kStatsRouteU8TwoPass || route == kStatsRouteU16;
+    const size_t plane_elems = (size_t)pitch * rows_alloc;
+    const int n_planes = route == kStatsRouteU16 ? 2 : chans;
+    const size_t img_bytes = plane_elems * n_planes * (bytes_in ? 1 : sizeof(float));
+    const bool u32_sums = route == kStatsRouteU8TwoPass || route == kStatsRouteU8TwoPassWide;
+    const long long hs_plane = (long long)st_pitch * rows;
+    const size_t hs_bytes = two_pass ? (u32_sums ? sizeof(uint32_t) : sizeof(double)) * (size_t)hs_plane * chans : 0;
+    const size_t st_bytes = sizeof(double) * (size_t)st_pitch * oh, rec_bytes = sizeof(double) * 4 * (size_t)blk_pitch * oh;
+    const size_t o_img = take(img_bytes), o_hs1 = take(hs_bytes), o_hs2 = take(hs_bytes), o_t = take(st_bytes * kMaxChans);
+    const size_t o_sum2 = take(st_bytes), o_sq = take(st_bytes), o_blk = take(rec_bytes);
+    if (total > ((size_t)256 << 20)) return bad("more than 256 MB of planes");
+    // the planes, on the host
+    std::vector<uint8_t> stage(img_bytes, route == kStatsRouteU16 ? 0x80 : 0);
+    {
+        const auto px = [&](int y, int x, int ch) -> double {
+            const size_t i = ((size_t)y * cols + x) * chans + ch;
+            return dtype == MTM_U8 ? (double)static_cast<const uint8_t*>(a->image)[i]
+                 : dtype == MTM_U16 ? (double)static_cast<const uint16_t*>(a->image)[i]
+                                    : (double)static_cast<const float*>(a->image)[i];
+        };
+        float* f = reinterpret_cast<float*>(stage.data());
+        for (int y = 0; y < rows; ++y)
+            for (int x = 0; x < cols; ++x) {
+                const size_t o = (size_t)y * pitch + x;
+                if (route == kStatsRouteU16) {
+                    const unsigned v = static_cast<const uint16_t*>(a->image)[(size_t)y * cols + x];
+                    stage[o] = (uint8_t)((v >> 8) ^ 0x80u);
+                    stage[plane_elems + o] = (uint8_t)((v & 255u) ^ 0x80u);
+                } else {
+                    for (int ch = 0; ch < chans; ++ch) {
+                        if (bytes_in) stage[ch * plane_elems + o] = static_cast<const uint8_t*>(a->image)[((size_t)y * cols + x) * chans + ch];
+                        else f[ch * plane_elems + o] = (float)px(y, x, ch);
+                    }
+                }
+            }
+    }
+    HIPC(hipSetDevice(c->device));
+    MTMC(c->stats_dbg.ensure(total));
+    uint8_t* b = c->stats_dbg.as<uint8_t>();
+    HIPC(hipMemsetAsync(b, a->pattern_byte, total, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    HIPC(hipMemcpy(b + o_img, stage.data(), img_bytes, hipMemcpyHostToDevice));
+    const StatScratch hs{b + o_hs1, b + o_hs2, st_pitch, hs_plane};
+    StatOut o{};
+    o.num_type = a->num_type, o.want_sq = want_sq, o.want_t = want_t, o.want_sum2 = want_sum2;
+    for (int k = 0; k < kMaxChans; ++k)
+        o.t[k] = (k < chans && (want_t || !nulls)) ? reinterpret_cast<double*>(b + o_t + st_bytes * k) : nullptr;
+    o.t_plane = (long long)st_pitch * oh, o.st_pitch = st_pitch;
+    o.sum2 = (want_sum2 || !nulls) ? reinterpret_cast<double*>(b + o_sum2) : nullptr;
+    o.sq = (want_sq || !nulls) ? reinterpret_cast<double*>(b + o_sq) : nullptr;
+    double* blk = want_blk ? reinterpret_cast<double*>(b + o_blk) : nullptr;
+    const int owg = stats_u8_owg(w);
+    const int hx = (ow + 256 * kHsumSeg - 1) / (256 * kHsumSeg), vx = (ow + 255) / 256, vy = (o1 - o0 + kVsumBand - 1) / kVsumBand;
+    int64_t info[12] = {route, st_pitch, blk_pitch, pitch, 0, 0, 0, two_pass ? vx : 0, two_pass ? vy : 0, two_pass ? st_pitch : 0, 0, 0};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int rc = MTM_OK;
+    float ms = 0.0f;
+    hipError_t e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
+    if (e == hipSuccess) switch (route) {
+        case kStatsRouteU8MC:
+            info[4] = (ow + owg - 1) / owg, info[5] = nsb, info[6] = 1;
+            rc = launch_stats_u8mc(c->stream, b + o_img, pitch, (long long)plane_elems, g, o);
+            break;
+        case kStatsRouteU16:
+            info[4] = (ow + owg - 1) / owg, info[5] = sb1 - sb0, info[6] = 1;
+            rc = launch_stats_u16(c->stream, b + o_img, b + o_img + plane_elems, pitch, g, o, blk, want_blk ? blk_pitch : 0, sb0, sb1);
+            break;
+        case kStatsRouteU8TwoPass:
+            info[4] = rows, info[5] = chans, info[6] = 1, info[10] = (int64_t)(sizeof(uint32_t) * 2 * (cols + 1));
+            rc = launch_stats_u8_2p(c->stream, b + o_img, pitch, (long long)plane_elems, g, hs, o);
+            break;
+        case kStatsRouteU8TwoPassWide:
+            info[4] = hx, info[5] = rows, info[6] = chans;
+            rc = launch_stats_u8_2p_wide(c->stream, reinterpret_cast<const float*>(b + o_img), pitch, (long long)plane_elems, g, hs, o);
+            break;
+        case kStatsRouteF64Lds:
+            info[4] = hx, info[5] = part ? a->lay_r1 - a->lay_r0 : rows, info[6] = chans, info[10] = (int64_t)hsum_lds_bytes(w);
+            rc = launch_stats_f64_lds(c->stream, reinterpret_cast<const float*>(b + o_img), pitch, (long long)plane_elems, g, hs, o,
+                                      part ? a->lay_r0 : 0, part ? a->lay_r1 : rows, o0, o1);
+            break;
+        default:
+            info[4] = hx, info[5] = rows, info[6] = chans;
+            rc = launch_stats_f64(c->stream, reinterpret_cast<const float*>(b + o_img), pitch, (long long)plane_elems, g, hs, o);
+            break;
+    }
+    if (e == hipSuccess && rc == MTM_OK) e = hipEventRecord(ev[1], c->stream);
+    if (e == hipSuccess && rc == MTM_OK) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && rc == MTM_OK) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    for (hipEvent_t v : ev)
+        if (v) (void)hipEventDestroy(v);
+    MTMC(rc);
+    HIPC(e);
+    const auto fetch = [&](void* to, size_t off, size_t bytes) -> int {
+        if (to) HIPC(hipMemcpy(to, b + off, bytes, hipMemcpyDeviceToHost));
+        return MTM_OK;
+    };
+    double* const tout[kMaxChans] = {a->t0, a->t1, a->t2, a->t3};
+    for (int k = 0; k < kMaxChans; ++k) MTMC(fetch(tout[k], o_t + st_bytes * k, st_bytes));
+    MTMC(fetch(a->sum2, o_sum2, st_bytes));
+    MTMC(fetch(a->sq, o_sq, st_bytes));
+    MTMC(fetch(a->blk, o_blk, rec_bytes));
+    info[11] = (int64_t)llround((double)ms * 1e6);
     std::memcpy(a->info, info, sizeof(info));
     return MTM_OK;
 }

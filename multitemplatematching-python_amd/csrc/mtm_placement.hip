@@ -468,7 +468,9 @@ void choose_tiling(const mtm_ctx* c, SizeClass& sc) {
     const bool one_pack = c->chans == 1 || (c->chans == 3 && !sc.masked);
     // row-multiplexed mode: <= 16 templates (one channel, masked or not, or unmasked RGB) whose window statistics the fused
     // kernels produce (the single-channel one also writes the 1/sqrt plane); wide templates take fewer rows per MFMA group
-    if (c->row_mux && n_cls <= 16 && c->fuse_stats && one_pack && (double)c->chans * sc.w * sc.h * 65025.0 < 4294967296.0) {
+    const mtm::StatsRoute stats = mtm::stats_route(c->dtype, c->chans, sc.h, sc.w, c->cols, c->fuse_stats != 0);
+    const bool stats_fused = stats == mtm::kStatsRouteU8 || stats == mtm::kStatsRouteU8MC;
+    if (c->row_mux && n_cls <= 16 && one_pack && stats_fused) {
         sc.rm_nt = rm_group_templates(n_cls, sc.h, sc.w);
         sc.rm_R = 16 / sc.rm_nt;
     }

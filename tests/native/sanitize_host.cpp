@@ -20,6 +20,7 @@
 #include "../../multitemplatematching-python_amd/csrc/mtm_internal.h"
 #include "../../multitemplatematching-python_amd/csrc/mtm_nms_core.h"
 #include "../../multitemplatematching-python_amd/csrc/mtm_peak_sizing.h"
+#include "../../multitemplatematching-python_amd/csrc/mtm_stats_route.h"
 
 using namespace mtm;
 
@@ -584,6 +585,84 @@ static void test_peak_sizing(std::mt19937& rng) {
     }
 }
 
+// ---- which kernel chain makes a class's window statistics (mtm_stats_route.h): every boundary of the rule, and for the route
+// it names the preconditions of that route's kernels (mtm_k_stats.hip.h), restated here in integer arithmetic
+static bool route_kernels_fit(int route, int dtype, int chans, int h, int w, int cols) {
+    const unsigned long long area = (unsigned long long)w * (unsigned long long)h, two32 = 1ull << 32;
+    const int owg = (1024 + 1 - w) & ~15;       // stats_u8_owg: output columns of a 1024-column strip
+    const bool strip_ok = w <= 768 && owg >= 256 && owg % 16 == 0 && owg + w - 1 <= 1024;
+    switch (route) {
+    case kStatsRouteU8:      // uint32 prefixes of I and I^2 over a strip: every window sum below 2^32
+        return dtype == MTM_U8 && chans == 1 && strip_ok && area * 255ull * 255ull < two32;
+    case kStatsRouteU8MC:    // ... the squares of all three channels in one prefix
+        return dtype == MTM_U8 && chans == 3 && strip_ok && 3ull * area * 255ull * 255ull < two32;
+    case kStatsRouteU16:     // ... of I only (the squares are uint64)
+        return dtype == MTM_U16 && chans == 1 && strip_ok && area * 65535ull < two32;
+    case kStatsRouteU8TwoPass:       // two uint32 prefix rows of cols + 1 words in 64 KB of dynamic LDS; uint32 row sums of I^2
+        return dtype == MTM_U8 && 2ull * 4ull * (unsigned long long)(cols + 1) <= 65536ull && (unsigned long long)w * 65025ull < two32;
+    case kStatsRouteU8TwoPassWide:
+        return dtype == MTM_U8 && (unsigned long long)w * 65025ull < two32;
+    case kStatsRouteF64Lds: {       // 256 * 16 + w floats of a row, one pad word per 16, in 64 KB
+        const long long n = 256 * 16 + w, words = n + n / 16 + 2;
+        return w <= 1024 && 4 * words <= 65536;
+    }
+    case kStatsRouteF64:
+        return true;
+    default:
+        return false;
+    }
+}
+
+static void test_stats_route() {
+    std::vector<int> ws = {1, 2, 16, 64, 65, 255, 256, 257, 767, 768, 769, 1023, 1024, 1025, 4096, 16384};
+    const int cols_set[] = {8190, 8191, 8192, 16384};
+    const double limits[] = {4294967295.0 / 65025.0, 4294967295.0 / (3.0 * 65025.0), 4294967295.0 / 65535.0};
+    int seen[kStatsRouteCount] = {0};
+    for (int dtype : {MTM_U8, MTM_F32, MTM_U16})
+        for (int chans = 1; chans <= 4; ++chans)
+            for (int fuse = 0; fuse <= 1; ++fuse)
+                for (int w : ws) {
+                    std::vector<int> hs = {1, 2, 8, 255, 256, 257, 16384};
+                    for (double lim : limits) {         // the three area limits: one below, at, one above
+                        const int h_at = (int)std::min(16384.0, std::floor(lim / w));
+                        for (int d = -1; d <= 1; ++d)
+                            if (h_at + d >= 1 && h_at + d <= 16384) hs.push_back(h_at + d);
+                    }
+                    for (int h : hs)
+                        for (int cols : cols_set) {
+                            if (cols < w) continue;
+                            const StatsRoute r = stats_route(dtype, chans, h, w, cols, fuse != 0);
+                            seen[r]++;
+                            CHECK(route_kernels_fit(r, dtype, chans, h, w, cols));
+                            CHECK(stats_route_refusal(r, dtype, chans, h, w, cols) == nullptr);
+                            // a fused kernel is chosen wherever it fits and the option is on; never with the option off
+                            const int fused = dtype == MTM_U8 && chans == 1 ? kStatsRouteU8 : dtype == MTM_U8 && chans == 3 ? kStatsRouteU8MC
+                                            : dtype == MTM_U16 && chans == 1 ? kStatsRouteU16 : -1;
+                            const bool fits = fused >= 0 && route_kernels_fit(fused, dtype, chans, h, w, cols);
+                            CHECK((r == fused) == (fits && fuse != 0));
+                            if (r != fused) {
+                                if (dtype == MTM_U8) CHECK(r == (cols <= 8191 ? kStatsRouteU8TwoPass : kStatsRouteU8TwoPassWide));
+                                else CHECK(r == (w <= 1024 ? kStatsRouteF64Lds : kStatsRouteF64));
+                            }
+                            // a forced route (the test-support entry) is admitted only where its kernels fit
+                            for (int f = 0; f < kStatsRouteCount; ++f)
+                                if (stats_route_refusal(f, dtype, chans, h, w, cols) == nullptr)
+                                    CHECK(route_kernels_fit(f, dtype, chans, h, w, cols));
+                        }
+                }
+    for (int r = 0; r < kStatsRouteCount; ++r) CHECK(seen[r] > 0);
+    CHECK(stats_route_refusal(kStatsRouteCount, MTM_U8, 1, 8, 8, 64) != nullptr && stats_route_refusal(-1, MTM_U8, 1, 8, 8, 64) != nullptr);
+    // the boundaries by name
+    CHECK(stats_route(MTM_U8, 1, 86, 768, 900, true) == kStatsRouteU8 && stats_route(MTM_U8, 1, 87, 768, 900, true) == kStatsRouteU8TwoPass);
+    CHECK(stats_route(MTM_U8, 1, 8, 769, 900, true) == kStatsRouteU8TwoPass && stats_route(MTM_U8, 1, 8, 8, 900, false) == kStatsRouteU8TwoPass);
+    CHECK(stats_route(MTM_U8, 3, 28, 768, 900, true) == kStatsRouteU8MC && stats_route(MTM_U8, 3, 29, 768, 900, true) == kStatsRouteU8TwoPass);
+    CHECK(stats_route(MTM_U8, 3, 86, 256, 900, true) == kStatsRouteU8MC && stats_route(MTM_U8, 3, 87, 256, 900, true) == kStatsRouteU8TwoPass);
+    CHECK(stats_route(MTM_U8, 2, 8, 8, 8191, true) == kStatsRouteU8TwoPass && stats_route(MTM_U8, 2, 8, 8, 8192, true) == kStatsRouteU8TwoPassWide);
+    CHECK(stats_route(MTM_U16, 1, 256, 256, 900, true) == kStatsRouteU16 && stats_route(MTM_U16, 1, 255, 257, 900, true) == kStatsRouteU16);
+    CHECK(stats_route(MTM_U16, 1, 256, 257, 900, true) == kStatsRouteF64Lds && stats_route(MTM_U16, 1, 8, 8, 900, false) == kStatsRouteF64Lds);
+    CHECK(stats_route(MTM_F32, 1, 8, 1024, 2000, true) == kStatsRouteF64Lds && stats_route(MTM_F32, 1, 8, 1025, 2000, true) == kStatsRouteF64);
+}
+
 // ---- the host-only pieces of fm_end (mtm_api.hip; its peak pass: mtm_peaks.hip): the 3x3 test of the candidate list, the trivial-map rule, the ladder
 
 // one case of verify_candidates_3x3 against brute force over the maps: `maps[t]` the scores of an oh[t] x ow[t] map, the list
@@ -1000,6 +1079,7 @@ int main() {
     test_track_plan();
     test_nms_grid(rng);
     test_peak_sizing(rng);
+    test_stats_route();
     test_host(rng);
     test_group(rng);
     // two groups driven from two caller threads at once (each group is single-caller; the library must not share state)

@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -693,6 +693,48 @@ int mtm_match_blocks_stack(mtm_ctx* ctx, const void* const* frames, int n_frames
 int mtm_debug_plan_blocks_stack(int n_frames, int frames_per_chunk, int mode, int32_t* chunks, int64_t chunk_cap,
                                 int64_t* n_chunks, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
                                 int n_blocks, int margin, int32_t* clip);
+
+/* mtm_match_blocks with a predicted displacement per block: offsets[2 k], offsets[2 k + 1] = (dx, dy) of
+ * block k.  The block's position is moved by its offset and clamped so that the block still lies inside the image - cx =
+ * min(max(x + dx, 0), cols - w), cy likewise -, and the search box is the box of the moved block widened by `margin` and
+ * clipped to the image (MTM.blocks.search_box_at); the template is still the block at (x, y) of the reference.  out, nbhd,
+ * checks, chunks and the context's state afterwards as mtm_match_blocks'; zero offsets give its records bit for bit.  Any
+ * int32 offset is valid.  The boxes are computed on the device from the uploaded offsets, and every block's map is scored
+ * over a fixed grid of ceil((2 margin + 1) / 16)^2 tiles (per axis at most the tiles of the block's map over the whole
+ * image); the tiles of all blocks must stay below 2^31. */
+int mtm_match_blocks_at(mtm_ctx* ctx, const void* reference, int64_t reference_stride_bytes, const void* image,
+                        int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
+                        const int32_t* offsets, int n_blocks, int margin, int method, mtm_hit* out, float* nbhd);
+
+/* One pass of mtm_match_blocks_passes: every bw x bh block at stride (sx, sy) that lies wholly inside the image, in
+ * row-major order (MTM.blocks.grid), searched with `margin`. */
+typedef struct mtm_block_pass {
+    int32_t bw, bh, sx, sy, margin;
+} mtm_block_pass;
+
+/* Coarse-to-fine block matching in one call.  Pass 0 is mtm_match_blocks over its grid.  Every later pass
+ * p is mtm_match_blocks_at over its own grid with, for each block, the displacement (record position - block position) of
+ * the block of pass p - 1 whose centre is nearest: per axis, on doubled centres, index min(n - 1, max(0, 2 x + wf - wc +
+ * s) / (2 s)) of a coarse axis of n blocks of size wc at stride s for a fine block of size wf at x (an exact tie goes to
+ * the higher index).  Records are pass-major: out holds those of pass 0's blocks, then pass 1's, ...; nbhd (optional) 9
+ * floats per record in the same order.  Both images are uploaded once and the host waits once: the boxes of the later
+ * passes are computed on the device from the previous pass's records and never reach the host.  A pass with bw, bh, sx or
+ * sy < 1 or margin < 0, or whose grid is empty, returns MTM_E_INVALID and names the pass; other checks, the template-byte
+ * chunks within a pass and the context's state afterwards as mtm_match_blocks'. */
+int mtm_match_blocks_passes(mtm_ctx* ctx, const void* reference, int64_t reference_stride_bytes, const void* image,
+                            int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                            const mtm_block_pass* passes, int n_passes, int method, mtm_hit* out, float* nbhd);
+
+/* Test support: the host plan of a mtm_match_blocks_passes call (no context, no GPU).  counts[p] = the blocks of pass p;
+ * tiles: 4 int32 per tile of the fixed tile table - (pass, block within the pass, first output row, first output column) -
+ * pass after pass, at most tile_cap tiles are written and *n_tiles is their full number; chunk_of: one int32 per block,
+ * pass-major, the chunk of its pass the block runs in (budget_bytes as mtm_debug_plan_blocks').  With coarse != NULL and 1
+ * <= at_pass < n_passes: coarse holds one record per block of pass at_pass - 1, and for every block k of pass at_pass
+ * pred[2 k], pred[2 k + 1] = the predicted (dx, dy) and maps[4 k ..] = (x0, y0, ow, oh) of the unit the device would
+ * search - the very functions the kernel runs.  Any output may be NULL. */
+int mtm_debug_plan_blocks_passes(int rows, int cols, int chans, int dtype, const mtm_block_pass* passes, int n_passes,
+                                 int64_t budget_bytes, int64_t* counts, int32_t* tiles, int64_t tile_cap, int64_t* n_tiles,
+                                 int32_t* chunk_of, const mtm_hit* coarse, int at_pass, int32_t* pred, int32_t* maps);
 
 /* The 3 x 3 score neighbourhoods of n points in one call: out[9 k + 3 (1 + dy) + (1 + dx)] = the score of
  * template pts[k].templ_idx at window (x + dx, y + dy) of the image's score map, NaN for a window outside the map.  Image:

@@ -26,7 +26,7 @@ pinned_empty = _lib.pinned_empty        # numpy arrays in page-locked memory (fa
 
 __all__ = ["NMS", "Hit", "matchTemplates", "findMatches", "computeScoreMap", "TemplateMatcher", "matchTemplatesBatch",
            "findMatchesPyramid", "matchTemplatesPyramid", "findMatchesInBoxes", "matchTemplatesInBoxes", "trackTemplates",
-           "hitNeighbourhoods", "refineHits", "matchBlocks", "matchBlocksStack",
+           "hitNeighbourhoods", "refineHits", "matchBlocks", "matchBlocksStack", "matchBlocksMultipass",
            "pinned_empty", "drawBoxesOnRGB",
            "drawBoxesOnGray", "TM_SQDIFF", "TM_SQDIFF_NORMED", "TM_CCORR", "TM_CCORR_NORMED",
            "TM_CCOEFF", "TM_CCOEFF_NORMED", "__version__"]
@@ -718,4 +718,4 @@ from .pyramid import findMatchesPyramid, matchTemplatesPyramid  # noqa: E402  (c
 from .boxes import findMatchesInBoxes, matchTemplatesInBoxes  # noqa: E402  (many searchBoxes in one call)
 from .tracking import trackTemplates  # noqa: E402  (templates tracked through a stack of frames)
 from .subpixel import hitNeighbourhoods, refineHits  # noqa: E402  (sub-pixel positions from score neighbourhoods)
-from .blocks import matchBlocks, matchBlocksStack  # noqa: E402  (block matching between two images or over a frame stack)
+from .blocks import matchBlocks, matchBlocksStack, matchBlocksMultipass  # noqa: E402  (block matching between two images, over a frame stack, coarse to fine)

@@ -64,6 +64,8 @@ BOX_UNIT_DTYPE = np.dtype([("templ_idx", "<i4"), ("y0", "<i4"), ("x0", "<i4"), (
 # mtm_point: a template index and the window (x, y) at the centre of a 3 x 3 neighbourhood (mtm_hit_neighbourhoods)
 # one mtm_block of mtm_match_blocks: a block (x, y, w, h) of the reference image
 BLOCK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4")])
+# one mtm_block_pass of mtm_match_blocks_passes: a grid of bw x bh blocks at stride (sx, sy), searched with `margin`
+BLOCK_PASS_DTYPE = np.dtype([("bw", "<i4"), ("bh", "<i4"), ("sx", "<i4"), ("sy", "<i4"), ("margin", "<i4")])
 POINT_DTYPE = np.dtype([("templ_idx", "<i4"), ("x", "<i4"), ("y", "<i4")])
 assert HIT_DTYPE.itemsize == ctypes.sizeof(MtmHit) == 24
 # mtm_templ as a numpy record: a whole template list is filled column-wise instead of field by field
@@ -211,6 +213,17 @@ SYMBOLS = {
     "mtm_debug_plan_blocks_stack": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                                    _P(ctypes.c_int64), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "mtm_match_blocks_at": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
+    "mtm_match_blocks_passes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                               ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "mtm_debug_plan_blocks_passes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                    ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_int64, _P(ctypes.c_int64), ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_hit_neighbourhoods": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
@@ -520,6 +533,51 @@ def debug_plan_blocks_stack(n_frames, frames_per_chunk, mode, shape=None, chans=
     check(lib.mtm_debug_plan_blocks_stack(*head, chunks.ctypes.data, n_chunks.value, ctypes.byref(n_chunks), *tail),
           "mtm_debug_plan_blocks_stack")
     return chunks, clip
+
+
+def block_pass_records(passes):
+    """BLOCK_PASS_DTYPE records from such records or from an (P, 5) integer array of (bw, bh, sx, sy, margin)."""
+    a = np.asarray(passes)
+    if a.dtype == BLOCK_PASS_DTYPE:
+        return np.ascontiguousarray(a)
+    a = a.reshape(-1, 5)
+    rec = np.empty(len(a), dtype=BLOCK_PASS_DTYPE)
+    for i, name in enumerate(BLOCK_PASS_DTYPE.names):
+        rec[name] = a[:, i]
+    return rec
+
+
+def debug_plan_blocks_passes(shape, chans, dtype, passes, budget_bytes, coarse=None, at_pass=0):
+    """The host plan of a mtm_match_blocks_passes call for images of `shape` (rows, cols), no GPU needed
+    (mtm_debug_plan_blocks_passes): (counts (P,) int64, the blocks of every pass; tiles (n, 4) int32 of (pass, block, ty0,
+    tx0), the fixed tile table; chunk_of int32, pass-major, every block's chunk within its pass).  With `coarse` - the
+    positions (Nc, 2) of pass at_pass - 1's blocks - two more: pred (Nf, 2) int32, the (dx, dy) predicted for every block of
+    pass `at_pass`, and maps (Nf, 4) int32 of (x0, y0, ow, oh), the units searched - the functions the kernel runs."""
+    lib = load()
+    passes = block_pass_records(passes)
+    n_passes = len(passes)
+    code = _DT_CODES[np.dtype(dtype)]
+    head = (int(shape[0]), int(shape[1]), int(chans), code, passes.ctypes.data, n_passes, int(budget_bytes))
+    counts = np.zeros(n_passes, dtype=np.int64)
+    n_tiles = ctypes.c_int64(0)
+    check(lib.mtm_debug_plan_blocks_passes(*head, counts.ctypes.data, None, 0, ctypes.byref(n_tiles), None, None, 0, None, None),
+          "mtm_debug_plan_blocks_passes")
+    tiles = np.zeros((n_tiles.value, 4), dtype=np.int32)
+    chunk_of = np.zeros(int(counts.sum()), dtype=np.int32)
+    rec = pred = maps = None
+    if coarse is not None:
+        pos = np.asarray(coarse, dtype=np.int64).reshape(-1, 2)
+        if not 1 <= at_pass < n_passes or len(pos) != counts[at_pass - 1]:
+            raise ValueError("debug_plan_blocks_passes: coarse needs one position per block of pass at_pass - 1")
+        rec = np.zeros(len(pos), dtype=HIT_DTYPE)
+        rec["x"], rec["y"] = pos[:, 0], pos[:, 1]
+        pred = np.zeros((int(counts[at_pass]), 2), dtype=np.int32)
+        maps = np.zeros((int(counts[at_pass]), 4), dtype=np.int32)
+    check(lib.mtm_debug_plan_blocks_passes(*head, None, tiles.ctypes.data, n_tiles.value, ctypes.byref(n_tiles),
+                                           chunk_of.ctypes.data, rec.ctypes.data if rec is not None else None, int(at_pass),
+                                           pred.ctypes.data if rec is not None else None,
+                                           maps.ctypes.data if rec is not None else None), "mtm_debug_plan_blocks_passes")
+    return (counts, tiles, chunk_of) if coarse is None else (counts, tiles, chunk_of, pred, maps)
 
 
 def debug_templ_stats(template, method):
@@ -962,6 +1020,40 @@ class Context(_RecordMemo):
         check(self._lib.mtm_match_blocks(self._h, rptr, rstride, aptr, astride, a.shape[0], a.shape[1], chans, _dtype_code(a),
                                          blocks.ctypes.data, n, int(margin), int(method), out.ctypes.data,
                                          nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks")
+        return out, nbhd
+
+    def match_blocks_at(self, reference, image, blocks, offsets, margin, method, with_nbhd=False):
+        """match_blocks with a displacement per block (mtm_match_blocks_at): `offsets` an (N, 2) int32 array of (dx, dy);
+        block k's box is that of the block moved by its offset and clamped into the image, widened by `margin`."""
+        blocks = block_records(blocks)
+        n = len(blocks)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32).reshape(n, 2)
+        out = np.empty(n, dtype=HIT_DTYPE)
+        nbhd = np.empty((n, 3, 3), dtype=np.float32) if with_nbhd else None
+        if n == 0:
+            return out, nbhd
+        r, rptr, rstride = _pixel_rows(reference)
+        a, aptr, astride = _pixel_rows(image)
+        chans = 1 if a.ndim == 2 else a.shape[2]
+        check(self._lib.mtm_match_blocks_at(self._h, rptr, rstride, aptr, astride, a.shape[0], a.shape[1], chans, _dtype_code(a),
+                                            blocks.ctypes.data, offsets.ctypes.data, n, int(margin), int(method),
+                                            out.ctypes.data, nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks_at")
+        return out, nbhd
+
+    def match_blocks_passes(self, reference, image, passes, counts, method, with_nbhd=False):
+        """Coarse-to-fine block matching in one native call (mtm_match_blocks_passes): `passes` BLOCK_PASS_DTYPE records,
+        `counts` the blocks of every pass's grid.  Returns (records, pass-major, sum(counts) of them; neighbourhoods in
+        the same order, or None).  The templates set on the context are not touched."""
+        passes = block_pass_records(passes)
+        n = int(sum(counts))
+        out = np.empty(n, dtype=HIT_DTYPE)
+        nbhd = np.empty((n, 3, 3), dtype=np.float32) if with_nbhd else None
+        r, rptr, rstride = _pixel_rows(reference)
+        a, aptr, astride = _pixel_rows(image)
+        chans = 1 if a.ndim == 2 else a.shape[2]
+        check(self._lib.mtm_match_blocks_passes(self._h, rptr, rstride, aptr, astride, a.shape[0], a.shape[1], chans,
+                                                _dtype_code(a), passes.ctypes.data, len(passes), int(method), out.ctypes.data,
+                                                nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks_passes")
         return out, nbhd
 
     def match_blocks_stack(self, frames, blocks, margin, method, mode, with_nbhd=False, planes=False):

@@ -29,6 +29,11 @@ Scope (anything else raises ValueError / TypeError before any native call): two 
 count - uint8 with 1 or 3 channels or single-channel uint16, at most 32767 rows -, methods 0..5, blocks wholly inside the
 reference, uint16 blocks of at most 2^21 pixels, ``margin`` an integer >= 0.
 
+``matchBlocks(..., offsets=)`` centres every block's box on a predicted displacement (``search_box_at``), and
+``matchBlocksMultipass`` is the coarse-to-fine scheme built on it (mtm_match_blocks_passes): a sparse pass
+with a wide margin finds the large motion, every later pass searches a small margin around what the nearest block of the
+pass before found (``predict_offsets``) - one native call, the boxes of the later passes computed on the device.
+
 ``matchBlocksStack`` is the movie form: the pairs of a stack of frames - each frame against the previous or against the
 first - in one native call (mtm_match_blocks_stack), every frame uploaded once; per pair the very results of
 ``matchBlocks``, or (``ensemble=True``) every block's correlation plane averaged over the pairs and its peak
@@ -41,7 +46,8 @@ import numpy as np
 from . import _lib, subpixel
 from . import TM_CCOEFF_NORMED
 
-__all__ = ["matchBlocks", "matchBlocksStack", "plane_peaks", "grid", "search_box", "displacements"]
+__all__ = ["matchBlocks", "matchBlocksStack", "matchBlocksMultipass", "plane_peaks", "grid", "search_box", "search_box_at",
+           "predict_offsets", "displacements"]
 
 _I64 = np.dtype(np.int64)
 _U16_MAX_PIXELS = 1 << 21       # mtm_match_blocks: uint16 correlations stay below 2^53, exact in float64
@@ -63,21 +69,42 @@ def search_box(block, margin, shape):
     return (x0, y0, x1 - x0, y1 - y0)
 
 
+def search_box_at(block, offset, margin, shape):
+    """``search_box`` of ``block = (x, y, w, h)`` moved by ``offset = (dx, dy)``: the position is moved and clamped so
+    that the block still lies inside the image - ``cx = min(max(x + dx, 0), W - w)``, ``cy`` likewise -, and the result
+    is ``search_box((cx, cy, w, h), margin, shape)``.  A zero offset gives ``search_box(block, ...)``; the box's map is
+    never empty, whatever the offset."""
+    x, y, w, h = (int(v) for v in block)
+    dx, dy = (int(v) for v in offset)
+    H, W = int(shape[0]), int(shape[1])
+    cx, cy = min(max(x + dx, 0), W - w), min(max(y + dy, 0), H - h)
+    return search_box((cx, cy, w, h), margin, shape)
+
+
+def _pair(v, what, who="grid"):
+    try:
+        p = (v, v) if _is_int(v) else tuple(v)
+    except TypeError:
+        p = ()
+    if len(p) != 2 or not all(_is_int(q) for q in p) or min(p) < 1:
+        raise ValueError("%s: %s must be a positive integer or a pair of them (got %r)" % (who, what, v))
+    return int(p[0]), int(p[1])
+
+
+def _grid_axes(shape, block, step, who="grid"):
+    """(w, h, sx, sy, nx, ny) of ``grid(shape, block, step)``."""
+    w, h = _pair(block, "block", who)
+    sx, sy = (w, h) if step is None else _pair(step, "step", who)
+    H, W = int(shape[0]), int(shape[1])
+    return w, h, sx, sy, ((W - w) // sx + 1 if W >= w else 0), ((H - h) // sy + 1 if H >= h else 0)
+
+
 def grid(shape, block, step=None):
     """Every block of size ``block`` (an int, or ``(w, h)``) at stride ``step`` (an int or ``(sx, sy)``; default: the
     block size) that lies wholly inside an image of shape ``shape``, in row-major order: an (N, 4) int64 array of
     ``(x, y, w, h)``."""
-    def pair(v, what):
-        try:
-            p = (v, v) if _is_int(v) else tuple(v)
-        except TypeError:
-            p = ()
-        if len(p) != 2 or not all(_is_int(q) for q in p) or min(p) < 1:
-            raise ValueError("grid: %s must be a positive integer or a pair of them (got %r)" % (what, v))
-        return int(p[0]), int(p[1])
-
-    w, h = pair(block, "block")
-    sx, sy = (w, h) if step is None else pair(step, "step")
+    w, h = _pair(block, "block")
+    sx, sy = (w, h) if step is None else _pair(step, "step")
     H, W = int(shape[0]), int(shape[1])
     xs = np.arange(0, W - w + 1, sx, dtype=_I64) if W >= w else np.zeros(0, _I64)
     ys = np.arange(0, H - h + 1, sy, dtype=_I64) if H >= h else np.zeros(0, _I64)
@@ -87,6 +114,41 @@ def grid(shape, block, step=None):
     out[:, 2] = w
     out[:, 3] = h
     return out
+
+
+def _nearest(n, s, wc, x, wf):
+    """Per axis: the index of the coarse block (size wc, stride s, n of them) whose centre is nearest to that of every
+    fine block of size wf at x, on doubled centres; an exact tie goes to the higher index (blocks_nearest_inl,
+    mtm_blocks_predict.h)."""
+    return np.minimum(n - 1, np.maximum(0, 2 * x + wf - wc + s) // (2 * s))
+
+
+def predict_offsets(shape, coarse, positions, fine):
+    """The displacements a coarse pass predicts for the blocks of a finer one.  ``coarse`` and ``fine``: ``(block, step)``
+    as ``grid`` takes them; ``positions``: the integer (Nc, 2) positions found for ``grid(shape, *coarse)``.  Returns an
+    (Nf, 2) int64 array: for every block of ``grid(shape, *fine)`` the displacement ``positions - blocks[:, :2]`` of the
+    coarse block whose centre is nearest - per axis ``i = min(n - 1, max(0, 2 x + wf - wc + s) // (2 s))`` for a coarse
+    axis of n blocks of size wc at stride s and a fine block of size wf at x; an exact tie goes to the higher index."""
+    try:
+        (cb, cs), (fb, fs) = coarse, fine
+    except (TypeError, ValueError):
+        raise ValueError("predict_offsets: coarse and fine are (block, step) pairs (got %r and %r)" % (coarse, fine)) from None
+    wc, hc, sx, sy, nx, ny = _grid_axes(shape, cb, cs, "predict_offsets")
+    fg = grid(shape, fb, fs)
+    pos = np.asarray(positions)
+    if pos.ndim != 2 or pos.shape[1] != 2 or len(pos) != nx * ny:
+        raise ValueError("predict_offsets: positions of shape %s for a coarse grid of %d blocks (expected (%d, 2))" % (
+            pos.shape, nx * ny, nx * ny))
+    if pos.dtype.kind not in "iu":
+        raise TypeError("predict_offsets: positions must be integers (got %s): refined positions never steer a pass" % pos.dtype)
+    if len(fg) == 0:
+        return np.zeros((0, 2), _I64)
+    if nx * ny == 0:
+        raise ValueError("predict_offsets: the coarse grid is empty")
+    pos = pos.astype(_I64)
+    ix = _nearest(nx, sx, wc, fg[:, 0], fg[:, 2])
+    iy = _nearest(ny, sy, hc, fg[:, 1], fg[:, 3])
+    return pos[iy * nx + ix] - np.stack((ix * sx, iy * sy), axis=1)
 
 
 def displacements(blocks, positions):
@@ -151,8 +213,38 @@ def _check_blocks(blocks, reference):
     return b
 
 
+_OFF_LIMIT = 1 << 62            # offsets beyond it are clamped to it first: int64 sums below stay exact
+
+
+def _check_offsets(offsets, b, shape):
+    """offsets -> the (N, 2) int32 offsets that move every block of ``b`` to its clamped position (any integer magnitude
+    is taken: the clamp makes it harmless, and it is applied here, in int64, before anything is narrowed)."""
+    try:
+        o = np.asarray(offsets)
+    except (ValueError, TypeError):
+        o = None
+    if o is not None and o.size == 0 and len(b) == 0:
+        return np.zeros((0, 2), np.int32)
+    if o is None or o.ndim != 2 or o.shape[1] != 2 or len(o) != len(b):
+        raise ValueError("offsets must be an (N, 2) integer array of (dx, dy), one per block (got shape %s for blocks of shape %s)"
+                         % (None if o is None else o.shape, b.shape))
+    if o.dtype.kind not in "iu":
+        flat = np.asarray(offsets, dtype=object).reshape(-1)
+        for k, v in enumerate(flat):
+            if not _is_int(v):
+                raise TypeError("offsets[%d]: (dx, dy) of block %d must be integers (got %r)" % (k // 2, k // 2, v))
+        o = np.array([min(max(int(v), -_OFF_LIMIT), _OFF_LIMIT) for v in flat], dtype=_I64).reshape(-1, 2)
+    elif o.dtype.kind == "u":
+        o = np.minimum(o, np.uint64(_OFF_LIMIT)).astype(_I64)
+    o = np.clip(o.astype(_I64), -_OFF_LIMIT, _OFF_LIMIT)
+    H, W = int(shape[0]), int(shape[1])
+    cx = np.clip(b[:, 0] + o[:, 0], 0, W - b[:, 2])
+    cy = np.clip(b[:, 1] + o[:, 1], 0, H - b[:, 3])
+    return np.stack((cx - b[:, 0], cy - b[:, 1]), axis=1).astype(np.int32)
+
+
 def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, method: int = TM_CCOEFF_NORMED, *,
-                refine: bool = False, context=None):
+                refine: bool = False, context=None, offsets=None):
     """
     Where every block of ``reference`` is in ``image``: ``(positions, scores)``, ``positions[k]`` the int64 ``[x, y]``
     (image coordinates) and ``scores[k]`` the float32 score of the single hit of
@@ -164,6 +256,11 @@ def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, m
     (``grid`` makes regular ones).  ``refine=True``: float64 positions, ``refineHits``' of each hit (the module's
     docstring).  ``context``: the _lib.Context to run on (default: the process's); its templates are not touched.
     ``displacements(blocks, positions)`` gives the displacement field.
+
+    ``offsets``: an (N, 2) integer array of predicted displacements ``(dx, dy)``; block k is then searched in
+    ``search_box_at(blocks[k], offsets[k], margin, image.shape)`` - the box of the block moved by its offset and clamped
+    into the image - instead (mtm_match_blocks_at: the boxes are computed on the device).  Zero offsets give the call
+    without them, bit for bit.
     """
     _check_images(reference, image)
     if not _is_int(method) or method not in (0, 1, 2, 3, 4, 5):
@@ -173,6 +270,7 @@ def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, m
     if not isinstance(refine, bool):
         raise ValueError("refine must be True or False (got %r)" % (refine,))
     b = _check_blocks(blocks, reference)
+    off = None if offsets is None else _check_offsets(offsets, b, image.shape)
     n = len(b)
     if n == 0:
         return np.zeros((0, 2), dtype=np.float64 if refine else _I64), np.zeros(0, dtype=np.float32)
@@ -182,13 +280,81 @@ def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, m
     m = int(min(margin, max(image.shape[0], image.shape[1])))
     ctx = context or _lib.default_context()     # (only now: every argument error comes before "no GPU")
     with ctx.lock:
-        raw, nbhd = ctx.match_blocks(reference, image, rec, m, int(method), refine)
+        if off is None:
+            raw, nbhd = ctx.match_blocks(reference, image, rec, m, int(method), refine)
+        else:
+            raw, nbhd = ctx.match_blocks_at(reference, image, rec, off, m, int(method), refine)
     positions = np.stack((raw["x"], raw["y"]), axis=1).astype(_I64)
     scores = raw["score"].astype(np.float32)
     if refine:          # (one fit over every block: refineHits' numbers by construction)
         ox, oy = subpixel.fit_offsets(nbhd, method)
         positions = positions.astype(np.float64) + np.stack((ox, oy), axis=1)
     return positions, scores
+
+
+def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, method: int = TM_CCOEFF_NORMED, *,
+                         refine: bool = False, context=None):
+    """
+    Coarse-to-fine block matching in one native call.  ``passes``: a non-empty sequence of ``(block, step, margin)``,
+    ``block`` and ``step`` as ``grid`` takes them (``step=None``: the block size).  Pass 0 is ``matchBlocks`` over its
+    grid; every later pass searches each block of its own grid in the box centred on what the nearest block of the pass
+    before found.  Returns a list with one ``(blocks_p, positions_p, scores_p)`` per pass, exactly what this loop gives:
+
+        off = None
+        for p, (block, step, margin) in enumerate(passes):
+            b = grid(image.shape, block, step)
+            if p: off = predict_offsets(image.shape, passes[p - 1][:2], steer, passes[p][:2])
+            steer, _ = matchBlocks(reference, image, b, margin, method, offsets=off)
+            pos, sc = matchBlocks(reference, image, b, margin, method, offsets=off, refine=refine)
+
+    The integer positions steer the next pass, never the refined ones.  Scope and checks as ``matchBlocks``'; a pass whose
+    grid is empty raises ValueError.  The templates set on the context are left alone.
+    """
+    _check_images(reference, image)
+    if not _is_int(method) or method not in (0, 1, 2, 3, 4, 5):
+        raise ValueError("matchBlocksMultipass takes methods 0..5 (got %r)" % (method,))
+    if not isinstance(refine, bool):
+        raise ValueError("refine must be True or False (got %r)" % (refine,))
+    try:
+        pl = list(passes)
+    except TypeError:
+        raise TypeError("passes must be a sequence of (block, step, margin) (got %s)" % type(passes).__name__) from None
+    if not pl:
+        raise ValueError("passes is empty")
+    rec = np.empty(len(pl), dtype=_lib.BLOCK_PASS_DTYPE)
+    grids = []
+    for p, item in enumerate(pl):
+        who = "passes[%d]" % p
+        try:
+            block, step, margin = item
+        except (TypeError, ValueError):
+            raise ValueError("%s must be (block, step, margin) (got %r)" % (who, item)) from None
+        w, h, sx, sy, nx, ny = _grid_axes(image.shape, block, step, who)
+        if not _is_int(margin) or margin < 0:
+            raise ValueError("%s: margin must be an integer >= 0 (got %r)" % (who, margin))
+        if nx * ny == 0:
+            raise ValueError("%s: no %d x %d block fits the %d x %d images (empty grid)" % (
+                who, w, h, image.shape[0], image.shape[1]))
+        if reference.dtype == np.uint16 and w * h > _U16_MAX_PIXELS:
+            raise ValueError("%s: uint16 blocks of more than 2^21 pixels are not supported (their exact correlations would "
+                             "pass 2^53)" % who)
+        # (a margin past the images' larger side clips to the whole image, as a margin of that side does)
+        rec[p] = (w, h, sx, sy, int(min(margin, max(image.shape[0], image.shape[1]))))
+        grids.append(grid(image.shape, block, step))
+    counts = [len(g) for g in grids]
+    ctx = context or _lib.default_context()     # (only now: every argument error comes before "no GPU")
+    with ctx.lock:
+        raw, nbhd = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine)
+    positions = np.stack((raw["x"], raw["y"]), axis=1).astype(_I64)
+    scores = raw["score"].astype(np.float32)
+    if refine:          # (one fit over every pass and block: matchBlocks' numbers by construction)
+        ox, oy = subpixel.fit_offsets(nbhd, method)
+        positions = positions.astype(np.float64) + np.stack((ox, oy), axis=1)
+    out, at = [], 0
+    for g in grids:
+        out.append((g, positions[at:at + len(g)], scores[at:at + len(g)]))
+        at += len(g)
+    return out
 
 
 _REFERENCE_MODES = {"previous": _lib.BLOCKS_REF_PREVIOUS, "first": _lib.BLOCKS_REF_FIRST}

@@ -15,9 +15,16 @@
 // adds every output's score to the block's plane of float64 sums instead of keeping an extremum.
 // Both entry points are compositions of the same host steps: check_block_images, stage_block_tables, blocks_pair (a
 // pair's launch chain, the one place the kernels are launched) and decode_block_keys.
+// mtm_match_blocks_at and mtm_match_blocks_passes search boxes that follow a displacement - uploaded
+// offsets, or the previous pass's records -: blocks_unit_kernel computes every block's unit on the device
+// (mtm_blocks_predict.h, the single source of host and device), blocks_score_fixed_kernel runs blocks_score_kernel's tile
+// over a fixed tile table and leaves the tiles outside the unit's map, blocks_record_kernel decodes the keys into records
+// on the device, which the next pass and the final copy read.  One chain (match_block_passes) behind both, through
+// blocks_pair; every pass has its own row of keys, records and neighbourhoods.
 #include <climits>
 #include <type_traits>
 
+#include "mtm_blocks_predict.h"
 #include "mtm_ctx.h"
 #include "mtm_device_util.hip.h"
 #include "mtm_k_nbhd.hip.h"
@@ -117,6 +124,75 @@ __global__ __launch_bounds__(256) void blocks_score_kernel(ImageDev img, const u
                             [&](bool inside, int y, int x, auto&& score) {
                                 win_merge_key(inside, win_pos_word(y, x, U.ow), mode_min, score, keys + K.u0);
                             });
+}
+
+// blocks_score_kernel over a FIXED tile table (fix_block_tiles, mtm_host.cpp: ceil((2 margin + 1) / 16)^2 tiles per
+// block) for units that a kernel computed (blocks_unit_kernel): the host does not know the maps, so a tile may lie
+// outside its unit's clipped map - it leaves before any barrier, the test being the same for the whole work-group
+// (track_score_kernel's rule).  A tile inside is blocks_score_kernel's to the letter: win_score_tile and win_merge_key.
+// No LDS and no scratch over blocks_score_kernel.
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void blocks_score_fixed_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
+                                                                 const uint8_t* __restrict__ tpx,
+                                                                 const long long* __restrict__ toff,
+                                                                 const TemplDev* __restrict__ td,
+                                                                 const TrackUnit* __restrict__ units,
+                                                                 const TrackTile* __restrict__ tiles, int method, int mode_min,
+                                                                 unsigned long long* __restrict__ keys) {
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
+    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
+    const TrackTile K = tiles[blockIdx.x];
+    const TrackUnit U = units[K.u0];
+    if (K.ty0 >= U.oh || K.tx0 >= U.ow) return;         // (the same for the whole work-group: before any barrier)
+    const TemplDev T = td[K.u0];
+    win_score_tile<CH, U16>(Tl, Il, img, lo_b, tpx + toff[K.u0], T, U.y0 + K.ty0, U.x0 + K.tx0, K.ty0, K.tx0, U.oh, U.ow, method,
+                            [&](bool inside, int y, int x, auto&& score) {
+                                win_merge_key(inside, win_pos_word(y, x, U.ow), mode_min, score, keys + K.u0);
+                            });
+}
+
+// One lane per block k < n: the unit of the block moved by its displacement - offs[2 k], offs[2 k + 1], or (prev !=
+// nullptr) the one the records `prev` of the previous pass over grid `coarse` predict (blocks_predict_inl) -, clamped,
+// widened by `margin` and clipped to the rows x cols image (blocks_unit_at_inl): units[k] = (k, y0, x0, oh, ow).  Every
+// block lies inside the image (plan_blocks), so the coarse index is in range and the map has an output.
+__global__ __launch_bounds__(256) void blocks_unit_kernel(const mtm_block* __restrict__ blocks, int n,
+                                                          const int32_t* __restrict__ offs, const mtm_hit* __restrict__ prev,
+                                                          BlockGrid coarse, int margin, int rows, int cols,
+                                                          TrackUnit* __restrict__ units) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const mtm_block B = blocks[k];
+    long long dx, dy;
+    if (prev) {
+        blocks_predict_inl(coarse, prev, B, &dx, &dy);
+    } else {
+        dx = offs[2 * (size_t)k];
+        dy = offs[2 * (size_t)k + 1];
+    }
+    const BlockUnitBox u = blocks_unit_at_inl(B, dx, dy, margin, rows, cols);
+    units[k] = TrackUnit{k, u.y0, u.x0, u.oh, u.ow};
+}
+
+// One lane per block k < n, after the pass's score launches: the block's key as its record in image coordinates -
+// decode_quality_key (mtm_host.cpp) moved by the unit's origin, what decode_block_keys gives on the host - into recs[k].
+__global__ __launch_bounds__(256) void blocks_record_kernel(const TrackUnit* __restrict__ units,
+                                                            const unsigned long long* __restrict__ keys,
+                                                            const mtm_block* __restrict__ blocks, int n, int mode_min,
+                                                            mtm_hit* __restrict__ recs) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const TrackUnit U = units[k];
+    const unsigned long long key = keys[k];
+    const float q = mf_order_float((uint32_t)(key >> 32));
+    const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull);
+    mtm_hit r;
+    r.templ_idx = k;
+    r.x = U.x0 + (int)(idx % (uint32_t)U.ow);
+    r.y = U.y0 + (int)(idx / (uint32_t)U.ow);
+    r.w = blocks[k].w;
+    r.h = blocks[k].h;
+    r.score = key ? (mode_min ? -q : q) + 0.0f : __builtin_nanf("");
+    recs[k] = r;
 }
 
 // blocks_score_kernel's sibling for the ensemble planes of mtm_match_blocks_stack: the same tile and float32 score
@@ -263,12 +339,28 @@ struct BlockSink {
     int side, first;
 };
 
+// The device tables a chain reads, indexed as its plan indexes them: the call's buffers from their start
+// (ctx_block_tables), or one pass's part of them.  fixed: `tiles` is the fixed table (fix_block_tiles) and the units are
+// the device's - blocks_score_fixed_kernel scores.
+struct BlockTables {
+    const mtm_block* blocks;
+    const long long* toff;
+    TemplDev* td;
+    const TrackUnit* units;
+    const TrackTile* tiles;
+    bool fixed;
+};
+BlockTables ctx_block_tables(mtm_ctx* c) {
+    return BlockTables{c->blk_blocks.as<mtm_block>(), c->blk_toff.as<long long>(), c->blk_td.as<TemplDev>(),
+                       c->blk_units.as<TrackUnit>(), c->blk_tiles.as<TrackTile>(), false};
+}
+
 // One pair's launch chain for every block chunk - gather (unless the templates are already there), score or plane,
 // [neighbourhoods] - in stream order: the next chunk's gather overwrites the template planes behind this chunk's last
 // reader, and the host waits for none of them.  The pair is the stack's current image: the reference its rows
 // r_slot * rows .., the searched image its rows i_slot * rows ...
-int blocks_pair(mtm_ctx* c, const BlockPlan& P, int rows, int chans, int dtype, int method, int r_slot, int i_slot, bool gather,
-                const BlockSink& S) {
+int blocks_pair(mtm_ctx* c, const BlockPlan& P, const BlockTables& B, int rows, int chans, int dtype, int method, int r_slot,
+                int i_slot, bool gather, const BlockSink& S) {
     const ImageDev st = image_dev(c);
     const uint8_t* st_lo = c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane;        // uint16: [high ^ 0x80][low ^ 0x80]
     const ImageDev ref = stack_view(st, r_slot * rows, rows), img = stack_view(st, i_slot * rows, rows);
@@ -276,9 +368,9 @@ int blocks_pair(mtm_ctx* c, const BlockPlan& P, int rows, int chans, int dtype, 
     const uint8_t* img_lo = st_lo + (size_t)i_slot * rows * st.u8_pitch;
     const int mode_min = method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED ? 1 : 0;
     uint8_t* tpx = c->blk_tpx.as<uint8_t>();
-    const long long* toff = c->blk_toff.as<long long>();
-    TemplDev* td = c->blk_td.as<TemplDev>();
-    const TrackUnit* units = c->blk_units.as<TrackUnit>();
+    const long long* toff = B.toff;
+    TemplDev* td = B.td;
+    const TrackUnit* units = B.units;
     return blocks_dispatch(dtype, chans, [&](auto ch, auto u16) -> int {
         constexpr int CH = decltype(ch)::value;
         constexpr bool U16 = decltype(u16)::value;
@@ -286,18 +378,21 @@ int blocks_pair(mtm_ctx* c, const BlockPlan& P, int rows, int chans, int dtype, 
             if (gather)
                 MTMC(for_launch_slices((size_t)C.b0, (size_t)C.b1, [&](size_t b0, unsigned nb) -> int {
                     hipLaunchKernelGGL((blocks_gather_kernel<CH, U16>), dim3(nb), dim3(256), 0, c->stream, ref, ref_lo,
-                                       c->blk_blocks.as<mtm_block>(), (int)b0, tpx, toff, td, method);
+                                       B.blocks, (int)b0, tpx, toff, td, method);
                     HIPC(hipGetLastError());
                     return MTM_OK;
                 }));
             MTMC(for_launch_slices(C.t0, C.t1, [&](size_t t0, unsigned nt) -> int {
                 if (S.side > 0)
                     hipLaunchKernelGGL((blocks_plane_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo, tpx, toff,
-                                       td, units, c->blk_tiles.as<TrackTile>() + t0, method, c->blk_clip.as<int32_t>(), S.side,
-                                       S.first, c->blk_acc.as<double>());
+                                       td, units, B.tiles + t0, method, c->blk_clip.as<int32_t>(), S.side, S.first,
+                                       c->blk_acc.as<double>());
+                else if (B.fixed)
+                    hipLaunchKernelGGL((blocks_score_fixed_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo, tpx,
+                                       toff, td, units, B.tiles + t0, method, mode_min, S.keys);
                 else
                     hipLaunchKernelGGL((blocks_score_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo, tpx, toff,
-                                       td, units, c->blk_tiles.as<TrackTile>() + t0, method, mode_min, S.keys);
+                                       td, units, B.tiles + t0, method, mode_min, S.keys);
                 HIPC(hipGetLastError());
                 return MTM_OK;
             }));
@@ -325,9 +420,142 @@ void decode_block_keys(const BlockPlan& P, const mtm_block* blocks, const unsign
     }
 }
 
+// The chain behind mtm_match_blocks_at (one pass over the caller's blocks, `offsets` uploaded) and
+// mtm_match_blocks_passes (offsets == nullptr): both images go up once; per pass the units - pass 0 without offsets: the
+// host's, of zero offsets; else blocks_unit_kernel's -, the pass's chain over its fixed tile table (blocks_pair) and
+// blocks_record_kernel, all in stream order, so a pass reads the finished records of the one before and no work-group
+// waits for another.  The records (and neighbourhoods) of every pass, pass-major, come back behind the call's single wait.
+int match_block_passes(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                       int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                       const std::vector<BlockPassPlan>& Q, const int32_t* offsets, int method, mtm_hit* out, float* nbhd) {
+    // the tables of every pass, concatenated: one upload each
+    std::vector<mtm_block> blocks;
+    std::vector<long long> toff;
+    std::vector<TrackUnit> units;
+    std::vector<TrackTile> tiles;
+    size_t max_bytes = 0;
+    for (const BlockPassPlan& q : Q) {
+        blocks.insert(blocks.end(), q.blocks.begin(), q.blocks.end());
+        toff.insert(toff.end(), q.plan.toff.begin(), q.plan.toff.end());
+        units.insert(units.end(), q.plan.units.begin(), q.plan.units.end());
+        tiles.insert(tiles.end(), q.plan.tiles.begin(), q.plan.tiles.end());
+        max_bytes = std::max(max_bytes, q.plan.max_bytes);
+    }
+    const size_t n = blocks.size();
+    HIPC(hipSetDevice(c->device));
+    c->timing = mtm_timing{};
+    c->maps_valid = false;
+    c->last_hits.clear();
+    MTMC(c->blk_tpx.ensure(max_bytes));
+    MTMC(c->blk_toff.ensure(sizeof(long long) * n));
+    MTMC(c->blk_td.ensure(sizeof(TemplDev) * n));
+    MTMC(c->blk_blocks.ensure(sizeof(mtm_block) * n));
+    MTMC(c->blk_units.ensure(sizeof(TrackUnit) * n));
+    MTMC(c->blk_tiles.ensure(sizeof(TrackTile) * tiles.size()));
+    MTMC(c->blk_keys.ensure(sizeof(unsigned long long) * n));
+    MTMC(c->blk_recs.ensure(sizeof(mtm_hit) * n));
+    if (nbhd) MTMC(c->blk_nbhd.ensure(sizeof(float) * 9 * n));
+    if (offsets) MTMC(c->blk_offs.ensure(sizeof(int32_t) * 2 * n));
+
+    // ONE upload of each image, ahead of the call's clock (mtm_match_blocks' stack of two)
+    adopt_image(c, 2 * rows, cols, chans, dtype);
+    MTMC(upload_image_pair(c, c->slot[c->cur], reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans,
+                           dtype, c->stream));
+    HIPC(hipEventRecord(c->ev[0], c->stream));
+    HIPC(hipMemcpyAsync(c->blk_blocks.p, blocks.data(), sizeof(mtm_block) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_toff.p, toff.data(), sizeof(long long) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_units.p, units.data(), sizeof(TrackUnit) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_tiles.p, tiles.data(), sizeof(TrackTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
+    if (offsets) HIPC(hipMemcpyAsync(c->blk_offs.p, offsets, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemsetAsync(c->blk_keys.p, 0, sizeof(unsigned long long) * n, c->stream));
+
+    const int mode_min = method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED ? 1 : 0;
+    size_t b0 = 0, t0 = 0;
+    for (size_t p = 0; p < Q.size(); ++p) {
+        const BlockPassPlan& q = Q[p];
+        const int np = (int)q.blocks.size();
+        const unsigned lanes_grid = (unsigned)((np + 255) / 256);
+        BlockTables B = ctx_block_tables(c);
+        B.blocks += b0;
+        B.toff += b0;
+        B.units += b0;
+        B.tiles += t0;
+        B.fixed = true;
+        TrackUnit* dunits = c->blk_units.as<TrackUnit>() + b0;
+        unsigned long long* keys = c->blk_keys.as<unsigned long long>() + b0;
+        mtm_hit* recs = c->blk_recs.as<mtm_hit>() + b0;
+        if (p > 0 || offsets) {
+            hipLaunchKernelGGL(blocks_unit_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.blocks, np,
+                               p > 0 ? nullptr : c->blk_offs.as<int32_t>(), p > 0 ? recs - Q[p - 1].blocks.size() : nullptr,
+                               p > 0 ? Q[p - 1].grid : BlockGrid{}, q.margin, rows, cols, dunits);
+            HIPC(hipGetLastError());
+        }
+        MTMC(blocks_pair(c, q.plan, B, rows, chans, dtype, method, 0, 1, true,
+                         BlockSink{keys, nbhd ? c->blk_nbhd.as<float>() + 9 * b0 : nullptr, 0, 0}));
+        hipLaunchKernelGGL(blocks_record_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.units, keys, B.blocks, np, mode_min,
+                           recs);
+        HIPC(hipGetLastError());
+        b0 += q.blocks.size();
+        t0 += q.plan.tiles.size();
+    }
+
+    HIPC(hipEventRecord(c->ev[1], c->stream));
+    HIPC(hipMemcpyAsync(out, c->blk_recs.p, sizeof(mtm_hit) * n, hipMemcpyDeviceToHost, c->stream));
+    if (nbhd) HIPC(hipMemcpyAsync(nbhd, c->blk_nbhd.p, sizeof(float) * 9 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
+    c->timing.n_hits = (int64_t)n;
+    // the stack is none of the caller's images: no current image, no published maps
+    c->have_image = false;
+    return MTM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mtm_match_blocks_at(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                        int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
+                        const int32_t* offsets, int n_blocks, int margin, int method, mtm_hit* out, float* nbhd) {
+    const char* who = "mtm_match_blocks_at";
+    if (!c || n_blocks < 0 || margin < 0 || (n_blocks > 0 && (!blocks || !offsets || !out)) || method < MTM_TM_SQDIFF ||
+        method > MTM_TM_CCOEFF_NORMED) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    MTMC(check_image_args(reference, rows, cols, chans, dtype, reference_stride_bytes, who));
+    MTMC(check_image_args(image, rows, cols, chans, dtype, image_stride_bytes, who));
+    MTMC(check_block_images(who, "images", rows, chans, dtype));
+    std::vector<BlockPassPlan> Q(1);
+    Q[0].grid = BlockGrid{};
+    Q[0].margin = margin;
+    MTMC(plan_blocks(rows, cols, chans, dtype, blocks, n_blocks, margin, 4 * (long long)c->boxes_max_floats, who, Q[0].plan,
+                     false));
+    if (n_blocks == 0) return MTM_OK;
+    MTMC(fix_block_tiles(Q[0].plan, rows, cols, blocks, margin, who));
+    Q[0].blocks.assign(blocks, blocks + n_blocks);
+    return match_block_passes(c, reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype, Q,
+                              offsets, method, out, nbhd);
+}
+
+int mtm_match_blocks_passes(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                            int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                            const mtm_block_pass* passes, int n_passes, int method, mtm_hit* out, float* nbhd) {
+    const char* who = "mtm_match_blocks_passes";
+    if (!c || n_passes < 1 || !passes || !out || method < MTM_TM_SQDIFF || method > MTM_TM_CCOEFF_NORMED) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    MTMC(check_image_args(reference, rows, cols, chans, dtype, reference_stride_bytes, who));
+    MTMC(check_image_args(image, rows, cols, chans, dtype, image_stride_bytes, who));
+    MTMC(check_block_images(who, "images", rows, chans, dtype));
+    std::vector<BlockPassPlan> Q;
+    MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
+    return match_block_passes(c, reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype, Q,
+                              nullptr, method, out, nbhd);
+}
 
 int mtm_match_blocks(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
                      int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
@@ -355,7 +583,8 @@ int mtm_match_blocks(mtm_ctx* c, const void* reference, int64_t reference_stride
                                  chans, dtype, c->stream);
     }));
     unsigned long long* keys = c->blk_keys.as<unsigned long long>();
-    MTMC(blocks_pair(c, P, rows, chans, dtype, method, 0, 1, true, BlockSink{keys, nbhd ? c->blk_nbhd.as<float>() : nullptr, 0, 0}));
+    MTMC(blocks_pair(c, P, ctx_block_tables(c), rows, chans, dtype, method, 0, 1, true,
+                     BlockSink{keys, nbhd ? c->blk_nbhd.as<float>() : nullptr, 0, 0}));
 
     // the keys (and neighbourhoods) come back behind the call's single wait
     std::vector<unsigned long long> hkeys(n);
@@ -418,7 +647,7 @@ int mtm_match_blocks_stack(mtm_ctx* c, const void* const* frames, int n_frames, 
             const size_t p = (size_t)(S.p0 + i);
             const BlockSink sink{ens ? nullptr : c->blk_keys.as<unsigned long long>() + p * n,
                                  nbhd ? c->blk_nbhd.as<float>() + 9 * p * n : nullptr, ens ? (int)side : 0, p == 0 ? 1 : 0};
-            MTMC(blocks_pair(c, P, rows, chans, dtype, method, mode == MTM_BLOCKS_REF_FIRST ? 0 : i, i + 1,
+            MTMC(blocks_pair(c, P, ctx_block_tables(c), rows, chans, dtype, method, mode == MTM_BLOCKS_REF_FIRST ? 0 : i, i + 1,
                              !(gather_once && i > 0), sink));
         }
     }

@@ -381,6 +381,8 @@ struct mtm_ctx {
     // blocks' clip offsets (BlockPlan::clip) and the float64 sums of the ensemble planes (blk_acc: zeroed at the start of
     // a call, one writer per cell and launch).
     DevBuf blk_tpx, blk_toff, blk_td, blk_blocks, blk_units, blk_tiles, blk_keys, blk_nbhd, blk_clip, blk_acc;
+    // mtm_match_blocks_at / _passes: the records of every pass (24 B per block, resident for the call) and the uploaded offsets
+    DevBuf blk_recs, blk_offs;
     // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
     // template set sub_gen) and the per-call point table and scores.
     uint64_t sub_gen = 0;

@@ -635,7 +635,7 @@ int plan_tracks(const std::vector<BlobTempl>& tl, int rows, int cols, int chans,
 
 // ---- the host plan of a block-matching call (mtm_blocks.hip)
 int plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* blocks, int n_blocks, int margin,
-                long long budget_bytes, const char* who, BlockPlan& P) {
+                long long budget_bytes, const char* who, BlockPlan& P, bool with_tiles) {
     P = BlockPlan{};
     P.units.reserve((size_t)n_blocks);
     P.toff.reserve((size_t)n_blocks);
@@ -672,13 +672,81 @@ int plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* block
         P.clip.push_back((int32_t)((long long)margin - (b.y - y0)));
         cur.bytes += bytes;
         P.max_bytes = std::max(P.max_bytes, cur.bytes);
-        for (int ty = 0; ty < (int)oh; ty += kTrackTile)
+        for (int ty = 0; with_tiles && ty < (int)oh; ty += kTrackTile)
             for (int tx = 0; tx < (int)ow; tx += kTrackTile) P.tiles.push_back(TrackTile{k, 1, ty, tx});
     }
     if (n_blocks > 0) {
         cur.b1 = n_blocks;
         cur.t1 = P.tiles.size();
         P.chunks.push_back(cur);
+    }
+    return MTM_OK;
+}
+
+// ---- the fixed tile table and the passes of a call whose boxes the device computes (mtm_blocks.hip)
+int fix_block_tiles(BlockPlan& P, int rows, int cols, const mtm_block* blocks, int margin, const char* who) {
+    const long long side = 2ll * margin + 1;
+    const size_t n = P.units.size();
+    // block k's grid covers the largest map a moved block can have: 2 margin + 1 outputs per side, or the whole image's
+    auto span_h = [&](size_t k) { return std::min(side, (long long)rows - blocks[k].h + 1); };
+    auto span_w = [&](size_t k) { return std::min(side, (long long)cols - blocks[k].w + 1); };
+    unsigned long long total = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const long long oh = span_h(k), ow = span_w(k);
+        if (oh * ow >= (1ll << 32)) {
+            set_error(std::string(who) + ": block " + std::to_string(k) + ": map of 2^32 outputs or more");
+            return MTM_E_INVALID;
+        }
+        total += (unsigned long long)((oh + kTrackTile - 1) / kTrackTile) * (unsigned long long)((ow + kTrackTile - 1) / kTrackTile);
+    }
+    if (total >= (1ull << 31)) {
+        set_error(std::string(who) + ": " + std::to_string(n) + " blocks at margin " + std::to_string(margin) +
+                  " need 2^31 tiles or more");
+        return MTM_E_INVALID;
+    }
+    P.tiles.clear();
+    P.tiles.reserve((size_t)total);
+    for (BlockChunk& C : P.chunks) {
+        C.t0 = P.tiles.size();
+        for (int k = C.b0; k < C.b1; ++k) {
+            const int th = (int)span_h((size_t)k), tw = (int)span_w((size_t)k);
+            for (int ty = 0; ty < th; ty += kTrackTile)
+                for (int tx = 0; tx < tw; tx += kTrackTile) P.tiles.push_back(TrackTile{k, 1, ty, tx});
+        }
+        C.t1 = P.tiles.size();
+    }
+    return MTM_OK;
+}
+
+int plan_block_passes(int rows, int cols, int chans, int dtype, const mtm_block_pass* passes, int n_passes,
+                      long long budget_bytes, const char* who, std::vector<BlockPassPlan>& plans) {
+    plans.clear();
+    plans.resize((size_t)n_passes);
+    for (int p = 0; p < n_passes; ++p) {
+        const mtm_block_pass& a = passes[p];
+        BlockPassPlan& Q = plans[(size_t)p];
+        const std::string pw = std::string(who) + ": pass " + std::to_string(p);
+        if (a.bw < 1 || a.bh < 1 || a.sx < 1 || a.sy < 1 || a.margin < 0) {
+            set_error(pw + ": block and step must be >= 1 and the margin >= 0");
+            return MTM_E_INVALID;
+        }
+        Q.grid = block_grid_of(a, rows, cols);
+        Q.margin = a.margin;
+        const long long n = (long long)Q.grid.nx * Q.grid.ny;
+        if (n < 1) {
+            set_error(pw + ": no " + std::to_string(a.bw) + " x " + std::to_string(a.bh) + " block fits the images (empty grid)");
+            return MTM_E_INVALID;
+        }
+        if (n > INT_MAX) {
+            set_error(pw + ": grid of 2^31 blocks or more");
+            return MTM_E_INVALID;
+        }
+        Q.blocks.reserve((size_t)n);
+        for (int iy = 0; iy < Q.grid.ny; ++iy)
+            for (int ix = 0; ix < Q.grid.nx; ++ix) Q.blocks.push_back(mtm_block{ix * a.sx, iy * a.sy, a.bw, a.bh});
+        int rc = plan_blocks(rows, cols, chans, dtype, Q.blocks.data(), (int)n, a.margin, budget_bytes, pw.c_str(), Q.plan, false);
+        if (rc == MTM_OK) rc = fix_block_tiles(Q.plan, rows, cols, Q.blocks.data(), a.margin, pw.c_str());
+        if (rc != MTM_OK) return rc;
     }
     return MTM_OK;
 }
@@ -793,6 +861,57 @@ int mtm_debug_plan_blocks_stack(int n_frames, int frames_per_chunk, int mode, in
                                         "mtm_debug_plan_blocks_stack", P);
         if (rc != MTM_OK) return rc;
         std::copy(P.clip.begin(), P.clip.end(), clip);
+    }
+    return MTM_OK;
+}
+
+int mtm_debug_plan_blocks_passes(int rows, int cols, int chans, int dtype, const mtm_block_pass* passes, int n_passes,
+                                 int64_t budget_bytes, int64_t* counts, int32_t* tiles, int64_t tile_cap, int64_t* n_tiles,
+                                 int32_t* chunk_of, const mtm_hit* coarse, int at_pass, int32_t* pred, int32_t* maps) {
+    if (rows < 1 || cols < 1 || n_passes < 1 || !passes || tile_cap < 0 ||
+        (coarse && (at_pass < 1 || at_pass >= n_passes)) ||
+        !((dtype == MTM_U8 && (chans == 1 || chans == 3)) || (dtype == MTM_U16 && chans == 1))) {
+        mtm::set_error("mtm_debug_plan_blocks_passes: bad arguments");
+        return MTM_E_INVALID;
+    }
+    std::vector<mtm::BlockPassPlan> Q;
+    const int rc = mtm::plan_block_passes(rows, cols, chans, dtype, passes, n_passes, budget_bytes,
+                                          "mtm_debug_plan_blocks_passes", Q);
+    if (rc != MTM_OK) return rc;
+    int64_t nt = 0, base = 0;
+    for (int p = 0; p < n_passes; ++p) {
+        const mtm::BlockPlan& P = Q[(size_t)p].plan;
+        if (counts) counts[p] = (int64_t)P.units.size();
+        for (size_t i = 0; i < P.tiles.size(); ++i, ++nt)
+            if (tiles && nt < tile_cap) {
+                tiles[4 * nt] = p;
+                tiles[4 * nt + 1] = P.tiles[i].u0;
+                tiles[4 * nt + 2] = P.tiles[i].ty0;
+                tiles[4 * nt + 3] = P.tiles[i].tx0;
+            }
+        for (size_t ci = 0; chunk_of && ci < P.chunks.size(); ++ci)
+            for (int k = P.chunks[ci].b0; k < P.chunks[ci].b1; ++k) chunk_of[base + k] = (int32_t)ci;
+        base += (int64_t)P.units.size();
+    }
+    if (n_tiles) *n_tiles = nt;
+    if (coarse) {
+        const mtm::BlockPassPlan& F = Q[(size_t)at_pass];
+        const mtm::BlockGrid& G = Q[(size_t)at_pass - 1].grid;
+        for (size_t k = 0; k < F.blocks.size(); ++k) {
+            long long dx, dy;
+            mtm::blocks_predict_inl(G, coarse, F.blocks[k], &dx, &dy);
+            const mtm::BlockUnitBox u = mtm::blocks_unit_at_inl(F.blocks[k], dx, dy, F.margin, rows, cols);
+            if (pred) {
+                pred[2 * k] = (int32_t)dx;
+                pred[2 * k + 1] = (int32_t)dy;
+            }
+            if (maps) {
+                maps[4 * k] = u.x0;
+                maps[4 * k + 1] = u.y0;
+                maps[4 * k + 2] = u.ow;
+                maps[4 * k + 3] = u.oh;
+            }
+        }
     }
     return MTM_OK;
 }

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/mtm_hip.h"
+#include "mtm_blocks_predict.h"    // BlockGrid, the shared predict and box functions
 #include "mtm_route.h"
 #include "mtm_templ_stats.h"       // TemplStats, templ_stats_from_sums_inl
 
@@ -165,8 +166,31 @@ struct BlockPlan {
 // box widened by `margin` on every side and clipped to the image (MTM.blocks.search_box), its map that of a template of
 // the block's size over the box.  Chunks hold whole blocks while their template bytes - w h chans, uint16: 2 w h - stay
 // within budget_bytes.  MTM_OK, or the code and message (set_error, prefixed `who`) of the first block that is not valid.
+// with_tiles = false leaves the tile table empty, for fix_block_tiles to fill.
 int plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* blocks, int n_blocks, int margin,
-                long long budget_bytes, const char* who, BlockPlan& plan);
+                long long budget_bytes, const char* who, BlockPlan& plan, bool with_tiles = true);
+
+// ---- block matching with boxes the device computes (mtm_match_blocks_at, mtm_match_blocks_passes, mtm_blocks.hip)
+
+// The plan's tile table replaced by the fixed one: T^2 tiles per block, T = ceil((2 margin + 1) / 16), row-major, whatever
+// the block's clipped map - the kernel leaves the tiles that lie outside the map the device computed.  (Per axis never
+// more tiles than the whole image's map of the block has: no moved box has a larger one.)  The chunks keep
+// their blocks and get the new tile ranges; the units stay those of zero offsets.  MTM_E_INVALID (set_error, prefixed
+// `who`) when the table would hold 2^31 tiles or more, or a moved block could have a map of 2^32 outputs or more.
+int fix_block_tiles(BlockPlan& plan, int rows, int cols, const mtm_block* blocks, int margin, const char* who);
+
+// One pass of a mtm_match_blocks_passes call: its grid, the grid's blocks in row-major order and their plan with the
+// fixed tile table.
+struct BlockPassPlan {
+    BlockGrid grid;
+    int margin;
+    std::vector<mtm_block> blocks;
+    BlockPlan plan;
+};
+// The passes of a call checked and laid out (plan_blocks and fix_block_tiles per pass).  MTM_OK, or the code and message
+// (set_error, prefixed `who`) of the first pass that is not valid; a pass whose grid is empty is not.
+int plan_block_passes(int rows, int cols, int chans, int dtype, const mtm_block_pass* passes, int n_passes,
+                      long long budget_bytes, const char* who, std::vector<BlockPassPlan>& plans);
 
 // ---- the frame chunks of a block-matching call over a frame stack (mtm_match_blocks_stack, mtm_blocks.hip)
 

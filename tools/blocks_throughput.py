@@ -23,7 +23,18 @@ frames of noise around a weak pattern that moves by (2, 1) a frame (``noisy_movi
 deviations above the correlation noise of a block), the fraction of blocks found at that step by the pairs' own peaks
 (``noisy_found_pairs``, mean over the pairs) and by the ensemble peak (``noisy_found_ensemble``).
 
-Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F]
+--passes: coarse to fine instead - milliseconds per call of
+  single    - matchBlocks(reference, image, grid, margin): today's single pass at the workload's margin
+  multipass - matchBlocksMultipass with a sparse wide pass (the workload's block at stride 2 x the block, the workload's
+              margin) and a dense pass (the workload's grid, a quarter of the margin)
+  by_hand   - the same two passes as the loop of matchBlocks(offsets=) and predict_offsets a user writes
+with ``equal_to_loop`` (multipass against by_hand, every pass, positions and score bits) and, on a pair whose four quadrants
+moved by four different known shifts within the workload's margin, with noise (``quadrant_pair``), the share of the blocks
+that lie clear of the quadrants' seams found at their true displacement by the single pass and by the dense pass of
+multipass (``found_single``, ``found_multipass``).  One further line (workload "K1 far") moves the whole image by more than
+the dense margin: the dense grid alone at the dense margin against the two passes.
+
+Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F] [--passes]
 """
 import argparse
 import json
@@ -198,12 +209,113 @@ def run_stack(MTM, spec, n_frames, reps, warmup):
     }
 
 
+def quadrant_pair(spec, seed=0):
+    """A reference and an image whose four quadrants are the reference's moved by four different shifts (dx, dy) within the
+    workload's margin, with a little noise: (ref, img, shifts (2, 2, 2) by quadrant row and column)."""
+    name, hw, chans, dtype, side, margin = spec
+    ref, _ = workload(spec, seed)
+    m = margin
+    shifts = np.array([[(m - 1, -(m // 2)), (-(m - 2), 3)], [(2, m - 1), (-(m // 2 + 1), -(m - 1))]])
+    rng = np.random.default_rng(seed + 40)
+    top = 65535 if ref.dtype == np.uint16 else 255
+    H, W = hw
+    img = np.empty_like(ref)
+    for qy, (y0, y1) in enumerate(((0, H // 2), (H // 2, H))):
+        for qx, (x0, x1) in enumerate(((0, W // 2), (W // 2, W))):
+            dx, dy = (int(v) for v in shifts[qy, qx])
+            img[y0:y1, x0:x1] = np.roll(ref, (dy, dx), axis=(0, 1))[y0:y1, x0:x1]
+    img = img.astype(np.int64) + rng.integers(-2, 3, size=ref.shape)
+    return ref, np.clip(img, 0, top).astype(ref.dtype), shifts
+
+
+def found_share(B, grid, pos, shape, shifts, margin):
+    """The share of the blocks clear of the image's border and of the quadrants' seams (by a block and the margin) whose
+    displacement is their quadrant's shift."""
+    H, W = shape[0], shape[1]
+    x, y, w, h = grid[:, 0], grid[:, 1], grid[:, 2], grid[:, 3]
+    qx, qy = (x >= W // 2).astype(int), (y >= H // 2).astype(int)
+    pad = margin + 1
+    clear = (x >= pad) & (x + w <= W - pad) & (y >= pad) & (y + h <= H - pad)
+    clear &= np.where(qx == 0, x + w + pad <= W // 2, x - pad >= W // 2)
+    clear &= np.where(qy == 0, y + h + pad <= H // 2, y - pad >= H // 2)
+    d = B.displacements(grid, pos)
+    return float(np.mean((d[clear] == shifts[qy[clear], qx[clear]]).all(axis=1))), int(clear.sum())
+
+
+def run_passes(MTM, spec, reps, warmup, far=False):
+    from MTM import blocks as B
+    name, hw, chans, dtype, side, margin = spec
+    ref, img = workload(spec, shift=(margin - 1, -(margin - 2))) if far else workload(spec)
+    method = MTM.TM_CCOEFF_NORMED
+    fine_margin = max(1, margin // 4)
+    passes = [(side, 2 * side, margin), (side, side, fine_margin)]
+    grid = B.grid(ref.shape, side)
+    single_margin = fine_margin if far else margin
+
+    def by_hand(r=ref, i=img):
+        out, off, steer = [], None, None
+        for p, (block, step, m) in enumerate(passes):
+            b = B.grid(i.shape, block, step)
+            if p:
+                off = B.predict_offsets(i.shape, passes[p - 1][:2], steer, passes[p][:2])
+            steer, sc = MTM.matchBlocks(r, i, b, m, method, offsets=off)
+            out.append((b, steer, sc))
+        return out
+
+    methods = {
+        "single": lambda: MTM.matchBlocks(ref, img, grid, single_margin, method),
+        "multipass": lambda: MTM.matchBlocksMultipass(ref, img, passes, method),
+        "by_hand": by_hand,
+    }
+    results = {}
+    for k, fn in methods.items():
+        for _ in range(warmup):
+            results[k] = fn()
+    ms = {k: [] for k in methods}
+    for _ in range(reps):
+        for k, fn in methods.items():
+            t0 = time.perf_counter()
+            fn()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    equal = all(bool((a[0] == b[0]).all() and (a[1] == b[1]).all() and a[2].tobytes() == b[2].tobytes())
+                for a, b in zip(results["multipass"], results["by_hand"]))
+    tiles = lambda n, m: n * (-(-(2 * m + 1) // 16)) ** 2      # noqa: E731
+    out = {
+        "workload": name + (" far" if far else ""), "image": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype),
+        "blocks": int(len(grid)), "block": side, "single_margin": single_margin,
+        "passes": [[b, st, m] for b, st, m in passes], "pass_blocks": [int(len(r[0])) for r in results["multipass"]],
+        "tile_ratio": round(sum(tiles(len(r[0]), p[2]) for r, p in zip(results["multipass"], passes)) /
+                            tiles(len(grid), margin), 3),
+        "ms": {k: round(v, 3) for k, v in med.items()},
+        "ms_min": {k: round(min(v), 3) for k, v in ms.items()},
+        "multipass_vs_single": round(med["single"] / med["multipass"], 2),
+        "multipass_vs_by_hand": round(med["by_hand"] / med["multipass"], 2),
+        "equal_to_loop": equal, "reps": reps,
+    }
+    if far:
+        shift = (margin - 1, -(margin - 2))
+        inner = (grid[:, 0] >= 2 * side) & (grid[:, 1] >= 2 * side) & (grid[:, 0] + 3 * side <= hw[1]) & \
+            (grid[:, 1] + 3 * side <= hw[0])
+        share = lambda pos: round(float(np.mean((B.displacements(grid, pos)[inner] == shift).all(axis=1))), 4)  # noqa: E731
+        out.update({"shift": list(shift), "found_single": share(results["single"][0]),
+                    "found_multipass": share(results["multipass"][1][1]), "blocks_counted": int(inner.sum())})
+    else:
+        qref, qimg, shifts = quadrant_pair(spec)
+        f_single, n_clear = found_share(B, grid, MTM.matchBlocks(qref, qimg, grid, margin, method)[0], hw, shifts, margin)
+        f_multi, _ = found_share(B, grid, MTM.matchBlocksMultipass(qref, qimg, passes, method)[1][1], hw, shifts, margin)
+        out.update({"quadrant_shifts": shifts.reshape(4, 2).tolist(), "found_single": round(f_single, 4),
+                    "found_multipass": round(f_multi, 4), "blocks_counted": n_clear})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--only", default=None, help="run the one workload of this name (profiling runs)")
     ap.add_argument("--stack", type=int, default=0, metavar="F", help="the movie form: matchBlocksStack over F frames")
+    ap.add_argument("--passes", action="store_true", help="coarse to fine: matchBlocksMultipass against the single pass")
     args = ap.parse_args()
     import build as mtm_build
     mtm_build.build()
@@ -211,7 +323,11 @@ def main():
     for spec in WORKLOADS:
         if args.only and spec[0] != args.only:
             continue
-        if args.stack:
+        if args.passes:
+            print(json.dumps(run_passes(MTM, spec, args.reps, args.warmup)), flush=True)
+            if spec[0] == "K1":
+                print(json.dumps(run_passes(MTM, spec, args.reps, args.warmup, far=True)), flush=True)
+        elif args.stack:
             if args.stack < 2:
                 ap.error("--stack needs two frames at least")
             print(json.dumps(run_stack(MTM, spec, args.stack, args.reps, args.warmup)), flush=True)

@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes, mtm_match_blocks_passes_validated, mtm_debug_validate_blocks - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -735,6 +735,34 @@ int mtm_match_blocks_passes(mtm_ctx* ctx, const void* reference, int64_t referen
 int mtm_debug_plan_blocks_passes(int rows, int cols, int chans, int dtype, const mtm_block_pass* passes, int n_passes,
                                  int64_t budget_bytes, int64_t* counts, int32_t* tiles, int64_t tile_cap, int64_t* n_tiles,
                                  int32_t* chunk_of, const mtm_hit* coarse, int at_pass, int32_t* pred, int32_t* maps);
+
+/* mtm_match_blocks_passes with outlier validation between the passes: after every pass its records go
+ * through the normalised median test (Westerweel & Scarano), and the next pass is steered by the validated records instead
+ * of the raw ones.  The grid of a pass is nx x ny blocks in row-major order, d = (dx, dy) = record position - block
+ * position.  The neighbours of a block are the blocks of its 3 x 3 grid neighbourhood that exist, without the block itself;
+ * a block with fewer than 3 neighbours is valid.  Per component u (dx, then dy) over the n >= 3 neighbour values, with
+ * dmed(s) = s[(n - 1) / 2] + s[n / 2] of the sorted values (the doubled median, int64): m2 = dmed(u_i), r_i = |2 u_i - m2|,
+ * rm4 = dmed(r_i), and the block is an outlier in the component iff (double)(2 |2 u_0 - m2|) > threshold * ((double)rm4 +
+ * 4.0 * epsilon) - one rounded float64 addition, one rounded float64 multiplication, no fused operation.  A block is invalid if
+ * either component is an outlier; the displacement that steers the next pass is then ((m2x + 1) >> 1, (m2y + 1) >> 1), the
+ * neighbours' median rounded half towards +infinity.  Only raw records are read - neighbours that are outliers themselves
+ * count as they are, nothing is iterated -, so the result depends on no order of evaluation.  out and nbhd are the RAW
+ * records and their neighbourhoods, exactly mtm_match_blocks_passes' layout; valid (required): one byte per record in
+ * the same pass-major order, 1 = valid, 0 = outlier; the last pass is validated too.  threshold and epsilon must be
+ * finite and >= 0 (MTM_E_INVALID names the argument).  One small launch per pass more than mtm_match_blocks_passes; the
+ * flags come back behind the call's single wait.  Everything else as mtm_match_blocks_passes. */
+int mtm_match_blocks_passes_validated(mtm_ctx* ctx, const void* reference, int64_t reference_stride_bytes, const void* image,
+                                      int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                                      const mtm_block_pass* passes, int n_passes, int method, double threshold,
+                                      double epsilon, mtm_hit* out, float* nbhd, uint8_t* valid);
+
+/* Test support: the median test of mtm_match_blocks_passes_validated over one grid of records.  recs: nx * ny records in
+ * row-major order, block (iy, ix) at (ix sx, iy sy).  valid[k] = 1 / 0 as above; steer[k] = recs[k], or for an outlier
+ * recs[k] with x, y = block position + replacement displacement.  ctx == NULL runs the rule on the host (no GPU); with a
+ * context the records are uploaded, the validation kernel is launched once and its output comes back.  nx, ny, sx, sy >=
+ * 1, nx * ny < 2^31; threshold and epsilon as above. */
+int mtm_debug_validate_blocks(mtm_ctx* ctx, const mtm_hit* recs, int nx, int ny, int sx, int sy, double threshold,
+                              double epsilon, uint8_t* valid, mtm_hit* steer);
 
 /* The 3 x 3 score neighbourhoods of n points in one call: out[9 k + 3 (1 + dy) + (1 + dx)] = the score of
  * template pts[k].templ_idx at window (x + dx, y + dy) of the image's score map, NaN for a window outside the map.  Image:

@@ -224,6 +224,13 @@ SYMBOLS = {
                                                     ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_int64, _P(ctypes.c_int64), ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "mtm_match_blocks_passes_validated": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                         ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                                         ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mtm_debug_validate_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
+                                                 ctypes.c_void_p]),
     "mtm_hit_neighbourhoods": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
@@ -578,6 +585,30 @@ def debug_plan_blocks_passes(shape, chans, dtype, passes, budget_bytes, coarse=N
                                            pred.ctypes.data if rec is not None else None,
                                            maps.ctypes.data if rec is not None else None), "mtm_debug_plan_blocks_passes")
     return (counts, tiles, chunk_of) if coarse is None else (counts, tiles, chunk_of, pred, maps)
+
+
+def debug_validate_blocks(positions, grid_shape, step, threshold=2.0, epsilon=0.5, context=None):
+    """Test support (mtm_debug_validate_blocks): the median test of mtm_match_blocks_passes_validated over one grid of
+    records.  `positions`: the (ny * nx, 2) integer (x, y) found for the blocks of a `grid_shape` = (ny, nx) grid in
+    row-major order, block (iy, ix) at (ix * sx, iy * sy) with `step` = (sx, sy).  Returns (valid (N,) bool, steer (N, 2)
+    int64): the flags and the positions that steer a next pass (an outlier's: block position + the neighbours' median
+    displacement).  `context=None` runs the rule in the library's host code, no GPU needed; with a Context the records go
+    through blocks_validate_kernel."""
+    ny, nx = (int(v) for v in grid_shape)
+    sx, sy = (int(v) for v in step)
+    pos = np.asarray(positions).reshape(-1, 2)
+    if len(pos) != nx * ny:
+        raise ValueError("debug_validate_blocks: %d positions for a grid of %d x %d blocks" % (len(pos), ny, nx))
+    rec = np.zeros(len(pos), dtype=HIT_DTYPE)
+    rec["templ_idx"] = np.arange(len(pos))
+    rec["x"], rec["y"] = pos[:, 0], pos[:, 1]
+    valid = np.zeros(len(pos), dtype=np.uint8)
+    steer = np.zeros(len(pos), dtype=HIT_DTYPE)
+    lib = load() if context is None else context._lib
+    check(lib.mtm_debug_validate_blocks(None if context is None else context._h, rec.ctypes.data, nx, ny, sx, sy,
+                                        float(threshold), float(epsilon), valid.ctypes.data, steer.ctypes.data),
+          "mtm_debug_validate_blocks")
+    return valid.astype(bool), np.stack((steer["x"], steer["y"]), axis=1).astype(np.int64)
 
 
 def debug_templ_stats(template, method):
@@ -1040,10 +1071,16 @@ class Context(_RecordMemo):
                                             out.ctypes.data, nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks_at")
         return out, nbhd
 
-    def match_blocks_passes(self, reference, image, passes, counts, method, with_nbhd=False):
+    def debug_validate_blocks(self, positions, grid_shape, step, threshold=2.0, epsilon=0.5):
+        """Test support: the module's debug_validate_blocks on this context - blocks_validate_kernel, launched once."""
+        return debug_validate_blocks(positions, grid_shape, step, threshold, epsilon, context=self)
+
+    def match_blocks_passes(self, reference, image, passes, counts, method, with_nbhd=False, validate=None):
         """Coarse-to-fine block matching in one native call (mtm_match_blocks_passes): `passes` BLOCK_PASS_DTYPE records,
         `counts` the blocks of every pass's grid.  Returns (records, pass-major, sum(counts) of them; neighbourhoods in
-        the same order, or None).  The templates set on the context are not touched."""
+        the same order, or None).  The templates set on the context are not touched.
+        `validate` = (threshold, epsilon): the median test between the passes (mtm_match_blocks_passes_validated); a third
+        element is returned, the (sum(counts),) bool flags of the records in the same order."""
         passes = block_pass_records(passes)
         n = int(sum(counts))
         out = np.empty(n, dtype=HIT_DTYPE)
@@ -1051,6 +1088,15 @@ class Context(_RecordMemo):
         r, rptr, rstride = _pixel_rows(reference)
         a, aptr, astride = _pixel_rows(image)
         chans = 1 if a.ndim == 2 else a.shape[2]
+        if validate is not None:
+            threshold, epsilon = validate
+            valid = np.zeros(n, dtype=np.uint8)
+            check(self._lib.mtm_match_blocks_passes_validated(self._h, rptr, rstride, aptr, astride, a.shape[0], a.shape[1],
+                                                              chans, _dtype_code(a), passes.ctypes.data, len(passes),
+                                                              int(method), float(threshold), float(epsilon), out.ctypes.data,
+                                                              nbhd.ctypes.data if with_nbhd else None, valid.ctypes.data),
+                  "mtm_match_blocks_passes_validated")
+            return out, nbhd, valid.astype(bool)
         check(self._lib.mtm_match_blocks_passes(self._h, rptr, rstride, aptr, astride, a.shape[0], a.shape[1], chans,
                                                 _dtype_code(a), passes.ctypes.data, len(passes), int(method), out.ctypes.data,
                                                 nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks_passes")

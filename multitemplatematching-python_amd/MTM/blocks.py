@@ -33,6 +33,9 @@ reference, uint16 blocks of at most 2^21 pixels, ``margin`` an integer >= 0.
 ``matchBlocksMultipass`` is the coarse-to-fine scheme built on it (mtm_match_blocks_passes): a sparse pass
 with a wide margin finds the large motion, every later pass searches a small margin around what the nearest block of the
 pass before found (``predict_offsets``) - one native call, the boxes of the later passes computed on the device.
+``validate=`` runs the normalised median test (``validate``) over every pass's displacements on the device before they
+steer the next pass: a coarse block that matched wrongly - a flat, periodic or occluded patch - is steered by its
+neighbours' median instead of misleading every fine block nearest to it.
 
 ``matchBlocksStack`` is the movie form: the pairs of a stack of frames - each frame against the previous or against the
 first - in one native call (mtm_match_blocks_stack), every frame uploaded once; per pair the very results of
@@ -47,7 +50,7 @@ from . import _lib, subpixel
 from . import TM_CCOEFF_NORMED
 
 __all__ = ["matchBlocks", "matchBlocksStack", "matchBlocksMultipass", "plane_peaks", "grid", "search_box", "search_box_at",
-           "predict_offsets", "displacements"]
+           "predict_offsets", "displacements", "grid_shape", "validate"]
 
 _I64 = np.dtype(np.int64)
 _U16_MAX_PIXELS = 1 << 21       # mtm_match_blocks: uint16 correlations stay below 2^53, exact in float64
@@ -114,6 +117,87 @@ def grid(shape, block, step=None):
     out[:, 2] = w
     out[:, 3] = h
     return out
+
+
+def grid_shape(shape, block, step=None):
+    """``(ny, nx)``: the rows and columns of blocks of ``grid(shape, block, step)`` (block ``iy * nx + ix`` is in row iy
+    and column ix)."""
+    _, _, _, _, nx, ny = _grid_axes(shape, block, step, "grid_shape")
+    return ny, nx
+
+
+def _check_validate_params(threshold, epsilon, who):
+    for name, v in (("threshold", threshold), ("epsilon", epsilon)):
+        if not isinstance(v, numbers.Real) or isinstance(v, (bool, np.bool_)) or not np.isfinite(v) or v < 0:
+            raise ValueError("%s: %s must be a finite number >= 0 (got %r)" % (who, name, v))
+    return float(threshold), float(epsilon)
+
+
+_NEIGHBOURS = tuple((oy, ox) for oy in (-1, 0, 1) for ox in (-1, 0, 1) if (oy, ox) != (0, 0))
+
+
+def _doubled_median(values, present, n):
+    """Along axis 0: s[(n - 1) // 2] + s[n // 2] of the sorted ``values`` that are ``present`` (n >= 1 of them)."""
+    s = np.sort(np.where(present, values, np.iinfo(np.int64).max), axis=0)
+    return (np.take_along_axis(s, ((n - 1) // 2)[None], axis=0) + np.take_along_axis(s, (n // 2)[None], axis=0))[0]
+
+
+def validate(grid_shape, displacements, threshold=2.0, epsilon=0.5):
+    """The normalised median test (Westerweel & Scarano) over a displacement field, in plain numpy - the rule
+    ``matchBlocksMultipass(validate=)`` runs on the device between its passes (mtm_blocks_validate.h).
+    ``grid_shape``: ``(ny, nx)``; ``displacements``: the integer (ny * nx, 2) ``(dx, dy)`` of the grid's blocks in
+    row-major order.  Returns ``(valid, replaced)``: ``valid`` bool (N,), and ``replaced`` int64 (N, 2), the input with
+    every outlier's row substituted.
+
+    The neighbours of a block are the blocks of its 3 x 3 grid neighbourhood that exist, without the block itself; a
+    block with fewer than 3 of them is valid (every block of a 1 x n or n x 1 grid).  Per component u over the n >= 3
+    neighbour values, in integers: ``m2 = dmed(u_i)`` with ``dmed(s) = s[(n - 1) // 2] + s[n // 2]`` of the sorted
+    values (the doubled median), ``r_i = |2 u_i - m2|``, ``rm4 = dmed(r_i)``; the block is an outlier in the component iff
+    ``float64(2 |2 u_0 - m2|) > threshold * (float64(rm4) + 4.0 * epsilon)``.  A block is invalid if either component is
+    an outlier, and its row becomes ``((m2x + 1) >> 1, (m2y + 1) >> 1)``: the neighbours' median, rounded half towards
+    +infinity.  Only the input is read - neighbours that are outliers themselves count as they are, nothing is iterated.
+
+    The defaults are for integer fields: in a uniform neighbourhood (rm4 = 0) a deviation of 1 px passes (4 > 4 is
+    false) and 2 px is flagged; a sub-pixel epsilon such as 0.1 would flag every 1-px step.  Float displacements raise
+    TypeError (refined positions never steer a pass); bad shapes and a negative or non-finite threshold or epsilon raise
+    ValueError.
+    """
+    try:
+        ny, nx = grid_shape
+    except (TypeError, ValueError):
+        raise ValueError("validate: grid_shape must be (ny, nx) (got %r)" % (grid_shape,)) from None
+    if not _is_int(ny) or not _is_int(nx) or ny < 0 or nx < 0:
+        raise ValueError("validate: grid_shape must be two integers >= 0 (got %r)" % (grid_shape,))
+    ny, nx = int(ny), int(nx)
+    threshold, epsilon = _check_validate_params(threshold, epsilon, "validate")
+    d = np.asarray(displacements)
+    if d.ndim != 2 or d.shape[1] != 2 or len(d) != ny * nx:
+        raise ValueError("validate: displacements of shape %s for a grid of %d x %d blocks (expected (%d, 2))" % (
+            d.shape, ny, nx, ny * nx))
+    if d.dtype.kind not in "iu":
+        raise TypeError("validate: displacements must be integers (got %s): refined positions never steer a pass" % d.dtype)
+    d = d.astype(_I64)
+    if ny * nx == 0:
+        return np.zeros(0, bool), d
+    u0 = d.reshape(ny, nx, 2)
+    values = np.zeros((8, ny, nx, 2), _I64)
+    present = np.zeros((8, ny, nx, 1), bool)
+    for j, (oy, ox) in enumerate(_NEIGHBOURS):
+        ys, xs = slice(max(0, -oy), ny - max(0, oy)), slice(max(0, -ox), nx - max(0, ox))
+        yn, xn = slice(max(0, oy), ny - max(0, -oy)), slice(max(0, ox), nx - max(0, -ox))
+        values[j, ys, xs] = u0[yn, xn]
+        present[j, ys, xs] = True
+    n = present.sum(axis=0)
+    tested = n >= 3
+    n = np.maximum(n, 1)
+    m2 = np.where(tested, _doubled_median(values, present, n), 0)
+    rm4 = np.where(tested, _doubled_median(np.abs(2 * values - m2), present, n), 0)
+    lhs = (2 * np.abs(2 * u0 - m2)).astype(np.float64)
+    with np.errstate(over="ignore"):
+        rhs = np.float64(threshold) * (rm4.astype(np.float64) + np.float64(4.0 * epsilon))
+    valid = ~(tested & (lhs > rhs)).any(axis=2)
+    replaced = np.where(valid[:, :, None], u0, (m2 + 1) >> 1)
+    return valid.reshape(-1), replaced.reshape(-1, 2)
 
 
 def _nearest(n, s, wc, x, wf):
@@ -293,7 +377,7 @@ def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, m
 
 
 def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, method: int = TM_CCOEFF_NORMED, *,
-                         refine: bool = False, context=None):
+                         refine: bool = False, context=None, validate=None):
     """
     Coarse-to-fine block matching in one native call.  ``passes``: a non-empty sequence of ``(block, step, margin)``,
     ``block`` and ``step`` as ``grid`` takes them (``step=None``: the block size).  Pass 0 is ``matchBlocks`` over its
@@ -309,12 +393,37 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
 
     The integer positions steer the next pass, never the refined ones.  Scope and checks as ``matchBlocks``'; a pass whose
     grid is empty raises ValueError.  The templates set on the context are left alone.
+
+    ``validate``: ``None`` (the call above, in every respect), ``True`` (threshold 2.0, epsilon 0.5) or ``(threshold,
+    epsilon)``: the normalised median test of ``validate`` runs on the device over every pass's displacements, and an
+    outlier steers the next pass by its neighbours' median instead of by what it found (mtm_match_blocks_passes_validated:
+    still one native call, one small launch per pass more).  Every pass's tuple is then ``(blocks_p, positions_p,
+    scores_p, valid_p)``, ``valid_p`` the bool flags of the pass - the last pass is tested too.  ``positions_p`` and
+    ``scores_p`` stay the raw matches (refined positions with ``refine=True``): validation only changes what steers the
+    next pass.  This equals the loop
+
+        steer = None
+        for p, (block, step, margin) in enumerate(passes):
+            b = grid(image.shape, block, step)
+            off = None if p == 0 else predict_offsets(image.shape, passes[p - 1][:2], steer, passes[p][:2])
+            pos, sc = matchBlocks(reference, image, b, margin, method, offsets=off)
+            valid, rep = validate(grid_shape(image.shape, block, step), displacements(b, pos), threshold, epsilon)
+            steer = b[:, :2] + rep
+
+    (and ``matchBlocks(..., offsets=off, refine=True)`` for the refined positions).
     """
     _check_images(reference, image)
     if not _is_int(method) or method not in (0, 1, 2, 3, 4, 5):
         raise ValueError("matchBlocksMultipass takes methods 0..5 (got %r)" % (method,))
     if not isinstance(refine, bool):
         raise ValueError("refine must be True or False (got %r)" % (refine,))
+    if validate is not None:
+        if validate is True:
+            validate = (2.0, 0.5)
+        else:
+            if isinstance(validate, (bool, np.bool_, str)) or not hasattr(validate, "__len__") or len(validate) != 2:
+                raise ValueError("validate must be None, True or (threshold, epsilon) (got %r)" % (validate,))
+            validate = _check_validate_params(validate[0], validate[1], "validate")
     try:
         pl = list(passes)
     except TypeError:
@@ -344,7 +453,10 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
     counts = [len(g) for g in grids]
     ctx = context or _lib.default_context()     # (only now: every argument error comes before "no GPU")
     with ctx.lock:
-        raw, nbhd = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine)
+        if validate is None:
+            raw, nbhd = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine)
+        else:
+            raw, nbhd, flags = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine, validate=validate)
     positions = np.stack((raw["x"], raw["y"]), axis=1).astype(_I64)
     scores = raw["score"].astype(np.float32)
     if refine:          # (one fit over every pass and block: matchBlocks' numbers by construction)
@@ -352,7 +464,8 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
         positions = positions.astype(np.float64) + np.stack((ox, oy), axis=1)
     out, at = [], 0
     for g in grids:
-        out.append((g, positions[at:at + len(g)], scores[at:at + len(g)]))
+        res = (g, positions[at:at + len(g)], scores[at:at + len(g)])
+        out.append(res if validate is None else res + (np.asarray(flags[at:at + len(g)], dtype=bool),))
         at += len(g)
     return out
 

@@ -21,10 +21,14 @@
 // over a fixed tile table and leaves the tiles outside the unit's map, blocks_record_kernel decodes the keys into records
 // on the device, which the next pass and the final copy read.  One chain (match_block_passes) behind both, through
 // blocks_pair; every pass has its own row of keys, records and neighbourhoods.
+// mtm_match_blocks_passes_validated runs the same chain with blocks_validate_kernel behind every pass's
+// blocks_record_kernel: the median test of mtm_blocks_validate.h (the single source of host and device) over the pass's
+// records, a flag per record and the records that steer the next pass instead of the raw ones.
 #include <climits>
 #include <type_traits>
 
 #include "mtm_blocks_predict.h"
+#include "mtm_blocks_validate.h"
 #include "mtm_ctx.h"
 #include "mtm_device_util.hip.h"
 #include "mtm_k_nbhd.hip.h"
@@ -193,6 +197,28 @@ __global__ __launch_bounds__(256) void blocks_record_kernel(const TrackUnit* __r
     r.h = blocks[k].h;
     r.score = key ? (mode_min ? -q : q) + 0.0f : __builtin_nanf("");
     recs[k] = r;
+}
+
+// One lane per block k < nx ny of a pass's grid, after the pass's blocks_record_kernel: the median test of the block's
+// displacement against those of its 3 x 3 grid neighbourhood (blocks_validate_inl: raw records only, so no lane waits for
+// another) - valid[k] = 1 / 0, and steer[k] = the record that steers the next pass: recs[k], or for an outlier recs[k]
+// moved to block position + the neighbours' median.  Every neighbour index is checked against the grid before its
+// record is read.  No LDS and no scratch: the eight values are sorted in registers.
+__global__ __launch_bounds__(256) void blocks_validate_kernel(const mtm_hit* __restrict__ recs, int nx, int ny, int sx, int sy,
+                                                              double threshold, double e4, uint8_t* __restrict__ valid,
+                                                              mtm_hit* __restrict__ steer) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nx * ny) return;
+    const int ix = k % nx, iy = k / nx;
+    long long dx, dy;
+    const bool ok = blocks_validate_inl(recs, nx, ny, sx, sy, ix, iy, threshold, e4, &dx, &dy);
+    mtm_hit r = recs[k];
+    if (!ok) {
+        r.x = (int)((long long)ix * sx + dx);
+        r.y = (int)((long long)iy * sy + dy);
+    }
+    valid[k] = ok ? 1 : 0;
+    steer[k] = r;
 }
 
 // blocks_score_kernel's sibling for the ensemble planes of mtm_match_blocks_stack: the same tile and float32 score
@@ -420,14 +446,25 @@ void decode_block_keys(const BlockPlan& P, const mtm_block* blocks, const unsign
     }
 }
 
+// The median test a validated call runs behind every pass: its threshold, e4 = 4 epsilon (computed once, exact), and where
+// the flags of every record go, pass-major.
+struct BlockValidate {
+    double threshold, e4;
+    uint8_t* valid;
+};
+
 // The chain behind mtm_match_blocks_at (one pass over the caller's blocks, `offsets` uploaded) and
 // mtm_match_blocks_passes (offsets == nullptr): both images go up once; per pass the units - pass 0 without offsets: the
 // host's, of zero offsets; else blocks_unit_kernel's -, the pass's chain over its fixed tile table (blocks_pair) and
 // blocks_record_kernel, all in stream order, so a pass reads the finished records of the one before and no work-group
 // waits for another.  The records (and neighbourhoods) of every pass, pass-major, come back behind the call's single wait.
+// V != nullptr (mtm_match_blocks_passes_validated): blocks_validate_kernel behind every pass's records, the next pass's
+// units are predicted from its `steer` records instead of the raw ones, and the flags come back with the records.
+// V == nullptr launches and copies exactly what the chain did before validation existed.
 int match_block_passes(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
                        int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
-                       const std::vector<BlockPassPlan>& Q, const int32_t* offsets, int method, mtm_hit* out, float* nbhd) {
+                       const std::vector<BlockPassPlan>& Q, const int32_t* offsets, int method, mtm_hit* out, float* nbhd,
+                       const BlockValidate* V = nullptr) {
     // the tables of every pass, concatenated: one upload each
     std::vector<mtm_block> blocks;
     std::vector<long long> toff;
@@ -456,6 +493,10 @@ int match_block_passes(mtm_ctx* c, const void* reference, int64_t reference_stri
     MTMC(c->blk_recs.ensure(sizeof(mtm_hit) * n));
     if (nbhd) MTMC(c->blk_nbhd.ensure(sizeof(float) * 9 * n));
     if (offsets) MTMC(c->blk_offs.ensure(sizeof(int32_t) * 2 * n));
+    if (V) {
+        MTMC(c->blk_valid.ensure(n));
+        MTMC(c->blk_steer.ensure(sizeof(mtm_hit) * n));
+    }
 
     // ONE upload of each image, ahead of the call's clock (mtm_match_blocks' stack of two)
     adopt_image(c, 2 * rows, cols, chans, dtype);
@@ -484,9 +525,11 @@ int match_block_passes(mtm_ctx* c, const void* reference, int64_t reference_stri
         TrackUnit* dunits = c->blk_units.as<TrackUnit>() + b0;
         unsigned long long* keys = c->blk_keys.as<unsigned long long>() + b0;
         mtm_hit* recs = c->blk_recs.as<mtm_hit>() + b0;
+        // what steers this pass: the previous pass's records, validated or raw
+        const mtm_hit* prev = V ? c->blk_steer.as<mtm_hit>() + b0 : recs;
         if (p > 0 || offsets) {
             hipLaunchKernelGGL(blocks_unit_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.blocks, np,
-                               p > 0 ? nullptr : c->blk_offs.as<int32_t>(), p > 0 ? recs - Q[p - 1].blocks.size() : nullptr,
+                               p > 0 ? nullptr : c->blk_offs.as<int32_t>(), p > 0 ? prev - Q[p - 1].blocks.size() : nullptr,
                                p > 0 ? Q[p - 1].grid : BlockGrid{}, q.margin, rows, cols, dunits);
             HIPC(hipGetLastError());
         }
@@ -495,6 +538,12 @@ int match_block_passes(mtm_ctx* c, const void* reference, int64_t reference_stri
         hipLaunchKernelGGL(blocks_record_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.units, keys, B.blocks, np, mode_min,
                            recs);
         HIPC(hipGetLastError());
+        if (V) {        // (np = nx ny: plan_block_passes lays out the whole grid)
+            hipLaunchKernelGGL(blocks_validate_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, recs, q.grid.nx, q.grid.ny,
+                               q.grid.sx, q.grid.sy, V->threshold, V->e4, c->blk_valid.as<uint8_t>() + b0,
+                               c->blk_steer.as<mtm_hit>() + b0);
+            HIPC(hipGetLastError());
+        }
         b0 += q.blocks.size();
         t0 += q.plan.tiles.size();
     }
@@ -502,11 +551,22 @@ int match_block_passes(mtm_ctx* c, const void* reference, int64_t reference_stri
     HIPC(hipEventRecord(c->ev[1], c->stream));
     HIPC(hipMemcpyAsync(out, c->blk_recs.p, sizeof(mtm_hit) * n, hipMemcpyDeviceToHost, c->stream));
     if (nbhd) HIPC(hipMemcpyAsync(nbhd, c->blk_nbhd.p, sizeof(float) * 9 * n, hipMemcpyDeviceToHost, c->stream));
+    if (V) HIPC(hipMemcpyAsync(V->valid, c->blk_valid.p, n, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
     HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
     c->timing.n_hits = (int64_t)n;
     // the stack is none of the caller's images: no current image, no published maps
     c->have_image = false;
+    return MTM_OK;
+}
+
+// threshold and epsilon of the median test: finite and >= 0, else MTM_E_INVALID naming the argument.
+int check_validate_args(const char* who, double threshold, double epsilon) {
+    for (const auto& a : {std::make_pair("threshold", threshold), std::make_pair("epsilon", epsilon)})
+        if (!(a.second >= 0.0) || !std::isfinite(a.second)) {
+            set_error(std::string(who) + ": " + a.first + " must be finite and >= 0 (got " + std::to_string(a.second) + ")");
+            return MTM_E_INVALID;
+        }
     return MTM_OK;
 }
 
@@ -555,6 +615,69 @@ int mtm_match_blocks_passes(mtm_ctx* c, const void* reference, int64_t reference
     MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
     return match_block_passes(c, reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype, Q,
                               nullptr, method, out, nbhd);
+}
+
+int mtm_match_blocks_passes_validated(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                                      int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                                      const mtm_block_pass* passes, int n_passes, int method, double threshold,
+                                      double epsilon, mtm_hit* out, float* nbhd, uint8_t* valid) {
+    const char* who = "mtm_match_blocks_passes_validated";
+    MTMC(check_validate_args(who, threshold, epsilon));
+    if (!c || n_passes < 1 || !passes || !out || !valid || method < MTM_TM_SQDIFF || method > MTM_TM_CCOEFF_NORMED) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    MTMC(check_image_args(reference, rows, cols, chans, dtype, reference_stride_bytes, who));
+    MTMC(check_image_args(image, rows, cols, chans, dtype, image_stride_bytes, who));
+    MTMC(check_block_images(who, "images", rows, chans, dtype));
+    std::vector<BlockPassPlan> Q;
+    MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
+    const BlockValidate V{threshold, 4.0 * epsilon, valid};
+    return match_block_passes(c, reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype, Q,
+                              nullptr, method, out, nbhd, &V);
+}
+
+int mtm_debug_validate_blocks(mtm_ctx* c, const mtm_hit* recs, int nx, int ny, int sx, int sy, double threshold, double epsilon,
+                              uint8_t* valid, mtm_hit* steer) {
+    const char* who = "mtm_debug_validate_blocks";
+    if (!recs || !valid || !steer || nx < 1 || ny < 1 || sx < 1 || sy < 1 || (long long)nx * ny > INT_MAX) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    MTMC(check_validate_args(who, threshold, epsilon));
+    const size_t n = (size_t)nx * (size_t)ny;
+    const double e4 = 4.0 * epsilon;
+    if (!c) {           // the rule itself, on the host
+        for (int iy = 0; iy < ny; ++iy)
+            for (int ix = 0; ix < nx; ++ix) {
+                const size_t k = (size_t)iy * nx + ix;
+                long long dx, dy;
+                const bool ok = blocks_validate_inl(recs, nx, ny, sx, sy, ix, iy, threshold, e4, &dx, &dy);
+                mtm_hit r = recs[k];
+                if (!ok) {
+                    r.x = (int)((long long)ix * sx + dx);
+                    r.y = (int)((long long)iy * sy + dy);
+                }
+                valid[k] = ok ? 1 : 0;
+                steer[k] = r;
+            }
+        return MTM_OK;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    HIPC(hipSetDevice(c->device));
+    MTMC(c->blk_recs.ensure(sizeof(mtm_hit) * n));
+    MTMC(c->blk_valid.ensure(n));
+    MTMC(c->blk_steer.ensure(sizeof(mtm_hit) * n));
+    HIPC(hipMemcpyAsync(c->blk_recs.p, recs, sizeof(mtm_hit) * n, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(blocks_validate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
+                       c->blk_recs.as<mtm_hit>(), nx, ny, sx, sy, threshold, e4, c->blk_valid.as<uint8_t>(),
+                       c->blk_steer.as<mtm_hit>());
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(valid, c->blk_valid.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(steer, c->blk_steer.p, sizeof(mtm_hit) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return MTM_OK;
 }
 
 int mtm_match_blocks(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,

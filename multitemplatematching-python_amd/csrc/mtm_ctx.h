@@ -383,6 +383,9 @@ struct mtm_ctx {
     DevBuf blk_tpx, blk_toff, blk_td, blk_blocks, blk_units, blk_tiles, blk_keys, blk_nbhd, blk_clip, blk_acc;
     // mtm_match_blocks_at / _passes: the records of every pass (24 B per block, resident for the call) and the uploaded offsets
     DevBuf blk_recs, blk_offs;
+    // mtm_match_blocks_passes_validated / mtm_debug_validate_blocks: blocks_validate_kernel's flag per record (1 B) and the
+    // records that steer the next pass (the raw ones with every outlier's position replaced), pass-major as blk_recs
+    DevBuf blk_valid, blk_steer;
     // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
     // template set sub_gen) and the per-call point table and scores.
     uint64_t sub_gen = 0;

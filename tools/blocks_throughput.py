@@ -34,7 +34,17 @@ that lie clear of the quadrants' seams found at their true displacement by the s
 multipass (``found_single``, ``found_multipass``).  One further line (workload "K1 far") moves the whole image by more than
 the dense margin: the dense grid alone at the dense margin against the two passes.
 
-Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F] [--passes]
+--passes --validate: the same two passes with the median test between them - milliseconds per call of
+  validated   - matchBlocksMultipass(..., validate=True)
+  unvalidated - matchBlocksMultipass(...) of the same build
+  by_hand     - the loop of matchBlocks(offsets=), validate and predict_offsets the validated call documents
+with ``equal_to_loop`` (validated against by_hand, every pass, positions, score bits and flags), the difference between
+the validated and the unvalidated call (``validate_cost_ms``, medians of the same run) and, on the workload's pair with one
+flat patch planted in the reference over a coarse block (``flat_block_pair``), the share of the dense blocks outside the
+patch and clear of the border found at the true shift with and without validation (``found_validated``,
+``found_unvalidated``).
+
+Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F] [--passes [--validate]]
 """
 import argparse
 import json
@@ -309,6 +319,85 @@ def run_passes(MTM, spec, reps, warmup, far=False):
     return out
 
 
+def flat_block_pair(spec, passes, seed=0):
+    """The workload's pair with a flat patch planted in the reference over the middle block of the coarse pass's grid:
+    (ref, img, (x, y, w, h) of the patch).  Under TM_CCOEFF_NORMED the flat block scores 1.0 everywhere and lands on its
+    box's first output, a displacement of minus the coarse margin."""
+    from MTM import blocks as B
+    ref, img = workload(spec, seed)
+    block, step, _ = passes[0]
+    ny, nx = B.grid_shape(ref.shape, block, step)
+    x, y = (nx // 2) * step, (ny // 2) * step
+    ref = ref.copy()
+    ref[y:y + block, x:x + block] = 77
+    return ref, img, (x, y, block, block)
+
+
+def run_passes_validate(MTM, spec, reps, warmup):
+    from MTM import blocks as B
+    name, hw, chans, dtype, side, margin = spec
+    ref, img = workload(spec)
+    method = MTM.TM_CCOEFF_NORMED
+    fine_margin = max(1, margin // 4)
+    passes = [(side, 2 * side, margin), (side, side, fine_margin)]
+    threshold, epsilon = 2.0, 0.5
+
+    def by_hand(r=ref, i=img):
+        out, steer = [], None
+        for p, (block, step, m) in enumerate(passes):
+            b = B.grid(i.shape, block, step)
+            off = None if p == 0 else B.predict_offsets(i.shape, passes[p - 1][:2], steer, passes[p][:2])
+            pos, sc = MTM.matchBlocks(r, i, b, m, method, offsets=off)
+            valid, repl = B.validate(B.grid_shape(i.shape, block, step), B.displacements(b, pos), threshold, epsilon)
+            steer = b[:, :2] + repl
+            out.append((b, pos, sc, valid))
+        return out
+
+    methods = {
+        "validated": lambda: MTM.matchBlocksMultipass(ref, img, passes, method, validate=(threshold, epsilon)),
+        "unvalidated": lambda: MTM.matchBlocksMultipass(ref, img, passes, method),
+        "by_hand": by_hand,
+    }
+    results = {}
+    for k, fn in methods.items():
+        for _ in range(warmup):
+            results[k] = fn()
+    ms = {k: [] for k in methods}
+    for _ in range(reps):
+        for k, fn in methods.items():
+            t0 = time.perf_counter()
+            fn()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+
+    def same(x, y):
+        return all(bool((a[0] == b[0]).all() and (a[1] == b[1]).all() and a[2].tobytes() == b[2].tobytes() and
+                        (a[3] == b[3]).all()) for a, b in zip(x, y))
+
+    fref, fimg, (px, py, pw, ph) = flat_block_pair(spec, passes)
+    fval = MTM.matchBlocksMultipass(fref, fimg, passes, method, validate=(threshold, epsilon))
+    fraw = MTM.matchBlocksMultipass(fref, fimg, passes, method)
+    grid = fval[1][0]
+    x, y, w, h = grid[:, 0], grid[:, 1], grid[:, 2], grid[:, 3]
+    counted = ((x >= px + pw) | (x + w <= px) | (y >= py + ph) | (y + h <= py)) & (x >= 2 * side) & (y >= 2 * side) & \
+        (x + 3 * side <= hw[1]) & (y + 3 * side <= hw[0])
+    share = lambda pos: round(float(np.mean((B.displacements(grid, pos)[counted] == (3, -2)).all(axis=1))), 4)   # noqa: E731
+    return {
+        "workload": name, "image": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype),
+        "passes": [[b, st, m] for b, st, m in passes], "pass_blocks": [int(len(r[0])) for r in results["validated"]],
+        "threshold": threshold, "epsilon": epsilon,
+        "ms": {k: round(v, 3) for k, v in med.items()},
+        "ms_min": {k: round(min(v), 3) for k, v in ms.items()},
+        "validate_cost_ms": round(med["validated"] - med["unvalidated"], 3),
+        "validated_vs_by_hand": round(med["by_hand"] / med["validated"], 2),
+        "flagged": [int((~r[3]).sum()) for r in results["validated"]],
+        "equal_to_loop": same(results["validated"], results["by_hand"]) and same(fval, by_hand(fref, fimg)),
+        "flat_patch": [int(px), int(py), int(pw), int(ph)], "flat_flagged": [int((~r[3]).sum()) for r in fval],
+        "found_validated": share(fval[1][1]), "found_unvalidated": share(fraw[1][1]), "blocks_counted": int(counted.sum()),
+        "reps": reps,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=5)
@@ -316,14 +405,19 @@ def main():
     ap.add_argument("--only", default=None, help="run the one workload of this name (profiling runs)")
     ap.add_argument("--stack", type=int, default=0, metavar="F", help="the movie form: matchBlocksStack over F frames")
     ap.add_argument("--passes", action="store_true", help="coarse to fine: matchBlocksMultipass against the single pass")
+    ap.add_argument("--validate", action="store_true", help="with --passes: the median test between the passes")
     args = ap.parse_args()
+    if args.validate and not args.passes:
+        ap.error("--validate goes with --passes")
     import build as mtm_build
     mtm_build.build()
     import MTM
     for spec in WORKLOADS:
         if args.only and spec[0] != args.only:
             continue
-        if args.passes:
+        if args.passes and args.validate:
+            print(json.dumps(run_passes_validate(MTM, spec, args.reps, args.warmup)), flush=True)
+        elif args.passes:
             print(json.dumps(run_passes(MTM, spec, args.reps, args.warmup)), flush=True)
             if spec[0] == "K1":
                 print(json.dumps(run_passes(MTM, spec, args.reps, args.warmup, far=True)), flush=True)

@@ -1033,6 +1033,15 @@ class Context(_RecordMemo):
               "mtm_track_boxes_sets")
         return out, nbhd
 
+    def _pair_args(self, reference, image):
+        """(args, keep): the nine leading arguments of the mtm_match_blocks* pair entry points - the context, both images'
+        rows and row strides, the shape and pixel kind they share - and the arrays the pointers point into, for the
+        caller to hold until its call returns."""
+        r, rptr, rstride = _pixel_rows(reference)
+        a, aptr, astride = _pixel_rows(image)
+        chans = 1 if a.ndim == 2 else a.shape[2]
+        return (self._h, rptr, rstride, aptr, astride, a.shape[0], a.shape[1], chans, _dtype_code(a)), (r, a)
+
     def match_blocks(self, reference, image, blocks, margin, method, with_nbhd=False):
         """Every block of `reference` (BLOCK_DTYPE records) searched in `image` - same shape and pixel type, row strides of
         their own - inside its box widened by `margin`, in one native call (mtm_match_blocks).  Returns (records, one per
@@ -1045,11 +1054,8 @@ class Context(_RecordMemo):
         nbhd = np.empty((n, 3, 3), dtype=np.float32) if with_nbhd else None
         if n == 0:
             return out, nbhd
-        r, rptr, rstride = _pixel_rows(reference)
-        a, aptr, astride = _pixel_rows(image)
-        chans = 1 if a.ndim == 2 else a.shape[2]
-        check(self._lib.mtm_match_blocks(self._h, rptr, rstride, aptr, astride, a.shape[0], a.shape[1], chans, _dtype_code(a),
-                                         blocks.ctypes.data, n, int(margin), int(method), out.ctypes.data,
+        pair, keep = self._pair_args(reference, image)
+        check(self._lib.mtm_match_blocks(*pair, blocks.ctypes.data, n, int(margin), int(method), out.ctypes.data,
                                          nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks")
         return out, nbhd
 
@@ -1063,11 +1069,8 @@ class Context(_RecordMemo):
         nbhd = np.empty((n, 3, 3), dtype=np.float32) if with_nbhd else None
         if n == 0:
             return out, nbhd
-        r, rptr, rstride = _pixel_rows(reference)
-        a, aptr, astride = _pixel_rows(image)
-        chans = 1 if a.ndim == 2 else a.shape[2]
-        check(self._lib.mtm_match_blocks_at(self._h, rptr, rstride, aptr, astride, a.shape[0], a.shape[1], chans, _dtype_code(a),
-                                            blocks.ctypes.data, offsets.ctypes.data, n, int(margin), int(method),
+        pair, keep = self._pair_args(reference, image)
+        check(self._lib.mtm_match_blocks_at(*pair, blocks.ctypes.data, offsets.ctypes.data, n, int(margin), int(method),
                                             out.ctypes.data, nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks_at")
         return out, nbhd
 
@@ -1085,20 +1088,16 @@ class Context(_RecordMemo):
         n = int(sum(counts))
         out = np.empty(n, dtype=HIT_DTYPE)
         nbhd = np.empty((n, 3, 3), dtype=np.float32) if with_nbhd else None
-        r, rptr, rstride = _pixel_rows(reference)
-        a, aptr, astride = _pixel_rows(image)
-        chans = 1 if a.ndim == 2 else a.shape[2]
+        pair, keep = self._pair_args(reference, image)
         if validate is not None:
             threshold, epsilon = validate
             valid = np.zeros(n, dtype=np.uint8)
-            check(self._lib.mtm_match_blocks_passes_validated(self._h, rptr, rstride, aptr, astride, a.shape[0], a.shape[1],
-                                                              chans, _dtype_code(a), passes.ctypes.data, len(passes),
-                                                              int(method), float(threshold), float(epsilon), out.ctypes.data,
+            check(self._lib.mtm_match_blocks_passes_validated(*pair, passes.ctypes.data, len(passes), int(method),
+                                                              float(threshold), float(epsilon), out.ctypes.data,
                                                               nbhd.ctypes.data if with_nbhd else None, valid.ctypes.data),
                   "mtm_match_blocks_passes_validated")
             return out, nbhd, valid.astype(bool)
-        check(self._lib.mtm_match_blocks_passes(self._h, rptr, rstride, aptr, astride, a.shape[0], a.shape[1], chans,
-                                                _dtype_code(a), passes.ctypes.data, len(passes), int(method), out.ctypes.data,
+        check(self._lib.mtm_match_blocks_passes(*pair, passes.ctypes.data, len(passes), int(method), out.ctypes.data,
                                                 nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks_passes")
         return out, nbhd
 

@@ -106,14 +106,10 @@ def grid(shape, block, step=None):
     """Every block of size ``block`` (an int, or ``(w, h)``) at stride ``step`` (an int or ``(sx, sy)``; default: the
     block size) that lies wholly inside an image of shape ``shape``, in row-major order: an (N, 4) int64 array of
     ``(x, y, w, h)``."""
-    w, h = _pair(block, "block")
-    sx, sy = (w, h) if step is None else _pair(step, "step")
-    H, W = int(shape[0]), int(shape[1])
-    xs = np.arange(0, W - w + 1, sx, dtype=_I64) if W >= w else np.zeros(0, _I64)
-    ys = np.arange(0, H - h + 1, sy, dtype=_I64) if H >= h else np.zeros(0, _I64)
-    out = np.empty((len(ys) * len(xs), 4), dtype=_I64)
-    out[:, 0] = np.tile(xs, len(ys))
-    out[:, 1] = np.repeat(ys, len(xs))
+    w, h, sx, sy, nx, ny = _grid_axes(shape, block, step)
+    out = np.empty((ny * nx, 4), dtype=_I64)
+    out[:, 0] = np.tile(np.arange(0, nx * sx, sx, dtype=_I64), ny)
+    out[:, 1] = np.repeat(np.arange(0, ny * sy, sy, dtype=_I64), nx)
     out[:, 2] = w
     out[:, 3] = h
     return out
@@ -245,22 +241,67 @@ def displacements(blocks, positions):
     return p - b[:, :2]
 
 
+def _check_method(method, who):
+    if not _is_int(method) or method not in (0, 1, 2, 3, 4, 5):
+        raise ValueError("%s takes methods 0..5 (got %r)" % (who, method))
+
+
+def _check_margin(margin, prefix=""):
+    if not _is_int(margin) or margin < 0:
+        raise ValueError("%smargin must be an integer >= 0 (got %r)" % (prefix, margin))
+
+
+def _check_flag(value, name):
+    if not isinstance(value, bool):
+        raise ValueError("%s must be True or False (got %r)" % (name, value))
+
+
+def _check_pixels(a, who, noun, got):
+    """What ``who`` asks of its ``noun`` ("images" / "frames"), all shaped and typed as ``a``: the pixel kind (``got``: how
+    the message names ``a``, a format for its dtype), not empty, the row limit."""
+    ok = (a.dtype == np.uint8 and (a.ndim == 2 or (a.ndim == 3 and a.shape[2] in (1, 3)))) or \
+        (a.dtype == np.uint16 and (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 1)))
+    if not ok:
+        raise ValueError("%s takes uint8 %s with 1 or 3 channels and single-channel uint16 %s (got %s of shape %s)" % (
+            who, noun, noun, got % a.dtype, a.shape))
+    if a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError("%s: the %s are empty (shape %s)" % (who, noun, a.shape))
+    if a.shape[0] > _MAX_ROWS:
+        raise ValueError("%s takes %s of at most %d rows (got %d)" % (who, noun, _MAX_ROWS, a.shape[0]))
+
+
+def _clip_margin(margin, shape):
+    """A margin past the images' larger side clips to the whole image, as a margin of that side does."""
+    return int(min(margin, max(shape[0], shape[1])))
+
+
+def _block_records(b):
+    rec = np.empty(len(b), dtype=_lib.BLOCK_DTYPE)
+    rec["x"], rec["y"], rec["w"], rec["h"] = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+    return rec
+
+
+def _positions_scores(raw, nbhd, method, refine, shape=None):
+    """The records of a call as ``(positions, scores)`` of leading shape ``shape`` (default: one axis); ``refine``: one
+    fit over every record's neighbourhood - refineHits' numbers by construction."""
+    positions = np.stack((raw["x"], raw["y"]), axis=1).astype(_I64)
+    scores = raw["score"].astype(np.float32)
+    if refine:
+        ox, oy = subpixel.fit_offsets(nbhd, method)
+        positions = positions.astype(np.float64) + np.stack((ox, oy), axis=1)
+    if shape is None:
+        return positions, scores
+    return positions.reshape(shape + (2,)), scores.reshape(shape)
+
+
 def _check_images(reference, image):
     for name, a in (("reference", reference), ("image", image)):
         if not isinstance(a, np.ndarray):
             raise TypeError("%s must be a numpy array (got %s)" % (name, type(a).__name__))
-    ok = (image.dtype == np.uint8 and (image.ndim == 2 or (image.ndim == 3 and image.shape[2] in (1, 3)))) or \
-        (image.dtype == np.uint16 and (image.ndim == 2 or (image.ndim == 3 and image.shape[2] == 1)))
     if reference.shape != image.shape or reference.dtype != image.dtype:
         raise ValueError("reference and image differ in shape, dtype or channel count (%s %s and %s %s)" % (
             reference.shape, reference.dtype, image.shape, image.dtype))
-    if not ok:
-        raise ValueError("matchBlocks takes uint8 images with 1 or 3 channels and single-channel uint16 images (got %s "
-                         "images of shape %s)" % (image.dtype, image.shape))
-    if image.shape[0] == 0 or image.shape[1] == 0:
-        raise ValueError("matchBlocks: the images are empty (shape %s)" % (image.shape,))
-    if image.shape[0] > _MAX_ROWS:
-        raise ValueError("matchBlocks takes images of at most %d rows (got %d)" % (_MAX_ROWS, image.shape[0]))
+    _check_pixels(image, "matchBlocks", "images", "%s images")
 
 
 def _check_blocks(blocks, reference):
@@ -347,33 +388,21 @@ def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, m
     without them, bit for bit.
     """
     _check_images(reference, image)
-    if not _is_int(method) or method not in (0, 1, 2, 3, 4, 5):
-        raise ValueError("matchBlocks takes methods 0..5 (got %r)" % (method,))
-    if not _is_int(margin) or margin < 0:
-        raise ValueError("margin must be an integer >= 0 (got %r)" % (margin,))
-    if not isinstance(refine, bool):
-        raise ValueError("refine must be True or False (got %r)" % (refine,))
+    _check_method(method, "matchBlocks")
+    _check_margin(margin)
+    _check_flag(refine, "refine")
     b = _check_blocks(blocks, reference)
     off = None if offsets is None else _check_offsets(offsets, b, image.shape)
-    n = len(b)
-    if n == 0:
+    if len(b) == 0:
         return np.zeros((0, 2), dtype=np.float64 if refine else _I64), np.zeros(0, dtype=np.float32)
-    rec = np.empty(n, dtype=_lib.BLOCK_DTYPE)
-    rec["x"], rec["y"], rec["w"], rec["h"] = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
-    # (a margin past the images' larger side clips to the whole image, as a margin of that side does)
-    m = int(min(margin, max(image.shape[0], image.shape[1])))
+    rec, m = _block_records(b), _clip_margin(margin, image.shape)
     ctx = context or _lib.default_context()     # (only now: every argument error comes before "no GPU")
     with ctx.lock:
         if off is None:
             raw, nbhd = ctx.match_blocks(reference, image, rec, m, int(method), refine)
         else:
             raw, nbhd = ctx.match_blocks_at(reference, image, rec, off, m, int(method), refine)
-    positions = np.stack((raw["x"], raw["y"]), axis=1).astype(_I64)
-    scores = raw["score"].astype(np.float32)
-    if refine:          # (one fit over every block: refineHits' numbers by construction)
-        ox, oy = subpixel.fit_offsets(nbhd, method)
-        positions = positions.astype(np.float64) + np.stack((ox, oy), axis=1)
-    return positions, scores
+    return _positions_scores(raw, nbhd, method, refine)
 
 
 def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, method: int = TM_CCOEFF_NORMED, *,
@@ -413,10 +442,8 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
     (and ``matchBlocks(..., offsets=off, refine=True)`` for the refined positions).
     """
     _check_images(reference, image)
-    if not _is_int(method) or method not in (0, 1, 2, 3, 4, 5):
-        raise ValueError("matchBlocksMultipass takes methods 0..5 (got %r)" % (method,))
-    if not isinstance(refine, bool):
-        raise ValueError("refine must be True or False (got %r)" % (refine,))
+    _check_method(method, "matchBlocksMultipass")
+    _check_flag(refine, "refine")
     if validate is not None:
         if validate is True:
             validate = (2.0, 0.5)
@@ -439,16 +466,14 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
         except (TypeError, ValueError):
             raise ValueError("%s must be (block, step, margin) (got %r)" % (who, item)) from None
         w, h, sx, sy, nx, ny = _grid_axes(image.shape, block, step, who)
-        if not _is_int(margin) or margin < 0:
-            raise ValueError("%s: margin must be an integer >= 0 (got %r)" % (who, margin))
+        _check_margin(margin, who + ": ")
         if nx * ny == 0:
             raise ValueError("%s: no %d x %d block fits the %d x %d images (empty grid)" % (
                 who, w, h, image.shape[0], image.shape[1]))
         if reference.dtype == np.uint16 and w * h > _U16_MAX_PIXELS:
             raise ValueError("%s: uint16 blocks of more than 2^21 pixels are not supported (their exact correlations would "
                              "pass 2^53)" % who)
-        # (a margin past the images' larger side clips to the whole image, as a margin of that side does)
-        rec[p] = (w, h, sx, sy, int(min(margin, max(image.shape[0], image.shape[1]))))
+        rec[p] = (w, h, sx, sy, _clip_margin(margin, image.shape))
         grids.append(grid(image.shape, block, step))
     counts = [len(g) for g in grids]
     ctx = context or _lib.default_context()     # (only now: every argument error comes before "no GPU")
@@ -457,11 +482,7 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
             raw, nbhd = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine)
         else:
             raw, nbhd, flags = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine, validate=validate)
-    positions = np.stack((raw["x"], raw["y"]), axis=1).astype(_I64)
-    scores = raw["score"].astype(np.float32)
-    if refine:          # (one fit over every pass and block: matchBlocks' numbers by construction)
-        ox, oy = subpixel.fit_offsets(nbhd, method)
-        positions = positions.astype(np.float64) + np.stack((ox, oy), axis=1)
+    positions, scores = _positions_scores(raw, nbhd, method, refine)       # (one fit over every pass and block)
     out, at = [], 0
     for g in grids:
         res = (g, positions[at:at + len(g)], scores[at:at + len(g)])
@@ -494,16 +515,7 @@ def _check_frames(frames):
         if f.shape != fl[0].shape or f.dtype != fl[0].dtype:
             raise ValueError("frames[%d] differs from frames[0] in shape, dtype or channel count (%s %s, frames[0] %s %s)" % (
                 i, f.shape, f.dtype, fl[0].shape, fl[0].dtype))
-    a = fl[0]
-    ok = (a.dtype == np.uint8 and (a.ndim == 2 or (a.ndim == 3 and a.shape[2] in (1, 3)))) or \
-        (a.dtype == np.uint16 and (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 1)))
-    if not ok:
-        raise ValueError("matchBlocksStack takes uint8 frames with 1 or 3 channels and single-channel uint16 frames (got "
-                         "frames[0] %s of shape %s)" % (a.dtype, a.shape))
-    if a.shape[0] == 0 or a.shape[1] == 0:
-        raise ValueError("matchBlocksStack: the frames are empty (shape %s)" % (a.shape,))
-    if a.shape[0] > _MAX_ROWS:
-        raise ValueError("matchBlocksStack takes frames of at most %d rows (got %d)" % (_MAX_ROWS, a.shape[0]))
+    _check_pixels(fl[0], "matchBlocksStack", "frames", "frames[0] %s")
     return fl
 
 
@@ -517,10 +529,8 @@ def plane_peaks(planes, blocks, method, refine=False):
     ``subpixel.fit_offsets`` of the plane's 3 x 3 cells around it (cells outside the plane count as NaN: no offset along
     an axis whose three cells are not all numbers).  Host numpy; a plane without a number raises ValueError.
     """
-    if not _is_int(method) or method not in (0, 1, 2, 3, 4, 5):
-        raise ValueError("plane_peaks takes methods 0..5 (got %r)" % (method,))
-    if not isinstance(refine, bool):
-        raise ValueError("refine must be True or False (got %r)" % (refine,))
+    _check_method(method, "plane_peaks")
+    _check_flag(refine, "refine")
     p = np.asarray(planes)
     if p.ndim != 3 or p.shape[1] != p.shape[2] or p.shape[1] % 2 != 1 or p.dtype.kind != "f":
         raise ValueError("planes must be an (N, 2m+1, 2m+1) float array (got %s %s)" % (p.dtype, p.shape))
@@ -575,30 +585,24 @@ def matchBlocksStack(frames, blocks, margin: int, method: int = TM_CCOEFF_NORMED
     most OPT_BOXES_MAX_FLOATS cells in all.
     """
     fl = _check_frames(frames)
-    if not _is_int(method) or method not in (0, 1, 2, 3, 4, 5):
-        raise ValueError("matchBlocksStack takes methods 0..5 (got %r)" % (method,))
-    if not _is_int(margin) or margin < 0:
-        raise ValueError("margin must be an integer >= 0 (got %r)" % (margin,))
+    _check_method(method, "matchBlocksStack")
+    _check_margin(margin)
     if not isinstance(reference, str) or reference not in _REFERENCE_MODES:
         raise ValueError('reference must be "previous" or "first" (got %r)' % (reference,))
-    if not isinstance(refine, bool):
-        raise ValueError("refine must be True or False (got %r)" % (refine,))
-    if not isinstance(ensemble, bool):
-        raise ValueError("ensemble must be True or False (got %r)" % (ensemble,))
+    _check_flag(refine, "refine")
+    _check_flag(ensemble, "ensemble")
     b = _check_blocks(blocks, fl[0])
     n, pairs = len(b), len(fl) - 1
     if ensemble and pairs < 1:
         raise ValueError("ensemble=True needs two frames at least: there is no pair to average")
-    # (a margin past the frames' larger side clips to the whole frame, as a margin of that side does)
-    m = int(min(margin, max(fl[0].shape[0], fl[0].shape[1])))
+    m = _clip_margin(margin, fl[0].shape)
     side = 2 * m + 1
     ptype = np.float64 if refine else _I64
     if ensemble and n == 0:
         return np.zeros((0, 2), dtype=ptype), np.zeros(0, dtype=np.float32), np.zeros((0, side, side), dtype=np.float32)
     if not ensemble and (n == 0 or pairs == 0):
         return np.zeros((pairs, n, 2), dtype=ptype), np.zeros((pairs, n), dtype=np.float32)
-    rec = np.empty(n, dtype=_lib.BLOCK_DTYPE)
-    rec["x"], rec["y"], rec["w"], rec["h"] = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+    rec = _block_records(b)
     ctx = context or _lib.default_context()     # (only now: every argument error above comes before "no GPU")
     mode = _REFERENCE_MODES[reference]
     with ctx.lock:
@@ -613,9 +617,4 @@ def matchBlocksStack(frames, blocks, margin: int, method: int = TM_CCOEFF_NORMED
     if ensemble:
         positions, scores = plane_peaks(planes, b, int(method), refine)
         return positions, scores, planes
-    positions = np.stack((raw["x"], raw["y"]), axis=1).astype(_I64).reshape(pairs, n, 2)
-    scores = raw["score"].astype(np.float32).reshape(pairs, n)
-    if refine:          # (one fit over every pair and block: matchBlocks' numbers by construction)
-        ox, oy = subpixel.fit_offsets(nbhd, method)
-        positions = positions.astype(np.float64) + np.stack((ox, oy), axis=1).reshape(pairs, n, 2)
-    return positions, scores
+    return _positions_scores(raw, nbhd, method, refine, (pairs, n))     # (one fit over every pair and block)

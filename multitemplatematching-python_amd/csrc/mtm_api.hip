@@ -44,7 +44,7 @@ int find_matches_impl(mtm_ctx* c, int mode, double score_threshold, mtm_hit* out
 CallRoute plan_call(const mtm_ctx* c, int mode, float thr, bool banded) {
     CallRoute R;
     const int n = (int)c->templs.size();
-    const bool mode_min = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_SQDIFF_NORMED;
+    const bool mode_min = method_mode_min(c->method);
     R.mode = mode;
     R.n = n;
     R.thr = thr;
@@ -614,7 +614,7 @@ int batch_chunk(mtm_ctx* c, const void* const* px, int nb, int rows, int cols, i
     MTMC(upload_image_stack(c, c->slot[c->cur], px, nb, stride, rows, cols, chans, dtype, c->stream));
     c->timing = mtm_timing{};
     const int n = (int)c->templs.size();
-    const bool mode_min = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_SQDIFF_NORMED;
+    const bool mode_min = method_mode_min(c->method);
     // the map route: no candidate list, no fused extremum, no segment flags (each keeps one answer per template over the
     // whole launch, or packs stack rows where the seams need image rows)
     CallRoute R;
@@ -794,7 +794,7 @@ int mtm_find_matches_image_sharded_nms(mtm_ctx* c, const void* px, int rows, int
         all.swap(local);
     }
     std::stable_sort(all.begin(), all.end(), [](const mtm_hit& a, const mtm_hit& b) { return a.templ_idx < b.templ_idx; });
-    const bool ascending = method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED;
+    const bool ascending = method_mode_min(method);
     if (all.size() > 1) {                       // (MTM/NMS.py:53-55: a list of one hit is returned as it is)
         const float thr_s = (float)(ascending ? (1.0 - score_threshold) : score_threshold);
         std::vector<int32_t> keep;

@@ -13,17 +13,20 @@
 // mtm_match_blocks_stack runs the same chain for every pair of a frame stack: the frames go up in stacked
 // chunks (plan_blocks_stack, mtm_host.cpp), every pair has a row of keys of its own, and - ensemble planes - blocks_plane_kernel
 // adds every output's score to the block's plane of float64 sums instead of keeping an extremum.
-// Both entry points are compositions of the same host steps: check_block_images, stage_block_tables, blocks_pair (a
-// pair's launch chain, the one place the kernels are launched) and decode_block_keys.
 // mtm_match_blocks_at and mtm_match_blocks_passes search boxes that follow a displacement - uploaded
 // offsets, or the previous pass's records -: blocks_unit_kernel computes every block's unit on the device
 // (mtm_blocks_predict.h, the single source of host and device), blocks_score_fixed_kernel runs blocks_score_kernel's tile
 // over a fixed tile table and leaves the tiles outside the unit's map, blocks_record_kernel decodes the keys into records
-// on the device, which the next pass and the final copy read.  One chain (match_block_passes) behind both, through
-// blocks_pair; every pass has its own row of keys, records and neighbourhoods.
+// on the device, which the next pass and the final copy read.  One chain (match_block_passes) behind both; every pass has
+// its own row of keys, records and neighbourhoods.
 // mtm_match_blocks_passes_validated runs the same chain with blocks_validate_kernel behind every pass's
 // blocks_record_kernel: the median test of mtm_blocks_validate.h (the single source of host and device) over the pass's
 // records, a flag per record and the records that steer the next pass instead of the raw ones.
+// One of each: the tile body of the three score kernels (blocks_tile; the kernels supply the sink), the key's decoder
+// (mtm_quality_key.h: decode_block_keys on the host, blocks_record_kernel and blocks_nbhd_kernel on the device), the
+// record that steers (blocks_steer_record_inl).  Every entry point is a composition of the same host steps:
+// check_block_entry / check_block_pair, stage_block_call (buffers, the call's clock, uploads), blocks_pair (a pair's
+// launch chain, the one place its kernels are launched), finish_block_call (copies back, the single wait, timing).
 #include <climits>
 #include <type_traits>
 
@@ -107,12 +110,41 @@ __global__ __launch_bounds__(256) void blocks_gather_kernel(ImageDev ref, const 
     }
 }
 
-// Grid: one work-group per tile of the chunk's part of the tile table (launch slice).  `img` is the searched image, entered
-// and bounded as `ref` above: no row of the reference is read.  The windows of tile (ty0, tx0) of block u0's map are summed
-// and scored by win_score_tile - boxes_score_kernel's float32 bits, the same function -, with the gathered template of the
-// block, and instead of a map the tile's best output goes into keys[u0] (win_merge_key): order(quality) << 32 | ~index, one
-// atomicMax per wave.  Every tile of the table lies inside its map (plan_blocks); a (2 margin + 1)^2 map fills only part of
-// its tiles.
+// The tile body of the three score kernels below, one work-group per tile of the launch's part of the tile table.  `img` is
+// the searched image, entered and bounded as `ref` above: no row of the reference is read.  The windows of tile (ty0, tx0)
+// of block u0's map are summed and scored by win_score_tile - boxes_score_kernel's float32 bits, the same function -, with
+// the gathered template of the block, and every lane's output goes to sink(K, U, inside, y, x, score) instead of a map.
+// MAY_LIE_OUTSIDE: the fixed table (fix_block_tiles) over units that a kernel computed - a tile outside its unit's clipped
+// map leaves before any barrier, the test being the same for the whole work-group (track_score_kernel's rule); else
+// every tile lies inside its map (plan_blocks).  A (2 margin + 1)^2 map fills only part of its tiles.
+template <int CH, bool U16, bool MAY_LIE_OUTSIDE, class Sink>
+__device__ __forceinline__ void blocks_tile(WinTemplLds (&Tl)[U16 ? 2 : 1], WinImageLds (&Il)[U16 ? 2 : 1], const ImageDev& img,
+                                            const uint8_t* __restrict__ lo_b, const uint8_t* __restrict__ tpx,
+                                            const long long* __restrict__ toff, const TemplDev* __restrict__ td,
+                                            const TrackUnit* __restrict__ units, const TrackTile* __restrict__ tiles,
+                                            int method, Sink&& sink) {
+    const TrackTile K = tiles[blockIdx.x];
+    const TrackUnit U = units[K.u0];
+    if constexpr (MAY_LIE_OUTSIDE)
+        if (K.ty0 >= U.oh || K.tx0 >= U.ow) return;     // (the same for the whole work-group: before any barrier)
+    const TemplDev T = td[K.u0];
+    win_score_tile<CH, U16>(Tl, Il, img, lo_b, tpx + toff[K.u0], T, U.y0 + K.ty0, U.x0 + K.tx0, K.ty0, K.tx0, U.oh, U.ow, method,
+                            [&](bool inside, int y, int x, auto&& score) { sink(K, U, inside, y, x, score); });
+}
+
+// The sink of the two key kernels: the tile's best output goes into keys[u0] (win_merge_key): order(quality) << 32 |
+// ~index, one atomicMax per wave.
+struct BlocksKeySink {
+    int mode_min;
+    unsigned long long* __restrict__ keys;
+    template <class Score>
+    __device__ __forceinline__ void operator()(const TrackTile& K, const TrackUnit& U, bool inside, int y, int x,
+                                               Score&& score) const {
+        win_merge_key(inside, win_pos_word(y, x, U.ow), mode_min, score, keys + K.u0);
+    }
+};
+
+// Each block's extremum as a key, over the plan's own tile table (blocks_tile, BlocksKeySink).
 template <int CH, bool U16>
 __global__ __launch_bounds__(256) void blocks_score_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
                                                            const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
@@ -121,38 +153,20 @@ __global__ __launch_bounds__(256) void blocks_score_kernel(ImageDev img, const u
                                                            unsigned long long* __restrict__ keys) {
     __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
     __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
-    const TrackTile K = tiles[blockIdx.x];
-    const TrackUnit U = units[K.u0];
-    const TemplDev T = td[K.u0];
-    win_score_tile<CH, U16>(Tl, Il, img, lo_b, tpx + toff[K.u0], T, U.y0 + K.ty0, U.x0 + K.tx0, K.ty0, K.tx0, U.oh, U.ow, method,
-                            [&](bool inside, int y, int x, auto&& score) {
-                                win_merge_key(inside, win_pos_word(y, x, U.ow), mode_min, score, keys + K.u0);
-                            });
+    blocks_tile<CH, U16, false>(Tl, Il, img, lo_b, tpx, toff, td, units, tiles, method, BlocksKeySink{mode_min, keys});
 }
 
 // blocks_score_kernel over a FIXED tile table (fix_block_tiles, mtm_host.cpp: ceil((2 margin + 1) / 16)^2 tiles per
-// block) for units that a kernel computed (blocks_unit_kernel): the host does not know the maps, so a tile may lie
-// outside its unit's clipped map - it leaves before any barrier, the test being the same for the whole work-group
-// (track_score_kernel's rule).  A tile inside is blocks_score_kernel's to the letter: win_score_tile and win_merge_key.
-// No LDS and no scratch over blocks_score_kernel.
+// block) for units that a kernel computed (blocks_unit_kernel): the same body and sink, with the early exit.  No LDS and
+// no scratch over blocks_score_kernel.
 template <int CH, bool U16>
-__global__ __launch_bounds__(256) void blocks_score_fixed_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
-                                                                 const uint8_t* __restrict__ tpx,
-                                                                 const long long* __restrict__ toff,
-                                                                 const TemplDev* __restrict__ td,
-                                                                 const TrackUnit* __restrict__ units,
-                                                                 const TrackTile* __restrict__ tiles, int method, int mode_min,
-                                                                 unsigned long long* __restrict__ keys) {
+__global__ __launch_bounds__(256) void blocks_score_fixed_kernel(
+    ImageDev img, const uint8_t* __restrict__ lo_b, const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
+    const TemplDev* __restrict__ td, const TrackUnit* __restrict__ units, const TrackTile* __restrict__ tiles, int method,
+    int mode_min, unsigned long long* __restrict__ keys) {
     __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
     __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
-    const TrackTile K = tiles[blockIdx.x];
-    const TrackUnit U = units[K.u0];
-    if (K.ty0 >= U.oh || K.tx0 >= U.ow) return;         // (the same for the whole work-group: before any barrier)
-    const TemplDev T = td[K.u0];
-    win_score_tile<CH, U16>(Tl, Il, img, lo_b, tpx + toff[K.u0], T, U.y0 + K.ty0, U.x0 + K.tx0, K.ty0, K.tx0, U.oh, U.ow, method,
-                            [&](bool inside, int y, int x, auto&& score) {
-                                win_merge_key(inside, win_pos_word(y, x, U.ow), mode_min, score, keys + K.u0);
-                            });
+    blocks_tile<CH, U16, true>(Tl, Il, img, lo_b, tpx, toff, td, units, tiles, method, BlocksKeySink{mode_min, keys});
 }
 
 // One lane per block k < n: the unit of the block moved by its displacement - offs[2 k], offs[2 k + 1], or (prev !=
@@ -178,7 +192,7 @@ __global__ __launch_bounds__(256) void blocks_unit_kernel(const mtm_block* __res
 }
 
 // One lane per block k < n, after the pass's score launches: the block's key as its record in image coordinates -
-// decode_quality_key (mtm_host.cpp) moved by the unit's origin, what decode_block_keys gives on the host - into recs[k].
+// quality_key_record (mtm_quality_key.h) at the unit's origin, what decode_block_keys gives on the host - into recs[k].
 __global__ __launch_bounds__(256) void blocks_record_kernel(const TrackUnit* __restrict__ units,
                                                             const unsigned long long* __restrict__ keys,
                                                             const mtm_block* __restrict__ blocks, int n, int mode_min,
@@ -186,38 +200,21 @@ __global__ __launch_bounds__(256) void blocks_record_kernel(const TrackUnit* __r
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const TrackUnit U = units[k];
-    const unsigned long long key = keys[k];
-    const float q = mf_order_float((uint32_t)(key >> 32));
-    const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull);
-    mtm_hit r;
-    r.templ_idx = k;
-    r.x = U.x0 + (int)(idx % (uint32_t)U.ow);
-    r.y = U.y0 + (int)(idx / (uint32_t)U.ow);
-    r.w = blocks[k].w;
-    r.h = blocks[k].h;
-    r.score = key ? (mode_min ? -q : q) + 0.0f : __builtin_nanf("");
-    recs[k] = r;
+    recs[k] = quality_key_record(keys[k], mode_min, k, U.y0, U.x0, U.ow, blocks[k].w, blocks[k].h);
 }
 
 // One lane per block k < nx ny of a pass's grid, after the pass's blocks_record_kernel: the median test of the block's
-// displacement against those of its 3 x 3 grid neighbourhood (blocks_validate_inl: raw records only, so no lane waits for
-// another) - valid[k] = 1 / 0, and steer[k] = the record that steers the next pass: recs[k], or for an outlier recs[k]
-// moved to block position + the neighbours' median.  Every neighbour index is checked against the grid before its
-// record is read.  No LDS and no scratch: the eight values are sorted in registers.
+// displacement against those of its 3 x 3 grid neighbourhood (blocks_steer_record_inl, mtm_blocks_validate.h: raw records
+// only, so no lane waits for another) - valid[k] = 1 / 0, and steer[k] = the record that steers the next pass: recs[k],
+// or for an outlier recs[k] moved to block position + the neighbours' median.  Every neighbour index is checked against
+// the grid before its record is read.  No LDS and no scratch: the eight values are sorted in registers.
 __global__ __launch_bounds__(256) void blocks_validate_kernel(const mtm_hit* __restrict__ recs, int nx, int ny, int sx, int sy,
                                                               double threshold, double e4, uint8_t* __restrict__ valid,
                                                               mtm_hit* __restrict__ steer) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nx * ny) return;
-    const int ix = k % nx, iy = k / nx;
-    long long dx, dy;
-    const bool ok = blocks_validate_inl(recs, nx, ny, sx, sy, ix, iy, threshold, e4, &dx, &dy);
-    mtm_hit r = recs[k];
-    if (!ok) {
-        r.x = (int)((long long)ix * sx + dx);
-        r.y = (int)((long long)iy * sy + dy);
-    }
-    valid[k] = ok ? 1 : 0;
+    mtm_hit r;
+    valid[k] = blocks_steer_record_inl(recs, nx, ny, sx, sy, k, threshold, e4, &r) ? 1 : 0;
     steer[k] = r;
 }
 
@@ -237,22 +234,19 @@ __global__ __launch_bounds__(256) void blocks_plane_kernel(ImageDev img, const u
                                                            double* __restrict__ acc) {
     __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
     __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
-    const TrackTile K = tiles[blockIdx.x];
-    const TrackUnit U = units[K.u0];
-    const TemplDev T = td[K.u0];
-    win_score_tile<CH, U16>(Tl, Il, img, lo_b, tpx + toff[K.u0], T, U.y0 + K.ty0, U.x0 + K.tx0, K.ty0, K.tx0, U.oh, U.ow, method,
-                            [&](bool inside, int y, int x, auto&& score) {
-                                const int cy = y + clip[2 * K.u0 + 1], cx = x + clip[2 * K.u0];
-                                if (inside && cy < side && cx < side) {
-                                    const float s = score();
-                                    double* cell = acc + ((size_t)K.u0 * (size_t)side + (size_t)cy) * (size_t)side + (size_t)cx;
-                                    *cell = first ? (double)s : *cell + (double)s;
-                                }
-                            });
+    blocks_tile<CH, U16, false>(Tl, Il, img, lo_b, tpx, toff, td, units, tiles, method,
+                                [&](const TrackTile& K, const TrackUnit&, bool inside, int y, int x, auto&& score) {
+                                    const int cy = y + clip[2 * K.u0 + 1], cx = x + clip[2 * K.u0];
+                                    if (inside && cy < side && cx < side) {
+                                        const float s = score();
+                                        double* cell = acc + ((size_t)K.u0 * (size_t)side + (size_t)cy) * (size_t)side + (size_t)cx;
+                                        *cell = first ? (double)s : *cell + (double)s;
+                                    }
+                                });
 }
 
 // Grid: one 256-thread work-group per block (launch slice; block k = k0 + blockIdx.x), after the chunk's score launches:
-// the key of the block is decoded (decode_quality_key, mtm_host.cpp: the extremum's index in the block's map, moved by the
+// the key of the block is decoded (key_index, mtm_quality_key.h: the extremum's index in the block's map, moved by the
 // map's origin into image coordinates) and the 3 x 3 neighbourhood of that window in the WHOLE image's map goes into
 // out[9 k ..]: sub_nbhd_int's sums and win_score, mtm_hit_neighbourhoods' float32 bits, NaN outside the map.  A block
 // without a key (no output scored) gets nine NaNs and reads no pixel.
@@ -270,7 +264,7 @@ __global__ __launch_bounds__(256) void blocks_nbhd_kernel(ImageDev img, const ui
     const TrackUnit U = units[k];
     const TemplDev T = td[k];
     const unsigned long long key = keys[k];
-    const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull);
+    const uint32_t idx = key_index(key);
     const int px = U.x0 + (int)(idx % (uint32_t)U.ow), py = U.y0 + (int)(idx / (uint32_t)U.ow);
     const int tid = threadIdx.x;
     float score = NAN;
@@ -317,44 +311,106 @@ int check_block_images(const char* who, const std::string& noun, int rows, int c
     return MTM_OK;
 }
 
-// The call's buffers, sized by the plan - template planes, the block, offset, constant, unit and tile tables, then either
-// `cells` float64 sums with the clip table (ensemble planes: cells > 0) or n_pairs rows of keys (and of neighbourhoods,
-// want_nbhd) -, then before() - what the entry enqueues ahead of the call's clock -, the event the call's time counts
-// from, and the tables and zeroed results on the stream.
+// The host tables of a call, n blocks and n_tiles tiles in all (a multipass call: those of every pass, concatenated), and
+// what the call needs besides them: `cells` float64 sums with the clip table (ensemble planes: cells > 0), or `key_rows`
+// rows of n keys - with as many rows of neighbourhoods (nbhd), the uploaded offsets (offsets != nullptr), a row of records
+// (recs) and of validation flags and steering records (validate).
+struct BlockStage {
+    const mtm_block* blocks;
+    const long long* toff;
+    const TrackUnit* units;
+    const TrackTile* tiles;
+    size_t n, n_tiles, max_bytes;
+    size_t key_rows = 1, cells = 0;
+    const int32_t *clip = nullptr, *offsets = nullptr;
+    bool nbhd = false, recs = false, validate = false;
+};
+BlockStage plan_stage(const mtm_block* blocks, const BlockPlan& P) {
+    return BlockStage{blocks, P.toff.data(), P.units.data(), P.tiles.data(), P.units.size(), P.tiles.size(), P.max_bytes};
+}
+
+// The staging of every block call: the call's buffers, sized by S, then before() - what the entry enqueues ahead of the
+// call's clock -, the event the call's time counts from, and the tables and zeroed results on the stream.
 template <class Before>
-int stage_block_tables(mtm_ctx* c, const mtm_block* blocks, const BlockPlan& P, size_t n_pairs, bool want_nbhd, size_t cells,
-                       Before&& before) {
-    const size_t n = P.units.size();
+int stage_block_call(mtm_ctx* c, const BlockStage& S, Before&& before) {
+    const size_t n = S.n, n_keys = S.cells ? 0 : S.key_rows * n;
+    // what goes up, in stream order (no source: not part of this call), and what is only sized
+    const struct { DevBuf& buf; const void* src; size_t bytes; } up[] = {
+        {c->blk_blocks, S.blocks, sizeof(mtm_block) * n},   {c->blk_toff, S.toff, sizeof(long long) * n},
+        {c->blk_units, S.units, sizeof(TrackUnit) * n},     {c->blk_tiles, S.tiles, sizeof(TrackTile) * S.n_tiles},
+        {c->blk_clip, S.clip, sizeof(int32_t) * 2 * n},     {c->blk_offs, S.offsets, sizeof(int32_t) * 2 * n}};
+    const struct { DevBuf& buf; size_t bytes; } sized[] = {
+        {c->blk_tpx, S.max_bytes},                          {c->blk_td, sizeof(TemplDev) * n},
+        {c->blk_acc, sizeof(double) * S.cells},             {c->blk_keys, sizeof(unsigned long long) * n_keys},
+        {c->blk_recs, S.recs ? sizeof(mtm_hit) * n : 0},    {c->blk_nbhd, S.nbhd ? sizeof(float) * 9 * n_keys : 0},
+        {c->blk_valid, S.validate ? n : 0},                 {c->blk_steer, S.validate ? sizeof(mtm_hit) * n : 0}};
     HIPC(hipSetDevice(c->device));
     c->timing = mtm_timing{};
     c->maps_valid = false;
     c->last_hits.clear();
-    MTMC(c->blk_tpx.ensure(P.max_bytes));
-    MTMC(c->blk_toff.ensure(sizeof(long long) * n));
-    MTMC(c->blk_td.ensure(sizeof(TemplDev) * n));
-    MTMC(c->blk_blocks.ensure(sizeof(mtm_block) * n));
-    MTMC(c->blk_units.ensure(sizeof(TrackUnit) * n));
-    MTMC(c->blk_tiles.ensure(sizeof(TrackTile) * P.tiles.size()));
-    if (cells) {
-        MTMC(c->blk_clip.ensure(sizeof(int32_t) * 2 * n));
-        MTMC(c->blk_acc.ensure(sizeof(double) * cells));
-    } else {
-        MTMC(c->blk_keys.ensure(sizeof(unsigned long long) * n_pairs * n));
-        if (want_nbhd) MTMC(c->blk_nbhd.ensure(sizeof(float) * 9 * n_pairs * n));
-    }
+    for (const auto& u : up)
+        if (u.src) MTMC(u.buf.ensure(u.bytes));
+    for (const auto& s : sized) MTMC(s.buf.ensure(s.bytes));
     MTMC(before());
     HIPC(hipEventRecord(c->ev[0], c->stream));
-    HIPC(hipMemcpyAsync(c->blk_blocks.p, blocks, sizeof(mtm_block) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_toff.p, P.toff.data(), sizeof(long long) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_units.p, P.units.data(), sizeof(TrackUnit) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_tiles.p, P.tiles.data(), sizeof(TrackTile) * P.tiles.size(), hipMemcpyHostToDevice, c->stream));
-    if (cells) {
-        HIPC(hipMemcpyAsync(c->blk_clip.p, P.clip.data(), sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
-        HIPC(hipMemsetAsync(c->blk_acc.p, 0, sizeof(double) * cells, c->stream));
-    } else {
-        HIPC(hipMemsetAsync(c->blk_keys.p, 0, sizeof(unsigned long long) * n_pairs * n, c->stream));
-    }
+    for (const auto& u : up)
+        if (u.src) HIPC(hipMemcpyAsync(u.buf.p, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
+    if (S.cells) HIPC(hipMemsetAsync(c->blk_acc.p, 0, sizeof(double) * S.cells, c->stream));
+    else HIPC(hipMemsetAsync(c->blk_keys.p, 0, sizeof(unsigned long long) * n_keys, c->stream));
     return MTM_OK;
+}
+
+// The end of every block call's chain: the event its time counts to, the copies back (`dst` == nullptr: not asked for),
+// the call's single wait and its timing; the stacks a call uploads are none of the caller's images (no current image).
+struct BlockCopy {
+    void* dst;
+    const void* src;
+    size_t bytes;
+};
+int finish_block_call(mtm_ctx* c, std::initializer_list<BlockCopy> copies, size_t n_hits) {
+    HIPC(hipEventRecord(c->ev[1], c->stream));
+    for (const BlockCopy& b : copies)
+        if (b.dst) HIPC(hipMemcpyAsync(b.dst, b.src, b.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
+    c->timing.n_hits = (int64_t)n_hits;
+    c->have_image = false;
+    return MTM_OK;
+}
+
+// The two images of a pair entry point, of one shape and pixel kind.
+struct BlockPair {
+    const void* reference;
+    int64_t reference_stride_bytes;
+    const void* image;
+    int64_t image_stride_bytes;
+    int rows, cols, chans, dtype;
+};
+
+// ONE upload of each image of a pair, ahead of the call's clock: the stack's rows 0 .. rows - 1 are the reference, rows ..
+// 2 rows - 1 the image.
+int upload_block_pair(mtm_ctx* c, const BlockPair& I) {
+    adopt_image(c, 2 * I.rows, I.cols, I.chans, I.dtype);
+    return upload_image_pair(c, c->slot[c->cur], I.reference, I.reference_stride_bytes, I.image, I.image_stride_bytes, I.rows,
+                             I.cols, I.chans, I.dtype, c->stream);
+}
+
+// The preamble of every entry point with a chain: the context, the entry's own argument test (`args_ok`) and the method, as
+// one "bad arguments"; then no call in flight.
+int check_block_entry(mtm_ctx* c, const char* who, bool args_ok, int method) {
+    if (!c || !args_ok || method < MTM_TM_SQDIFF || method > MTM_TM_CCOEFF_NORMED) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    return MTM_OK;
+}
+// ... and of the pair entry points: both images, then what blocks ask of them.
+int check_block_pair(mtm_ctx* c, const char* who, bool args_ok, int method, const BlockPair& I) {
+    MTMC(check_block_entry(c, who, args_ok, method));
+    MTMC(check_image_args(I.reference, I.rows, I.cols, I.chans, I.dtype, I.reference_stride_bytes, who));
+    MTMC(check_image_args(I.image, I.rows, I.cols, I.chans, I.dtype, I.image_stride_bytes, who));
+    return check_block_images(who, "images", I.rows, I.chans, I.dtype);
 }
 
 // What a pair's chain writes: a row of keys (and of neighbourhoods, or nullptr), or - side > 0, ensemble planes - the
@@ -365,20 +421,20 @@ struct BlockSink {
     int side, first;
 };
 
-// The device tables a chain reads, indexed as its plan indexes them: the call's buffers from their start
-// (ctx_block_tables), or one pass's part of them.  fixed: `tiles` is the fixed table (fix_block_tiles) and the units are
-// the device's - blocks_score_fixed_kernel scores.
+// The device tables a chain reads, indexed as its plan indexes them: the call's buffers from their start, or - one pass
+// of several - from the pass's first block b0 and tile t0 (the constants td are every pass's in turn).  fixed: `tiles` is
+// the fixed table (fix_block_tiles) and the units are the device's - blocks_score_fixed_kernel scores.
 struct BlockTables {
     const mtm_block* blocks;
     const long long* toff;
     TemplDev* td;
-    const TrackUnit* units;
+    TrackUnit* units;
     const TrackTile* tiles;
     bool fixed;
 };
-BlockTables ctx_block_tables(mtm_ctx* c) {
-    return BlockTables{c->blk_blocks.as<mtm_block>(), c->blk_toff.as<long long>(), c->blk_td.as<TemplDev>(),
-                       c->blk_units.as<TrackUnit>(), c->blk_tiles.as<TrackTile>(), false};
+BlockTables ctx_block_tables(mtm_ctx* c, size_t b0 = 0, size_t t0 = 0, bool fixed = false) {
+    return BlockTables{c->blk_blocks.as<mtm_block>() + b0, c->blk_toff.as<long long>() + b0, c->blk_td.as<TemplDev>(),
+                       c->blk_units.as<TrackUnit>() + b0, c->blk_tiles.as<TrackTile>() + t0, fixed};
 }
 
 // One pair's launch chain for every block chunk - gather (unless the templates are already there), score or plane,
@@ -392,7 +448,7 @@ int blocks_pair(mtm_ctx* c, const BlockPlan& P, const BlockTables& B, int rows, 
     const ImageDev ref = stack_view(st, r_slot * rows, rows), img = stack_view(st, i_slot * rows, rows);
     const uint8_t* ref_lo = st_lo + (size_t)r_slot * rows * st.u8_pitch;
     const uint8_t* img_lo = st_lo + (size_t)i_slot * rows * st.u8_pitch;
-    const int mode_min = method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED ? 1 : 0;
+    const int mode_min = method_mode_min(method) ? 1 : 0;
     uint8_t* tpx = c->blk_tpx.as<uint8_t>();
     const long long* toff = B.toff;
     TemplDev* td = B.td;
@@ -434,15 +490,13 @@ int blocks_pair(mtm_ctx* c, const BlockPlan& P, const BlockTables& B, int rows, 
     });
 }
 
-// A pair's row of keys as hits: each block's extremum in its own map, moved by the map's origin into image coordinates.
+// A pair's row of keys as hits: each block's extremum in its own map, at the map's origin in image coordinates
+// (quality_key_record: blocks_record_kernel's function).
 void decode_block_keys(const BlockPlan& P, const mtm_block* blocks, const unsigned long long* hkeys, int method, mtm_hit* out) {
-    const bool mode_min = method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED;
+    const int mode_min = method_mode_min(method) ? 1 : 0;
     for (size_t k = 0; k < P.units.size(); ++k) {
         const TrackUnit& u = P.units[k];
-        mtm_hit r = decode_quality_key(hkeys[k], mode_min, (int)k, u.ow, blocks[k].w, blocks[k].h);
-        r.x += u.x0;
-        r.y += u.y0;
-        out[k] = r;
+        out[k] = quality_key_record(hkeys[k], mode_min, (int)k, u.y0, u.x0, u.ow, blocks[k].w, blocks[k].h);
     }
 }
 
@@ -461,10 +515,9 @@ struct BlockValidate {
 // V != nullptr (mtm_match_blocks_passes_validated): blocks_validate_kernel behind every pass's records, the next pass's
 // units are predicted from its `steer` records instead of the raw ones, and the flags come back with the records.
 // V == nullptr launches and copies exactly what the chain did before validation existed.
-int match_block_passes(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
-                       int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
-                       const std::vector<BlockPassPlan>& Q, const int32_t* offsets, int method, mtm_hit* out, float* nbhd,
-                       const BlockValidate* V = nullptr) {
+int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPassPlan>& Q, const int32_t* offsets, int method,
+                       mtm_hit* out, float* nbhd, const BlockValidate* V = nullptr) {
+    const int rows = I.rows, cols = I.cols, chans = I.chans, dtype = I.dtype;
     // the tables of every pass, concatenated: one upload each
     std::vector<mtm_block> blocks;
     std::vector<long long> toff;
@@ -479,50 +532,20 @@ int match_block_passes(mtm_ctx* c, const void* reference, int64_t reference_stri
         max_bytes = std::max(max_bytes, q.plan.max_bytes);
     }
     const size_t n = blocks.size();
-    HIPC(hipSetDevice(c->device));
-    c->timing = mtm_timing{};
-    c->maps_valid = false;
-    c->last_hits.clear();
-    MTMC(c->blk_tpx.ensure(max_bytes));
-    MTMC(c->blk_toff.ensure(sizeof(long long) * n));
-    MTMC(c->blk_td.ensure(sizeof(TemplDev) * n));
-    MTMC(c->blk_blocks.ensure(sizeof(mtm_block) * n));
-    MTMC(c->blk_units.ensure(sizeof(TrackUnit) * n));
-    MTMC(c->blk_tiles.ensure(sizeof(TrackTile) * tiles.size()));
-    MTMC(c->blk_keys.ensure(sizeof(unsigned long long) * n));
-    MTMC(c->blk_recs.ensure(sizeof(mtm_hit) * n));
-    if (nbhd) MTMC(c->blk_nbhd.ensure(sizeof(float) * 9 * n));
-    if (offsets) MTMC(c->blk_offs.ensure(sizeof(int32_t) * 2 * n));
-    if (V) {
-        MTMC(c->blk_valid.ensure(n));
-        MTMC(c->blk_steer.ensure(sizeof(mtm_hit) * n));
-    }
+    BlockStage S{blocks.data(), toff.data(), units.data(), tiles.data(), n, tiles.size(), max_bytes};
+    S.nbhd = nbhd != nullptr;
+    S.offsets = offsets;
+    S.recs = true;
+    S.validate = V != nullptr;
+    MTMC(stage_block_call(c, S, [&] { return upload_block_pair(c, I); }));
 
-    // ONE upload of each image, ahead of the call's clock (mtm_match_blocks' stack of two)
-    adopt_image(c, 2 * rows, cols, chans, dtype);
-    MTMC(upload_image_pair(c, c->slot[c->cur], reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans,
-                           dtype, c->stream));
-    HIPC(hipEventRecord(c->ev[0], c->stream));
-    HIPC(hipMemcpyAsync(c->blk_blocks.p, blocks.data(), sizeof(mtm_block) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_toff.p, toff.data(), sizeof(long long) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_units.p, units.data(), sizeof(TrackUnit) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_tiles.p, tiles.data(), sizeof(TrackTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
-    if (offsets) HIPC(hipMemcpyAsync(c->blk_offs.p, offsets, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemsetAsync(c->blk_keys.p, 0, sizeof(unsigned long long) * n, c->stream));
-
-    const int mode_min = method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED ? 1 : 0;
+    const int mode_min = method_mode_min(method) ? 1 : 0;
     size_t b0 = 0, t0 = 0;
     for (size_t p = 0; p < Q.size(); ++p) {
         const BlockPassPlan& q = Q[p];
         const int np = (int)q.blocks.size();
         const unsigned lanes_grid = (unsigned)((np + 255) / 256);
-        BlockTables B = ctx_block_tables(c);
-        B.blocks += b0;
-        B.toff += b0;
-        B.units += b0;
-        B.tiles += t0;
-        B.fixed = true;
-        TrackUnit* dunits = c->blk_units.as<TrackUnit>() + b0;
+        const BlockTables B = ctx_block_tables(c, b0, t0, true);
         unsigned long long* keys = c->blk_keys.as<unsigned long long>() + b0;
         mtm_hit* recs = c->blk_recs.as<mtm_hit>() + b0;
         // what steers this pass: the previous pass's records, validated or raw
@@ -530,7 +553,7 @@ int match_block_passes(mtm_ctx* c, const void* reference, int64_t reference_stri
         if (p > 0 || offsets) {
             hipLaunchKernelGGL(blocks_unit_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.blocks, np,
                                p > 0 ? nullptr : c->blk_offs.as<int32_t>(), p > 0 ? prev - Q[p - 1].blocks.size() : nullptr,
-                               p > 0 ? Q[p - 1].grid : BlockGrid{}, q.margin, rows, cols, dunits);
+                               p > 0 ? Q[p - 1].grid : BlockGrid{}, q.margin, rows, cols, B.units);
             HIPC(hipGetLastError());
         }
         MTMC(blocks_pair(c, q.plan, B, rows, chans, dtype, method, 0, 1, true,
@@ -548,16 +571,9 @@ int match_block_passes(mtm_ctx* c, const void* reference, int64_t reference_stri
         t0 += q.plan.tiles.size();
     }
 
-    HIPC(hipEventRecord(c->ev[1], c->stream));
-    HIPC(hipMemcpyAsync(out, c->blk_recs.p, sizeof(mtm_hit) * n, hipMemcpyDeviceToHost, c->stream));
-    if (nbhd) HIPC(hipMemcpyAsync(nbhd, c->blk_nbhd.p, sizeof(float) * 9 * n, hipMemcpyDeviceToHost, c->stream));
-    if (V) HIPC(hipMemcpyAsync(V->valid, c->blk_valid.p, n, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
-    c->timing.n_hits = (int64_t)n;
-    // the stack is none of the caller's images: no current image, no published maps
-    c->have_image = false;
-    return MTM_OK;
+    // the records (and neighbourhoods, and flags) come back behind the call's single wait
+    return finish_block_call(c, {{out, c->blk_recs.p, sizeof(mtm_hit) * n}, {nbhd, c->blk_nbhd.p, sizeof(float) * 9 * n},
+                                 {V ? V->valid : nullptr, c->blk_valid.p, n}}, n);
 }
 
 // threshold and epsilon of the median test: finite and >= 0, else MTM_E_INVALID naming the argument.
@@ -578,15 +594,8 @@ int mtm_match_blocks_at(mtm_ctx* c, const void* reference, int64_t reference_str
                         int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
                         const int32_t* offsets, int n_blocks, int margin, int method, mtm_hit* out, float* nbhd) {
     const char* who = "mtm_match_blocks_at";
-    if (!c || n_blocks < 0 || margin < 0 || (n_blocks > 0 && (!blocks || !offsets || !out)) || method < MTM_TM_SQDIFF ||
-        method > MTM_TM_CCOEFF_NORMED) {
-        set_error(std::string(who) + ": bad arguments");
-        return MTM_E_INVALID;
-    }
-    MTM_NOT_IN_FLIGHT(c, who);
-    MTMC(check_image_args(reference, rows, cols, chans, dtype, reference_stride_bytes, who));
-    MTMC(check_image_args(image, rows, cols, chans, dtype, image_stride_bytes, who));
-    MTMC(check_block_images(who, "images", rows, chans, dtype));
+    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
+    MTMC(check_block_pair(c, who, n_blocks >= 0 && margin >= 0 && (n_blocks == 0 || (blocks && offsets && out)), method, I));
     std::vector<BlockPassPlan> Q(1);
     Q[0].grid = BlockGrid{};
     Q[0].margin = margin;
@@ -595,26 +604,18 @@ int mtm_match_blocks_at(mtm_ctx* c, const void* reference, int64_t reference_str
     if (n_blocks == 0) return MTM_OK;
     MTMC(fix_block_tiles(Q[0].plan, rows, cols, blocks, margin, who));
     Q[0].blocks.assign(blocks, blocks + n_blocks);
-    return match_block_passes(c, reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype, Q,
-                              offsets, method, out, nbhd);
+    return match_block_passes(c, I, Q, offsets, method, out, nbhd);
 }
 
 int mtm_match_blocks_passes(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
                             int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
                             const mtm_block_pass* passes, int n_passes, int method, mtm_hit* out, float* nbhd) {
     const char* who = "mtm_match_blocks_passes";
-    if (!c || n_passes < 1 || !passes || !out || method < MTM_TM_SQDIFF || method > MTM_TM_CCOEFF_NORMED) {
-        set_error(std::string(who) + ": bad arguments");
-        return MTM_E_INVALID;
-    }
-    MTM_NOT_IN_FLIGHT(c, who);
-    MTMC(check_image_args(reference, rows, cols, chans, dtype, reference_stride_bytes, who));
-    MTMC(check_image_args(image, rows, cols, chans, dtype, image_stride_bytes, who));
-    MTMC(check_block_images(who, "images", rows, chans, dtype));
+    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
+    MTMC(check_block_pair(c, who, n_passes >= 1 && passes && out, method, I));
     std::vector<BlockPassPlan> Q;
     MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
-    return match_block_passes(c, reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype, Q,
-                              nullptr, method, out, nbhd);
+    return match_block_passes(c, I, Q, nullptr, method, out, nbhd);
 }
 
 int mtm_match_blocks_passes_validated(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
@@ -622,20 +623,13 @@ int mtm_match_blocks_passes_validated(mtm_ctx* c, const void* reference, int64_t
                                       const mtm_block_pass* passes, int n_passes, int method, double threshold,
                                       double epsilon, mtm_hit* out, float* nbhd, uint8_t* valid) {
     const char* who = "mtm_match_blocks_passes_validated";
-    MTMC(check_validate_args(who, threshold, epsilon));
-    if (!c || n_passes < 1 || !passes || !out || !valid || method < MTM_TM_SQDIFF || method > MTM_TM_CCOEFF_NORMED) {
-        set_error(std::string(who) + ": bad arguments");
-        return MTM_E_INVALID;
-    }
-    MTM_NOT_IN_FLIGHT(c, who);
-    MTMC(check_image_args(reference, rows, cols, chans, dtype, reference_stride_bytes, who));
-    MTMC(check_image_args(image, rows, cols, chans, dtype, image_stride_bytes, who));
-    MTMC(check_block_images(who, "images", rows, chans, dtype));
+    MTMC(check_validate_args(who, threshold, epsilon));         // (ahead of everything else, a null context included)
+    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
+    MTMC(check_block_pair(c, who, n_passes >= 1 && passes && out && valid, method, I));
     std::vector<BlockPassPlan> Q;
     MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
     const BlockValidate V{threshold, 4.0 * epsilon, valid};
-    return match_block_passes(c, reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype, Q,
-                              nullptr, method, out, nbhd, &V);
+    return match_block_passes(c, I, Q, nullptr, method, out, nbhd, &V);
 }
 
 int mtm_debug_validate_blocks(mtm_ctx* c, const mtm_hit* recs, int nx, int ny, int sx, int sy, double threshold, double epsilon,
@@ -649,19 +643,8 @@ int mtm_debug_validate_blocks(mtm_ctx* c, const mtm_hit* recs, int nx, int ny, i
     const size_t n = (size_t)nx * (size_t)ny;
     const double e4 = 4.0 * epsilon;
     if (!c) {           // the rule itself, on the host
-        for (int iy = 0; iy < ny; ++iy)
-            for (int ix = 0; ix < nx; ++ix) {
-                const size_t k = (size_t)iy * nx + ix;
-                long long dx, dy;
-                const bool ok = blocks_validate_inl(recs, nx, ny, sx, sy, ix, iy, threshold, e4, &dx, &dy);
-                mtm_hit r = recs[k];
-                if (!ok) {
-                    r.x = (int)((long long)ix * sx + dx);
-                    r.y = (int)((long long)iy * sy + dy);
-                }
-                valid[k] = ok ? 1 : 0;
-                steer[k] = r;
-            }
+        for (int k = 0; k < (int)n; ++k)
+            valid[k] = blocks_steer_record_inl(recs, nx, ny, sx, sy, k, threshold, e4, &steer[k]) ? 1 : 0;
         return MTM_OK;
     }
     MTM_NOT_IN_FLIGHT(c, who);
@@ -684,42 +667,25 @@ int mtm_match_blocks(mtm_ctx* c, const void* reference, int64_t reference_stride
                      int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
                      int n_blocks, int margin, int method, mtm_hit* out, float* nbhd) {
     const char* who = "mtm_match_blocks";
-    if (!c || n_blocks < 0 || margin < 0 || (n_blocks > 0 && (!blocks || !out)) || method < MTM_TM_SQDIFF ||
-        method > MTM_TM_CCOEFF_NORMED) {
-        set_error(std::string(who) + ": bad arguments");
-        return MTM_E_INVALID;
-    }
-    MTM_NOT_IN_FLIGHT(c, who);
-    MTMC(check_image_args(reference, rows, cols, chans, dtype, reference_stride_bytes, who));
-    MTMC(check_image_args(image, rows, cols, chans, dtype, image_stride_bytes, who));
-    MTMC(check_block_images(who, "images", rows, chans, dtype));
+    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
+    MTMC(check_block_pair(c, who, n_blocks >= 0 && margin >= 0 && (n_blocks == 0 || (blocks && out)), method, I));
     BlockPlan P;
     MTMC(plan_blocks(rows, cols, chans, dtype, blocks, n_blocks, margin, 4 * (long long)c->boxes_max_floats, who, P));
     if (n_blocks == 0) return MTM_OK;
     const size_t n = (size_t)n_blocks;
 
-    // ONE upload of each image, ahead of the call's clock: the stack's rows 0 .. rows - 1 are the reference, rows ..
-    // 2 rows - 1 the image
-    MTMC(stage_block_tables(c, blocks, P, 1, nbhd != nullptr, 0, [&]() -> int {
-        adopt_image(c, 2 * rows, cols, chans, dtype);
-        return upload_image_pair(c, c->slot[c->cur], reference, reference_stride_bytes, image, image_stride_bytes, rows, cols,
-                                 chans, dtype, c->stream);
-    }));
+    BlockStage S = plan_stage(blocks, P);
+    S.nbhd = nbhd != nullptr;
+    MTMC(stage_block_call(c, S, [&] { return upload_block_pair(c, I); }));
     unsigned long long* keys = c->blk_keys.as<unsigned long long>();
     MTMC(blocks_pair(c, P, ctx_block_tables(c), rows, chans, dtype, method, 0, 1, true,
                      BlockSink{keys, nbhd ? c->blk_nbhd.as<float>() : nullptr, 0, 0}));
 
     // the keys (and neighbourhoods) come back behind the call's single wait
     std::vector<unsigned long long> hkeys(n);
-    HIPC(hipEventRecord(c->ev[1], c->stream));
-    HIPC(hipMemcpyAsync(hkeys.data(), keys, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
-    if (nbhd) HIPC(hipMemcpyAsync(nbhd, c->blk_nbhd.p, sizeof(float) * 9 * n, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
-    c->timing.n_hits = (int64_t)n;
+    MTMC(finish_block_call(c, {{hkeys.data(), keys, sizeof(unsigned long long) * n}, {nbhd, c->blk_nbhd.p, sizeof(float) * 9 * n}},
+                           n));
     decode_block_keys(P, blocks, hkeys.data(), method, out);
-    // the stack is none of the caller's images: no current image, no published maps
-    c->have_image = false;
     return MTM_OK;
 }
 
@@ -727,13 +693,11 @@ int mtm_match_blocks_stack(mtm_ctx* c, const void* const* frames, int n_frames, 
                            int64_t row_stride_bytes, const mtm_block* blocks, int n_blocks, int margin, int method, int mode,
                            mtm_hit* out_hits, float* nbhd, float* planes) {
     const char* who = "mtm_match_blocks_stack";
-    if (!c || n_frames < 0 || n_blocks < 0 || margin < 0 || (n_frames > 0 && !frames) ||
-        (n_blocks > 0 && (!blocks || n_frames < 2 || (!out_hits && !planes))) || method < MTM_TM_SQDIFF ||
-        method > MTM_TM_CCOEFF_NORMED || (mode != MTM_BLOCKS_REF_PREVIOUS && mode != MTM_BLOCKS_REF_FIRST)) {
-        set_error(std::string(who) + ": bad arguments");
-        return MTM_E_INVALID;
-    }
-    MTM_NOT_IN_FLIGHT(c, who);
+    MTMC(check_block_entry(c, who,
+                           n_frames >= 0 && n_blocks >= 0 && margin >= 0 && (n_frames == 0 || frames) &&
+                               (n_blocks == 0 || (blocks && n_frames >= 2 && (out_hits || planes))) &&
+                               (mode == MTM_BLOCKS_REF_PREVIOUS || mode == MTM_BLOCKS_REF_FIRST),
+                           method));
     for (int f = 0; f < n_frames; ++f) MTMC(check_image_args(frames[f], rows, cols, chans, dtype, row_stride_bytes, who));
     MTMC(check_block_images(who, "frames", rows, chans, dtype));
     BlockPlan P;
@@ -753,7 +717,12 @@ int mtm_match_blocks_stack(mtm_ctx* c, const void* const* frames, int n_frames, 
     const size_t cells = ens ? (size_t)cells128 : 0;
 
     // the call's clock starts ahead of the uploads: the frames go up chunk by chunk between the pairs' chains
-    MTMC(stage_block_tables(c, blocks, P, np, nbhd != nullptr, cells, [] { return MTM_OK; }));
+    BlockStage S = plan_stage(blocks, P);
+    S.key_rows = np;
+    S.nbhd = nbhd != nullptr;
+    S.cells = cells;
+    S.clip = ens ? P.clip.data() : nullptr;
+    MTMC(stage_block_call(c, S, [] { return MTM_OK; }));
 
     // mode "first" with every block in one chunk: the gathered templates outlive the pairs of a frame chunk
     const bool gather_once = mode == MTM_BLOCKS_REF_FIRST && P.chunks.size() == 1;
@@ -778,16 +747,9 @@ int mtm_match_blocks_stack(mtm_ctx* c, const void* const* frames, int n_frames, 
     // the keys (and neighbourhoods), or the planes' sums, come back behind the call's single wait
     std::vector<unsigned long long> hkeys(ens ? 0 : np * n);
     std::vector<double> hacc(cells);
-    HIPC(hipEventRecord(c->ev[1], c->stream));
-    if (ens) {
-        HIPC(hipMemcpyAsync(hacc.data(), c->blk_acc.p, sizeof(double) * cells, hipMemcpyDeviceToHost, c->stream));
-    } else {
-        HIPC(hipMemcpyAsync(hkeys.data(), c->blk_keys.p, sizeof(unsigned long long) * np * n, hipMemcpyDeviceToHost, c->stream));
-        if (nbhd) HIPC(hipMemcpyAsync(nbhd, c->blk_nbhd.p, sizeof(float) * 9 * np * n, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPC(hipStreamSynchronize(c->stream));
-    HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
-    c->timing.n_hits = (int64_t)(ens ? n : np * n);
+    MTMC(finish_block_call(c, {{ens ? hacc.data() : nullptr, c->blk_acc.p, sizeof(double) * cells},
+                               {ens ? nullptr : hkeys.data(), c->blk_keys.p, sizeof(unsigned long long) * np * n},
+                               {nbhd, c->blk_nbhd.p, sizeof(float) * 9 * np * n}}, ens ? n : np * n));
     if (ens) {
         // the mean of the pairs in float64, rounded to float32; NaN where the clipped box has no output
         const size_t sd = (size_t)side;
@@ -805,8 +767,6 @@ int mtm_match_blocks_stack(mtm_ctx* c, const void* const* frames, int n_frames, 
     } else {
         for (size_t p = 0; p < np; ++p) decode_block_keys(P, blocks, hkeys.data() + p * n, method, out_hits + p * n);
     }
-    // the stacks are none of the caller's images: no current image, no published maps
-    c->have_image = false;
     return MTM_OK;
 }
 

@@ -105,4 +105,21 @@ MTM_HOST_DEVICE inline bool blocks_validate_inl(const mtm_hit* recs, int nx, int
     return false;
 }
 
+// Block k = iy nx + ix of the same grid: whether it passes (blocks_validate_inl), and in *steer the record that steers
+// the next pass - recs[k], or for an outlier recs[k] moved to block position + the neighbours' median.  What
+// blocks_validate_kernel writes per lane and mtm_debug_validate_blocks computes without a context.
+MTM_HOST_DEVICE inline bool blocks_steer_record_inl(const mtm_hit* recs, int nx, int ny, int sx, int sy, int k, double threshold,
+                                                    double e4, mtm_hit* steer) {
+    const int ix = k % nx, iy = k / nx;
+    long long dx, dy;
+    const bool ok = blocks_validate_inl(recs, nx, ny, sx, sy, ix, iy, threshold, e4, &dx, &dy);
+    mtm_hit r = recs[k];
+    if (!ok) {
+        r.x = (int)((long long)ix * sx + dx);
+        r.y = (int)((long long)iy * sy + dy);
+    }
+    *steer = r;
+    return ok;
+}
+
 }  // namespace mtm

@@ -148,7 +148,7 @@ namespace {
 int boxes_chunk(mtm_ctx* c, const mtm_box_unit* units, const std::vector<BlobTempl>& tl, int u0, int u1, int chans,
                 int dtype, int mode, float thr, std::vector<mtm_hit>& hits, int64_t* counts) {
     const int nu = u1 - u0;
-    const bool mode_min = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_SQDIFF_NORMED;
+    const bool mode_min = method_mode_min(c->method);
     const bool global = mode == MTM_PEAKS_GLOBAL;
     // unit table: the maps of 2-D units first, those of 1-D / 1x1 units after them in one block (local mode reads that
     // block back for the host's rules in one copy); tile table: the tiles of 2-D units first (the peak kernel's grid in

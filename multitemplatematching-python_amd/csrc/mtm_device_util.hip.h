@@ -8,6 +8,7 @@
 #include "mtm_kernels.h"
 #include "../../include/mtm_hip.h"
 #include "mtm_peak_sizing.h"
+#include "mtm_quality_key.h"
 
 namespace mtm {
 
@@ -103,9 +104,7 @@ __device__ __forceinline__ uint32_t mf_float_order(float v) {
     const uint32_t b = __float_as_uint(v);
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
-__device__ __forceinline__ float mf_order_float(uint32_t o) {
-    return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
-}
+__device__ __forceinline__ float mf_order_float(uint32_t o) { return key_order_float(o); }     // (mtm_quality_key.h)
 
 // rows of a score map for the 3x3 scans (peaks_kernel, refine_scan_kernel); kPkCols, kPkRows: mtm_peak_sizing.h
 

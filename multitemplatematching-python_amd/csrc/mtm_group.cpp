@@ -417,7 +417,7 @@ static int group_search(mtm_group* g, const mtm_templ* templs, int n_templ, int 
     if (nms.on) {
         // MTM.NMS on the merged list, as mtm_find_matches_image_nms runs it on a single context's (MTM/NMS.py:53-84): a list
         // of one hit is returned as it is, else cv2.dnn.NMSBoxes' selection in its order, then the first N_object
-        const bool ascending = method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED;
+        const bool ascending = method_mode_min(method);
         if (all.size() > 1) {
             const float thr_s = (float)(ascending ? (1.0 - nms.score_threshold) : nms.score_threshold);
             std::vector<int32_t> keep;

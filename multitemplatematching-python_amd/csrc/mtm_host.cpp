@@ -177,34 +177,15 @@ void line_map_peaks(const float* line, int oh, int ow, float thr, bool mode_min,
 // ---------------------------------------------------------------------------------------------
 // Extremum keys and published results.
 // ---------------------------------------------------------------------------------------------
-float order_to_float(uint32_t o) {
-    const uint32_t b = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;
-    float v;
-    std::memcpy(&v, &b, 4);
-    return v;
-}
-
-static mtm_hit key_record(uint32_t idx, float score, int templ_idx, int ow, int w, int h) {
-    mtm_hit r;
-    r.templ_idx = templ_idx;
-    r.x = (int)(idx % (uint32_t)ow);
-    r.y = (int)(idx / (uint32_t)ow);
-    r.w = w;
-    r.h = h;
-    r.score = score;
-    return r;
-}
+float order_to_float(uint32_t o) { return key_order_float(o); }
 
 mtm_hit decode_extremum_key(unsigned long long key, bool mode_min, int templ_idx, int ow, int w, int h) {
     const uint32_t o = (uint32_t)(key >> 32);
-    const uint32_t idx = key ? (0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu)) : 0u;
-    return key_record(idx, key ? order_to_float(mode_min ? ~o : o) : NAN, templ_idx, ow, w, h);
+    return key_record(key ? key_index(key) : 0u, key ? key_order_float(mode_min ? ~o : o) : NAN, templ_idx, 0, 0, ow, w, h);
 }
 
 mtm_hit decode_quality_key(unsigned long long key, bool mode_min, int templ_idx, int ow, int w, int h) {
-    const float q = order_to_float((uint32_t)(key >> 32));
-    const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu);
-    return key_record(idx, key ? (mode_min ? -q : q) + 0.0f : NAN, templ_idx, ow, w, h);
+    return quality_key_record(key, mode_min ? 1 : 0, templ_idx, 0, 0, ow, w, h);
 }
 
 int copy_out_hits(const std::vector<mtm_hit>& hits, mtm_hit* out, int64_t capacity, int64_t* n_out, const std::string& msg) {

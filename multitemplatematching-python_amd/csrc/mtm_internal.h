@@ -7,12 +7,16 @@
 
 #include "../../include/mtm_hip.h"
 #include "mtm_blocks_predict.h"    // BlockGrid, the shared predict and box functions
+#include "mtm_quality_key.h"       // the keys' decoders, shared with the device
 #include "mtm_route.h"
 #include "mtm_templ_stats.h"       // TemplStats, templ_stats_from_sums_inl
 
 namespace mtm {
 
 void set_error(const std::string& msg);   // thread-local message behind mtm_last_error()
+
+// Whether the best match of `method` is the map's minimum (the difference methods): hits are then ranked by -score.
+constexpr bool method_mode_min(int method) { return method == MTM_TM_SQDIFF || method == MTM_TM_SQDIFF_NORMED; }
 
 // px: planar float64 copies of the template (and mask weights, or nullptr), chans planes of
 // rows*cols each.  `integer` = values are exact integers (uint8 source).
@@ -41,13 +45,14 @@ std::vector<int> find_peaks_1d(const float* x, int n, int stride, float height, 
 void line_map_peaks(const float* line, int oh, int ow, float thr, bool mode_min, int templ_idx, int w, int h,
                     std::vector<mtm_hit>& out);
 
-// the float32 of an order key's high word (the inverse of mf_float_order, mtm_device_util.hip.h)
+// the float32 of an order key's high word (key_order_float, mtm_quality_key.h)
 float order_to_float(uint32_t o);
 
-// Hit records from the 64-bit extremum keys of a map ow outputs wide (order << 32 | ~row-major index):
+// Hit records from the 64-bit extremum keys of a map ow outputs wide (order << 32 | ~row-major index), both built on
+// mtm_quality_key.h:
 //  - decode_extremum_key: one of the max / min pair of extremum_kernel / extremum_batch_kernel (the minimum's order is
 //    stored complemented); key == 0 (no output) -> score NaN at (0, 0)
-//  - decode_quality_key: the window kernels' key over the quality (score, or -score for the difference methods);
+//  - decode_quality_key: the window kernels' key over the quality (quality_key_record at origin (0, 0));
 //    key == 0 -> score NaN, the index as the key reads
 mtm_hit decode_extremum_key(unsigned long long key, bool mode_min, int templ_idx, int ow, int w, int h);
 mtm_hit decode_quality_key(unsigned long long key, bool mode_min, int templ_idx, int ow, int w, int h);

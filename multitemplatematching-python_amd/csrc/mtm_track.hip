@@ -81,18 +81,10 @@ __global__ __launch_bounds__(256) void track_score_kernel(ImageDev img, const ui
     track_score_tile<CH, U16>(Tl, Il, img, lo_b, tpx, toff, td, U, K.ty0, K.tx0, row_off, method, mode_min, keys + K.u0);
 }
 
-// The record of a key (decode_quality_key, mtm_host.cpp) reduced over the map of unit U, in frame coordinates.
+// The record of a key (quality_key_record, mtm_quality_key.h: what decode_quality_key gives on the host) reduced over the
+// map of unit U, in frame coordinates.
 __device__ __forceinline__ mtm_hit track_record(const TrackUnit& U, unsigned long long key, int w, int h, int mode_min) {
-    const float q = mf_order_float((uint32_t)(key >> 32));
-    const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull);
-    mtm_hit r;
-    r.templ_idx = U.t;
-    r.x = U.x0 + (int)(idx % (uint32_t)U.ow);
-    r.y = U.y0 + (int)(idx / (uint32_t)U.ow);
-    r.w = w;
-    r.h = h;
-    r.score = key ? (mode_min ? -q : q) + 0.0f : __builtin_nanf("");
-    return r;
+    return quality_key_record(key, mode_min, U.t, U.y0, U.x0, U.ow, w, h);
 }
 
 // U's map becomes that of the hit r widened by `margin` on every side and clipped to the frame (MTM.tracking.next_box).
@@ -651,7 +643,7 @@ int stage_tables(mtm_ctx* c, const TrackArgs& A, const std::vector<BlobTempl>& t
 // rows row_off .. row_off + rows - 1 of the stack `img`: no upload, no wait.
 int track_frame(mtm_ctx* c, const TrackArgs& A, const TrackPlan& P, const TrackTables& T, const ImageDev& img,
                 const uint8_t* lo_b, int row_off, int f) {
-    const int mode_min = c->method == MTM_TM_SQDIFF || c->method == MTM_TM_SQDIFF_NORMED ? 1 : 0;
+    const int mode_min = method_mode_min(c->method) ? 1 : 0;
     const int n = A.n_tracks, ublocks = (n + 255) / 256;
     const size_t r0 = (size_t)f * n;
     return track_dispatch(A.dtype, A.chans, [&](auto ch, auto u16) -> int {

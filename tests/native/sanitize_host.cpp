@@ -17,6 +17,7 @@
 #include <tuple>
 #include <vector>
 
+#include "../../multitemplatematching-python_amd/csrc/mtm_blocks_validate.h"
 #include "../../multitemplatematching-python_amd/csrc/mtm_internal.h"
 #include "../../multitemplatematching-python_amd/csrc/mtm_nms_core.h"
 #include "../../multitemplatematching-python_amd/csrc/mtm_peak_sizing.h"
@@ -1072,8 +1073,102 @@ static void test_track_plan() {
     CHECK(P.tiles_max == 4096ull * 4096ull && P.groups_max == 1 && P.tiles.size() == 1);
 }
 
+// ---- the keys' decoder shared by host and device (mtm_quality_key.h), against bit patterns and positions worked out by hand
+static uint32_t f32_bits(float v) {
+    uint32_t b;
+    std::memcpy(&b, &v, 4);
+    return b;
+}
+
+static void test_quality_key() {
+    // order word of a quality (sign bit set for v >= +0, all bits complemented below) -> the score's bits for the
+    // maxima methods and for the difference methods (the quality negated, then + 0.0f: never -0)
+    struct Q {
+        uint32_t order, score_max, score_min;
+    };
+    const Q qs[] = {
+        {0xBFC00000u, 0x3FC00000u, 0xBFC00000u},    // quality 1.5
+        {0x403FFFFFu, 0xBFC00000u, 0x3FC00000u},    // quality -1.5
+        {0xFF800000u, 0x7F800000u, 0xFF800000u},    // quality +inf
+        {0x80000000u, 0x00000000u, 0x00000000u},    // quality +0: the score of a difference method is -(+0) + 0 = +0
+        {0x7FFFFFFFu, 0x00000000u, 0x00000000u},    // quality -0 (no kernel stores it): +0 all the same
+    };
+    // a zero key reads index 2^32 - 1: column and row of it in a map `ow` wide (the row as the int it is cast to)
+    struct W {
+        int ow, zero_col, zero_row;
+    };
+    const W ws[] = {{1, 0, -1}, {7, 3, 613566756}, {65535, 0, 65537}};
+    const int y0 = 11, x0 = 23;
+    for (int mode_min = 0; mode_min < 2; ++mode_min)
+        for (const W& wd : ws) {
+            const int ow = wd.ow;
+            // the first output, the end of row 0, the start of row 1, the last output of a 3-row map
+            const int at[4][2] = {{0, 0}, {0, ow - 1}, {1, 0}, {2, ow - 1}};
+            for (const auto& rc : at)
+                for (const Q& q : qs) {
+                    const uint32_t idx = (uint32_t)rc[0] * (uint32_t)ow + (uint32_t)rc[1];
+                    const unsigned long long key = ((unsigned long long)q.order << 32) | (0xFFFFFFFFull - idx);
+                    CHECK(key_index(key) == idx);
+                    const mtm_hit r = quality_key_record(key, mode_min, 4, y0, x0, ow, 5, 6);
+                    CHECK(r.templ_idx == 4 && r.w == 5 && r.h == 6 && r.x == x0 + rc[1] && r.y == y0 + rc[0]);
+                    CHECK(f32_bits(r.score) == (mode_min ? q.score_min : q.score_max));
+                    // the host's entry is the header at origin (0, 0)
+                    const mtm_hit d = decode_quality_key(key, mode_min != 0, 4, ow, 5, 6);
+                    const mtm_hit z = quality_key_record(key, mode_min, 4, 0, 0, ow, 5, 6);
+                    CHECK(std::memcmp(&d, &z, sizeof(mtm_hit)) == 0 && d.x == rc[1] && d.y == rc[0] &&
+                          f32_bits(d.score) == f32_bits(r.score));
+                }
+            const mtm_hit r = quality_key_record(0ull, mode_min, 4, y0, x0, ow, 5, 6);
+            CHECK(r.templ_idx == 4 && r.w == 5 && r.h == 6 && r.x == x0 + wd.zero_col && r.y == y0 + wd.zero_row);
+            CHECK(f32_bits(r.score) == 0x7FC00000u);        // the quiet NaN
+            const mtm_hit d = decode_quality_key(0ull, mode_min != 0, 4, ow, 5, 6);
+            CHECK(d.x == wd.zero_col && d.y == wd.zero_row && f32_bits(d.score) == 0x7FC00000u);
+        }
+    CHECK(f32_bits(key_order_float(0xBFC00000u)) == 0x3FC00000u && f32_bits(order_to_float(0x403FFFFFu)) == 0xBFC00000u);
+}
+
+// ---- the record that steers the next pass (blocks_steer_record_inl, mtm_blocks_validate.h), threshold 2, epsilon 0.5
+static void test_steer_record() {
+    const double threshold = 2.0, e4 = 4.0 * 0.5;
+    // 3 x 3 blocks at stride (8, 6), every block displaced by (3, 2), the centre by (5, 2): the centre's neighbours are
+    // uniform (median 3, residuals 0), so 2 |2 * 5 - 6| = 8 > 2 * (0 + 2) flags it; every other block sees at most one 5
+    // among at least three values, median 3, and its own residual is 0
+    {
+        const int nx = 3, ny = 3, sx = 8, sy = 6;
+        mtm_hit recs[9];
+        for (int k = 0; k < 9; ++k) recs[k] = mtm_hit{k, (k % 3) * sx + 3, (k / 3) * sy + 2, 16, 12, 0.5f + (float)k};
+        recs[4].x = 1 * sx + 5;
+        for (int k = 0; k < 9; ++k) {
+            mtm_hit s;
+            std::memset(&s, 0xEE, sizeof s);
+            const bool ok = blocks_steer_record_inl(recs, nx, ny, sx, sy, k, threshold, e4, &s);
+            mtm_hit expect = recs[k];
+            if (k == 4) {
+                expect.x = 1 * sx + 3;          // = 11: block position + the neighbours' median
+                expect.y = 1 * sy + 2;          // = 8
+            }
+            CHECK(ok == (k != 4));
+            CHECK(s.templ_idx == expect.templ_idx && s.x == expect.x && s.y == expect.y && s.w == expect.w && s.h == expect.h &&
+                  f32_bits(s.score) == f32_bits(expect.score));
+        }
+    }
+    // 1 x 4: no block has three neighbours - all valid, whatever they found
+    {
+        const int nx = 4, ny = 1, sx = 5, sy = 5;
+        const mtm_hit recs[4] = {{0, 40, 9, 4, 4, 1.0f}, {1, -30, 0, 4, 4, 2.0f}, {2, 10, -7, 4, 4, 3.0f}, {3, 15, 100, 4, 4, 4.0f}};
+        for (int k = 0; k < 4; ++k) {
+            mtm_hit s;
+            std::memset(&s, 0xEE, sizeof s);
+            CHECK(blocks_steer_record_inl(recs, nx, ny, sx, sy, k, threshold, e4, &s));
+            CHECK(std::memcmp(&s, &recs[k], sizeof(mtm_hit)) == 0);
+        }
+    }
+}
+
 int main() {
     std::mt19937 rng(12345);
+    test_quality_key();
+    test_steer_record();
     test_verify_candidates(rng);
     test_ladder();
     test_track_plan();

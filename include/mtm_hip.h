@@ -240,9 +240,11 @@ int         mtm_debug_templ_stats(const void* px, int rows, int cols, int chans,
  * and output rows per MFMA group, 0 = not), kp_nseg (packed K: 16-tap segments per template row, 0 = not), r2 (2 = two-row
  * tiling), tail_ok (the two-row class can screen its K loop), tail_split (the split the class's last score launch carried,
  * 0 = it ran unscreened), n_slabs, slab_nt (slabs of a large-template class; templates per MFMA group of their
- * row-multiplexed launches, 0 = plain launches).  Records of the first cap_classes classes go to `out`; returns the number
- * of classes, or a negative MTM_E_* code (no template set placed). */
-#define MTM_CLASS_TILING_FIELDS 12
+ * row-multiplexed launches, 0 = plain launches), dot_variant (the variant of the dot4 kernel the class's last dot4 launch
+ * took: 0 .. 6 as MTM_OPT_DOT4_VARIANT numbers them, 7 = the one with uint64 totals, which the launcher takes where
+ * chans w h 65025 >= 2^32; -1 = the class has not run on the dot4 kernel since it was placed).  Records of the first
+ * cap_classes classes go to `out`; returns the number of classes, or a negative MTM_E_* code (no template set placed). */
+#define MTM_CLASS_TILING_FIELDS 13
 int         mtm_debug_class_tilings(mtm_ctx* ctx, int32_t* out, int cap_classes);
 /* Test support (added under ABI 9; needs no image and no templates on the context).  The device's share of the non-maxima
  * suppression of mtm_find_matches_image_nms - the counting sort by grid cell, the champion pass, the prune pass - on a hit

@@ -472,7 +472,7 @@ def live_contexts():
 
 # the fields of one mtm_debug_class_tilings record (MTM_CLASS_TILING_FIELDS of them)
 CLASS_TILING_FIELDS = ("h", "w", "n_templates", "kernel", "rm_nt", "rm_R", "kp_nseg", "r2", "tail_ok", "tail_split", "n_slabs",
-                       "slab_nt")
+                       "slab_nt", "dot_variant")
 
 
 def debug_tail_split(h, w, thr):

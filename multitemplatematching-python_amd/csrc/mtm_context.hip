@@ -571,7 +571,7 @@ int mtm_debug_poison(mtm_ctx* c, int pattern_byte, int what) {
 }
 
 // ---- test support: the tiling placement chose for every size class (mtm_debug_class_tilings) ---------------------------
-// Reads SizeClass as place_templates left it (and the split the class's last score launch carried); derives nothing,
+// Reads SizeClass as place_templates left it (and the split, or the dot4 variant, the class's last score launch carried); derives nothing,
 // launches nothing.
 int mtm_debug_class_tilings(mtm_ctx* c, int32_t* out, int cap_classes) {
     if (!c || (!out && cap_classes > 0)) return MTM_E_INVALID;
@@ -596,6 +596,7 @@ int mtm_debug_class_tilings(mtm_ctx* c, int32_t* out, int cap_classes) {
         r[9] = (size_t)k < c->tail_last.size() ? c->tail_last[(size_t)k] : 0;
         r[10] = (int32_t)sc.slabs.size();
         r[11] = sc.slab_nt;
+        r[12] = (size_t)k < c->dot_last.size() ? c->dot_last[(size_t)k] : -1;
     }
     return n;
 }

@@ -224,7 +224,9 @@ struct mtm_ctx {
                                             // (ensure_tail_consts re-derives them when a call's split differs), 0 = none
     std::vector<int> tail_last;             // per size class: the split its last score launch carried, 0 = unscreened
                                             // (test support: mtm_debug_class_tilings)
-    int f32_mfma = 1;                       // MTM_F32_MFMA / MTM_OPT_F32_MFMA: unmasked float32 classes on the bf16 matrix cores:
+    std::vector<int> dot_last;              // per size class: the kDotVariants entry its last dot4 launch took, -1 = none yet
+                                            // (test support: mtm_debug_class_tilings)
+    int f32_mfma = 1;                      // MTM_F32_MFMA / MTM_OPT_F32_MFMA: unmasked float32 classes on the bf16 matrix cores:
                                             // 0 = float64 kernel, 1 = bf16 screen + exact float64 re-scoring of everything
                                             // that could be a peak (hit lists of the float64 kernel), 2 = bf16 scores as they are,
                                             // 3 = as 1 without the one-product tier (every screen with three piece products),

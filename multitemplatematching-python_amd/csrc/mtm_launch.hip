@@ -1128,7 +1128,11 @@ static int launch_bf16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, const Stat
 // uint8 classes on the dot4 (VALU) kernel
 static void launch_dot4(mtm_ctx* c, const SizeClass& sc, const int* tl, int n_list, const StatPlanes& st) {
     const bool wide = (double)c->chans * sc.w * sc.h * 65025.0 >= 4294967296.0;
-    const DotVariant& v = kDotVariants[wide ? kDotWideVariant : c->dot_variant];
+    const int vi = wide ? kDotWideVariant : c->dot_variant;
+    const DotVariant& v = kDotVariants[vi];
+    if (!c->classes.empty() && &sc >= c->classes.data() && &sc < c->classes.data() + c->classes.size() &&
+        (size_t)(&sc - c->classes.data()) < c->dot_last.size())
+        c->dot_last[(size_t)(&sc - c->classes.data())] = vi;                 // (what mtm_debug_class_tilings reports)
     const DotParams p = dot_params(c, v, c->chans, sc.h, sc.w, n_list);
     hipLaunchKernelGGL(v.fn, work_grid(p.n_work), dim3(256), 0, c->stream, p, c->td.as<TemplDev>(), tl, c->packs.as<uint8_t>(),
                        st, c->maps.as<float>());

@@ -782,6 +782,7 @@ int upload_placement(mtm_ctx* c, Placement& P, HostArenas& H) {
     c->classes.swap(P.classes);
     c->tail_valid.assign(c->classes.size(), 0);
     c->tail_last.assign(c->classes.size(), 0);
+    c->dot_last.assign(c->classes.size(), -1);
     for (size_t k = 0; k < c->classes.size(); ++k) {
         const SizeClass& sc = c->classes[k];
         if (sc.tail_split > 0 && sc.kernel == MTM_KERNEL_MFMA && !sc.members.empty()) c->tail_valid[k] = sc.tail_split;

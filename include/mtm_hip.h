@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes, mtm_match_blocks_passes_validated, mtm_debug_validate_blocks - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes, mtm_match_blocks_passes_validated, mtm_debug_validate_blocks, mtm_match_blocks_second, mtm_match_blocks_passes_second, mtm_debug_second_peaks - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -765,6 +765,40 @@ int mtm_match_blocks_passes_validated(mtm_ctx* ctx, const void* reference, int64
  * 1, nx * ny < 2^31; threshold and epsilon as above. */
 int mtm_debug_validate_blocks(mtm_ctx* ctx, const mtm_hit* recs, int nx, int ny, int sx, int sy, double threshold,
                               double epsilon, uint8_t* valid, mtm_hit* steer);
+
+/* mtm_match_blocks_at with every block's SECOND correlation peak: the best output of the block's map outside
+ * an exclusion window around the first peak - what a PIV package divides the first peak by for a vector's signal-to-noise.
+ * The map is the oh x ow one the record in `out` is the extremum of; its cells are ordered as the 64-bit quality key orders
+ * them, quality q = score, or -score for methods 0 and 1: larger q first, -0 equal to +0, ties to the smaller row-major
+ * index.  With (py, px) the first peak's cell, the second peak is the first cell in that order among those with
+ * max(|y - py|, |x - px|) > exclusion.  second[k]: templ_idx, w, h as out[k], x, y the cell in image coordinates and score
+ * its float32 score, (mode_min ? -q : q) + 0.0f; a map with no cell outside the exclusion (a 1 x 1 map; any map that reaches
+ * at most `exclusion` cells beyond the peak) gives x = y = -1 and a NaN score - the maps of these calls hold no NaN, so NaN
+ * means "none" and nothing else.  offsets may be NULL (no displacement: mtm_match_blocks' boxes); out and nbhd are
+ * mtm_match_blocks_at's, bit for bit.  The scores stay on the device: the score launch also stores them, one launch
+ * sub-range of whole blocks within MTM_OPT_BOXES_MAX_FLOATS floats at a time (never fewer than one block), and a small
+ * kernel per sub-range reduces them; still one wait.  exclusion < 0 or second == NULL: MTM_E_INVALID, "bad arguments". */
+int mtm_match_blocks_second(mtm_ctx* ctx, const void* reference, int64_t reference_stride_bytes, const void* image,
+                            int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
+                            const int32_t* offsets, int n_blocks, int margin, int method, mtm_hit* out, float* nbhd,
+                            int exclusion, mtm_hit* second);
+
+/* mtm_match_blocks_passes_validated with the second peak of every record, pass-major as out (second: required).  valid may
+ * be NULL: no validation, mtm_match_blocks_passes' chain (threshold and epsilon are then not read).  The second peaks steer
+ * nothing: out, nbhd and valid are those of the call without them, bit for bit. */
+int mtm_match_blocks_passes_second(mtm_ctx* ctx, const void* reference, int64_t reference_stride_bytes, const void* image,
+                                   int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                                   const mtm_block_pass* passes, int n_passes, int method, double threshold, double epsilon,
+                                   mtm_hit* out, float* nbhd, uint8_t* valid, int exclusion, mtm_hit* second);
+
+/* Test support: the second peaks of n constructed maps.  planes: the maps back to back, map k of oh[k] x ow[k] float32
+ * cells, row-major; a NaN cell takes no part.  firsts: the row-major index of each map's first peak, or NULL - the map's
+ * best cell by the rule above.  out[k]: templ_idx = k, x, y the second peak's cell in the map's own coordinates (origin 0,
+ * 0), w = h = 0, score as above; (-1, -1) and NaN where there is none (a map of NaNs included).  ctx == NULL runs the
+ * rule on the host (no GPU); with a context the maps are uploaded and the second-peak kernel is launched once over all of
+ * them.  n >= 1, oh, ow >= 1, oh * ow < 2^32, mode_min 0 or 1, exclusion >= 0. */
+int mtm_debug_second_peaks(mtm_ctx* ctx, const float* planes, int n, const int32_t* oh, const int32_t* ow,
+                           const int32_t* firsts, int mode_min, int exclusion, mtm_hit* out);
 
 /* The 3 x 3 score neighbourhoods of n points in one call: out[9 k + 3 (1 + dy) + (1 + dx)] = the score of
  * template pts[k].templ_idx at window (x + dx, y + dy) of the image's score map, NaN for a window outside the map.  Image:

@@ -231,6 +231,17 @@ SYMBOLS = {
     "mtm_debug_validate_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
                                                  ctypes.c_void_p]),
+    "mtm_match_blocks_second": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                               ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "mtm_match_blocks_passes_second": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                      ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                                      ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_int, ctypes.c_void_p]),
+    "mtm_debug_second_peaks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "mtm_hit_neighbourhoods": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
@@ -609,6 +620,28 @@ def debug_validate_blocks(positions, grid_shape, step, threshold=2.0, epsilon=0.
                                         float(threshold), float(epsilon), valid.ctypes.data, steer.ctypes.data),
           "mtm_debug_validate_blocks")
     return valid.astype(bool), np.stack((steer["x"], steer["y"]), axis=1).astype(np.int64)
+
+
+def debug_second_peaks(planes, mode_min, exclusion, firsts=None, context=None):
+    """Test support (mtm_debug_second_peaks): the second peaks of constructed maps.  `planes`: a sequence of 2-D float32
+    maps (any sizes); `firsts`: the row-major index of every map's first peak, or None - the map's best cell.  Returns
+    (positions (N, 2) int64 of (x, y) in the map's own coordinates, (-1, -1) where there is none; scores (N,) float32, NaN
+    there).  `context=None` runs the rule in the library's host code, no GPU needed; with a Context the maps go through
+    blocks_second_kernel, launched once over all of them."""
+    maps = [np.ascontiguousarray(p, dtype=np.float32) for p in planes]
+    if any(m.ndim != 2 for m in maps):
+        raise ValueError("debug_second_peaks: every plane is a 2-D map")
+    n = len(maps)
+    oh = np.array([m.shape[0] for m in maps], dtype=np.int32)
+    ow = np.array([m.shape[1] for m in maps], dtype=np.int32)
+    flat = np.concatenate([m.reshape(-1) for m in maps]) if n else np.zeros(0, np.float32)
+    at = None if firsts is None else np.ascontiguousarray(firsts, dtype=np.int32).reshape(n)
+    out = np.zeros(n, dtype=HIT_DTYPE)
+    lib = load() if context is None else context._lib
+    check(lib.mtm_debug_second_peaks(None if context is None else context._h, flat.ctypes.data, n, oh.ctypes.data,
+                                     ow.ctypes.data, None if at is None else at.ctypes.data, int(mode_min), int(exclusion),
+                                     out.ctypes.data), "mtm_debug_second_peaks")
+    return np.stack((out["x"], out["y"]), axis=1).astype(np.int64), out["score"].astype(np.float32)
 
 
 def debug_templ_stats(template, method):
@@ -1059,14 +1092,27 @@ class Context(_RecordMemo):
                                          nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks")
         return out, nbhd
 
-    def match_blocks_at(self, reference, image, blocks, offsets, margin, method, with_nbhd=False):
+    def match_blocks_at(self, reference, image, blocks, offsets, margin, method, with_nbhd=False, second=None):
         """match_blocks with a displacement per block (mtm_match_blocks_at): `offsets` an (N, 2) int32 array of (dx, dy);
-        block k's box is that of the block moved by its offset and clamped into the image, widened by `margin`."""
+        block k's box is that of the block moved by its offset and clamped into the image, widened by `margin`.
+        `second` = the exclusion radius: every block's second peak too (mtm_match_blocks_second; `offsets` may then be
+        None, mtm_match_blocks' boxes) - a third element is returned, the second peaks' records: x = y = -1 and a NaN
+        score where a map has no cell outside the exclusion."""
         blocks = block_records(blocks)
         n = len(blocks)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int32).reshape(n, 2)
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.int32).reshape(n, 2)
         out = np.empty(n, dtype=HIT_DTYPE)
         nbhd = np.empty((n, 3, 3), dtype=np.float32) if with_nbhd else None
+        if second is not None:
+            out2 = np.empty(n, dtype=HIT_DTYPE)
+            if n:
+                pair, keep = self._pair_args(reference, image)
+                check(self._lib.mtm_match_blocks_second(*pair, blocks.ctypes.data,
+                                                        None if offsets is None else offsets.ctypes.data, n, int(margin),
+                                                        int(method), out.ctypes.data, nbhd.ctypes.data if with_nbhd else None,
+                                                        int(second), out2.ctypes.data), "mtm_match_blocks_second")
+            return out, nbhd, out2
         if n == 0:
             return out, nbhd
         pair, keep = self._pair_args(reference, image)
@@ -1074,21 +1120,37 @@ class Context(_RecordMemo):
                                             out.ctypes.data, nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks_at")
         return out, nbhd
 
+    def debug_second_peaks(self, planes, mode_min, exclusion, firsts=None):
+        """Test support: the module's debug_second_peaks on this context - blocks_second_kernel, launched once."""
+        return debug_second_peaks(planes, mode_min, exclusion, firsts, context=self)
+
     def debug_validate_blocks(self, positions, grid_shape, step, threshold=2.0, epsilon=0.5):
         """Test support: the module's debug_validate_blocks on this context - blocks_validate_kernel, launched once."""
         return debug_validate_blocks(positions, grid_shape, step, threshold, epsilon, context=self)
 
-    def match_blocks_passes(self, reference, image, passes, counts, method, with_nbhd=False, validate=None):
+    def match_blocks_passes(self, reference, image, passes, counts, method, with_nbhd=False, validate=None, second=None):
         """Coarse-to-fine block matching in one native call (mtm_match_blocks_passes): `passes` BLOCK_PASS_DTYPE records,
         `counts` the blocks of every pass's grid.  Returns (records, pass-major, sum(counts) of them; neighbourhoods in
         the same order, or None).  The templates set on the context are not touched.
         `validate` = (threshold, epsilon): the median test between the passes (mtm_match_blocks_passes_validated); a third
-        element is returned, the (sum(counts),) bool flags of the records in the same order."""
+        element is returned, the (sum(counts),) bool flags of the records in the same order.
+        `second` = the exclusion radius (mtm_match_blocks_passes_second): the second peaks' records of every pass, in the
+        same order, are returned as the last element."""
         passes = block_pass_records(passes)
         n = int(sum(counts))
         out = np.empty(n, dtype=HIT_DTYPE)
         nbhd = np.empty((n, 3, 3), dtype=np.float32) if with_nbhd else None
         pair, keep = self._pair_args(reference, image)
+        if second is not None:
+            threshold, epsilon = validate if validate is not None else (0.0, 0.0)
+            valid = np.zeros(n, dtype=np.uint8) if validate is not None else None
+            out2 = np.empty(n, dtype=HIT_DTYPE)
+            check(self._lib.mtm_match_blocks_passes_second(*pair, passes.ctypes.data, len(passes), int(method), float(threshold),
+                                                           float(epsilon), out.ctypes.data,
+                                                           nbhd.ctypes.data if with_nbhd else None,
+                                                           None if valid is None else valid.ctypes.data, int(second),
+                                                           out2.ctypes.data), "mtm_match_blocks_passes_second")
+            return (out, nbhd, out2) if valid is None else (out, nbhd, valid.astype(bool), out2)
         if validate is not None:
             threshold, epsilon = validate
             valid = np.zeros(n, dtype=np.uint8)

@@ -37,6 +37,11 @@ pass before found (``predict_offsets``) - one native call, the boxes of the late
 steer the next pass: a coarse block that matched wrongly - a flat, periodic or occluded patch - is steered by its
 neighbours' median instead of misleading every fine block nearest to it.
 
+``second=`` (``matchBlocks``, ``matchBlocksMultipass``) adds every block's second correlation peak - the best output of the
+block's map outside a small exclusion window around the first - from the same native call (mtm_match_blocks_second, DESIGN
+5.6.3); ``peak_ratio`` of the two is the vector's signal-to-noise, which tells a unique match from a periodic texture, a
+flat patch or an occluded block.  ``second_peaks`` states the rule in numpy, for ensemble planes.
+
 ``matchBlocksStack`` is the movie form: the pairs of a stack of frames - each frame against the previous or against the
 first - in one native call (mtm_match_blocks_stack), every frame uploaded once; per pair the very results of
 ``matchBlocks``, or (``ensemble=True``) every block's correlation plane averaged over the pairs and its peak
@@ -50,7 +55,7 @@ from . import _lib, subpixel
 from . import TM_CCOEFF_NORMED
 
 __all__ = ["matchBlocks", "matchBlocksStack", "matchBlocksMultipass", "plane_peaks", "grid", "search_box", "search_box_at",
-           "predict_offsets", "displacements", "grid_shape", "validate"]
+           "predict_offsets", "displacements", "grid_shape", "validate", "second_peaks", "peak_ratio"]
 
 _I64 = np.dtype(np.int64)
 _U16_MAX_PIXELS = 1 << 21       # mtm_match_blocks: uint16 correlations stay below 2^53, exact in float64
@@ -256,6 +261,24 @@ def _check_flag(value, name):
         raise ValueError("%s must be True or False (got %r)" % (name, value))
 
 
+def _check_second(second):
+    """second -> None or the exclusion radius: True is 2, an integer r >= 0 is r."""
+    if second is None:
+        return None
+    if second is True:
+        return 2
+    if not _is_int(second):
+        raise TypeError("second must be None, True or an integer exclusion radius >= 0 (got %r)" % (second,))
+    if second < 0:
+        raise ValueError("second: the exclusion radius must be >= 0 (got %r)" % (second,))
+    return int(min(second, 2 ** 31 - 1))        # (no map is that large: everything is excluded either way)
+
+
+def _second_arrays(raw2):
+    """The second peaks' records as ``(second_positions, second_scores)``."""
+    return np.stack((raw2["x"], raw2["y"]), axis=1).astype(_I64), raw2["score"].astype(np.float32)
+
+
 def _check_pixels(a, who, noun, got):
     """What ``who`` asks of its ``noun`` ("images" / "frames"), all shaped and typed as ``a``: the pixel kind (``got``: how
     the message names ``a``, a format for its dtype), not empty, the row limit."""
@@ -369,7 +392,7 @@ def _check_offsets(offsets, b, shape):
 
 
 def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, method: int = TM_CCOEFF_NORMED, *,
-                refine: bool = False, context=None, offsets=None):
+                refine: bool = False, context=None, offsets=None, second=None):
     """
     Where every block of ``reference`` is in ``image``: ``(positions, scores)``, ``positions[k]`` the int64 ``[x, y]``
     (image coordinates) and ``scores[k]`` the float32 score of the single hit of
@@ -386,27 +409,43 @@ def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, m
     ``search_box_at(blocks[k], offsets[k], margin, image.shape)`` - the box of the block moved by its offset and clamped
     into the image - instead (mtm_match_blocks_at: the boxes are computed on the device).  Zero offsets give the call
     without them, bit for bit.
+
+    ``second``: ``None`` (the call above), ``True`` (exclusion radius 2) or an integer radius ``r >= 0``: the call returns
+    ``(positions, scores, second_positions, second_scores)``, the last two every block's second correlation peak - the best
+    output of the block's map (``computeScoreMap`` of the block over its search box, the map ``positions`` is the best
+    output of) among the cells more than ``r`` cells away from the first peak, ``max(|dy|, |dx|) > r``, in the order the
+    first peak is chosen by: the larger score (the smaller for methods 0 and 1), ties to the first cell in row-major
+    order.  ``second_positions`` is (N, 2) int64 in image coordinates, always integers (``refine`` moves only
+    ``positions``), ``second_scores`` float32; a map with no cell outside the exclusion - ``margin=0``, or a map within
+    ``r`` cells of its peak - gives ``(-1, -1)`` and NaN.  Computed on the device inside the same native call
+    (mtm_match_blocks_second); ``positions`` and ``scores`` are those of the call without ``second``, bit for bit.
+    ``peak_ratio(scores, second_scores, method)`` is the signal-to-noise PIV packages report.
     """
     _check_images(reference, image)
     _check_method(method, "matchBlocks")
     _check_margin(margin)
     _check_flag(refine, "refine")
+    r = _check_second(second)
     b = _check_blocks(blocks, reference)
     off = None if offsets is None else _check_offsets(offsets, b, image.shape)
     if len(b) == 0:
-        return np.zeros((0, 2), dtype=np.float64 if refine else _I64), np.zeros(0, dtype=np.float32)
+        none = (np.zeros((0, 2), dtype=np.float64 if refine else _I64), np.zeros(0, dtype=np.float32))
+        return none if r is None else none + (np.zeros((0, 2), dtype=_I64), np.zeros(0, dtype=np.float32))
     rec, m = _block_records(b), _clip_margin(margin, image.shape)
     ctx = context or _lib.default_context()     # (only now: every argument error comes before "no GPU")
     with ctx.lock:
-        if off is None:
+        if r is not None:
+            raw, nbhd, raw2 = ctx.match_blocks_at(reference, image, rec, off, m, int(method), refine, second=r)
+        elif off is None:
             raw, nbhd = ctx.match_blocks(reference, image, rec, m, int(method), refine)
         else:
             raw, nbhd = ctx.match_blocks_at(reference, image, rec, off, m, int(method), refine)
-    return _positions_scores(raw, nbhd, method, refine)
+    res = _positions_scores(raw, nbhd, method, refine)
+    return res if r is None else res + _second_arrays(raw2)
 
 
 def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, method: int = TM_CCOEFF_NORMED, *,
-                         refine: bool = False, context=None, validate=None):
+                         refine: bool = False, context=None, validate=None, second=None):
     """
     Coarse-to-fine block matching in one native call.  ``passes``: a non-empty sequence of ``(block, step, margin)``,
     ``block`` and ``step`` as ``grid`` takes them (``step=None``: the block size).  Pass 0 is ``matchBlocks`` over its
@@ -440,10 +479,16 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
             steer = b[:, :2] + rep
 
     (and ``matchBlocks(..., offsets=off, refine=True)`` for the refined positions).
+
+    ``second``: as ``matchBlocks``' - every pass's tuple gets ``second_positions_p, second_scores_p`` appended at its end
+    (after ``valid_p`` when ``validate`` is given), those of ``matchBlocks(reference, image, b, margin, method,
+    offsets=off, second=second)`` in the loops above (mtm_match_blocks_passes_second, still one native call).  The second
+    peaks steer nothing: positions, scores and flags are those of the call without ``second``, bit for bit.
     """
     _check_images(reference, image)
     _check_method(method, "matchBlocksMultipass")
     _check_flag(refine, "refine")
+    r = _check_second(second)
     if validate is not None:
         if validate is True:
             validate = (2.0, 0.5)
@@ -478,15 +523,26 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
     counts = [len(g) for g in grids]
     ctx = context or _lib.default_context()     # (only now: every argument error comes before "no GPU")
     with ctx.lock:
-        if validate is None:
+        if r is not None:
+            kw = {} if validate is None else {"validate": validate}
+            *got, raw2 = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine, second=r, **kw)
+            raw, nbhd = got[:2]
+            flags = got[2] if validate is not None else None
+        elif validate is None:
             raw, nbhd = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine)
         else:
             raw, nbhd, flags = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine, validate=validate)
     positions, scores = _positions_scores(raw, nbhd, method, refine)       # (one fit over every pass and block)
+    if r is not None:
+        positions2, scores2 = _second_arrays(raw2)
     out, at = [], 0
     for g in grids:
         res = (g, positions[at:at + len(g)], scores[at:at + len(g)])
-        out.append(res if validate is None else res + (np.asarray(flags[at:at + len(g)], dtype=bool),))
+        if validate is not None:
+            res += (np.asarray(flags[at:at + len(g)], dtype=bool),)
+        if r is not None:
+            res += (positions2[at:at + len(g)], scores2[at:at + len(g)])
+        out.append(res)
         at += len(g)
     return out
 
@@ -565,6 +621,79 @@ def plane_peaks(planes, blocks, method, refine=False):
         ox, oy = subpixel.fit_offsets(nbhd, method)
         positions = positions.astype(np.float64) + np.stack((ox, oy), axis=1)
     return positions, scores
+
+
+def second_peaks(planes, blocks, method, exclusion=2):
+    """
+    The second peak of every block's score plane, ``(second_positions, second_scores)`` - ``matchBlocks(second=)``'s rule
+    in host numpy, in the shape of ``plane_peaks``: how ``matchBlocksStack(ensemble=True)`` users get the second peak of
+    the ensemble planes.  ``planes``: an (N, 2m+1, 2m+1) float array as ``plane_peaks`` takes it, NaN cells counting as
+    absent.  Per plane the cells are ordered by score - larger first, smaller first for methods 0 and 1, -0 equal to +0,
+    ties to the first cell in row-major order -; the first peak is the first cell of that order (``plane_peaks``' cell),
+    the second peak the first among the cells with ``max(|dy|, |dx|) > exclusion`` from it.  ``second_positions[k]`` is the
+    int64 ``(x_k + dx, y_k + dy)``, ``second_scores[k]`` the plane's value as float32 (+0 for a zero of either sign);
+    ``(-1, -1)`` and NaN where no cell that holds a number lies outside the exclusion.  A plane without a number raises
+    ValueError.
+    """
+    _check_method(method, "second_peaks")
+    if not _is_int(exclusion):
+        raise TypeError("second_peaks: exclusion must be an integer >= 0 (got %r)" % (exclusion,))
+    if exclusion < 0:
+        raise ValueError("second_peaks: exclusion must be an integer >= 0 (got %r)" % (exclusion,))
+    p = np.asarray(planes)
+    if p.ndim != 3 or p.shape[1] != p.shape[2] or p.shape[1] % 2 != 1 or p.dtype.kind != "f":
+        raise ValueError("planes must be an (N, 2m+1, 2m+1) float array (got %s %s)" % (p.dtype, p.shape))
+    p = p.astype(np.float32, copy=False)
+    b = np.asarray(blocks)
+    if b.size == 0 and len(p) == 0:
+        b = np.zeros((0, 4), _I64)
+    if b.ndim != 2 or b.shape[1] != 4 or b.dtype.kind not in "iu" or len(b) != len(p):
+        raise ValueError("blocks must be an (N, 4) integer array of (x, y, w, h), one block per plane (got %s for %d planes)"
+                         % (b.shape, len(p)))
+    n, side = len(p), p.shape[1]
+    m = side // 2
+    flat = np.ascontiguousarray(p.reshape(n, side * side))
+    nan = np.isnan(flat)
+    if nan.all(axis=1).any():
+        raise ValueError("planes[%d] holds no number" % int(np.argmax(nan.all(axis=1))))
+    if n == 0:
+        return np.zeros((0, 2), _I64), np.zeros(0, np.float32)
+    # the 64-bit quality key of every cell (mtm_quality_key.h): order(q) << 32 | ~index, 0 for a NaN cell
+    q = (-flat if method in (0, 1) else flat) + np.float32(0.0)            # (-0 -> +0)
+    bits = q.view(np.uint32).astype(np.uint64)
+    order = np.where(bits >> np.uint64(31), bits ^ np.uint64(0xFFFFFFFF), bits | np.uint64(0x80000000))
+    keys = (order << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - np.arange(side * side, dtype=np.uint64))[None, :]
+    keys[nan] = 0
+    rows = np.arange(n)
+    first = np.argmax(keys, axis=1)
+    cy, cx = np.divmod(np.arange(side * side), side)
+    away = np.maximum(np.abs(cy[None, :] - (first // side)[:, None]), np.abs(cx[None, :] - (first % side)[:, None])) > exclusion
+    keys[~away] = 0
+    at = np.argmax(keys, axis=1)
+    some = keys[rows, at] != 0
+    positions = np.where(some[:, None], b[:, :2].astype(_I64) + np.stack((at % side - m, at // side - m), axis=1), -1)
+    scores = np.where(some, flat[rows, at] + np.float32(0.0), np.float32(np.nan)).astype(np.float32)
+    return positions.astype(_I64), scores
+
+
+def peak_ratio(scores, second_scores, method):
+    """
+    The peak-to-peak ratio of ``matchBlocks(second=)``'s two scores, float64 and >= 1 for a first peak that beats the
+    second: the signal-to-noise PIV packages report per vector.  Methods 2..5 (a larger score is better): ``scores /
+    second_scores`` where the second score is > 0, ``inf`` where it is <= 0.  Methods 0 and 1 (smaller is better):
+    ``second_scores / scores`` where the first score is > 0, ``inf`` where it is 0.  NaN where there is no second peak
+    (a NaN second score).  Meant for the normalised methods (1, 3, 5), whose scores have a fixed scale; the raw sums of
+    methods 0, 2 and 4 grow with the block's brightness, and TM_CCOEFF's can be negative.
+    """
+    _check_method(method, "peak_ratio")
+    s1 = np.asarray(scores, dtype=np.float64)
+    s2 = np.asarray(second_scores, dtype=np.float64)
+    if s1.shape != s2.shape:
+        raise ValueError("peak_ratio: scores of shape %s and second_scores of shape %s" % (s1.shape, s2.shape))
+    num, den = (s2, s1) if method in (0, 1) else (s1, s2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(den > 0, num / np.where(den > 0, den, 1.0), np.inf)
+    return np.where(np.isnan(s2), np.nan, ratio).astype(np.float64)
 
 
 def matchBlocksStack(frames, blocks, margin: int, method: int = TM_CCOEFF_NORMED, *, reference: str = "previous",

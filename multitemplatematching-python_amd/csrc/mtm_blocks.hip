@@ -22,7 +22,12 @@
 // mtm_match_blocks_passes_validated runs the same chain with blocks_validate_kernel behind every pass's
 // blocks_record_kernel: the median test of mtm_blocks_validate.h (the single source of host and device) over the pass's
 // records, a flag per record and the records that steer the next pass instead of the raw ones.
-// One of each: the tile body of the three score kernels (blocks_tile; the kernels supply the sink), the key's decoder
+// mtm_match_blocks_second and mtm_match_blocks_passes_second add every block's second correlation peak to that
+// chain: blocks_score_plane_kernel - blocks_score_fixed_kernel with a sink that also stores the float32 scores - fills the
+// planes of one sub-range of whole blocks, blocks_second_kernel reduces each plane to the best key outside the exclusion
+// window around the first peak (mtm_blocks_second.h, the single source of host and device), and
+// blocks_second_record_kernel decodes those keys behind blocks_record_kernel; the records come back behind the same wait.
+// One of each: the tile body of the four score kernels (blocks_tile; the kernels supply the sink), the key's decoder
 // (mtm_quality_key.h: decode_block_keys on the host, blocks_record_kernel and blocks_nbhd_kernel on the device), the
 // record that steers (blocks_steer_record_inl).  Every entry point is a composition of the same host steps:
 // check_block_entry / check_block_pair, stage_block_call (buffers, the call's clock, uploads), blocks_pair (a pair's
@@ -31,6 +36,7 @@
 #include <type_traits>
 
 #include "mtm_blocks_predict.h"
+#include "mtm_blocks_second.h"
 #include "mtm_blocks_validate.h"
 #include "mtm_ctx.h"
 #include "mtm_device_util.hip.h"
@@ -167,6 +173,108 @@ __global__ __launch_bounds__(256) void blocks_score_fixed_kernel(
     __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
     __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
     blocks_tile<CH, U16, true>(Tl, Il, img, lo_b, tpx, toff, td, units, tiles, method, BlocksKeySink{mode_min, keys});
+}
+
+// BlocksKeySink that also keeps the scores: an inside lane calls score() once, stores the float32 at cell (y, x) of block
+// u0's plane - plane[poff[u0] + y U.ow + x], the map row-major and contiguous - and feeds the same value to win_merge_key,
+// so the key is BlocksKeySink's.  A plain store: the tile table partitions a map, every cell has one writer.
+struct BlocksScoredPlaneSink {
+    int mode_min;
+    unsigned long long* __restrict__ keys;
+    float* __restrict__ plane;
+    const long long* __restrict__ poff;
+    template <class Score>
+    __device__ __forceinline__ void operator()(const TrackTile& K, const TrackUnit& U, bool inside, int y, int x,
+                                               Score&& score) const {
+        float s = 0.0f;
+        if (inside) {
+            s = score();
+            plane[(size_t)poff[K.u0] + (size_t)y * (size_t)U.ow + (size_t)x] = s;
+        }
+        win_merge_key(inside, win_pos_word(y, x, U.ow), mode_min, [&] { return s; }, keys + K.u0);
+    }
+};
+
+// blocks_score_fixed_kernel with the scored-plane sink (the second-peak calls; their tables are always the fixed ones): the
+// same body, LDS and keys, and every output of every unit's map lands in the unit's plane for blocks_second_kernel.  The
+// plane of block u0 holds at least U.oh U.ow floats whatever unit the device computed (second_plane_floats).
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void blocks_score_plane_kernel(
+    ImageDev img, const uint8_t* __restrict__ lo_b, const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
+    const TemplDev* __restrict__ td, const TrackUnit* __restrict__ units, const TrackTile* __restrict__ tiles, int method,
+    int mode_min, unsigned long long* __restrict__ keys, float* __restrict__ plane, const long long* __restrict__ poff) {
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
+    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
+    blocks_tile<CH, U16, true>(Tl, Il, img, lo_b, tpx, toff, td, units, tiles, method,
+                               BlocksScoredPlaneSink{mode_min, keys, plane, poff});
+}
+
+// Grid: one 256-thread work-group per block (launch slice; block k = k0 + blockIdx.x), behind the score launch that wrote
+// the block's plane: the largest key among the cells of the unit's oh x ow map outside the exclusion of radius
+// `exclusion` around the first peak (keys[k], decoded by key_index) goes into keys2[k] - second_excluded and
+// second_cell_key (mtm_blocks_second.h, the host's functions).  Lanes walk idx = tid, tid + 256, .. < oh ow: coalesced
+// loads of cells the score launch wrote, nothing outside the map is read; per wave the shuffle ladder of win_merge_key,
+// then the four waves through 32 B of LDS.  A block without a key reads nothing; keys2[k] is written either way (0: no
+// second peak).
+__global__ __launch_bounds__(256) void blocks_second_kernel(const TrackUnit* __restrict__ units,
+                                                            const unsigned long long* __restrict__ keys,
+                                                            const float* __restrict__ plane, const long long* __restrict__ poff,
+                                                            int k0, int mode_min, int exclusion,
+                                                            unsigned long long* __restrict__ keys2) {
+    __shared__ unsigned long long red[4];
+    const int k = k0 + (int)blockIdx.x;
+    const int tid = threadIdx.x;
+    const unsigned long long first = keys[k];
+    if (first == 0ull) {                                    // (the same for the whole work-group: before any barrier)
+        if (tid == 0) keys2[k] = 0ull;
+        return;
+    }
+    const TrackUnit U = units[k];
+    const uint32_t ow = (uint32_t)U.ow, n = (uint32_t)U.oh * ow;     // (< 2^32: plan_blocks, fix_block_tiles)
+    const uint32_t at = key_index(first);
+    const int py = (int)(at / ow), px = (int)(at % ow);
+    const float* __restrict__ m = plane + poff[k];
+    // the lane's cell (y, x) steps by 256 cells: 256 / ow rows and 256 % ow columns, with one carry
+    const uint32_t sy = 256u / ow, sx = 256u % ow;
+    uint32_t y = (uint32_t)tid / ow, x = (uint32_t)tid % ow;
+    unsigned long long best = 0ull;
+    for (unsigned long long idx = (unsigned long long)tid; idx < (unsigned long long)n; idx += 256ull) {
+        if (!second_excluded((int)y, (int)x, py, px, exclusion)) {
+            const unsigned long long key = second_cell_key(m[idx], mode_min, (uint32_t)idx);
+            best = key > best ? key : best;
+        }
+        y += sy;
+        x += sx;
+        if (x >= ow) {
+            x -= ow;
+            ++y;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = __shfl_xor(best, off);
+        best = o > best ? o : best;
+    }
+    if ((tid & 63) == 0) red[tid >> 6] = best;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long b = red[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) b = red[w] > b ? red[w] : b;
+        keys2[k] = b;
+    }
+}
+
+// blocks_record_kernel for the second keys: second_key_record (mtm_blocks_second.h) at the unit's origin into recs2[k] -
+// a block without a second peak gets position (-1, -1) and a NaN score.
+__global__ __launch_bounds__(256) void blocks_second_record_kernel(const TrackUnit* __restrict__ units,
+                                                                   const unsigned long long* __restrict__ keys2,
+                                                                   const mtm_block* __restrict__ blocks, int n, int mode_min,
+                                                                   mtm_hit* __restrict__ recs2) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const TrackUnit U = units[k];
+    recs2[k] = second_key_record(keys2[k], mode_min, k, U.y0, U.x0, U.ow, blocks[k].w, blocks[k].h);
 }
 
 // One lane per block k < n: the unit of the block moved by its displacement - offs[2 k], offs[2 k + 1], or (prev !=
@@ -314,7 +422,8 @@ int check_block_images(const char* who, const std::string& noun, int rows, int c
 // The host tables of a call, n blocks and n_tiles tiles in all (a multipass call: those of every pass, concatenated), and
 // what the call needs besides them: `cells` float64 sums with the clip table (ensemble planes: cells > 0), or `key_rows`
 // rows of n keys - with as many rows of neighbourhoods (nbhd), the uploaded offsets (offsets != nullptr), a row of records
-// (recs) and of validation flags and steering records (validate).
+// (recs) and of validation flags and steering records (validate); the second-peak calls: the plane offsets `poff` with
+// plane_floats floats of planes (the largest launch sub-range's), a row of second keys and of their records.
 struct BlockStage {
     const mtm_block* blocks;
     const long long* toff;
@@ -324,6 +433,8 @@ struct BlockStage {
     size_t key_rows = 1, cells = 0;
     const int32_t *clip = nullptr, *offsets = nullptr;
     bool nbhd = false, recs = false, validate = false;
+    const long long* poff = nullptr;
+    size_t plane_floats = 0;
 };
 BlockStage plan_stage(const mtm_block* blocks, const BlockPlan& P) {
     return BlockStage{blocks, P.toff.data(), P.units.data(), P.tiles.data(), P.units.size(), P.tiles.size(), P.max_bytes};
@@ -338,12 +449,15 @@ int stage_block_call(mtm_ctx* c, const BlockStage& S, Before&& before) {
     const struct { DevBuf& buf; const void* src; size_t bytes; } up[] = {
         {c->blk_blocks, S.blocks, sizeof(mtm_block) * n},   {c->blk_toff, S.toff, sizeof(long long) * n},
         {c->blk_units, S.units, sizeof(TrackUnit) * n},     {c->blk_tiles, S.tiles, sizeof(TrackTile) * S.n_tiles},
-        {c->blk_clip, S.clip, sizeof(int32_t) * 2 * n},     {c->blk_offs, S.offsets, sizeof(int32_t) * 2 * n}};
+        {c->blk_clip, S.clip, sizeof(int32_t) * 2 * n},     {c->blk_offs, S.offsets, sizeof(int32_t) * 2 * n},
+        {c->blk_poff, S.poff, sizeof(long long) * n}};
     const struct { DevBuf& buf; size_t bytes; } sized[] = {
         {c->blk_tpx, S.max_bytes},                          {c->blk_td, sizeof(TemplDev) * n},
         {c->blk_acc, sizeof(double) * S.cells},             {c->blk_keys, sizeof(unsigned long long) * n_keys},
         {c->blk_recs, S.recs ? sizeof(mtm_hit) * n : 0},    {c->blk_nbhd, S.nbhd ? sizeof(float) * 9 * n_keys : 0},
-        {c->blk_valid, S.validate ? n : 0},                 {c->blk_steer, S.validate ? sizeof(mtm_hit) * n : 0}};
+        {c->blk_valid, S.validate ? n : 0},                 {c->blk_steer, S.validate ? sizeof(mtm_hit) * n : 0},
+        {c->blk_plane, sizeof(float) * S.plane_floats},     {c->blk_keys2, S.poff ? sizeof(unsigned long long) * n : 0},
+        {c->blk_recs2, S.poff ? sizeof(mtm_hit) * n : 0}};
     HIPC(hipSetDevice(c->device));
     c->timing = mtm_timing{};
     c->maps_valid = false;
@@ -437,12 +551,56 @@ BlockTables ctx_block_tables(mtm_ctx* c, size_t b0 = 0, size_t t0 = 0, bool fixe
                        c->blk_units.as<TrackUnit>() + b0, c->blk_tiles.as<TrackTile>() + t0, fixed};
 }
 
+// The floats block b's scored plane holds: the largest map a moved block can have, min(2 margin + 1, rows - h + 1) x
+// min(2 margin + 1, cols - w + 1) (fix_block_tiles' spans: < 2^32) - known to the host whatever unit the device computes.
+size_t second_plane_floats(const mtm_block& b, int margin, int rows, int cols) {
+    const long long side = 2ll * margin + 1;
+    return (size_t)std::min(side, (long long)rows - b.h + 1) * (size_t)std::min(side, (long long)cols - b.w + 1);
+}
+
+// What a second-peak pass adds to its chain (blocks_pair): the plan's blocks in sub-ranges of whole blocks - within a
+// template-byte chunk, and their planes within `budget` floats, never fewer than one block -, each scored into the plane
+// buffer (block k's plane at poff[k] floats) and reduced to keys2 by blocks_second_kernel before the next one overwrites it.
+struct BlockSecondPass {
+    int exclusion;
+    std::vector<std::pair<int, int>> ranges;    // [b0, b1), in order, covering the pass
+    std::vector<size_t> tstart;                 // block k's tiles are tiles[tstart[k] .. tstart[k + 1] - 1] of the pass
+    const long long* poff;                      // device, indexed as the pass's tables
+    unsigned long long* keys2;
+};
+
+// The sub-ranges and tile starts of plan P (fixed tile table) over `blocks`, the plane offsets appended to `poff` (one per
+// block, relative to its sub-range's start) and the largest sub-range's floats raised into *max_floats.
+void plan_second_pass(const BlockPlan& P, const mtm_block* blocks, int margin, int rows, int cols, size_t budget,
+                      BlockSecondPass& X, std::vector<long long>& poff, size_t* max_floats) {
+    const size_t n = P.units.size();
+    X.tstart.assign(n + 1, P.tiles.size());
+    for (size_t t = P.tiles.size(); t-- > 0;) X.tstart[(size_t)P.tiles[t].u0] = t;
+    for (const BlockChunk& C : P.chunks) {
+        int r0 = C.b0;
+        size_t used = 0;
+        for (int k = C.b0; k < C.b1; ++k) {
+            const size_t f = second_plane_floats(blocks[k], margin, rows, cols);
+            if (k > r0 && used + f > budget) {
+                X.ranges.emplace_back(r0, k);
+                r0 = k;
+                used = 0;
+            }
+            poff.push_back((long long)used);
+            used += f;
+            *max_floats = std::max(*max_floats, used);
+        }
+        X.ranges.emplace_back(r0, C.b1);
+    }
+}
+
 // One pair's launch chain for every block chunk - gather (unless the templates are already there), score or plane,
 // [neighbourhoods] - in stream order: the next chunk's gather overwrites the template planes behind this chunk's last
 // reader, and the host waits for none of them.  The pair is the stack's current image: the reference its rows
-// r_slot * rows .., the searched image its rows i_slot * rows ...
+// r_slot * rows .., the searched image its rows i_slot * rows ...  X != nullptr (a second-peak pass over the fixed table):
+// the chunk's score launch runs sub-range by sub-range with the scored-plane sink, blocks_second_kernel behind each.
 int blocks_pair(mtm_ctx* c, const BlockPlan& P, const BlockTables& B, int rows, int chans, int dtype, int method, int r_slot,
-                int i_slot, bool gather, const BlockSink& S) {
+                int i_slot, bool gather, const BlockSink& S, const BlockSecondPass* X = nullptr) {
     const ImageDev st = image_dev(c);
     const uint8_t* st_lo = c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane;        // uint16: [high ^ 0x80][low ^ 0x80]
     const ImageDev ref = stack_view(st, r_slot * rows, rows), img = stack_view(st, i_slot * rows, rows);
@@ -456,6 +614,7 @@ int blocks_pair(mtm_ctx* c, const BlockPlan& P, const BlockTables& B, int rows, 
     return blocks_dispatch(dtype, chans, [&](auto ch, auto u16) -> int {
         constexpr int CH = decltype(ch)::value;
         constexpr bool U16 = decltype(u16)::value;
+        size_t xr = 0;          // (the second-peak sub-ranges are walked in step with the chunks)
         for (const BlockChunk& C : P.chunks) {
             if (gather)
                 MTMC(for_launch_slices((size_t)C.b0, (size_t)C.b1, [&](size_t b0, unsigned nb) -> int {
@@ -464,7 +623,22 @@ int blocks_pair(mtm_ctx* c, const BlockPlan& P, const BlockTables& B, int rows, 
                     HIPC(hipGetLastError());
                     return MTM_OK;
                 }));
-            MTMC(for_launch_slices(C.t0, C.t1, [&](size_t t0, unsigned nt) -> int {
+            for (; X && xr < X->ranges.size() && X->ranges[xr].second <= C.b1; ++xr) {
+                const size_t r0 = (size_t)X->ranges[xr].first, r1 = (size_t)X->ranges[xr].second;
+                MTMC(for_launch_slices(X->tstart[r0], X->tstart[r1], [&](size_t t0, unsigned nt) -> int {
+                    hipLaunchKernelGGL((blocks_score_plane_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo, tpx,
+                                       toff, td, units, B.tiles + t0, method, mode_min, S.keys, c->blk_plane.as<float>(), X->poff);
+                    HIPC(hipGetLastError());
+                    return MTM_OK;
+                }));
+                MTMC(for_launch_slices(r0, r1, [&](size_t b0, unsigned nb) -> int {
+                    hipLaunchKernelGGL(blocks_second_kernel, dim3(nb), dim3(256), 0, c->stream, units, S.keys,
+                                       c->blk_plane.as<float>(), X->poff, (int)b0, mode_min, X->exclusion, X->keys2);
+                    HIPC(hipGetLastError());
+                    return MTM_OK;
+                }));
+            }
+            if (!X) MTMC(for_launch_slices(C.t0, C.t1, [&](size_t t0, unsigned nt) -> int {
                 if (S.side > 0)
                     hipLaunchKernelGGL((blocks_plane_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo, tpx, toff,
                                        td, units, B.tiles + t0, method, c->blk_clip.as<int32_t>(), S.side, S.first,
@@ -515,8 +689,15 @@ struct BlockValidate {
 // V != nullptr (mtm_match_blocks_passes_validated): blocks_validate_kernel behind every pass's records, the next pass's
 // units are predicted from its `steer` records instead of the raw ones, and the flags come back with the records.
 // V == nullptr launches and copies exactly what the chain did before validation existed.
+// X2 != nullptr (mtm_match_blocks_second, mtm_match_blocks_passes_second): every pass scores into planes and reduces them to
+// second keys (blocks_pair, BlockSecondPass), blocks_second_record_kernel behind the pass's blocks_record_kernel turns them
+// into records, which come back with the others and steer nothing.  X2 == nullptr: the chain as it is without.
+struct BlockSecondOut {
+    int exclusion;
+    mtm_hit* second;
+};
 int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPassPlan>& Q, const int32_t* offsets, int method,
-                       mtm_hit* out, float* nbhd, const BlockValidate* V = nullptr) {
+                       mtm_hit* out, float* nbhd, const BlockValidate* V = nullptr, const BlockSecondOut* X2 = nullptr) {
     const int rows = I.rows, cols = I.cols, chans = I.chans, dtype = I.dtype;
     // the tables of every pass, concatenated: one upload each
     std::vector<mtm_block> blocks;
@@ -537,6 +718,18 @@ int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
     S.offsets = offsets;
     S.recs = true;
     S.validate = V != nullptr;
+    // second peaks: every pass's plane sub-ranges, one table of plane offsets for the call
+    std::vector<BlockSecondPass> X(X2 ? Q.size() : 0);
+    std::vector<long long> poff;
+    if (X2) {
+        poff.reserve(n);
+        for (size_t p = 0; p < Q.size(); ++p) {
+            X[p].exclusion = X2->exclusion;
+            plan_second_pass(Q[p].plan, Q[p].blocks.data(), Q[p].margin, rows, cols, (size_t)c->boxes_max_floats, X[p], poff,
+                             &S.plane_floats);
+        }
+        S.poff = poff.data();
+    }
     MTMC(stage_block_call(c, S, [&] { return upload_block_pair(c, I); }));
 
     const int mode_min = method_mode_min(method) ? 1 : 0;
@@ -556,11 +749,20 @@ int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
                                p > 0 ? Q[p - 1].grid : BlockGrid{}, q.margin, rows, cols, B.units);
             HIPC(hipGetLastError());
         }
+        if (X2) {
+            X[p].poff = c->blk_poff.as<long long>() + b0;
+            X[p].keys2 = c->blk_keys2.as<unsigned long long>() + b0;
+        }
         MTMC(blocks_pair(c, q.plan, B, rows, chans, dtype, method, 0, 1, true,
-                         BlockSink{keys, nbhd ? c->blk_nbhd.as<float>() + 9 * b0 : nullptr, 0, 0}));
+                         BlockSink{keys, nbhd ? c->blk_nbhd.as<float>() + 9 * b0 : nullptr, 0, 0}, X2 ? &X[p] : nullptr));
         hipLaunchKernelGGL(blocks_record_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.units, keys, B.blocks, np, mode_min,
                            recs);
         HIPC(hipGetLastError());
+        if (X2) {
+            hipLaunchKernelGGL(blocks_second_record_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.units, X[p].keys2,
+                               B.blocks, np, mode_min, c->blk_recs2.as<mtm_hit>() + b0);
+            HIPC(hipGetLastError());
+        }
         if (V) {        // (np = nx ny: plan_block_passes lays out the whole grid)
             hipLaunchKernelGGL(blocks_validate_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, recs, q.grid.nx, q.grid.ny,
                                q.grid.sx, q.grid.sy, V->threshold, V->e4, c->blk_valid.as<uint8_t>() + b0,
@@ -573,7 +775,8 @@ int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
 
     // the records (and neighbourhoods, and flags) come back behind the call's single wait
     return finish_block_call(c, {{out, c->blk_recs.p, sizeof(mtm_hit) * n}, {nbhd, c->blk_nbhd.p, sizeof(float) * 9 * n},
-                                 {V ? V->valid : nullptr, c->blk_valid.p, n}}, n);
+                                 {V ? V->valid : nullptr, c->blk_valid.p, n},
+                                 {X2 ? X2->second : nullptr, c->blk_recs2.p, sizeof(mtm_hit) * n}}, n);
 }
 
 // threshold and epsilon of the median test: finite and >= 0, else MTM_E_INVALID naming the argument.
@@ -659,6 +862,102 @@ int mtm_debug_validate_blocks(mtm_ctx* c, const mtm_hit* recs, int nx, int ny, i
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(valid, c->blk_valid.p, n, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipMemcpyAsync(steer, c->blk_steer.p, sizeof(mtm_hit) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return MTM_OK;
+}
+
+int mtm_match_blocks_second(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                            int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
+                            const int32_t* offsets, int n_blocks, int margin, int method, mtm_hit* out, float* nbhd,
+                            int exclusion, mtm_hit* second) {
+    const char* who = "mtm_match_blocks_second";
+    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
+    MTMC(check_block_pair(c, who, n_blocks >= 0 && margin >= 0 && exclusion >= 0 && second && (n_blocks == 0 || (blocks && out)),
+                          method, I));
+    std::vector<BlockPassPlan> Q(1);
+    Q[0].grid = BlockGrid{};
+    Q[0].margin = margin;
+    MTMC(plan_blocks(rows, cols, chans, dtype, blocks, n_blocks, margin, 4 * (long long)c->boxes_max_floats, who, Q[0].plan,
+                     false));
+    if (n_blocks == 0) return MTM_OK;
+    MTMC(fix_block_tiles(Q[0].plan, rows, cols, blocks, margin, who));
+    Q[0].blocks.assign(blocks, blocks + n_blocks);
+    const BlockSecondOut X2{exclusion, second};
+    return match_block_passes(c, I, Q, offsets, method, out, nbhd, nullptr, &X2);
+}
+
+int mtm_match_blocks_passes_second(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                                   int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                                   const mtm_block_pass* passes, int n_passes, int method, double threshold, double epsilon,
+                                   mtm_hit* out, float* nbhd, uint8_t* valid, int exclusion, mtm_hit* second) {
+    const char* who = "mtm_match_blocks_passes_second";
+    if (valid) MTMC(check_validate_args(who, threshold, epsilon));      // (ahead of everything else, as the validated call)
+    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
+    MTMC(check_block_pair(c, who, n_passes >= 1 && passes && out && exclusion >= 0 && second, method, I));
+    std::vector<BlockPassPlan> Q;
+    MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
+    const BlockValidate V{threshold, 4.0 * epsilon, valid};
+    const BlockSecondOut X2{exclusion, second};
+    return match_block_passes(c, I, Q, nullptr, method, out, nbhd, valid ? &V : nullptr, &X2);
+}
+
+int mtm_debug_second_peaks(mtm_ctx* c, const float* planes, int n, const int32_t* oh, const int32_t* ow, const int32_t* firsts,
+                           int mode_min, int exclusion, mtm_hit* out) {
+    const char* who = "mtm_debug_second_peaks";
+    bool ok = planes && oh && ow && out && n >= 1 && exclusion >= 0 && (mode_min == 0 || mode_min == 1);
+    std::vector<long long> poff;
+    size_t total = 0;
+    for (int k = 0; ok && k < n; ++k) {
+        ok = oh[k] >= 1 && ow[k] >= 1 && (long long)oh[k] * ow[k] < (1ll << 32) &&
+             (!firsts || (firsts[k] >= 0 && (long long)firsts[k] < (long long)oh[k] * ow[k]));
+        poff.push_back((long long)total);
+        if (ok) total += (size_t)oh[k] * (size_t)ow[k];
+    }
+    if (!ok) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    // the first peak of every plane: the cell the caller names, or the largest key of the plane (0: a plane of NaNs)
+    std::vector<unsigned long long> first((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        const float* m = planes + poff[(size_t)k];
+        first[(size_t)k] = firsts ? second_cell_key(m[firsts[k]], mode_min, (uint32_t)firsts[k])
+                                  : second_scan_inl(m, oh[k], ow[k], 0ull, mode_min, 0);
+    }
+    if (!c) {           // the rule itself, on the host
+        for (int k = 0; k < n; ++k) {
+            const unsigned long long f = first[(size_t)k];
+            const unsigned long long key2 = f ? second_scan_inl(planes + poff[(size_t)k], oh[k], ow[k], f, mode_min, exclusion) : 0ull;
+            out[k] = second_key_record(key2, mode_min, k, 0, 0, ow[k], 0, 0);
+        }
+        return MTM_OK;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    HIPC(hipSetDevice(c->device));
+    std::vector<TrackUnit> units((size_t)n);
+    for (int k = 0; k < n; ++k) units[(size_t)k] = TrackUnit{k, 0, 0, oh[k], ow[k]};
+    const std::vector<mtm_block> blocks((size_t)n, mtm_block{0, 0, 0, 0});
+    const size_t nn = (size_t)n;
+    const struct { DevBuf& buf; const void* src; size_t bytes; } up[] = {
+        {c->blk_plane, planes, sizeof(float) * total},      {c->blk_poff, poff.data(), sizeof(long long) * nn},
+        {c->blk_units, units.data(), sizeof(TrackUnit) * nn}, {c->blk_blocks, blocks.data(), sizeof(mtm_block) * nn},
+        {c->blk_keys, first.data(), sizeof(unsigned long long) * nn}};
+    for (const auto& u : up) MTMC(u.buf.ensure(u.bytes));
+    MTMC(c->blk_keys2.ensure(sizeof(unsigned long long) * nn));
+    MTMC(c->blk_recs2.ensure(sizeof(mtm_hit) * nn));
+    for (const auto& u : up) HIPC(hipMemcpyAsync(u.buf.p, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
+    MTMC(for_launch_slices(0, nn, [&](size_t k0, unsigned nk) -> int {
+        hipLaunchKernelGGL(blocks_second_kernel, dim3(nk), dim3(256), 0, c->stream, c->blk_units.as<TrackUnit>(),
+                           c->blk_keys.as<unsigned long long>(), c->blk_plane.as<float>(), c->blk_poff.as<long long>(), (int)k0,
+                           mode_min, exclusion, c->blk_keys2.as<unsigned long long>());
+        HIPC(hipGetLastError());
+        return MTM_OK;
+    }));
+    hipLaunchKernelGGL(blocks_second_record_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, c->stream,
+                       c->blk_units.as<TrackUnit>(), c->blk_keys2.as<unsigned long long>(), c->blk_blocks.as<mtm_block>(), n,
+                       mode_min, c->blk_recs2.as<mtm_hit>());
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(out, c->blk_recs2.p, sizeof(mtm_hit) * nn, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
     return MTM_OK;
 }

@@ -388,6 +388,10 @@ struct mtm_ctx {
     // mtm_match_blocks_passes_validated / mtm_debug_validate_blocks: blocks_validate_kernel's flag per record (1 B) and the
     // records that steer the next pass (the raw ones with every outlier's position replaced), pass-major as blk_recs
     DevBuf blk_valid, blk_steer;
+    // mtm_match_blocks_second / mtm_match_blocks_passes_second / mtm_debug_second_peaks: the float32 scores of one launch
+    // sub-range's maps (block k's oh x ow plane at blk_poff[k] floats, written by blocks_score_plane_kernel and read by
+    // blocks_second_kernel behind it), the second-peak key per block and its record, pass-major as blk_recs
+    DevBuf blk_plane, blk_poff, blk_keys2, blk_recs2;
     // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
     // template set sub_gen) and the per-call point table and scores.
     uint64_t sub_gen = 0;

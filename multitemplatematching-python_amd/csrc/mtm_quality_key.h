@@ -2,7 +2,8 @@
 // index, merged by atomicMax) read back, as inline functions for the host (decode_quality_key and decode_extremum_key,
 // mtm_host.cpp; decode_block_keys, mtm_blocks.hip) and the device (track_record, mtm_track.hip; blocks_record_kernel and
 // blocks_nbhd_kernel, mtm_blocks.hip): a single source for the order word's float32, the index and the record, so that
-// the record a call decodes on the host is the record a kernel writes, bit for bit.
+// the record a call decodes on the host is the record a kernel writes, bit for bit.  key_float_order forms the order word
+// where host and device share the code that builds a key (mtm_blocks_second.h).
 #pragma once
 #include <cstdint>
 
@@ -17,6 +18,15 @@ MTM_HOST_DEVICE inline float key_order_float(uint32_t o) {
     float v;
     __builtin_memcpy(&v, &b, 4);
     return v;
+}
+
+// The order word of a float32, key_order_float's inverse: mf_float_order's bits (-0 stored as +0), for code that forms a
+// key on the host as well as on the device (mtm_blocks_second.h).  The score kernels keep calling mf_float_order.
+MTM_HOST_DEVICE inline uint32_t key_float_order(float v) {
+    if (v == 0.0f) v = 0.0f;     // -0 -> +0
+    uint32_t b;
+    __builtin_memcpy(&b, &v, 4);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
 // The row-major index in a key's low word (stored complemented: of equal values the first output wins the atomicMax).

@@ -44,7 +44,15 @@ flat patch planted in the reference over a coarse block (``flat_block_pair``), t
 patch and clear of the border found at the true shift with and without validation (``found_validated``,
 ``found_unvalidated``).
 
-Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F] [--passes [--validate]]
+--second [r] (alone or with --passes): the second correlation peak - milliseconds per call of
+  plain  - matchBlocks(reference, image, grid, margin), or with --passes matchBlocksMultipass of the two passes above
+  second - the same call with second=r (default 2), interleaved with it in one run
+with their difference (``second_cost_ms``, medians of the same run), ``equal_to_model`` (every block's second position and
+float32 score bits against the brute-force rule of tests/blocks_second_model.py over MTM.computeScoreMap of the block and its
+box, NaN exactly where the model has no second peak), ``first_peaks_unchanged`` (positions and score bits of the call
+without ``second``), the blocks without a second peak and the median peak ratio of every pass.
+
+Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F] [--passes [--validate]] [--second [r]]
 """
 import argparse
 import json
@@ -398,6 +406,60 @@ def run_passes_validate(MTM, spec, reps, warmup):
     }
 
 
+def run_second(MTM, spec, reps, warmup, radius, passes_form):
+    """--second: the call with and without the second peak, interleaved; the second peaks against the brute-force model of
+    tests/blocks_second_model.py over MTM.computeScoreMap of every block and its box."""
+    for p in (os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import blocks_second_model as S
+    from MTM import blocks as B
+    name, hw, chans, dtype, side, margin = spec
+    ref, img = workload(spec)
+    method = MTM.TM_CCOEFF_NORMED
+    if passes_form:
+        passes = [(side, 2 * side, margin), (side, side, max(1, margin // 4))]
+        methods = {"plain": lambda: MTM.matchBlocksMultipass(ref, img, passes, method),
+                   "second": lambda: MTM.matchBlocksMultipass(ref, img, passes, method, second=radius)}
+    else:
+        grid = B.grid(ref.shape, side)
+        methods = {"plain": lambda: [(grid,) + MTM.matchBlocks(ref, img, grid, margin, method)],
+                   "second": lambda: [(grid,) + MTM.matchBlocks(ref, img, grid, margin, method, second=radius)]}
+    results = {}
+    for k, fn in methods.items():
+        for _ in range(warmup):
+            results[k] = fn()
+    ms = {k: [] for k in methods}
+    for _ in range(reps):
+        for k, fn in methods.items():
+            t0 = time.perf_counter()
+            fn()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    equal, unchanged, steer, n_none, ratios = True, True, None, 0, []
+    for p, (got, plain) in enumerate(zip(results["second"], results["plain"])):
+        b, pos, sc, pos2, sc2 = got
+        unchanged = unchanged and bool((pos == plain[1]).all() and sc.tobytes() == plain[2].tobytes())
+        off = None if p == 0 else B.predict_offsets(img.shape, passes[p - 1][:2], steer, passes[p][:2])
+        m = passes[p][2] if passes_form else margin
+        exp = S.expected_seconds(ref, img, b.tolist(), off, m, method, radius, MTM.computeScoreMap, firsts=pos)
+        try:
+            S.same_seconds(pos2, sc2, exp)
+        except AssertionError:
+            equal = False
+        steer = pos
+        n_none += int(np.isnan(sc2).sum())
+        ratio = B.peak_ratio(sc, sc2, method)
+        ratios.append(round(float(np.median(ratio[~np.isnan(ratio)])), 3) if not np.isnan(ratio).all() else None)
+    return {
+        "workload": name, "image": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype), "form": "passes" if passes_form else "pair",
+        "blocks": [int(len(r[0])) for r in results["second"]], "margin": [p[2] for p in passes] if passes_form else margin,
+        "exclusion": radius, "ms": {k: round(v, 3) for k, v in med.items()}, "ms_min": {k: round(min(v), 3) for k, v in ms.items()},
+        "second_cost_ms": round(med["second"] - med["plain"], 3), "equal_to_model": equal, "first_peaks_unchanged": unchanged,
+        "without_second_peak": n_none, "median_peak_ratio": ratios, "reps": reps,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=5)
@@ -406,16 +468,22 @@ def main():
     ap.add_argument("--stack", type=int, default=0, metavar="F", help="the movie form: matchBlocksStack over F frames")
     ap.add_argument("--passes", action="store_true", help="coarse to fine: matchBlocksMultipass against the single pass")
     ap.add_argument("--validate", action="store_true", help="with --passes: the median test between the passes")
+    ap.add_argument("--second", type=int, nargs="?", const=2, default=None, metavar="r",
+                    help="the second peak with exclusion radius r (default 2): the pair call, or with --passes the passes")
     args = ap.parse_args()
     if args.validate and not args.passes:
         ap.error("--validate goes with --passes")
+    if args.second is not None and (args.second < 0 or args.validate or args.stack):
+        ap.error("--second takes a radius >= 0 and goes alone or with --passes")
     import build as mtm_build
     mtm_build.build()
     import MTM
     for spec in WORKLOADS:
         if args.only and spec[0] != args.only:
             continue
-        if args.passes and args.validate:
+        if args.second is not None:
+            print(json.dumps(run_second(MTM, spec, args.reps, args.warmup, args.second, args.passes)), flush=True)
+        elif args.passes and args.validate:
             print(json.dumps(run_passes_validate(MTM, spec, args.reps, args.warmup)), flush=True)
         elif args.passes:
             print(json.dumps(run_passes(MTM, spec, args.reps, args.warmup)), flush=True)

@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes, mtm_match_blocks_passes_validated, mtm_debug_validate_blocks, mtm_match_blocks_second, mtm_match_blocks_passes_second, mtm_debug_second_peaks - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes, mtm_match_blocks_passes_validated, mtm_debug_validate_blocks, mtm_match_blocks_second, mtm_match_blocks_passes_second, mtm_debug_second_peaks, mtm_deform_image, mtm_match_blocks_passes_deformed - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -799,6 +799,43 @@ int mtm_match_blocks_passes_second(mtm_ctx* ctx, const void* reference, int64_t 
  * them.  n >= 1, oh, ow >= 1, oh * ow < 2^32, mode_min 0 or 1, exclusion >= 0. */
 int mtm_debug_second_peaks(mtm_ctx* ctx, const float* planes, int n, const int32_t* oh, const int32_t* ow,
                            const int32_t* firsts, int mode_min, int exclusion, mtm_hit* out);
+
+/* Window deformation.  THE RULE, in integers.  A coarse grid of nx x ny blocks of size (wc, hc) at stride (sx,
+ * sy), row-major, carries displacements d[j nx + i] = (dx, dy).  Coordinates are doubled: pixel x is X2 = 2 x, the centre of a
+ * block at x of width w is X2 = 2 x + w - 1, the centre of coarse column i is Cx_i = 2 i sx + wc - 1.  Per axis, nx == 1: i =
+ * 0, ax = 0; else i = clamp(floor((X2 - (wc - 1)) / (2 sx)), 0, nx - 2), a = clamp(X2 - Cx_i, 0, 2 sx), ax = (256 a + sx) / (2
+ * sx) in 0 .. 256 (constant extrapolation outside the centres' hull); j, ay likewise; i1 = min(i + 1, nx - 1), j1 likewise.
+ * The field in Q8 (1/256 pixel), per component, in int64, the shift arithmetic (a floor):
+ *   F = (d[j,i] (256 - ax)(256 - ay) + d[j,i1] ax (256 - ay) + d[j1,i] (256 - ax) ay + d[j1,i1] ax ay + 128) >> 8.
+ * The warp: output pixel (x, y) samples X = clamp(256 x + Fx(2 x, 2 y), 0, 256 (W - 1)), Y likewise with H; x0 = X >> 8, fx =
+ * X & 255, x1 = min(x0 + 1, W - 1), y0, fy, y1 likewise; per channel
+ *   out = (I[y0,x0] (256 - fx)(256 - fy) + I[y0,x1] fx (256 - fy) + I[y1,x0] (256 - fx) fy + I[y1,x1] fx fy + 32768) >> 16.
+ * A zero field returns the image, an integer constant field the shifted image with replicated edges, both exactly.
+ *
+ * mtm_deform_image warps one image by the field of `displacements` (2 int32 per block of the grid of bw x bh blocks at stride
+ * (sx, sy) over the image, row-major: dx, dy; each within +-2^22) into `out` (the image's shape and pixel type, rows
+ * out_stride_bytes apart).  uint8 with 1 or 3 channels or single-channel uint16, at most 65535 rows; an empty grid is
+ * MTM_E_INVALID.  ctx == NULL runs the rule on the host (no GPU); with a context the image and the displacements are
+ * uploaded, the warp kernel is launched once and the warped image comes back: one wait (mtm_get_timing: total_ms is the
+ * warp kernel's time alone).  The image becomes the context's current image. */
+int mtm_deform_image(mtm_ctx* ctx, const void* px, int64_t row_stride_bytes, int rows, int cols, int chans, int dtype, int bw,
+                     int bh, int sx, int sy, const int32_t* displacements, void* out, int64_t out_stride_bytes);
+
+/* mtm_match_blocks_passes with window deformation between the passes.  Pass 0 is unchanged.  For a pass p >=
+ * 1, with d the displacements (record position - block position) of the records that steer it - pass p - 1's, or with valid
+ * != NULL the validated ones of mtm_match_blocks_passes_validated -: the whole ORIGINAL image is warped by the field of d (the
+ * rule above; never a warp of a warp) into a buffer of its own, every block of pass p is searched in the warped image in its
+ * own box widened by the pass's margin (no offset), nbhd's neighbourhoods come from the warped image, and with c = F at the
+ * block's doubled centre (2 x + w - 1, 2 y + h - 1) the record's position is the one found plus ((c + 128) >> 8) per
+ * component - not clamped: it may lie outside the image, it carries a displacement.  That record is what `out` holds, what
+ * validation tests and what steers pass p + 1.  predicted (required): 2 int32 per record, pass-major as out, c in Q8, zero
+ * for pass 0; a refined position is the fitted one in the warped image plus c / 256.  valid may be NULL (no validation;
+ * threshold and epsilon are then not read).  n_passes * max(rows, cols) must not pass 2^22.  Still one wait; a deformed
+ * pass launches the warp and two small kernels, and no unit kernel.  Everything else as mtm_match_blocks_passes. */
+int mtm_match_blocks_passes_deformed(mtm_ctx* ctx, const void* reference, int64_t reference_stride_bytes, const void* image,
+                                     int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                                     const mtm_block_pass* passes, int n_passes, int method, double threshold, double epsilon,
+                                     mtm_hit* out, float* nbhd, uint8_t* valid, int32_t* predicted);
 
 /* The 3 x 3 score neighbourhoods of n points in one call: out[9 k + 3 (1 + dy) + (1 + dx)] = the score of
  * template pts[k].templ_idx at window (x + dx, y + dy) of the image's score map, NaN for a window outside the map.  Image:

@@ -27,7 +27,7 @@ pinned_empty = _lib.pinned_empty        # numpy arrays in page-locked memory (fa
 __all__ = ["NMS", "Hit", "matchTemplates", "findMatches", "computeScoreMap", "TemplateMatcher", "matchTemplatesBatch",
            "findMatchesPyramid", "matchTemplatesPyramid", "findMatchesInBoxes", "matchTemplatesInBoxes", "trackTemplates",
            "hitNeighbourhoods", "refineHits", "matchBlocks", "matchBlocksStack", "matchBlocksMultipass",
-           "pinned_empty", "drawBoxesOnRGB",
+           "deformImage", "pinned_empty", "drawBoxesOnRGB",
            "drawBoxesOnGray", "TM_SQDIFF", "TM_SQDIFF_NORMED", "TM_CCORR", "TM_CCORR_NORMED",
            "TM_CCOEFF", "TM_CCOEFF_NORMED", "__version__"]
 
@@ -719,3 +719,4 @@ from .boxes import findMatchesInBoxes, matchTemplatesInBoxes  # noqa: E402  (man
 from .tracking import trackTemplates  # noqa: E402  (templates tracked through a stack of frames)
 from .subpixel import hitNeighbourhoods, refineHits  # noqa: E402  (sub-pixel positions from score neighbourhoods)
 from .blocks import matchBlocks, matchBlocksStack, matchBlocksMultipass  # noqa: E402  (block matching between two images, over a frame stack, coarse to fine)
+from .blocks import deformImage  # noqa: E402  (an image warped by a measured displacement field, on the device)

@@ -242,6 +242,14 @@ SYMBOLS = {
                                                       ctypes.c_int, ctypes.c_void_p]),
     "mtm_debug_second_peaks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "mtm_deform_image": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    "mtm_match_blocks_passes_deformed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                        ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                                        ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p]),
     "mtm_hit_neighbourhoods": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
@@ -620,6 +628,22 @@ def debug_validate_blocks(positions, grid_shape, step, threshold=2.0, epsilon=0.
                                         float(threshold), float(epsilon), valid.ctypes.data, steer.ctypes.data),
           "mtm_debug_validate_blocks")
     return valid.astype(bool), np.stack((steer["x"], steer["y"]), axis=1).astype(np.int64)
+
+
+def deform_image(image, grid, displacements, context=None):
+    """The warp of mtm_deform_image: `image` (uint8 with 1 or 3 channels, or single-channel uint16) by the field of
+    `displacements` - (N, 2) integers (dx, dy), each within +-2^22 - over the coarse `grid` = (bw, bh, sx, sy); the warped
+    image, of the image's shape.  `context=None` runs the rule in the library's host code, no GPU needed; with a Context
+    the image goes through deform_image_kernel."""
+    a, ptr, stride = _pixel_rows(image)
+    chans = 1 if a.ndim == 2 else a.shape[2]
+    d = np.ascontiguousarray(displacements, dtype=np.int32).reshape(-1, 2)
+    out = np.empty(a.shape, dtype=a.dtype)
+    lib = load() if context is None else context._lib
+    check(lib.mtm_deform_image(None if context is None else context._h, ptr, stride, a.shape[0], a.shape[1], chans,
+                               _dtype_code(a), *(int(v) for v in grid), d.ctypes.data, out.ctypes.data, out.strides[0]),
+          "mtm_deform_image")
+    return out
 
 
 def debug_second_peaks(planes, mode_min, exclusion, firsts=None, context=None):
@@ -1128,19 +1152,38 @@ class Context(_RecordMemo):
         """Test support: the module's debug_validate_blocks on this context - blocks_validate_kernel, launched once."""
         return debug_validate_blocks(positions, grid_shape, step, threshold, epsilon, context=self)
 
-    def match_blocks_passes(self, reference, image, passes, counts, method, with_nbhd=False, validate=None, second=None):
+    def deform_image(self, image, grid, displacements):
+        """The module's deform_image on this context: one upload, deform_image_kernel, the warped image back."""
+        return deform_image(image, grid, displacements, context=self)
+
+    def match_blocks_passes(self, reference, image, passes, counts, method, with_nbhd=False, validate=None, second=None,
+                            deform=False):
         """Coarse-to-fine block matching in one native call (mtm_match_blocks_passes): `passes` BLOCK_PASS_DTYPE records,
         `counts` the blocks of every pass's grid.  Returns (records, pass-major, sum(counts) of them; neighbourhoods in
         the same order, or None).  The templates set on the context are not touched.
         `validate` = (threshold, epsilon): the median test between the passes (mtm_match_blocks_passes_validated); a third
         element is returned, the (sum(counts),) bool flags of the records in the same order.
         `second` = the exclusion radius (mtm_match_blocks_passes_second): the second peaks' records of every pass, in the
-        same order, are returned as the last element."""
+        same order, are returned as the last element.
+        `deform` (not with `second`): window deformation between the passes (mtm_match_blocks_passes_deformed); the last
+        element returned is then the (sum(counts), 2) int32 field at every block's centre in Q8, zero for pass 0."""
         passes = block_pass_records(passes)
         n = int(sum(counts))
         out = np.empty(n, dtype=HIT_DTYPE)
         nbhd = np.empty((n, 3, 3), dtype=np.float32) if with_nbhd else None
         pair, keep = self._pair_args(reference, image)
+        if deform:
+            if second is not None:
+                raise ValueError("match_blocks_passes: deform does not go with second")
+            threshold, epsilon = validate if validate is not None else (0.0, 0.0)
+            valid = np.zeros(n, dtype=np.uint8) if validate is not None else None
+            pred = np.zeros((n, 2), dtype=np.int32)
+            check(self._lib.mtm_match_blocks_passes_deformed(*pair, passes.ctypes.data, len(passes), int(method),
+                                                             float(threshold), float(epsilon), out.ctypes.data,
+                                                             nbhd.ctypes.data if with_nbhd else None,
+                                                             None if valid is None else valid.ctypes.data, pred.ctypes.data),
+                  "mtm_match_blocks_passes_deformed")
+            return (out, nbhd, pred) if valid is None else (out, nbhd, valid.astype(bool), pred)
         if second is not None:
             threshold, epsilon = validate if validate is not None else (0.0, 0.0)
             valid = np.zeros(n, dtype=np.uint8) if validate is not None else None

@@ -42,6 +42,15 @@ block's map outside a small exclusion window around the first - from the same na
 5.6.3); ``peak_ratio`` of the two is the vector's signal-to-noise, which tells a unique match from a periodic texture, a
 flat patch or an occluded block.  ``second_peaks`` states the rule in numpy, for ensemble planes.
 
+``matchBlocksMultipass(deform=True)`` adds window deformation between the passes (mtm_match_blocks_passes_deformed, DESIGN
+5.6.4): a later pass does not just move every block's box, it warps the whole original image back by the displacement
+field interpolated from the pass before (``displacement_field``: bilinear between the coarse blocks' centres, Q8 integers;
+``deform``: the bilinear warp, integers again) and searches the blocks in the warped image, so that a block under shear,
+rotation or strain still meets a window shaped like itself; ``field_at`` is the field at the blocks' centres, which the
+pass adds to what it finds.  All on the device, one native call; the three helpers state the rule in numpy, bit for bit.
+``deformImage`` is the warp by itself on the device (mtm_deform_image): how a frame is registered once its drift field
+is known.
+
 ``matchBlocksStack`` is the movie form: the pairs of a stack of frames - each frame against the previous or against the
 first - in one native call (mtm_match_blocks_stack), every frame uploaded once; per pair the very results of
 ``matchBlocks``, or (``ensemble=True``) every block's correlation plane averaged over the pairs and its peak
@@ -55,7 +64,8 @@ from . import _lib, subpixel
 from . import TM_CCOEFF_NORMED
 
 __all__ = ["matchBlocks", "matchBlocksStack", "matchBlocksMultipass", "plane_peaks", "grid", "search_box", "search_box_at",
-           "predict_offsets", "displacements", "grid_shape", "validate", "second_peaks", "peak_ratio"]
+           "predict_offsets", "displacements", "grid_shape", "validate", "second_peaks", "peak_ratio", "displacement_field",
+           "field_at", "deform", "deformImage"]
 
 _I64 = np.dtype(np.int64)
 _U16_MAX_PIXELS = 1 << 21       # mtm_match_blocks: uint16 correlations stay below 2^53, exact in float64
@@ -234,6 +244,133 @@ def predict_offsets(shape, coarse, positions, fine):
     ix = _nearest(nx, sx, wc, fg[:, 0], fg[:, 2])
     iy = _nearest(ny, sy, hc, fg[:, 1], fg[:, 3])
     return pos[iy * nx + ix] - np.stack((ix * sx, iy * sy), axis=1)
+
+
+_DEFORM_MAX = 1 << 22           # mtm_blocks_deform.h: the largest |displacement| the field takes
+
+
+def _deform_axis(n, s, wc, X2):
+    """Per axis of n coarse blocks of size wc at stride s: (i, a8) at the doubled coordinates X2 - the lower node and the
+    weight (0 .. 256) of node min(i + 1, n - 1) (deform_axis_inl, mtm_blocks_deform.h)."""
+    X2 = np.asarray(X2, dtype=_I64)
+    if n <= 1:
+        return np.zeros(X2.shape, _I64), np.zeros(X2.shape, _I64)
+    i = np.clip((X2 - (wc - 1)) // (2 * s), 0, n - 2)
+    a = np.clip(X2 - (2 * i * s + wc - 1), 0, 2 * s)
+    return i, (256 * a + s) // (2 * s)
+
+
+def _deform_args(shape, coarse, displacements, who):
+    """(wc, hc, sx, sy, nx, ny, d): the coarse grid's axes and its displacements as an (ny, nx, 2) int64 array."""
+    try:
+        cb, cs = coarse
+    except (TypeError, ValueError):
+        raise ValueError("%s: coarse is a (block, step) pair (got %r)" % (who, coarse)) from None
+    wc, hc, sx, sy, nx, ny = _grid_axes(shape, cb, cs, who)
+    d = np.asarray(displacements)
+    if d.ndim != 2 or d.shape[1] != 2 or len(d) != nx * ny:
+        raise ValueError("%s: displacements of shape %s for a coarse grid of %d blocks (expected (%d, 2))" % (
+            who, d.shape, nx * ny, nx * ny))
+    if d.dtype.kind not in "iu":
+        raise TypeError("%s: displacements must be integers (got %s): refined positions never steer a pass" % (who, d.dtype))
+    if nx * ny == 0:
+        raise ValueError("%s: the coarse grid is empty" % who)
+    if d.dtype.kind == "u":
+        d = np.minimum(d, np.uint64(_DEFORM_MAX + 1))
+    d = d.astype(_I64)
+    if np.abs(d).max() > _DEFORM_MAX:
+        raise ValueError("%s: displacements beyond 2^22 pixels are not supported" % who)
+    return wc, hc, sx, sy, nx, ny, d.reshape(ny, nx, 2)
+
+
+def _field(d, ix, ax, iy, ay):
+    """The Q8 field from the nodes d (ny, nx, 2) at lower nodes (iy, ix) with weights (ay, ax), broadcast together."""
+    ny, nx = d.shape[:2]
+    ix1, iy1 = np.minimum(ix + 1, nx - 1), np.minimum(iy + 1, ny - 1)
+    ax, ay = ax[..., None], ay[..., None]
+    return (d[iy, ix] * (256 - ax) * (256 - ay) + d[iy, ix1] * ax * (256 - ay) + d[iy1, ix] * (256 - ax) * ay
+            + d[iy1, ix1] * ax * ay + 128) >> 8
+
+
+def displacement_field(shape, coarse, displacements):
+    """The per-pixel displacement field a coarse grid's displacements give, (H, W, 2) int64 of (Fx, Fy) in Q8 (1/256 px) -
+    the field ``matchBlocksMultipass(deform=True)`` warps by, in plain numpy.  ``coarse``: ``(block, step)`` as ``grid``
+    takes them; ``displacements``: the integer (Nc, 2) ``(dx, dy)`` of ``grid(shape, *coarse)`` in row-major order.
+
+    The rule (mtm_blocks_deform.h), in integers on DOUBLED coordinates - pixel x is ``X2 = 2 x``, the centre of a block at
+    x of width w is ``2 x + w - 1``, the centre of coarse column i is ``Cx_i = 2 i sx + wc - 1``.  Per axis (nx == 1: ``i =
+    0, ax = 0``): ``i = clamp((X2 - (wc - 1)) // (2 sx), 0, nx - 2)``, ``a = clamp(X2 - Cx_i, 0, 2 sx)``, ``ax = (256 a +
+    sx) // (2 sx)`` in 0..256 - constant extrapolation outside the centres' hull -, ``i1 = min(i + 1, nx - 1)``; ``j, ay,
+    j1`` likewise.  Per component, in int64, the shift a floor:
+
+        F = (d[j,i] (256-ax)(256-ay) + d[j,i1] ax (256-ay) + d[j1,i] (256-ax) ay + d[j1,i1] ax ay + 128) >> 8
+
+    Float displacements raise TypeError, a wrong length (or one beyond 2^22 pixels) ValueError."""
+    wc, hc, sx, sy, nx, ny, d = _deform_args(shape, coarse, displacements, "displacement_field")
+    H, W = int(shape[0]), int(shape[1])
+    ix, ax = _deform_axis(nx, sx, wc, 2 * np.arange(W, dtype=_I64))
+    iy, ay = _deform_axis(ny, sy, hc, 2 * np.arange(H, dtype=_I64))
+    return _field(d, ix[None, :], ax[None, :], iy[:, None], ay[:, None])
+
+
+def field_at(shape, coarse, displacements, blocks):
+    """``displacement_field``'s rule at the doubled centres ``(2 x + w - 1, 2 y + h - 1)`` of ``blocks`` ((N, 4) integers
+    of ``(x, y, w, h)``): (N, 2) int64 in Q8 - what a deformed pass adds to what it finds in the warped image."""
+    wc, hc, sx, sy, nx, ny, d = _deform_args(shape, coarse, displacements, "field_at")
+    b = np.asarray(blocks)
+    if b.size == 0:
+        return np.zeros((0, 2), _I64)
+    if b.ndim != 2 or b.shape[1] != 4 or b.dtype.kind not in "iu":
+        raise ValueError("field_at: blocks must be an (N, 4) integer array of (x, y, w, h)")
+    b = b.astype(_I64)
+    ix, ax = _deform_axis(nx, sx, wc, 2 * b[:, 0] + b[:, 2] - 1)
+    iy, ay = _deform_axis(ny, sy, hc, 2 * b[:, 1] + b[:, 3] - 1)
+    return _field(d, ix, ax, iy, ay)
+
+
+def deform(image, field):
+    """``image`` (H, W[, C], uint8 or uint16) warped by ``field`` ((H, W, 2) integers, Q8): output pixel (x, y) samples
+    ``X = clamp(256 x + Fx, 0, 256 (W - 1))``, ``Y`` likewise with H; ``x0 = X >> 8, fx = X & 255, x1 = min(x0 + 1, W -
+    1)``, ``y0, fy, y1`` likewise; per channel
+
+        out = (I[y0,x0] (256-fx)(256-fy) + I[y0,x1] fx (256-fy) + I[y1,x0] (256-fx) fy + I[y1,x1] fx fy + 32768) >> 16
+
+    A zero field returns the image, an integer constant field the shifted image with replicated edges - both exactly."""
+    img = np.asarray(image)
+    f = np.asarray(field)
+    if img.dtype not in (np.uint8, np.uint16) or img.ndim not in (2, 3) or img.size == 0:
+        raise ValueError("deform takes a non-empty uint8 or uint16 image (got %s of shape %s)" % (img.dtype, img.shape))
+    if f.shape != img.shape[:2] + (2,):
+        raise ValueError("deform: a field of shape %s for an image of shape %s" % (f.shape, img.shape))
+    if f.dtype.kind not in "iu":
+        raise TypeError("deform: the field must be integers in Q8 (got %s)" % f.dtype)
+    H, W = img.shape[:2]
+    f = f.astype(_I64)
+    X = np.clip(256 * np.arange(W, dtype=_I64)[None, :] + f[:, :, 0], 0, 256 * (W - 1))
+    Y = np.clip(256 * np.arange(H, dtype=_I64)[:, None] + f[:, :, 1], 0, 256 * (H - 1))
+    x0, fx, y0, fy = X >> 8, X & 255, Y >> 8, Y & 255
+    x1, y1 = np.minimum(x0 + 1, W - 1), np.minimum(y0 + 1, H - 1)
+    v = img.astype(_I64)
+    if img.ndim == 3:
+        fx, fy = fx[:, :, None], fy[:, :, None]
+    out = (v[y0, x0] * (256 - fx) * (256 - fy) + v[y0, x1] * fx * (256 - fy) + v[y1, x0] * (256 - fx) * fy
+           + v[y1, x1] * fx * fy + 32768) >> 16
+    return out.astype(img.dtype)
+
+
+def deformImage(image: np.ndarray, coarse, displacements, context=None):
+    """``image`` warped by the field of a coarse grid's displacements, on the device: ``deform(image,
+    displacement_field(image.shape, coarse, displacements))`` bit for bit, in one native call (mtm_deform_image: the
+    image and the displacements go up, one kernel interpolates the field and resamples, the warped image comes back) - how
+    a frame is registered once its drift field is known.  ``image``: uint8 with 1 or 3 channels or single-channel uint16;
+    ``coarse`` and ``displacements`` as ``displacement_field`` takes them; ``context``: the _lib.Context to run on."""
+    if not isinstance(image, np.ndarray):
+        raise TypeError("image must be a numpy array (got %s)" % type(image).__name__)
+    _check_pixels(image, "deformImage", "images", "%s images")
+    wc, hc, sx, sy, nx, ny, d = _deform_args(image.shape, coarse, displacements, "deformImage")
+    ctx = context or _lib.default_context()     # (only now: every argument error comes before "no GPU")
+    with ctx.lock:
+        return ctx.deform_image(image, (wc, hc, sx, sy), d.reshape(-1, 2)).reshape(image.shape)
 
 
 def displacements(blocks, positions):
@@ -445,7 +582,7 @@ def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, m
 
 
 def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, method: int = TM_CCOEFF_NORMED, *,
-                         refine: bool = False, context=None, validate=None, second=None):
+                         refine: bool = False, context=None, validate=None, second=None, deform: bool = False):
     """
     Coarse-to-fine block matching in one native call.  ``passes``: a non-empty sequence of ``(block, step, margin)``,
     ``block`` and ``step`` as ``grid`` takes them (``step=None``: the block size).  Pass 0 is ``matchBlocks`` over its
@@ -484,11 +621,43 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
     (after ``valid_p`` when ``validate`` is given), those of ``matchBlocks(reference, image, b, margin, method,
     offsets=off, second=second)`` in the loops above (mtm_match_blocks_passes_second, still one native call).  The second
     peaks steer nothing: positions, scores and flags are those of the call without ``second``, bit for bit.
+
+    ``deform``: ``False`` (the call above, in every respect) or ``True``: window deformation between the passes
+    (mtm_match_blocks_passes_deformed, DESIGN 5.6.4: still one native call and one host wait).  Instead of moving every
+    block's box by the nearest coarse block's displacement, a pass p >= 1 warps the whole ORIGINAL image back by the field
+    interpolated from the displacements that steer it (``displacement_field``, ``deform``; never a warp of a warp, so blur
+    does not compound), searches every block in the warped image in its own box, and adds the field at the block's centre
+    (``field_at``) to what it found - under shear, rotation or strain the block then matches a window deformed like
+    itself.  Every pass's tuple gets ``predicted_p`` appended (after ``valid_p`` when ``validate`` is given): float64 (N,
+    2), the field at the blocks' centres in pixels, zeros for pass 0.  The call equals, bit for bit, the loop
+
+        steer = None
+        for p, (block, step, margin) in enumerate(passes):
+            b = grid(image.shape, block, step)
+            if p == 0:
+                searched, c = image, np.zeros((len(b), 2), np.int64)
+            else:
+                prev = passes[p - 1][:2]
+                d = steer - grid(image.shape, *prev)[:, :2]
+                searched = deform(image, displacement_field(image.shape, prev, d))
+                c = field_at(image.shape, prev, d, b)
+            pos_w, sc = matchBlocks(reference, searched, b, margin, method)
+            pos = pos_w + ((c + 128) >> 8)
+            steer = pos     # with validate: b[:, :2] + validate(grid_shape(...), pos - b[:, :2], thr, eps)[1]
+            # refine=True: matchBlocks(..., refine=True)[0] + c / 256.0
+
+    with ``positions_p = pos`` (refined: the fit in the warped image plus ``c / 256.0``), ``scores_p = sc``, ``valid_p``
+    the flags of ``validate`` over ``pos - b[:, :2]`` and ``predicted_p = c / 256.0``.  An integer position of a deformed
+    pass carries a displacement and is NOT clamped: it may lie outside ``[0, W - w]`` x ``[0, H - h]``.  ``deform=True``
+    with ``second`` raises ValueError; ``len(passes) * max(H, W)`` must stay within 2^22.
     """
     _check_images(reference, image)
     _check_method(method, "matchBlocksMultipass")
     _check_flag(refine, "refine")
+    _check_flag(deform, "deform")
     r = _check_second(second)
+    if deform and r is not None:
+        raise ValueError("matchBlocksMultipass: deform=True does not go with second= in this version")
     if validate is not None:
         if validate is True:
             validate = (2.0, 0.5)
@@ -521,9 +690,18 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
         rec[p] = (w, h, sx, sy, _clip_margin(margin, image.shape))
         grids.append(grid(image.shape, block, step))
     counts = [len(g) for g in grids]
+    if deform and len(pl) * max(image.shape[0], image.shape[1]) > _DEFORM_MAX:
+        raise ValueError("matchBlocksMultipass: deform=True takes len(passes) * max(H, W) of at most 2^22 (got %d passes "
+                         "over %d x %d images)" % (len(pl), image.shape[0], image.shape[1]))
     ctx = context or _lib.default_context()     # (only now: every argument error comes before "no GPU")
+    pred = None
     with ctx.lock:
-        if r is not None:
+        if deform:
+            kw = {} if validate is None else {"validate": validate}
+            raw, nbhd, *got = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine, deform=True, **kw)
+            flags = got[0] if validate is not None else None
+            pred = np.asarray(got[-1], dtype=_I64).reshape(-1, 2) / 256.0
+        elif r is not None:
             kw = {} if validate is None else {"validate": validate}
             *got, raw2 = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine, second=r, **kw)
             raw, nbhd = got[:2]
@@ -532,7 +710,15 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
             raw, nbhd = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine)
         else:
             raw, nbhd, flags = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine, validate=validate)
-    positions, scores = _positions_scores(raw, nbhd, method, refine)       # (one fit over every pass and block)
+    if deform and refine:
+        # the record holds the warped position plus the field's integer part: the fit starts from the position in the
+        # warped image, in integers, and the whole field is added to it
+        positions, scores = _positions_scores(raw, None, method, False)
+        ox, oy = subpixel.fit_offsets(nbhd, method)
+        shift = (np.asarray(got[-1], dtype=_I64).reshape(-1, 2) + 128) >> 8
+        positions = ((positions - shift).astype(np.float64) + np.stack((ox, oy), axis=1)) + pred
+    else:
+        positions, scores = _positions_scores(raw, nbhd, method, refine)       # (one fit over every pass and block)
     if r is not None:
         positions2, scores2 = _second_arrays(raw2)
     out, at = [], 0
@@ -542,6 +728,8 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
             res += (np.asarray(flags[at:at + len(g)], dtype=bool),)
         if r is not None:
             res += (positions2[at:at + len(g)], scores2[at:at + len(g)])
+        if deform:
+            res += (pred[at:at + len(g)],)
         out.append(res)
         at += len(g)
     return out

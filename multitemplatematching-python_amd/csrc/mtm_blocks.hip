@@ -27,6 +27,11 @@
 // planes of one sub-range of whole blocks, blocks_second_kernel reduces each plane to the best key outside the exclusion
 // window around the first peak (mtm_blocks_second.h, the single source of host and device), and
 // blocks_second_record_kernel decodes those keys behind blocks_record_kernel; the records come back behind the same wait.
+// mtm_match_blocks_passes_deformed and mtm_deform_image add window deformation: a pass p >= 1 warps the
+// original image by the field of the records that steer it (deform_disp_kernel, deform_image_kernel: mtm_k_deform.hip.h;
+// the rule: mtm_blocks_deform.h, the single source of host and device) into a buffer of its own, searches the warped image
+// over the host's units, and blocks_deform_record_kernel behind blocks_record_kernel adds the field at every block's centre
+// to its record.
 // One of each: the tile body of the four score kernels (blocks_tile; the kernels supply the sink), the key's decoder
 // (mtm_quality_key.h: decode_block_keys on the host, blocks_record_kernel and blocks_nbhd_kernel on the device), the
 // record that steers (blocks_steer_record_inl).  Every entry point is a composition of the same host steps:
@@ -35,11 +40,13 @@
 #include <climits>
 #include <type_traits>
 
+#include "mtm_blocks_deform.h"
 #include "mtm_blocks_predict.h"
 #include "mtm_blocks_second.h"
 #include "mtm_blocks_validate.h"
 #include "mtm_ctx.h"
 #include "mtm_device_util.hip.h"
+#include "mtm_k_deform.hip.h"
 #include "mtm_k_nbhd.hip.h"
 #include "mtm_k_window.hip.h"
 #include "mtm_templ_stats.h"
@@ -311,6 +318,24 @@ __global__ __launch_bounds__(256) void blocks_record_kernel(const TrackUnit* __r
     recs[k] = quality_key_record(keys[k], mode_min, k, U.y0, U.x0, U.ow, blocks[k].w, blocks[k].h);
 }
 
+// One lane per block k < n of a DEFORMED pass, behind the pass's blocks_record_kernel: the field of the coarse grid's
+// displacements `disp` (deform_disp_kernel's pairs) at the block's doubled centre (deform_field_at_inl) goes into
+// pred[2 k], pred[2 k + 1] in Q8, and its rounded integer part is added to the record's position - found in the warped
+// image - so that recs[k] carries the block's displacement in the original image.  The position is not clamped.
+__global__ __launch_bounds__(256) void blocks_deform_record_kernel(const mtm_block* __restrict__ blocks, int n, BlockGrid coarse,
+                                                                   const int32_t* __restrict__ disp, mtm_hit* __restrict__ recs,
+                                                                   int32_t* __restrict__ pred) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const mtm_block B = blocks[k];
+    long long fx, fy;
+    deform_field_at_inl(coarse, disp, 2ll * B.x + B.w - 1, 2ll * B.y + B.h - 1, &fx, &fy);
+    pred[2 * (size_t)k] = (int32_t)fx;
+    pred[2 * (size_t)k + 1] = (int32_t)fy;
+    recs[k].x += (int)deform_round_inl(fx);
+    recs[k].y += (int)deform_round_inl(fy);
+}
+
 // One lane per block k < nx ny of a pass's grid, after the pass's blocks_record_kernel: the median test of the block's
 // displacement against those of its 3 x 3 grid neighbourhood (blocks_steer_record_inl, mtm_blocks_validate.h: raw records
 // only, so no lane waits for another) - valid[k] = 1 / 0, and steer[k] = the record that steers the next pass: recs[k],
@@ -435,6 +460,11 @@ struct BlockStage {
     bool nbhd = false, recs = false, validate = false;
     const long long* poff = nullptr;
     size_t plane_floats = 0;
+    // a deformed call: the weight tables of its deformed passes (dtab_words words), the warped image's bytes, the largest
+    // steering grid's blocks and a row of Q8 fields at the blocks' centres
+    const uint32_t* dtab = nullptr;
+    size_t dtab_words = 0, warp_bytes = 0, disp_blocks = 0;
+    bool deform = false;
 };
 BlockStage plan_stage(const mtm_block* blocks, const BlockPlan& P) {
     return BlockStage{blocks, P.toff.data(), P.units.data(), P.tiles.data(), P.units.size(), P.tiles.size(), P.max_bytes};
@@ -450,14 +480,15 @@ int stage_block_call(mtm_ctx* c, const BlockStage& S, Before&& before) {
         {c->blk_blocks, S.blocks, sizeof(mtm_block) * n},   {c->blk_toff, S.toff, sizeof(long long) * n},
         {c->blk_units, S.units, sizeof(TrackUnit) * n},     {c->blk_tiles, S.tiles, sizeof(TrackTile) * S.n_tiles},
         {c->blk_clip, S.clip, sizeof(int32_t) * 2 * n},     {c->blk_offs, S.offsets, sizeof(int32_t) * 2 * n},
-        {c->blk_poff, S.poff, sizeof(long long) * n}};
+        {c->blk_poff, S.poff, sizeof(long long) * n},       {c->blk_dtab, S.dtab, sizeof(uint32_t) * S.dtab_words}};
     const struct { DevBuf& buf; size_t bytes; } sized[] = {
         {c->blk_tpx, S.max_bytes},                          {c->blk_td, sizeof(TemplDev) * n},
         {c->blk_acc, sizeof(double) * S.cells},             {c->blk_keys, sizeof(unsigned long long) * n_keys},
         {c->blk_recs, S.recs ? sizeof(mtm_hit) * n : 0},    {c->blk_nbhd, S.nbhd ? sizeof(float) * 9 * n_keys : 0},
         {c->blk_valid, S.validate ? n : 0},                 {c->blk_steer, S.validate ? sizeof(mtm_hit) * n : 0},
         {c->blk_plane, sizeof(float) * S.plane_floats},     {c->blk_keys2, S.poff ? sizeof(unsigned long long) * n : 0},
-        {c->blk_recs2, S.poff ? sizeof(mtm_hit) * n : 0}};
+        {c->blk_recs2, S.poff ? sizeof(mtm_hit) * n : 0},   {c->blk_warp, S.warp_bytes},
+        {c->blk_disp, sizeof(int32_t) * 2 * S.disp_blocks}, {c->blk_pred, S.deform ? sizeof(int32_t) * 2 * n : 0}};
     HIPC(hipSetDevice(c->device));
     c->timing = mtm_timing{};
     c->maps_valid = false;
@@ -471,6 +502,7 @@ int stage_block_call(mtm_ctx* c, const BlockStage& S, Before&& before) {
         if (u.src) HIPC(hipMemcpyAsync(u.buf.p, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
     if (S.cells) HIPC(hipMemsetAsync(c->blk_acc.p, 0, sizeof(double) * S.cells, c->stream));
     else HIPC(hipMemsetAsync(c->blk_keys.p, 0, sizeof(unsigned long long) * n_keys, c->stream));
+    if (S.deform) HIPC(hipMemsetAsync(c->blk_pred.p, 0, sizeof(int32_t) * 2 * n, c->stream));    // (pass 0 predicts nothing)
     return MTM_OK;
 }
 
@@ -599,13 +631,16 @@ void plan_second_pass(const BlockPlan& P, const mtm_block* blocks, int margin, i
 // reader, and the host waits for none of them.  The pair is the stack's current image: the reference its rows
 // r_slot * rows .., the searched image its rows i_slot * rows ...  X != nullptr (a second-peak pass over the fixed table):
 // the chunk's score launch runs sub-range by sub-range with the scored-plane sink, blocks_second_kernel behind each.
+// W != nullptr (a deformed pass): the searched image is *W with its low-byte plane W_lo - the warped image in a buffer
+// of its own - instead of the stack's slot i_slot.
 int blocks_pair(mtm_ctx* c, const BlockPlan& P, const BlockTables& B, int rows, int chans, int dtype, int method, int r_slot,
-                int i_slot, bool gather, const BlockSink& S, const BlockSecondPass* X = nullptr) {
+                int i_slot, bool gather, const BlockSink& S, const BlockSecondPass* X = nullptr, const ImageDev* W = nullptr,
+                const uint8_t* W_lo = nullptr) {
     const ImageDev st = image_dev(c);
     const uint8_t* st_lo = c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane;        // uint16: [high ^ 0x80][low ^ 0x80]
-    const ImageDev ref = stack_view(st, r_slot * rows, rows), img = stack_view(st, i_slot * rows, rows);
+    const ImageDev ref = stack_view(st, r_slot * rows, rows), img = W ? *W : stack_view(st, i_slot * rows, rows);
     const uint8_t* ref_lo = st_lo + (size_t)r_slot * rows * st.u8_pitch;
-    const uint8_t* img_lo = st_lo + (size_t)i_slot * rows * st.u8_pitch;
+    const uint8_t* img_lo = W ? W_lo : st_lo + (size_t)i_slot * rows * st.u8_pitch;
     const int mode_min = method_mode_min(method) ? 1 : 0;
     uint8_t* tpx = c->blk_tpx.as<uint8_t>();
     const long long* toff = B.toff;
@@ -674,6 +709,73 @@ void decode_block_keys(const BlockPlan& P, const mtm_block* blocks, const unsign
     }
 }
 
+// The weight tables of the warp by the field of grid g over a rows x cols image, appended to t: deform_pack_inl of
+// deform_axis_inl per column (padded with the last column's word to a multiple of kDeformPx) and per row (padded
+// likewise, so that the next tables start 32-byte aligned).  Returns the column table's first word.
+size_t deform_tables(const BlockGrid& g, int rows, int cols, std::vector<uint32_t>& t) {
+    const size_t at = t.size();
+    auto axis = [&](int n, int s, int wc, int len) {
+        uint32_t w = 0;
+        for (int x = 0; x < len; ++x) {
+            int i, a8;
+            deform_axis_inl(n, s, wc, 2ll * x, &i, &a8);
+            t.push_back(w = deform_pack_inl(i, a8));
+        }
+        while (t.size() % kDeformPx) t.push_back(w);
+    };
+    axis(g.nx, g.sx, g.bw, cols);
+    axis(g.ny, g.sy, g.bh, rows);
+    return at;
+}
+size_t deform_table_rows_at(int cols) { return (size_t)(cols + kDeformPx - 1) / kDeformPx * kDeformPx; }
+
+// The warped image of a call: byte planes of `pitch` bytes per row in blk_warp, `rows` rows each.
+size_t warp_bytes(int rows, int pitch, int chans, int dtype) { return (size_t)rows * pitch * (dtype == MTM_U16 ? 2 : chans); }
+ImageDev warp_view(const mtm_ctx* c, int rows, int cols, int chans) {
+    ImageDev v{};
+    v.u8 = c->blk_warp.as<uint8_t>();
+    v.rows = rows;
+    v.cols = cols;
+    v.chans = chans;
+    v.u8_pitch = c->u8_pitch;
+    v.u8_plane = (long long)c->u8_pitch * rows;
+    return v;
+}
+
+// The warp launch: `src` (its low-byte plane src_lo) warped into the call's blk_warp by the field of grid g with the
+// displacements in blk_disp and the tables at word `tab` of blk_dtab.
+int launch_deform(mtm_ctx* c, const ImageDev& src, const uint8_t* src_lo, int chans, int dtype, const BlockGrid& g, size_t tab) {
+    const ImageDev dst = warp_view(c, src.rows, src.cols, chans);
+    DeformArgs a{};
+    a.src = src.u8;
+    a.src_lo = src_lo;
+    a.src_plane = src.u8_plane;
+    a.src_pitch = src.u8_pitch;
+    a.dst = c->blk_warp.as<uint8_t>();
+    a.dst_lo = a.dst + dst.u8_plane;
+    a.dst_plane = dst.u8_plane;
+    a.dst_pitch = dst.u8_pitch;
+    a.rows = src.rows;
+    a.cols = src.cols;
+    a.disp = c->blk_disp.as<int32_t>();
+    a.nx = g.nx;
+    a.ny = g.ny;
+    a.colw = c->blk_dtab.as<uint32_t>() + tab;
+    a.roww = a.colw + deform_table_rows_at(src.cols);
+    const dim3 grd((unsigned)((src.cols + kDeformLanesX * kDeformPx - 1) / (kDeformLanesX * kDeformPx)),
+                   (unsigned)((src.rows + 256 / kDeformLanesX - 1) / (256 / kDeformLanesX)));
+    return blocks_dispatch(dtype, chans, [&](auto ch, auto u16) -> int {
+        hipLaunchKernelGGL((deform_image_kernel<decltype(ch)::value, decltype(u16)::value>), grd, dim3(256), 0, c->stream, a);
+        HIPC(hipGetLastError());
+        return MTM_OK;
+    });
+}
+
+// What a deformed call adds (mtm_match_blocks_passes_deformed): where the Q8 field at every block's centre goes, pass-major.
+struct BlockDeform {
+    int32_t* predicted;
+};
+
 // The median test a validated call runs behind every pass: its threshold, e4 = 4 epsilon (computed once, exact), and where
 // the flags of every record go, pass-major.
 struct BlockValidate {
@@ -692,12 +794,19 @@ struct BlockValidate {
 // X2 != nullptr (mtm_match_blocks_second, mtm_match_blocks_passes_second): every pass scores into planes and reduces them to
 // second keys (blocks_pair, BlockSecondPass), blocks_second_record_kernel behind the pass's blocks_record_kernel turns them
 // into records, which come back with the others and steer nothing.  X2 == nullptr: the chain as it is without.
+// D != nullptr (mtm_match_blocks_passes_deformed; never with offsets or X2): a pass p >= 1 does not move its boxes - the
+// records that steer it become compact displacements (deform_disp_kernel), the ORIGINAL image is warped by their field
+// into blk_warp (deform_image_kernel), the pass searches the warped image over the host's units of zero offsets, and
+// blocks_deform_record_kernel behind blocks_record_kernel adds the field at every block's centre to its record, which is
+// what validation tests and what steers the next pass; the fields come back with the records.  D == nullptr launches and
+// copies exactly what the chain did before deformation existed.
 struct BlockSecondOut {
     int exclusion;
     mtm_hit* second;
 };
 int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPassPlan>& Q, const int32_t* offsets, int method,
-                       mtm_hit* out, float* nbhd, const BlockValidate* V = nullptr, const BlockSecondOut* X2 = nullptr) {
+                       mtm_hit* out, float* nbhd, const BlockValidate* V = nullptr, const BlockSecondOut* X2 = nullptr,
+                       const BlockDeform* D = nullptr) {
     const int rows = I.rows, cols = I.cols, chans = I.chans, dtype = I.dtype;
     // the tables of every pass, concatenated: one upload each
     std::vector<mtm_block> blocks;
@@ -730,6 +839,19 @@ int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
         }
         S.poff = poff.data();
     }
+    // deformation: the weight tables of every pass p >= 1 (those of pass p - 1's grid), one upload
+    std::vector<uint32_t> dtab;
+    std::vector<size_t> dtab_at(Q.size(), 0);
+    if (D) {
+        for (size_t p = 1; p < Q.size(); ++p) {
+            dtab_at[p] = deform_tables(Q[p - 1].grid, rows, cols, dtab);
+            S.disp_blocks = std::max(S.disp_blocks, Q[p - 1].blocks.size());
+        }
+        S.deform = true;
+        S.dtab = dtab.empty() ? nullptr : dtab.data();
+        S.dtab_words = dtab.size();
+        if (Q.size() > 1) S.warp_bytes = warp_bytes(rows, (int)round_up((size_t)cols + kPadCols, 64), chans, dtype);
+    }
     MTMC(stage_block_call(c, S, [&] { return upload_block_pair(c, I); }));
 
     const int mode_min = method_mode_min(method) ? 1 : 0;
@@ -743,7 +865,19 @@ int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
         mtm_hit* recs = c->blk_recs.as<mtm_hit>() + b0;
         // what steers this pass: the previous pass's records, validated or raw
         const mtm_hit* prev = V ? c->blk_steer.as<mtm_hit>() + b0 : recs;
-        if (p > 0 || offsets) {
+        const bool warped = D && p > 0;
+        ImageDev wimg{};
+        if (warped) {
+            const BlockGrid& g = Q[p - 1].grid;
+            hipLaunchKernelGGL(deform_disp_kernel, dim3((unsigned)((Q[p - 1].blocks.size() + 255) / 256)), dim3(256), 0, c->stream,
+                               prev - Q[p - 1].blocks.size(), g, c->blk_disp.as<int32_t>());
+            HIPC(hipGetLastError());
+            const ImageDev st = image_dev(c);
+            MTMC(launch_deform(c, stack_view(st, rows, rows),
+                               c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane + (size_t)rows * st.u8_pitch, chans, dtype, g,
+                               dtab_at[p]));
+            wimg = warp_view(c, rows, cols, chans);
+        } else if (p > 0 || offsets) {
             hipLaunchKernelGGL(blocks_unit_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.blocks, np,
                                p > 0 ? nullptr : c->blk_offs.as<int32_t>(), p > 0 ? prev - Q[p - 1].blocks.size() : nullptr,
                                p > 0 ? Q[p - 1].grid : BlockGrid{}, q.margin, rows, cols, B.units);
@@ -754,10 +888,16 @@ int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
             X[p].keys2 = c->blk_keys2.as<unsigned long long>() + b0;
         }
         MTMC(blocks_pair(c, q.plan, B, rows, chans, dtype, method, 0, 1, true,
-                         BlockSink{keys, nbhd ? c->blk_nbhd.as<float>() + 9 * b0 : nullptr, 0, 0}, X2 ? &X[p] : nullptr));
+                         BlockSink{keys, nbhd ? c->blk_nbhd.as<float>() + 9 * b0 : nullptr, 0, 0}, X2 ? &X[p] : nullptr,
+                         warped ? &wimg : nullptr, warped ? wimg.u8 + wimg.u8_plane : nullptr));
         hipLaunchKernelGGL(blocks_record_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.units, keys, B.blocks, np, mode_min,
                            recs);
         HIPC(hipGetLastError());
+        if (warped) {
+            hipLaunchKernelGGL(blocks_deform_record_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.blocks, np,
+                               Q[p - 1].grid, c->blk_disp.as<int32_t>(), recs, c->blk_pred.as<int32_t>() + 2 * b0);
+            HIPC(hipGetLastError());
+        }
         if (X2) {
             hipLaunchKernelGGL(blocks_second_record_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.units, X[p].keys2,
                                B.blocks, np, mode_min, c->blk_recs2.as<mtm_hit>() + b0);
@@ -776,7 +916,8 @@ int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
     // the records (and neighbourhoods, and flags) come back behind the call's single wait
     return finish_block_call(c, {{out, c->blk_recs.p, sizeof(mtm_hit) * n}, {nbhd, c->blk_nbhd.p, sizeof(float) * 9 * n},
                                  {V ? V->valid : nullptr, c->blk_valid.p, n},
-                                 {X2 ? X2->second : nullptr, c->blk_recs2.p, sizeof(mtm_hit) * n}}, n);
+                                 {X2 ? X2->second : nullptr, c->blk_recs2.p, sizeof(mtm_hit) * n},
+                                 {D ? D->predicted : nullptr, c->blk_pred.p, sizeof(int32_t) * 2 * n}}, n);
 }
 
 // threshold and epsilon of the median test: finite and >= 0, else MTM_E_INVALID naming the argument.
@@ -863,6 +1004,122 @@ int mtm_debug_validate_blocks(mtm_ctx* c, const mtm_hit* recs, int nx, int ny, i
     HIPC(hipMemcpyAsync(valid, c->blk_valid.p, n, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipMemcpyAsync(steer, c->blk_steer.p, sizeof(mtm_hit) * n, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
+    return MTM_OK;
+}
+
+int mtm_match_blocks_passes_deformed(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                                     int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                                     const mtm_block_pass* passes, int n_passes, int method, double threshold, double epsilon,
+                                     mtm_hit* out, float* nbhd, uint8_t* valid, int32_t* predicted) {
+    const char* who = "mtm_match_blocks_passes_deformed";
+    if (valid) MTMC(check_validate_args(who, threshold, epsilon));      // (ahead of everything else, as the validated call)
+    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
+    MTMC(check_block_pair(c, who, n_passes >= 1 && passes && out && predicted, method, I));
+    // every pass moves a record by less than the image's larger side past the field that steered it
+    if ((long long)n_passes * std::max(rows, cols) > kDeformMaxDisp) {
+        set_error(std::string(who) + ": " + std::to_string(n_passes) + " passes over images of this size could pass the "
+                  "largest displacement the field takes (2^22 pixels)");
+        return MTM_E_INVALID;
+    }
+    std::vector<BlockPassPlan> Q;
+    MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
+    const BlockValidate V{threshold, 4.0 * epsilon, valid};
+    const BlockDeform D{predicted};
+    return match_block_passes(c, I, Q, nullptr, method, out, nbhd, valid ? &V : nullptr, nullptr, &D);
+}
+
+int mtm_deform_image(mtm_ctx* c, const void* px, int64_t row_stride_bytes, int rows, int cols, int chans, int dtype, int bw, int bh,
+                     int sx, int sy, const int32_t* displacements, void* out, int64_t out_stride_bytes) {
+    const char* who = "mtm_deform_image";
+    if (!displacements || !out) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    MTMC(check_image_args(px, rows, cols, chans, dtype, row_stride_bytes, who));
+    MTMC(check_image_args(out, rows, cols, chans, dtype, out_stride_bytes, who));
+    if (!((dtype == MTM_U8 && (chans == 1 || chans == 3)) || (dtype == MTM_U16 && chans == 1)) || rows > kBatchMaxRows) {
+        set_error(std::string(who) + ": takes uint8 images with 1 or 3 channels and single-channel uint16 images of at most " +
+                  std::to_string(kBatchMaxRows) + " rows");
+        return MTM_E_INVALID;
+    }
+    const BlockGrid g = block_grid_of(mtm_block_pass{bw, bh, sx, sy, 0}, rows, cols);
+    if (g.nx < 1 || g.ny < 1 || (long long)g.nx * g.ny > INT_MAX / 2) {
+        set_error(std::string(who) + ": block and step must be >= 1 and a block must fit the image (fewer than 2^30 of them)");
+        return MTM_E_INVALID;
+    }
+    const size_t n = (size_t)g.nx * (size_t)g.ny;
+    for (size_t k = 0; k < 2 * n; ++k)
+        if (displacements[k] > kDeformMaxDisp || displacements[k] < -kDeformMaxDisp) {
+            set_error(std::string(who) + ": block " + std::to_string(k / 2) + ": displacement beyond 2^22 pixels");
+            return MTM_E_INVALID;
+        }
+    const size_t es = elem_size(dtype);
+    if (!c) {           // the rule itself, on the host
+        for (int y = 0; y < rows; ++y) {
+            uint8_t* orow = (uint8_t*)out + (size_t)y * (size_t)out_stride_bytes;
+            for (int x = 0; x < cols; ++x) {
+                long long fx, fy;
+                deform_field_at_inl(g, displacements, 2ll * x, 2ll * y, &fx, &fy);
+                int x0, x1, wx, y0, y1, wy;
+                deform_sample_inl(x, fx, cols, &x0, &x1, &wx);
+                deform_sample_inl(y, fy, rows, &y0, &y1, &wy);
+                const uint8_t* r0 = (const uint8_t*)px + (size_t)y0 * (size_t)row_stride_bytes;
+                const uint8_t* r1 = (const uint8_t*)px + (size_t)y1 * (size_t)row_stride_bytes;
+                for (int ch = 0; ch < chans; ++ch) {
+                    auto at = [&](const uint8_t* r, int xx) -> uint32_t {
+                        const size_t e = (size_t)xx * chans + ch;
+                        return es == 2 ? (uint32_t)((const uint16_t*)r)[e] : (uint32_t)r[e];
+                    };
+                    const uint32_t v = deform_blend_inl(at(r0, x0), at(r0, x1), at(r1, x0), at(r1, x1), wx, wy);
+                    const size_t e = (size_t)x * chans + ch;
+                    if (es == 2) ((uint16_t*)orow)[e] = (uint16_t)v;
+                    else orow[e] = (uint8_t)v;
+                }
+            }
+        }
+        return MTM_OK;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    HIPC(hipSetDevice(c->device));
+    std::vector<uint32_t> tab;
+    deform_tables(g, rows, cols, tab);
+    const int pitch = (int)round_up((size_t)cols + kPadCols, 64);
+    const size_t wbytes = warp_bytes(rows, pitch, chans, dtype);
+    MTMC(c->blk_disp.ensure(sizeof(int32_t) * 2 * n));
+    MTMC(c->blk_dtab.ensure(sizeof(uint32_t) * tab.size()));
+    MTMC(c->blk_warp.ensure(wbytes));
+    c->timing = mtm_timing{};
+    c->maps_valid = false;
+    c->last_hits.clear();
+    // ONE upload of the image; the warp reads its planes and writes planes of the same layout
+    MTMC(upload_image(c, c->slot[c->cur], px, row_stride_bytes, rows, cols, chans, dtype, c->stream, 1));
+    adopt_image(c, rows, cols, chans, dtype);
+    HIPC(hipMemcpyAsync(c->blk_disp.p, displacements, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_dtab.p, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice, c->stream));
+    const ImageDev src = image_dev(c);
+    HIPC(hipEventRecord(c->ev[0], c->stream));                  // (the call's time is the warp kernel's)
+    MTMC(launch_deform(c, src, c->slot[c->cur].u8b.as<uint8_t>() + src.u8_plane, chans, dtype, g, 0));
+    HIPC(hipEventRecord(c->ev[1], c->stream));
+    // the planes come back tightly packed; interleaved pixels are put together on the host
+    const int np = dtype == MTM_U16 ? 2 : chans;
+    const bool direct = np == 1;
+    std::vector<uint8_t> planes(direct ? 0 : (size_t)np * rows * cols);
+    for (int p = 0; p < np; ++p)
+        HIPC(hipMemcpy2DAsync(direct ? out : (void*)(planes.data() + (size_t)p * rows * cols),
+                              direct ? (size_t)out_stride_bytes : (size_t)cols, c->blk_warp.as<uint8_t>() + (size_t)p * pitch * rows,
+                              (size_t)pitch, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    HIPC(hipEventElapsedTime(&c->timing.total_ms, c->ev[0], c->ev[1]));
+    const size_t plane = (size_t)rows * cols;
+    for (int y = 0; !direct && y < rows; ++y) {
+        uint8_t* orow = (uint8_t*)out + (size_t)y * (size_t)out_stride_bytes;
+        const uint8_t* q = planes.data() + (size_t)y * cols;
+        for (int x = 0; x < cols; ++x) {
+            if (dtype == MTM_U16) ((uint16_t*)orow)[x] = (uint16_t)(((uint32_t)q[x] << 8) | ((uint32_t)q[plane + x] ^ 0x80u));
+            else
+                for (int ch = 0; ch < chans; ++ch) orow[(size_t)x * chans + ch] = q[(size_t)ch * plane + x];
+        }
+    }
     return MTM_OK;
 }
 

@@ -392,6 +392,11 @@ struct mtm_ctx {
     // sub-range's maps (block k's oh x ow plane at blk_poff[k] floats, written by blocks_score_plane_kernel and read by
     // blocks_second_kernel behind it), the second-peak key per block and its record, pass-major as blk_recs
     DevBuf blk_plane, blk_poff, blk_keys2, blk_recs2;
+    // mtm_match_blocks_passes_deformed / mtm_deform_image: the warped image's byte planes in the image
+    // layout (plane c at c * u8_pitch * rows; uint16: the high-byte plane, then the low-byte plane XOR 0x80), the coarse
+    // displacements of the pass that steers (8 B per block), the per-column and per-row weight tables of every deformed pass
+    // and the field at every block's centre (Q8, 8 B per block, pass-major as blk_recs)
+    DevBuf blk_warp, blk_disp, blk_dtab, blk_pred;
     // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
     // template set sub_gen) and the per-call point table and scores.
     uint64_t sub_gen = 0;

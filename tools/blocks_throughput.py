@@ -52,7 +52,18 @@ float32 score bits against the brute-force rule of tests/blocks_second_model.py 
 box, NaN exactly where the model has no second peak), ``first_peaks_unchanged`` (positions and score bits of the call
 without ``second``), the blocks without a second peak and the median peak ratio of every pass.
 
-Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F] [--passes [--validate]] [--second [r]]
+--passes --deform: the same two passes with window deformation between them - milliseconds per call of
+  deformed   - matchBlocksMultipass(..., deform=True)
+  undeformed - matchBlocksMultipass(...) of the same build
+  by_hand    - the loop of matchBlocks, displacement_field, deform and field_at the deformed call documents
+with ``equal_to_loop`` (deformed against by_hand, every pass: positions, score bits, predicted fields), their difference
+(``deform_cost_ms``), the warp kernel alone (``warp_kernel_ms``: device events around deformImage's launch) against a
+device-to-device copy of the image's bytes timed in the same run (``device_copy_ms``, ``warp_vs_copy``), and, on the
+workload's reference under a known shear and a known rotation (``warped_pair``), the mean last-pass score and the RMS error
+of the refined displacements against the known field over the blocks clear of the border, with and without ``deform``.
+
+Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F] [--passes [--validate | --deform]]
+       [--second [r]]
 """
 import argparse
 import json
@@ -406,6 +417,155 @@ def run_passes_validate(MTM, spec, reps, warmup):
     }
 
 
+def warped_pair(spec, kind, seed=0):
+    """The workload's reference and the same content under a known smooth motion, resampled bilinearly in float64:
+    (ref, img, field) with field(x, y) -> (dx, dy), where the block centred on (x, y) of the reference is found in the
+    image.  "shear": dx = g (y - H / 2); "rotation": a rotation about the image centre.  Either way the largest
+    displacement is 0.6 of the workload's margin."""
+    name, hw, chans, dtype, side, margin = spec
+    ref, _ = workload(spec, seed)
+    H, W = hw
+    cy, cx = (H - 1) / 2.0, (W - 1) / 2.0
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    if kind == "shear":
+        g = 0.6 * margin / (H / 2.0)
+        field = lambda x, y: (g * (y - cy), 0.0 * x)                    # noqa: E731
+        sx, sy = xx - g * (yy - cy), yy
+    else:
+        th = 0.6 * margin / np.hypot(cy, cx)
+        c, s = np.cos(th), np.sin(th)
+        field = lambda x, y: (c * (x - cx) - s * (y - cy) - (x - cx), s * (x - cx) + c * (y - cy) - (y - cy))   # noqa: E731
+        sx, sy = c * (xx - cx) + s * (yy - cy) + cx, -s * (xx - cx) + c * (yy - cy) + cy
+    sx, sy = np.clip(sx, 0, W - 1), np.clip(sy, 0, H - 1)
+    x0, y0 = np.minimum(np.floor(sx).astype(np.int64), W - 2), np.minimum(np.floor(sy).astype(np.int64), H - 2)
+    tx, ty = sx - x0, sy - y0
+    if ref.ndim == 3:
+        tx, ty = tx[:, :, None], ty[:, :, None]
+    v = ref.astype(np.float64)
+    img = (v[y0, x0] * (1 - tx) + v[y0, x0 + 1] * tx) * (1 - ty) + (v[y0 + 1, x0] * (1 - tx) + v[y0 + 1, x0 + 1] * tx) * ty
+    return ref, np.round(img).astype(ref.dtype), field
+
+
+def device_copy_ms(nbytes, reps):
+    """Milliseconds (device events, the median of `reps`) of one device-to-device copy of nbytes."""
+    import ctypes
+    with open("/proc/self/maps") as maps:       # (the runtime the library itself runs on, already in the process)
+        hip = ctypes.CDLL(next((ln.split()[-1] for ln in maps if "libamdhip64" in ln), "libamdhip64.so"))
+
+    def ok(rc):
+        if rc != 0:
+            raise RuntimeError("HIP call failed (%d)" % rc)
+    src, dst, a, b = (ctypes.c_void_p() for _ in range(4))
+    ok(hip.hipMalloc(ctypes.byref(src), ctypes.c_size_t(nbytes)))
+    ok(hip.hipMalloc(ctypes.byref(dst), ctypes.c_size_t(nbytes)))
+    ok(hip.hipMemset(src, 0, ctypes.c_size_t(nbytes)))
+    ok(hip.hipEventCreate(ctypes.byref(a)))
+    ok(hip.hipEventCreate(ctypes.byref(b)))
+    out, ms = [], ctypes.c_float(0.0)
+    for i in range(reps + 2):
+        ok(hip.hipEventRecord(a, None))
+        ok(hip.hipMemcpyAsync(dst, src, ctypes.c_size_t(nbytes), 3, None))      # 3: hipMemcpyDeviceToDevice
+        ok(hip.hipEventRecord(b, None))
+        ok(hip.hipEventSynchronize(b))
+        ok(hip.hipEventElapsedTime(ctypes.byref(ms), a, b))
+        if i >= 2:
+            out.append(ms.value)
+    for e in (a, b):
+        ok(hip.hipEventDestroy(e))
+    for p in (src, dst):
+        ok(hip.hipFree(p))
+    return statistics.median(out)
+
+
+def run_passes_deform(MTM, spec, reps, warmup):
+    """--passes --deform: the two passes with and without window deformation and the loop the deformed call documents,
+    interleaved; the warp kernel against a device-to-device copy of the image's bytes; what deformation buys on a
+    sheared and on a rotated pair."""
+    from MTM import _lib
+    from MTM import blocks as B
+    name, hw, chans, dtype, side, margin = spec
+    ref, img = workload(spec)
+    method = MTM.TM_CCOEFF_NORMED
+    passes = [(side, 2 * side, margin), (side, side, max(1, margin // 4))]
+
+    def by_hand(r=ref, i=img):
+        out, steer = [], None
+        for p, (block, step, m) in enumerate(passes):
+            b = B.grid(i.shape, block, step)
+            if p == 0:
+                searched, c = i, np.zeros((len(b), 2), np.int64)
+            else:
+                prev = passes[p - 1][:2]
+                d = steer - B.grid(i.shape, *prev)[:, :2]
+                searched = B.deform(i, B.displacement_field(i.shape, prev, d))
+                c = B.field_at(i.shape, prev, d, b)
+            pos_w, sc = MTM.matchBlocks(r, searched, b, m, method)
+            steer = pos_w + ((c + 128) >> 8)
+            out.append((b, steer, sc, c / 256.0))
+        return out
+
+    methods = {
+        "deformed": lambda: MTM.matchBlocksMultipass(ref, img, passes, method, deform=True),
+        "undeformed": lambda: MTM.matchBlocksMultipass(ref, img, passes, method),
+        "by_hand": by_hand,
+    }
+    results = {}
+    for k, fn in methods.items():
+        for _ in range(warmup):
+            results[k] = fn()
+    ms = {k: [] for k in methods}
+    for _ in range(reps):
+        for k, fn in methods.items():
+            t0 = time.perf_counter()
+            fn()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+
+    def same(x, y):
+        return all(bool((a[0] == b[0]).all() and (a[1] == b[1]).all() and a[2].tobytes() == b[2].tobytes() and
+                        (a[3] == b[3]).all()) for a, b in zip(x, y))
+
+    # the warp kernel alone (device events around its launch: the context's timing) against a copy of the same bytes
+    ctx = _lib.default_context()
+    coarse = passes[0][:2]
+    d = B.displacements(results["deformed"][0][0], results["deformed"][0][1])
+    warp = []
+    for i in range(reps + 2):
+        out = MTM.deformImage(img, coarse, d)
+        if i >= 2:
+            warp.append(ctx.timing()["total_ms"])
+    warp_equal = bool(np.array_equal(out, B.deform(img, B.displacement_field(img.shape, coarse, d))))
+    warp_ms, copy_ms = statistics.median(warp), device_copy_ms(img.nbytes, reps)
+
+    motion = {}
+    for kind in ("shear", "rotation"):
+        r, i, field = warped_pair(spec, kind)
+        row = {"equal_to_loop": same(MTM.matchBlocksMultipass(r, i, passes, method, deform=True), by_hand(r, i))}
+        for key, flag in (("rigid", False), ("deformed", True)):
+            b, pos, sc = MTM.matchBlocksMultipass(r, i, passes, method, refine=True, deform=flag)[-1][:3]
+            x, y, w, h = (b[:, j] for j in range(4))
+            inner = (x >= 2 * side) & (y >= 2 * side) & (x + 3 * side <= hw[1]) & (y + 3 * side <= hw[0])
+            fx, fy = field(x + (w - 1) / 2.0, y + (h - 1) / 2.0)
+            err = (pos - b[:, :2]) - np.stack((fx, fy), axis=1)
+            row[key] = {"mean_score": round(float(sc[inner].mean()), 4),
+                        "rms_error_px": round(float(np.sqrt((err[inner] ** 2).sum(axis=1).mean())), 4)}
+        row["blocks_counted"] = int(inner.sum())
+        motion[kind] = row
+    return {
+        "workload": name, "image": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype),
+        "passes": [[b, st, m] for b, st, m in passes], "pass_blocks": [int(len(r[0])) for r in results["deformed"]],
+        "ms": {k: round(v, 3) for k, v in med.items()},
+        "ms_min": {k: round(min(v), 3) for k, v in ms.items()},
+        "ms_max": {k: round(max(v), 3) for k, v in ms.items()},
+        "deform_cost_ms": round(med["deformed"] - med["undeformed"], 3),
+        "deformed_vs_by_hand": round(med["by_hand"] / med["deformed"], 2),
+        "equal_to_loop": same(results["deformed"], results["by_hand"]),
+        "warp_kernel_ms": round(warp_ms, 4), "device_copy_ms": round(copy_ms, 4), "image_bytes": int(img.nbytes),
+        "warp_vs_copy": round(warp_ms / copy_ms, 2), "warp_equal_to_numpy": warp_equal,
+        "motion": motion, "reps": reps,
+    }
+
+
 def run_second(MTM, spec, reps, warmup, radius, passes_form):
     """--second: the call with and without the second peak, interleaved; the second peaks against the brute-force model of
     tests/blocks_second_model.py over MTM.computeScoreMap of every block and its box."""
@@ -470,9 +630,12 @@ def main():
     ap.add_argument("--validate", action="store_true", help="with --passes: the median test between the passes")
     ap.add_argument("--second", type=int, nargs="?", const=2, default=None, metavar="r",
                     help="the second peak with exclusion radius r (default 2): the pair call, or with --passes the passes")
+    ap.add_argument("--deform", action="store_true", help="with --passes: window deformation between the passes")
     args = ap.parse_args()
     if args.validate and not args.passes:
         ap.error("--validate goes with --passes")
+    if args.deform and (not args.passes or args.validate or args.second is not None):
+        ap.error("--deform goes with --passes alone")
     if args.second is not None and (args.second < 0 or args.validate or args.stack):
         ap.error("--second takes a radius >= 0 and goes alone or with --passes")
     import build as mtm_build
@@ -483,6 +646,8 @@ def main():
             continue
         if args.second is not None:
             print(json.dumps(run_second(MTM, spec, args.reps, args.warmup, args.second, args.passes)), flush=True)
+        elif args.passes and args.deform:
+            print(json.dumps(run_passes_deform(MTM, spec, args.reps, args.warmup)), flush=True)
         elif args.passes and args.validate:
             print(json.dumps(run_passes_validate(MTM, spec, args.reps, args.warmup)), flush=True)
         elif args.passes:

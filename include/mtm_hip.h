@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes, mtm_match_blocks_passes_validated, mtm_debug_validate_blocks, mtm_match_blocks_second, mtm_match_blocks_passes_second, mtm_debug_second_peaks, mtm_deform_image, mtm_match_blocks_passes_deformed - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes, mtm_match_blocks_passes_validated, mtm_debug_validate_blocks, mtm_match_blocks_second, mtm_match_blocks_passes_second, mtm_debug_second_peaks, mtm_deform_image, mtm_match_blocks_passes_deformed, mtm_debug_maskf32_screen - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -395,6 +395,46 @@ typedef struct mtm_window_stats_route {
     int64_t*       info;
 } mtm_window_stats_route;
 int         mtm_debug_window_stats_route(mtm_ctx* ctx, const mtm_window_stats_route* args);
+/* Test support (added under ABI 9; as above).  The screen of a masked float32 size class (two raw bf16 correlations, a
+ * rigorous interval of every output's quality, placeholders below the threshold, exact re-scoring of the rest), stage by
+ * stage through the functions a search call runs, with what each stage leaves behind.  After mtm_set_image and
+ * mtm_set_templates (the method is the template set's) on a context whose templates form ONE size class the screen takes:
+ * single channel, float32 image and templates with masks, w <= 256, TM_SQDIFF or TM_CCORR_NORMED, MTM_OPT_F32_MFMA 1 or 3 -
+ * anything else is refused with MTM_E_INVALID.
+ * pieces: 1 or 3 piece products in the raw launches; mode: MTM_PEAKS_LOCAL (listing against thr, the score threshold as a
+ * search call takes it) or MTM_PEAKS_GLOBAL (against the templates' best lower bounds); rescore: run the exact re-scoring
+ * of the list (not when the list overflowed: a search call repeats the screen then); list_cap: 0 = the capacity a search
+ * call gives the list, else a smaller one.  set_cap != 0: nothing runs - list_cap becomes the capacity the NEXT search
+ * calls of this context give the list (0: their own again).
+ * n_templ, oh, ow: what the caller sized its planes by (checked).  Results, each optional, planes tightly packed
+ * [n_templ][oh][ow]: c1, c2 - the float32 sums the raw launches wrote; lb, ub - the bounds of the quality (the score;
+ * minima: minus the score) the listing pass computes; map_listed, map_rescored - the score maps after the listing pass and
+ * after re-scoring (outputs no stage wrote hold what the buffer held); mu_i, mu_j - the launches' tile constants,
+ * [nyb][nseg], `tiles` floats of room each; records (capacity >= min(capacity of the list, n_templ * oh * ow) + 8) - the
+ * records written, min(count, capacity of the list) of them, then the 8 records behind the list's capacity, which were
+ * filled with the byte 0xC5 before the listing pass; best - n_templ ordered-float keys (MTM_PEAKS_GLOBAL).
+ * info[12] = {n_templ, h, w, oh, ow, nyb, nseg, template groups per work item, a search call's list capacity, the capacity
+ * used, the count as the device counted it, 1 if the list was re-scored}. */
+typedef struct mtm_maskf32_screen {
+    int32_t   pieces, mode, rescore, set_cap;
+    float     thr;
+    int32_t   reserved;
+    int64_t   list_cap;
+    int64_t   n_templ, oh, ow, tiles;
+    float*    c1;
+    float*    c2;
+    double*   lb;
+    double*   ub;
+    float*    map_listed;
+    float*    map_rescored;
+    float*    mu_i;
+    float*    mu_j;
+    mtm_hit*  records;
+    int64_t   capacity;
+    uint32_t* best;
+    int64_t*  info;
+} mtm_maskf32_screen;
+int         mtm_debug_maskf32_screen(mtm_ctx* ctx, const mtm_maskf32_screen* args);
 /* Page-locked host memory for pixel buffers (optional).  The reference's caller hands over whatever numpy holds
  * (MTM/__init__.py:247 `image`) - pageable memory, which the runtime stages through its own pinned buffers while the
  * upload call blocks.  An image kept in memory from mtm_host_alloc crosses PCIe as a plain DMA transfer behind the call

@@ -128,6 +128,22 @@ class MtmWindowStatsRoute(ctypes.Structure):
                 ("info", ctypes.c_void_p)]
 
 
+# mtm_debug_maskf32_screen: the argument block (mtm_maskf32_screen) and the names of info[]
+MASKF32_SCREEN_INFO_FIELDS = ("n_templ", "h", "w", "oh", "ow", "nyb", "nseg", "mb", "cap_production", "cap", "count", "rescored")
+MASKF32_CANARY = 8          # records behind the list's capacity, filled with the byte 0xC5 before the listing pass
+
+
+class MtmMaskF32Screen(ctypes.Structure):
+    _fields_ = [("pieces", ctypes.c_int32), ("mode", ctypes.c_int32), ("rescore", ctypes.c_int32), ("set_cap", ctypes.c_int32),
+                ("thr", ctypes.c_float), ("reserved", ctypes.c_int32),
+                ("list_cap", ctypes.c_int64),
+                ("n_templ", ctypes.c_int64), ("oh", ctypes.c_int64), ("ow", ctypes.c_int64), ("tiles", ctypes.c_int64),
+                ("c1", ctypes.c_void_p), ("c2", ctypes.c_void_p), ("lb", ctypes.c_void_p), ("ub", ctypes.c_void_p),
+                ("map_listed", ctypes.c_void_p), ("map_rescored", ctypes.c_void_p), ("mu_i", ctypes.c_void_p),
+                ("mu_j", ctypes.c_void_p), ("records", ctypes.c_void_p), ("capacity", ctypes.c_int64),
+                ("best", ctypes.c_void_p), ("info", ctypes.c_void_p)]
+
+
 # every symbol include/mtm_hip.h declares: (restype, argtypes)
 _P = ctypes.POINTER
 SYMBOLS = {
@@ -151,6 +167,7 @@ SYMBOLS = {
     "mtm_debug_peak_pass": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_debug_window_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_debug_window_stats_route": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "mtm_debug_maskf32_screen": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "mtm_set_image": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
     "mtm_set_image_downscaled": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -903,6 +920,52 @@ class Context(_RecordMemo):
         out["info"] = dict(zip(STATS_ROUTE_INFO_FIELDS, (int(v) for v in info)))
         assert (out["info"]["st_pitch"], out["info"]["blk_pitch"]) == (st_pitch, blk_pitch)
         return out
+
+    def debug_maskf32_screen(self, n_templ, out_shape, pieces, mode, thr=0.0, rescore=True, list_cap=0):
+        """Test support (mtm_debug_maskf32_screen): the screen of the context's ONE masked float32 size class (after set_image
+        and set_templates), stage by stage: `pieces` piece products in the two raw launches, the listing pass of `mode`
+        (PEAKS_LOCAL against the score threshold `thr`, PEAKS_GLOBAL against the templates' best lower bounds), the exact
+        re-scoring; list_cap: 0 = a search call's capacity of the list, else a smaller one.
+        -> dict: c1, c2 (float32), lb, ub (float64), map_listed, map_rescored (float32): (n_templ, oh, ow); mu_i, mu_j
+        (nyb, nseg) float32; records (HIT_DTYPE: what was written), canary (the bytes of the 8 records behind the list's
+        capacity, set to 0xC5 before the listing pass), best (uint32 keys, PEAKS_GLOBAL) and info
+        (MASKF32_SCREEN_INFO_FIELDS)."""
+        oh, ow = int(out_shape[0]), int(out_shape[1])
+        n = int(n_templ)
+        a = MtmMaskF32Screen()
+        a.pieces, a.mode, a.rescore, a.set_cap = int(pieces), int(mode), 1 if rescore else 0, 0
+        a.thr, a.list_cap = float(thr), int(list_cap)
+        a.n_templ, a.oh, a.ow = n, oh, ow
+        nyb, nseg = (oh + 3) // 4, (ow + 127) // 128
+        a.tiles = nyb * nseg
+        out = {}
+        for name, dt in (("c1", np.float32), ("c2", np.float32), ("lb", np.float64), ("ub", np.float64),
+                         ("map_listed", np.float32), ("map_rescored", np.float32)):
+            out[name] = np.zeros((n, oh, ow), dtype=dt)
+            setattr(a, name, out[name].ctypes.data)
+        for name in ("mu_i", "mu_j"):
+            out[name] = np.zeros((nyb, nseg), dtype=np.float32)
+            setattr(a, name, out[name].ctypes.data)
+        rec = np.zeros(n * oh * ow + MASKF32_CANARY, dtype=HIT_DTYPE)
+        a.records, a.capacity = rec.ctypes.data, len(rec)
+        out["best"] = np.zeros(n, dtype=np.uint32)
+        a.best = out["best"].ctypes.data
+        info = np.zeros(len(MASKF32_SCREEN_INFO_FIELDS), dtype=np.int64)
+        a.info = info.ctypes.data
+        check(self._lib.mtm_debug_maskf32_screen(self._h, ctypes.byref(a)), "mtm_debug_maskf32_screen")
+        out["info"] = dict(zip(MASKF32_SCREEN_INFO_FIELDS, (int(v) for v in info)))
+        assert (out["info"]["nyb"], out["info"]["nseg"]) == (nyb, nseg), out["info"]
+        n_rec = min(out["info"]["count"], out["info"]["cap"])
+        out["records"] = rec[:n_rec].copy()
+        out["canary"] = rec[n_rec:n_rec + MASKF32_CANARY].view(np.uint8).copy()
+        return out
+
+    def debug_maskf32_list_cap(self, list_cap):
+        """Test support: the capacity the NEXT search calls of this context give the masked float32 screen's list (0: their
+        own again) - what shows the ladder one piece product -> three -> the float64 kernel on a small map."""
+        a = MtmMaskF32Screen()
+        a.set_cap, a.list_cap = 1, int(list_cap)
+        check(self._lib.mtm_debug_maskf32_screen(self._h, ctypes.byref(a)), "mtm_debug_maskf32_screen")
 
     def set_image(self, image, downscale=1):
         """Upload the search image; `downscale` > 1 area-averages it by that integer factor on the

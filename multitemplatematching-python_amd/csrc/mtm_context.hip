@@ -387,7 +387,7 @@ void mtm_ctx_destroy(mtm_ctx* c) {
     for (auto& sl : c->slot)
         for (DevBuf* b : {&sl.raw, &sl.u8, &sl.u8b, &sl.f32}) b->release();
     for (DevBuf* b : {&c->tsrc, &c->usrc_dev, &c->tsums_dev, &c->tgather, &c->slab_raw, &c->seg_flags, &c->hits_t, &c->nms_buf, &c->nms_dbg, &c->peak_dbg, &c->stats_dbg, &c->td_u, &c->td_v,
-                      &c->mbf_maps, &c->f32_sq, &c->mbf_stats, &c->mbf_mu, &c->mbf_list, &c->mbf_best}) b->release();
+                      &c->mbf_maps, &c->f32_sq, &c->mbf_stats, &c->mbf_mu, &c->mbf_list, &c->mbf_best, &c->mbf_dbg}) b->release();
     for (DevBuf* b : {&c->td, &c->tlist, &c->weights, &c->packs, &c->apacks, &c->maps, &c->hs1, &c->hs2, &c->stats, &c->hits,
                       &c->counters, &c->sched, &c->cands, &c->mask_td, &c->chash, &c->raw16, &c->stats_hi, &c->tsum, &c->stats_rsq, &c->stats_blk, &c->sq_planes, &c->comm_send,
                       &c->comm_recv})
@@ -546,14 +546,15 @@ int mtm_debug_poison(mtm_ctx* c, int pattern_byte, int what) {
         // buffers a call writes before it reads them: window statistics (planes, reciprocals, block ranges, row sums),
         // raw partial maps, the score maps, the byte planes of I^2 - of the context and of every class lane -, the device
         // NMS's work buffer (cell counts and counters cleared, ranks, sorted records and status words written per call), the
-        // buffers of mtm_debug_peak_pass and mtm_debug_window_stats (laid out and written per call).  Buffers with
+        // buffers of mtm_debug_peak_pass and mtm_debug_window_stats (laid out and written per call), the masked float32
+        // screen's best[] keys (cleared per call) and mtm_debug_maskf32_screen's dump (written per call).  Buffers with
         // an invariant kept between calls (image padding, candidate header, hash tables, flags, packs) are left alone.
         auto fill = [&](mtm_ctx::DevBuf& d) -> int {
             if (d.p && d.cap) HIPC(hipMemsetAsync(d.p, (int)b, d.cap, c->stream));
             return MTM_OK;
         };
         for (mtm_ctx::DevBuf* d : {&c->stats, &c->stats_rsq, &c->stats_blk, &c->hs1, &c->hs2, &c->raw16, &c->slab_raw,
-                                   &c->stats_hi, &c->maps, &c->sq_planes, &c->mbf_maps, &c->f32_sq, &c->mbf_stats, &c->mbf_mu,
+                                   &c->stats_hi, &c->maps, &c->sq_planes, &c->mbf_maps, &c->f32_sq, &c->mbf_stats, &c->mbf_mu, &c->mbf_best, &c->mbf_dbg,
                                    &c->trk_units, &c->trk_keys, &c->trk_out, &c->trk_nbhd, &c->trk_tpx, &c->trk_toff, &c->trk_td,
                                    &c->trk_pass, &c->trk_lost, &c->trk_sets, &c->blk_tpx, &c->blk_toff, &c->blk_td, &c->blk_blocks, &c->blk_units,
                                    &c->blk_tiles, &c->blk_keys, &c->blk_nbhd, &c->blk_clip, &c->blk_acc, &c->blk_recs, &c->blk_offs, &c->blk_valid, &c->blk_steer, &c->blk_plane, &c->blk_poff, &c->blk_keys2, &c->blk_recs2, &c->blk_warp, &c->blk_disp, &c->blk_dtab, &c->blk_pred, &c->sub_pts, &c->sub_out, &c->nms_buf, &c->peak_dbg, &c->stats_dbg})

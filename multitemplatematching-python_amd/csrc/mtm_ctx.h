@@ -296,6 +296,8 @@ struct mtm_ctx {
     // J = I^2, the window sums of I and J, the launches' tile constants, the list of outputs to re-score exactly
     DevBuf td_u, td_v, mbf_maps, f32_sq, mbf_stats, mbf_mu, mbf_list, mbf_best;
     bool f32_sq_valid = false;                      // f32_sq holds the square of the current float32 plane
+    long long mbf_cap_debug = 0;                    // test support (mtm_debug_maskf32_screen): a list capacity below the production one; 0: none
+    DevBuf mbf_dbg;                                 // ... and that entry's dump of the bounds
     DevBuf tsrc, usrc_dev, tsums_dev, tgather;      // template source arena, unit views, source sums, gather scratch
     DevBuf td, tlist, weights, packs, apacks, maps, hs1, hs2, stats, hits, counters, sched, cands, mask_td, chash, raw16, stats_hi, tsum, stats_rsq, stats_blk;
 

@@ -635,13 +635,27 @@ static int launch_masked_sumsq(mtm_ctx* c, const SizeClass& sc, bool fused_stats
     return MTM_OK;
 }
 
-// Masked float32 class on the bf16 matrix cores (mtm_maskf32.hip.h): J = I^2 and the window sums of I and J, two raw
-// launches of ncc_bf16_kernel (I x U = T M^2, J x V = M^2) into scratch maps, the combine pass (placeholders + the list of
-// outputs that could pass the threshold), exact re-scoring of the list into the score maps.  *done = false: the list
-// overflowed (a threshold that passes nearly everything) - the caller runs the float64 kernel.
-static int launch_masked_bf16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, float* maps, bool* done) {
-    *done = false;
+// Masked float32 class on the bf16 matrix cores (mtm_maskf32.hip.h), in the stages launch_masked_bf16 and the test-support
+// entry mtm_debug_maskf32_screen both run: mbf_prepare (J = I^2, the window sums of I and J, the buffers and the raw
+// launches' geometry), mbf_raw (two raw launches of ncc_bf16_kernel - I x U = T M^2, J x V = M^2 - into scratch maps, with
+// `np` piece products), mbf_list (placeholders + the list of outputs that could pass; the count comes back to the host),
+// mbf_rescore (exact re-scoring of the list into the score maps).
+struct MaskBf16Plan {
+    int h, w, oh, ow, n_all, mb, st_pitch;
+    double* s1i;                // window sums (float64) of I, I^2, J, J^2
+    double* s2i;
+    double* s1j;
+    double* s2j;
+    Bf16Params p;               // the raw launches' geometry (img and mu_out per launch)
+    size_t n_tiles, lds;
+    const int* tl_k;
+    unsigned long long cap;     // records the list holds
+};
+
+static int mbf_prepare(mtm_ctx* c, const SizeClass& sc, MaskBf16Plan* out) {
+    MaskBf16Plan P{};
     const int h = sc.h, w = sc.w, oh = c->rows - h + 1, ow = c->cols - w + 1, n_all = (int)sc.members.size();
+    P.h = h, P.w = w, P.oh = oh, P.ow = ow, P.n_all = n_all;
     const ImageDev img = image_dev(c);
     const size_t plane_floats = (size_t)img.f32_plane;
     MTMC(c->f32_sq.ensure(sizeof(float) * plane_floats));
@@ -654,10 +668,11 @@ static int launch_masked_bf16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, flo
     const int st_pitch = (int)round_up((size_t)ow, 4);
     const size_t st_plane = (size_t)st_pitch * oh;
     MTMC(c->mbf_stats.ensure(sizeof(double) * 4 * st_plane));
-    double* s1i = c->mbf_stats.as<double>();
-    double* s2i = s1i + st_plane;
-    double* s1j = s2i + st_plane;
-    double* s2j = s1j + st_plane;
+    P.st_pitch = st_pitch;
+    P.s1i = c->mbf_stats.as<double>();
+    P.s2i = P.s1i + st_plane;
+    P.s1j = P.s2i + st_plane;
+    P.s2j = P.s1j + st_plane;
     {
         const int hs_pitch = (int)round_up((size_t)ow, 4);
         const size_t hs_plane = (size_t)hs_pitch * c->rows;
@@ -668,68 +683,82 @@ static int launch_masked_bf16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, flo
         for (int pl = 0; pl < 2; ++pl) {
             const float* src = pl == 0 ? img.f32 : c->f32_sq.as<float>();
             StatOut o{};                    // sums only: num_type 0, no sqrt plane
-            o.want_t = 1, o.t[0] = pl == 0 ? s1i : s1j, o.sum2 = pl == 0 ? s2i : s2j, o.st_pitch = st_pitch;
+            o.want_t = 1, o.t[0] = pl == 0 ? P.s1i : P.s1j, o.sum2 = pl == 0 ? P.s2i : P.s2j, o.st_pitch = st_pitch;
             MTMC(launch_stats_f64_lds(c->stream, src, img.f32_pitch, img.f32_plane, g, hs, o, 0, c->rows, 0, oh));
         }
     }
-    // the two raw launches
+    // the two raw launches' buffers and geometry
     MTMC(c->mbf_maps.ensure(sizeof(float) * 2 * std::max<size_t>(4, c->maps_floats)));
-    const int mb = n_all > 16 ? 2 : 1;
-    Bf16Params p = bf16_geometry(c, sc, 1, mb, sc.mbf_group_bytes, MTM_TM_CCORR);      // raw sums: acc + centre * S1
-    const size_t n_tiles = (size_t)p.nseg * p.nyb;
-    MTMC(c->mbf_mu.ensure(sizeof(float) * 2 * n_tiles));
-    const size_t lds = bf16_lds_bytes(p.chunk_h, p.lds_cols);
-    const int* tl_k = c->tlist.as<int>() + sc.tlist_off;
+    P.mb = n_all > 16 ? 2 : 1;
+    P.p = bf16_geometry(c, sc, 1, P.mb, sc.mbf_group_bytes, MTM_TM_CCORR);      // raw sums: acc + centre * S1
+    P.n_tiles = (size_t)P.p.nseg * P.p.nyb;
+    MTMC(c->mbf_mu.ensure(sizeof(float) * 2 * P.n_tiles));
+    P.lds = bf16_lds_bytes(P.p.chunk_h, P.p.lds_cols);
+    P.tl_k = c->tlist.as<int>() + sc.tlist_off;
+    P.cap = (unsigned long long)std::min<int64_t>(std::max<int64_t>(c->hit_cap, 1 << 18), kCandListMax);
+    if (c->mbf_cap_debug > 0) P.cap = std::min<unsigned long long>(P.cap, (unsigned long long)c->mbf_cap_debug);  // (test support)
+    MTMC(c->mbf_list.ensure(16 + sizeof(mtm_hit) * (size_t)P.cap));
+    *out = P;
+    return MTM_OK;
+}
+
+static int mbf_raw(mtm_ctx* c, const SizeClass& sc, const MaskBf16Plan& P, int np) {
+    const ImageDev img = image_dev(c);
+    Bf16Params p = P.p;
     StatPlanes st{};
-    st.pitch = st_pitch;
-    const unsigned long long cap = (unsigned long long)std::min<int64_t>(std::max<int64_t>(c->hit_cap, 1 << 18), kCandListMax);
-    MTMC(c->mbf_list.ensure(16 + sizeof(mtm_hit) * (size_t)cap));
-    MaskF32Params q{};
-    unsigned long long count = 0;
-    // Round 6: ONE piece product first (ncc_bf16_kernel<MB, 1>: bounds 2^-7 instead of 2^-15 of the norms' products - the
-    // combine pass states them with the eps of the launch that ran); a list that overflows repeats the screen with three
-    for (int np = R.bf16_np == 1 ? 1 : 3;; np = 3) {
+    st.pitch = P.st_pitch;
     for (int pl = 0; pl < 2; ++pl) {
         p.img = pl == 0 ? img.f32 : c->f32_sq.as<float>();
-        p.mu_out = c->mbf_mu.as<float>() + (size_t)pl * n_tiles;
-        st.t[0] = pl == 0 ? s1i : s1j;
-        st.sum2 = pl == 0 ? s2i : s2j;
+        p.mu_out = c->mbf_mu.as<float>() + (size_t)pl * P.n_tiles;
+        st.t[0] = pl == 0 ? P.s1i : P.s1j;
+        st.sum2 = pl == 0 ? P.s2i : P.s2j;
         st.sq = st.sum2;                                        // (not read by a raw-sum launch)
         const uint8_t* ap = c->apacks.as<uint8_t>() + (pl == 0 ? sc.mbf_off_u : sc.mbf_off_v);
         const TemplDev* tdp = (pl == 0 ? c->td_u : c->td_v).as<TemplDev>();
-        hipLaunchKernelGGL(bf16_kernel(mb, np), work_grid(p.n_work), dim3(256), lds, c->stream, p, tdp, tl_k, ap, st,
+        hipLaunchKernelGGL(bf16_kernel(P.mb, np), work_grid(p.n_work), dim3(256), P.lds, c->stream, p, tdp, P.tl_k, ap, st,
                            c->mbf_maps.as<float>());
     }
-    c->timing.f32_pieces = np;
-    // combine: placeholders into the score maps, the rest listed
-    HIPC(hipMemsetAsync(c->mbf_list.p, 0, 16, c->stream));
-    q = MaskF32Params{};
+    return MTM_OK;
+}
+
+// what the listing kernels (and the test-support dump of the bounds) read: the launches' maps and constants, the statistics,
+// the eps of the launch that ran (`np`)
+static MaskF32Params mbf_params(mtm_ctx* c, const MaskBf16Plan& P, int np, float thr, float* maps) {
+    MaskF32Params q{};
     q.m1 = q.m2 = c->mbf_maps.as<float>();
     q.td = c->td.as<TemplDev>();
     q.td_u = c->td_u.as<TemplDev>();
     q.td_v = c->td_v.as<TemplDev>();
-    q.tlist = tl_k;
-    q.s1i = s1i;
-    q.s2i = s2i;
-    q.s1j = s1j;
-    q.s2j = s2j;
-    q.st_pitch = st_pitch;
+    q.tlist = P.tl_k;
+    q.s1i = P.s1i;
+    q.s2i = P.s2i;
+    q.s1j = P.s1j;
+    q.s2j = P.s2j;
+    q.st_pitch = P.st_pitch;
     q.mu_i = c->mbf_mu.as<float>();
-    q.mu_j = c->mbf_mu.as<float>() + n_tiles;
-    q.nseg = p.nseg;
+    q.mu_j = c->mbf_mu.as<float>() + P.n_tiles;
+    q.nseg = P.p.nseg;
     q.method = c->method;
     q.mode_min = c->method == MTM_TM_SQDIFF ? 1 : 0;
-    q.thr = R.mbf_thr;
-    q.eps = bf16_rig_eps(1, h, p.nkb, np);
-    q.h = h;
-    q.w = w;
-    q.oh = oh;
-    q.ow = ow;
+    q.thr = thr;
+    q.eps = bf16_rig_eps(1, P.h, P.p.nkb, np);
+    q.h = P.h;
+    q.w = P.w;
+    q.oh = P.oh;
+    q.ow = P.ow;
     q.maps = maps;
     q.list = reinterpret_cast<mtm_hit*>(c->mbf_list.as<uint8_t>() + 16);
     q.counter = c->mbf_list.as<unsigned long long>();
-    q.cap = cap;
-    if (R.mbf_global) {
+    q.cap = P.cap;
+    return q;
+}
+
+// combine: placeholders into the score maps, the rest listed; *count: how many the device counted (one small read-back: this
+// path is milliseconds long, and an overflowing list changes the route)
+static int mbf_list(mtm_ctx* c, const MaskBf16Plan& P, const MaskF32Params& q, bool global, unsigned long long* count) {
+    const int oh = P.oh, ow = P.ow, n_all = P.n_all;
+    HIPC(hipMemsetAsync(c->mbf_list.p, 0, 16, c->stream));
+    if (global) {
         // N_object == 1: the templates' best lower bounds first (ordered-float keys behind the list's header + records), then
         // everything that reaches them
         MTMC(c->mbf_best.ensure(sizeof(unsigned int) * c->templs.size()));
@@ -741,34 +770,56 @@ static int launch_masked_bf16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, flo
         hipLaunchKernelGGL(maskf32_combine_kernel, dim3((ow + 255) / 256, oh), dim3(256), 0, c->stream, q, n_all);
     }
     HIPC(hipGetLastError());
-    // how many?  (one small read-back: this path is milliseconds long, and an overflowing list changes the route)
-    HIPC(hipMemcpyAsync(&count, c->mbf_list.p, sizeof(count), hipMemcpyDeviceToHost, c->stream));
+    *count = 0;
+    HIPC(hipMemcpyAsync(count, c->mbf_list.p, sizeof(*count), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
-    if (count <= cap) {
-        if (np == 1) c->np1_backoff_len = 16;
-        break;
+    return MTM_OK;
+}
+
+static int mbf_rescore(mtm_ctx* c, const SizeClass& sc, const MaskF32Params& q, unsigned long long count) {
+    if (count == 0) return MTM_OK;
+    RefineParams r{};
+    r.img = image_dev(c);
+    r.td = c->td.as<TemplDev>();
+    r.weights = c->weights.as<double>();
+    r.method = c->method;
+    r.cls = c->td_host[(size_t)sc.members[0]].cls;
+    r.ring = 0;
+    r.list = q.list;
+    r.count = q.counter;
+    r.cap = q.cap;
+    r.maps = q.maps;
+    const unsigned rgrid = (unsigned)std::min<unsigned long long>(count, 16384ull);
+    hipLaunchKernelGGL(refine_rescore_masked_kernel, dim3(rgrid), dim3(64), 0, c->stream, r);
+    HIPC(hipGetLastError());
+    return MTM_OK;
+}
+
+// The whole route.  *done = false: the list overflowed (a threshold that passes nearly everything) - the caller runs the
+// float64 kernel.
+static int launch_masked_bf16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, float* maps, bool* done) {
+    *done = false;
+    MaskBf16Plan P;
+    MTMC(mbf_prepare(c, sc, &P));
+    MaskF32Params q{};
+    unsigned long long count = 0;
+    // Round 6: ONE piece product first (ncc_bf16_kernel<MB, 1>: bounds 2^-7 instead of 2^-15 of the norms' products - the
+    // combine pass states them with the eps of the launch that ran); a list that overflows repeats the screen with three
+    for (int np = R.bf16_np == 1 ? 1 : 3;; np = 3) {
+        MTMC(mbf_raw(c, sc, P, np));
+        c->timing.f32_pieces = np;
+        q = mbf_params(c, P, np, R.mbf_thr, maps);
+        MTMC(mbf_list(c, P, q, R.mbf_global, &count));
+        if (count <= P.cap) {
+            if (np == 1) c->np1_backoff_len = 16;
+            break;
+        }
+        if (np == 3) return MTM_OK;                                 // *done stays false: float64 kernel
+        R.bf16_np = 3;                                              // (this call's other classes and the next calls start with three)
+        c->np1_backoff = c->np1_backoff_len;
+        c->np1_backoff_len = std::min(2 * c->np1_backoff_len, 1024);
     }
-    if (np == 3) return MTM_OK;                                 // *done stays false: float64 kernel
-    R.bf16_np = 3;                                              // (this call's other classes and the next calls start with three)
-    c->np1_backoff = c->np1_backoff_len;
-    c->np1_backoff_len = std::min(2 * c->np1_backoff_len, 1024);
-    }
-    if (count > 0) {
-        RefineParams r{};
-        r.img = img;
-        r.td = c->td.as<TemplDev>();
-        r.weights = c->weights.as<double>();
-        r.method = c->method;
-        r.cls = c->td_host[(size_t)sc.members[0]].cls;
-        r.ring = 0;
-        r.list = q.list;
-        r.count = q.counter;
-        r.cap = cap;
-        r.maps = maps;
-        const unsigned rgrid = (unsigned)std::min<unsigned long long>(count, 16384ull);
-        hipLaunchKernelGGL(refine_rescore_masked_kernel, dim3(rgrid), dim3(64), 0, c->stream, r);
-        HIPC(hipGetLastError());
-    }
+    MTMC(mbf_rescore(c, sc, q, count));
     R.mbf_used = true;
     *done = true;
     return MTM_OK;
@@ -1927,6 +1978,108 @@ int mtm_debug_window_stats_route(mtm_ctx* c, const mtm_window_stats_route* a) {
     MTMC(fetch(a->sq, o_sq, st_bytes));
     MTMC(fetch(a->blk, o_blk, rec_bytes));
     info[11] = (int64_t)llround((double)ms * 1e6);
+    std::memcpy(a->info, info, sizeof(info));
+    return MTM_OK;
+}
+
+// Test support: the masked float32 screen (tests/test_gpu_maskf32_screen.py) through the stage functions launch_masked_bf16
+// runs - mbf_prepare, mbf_raw, mbf_list, mbf_rescore - with what they leave behind copied out in between: the two raw
+// launches' sums and the bounds (maskf32_dump_kernel: maskf32_pixel and maskf32_bounds as the listing kernels call them),
+// the tile constants, the score maps after the listing pass and after re-scoring, the list and the best[] keys.
+int mtm_debug_maskf32_screen(mtm_ctx* c, const mtm_maskf32_screen* a) {
+    if (!c || !a) {
+        set_error("mtm_debug_maskf32_screen: null context or arguments");
+        return MTM_E_INVALID;
+    }
+    MTM_NOT_IN_FLIGHT(c, "mtm_debug_maskf32_screen");
+    const auto bad = [](const char* what, int rc = MTM_E_INVALID) {
+        set_error(std::string("mtm_debug_maskf32_screen: ") + what);
+        return rc;
+    };
+    if (a->list_cap < 0 || a->list_cap > kCandListMax) return bad("list_cap in 0 .. 2^20");
+    if (a->set_cap) {           // only: the capacity the next search calls of this context give the screen's list (0: their own)
+        c->mbf_cap_debug = a->list_cap;
+        return MTM_OK;
+    }
+    if ((a->pieces != 1 && a->pieces != 3) || (a->mode != MTM_PEAKS_LOCAL && a->mode != MTM_PEAKS_GLOBAL) || !a->info)
+        return bad("pieces 1 or 3, mode MTM_PEAKS_LOCAL or MTM_PEAKS_GLOBAL and info are needed");
+    if (!c->have_image || !c->have_templ) return bad("set the image and the templates first", MTM_E_STATE);
+    HIPC(hipSetDevice(c->device));
+    MTMC(place_templates(c));
+    // (SizeClass::mask_bf16: placement's masked_bf16_class_ok on a class of the default kernel choice)
+    if (c->classes.size() != 1 || !c->classes[0].masked || !c->classes[0].mask_bf16)
+        return bad("the templates are not ONE masked float32 size class the screen takes (single channel, float32 image and "
+                   "templates, w <= 256, TM_SQDIFF or TM_CCORR_NORMED, MTM_OPT_F32_MFMA 1 or 3)");
+    const SizeClass& sc = c->classes[0];
+    const int n = (int)c->templs.size();
+    if ((int)sc.members.size() != n) return bad("internal: the class does not hold every template", MTM_E_STATE);
+    const int oh = c->rows - sc.h + 1, ow = c->cols - sc.w + 1;
+    const size_t n_out = (size_t)n * oh * ow;
+    if (a->n_templ != n || a->oh != oh || a->ow != ow) return bad("n_templ, oh, ow do not match the context's templates and image");
+    MTMC(ensure_maps(c));
+    MTMC(ensure_f32_plane(c));
+    c->maps_valid = false;
+    float* maps = c->maps.as<float>();
+    const long long cap_before = c->mbf_cap_debug;
+    if (a->list_cap > 0) c->mbf_cap_debug = a->list_cap;
+    MaskBf16Plan P;
+    const int rc_prep = mbf_prepare(c, sc, &P);
+    c->mbf_cap_debug = cap_before;
+    MTMC(rc_prep);
+    const int nyb = P.p.nyb, nseg = P.p.nseg;
+    constexpr int kCanary = 8;
+    const size_t n_rec_max = (size_t)std::min<unsigned long long>(P.cap, n_out);
+    if (a->tiles < (int64_t)P.n_tiles || (a->records && a->capacity < (int64_t)n_rec_max + kCanary))
+        return bad("tiles below nyb * nseg, or records without room for min(list_cap, n_templ * oh * ow) + 8");
+    // the list with a canary of 8 records behind its capacity
+    MTMC(c->mbf_list.ensure(16 + sizeof(mtm_hit) * ((size_t)P.cap + kCanary)));
+    HIPC(hipMemsetAsync(c->mbf_list.as<uint8_t>() + 16 + sizeof(mtm_hit) * (size_t)P.cap, 0xC5, sizeof(mtm_hit) * kCanary, c->stream));
+    MTMC(mbf_raw(c, sc, P, a->pieces));
+    HIPC(hipGetLastError());
+    const MaskF32Params q = mbf_params(c, P, a->pieces, a->thr, maps);
+    // the bounds, ahead of the listing pass
+    const size_t o_c1 = 0, o_c2 = round_up(sizeof(float) * n_out, 256), o_lb = 2 * o_c2, o_ub = o_lb + round_up(sizeof(double) * n_out, 256);
+    MTMC(c->mbf_dbg.ensure(o_ub + sizeof(double) * n_out));
+    uint8_t* d = c->mbf_dbg.as<uint8_t>();
+    hipLaunchKernelGGL(maskf32_dump_kernel, dim3((ow + 255) / 256, oh), dim3(256), 0, c->stream, q, n, reinterpret_cast<float*>(d + o_c1),
+                       reinterpret_cast<float*>(d + o_c2), reinterpret_cast<double*>(d + o_lb), reinterpret_cast<double*>(d + o_ub));
+    HIPC(hipGetLastError());
+    unsigned long long count = 0;
+    MTMC(mbf_list(c, P, q, a->mode == MTM_PEAKS_GLOBAL, &count));
+    const auto fetch = [&](void* to, const void* from, size_t bytes) -> int {
+        if (to && bytes) HIPC(hipMemcpy(to, from, bytes, hipMemcpyDeviceToHost));
+        return MTM_OK;
+    };
+    const auto fetch_maps = [&](float* to) -> int {
+        if (!to) return MTM_OK;
+        for (int t = 0; t < n; ++t) {
+            const TemplDev& T = c->td_host[(size_t)t];
+            HIPC(hipMemcpy2D(to + (size_t)t * oh * ow, sizeof(float) * ow, maps + T.map_off, sizeof(float) * T.map_pitch,
+                             sizeof(float) * ow, (size_t)oh, hipMemcpyDeviceToHost));
+        }
+        return MTM_OK;
+    };
+    MTMC(fetch(a->c1, d + o_c1, sizeof(float) * n_out));
+    MTMC(fetch(a->c2, d + o_c2, sizeof(float) * n_out));
+    MTMC(fetch(a->lb, d + o_lb, sizeof(double) * n_out));
+    MTMC(fetch(a->ub, d + o_ub, sizeof(double) * n_out));
+    MTMC(fetch(a->mu_i, q.mu_i, sizeof(float) * P.n_tiles));
+    MTMC(fetch(a->mu_j, q.mu_j, sizeof(float) * P.n_tiles));
+    MTMC(fetch_maps(a->map_listed));
+    if (a->mode == MTM_PEAKS_GLOBAL) MTMC(fetch(a->best, c->mbf_best.p, sizeof(unsigned int) * (size_t)n));
+    const unsigned long long n_rec = std::min(count, P.cap);
+    int rescored = 0;
+    if (a->rescore && count <= P.cap) {             // (an overflowing list is not re-scored: production repeats the screen)
+        MTMC(mbf_rescore(c, sc, q, count));
+        HIPC(hipStreamSynchronize(c->stream));
+        rescored = 1;
+    }
+    MTMC(fetch_maps(a->map_rescored));
+    // the records that were written, then the canary
+    MTMC(fetch(a->records, q.list, sizeof(mtm_hit) * (size_t)n_rec));
+    if (a->records) MTMC(fetch(a->records + n_rec, q.list + P.cap, sizeof(mtm_hit) * kCanary));
+    const unsigned long long cap_production = (unsigned long long)std::min<int64_t>(std::max<int64_t>(c->hit_cap, 1 << 18), kCandListMax);
+    const int64_t info[12] = {n, sc.h, sc.w, oh, ow, nyb, nseg, P.mb, (int64_t)cap_production, (int64_t)P.cap, (int64_t)count, rescored};
     std::memcpy(a->info, info, sizeof(info));
     return MTM_OK;
 }

@@ -112,6 +112,26 @@ __device__ __forceinline__ void maskf32_bounds(const MaskF32Params& p, int t, co
     *approx = (float)(c1 / sqrt(tms * fmax(c2, 1e-300)));
 }
 
+// Test support (mtm_debug_maskf32_screen): the two approximate sums as the listing kernels read them and the bounds as they
+// compute them, per template and output, tightly packed [template index][oh][ow].  Same grid as the listing kernels.
+__global__ __launch_bounds__(256) void maskf32_dump_kernel(MaskF32Params p, int n_list, float* __restrict__ c1, float* __restrict__ c2,
+                                                           double* __restrict__ lb_out, double* __restrict__ ub_out) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= p.ow || y >= p.oh) return;
+    const MaskF32Pixel px = maskf32_pixel(p, x, y);
+    for (int li = 0; li < n_list; ++li) {
+        const int t = p.tlist[li];
+        float approx;
+        double lb, ub;
+        maskf32_bounds(p, t, p.td[t], px, x, y, &approx, &lb, &ub);
+        const size_t o = ((size_t)t * p.oh + y) * p.ow + x;
+        c1[o] = p.m1[p.td_u[t].map_off + (size_t)y * p.td_u[t].map_pitch + x];
+        c2[o] = p.m2[p.td_v[t].map_off + (size_t)y * p.td_v[t].map_pitch + x];
+        lb_out[o] = lb;
+        ub_out[o] = ub;
+    }
+}
+
 // Local extrema against a threshold: "below" placeholders where the upper bound stays below it, the rest listed.
 // Grid: (ceil(ow / 256), oh); every thread walks the n_list templates of the class for its pixel.
 __global__ __launch_bounds__(256) void maskf32_combine_kernel(MaskF32Params p, int n_list) {

@@ -181,7 +181,8 @@ def model_acc(img, templs, pieces=3):
     assert pieces in (1, 3)
     img3 = _as3d(img)
     t3s = [_as3d(t) for t in templs]
-    assert img3.dtype == np.float32 and all(t.dtype == np.float32 and t.shape == t3s[0].shape for t in t3s)
+    # (float64 templates: the masked screen's U = T M^2 and V = M^2, which pack_class_bf16 centres in float64 as well)
+    assert img3.dtype == np.float32 and all(t.dtype in (np.float32, np.float64) and t.shape == t3s[0].shape for t in t3s)
     rows, cols, chans = img3.shape
     h, w, _ = t3s[0].shape
     assert 1 <= chans <= K_MAX_CHANS and chans == t3s[0].shape[2] and w <= MAX_W

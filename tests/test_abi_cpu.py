@@ -65,6 +65,22 @@ def test_peak_pass_block_matches_the_header(lib):
     assert lib.load().mtm_debug_peak_pass(None, ctypes.byref(a)) == -1 and b"mtm_debug_peak_pass" in lib.load().mtm_last_error()
 
 
+def test_maskf32_screen_block_matches_the_header(lib):
+    """mtm_debug_maskf32_screen (test support): the binding's argument block has the header's fields in the header's order
+    and size, the header's ABI note names the entry, and the entry point refuses null arguments without a GPU."""
+    hdr = open(os.path.join(ROOT, "include", "mtm_hip.h")).read()
+    body = hdr[hdr.index("typedef struct mtm_maskf32_screen {"):hdr.index("} mtm_maskf32_screen;")]
+    fields = [f for line in body.splitlines()[1:] for f in re.findall(r"\b([a-z_0-9]+)\s*[,;]", line)]
+    assert fields == [f[0] for f in lib.MtmMaskF32Screen._fields_], fields
+    assert ctypes.sizeof(lib.MtmMaskF32Screen) == 6 * 4 + 17 * 8 == 160      # (no padding: six 4-byte fields, then 8-byte ones)
+    assert len(lib.MASKF32_SCREEN_INFO_FIELDS) == 12 and "info[12]" in hdr[hdr.index("mtm_debug_window_stats_route(mtm_ctx"):]
+    assert "mtm_debug_maskf32_screen" in hdr[hdr.index("Bumped when"):hdr.index("#define MTM_ABI_VERSION")]
+    assert lib.load().mtm_debug_maskf32_screen(None, None) == -1
+    a = lib.MtmMaskF32Screen()
+    assert lib.load().mtm_debug_maskf32_screen(None, ctypes.byref(a)) == -1
+    assert b"mtm_debug_maskf32_screen" in lib.load().mtm_last_error()
+
+
 def test_struct_layout(lib):
     assert ctypes.sizeof(lib.MtmHit) == 24
     assert ctypes.sizeof(lib.MtmTempl) == 48

@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes, mtm_match_blocks_passes_validated, mtm_debug_validate_blocks, mtm_match_blocks_second, mtm_match_blocks_passes_second, mtm_debug_second_peaks, mtm_deform_image, mtm_match_blocks_passes_deformed, mtm_debug_maskf32_screen - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes, mtm_match_blocks_passes_validated, mtm_debug_validate_blocks, mtm_match_blocks_second, mtm_match_blocks_passes_second, mtm_debug_second_peaks, mtm_deform_image, mtm_match_blocks_passes_deformed, mtm_debug_maskf32_screen, mtm_match_blocks_passes_steered, mtm_deform_image_q8, mtm_debug_steer_q8 - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -876,6 +876,44 @@ int mtm_match_blocks_passes_deformed(mtm_ctx* ctx, const void* reference, int64_
                                      int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
                                      const mtm_block_pass* passes, int n_passes, int method, double threshold, double epsilon,
                                      mtm_hit* out, float* nbhd, uint8_t* valid, int32_t* predicted);
+
+/* Sub-pixel steering of the deformed passes.  THE RULE.  The fit: per axis the three float32 scores of the
+ * record's 3 x 3 neighbourhood (neighbour at -1, centre, neighbour at +1) widened to double as a, b, c, negated for methods 0
+ * and 1; d = (a - 2.0 b) + c; the offset o = 0.5 (a - c) / d when a, b, c are finite, b >= a, b >= c and d < 0, else 0.0
+ * (IEEE float64, nothing contracted).  The Q8 position: P = (double)pos_w + o per component, pos_w the integer position found
+ * in the searched (warped) image; Q = floor(256.0 P + 0.5).  The steering displacement of record k of a pass, b its block's
+ * (x, y) and c the pass's predicted field at the block's centre (Q8; zero for pass 0): D8 = Q - 256 b + c; with validation an
+ * outlier - flagged as before, on the integer record - takes D8 = 256 rep, rep its neighbours' integer median.  The filter over
+ * the pass's ny x nx grid, per component in int64, reading only the unfiltered set:
+ *   S8[j,i] = (sum over u, v in {-1, 0, 1} of k[u] k[v] D8[clamp(j + u, 0, ny - 1), clamp(i + v, 0, nx - 1)] + 8) >> 4,
+ * k = (1, 2, 1), the shift arithmetic.  The field of Q8 nodes S (|S| <= 2^30), (i, ax), (j, ay) as above:
+ *   F = (S[j,i] (256 - ax)(256 - ay) + S[j,i1] ax (256 - ay) + S[j1,i] (256 - ax) ay + S[j1,i1] ax ay + 32768) >> 16,
+ * which for S = 256 d is the F of d above, bit for bit.  The warp and the record's shift (c + 128) >> 8 are unchanged.
+ *
+ * mtm_match_blocks_passes_steered is mtm_match_blocks_passes_deformed with the argument `steer`: 0 is that function in every
+ * respect (the same launches); 1 steers every pass p >= 1 by the field of the S8 of pass p - 1 instead of the field of its
+ * integer records - the neighbourhoods of every pass that steers another are then computed whether or not nbhd is asked
+ * for, and two small kernels (one lane per record: D8; one lane per node: S8) follow such a pass.  out, nbhd, valid and
+ * predicted keep their meaning and layout; the last pass steers nothing.  Any other steer is MTM_E_INVALID naming it. */
+int mtm_match_blocks_passes_steered(mtm_ctx* ctx, const void* reference, int64_t reference_stride_bytes, const void* image,
+                                    int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                                    const mtm_block_pass* passes, int n_passes, int method, double threshold, double epsilon,
+                                    mtm_hit* out, float* nbhd, uint8_t* valid, int32_t* predicted, int steer);
+
+/* mtm_deform_image with displacements in Q8 (1/256 pixel), each within +-2^30: the warp by the field of Q8 nodes above - how a
+ * frame is registered when its drift field is known to sub-pixel precision.  256 d gives mtm_deform_image's pixels of d.
+ * ctx == NULL runs the rule on the host.  Everything else as mtm_deform_image. */
+int mtm_deform_image_q8(mtm_ctx* ctx, const void* px, int64_t row_stride_bytes, int rows, int cols, int chans, int dtype, int bw,
+                        int bh, int sx, int sy, const int32_t* displacements_q8, void* out, int64_t out_stride_bytes);
+
+/* Test support: the steering displacements of one pass over a grid of nx x ny blocks at stride (sx, sy), row-major.  recs:
+ * the pass's records (positions: the one found plus the rounded field); nbhd: 9 floats per record; predicted: 2 int32 per
+ * record, the pass's field in Q8; valid and steer_recs: both NULL, or the flags and validated records of the median test;
+ * mode_min: 1 for methods 0 and 1.  out_q8: 2 int32 per record - D8, or with smooth != 0 the filtered S8.  ctx == NULL runs the
+ * inline functions on the host (no GPU); with a context everything is uploaded, the steer kernel and - smooth != 0 - the
+ * filter kernel are launched once each and out_q8 comes back. */
+int mtm_debug_steer_q8(mtm_ctx* ctx, const mtm_hit* recs, const float* nbhd, const int32_t* predicted, const uint8_t* valid,
+                       const mtm_hit* steer_recs, int nx, int ny, int sx, int sy, int mode_min, int smooth, int32_t* out_q8);
 
 /* The 3 x 3 score neighbourhoods of n points in one call: out[9 k + 3 (1 + dy) + (1 + dx)] = the score of
  * template pts[k].templ_idx at window (x + dx, y + dy) of the image's score map, NaN for a window outside the map.  Image:

@@ -267,6 +267,17 @@ SYMBOLS = {
                                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                                         ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                         ctypes.c_void_p]),
+    "mtm_match_blocks_passes_steered": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                       ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                                       ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_int]),
+    "mtm_deform_image_q8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    "mtm_debug_steer_q8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_void_p]),
     "mtm_hit_neighbourhoods": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "mtm_find_matches_next": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
@@ -647,19 +658,56 @@ def debug_validate_blocks(positions, grid_shape, step, threshold=2.0, epsilon=0.
     return valid.astype(bool), np.stack((steer["x"], steer["y"]), axis=1).astype(np.int64)
 
 
-def deform_image(image, grid, displacements, context=None):
+def deform_image(image, grid, displacements, context=None, q8=False):
     """The warp of mtm_deform_image: `image` (uint8 with 1 or 3 channels, or single-channel uint16) by the field of
     `displacements` - (N, 2) integers (dx, dy), each within +-2^22 - over the coarse `grid` = (bw, bh, sx, sy); the warped
     image, of the image's shape.  `context=None` runs the rule in the library's host code, no GPU needed; with a Context
-    the image goes through deform_image_kernel."""
+    the image goes through deform_image_kernel.  `q8`: the displacements are in Q8, each within +-2^30
+    (mtm_deform_image_q8)."""
     a, ptr, stride = _pixel_rows(image)
     chans = 1 if a.ndim == 2 else a.shape[2]
     d = np.ascontiguousarray(displacements, dtype=np.int32).reshape(-1, 2)
     out = np.empty(a.shape, dtype=a.dtype)
     lib = load() if context is None else context._lib
-    check(lib.mtm_deform_image(None if context is None else context._h, ptr, stride, a.shape[0], a.shape[1], chans,
-                               _dtype_code(a), *(int(v) for v in grid), d.ctypes.data, out.ctypes.data, out.strides[0]),
-          "mtm_deform_image")
+    name = "mtm_deform_image_q8" if q8 else "mtm_deform_image"
+    check(getattr(lib, name)(None if context is None else context._h, ptr, stride, a.shape[0], a.shape[1], chans,
+                             _dtype_code(a), *(int(v) for v in grid), d.ctypes.data, out.ctypes.data, out.strides[0]), name)
+    return out
+
+
+def debug_steer_q8(positions, nbhd, predicted, grid_shape, step, mode_min, smooth, valid=None, steer_positions=None,
+                   context=None):
+    """Test support (mtm_debug_steer_q8): the Q8 steering displacements of one pass of a steered call.  `positions`: the
+    (ny * nx, 2) integer record positions of a `grid_shape` = (ny, nx) grid in row-major order, block (iy, ix) at (ix * sx,
+    iy * sy) with `step` = (sx, sy); `nbhd`: (N, 3, 3) float32; `predicted`: (N, 2) integers, the pass's field in Q8;
+    `valid` / `steer_positions`: both None, or the median test's flags and the (N, 2) positions that steer.  Returns (N, 2)
+    int32: D8, or with `smooth` the filtered S8.  `context=None` runs the rule in the library's host code, no GPU needed;
+    with a Context the records go through blocks_steer_q8_kernel and blocks_smooth_q8_kernel."""
+    ny, nx = (int(v) for v in grid_shape)
+    sx, sy = (int(v) for v in step)
+    pos = np.asarray(positions).reshape(-1, 2)
+    n = len(pos)
+    nb = np.ascontiguousarray(nbhd, dtype=np.float32).reshape(-1, 9)
+    pred = np.ascontiguousarray(predicted, dtype=np.int32).reshape(-1, 2)
+    if n != nx * ny or len(nb) != n or len(pred) != n or (valid is None) != (steer_positions is None):
+        raise ValueError("debug_steer_q8: one position, neighbourhood and field per block of the %d x %d grid" % (ny, nx))
+
+    def records(p):
+        rec = np.zeros(n, dtype=HIT_DTYPE)
+        rec["templ_idx"] = np.arange(n)
+        rec["x"], rec["y"] = p[:, 0], p[:, 1]
+        return rec
+
+    rec = records(pos)
+    flags = steer = None
+    if valid is not None:
+        flags = np.ascontiguousarray(valid, dtype=np.uint8).reshape(n)
+        steer = records(np.asarray(steer_positions).reshape(n, 2))
+    out = np.zeros((n, 2), dtype=np.int32)
+    lib = load() if context is None else context._lib
+    check(lib.mtm_debug_steer_q8(None if context is None else context._h, rec.ctypes.data, nb.ctypes.data, pred.ctypes.data,
+                                 None if flags is None else flags.ctypes.data, None if steer is None else steer.ctypes.data,
+                                 nx, ny, sx, sy, int(mode_min), int(bool(smooth)), out.ctypes.data), "mtm_debug_steer_q8")
     return out
 
 
@@ -1215,12 +1263,16 @@ class Context(_RecordMemo):
         """Test support: the module's debug_validate_blocks on this context - blocks_validate_kernel, launched once."""
         return debug_validate_blocks(positions, grid_shape, step, threshold, epsilon, context=self)
 
-    def deform_image(self, image, grid, displacements):
+    def deform_image(self, image, grid, displacements, q8=False):
         """The module's deform_image on this context: one upload, deform_image_kernel, the warped image back."""
-        return deform_image(image, grid, displacements, context=self)
+        return deform_image(image, grid, displacements, context=self, q8=q8)
+
+    def debug_steer_q8(self, positions, nbhd, predicted, grid_shape, step, mode_min, smooth, valid=None, steer_positions=None):
+        """Test support: the module's debug_steer_q8 on this context - the steer and filter kernels, launched once each."""
+        return debug_steer_q8(positions, nbhd, predicted, grid_shape, step, mode_min, smooth, valid, steer_positions, context=self)
 
     def match_blocks_passes(self, reference, image, passes, counts, method, with_nbhd=False, validate=None, second=None,
-                            deform=False):
+                            deform=False, steer=0):
         """Coarse-to-fine block matching in one native call (mtm_match_blocks_passes): `passes` BLOCK_PASS_DTYPE records,
         `counts` the blocks of every pass's grid.  Returns (records, pass-major, sum(counts) of them; neighbourhoods in
         the same order, or None).  The templates set on the context are not touched.
@@ -1229,23 +1281,28 @@ class Context(_RecordMemo):
         `second` = the exclusion radius (mtm_match_blocks_passes_second): the second peaks' records of every pass, in the
         same order, are returned as the last element.
         `deform` (not with `second`): window deformation between the passes (mtm_match_blocks_passes_deformed); the last
-        element returned is then the (sum(counts), 2) int32 field at every block's centre in Q8, zero for pass 0."""
+        element returned is then the (sum(counts), 2) int32 field at every block's centre in Q8, zero for pass 0.
+        `steer` (with `deform`): 1 - refined positions, filtered, steer the deformed passes
+        (mtm_match_blocks_passes_steered); 0 is the deformed call as it is."""
         passes = block_pass_records(passes)
         n = int(sum(counts))
         out = np.empty(n, dtype=HIT_DTYPE)
         nbhd = np.empty((n, 3, 3), dtype=np.float32) if with_nbhd else None
         pair, keep = self._pair_args(reference, image)
+        if steer and not deform:
+            raise ValueError("match_blocks_passes: steer needs deform")
         if deform:
             if second is not None:
                 raise ValueError("match_blocks_passes: deform does not go with second")
             threshold, epsilon = validate if validate is not None else (0.0, 0.0)
             valid = np.zeros(n, dtype=np.uint8) if validate is not None else None
             pred = np.zeros((n, 2), dtype=np.int32)
-            check(self._lib.mtm_match_blocks_passes_deformed(*pair, passes.ctypes.data, len(passes), int(method),
-                                                             float(threshold), float(epsilon), out.ctypes.data,
-                                                             nbhd.ctypes.data if with_nbhd else None,
-                                                             None if valid is None else valid.ctypes.data, pred.ctypes.data),
-                  "mtm_match_blocks_passes_deformed")
+            tail = (passes.ctypes.data, len(passes), int(method), float(threshold), float(epsilon), out.ctypes.data,
+                    nbhd.ctypes.data if with_nbhd else None, None if valid is None else valid.ctypes.data, pred.ctypes.data)
+            if steer:
+                check(self._lib.mtm_match_blocks_passes_steered(*pair, *tail, int(steer)), "mtm_match_blocks_passes_steered")
+            else:
+                check(self._lib.mtm_match_blocks_passes_deformed(*pair, *tail), "mtm_match_blocks_passes_deformed")
             return (out, nbhd, pred) if valid is None else (out, nbhd, valid.astype(bool), pred)
         if second is not None:
             threshold, epsilon = validate if validate is not None else (0.0, 0.0)

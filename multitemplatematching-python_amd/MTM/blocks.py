@@ -49,7 +49,9 @@ field interpolated from the pass before (``displacement_field``: bilinear betwee
 rotation or strain still meets a window shaped like itself; ``field_at`` is the field at the blocks' centres, which the
 pass adds to what it finds.  All on the device, one native call; the three helpers state the rule in numpy, bit for bit.
 ``deformImage`` is the warp by itself on the device (mtm_deform_image): how a frame is registered once its drift field
-is known.
+is known.  ``steer="refined"`` steers every deformed pass by the pass before's SUB-PIXEL positions (``to_q8``), filtered by
+a 3 x 3 binomial kernel over the grid (``smooth_displacements``), instead of by its integer records: what makes deformation
+worth iterating on the final grid.
 
 ``matchBlocksStack`` is the movie form: the pairs of a stack of frames - each frame against the previous or against the
 first - in one native call (mtm_match_blocks_stack), every frame uploaded once; per pair the very results of
@@ -65,7 +67,7 @@ from . import TM_CCOEFF_NORMED
 
 __all__ = ["matchBlocks", "matchBlocksStack", "matchBlocksMultipass", "plane_peaks", "grid", "search_box", "search_box_at",
            "predict_offsets", "displacements", "grid_shape", "validate", "second_peaks", "peak_ratio", "displacement_field",
-           "field_at", "deform", "deformImage"]
+           "field_at", "deform", "deformImage", "to_q8", "smooth_displacements"]
 
 _I64 = np.dtype(np.int64)
 _U16_MAX_PIXELS = 1 << 21       # mtm_match_blocks: uint16 correlations stay below 2^53, exact in float64
@@ -260,8 +262,11 @@ def _deform_axis(n, s, wc, X2):
     return i, (256 * a + s) // (2 * s)
 
 
-def _deform_args(shape, coarse, displacements, who):
-    """(wc, hc, sx, sy, nx, ny, d): the coarse grid's axes and its displacements as an (ny, nx, 2) int64 array."""
+def _deform_args(shape, coarse, displacements, who, q8=False):
+    """(wc, hc, sx, sy, nx, ny, d): the coarse grid's axes and its displacements as an (ny, nx, 2) int64 array.  ``q8``: the
+    displacements are in Q8 (the same limit of 2^22 pixels)."""
+    _check_flag(q8, "q8")
+    top = _DEFORM_MAX << 8 if q8 else _DEFORM_MAX
     try:
         cb, cs = coarse
     except (TypeError, ValueError):
@@ -276,23 +281,25 @@ def _deform_args(shape, coarse, displacements, who):
     if nx * ny == 0:
         raise ValueError("%s: the coarse grid is empty" % who)
     if d.dtype.kind == "u":
-        d = np.minimum(d, np.uint64(_DEFORM_MAX + 1))
+        d = np.minimum(d, np.uint64(top + 1))
     d = d.astype(_I64)
-    if np.abs(d).max() > _DEFORM_MAX:
+    if np.abs(d).max() > top:
         raise ValueError("%s: displacements beyond 2^22 pixels are not supported" % who)
     return wc, hc, sx, sy, nx, ny, d.reshape(ny, nx, 2)
 
 
-def _field(d, ix, ax, iy, ay):
-    """The Q8 field from the nodes d (ny, nx, 2) at lower nodes (iy, ix) with weights (ay, ax), broadcast together."""
+def _field(d, ix, ax, iy, ay, q8=False):
+    """The Q8 field from the nodes d (ny, nx, 2) at lower nodes (iy, ix) with weights (ay, ax), broadcast together; ``q8``:
+    the nodes are in Q8 themselves."""
     ny, nx = d.shape[:2]
     ix1, iy1 = np.minimum(ix + 1, nx - 1), np.minimum(iy + 1, ny - 1)
     ax, ay = ax[..., None], ay[..., None]
-    return (d[iy, ix] * (256 - ax) * (256 - ay) + d[iy, ix1] * ax * (256 - ay) + d[iy1, ix] * (256 - ax) * ay
-            + d[iy1, ix1] * ax * ay + 128) >> 8
+    acc = (d[iy, ix] * (256 - ax) * (256 - ay) + d[iy, ix1] * ax * (256 - ay) + d[iy1, ix] * (256 - ax) * ay
+           + d[iy1, ix1] * ax * ay)
+    return (acc + 32768) >> 16 if q8 else (acc + 128) >> 8
 
 
-def displacement_field(shape, coarse, displacements):
+def displacement_field(shape, coarse, displacements, q8=False):
     """The per-pixel displacement field a coarse grid's displacements give, (H, W, 2) int64 of (Fx, Fy) in Q8 (1/256 px) -
     the field ``matchBlocksMultipass(deform=True)`` warps by, in plain numpy.  ``coarse``: ``(block, step)`` as ``grid``
     takes them; ``displacements``: the integer (Nc, 2) ``(dx, dy)`` of ``grid(shape, *coarse)`` in row-major order.
@@ -305,18 +312,25 @@ def displacement_field(shape, coarse, displacements):
 
         F = (d[j,i] (256-ax)(256-ay) + d[j,i1] ax (256-ay) + d[j1,i] (256-ax) ay + d[j1,i1] ax ay + 128) >> 8
 
+    ``q8=True``: the integer displacements are themselves in Q8 (sub-pixel nodes ``S``, ``|S| <= 2^30``), and
+
+        F = (S[j,i] (256-ax)(256-ay) + S[j,i1] ax (256-ay) + S[j1,i] (256-ax) ay + S[j1,i1] ax ay + 32768) >> 16
+
+    which for ``S = 256 d`` is the field of ``d``, bit for bit.
+
     Float displacements raise TypeError, a wrong length (or one beyond 2^22 pixels) ValueError."""
-    wc, hc, sx, sy, nx, ny, d = _deform_args(shape, coarse, displacements, "displacement_field")
+    wc, hc, sx, sy, nx, ny, d = _deform_args(shape, coarse, displacements, "displacement_field", q8)
     H, W = int(shape[0]), int(shape[1])
     ix, ax = _deform_axis(nx, sx, wc, 2 * np.arange(W, dtype=_I64))
     iy, ay = _deform_axis(ny, sy, hc, 2 * np.arange(H, dtype=_I64))
-    return _field(d, ix[None, :], ax[None, :], iy[:, None], ay[:, None])
+    return _field(d, ix[None, :], ax[None, :], iy[:, None], ay[:, None], q8)
 
 
-def field_at(shape, coarse, displacements, blocks):
+def field_at(shape, coarse, displacements, blocks, q8=False):
     """``displacement_field``'s rule at the doubled centres ``(2 x + w - 1, 2 y + h - 1)`` of ``blocks`` ((N, 4) integers
-    of ``(x, y, w, h)``): (N, 2) int64 in Q8 - what a deformed pass adds to what it finds in the warped image."""
-    wc, hc, sx, sy, nx, ny, d = _deform_args(shape, coarse, displacements, "field_at")
+    of ``(x, y, w, h)``): (N, 2) int64 in Q8 - what a deformed pass adds to what it finds in the warped image.  ``q8``:
+    as ``displacement_field``'s."""
+    wc, hc, sx, sy, nx, ny, d = _deform_args(shape, coarse, displacements, "field_at", q8)
     b = np.asarray(blocks)
     if b.size == 0:
         return np.zeros((0, 2), _I64)
@@ -325,7 +339,63 @@ def field_at(shape, coarse, displacements, blocks):
     b = b.astype(_I64)
     ix, ax = _deform_axis(nx, sx, wc, 2 * b[:, 0] + b[:, 2] - 1)
     iy, ay = _deform_axis(ny, sy, hc, 2 * b[:, 1] + b[:, 3] - 1)
-    return _field(d, ix, ax, iy, ay)
+    return _field(d, ix, ax, iy, ay, q8)
+
+
+def to_q8(positions):
+    """Positions (or displacements) in pixels as int64 in Q8 (1/256 px): ``floor(256.0 * p + 0.5)`` in float64 - how a
+    steered call (``matchBlocksMultipass(steer="refined")``) takes the refined positions of ``matchBlocks(refine=True)``.
+    Integers give ``256 * p`` exactly; values that are not finite or beyond 2^22 pixels raise ValueError."""
+    p = np.asarray(positions)
+    if p.dtype.kind in "iu":
+        p = p.astype(_I64)
+        if p.size and np.abs(p).max() > _DEFORM_MAX:
+            raise ValueError("to_q8: positions beyond 2^22 pixels are not supported")
+        return 256 * p
+    if p.dtype.kind != "f":
+        raise TypeError("to_q8: positions must be numbers (got %s)" % p.dtype)
+    p = p.astype(np.float64)
+    if p.size and not (np.abs(p) <= _DEFORM_MAX).all():
+        raise ValueError("to_q8: positions must be finite and within 2^22 pixels")
+    return np.floor(256.0 * p + 0.5).astype(_I64)
+
+
+def smooth_displacements(grid_shape, d):
+    """The predictor filter of a steered call, in plain numpy: the (ny * nx, 2) integer displacements ``d`` of a
+    ``grid_shape`` = ``(ny, nx)`` grid in row-major order filtered by the 3 x 3 binomial kernel, per component in int64:
+
+        S[j,i] = (sum over u, v in {-1, 0, 1} of k[u] k[v] d[clamp(j + u, 0, ny - 1), clamp(i + v, 0, nx - 1)] + 8) >> 4
+
+    with ``k = (1, 2, 1)`` and an arithmetic shift (a floor).  Only the input is read.  A constant field comes back
+    unchanged, a 1 x 1 grid is the identity.  Returns (N, 2) int64.  Float displacements raise TypeError; values beyond
+    2^30 (2^22 pixels in Q8) and bad shapes ValueError."""
+    try:
+        ny, nx = grid_shape
+    except (TypeError, ValueError):
+        raise ValueError("smooth_displacements: grid_shape must be (ny, nx) (got %r)" % (grid_shape,)) from None
+    if not _is_int(ny) or not _is_int(nx) or ny < 0 or nx < 0:
+        raise ValueError("smooth_displacements: grid_shape must be two integers >= 0 (got %r)" % (grid_shape,))
+    ny, nx = int(ny), int(nx)
+    a = np.asarray(d)
+    if a.ndim != 2 or a.shape[1] != 2 or len(a) != ny * nx:
+        raise ValueError("smooth_displacements: displacements of shape %s for a grid of %d x %d blocks (expected (%d, 2))" % (
+            a.shape, ny, nx, ny * nx))
+    if a.dtype.kind not in "iu":
+        raise TypeError("smooth_displacements: displacements must be integers (got %s): to_q8 makes them" % a.dtype)
+    if a.dtype.kind == "u":
+        a = np.minimum(a, np.uint64((_DEFORM_MAX << 8) + 1))
+    a = a.astype(_I64)
+    if ny * nx == 0:
+        return a
+    if np.abs(a).max() > _DEFORM_MAX << 8:
+        raise ValueError("smooth_displacements: displacements beyond 2^30 are not supported")
+    g = a.reshape(ny, nx, 2)
+    rows = np.clip(np.arange(-1, ny + 1), 0, ny - 1)
+    cols = np.clip(np.arange(-1, nx + 1), 0, nx - 1)
+    g = g[rows][:, cols]
+    v = g[:-2] + 2 * g[1:-1] + g[2:]
+    h = v[:, :-2] + 2 * v[:, 1:-1] + v[:, 2:]
+    return ((h + 8) >> 4).reshape(-1, 2)
 
 
 def deform(image, field):
@@ -358,19 +428,22 @@ def deform(image, field):
     return out.astype(img.dtype)
 
 
-def deformImage(image: np.ndarray, coarse, displacements, context=None):
+def deformImage(image: np.ndarray, coarse, displacements, context=None, q8=False):
     """``image`` warped by the field of a coarse grid's displacements, on the device: ``deform(image,
     displacement_field(image.shape, coarse, displacements))`` bit for bit, in one native call (mtm_deform_image: the
     image and the displacements go up, one kernel interpolates the field and resamples, the warped image comes back) - how
     a frame is registered once its drift field is known.  ``image``: uint8 with 1 or 3 channels or single-channel uint16;
-    ``coarse`` and ``displacements`` as ``displacement_field`` takes them; ``context``: the _lib.Context to run on."""
+    ``coarse`` and ``displacements`` as ``displacement_field`` takes them; ``context``: the _lib.Context to run on.
+    ``q8=True``: the integer displacements are in Q8 (``to_q8`` of a drift field known to sub-pixel precision), the result
+    ``deform(image, displacement_field(image.shape, coarse, displacements, q8=True))`` (mtm_deform_image_q8)."""
     if not isinstance(image, np.ndarray):
         raise TypeError("image must be a numpy array (got %s)" % type(image).__name__)
     _check_pixels(image, "deformImage", "images", "%s images")
-    wc, hc, sx, sy, nx, ny, d = _deform_args(image.shape, coarse, displacements, "deformImage")
+    wc, hc, sx, sy, nx, ny, d = _deform_args(image.shape, coarse, displacements, "deformImage", q8)
     ctx = context or _lib.default_context()     # (only now: every argument error comes before "no GPU")
+    kw = {"q8": True} if q8 else {}             # (the default reaches the context as it always did)
     with ctx.lock:
-        return ctx.deform_image(image, (wc, hc, sx, sy), d.reshape(-1, 2)).reshape(image.shape)
+        return ctx.deform_image(image, (wc, hc, sx, sy), d.reshape(-1, 2), **kw).reshape(image.shape)
 
 
 def displacements(blocks, positions):
@@ -582,7 +655,8 @@ def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, m
 
 
 def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, method: int = TM_CCOEFF_NORMED, *,
-                         refine: bool = False, context=None, validate=None, second=None, deform: bool = False):
+                         refine: bool = False, context=None, validate=None, second=None, deform: bool = False,
+                         steer: str = "integer"):
     """
     Coarse-to-fine block matching in one native call.  ``passes``: a non-empty sequence of ``(block, step, margin)``,
     ``block`` and ``step`` as ``grid`` takes them (``step=None``: the block size).  Pass 0 is ``matchBlocks`` over its
@@ -650,11 +724,38 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
     the flags of ``validate`` over ``pos - b[:, :2]`` and ``predicted_p = c / 256.0``.  An integer position of a deformed
     pass carries a displacement and is NOT clamped: it may lie outside ``[0, W - w]`` x ``[0, H - h]``.  ``deform=True``
     with ``second`` raises ValueError; ``len(passes) * max(H, W)`` must stay within 2^22.
+
+    ``steer``: ``"integer"`` (the call above, in every respect) or ``"refined"`` (needs ``deform=True``;
+    mtm_match_blocks_passes_steered, still one native call and one host wait): the displacement that steers pass p + 1 is
+    pass p's SUB-PIXEL position in Q8 (``to_q8`` of the fit in the searched image, plus the field that steered pass p), an
+    outlier's its neighbours' integer median as before, filtered by the 3 x 3 binomial kernel over the grid
+    (``smooth_displacements``) - an integer record carries up to half a pixel of rounding into every node of the next field,
+    which is why integer steering cannot be iterated, and the filter is what keeps the iteration from diverging.  The
+    tuples keep ``deform=True``'s layout and meaning; only what steers the next pass changes.  The call equals, bit for bit,
+
+        S8 = None
+        for p, (block, step, margin) in enumerate(passes):
+            b = grid(image.shape, block, step)
+            if p == 0:
+                searched, c = image, np.zeros((len(b), 2), np.int64)
+            else:
+                searched = deform(image, displacement_field(image.shape, prev, S8, q8=True))
+                c = field_at(image.shape, prev, S8, b, q8=True)
+            pos_w, sc = matchBlocks(reference, searched, b, margin, method)
+            fine_w, _ = matchBlocks(reference, searched, b, margin, method, refine=True)
+            pos = pos_w + ((c + 128) >> 8)              # the record; positions_p (refine=True: fine_w + c / 256.0)
+            D8 = to_q8(fine_w) - 256 * b[:, :2] + c     # with validate: D8[~valid] = 256 * rep[~valid], (valid, rep) =
+            #                                             validate(grid_shape(image.shape, block, step), pos - b[:, :2], ...)
+            S8 = smooth_displacements(grid_shape(image.shape, block, step), D8); prev = (block, step)
     """
     _check_images(reference, image)
     _check_method(method, "matchBlocksMultipass")
     _check_flag(refine, "refine")
     _check_flag(deform, "deform")
+    if not isinstance(steer, str) or steer not in ("integer", "refined"):
+        raise ValueError('steer must be "integer" or "refined" (got %r)' % (steer,))
+    if steer == "refined" and not deform:
+        raise ValueError("steer='refined' needs deform=True")
     r = _check_second(second)
     if deform and r is not None:
         raise ValueError("matchBlocksMultipass: deform=True does not go with second= in this version")
@@ -698,6 +799,8 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
     with ctx.lock:
         if deform:
             kw = {} if validate is None else {"validate": validate}
+            if steer == "refined":              # (the default passes nothing new: a context that knows no steer serves it)
+                kw["steer"] = 1
             raw, nbhd, *got = ctx.match_blocks_passes(reference, image, rec, counts, int(method), refine, deform=True, **kw)
             flags = got[0] if validate is not None else None
             pred = np.asarray(got[-1], dtype=_I64).reshape(-1, 2) / 256.0

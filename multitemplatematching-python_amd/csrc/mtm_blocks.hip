@@ -31,7 +31,10 @@
 // original image by the field of the records that steer it (deform_disp_kernel, deform_image_kernel: mtm_k_deform.hip.h;
 // the rule: mtm_blocks_deform.h, the single source of host and device) into a buffer of its own, searches the warped image
 // over the host's units, and blocks_deform_record_kernel behind blocks_record_kernel adds the field at every block's centre
-// to its record.
+// to its record.  mtm_match_blocks_passes_steered with steer = 1 steers those passes by refined positions: behind a pass
+// that steers another, blocks_steer_q8_kernel turns records and neighbourhoods into Q8 displacements and
+// blocks_smooth_q8_kernel filters them over the grid (the rule: mtm_blocks_steer.h) into the nodes the next pass's warp and
+// record kernels read - their Q8 instantiations; mtm_deform_image_q8 is the warp by Q8 nodes alone.
 // One of each: the tile body of the four score kernels (blocks_tile; the kernels supply the sink), the key's decoder
 // (mtm_quality_key.h: decode_block_keys on the host, blocks_record_kernel and blocks_nbhd_kernel on the device), the
 // record that steers (blocks_steer_record_inl).  Every entry point is a composition of the same host steps:
@@ -43,6 +46,7 @@
 #include "mtm_blocks_deform.h"
 #include "mtm_blocks_predict.h"
 #include "mtm_blocks_second.h"
+#include "mtm_blocks_steer.h"
 #include "mtm_blocks_validate.h"
 #include "mtm_ctx.h"
 #include "mtm_device_util.hip.h"
@@ -322,6 +326,8 @@ __global__ __launch_bounds__(256) void blocks_record_kernel(const TrackUnit* __r
 // displacements `disp` (deform_disp_kernel's pairs) at the block's doubled centre (deform_field_at_inl) goes into
 // pred[2 k], pred[2 k + 1] in Q8, and its rounded integer part is added to the record's position - found in the warped
 // image - so that recs[k] carries the block's displacement in the original image.  The position is not clamped.
+// Q8: the nodes are themselves in Q8 (steer = 1: blocks_smooth_q8_kernel's), else whole pixels.
+template <bool Q8>
 __global__ __launch_bounds__(256) void blocks_deform_record_kernel(const mtm_block* __restrict__ blocks, int n, BlockGrid coarse,
                                                                    const int32_t* __restrict__ disp, mtm_hit* __restrict__ recs,
                                                                    int32_t* __restrict__ pred) {
@@ -329,7 +335,7 @@ __global__ __launch_bounds__(256) void blocks_deform_record_kernel(const mtm_blo
     if (k >= n) return;
     const mtm_block B = blocks[k];
     long long fx, fy;
-    deform_field_at_inl(coarse, disp, 2ll * B.x + B.w - 1, 2ll * B.y + B.h - 1, &fx, &fy);
+    deform_field_at_of_inl<Q8>(coarse, disp, 2ll * B.x + B.w - 1, 2ll * B.y + B.h - 1, &fx, &fy);
     pred[2 * (size_t)k] = (int32_t)fx;
     pred[2 * (size_t)k + 1] = (int32_t)fy;
     recs[k].x += (int)deform_round_inl(fx);
@@ -349,6 +355,32 @@ __global__ __launch_bounds__(256) void blocks_validate_kernel(const mtm_hit* __r
     mtm_hit r;
     valid[k] = blocks_steer_record_inl(recs, nx, ny, sx, sy, k, threshold, e4, &r) ? 1 : 0;
     steer[k] = r;
+}
+
+// One lane per record k < nx ny of a pass that steers another by refined positions (steer = 1), behind the pass's records,
+// neighbourhoods and - with validation - flags: the record's steering displacement in Q8 (steer_d8_inl, mtm_blocks_steer.h:
+// the fitted position in the searched image plus the field that steered the pass, minus the block's position; an outlier's:
+// its neighbours' median) as a compact pair d8[2 k], d8[2 k + 1] - one 8-byte store.  Reads its own record only.
+__global__ __launch_bounds__(256) void blocks_steer_q8_kernel(const mtm_hit* __restrict__ recs, const float* __restrict__ nbhd,
+                                                              const int32_t* __restrict__ pred, const uint8_t* __restrict__ valid,
+                                                              const mtm_hit* __restrict__ steer, int nx, int ny, int sx, int sy,
+                                                              int mode_min, int32_t* __restrict__ d8) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nx * ny) return;
+    int32_t dx, dy;
+    steer_d8_inl(recs, nbhd, pred, valid, steer, nx, sx, sy, mode_min, k, &dx, &dy);
+    *reinterpret_cast<int2*>(d8 + 2 * (size_t)k) = make_int2(dx, dy);
+}
+
+// One lane per node k < nx ny: the predictor filter (steer_smooth_inl: 3 x 3 binomial, clamped indices) of the pairs d8
+// into `out` - another buffer, the one the warp reads -, so that no lane reads what another writes.
+__global__ __launch_bounds__(256) void blocks_smooth_q8_kernel(const int32_t* __restrict__ d8, int nx, int ny,
+                                                               int32_t* __restrict__ out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nx * ny) return;
+    int32_t sx8, sy8;
+    steer_smooth_inl(d8, nx, ny, k % nx, k / nx, &sx8, &sy8);
+    *reinterpret_cast<int2*>(out + 2 * (size_t)k) = make_int2(sx8, sy8);
 }
 
 // blocks_score_kernel's sibling for the ensemble planes of mtm_match_blocks_stack: the same tile and float32 score
@@ -465,6 +497,8 @@ struct BlockStage {
     const uint32_t* dtab = nullptr;
     size_t dtab_words = 0, warp_bytes = 0, disp_blocks = 0;
     bool deform = false;
+    // ... steered by refined positions: the largest steering grid's unfiltered Q8 displacements
+    size_t d8_blocks = 0;
 };
 BlockStage plan_stage(const mtm_block* blocks, const BlockPlan& P) {
     return BlockStage{blocks, P.toff.data(), P.units.data(), P.tiles.data(), P.units.size(), P.tiles.size(), P.max_bytes};
@@ -488,7 +522,8 @@ int stage_block_call(mtm_ctx* c, const BlockStage& S, Before&& before) {
         {c->blk_valid, S.validate ? n : 0},                 {c->blk_steer, S.validate ? sizeof(mtm_hit) * n : 0},
         {c->blk_plane, sizeof(float) * S.plane_floats},     {c->blk_keys2, S.poff ? sizeof(unsigned long long) * n : 0},
         {c->blk_recs2, S.poff ? sizeof(mtm_hit) * n : 0},   {c->blk_warp, S.warp_bytes},
-        {c->blk_disp, sizeof(int32_t) * 2 * S.disp_blocks}, {c->blk_pred, S.deform ? sizeof(int32_t) * 2 * n : 0}};
+        {c->blk_disp, sizeof(int32_t) * 2 * S.disp_blocks}, {c->blk_pred, S.deform ? sizeof(int32_t) * 2 * n : 0},
+        {c->blk_d8, sizeof(int32_t) * 2 * S.d8_blocks}};
     HIPC(hipSetDevice(c->device));
     c->timing = mtm_timing{};
     c->maps_valid = false;
@@ -743,8 +778,9 @@ ImageDev warp_view(const mtm_ctx* c, int rows, int cols, int chans) {
 }
 
 // The warp launch: `src` (its low-byte plane src_lo) warped into the call's blk_warp by the field of grid g with the
-// displacements in blk_disp and the tables at word `tab` of blk_dtab.
-int launch_deform(mtm_ctx* c, const ImageDev& src, const uint8_t* src_lo, int chans, int dtype, const BlockGrid& g, size_t tab) {
+// displacements in blk_disp - q8: Q8 nodes - and the tables at word `tab` of blk_dtab.
+int launch_deform(mtm_ctx* c, const ImageDev& src, const uint8_t* src_lo, int chans, int dtype, const BlockGrid& g, size_t tab,
+                  bool q8 = false) {
     const ImageDev dst = warp_view(c, src.rows, src.cols, chans);
     DeformArgs a{};
     a.src = src.u8;
@@ -765,15 +801,21 @@ int launch_deform(mtm_ctx* c, const ImageDev& src, const uint8_t* src_lo, int ch
     const dim3 grd((unsigned)((src.cols + kDeformLanesX * kDeformPx - 1) / (kDeformLanesX * kDeformPx)),
                    (unsigned)((src.rows + 256 / kDeformLanesX - 1) / (256 / kDeformLanesX)));
     return blocks_dispatch(dtype, chans, [&](auto ch, auto u16) -> int {
-        hipLaunchKernelGGL((deform_image_kernel<decltype(ch)::value, decltype(u16)::value>), grd, dim3(256), 0, c->stream, a);
+        if (q8)
+            hipLaunchKernelGGL((deform_image_kernel<decltype(ch)::value, decltype(u16)::value, true>), grd, dim3(256), 0, c->stream,
+                               a);
+        else
+            hipLaunchKernelGGL((deform_image_kernel<decltype(ch)::value, decltype(u16)::value>), grd, dim3(256), 0, c->stream, a);
         HIPC(hipGetLastError());
         return MTM_OK;
     });
 }
 
-// What a deformed call adds (mtm_match_blocks_passes_deformed): where the Q8 field at every block's centre goes, pass-major.
+// What a deformed call adds (mtm_match_blocks_passes_deformed): where the Q8 field at every block's centre goes, pass-major;
+// steer (mtm_match_blocks_passes_steered): 0 - integer records steer the next pass -, 1 - refined positions, filtered.
 struct BlockDeform {
     int32_t* predicted;
+    int steer = 0;
 };
 
 // The median test a validated call runs behind every pass: its threshold, e4 = 4 epsilon (computed once, exact), and where
@@ -800,6 +842,10 @@ struct BlockValidate {
 // blocks_deform_record_kernel behind blocks_record_kernel adds the field at every block's centre to its record, which is
 // what validation tests and what steers the next pass; the fields come back with the records.  D == nullptr launches and
 // copies exactly what the chain did before deformation existed.
+// D->steer == 1: every pass that steers another also gets its neighbourhoods (whether or not the caller asked for them),
+// blocks_steer_q8_kernel behind its records and flags turns them into Q8 steering displacements and
+// blocks_smooth_q8_kernel filters those into blk_disp - in place of deform_disp_kernel ahead of the next pass, whose warp
+// and record kernels then read Q8 nodes.  D->steer == 0 launches exactly the kernels it did before.
 struct BlockSecondOut {
     int exclusion;
     mtm_hit* second;
@@ -848,6 +894,10 @@ int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
             S.disp_blocks = std::max(S.disp_blocks, Q[p - 1].blocks.size());
         }
         S.deform = true;
+        if (D->steer && Q.size() > 1) {
+            S.d8_blocks = S.disp_blocks;
+            S.nbhd = true;
+        }
         S.dtab = dtab.empty() ? nullptr : dtab.data();
         S.dtab_words = dtab.size();
         if (Q.size() > 1) S.warp_bytes = warp_bytes(rows, (int)round_up((size_t)cols + kPadCols, 64), chans, dtype);
@@ -865,17 +915,19 @@ int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
         mtm_hit* recs = c->blk_recs.as<mtm_hit>() + b0;
         // what steers this pass: the previous pass's records, validated or raw
         const mtm_hit* prev = V ? c->blk_steer.as<mtm_hit>() + b0 : recs;
-        const bool warped = D && p > 0;
+        const bool warped = D && p > 0, q8 = D && D->steer, steers = q8 && p + 1 < Q.size();
         ImageDev wimg{};
         if (warped) {
             const BlockGrid& g = Q[p - 1].grid;
-            hipLaunchKernelGGL(deform_disp_kernel, dim3((unsigned)((Q[p - 1].blocks.size() + 255) / 256)), dim3(256), 0, c->stream,
-                               prev - Q[p - 1].blocks.size(), g, c->blk_disp.as<int32_t>());
-            HIPC(hipGetLastError());
+            if (!q8) {          // (q8: the pass before left its filtered Q8 nodes in blk_disp)
+                hipLaunchKernelGGL(deform_disp_kernel, dim3((unsigned)((Q[p - 1].blocks.size() + 255) / 256)), dim3(256), 0,
+                                   c->stream, prev - Q[p - 1].blocks.size(), g, c->blk_disp.as<int32_t>());
+                HIPC(hipGetLastError());
+            }
             const ImageDev st = image_dev(c);
             MTMC(launch_deform(c, stack_view(st, rows, rows),
                                c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane + (size_t)rows * st.u8_pitch, chans, dtype, g,
-                               dtab_at[p]));
+                               dtab_at[p], q8));
             wimg = warp_view(c, rows, cols, chans);
         } else if (p > 0 || offsets) {
             hipLaunchKernelGGL(blocks_unit_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.blocks, np,
@@ -888,14 +940,18 @@ int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
             X[p].keys2 = c->blk_keys2.as<unsigned long long>() + b0;
         }
         MTMC(blocks_pair(c, q.plan, B, rows, chans, dtype, method, 0, 1, true,
-                         BlockSink{keys, nbhd ? c->blk_nbhd.as<float>() + 9 * b0 : nullptr, 0, 0}, X2 ? &X[p] : nullptr,
+                         BlockSink{keys, nbhd || steers ? c->blk_nbhd.as<float>() + 9 * b0 : nullptr, 0, 0}, X2 ? &X[p] : nullptr,
                          warped ? &wimg : nullptr, warped ? wimg.u8 + wimg.u8_plane : nullptr));
         hipLaunchKernelGGL(blocks_record_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.units, keys, B.blocks, np, mode_min,
                            recs);
         HIPC(hipGetLastError());
         if (warped) {
-            hipLaunchKernelGGL(blocks_deform_record_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.blocks, np,
-                               Q[p - 1].grid, c->blk_disp.as<int32_t>(), recs, c->blk_pred.as<int32_t>() + 2 * b0);
+            if (q8)
+                hipLaunchKernelGGL(blocks_deform_record_kernel<true>, dim3(lanes_grid), dim3(256), 0, c->stream, B.blocks, np,
+                                   Q[p - 1].grid, c->blk_disp.as<int32_t>(), recs, c->blk_pred.as<int32_t>() + 2 * b0);
+            else
+                hipLaunchKernelGGL(blocks_deform_record_kernel<false>, dim3(lanes_grid), dim3(256), 0, c->stream, B.blocks, np,
+                                   Q[p - 1].grid, c->blk_disp.as<int32_t>(), recs, c->blk_pred.as<int32_t>() + 2 * b0);
             HIPC(hipGetLastError());
         }
         if (X2) {
@@ -907,6 +963,16 @@ int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
             hipLaunchKernelGGL(blocks_validate_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, recs, q.grid.nx, q.grid.ny,
                                q.grid.sx, q.grid.sy, V->threshold, V->e4, c->blk_valid.as<uint8_t>() + b0,
                                c->blk_steer.as<mtm_hit>() + b0);
+            HIPC(hipGetLastError());
+        }
+        if (steers) {   // (behind this pass's last reader of blk_disp: the filter may overwrite it)
+            hipLaunchKernelGGL(blocks_steer_q8_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, recs,
+                               c->blk_nbhd.as<float>() + 9 * b0, c->blk_pred.as<int32_t>() + 2 * b0,
+                               V ? c->blk_valid.as<uint8_t>() + b0 : nullptr, V ? c->blk_steer.as<mtm_hit>() + b0 : nullptr,
+                               q.grid.nx, q.grid.ny, q.grid.sx, q.grid.sy, mode_min, c->blk_d8.as<int32_t>());
+            HIPC(hipGetLastError());
+            hipLaunchKernelGGL(blocks_smooth_q8_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, c->blk_d8.as<int32_t>(),
+                               q.grid.nx, q.grid.ny, c->blk_disp.as<int32_t>());
             HIPC(hipGetLastError());
         }
         b0 += q.blocks.size();
@@ -1028,9 +1094,89 @@ int mtm_match_blocks_passes_deformed(mtm_ctx* c, const void* reference, int64_t 
     return match_block_passes(c, I, Q, nullptr, method, out, nbhd, valid ? &V : nullptr, nullptr, &D);
 }
 
-int mtm_deform_image(mtm_ctx* c, const void* px, int64_t row_stride_bytes, int rows, int cols, int chans, int dtype, int bw, int bh,
-                     int sx, int sy, const int32_t* displacements, void* out, int64_t out_stride_bytes) {
-    const char* who = "mtm_deform_image";
+int mtm_match_blocks_passes_steered(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                                    int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                                    const mtm_block_pass* passes, int n_passes, int method, double threshold, double epsilon,
+                                    mtm_hit* out, float* nbhd, uint8_t* valid, int32_t* predicted, int steer) {
+    const char* who = "mtm_match_blocks_passes_steered";
+    if (steer != 0 && steer != 1) {
+        set_error(std::string(who) + ": steer must be 0 (integer records) or 1 (refined positions) (got " + std::to_string(steer) +
+                  ")");
+        return MTM_E_INVALID;
+    }
+    if (steer == 0)
+        return mtm_match_blocks_passes_deformed(c, reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans,
+                                                dtype, passes, n_passes, method, threshold, epsilon, out, nbhd, valid, predicted);
+    if (valid) MTMC(check_validate_args(who, threshold, epsilon));
+    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
+    MTMC(check_block_pair(c, who, n_passes >= 1 && passes && out && predicted, method, I));
+    if ((long long)n_passes * std::max(rows, cols) > kDeformMaxDisp) {
+        set_error(std::string(who) + ": " + std::to_string(n_passes) + " passes over images of this size could pass the "
+                  "largest displacement the field takes (2^22 pixels)");
+        return MTM_E_INVALID;
+    }
+    std::vector<BlockPassPlan> Q;
+    MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
+    const BlockValidate V{threshold, 4.0 * epsilon, valid};
+    const BlockDeform D{predicted, 1};
+    return match_block_passes(c, I, Q, nullptr, method, out, nbhd, valid ? &V : nullptr, nullptr, &D);
+}
+
+int mtm_debug_steer_q8(mtm_ctx* c, const mtm_hit* recs, const float* nbhd, const int32_t* predicted, const uint8_t* valid,
+                       const mtm_hit* steer_recs, int nx, int ny, int sx, int sy, int mode_min, int smooth, int32_t* out_q8) {
+    const char* who = "mtm_debug_steer_q8";
+    if (!recs || !nbhd || !predicted || !out_q8 || (valid != nullptr) != (steer_recs != nullptr) || nx < 1 || ny < 1 || sx < 1 ||
+        sy < 1 || (long long)nx * ny > INT_MAX / 16) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    const size_t n = (size_t)nx * (size_t)ny;
+    mode_min = mode_min ? 1 : 0;
+    if (!c) {           // the rule itself, on the host
+        std::vector<int32_t> d8(2 * n);
+        for (int k = 0; k < (int)n; ++k)
+            steer_d8_inl(recs, nbhd, predicted, valid, steer_recs, nx, sx, sy, mode_min, k, &d8[2 * (size_t)k], &d8[2 * (size_t)k + 1]);
+        for (int k = 0; k < (int)n; ++k) {
+            if (smooth) steer_smooth_inl(d8.data(), nx, ny, k % nx, k / nx, &out_q8[2 * (size_t)k], &out_q8[2 * (size_t)k + 1]);
+            else out_q8[2 * (size_t)k] = d8[2 * (size_t)k], out_q8[2 * (size_t)k + 1] = d8[2 * (size_t)k + 1];
+        }
+        return MTM_OK;
+    }
+    MTM_NOT_IN_FLIGHT(c, who);
+    HIPC(hipSetDevice(c->device));
+    MTMC(c->blk_recs.ensure(sizeof(mtm_hit) * n));
+    MTMC(c->blk_nbhd.ensure(sizeof(float) * 9 * n));
+    MTMC(c->blk_pred.ensure(sizeof(int32_t) * 2 * n));
+    MTMC(c->blk_d8.ensure(sizeof(int32_t) * 2 * n));
+    MTMC(c->blk_disp.ensure(sizeof(int32_t) * 2 * n));
+    if (valid) {
+        MTMC(c->blk_valid.ensure(n));
+        MTMC(c->blk_steer.ensure(sizeof(mtm_hit) * n));
+        HIPC(hipMemcpyAsync(c->blk_valid.p, valid, n, hipMemcpyHostToDevice, c->stream));
+        HIPC(hipMemcpyAsync(c->blk_steer.p, steer_recs, sizeof(mtm_hit) * n, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPC(hipMemcpyAsync(c->blk_recs.p, recs, sizeof(mtm_hit) * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_nbhd.p, nbhd, sizeof(float) * 9 * n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->blk_pred.p, predicted, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    const dim3 grd((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(blocks_steer_q8_kernel, grd, dim3(256), 0, c->stream, c->blk_recs.as<mtm_hit>(), c->blk_nbhd.as<float>(),
+                       c->blk_pred.as<int32_t>(), valid ? c->blk_valid.as<uint8_t>() : nullptr,
+                       valid ? c->blk_steer.as<mtm_hit>() : nullptr, nx, ny, sx, sy, mode_min, c->blk_d8.as<int32_t>());
+    HIPC(hipGetLastError());
+    if (smooth) {
+        hipLaunchKernelGGL(blocks_smooth_q8_kernel, grd, dim3(256), 0, c->stream, c->blk_d8.as<int32_t>(), nx, ny,
+                           c->blk_disp.as<int32_t>());
+        HIPC(hipGetLastError());
+    }
+    HIPC(hipMemcpyAsync(out_q8, smooth ? c->blk_disp.p : c->blk_d8.p, sizeof(int32_t) * 2 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return MTM_OK;
+}
+
+// mtm_deform_image (q8 = false: whole-pixel displacements within +-2^22) and mtm_deform_image_q8 (Q8 ones within +-2^30).
+static int deform_image_entry(const char* who, bool q8, mtm_ctx* c, const void* px, int64_t row_stride_bytes, int rows, int cols,
+                              int chans, int dtype, int bw, int bh, int sx, int sy, const int32_t* displacements, void* out,
+                              int64_t out_stride_bytes) {
     if (!displacements || !out) {
         set_error(std::string(who) + ": bad arguments");
         return MTM_E_INVALID;
@@ -1048,8 +1194,9 @@ int mtm_deform_image(mtm_ctx* c, const void* px, int64_t row_stride_bytes, int r
         return MTM_E_INVALID;
     }
     const size_t n = (size_t)g.nx * (size_t)g.ny;
+    const long long dmax = q8 ? kDeformMaxDispQ8 : kDeformMaxDisp;
     for (size_t k = 0; k < 2 * n; ++k)
-        if (displacements[k] > kDeformMaxDisp || displacements[k] < -kDeformMaxDisp) {
+        if (displacements[k] > dmax || displacements[k] < -dmax) {
             set_error(std::string(who) + ": block " + std::to_string(k / 2) + ": displacement beyond 2^22 pixels");
             return MTM_E_INVALID;
         }
@@ -1059,7 +1206,8 @@ int mtm_deform_image(mtm_ctx* c, const void* px, int64_t row_stride_bytes, int r
             uint8_t* orow = (uint8_t*)out + (size_t)y * (size_t)out_stride_bytes;
             for (int x = 0; x < cols; ++x) {
                 long long fx, fy;
-                deform_field_at_inl(g, displacements, 2ll * x, 2ll * y, &fx, &fy);
+                if (q8) deform_field_at_of_inl<true>(g, displacements, 2ll * x, 2ll * y, &fx, &fy);
+                else deform_field_at_inl(g, displacements, 2ll * x, 2ll * y, &fx, &fy);
                 int x0, x1, wx, y0, y1, wy;
                 deform_sample_inl(x, fx, cols, &x0, &x1, &wx);
                 deform_sample_inl(y, fy, rows, &y0, &y1, &wy);
@@ -1098,7 +1246,7 @@ int mtm_deform_image(mtm_ctx* c, const void* px, int64_t row_stride_bytes, int r
     HIPC(hipMemcpyAsync(c->blk_dtab.p, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice, c->stream));
     const ImageDev src = image_dev(c);
     HIPC(hipEventRecord(c->ev[0], c->stream));                  // (the call's time is the warp kernel's)
-    MTMC(launch_deform(c, src, c->slot[c->cur].u8b.as<uint8_t>() + src.u8_plane, chans, dtype, g, 0));
+    MTMC(launch_deform(c, src, c->slot[c->cur].u8b.as<uint8_t>() + src.u8_plane, chans, dtype, g, 0, q8));
     HIPC(hipEventRecord(c->ev[1], c->stream));
     // the planes come back tightly packed; interleaved pixels are put together on the host
     const int np = dtype == MTM_U16 ? 2 : chans;
@@ -1121,6 +1269,18 @@ int mtm_deform_image(mtm_ctx* c, const void* px, int64_t row_stride_bytes, int r
         }
     }
     return MTM_OK;
+}
+
+int mtm_deform_image(mtm_ctx* c, const void* px, int64_t row_stride_bytes, int rows, int cols, int chans, int dtype, int bw, int bh,
+                     int sx, int sy, const int32_t* displacements, void* out, int64_t out_stride_bytes) {
+    return deform_image_entry("mtm_deform_image", false, c, px, row_stride_bytes, rows, cols, chans, dtype, bw, bh, sx, sy,
+                              displacements, out, out_stride_bytes);
+}
+
+int mtm_deform_image_q8(mtm_ctx* c, const void* px, int64_t row_stride_bytes, int rows, int cols, int chans, int dtype, int bw,
+                        int bh, int sx, int sy, const int32_t* displacements_q8, void* out, int64_t out_stride_bytes) {
+    return deform_image_entry("mtm_deform_image_q8", true, c, px, row_stride_bytes, rows, cols, chans, dtype, bw, bh, sx, sy,
+                              displacements_q8, out, out_stride_bytes);
 }
 
 int mtm_match_blocks_second(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,

@@ -62,6 +62,44 @@ MTM_HOST_DEVICE inline void deform_field_at_inl(const BlockGrid& g, const int32_
     *fy = deform_field_inl(p00[1], p01[1], p10[1], p11[1], ax, ay);
 }
 
+// The largest |Q8 node| of the sub-pixel fields below (mtm_deform_image_q8, steer = 1): the same 2^22 pixels.
+constexpr long long kDeformMaxDispQ8 = kDeformMaxDisp << 8;
+
+// deform_field_inl for nodes that are themselves in Q8 (1/256 pixel; |s| <= 2^30, so every product stays below 2^46):
+// the weights' 2^16 is divided out in one arithmetic shift, rounded half up.  For s = 256 d this is deform_field_inl(d),
+// bit for bit: (256 sum + 32768) >> 16 = (sum + 128) >> 8.
+MTM_HOST_DEVICE inline long long deform_field_q8_inl(int32_t s00, int32_t s01, int32_t s10, int32_t s11, int ax, int ay) {
+    const int32_t w00 = (256 - ax) * (256 - ay), w01 = ax * (256 - ay), w10 = (256 - ax) * ay, w11 = ax * ay;
+    return ((long long)s00 * w00 + (long long)s01 * w01 + (long long)s10 * w10 + (long long)s11 * w11 + 32768) >> 16;
+}
+
+// The field of either kind of node: Q8 nodes (deform_field_q8_inl) or whole pixels (deform_field_inl).
+template <bool Q8>
+MTM_HOST_DEVICE inline long long deform_field_of_inl(int32_t d00, int32_t d01, int32_t d10, int32_t d11, int ax, int ay) {
+    if constexpr (Q8) return deform_field_q8_inl(d00, d01, d10, d11, ax, ay);
+    else return deform_field_inl(d00, d01, d10, d11, ax, ay);
+}
+
+// deform_field_at_inl for either kind of node.
+template <bool Q8>
+MTM_HOST_DEVICE inline void deform_field_at_of_inl(const BlockGrid& g, const int32_t* d, long long X2, long long Y2, long long* fx,
+                                                   long long* fy) {
+    if constexpr (!Q8) {
+        deform_field_at_inl(g, d, X2, Y2, fx, fy);
+    } else {
+        int i, ax, j, ay;
+        deform_axis_inl(g.nx, g.sx, g.bw, X2, &i, &ax);
+        deform_axis_inl(g.ny, g.sy, g.bh, Y2, &j, &ay);
+        const int i1 = i + 1 < g.nx ? i + 1 : g.nx - 1, j1 = j + 1 < g.ny ? j + 1 : g.ny - 1;
+        const int32_t* p00 = d + 2 * ((long long)j * g.nx + i);
+        const int32_t* p01 = d + 2 * ((long long)j * g.nx + i1);
+        const int32_t* p10 = d + 2 * ((long long)j1 * g.nx + i);
+        const int32_t* p11 = d + 2 * ((long long)j1 * g.nx + i1);
+        *fx = deform_field_q8_inl(p00[0], p01[0], p10[0], p11[0], ax, ay);
+        *fy = deform_field_q8_inl(p00[1], p01[1], p10[1], p11[1], ax, ay);
+    }
+}
+
 // Along one axis of n pixels: the sample of output pixel x under field f (Q8) - the lower source pixel *x0, its
 // neighbour *x1 = min(*x0 + 1, n - 1) and the weight *w8 (0 .. 255) of the neighbour.  Replicated edges.
 MTM_HOST_DEVICE inline void deform_sample_inl(int x, long long f, int n, int* x0, int* x1, int* w8) {

@@ -399,6 +399,9 @@ struct mtm_ctx {
     // displacements of the pass that steers (8 B per block), the per-column and per-row weight tables of every deformed pass
     // and the field at every block's centre (Q8, 8 B per block, pass-major as blk_recs)
     DevBuf blk_warp, blk_disp, blk_dtab, blk_pred;
+    // mtm_match_blocks_passes_steered with steer = 1: the unfiltered Q8 steering displacements of the pass that steers (8 B
+    // per block; the filtered ones go into blk_disp)
+    DevBuf blk_d8;
     // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
     // template set sub_gen) and the per-call point table and scores.
     uint64_t sub_gen = 0;

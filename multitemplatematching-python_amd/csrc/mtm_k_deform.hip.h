@@ -49,7 +49,8 @@ __global__ __launch_bounds__(256) void deform_disp_kernel(const mtm_hit* __restr
 // (deform_sample_inl) and per plane four gathered bytes and their blend (deform_blend_inl); the field never reaches
 // memory.  Every source index is clamped into rows x cols by deform_sample_inl; a lane whose first pixel lies outside the
 // image leaves; the bytes of a lane's pixels right of the image are stored as zero (inside the pitch: pitch >= cols + 7).
-template <int CH, bool U16>
+// Q8: disp holds Q8 nodes (mtm_deform_image_q8, steer = 1) and the field is deform_field_q8_inl's; else whole pixels.
+template <int CH, bool U16, bool Q8 = false>
 __global__ __launch_bounds__(256) void deform_image_kernel(DeformArgs a) {
     constexpr int NP = U16 ? 2 : CH;        // byte planes written
     const int x0 = ((int)blockIdx.x * kDeformLanesX + ((int)threadIdx.x & (kDeformLanesX - 1))) * kDeformPx;
@@ -84,8 +85,8 @@ __global__ __launch_bounds__(256) void deform_image_kernel(DeformArgs a) {
                 d11 = *reinterpret_cast<const int2*>(n1 + 2 * (size_t)i1);
                 ci = i;
             }
-            const long long fx = deform_field_inl(d00.x, d01.x, d10.x, d11.x, ax, ay);
-            const long long fy = deform_field_inl(d00.y, d01.y, d10.y, d11.y, ax, ay);
+            const long long fx = deform_field_of_inl<Q8>(d00.x, d01.x, d10.x, d11.x, ax, ay);
+            const long long fy = deform_field_of_inl<Q8>(d00.y, d01.y, d10.y, d11.y, ax, ay);
             int sx0, sx1, wx, sy0, sy1, wy;
             deform_sample_inl(x, fx, a.cols, &sx0, &sx1, &wx);
             deform_sample_inl(y, fy, a.rows, &sy0, &sy1, &wy);

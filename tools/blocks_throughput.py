@@ -62,7 +62,15 @@ device-to-device copy of the image's bytes timed in the same run (``device_copy_
 workload's reference under a known shear and a known rotation (``warped_pair``), the mean last-pass score and the RMS error
 of the refined displacements against the known field over the blocks clear of the border, with and without ``deform``.
 
-Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F] [--passes [--validate | --deform]]
+--passes --deform --steer refined: a third pass, the dense one repeated - milliseconds per call of
+  undeformed - matchBlocksMultipass(...)
+  deformed   - matchBlocksMultipass(..., deform=True): integer records steer
+  steered    - matchBlocksMultipass(..., deform=True, steer="refined"): sub-pixel positions, filtered, steer
+with ``equal_to_loop`` (steered against the loop it documents), ``steer_cost_ms`` (steered - deformed) and, on the sheared
+and the rotated pair with 2 and 3 passes and (K1's row) on the tests' particle pair, ``rms_error_px`` of all three.
+
+Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F]
+       [--passes [--validate | --deform [--steer refined]]]
        [--second [r]]
 """
 import argparse
@@ -566,6 +574,99 @@ def run_passes_deform(MTM, spec, reps, warmup):
     }
 
 
+def run_passes_steer(MTM, spec, reps, warmup):
+    """--passes --deform --steer refined: three passes - the dense pass repeated - undeformed, with deform=True and steered
+    by refined positions (and steered with validation: the median test's kernel next to the two new ones in a kernel
+    trace), interleaved; the steered call against the loop it documents; the RMS error of the refined displacements of
+    all three on the sheared and the rotated pair with 2 and 3 passes, and (K1's row) on the tests' particle pair."""
+    from MTM import blocks as B
+    name, hw, chans, dtype, side, margin = spec
+    ref, img = workload(spec)
+    method = MTM.TM_CCOEFF_NORMED
+    dense = (side, side, max(1, margin // 4))
+    passes = [(side, 2 * side, margin), dense, dense]
+
+    def by_hand(r, i, pl):
+        out, S8, prev = [], None, None
+        for p, (block, step, m) in enumerate(pl):
+            b = B.grid(i.shape, block, step)
+            if p == 0:
+                searched, c = i, np.zeros((len(b), 2), np.int64)
+            else:
+                searched = B.deform(i, B.displacement_field(i.shape, prev, S8, q8=True))
+                c = B.field_at(i.shape, prev, S8, b, q8=True)
+            pos_w, sc = MTM.matchBlocks(r, searched, b, m, method)
+            fine_w, _ = MTM.matchBlocks(r, searched, b, m, method, refine=True)
+            D8 = B.to_q8(fine_w) - 256 * b[:, :2] + c
+            S8, prev = B.smooth_displacements(B.grid_shape(i.shape, block, step), D8), (block, step)
+            out.append((b, pos_w + ((c + 128) >> 8), sc, c / 256.0))
+        return out
+
+    methods = {
+        "undeformed": lambda: MTM.matchBlocksMultipass(ref, img, passes, method),
+        "deformed": lambda: MTM.matchBlocksMultipass(ref, img, passes, method, deform=True),
+        "steered": lambda: MTM.matchBlocksMultipass(ref, img, passes, method, deform=True, steer="refined"),
+        "steered_validated": lambda: MTM.matchBlocksMultipass(ref, img, passes, method, deform=True, steer="refined",
+                                                              validate=True),
+    }
+    results = {}
+    for k, fn in methods.items():
+        for _ in range(warmup):
+            results[k] = fn()
+    ms = {k: [] for k in methods}
+    for _ in range(reps):
+        for k, fn in methods.items():
+            t0 = time.perf_counter()
+            fn()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+
+    def same(x, y):
+        return len(x) == len(y) and all(bool((a[0] == b[0]).all() and (a[1] == b[1]).all() and a[2].tobytes() == b[2].tobytes()
+                                             and (a[-1] == b[-1]).all()) for a, b in zip(x, y))
+
+    calls = (("rigid", {}), ("deformed", {"deform": True}), ("steered", {"deform": True, "steer": "refined"}))
+    motion = {}
+    for kind in ("shear", "rotation"):
+        r, i, field = warped_pair(spec, kind)
+        for n_passes in (2, 3):
+            pl = passes[:n_passes]
+            row = {"equal_to_loop": same(MTM.matchBlocksMultipass(r, i, pl, method, deform=True, steer="refined"), by_hand(r, i, pl))}
+            for key, kw in calls:
+                b, pos, sc = MTM.matchBlocksMultipass(r, i, pl, method, refine=True, **kw)[-1][:3]
+                x, y, w, h = (b[:, j] for j in range(4))
+                inner = (x >= 2 * side) & (y >= 2 * side) & (x + 3 * side <= hw[1]) & (y + 3 * side <= hw[0])
+                fx, fy = field(x + (w - 1) / 2.0, y + (h - 1) / 2.0)
+                err = (pos - b[:, :2]) - np.stack((fx, fy), axis=1)
+                row[key] = {"mean_score": round(float(sc[inner].mean()), 4),
+                            "rms_error_px": round(float(np.sqrt((err[inner] ** 2).sum(axis=1).mean())), 4)}
+            row["blocks_counted"] = int(inner.sum())
+            motion["%s_%d_passes" % (kind, n_passes)] = row
+    out = {
+        "workload": name, "image": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype),
+        "passes": [[b, st, m] for b, st, m in passes], "pass_blocks": [int(len(r[0])) for r in results["steered"]],
+        "ms": {k: round(v, 3) for k, v in med.items()},
+        "ms_min": {k: round(min(v), 3) for k, v in ms.items()},
+        "ms_max": {k: round(max(v), 3) for k, v in ms.items()},
+        "deform_cost_ms": round(med["deformed"] - med["undeformed"], 3),
+        "steer_cost_ms": round(med["steered"] - med["deformed"], 3),
+        "equal_to_loop": same(results["steered"], by_hand(ref, img, passes)),
+        "motion": motion, "reps": reps,
+    }
+    if name == "K1":
+        for p in (os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+            if p not in sys.path:
+                sys.path.insert(0, p)
+        import blocks_steer_model as S
+        pr, pi = S.particle_pair()
+        out["particle_pair"] = {}
+        for n_passes in (2, 3, 6):
+            pl = S.PARTICLE_PASSES[:2] + S.PARTICLE_PASSES[1:2] * (n_passes - 2)
+            rms = S.three_rms(pr, pi, passes=pl)
+            out["particle_pair"]["%d_passes" % n_passes] = dict(zip(("rigid", "deformed", "steered"), (round(v, 4) for v in rms)))
+    return out
+
+
 def run_second(MTM, spec, reps, warmup, radius, passes_form):
     """--second: the call with and without the second peak, interleaved; the second peaks against the brute-force model of
     tests/blocks_second_model.py over MTM.computeScoreMap of every block and its box."""
@@ -631,7 +732,11 @@ def main():
     ap.add_argument("--second", type=int, nargs="?", const=2, default=None, metavar="r",
                     help="the second peak with exclusion radius r (default 2): the pair call, or with --passes the passes")
     ap.add_argument("--deform", action="store_true", help="with --passes: window deformation between the passes")
+    ap.add_argument("--steer", choices=["integer", "refined"], default="integer",
+                    help="with --passes --deform: refined = the deformed passes steered by sub-pixel positions, three passes")
     args = ap.parse_args()
+    if args.steer == "refined" and not args.deform:
+        ap.error("--steer refined goes with --passes --deform")
     if args.validate and not args.passes:
         ap.error("--validate goes with --passes")
     if args.deform and (not args.passes or args.validate or args.second is not None):
@@ -646,6 +751,8 @@ def main():
             continue
         if args.second is not None:
             print(json.dumps(run_second(MTM, spec, args.reps, args.warmup, args.second, args.passes)), flush=True)
+        elif args.passes and args.deform and args.steer == "refined":
+            print(json.dumps(run_passes_steer(MTM, spec, args.reps, args.warmup)), flush=True)
         elif args.passes and args.deform:
             print(json.dumps(run_passes_deform(MTM, spec, args.reps, args.warmup)), flush=True)
         elif args.passes and args.validate:

@@ -1291,40 +1291,28 @@ class Context(_RecordMemo):
         pair, keep = self._pair_args(reference, image)
         if steer and not deform:
             raise ValueError("match_blocks_passes: steer needs deform")
-        if deform:
-            if second is not None:
-                raise ValueError("match_blocks_passes: deform does not go with second")
-            threshold, epsilon = validate if validate is not None else (0.0, 0.0)
-            valid = np.zeros(n, dtype=np.uint8) if validate is not None else None
-            pred = np.zeros((n, 2), dtype=np.int32)
-            tail = (passes.ctypes.data, len(passes), int(method), float(threshold), float(epsilon), out.ctypes.data,
-                    nbhd.ctypes.data if with_nbhd else None, None if valid is None else valid.ctypes.data, pred.ctypes.data)
-            if steer:
-                check(self._lib.mtm_match_blocks_passes_steered(*pair, *tail, int(steer)), "mtm_match_blocks_passes_steered")
-            else:
-                check(self._lib.mtm_match_blocks_passes_deformed(*pair, *tail), "mtm_match_blocks_passes_deformed")
-            return (out, nbhd, pred) if valid is None else (out, nbhd, valid.astype(bool), pred)
-        if second is not None:
-            threshold, epsilon = validate if validate is not None else (0.0, 0.0)
-            valid = np.zeros(n, dtype=np.uint8) if validate is not None else None
-            out2 = np.empty(n, dtype=HIT_DTYPE)
-            check(self._lib.mtm_match_blocks_passes_second(*pair, passes.ctypes.data, len(passes), int(method), float(threshold),
-                                                           float(epsilon), out.ctypes.data,
-                                                           nbhd.ctypes.data if with_nbhd else None,
-                                                           None if valid is None else valid.ctypes.data, int(second),
-                                                           out2.ctypes.data), "mtm_match_blocks_passes_second")
-            return (out, nbhd, out2) if valid is None else (out, nbhd, valid.astype(bool), out2)
-        if validate is not None:
-            threshold, epsilon = validate
-            valid = np.zeros(n, dtype=np.uint8)
-            check(self._lib.mtm_match_blocks_passes_validated(*pair, passes.ctypes.data, len(passes), int(method),
-                                                              float(threshold), float(epsilon), out.ctypes.data,
-                                                              nbhd.ctypes.data if with_nbhd else None, valid.ctypes.data),
-                  "mtm_match_blocks_passes_validated")
-            return out, nbhd, valid.astype(bool)
-        check(self._lib.mtm_match_blocks_passes(*pair, passes.ctypes.data, len(passes), int(method), out.ctypes.data,
-                                                nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks_passes")
-        return out, nbhd
+        if deform and second is not None:
+            raise ValueError("match_blocks_passes: deform does not go with second")
+        threshold, epsilon = validate if validate is not None else (0.0, 0.0)
+        valid = np.zeros(n, dtype=np.uint8) if validate is not None else None
+        last = np.zeros((n, 2), dtype=np.int32) if deform else np.empty(n, dtype=HIT_DTYPE) if second is not None else None
+        ptr = lambda a: None if a is None else a.ctypes.data     # noqa: E731
+        # the native entry, the first that applies: (asked for, its suffix, what follows `valid` in its arguments; None: the
+        # plain entry, which takes no median test either)
+        suffix, tail = next((s, t) for on, s, t in ((steer, "_steered", lambda: (ptr(last), int(steer))),
+                                                    (deform, "_deformed", lambda: (ptr(last),)),
+                                                    (second is not None, "_second", lambda: (int(second), ptr(last))),
+                                                    (validate is not None, "_validated", tuple),
+                                                    (True, "", None)) if on)
+        name = "mtm_match_blocks_passes" + suffix
+        args = pair + (passes.ctypes.data, len(passes), int(method))
+        if tail is None:
+            args += (ptr(out), ptr(nbhd))
+        else:
+            args += (float(threshold), float(epsilon), ptr(out), ptr(nbhd), ptr(valid)) + tail()
+        check(getattr(self._lib, name)(*args), name)
+        # out, nbhd, [valid], [second | predicted]
+        return (out, nbhd) + (() if valid is None else (valid.astype(bool),)) + (() if last is None else (last,))
 
     def match_blocks_stack(self, frames, blocks, margin, method, mode, with_nbhd=False, planes=False):
         """matchBlocks over the pairs of a frame stack in one native call (mtm_match_blocks_stack): pair p searches

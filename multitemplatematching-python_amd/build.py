@@ -28,7 +28,7 @@ SOURCES = ["mtm_context.hip", "mtm_placement.hip", "mtm_launch.hip", "mtm_api.hi
 HEADERS = ["mtm_ctx.h", "mtm_k_image.hip.h", "mtm_k_stats.hip.h", "mtm_k_score.hip.h", "mtm_k_peaks.hip.h", "mtm_score_params.h",
            "mtm_templates_params.h", "mtm_device_util.hip.h", "mtm_mfma.hip.h", "mtm_mfma_kloop.hip.h", "mtm_mfma_epilogue.hip.h", "mtm_mfma_finish.hip.h", "mtm_mfma_params.h", "mtm_templates.hip.h",
            "mtm_bf16.hip.h", "mtm_bf16_params.h", "mtm_refine.hip.h", "mtm_mfma_step_asm.inc", "mtm_kernels.h", "mtm_internal.h",
-           "mtm_k_nms.hip.h", "mtm_nms_core.h", "mtm_peak_sizing.h", "mtm_stats_route.h", "mtm_k_window.hip.h", "mtm_k_nbhd.hip.h", "mtm_route.h", "mtm_templ_stats.h", "mtm_blocks_predict.h", "mtm_blocks_validate.h", "mtm_blocks_second.h", "mtm_quality_key.h", "mtm_blocks_deform.h", "mtm_k_deform.hip.h", "mtm_maskf32.hip.h", "mtm_blocks_steer.h",
+           "mtm_k_nms.hip.h", "mtm_nms_core.h", "mtm_peak_sizing.h", "mtm_stats_route.h", "mtm_k_window.hip.h", "mtm_k_nbhd.hip.h", "mtm_route.h", "mtm_templ_stats.h", "mtm_blocks_predict.h", "mtm_blocks_validate.h", "mtm_blocks_second.h", "mtm_quality_key.h", "mtm_blocks_deform.h", "mtm_k_deform.hip.h", "mtm_maskf32.hip.h", "mtm_blocks_steer.h", "mtm_k_blocks.hip.h",
            os.path.join("..", "..", "include", "mtm_hip.h")]
 # -save-temps=obj: the device assembly of every unit stays next to its object (csrc/build/*-gfx950.s) - what
 # tools/spill_exec_scan.py and tests/test_abi_cpu.py::test_no_spill_ahead_of_an_exec_restore read (this compiler

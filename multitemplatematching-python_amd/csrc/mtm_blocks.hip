@@ -1,446 +1,30 @@
 // libmtm_hip.so - block matching between two images of one shape in one call (mtm_match_blocks): every block
 // of the reference image is a template, searched in the other image inside the block's own box widened by a margin - what
-// mtm_find_matches_boxes returns in MTM_PEAKS_GLOBAL mode for the block's pixels set as a template.  The templates never
-// exist on the host: both images go up as one stack of two (the reference in rows 0 .., the image below it),
-// blocks_gather_kernel cuts every block out of the reference's planes into planes of the call's own - the layout
-// prepare_window_templates gives a template set - and computes the constants mtm_set_templates would give it
-// (templ_stats_from_sums_inl, the single source of host and device); blocks_score_kernel scores the tiles of every block's
-// map with the window kernels' tile scorer (win_score_tile, mtm_k_window.hip.h: the exhaustive map's float32 bits) and
-// keeps each block's extremum in a key, no map is written; blocks_nbhd_kernel, where asked for, decodes the keys and
-// scores the 3 x 3 neighbourhoods in the whole image's map.  plan_blocks (mtm_host.cpp) checks the blocks and lays out
-// the unit and tile tables and the chunks; the host waits once per call.  uint8 (1 or 3 channels) and single-channel
-// uint16.  The template set of the context is neither read nor written.
-// mtm_match_blocks_stack runs the same chain for every pair of a frame stack: the frames go up in stacked
-// chunks (plan_blocks_stack, mtm_host.cpp), every pair has a row of keys of its own, and - ensemble planes - blocks_plane_kernel
-// adds every output's score to the block's plane of float64 sums instead of keeping an extremum.
-// mtm_match_blocks_at and mtm_match_blocks_passes search boxes that follow a displacement - uploaded
-// offsets, or the previous pass's records -: blocks_unit_kernel computes every block's unit on the device
-// (mtm_blocks_predict.h, the single source of host and device), blocks_score_fixed_kernel runs blocks_score_kernel's tile
-// over a fixed tile table and leaves the tiles outside the unit's map, blocks_record_kernel decodes the keys into records
-// on the device, which the next pass and the final copy read.  One chain (match_block_passes) behind both; every pass has
-// its own row of keys, records and neighbourhoods.
-// mtm_match_blocks_passes_validated runs the same chain with blocks_validate_kernel behind every pass's
-// blocks_record_kernel: the median test of mtm_blocks_validate.h (the single source of host and device) over the pass's
-// records, a flag per record and the records that steer the next pass instead of the raw ones.
-// mtm_match_blocks_second and mtm_match_blocks_passes_second add every block's second correlation peak to that
-// chain: blocks_score_plane_kernel - blocks_score_fixed_kernel with a sink that also stores the float32 scores - fills the
-// planes of one sub-range of whole blocks, blocks_second_kernel reduces each plane to the best key outside the exclusion
-// window around the first peak (mtm_blocks_second.h, the single source of host and device), and
-// blocks_second_record_kernel decodes those keys behind blocks_record_kernel; the records come back behind the same wait.
-// mtm_match_blocks_passes_deformed and mtm_deform_image add window deformation: a pass p >= 1 warps the
-// original image by the field of the records that steer it (deform_disp_kernel, deform_image_kernel: mtm_k_deform.hip.h;
-// the rule: mtm_blocks_deform.h, the single source of host and device) into a buffer of its own, searches the warped image
-// over the host's units, and blocks_deform_record_kernel behind blocks_record_kernel adds the field at every block's centre
-// to its record.  mtm_match_blocks_passes_steered with steer = 1 steers those passes by refined positions: behind a pass
-// that steers another, blocks_steer_q8_kernel turns records and neighbourhoods into Q8 displacements and
-// blocks_smooth_q8_kernel filters them over the grid (the rule: mtm_blocks_steer.h) into the nodes the next pass's warp and
-// record kernels read - their Q8 instantiations; mtm_deform_image_q8 is the warp by Q8 nodes alone.
-// One of each: the tile body of the four score kernels (blocks_tile; the kernels supply the sink), the key's decoder
-// (mtm_quality_key.h: decode_block_keys on the host, blocks_record_kernel and blocks_nbhd_kernel on the device), the
-// record that steers (blocks_steer_record_inl).  Every entry point is a composition of the same host steps:
-// check_block_entry / check_block_pair, stage_block_call (buffers, the call's clock, uploads), blocks_pair (a pair's
-// launch chain, the one place its kernels are launched), finish_block_call (copies back, the single wait, timing).
+// mtm_find_matches_boxes returns in MTM_PEAKS_GLOBAL mode for the block's pixels set as a template.  Both images go up as
+// one stack of two (the reference in rows 0 .., the image below it); the kernels are mtm_k_blocks.hip.h's (and
+// mtm_k_deform.hip.h's), this file is the host side: plan_blocks (mtm_host.cpp) checks the blocks and lays out the unit
+// and tile tables and the chunks; the host waits once per call.  uint8 (1 or 3 channels) and single-channel uint16.  The
+// template set of the context is neither read nor written.
+// mtm_match_blocks_stack runs the same chain for every pair of a frame stack, which goes up in stacked
+// chunks (plan_blocks_stack, mtm_host.cpp); every pair has a row of keys of its own, or - ensemble planes - a plane of sums.
+// mtm_match_blocks_at / _second and the five mtm_match_blocks_passes* entries search boxes that
+// follow a displacement - uploaded offsets, or the previous pass's records.  Each entry fills one record of what is asked
+// for and where results go (BlockPassCall: validation, second peaks, deformation, steering; an absent feature is an empty
+// field) behind one of two preambles (block_passes_entry, block_single_entry), and one chain runs it (match_block_passes):
+// stage_block_passes (the passes' tables concatenated, second-peak sub-ranges, deform tables, stage_block_call), then per
+// pass block_pass_view (the pass's device pointers and what it does, derived once), pass_search (the units it searches,
+// or the warped image), blocks_pair, pass_records (record, deform-record, second-record, validate) and pass_handover
+// (steer-q8, smooth), in stream order; every pass has its own row of keys, records and neighbourhoods.
+// Every entry point composes the same host steps: check_block_entry / check_block_pair, stage_block_call (buffers, the
+// call's clock, uploads), blocks_pair (a pair's launch chain, the one place its kernels are launched), launch_lanes (the
+// one-lane-per-block launches), finish_block_call (copies back, the single wait, timing); debug entries: debug_block_run.
 #include <climits>
 #include <type_traits>
 
-#include "mtm_blocks_deform.h"
-#include "mtm_blocks_predict.h"
-#include "mtm_blocks_second.h"
-#include "mtm_blocks_steer.h"
-#include "mtm_blocks_validate.h"
-#include "mtm_ctx.h"
-#include "mtm_device_util.hip.h"
-#include "mtm_k_deform.hip.h"
-#include "mtm_k_nbhd.hip.h"
-#include "mtm_k_window.hip.h"
-#include "mtm_templ_stats.h"
+#include "mtm_k_blocks.hip.h"
 
 using namespace mtm;
 using namespace mtmi;
-
-namespace mtm {
-
-static_assert(kTrackTile == kWinTile, "plan_blocks tiles the maps as the window kernels walk them");
-
-// Grid: one 256-thread work-group per block (launch slice; block k = k0 + blockIdx.x).  `ref` is the reference image - the
-// stack's planes entered at its first row and bounded by its own `rows` -: uint8, plane c at ref.u8 + c * u8_plane;
-// uint16, the high-byte plane with `lo_b` the low-byte plane XOR 0x80.  The block's window is copied into the call's
-// template planes at tpx + toff[k] - uint8: [CH][h][w], tightly packed; uint16: the high-byte plane, then the low-byte
-// plane, unbiased - and the sums of its pixels and of their squares per channel are reduced in uint64 (exact: at most 2^21
-// uint16 pixels, sum v^2 < 2^53) in a fixed order; thread 0 writes the constants templ_stats_from_sums_inl gives for them -
-// what mtm_set_templates would compute for the block set as a template - and the block's size into td[k] (the fields
-// prepare_box_td fills; the others are zero).  A block that is not inside the reference is left alone (plan_blocks
-// refuses it: a window that did not lie inside would be read out of bounds).
-template <int CH, bool U16>
-__global__ __launch_bounds__(256) void blocks_gather_kernel(ImageDev ref, const uint8_t* __restrict__ lo_b,
-                                                            const mtm_block* __restrict__ blocks, int k0,
-                                                            uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
-                                                            TemplDev* __restrict__ td, int method) {
-    __shared__ unsigned long long red[4];
-    const int k = k0 + (int)blockIdx.x;
-    const mtm_block B = blocks[k];
-    const int h = B.h, w = B.w;
-    // (the same for the whole work-group: before any barrier)
-    if (w < 1 || h < 1 || B.x < 0 || B.y < 0 || B.x > ref.cols - w || B.y > ref.rows - h) return;
-    const int tid = threadIdx.x;
-    const uint32_t n = (uint32_t)h * (uint32_t)w;           // (< 2^31: plan_blocks)
-    uint8_t* tp = tpx + toff[k];
-    const size_t base = (size_t)B.y * ref.u8_pitch + (size_t)B.x;
-    unsigned long long s1[CH], s2[CH];
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-        s1[c] = 0ull;
-        s2[c] = 0ull;
-        for (uint32_t p = (uint32_t)tid; p < n; p += 256u) {
-            const size_t ip = base + (size_t)(p / (uint32_t)w) * ref.u8_pitch + (size_t)(p % (uint32_t)w);
-            uint32_t v;
-            if constexpr (U16) {
-                const uint32_t hi = ref.u8[ip], lo = (uint32_t)lo_b[ip] ^ 0x80u;
-                tp[p] = (uint8_t)hi;
-                tp[(size_t)n + p] = (uint8_t)lo;
-                v = (hi << 8) | lo;
-            } else {
-                v = ref.u8[(size_t)c * ref.u8_plane + ip];
-                tp[(size_t)c * n + p] = (uint8_t)v;
-            }
-            s1[c] += v;
-            s2[c] += (unsigned long long)v * v;
-        }
-    }
-    double sum[kMaxChans] = {0.0, 0.0, 0.0, 0.0}, sumsq[kMaxChans] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-        sum[c] = (double)sub_reduce(s1[c], red);
-        sumsq[c] = (double)sub_reduce(s2[c], red);
-    }
-    if (tid == 0) {
-        const TemplStats st = templ_stats_from_sums_inl(sum, sumsq, 0.0, false, h, w, CH, method);
-        TemplDev T{};
-#pragma unroll
-        for (int c = 0; c < kMaxChans; ++c) T.mean[c] = st.mean[c];
-        T.templ_norm = st.templ_norm;
-        T.templ_sum2 = st.templ_sum2;
-        T.all_ones = st.all_ones;
-        T.rows = h;
-        T.cols = w;
-        td[k] = T;
-    }
-}
-
-// The tile body of the three score kernels below, one work-group per tile of the launch's part of the tile table.  `img` is
-// the searched image, entered and bounded as `ref` above: no row of the reference is read.  The windows of tile (ty0, tx0)
-// of block u0's map are summed and scored by win_score_tile - boxes_score_kernel's float32 bits, the same function -, with
-// the gathered template of the block, and every lane's output goes to sink(K, U, inside, y, x, score) instead of a map.
-// MAY_LIE_OUTSIDE: the fixed table (fix_block_tiles) over units that a kernel computed - a tile outside its unit's clipped
-// map leaves before any barrier, the test being the same for the whole work-group (track_score_kernel's rule); else
-// every tile lies inside its map (plan_blocks).  A (2 margin + 1)^2 map fills only part of its tiles.
-template <int CH, bool U16, bool MAY_LIE_OUTSIDE, class Sink>
-__device__ __forceinline__ void blocks_tile(WinTemplLds (&Tl)[U16 ? 2 : 1], WinImageLds (&Il)[U16 ? 2 : 1], const ImageDev& img,
-                                            const uint8_t* __restrict__ lo_b, const uint8_t* __restrict__ tpx,
-                                            const long long* __restrict__ toff, const TemplDev* __restrict__ td,
-                                            const TrackUnit* __restrict__ units, const TrackTile* __restrict__ tiles,
-                                            int method, Sink&& sink) {
-    const TrackTile K = tiles[blockIdx.x];
-    const TrackUnit U = units[K.u0];
-    if constexpr (MAY_LIE_OUTSIDE)
-        if (K.ty0 >= U.oh || K.tx0 >= U.ow) return;     // (the same for the whole work-group: before any barrier)
-    const TemplDev T = td[K.u0];
-    win_score_tile<CH, U16>(Tl, Il, img, lo_b, tpx + toff[K.u0], T, U.y0 + K.ty0, U.x0 + K.tx0, K.ty0, K.tx0, U.oh, U.ow, method,
-                            [&](bool inside, int y, int x, auto&& score) { sink(K, U, inside, y, x, score); });
-}
-
-// The sink of the two key kernels: the tile's best output goes into keys[u0] (win_merge_key): order(quality) << 32 |
-// ~index, one atomicMax per wave.
-struct BlocksKeySink {
-    int mode_min;
-    unsigned long long* __restrict__ keys;
-    template <class Score>
-    __device__ __forceinline__ void operator()(const TrackTile& K, const TrackUnit& U, bool inside, int y, int x,
-                                               Score&& score) const {
-        win_merge_key(inside, win_pos_word(y, x, U.ow), mode_min, score, keys + K.u0);
-    }
-};
-
-// Each block's extremum as a key, over the plan's own tile table (blocks_tile, BlocksKeySink).
-template <int CH, bool U16>
-__global__ __launch_bounds__(256) void blocks_score_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
-                                                           const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
-                                                           const TemplDev* __restrict__ td, const TrackUnit* __restrict__ units,
-                                                           const TrackTile* __restrict__ tiles, int method, int mode_min,
-                                                           unsigned long long* __restrict__ keys) {
-    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
-    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
-    blocks_tile<CH, U16, false>(Tl, Il, img, lo_b, tpx, toff, td, units, tiles, method, BlocksKeySink{mode_min, keys});
-}
-
-// blocks_score_kernel over a FIXED tile table (fix_block_tiles, mtm_host.cpp: ceil((2 margin + 1) / 16)^2 tiles per
-// block) for units that a kernel computed (blocks_unit_kernel): the same body and sink, with the early exit.  No LDS and
-// no scratch over blocks_score_kernel.
-template <int CH, bool U16>
-__global__ __launch_bounds__(256) void blocks_score_fixed_kernel(
-    ImageDev img, const uint8_t* __restrict__ lo_b, const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
-    const TemplDev* __restrict__ td, const TrackUnit* __restrict__ units, const TrackTile* __restrict__ tiles, int method,
-    int mode_min, unsigned long long* __restrict__ keys) {
-    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
-    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
-    blocks_tile<CH, U16, true>(Tl, Il, img, lo_b, tpx, toff, td, units, tiles, method, BlocksKeySink{mode_min, keys});
-}
-
-// BlocksKeySink that also keeps the scores: an inside lane calls score() once, stores the float32 at cell (y, x) of block
-// u0's plane - plane[poff[u0] + y U.ow + x], the map row-major and contiguous - and feeds the same value to win_merge_key,
-// so the key is BlocksKeySink's.  A plain store: the tile table partitions a map, every cell has one writer.
-struct BlocksScoredPlaneSink {
-    int mode_min;
-    unsigned long long* __restrict__ keys;
-    float* __restrict__ plane;
-    const long long* __restrict__ poff;
-    template <class Score>
-    __device__ __forceinline__ void operator()(const TrackTile& K, const TrackUnit& U, bool inside, int y, int x,
-                                               Score&& score) const {
-        float s = 0.0f;
-        if (inside) {
-            s = score();
-            plane[(size_t)poff[K.u0] + (size_t)y * (size_t)U.ow + (size_t)x] = s;
-        }
-        win_merge_key(inside, win_pos_word(y, x, U.ow), mode_min, [&] { return s; }, keys + K.u0);
-    }
-};
-
-// blocks_score_fixed_kernel with the scored-plane sink (the second-peak calls; their tables are always the fixed ones): the
-// same body, LDS and keys, and every output of every unit's map lands in the unit's plane for blocks_second_kernel.  The
-// plane of block u0 holds at least U.oh U.ow floats whatever unit the device computed (second_plane_floats).
-template <int CH, bool U16>
-__global__ __launch_bounds__(256) void blocks_score_plane_kernel(
-    ImageDev img, const uint8_t* __restrict__ lo_b, const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
-    const TemplDev* __restrict__ td, const TrackUnit* __restrict__ units, const TrackTile* __restrict__ tiles, int method,
-    int mode_min, unsigned long long* __restrict__ keys, float* __restrict__ plane, const long long* __restrict__ poff) {
-    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
-    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
-    blocks_tile<CH, U16, true>(Tl, Il, img, lo_b, tpx, toff, td, units, tiles, method,
-                               BlocksScoredPlaneSink{mode_min, keys, plane, poff});
-}
-
-// Grid: one 256-thread work-group per block (launch slice; block k = k0 + blockIdx.x), behind the score launch that wrote
-// the block's plane: the largest key among the cells of the unit's oh x ow map outside the exclusion of radius
-// `exclusion` around the first peak (keys[k], decoded by key_index) goes into keys2[k] - second_excluded and
-// second_cell_key (mtm_blocks_second.h, the host's functions).  Lanes walk idx = tid, tid + 256, .. < oh ow: coalesced
-// loads of cells the score launch wrote, nothing outside the map is read; per wave the shuffle ladder of win_merge_key,
-// then the four waves through 32 B of LDS.  A block without a key reads nothing; keys2[k] is written either way (0: no
-// second peak).
-__global__ __launch_bounds__(256) void blocks_second_kernel(const TrackUnit* __restrict__ units,
-                                                            const unsigned long long* __restrict__ keys,
-                                                            const float* __restrict__ plane, const long long* __restrict__ poff,
-                                                            int k0, int mode_min, int exclusion,
-                                                            unsigned long long* __restrict__ keys2) {
-    __shared__ unsigned long long red[4];
-    const int k = k0 + (int)blockIdx.x;
-    const int tid = threadIdx.x;
-    const unsigned long long first = keys[k];
-    if (first == 0ull) {                                    // (the same for the whole work-group: before any barrier)
-        if (tid == 0) keys2[k] = 0ull;
-        return;
-    }
-    const TrackUnit U = units[k];
-    const uint32_t ow = (uint32_t)U.ow, n = (uint32_t)U.oh * ow;     // (< 2^32: plan_blocks, fix_block_tiles)
-    const uint32_t at = key_index(first);
-    const int py = (int)(at / ow), px = (int)(at % ow);
-    const float* __restrict__ m = plane + poff[k];
-    // the lane's cell (y, x) steps by 256 cells: 256 / ow rows and 256 % ow columns, with one carry
-    const uint32_t sy = 256u / ow, sx = 256u % ow;
-    uint32_t y = (uint32_t)tid / ow, x = (uint32_t)tid % ow;
-    unsigned long long best = 0ull;
-    for (unsigned long long idx = (unsigned long long)tid; idx < (unsigned long long)n; idx += 256ull) {
-        if (!second_excluded((int)y, (int)x, py, px, exclusion)) {
-            const unsigned long long key = second_cell_key(m[idx], mode_min, (uint32_t)idx);
-            best = key > best ? key : best;
-        }
-        y += sy;
-        x += sx;
-        if (x >= ow) {
-            x -= ow;
-            ++y;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off);
-        best = o > best ? o : best;
-    }
-    if ((tid & 63) == 0) red[tid >> 6] = best;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long b = red[0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) b = red[w] > b ? red[w] : b;
-        keys2[k] = b;
-    }
-}
-
-// blocks_record_kernel for the second keys: second_key_record (mtm_blocks_second.h) at the unit's origin into recs2[k] -
-// a block without a second peak gets position (-1, -1) and a NaN score.
-__global__ __launch_bounds__(256) void blocks_second_record_kernel(const TrackUnit* __restrict__ units,
-                                                                   const unsigned long long* __restrict__ keys2,
-                                                                   const mtm_block* __restrict__ blocks, int n, int mode_min,
-                                                                   mtm_hit* __restrict__ recs2) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const TrackUnit U = units[k];
-    recs2[k] = second_key_record(keys2[k], mode_min, k, U.y0, U.x0, U.ow, blocks[k].w, blocks[k].h);
-}
-
-// One lane per block k < n: the unit of the block moved by its displacement - offs[2 k], offs[2 k + 1], or (prev !=
-// nullptr) the one the records `prev` of the previous pass over grid `coarse` predict (blocks_predict_inl) -, clamped,
-// widened by `margin` and clipped to the rows x cols image (blocks_unit_at_inl): units[k] = (k, y0, x0, oh, ow).  Every
-// block lies inside the image (plan_blocks), so the coarse index is in range and the map has an output.
-__global__ __launch_bounds__(256) void blocks_unit_kernel(const mtm_block* __restrict__ blocks, int n,
-                                                          const int32_t* __restrict__ offs, const mtm_hit* __restrict__ prev,
-                                                          BlockGrid coarse, int margin, int rows, int cols,
-                                                          TrackUnit* __restrict__ units) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const mtm_block B = blocks[k];
-    long long dx, dy;
-    if (prev) {
-        blocks_predict_inl(coarse, prev, B, &dx, &dy);
-    } else {
-        dx = offs[2 * (size_t)k];
-        dy = offs[2 * (size_t)k + 1];
-    }
-    const BlockUnitBox u = blocks_unit_at_inl(B, dx, dy, margin, rows, cols);
-    units[k] = TrackUnit{k, u.y0, u.x0, u.oh, u.ow};
-}
-
-// One lane per block k < n, after the pass's score launches: the block's key as its record in image coordinates -
-// quality_key_record (mtm_quality_key.h) at the unit's origin, what decode_block_keys gives on the host - into recs[k].
-__global__ __launch_bounds__(256) void blocks_record_kernel(const TrackUnit* __restrict__ units,
-                                                            const unsigned long long* __restrict__ keys,
-                                                            const mtm_block* __restrict__ blocks, int n, int mode_min,
-                                                            mtm_hit* __restrict__ recs) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const TrackUnit U = units[k];
-    recs[k] = quality_key_record(keys[k], mode_min, k, U.y0, U.x0, U.ow, blocks[k].w, blocks[k].h);
-}
-
-// One lane per block k < n of a DEFORMED pass, behind the pass's blocks_record_kernel: the field of the coarse grid's
-// displacements `disp` (deform_disp_kernel's pairs) at the block's doubled centre (deform_field_at_inl) goes into
-// pred[2 k], pred[2 k + 1] in Q8, and its rounded integer part is added to the record's position - found in the warped
-// image - so that recs[k] carries the block's displacement in the original image.  The position is not clamped.
-// Q8: the nodes are themselves in Q8 (steer = 1: blocks_smooth_q8_kernel's), else whole pixels.
-template <bool Q8>
-__global__ __launch_bounds__(256) void blocks_deform_record_kernel(const mtm_block* __restrict__ blocks, int n, BlockGrid coarse,
-                                                                   const int32_t* __restrict__ disp, mtm_hit* __restrict__ recs,
-                                                                   int32_t* __restrict__ pred) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const mtm_block B = blocks[k];
-    long long fx, fy;
-    deform_field_at_of_inl<Q8>(coarse, disp, 2ll * B.x + B.w - 1, 2ll * B.y + B.h - 1, &fx, &fy);
-    pred[2 * (size_t)k] = (int32_t)fx;
-    pred[2 * (size_t)k + 1] = (int32_t)fy;
-    recs[k].x += (int)deform_round_inl(fx);
-    recs[k].y += (int)deform_round_inl(fy);
-}
-
-// One lane per block k < nx ny of a pass's grid, after the pass's blocks_record_kernel: the median test of the block's
-// displacement against those of its 3 x 3 grid neighbourhood (blocks_steer_record_inl, mtm_blocks_validate.h: raw records
-// only, so no lane waits for another) - valid[k] = 1 / 0, and steer[k] = the record that steers the next pass: recs[k],
-// or for an outlier recs[k] moved to block position + the neighbours' median.  Every neighbour index is checked against
-// the grid before its record is read.  No LDS and no scratch: the eight values are sorted in registers.
-__global__ __launch_bounds__(256) void blocks_validate_kernel(const mtm_hit* __restrict__ recs, int nx, int ny, int sx, int sy,
-                                                              double threshold, double e4, uint8_t* __restrict__ valid,
-                                                              mtm_hit* __restrict__ steer) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nx * ny) return;
-    mtm_hit r;
-    valid[k] = blocks_steer_record_inl(recs, nx, ny, sx, sy, k, threshold, e4, &r) ? 1 : 0;
-    steer[k] = r;
-}
-
-// One lane per record k < nx ny of a pass that steers another by refined positions (steer = 1), behind the pass's records,
-// neighbourhoods and - with validation - flags: the record's steering displacement in Q8 (steer_d8_inl, mtm_blocks_steer.h:
-// the fitted position in the searched image plus the field that steered the pass, minus the block's position; an outlier's:
-// its neighbours' median) as a compact pair d8[2 k], d8[2 k + 1] - one 8-byte store.  Reads its own record only.
-__global__ __launch_bounds__(256) void blocks_steer_q8_kernel(const mtm_hit* __restrict__ recs, const float* __restrict__ nbhd,
-                                                              const int32_t* __restrict__ pred, const uint8_t* __restrict__ valid,
-                                                              const mtm_hit* __restrict__ steer, int nx, int ny, int sx, int sy,
-                                                              int mode_min, int32_t* __restrict__ d8) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nx * ny) return;
-    int32_t dx, dy;
-    steer_d8_inl(recs, nbhd, pred, valid, steer, nx, sx, sy, mode_min, k, &dx, &dy);
-    *reinterpret_cast<int2*>(d8 + 2 * (size_t)k) = make_int2(dx, dy);
-}
-
-// One lane per node k < nx ny: the predictor filter (steer_smooth_inl: 3 x 3 binomial, clamped indices) of the pairs d8
-// into `out` - another buffer, the one the warp reads -, so that no lane reads what another writes.
-__global__ __launch_bounds__(256) void blocks_smooth_q8_kernel(const int32_t* __restrict__ d8, int nx, int ny,
-                                                               int32_t* __restrict__ out) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nx * ny) return;
-    int32_t sx8, sy8;
-    steer_smooth_inl(d8, nx, ny, k % nx, k / nx, &sx8, &sy8);
-    *reinterpret_cast<int2*>(out + 2 * (size_t)k) = make_int2(sx8, sy8);
-}
-
-// blocks_score_kernel's sibling for the ensemble planes of mtm_match_blocks_stack: the same tile and float32 score
-// (win_score_tile), and instead of merging a key every output (y, x) of the map adds its score, widened to float64, to its
-// cell of block u0's side x side plane of sums: acc[(u0 side + y + oy) side + x + ox], (ox, oy) = clip[2 u0],
-// clip[2 u0 + 1] the block's clip offsets (BlockPlan::clip: y + oy, x + ox < side).  A plain read-modify-write:
-// the tile table partitions every map, so a cell has one writer per launch, and the launches of successive pairs are
-// ordered by the call's one stream - the sums are those of the pairs in order, bit for bit.  `first` (the call's first
-// pair) stores instead of adding: the sum starts from s_0 itself, a -0.0 included.
-template <int CH, bool U16>
-__global__ __launch_bounds__(256) void blocks_plane_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
-                                                           const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
-                                                           const TemplDev* __restrict__ td, const TrackUnit* __restrict__ units,
-                                                           const TrackTile* __restrict__ tiles, int method,
-                                                           const int32_t* __restrict__ clip, int side, int first,
-                                                           double* __restrict__ acc) {
-    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
-    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
-    blocks_tile<CH, U16, false>(Tl, Il, img, lo_b, tpx, toff, td, units, tiles, method,
-                                [&](const TrackTile& K, const TrackUnit&, bool inside, int y, int x, auto&& score) {
-                                    const int cy = y + clip[2 * K.u0 + 1], cx = x + clip[2 * K.u0];
-                                    if (inside && cy < side && cx < side) {
-                                        const float s = score();
-                                        double* cell = acc + ((size_t)K.u0 * (size_t)side + (size_t)cy) * (size_t)side + (size_t)cx;
-                                        *cell = first ? (double)s : *cell + (double)s;
-                                    }
-                                });
-}
-
-// Grid: one 256-thread work-group per block (launch slice; block k = k0 + blockIdx.x), after the chunk's score launches:
-// the key of the block is decoded (key_index, mtm_quality_key.h: the extremum's index in the block's map, moved by the
-// map's origin into image coordinates) and the 3 x 3 neighbourhood of that window in the WHOLE image's map goes into
-// out[9 k ..]: sub_nbhd_int's sums and win_score, mtm_hit_neighbourhoods' float32 bits, NaN outside the map.  A block
-// without a key (no output scored) gets nine NaNs and reads no pixel.
-template <int CH, bool U16>
-__global__ __launch_bounds__(256) void blocks_nbhd_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
-                                                          const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
-                                                          const TemplDev* __restrict__ td, const TrackUnit* __restrict__ units,
-                                                          const unsigned long long* __restrict__ keys, int k0, int method,
-                                                          float* __restrict__ out) {
-    constexpr int kKind = U16 ? kSubU16 : kSubU8;
-    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
-    __shared__ __attribute__((aligned(16))) SubImageLds Il[U16 ? 2 : 1];
-    __shared__ unsigned long long red[4];
-    const int k = k0 + (int)blockIdx.x;
-    const TrackUnit U = units[k];
-    const TemplDev T = td[k];
-    const unsigned long long key = keys[k];
-    const uint32_t idx = key_index(key);
-    const int px = U.x0 + (int)(idx % (uint32_t)U.ow), py = U.y0 + (int)(idx / (uint32_t)U.ow);
-    const int tid = threadIdx.x;
-    float score = NAN;
-    // (the same for the whole work-group: before any barrier)
-    if (key != 0ull && px >= 0 && py >= 0 && px <= img.cols - T.cols && py <= img.rows - T.rows)
-        score = sub_nbhd_int<CH, kKind>(Tl, Il, red, img.u8, img.u8_plane, lo_b, img.u8_pitch, img.rows, img.cols,
-                                        tpx + toff[k], nullptr, T, px, py, method);
-    if (tid < 9) out[(size_t)k * 9 + tid] = score;
-}
-
-}  // namespace mtm
 
 namespace {
 
@@ -450,6 +34,14 @@ int blocks_dispatch(int dtype, int chans, F&& f) {
     if (dtype == MTM_U16) return f(std::integral_constant<int, 1>{}, std::true_type{});
     if (chans == 1) return f(std::integral_constant<int, 1>{}, std::false_type{});
     return f(std::integral_constant<int, 3>{}, std::false_type{});
+}
+
+// The one-lane-per-block launch: `kernel` over n lanes in work-groups of 256 on the call's stream.
+template <class... P, class... A>
+int launch_lanes(mtm_ctx* c, void (*kernel)(P...), size_t n, A&&... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, static_cast<P>(args)...);
+    HIPC(hipGetLastError());
+    return MTM_OK;
 }
 
 // The image of rows row_off .. row_off + rows - 1 of the stack `st`: its planes entered at that row and bounded by `rows`,
@@ -811,179 +403,189 @@ int launch_deform(mtm_ctx* c, const ImageDev& src, const uint8_t* src_lo, int ch
     });
 }
 
-// What a deformed call adds (mtm_match_blocks_passes_deformed): where the Q8 field at every block's centre goes, pass-major;
-// steer (mtm_match_blocks_passes_steered): 0 - integer records steer the next pass -, 1 - refined positions, filtered.
-struct BlockDeform {
-    int32_t* predicted;
-    int steer = 0;
+// What a call of the pass chain asks for and where its results go (host memory, pass-major); an absent feature is an
+// empty field, and a chain without it launches and copies exactly what it would if the feature did not exist.
+struct BlockPassCall {
+    int method;
+    mtm_hit* out;                       // every pass's records
+    float* nbhd;                        // ... and their neighbourhoods (nullptr: not asked for)
+    const int32_t* offsets = nullptr;   // mtm_match_blocks_at / _second: pass 0 follows an uploaded displacement per block
+    uint8_t* valid = nullptr;           // validation: the median test behind every pass's records - its flags,
+    double threshold = 0.0, epsilon = 0.0;      // threshold and epsilon -, which steer the next pass instead of the raw ones
+    mtm_hit* second = nullptr;          // second peaks: every pass's second records, which steer nothing;
+    int exclusion = 0;                  //   the exclusion radius around the first peak
+    int32_t* predicted = nullptr;       // deformation (never with offsets or second): the Q8 field at every block's centre;
+    int steer = 0;                      //   0 - integer records steer the next pass -, 1 - refined positions, filtered
 };
 
-// The median test a validated call runs behind every pass: its threshold, e4 = 4 epsilon (computed once, exact), and where
-// the flags of every record go, pass-major.
-struct BlockValidate {
-    double threshold, e4;
-    uint8_t* valid;
-};
-
-// The chain behind mtm_match_blocks_at (one pass over the caller's blocks, `offsets` uploaded) and
-// mtm_match_blocks_passes (offsets == nullptr): both images go up once; per pass the units - pass 0 without offsets: the
-// host's, of zero offsets; else blocks_unit_kernel's -, the pass's chain over its fixed tile table (blocks_pair) and
-// blocks_record_kernel, all in stream order, so a pass reads the finished records of the one before and no work-group
-// waits for another.  The records (and neighbourhoods) of every pass, pass-major, come back behind the call's single wait.
-// V != nullptr (mtm_match_blocks_passes_validated): blocks_validate_kernel behind every pass's records, the next pass's
-// units are predicted from its `steer` records instead of the raw ones, and the flags come back with the records.
-// V == nullptr launches and copies exactly what the chain did before validation existed.
-// X2 != nullptr (mtm_match_blocks_second, mtm_match_blocks_passes_second): every pass scores into planes and reduces them to
-// second keys (blocks_pair, BlockSecondPass), blocks_second_record_kernel behind the pass's blocks_record_kernel turns them
-// into records, which come back with the others and steer nothing.  X2 == nullptr: the chain as it is without.
-// D != nullptr (mtm_match_blocks_passes_deformed; never with offsets or X2): a pass p >= 1 does not move its boxes - the
-// records that steer it become compact displacements (deform_disp_kernel), the ORIGINAL image is warped by their field
-// into blk_warp (deform_image_kernel), the pass searches the warped image over the host's units of zero offsets, and
-// blocks_deform_record_kernel behind blocks_record_kernel adds the field at every block's centre to its record, which is
-// what validation tests and what steers the next pass; the fields come back with the records.  D == nullptr launches and
-// copies exactly what the chain did before deformation existed.
-// D->steer == 1: every pass that steers another also gets its neighbourhoods (whether or not the caller asked for them),
-// blocks_steer_q8_kernel behind its records and flags turns them into Q8 steering displacements and
-// blocks_smooth_q8_kernel filters those into blk_disp - in place of deform_disp_kernel ahead of the next pass, whose warp
-// and record kernels then read Q8 nodes.  D->steer == 0 launches exactly the kernels it did before.
-struct BlockSecondOut {
-    int exclusion;
-    mtm_hit* second;
-};
-int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPassPlan>& Q, const int32_t* offsets, int method,
-                       mtm_hit* out, float* nbhd, const BlockValidate* V = nullptr, const BlockSecondOut* X2 = nullptr,
-                       const BlockDeform* D = nullptr) {
-    const int rows = I.rows, cols = I.cols, chans = I.chans, dtype = I.dtype;
-    // the tables of every pass, concatenated: one upload each
+// What stage_block_passes lays out on the host for the whole call: the tables of every pass, concatenated (one upload
+// each); second peaks: every pass's plane sub-ranges and one table of plane offsets; deformation: the weight tables of
+// every pass p >= 1 (those of pass p - 1's grid), pass p's at word dtab_at[p].
+struct BlockPassHost {
     std::vector<mtm_block> blocks;
-    std::vector<long long> toff;
+    std::vector<long long> toff, poff;
     std::vector<TrackUnit> units;
     std::vector<TrackTile> tiles;
+    std::vector<BlockSecondPass> X;
+    std::vector<uint32_t> dtab;
+    std::vector<size_t> dtab_at;
+};
+
+// Stage the call: H, the buffers they and the asked-for results need, both images up once, then the call's clock and the
+// tables (stage_block_call).  steer = 1 with a pass to steer: the neighbourhoods exist whether or not the caller asked.
+int stage_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPassPlan>& Q, const BlockPassCall& A,
+                       BlockPassHost& H) {
     size_t max_bytes = 0;
     for (const BlockPassPlan& q : Q) {
-        blocks.insert(blocks.end(), q.blocks.begin(), q.blocks.end());
-        toff.insert(toff.end(), q.plan.toff.begin(), q.plan.toff.end());
-        units.insert(units.end(), q.plan.units.begin(), q.plan.units.end());
-        tiles.insert(tiles.end(), q.plan.tiles.begin(), q.plan.tiles.end());
+        H.blocks.insert(H.blocks.end(), q.blocks.begin(), q.blocks.end());
+        H.toff.insert(H.toff.end(), q.plan.toff.begin(), q.plan.toff.end());
+        H.units.insert(H.units.end(), q.plan.units.begin(), q.plan.units.end());
+        H.tiles.insert(H.tiles.end(), q.plan.tiles.begin(), q.plan.tiles.end());
         max_bytes = std::max(max_bytes, q.plan.max_bytes);
     }
-    const size_t n = blocks.size();
-    BlockStage S{blocks.data(), toff.data(), units.data(), tiles.data(), n, tiles.size(), max_bytes};
-    S.nbhd = nbhd != nullptr;
-    S.offsets = offsets;
-    S.recs = true;
-    S.validate = V != nullptr;
-    // second peaks: every pass's plane sub-ranges, one table of plane offsets for the call
-    std::vector<BlockSecondPass> X(X2 ? Q.size() : 0);
-    std::vector<long long> poff;
-    if (X2) {
-        poff.reserve(n);
+    BlockStage S{H.blocks.data(), H.toff.data(), H.units.data(), H.tiles.data(), H.blocks.size(), H.tiles.size(), max_bytes};
+    S.nbhd = A.nbhd != nullptr, S.offsets = A.offsets;
+    S.recs = true, S.validate = A.valid != nullptr;
+    if (A.second) {
+        H.X.resize(Q.size());
+        H.poff.reserve(S.n);
         for (size_t p = 0; p < Q.size(); ++p) {
-            X[p].exclusion = X2->exclusion;
-            plan_second_pass(Q[p].plan, Q[p].blocks.data(), Q[p].margin, rows, cols, (size_t)c->boxes_max_floats, X[p], poff,
-                             &S.plane_floats);
+            H.X[p].exclusion = A.exclusion;
+            plan_second_pass(Q[p].plan, Q[p].blocks.data(), Q[p].margin, I.rows, I.cols, (size_t)c->boxes_max_floats, H.X[p],
+                             H.poff, &S.plane_floats);
         }
-        S.poff = poff.data();
+        S.poff = H.poff.data();
     }
-    // deformation: the weight tables of every pass p >= 1 (those of pass p - 1's grid), one upload
-    std::vector<uint32_t> dtab;
-    std::vector<size_t> dtab_at(Q.size(), 0);
-    if (D) {
+    H.dtab_at.assign(Q.size(), 0);
+    if (A.predicted) {
         for (size_t p = 1; p < Q.size(); ++p) {
-            dtab_at[p] = deform_tables(Q[p - 1].grid, rows, cols, dtab);
+            H.dtab_at[p] = deform_tables(Q[p - 1].grid, I.rows, I.cols, H.dtab);
             S.disp_blocks = std::max(S.disp_blocks, Q[p - 1].blocks.size());
         }
         S.deform = true;
-        if (D->steer && Q.size() > 1) {
+        if (A.steer && Q.size() > 1) {
             S.d8_blocks = S.disp_blocks;
             S.nbhd = true;
         }
-        S.dtab = dtab.empty() ? nullptr : dtab.data();
-        S.dtab_words = dtab.size();
-        if (Q.size() > 1) S.warp_bytes = warp_bytes(rows, (int)round_up((size_t)cols + kPadCols, 64), chans, dtype);
+        S.dtab = H.dtab.empty() ? nullptr : H.dtab.data(), S.dtab_words = H.dtab.size();
+        if (Q.size() > 1) S.warp_bytes = warp_bytes(I.rows, (int)round_up((size_t)I.cols + kPadCols, 64), I.chans, I.dtype);
     }
-    MTMC(stage_block_call(c, S, [&] { return upload_block_pair(c, I); }));
+    return stage_block_call(c, S, [&] { return upload_block_pair(c, I); });
+}
 
-    const int mode_min = method_mode_min(method) ? 1 : 0;
+// One pass of the chain: its plan and the one that steers it, its rows of the call's device buffers (from the pass's first
+// block b0 and tile t0; nullptr: the call has no such row) and what the pass does - every flag derived here, once.
+struct BlockPass {
+    const BlockPassPlan& q;
+    const BlockPassPlan* before;        // the pass whose records steer this one (pass 0: nullptr)
+    int np, mode_min;
+    BlockTables B;                      // blocks, units (with the constants td) and the fixed tile table
+    unsigned long long* keys;
+    mtm_hit *recs, *recs2, *steer;
+    float* nbhd;
+    uint8_t* valid;
+    int32_t* pred;
+    const BlockSecondPass* X;           // (with poff and keys2)
+    const mtm_hit* prev;                // the records of `before` that steer this pass: validated or raw
+    size_t dtab;                        // the pass's deform tables start at this word of blk_dtab
+    bool warped, q8, steers, moved;
+};
+BlockPass block_pass_view(mtm_ctx* c, const std::vector<BlockPassPlan>& Q, const BlockPassCall& A, BlockPassHost& H, size_t p,
+                          size_t b0, size_t t0) {
+    BlockPass V{Q[p], p > 0 ? &Q[p - 1] : nullptr, (int)Q[p].blocks.size(), method_mode_min(A.method) ? 1 : 0,
+                ctx_block_tables(c, b0, t0, true)};
+    // warped: a deformed pass p >= 1 searches the image warped by its steering records' field, over the host's units
+    V.warped = A.predicted && p > 0;
+    // q8: the field's nodes are Q8 ones, which the pass before left in blk_disp (pass_handover) - else whole pixels
+    V.q8 = A.predicted && A.steer;
+    // steers: this pass steers another by refined positions, so it needs its neighbourhoods and hands Q8 nodes on
+    V.steers = V.q8 && p + 1 < Q.size();
+    // moved: blocks_unit_kernel moves the boxes - by the previous pass's records or pass 0's offsets; else the host's units
+    V.moved = !V.warped && (p > 0 || A.offsets);
+    V.keys = c->blk_keys.as<unsigned long long>() + b0;
+    V.recs = c->blk_recs.as<mtm_hit>() + b0;
+    V.nbhd = A.nbhd || V.steers ? c->blk_nbhd.as<float>() + 9 * b0 : nullptr;
+    V.valid = A.valid ? c->blk_valid.as<uint8_t>() + b0 : nullptr;
+    V.steer = A.valid ? c->blk_steer.as<mtm_hit>() + b0 : nullptr;
+    V.pred = A.predicted ? c->blk_pred.as<int32_t>() + 2 * b0 : nullptr;
+    V.recs2 = A.second ? c->blk_recs2.as<mtm_hit>() + b0 : nullptr;
+    if (A.second) {
+        H.X[p].poff = c->blk_poff.as<long long>() + b0;
+        H.X[p].keys2 = c->blk_keys2.as<unsigned long long>() + b0;
+        V.X = &H.X[p];
+    }
+    V.prev = p > 0 ? (A.valid ? V.steer : V.recs) - Q[p - 1].blocks.size() : nullptr;
+    V.dtab = H.dtab_at[p];
+    return V;
+}
+
+// What the pass searches, ahead of its chain.  Warped: the steering records become compact displacements
+// (deform_disp_kernel; q8: the nodes are already there) and the ORIGINAL image - the stack's slot 1 - is warped by their
+// field into blk_warp, *wimg.  Moved: blocks_unit_kernel's units.  Else nothing: the host's units.
+int pass_search(mtm_ctx* c, const BlockPair& I, const BlockPass& V, ImageDev* wimg) {
+    if (V.warped) {
+        const BlockGrid& g = V.before->grid;
+        if (!V.q8) MTMC(launch_lanes(c, deform_disp_kernel, V.before->blocks.size(), V.prev, g, c->blk_disp.as<int32_t>()));
+        const ImageDev st = image_dev(c);
+        MTMC(launch_deform(c, stack_view(st, I.rows, I.rows),
+                           c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane + (size_t)I.rows * st.u8_pitch, I.chans, I.dtype, g,
+                           V.dtab, V.q8));
+        *wimg = warp_view(c, I.rows, I.cols, I.chans);
+    } else if (V.moved) {
+        return launch_lanes(c, blocks_unit_kernel, V.np, V.B.blocks, V.np, V.before ? nullptr : c->blk_offs.as<int32_t>(), V.prev,
+                            V.before ? V.before->grid : BlockGrid{}, V.q.margin, I.rows, I.cols, V.B.units);
+    }
+    return MTM_OK;
+}
+
+// The pass's records, behind its chain: blocks_record_kernel decodes the keys; a warped pass adds the field at every
+// block's centre (blocks_deform_record_kernel: the record then carries the displacement in the original image, which is
+// what validation tests and what steers the next pass); the second keys' records; the median test's flags and steering
+// records (np = nx ny: plan_block_passes lays out the whole grid).
+int pass_records(mtm_ctx* c, const BlockPassCall& A, const BlockPass& V) {
+    const BlockGrid& g = V.q.grid;
+    MTMC(launch_lanes(c, blocks_record_kernel, V.np, V.B.units, V.keys, V.B.blocks, V.np, V.mode_min, V.recs));
+    if (V.warped)
+        MTMC(launch_lanes(c, V.q8 ? blocks_deform_record_kernel<true> : blocks_deform_record_kernel<false>, V.np, V.B.blocks, V.np,
+                          V.before->grid, c->blk_disp.as<int32_t>(), V.recs, V.pred));
+    if (V.X) MTMC(launch_lanes(c, blocks_second_record_kernel, V.np, V.B.units, V.X->keys2, V.B.blocks, V.np, V.mode_min, V.recs2));
+    if (V.valid)        // (4 epsilon: exact)
+        MTMC(launch_lanes(c, blocks_validate_kernel, V.np, V.recs, g.nx, g.ny, g.sx, g.sy, A.threshold, 4.0 * A.epsilon, V.valid,
+                          V.steer));
+    return MTM_OK;
+}
+
+// What a pass that steers hands the next: its records, neighbourhoods and flags as Q8 displacements (blocks_steer_q8_kernel),
+// filtered into blk_disp (blocks_smooth_q8_kernel) - behind this pass's last reader of blk_disp, which the filter overwrites.
+int pass_handover(mtm_ctx* c, const BlockPass& V) {
+    if (!V.steers) return MTM_OK;
+    const BlockGrid& g = V.q.grid;
+    MTMC(launch_lanes(c, blocks_steer_q8_kernel, V.np, V.recs, V.nbhd, V.pred, V.valid, V.steer, g.nx, g.ny, g.sx, g.sy, V.mode_min,
+                      c->blk_d8.as<int32_t>()));
+    return launch_lanes(c, blocks_smooth_q8_kernel, V.np, c->blk_d8.as<int32_t>(), g.nx, g.ny, c->blk_disp.as<int32_t>());
+}
+
+// The chain behind mtm_match_blocks_at / _second (one pass) and the mtm_match_blocks_passes* entries: the stages above per
+// pass, in stream order - a pass reads the finished records of the one before -, then what was asked for, behind one wait.
+int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPassPlan>& Q, const BlockPassCall& A) {
+    BlockPassHost H;
+    MTMC(stage_block_passes(c, I, Q, A, H));
     size_t b0 = 0, t0 = 0;
     for (size_t p = 0; p < Q.size(); ++p) {
-        const BlockPassPlan& q = Q[p];
-        const int np = (int)q.blocks.size();
-        const unsigned lanes_grid = (unsigned)((np + 255) / 256);
-        const BlockTables B = ctx_block_tables(c, b0, t0, true);
-        unsigned long long* keys = c->blk_keys.as<unsigned long long>() + b0;
-        mtm_hit* recs = c->blk_recs.as<mtm_hit>() + b0;
-        // what steers this pass: the previous pass's records, validated or raw
-        const mtm_hit* prev = V ? c->blk_steer.as<mtm_hit>() + b0 : recs;
-        const bool warped = D && p > 0, q8 = D && D->steer, steers = q8 && p + 1 < Q.size();
+        const BlockPass V = block_pass_view(c, Q, A, H, p, b0, t0);
         ImageDev wimg{};
-        if (warped) {
-            const BlockGrid& g = Q[p - 1].grid;
-            if (!q8) {          // (q8: the pass before left its filtered Q8 nodes in blk_disp)
-                hipLaunchKernelGGL(deform_disp_kernel, dim3((unsigned)((Q[p - 1].blocks.size() + 255) / 256)), dim3(256), 0,
-                                   c->stream, prev - Q[p - 1].blocks.size(), g, c->blk_disp.as<int32_t>());
-                HIPC(hipGetLastError());
-            }
-            const ImageDev st = image_dev(c);
-            MTMC(launch_deform(c, stack_view(st, rows, rows),
-                               c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane + (size_t)rows * st.u8_pitch, chans, dtype, g,
-                               dtab_at[p], q8));
-            wimg = warp_view(c, rows, cols, chans);
-        } else if (p > 0 || offsets) {
-            hipLaunchKernelGGL(blocks_unit_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.blocks, np,
-                               p > 0 ? nullptr : c->blk_offs.as<int32_t>(), p > 0 ? prev - Q[p - 1].blocks.size() : nullptr,
-                               p > 0 ? Q[p - 1].grid : BlockGrid{}, q.margin, rows, cols, B.units);
-            HIPC(hipGetLastError());
-        }
-        if (X2) {
-            X[p].poff = c->blk_poff.as<long long>() + b0;
-            X[p].keys2 = c->blk_keys2.as<unsigned long long>() + b0;
-        }
-        MTMC(blocks_pair(c, q.plan, B, rows, chans, dtype, method, 0, 1, true,
-                         BlockSink{keys, nbhd || steers ? c->blk_nbhd.as<float>() + 9 * b0 : nullptr, 0, 0}, X2 ? &X[p] : nullptr,
-                         warped ? &wimg : nullptr, warped ? wimg.u8 + wimg.u8_plane : nullptr));
-        hipLaunchKernelGGL(blocks_record_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.units, keys, B.blocks, np, mode_min,
-                           recs);
-        HIPC(hipGetLastError());
-        if (warped) {
-            if (q8)
-                hipLaunchKernelGGL(blocks_deform_record_kernel<true>, dim3(lanes_grid), dim3(256), 0, c->stream, B.blocks, np,
-                                   Q[p - 1].grid, c->blk_disp.as<int32_t>(), recs, c->blk_pred.as<int32_t>() + 2 * b0);
-            else
-                hipLaunchKernelGGL(blocks_deform_record_kernel<false>, dim3(lanes_grid), dim3(256), 0, c->stream, B.blocks, np,
-                                   Q[p - 1].grid, c->blk_disp.as<int32_t>(), recs, c->blk_pred.as<int32_t>() + 2 * b0);
-            HIPC(hipGetLastError());
-        }
-        if (X2) {
-            hipLaunchKernelGGL(blocks_second_record_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, B.units, X[p].keys2,
-                               B.blocks, np, mode_min, c->blk_recs2.as<mtm_hit>() + b0);
-            HIPC(hipGetLastError());
-        }
-        if (V) {        // (np = nx ny: plan_block_passes lays out the whole grid)
-            hipLaunchKernelGGL(blocks_validate_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, recs, q.grid.nx, q.grid.ny,
-                               q.grid.sx, q.grid.sy, V->threshold, V->e4, c->blk_valid.as<uint8_t>() + b0,
-                               c->blk_steer.as<mtm_hit>() + b0);
-            HIPC(hipGetLastError());
-        }
-        if (steers) {   // (behind this pass's last reader of blk_disp: the filter may overwrite it)
-            hipLaunchKernelGGL(blocks_steer_q8_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, recs,
-                               c->blk_nbhd.as<float>() + 9 * b0, c->blk_pred.as<int32_t>() + 2 * b0,
-                               V ? c->blk_valid.as<uint8_t>() + b0 : nullptr, V ? c->blk_steer.as<mtm_hit>() + b0 : nullptr,
-                               q.grid.nx, q.grid.ny, q.grid.sx, q.grid.sy, mode_min, c->blk_d8.as<int32_t>());
-            HIPC(hipGetLastError());
-            hipLaunchKernelGGL(blocks_smooth_q8_kernel, dim3(lanes_grid), dim3(256), 0, c->stream, c->blk_d8.as<int32_t>(),
-                               q.grid.nx, q.grid.ny, c->blk_disp.as<int32_t>());
-            HIPC(hipGetLastError());
-        }
-        b0 += q.blocks.size();
-        t0 += q.plan.tiles.size();
+        MTMC(pass_search(c, I, V, &wimg));
+        MTMC(blocks_pair(c, V.q.plan, V.B, I.rows, I.chans, I.dtype, A.method, 0, 1, true, BlockSink{V.keys, V.nbhd, 0, 0}, V.X,
+                         V.warped ? &wimg : nullptr, V.warped ? wimg.u8 + wimg.u8_plane : nullptr));
+        MTMC(pass_records(c, A, V));
+        MTMC(pass_handover(c, V));
+        b0 += V.q.blocks.size();
+        t0 += V.q.plan.tiles.size();
     }
-
-    // the records (and neighbourhoods, and flags) come back behind the call's single wait
-    return finish_block_call(c, {{out, c->blk_recs.p, sizeof(mtm_hit) * n}, {nbhd, c->blk_nbhd.p, sizeof(float) * 9 * n},
-                                 {V ? V->valid : nullptr, c->blk_valid.p, n},
-                                 {X2 ? X2->second : nullptr, c->blk_recs2.p, sizeof(mtm_hit) * n},
-                                 {D ? D->predicted : nullptr, c->blk_pred.p, sizeof(int32_t) * 2 * n}}, n);
+    const size_t n = H.blocks.size();
+    return finish_block_call(c, {{A.out, c->blk_recs.p, sizeof(mtm_hit) * n}, {A.nbhd, c->blk_nbhd.p, sizeof(float) * 9 * n},
+                                 {A.valid, c->blk_valid.p, n}, {A.second, c->blk_recs2.p, sizeof(mtm_hit) * n},
+                                 {A.predicted, c->blk_pred.p, sizeof(int32_t) * 2 * n}}, n);
 }
 
 // threshold and epsilon of the median test: finite and >= 0, else MTM_E_INVALID naming the argument.
@@ -996,6 +598,66 @@ int check_validate_args(const char* who, double threshold, double epsilon) {
     return MTM_OK;
 }
 
+// The preamble of mtm_match_blocks_at / _second behind their record: one pass over the caller's blocks, planned over the
+// fixed tile table.  extra_ok: what the entry asks of the arguments that are its own.
+int block_single_entry(mtm_ctx* c, const char* who, const BlockPair& I, const mtm_block* blocks, int n_blocks, int margin,
+                       bool extra_ok, const BlockPassCall& A) {
+    MTMC(check_block_pair(c, who, n_blocks >= 0 && margin >= 0 && extra_ok && (n_blocks == 0 || (blocks && A.out)), A.method, I));
+    std::vector<BlockPassPlan> Q(1);
+    Q[0].grid = BlockGrid{};
+    Q[0].margin = margin;
+    MTMC(plan_blocks(I.rows, I.cols, I.chans, I.dtype, blocks, n_blocks, margin, 4 * (long long)c->boxes_max_floats, who, Q[0].plan,
+                     false));
+    if (n_blocks == 0) return MTM_OK;
+    MTMC(fix_block_tiles(Q[0].plan, I.rows, I.cols, blocks, margin, who));
+    Q[0].blocks.assign(blocks, blocks + n_blocks);
+    return match_block_passes(c, I, Q, A);
+}
+
+// ... and of the five mtm_match_blocks_passes* entries.  check_median: the median test's arguments are checked - ahead of
+// everything else, a null context included.
+int block_passes_entry(mtm_ctx* c, const char* who, const BlockPair& I, const mtm_block_pass* passes, int n_passes,
+                       bool check_median, bool extra_ok, const BlockPassCall& A) {
+    if (check_median) MTMC(check_validate_args(who, A.threshold, A.epsilon));
+    MTMC(check_block_pair(c, who, n_passes >= 1 && passes && A.out && extra_ok, A.method, I));
+    // deformation: every pass moves a record by less than the image's larger side past the field that steered it
+    if (A.predicted && (long long)n_passes * std::max(I.rows, I.cols) > kDeformMaxDisp) {
+        set_error(std::string(who) + ": " + std::to_string(n_passes) + " passes over images of this size could pass the "
+                  "largest displacement the field takes (2^22 pixels)");
+        return MTM_E_INVALID;
+    }
+    std::vector<BlockPassPlan> Q;
+    MTMC(plan_block_passes(I.rows, I.cols, I.chans, I.dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
+    return match_block_passes(c, I, Q, A);
+}
+
+// mtm_match_blocks_passes_deformed and mtm_match_blocks_passes_steered - steer = 0: the deformed call, under its name.
+int block_deformed_entry(mtm_ctx* c, const char* who, const BlockPair& I, const mtm_block_pass* passes, int n_passes, int method,
+                         double threshold, double epsilon, mtm_hit* out, float* nbhd, uint8_t* valid, int32_t* predicted,
+                         int steer) {
+    BlockPassCall A{method, out, nbhd};
+    A.valid = valid, A.threshold = threshold, A.epsilon = epsilon;
+    A.predicted = predicted, A.steer = steer;
+    return block_passes_entry(c, who, I, passes, n_passes, valid != nullptr, predicted != nullptr, A);
+}
+
+// What a debug entry does around its kernels: ensure these buffers, upload those with a source, run(), copy back those
+// with a destination, wait.
+struct DebugBuf { DevBuf& buf; size_t bytes; const void* src; void* dst; };
+template <class Run>
+int debug_block_run(mtm_ctx* c, const char* who, std::initializer_list<DebugBuf> bufs, Run&& run) {
+    MTM_NOT_IN_FLIGHT(c, who);
+    HIPC(hipSetDevice(c->device));
+    for (const DebugBuf& b : bufs) MTMC(b.buf.ensure(b.bytes));
+    for (const DebugBuf& b : bufs)
+        if (b.src) HIPC(hipMemcpyAsync(b.buf.p, b.src, b.bytes, hipMemcpyHostToDevice, c->stream));
+    MTMC(run());
+    for (const DebugBuf& b : bufs)
+        if (b.dst) HIPC(hipMemcpyAsync(b.dst, b.buf.p, b.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return MTM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1003,43 +665,76 @@ extern "C" {
 int mtm_match_blocks_at(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
                         int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
                         const int32_t* offsets, int n_blocks, int margin, int method, mtm_hit* out, float* nbhd) {
-    const char* who = "mtm_match_blocks_at";
-    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
-    MTMC(check_block_pair(c, who, n_blocks >= 0 && margin >= 0 && (n_blocks == 0 || (blocks && offsets && out)), method, I));
-    std::vector<BlockPassPlan> Q(1);
-    Q[0].grid = BlockGrid{};
-    Q[0].margin = margin;
-    MTMC(plan_blocks(rows, cols, chans, dtype, blocks, n_blocks, margin, 4 * (long long)c->boxes_max_floats, who, Q[0].plan,
-                     false));
-    if (n_blocks == 0) return MTM_OK;
-    MTMC(fix_block_tiles(Q[0].plan, rows, cols, blocks, margin, who));
-    Q[0].blocks.assign(blocks, blocks + n_blocks);
-    return match_block_passes(c, I, Q, offsets, method, out, nbhd);
+    BlockPassCall A{method, out, nbhd};
+    A.offsets = offsets;
+    return block_single_entry(c, "mtm_match_blocks_at",
+                              {reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype}, blocks,
+                              n_blocks, margin, n_blocks == 0 || offsets, A);
+}
+
+int mtm_match_blocks_second(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                            int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
+                            const int32_t* offsets, int n_blocks, int margin, int method, mtm_hit* out, float* nbhd,
+                            int exclusion, mtm_hit* second) {
+    BlockPassCall A{method, out, nbhd};
+    A.offsets = offsets, A.second = second, A.exclusion = exclusion;
+    return block_single_entry(c, "mtm_match_blocks_second",
+                              {reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype}, blocks,
+                              n_blocks, margin, exclusion >= 0 && second, A);
 }
 
 int mtm_match_blocks_passes(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
                             int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
                             const mtm_block_pass* passes, int n_passes, int method, mtm_hit* out, float* nbhd) {
-    const char* who = "mtm_match_blocks_passes";
-    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
-    MTMC(check_block_pair(c, who, n_passes >= 1 && passes && out, method, I));
-    std::vector<BlockPassPlan> Q;
-    MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
-    return match_block_passes(c, I, Q, nullptr, method, out, nbhd);
+    return block_passes_entry(c, "mtm_match_blocks_passes",
+                              {reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype}, passes,
+                              n_passes, /* check_median */ false, /* extra_ok */ true, BlockPassCall{method, out, nbhd});
 }
 
 int mtm_match_blocks_passes_validated(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
                                       int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
                                       const mtm_block_pass* passes, int n_passes, int method, double threshold,
                                       double epsilon, mtm_hit* out, float* nbhd, uint8_t* valid) {
-    const char* who = "mtm_match_blocks_passes_validated";
-    MTMC(check_validate_args(who, threshold, epsilon));         // (ahead of everything else, a null context included)
-    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
-    MTMC(check_block_pair(c, who, n_passes >= 1 && passes && out && valid, method, I));
-    std::vector<BlockPassPlan> Q;
-    MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
-    const BlockValidate V{threshold, 4.0 * epsilon, valid};
-    return match_block_passes(c, I, Q, nullptr, method, out, nbhd, &V);
+    BlockPassCall A{method, out, nbhd};
+    A.valid = valid, A.threshold = threshold, A.epsilon = epsilon;
+    return block_passes_entry(c, "mtm_match_blocks_passes_validated",
+                              {reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype}, passes,
+                              n_passes, /* check_median */ true, valid != nullptr, A);
+}
+
+int mtm_match_blocks_passes_second(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                                   int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                                   const mtm_block_pass* passes, int n_passes, int method, double threshold, double epsilon,
+                                   mtm_hit* out, float* nbhd, uint8_t* valid, int exclusion, mtm_hit* second) {
+    BlockPassCall A{method, out, nbhd};
+    A.valid = valid, A.threshold = threshold, A.epsilon = epsilon;
+    A.second = second, A.exclusion = exclusion;
+    return block_passes_entry(c, "mtm_match_blocks_passes_second",
+                              {reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype}, passes,
+                              n_passes, valid != nullptr, exclusion >= 0 && second, A);
+}
+
+int mtm_match_blocks_passes_deformed(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                                     int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                                     const mtm_block_pass* passes, int n_passes, int method, double threshold, double epsilon,
+                                     mtm_hit* out, float* nbhd, uint8_t* valid, int32_t* predicted) {
+    return block_deformed_entry(c, "mtm_match_blocks_passes_deformed",
+                                {reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype}, passes,
+                                n_passes, method, threshold, epsilon, out, nbhd, valid, predicted, 0);
+}
+
+int mtm_match_blocks_passes_steered(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                                    int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
+                                    const mtm_block_pass* passes, int n_passes, int method, double threshold, double epsilon,
+                                    mtm_hit* out, float* nbhd, uint8_t* valid, int32_t* predicted, int steer) {
+    if (steer != 0 && steer != 1) {
+        set_error(std::string("mtm_match_blocks_passes_steered: steer must be 0 (integer records) or 1 (refined positions) (got ") +
+                  std::to_string(steer) + ")");
+        return MTM_E_INVALID;
+    }
+    return block_deformed_entry(c, steer ? "mtm_match_blocks_passes_steered" : "mtm_match_blocks_passes_deformed",
+                                {reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype}, passes,
+                                n_passes, method, threshold, epsilon, out, nbhd, valid, predicted, steer);
 }
 
 int mtm_debug_validate_blocks(mtm_ctx* c, const mtm_hit* recs, int nx, int ny, int sx, int sy, double threshold, double epsilon,
@@ -1057,69 +752,11 @@ int mtm_debug_validate_blocks(mtm_ctx* c, const mtm_hit* recs, int nx, int ny, i
             valid[k] = blocks_steer_record_inl(recs, nx, ny, sx, sy, k, threshold, e4, &steer[k]) ? 1 : 0;
         return MTM_OK;
     }
-    MTM_NOT_IN_FLIGHT(c, who);
-    HIPC(hipSetDevice(c->device));
-    MTMC(c->blk_recs.ensure(sizeof(mtm_hit) * n));
-    MTMC(c->blk_valid.ensure(n));
-    MTMC(c->blk_steer.ensure(sizeof(mtm_hit) * n));
-    HIPC(hipMemcpyAsync(c->blk_recs.p, recs, sizeof(mtm_hit) * n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(blocks_validate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                       c->blk_recs.as<mtm_hit>(), nx, ny, sx, sy, threshold, e4, c->blk_valid.as<uint8_t>(),
-                       c->blk_steer.as<mtm_hit>());
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(valid, c->blk_valid.p, n, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipMemcpyAsync(steer, c->blk_steer.p, sizeof(mtm_hit) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    return MTM_OK;
-}
-
-int mtm_match_blocks_passes_deformed(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
-                                     int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
-                                     const mtm_block_pass* passes, int n_passes, int method, double threshold, double epsilon,
-                                     mtm_hit* out, float* nbhd, uint8_t* valid, int32_t* predicted) {
-    const char* who = "mtm_match_blocks_passes_deformed";
-    if (valid) MTMC(check_validate_args(who, threshold, epsilon));      // (ahead of everything else, as the validated call)
-    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
-    MTMC(check_block_pair(c, who, n_passes >= 1 && passes && out && predicted, method, I));
-    // every pass moves a record by less than the image's larger side past the field that steered it
-    if ((long long)n_passes * std::max(rows, cols) > kDeformMaxDisp) {
-        set_error(std::string(who) + ": " + std::to_string(n_passes) + " passes over images of this size could pass the "
-                  "largest displacement the field takes (2^22 pixels)");
-        return MTM_E_INVALID;
-    }
-    std::vector<BlockPassPlan> Q;
-    MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
-    const BlockValidate V{threshold, 4.0 * epsilon, valid};
-    const BlockDeform D{predicted};
-    return match_block_passes(c, I, Q, nullptr, method, out, nbhd, valid ? &V : nullptr, nullptr, &D);
-}
-
-int mtm_match_blocks_passes_steered(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
-                                    int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
-                                    const mtm_block_pass* passes, int n_passes, int method, double threshold, double epsilon,
-                                    mtm_hit* out, float* nbhd, uint8_t* valid, int32_t* predicted, int steer) {
-    const char* who = "mtm_match_blocks_passes_steered";
-    if (steer != 0 && steer != 1) {
-        set_error(std::string(who) + ": steer must be 0 (integer records) or 1 (refined positions) (got " + std::to_string(steer) +
-                  ")");
-        return MTM_E_INVALID;
-    }
-    if (steer == 0)
-        return mtm_match_blocks_passes_deformed(c, reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans,
-                                                dtype, passes, n_passes, method, threshold, epsilon, out, nbhd, valid, predicted);
-    if (valid) MTMC(check_validate_args(who, threshold, epsilon));
-    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
-    MTMC(check_block_pair(c, who, n_passes >= 1 && passes && out && predicted, method, I));
-    if ((long long)n_passes * std::max(rows, cols) > kDeformMaxDisp) {
-        set_error(std::string(who) + ": " + std::to_string(n_passes) + " passes over images of this size could pass the "
-                  "largest displacement the field takes (2^22 pixels)");
-        return MTM_E_INVALID;
-    }
-    std::vector<BlockPassPlan> Q;
-    MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
-    const BlockValidate V{threshold, 4.0 * epsilon, valid};
-    const BlockDeform D{predicted, 1};
-    return match_block_passes(c, I, Q, nullptr, method, out, nbhd, valid ? &V : nullptr, nullptr, &D);
+    return debug_block_run(c, who, {{c->blk_recs, sizeof(mtm_hit) * n, recs, nullptr}, {c->blk_valid, n, nullptr, valid},
+                                    {c->blk_steer, sizeof(mtm_hit) * n, nullptr, steer}}, [&] {
+        return launch_lanes(c, blocks_validate_kernel, n, c->blk_recs.as<mtm_hit>(), nx, ny, sx, sy, threshold, e4,
+                            c->blk_valid.as<uint8_t>(), c->blk_steer.as<mtm_hit>());
+    });
 }
 
 int mtm_debug_steer_q8(mtm_ctx* c, const mtm_hit* recs, const float* nbhd, const int32_t* predicted, const uint8_t* valid,
@@ -1142,36 +779,22 @@ int mtm_debug_steer_q8(mtm_ctx* c, const mtm_hit* recs, const float* nbhd, const
         }
         return MTM_OK;
     }
-    MTM_NOT_IN_FLIGHT(c, who);
-    HIPC(hipSetDevice(c->device));
-    MTMC(c->blk_recs.ensure(sizeof(mtm_hit) * n));
-    MTMC(c->blk_nbhd.ensure(sizeof(float) * 9 * n));
-    MTMC(c->blk_pred.ensure(sizeof(int32_t) * 2 * n));
-    MTMC(c->blk_d8.ensure(sizeof(int32_t) * 2 * n));
-    MTMC(c->blk_disp.ensure(sizeof(int32_t) * 2 * n));
-    if (valid) {
-        MTMC(c->blk_valid.ensure(n));
-        MTMC(c->blk_steer.ensure(sizeof(mtm_hit) * n));
-        HIPC(hipMemcpyAsync(c->blk_valid.p, valid, n, hipMemcpyHostToDevice, c->stream));
-        HIPC(hipMemcpyAsync(c->blk_steer.p, steer_recs, sizeof(mtm_hit) * n, hipMemcpyHostToDevice, c->stream));
-    }
-    HIPC(hipMemcpyAsync(c->blk_recs.p, recs, sizeof(mtm_hit) * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_nbhd.p, nbhd, sizeof(float) * 9 * n, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->blk_pred.p, predicted, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    const dim3 grd((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(blocks_steer_q8_kernel, grd, dim3(256), 0, c->stream, c->blk_recs.as<mtm_hit>(), c->blk_nbhd.as<float>(),
-                       c->blk_pred.as<int32_t>(), valid ? c->blk_valid.as<uint8_t>() : nullptr,
-                       valid ? c->blk_steer.as<mtm_hit>() : nullptr, nx, ny, sx, sy, mode_min, c->blk_d8.as<int32_t>());
-    HIPC(hipGetLastError());
-    if (smooth) {
-        hipLaunchKernelGGL(blocks_smooth_q8_kernel, grd, dim3(256), 0, c->stream, c->blk_d8.as<int32_t>(), nx, ny,
-                           c->blk_disp.as<int32_t>());
-        HIPC(hipGetLastError());
-    }
-    HIPC(hipMemcpyAsync(out_q8, smooth ? c->blk_disp.p : c->blk_d8.p, sizeof(int32_t) * 2 * n, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    return MTM_OK;
+    const size_t rb = sizeof(mtm_hit) * n, pairs = sizeof(int32_t) * 2 * n;
+    return debug_block_run(
+        c, who,
+        {{c->blk_valid, valid ? n : 0, valid, nullptr}, {c->blk_steer, valid ? rb : 0, steer_recs, nullptr},
+         {c->blk_recs, rb, recs, nullptr}, {c->blk_nbhd, sizeof(float) * 9 * n, nbhd, nullptr},
+         {c->blk_pred, pairs, predicted, nullptr}, {c->blk_d8, pairs, nullptr, smooth ? nullptr : out_q8},
+         {c->blk_disp, pairs, nullptr, smooth ? out_q8 : nullptr}},
+        [&]() -> int {
+            MTMC(launch_lanes(c, blocks_steer_q8_kernel, n, c->blk_recs.as<mtm_hit>(), c->blk_nbhd.as<float>(),
+                              c->blk_pred.as<int32_t>(), valid ? c->blk_valid.as<uint8_t>() : nullptr,
+                              valid ? c->blk_steer.as<mtm_hit>() : nullptr, nx, ny, sx, sy, mode_min, c->blk_d8.as<int32_t>()));
+            if (!smooth) return MTM_OK;
+            return launch_lanes(c, blocks_smooth_q8_kernel, n, c->blk_d8.as<int32_t>(), nx, ny, c->blk_disp.as<int32_t>());
+        });
 }
+
 
 // mtm_deform_image (q8 = false: whole-pixel displacements within +-2^22) and mtm_deform_image_q8 (Q8 ones within +-2^30).
 static int deform_image_entry(const char* who, bool q8, mtm_ctx* c, const void* px, int64_t row_stride_bytes, int rows, int cols,
@@ -1283,41 +906,6 @@ int mtm_deform_image_q8(mtm_ctx* c, const void* px, int64_t row_stride_bytes, in
                               displacements_q8, out, out_stride_bytes);
 }
 
-int mtm_match_blocks_second(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
-                            int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
-                            const int32_t* offsets, int n_blocks, int margin, int method, mtm_hit* out, float* nbhd,
-                            int exclusion, mtm_hit* second) {
-    const char* who = "mtm_match_blocks_second";
-    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
-    MTMC(check_block_pair(c, who, n_blocks >= 0 && margin >= 0 && exclusion >= 0 && second && (n_blocks == 0 || (blocks && out)),
-                          method, I));
-    std::vector<BlockPassPlan> Q(1);
-    Q[0].grid = BlockGrid{};
-    Q[0].margin = margin;
-    MTMC(plan_blocks(rows, cols, chans, dtype, blocks, n_blocks, margin, 4 * (long long)c->boxes_max_floats, who, Q[0].plan,
-                     false));
-    if (n_blocks == 0) return MTM_OK;
-    MTMC(fix_block_tiles(Q[0].plan, rows, cols, blocks, margin, who));
-    Q[0].blocks.assign(blocks, blocks + n_blocks);
-    const BlockSecondOut X2{exclusion, second};
-    return match_block_passes(c, I, Q, offsets, method, out, nbhd, nullptr, &X2);
-}
-
-int mtm_match_blocks_passes_second(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
-                                   int64_t image_stride_bytes, int rows, int cols, int chans, int dtype,
-                                   const mtm_block_pass* passes, int n_passes, int method, double threshold, double epsilon,
-                                   mtm_hit* out, float* nbhd, uint8_t* valid, int exclusion, mtm_hit* second) {
-    const char* who = "mtm_match_blocks_passes_second";
-    if (valid) MTMC(check_validate_args(who, threshold, epsilon));      // (ahead of everything else, as the validated call)
-    const BlockPair I{reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype};
-    MTMC(check_block_pair(c, who, n_passes >= 1 && passes && out && exclusion >= 0 && second, method, I));
-    std::vector<BlockPassPlan> Q;
-    MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
-    const BlockValidate V{threshold, 4.0 * epsilon, valid};
-    const BlockSecondOut X2{exclusion, second};
-    return match_block_passes(c, I, Q, nullptr, method, out, nbhd, valid ? &V : nullptr, &X2);
-}
-
 int mtm_debug_second_peaks(mtm_ctx* c, const float* planes, int n, const int32_t* oh, const int32_t* ow, const int32_t* firsts,
                            int mode_min, int exclusion, mtm_hit* out) {
     const char* who = "mtm_debug_second_peaks";
@@ -1349,35 +937,31 @@ int mtm_debug_second_peaks(mtm_ctx* c, const float* planes, int n, const int32_t
         }
         return MTM_OK;
     }
-    MTM_NOT_IN_FLIGHT(c, who);
-    HIPC(hipSetDevice(c->device));
     std::vector<TrackUnit> units((size_t)n);
     for (int k = 0; k < n; ++k) units[(size_t)k] = TrackUnit{k, 0, 0, oh[k], ow[k]};
     const std::vector<mtm_block> blocks((size_t)n, mtm_block{0, 0, 0, 0});
     const size_t nn = (size_t)n;
-    const struct { DevBuf& buf; const void* src; size_t bytes; } up[] = {
-        {c->blk_plane, planes, sizeof(float) * total},      {c->blk_poff, poff.data(), sizeof(long long) * nn},
-        {c->blk_units, units.data(), sizeof(TrackUnit) * nn}, {c->blk_blocks, blocks.data(), sizeof(mtm_block) * nn},
-        {c->blk_keys, first.data(), sizeof(unsigned long long) * nn}};
-    for (const auto& u : up) MTMC(u.buf.ensure(u.bytes));
-    MTMC(c->blk_keys2.ensure(sizeof(unsigned long long) * nn));
-    MTMC(c->blk_recs2.ensure(sizeof(mtm_hit) * nn));
-    for (const auto& u : up) HIPC(hipMemcpyAsync(u.buf.p, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
-    MTMC(for_launch_slices(0, nn, [&](size_t k0, unsigned nk) -> int {
-        hipLaunchKernelGGL(blocks_second_kernel, dim3(nk), dim3(256), 0, c->stream, c->blk_units.as<TrackUnit>(),
-                           c->blk_keys.as<unsigned long long>(), c->blk_plane.as<float>(), c->blk_poff.as<long long>(), (int)k0,
-                           mode_min, exclusion, c->blk_keys2.as<unsigned long long>());
-        HIPC(hipGetLastError());
-        return MTM_OK;
-    }));
-    hipLaunchKernelGGL(blocks_second_record_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, c->stream,
-                       c->blk_units.as<TrackUnit>(), c->blk_keys2.as<unsigned long long>(), c->blk_blocks.as<mtm_block>(), n,
-                       mode_min, c->blk_recs2.as<mtm_hit>());
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(out, c->blk_recs2.p, sizeof(mtm_hit) * nn, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    return MTM_OK;
+    const size_t kb = sizeof(unsigned long long) * nn;
+    return debug_block_run(
+        c, who,
+        {{c->blk_plane, sizeof(float) * total, planes, nullptr}, {c->blk_poff, sizeof(long long) * nn, poff.data(), nullptr},
+         {c->blk_units, sizeof(TrackUnit) * nn, units.data(), nullptr}, {c->blk_blocks, sizeof(mtm_block) * nn, blocks.data(), nullptr},
+         {c->blk_keys, kb, first.data(), nullptr}, {c->blk_keys2, kb, nullptr, nullptr},
+         {c->blk_recs2, sizeof(mtm_hit) * nn, nullptr, out}},
+        [&]() -> int {
+            MTMC(for_launch_slices(0, nn, [&](size_t k0, unsigned nk) -> int {
+                hipLaunchKernelGGL(blocks_second_kernel, dim3(nk), dim3(256), 0, c->stream, c->blk_units.as<TrackUnit>(),
+                                   c->blk_keys.as<unsigned long long>(), c->blk_plane.as<float>(), c->blk_poff.as<long long>(),
+                                   (int)k0, mode_min, exclusion, c->blk_keys2.as<unsigned long long>());
+                HIPC(hipGetLastError());
+                return MTM_OK;
+            }));
+            return launch_lanes(c, blocks_second_record_kernel, nn, c->blk_units.as<TrackUnit>(),
+                                c->blk_keys2.as<unsigned long long>(), c->blk_blocks.as<mtm_block>(), n, mode_min,
+                                c->blk_recs2.as<mtm_hit>());
+        });
 }
+
 
 int mtm_match_blocks(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
                      int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,

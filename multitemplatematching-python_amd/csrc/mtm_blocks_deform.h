@@ -1,7 +1,7 @@
 // Window deformation between the passes of a block-matching call (mtm_match_blocks_passes_deformed, mtm_deform_image;
 // DESIGN 5.6.4): the displacement field interpolated from a coarse grid's displacements and the bilinear warp of an
 // image by it, as inline functions for the host (mtm_deform_image without a context, the weight tables of a call) and
-// the device (deform_image_kernel, mtm_k_deform.hip.h; blocks_deform_record_kernel, mtm_blocks.hip) - a single source
+// the device (deform_image_kernel, mtm_k_deform.hip.h; blocks_deform_record_kernel, mtm_k_blocks.hip.h) - a single source
 // for the rule, so that the pixels a test computes on the host are the pixels the kernel writes.  Integers only.
 // (MTM.blocks.displacement_field, field_at and deform state the same rule in numpy.)
 //

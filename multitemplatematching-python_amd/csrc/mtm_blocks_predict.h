@@ -1,6 +1,6 @@
 // Where a block's search box goes when a displacement is predicted for it (mtm_match_blocks_at, mtm_match_blocks_passes;
 // DESIGN 5.6.2), as inline functions for the host (plan_block_passes' callers, mtm_debug_plan_blocks_passes: mtm_host.cpp)
-// and the device (blocks_unit_kernel, mtm_blocks.hip): a single source for the nearest-block rule and for the moved,
+// and the device (blocks_unit_kernel, mtm_k_blocks.hip.h): a single source for the nearest-block rule and for the moved,
 // clamped and clipped box, so that the boxes a test computes on the host are the boxes the kernels search.  Integers only.
 #pragma once
 #include <cstdint>

@@ -1,6 +1,6 @@
 // The second correlation peak of a block's map (mtm_match_blocks_second, mtm_match_blocks_passes_second),
 // as inline functions for the host (mtm_debug_second_peaks without a context) and the device (blocks_second_kernel,
-// mtm_blocks.hip): a single source for which cells the first peak excludes and for the key a cell competes with, so that
+// mtm_k_blocks.hip.h): a single source for which cells the first peak excludes and for the key a cell competes with, so that
 // the second peak a test computes on the host is the one the kernel finds.  The cells are ordered as the first peak's key
 // orders them (win_merge_key: order(quality) << 32 | ~row-major index, quality = score, or -score for the difference
 // methods): larger quality first, -0 equal to +0, ties to the smaller index.

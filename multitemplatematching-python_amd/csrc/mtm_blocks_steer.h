@@ -1,7 +1,7 @@
 // Sub-pixel steering of the deformed passes of a block-matching call (mtm_match_blocks_passes_steered with steer = 1,
 // mtm_debug_steer_q8): the displacement that steers pass p + 1 comes from pass p's fitted position in Q8
 // (1/256 pixel) and is filtered by a 3 x 3 binomial kernel over the grid.  Inline functions for the host
-// (mtm_debug_steer_q8 without a context) and the device (blocks_steer_q8_kernel, blocks_smooth_q8_kernel, mtm_blocks.hip) -
+// (mtm_debug_steer_q8 without a context) and the device (blocks_steer_q8_kernel, blocks_smooth_q8_kernel, mtm_k_blocks.hip.h) -
 // a single source for the rule.  (MTM.subpixel.fit_offsets, MTM.blocks.to_q8 and smooth_displacements state it in numpy.)
 #pragma once
 #include <cmath>

@@ -1,7 +1,7 @@
 // The outlier test a pass's records go through before they steer the next pass (mtm_match_blocks_passes_validated,
 // mtm_debug_validate_blocks): the normalised median test of Westerweel & Scarano over the displacements of a
 // block's 3 x 3 grid neighbourhood, as one inline function for the host (mtm_debug_validate_blocks without a context) and
-// the device (blocks_validate_kernel, mtm_blocks.hip) - a single source for the rule, so that the flags a test computes on
+// the device (blocks_validate_kernel, mtm_k_blocks.hip.h) - a single source for the rule, so that the flags a test computes on
 // the host are the flags the kernel writes.  (MTM.blocks.validate states the same rule in numpy.)  Integers, and one
 // rounded float64 addition and one rounded float64 multiplication per component: no product is fused into a sum on
 // either side (the device calls the _rn intrinsics, the library is built with -ffp-contract=off).

@@ -7,7 +7,7 @@
 // and those are never scored.
 // win_score_tile is the one body of the kernels that score a tile of a unit's map for one template - boxes_score_kernel
 // (mtm_boxes.hip), track_score_kernel and track_reacquire_kernel (mtm_track.hip), blocks_score_kernel and
-// blocks_plane_kernel (mtm_blocks.hip): the sums, the lane's output and whether it lies in the map, and the float32 score
+// blocks_plane_kernel (mtm_k_blocks.hip.h): the sums, the lane's output and whether it lies in the map, and the float32 score
 // (win_score) handed to the kernel's sink, which stores it, merges it into a key (win_merge_key) or adds it to a plane.
 // That these kernels give the same float32 bits rests on this one function.  pyr_window_kernel (mtm_pyramid.hip, uint8
 // only) calls win_tile_sums_u8 and win_score itself inside its tile loop: with win_score_tile as the loop's body its
@@ -326,7 +326,7 @@ __device__ __forceinline__ unsigned long long win_pos_word(int y, int x, int ow)
 // The key of this lane's output - order(quality) << 32 | pos (win_pos_word), quality score() or its negative for the
 // difference methods; 0 for a lane outside the map, which never calls score() -, reduced per wave and merged into *slot
 // with one atomicMax per wave, as boxes_peaks_kernel keys a unit's extremum in global mode.  Every lane of the wave calls
-// it (the shuffles).  (The tracking score kernels, mtm_track.hip, and blocks_score_kernel, mtm_blocks.hip.)
+// it (the shuffles).  (The tracking score kernels, mtm_track.hip, and blocks_score_kernel, mtm_k_blocks.hip.h.)
 template <class Score>
 __device__ __forceinline__ void win_merge_key(bool inside, unsigned long long pos, int mode_min, Score&& score,
                                               unsigned long long* __restrict__ slot) {

@@ -1,7 +1,7 @@
 // The 64-bit keys the score kernels reduce a map to (win_merge_key, extremum_kernel: order(value) << 32 | ~row-major
 // index, merged by atomicMax) read back, as inline functions for the host (decode_quality_key and decode_extremum_key,
 // mtm_host.cpp; decode_block_keys, mtm_blocks.hip) and the device (track_record, mtm_track.hip; blocks_record_kernel and
-// blocks_nbhd_kernel, mtm_blocks.hip): a single source for the order word's float32, the index and the record, so that
+// blocks_nbhd_kernel, mtm_k_blocks.hip.h): a single source for the order word's float32, the index and the record, so that
 // the record a call decodes on the host is the record a kernel writes, bit for bit.  key_float_order forms the order word
 // where host and device share the code that builds a key (mtm_blocks_second.h).
 #pragma once

@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes, mtm_match_blocks_passes_validated, mtm_debug_validate_blocks, mtm_match_blocks_second, mtm_match_blocks_passes_second, mtm_debug_second_peaks, mtm_deform_image, mtm_match_blocks_passes_deformed, mtm_debug_maskf32_screen, mtm_match_blocks_passes_steered, mtm_deform_image_q8, mtm_debug_steer_q8 - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes, mtm_match_blocks_passes_validated, mtm_debug_validate_blocks, mtm_match_blocks_second, mtm_match_blocks_passes_second, mtm_debug_second_peaks, mtm_deform_image, mtm_match_blocks_passes_deformed, mtm_debug_maskf32_screen, mtm_match_blocks_passes_steered, mtm_deform_image_q8, mtm_debug_steer_q8, mtm_debug_tail_consts - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -246,6 +246,20 @@ int         mtm_debug_templ_stats(const void* px, int rows, int cols, int chans,
  * cap_classes classes go to `out`; returns the number of classes, or a negative MTM_E_* code (no template set placed). */
 #define MTM_CLASS_TILING_FIELDS 13
 int         mtm_debug_class_tilings(mtm_ctx* ctx, int32_t* out, int cap_classes);
+/* Test support (added under ABI 9).  The tail screen's constants (csrc/mtm_kernels.h: TemplDev::tail_k / tail_d / tail_g,
+ * written on the device by tail_consts_kernel) of every template of the set placed on the context, copied back from the
+ * device: MTM_TAIL_CONST_FIELDS doubles per template, in the order of the template list - k0, k1, d0, d1, g0, g1 ([0]: the
+ * wave's first output row, template rows 0 .. split - 1 accumulated; [1]: its second, rows 0 .. split - 2), valid_split (the
+ * split the context takes them to hold for: a launch with another one re-derives them first; 0 = none).  split == 0
+ * launches nothing and reports what the device holds.  split > 0: every placed class that can screen its K loop (tail_ok)
+ * first re-derives its constants for that split, clamped to [6, h - 2], on the context's stream, and the context records
+ * that split as the one they hold for - what a search call with that split does ahead of its first score launch, so a later
+ * search re-derives or re-uses them exactly as it would behind such a call.  Templates of classes without a screen: NaN in
+ * the six constants, valid_split -1.  MTM_E_STATE: no template set is placed (run a search first); MTM_E_INVALID: a
+ * mtm_find_matches_async call is in flight, split < 0; MTM_E_OVERFLOW: n_out (the doubles `out` holds) is below
+ * MTM_TAIL_CONST_FIELDS times the number of templates. */
+#define MTM_TAIL_CONST_FIELDS 7
+int         mtm_debug_tail_consts(mtm_ctx* ctx, int split, double* out, int64_t n_out);
 /* Test support (added under ABI 9; needs no image and no templates on the context).  The device's share of the non-maxima
  * suppression of mtm_find_matches_image_nms - the counting sort by grid cell, the champion pass, the prune pass - on a hit
  * list the caller hands over: the n records of `hits` and the count n go to device memory, the grid is the one a

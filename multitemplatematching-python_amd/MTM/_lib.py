@@ -158,6 +158,7 @@ SYMBOLS = {
     "mtm_debug_quotient_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, _P(ctypes.c_uint64)]),
     "mtm_debug_tail_split": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double]),
     "mtm_debug_class_tilings": (ctypes.c_int, [ctypes.c_void_p, _P(ctypes.c_int32), ctypes.c_int]),
+    "mtm_debug_tail_consts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _P(ctypes.c_double), ctypes.c_int64]),
     "mtm_debug_templ_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_int, _P(ctypes.c_double)]),
     "mtm_debug_device_nms": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
@@ -522,6 +523,10 @@ CLASS_TILING_FIELDS = ("h", "w", "n_templates", "kernel", "rm_nt", "rm_R", "kp_n
                        "slab_nt", "dot_variant")
 
 
+# the doubles of one mtm_debug_tail_consts record (MTM_TAIL_CONST_FIELDS of them)
+TAIL_CONST_FIELDS = ("k0", "k1", "d0", "d1", "g0", "g1", "valid_split")
+
+
 def debug_tail_split(h, w, thr):
     """Test support (mtm_debug_tail_split; needs no GPU): the K steps after which the two-row score kernel of an h x w
     class screens its waves at the candidate threshold `thr`, 0 = unscreened."""
@@ -810,6 +815,19 @@ class Context(_RecordMemo):
         buf = (ctypes.c_int32 * (nf * max(n, 1)))()
         check(min(self._lib.mtm_debug_class_tilings(self._h, buf, n), 0), "mtm_debug_class_tilings")
         return [dict(zip(CLASS_TILING_FIELDS, buf[k * nf:(k + 1) * nf])) for k in range(n)]
+
+    def debug_tail_consts(self, split=0):
+        """Test support (mtm_debug_tail_consts): the tail screen's constants of every template of the set placed on the
+        context, as the device holds them -> an (n_templ, 7) float64 array of TAIL_CONST_FIELDS (k, d, g of the wave's first
+        and second output row; valid_split: the split the context takes them to hold for).  split > 0 first re-derives them
+        for that split (clamped to [6, h - 2]) in every class that can screen, as a search call with that split would;
+        split == 0 launches nothing.  Templates of classes without a screen: NaN, valid_split -1."""
+        nf = len(TAIL_CONST_FIELDS)
+        n = sum(r["n_templates"] for r in self.class_tilings())
+        out = np.zeros((n, nf), dtype=np.float64)
+        check(self._lib.mtm_debug_tail_consts(self._h, int(split), out.ctypes.data_as(_P(ctypes.c_double)), out.size),
+              "mtm_debug_tail_consts")
+        return out
 
     def debug_quotient_check(self, n_cases=1 << 28, seed=1):
         """Test support (mtm_debug_quotient_check): the epilogue's division-free quotient against the IEEE division on

@@ -1,6 +1,7 @@
 // libmtm_hip.so - the context: creation, options, the device copies of an image (upload, layout conversion).
 // gfx950 (MI355X / CDNA4) only; built by multitemplatematching-python_amd/build.py.
 #include <cstdio>
+#include <limits>
 #include "mtm_ctx.h"
 
 using namespace mtm;
@@ -600,6 +601,52 @@ int mtm_debug_class_tilings(mtm_ctx* c, int32_t* out, int cap_classes) {
         r[12] = (size_t)k < c->dot_last.size() ? c->dot_last[(size_t)k] : -1;
     }
     return n;
+}
+
+// ---- test support: the tail screen's constants as the device holds them (mtm_debug_tail_consts) -------------------------
+// split == 0 launches nothing.  split > 0 does, for every class that can screen, what ensure_tail_consts does for one
+// (csrc/mtm_launch.hip): the clamp of tail_split_for's forced branch, launch_tail_consts on the context's stream, tail_valid.
+int mtm_debug_tail_consts(mtm_ctx* c, int split, double* out, int64_t n_out) {
+    if (!c || !out || split < 0) return MTM_E_INVALID;
+    MTM_NOT_IN_FLIGHT(c, "mtm_debug_tail_consts");
+    if (!c->placed) {
+        set_error("mtm_debug_tail_consts: no template set is placed (run a search first)");
+        return MTM_E_STATE;
+    }
+    const size_t n = c->td_host.size();
+    if (n_out < (int64_t)(MTM_TAIL_CONST_FIELDS * n)) {
+        set_error("mtm_debug_tail_consts: out holds fewer than MTM_TAIL_CONST_FIELDS doubles per template");
+        return MTM_E_OVERFLOW;
+    }
+    HIPC(hipSetDevice(c->device));
+    auto screens = [](const mtm_ctx::SizeClass& sc) { return sc.tail_ok && sc.kernel == MTM_KERNEL_MFMA && !sc.members.empty(); };
+    if (split > 0)
+        for (size_t k = 0; k < c->classes.size(); ++k) {
+            const mtm_ctx::SizeClass& sc = c->classes[k];
+            if (!screens(sc)) continue;
+            const int s = std::max(6, std::min(split, sc.h - 2));
+            MTMC(mtmi::launch_tail_consts(c, sc, s, c->stream));
+            if (k < c->tail_valid.size()) c->tail_valid[k] = s;
+        }
+    std::vector<mtm::TemplDev> td(n);
+    HIPC(hipStreamSynchronize(c->stream));
+    if (n) HIPC(hipMemcpy(td.data(), c->td.p, sizeof(mtm::TemplDev) * n, hipMemcpyDeviceToHost));
+    for (size_t t = 0; t < n; ++t) {
+        double* r = out + MTM_TAIL_CONST_FIELDS * t;
+        for (int f = 0; f < MTM_TAIL_CONST_FIELDS - 1; ++f) r[f] = std::numeric_limits<double>::quiet_NaN();
+        r[MTM_TAIL_CONST_FIELDS - 1] = -1.0;
+    }
+    for (size_t k = 0; k < c->classes.size(); ++k) {
+        const mtm_ctx::SizeClass& sc = c->classes[k];
+        if (!screens(sc)) continue;
+        for (int t : sc.members) {
+            if (t < 0 || (size_t)t >= n) continue;
+            double* r = out + MTM_TAIL_CONST_FIELDS * (size_t)t;
+            for (int p = 0; p < 2; ++p) r[p] = td[(size_t)t].tail_k[p], r[2 + p] = td[(size_t)t].tail_d[p], r[4 + p] = td[(size_t)t].tail_g[p];
+            r[6] = k < c->tail_valid.size() ? (double)c->tail_valid[k] : 0.0;
+        }
+    }
+    return MTM_OK;
 }
 
 // ---- test support: quotient_as_float against the IEEE division it replaces (mtm_debug_quotient_check) -------------------

@@ -49,6 +49,22 @@ def test_class_tilings_record_matches_the_header(lib):
     assert list(out) == [-7] * n_fields
 
 
+def test_tail_consts_record_matches_the_header(lib):
+    """mtm_debug_tail_consts (test support): the binding's field list is as long as the header's record, in the header's
+    order, the header's ABI note names the entry, and the entry point refuses a null context or a null output."""
+    hdr = open(os.path.join(ROOT, "include", "mtm_hip.h")).read()
+    n_fields = int(re.search(r"#define\s+MTM_TAIL_CONST_FIELDS\s+(\d+)", hdr).group(1))
+    assert len(lib.TAIL_CONST_FIELDS) == n_fields == 7
+    comment = hdr[:hdr.index("#define MTM_TAIL_CONST_FIELDS")]
+    comment = comment[comment.rindex("/*"):]
+    pos = [comment.index(f) for f in lib.TAIL_CONST_FIELDS]
+    assert pos == sorted(pos), list(zip(lib.TAIL_CONST_FIELDS, pos))
+    assert "mtm_debug_tail_consts" in hdr[hdr.index("Bumped when"):hdr.index("#define MTM_ABI_VERSION")]
+    out = (ctypes.c_double * n_fields)(*([-7.0] * n_fields))
+    assert lib.load().mtm_debug_tail_consts(None, 0, out, n_fields) == -1
+    assert list(out) == [-7.0] * n_fields
+
+
 def test_peak_pass_block_matches_the_header(lib):
     """mtm_debug_peak_pass (test support): the binding's argument block has the header's fields in the header's order, the
     routes carry the header's numbers, and the entry point refuses null arguments."""

@@ -395,11 +395,14 @@ int collect_global_extremum(mtm_ctx* c, CallRoute& R, std::vector<mtm_hit>& hits
         HIPC(hipEventRecord(c->ev[2], c->stream));
         HIPC(hipMemcpyAsync(best.data(), c->counters.p, key_bytes, hipMemcpyDeviceToHost, c->stream));
         // refined: the outputs within the margin of their template's best are listed - more than the list holds?
-        unsigned long long nlisted = 0;
+        // ... or an output that cannot be screened at all (Bf16Params::nf_flag, the header's spare word)?
+        unsigned long long hdr[2] = {0ull, 0ull};
         const bool refined = R.refine && R.ext;
-        if (refined) HIPC(hipMemcpyAsync(&nlisted, c->cands.p, sizeof(nlisted), hipMemcpyDeviceToHost, c->stream));
+        if (refined) HIPC(hipMemcpyAsync(hdr, c->cands.p, sizeof(hdr), hipMemcpyDeviceToHost, c->stream));
         HIPC(hipStreamSynchronize(c->stream));
-        const LadderStep step = ladder_next(R, PassOutcome{false, refined && (int64_t)nlisted > R.cand_cap, false}, pass);
+        const unsigned long long nlisted = hdr[0];
+        const bool not_finite = refined && (unsigned)hdr[1] != 0u;
+        const LadderStep step = ladder_next(R, PassOutcome{not_finite, refined && (int64_t)nlisted > R.cand_cap, false}, pass);
         if (step == LadderStep::Done) {
             if (refined && R.bf16_np == 1) c->np1_backoff_len = 16;
             done = true;

@@ -30,11 +30,20 @@
 
 namespace mtm {
 
-// round-to-nearest-even bfloat16 bits of a finite float
+// round-to-nearest-even bfloat16 bits of a finite float; +-inf stays +-inf.  A NaN stays a NaN unless its payload carries
+// into the exponent (0x7FFF8000 .. 0x7FFFFFFF become -0.0) - harmless: every output that multiplies the pixel by a non-zero
+// tap has it in its window, so its statistics are NaN and the listing tests below send it to the exact chain.
 __device__ __forceinline__ uint32_t bf16_rne(float v) {
     const uint32_t b = __float_as_uint(v);
     return (b + 0x7FFFu + ((b >> 16) & 1u)) >> 16;
 }
+// THE RULE of the screen: an output whose accumulator or bound is not finite cannot be screened.  An accumulator is not
+// finite when a non-finite pixel lies under one of its taps - the zero taps w .. 32 nkb - 1 right of the window included
+// (0 * inf = NaN) -, when its tile's constant s_mu sampled one, or when its float32 sum overflowed (pixels near 2^60); the
+// window's own float64 statistics may be clean in all three cases and the float64 chain returns an ordinary score.  Threshold
+// modes list such an output; the global extremum and map mode raise a flag that takes the call to the float64 kernel.
+__device__ __forceinline__ bool bf_not_finite(float v) { return !(fabsf(v) <= 3.402823466e38f); }
+__device__ __forceinline__ bool bf_not_finite(double v) { return !(fabs(v) <= 1.7976931348623157e308); }
 // finish_unmasked on values already in registers (same arithmetic, same order)
 __device__ __forceinline__ float bf_finish(int method, double corr, const double (&t)[kMaxChans], double sum2, double sq,
                                            const BfTemplConst& T, int chans) {
@@ -524,14 +533,16 @@ __global__ __launch_bounds__(256, 2) void ncc_bf16_kernel(Bf16Params p, const Te
                     bool anyp = false;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        double num = (double)acc[mb][4 * half + i][e];
+                        const float av = acc[mb][4 * half + i][e];
+                        double num = (double)av;
                         if (p.chans == 1) {
                             num = fma(cm0, ts[i][0], num);
                         } else {
                             for (int cc = 0; cc < p.chans; ++cc)
                                 num = fma(method == MTM_TM_CCOEFF_NORMED ? T.centre[cc] - T.mean[cc] : T.centre[cc], ts[i][cc], num);
                         }
-                        anyp = anyp || fma(G, fs_E[i], num) > tnthr * sq[i];
+                        // (NaN-aware: what is not provably below stays - and raises the flag in the exact form below)
+                        anyp = anyp || bf_not_finite(av) || !(fma(G, fs_E[i], num) <= tnthr * sq[i]);
                     }
                     if (!anyp) {
                         skip = true;
@@ -556,6 +567,8 @@ __global__ __launch_bounds__(256, 2) void ncc_bf16_kernel(Bf16Params p, const Te
                     // B - thr by the same d.  Constant templates take the exact test as well.
                     const double tn = T.templ_norm, G = T.bfac * tn;
                     bool anyp = p.list_all != 0 || T.all_ones != 0 || !(tn > 0.0) || fs_wide;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) anyp = anyp || bf_not_finite(acc[mb][4 * half + i][e]);     // (the rule above)
                     double cm[kMaxChans];
 #pragma unroll
                     for (int cc = 0; cc < kMaxChans; ++cc)
@@ -581,16 +594,18 @@ __global__ __launch_bounds__(256, 2) void ncc_bf16_kernel(Bf16Params p, const Te
                         double num = numv[i];
                         if (method == MTM_TM_SQDIFF_NORMED) num = fmax(fma(-2.0, num, s2[i] + ts2), 0.0);
                         const double lhs = fma(Gs, fs_E[i], num), rhs = tn * fs_P[i];
-                        anyp = anyp || (p.cand_min ? lhs < rhs : lhs > rhs);
+                        anyp = anyp || (p.cand_min ? !(lhs >= rhs) : !(lhs <= rhs));        // (NaN-aware: a NaN is listed)
                     }
                     skip = !anyp;
                 }
                 if (!skip) {
                 float out[4];
                 double qv[4], Mv[4];        // rig: quality before the saturation rules, bound of its error
+                bool nf[4];                 // the rule above: accumulator, quality or bound not finite
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    double corr = (double)acc[mb][4 * half + i][e];
+                    const float av = acc[mb][4 * half + i][e];
+                    double corr = (double)av;
 #pragma unroll
                     for (int cc = 0; cc < kMaxChans; ++cc)
                         if (cc < p.chans) corr += T.centre[cc] * ts[i][cc];
@@ -601,6 +616,7 @@ __global__ __launch_bounds__(256, 2) void ncc_bf16_kernel(Bf16Params p, const Te
                     qv[i] = p.cand_min ? -r : r;
                     // (+ the rounding of the exact score to float32 and of this arithmetic)
                     Mv[i] = ex ? 0.0 : bp[i] * T.bfac + 3e-7 * fmax(1.0, fabs(r));
+                    nf[i] = bf_not_finite(av) || bf_not_finite(qv[i] + Mv[i]);
                 }
                 const int xb = xq + 4 * half;
                 if (rig_n && p.rig_flag != nullptr) {
@@ -609,8 +625,16 @@ __global__ __launch_bounds__(256, 2) void ncc_bf16_kernel(Bf16Params p, const Te
                     bool wide = false;
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
-                        wide = wide || (xb + i < p.ow && Mv[i] > (double)p.rig_cap && (p.list_all || qv[i] + Mv[i] > (double)p.rig_thr));
+                        wide = wide || (xb + i < p.ow && (nf[i] || (Mv[i] > (double)p.rig_cap &&
+                                                                      (p.list_all || qv[i] + Mv[i] > (double)p.rig_thr))));
                     if (wide) *p.rig_flag = 1u;
+                }
+                if (p.ext_on && p.nf_flag != nullptr) {
+                    // refined global extremum: a NaN is neither a key nor a listing below - the exact best may sit on it
+                    bool any_nf = false;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) any_nf = any_nf || (xb + i < p.ow && nf[i]);
+                    if (any_nf) *p.nf_flag = 1u;
                 }
                 float key_v[4] = {out[0], out[1], out[2], out[3]};      // what the published key is built from
                 if (p.ext_on && p.ext_raw && rig_n) {
@@ -675,7 +699,7 @@ __global__ __launch_bounds__(256, 2) void ncc_bf16_kernel(Bf16Params p, const Te
                     bool pass[4], any = false;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        pass[i] = xb + i < p.ow && (p.list_all != 0 || qv[i] + Mv[i] > (double)p.rig_thr);
+                        pass[i] = xb + i < p.ow && (p.list_all != 0 || nf[i] || qv[i] + Mv[i] > (double)p.rig_thr);
                         any = any || pass[i];
                     }
                     if (any) {

@@ -72,6 +72,9 @@ struct Bf16Params {
     float rig_cap;
     float rig_thr;           // the exact quality threshold (score_threshold, negated for minima)
     unsigned int* rig_flag;
+    // the refined global extremum: set when an output's accumulator, quality or bound is not finite (mtm_bf16.hip.h, "the
+    // rule") - the host then takes the float64 kernel, as for rig_flag.  nullptr: not wanted (threshold modes list instead)
+    unsigned int* nf_flag;
     // Round 6 (masked float32 templates, mtm_maskf32.hip.h): the constant a work item subtracted from its tile, per (row
     // block, segment) - mu_out[yb * nseg + seg], single-channel launches - so that a later pass can restate this launch's
     // error bound eps * sqrt(sum (I - mu)^2 ...) with the very constant that was used.  nullptr: not wanted

@@ -260,7 +260,10 @@ bool fused_count_trivial(long long n_peaks, int oh, int ow) { return n_peaks == 
 
 LadderStep ladder_next(const mtmi::CallRoute& R, const PassOutcome& o, int attempt) {
     if (R.mode == MTM_PEAKS_GLOBAL) {
-        if (!(R.refine && R.ext) || !o.cands_overflow) return LadderStep::Done;
+        if (!(R.refine && R.ext)) return LadderStep::Done;
+        // an output whose accumulator or bound is not finite cannot be screened (Bf16Params::nf_flag): the float64 kernel
+        if (o.rig_wide) return LadderStep::Float64;
+        if (!o.cands_overflow) return LadderStep::Done;
         // the one-product screen's bounds let more outputs reach their template's best than the list holds: three products;
         // still more within the margin of their template's best (near-flat maps): the float64 kernel
         return R.bf16_np == 1 ? LadderStep::ThreeProducts : LadderStep::Float64;

@@ -102,7 +102,7 @@ enum class LadderStep {
     GrowListLeaveSegments,  // ... and the flagged segments' bounded lists were the reason: the full scan's single list
 };
 struct PassOutcome {
-    bool rig_wide;          // map scan: a bound beyond its tolerances
+    bool rig_wide;          // map scan: a bound beyond its tolerances; map scan and refined global extremum: an output not finite
     bool cands_overflow;    // more candidates (global extremum: outputs within the margin of the best) than the list holds
     bool hits_overflow;     // more peaks than the hit list holds
 };

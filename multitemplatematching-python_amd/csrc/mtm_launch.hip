@@ -1151,6 +1151,8 @@ static int launch_bf16(mtm_ctx* c, CallRoute& R, const SizeClass& sc, const Stat
         p.cand_on = 1;
         p.hits_only = 1;
         p.ext_margin = R.refine ? kRefineThrMargin : 0.0f;
+        // (the spare word of the candidate header, as rig_flag in map mode: collect_global_extremum reads it with the count)
+        if (R.refine) p.nf_flag = reinterpret_cast<unsigned int*>(c->cands.as<uint8_t>() + 8);
         if (raw_m && R.refine) {
             // rigorous bounds instead of a relative margin (Bf16Params::ext_raw): 2^-15 for the dropped piece products
             // and the two 16-bit representations, 2^-24 per float32 accumulation (three MFMAs per 32-tap block)

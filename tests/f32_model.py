@@ -280,3 +280,230 @@ def tolerances(img, templ, method, pieces=3):
     chans, h, nkb = t3.shape[2], t3.shape[0], nkb_of(t3.shape[1])
     return (np.where(live, accum_eps(chans, h, nkb, pieces) * f + 3e-7, 0.0),
             np.where(live, rig_eps(chans, h, nkb, pieces) * f + 3e-7, 0.0), live)
+
+
+# ---- scenes beyond the range the geometry sweep covers -------------------------------------------------------------------
+# The cells of tests/test_gpu_f32_range.py: the smallest ones that still reach each code form of the kernel.
+RANGE_CELLS = [
+    dict(name="12x20", h=12, w=20, n=4, chans=1, out=(9, 133)),         # nkb 1, 12 padded taps
+    dict(name="5x33", h=5, w=33, n=4, chans=1, out=(9, 133)),           # nkb 2, 31 padded taps: the widest reach
+    dict(name="5x64", h=5, w=64, n=4, chans=1, out=(9, 133)),           # no padded tap: the control
+    dict(name="33x97", h=33, w=97, n=4, chans=1, out=(5, 41)),          # nkb 4, two K chunks of 32 rows
+    dict(name="24x40-n17", h=24, w=40, n=17, chans=1, out=(9, 133)),    # MB = 2, two template groups
+    dict(name="7x40-c3", h=7, w=40, n=4, chans=3, out=(9, 133)),        # channels
+]
+# power-of-two factors: every scaled scene is the base scene exactly (float32 scaling by 2^k neither rounds nor leaves the
+# normal range at these magnitudes)
+SCALES = {"up40": 40, "down20": -20, "down40": -40, "huge": 60, "tiny": -60}
+IN_RANGE = ("up40", "down20", "down40")
+BASE_NOISE = 10.0           # the noisy templates' noise in base units (the geometry sweep's, noise+ and signed)
+NAN_PAYLOAD = 0x7FFFFFFF    # bad pixel (d): a NaN whose payload carries into the exponent under bf16_rne's rounding add
+FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def _range_rng(*key):
+    import zlib
+    return np.random.default_rng(zlib.crc32("/".join(str(k) for k in key).encode()))
+
+
+def tile_samples(rows, cols, oh, ow, h, w):
+    """{(row, column)} of every work item's 8 x 8 sample grid (tile_mu's addresses)."""
+    lds_cols = SEG + 32 * nkb_of(w)
+    out = set()
+    for y0 in range(0, oh, ROWS):
+        for x0 in range(0, ow, SEG):
+            sr = np.minimum(y0 + (np.arange(8) * (h + ROWS - 2)) // 7, rows - 1)
+            sc = np.minimum(x0 + (np.arange(8) * (lds_cols - 1)) // 7, cols - 1)
+            out |= {(int(r), int(c)) for r in sr for c in sc}
+    return out
+
+
+def _not_finite(img):
+    return ~np.isfinite(_as3d(img)).all(axis=2)
+
+
+def kernel_reach(img, h, w):
+    """The outputs whose accumulators see a non-finite operand: the work item's sample grid holds one (s_mu, subtracted from
+    every pixel of the tile), or one lies in rows y .. y + h - 1 and columns x .. x + 32 nkb - 1 - the taps w .. 32 nkb - 1
+    carry zero template pieces and still multiply the pixels right of the window (0 * NaN = NaN).  The staging loop of
+    ncc_bf16_kernel fills lds_cols = 128 + 32 nkb columns from the tile's first column; an output at column x reads columns
+    x - x0 .. x - x0 + 32 nkb - 1 of it.  Beyond the image the staged pixels are the zero padding."""
+    nf = _not_finite(img)
+    rows, cols = nf.shape
+    oh, ow = rows - h + 1, cols - w + 1
+    span = 32 * nkb_of(w)
+    lds_cols = SEG + span
+    out = np.zeros((oh, ow), bool)
+    for y0 in range(0, oh, ROWS):
+        for x0 in range(0, ow, SEG):
+            sr = np.minimum(y0 + (np.arange(8) * (h + ROWS - 2)) // 7, rows - 1)
+            sc = np.minimum(x0 + (np.arange(8) * (lds_cols - 1)) // 7, cols - 1)
+            tile_bad = bool(nf[np.ix_(sr, sc)].any())
+            for y in range(y0, min(y0 + ROWS, oh)):
+                for x in range(x0, min(x0 + SEG, ow)):
+                    out[y, x] = tile_bad or bool(nf[y:y + h, x:x + span].any())
+    return out
+
+
+def window_dirty(img, h, w):
+    """The outputs whose own window holds a non-finite pixel."""
+    nf = _not_finite(img)
+    oh, ow = nf.shape[0] - h + 1, nf.shape[1] - w + 1
+    return np.array([[bool(nf[y:y + h, x:x + w].any()) for x in range(ow)] for y in range(oh)])
+
+
+def engine_stats_dirty(img, h, w):
+    """The outputs whose window statistics the engine's running sums poison.  hsum_kernel / hsum_lds_kernel: a thread sums
+    columns x0 .. x0 + w - 1 of a row (x0 a multiple of 16), stores, and slides 16 times (s += I[x + w] - I[x]); once a
+    non-finite pixel has entered the sum it stays (inf - inf = NaN).  vsum_stats_kernel: the same down a column of those
+    sums, restarting every 32 output rows.  So a bad pixel reaches right and downward, to the end of its segment."""
+    nf = _not_finite(img)
+    rows, cols = nf.shape
+    oh, ow = rows - h + 1, cols - w + 1
+    hs = np.zeros((rows, ow), bool)
+    for r in range(rows):
+        for x0 in range(0, ow, 16):
+            dirty = False
+            for dx in range(w):
+                dirty = dirty or bool(nf[r, x0 + dx])
+            for k in range(16):
+                x = x0 + k
+                if x >= ow:
+                    break
+                hs[r, x] = dirty
+                if x + w < cols:                        # (the zero padding beyond the row is finite)
+                    dirty = dirty or bool(nf[r, x + w])
+    out = np.zeros((oh, ow), bool)
+    for x in range(ow):
+        for y0 in range(0, oh, 32):
+            dirty = False
+            for dy in range(h):
+                dirty = dirty or bool(hs[y0 + dy, x])
+            for y in range(y0, min(y0 + 32, oh)):
+                out[y, x] = dirty
+                if y + 1 < min(y0 + 32, oh):
+                    dirty = dirty or bool(hs[y + h, x])
+    return out
+
+
+def window_scores(img, templ, method, points):
+    """cv2.matchTemplate's epilogue on sums taken window by window in float64 - no cumulative sums, so a non-finite pixel
+    touches the windows that hold it and no other: float32 scores at `points` [(y, x)]."""
+    img3, t3 = _as3d(img), _as3d(templ)
+    h, w, chans = t3.shape
+    T = t3.astype(np.float64)
+    corr = np.zeros(len(points))
+    S1 = [np.zeros(len(points)) for _ in range(chans)]
+    S2 = np.zeros(len(points))
+    for i, (y, x) in enumerate(points):
+        W = img3[y:y + h, x:x + w].astype(np.float64)
+        for c in range(chans):
+            corr[i] += float((W[:, :, c] * T[:, :, c]).sum())
+            S1[c][i] = float(W[:, :, c].sum())
+            S2[i] += float((W[:, :, c] * W[:, :, c]).sum())
+    with np.errstate(invalid="ignore", over="ignore"):
+        return finish(corr, img3, t3, method, S1, S2)[0]
+
+
+def accumulators_surely_finite(img, templ):
+    """True when no float32 partial sum of the kernel's accumulators can leave the finite range: every centred operand is at
+    most twice the largest magnitude of its array, the pieces add up to (1 + 2^-7) of it, three products per tap."""
+    img3, t3 = _as3d(img), _as3d(templ)
+    h, w, chans = t3.shape
+    fin = np.abs(img3[np.isfinite(img3)].astype(np.float64))
+    amax = 2.0 * float(fin.max()) if fin.size else 0.0
+    tmax = 2.0 * float(np.abs(t3.astype(np.float64)).max())
+    return 3.0 * 1.02 * chans * h * 32 * nkb_of(w) * amax * tmax < FLT_MAX
+
+
+def _place_nonfinite(shape, h, w, oh, ow, chans, t0):
+    """Where the copies of template 0 and the bad pixels go: ({label: (y, x)}, {label: (row, column, channel, bits)},
+    {label: why it is left out}).  Copies in the order a, c, b from the left, their windows apart; (b) and (c) outside the
+    work item (0, 0) whose sample grid holds pixel (a)."""
+    rows, cols = shape[:2]
+    nkb = nkb_of(w)
+    pad = 32 * nkb - w
+    samples = tile_samples(rows, cols, oh, ow, h, w)
+    copies, bad, skipped = {}, {}, {}
+    nan_bits = int(np.array([np.nan], np.float32).view(np.uint32)[0])
+    inf_bits = int(np.array([np.inf], np.float32).view(np.uint32)[0])
+    # (a) a default NaN at pixel (0, 0), a sample of tile (0, 0); its copy at output (1, 40): inside that tile, right of
+    # columns 0 .. 15 whose statistics the NaN poisons
+    if oh > 1 and ow > 40:
+        copies["a"], bad["a"] = (1, 40), (0, 0, 0, nan_bits)
+    else:
+        skipped["a"] = "no output (1, 40) in a %d x %d map" % (oh, ow)
+    x_next = 40 + w
+    # (c) -inf one row under a copy's last row
+    yc, xc = min(4, oh - 2), x_next
+    if oh >= 6 and xc + w <= ow - 1 + w and xc <= ow - 1 and xc + w <= cols:
+        # (the three windows under the copy multiply the pixel by taps of template 0's last row: positive ones, or the
+        # float64 kernel's TM_SQDIFF_NORMED there is fmax(S2 - 2 (+inf) + T2, 0) = 0 and the copy is no local minimum)
+        last = _as3d(t0)[h - 1, :, 2 % chans]
+        cc = next((c for c in range(xc + w // 2, xc + w - 1) if (yc + h, c) not in samples and
+                   (last[c - xc - 1:c - xc + 2] > 0).all()), None)
+        if cc is not None and yc >= ROWS:
+            copies["c"], bad["c"] = (yc, xc), (yc + h, cc, 2 % chans, inf_bits | 0x80000000)
+            x_next = xc + w
+    if "c" not in copies:
+        skipped["c"] = "no room for a third copy outside work item (0, 0) with a row under it in a %d x %d map" % (oh, ow)
+    # (b) +inf d columns right of a copy's last column, in a row the copy covers (below copy (a)'s rows)
+    yb, xb = min(4, oh - 1), x_next
+    if pad == 0:
+        skipped["b"] = "w = %d is a multiple of 32: no padded tap" % w
+    elif yb < ROWS or xb > ow - 1:
+        skipped["b"] = "no room for a copy beside copy (a) outside work item (0, 0) in a %d x %d map" % (oh, ow)
+    else:
+        spot = next(((r, xb + w - 1 + d, d) for d in range(pad, 0, -1) for r in range(yb + h - 1, max(yb, h + 1) - 1, -1)
+                     if xb + w - 1 + d <= cols - 1 and (r, xb + w - 1 + d) not in samples), None)
+        if spot is None:
+            skipped["b"] = "no pixel right of the copy inside the image"
+        else:
+            copies["b"], bad["b"] = (yb, xb), (spot[0], spot[1], 1 % chans, inf_bits)
+    # (d) a NaN with payload 0x7FFFFFFF in a region no copy touches: the image's last row, under the columns 0 .. 15 whose
+    # statistics pixel (a) poisons already (a small map keeps outputs the model is compared on)
+    rd = rows - 1
+    cd = next((c for c in range(4, 16) if (rd, c) not in samples), None)
+    if cd is not None and rd > h:
+        bad["d"] = (rd, cd, 0, NAN_PAYLOAD)
+    else:
+        skipped["d"] = "no free pixel in the last row"
+    return copies, bad, skipped
+
+
+def range_scene(cell, name, kind="noise+"):
+    """A scene of tests/test_gpu_f32_range.py: dict(img, clean, templs, cuts, copies, bad, skipped).  `name`: a key of SCALES - the
+    base scene of `kind` ("noise+": N(100, 40), "signed": N(0, 40)) times 2^k, templates included - or "nonfinite": noise+
+    with exact copies of template 0 planted beside bad pixels (clean: the image without them).  Templates are cut from the
+    image; every third one (1, 4, 7 ..) carries noise in the scene's own units."""
+    h, w, chans, (oh, ow) = cell["h"], cell["w"], cell["chans"], cell["out"]
+    shape = (h + oh - 1, w + ow - 1) + ((chans,) if chans > 1 else ())
+    assert kind in ("noise+", "signed") and (name in SCALES or (name == "nonfinite" and kind == "noise+"))
+    rng = _range_rng("range", cell["name"], kind)               # (one base scene per cell and kind, whatever the factor)
+    img = rng.normal(100.0 if kind == "noise+" else 0.0, 40.0, shape).astype(np.float32)
+    templs, cuts = [], []
+    for k in range(cell["n"]):
+        r = _range_rng("range", cell["name"], kind, "t", k)
+        y, x = int(r.integers(0, oh)), int(r.integers(0, ow))
+        cuts.append((y, x))
+        t = img[y:y + h, x:x + w].copy()
+        if k % 3 == 1:
+            t = (t + r.normal(0.0, BASE_NOISE, t.shape)).astype(np.float32)
+        templs.append(np.ascontiguousarray(t))
+    copies, bad, skipped = {}, {}, {}
+    clean = img
+    if name == "nonfinite":
+        copies, bad, skipped = _place_nonfinite(shape, h, w, oh, ow, chans, templs[0])
+        for y, x in copies.values():
+            img[y:y + h, x:x + w] = templs[0]
+        clean = img.copy()
+        flat = _as3d(img).view(np.uint32)
+        for r, c, ch, bits in bad.values():
+            flat[r, c, ch] = bits
+    else:
+        f = np.float32(2.0 ** SCALES[name])
+        img = img * f
+        templs = [np.ascontiguousarray(t * f) for t in templs]
+        assert np.isfinite(img).all() and img.dtype == np.float32
+        clean = img
+    return dict(img=img, clean=clean, templs=templs, cuts=cuts, copies=copies, bad=bad, skipped=skipped)

@@ -812,7 +812,8 @@ static void test_verify_candidates(std::mt19937& rng) {
                 }
 }
 
-// Every sequence of outcomes the device can report from `R` on: rig_wide only in pp_mode, cands_overflow only while fused,
+// Every sequence of outcomes the device can report from `R` on: rig_wide only in pp_mode and from the refined global extremum
+// (an output that is not finite), cands_overflow only while fused,
 // hits_overflow only when not fused (a verified list is no longer than the candidate list, whose capacity never exceeds
 // hit_cap) and never right after the single list of a non-flagged full scan was grown (same maps, room for every peak).
 // Pass `attempt` is about to run: it must lie within `cap`; no step but a grown list is taken twice (`seen`).
@@ -820,7 +821,7 @@ static void walk_ladder(const mtmi::CallRoute& R, int attempt, unsigned seen, bo
     CHECK(attempt < cap);
     CHECK(!(R.refine && R.f32_exact));
     const bool local = R.mode == MTM_PEAKS_LOCAL;
-    for (int rig = 0; rig <= (local && R.pp_mode ? 1 : 0); ++rig)
+    for (int rig = 0; rig <= ((local ? R.pp_mode : (R.refine && R.ext)) ? 1 : 0); ++rig)
         for (int co = 0; co <= ((local ? R.fused : (R.refine && R.ext)) ? 1 : 0); ++co)
             for (int ho = 0; ho <= (local && !R.fused && !list_holds_all ? 1 : 0); ++ho) {
                 const LadderStep step = ladder_next(R, PassOutcome{rig != 0, co != 0, ho != 0}, attempt);

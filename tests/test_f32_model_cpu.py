@@ -151,3 +151,131 @@ def test_impulse_templates_pick_the_shifted_normalised_image(shape):
                 other = F.model_scores(img, t2, 3, 3).astype(np.float64)
                 A, _, _ = F.tolerances(img, t, 3, 3)
                 assert (np.abs(other - want)[ok] > A[ok]).mean() > 0.9
+
+
+# ---- the scenes of tests/test_gpu_f32_range.py: every cell exercises what it is there for, shown on the reference alone ----
+import test_gpu_f32_range as R     # noqa: E402
+
+
+def _range_id(case):
+    return "%s-%s-%s" % (case[0]["name"], case[1], case[2])
+
+
+@pytest.mark.parametrize("case", [c for c in R.CASES if c[2] in F.IN_RANGE], ids=_range_id)
+def test_range_model_meets_the_bound_on_in_range_scenes(case):
+    cell, kind, scene = case
+    worst = 0.0
+    for method in R.methods_of(kind):
+        for i, (exact, model, tol, valid) in R.refs_of(cell, kind, scene, method).items():
+            assert valid.all()
+            for pc in (3, 1):
+                m = model[pc]
+                if R.always_one(scene, method):
+                    # cv2's absolute DBL_EPSILON rule: the template is constant, the score 1 everywhere - and nothing else
+                    # is claimed for this pair
+                    assert np.array_equal(m, np.ones_like(m)) and np.array_equal(exact, np.ones_like(m))
+                    continue
+                assert not (m == 1.0).all()
+                A, M, live = tol[pc]
+                unsat, enough = R.compared(i % 3 != 1, m, exact, live, valid)
+                assert enough, (cell["name"], kind, scene, method, i, int(unsat.sum()), unsat.size)
+                d = np.abs(m - exact)
+                assert (d[unsat] <= M[unsat]).all(), (cell["name"], kind, scene, method, i, pc, float((d[unsat] / M[unsat]).max()))
+                assert (A[unsat] <= M[unsat]).all() and (A[unsat] > 0.0).all()
+                worst = max(worst, float((d[unsat] / M[unsat]).max()))
+    print("%s: worst |model - exact| / bound_map %.3f" % (_range_id(case), worst))
+
+
+def test_range_scaled_scenes_are_the_base_scene_exactly():
+    cell = F.RANGE_CELLS[0]
+    a, b = F.range_scene(cell, "up40"), F.range_scene(cell, "tiny")
+    assert np.array_equal(a["img"] * np.float32(2.0 ** -100), b["img"]) and a["cuts"] == b["cuts"]
+    for ta, tb in zip(a["templs"], b["templs"]):
+        assert np.array_equal(ta * np.float32(2.0 ** -100), tb)
+    assert np.array_equal(a["img"][a["cuts"][0][0]:, a["cuts"][0][1]:][:cell["h"], :cell["w"]], a["templs"][0])
+    assert not np.array_equal(a["img"][a["cuts"][1][0]:, a["cuts"][1][1]:][:cell["h"], :cell["w"]], a["templs"][1])   # (noisy)
+
+
+@pytest.mark.parametrize("cell", F.RANGE_CELLS, ids=lambda c: c["name"])
+def test_range_huge_and_tiny_provoke_what_they_are_there_for(cell):
+    h, w = cell["h"], cell["w"]
+    for scene in ("huge", "tiny"):
+        S = F.range_scene(cell, scene)
+        for method in (5, 3, 1):
+            for i, (exact, model, tol, valid) in R.refs_of(cell, "noise+", scene, method).items():
+                assert valid.all() == (scene == "tiny")         # huge: a float32 accumulator may overflow anywhere
+                for pc in (3, 1):
+                    m = model[pc]
+                    if R.always_one(scene, method):
+                        assert scene == "tiny" and np.array_equal(m, np.ones_like(m)) and np.array_equal(exact, np.ones_like(m))
+                        continue
+                    # the float64 restatement still meets the bound
+                    A, M, live = tol[pc]
+                    unsat, enough = R.compared(i % 3 != 1, m, exact, live, np.ones_like(valid))
+                    assert enough and (np.abs(m - exact)[unsat] <= M[unsat]).all(), (cell["name"], scene, method, i, pc)
+    # huge: the float32 sum of the exact copy's centred leading-piece products is not finite
+    S = F.range_scene(cell, "huge")
+    y, x = S["cuts"][0]
+    img3, t3 = F._as3d(S["img"]), F._as3d(S["templs"][0])
+    _, planes = F.templ_centred(t3)
+    total = np.float32(0.0)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for c in range(cell["chans"]):
+            mu = F.tile_mu(img3[:, :, c], y - y % F.ROWS, x - x % F.SEG, h, F.SEG + 32 * F.nkb_of(w))
+            a0 = F.bf16_rne(img3[y:y + h, x:x + w, c] - mu)
+            total = total + (a0 * F.bf16_rne(planes[c])).sum(dtype=np.float32)
+    assert not np.isfinite(total)
+    assert F.window_scores(S["img"], S["templs"][0], 3, [(y, x)])[0] == 1.0     # ... while the float64 sums give 1
+
+
+@pytest.mark.parametrize("cell", F.RANGE_CELLS, ids=lambda c: c["name"])
+def test_range_nonfinite_scene_is_live(cell):
+    h, w = cell["h"], cell["w"]
+    S = F.range_scene(cell, "nonfinite")
+    img = S["img"]
+    assert set(S["copies"]) | set(S["skipped"]) >= {"a", "b", "c"} and set(S["bad"]) | set(S["skipped"]) == {"a", "b", "c", "d"}
+    assert "a" in S["copies"]                       # every cell has room for (a)
+    assert ("b" in S["copies"]) == (cell["name"] in ("12x20", "5x33", "24x40-n17", "7x40-c3"))
+    assert "d" in S["bad"]
+    reach, dirty, inside = F.kernel_reach(img, h, w), F.engine_stats_dirty(img, h, w), F.window_dirty(img, h, w)
+    samples = F.tile_samples(img.shape[0], img.shape[1], cell["out"][0], cell["out"][1], h, w)
+    for label, (y, x) in S["copies"].items():
+        assert np.array_equal(F._as3d(img)[y:y + h, x:x + w], F._as3d(S["templs"][0])), label       # an exact copy, intact
+        assert not inside[y, x] and not dirty[y, x], label
+        assert reach[y, x] == (label in ("a", "b")), label
+        for method, want in ((5, 1.0), (3, 1.0)):
+            assert F.window_scores(img, S["templs"][0], method, [(y, x)])[0] == want, (label, method)
+        # TM_SQDIFF_NORMED: cv2 takes sum T^2 from meanStdDev, (variance + mean^2) * area - a few float64 ulp from the direct
+        # sum, so the exact copy scores 0 up to ~1e-16
+        assert 0.0 <= F.window_scores(img, S["templs"][0], 1, [(y, x)])[0] <= 1e-12, label
+    r, c, ch, bits = S["bad"]["a"]
+    assert (r, c) == (0, 0) and (0, 0) in samples and S["copies"]["a"] == (1, 40)
+    for label in ("b", "c", "d"):
+        if label in S["bad"]:
+            assert S["bad"][label][:2] not in samples, label
+    if "b" in S["copies"]:
+        (y, x), (r, c, ch, bits) = S["copies"]["b"], S["bad"]["b"]
+        assert y <= r <= y + h - 1 and 1 <= c - (x + w - 1) <= 32 * F.nkb_of(w) - w and y >= F.ROWS
+        assert np.isposinf(F._as3d(img)[r, c, ch])
+    if "c" in S["copies"]:
+        (y, x), (r, c, ch, bits) = S["copies"]["c"], S["bad"]["c"]
+        assert r == y + h and x <= c < x + w and np.isneginf(F._as3d(img)[r, c, ch])
+        # the windows under the copy meet the pixel with positive taps: -inf there, never the +inf that TM_SQDIFF_NORMED's
+        # fmax(.., 0) turns into a score of 0 beside the copy
+        assert (F._as3d(S["templs"][0])[h - 1, c - x - 1:c - x + 2, ch] > 0).all()
+    # (d): a NaN whose payload carries - in no copy's window, and the model is compared somewhere
+    r, c, ch, bits = S["bad"]["d"]
+    assert F._as3d(img).view(np.uint32)[r, c, ch] == F.NAN_PAYLOAD
+    assert not any(y <= r < y + h and x <= c < x + w for y, x in S["copies"].values())
+    assert (~(reach | dirty | inside)).mean() >= 0.1
+    assert np.isfinite(S["clean"]).all()
+
+
+def test_bf16_rne_on_nan():
+    """bf16_rne is stated for finite floats and infinities.  A NaN keeps being one while its payload does not carry into the
+    exponent; 0x7FFFFFFF + 0x8000 wraps to -0.0.  Harmless: the windows that hold the pixel have NaN statistics."""
+    v = np.array([np.nan, np.inf, -np.inf], np.float32)
+    out = F.bf16_rne(v)
+    assert np.isnan(out[0]) and out[1] == np.inf and out[2] == -np.inf
+    p = np.array([F.NAN_PAYLOAD], np.uint32).view(np.float32)
+    assert np.isnan(p[0]) and F.bf16_rne(p).view(np.uint32)[0] == 0x80000000

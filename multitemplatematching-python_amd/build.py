@@ -5,7 +5,7 @@ tests and by hand:  python multitemplatematching-python_amd/build.py [--force]
 hipcc cross-compiles without a GPU.  The built .so is git-ignored but travels to the GPU box with
 the gpurun snapshot.
 
-The library is several translation units (context / placement / launches / search API / peak pass / hit exchange, each with the
+The library is several translation units (context / placement / window statistics / score launches / search API / peak pass / hit exchange, each with the
 kernels only it launches; the ~300 instantiations of the MFMA score kernel alone are five more): every unit is compiled to an object of its own, in parallel, and only the units whose inputs changed
 are recompiled (objects and their stamps live in csrc/build/, git-ignored).
 """
@@ -23,7 +23,7 @@ _TAG = os.environ.get("MTM_BUILD_TAG", "")
 OBJ = os.path.join(CSRC, "build" + ("_" + _TAG if _TAG else ""))
 LIB = os.path.join(HERE, "MTM", "libmtm_hip%s.so" % ("_" + _TAG if _TAG else ""))
 STAMP = LIB + ".stamp"
-SOURCES = ["mtm_context.hip", "mtm_placement.hip", "mtm_launch.hip", "mtm_api.hip", "mtm_peaks.hip", "mtm_comm.hip", "mtm_mfma_plain.hip", "mtm_mfma_rm.hip", "mtm_mfma_ext.hip", "mtm_mfma_kp.hip", "mtm_mfma_rows.hip", "mtm_bf16.hip", "mtm_pyramid.hip", "mtm_boxes.hip", "mtm_track.hip", "mtm_subpixel.hip", "mtm_blocks.hip",
+SOURCES = ["mtm_context.hip", "mtm_placement.hip", "mtm_stats.hip", "mtm_launch.hip", "mtm_api.hip", "mtm_peaks.hip", "mtm_comm.hip", "mtm_mfma_plain.hip", "mtm_mfma_rm.hip", "mtm_mfma_ext.hip", "mtm_mfma_kp.hip", "mtm_mfma_rows.hip", "mtm_bf16.hip", "mtm_pyramid.hip", "mtm_boxes.hip", "mtm_track.hip", "mtm_subpixel.hip", "mtm_blocks.hip",
            "mtm_host.cpp", "mtm_group.cpp"]
 HEADERS = ["mtm_ctx.h", "mtm_k_image.hip.h", "mtm_k_stats.hip.h", "mtm_k_score.hip.h", "mtm_k_peaks.hip.h", "mtm_score_params.h",
            "mtm_templates_params.h", "mtm_device_util.hip.h", "mtm_mfma.hip.h", "mtm_mfma_kloop.hip.h", "mtm_mfma_epilogue.hip.h", "mtm_mfma_finish.hip.h", "mtm_mfma_params.h", "mtm_templates.hip.h",

@@ -1,6 +1,7 @@
 // Internal header of libmtm_hip.so's GPU side: the context, the size classes of a template set, and the functions the
 // translation units share.  Units: mtm_context.hip (context, options, image upload), mtm_placement.hip (template sets ->
-// size classes, packs, constants), mtm_launch.hip (window statistics and score-map launches), mtm_api.hip
+// size classes, packs, constants), mtm_stats.hip (window statistics: their launchers and test-support entries),
+// mtm_launch.hip (score-map launches and the score pass of a call, plain and banded), mtm_api.hip
 // (mtm_find_matches and friends: a call's route, its ladder, hit lists), mtm_peaks.hip (the peak pass: its launchers and
 // fetches, the device's share of the NMS), mtm_comm.hip (RCCL hit exchange), mtm_pyramid.hip (the
 // coarse-to-fine search), mtm_boxes.hip (many searchBoxes in one call), mtm_subpixel.hip (hit neighbourhoods), mtm_blocks.hip (block matching
@@ -181,7 +182,6 @@ struct mtm_ctx {
     int cand_pinned = 1;        // MTM_CAND_PINNED: the score kernel writes the first records of its candidate list into the pinned
                                 // landing buffer itself (MfmaParams::cand_pin) - no fetch kernel behind the score launch (0: round 4)
     int fuse_layout = 1;        // MTM_FUSE_LAYOUT: banded uploads convert a band's rows inside its statistics launch (0: planarize kernel)
-    int lay_r0 = 0, lay_r1 = 0; // ... the rows the statistics launch being queued converts (run_score_banded -> launch_stats)
     int masksq_fused = 1;       // MTM_MASKSQ_FUSED: sum I^2 M of a masked class as ONE launch over both byte planes of I^2 that
                                 // writes the sum2 plane itself (0: round 3's two raw launches + masksq_combine_kernel)
 
@@ -214,7 +214,6 @@ struct mtm_ctx {
     hipEvent_t next_ready = nullptr;
     // mtm_find_matches_image: the image arrives in row bands on copy_stream (copy, layout conversion, window
     // statistics of the rows that became computable); the score kernel of a band waits for its event
-    hipStream_t stats_stream = nullptr;     // non-null while a banded call queues its statistics launches
     int screen_l1 = 1;                      // MTM_SCREEN_L1: the hits-only screen starts with the per-lane bound (0: round 2's screen alone)
     int tail_screen = 1;                    // MTM_TAIL_SCREEN: the two-row variant's hits-only K loop stops early where a bound on the
                                             // template rows still missing rules out every candidate (MfmaParams::tail_split)
@@ -564,9 +563,50 @@ int comm_allgather_hits_flagged(mtm_ctx* c, const mtm_hit* local, int64_t n_loca
                                 int64_t capacity, int64_t* counts_out, int64_t* n_out, std::vector<int32_t>* flags_out);
 // ---- mtm_placement.hip
 int place_templates(mtm_ctx* c);
+// ---- mtm_stats.hip: the host side of the window statistics (the only unit that launches mtm_k_stats.hip.h)
+// What the launchers of the two-pass chains take - a stream, device pointers and these, nothing of a context:
+struct StatGeom {           // an h x w window over `chans` planes of rows x cols pixels
+    int rows, cols, chans, h, w, oh, ow;
+    double inv_area;
+};
+inline StatGeom stat_geom(int rows, int cols, int chans, int h, int w) {
+    return StatGeom{rows, cols, chans, h, w, rows - h + 1, cols - w + 1, 1.0 / ((double)h * (double)w)};
+}
+struct StatScratch {        // the row sums between the two passes: `chans` planes of rows x pitch (uint32 or double) each
+    void* hs1;
+    void* hs2;
+    int pitch;
+    long long plane;
+};
+struct StatOut {            // the planes to write (st_pitch doubles a row, oh rows); a null plane goes with its flag off
+    int num_type = 0, want_sq = 0, want_t = 0, want_sum2 = 1;       // (the two-pass chains write sum2 whatever is asked)
+    double* t[kMaxChans] = {nullptr, nullptr, nullptr, nullptr};
+    long long t_plane = 0;  // the fused RGB kernel: doubles from t[0] to t[1] to t[2]
+    double* sum2 = nullptr;
+    double* sq = nullptr;
+    int st_pitch = 0;
+};
+// F64_LDS: hsum_lds_kernel (w <= kStatsHsumLdsMaxW) over the image rows [r0, r1) + vsum over the output rows [o0, o1) - the
+// whole image, or the rows a band of a banded upload brought and the windows they complete (launch_stats; mbf_prepare)
+int launch_stats_f64_lds(hipStream_t stream, const float* f32, int pitch, long long plane, const StatGeom& g,
+                         const StatScratch& s, const StatOut& o, int r0, int r1, int o0, int o1);
+// What a band of a banded upload asks of launch_stats; the default: the whole image, on the context's stream.
+struct StatBand {
+    hipStream_t stream = nullptr;   // the stream of a banded call's statistics launches (null: no banded call, c->stream)
+    int sb0 = 0, sb1 = -1;          // the kStatBand4-row units of output rows to compute (fused kernels, F64_LDS), sb1 < 0 = all
+    int lay_r0 = 0, lay_r1 = 0;     // the image rows that have just arrived - fused uint8: the rows whose layout this launch
+                                    // converts; F64_LDS: the rows whose horizontal sums it adds
+};
+// Window statistics of one size class into c->stats; *out: the plane table its score launch reads.
+int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out, const StatBand& band = {});
 // ---- mtm_launch.hip
 bool dot_variant_ok(int64_t v);
-int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out, int sb0 = 0, int sb1 = -1);
+// the tail screen's split for a launch of class `sc` on route R (MfmaParams::tail_split), 0 = off
+int tail_split_for(const mtm_ctx* c, CallRoute& R, const SizeClass& sc);
+// ... and the templates' tail constants for it, re-derived on the score stream where the last ones were another split's
+int ensure_tail_consts(mtm_ctx* c, const SizeClass& sc, int split);
+// sum I^2 M of a masked class on the int8 matrix cores into `sum2`, the sum2 plane of `st` (launch_stats' last step)
+int launch_masked_sumsq(mtm_ctx* c, const SizeClass& sc, bool fused_stats, const StatPlanes& st, double* sum2);
 // the tail constants of class `sc` for `split` (tail_consts_kernel -> TemplDev::tail_*), queued on `stream`
 int launch_tail_consts(mtm_ctx* c, const SizeClass& sc, int split, hipStream_t stream);
 int launch_ncc(mtm_ctx* c, CallRoute& R, const SizeClass& sc, int list_off, int n_list, const StatPlanes& st, int only_li = -1,

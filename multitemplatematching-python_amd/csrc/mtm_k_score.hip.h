@@ -1,4 +1,4 @@
-// Score-map kernels besides the matrix-core ones: slab combination, the naive cross-check, the tiled float64 kernel, the dot4 (VALU) kernel.  Launched by mtm_launch.hip only.
+// Score-map kernels besides the matrix-core ones: slab combination, the sum I^2 M helpers of masked classes, the naive cross-check, the tiled float64 kernel, the dot4 (VALU) kernel.  Launched by mtm_launch.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cfloat>
@@ -82,6 +82,59 @@ __global__ __launch_bounds__(256) void slab_combine_kernel(SlabParams p, const T
         cand_append((p.cand_min ? -out : out) > p.cand_thr, p.cand_counter, p.cand_cap, p.cand_hits, hrec);
     }
     if (!p.hits_only) maps[T.map_off + (size_t)y * T.map_pitch + x] = out;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Masked templates: sum I^2 * M over every window on the matrix cores.  I^2 is a 16-bit number; its two
+// bytes are image planes of their own (square_planes_kernel, biased to int8 like every image plane), the binary
+// mask is the "template" of a row-multiplexed raw correlation (one template, 16 output rows per MFMA) - as the
+// int8 values 0 / 1 it already is, NOT biased: with a_x = sum (I_x - 128) * M the window sums drop out,
+//   sum I_x * M = a_x + 128 * sum(M),        c2 = 256 * sum I_h * M + sum I_l * M = 256 a_h + a_l + 257 * 128 * sum(M)
+// (round 2 biased the mask too and needed a window-sum pass over the high-byte plane per class to undo it).
+// All integers < 2^53: exact.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void square_planes_kernel(const uint8_t* __restrict__ u8, size_t n16,
+                                                            uint8_t* __restrict__ shb, uint8_t* __restrict__ slb) {
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n16) return;
+    const uint4 v = reinterpret_cast<const uint4*>(u8)[g];
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t hi[4], lo[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        hi[k] = lo[k] = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const uint32_t px = (w[k] >> (8 * b)) & 255u, sq = px * px;
+            hi[k] |= (sq >> 8) << (8 * b);
+            lo[k] |= (sq & 255u) << (8 * b);
+        }
+    }
+    reinterpret_cast<uint4*>(shb)[g] = make_uint4(hi[0] ^ 0x80808080u, hi[1] ^ 0x80808080u, hi[2] ^ 0x80808080u,
+                                                  hi[3] ^ 0x80808080u);
+    reinterpret_cast<uint4*>(slb)[g] = make_uint4(lo[0] ^ 0x80808080u, lo[1] ^ 0x80808080u, lo[2] ^ 0x80808080u,
+                                                  lo[3] ^ 0x80808080u);
+}
+
+__global__ __launch_bounds__(256) void masksq_combine_kernel(const int* __restrict__ raw_h, const int* __restrict__ raw_l,
+                                                             int raw_pitch, double* __restrict__ sum2, int st_pitch,
+                                                             double km257, int oh, int ow, double* __restrict__ blk,
+                                                             int blk_pitch) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    double c2 = INFINITY;
+    if (x < ow && y < oh) {
+        const size_t o = (size_t)y * st_pitch + x, r = (size_t)y * raw_pitch + x;
+        c2 = fma(256.0, (double)raw_h[r], (double)raw_l[r]) + km257;
+        sum2[o] = c2;
+    }
+    if (blk != nullptr) {
+        // smallest c2 of every 16-pixel column block (third slot of the block record; the row-multiplexed tiling's
+        // hits-only screen bounds sqrt(tms c2) from below with it); +inf for a block right of the last output column
+#pragma unroll
+        for (int off = 1; off <= 8; off <<= 1) c2 = fmin(c2, __shfl_xor(c2, off));
+        if ((threadIdx.x & 15) == 0 && y < oh && (x >> 4) < blk_pitch) blk[((size_t)y * blk_pitch + (x >> 4)) * 4 + 2] = c2;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

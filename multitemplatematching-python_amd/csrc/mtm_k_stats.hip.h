@@ -1,4 +1,4 @@
-// Window statistics kernels (exact box sums and the template-independent part of the normalisation per output pixel) and the sum I^2 M helpers of masked classes.  Launched by mtm_launch.hip only.
+// Window statistics kernels (exact box sums and the template-independent part of the normalisation per output pixel).  Launched by mtm_stats.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -8,6 +8,7 @@
 #include "mtm_kernels.h"
 #include "../../include/mtm_hip.h"
 #include "mtm_device_util.hip.h"
+#include "mtm_stats_route.h"
 
 namespace mtm {
 
@@ -192,11 +193,8 @@ __global__ __launch_bounds__(256) void hsum_u8_kernel(const uint8_t* __restrict_
 // The form of a launch (output rows per work-group) changes how the work is spread, never a byte of what is written;
 // stats_u8_form() is the launcher's rule.
 // ---------------------------------------------------------------------------------------------
-#ifndef MTM_STAT_BAND4
-#define MTM_STAT_BAND4 8
-#endif
-constexpr int kStatBand4 = MTM_STAT_BAND4;    // fused statistics kernels: output rows per row unit (the unit of [sb0, sb1) ranges)
-constexpr int kStatStrip = 1024;               // image columns per work-group
+// (kStatBand4, the output rows per row unit of the [sb0, sb1) ranges: mtm_stats_route.h)
+constexpr int kStatStrip = 1024;              // image columns per work-group
 #ifndef MTM_STAT_PRO_BATCH
 #define MTM_STAT_PRO_BATCH 32
 #endif
@@ -836,11 +834,7 @@ __global__ __launch_bounds__(256) void stats_u8_mc_kernel(const uint8_t* __restr
     }
 }
 
-#ifndef MTM_VSUM_BAND
-#define MTM_VSUM_BAND 32
-#endif
-constexpr int kVsumBand = MTM_VSUM_BAND;
-
+// (kVsumBand, the output rows of a band: mtm_stats_route.h)
 template <typename AccT, typename SumT>
 __global__ void vsum_stats_kernel(const AccT* __restrict__ hs1, const AccT* __restrict__ hs2,
                                   int hs_pitch, long long hs_plane, int chans, int h, int oh, int ow,
@@ -924,59 +918,5 @@ __global__ void vsum_stats_kernel(const AccT* __restrict__ hs1, const AccT* __re
         }
     }
 }
-
-// ---------------------------------------------------------------------------------------------
-// Masked templates: sum I^2 * M over every window on the matrix cores.  I^2 is a 16-bit number; its two
-// bytes are image planes of their own (square_planes_kernel, biased to int8 like every image plane), the binary
-// mask is the "template" of a row-multiplexed raw correlation (one template, 16 output rows per MFMA) - as the
-// int8 values 0 / 1 it already is, NOT biased: with a_x = sum (I_x - 128) * M the window sums drop out,
-//   sum I_x * M = a_x + 128 * sum(M),        c2 = 256 * sum I_h * M + sum I_l * M = 256 a_h + a_l + 257 * 128 * sum(M)
-// (round 2 biased the mask too and needed a window-sum pass over the high-byte plane per class to undo it).
-// All integers < 2^53: exact.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void square_planes_kernel(const uint8_t* __restrict__ u8, size_t n16,
-                                                            uint8_t* __restrict__ shb, uint8_t* __restrict__ slb) {
-    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (g >= n16) return;
-    const uint4 v = reinterpret_cast<const uint4*>(u8)[g];
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    uint32_t hi[4], lo[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        hi[k] = lo[k] = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const uint32_t px = (w[k] >> (8 * b)) & 255u, sq = px * px;
-            hi[k] |= (sq >> 8) << (8 * b);
-            lo[k] |= (sq & 255u) << (8 * b);
-        }
-    }
-    reinterpret_cast<uint4*>(shb)[g] = make_uint4(hi[0] ^ 0x80808080u, hi[1] ^ 0x80808080u, hi[2] ^ 0x80808080u,
-                                                  hi[3] ^ 0x80808080u);
-    reinterpret_cast<uint4*>(slb)[g] = make_uint4(lo[0] ^ 0x80808080u, lo[1] ^ 0x80808080u, lo[2] ^ 0x80808080u,
-                                                  lo[3] ^ 0x80808080u);
-}
-
-__global__ __launch_bounds__(256) void masksq_combine_kernel(const int* __restrict__ raw_h, const int* __restrict__ raw_l,
-                                                             int raw_pitch, double* __restrict__ sum2, int st_pitch,
-                                                             double km257, int oh, int ow, double* __restrict__ blk,
-                                                             int blk_pitch) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
-    double c2 = INFINITY;
-    if (x < ow && y < oh) {
-        const size_t o = (size_t)y * st_pitch + x, r = (size_t)y * raw_pitch + x;
-        c2 = fma(256.0, (double)raw_h[r], (double)raw_l[r]) + km257;
-        sum2[o] = c2;
-    }
-    if (blk != nullptr) {
-        // smallest c2 of every 16-pixel column block (third slot of the block record; the row-multiplexed tiling's
-        // hits-only screen bounds sqrt(tms c2) from below with it); +inf for a block right of the last output column
-#pragma unroll
-        for (int off = 1; off <= 8; off <<= 1) c2 = fmin(c2, __shfl_xor(c2, off));
-        if ((threadIdx.x & 15) == 0 && y < oh && (x >> 4) < blk_pitch) blk[((size_t)y * blk_pitch + (x >> 4)) * 4 + 2] = c2;
-    }
-}
-
 
 }  // namespace mtm

@@ -1,10 +1,11 @@
-// libmtm_hip.so - launches: window statistics and score maps of a size class on whichever kernel runs it, the float32
-// refinement behind the bf16 kernel, the score pass of a whole call (plain and with a banded image upload).
+// libmtm_hip.so - the score pass: the score maps of a size class on whichever kernel runs it (launch_ncc and one launcher
+// per kernel family), the sum I^2 M pass of masked classes, the masked float32 screen, the float32 refinement behind the
+// bf16 kernel, and the score pass of a whole call - classes over lanes, plain and with a banded image upload.  The window
+// statistics a score launch reads come from launch_stats (mtm_stats.hip).
 #include "mtm_ctx.h"
 
 using namespace mtm;
 using namespace mtmi;
-#include "mtm_k_stats.hip.h"
 #include "mtm_k_score.hip.h"
 #include "mtm_refine.hip.h"
 #include "mtm_maskf32.hip.h"
@@ -38,6 +39,12 @@ MfmaFn mfma_raw_fn(bool row_mux, bool packed_k) {
     s.rm = row_mux;
     s.kp = packed_k;
     return mfma_kernel(s);
+}
+
+// the index of `sc` among the context's size classes; -1: a class that is not the context's (a caller's own record)
+int class_index(const mtm_ctx* c, const SizeClass& sc) {
+    const bool mine = !c->classes.empty() && &sc >= c->classes.data() && &sc < c->classes.data() + c->classes.size();
+    return mine ? (int)(&sc - c->classes.data()) : -1;
 }
 
 // work items in whole groups of 8 work-groups
@@ -101,43 +108,6 @@ int mfma_row_mux(MfmaParams& p, int R, int nt) {
     p.nyb = (p.oh + 8 * R - 1) / (8 * R);
     p.ntg = 1;
     return rm_tile_rows(p.h, R);
-}
-
-// The tail screen's split for a launch of class `sc` on route R (MfmaParams::tail_split), 0 = off: hits-only candidate lists of
-// a two-row uint8 class in one K chunk, TM_CCOEFF_NORMED / TM_CCORR_NORMED, a non-negative threshold, neither the fused
-// extremum nor maps in memory - and a threshold the bound can get below early enough to pay.
-// The split itself follows the call's threshold (tail_split_rule, mtm_host.cpp), or is the forced one (MTM_TAIL_SPLIT).
-// The rule's value is computed once per call and kept in the route: every statistics and score launch of every band of the
-// call carries the same split (the route's other fields can change between a call's passes - they are tested every time).
-int tail_split_for(const mtm_ctx* c, CallRoute& R, const SizeClass& sc) {
-    if (!c->tail_screen || !c->screen_l1 || !sc.tail_ok || sc.r2 != 2 || sc.masked || sc.kernel != MTM_KERNEL_MFMA) return 0;
-    if (!R.cand_on || !R.hits_only || R.ext || R.sparse || R.cand_min || c->chans != 1 || c->dtype != MTM_U8) return 0;
-    if (c->method != MTM_TM_CCOEFF_NORMED && c->method != MTM_TM_CCORR_NORMED) return 0;
-    if (sc.h + 1 > kMfChunkR2 || sc.w > 64) return 0;
-    const double thr_lo = (double)R.cand_thr - 1e-6 * std::max(1.0, std::fabs((double)R.cand_thr));
-    if (!(thr_lo >= 0.0)) return 0;
-    if (c->tail_split_force > 0) return std::max(6, std::min(c->tail_split_force, sc.h - 2));
-    if (R.tail_h != sc.h || R.tail_w != sc.w || R.tail_thr != R.cand_thr) {
-        R.tail_s = tail_split_rule(sc.h, sc.w, thr_lo);
-        R.tail_h = sc.h;
-        R.tail_w = sc.w;
-        R.tail_thr = R.cand_thr;
-    }
-    return R.tail_s;
-}
-
-// The templates' tail constants (TemplDev::tail_*) hold for ONE split: a launch whose split is not the one they were last
-// computed for (mtm_ctx::tail_valid) re-derives them first - tail_consts_kernel, 64 threads per template, on the score
-// stream: ahead of the call's first score launch (launch_stats asks before the launch waits for its band, so the kernel
-// runs under band 0's copy) and behind the previous call's, never on the copy-side stream.
-static int ensure_tail_consts(mtm_ctx* c, const SizeClass& sc, int split) {
-    if (split <= 0 || sc.members.empty()) return MTM_OK;
-    const bool mine = !c->classes.empty() && &sc >= c->classes.data() && &sc < c->classes.data() + c->classes.size();
-    const size_t k = mine ? (size_t)(&sc - c->classes.data()) : 0;
-    if (mine && k < c->tail_valid.size() && c->tail_valid[k] == split) return MTM_OK;
-    MTMC(launch_tail_consts(c, sc, split, c->stream));
-    if (mine && k < c->tail_valid.size()) c->tail_valid[k] = split;
-    return MTM_OK;
 }
 
 // the candidate list (mtm_ctx::cands: a 16-byte header, then the records) a score kernel appends to, `cap` records long
@@ -244,6 +214,43 @@ namespace mtmi {
 
 bool dot_variant_ok(int64_t v) { return v >= 0 && v < kNumDotVariants && !kDotVariants[v].wide; }
 
+// The tail screen's split for a launch of class `sc` on route R (MfmaParams::tail_split), 0 = off: hits-only candidate lists of
+// a two-row uint8 class in one K chunk, TM_CCOEFF_NORMED / TM_CCORR_NORMED, a non-negative threshold, neither the fused
+// extremum nor maps in memory - and a threshold the bound can get below early enough to pay.
+// The split itself follows the call's threshold (tail_split_rule, mtm_host.cpp), or is the forced one (MTM_TAIL_SPLIT).
+// The rule's value is computed once per call and kept in the route: every statistics and score launch of every band of the
+// call carries the same split (the route's other fields can change between a call's passes - they are tested every time).
+int tail_split_for(const mtm_ctx* c, CallRoute& R, const SizeClass& sc) {
+    if (!c->tail_screen || !c->screen_l1 || !sc.tail_ok || sc.r2 != 2 || sc.masked || sc.kernel != MTM_KERNEL_MFMA) return 0;
+    if (!R.cand_on || !R.hits_only || R.ext || R.sparse || R.cand_min || c->chans != 1 || c->dtype != MTM_U8) return 0;
+    if (c->method != MTM_TM_CCOEFF_NORMED && c->method != MTM_TM_CCORR_NORMED) return 0;
+    if (sc.h + 1 > kMfChunkR2 || sc.w > 64) return 0;
+    const double thr_lo = (double)R.cand_thr - 1e-6 * std::max(1.0, std::fabs((double)R.cand_thr));
+    if (!(thr_lo >= 0.0)) return 0;
+    if (c->tail_split_force > 0) return std::max(6, std::min(c->tail_split_force, sc.h - 2));
+    if (R.tail_h != sc.h || R.tail_w != sc.w || R.tail_thr != R.cand_thr) {
+        R.tail_s = tail_split_rule(sc.h, sc.w, thr_lo);
+        R.tail_h = sc.h;
+        R.tail_w = sc.w;
+        R.tail_thr = R.cand_thr;
+    }
+    return R.tail_s;
+}
+
+// The templates' tail constants (TemplDev::tail_*) hold for ONE split: a launch whose split is not the one they were last
+// computed for (mtm_ctx::tail_valid) re-derives them first - tail_consts_kernel, 64 threads per template, on the score
+// stream: ahead of the call's first score launch (launch_stats asks before the launch waits for its band, so the kernel
+// runs under band 0's copy) and behind the previous call's, never on the copy-side stream.
+int ensure_tail_consts(mtm_ctx* c, const SizeClass& sc, int split) {
+    if (split <= 0 || sc.members.empty()) return MTM_OK;
+    const int k = class_index(c, sc);
+    const bool kept = k >= 0 && (size_t)k < c->tail_valid.size();
+    if (kept && c->tail_valid[(size_t)k] == split) return MTM_OK;
+    MTMC(launch_tail_consts(c, sc, split, c->stream));
+    if (kept) c->tail_valid[(size_t)k] = split;
+    return MTM_OK;
+}
+
 // The byte planes of I^2 (masked classes: sum I^2 M on the matrix cores), once per image; a no-op for everything but
 // single-channel uint8 images with a masked class on the MFMA kernel.
 int ensure_square_planes(mtm_ctx* c) {
@@ -263,306 +270,10 @@ int ensure_square_planes(mtm_ctx* c) {
     return MTM_OK;
 }
 
-static int launch_masked_sumsq(mtm_ctx* c, const SizeClass& sc, bool fused_stats, const StatPlanes& st, double* sum2);
-
-// One stats_u8_kernel launch: the row units [a.sb0, a.sb1) of the fused single-channel uint8 statistics, in form `form`
-// (kStatForms, from 1; 0 = stats_u8_form's choice).  Fills the derived fields of `a`.  launch_stats and the test-support
-// entry mtm_debug_window_stats both come through here.
-int launch_stats_u8(hipStream_t stream, StatU8Args a, int form, int n_cus) {
-    if (a.sb1 <= a.sb0) return MTM_OK;
-    a.owg = stats_u8_owg(a.w);
-    const int strips = (a.ow + a.owg - 1) / a.owg;
-    if (form == 0) form = stats_u8_form(strips, a.sb1 - a.sb0, n_cus);
-    if (form < 1 || form > kStatFormCount) {
-        set_error("launch_stats_u8: no such form");
-        return MTM_E_INVALID;
-    }
-    a.rows_wg = kStatFormRows[form - 1];
-    a.inv_area = 1.0 / ((double)a.h * (double)a.w);
-    const bool tail = a.blkq != nullptr;
-    if (tail) {
-        a.inv_nq[0] = 1.0 / (double)((a.h - a.tail_s) * a.w);
-        a.inv_nq[1] = 1.0 / (double)((a.h - a.tail_s + 1) * a.w);
-    }
-    const dim3 grid(strips, stats_u8_grid_y(a.sb0, a.sb1, a.oh, a.rows_wg)), block(kStatStrip / 4);
-    if (grid.y == 0) return MTM_OK;
-    // (the tail boxes and the reciprocal plane in instantiations of their own: a launch without them pays nothing for them)
-    auto* kernel = tail ? (a.rsq ? stats_u8_kernel<true, true> : stats_u8_kernel<true, false>)
-                        : (a.rsq ? stats_u8_kernel<false, true> : stats_u8_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
-    HIPC(hipGetLastError());
-    return MTM_OK;
-}
-
-// ---- one launcher per route of stats_route (mtm_stats_route.h) but the first, which launch_stats_u8 above is: a stream,
-// explicit device pointers and geometry, nothing of a context.  launch_stats, launch_masked_bf16 and the test-support entry
-// mtm_debug_window_stats_route all come through them.
-struct StatGeom {           // an h x w window over `chans` planes of rows x cols pixels
-    int rows, cols, chans, h, w, oh, ow;
-    double inv_area;
-};
-static StatGeom stat_geom(int rows, int cols, int chans, int h, int w) {
-    return StatGeom{rows, cols, chans, h, w, rows - h + 1, cols - w + 1, 1.0 / ((double)h * (double)w)};
-}
-struct StatScratch {        // the row sums between the two passes: `chans` planes of rows x pitch (uint32 or double) each
-    void* hs1;
-    void* hs2;
-    int pitch;
-    long long plane;
-};
-struct StatOut {            // the planes to write (st_pitch doubles a row, oh rows); a null plane goes with its flag off
-    int num_type = 0, want_sq = 0, want_t = 0, want_sum2 = 1;       // (the two-pass chains write sum2 whatever is asked)
-    double* t[kMaxChans] = {nullptr, nullptr, nullptr, nullptr};
-    long long t_plane = 0;  // the fused RGB kernel: doubles from t[0] to t[1] to t[2]
-    double* sum2 = nullptr;
-    double* sq = nullptr;
-    int st_pitch = 0;
-};
-
-// (every launcher: the planes' rows hold the output row - the fused kernels store whole quads)
-static int stat_out_check(const StatGeom& g, const StatOut& o) {
-    if (o.st_pitch >= g.ow && o.st_pitch % 4 == 0) return MTM_OK;
-    set_error("statistics launch: a plane pitch below the output width, or no multiple of 4");
-    return MTM_E_INVALID;
-}
-
-// U8MC: stats_u8_mc_kernel<3> over the three uint8 planes
-static int launch_stats_u8mc(hipStream_t stream, const uint8_t* u8, int pitch, long long plane, const StatGeom& g, const StatOut& o) {
-    MTMC(stat_out_check(g, o));
-    const int owg = stats_u8_owg(g.w);
-    const dim3 gs((g.ow + owg - 1) / owg, (g.oh + kStatBand4 - 1) / kStatBand4);
-    hipLaunchKernelGGL(stats_u8_mc_kernel<3>, gs, dim3(256), 0, stream, u8, pitch, plane, g.h, g.w, g.oh, g.ow, owg, g.inv_area,
-                       o.num_type, o.want_sq, o.want_t, o.want_sum2, o.t[0], o.t_plane, o.sum2, o.sq, o.st_pitch);
-    HIPC(hipGetLastError());
-    return MTM_OK;
-}
-
-// U16: stats_u16_kernel over the two biased byte planes, row units [sb0, sb1) of kStatBand4 output rows; blk: the records
-// per 16-column block (null: none)
-static int launch_stats_u16(hipStream_t stream, const uint8_t* hib, const uint8_t* lob, int pitch, const StatGeom& g,
-                            const StatOut& o, double* blk, int blk_pitch, int sb0, int sb1) {
-    MTMC(stat_out_check(g, o));
-    if (sb1 <= sb0) return MTM_OK;
-    const int owg = stats_u8_owg(g.w);
-    const dim3 gs((g.ow + owg - 1) / owg, sb1 - sb0);
-    hipLaunchKernelGGL(stats_u16_kernel, gs, dim3(256), 0, stream, hib, lob, pitch, g.h, g.w, g.oh, g.ow, owg, g.inv_area,
-                       o.num_type, o.want_sq, o.want_t, o.want_sum2, o.t[0], o.sum2, o.sq, o.st_pitch, blk, blk_pitch, sb0);
-    HIPC(hipGetLastError());
-    return MTM_OK;
-}
-
-// the second pass of the two-pass chains: output rows [o0, o1), o0 a multiple of kVsumBand (a band restarts its column sums)
-template <typename AccT, typename SumT>
-static int launch_vsum(hipStream_t stream, const StatGeom& g, const StatScratch& s, const StatOut& o, int o0, int o1) {
-    MTMC(stat_out_check(g, o));
-    if (o1 <= o0) return MTM_OK;
-    if (o0 % kVsumBand != 0) {
-        set_error("launch_vsum: a launch starts on a whole band of output rows");
-        return MTM_E_INVALID;
-    }
-    const dim3 g2((g.ow + 255) / 256, (o1 - o0 + kVsumBand - 1) / kVsumBand);
-    hipLaunchKernelGGL((vsum_stats_kernel<AccT, SumT>), g2, dim3(256), 0, stream, static_cast<const AccT*>(s.hs1),
-                       static_cast<const AccT*>(s.hs2), s.pitch, s.plane, g.chans, g.h, g.oh, g.ow, g.inv_area, o.num_type,
-                       o.want_sq, o.want_t, o.t[0], o.t[1], o.t[2], o.t[3], o.sum2, o.sq, o.st_pitch, o0 / kVsumBand);
-    HIPC(hipGetLastError());
-    return MTM_OK;
-}
-
-// U8_2P: hsum_u8_kernel (a row's two prefix sums in LDS: cols <= kStatsHsumU8MaxCols) + vsum over uint32 row sums
-static int launch_stats_u8_2p(hipStream_t stream, const uint8_t* u8, int pitch, long long plane, const StatGeom& g,
-                              const StatScratch& s, const StatOut& o) {
-    hipLaunchKernelGGL(hsum_u8_kernel, dim3(g.rows, g.chans), dim3(256), sizeof(uint32_t) * 2 * (g.cols + 1), stream, u8, pitch,
-                       plane, g.cols, g.w, g.ow, static_cast<uint32_t*>(s.hs1), static_cast<uint32_t*>(s.hs2), s.pitch, s.plane);
-    HIPC(hipGetLastError());
-    return launch_vsum<uint32_t, unsigned long long>(stream, g, s, o, 0, g.oh);
-}
-
-// U8_2P_WIDE: the generic hsum_kernel on the float32 plane of a uint8 image (uint32 row sums: exact) + the same vsum
-static int launch_stats_u8_2p_wide(hipStream_t stream, const float* f32, int pitch, long long plane, const StatGeom& g,
-                                   const StatScratch& s, const StatOut& o) {
-    const dim3 g1((g.ow + 256 * kHsumSeg - 1) / (256 * kHsumSeg), g.rows, g.chans);
-    hipLaunchKernelGGL(hsum_kernel<uint32_t>, g1, dim3(256), 0, stream, f32, pitch, plane, g.rows, g.w, g.ow,
-                       static_cast<uint32_t*>(s.hs1), static_cast<uint32_t*>(s.hs2), s.pitch, s.plane);
-    HIPC(hipGetLastError());
-    return launch_vsum<uint32_t, unsigned long long>(stream, g, s, o, 0, g.oh);
-}
-
-// F64_LDS: hsum_lds_kernel (w <= kStatsHsumLdsMaxW) over the image rows [r0, r1) + vsum over the output rows [o0, o1) - the
-// whole image, or the rows a band of a banded upload brought and the windows they complete
-static int launch_stats_f64_lds(hipStream_t stream, const float* f32, int pitch, long long plane, const StatGeom& g,
-                                const StatScratch& s, const StatOut& o, int r0, int r1, int o0, int o1) {
-    if (r1 > r0) {
-        const dim3 g1((g.ow + 256 * kHsumSeg - 1) / (256 * kHsumSeg), r1 - r0, g.chans);
-        hipLaunchKernelGGL(hsum_lds_kernel, g1, dim3(256), hsum_lds_bytes(g.w), stream, f32, pitch, plane, g.rows, g.w, g.ow,
-                           static_cast<double*>(s.hs1), static_cast<double*>(s.hs2), s.pitch, s.plane, r0);
-        HIPC(hipGetLastError());
-    }
-    return launch_vsum<double, double>(stream, g, s, o, o0, o1);
-}
-
-// F64: the generic hsum_kernel<double> (any window width) + the same vsum, whole image
-static int launch_stats_f64(hipStream_t stream, const float* f32, int pitch, long long plane, const StatGeom& g,
-                            const StatScratch& s, const StatOut& o) {
-    const dim3 g1((g.ow + 256 * kHsumSeg - 1) / (256 * kHsumSeg), g.rows, g.chans);
-    hipLaunchKernelGGL(hsum_kernel<double>, g1, dim3(256), 0, stream, f32, pitch, plane, g.rows, g.w, g.ow,
-                       static_cast<double*>(s.hs1), static_cast<double*>(s.hs2), s.pitch, s.plane);
-    HIPC(hipGetLastError());
-    return launch_vsum<double, double>(stream, g, s, o, 0, g.oh);
-}
-
-// Window statistics of one size class (two kernels), into c->stats.  Returns the plane table.
-// `sb0`, `sb1`: range of kStatBand4-row output blocks to compute (banded image upload; fused single-channel
-// kernel only), sb1 < 0 = all.
-int launch_stats(mtm_ctx* c, CallRoute& R, const SizeClass& sc, StatPlanes* out, int sb0, int sb1) {
-    const int h = sc.h, w = sc.w;
-    const int oh = c->rows - h + 1, ow = c->cols - w + 1;
-    const int method = c->method;
-    StatPlanes st{};
-    st.pitch = (int)round_up((size_t)ow, 4);
-    *out = st;
-    const int rk = sc.kernel;
-    const bool want_t_always = rk == MTM_KERNEL_MFMA || rk == MTM_KERNEL_MFMA16 || rk == MTM_KERNEL_MFMA_F32;
-    const bool masked_mfma = sc.masked && rk == MTM_KERNEL_MFMA;
-    if ((sc.masked && !masked_mfma) || (method == MTM_TM_CCORR && !want_t_always)) return MTM_OK;   // none needed
-    const int num_type = masked_mfma ? 0
-                       : (method == MTM_TM_CCORR_NORMED) ? 0
-                       : (method == MTM_TM_CCOEFF || method == MTM_TM_CCOEFF_NORMED) ? 1 : 2;
-    const bool normed = !masked_mfma && (method == MTM_TM_SQDIFF_NORMED || method == MTM_TM_CCORR_NORMED ||
-                                         method == MTM_TM_CCOEFF_NORMED);
-    const size_t plane = (size_t)st.pitch * oh;
-    MTMC(c->stats.ensure(sizeof(double) * plane * (kMaxChans + 2)));
-    double* base = c->stats.as<double>();
-    double* tp[kMaxChans];
-    for (int k = 0; k < kMaxChans; ++k) tp[k] = base + plane * k;
-    double* sum2 = base + plane * kMaxChans;
-    double* sq = base + plane * (kMaxChans + 1);
-    const int hs_pitch = st.pitch;
-    const long long hs_plane = (long long)hs_pitch * c->rows;
-    const bool u8 = c->dtype == MTM_U8;
-    const size_t esz = u8 ? sizeof(uint32_t) : sizeof(double);
-    MTMC(c->hs1.ensure(esz * hs_plane * c->chans));
-    MTMC(c->hs2.ensure(esz * hs_plane * c->chans));
-    const ImageDev img = image_dev(c);
-    const int want_t = (num_type == 1 || want_t_always) ? 1 : 0;
-    // what every launcher but the fused single-channel one takes: the window, the row-sum planes, the planes to write
-    const StatGeom g = stat_geom(c->rows, c->cols, c->chans, h, w);
-    const StatScratch hs{c->hs1.p, c->hs2.p, hs_pitch, hs_plane};
-    StatOut o{};
-    o.num_type = num_type, o.want_sq = normed ? 1 : 0, o.want_t = want_t, o.want_sum2 = 1;
-    for (int k = 0; k < kMaxChans; ++k) o.t[k] = tp[k];
-    o.t_plane = (long long)plane, o.sum2 = sum2, o.sq = sq, o.st_pitch = st.pitch;
-    const StatsRoute route = stats_route(c->dtype, c->chans, h, w, c->cols, c->fuse_stats != 0);
-    // fused single-kernel statistics for the common case
-    const bool fused_stats = route == kStatsRouteU8;
-    if (fused_stats) {
-        // (masked classes on the matrix cores: the sum2 plane is written by the sum I^2 M pass below, not here)
-        const int want_sum2 = (!masked_mfma && (num_type == 2 || (normed && num_type != 1) || !want_t_always)) ? 1 : 0;
-        const int nsb = (oh + kStatBand4 - 1) / kStatBand4;
-        const int b1 = sb1 < 0 ? nsb : std::min(sb1, nsb);
-        double* rsq = nullptr;
-        if (sc.rm_R > 0 && normed) {
-            MTMC(c->stats_rsq.ensure(sizeof(double) * plane));
-            rsq = c->stats_rsq.as<double>();
-        }
-        double* blk = nullptr;
-        double* blkq = nullptr;
-        int tail_s = 0;
-        // statistic ranges per 16-pixel column block: the hits-only screens of the multi-row and row-multiplexed tilings
-        if (c->chans == 1 && ((sc.r2 > 0 && normed) || (sc.rm_R > 0 && (normed || (masked_mfma && method == MTM_TM_CCORR_NORMED))))) {
-            st.blk_pitch = (st.pitch + 15) / 16;
-            // (the tail boxes' records, when the score launch screens its K loop, follow the window's in the same buffer)
-            const size_t nrec = 4 * (size_t)st.blk_pitch * oh;
-            tail_s = tail_split_for(c, R, sc);
-            MTMC(ensure_tail_consts(c, sc, tail_s));
-            MTMC(c->stats_blk.ensure(sizeof(double) * nrec * (tail_s ? 2 : 1)));
-            blk = c->stats_blk.as<double>();
-            st.blk = blk;
-            if (tail_s) {
-                blkq = blk + nrec;
-                st.blkq = blkq;
-            }
-        }
-        if (b1 > sb0) {
-            // banded upload with the layout conversion of the band's rows on this launch (run_score_banded): the kernel reads
-            // the raw upload buffer (every row that has arrived so far is there) and writes the planes of the new rows
-            StatLayout lay{};
-            const uint8_t* src = img.u8;
-            int src_pitch = img.u8_pitch;
-            if (c->lay_r1 > c->lay_r0) {
-                mtm_ctx::ImageSlot& sl = c->slot[c->cur];
-                lay.u8 = sl.u8.as<uint8_t>();
-                lay.u8b = sl.u8b.as<uint8_t>();
-                lay.pitch = img.u8_pitch;
-                lay.r0 = c->lay_r0;
-                lay.r1 = c->lay_r1;
-                src = sl.raw.as<uint8_t>();
-                src_pitch = c->cols;
-            }
-            if (R.zero_pending && c->stats_stream != nullptr) {         // banded call: the candidate header is cleared here
-                lay.zero16 = c->cands.as<unsigned long long>();
-                R.zero_pending = false;
-            }
-            StatU8Args a{};
-            a.img = src;
-            a.pitch = src_pitch;
-            a.h = h, a.w = w, a.oh = oh, a.ow = ow;
-            a.num_type = num_type, a.want_sq = normed ? 1 : 0, a.want_t = want_t, a.want_sum2 = want_sum2;
-            a.t0 = tp[0], a.sum2 = sum2, a.sq = sq, a.rsq = rsq, a.st_pitch = st.pitch;
-            a.blk = blk, a.blkq = blkq, a.blk_pitch = st.blk_pitch, a.tail_s = blkq ? tail_s : 0;
-            a.sb0 = sb0, a.sb1 = b1;
-            a.lay = lay;
-            MTMC(launch_stats_u8(c->stats_stream ? c->stats_stream : c->stream, a, 0, c->n_cus > 0 ? c->n_cus : 256));
-        }
-    } else if (route == kStatsRouteU8MC) {
-        // RGB: the fused kernel with one scan per channel + one for the squares (sum2 always written:
-        // vsum_stats_kernel does)
-        MTMC(launch_stats_u8mc(c->stream, img.u8, img.u8_pitch, img.u8_plane, g, o));
-    } else if (route == kStatsRouteU8TwoPass) {
-        MTMC(launch_stats_u8_2p(c->stream, img.u8, img.u8_pitch, img.u8_plane, g, hs, o));
-    } else if (route == kStatsRouteU8TwoPassWide) {
-        MTMC(ensure_f32_plane(c));
-        MTMC(launch_stats_u8_2p_wide(c->stream, img.f32, img.f32_pitch, img.f32_plane, g, hs, o));
-    } else if (route == kStatsRouteU16) {
-        // single-channel uint16: the fused kernel over the two byte planes (the ones the MFMA kernel reads)
-        const int nsb = (oh + kStatBand4 - 1) / kStatBand4;
-        const int b1 = sb1 < 0 ? nsb : std::min(sb1, nsb);
-        const uint8_t* hib = c->slot[c->cur].u8b.as<uint8_t>();
-        double* blk = nullptr;
-        if (normed && rk == MTM_KERNEL_MFMA16) {    // statistic ranges per 16-pixel column block: the kernel's hits-only screen
-            st.blk_pitch = (st.pitch + 15) / 16;
-            MTMC(c->stats_blk.ensure(sizeof(double) * 4 * (size_t)st.blk_pitch * oh));
-            blk = c->stats_blk.as<double>();
-            st.blk = blk;
-        }
-        MTMC(launch_stats_u16(c->stats_stream ? c->stats_stream : c->stream, hib, hib + img.u8_plane, img.u8_pitch, g, o, blk,
-                              st.blk_pitch, sb0, b1));
-    } else {
-        // Round 6, banded float32 uploads (run_score_banded): c->lay_r0 .. lay_r1 are the image rows that have just arrived
-        // (their horizontal sums), sb0 .. sb1 the output rows whose windows they complete, in blocks of kStatBand4 rows that
-        // make whole vsum bands (a band restarts its column sums: the planes are bit for bit those of one launch)
-        const bool part = c->lay_r1 > c->lay_r0 && route == kStatsRouteF64Lds;
-        const hipStream_t ss = c->stats_stream ? c->stats_stream : c->stream;
-        if (!part) MTMC(ensure_f32_plane(c));
-        const int o0 = part ? sb0 * kStatBand4 : 0, o1 = part && sb1 >= 0 ? std::min(oh, sb1 * kStatBand4) : oh;
-        if (route == kStatsRouteF64Lds)     // (the same sums in the same order, the row staged through LDS: mtm_k_stats.hip.h)
-            MTMC(launch_stats_f64_lds(ss, img.f32, img.f32_pitch, img.f32_plane, g, hs, o, part ? c->lay_r0 : 0,
-                                      part ? c->lay_r1 : c->rows, o0, o1));
-        else
-            MTMC(launch_stats_f64(ss, img.f32, img.f32_pitch, img.f32_plane, g, hs, o));
-    }
-    HIPC(hipGetLastError());
-    for (int k = 0; k < kMaxChans; ++k) st.t[k] = tp[k];
-    st.sum2 = sum2;
-    st.sq = sq;
-    if (masked_mfma) MTMC(launch_masked_sumsq(c, sc, fused_stats, st, sum2));
-    *out = st;
-    return MTM_OK;
-}
-
 // sum I^2 * M over every window of a masked uint8 class on the MFMA kernel, into `sum2`, the sum2 plane of `st` (it
 // overwrites the unmasked window sum of squares, which the masked path never uses).  `fused_stats`: launch_stats ran the
-// fused kernel.
-static int launch_masked_sumsq(mtm_ctx* c, const SizeClass& sc, bool fused_stats, const StatPlanes& st, double* sum2) {
+// fused kernel.  The last step of launch_stats (mtm_stats.hip), on c->stream behind the statistics launch.
+int launch_masked_sumsq(mtm_ctx* c, const SizeClass& sc, bool fused_stats, const StatPlanes& st, double* sum2) {
     const int h = sc.h, w = sc.w, oh = c->rows - h + 1, ow = c->cols - w + 1;
     const ImageDev img = image_dev(c);
     if (sc.mask_rm_off >= 0 && fused_stats) {
@@ -1014,9 +725,8 @@ static int launch_mfma(mtm_ctx* c, CallRoute& R, const SizeClass& sc, const Stat
     // (tail screen: the tail boxes' records and the templates' tail constants behind them)
     p.tail_split = (r2 && st.blkq != nullptr && only_li < 0 && !p.seg_skip) ? tail_split_for(c, R, sc) : 0;
     MTMC(ensure_tail_consts(c, sc, p.tail_split));          // (launch_stats has seen to it: a no-op)
-    if (!c->classes.empty() && &sc >= c->classes.data() && &sc < c->classes.data() + c->classes.size() &&
-        (size_t)(&sc - c->classes.data()) < c->tail_last.size())
-        c->tail_last[(size_t)(&sc - c->classes.data())] = p.tail_split;      // (what mtm_debug_class_tilings reports)
+    if (const int k = class_index(c, sc); k >= 0 && (size_t)k < c->tail_last.size())
+        c->tail_last[(size_t)k] = p.tail_split;                // (what mtm_debug_class_tilings reports)
     const size_t stat_bytes = rm ? 0 : r2 ? (size_t)kMfRows * ((mb + 1) / 2) * 1024 + (p.tail_split ? mf_tail_lds_bytes() : 0)
                                           : (size_t)kMfRows * mf_stat_bytes_per_wave(c->chans == 3 ? 3 : 1);
     const bool ext = R.ext;                          // plan_call checked the class
@@ -1183,9 +893,8 @@ static void launch_dot4(mtm_ctx* c, const SizeClass& sc, const int* tl, int n_li
     const bool wide = (double)c->chans * sc.w * sc.h * 65025.0 >= 4294967296.0;
     const int vi = wide ? kDotWideVariant : c->dot_variant;
     const DotVariant& v = kDotVariants[vi];
-    if (!c->classes.empty() && &sc >= c->classes.data() && &sc < c->classes.data() + c->classes.size() &&
-        (size_t)(&sc - c->classes.data()) < c->dot_last.size())
-        c->dot_last[(size_t)(&sc - c->classes.data())] = vi;                 // (what mtm_debug_class_tilings reports)
+    if (const int k = class_index(c, sc); k >= 0 && (size_t)k < c->dot_last.size())
+        c->dot_last[(size_t)k] = vi;                            // (what mtm_debug_class_tilings reports)
     const DotParams p = dot_params(c, v, c->chans, sc.h, sc.w, n_list);
     hipLaunchKernelGGL(v.fn, work_grid(p.n_work), dim3(256), 0, c->stream, p, c->td.as<TemplDev>(), tl, c->packs.as<uint8_t>(),
                        st, c->maps.as<float>());
@@ -1581,13 +1290,9 @@ static int run_score_banded_f32(mtm_ctx* c, CallRoute& R, const ImageArgs& a) {
         const int r1 = last ? a.rows : o_split + h - 1;
         MTMC(upload_rows_f32c1(sl, g, a.px, a.stride, r_done, r1, bs));
         if (k == 0) HIPC(hipEventRecord(c->ev[0], c->stream));          // (see fm_begin)
-        c->lay_r0 = r_done;
-        c->lay_r1 = r1;
-        c->stats_stream = bs;
-        const int rc = launch_stats(c, R, sc, &st, last ? o_split / kStatBand4 : 0, last ? -1 : o_split / kStatBand4);
-        c->stats_stream = nullptr;
-        c->lay_r0 = c->lay_r1 = 0;
-        MTMC(rc);
+        // (the output rows the band completes, the image rows that have just arrived)
+        const StatBand band{bs, last ? o_split / kStatBand4 : 0, last ? -1 : o_split / kStatBand4, r_done, r1};
+        MTMC(launch_stats(c, R, sc, &st, band));
         r_done = r1;
         HIPC(hipEventRecord(c->band_ev[(size_t)k], bs));
         (void)hipStreamQuery(bs);
@@ -1670,8 +1375,8 @@ int run_score_banded(mtm_ctx* c, CallRoute& R, const ImageArgs& a) {
             MTMC(upload_rows_u16c1(sl, g, a.px, a.stride, r_done, r1, bs));
         else
             MTMC(upload_rows_u8c1(sl, g, a.px, a.stride, r_done, r1, bs, true, nullptr, nullptr, !fuse_lay));
-        c->lay_r0 = fuse_lay ? r_done : 0;
-        c->lay_r1 = fuse_lay ? r1 : 0;
+        // (the band's statistics launch: its row units, and the rows it converts on the way)
+        const StatBand band{bs, sb_done, sb1, fuse_lay ? r_done : 0, fuse_lay ? r1 : 0};
         if (r_done == 0) {
             HIPC(hipEventRecord(c->ev[0], c->stream));           // (see fm_begin)
             if (c->classes.size() > 1) {                         // the lanes of the other classes start behind the call's set-up too
@@ -1682,11 +1387,7 @@ int run_score_banded(mtm_ctx* c, CallRoute& R, const ImageArgs& a) {
         r_done = r1;
         host_trace(c, k == 0 ? 4 : 7);                           // the band's copy call returned
         StatPlanes st;
-        c->stats_stream = bs;
-        const int rc = launch_stats(c, R, sc, &st, sb_done, sb1);
-        c->stats_stream = nullptr;
-        c->lay_r0 = c->lay_r1 = 0;
-        MTMC(rc);
+        MTMC(launch_stats(c, R, sc, &st, band));
         sb_done = sb1;
         HIPC(hipEventRecord(c->band_ev[(size_t)k], bs));
         (void)hipStreamQuery(bs);                                // submit now (the runtime batches commands)
@@ -1717,272 +1418,6 @@ int run_score_banded(mtm_ctx* c, CallRoute& R, const ImageArgs& a) {
 }  // namespace mtmi
 
 extern "C" {
-
-// Test support: stats_u8_kernel on an image the caller hands over (tests/test_gpu_window_stats.py), launched by
-// launch_stats_u8 like every statistics launch of a search call.  Everything lives in stats_dbg, laid out per call and
-// filled with the caller's pattern first; nothing of the context's image, placement or options is read or written.
-int mtm_debug_window_stats(mtm_ctx* c, const mtm_window_stats* a) {
-    if (!c || !a) {
-        set_error("mtm_debug_window_stats: null context or arguments");
-        return MTM_E_INVALID;
-    }
-    MTM_NOT_IN_FLIGHT(c, "mtm_debug_window_stats");
-    const auto bad = [](const char* what) {
-        set_error(std::string("mtm_debug_window_stats: ") + what);
-        return MTM_E_INVALID;
-    };
-    const int rows = a->rows, cols = a->cols, h = a->h, w = a->w;
-    if (!a->image || !a->info || rows < 1 || cols < 1 || rows > 16384 || cols > 16384 || h < 1 || w < 1 || h > rows || w > cols)
-        return bad("an image of 1 .. 16384 rows and columns and a window inside it are needed");
-    if (stats_route(MTM_U8, 1, h, w, cols, true) != kStatsRouteU8) return bad("the fused kernel takes w <= 768 and w h 255^2 < 2^32");
-    if (a->num_type < 0 || a->num_type > 2 || a->form < 0 || a->form > kStatFormCount || a->pattern_byte < 0 || a->pattern_byte > 255)
-        return bad("num_type 0 .. 2, a form and a pattern byte");
-    const int oh = rows - h + 1, ow = cols - w + 1, nsb = (oh + kStatBand4 - 1) / kStatBand4;
-    const int sb0 = a->sb0, sb1 = a->sb1 < 0 ? nsb : std::min(a->sb1, nsb);
-    if (sb0 < 0 || sb0 >= sb1) return bad("an empty range of row units");
-    const bool conv = a->lay_r1 > a->lay_r0;
-    if (conv && (cols % 4 != 0 || a->lay_r0 < 0 || a->lay_r1 > rows)) return bad("the conversion needs cols % 4 == 0 and rows inside the image");
-    const bool tail = a->tail_s != 0;
-    if (tail && (a->tail_s < 1 || a->tail_s > h - 1 || !a->blk || !a->blkq)) return bad("tail_s in 1 .. h - 1, with blk and blkq");
-    if (!tail && a->blkq) return bad("blkq without tail_s");
-    if (a->rsq && !a->sq) return bad("rsq without sq");
-    const int st_pitch = (int)round_up((size_t)ow, 4), blk_pitch = (st_pitch + 15) / 16;
-    const int pitch = (int)round_up((size_t)cols + kPadCols, 64), rows_alloc = rows + kPadRows;
-    // stats_dbg: [header][raw image][uint8 plane][int8 view][t0][sum2][sq][rsq][blk][blkq]
-    size_t total = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t off = total;
-        total += round_up(std::max<size_t>(bytes, 16), 256);
-        return off;
-    };
-    const size_t plane_bytes = (size_t)pitch * rows_alloc, st_bytes = sizeof(double) * (size_t)st_pitch * oh;
-    const size_t rec_bytes = sizeof(double) * 4 * (size_t)blk_pitch * oh;
-    const size_t o_hdr = take(16), o_raw = take((size_t)rows * cols), o_u8 = take(plane_bytes), o_u8b = take(plane_bytes);
-    const size_t o_t0 = take(st_bytes), o_sum2 = take(st_bytes), o_sq = take(st_bytes), o_rsq = take(st_bytes);
-    const size_t o_blk = take(rec_bytes), o_blkq = take(rec_bytes);
-    HIPC(hipSetDevice(c->device));
-    MTMC(c->stats_dbg.ensure(total));
-    uint8_t* b = c->stats_dbg.as<uint8_t>();
-    HIPC(hipMemsetAsync(b, a->pattern_byte, total, c->stream));
-    HIPC(hipMemcpyAsync(b + o_raw, a->image, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
-    if (!conv) {        // the plane as an upload leaves it: the image, zero padding
-        HIPC(hipMemsetAsync(b + o_u8, 0, plane_bytes, c->stream));
-        HIPC(hipMemcpy2DAsync(b + o_u8, (size_t)pitch, a->image, (size_t)cols, (size_t)cols, (size_t)rows, hipMemcpyHostToDevice,
-                              c->stream));
-    }
-    StatU8Args k{};
-    k.img = conv ? b + o_raw : b + o_u8;
-    k.pitch = conv ? cols : pitch;
-    k.h = h, k.w = w, k.oh = oh, k.ow = ow;
-    k.num_type = a->num_type, k.want_sq = a->sq ? 1 : 0, k.want_t = a->t0 ? 1 : 0, k.want_sum2 = a->sum2 ? 1 : 0;
-    k.t0 = reinterpret_cast<double*>(b + o_t0), k.sum2 = reinterpret_cast<double*>(b + o_sum2);
-    k.sq = reinterpret_cast<double*>(b + o_sq), k.rsq = a->rsq ? reinterpret_cast<double*>(b + o_rsq) : nullptr;
-    k.st_pitch = st_pitch;
-    k.blk = a->blk ? reinterpret_cast<double*>(b + o_blk) : nullptr;
-    k.blkq = tail ? reinterpret_cast<double*>(b + o_blkq) : nullptr;
-    k.blk_pitch = a->blk ? blk_pitch : 0, k.tail_s = a->tail_s;
-    k.sb0 = sb0, k.sb1 = sb1;
-    if (conv) {
-        k.lay.u8 = b + o_u8, k.lay.u8b = b + o_u8b, k.lay.pitch = pitch;
-        k.lay.r0 = a->lay_r0, k.lay.r1 = a->lay_r1;
-    }
-    if (a->zero_header) k.lay.zero16 = reinterpret_cast<unsigned long long*>(b + o_hdr);
-    const int n_cus = c->n_cus > 0 ? c->n_cus : 256;
-    const int strips = (ow + stats_u8_owg(w) - 1) / stats_u8_owg(w);
-    const int form = a->form ? a->form : stats_u8_form(strips, sb1 - sb0, n_cus);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int rc = MTM_OK;
-    float ms = 0.0f;
-    hipError_t e = hipEventCreate(&ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
-    if (e == hipSuccess) rc = launch_stats_u8(c->stream, k, form, n_cus);
-    if (e == hipSuccess && rc == MTM_OK) e = hipEventRecord(ev[1], c->stream);
-    if (e == hipSuccess && rc == MTM_OK) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && rc == MTM_OK) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    for (hipEvent_t v : ev)
-        if (v) (void)hipEventDestroy(v);
-    MTMC(rc);
-    HIPC(e);
-    const auto fetch = [&](void* to, size_t off, size_t bytes) -> int {
-        if (to) HIPC(hipMemcpy(to, b + off, bytes, hipMemcpyDeviceToHost));
-        return MTM_OK;
-    };
-    MTMC(fetch(a->t0, o_t0, st_bytes));
-    MTMC(fetch(a->sum2, o_sum2, st_bytes));
-    MTMC(fetch(a->sq, o_sq, st_bytes));
-    MTMC(fetch(a->rsq, o_rsq, st_bytes));
-    MTMC(fetch(a->blk, o_blk, rec_bytes));
-    MTMC(fetch(a->blkq, o_blkq, rec_bytes));
-    MTMC(fetch(a->u8, o_u8, (size_t)rows * pitch));
-    MTMC(fetch(a->u8b, o_u8b, (size_t)rows * pitch));
-    MTMC(fetch(a->header, o_hdr, 16));
-    const int rows_wg = kStatFormRows[form - 1];
-    const int64_t info[8] = {st_pitch, blk_pitch, pitch, form, strips, stats_u8_grid_y(sb0, sb1, oh, rows_wg), n_cus,
-                             (int64_t)llround((double)ms * 1e6)};
-    std::memcpy(a->info, info, sizeof(info));
-    return MTM_OK;
-}
-
-// Test support: the six other routes of stats_route (tests/test_gpu_stats_routes.py), each through the launcher launch_stats
-// uses.  Everything lives in stats_dbg, filled with the caller's pattern first.  The image planes are laid out on the HOST
-// exactly as an upload of that dtype leaves them (pitch = cols + 512 rounded up to 64, rows + kPadRows rows a plane, zero
-// padding - 0x80 in the biased byte planes) and copied in one piece: the conversion kernels are not what is under test.
-int mtm_debug_window_stats_route(mtm_ctx* c, const mtm_window_stats_route* a) {
-    if (!c || !a) {
-        set_error("mtm_debug_window_stats_route: null context or arguments");
-        return MTM_E_INVALID;
-    }
-    MTM_NOT_IN_FLIGHT(c, "mtm_debug_window_stats_route");
-    const auto bad = [](const char* what) {
-        set_error(std::string("mtm_debug_window_stats_route: ") + what);
-        return MTM_E_INVALID;
-    };
-    const int rows = a->rows, cols = a->cols, chans = a->chans, h = a->h, w = a->w, dtype = a->dtype;
-    if (!a->image || !a->info || rows < 1 || cols < 1 || rows > 16384 || cols > 16384 || h < 1 || w < 1 || h > rows || w > cols)
-        return bad("an image of 1 .. 16384 rows and columns and a window inside it are needed");
-    if (chans < 1 || chans > kMaxChans || (dtype != MTM_U8 && dtype != MTM_U16 && dtype != MTM_F32))
-        return bad("1 .. 4 channels of uint8, uint16 or float32");
-    if (a->num_type < 0 || a->num_type > 2 || a->pattern_byte < 0 || a->pattern_byte > 255 || a->route < 0 ||
-        a->route >= kStatsRouteCount || (a->want & ~31) != 0)
-        return bad("num_type 0 .. 2, a route, the planes wanted and a pattern byte");
-    const int route = a->route ? a->route : (int)stats_route(dtype, chans, h, w, cols, true);
-    if (route == kStatsRouteU8) return bad("the fused single-channel uint8 kernel is mtm_debug_window_stats's");
-    if (const char* why = stats_route_refusal(route, dtype, chans, h, w, cols)) return bad(why);
-    const StatGeom g = stat_geom(rows, cols, chans, h, w);
-    const int oh = g.oh, ow = g.ow, nsb = (oh + kStatBand4 - 1) / kStatBand4;
-    const int sb0 = a->sb0, sb1 = a->sb1 < 0 ? nsb : std::min(a->sb1, nsb);
-    if (sb0 < 0 || sb0 >= sb1) return bad("an empty range of row units");
-    const bool part = a->lay_r1 > a->lay_r0;
-    const bool ranged = route == kStatsRouteU16 || (route == kStatsRouteF64Lds && part);
-    if (part && route != kStatsRouteF64Lds) return bad("image rows lay_r0 .. lay_r1: the F64_LDS route only");
-    if (!ranged && (sb0 != 0 || sb1 != nsb)) return bad("a range of row units: the U16 route or a partial F64_LDS launch only");
-    const int o0 = sb0 * kStatBand4, o1 = std::min(oh, sb1 * kStatBand4);
-    if (part) {
-        if (o0 % kVsumBand != 0) return bad("a partial F64_LDS launch starts on a whole band: sb0 * 8 a multiple of 32");
-        if (a->lay_r0 < 0 || a->lay_r1 > rows || a->lay_r0 > o0) return bad("lay_r0 .. lay_r1 inside the image, lay_r0 <= sb0 * 8");
-        if (a->lay_r1 < o1 + h - 1) return bad("lay_r1 < min(oh, sb1 * 8) + h - 1: the windows' last rows have no sums");
-    }
-    const bool want_t = a->want & 1, want_sum2 = a->want & 2, want_sq = a->want & 4, want_blk = a->want & 8, nulls = a->want & 16;
-    const bool two_pass = route != kStatsRouteU8MC && route != kStatsRouteU16;
-    if (want_blk && route != kStatsRouteU16) return bad("blk: the U16 route only");
-    if (two_pass && nulls && !want_sum2) return bad("the two-pass chains write sum2 whatever is asked: it cannot be null");
-    const int st_pitch = (int)round_up((size_t)ow, 4), blk_pitch = (st_pitch + 15) / 16;
-    const int pitch = (int)round_up((size_t)cols + kPadCols, 64), rows_alloc = rows + kPadRows;
-    // stats_dbg: [image planes][hs1][hs2][t0 .. t3][sum2][sq][blk]
-    size_t total = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t off = total;
-        total += round_up(std::max<size_t>(bytes, 16), 256);
-        return off;
-    };
-    const bool bytes_in = route == kStatsRouteU8MC || route == kStatsRouteU8TwoPass || route == kStatsRouteU16;
-    const size_t plane_elems = (size_t)pitch * rows_alloc;
-    const int n_planes = route == kStatsRouteU16 ? 2 : chans;
-    const size_t img_bytes = plane_elems * n_planes * (bytes_in ? 1 : sizeof(float));
-    const bool u32_sums = route == kStatsRouteU8TwoPass || route == kStatsRouteU8TwoPassWide;
-    const long long hs_plane = (long long)st_pitch * rows;
-    const size_t hs_bytes = two_pass ? (u32_sums ? sizeof(uint32_t) : sizeof(double)) * (size_t)hs_plane * chans : 0;
-    const size_t st_bytes = sizeof(double) * (size_t)st_pitch * oh, rec_bytes = sizeof(double) * 4 * (size_t)blk_pitch * oh;
-    const size_t o_img = take(img_bytes), o_hs1 = take(hs_bytes), o_hs2 = take(hs_bytes), o_t = take(st_bytes * kMaxChans);
-    const size_t o_sum2 = take(st_bytes), o_sq = take(st_bytes), o_blk = take(rec_bytes);
-    if (total > ((size_t)256 << 20)) return bad("more than 256 MB of planes");
-    // the planes, on the host
-    std::vector<uint8_t> stage(img_bytes, route == kStatsRouteU16 ? 0x80 : 0);
-    {
-        const auto px = [&](int y, int x, int ch) -> double {
-            const size_t i = ((size_t)y * cols + x) * chans + ch;
-            return dtype == MTM_U8 ? (double)static_cast<const uint8_t*>(a->image)[i]
-                 : dtype == MTM_U16 ? (double)static_cast<const uint16_t*>(a->image)[i]
-                                    : (double)static_cast<const float*>(a->image)[i];
-        };
-        float* f = reinterpret_cast<float*>(stage.data());
-        for (int y = 0; y < rows; ++y)
-            for (int x = 0; x < cols; ++x) {
-                const size_t o = (size_t)y * pitch + x;
-                if (route == kStatsRouteU16) {
-                    const unsigned v = static_cast<const uint16_t*>(a->image)[(size_t)y * cols + x];
-                    stage[o] = (uint8_t)((v >> 8) ^ 0x80u);
-                    stage[plane_elems + o] = (uint8_t)((v & 255u) ^ 0x80u);
-                } else {
-                    for (int ch = 0; ch < chans; ++ch) {
-                        if (bytes_in) stage[ch * plane_elems + o] = static_cast<const uint8_t*>(a->image)[((size_t)y * cols + x) * chans + ch];
-                        else f[ch * plane_elems + o] = (float)px(y, x, ch);
-                    }
-                }
-            }
-    }
-    HIPC(hipSetDevice(c->device));
-    MTMC(c->stats_dbg.ensure(total));
-    uint8_t* b = c->stats_dbg.as<uint8_t>();
-    HIPC(hipMemsetAsync(b, a->pattern_byte, total, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    HIPC(hipMemcpy(b + o_img, stage.data(), img_bytes, hipMemcpyHostToDevice));
-    const StatScratch hs{b + o_hs1, b + o_hs2, st_pitch, hs_plane};
-    StatOut o{};
-    o.num_type = a->num_type, o.want_sq = want_sq, o.want_t = want_t, o.want_sum2 = want_sum2;
-    for (int k = 0; k < kMaxChans; ++k)
-        o.t[k] = (k < chans && (want_t || !nulls)) ? reinterpret_cast<double*>(b + o_t + st_bytes * k) : nullptr;
-    o.t_plane = (long long)st_pitch * oh, o.st_pitch = st_pitch;
-    o.sum2 = (want_sum2 || !nulls) ? reinterpret_cast<double*>(b + o_sum2) : nullptr;
-    o.sq = (want_sq || !nulls) ? reinterpret_cast<double*>(b + o_sq) : nullptr;
-    double* blk = want_blk ? reinterpret_cast<double*>(b + o_blk) : nullptr;
-    const int owg = stats_u8_owg(w);
-    const int hx = (ow + 256 * kHsumSeg - 1) / (256 * kHsumSeg), vx = (ow + 255) / 256, vy = (o1 - o0 + kVsumBand - 1) / kVsumBand;
-    int64_t info[12] = {route, st_pitch, blk_pitch, pitch, 0, 0, 0, two_pass ? vx : 0, two_pass ? vy : 0, two_pass ? st_pitch : 0, 0, 0};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int rc = MTM_OK;
-    float ms = 0.0f;
-    hipError_t e = hipEventCreate(&ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
-    if (e == hipSuccess) switch (route) {
-        case kStatsRouteU8MC:
-            info[4] = (ow + owg - 1) / owg, info[5] = nsb, info[6] = 1;
-            rc = launch_stats_u8mc(c->stream, b + o_img, pitch, (long long)plane_elems, g, o);
-            break;
-        case kStatsRouteU16:
-            info[4] = (ow + owg - 1) / owg, info[5] = sb1 - sb0, info[6] = 1;
-            rc = launch_stats_u16(c->stream, b + o_img, b + o_img + plane_elems, pitch, g, o, blk, want_blk ? blk_pitch : 0, sb0, sb1);
-            break;
-        case kStatsRouteU8TwoPass:
-            info[4] = rows, info[5] = chans, info[6] = 1, info[10] = (int64_t)(sizeof(uint32_t) * 2 * (cols + 1));
-            rc = launch_stats_u8_2p(c->stream, b + o_img, pitch, (long long)plane_elems, g, hs, o);
-            break;
-        case kStatsRouteU8TwoPassWide:
-            info[4] = hx, info[5] = rows, info[6] = chans;
-            rc = launch_stats_u8_2p_wide(c->stream, reinterpret_cast<const float*>(b + o_img), pitch, (long long)plane_elems, g, hs, o);
-            break;
-        case kStatsRouteF64Lds:
-            info[4] = hx, info[5] = part ? a->lay_r1 - a->lay_r0 : rows, info[6] = chans, info[10] = (int64_t)hsum_lds_bytes(w);
-            rc = launch_stats_f64_lds(c->stream, reinterpret_cast<const float*>(b + o_img), pitch, (long long)plane_elems, g, hs, o,
-                                      part ? a->lay_r0 : 0, part ? a->lay_r1 : rows, o0, o1);
-            break;
-        default:
-            info[4] = hx, info[5] = rows, info[6] = chans;
-            rc = launch_stats_f64(c->stream, reinterpret_cast<const float*>(b + o_img), pitch, (long long)plane_elems, g, hs, o);
-            break;
-    }
-    if (e == hipSuccess && rc == MTM_OK) e = hipEventRecord(ev[1], c->stream);
-    if (e == hipSuccess && rc == MTM_OK) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && rc == MTM_OK) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    for (hipEvent_t v : ev)
-        if (v) (void)hipEventDestroy(v);
-    MTMC(rc);
-    HIPC(e);
-    const auto fetch = [&](void* to, size_t off, size_t bytes) -> int {
-        if (to) HIPC(hipMemcpy(to, b + off, bytes, hipMemcpyDeviceToHost));
-        return MTM_OK;
-    };
-    double* const tout[kMaxChans] = {a->t0, a->t1, a->t2, a->t3};
-    for (int k = 0; k < kMaxChans; ++k) MTMC(fetch(tout[k], o_t + st_bytes * k, st_bytes));
-    MTMC(fetch(a->sum2, o_sum2, st_bytes));
-    MTMC(fetch(a->sq, o_sq, st_bytes));
-    MTMC(fetch(a->blk, o_blk, rec_bytes));
-    info[11] = (int64_t)llround((double)ms * 1e6);
-    std::memcpy(a->info, info, sizeof(info));
-    return MTM_OK;
-}
 
 // Test support: the masked float32 screen (tests/test_gpu_maskf32_screen.py) through the stage functions launch_masked_bf16
 // runs - mbf_prepare, mbf_raw, mbf_list, mbf_rescore - with what they leave behind copied out in between: the two raw

@@ -1,7 +1,8 @@
-// Which kernel chain produces a size class's window statistics, written once: launch_stats (mtm_launch.hip) switches on it,
-// class_reads_f32 / the banded-upload rule / choose_tiling (mtm_placement.hip) ask it, the test-support entries
-// mtm_debug_window_stats and mtm_debug_window_stats_route admit their arguments with it, and the host checks
-// (tests/native/sanitize_host.cpp) walk every boundary.  Plain C++: no HIP type, no context.
+// Which kernel chain produces a size class's window statistics (stats_route) and which planes and records the class's score
+// kernel reads (stat_wants), each written once: launch_stats (mtm_stats.hip) asks both and switches on the route,
+// class_reads_f32 / the banded-upload rule (mtm_launch.hip) / choose_tiling (mtm_placement.hip) ask the route, the
+// test-support entries mtm_debug_window_stats and mtm_debug_window_stats_route (mtm_stats.hip) admit their arguments with
+// it, and the host checks (tests/native/sanitize_host.cpp) walk every boundary.  Plain C++: no HIP type, no context.
 #pragma once
 #include "../../include/mtm_hip.h"
 
@@ -24,6 +25,15 @@ constexpr int kStatsFusedMaxW = 768;        // fused kernels: a strip of 1024 im
 constexpr int kStatsHsumU8MaxCols = 8191;   // hsum_u8_kernel: two uint32 prefix rows of cols + 1 words in 64 KB of LDS
 constexpr int kStatsHsumLdsMaxW = 1024;     // hsum_lds_kernel: 256 * 16 + w floats (and their padding) in LDS
 constexpr double kStatsU32Range = 4294967296.0;
+// the units the launches' row ranges are counted in (the banded runners of mtm_launch.hip cut their bands on them)
+#ifndef MTM_STAT_BAND4
+#define MTM_STAT_BAND4 8
+#endif
+constexpr int kStatBand4 = MTM_STAT_BAND4;    // fused statistics kernels: output rows per row unit (the unit of [sb0, sb1) ranges)
+#ifndef MTM_VSUM_BAND
+#define MTM_VSUM_BAND 32
+#endif
+constexpr int kVsumBand = MTM_VSUM_BAND;      // vsum_stats_kernel: output rows per band (a band restarts its column sums)
 
 // a fused kernel's uint32 prefix sums hold every window sum it forms: chans * w * h * 255^2 (uint8: the squares of all
 // channels in one prefix) or w * h * 65535 (uint16: the sums; the squares are uint64) stays below 2^32
@@ -68,6 +78,46 @@ inline const char* stats_route_refusal(int route, int dtype, int chans, int h, i
     default:
         return "no such route";
     }
+}
+
+// What the score kernel of a size class reads of the window statistics - a function of the call's method and the class's
+// placement, nothing else: launch_stats sizes, carves and fills exactly this.  (The tail boxes' records are not here:
+// tail_split_for needs the call's route.)
+struct StatWants {
+    bool none = false;          // the class's kernel reads no statistics at all: no launch
+    bool masked_mfma = false;   // masked class on the int8 matrix cores: window sums only, sum2 from the sum I^2 M pass
+    int num_type = 0;           // what the numerator needs: 0 nothing, 1 the window sums per channel, 2 the sum of squares
+    bool normed = false;        // the sqrt plane
+    bool want_t = false;        // the window sums are written
+    bool want_sum2 = false;     // ... the sum of squares, by the fused uint8 kernel (every other chain writes it anyway)
+    bool rsq = false;           // the reciprocal of the sqrt plane (fused uint8 kernel)
+    bool blk = false;           // the records per 16-column block (fused uint8 and uint16 kernels): the hits-only screens
+};
+// `mask_rm`: the masked class has its row-multiplexed mask pack (SizeClass::mask_rm_off >= 0) - that chooses the kernel of
+// the sum I^2 M pass, not what is wanted of this one: no field depends on it (the host checks hold that)
+inline StatWants stat_wants(int method, int kernel, bool masked, bool mask_rm, int r2, int rm_R, int chans, int dtype) {
+    (void)mask_rm;
+    StatWants s;
+    const bool want_t_always = kernel == MTM_KERNEL_MFMA || kernel == MTM_KERNEL_MFMA16 || kernel == MTM_KERNEL_MFMA_F32;
+    s.masked_mfma = masked && kernel == MTM_KERNEL_MFMA;
+    s.none = (masked && !s.masked_mfma) || (method == MTM_TM_CCORR && !want_t_always);
+    s.num_type = s.masked_mfma ? 0
+               : (method == MTM_TM_CCORR_NORMED) ? 0
+               : (method == MTM_TM_CCOEFF || method == MTM_TM_CCOEFF_NORMED) ? 1 : 2;
+    s.normed = !s.masked_mfma && (method == MTM_TM_SQDIFF_NORMED || method == MTM_TM_CCORR_NORMED ||
+                                  method == MTM_TM_CCOEFF_NORMED);
+    s.want_t = s.num_type == 1 || want_t_always;
+    // (masked classes on the matrix cores: the sum2 plane is written by the sum I^2 M pass, not by the statistics launch)
+    s.want_sum2 = !s.masked_mfma && (s.num_type == 2 || (s.normed && s.num_type != 1) || !want_t_always);
+    s.rsq = rm_R > 0 && s.normed;
+    // statistic ranges per 16-pixel column block: the hits-only screens of the multi-row and row-multiplexed tilings
+    // (uint8), of the uint16 kernel
+    if (dtype == MTM_U16)
+        s.blk = chans == 1 && s.normed && kernel == MTM_KERNEL_MFMA16;
+    else if (dtype == MTM_U8)
+        s.blk = chans == 1 && ((r2 > 0 && s.normed) ||
+                               (rm_R > 0 && (s.normed || (s.masked_mfma && method == MTM_TM_CCORR_NORMED))));
+    return s;
 }
 
 }  // namespace mtm

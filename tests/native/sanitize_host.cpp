@@ -664,6 +664,52 @@ static void test_stats_route() {
     CHECK(stats_route(MTM_F32, 1, 8, 1024, 2000, true) == kStatsRouteF64Lds && stats_route(MTM_F32, 1, 8, 1025, 2000, true) == kStatsRouteF64);
 }
 
+// ---- what a class's score kernel reads of the window statistics (stat_wants, mtm_stats_route.h), against what the consumers
+// need, stated per consumer: the masked float64 / naive / dot4 kernels and TM_CCORR off the matrix cores read no plane; the
+// numerator needs the window sums for the centred methods, the sum of squares for the two SQDIFF ones and plain TM_CCORR; the
+// matrix-core epilogues undo their operands' bias with the window sums whatever the method; a masked class on the int8 cores
+// takes its sum2 from the sum I^2 M pass and normalises there; the reciprocal plane is the row-multiplexed epilogue's; the
+// block records are the single-channel hits-only screens'
+static void test_stat_wants() {
+    const int methods[] = {MTM_TM_SQDIFF, MTM_TM_SQDIFF_NORMED, MTM_TM_CCORR, MTM_TM_CCORR_NORMED, MTM_TM_CCOEFF, MTM_TM_CCOEFF_NORMED};
+    const int kernels[] = {MTM_KERNEL_AUTO, MTM_KERNEL_NAIVE, MTM_KERNEL_DOT4, MTM_KERNEL_MFMA, MTM_KERNEL_MFMA16, MTM_KERNEL_MFMA_F32};
+    long long n = 0, n_none = 0, n_blk = 0, n_rsq = 0;
+    for (int method : methods)
+        for (int kernel : kernels)
+            for (int masked = 0; masked <= 1; ++masked)
+                for (int mask_rm = 0; mask_rm <= 1; ++mask_rm)
+                    for (int r2 : {0, 1, 2})
+                        for (int rm_R : {0, 2, 16})
+                            for (int chans = 1; chans <= 4; ++chans)
+                                for (int dtype : {MTM_U8, MTM_F32, MTM_U16}) {
+                                    const StatWants s = stat_wants(method, kernel, masked != 0, mask_rm != 0, r2, rm_R, chans, dtype);
+                                    ++n;
+                                    const bool cores = kernel == MTM_KERNEL_MFMA || kernel == MTM_KERNEL_MFMA16 || kernel == MTM_KERNEL_MFMA_F32;
+                                    const bool mm = masked && kernel == MTM_KERNEL_MFMA;
+                                    const bool normed_method = method == MTM_TM_SQDIFF_NORMED || method == MTM_TM_CCORR_NORMED || method == MTM_TM_CCOEFF_NORMED;
+                                    const bool ccoeff = method == MTM_TM_CCOEFF || method == MTM_TM_CCOEFF_NORMED;
+                                    CHECK(s.masked_mfma == mm);
+                                    CHECK(s.none == ((masked && kernel != MTM_KERNEL_MFMA) || (method == MTM_TM_CCORR && !cores)));
+                                    CHECK(s.num_type == ((mm || method == MTM_TM_CCORR_NORMED) ? 0 : ccoeff ? 1 : 2));
+                                    CHECK(s.normed == (normed_method && !mm));
+                                    CHECK(s.want_t == (s.num_type == 1 || cores));
+                                    if (mm) CHECK(!s.want_sum2);
+                                    else if (s.num_type == 2 || (s.normed && s.num_type != 1) || !cores) CHECK(s.want_sum2);
+                                    // ... and off where nothing reads the plane: a centred method on the matrix cores (the
+                                    // numerator takes the window sums, the norm comes from the sqrt plane)
+                                    else CHECK(!s.want_sum2);
+                                    if (s.rsq) CHECK(rm_R > 0 && s.normed);
+                                    if (s.blk) CHECK(chans == 1);
+                                    if (s.blk && mm) CHECK(method == MTM_TM_CCORR_NORMED && rm_R > 0);
+                                    // the mask's row-multiplexed pack chooses the kernel of the sum I^2 M pass, nothing here
+                                    const StatWants t = stat_wants(method, kernel, masked != 0, mask_rm == 0, r2, rm_R, chans, dtype);
+                                    CHECK(s.none == t.none && s.masked_mfma == t.masked_mfma && s.num_type == t.num_type && s.normed == t.normed &&
+                                          s.want_t == t.want_t && s.want_sum2 == t.want_sum2 && s.rsq == t.rsq && s.blk == t.blk);
+                                    n_none += s.none, n_blk += s.blk, n_rsq += s.rsq;
+                                }
+    CHECK(n == 6 * 6 * 2 * 2 * 3 * 3 * 4 * 3 && n_none > 0 && n_none < n && n_blk > 0 && n_rsq > 0);
+}
+
 // ---- the host-only pieces of fm_end (mtm_api.hip; its peak pass: mtm_peaks.hip): the 3x3 test of the candidate list, the trivial-map rule, the ladder
 
 // one case of verify_candidates_3x3 against brute force over the maps: `maps[t]` the scores of an oh[t] x ow[t] map, the list
@@ -1176,6 +1222,7 @@ int main() {
     test_nms_grid(rng);
     test_peak_sizing(rng);
     test_stats_route();
+    test_stat_wants();
     test_host(rng);
     test_group(rng);
     // two groups driven from two caller threads at once (each group is single-caller; the library must not share state)

@@ -1,5 +1,5 @@
 """The six window-statistics kernel chains next to the fused single-channel uint8 one (csrc/mtm_stats_route.h, the launchers of
-csrc/mtm_launch.hip, the kernels of csrc/mtm_k_stats.hip.h) restated in numpy, bit for bit - tests/stats_model.py does the same
+csrc/mtm_stats.hip, the kernels of csrc/mtm_k_stats.hip.h) restated in numpy, bit for bit - tests/stats_model.py does the same
 for the seventh.
 
 The library is built with -ffp-contract=off and the device's float64 sqrt is correctly rounded, so every plane is a fixed

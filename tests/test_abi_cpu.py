@@ -221,7 +221,7 @@ def test_no_spill_ahead_of_an_exec_restore():
     files, hits = scan.scan_all()
     assert len(files) >= 11, files                     # every .hip unit left its assembly behind
     names = " ".join(os.path.basename(f) for f in files)
-    for unit in ("mtm_mfma_plain", "mtm_mfma_rows", "mtm_mfma_rm", "mtm_mfma_ext", "mtm_mfma_kp", "mtm_bf16", "mtm_api", "mtm_peaks", "mtm_launch"):
+    for unit in ("mtm_mfma_plain", "mtm_mfma_rows", "mtm_mfma_rm", "mtm_mfma_ext", "mtm_mfma_kp", "mtm_bf16", "mtm_api", "mtm_peaks", "mtm_launch", "mtm_stats"):
         assert unit + "-hip-amdgcn-amd-amdhsa-gfx950.s" in names, unit
     assert not hits, hits[:3]
 

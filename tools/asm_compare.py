@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel comparison of two builds' device assembly (the csrc/build/*-gfx950.s listings build.py keeps).
 
-Usage: tools/asm_compare.py DIR_A DIR_B [name filter, default ncc_mfma_kernel] [--units mtm_mfma_]
+Usage: tools/asm_compare.py DIR_A DIR_B [name filter, default ncc_mfma_kernel] [--units mtm_mfma_] [--by-kernel]
 
 For every kernel whose name contains the filter, in every listing whose file name starts with the unit prefix and exists in
 both directories, one line: the six resource figures of the code object's metadata (VGPRs, SGPRs, VGPR / SGPR spills, scratch
@@ -9,6 +9,8 @@ and LDS bytes), the instruction count, and the difference of the opcode histogra
 _dpp, _sdwa) dropped.  `=` where B equals A, else `A->B`.  Exit status 1 if any kernel differs or is missing on one side.
 What a refactor of device code has to show: equivalent code, not byte-identical code - register numbers and the order of
 independent instructions are free to move, the counts are not.
+--by-kernel: kernels are paired by name across ALL listings of a directory, whichever unit holds them (a kernel that moved
+between units; the unit column then names B's).  A kernel compiled into two units of one build counts as a difference.
 """
 import collections
 import os
@@ -81,13 +83,33 @@ def main(argv):
         return 2
     da, db = args[0], args[1]
     flt = args[2] if len(args) > 2 else "ncc_mfma_kernel"
-    units = sorted(f for f in os.listdir(da) if f.startswith(prefix) and f.endswith("-gfx950.s") and os.path.exists(os.path.join(db, f)))
+    by_kernel = "--by-kernel" in argv
+    listed = lambda d: sorted(f for f in os.listdir(d) if f.startswith(prefix) and f.endswith("-gfx950.s"))
+    units = [f for f in listed(da) if os.path.exists(os.path.join(db, f))]
     n = bad = 0
     print("%-12s %-52s %s  %s  %s" % ("unit", "kernel", " ".join("%-8s" % s for s, _ in RES), "insns   ", "histogram delta (B - A)"))
-    for u in units:
-        a, b = parse_listing(os.path.join(da, u)), parse_listing(os.path.join(db, u))
-        unit = u.split("-")[0].replace("mtm_", "")
+
+    def merged(d):              # every kernel of every listing of `d`, and the unit that holds it
+        out, where, twice = {}, {}, []
+        for u in listed(d):
+            for k, v in parse_listing(os.path.join(d, u)).items():
+                if k in out:
+                    twice.append(k)
+                out[k], where[k] = v, u.split("-")[0].replace("mtm_", "").replace(".hip", "")
+        return out, where, twice
+
+    if by_kernel:
+        (a_all, _, twice_a), (b_all, where_b, twice_b) = merged(da), merged(db)
+        for k in twice_a + twice_b:
+            bad += 1
+            print("%-12s %-52s compiled into two units of %s" % ("", short_name(k), "A" if k in twice_a else "B"))
+        pairs = [("", a_all, b_all)]
+        units = listed(db)
+    else:
+        pairs = [(u.split("-")[0].replace("mtm_", ""), parse_listing(os.path.join(da, u)), parse_listing(os.path.join(db, u))) for u in units]
+    for unit0, a, b in pairs:
         for k in sorted(set(a) | set(b)):
+            unit = where_b.get(k, "-") if by_kernel else unit0
             if flt not in k:
                 continue
             n += 1

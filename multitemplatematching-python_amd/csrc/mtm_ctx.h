@@ -453,6 +453,15 @@ inline ImageDev image_dev(const mtm_ctx* c) {
 
 // ---- geometry of the operand packs (shared by the placement and the launches)
 constexpr int kMfmaMaxW = 256;          // widest template of one MFMA launch (wider: slabs)
+// sum I^2 M of a masked class in ONE launch (MfmaParams::sq_fused): the int32 accumulator holds 256 a_h + a_l,
+// a_x = sum (J_x - 128) M over the byte planes J_h, J_l of I^2, which reaches down to -(256 + 1) 128 n = -32896 n under a
+// mask of n set taps over black pixels (and up to 126 * 256 - 127 = 32129 n over saturated ones: 255^2 = 0xFE01).  That fits an int32 up to
+// n = 65280 - fewer than the 66051 taps mfma_class_ok admits, the uint16 path's kMfma16MaxArea over again
+// (tests/test_gpu_masked_cores.py ran 256 x 256 and 258 x 256 full masks over dark scenes).  Masks with more set taps
+// take the two raw launches + masksq_combine_kernel, which combines a_h and a_l in float64 (launch_masked_sumsq).
+constexpr long long kMasksqFusedMaxOnes = 65280;
+static_assert(32896 * kMasksqFusedMaxOnes <= 2147483648LL && 32896 * (kMasksqFusedMaxOnes + 1) > 2147483648LL,
+              "256 a_h + a_l of the fused sum I^2 M pass must fit an int32");
 inline long long mfma_group_bytes(int h, int w, int chans) { return (long long)chans * h * ((w + 63) / 64) * 1024; }
 // packed K: MFMA steps (1 KiB of A operand each) of `rows` stream rows of nseg 16-tap segments
 inline int kp_blocks(int rows, int nseg) { return (rows * nseg + 3) / 4; }

@@ -283,7 +283,8 @@ int launch_masked_sumsq(mtm_ctx* c, const SizeClass& sc, bool fused_stats, const
         MTMC(ensure_square_planes(c));
         const int map_pitch = (int)round_up((size_t)ow, 4);
         const long long raw_map = (long long)oh * map_pitch;
-        const bool fused_sq = c->masksq_fused != 0;
+        // (one launch only while its int32 accumulator holds 256 a_h + a_l: kMasksqFusedMaxOnes)
+        const bool fused_sq = c->masksq_fused != 0 && sc.mask_ones <= (double)kMasksqFusedMaxOnes;
         if (!fused_sq) MTMC(c->raw16.ensure(sizeof(int) * (size_t)(2 * raw_map)));
         MfmaParams p = mfma_geometry(nullptr, img, 1, h, w, oh, ow, c->method);
         const size_t lds = mfma_lds_layout(p, mfma_row_mux(p, 16, 1), kMfEpiBytesPerWave);

@@ -341,7 +341,8 @@ __global__ __launch_bounds__(256, 2) void ncc_mfma_kernel(MfmaParams p, const Te
         if constexpr (RM && METHOD == kMfRaw && !KP) {
             // sum I^2 M in ONE launch (round 4): the byte planes of I^2 are the two "channels".  The high-byte sums
             // a_h = sum (J_h - 128) M are scaled by 256 in place and the low-byte plane accumulates on top of them:
-            // 256 a_h + a_l, |.| <= 256 * 128 * w h + 128 w h < 2^31 for w h <= 65025 (the launcher's bound).
+            // 256 a_h + a_l >= -(256 + 1) 128 n under a mask of n set taps, which fits an int32 for n <= 65280
+            // (kMasksqFusedMaxOnes: launch_masked_sumsq sends larger masks through two raw launches instead).
             if (p.sq_fused && c == 1) {
 #pragma unroll
                 for (int mb = 0; mb < MB; ++mb)

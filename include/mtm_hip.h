@@ -31,7 +31,7 @@ extern "C" {
 
 /* Bumped when a declaration below changes.  Entry points added since 9 - mtm_find_matches_pyramid,
  * mtm_find_matches_boxes, mtm_track_boxes, mtm_hit_neighbourhoods, mtm_track_boxes_nbhd, mtm_track_boxes_adapt,
- * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes, mtm_match_blocks_passes_validated, mtm_debug_validate_blocks, mtm_match_blocks_second, mtm_match_blocks_passes_second, mtm_debug_second_peaks, mtm_deform_image, mtm_match_blocks_passes_deformed, mtm_debug_maskf32_screen, mtm_match_blocks_passes_steered, mtm_deform_image_q8, mtm_debug_steer_q8, mtm_debug_tail_consts - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
+ * mtm_debug_templ_stats, mtm_track_boxes_reacquire, mtm_track_boxes_sets, mtm_debug_device_nms, mtm_debug_peak_pass, mtm_debug_window_stats, mtm_match_blocks, mtm_debug_plan_blocks, mtm_match_blocks_stack, mtm_debug_plan_blocks_stack, mtm_debug_window_stats_route, mtm_match_blocks_at, mtm_match_blocks_passes, mtm_debug_plan_blocks_passes, mtm_match_blocks_passes_validated, mtm_debug_validate_blocks, mtm_match_blocks_second, mtm_match_blocks_passes_second, mtm_debug_second_peaks, mtm_deform_image, mtm_match_blocks_passes_deformed, mtm_debug_maskf32_screen, mtm_match_blocks_passes_steered, mtm_deform_image_q8, mtm_debug_steer_q8, mtm_debug_tail_consts, mtm_match_blocks_masked - are new symbols only and left it at 9: a caller built against an older 9 finds every function it knows unchanged (resolve the new ones by name). */
 #define MTM_ABI_VERSION 9
 
 /* pixel types (after the dtype policy of MTM/__init__.py:71-74: uint8 stays, all else float32) */
@@ -836,6 +836,23 @@ int mtm_match_blocks_second(mtm_ctx* ctx, const void* reference, int64_t referen
                             int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
                             const int32_t* offsets, int n_blocks, int margin, int method, mtm_hit* out, float* nbhd,
                             int exclusion, mtm_hit* second);
+
+/* mtm_match_blocks_at / mtm_match_blocks_second with a static MASK over the reference.  mask: rows x cols
+ * bytes at mask_stride_bytes per row, non-zero = the pixel takes part, for every channel.  Block k's template is its pixels
+ * of the reference with the mask's pixels under it - what mtm_find_matches_boxes returns in MTM_PEAKS_GLOBAL mode for the
+ * block set as a masked template.  With M the block's binary mask and the integers summed over all channels - tms = sum (T
+ * M)^2, per output c1 = sum I T M and c2 = sum (I M)^2 -, TM_CCORR_NORMED scores (float)(c1 / sqrt(tms c2)) in float64 with
+ * IEEE square root and division, TM_SQDIFF (float)(-2 c1 + c2 + tms): the exhaustive masked map's bits.  An output whose
+ * score is NaN (c2 == 0 or tms == 0 under TM_CCORR_NORMED) is never a peak; a block whose mask keeps no pixel is not
+ * searched; such a block, and a block all of whose outputs are NaN, gets x = y = -1 and a NaN score in out (nine NaNs in
+ * nbhd, x = y = -1 and NaN in second).  offsets may be NULL (mtm_match_blocks' boxes); exclusion < 0: no second peak
+ * (second is not read), else second is required and NaN cells are never chosen.  The mask goes up once, into a buffer of its
+ * own; a block takes 2 w h chans template bytes of the chunk budget.  MTM_E_INVALID names the argument for a NULL mask, a
+ * dtype other than MTM_U8 and a method other than TM_SQDIFF / TM_CCORR_NORMED; everything else as mtm_match_blocks_at. */
+int mtm_match_blocks_masked(mtm_ctx* ctx, const void* reference, int64_t reference_stride_bytes, const void* image,
+                            int64_t image_stride_bytes, const void* mask, int64_t mask_stride_bytes, int rows, int cols,
+                            int chans, int dtype, const mtm_block* blocks, int n_blocks, const int32_t* offsets, int margin,
+                            int method, int exclusion, mtm_hit* out, float* nbhd, mtm_hit* second);
 
 /* mtm_match_blocks_passes_validated with the second peak of every record, pass-major as out (second: required).  valid may
  * be NULL: no validation, mtm_match_blocks_passes' chain (threshold and epsilon are then not read).  The second peaks steer

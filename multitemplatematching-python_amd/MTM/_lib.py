@@ -253,6 +253,11 @@ SYMBOLS = {
                                                ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "mtm_match_blocks_masked": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                               ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p]),
     "mtm_match_blocks_passes_second": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                                       ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                       ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
@@ -1272,6 +1277,31 @@ class Context(_RecordMemo):
         check(self._lib.mtm_match_blocks_at(*pair, blocks.ctypes.data, offsets.ctypes.data, n, int(margin), int(method),
                                             out.ctypes.data, nbhd.ctypes.data if with_nbhd else None), "mtm_match_blocks_at")
         return out, nbhd
+
+    def match_blocks_masked(self, reference, image, mask, blocks, offsets, margin, method, with_nbhd=False, second=None):
+        """match_blocks_at with a static mask over the reference (mtm_match_blocks_masked): `mask` an (H, W) uint8 array,
+        non-zero = the pixel takes part, for every channel; uint8 images, methods 0 and 3.  `offsets` may be None
+        (match_blocks' boxes); `second` = the exclusion radius, or None.  Returns (records, neighbourhoods or None) and,
+        with `second`, the second peaks' records: x = y = -1 and a NaN score mean "none" - in the records, a block whose
+        mask keeps no pixel or whose map holds only NaNs."""
+        blocks = block_records(blocks)
+        n = len(blocks)
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.int32).reshape(n, 2)
+        out = np.empty(n, dtype=HIT_DTYPE)
+        nbhd = np.empty((n, 3, 3), dtype=np.float32) if with_nbhd else None
+        out2 = np.empty(n, dtype=HIT_DTYPE) if second is not None else None
+        if n:
+            pair, keep = self._pair_args(reference, image)
+            m = np.asarray(mask)
+            if m.dtype != np.uint8 or m.ndim != 2 or m.strides[1] != 1 or m.strides[0] < m.shape[1]:
+                m = np.ascontiguousarray(m, dtype=np.uint8)
+            check(self._lib.mtm_match_blocks_masked(*pair[:5], m.ctypes.data, m.strides[0], *pair[5:], blocks.ctypes.data, n,
+                                                    None if offsets is None else offsets.ctypes.data, int(margin), int(method),
+                                                    -1 if second is None else int(second), out.ctypes.data,
+                                                    nbhd.ctypes.data if with_nbhd else None,
+                                                    None if second is None else out2.ctypes.data), "mtm_match_blocks_masked")
+        return (out, nbhd) if second is None else (out, nbhd, out2)
 
     def debug_second_peaks(self, planes, mode_min, exclusion, firsts=None):
         """Test support: the module's debug_second_peaks on this context - blocks_second_kernel, launched once."""

@@ -53,6 +53,15 @@ is known.  ``steer="refined"`` steers every deformed pass by the pass before's S
 a 3 x 3 binomial kernel over the grid (``smooth_displacements``), instead of by its integer records: what makes deformation
 worth iterating on the final grid.
 
+``matchBlocks(..., mask=)`` takes a static mask over the reference - channel walls, a solid body in the flow, a reticle, a
+timestamp, a dead sensor region: an (H, W) bool or uint8 array, non-zero = the pixel takes part (mtm_match_blocks_masked,
+DESIGN 5.6.5).  Every block is then matched as the masked template ``(reference[y:y + h, x:x + w], mask[y:y + h, x:x + w])``
+- uint8 images, methods 0 and 3, the package's masked methods -, the block and its mask cut on the device; a block whose
+mask keeps no pixel, or whose map holds no number, comes back as position ``(-1, -1)`` and score NaN.  ``mask_fraction``
+gives the share of every block the mask keeps, to drop blocks that are mostly masked.  Not built: ``mask=`` in
+``matchBlocksMultipass`` and ``matchBlocksStack`` (a masked multipass can be written by hand with ``matchBlocks(mask=,
+offsets=)`` and ``predict_offsets``), masks with uint16 or float32 images, masked methods other than 0 and 3.
+
 ``matchBlocksStack`` is the movie form: the pairs of a stack of frames - each frame against the previous or against the
 first - in one native call (mtm_match_blocks_stack), every frame uploaded once; per pair the very results of
 ``matchBlocks``, or (``ensemble=True``) every block's correlation plane averaged over the pairs and its peak
@@ -67,7 +76,7 @@ from . import TM_CCOEFF_NORMED
 
 __all__ = ["matchBlocks", "matchBlocksStack", "matchBlocksMultipass", "plane_peaks", "grid", "search_box", "search_box_at",
            "predict_offsets", "displacements", "grid_shape", "validate", "second_peaks", "peak_ratio", "displacement_field",
-           "field_at", "deform", "deformImage", "to_q8", "smooth_displacements"]
+           "field_at", "deform", "deformImage", "to_q8", "smooth_displacements", "mask_fraction"]
 
 _I64 = np.dtype(np.int64)
 _U16_MAX_PIXELS = 1 << 21       # mtm_match_blocks: uint16 correlations stay below 2^53, exact in float64
@@ -601,8 +610,53 @@ def _check_offsets(offsets, b, shape):
     return np.stack((cx - b[:, 0], cy - b[:, 1]), axis=1).astype(np.int32)
 
 
+_MASK_METHODS = (0, 3)          # TM_SQDIFF and TM_CCORR_NORMED: the package's masked methods
+
+
+def _check_mask(mask, reference, method):
+    """mask -> an (H, W) uint8 array, non-zero where a pixel takes part; and what a masked call asks of the images and
+    the method."""
+    if not isinstance(mask, np.ndarray):
+        raise TypeError("mask must be a numpy array (got %s)" % type(mask).__name__)
+    if mask.dtype != np.bool_ and mask.dtype != np.uint8:
+        raise TypeError("mask must be of dtype bool or uint8 (got %s)" % mask.dtype)
+    if mask.ndim != 2:
+        raise ValueError("mask must be a 2-D (H, W) array, one value per pixel for every channel (got shape %s)" % (mask.shape,))
+    if mask.shape != reference.shape[:2]:
+        raise ValueError("mask of shape %s for a reference of %d x %d pixels" % (mask.shape, reference.shape[0],
+                                                                                reference.shape[1]))
+    if reference.dtype != np.uint8:
+        raise ValueError("matchBlocks: a mask goes with uint8 images (got %s: the package matches masked %s templates in "
+                         "float32, which block matching does not take)" % (reference.dtype, reference.dtype))
+    if method not in _MASK_METHODS:
+        raise ValueError("matchBlocks: a mask goes with methods 0 (TM_SQDIFF) and 3 (TM_CCORR_NORMED), the package's masked "
+                         "methods (got %r)" % (method,))
+    return np.ascontiguousarray(mask.view(np.uint8) if mask.dtype == np.bool_ else mask)
+
+
+def mask_fraction(mask, blocks):
+    """The share of each block's pixels that ``mask`` keeps: an (N,) float64 array, ``count_nonzero(mask[y:y + h, x:x + w])
+    / (w * h)`` for every ``(x, y, w, h)`` of ``blocks`` - from one summed-area table, in plain numpy, so that a caller can
+    drop the blocks that are mostly masked before ``matchBlocks(mask=)``.  ``mask``: an (H, W) bool or uint8 array,
+    non-zero = the pixel takes part; ``blocks``: as ``matchBlocks`` takes them, each inside the mask."""
+    if not isinstance(mask, np.ndarray):
+        raise TypeError("mask must be a numpy array (got %s)" % type(mask).__name__)
+    if mask.dtype != np.bool_ and mask.dtype != np.uint8:
+        raise TypeError("mask must be of dtype bool or uint8 (got %s)" % mask.dtype)
+    if mask.ndim != 2:
+        raise ValueError("mask must be a 2-D (H, W) array (got shape %s)" % (mask.shape,))
+    b = _check_blocks(blocks, mask)
+    if len(b) == 0:
+        return np.zeros(0, np.float64)
+    sat = np.zeros((mask.shape[0] + 1, mask.shape[1] + 1), _I64)
+    sat[1:, 1:] = (mask != 0).cumsum(axis=0, dtype=_I64).cumsum(axis=1, dtype=_I64)
+    x, y, w, h = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+    kept = sat[y + h, x + w] - sat[y, x + w] - sat[y + h, x] + sat[y, x]
+    return kept / (w * h).astype(np.float64)
+
+
 def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, method: int = TM_CCOEFF_NORMED, *,
-                refine: bool = False, context=None, offsets=None, second=None):
+                refine: bool = False, context=None, offsets=None, second=None, mask=None):
     """
     Where every block of ``reference`` is in ``image``: ``(positions, scores)``, ``positions[k]`` the int64 ``[x, y]``
     (image coordinates) and ``scores[k]`` the float32 score of the single hit of
@@ -630,12 +684,36 @@ def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, m
     ``r`` cells of its peak - gives ``(-1, -1)`` and NaN.  Computed on the device inside the same native call
     (mtm_match_blocks_second); ``positions`` and ``scores`` are those of the call without ``second``, bit for bit.
     ``peak_ratio(scores, second_scores, method)`` is the signal-to-noise PIV packages report.
+
+    ``mask``: ``None`` (the call above: the same native entry, kernels and launches) or an (H, W) array of dtype bool or
+    uint8 over the reference, non-zero = the pixel takes part, in every channel (mtm_match_blocks_masked, DESIGN 5.6.5:
+    the mask goes up once and a kernel cuts every block together with its mask).  Block k is then matched as a masked
+    template: the result is what this loop returns, positions equal and float32 score bits equal -
+
+        m = (mask[y:y + h, x:x + w] != 0).astype(np.uint8)
+        m = m if reference.ndim == 2 else np.repeat(m[:, :, None], reference.shape[2], 2)
+        hit, = findMatches([("b", reference[y:y + h, x:x + w], m)], image, method, N_object=1,
+                           searchBox=search_box(blocks[k], margin, image.shape))
+
+    - with ties to the first output in row-major order of the box's map.  Scope: uint8 images, methods 0 (TM_SQDIFF) and 3
+    (TM_CCORR_NORMED), the package's masked methods; any other method, uint16 images and a mask of another shape raise
+    ValueError, one of another dtype TypeError.  With M the block's binary mask, ``TM = T M`` and every sum taken over all
+    channels - ``tms = sum TM^2``, per output ``c1 = sum I TM`` and ``c2 = sum (I M)^2`` -, method 3 scores
+    ``float32(c1 / sqrt(tms c2))`` in float64 and method 0 ``float32(-2 c1 + c2 + tms)``.  The none rule: an output whose
+    score is NaN (``c2 == 0`` or ``tms == 0`` under method 3) is never the peak; a block whose mask has no set pixel is not
+    searched, under either method; such a block, and a block all of whose outputs are NaN, returns position ``(-1, -1)``
+    (``(-1.0, -1.0)`` with ``refine=True``) and score NaN, and its second peak is ``(-1, -1)`` / NaN.  ``mask`` composes
+    with the other keywords: ``offsets`` only moves the boxes, ``refine=True`` gives ``refineHits``' positions of the same
+    masked tuple, ``second`` uses the same maps and exclusion rule, NaN cells never chosen.  ``mask_fraction(mask,
+    blocks)`` tells how much of every block is kept.  ``matchBlocksMultipass`` and ``matchBlocksStack`` take no mask in
+    this version: a masked multipass is this call with ``offsets=predict_offsets(...)`` per pass.
     """
     _check_images(reference, image)
     _check_method(method, "matchBlocks")
     _check_margin(margin)
     _check_flag(refine, "refine")
     r = _check_second(second)
+    mk = None if mask is None else _check_mask(mask, reference, method)
     b = _check_blocks(blocks, reference)
     off = None if offsets is None else _check_offsets(offsets, b, image.shape)
     if len(b) == 0:
@@ -644,7 +722,10 @@ def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, m
     rec, m = _block_records(b), _clip_margin(margin, image.shape)
     ctx = context or _lib.default_context()     # (only now: every argument error comes before "no GPU")
     with ctx.lock:
-        if r is not None:
+        if mk is not None:
+            raw, nbhd, *got = ctx.match_blocks_masked(reference, image, mk, rec, off, m, int(method), refine, second=r)
+            raw2 = got[0] if got else None
+        elif r is not None:
             raw, nbhd, raw2 = ctx.match_blocks_at(reference, image, rec, off, m, int(method), refine, second=r)
         elif off is None:
             raw, nbhd = ctx.match_blocks(reference, image, rec, m, int(method), refine)

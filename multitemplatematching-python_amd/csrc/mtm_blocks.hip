@@ -15,6 +15,8 @@
 // pass block_pass_view (the pass's device pointers and what it does, derived once), pass_search (the units it searches,
 // or the warped image), blocks_pair, pass_records (record, deform-record, second-record, validate) and pass_handover
 // (steer-q8, smooth), in stream order; every pass has its own row of keys, records and neighbourhoods.
+// mtm_match_blocks_masked is the single-pass chain with a static mask over the reference: the mask goes up
+// once into blk_mask behind the images, and every launch of blocks_pair is the masked sibling of the unmasked kernel.
 // Every entry point composes the same host steps: check_block_entry / check_block_pair, stage_block_call (buffers, the
 // call's clock, uploads), blocks_pair (a pair's launch chain, the one place its kernels are launched), launch_lanes (the
 // one-lane-per-block launches), finish_block_call (copies back, the single wait, timing); debug entries: debug_block_run.
@@ -260,9 +262,11 @@ void plan_second_pass(const BlockPlan& P, const mtm_block* blocks, int margin, i
 // the chunk's score launch runs sub-range by sub-range with the scored-plane sink, blocks_second_kernel behind each.
 // W != nullptr (a deformed pass): the searched image is *W with its low-byte plane W_lo - the warped image in a buffer
 // of its own - instead of the stack's slot i_slot.
+// mask != nullptr (mtm_match_blocks_masked: uint8 images, keys only): the call's mask plane on the device, `cols` bytes
+// per row; every launch of the chain is then the masked sibling of the kernel named above, at the same place.
 int blocks_pair(mtm_ctx* c, const BlockPlan& P, const BlockTables& B, int rows, int chans, int dtype, int method, int r_slot,
                 int i_slot, bool gather, const BlockSink& S, const BlockSecondPass* X = nullptr, const ImageDev* W = nullptr,
-                const uint8_t* W_lo = nullptr) {
+                const uint8_t* W_lo = nullptr, const uint8_t* mask = nullptr) {
     const ImageDev st = image_dev(c);
     const uint8_t* st_lo = c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane;        // uint16: [high ^ 0x80][low ^ 0x80]
     const ImageDev ref = stack_view(st, r_slot * rows, rows), img = W ? *W : stack_view(st, i_slot * rows, rows);
@@ -280,6 +284,13 @@ int blocks_pair(mtm_ctx* c, const BlockPlan& P, const BlockTables& B, int rows, 
         for (const BlockChunk& C : P.chunks) {
             if (gather)
                 MTMC(for_launch_slices((size_t)C.b0, (size_t)C.b1, [&](size_t b0, unsigned nb) -> int {
+                    if constexpr (!U16)
+                        if (mask) {
+                            hipLaunchKernelGGL((blocks_gather_masked_kernel<CH>), dim3(nb), dim3(256), 0, c->stream, ref, mask,
+                                               ref.cols, B.blocks, (int)b0, tpx, toff, td, method);
+                            HIPC(hipGetLastError());
+                            return MTM_OK;
+                        }
                     hipLaunchKernelGGL((blocks_gather_kernel<CH, U16>), dim3(nb), dim3(256), 0, c->stream, ref, ref_lo,
                                        B.blocks, (int)b0, tpx, toff, td, method);
                     HIPC(hipGetLastError());
@@ -288,6 +299,14 @@ int blocks_pair(mtm_ctx* c, const BlockPlan& P, const BlockTables& B, int rows, 
             for (; X && xr < X->ranges.size() && X->ranges[xr].second <= C.b1; ++xr) {
                 const size_t r0 = (size_t)X->ranges[xr].first, r1 = (size_t)X->ranges[xr].second;
                 MTMC(for_launch_slices(X->tstart[r0], X->tstart[r1], [&](size_t t0, unsigned nt) -> int {
+                    if constexpr (!U16)
+                        if (mask) {
+                            hipLaunchKernelGGL((blocks_score_plane_masked_kernel<CH>), dim3(nt), dim3(256), 0, c->stream, img, tpx,
+                                               toff, td, units, B.tiles + t0, method, mode_min, S.keys, c->blk_plane.as<float>(),
+                                               X->poff);
+                            HIPC(hipGetLastError());
+                            return MTM_OK;
+                        }
                     hipLaunchKernelGGL((blocks_score_plane_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo, tpx,
                                        toff, td, units, B.tiles + t0, method, mode_min, S.keys, c->blk_plane.as<float>(), X->poff);
                     HIPC(hipGetLastError());
@@ -301,6 +320,17 @@ int blocks_pair(mtm_ctx* c, const BlockPlan& P, const BlockTables& B, int rows, 
                 }));
             }
             if (!X) MTMC(for_launch_slices(C.t0, C.t1, [&](size_t t0, unsigned nt) -> int {
+                if constexpr (!U16)
+                    if (mask) {
+                        if (B.fixed)
+                            hipLaunchKernelGGL((blocks_score_masked_kernel<CH, true>), dim3(nt), dim3(256), 0, c->stream, img, tpx,
+                                               toff, td, units, B.tiles + t0, method, mode_min, S.keys);
+                        else
+                            hipLaunchKernelGGL((blocks_score_masked_kernel<CH, false>), dim3(nt), dim3(256), 0, c->stream, img, tpx,
+                                               toff, td, units, B.tiles + t0, method, mode_min, S.keys);
+                        HIPC(hipGetLastError());
+                        return MTM_OK;
+                    }
                 if (S.side > 0)
                     hipLaunchKernelGGL((blocks_plane_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo, tpx, toff,
                                        td, units, B.tiles + t0, method, c->blk_clip.as<int32_t>(), S.side, S.first,
@@ -316,6 +346,13 @@ int blocks_pair(mtm_ctx* c, const BlockPlan& P, const BlockTables& B, int rows, 
             }));
             if (S.nbhd)
                 MTMC(for_launch_slices((size_t)C.b0, (size_t)C.b1, [&](size_t b0, unsigned nb) -> int {
+                    if constexpr (!U16)
+                        if (mask) {
+                            hipLaunchKernelGGL((blocks_nbhd_masked_kernel<CH>), dim3(nb), dim3(256), 0, c->stream, img, tpx, toff,
+                                               td, units, S.keys, (int)b0, method, S.nbhd);
+                            HIPC(hipGetLastError());
+                            return MTM_OK;
+                        }
                     hipLaunchKernelGGL((blocks_nbhd_kernel<CH, U16>), dim3(nb), dim3(256), 0, c->stream, img, img_lo, tpx, toff,
                                        td, units, S.keys, (int)b0, method, S.nbhd);
                     HIPC(hipGetLastError());
@@ -416,6 +453,9 @@ struct BlockPassCall {
     int exclusion = 0;                  //   the exclusion radius around the first peak
     int32_t* predicted = nullptr;       // deformation (never with offsets or second): the Q8 field at every block's centre;
     int steer = 0;                      //   0 - integer records steer the next pass -, 1 - refined positions, filtered
+    const void* mask = nullptr;         // mtm_match_blocks_masked (one pass, uint8): the mask over the reference, rows x cols
+    int64_t mask_stride_bytes = 0;      //   bytes, non-zero = the pixel takes part; never with deformation or validation
+    bool plan_tiles = false;            //   the pass scores over the plan's own tile table (no offsets, no second peaks)
 };
 
 // What stage_block_passes lays out on the host for the whole call: the tables of every pass, concatenated (one upload
@@ -470,7 +510,15 @@ int stage_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
         S.dtab = H.dtab.empty() ? nullptr : H.dtab.data(), S.dtab_words = H.dtab.size();
         if (Q.size() > 1) S.warp_bytes = warp_bytes(I.rows, (int)round_up((size_t)I.cols + kPadCols, 64), I.chans, I.dtype);
     }
-    return stage_block_call(c, S, [&] { return upload_block_pair(c, I); });
+    // the mask goes up once, into a buffer of its own, on the call's stream: behind the images, ahead of the gather
+    return stage_block_call(c, S, [&]() -> int {
+        MTMC(upload_block_pair(c, I));
+        if (!A.mask) return MTM_OK;
+        MTMC(c->blk_mask.ensure((size_t)I.rows * (size_t)I.cols));
+        HIPC(hipMemcpy2DAsync(c->blk_mask.p, (size_t)I.cols, A.mask, (size_t)A.mask_stride_bytes, (size_t)I.cols, (size_t)I.rows,
+                              hipMemcpyHostToDevice, c->stream));
+        return MTM_OK;
+    });
 }
 
 // One pass of the chain: its plan and the one that steers it, its rows of the call's device buffers (from the pass's first
@@ -493,7 +541,7 @@ struct BlockPass {
 BlockPass block_pass_view(mtm_ctx* c, const std::vector<BlockPassPlan>& Q, const BlockPassCall& A, BlockPassHost& H, size_t p,
                           size_t b0, size_t t0) {
     BlockPass V{Q[p], p > 0 ? &Q[p - 1] : nullptr, (int)Q[p].blocks.size(), method_mode_min(A.method) ? 1 : 0,
-                ctx_block_tables(c, b0, t0, true)};
+                ctx_block_tables(c, b0, t0, !A.plan_tiles)};
     // warped: a deformed pass p >= 1 searches the image warped by its steering records' field, over the host's units
     V.warped = A.predicted && p > 0;
     // q8: the field's nodes are Q8 ones, which the pass before left in blk_disp (pass_handover) - else whole pixels
@@ -544,7 +592,9 @@ int pass_search(mtm_ctx* c, const BlockPair& I, const BlockPass& V, ImageDev* wi
 // records (np = nx ny: plan_block_passes lays out the whole grid).
 int pass_records(mtm_ctx* c, const BlockPassCall& A, const BlockPass& V) {
     const BlockGrid& g = V.q.grid;
-    MTMC(launch_lanes(c, blocks_record_kernel, V.np, V.B.units, V.keys, V.B.blocks, V.np, V.mode_min, V.recs));
+    // (a masked call: a block may have no key - second_key_record's (-1, -1) and NaN, the rule its second peaks follow)
+    MTMC(launch_lanes(c, A.mask ? blocks_second_record_kernel : blocks_record_kernel, V.np, V.B.units, V.keys, V.B.blocks, V.np,
+                      V.mode_min, V.recs));
     if (V.warped)
         MTMC(launch_lanes(c, V.q8 ? blocks_deform_record_kernel<true> : blocks_deform_record_kernel<false>, V.np, V.B.blocks, V.np,
                           V.before->grid, c->blk_disp.as<int32_t>(), V.recs, V.pred));
@@ -576,7 +626,8 @@ int match_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
         ImageDev wimg{};
         MTMC(pass_search(c, I, V, &wimg));
         MTMC(blocks_pair(c, V.q.plan, V.B, I.rows, I.chans, I.dtype, A.method, 0, 1, true, BlockSink{V.keys, V.nbhd, 0, 0}, V.X,
-                         V.warped ? &wimg : nullptr, V.warped ? wimg.u8 + wimg.u8_plane : nullptr));
+                         V.warped ? &wimg : nullptr, V.warped ? wimg.u8 + wimg.u8_plane : nullptr,
+                         A.mask ? c->blk_mask.as<uint8_t>() : nullptr));
         MTMC(pass_records(c, A, V));
         MTMC(pass_handover(c, V));
         b0 += V.q.blocks.size();
@@ -607,9 +658,9 @@ int block_single_entry(mtm_ctx* c, const char* who, const BlockPair& I, const mt
     Q[0].grid = BlockGrid{};
     Q[0].margin = margin;
     MTMC(plan_blocks(I.rows, I.cols, I.chans, I.dtype, blocks, n_blocks, margin, 4 * (long long)c->boxes_max_floats, who, Q[0].plan,
-                     false));
+                     A.plan_tiles, A.mask != nullptr));
     if (n_blocks == 0) return MTM_OK;
-    MTMC(fix_block_tiles(Q[0].plan, I.rows, I.cols, blocks, margin, who));
+    if (!A.plan_tiles) MTMC(fix_block_tiles(Q[0].plan, I.rows, I.cols, blocks, margin, who));
     Q[0].blocks.assign(blocks, blocks + n_blocks);
     return match_block_passes(c, I, Q, A);
 }
@@ -681,6 +732,28 @@ int mtm_match_blocks_second(mtm_ctx* c, const void* reference, int64_t reference
     return block_single_entry(c, "mtm_match_blocks_second",
                               {reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype}, blocks,
                               n_blocks, margin, exclusion >= 0 && second, A);
+}
+
+int mtm_match_blocks_masked(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
+                            int64_t image_stride_bytes, const void* mask, int64_t mask_stride_bytes, int rows, int cols, int chans,
+                            int dtype, const mtm_block* blocks, int n_blocks, const int32_t* offsets, int margin, int method,
+                            int exclusion, mtm_hit* out, float* nbhd, mtm_hit* second) {
+    const char* who = "mtm_match_blocks_masked";
+    const char* bad = !mask ? "mask is NULL"
+                      : dtype != MTM_U8 ? "dtype: a masked call takes uint8 images"
+                      : method != MTM_TM_SQDIFF && method != MTM_TM_CCORR_NORMED
+                          ? "method: a masked call takes TM_SQDIFF (0) and TM_CCORR_NORMED (3)"
+                      : cols >= 1 && mask_stride_bytes < (int64_t)cols ? "mask_stride_bytes is below cols" : nullptr;
+    if (bad) {
+        set_error(std::string(who) + ": " + bad);
+        return MTM_E_INVALID;
+    }
+    BlockPassCall A{method, out, nbhd};
+    A.offsets = offsets, A.mask = mask, A.mask_stride_bytes = mask_stride_bytes;
+    if (exclusion >= 0) A.second = second, A.exclusion = exclusion;
+    A.plan_tiles = !offsets && exclusion < 0;
+    return block_single_entry(c, who, {reference, reference_stride_bytes, image, image_stride_bytes, rows, cols, chans, dtype},
+                              blocks, n_blocks, margin, exclusion < 0 || second, A);
 }
 
 int mtm_match_blocks_passes(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,

@@ -383,7 +383,7 @@ void mtm_ctx_destroy(mtm_ctx* c) {
                       &c->box_units, &c->box_tiles, &c->trk_units, &c->trk_tiles, &c->trk_keys, &c->trk_out,
                       &c->trk_nbhd, &c->trk_tpx, &c->trk_toff, &c->trk_td, &c->trk_pass, &c->trk_lost, &c->trk_sets,
                       &c->blk_tpx, &c->blk_toff, &c->blk_td, &c->blk_blocks, &c->blk_units, &c->blk_tiles, &c->blk_keys,
-                      &c->blk_nbhd, &c->blk_clip, &c->blk_acc, &c->blk_recs, &c->blk_offs, &c->blk_valid, &c->blk_steer, &c->blk_plane, &c->blk_poff, &c->blk_keys2, &c->blk_recs2, &c->blk_warp, &c->blk_disp, &c->blk_dtab, &c->blk_pred, &c->blk_d8})
+                      &c->blk_nbhd, &c->blk_clip, &c->blk_acc, &c->blk_recs, &c->blk_offs, &c->blk_valid, &c->blk_steer, &c->blk_plane, &c->blk_poff, &c->blk_keys2, &c->blk_recs2, &c->blk_warp, &c->blk_disp, &c->blk_dtab, &c->blk_pred, &c->blk_d8, &c->blk_mask})
         b->release();
     for (auto& sl : c->slot)
         for (DevBuf* b : {&sl.raw, &sl.u8, &sl.u8b, &sl.f32}) b->release();
@@ -558,7 +558,7 @@ int mtm_debug_poison(mtm_ctx* c, int pattern_byte, int what) {
                                    &c->stats_hi, &c->maps, &c->sq_planes, &c->mbf_maps, &c->f32_sq, &c->mbf_stats, &c->mbf_mu, &c->mbf_best, &c->mbf_dbg,
                                    &c->trk_units, &c->trk_keys, &c->trk_out, &c->trk_nbhd, &c->trk_tpx, &c->trk_toff, &c->trk_td,
                                    &c->trk_pass, &c->trk_lost, &c->trk_sets, &c->blk_tpx, &c->blk_toff, &c->blk_td, &c->blk_blocks, &c->blk_units,
-                                   &c->blk_tiles, &c->blk_keys, &c->blk_nbhd, &c->blk_clip, &c->blk_acc, &c->blk_recs, &c->blk_offs, &c->blk_valid, &c->blk_steer, &c->blk_plane, &c->blk_poff, &c->blk_keys2, &c->blk_recs2, &c->blk_warp, &c->blk_disp, &c->blk_dtab, &c->blk_pred, &c->blk_d8, &c->sub_pts, &c->sub_out, &c->nms_buf, &c->peak_dbg, &c->stats_dbg})
+                                   &c->blk_tiles, &c->blk_keys, &c->blk_nbhd, &c->blk_clip, &c->blk_acc, &c->blk_recs, &c->blk_offs, &c->blk_valid, &c->blk_steer, &c->blk_plane, &c->blk_poff, &c->blk_keys2, &c->blk_recs2, &c->blk_warp, &c->blk_disp, &c->blk_dtab, &c->blk_pred, &c->blk_d8, &c->blk_mask, &c->sub_pts, &c->sub_out, &c->nms_buf, &c->peak_dbg, &c->stats_dbg})
             MTMC(fill(*d));
         for (auto& ln : c->lanes)
             for (mtm_ctx::DevBuf* d : {&ln.stats, &ln.stats_rsq, &ln.stats_blk, &ln.hs1, &ln.hs2, &ln.raw16, &ln.slab_raw, &ln.stats_hi})

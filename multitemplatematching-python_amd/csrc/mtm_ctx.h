@@ -401,6 +401,9 @@ struct mtm_ctx {
     // mtm_match_blocks_passes_steered with steer = 1: the unfiltered Q8 steering displacements of the pass that steers (8 B
     // per block; the filtered ones go into blk_disp)
     DevBuf blk_d8;
+    // mtm_match_blocks_masked: the call's mask plane, rows x cols bytes, tightly packed - a buffer of its
+    // own, not a third frame of the stack
+    DevBuf blk_mask;
     // mtm_hit_neighbourhoods (mtm_subpixel.hip): the templates' operands (bytes, float64 weights, constants; made for the
     // template set sub_gen) and the per-call point table and scores.
     uint64_t sub_gen = 0;

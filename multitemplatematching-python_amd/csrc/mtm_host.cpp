@@ -619,7 +619,7 @@ int plan_tracks(const std::vector<BlobTempl>& tl, int rows, int cols, int chans,
 
 // ---- the host plan of a block-matching call (mtm_blocks.hip)
 int plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* blocks, int n_blocks, int margin,
-                long long budget_bytes, const char* who, BlockPlan& P, bool with_tiles) {
+                long long budget_bytes, const char* who, BlockPlan& P, bool with_tiles, bool masked) {
     P = BlockPlan{};
     P.units.reserve((size_t)n_blocks);
     P.toff.reserve((size_t)n_blocks);
@@ -643,7 +643,8 @@ int plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* block
         const long long y1 = std::min((long long)rows, (long long)b.y + b.h + margin);
         const long long oh = y1 - y0 - b.h + 1, ow = x1 - x0 - b.w + 1;
         if (oh * ow >= (1ll << 32)) return fail(": map of 2^32 outputs or more");
-        const size_t bytes = (size_t)area * (size_t)(dtype == MTM_U16 ? 2 : chans);
+        // (masked: the planes of T M, then as many of the mask)
+        const size_t bytes = (size_t)area * (size_t)(dtype == MTM_U16 ? 2 : chans) * (masked ? 2u : 1u);
         if (k > cur.b0 && (long long)(cur.bytes + bytes) > budget_bytes) {
             cur.b1 = k;
             cur.t1 = P.tiles.size();

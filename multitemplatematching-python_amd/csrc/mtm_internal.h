@@ -171,9 +171,10 @@ struct BlockPlan {
 // box widened by `margin` on every side and clipped to the image (MTM.blocks.search_box), its map that of a template of
 // the block's size over the box.  Chunks hold whole blocks while their template bytes - w h chans, uint16: 2 w h - stay
 // within budget_bytes.  MTM_OK, or the code and message (set_error, prefixed `who`) of the first block that is not valid.
-// with_tiles = false leaves the tile table empty, for fix_block_tiles to fill.
+// with_tiles = false leaves the tile table empty, for fix_block_tiles to fill.  masked (mtm_match_blocks_masked): a block's
+// planes are those of T M and, behind them, as many of its mask - 2 w h chans bytes.
 int plan_blocks(int rows, int cols, int chans, int dtype, const mtm_block* blocks, int n_blocks, int margin,
-                long long budget_bytes, const char* who, BlockPlan& plan, bool with_tiles = true);
+                long long budget_bytes, const char* who, BlockPlan& plan, bool with_tiles = true, bool masked = false);
 
 // ---- block matching with boxes the device computes (mtm_match_blocks_at, mtm_match_blocks_passes, mtm_blocks.hip)
 

@@ -10,6 +10,9 @@
 // reduces each plane outside the exclusion window, blocks_second_record_kernel decodes.  Window deformation (5.6.4; the
 // warp: mtm_k_deform.hip.h): blocks_deform_record_kernel adds the field at a block's centre to its record; steer = 1:
 // blocks_steer_q8_kernel and blocks_smooth_q8_kernel make the Q8 nodes the next pass's warp and record kernels read.
+// A mask over the reference (5.6.5): blocks_gather_masked_kernel cuts T M and the mask, blocks_score_masked_kernel,
+// blocks_score_plane_masked_kernel and blocks_nbhd_masked_kernel are the masked siblings over one tile body of their own
+// (blocks_tile_masked); the unmasked kernels are untouched by them.
 // The rules (mtm_blocks_*.h, mtm_quality_key.h, mtm_templ_stats.h) are the single source of host and device; one of each:
 // the tile body of the four score kernels (blocks_tile; the kernels supply the sink), the key's decoder, the record that
 // steers (blocks_steer_record_inl).  Launched by mtm_blocks.hip only.
@@ -189,6 +192,123 @@ __global__ __launch_bounds__(256) void blocks_score_plane_kernel(
     __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
     blocks_tile<CH, U16, true>(Tl, Il, img, lo_b, tpx, toff, td, units, tiles, method,
                                BlocksScoredPlaneSink{mode_min, keys, plane, poff});
+}
+
+// ---- a static mask over the reference (mtm_match_blocks_masked): uint8 images, TM_SQDIFF / TM_CCORR_NORMED
+
+// blocks_gather_kernel for a masked call.  `mask` is the call's mask plane, rows x cols bytes at `mask_pitch` bytes per
+// row, non-zero = the pixel takes part, for every channel.  Block k's planes at tpx + toff[k] are T M, [CH][h][w], then the
+// mask as bytes 0xFF / 0x00, [CH][h][w] (one copy per channel): what win_tile_sums_u8_masked and sub_nbhd_int<CH,
+// kSubU8Mask> read as tp / mk.  sum (T M)^2 over all channels and the count of set pixels are reduced in uint64 in
+// sub_reduce's fixed order (exact: < 2^49); thread 0 writes templ_stats_from_sums_inl's masked constants and the block's
+// size into td[k], and the count into td[k].map_off (a block's template has no map in the arena): 0 = the mask keeps no
+// pixel of the block, which is then not searched.  The same bounds test as blocks_gather_kernel covers the mask's reads.
+template <int CH>
+__global__ __launch_bounds__(256) void blocks_gather_masked_kernel(ImageDev ref, const uint8_t* __restrict__ mask,
+                                                                   int mask_pitch, const mtm_block* __restrict__ blocks, int k0,
+                                                                   uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
+                                                                   TemplDev* __restrict__ td, int method) {
+    __shared__ unsigned long long red[4];
+    const int k = k0 + (int)blockIdx.x;
+    const mtm_block B = blocks[k];
+    const int h = B.h, w = B.w;
+    // (the same for the whole work-group: before any barrier)
+    if (w < 1 || h < 1 || B.x < 0 || B.y < 0 || B.x > ref.cols - w || B.y > ref.rows - h) return;
+    const int tid = threadIdx.x;
+    const uint32_t n = (uint32_t)h * (uint32_t)w;           // (< 2^31: plan_blocks)
+    uint8_t* tp = tpx + toff[k];
+    uint8_t* mp = tp + (size_t)CH * n;
+    const size_t base = (size_t)B.y * ref.u8_pitch + (size_t)B.x;
+    const size_t mbase = (size_t)B.y * (size_t)mask_pitch + (size_t)B.x;
+    unsigned long long tms = 0ull, count = 0ull;
+    for (uint32_t p = (uint32_t)tid; p < n; p += 256u) {
+        const size_t py = (size_t)(p / (uint32_t)w), px = (size_t)(p % (uint32_t)w);
+        const bool m = mask[mbase + py * (size_t)mask_pitch + px] != 0;
+        count += m ? 1ull : 0ull;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const uint32_t v = m ? (uint32_t)ref.u8[(size_t)c * ref.u8_plane + base + py * ref.u8_pitch + px] : 0u;
+            tp[(size_t)c * n + p] = (uint8_t)v;
+            mp[(size_t)c * n + p] = m ? (uint8_t)0xFF : (uint8_t)0x00;
+            tms += (unsigned long long)(v * v);
+        }
+    }
+    const unsigned long long tms_all = sub_reduce(tms, red);
+    const unsigned long long count_all = sub_reduce(count, red);
+    if (tid == 0) {
+        const double none[kMaxChans] = {0.0, 0.0, 0.0, 0.0};
+        const TemplStats st = templ_stats_from_sums_inl(none, none, (double)tms_all, /*masked=*/true, h, w, CH, method);
+        TemplDev T{};
+        T.templ2_mask2_sum = st.templ2_mask2_sum;
+        T.map_off = (long long)count_all;
+        T.rows = h;
+        T.cols = w;
+        td[k] = T;
+    }
+}
+
+// blocks_tile for a masked call: the same tables and early exit, and a block whose mask keeps no pixel (td[u0].map_off ==
+// 0, blocks_gather_masked_kernel) leaves as well - the same for the whole work-group, before any barrier -, so its key
+// stays 0.  The tile is summed and scored by win_score_tile_masked with the block's T M and mask planes, and the sink gets
+// valid = in the map and not NaN in place of `inside`.
+template <int CH, bool MAY_LIE_OUTSIDE, class Sink>
+__device__ __forceinline__ void blocks_tile_masked(WinTemplLds (&Tl)[2], WinImageLds& Il, const ImageDev& img,
+                                                   const uint8_t* __restrict__ tpx, const long long* __restrict__ toff,
+                                                   const TemplDev* __restrict__ td, const TrackUnit* __restrict__ units,
+                                                   const TrackTile* __restrict__ tiles, int method, Sink&& sink) {
+    const TrackTile K = tiles[blockIdx.x];
+    const TrackUnit U = units[K.u0];
+    if constexpr (MAY_LIE_OUTSIDE)
+        if (K.ty0 >= U.oh || K.tx0 >= U.ow) return;     // (the same for the whole work-group: before any barrier)
+    const TemplDev T = td[K.u0];
+    if (T.map_off == 0) return;                         // (likewise: an empty mask)
+    const uint8_t* tp = tpx + toff[K.u0];
+    win_score_tile_masked<CH>(Tl, Il, img, tp, tp + (size_t)CH * (size_t)T.rows * (size_t)T.cols, T, U.y0 + K.ty0, U.x0 + K.tx0,
+                              K.ty0, K.tx0, U.oh, U.ow, method,
+                              [&](bool valid, int y, int x, auto&& score) { sink(K, U, valid, y, x, score); });
+}
+
+// blocks_score_kernel (FIXED = false: the plan's own tile table) and blocks_score_fixed_kernel (FIXED = true) of a masked
+// call: blocks_tile_masked with the key sink, which a NaN lane enters as a lane outside the map does.
+template <int CH, bool FIXED>
+__global__ __launch_bounds__(256) void blocks_score_masked_kernel(ImageDev img, const uint8_t* __restrict__ tpx,
+                                                                  const long long* __restrict__ toff,
+                                                                  const TemplDev* __restrict__ td,
+                                                                  const TrackUnit* __restrict__ units,
+                                                                  const TrackTile* __restrict__ tiles, int method, int mode_min,
+                                                                  unsigned long long* __restrict__ keys) {
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[2];
+    __shared__ __attribute__((aligned(16))) WinImageLds Il;
+    blocks_tile_masked<CH, FIXED>(Tl, Il, img, tpx, toff, td, units, tiles, method, BlocksKeySink{mode_min, keys});
+}
+
+// BlocksScoredPlaneSink of a masked call: every cell of the map is stored, a NaN score as NaN - second_cell_key gives such
+// a cell no key, so blocks_second_kernel never chooses it -, and only valid lanes compete for the first key.
+struct BlocksMaskedPlaneSink {
+    int mode_min;
+    unsigned long long* __restrict__ keys;
+    float* __restrict__ plane;
+    const long long* __restrict__ poff;
+    template <class Score>
+    __device__ __forceinline__ void operator()(const TrackTile& K, const TrackUnit& U, bool valid, int y, int x,
+                                               Score&& score) const {
+        const float s = score();
+        if (y < U.oh && x < U.ow) plane[(size_t)poff[K.u0] + (size_t)y * (size_t)U.ow + (size_t)x] = s;
+        win_merge_key(valid, win_pos_word(y, x, U.ow), mode_min, [&] { return s; }, keys + K.u0);
+    }
+};
+
+// blocks_score_plane_kernel of a masked call.  The plane of a block with an empty mask is not written and not read: its key
+// stays 0, and blocks_second_kernel reads no cell of a block without a key.
+template <int CH>
+__global__ __launch_bounds__(256) void blocks_score_plane_masked_kernel(
+    ImageDev img, const uint8_t* __restrict__ tpx, const long long* __restrict__ toff, const TemplDev* __restrict__ td,
+    const TrackUnit* __restrict__ units, const TrackTile* __restrict__ tiles, int method, int mode_min,
+    unsigned long long* __restrict__ keys, float* __restrict__ plane, const long long* __restrict__ poff) {
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[2];
+    __shared__ __attribute__((aligned(16))) WinImageLds Il;
+    blocks_tile_masked<CH, true>(Tl, Il, img, tpx, toff, td, units, tiles, method,
+                                 BlocksMaskedPlaneSink{mode_min, keys, plane, poff});
 }
 
 // Grid: one 256-thread work-group per block (launch slice; block k = k0 + blockIdx.x), behind the score launch that wrote
@@ -408,6 +528,36 @@ __global__ __launch_bounds__(256) void blocks_nbhd_kernel(ImageDev img, const ui
     if (key != 0ull && px >= 0 && py >= 0 && px <= img.cols - T.cols && py <= img.rows - T.rows)
         score = sub_nbhd_int<CH, kKind>(Tl, Il, red, img.u8, img.u8_plane, lo_b, img.u8_pitch, img.rows, img.cols,
                                         tpx + toff[k], nullptr, T, px, py, method);
+    if (tid < 9) out[(size_t)k * 9 + tid] = score;
+}
+
+// blocks_nbhd_kernel of a masked call: sub_nbhd_int's kSubU8Mask kind over the block's T M and mask planes
+// (blocks_gather_masked_kernel's layout) - mtm_hit_neighbourhoods' float32 bits for the block set as a masked template.
+// A block without a key - an empty mask, or a map of NaNs - gets nine NaNs and reads no pixel.
+template <int CH>
+__global__ __launch_bounds__(256) void blocks_nbhd_masked_kernel(ImageDev img, const uint8_t* __restrict__ tpx,
+                                                                 const long long* __restrict__ toff,
+                                                                 const TemplDev* __restrict__ td,
+                                                                 const TrackUnit* __restrict__ units,
+                                                                 const unsigned long long* __restrict__ keys, int k0, int method,
+                                                                 float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[2];
+    __shared__ __attribute__((aligned(16))) SubImageLds Il[1];
+    __shared__ unsigned long long red[4];
+    const int k = k0 + (int)blockIdx.x;
+    const TrackUnit U = units[k];
+    const TemplDev T = td[k];
+    const unsigned long long key = keys[k];
+    const uint32_t idx = key_index(key);
+    const int px = U.x0 + (int)(idx % (uint32_t)U.ow), py = U.y0 + (int)(idx / (uint32_t)U.ow);
+    const int tid = threadIdx.x;
+    float score = NAN;
+    // (the same for the whole work-group: before any barrier)
+    if (key != 0ull && px >= 0 && py >= 0 && px <= img.cols - T.cols && py <= img.rows - T.rows) {
+        const uint8_t* tp = tpx + toff[k];
+        score = sub_nbhd_int<CH, kSubU8Mask>(Tl, Il, red, img.u8, img.u8_plane, nullptr, img.u8_pitch, img.rows, img.cols, tp,
+                                             tp + (size_t)CH * (size_t)T.rows * (size_t)T.cols, T, px, py, method);
+    }
     if (tid < 9) out[(size_t)k * 9 + tid] = score;
 }
 

@@ -9,6 +9,7 @@
 // (mtm_boxes.hip), track_score_kernel and track_reacquire_kernel (mtm_track.hip), blocks_score_kernel and
 // blocks_plane_kernel (mtm_k_blocks.hip.h): the sums, the lane's output and whether it lies in the map, and the float32 score
 // (win_score) handed to the kernel's sink, which stores it, merges it into a key (win_merge_key) or adds it to a plane.
+// win_score_tile_masked is its sibling for a uint8 template with a binary mask (blocks_tile_masked, mtm_k_blocks.hip.h).
 // That these kernels give the same float32 bits rests on this one function.  pyr_window_kernel (mtm_pyramid.hip, uint8
 // only) calls win_tile_sums_u8 and win_score itself inside its tile loop: with win_score_tile as the loop's body its
 // 414 x 400 template case ran 6 % longer on the device (profiles/window_tile/summary.txt).
@@ -102,6 +103,49 @@ __device__ __forceinline__ void win_tile_sums_u8(WinTemplLds& Tl, WinImageLds& I
                 }
                 corr += a_corr;
                 s1[c] += a_s1;
+                s2 += a_s2;
+            }
+    }
+}
+
+// win_tile_sums_u8 for a template with a binary mask M (the same for every output): corr = sum I (T M), s2 = sum (I M)^2 over
+// all channels - the two sums finish_masked takes; there is no S1.  `tp`: the planes of T M, `mk`: the mask's planes of
+// 0xFF / 0x00 bytes, both [CH][h][w] tightly packed (sub_nbhd_int's kSubU8Mask operands).  The same chunk walk and
+// barriers; per image quad two v_dot4 streams and one AND where the unmasked body issues three streams.  A quad's bytes
+// past the chunk's last column are zero in v, in Tl and in Ml alike.
+template <int CH>
+__device__ __forceinline__ void win_tile_sums_u8_masked(WinTemplLds& Tl, WinTemplLds& Ml, WinImageLds& Il,
+                                                        const uint8_t* __restrict__ ip, long long plane, int pitch, int rows,
+                                                        int cols, const uint8_t* __restrict__ tp,
+                                                        const uint8_t* __restrict__ mk, int h, int w, int oy0, int ox0,
+                                                        unsigned long long& corr, unsigned long long& s2) {
+    const int tid = threadIdx.x, ly = tid / kWinTile, lx = tid % kWinTile;
+    corr = 0ull;
+    s2 = 0ull;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        const uint8_t* ipc = ip + c * plane;
+        const uint8_t* tc = tp + (size_t)c * h * w;
+        const uint8_t* mc = mk + (size_t)c * h * w;
+        for (int r0 = 0; r0 < h; r0 += kWinKR)
+            for (int c0 = 0; c0 < w; c0 += kWinKC) {
+                __syncthreads();            // the previous chunk's LDS reads are done
+                win_load_templ(Tl, tc, h, w, r0, c0, tid);
+                win_load_templ(Ml, mc, h, w, r0, c0, tid);
+                win_load_image(Il, ipc, pitch, rows, cols, oy0 + r0, ox0 + c0, 0u, tid);
+                __syncthreads();
+                const int ni = min(kWinKR, h - r0), nj = min(kWinKC, w - c0);
+                uint32_t a_corr = 0u, a_s2 = 0u;
+                for (int i = 0; i < ni; ++i) {
+                    const uint32_t* irow = &Il[ly + i][0];
+                    for (int j = 0; j < nj; j += 4) {
+                        const uint32_t v = win_image_quad(irow, lx, j, nj);
+                        a_corr = __builtin_amdgcn_udot4(v, Tl[i][j >> 2], a_corr, false);
+                        const uint32_t vm = v & Ml[i][j >> 2];          // I M (M binary: bytes 0xFF / 0x00)
+                        a_s2 = __builtin_amdgcn_udot4(vm, vm, a_s2, false);
+                    }
+                }
+                corr += a_corr;
                 s2 += a_s2;
             }
     }
@@ -369,6 +413,26 @@ __device__ __forceinline__ void win_score_tile(WinTemplLds (&Tl)[U16 ? 2 : 1], W
                              s2);
     const int y = ty0 + tid / kWinTile, x = tx0 + tid % kWinTile;
     sink(y < oh && x < ow, y, x, [&] { return win_score<CH>(method, T, inv_area, corr, s1, s2); });
+}
+
+// win_score_tile for a masked uint8 template (methods TM_SQDIFF and TM_CCORR_NORMED): win_tile_sums_u8_masked's sums, the
+// float32 score finish_masked gives for them with T.templ2_mask2_sum - the exhaustive masked map's bits - and
+// sink(valid, y, x, score) with valid = the lane's output lies in the map AND its score is not NaN (TM_CCORR_NORMED where
+// sum (I M)^2 or sum (T M)^2 is zero): mf_float_order ranks a positive NaN above +inf, so a NaN must never reach a key.
+// score() is the value itself, NaN for a lane outside the map.  `mk`: the mask's planes.  Called as win_score_tile is.
+template <int CH, class Sink>
+__device__ __forceinline__ void win_score_tile_masked(WinTemplLds (&Tl)[2], WinImageLds& Il, const ImageDev& img,
+                                                      const uint8_t* __restrict__ tp, const uint8_t* __restrict__ mk,
+                                                      const TemplDev& T, int py0, int px0, int ty0, int tx0, int oh, int ow,
+                                                      int method, Sink&& sink) {
+    const int tid = threadIdx.x;
+    unsigned long long corr, s2;
+    win_tile_sums_u8_masked<CH>(Tl[0], Tl[1], Il, img.u8, img.u8_plane, img.u8_pitch, img.rows, img.cols, tp, mk, T.rows, T.cols,
+                                py0, px0, corr, s2);
+    const int y = ty0 + tid / kWinTile, x = tx0 + tid % kWinTile;
+    float s = __builtin_nanf("");
+    if (y < oh && x < ow) s = finish_masked(method, (double)corr, (double)s2, T);
+    sink(s == s, y, x, [&] { return s; });
 }
 
 }  // namespace mtm

@@ -69,9 +69,27 @@ of the refined displacements against the known field over the blocks clear of th
 with ``equal_to_loop`` (steered against the loop it documents), ``steer_cost_ms`` (steered - deformed) and, on the sheared
 and the rotated pair with 2 and 3 passes and (K1's row) on the tests' particle pair, ``rms_error_px`` of all three.
 
+--mask: a static mask over the reference (the uint8 workloads K1 and K3, TM_CCORR_NORMED, pixels in 1..255 so that no
+score is NaN) - milliseconds per call of
+  masked   - matchBlocks(reference, image, grid, margin, 3, mask=mask)
+  unmasked - matchBlocks(reference, image, grid, margin, 3) on the same pair
+  loop     - what a user writes without the keyword: per block findMatches([(name, block, block's mask)], image, 3,
+             N_object=1, searchBox=search_box(block, margin, shape))
+  masked_at / unmasked_at - both calls with ``offsets=`` of zeros: the same results through the same native chain
+             (mtm_match_blocks_at's: units on the device, the fixed tile table, a record kernel), which the masked call
+             always takes a form of and the plain unmasked call does not
+interleaved in one run, with ``equal_to_loop`` (positions and score bits of masked against loop) and the device time
+between each call's events (``device_ms``: the call's table uploads and every launch of its chain - gather, score, and
+for the pass chain the unit and record kernels; the images' and the mask's uploads lie ahead of the first event and are
+not in it).  ``masked_vs_unmasked_device`` compares two different chains (the plain unmasked call decodes its keys on the
+host); ``masked_at_vs_unmasked_at_device`` compares like with like.  The score launch alone is a kernel-trace row:
+``--no-loop`` leaves the loop out so that a profiler run holds the calls' kernels only.  The mask keeps about 70 % of the
+pixels: a few discs and a band cut out, generated and seeded (``static_mask``).  The lines also go to
+profiles/blocks/mask_throughput.jsonl (``--out`` names another file).
+
 Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F]
        [--passes [--validate | --deform [--steer refined]]]
-       [--second [r]]
+       [--second [r]] [--mask [--no-loop] [--out FILE]]
 """
 import argparse
 import json
@@ -721,6 +739,93 @@ def run_second(MTM, spec, reps, warmup, radius, passes_form):
     }
 
 
+def static_mask(hw, seed=0):
+    """An (H, W) bool mask that keeps about 70 % of the pixels: a horizontal band (a channel wall) and discs (bodies in
+    the flow) cut out, the discs added from a seeded generator until 30 % are gone."""
+    H, W = hw
+    rng = np.random.default_rng(seed + 50)
+    mask = np.ones((H, W), bool)
+    mask[int(0.46 * H):int(0.54 * H), :] = False
+    yy, xx = np.mgrid[0:H, 0:W]
+    while mask.mean() > 0.70:
+        r = int(rng.integers(min(H, W) // 16, min(H, W) // 6))
+        cy, cx = int(rng.integers(0, H)), int(rng.integers(0, W))
+        mask[(yy - cy) ** 2 + (xx - cx) ** 2 <= r * r] = False
+    return mask
+
+
+def run_mask(MTM, spec, reps, warmup, with_loop=True):
+    """--mask: the masked call, the unmasked call on the same pair, both again through the offsets chain, and the by-hand
+    loop through findMatches, interleaved."""
+    from MTM import _lib
+    from MTM import blocks as B
+    name, hw, chans, dtype, side, margin = spec
+    ref, img = (np.maximum(a, 1) for a in workload(spec))
+    grid = B.grid(ref.shape, side)
+    method = MTM.TM_CCORR_NORMED
+    mask = static_mask(hw)
+    kept = B.mask_fraction(mask, grid)
+    grid = grid[kept > 0]           # (the loop has no answer for a block the mask removes entirely)
+    ctx = _lib.default_context()
+
+    def loop():
+        pos, sc = [], []
+        for x, y, w, h in grid.tolist():
+            m = mask[y:y + h, x:x + w].astype(np.uint8)
+            m = m if chans == 1 else np.repeat(m[:, :, None], chans, 2)
+            hit, = MTM.findMatches([("b", ref[y:y + h, x:x + w], m)], img, method, N_object=1,
+                                   searchBox=B.search_box((x, y, w, h), margin, img.shape))
+            pos.append(hit[1][:2])
+            sc.append(hit[2])
+        return np.array(pos, dtype=np.int64), np.array(sc, dtype=np.float32)
+
+    zeros = np.zeros((len(grid), 2), np.int32)
+    methods = {
+        "masked": lambda: MTM.matchBlocks(ref, img, grid, margin, method, mask=mask),
+        "unmasked": lambda: MTM.matchBlocks(ref, img, grid, margin, method),
+        "masked_at": lambda: MTM.matchBlocks(ref, img, grid, margin, method, mask=mask, offsets=zeros),
+        "unmasked_at": lambda: MTM.matchBlocks(ref, img, grid, margin, method, offsets=zeros),
+    }
+    if with_loop:
+        methods["loop"] = loop
+    results = {}
+    for k, fn in methods.items():
+        for _ in range(warmup if k != "loop" else 1):
+            results[k] = fn()
+    ms = {k: [] for k in methods}
+    dev = {k: [] for k in methods if k != "loop"}
+    for _ in range(reps):
+        for k, fn in methods.items():
+            t0 = time.perf_counter()
+            fn()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+            if k in dev:
+                dev[k].append(ctx.timing()["total_ms"])
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    dmed = {k: statistics.median(v) for k, v in dev.items()}
+    (pos, sc), (lpos, lsc) = results["masked"], results.get("loop", (None, None))
+    same = lambda a, b: bool((a[0] == b[0]).all() and a[1].tobytes() == b[1].tobytes())     # noqa: E731
+    d = B.displacements(grid, pos)
+    return {
+        "workload": name, "image": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype), "blocks": int(len(grid)), "block": side,
+        "margin": margin, "method": int(method), "mask_kept": round(float(mask.mean()), 4),
+        "blocks_dropped_empty": int((kept == 0).sum()), "blocks_partly_masked": int(((kept > 0) & (kept < 1)).sum()),
+        "ms": {k: round(v, 3) for k, v in med.items()},
+        "ms_min": {k: round(min(v), 3) for k, v in ms.items()},
+        "ms_max": {k: round(max(v), 3) for k, v in ms.items()},
+        "device_ms": {k: round(v, 4) for k, v in dmed.items()},
+        "device_ms_all": {k: [round(x, 4) for x in v] for k, v in dev.items()},
+        "masked_vs_unmasked_device": round(dmed["masked"] / dmed["unmasked"], 3),
+        "masked_at_vs_unmasked_at_device": round(dmed["masked_at"] / dmed["unmasked_at"], 3),
+        "masked_vs_unmasked": round(med["masked"] / med["unmasked"], 3),
+        "speedup_vs_loop": round(med["loop"] / med["masked"], 2) if with_loop else None,
+        "equal_to_loop": same((pos, sc), (lpos, lsc)) if with_loop else None,
+        "at_equal": same(results["masked_at"], results["masked"]) and same(results["unmasked_at"], results["unmasked"]),
+        "found_shift": float(np.mean((d == (3, -2)).all(axis=1))),
+        "reps": reps,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--reps", type=int, default=5)
@@ -734,7 +839,13 @@ def main():
     ap.add_argument("--deform", action="store_true", help="with --passes: window deformation between the passes")
     ap.add_argument("--steer", choices=["integer", "refined"], default="integer",
                     help="with --passes --deform: refined = the deformed passes steered by sub-pixel positions, three passes")
+    ap.add_argument("--mask", action="store_true", help="a static mask over the reference: masked, unmasked and the loop (K1, K3)")
+    ap.add_argument("--no-loop", action="store_true", help="with --mask: leave the by-hand loop out (profiler runs)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "blocks", "mask_throughput.jsonl"),
+                    help="with --mask: the file the lines are written to")
     args = ap.parse_args()
+    if args.mask and (args.passes or args.stack or args.second is not None):
+        ap.error("--mask goes alone")
     if args.steer == "refined" and not args.deform:
         ap.error("--steer refined goes with --passes --deform")
     if args.validate and not args.passes:
@@ -746,10 +857,15 @@ def main():
     import build as mtm_build
     mtm_build.build()
     import MTM
+    lines = []
     for spec in WORKLOADS:
         if args.only and spec[0] != args.only:
             continue
-        if args.second is not None:
+        if args.mask:
+            if spec[3] == "uint8":
+                lines.append(json.dumps(run_mask(MTM, spec, args.reps, args.warmup, not args.no_loop)))
+                print(lines[-1], flush=True)
+        elif args.second is not None:
             print(json.dumps(run_second(MTM, spec, args.reps, args.warmup, args.second, args.passes)), flush=True)
         elif args.passes and args.deform and args.steer == "refined":
             print(json.dumps(run_passes_steer(MTM, spec, args.reps, args.warmup)), flush=True)
@@ -767,6 +883,9 @@ def main():
             print(json.dumps(run_stack(MTM, spec, args.stack, args.reps, args.warmup)), flush=True)
         else:
             print(json.dumps(run(MTM, spec, args.reps, args.warmup)), flush=True)
+    if args.mask and lines and not args.no_loop:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":

@@ -750,6 +750,21 @@ int mtm_debug_plan_blocks_stack(int n_frames, int frames_per_chunk, int mode, in
                                 int64_t* n_chunks, int rows, int cols, int chans, int dtype, const mtm_block* blocks,
                                 int n_blocks, int margin, int32_t* clip);
 
+/* mtm_match_blocks_stack with a predicted displacement per block, shared by every pair: block k is searched
+ * in the box mtm_match_blocks_at gives it for offsets[2 k], offsets[2 k + 1].  Frames, mode, checks and the context's state
+ * afterwards as mtm_match_blocks_stack's; the boxes and the fixed tile table as mtm_match_blocks_at's.
+ * Per-pair results (planes == NULL): out_hits[p n_blocks + k] = mtm_match_blocks_at's out[k] of pair p, bit for bit; nbhd
+ * likewise.
+ * Ensemble planes (planes != NULL; nbhd is ignored): with (cx, cy) the block's moved and clamped position, planes[(k S +
+ * margin + dy) S + margin + dx] = the mean over the pairs of block k's score at position (cx + dx, cy + dy), in
+ * mtm_match_blocks_stack's arithmetic, NaN where the clipped box has no such output.  The means and the NaN fill are
+ * computed on the device (blocks_plane_peak_kernel) and the planes come back as float32; out_hits, if not NULL, gets one
+ * record per block: the plane's peak - the largest mean that is not NaN, the smallest for TM_SQDIFF(_NORMED), -0 equal to
+ * +0, the first cell in row-major order on ties - at (cx + dx, cy + dy) with the plane's own float32. */
+int mtm_match_blocks_stack_at(mtm_ctx* ctx, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                              int64_t row_stride_bytes, const mtm_block* blocks, const int32_t* offsets, int n_blocks,
+                              int margin, int method, int mode, mtm_hit* out_hits, float* nbhd, float* planes);
+
 /* mtm_match_blocks with a predicted displacement per block: offsets[2 k], offsets[2 k + 1] = (dx, dy) of
  * block k.  The block's position is moved by its offset and clamped so that the block still lies inside the image - cx =
  * min(max(x + dx, 0), cols - w), cy likewise -, and the search box is the box of the moved block widened by `margin` and
@@ -870,6 +885,29 @@ int mtm_match_blocks_passes_second(mtm_ctx* ctx, const void* reference, int64_t 
  * them.  n >= 1, oh, ow >= 1, oh * ow < 2^32, mode_min 0 or 1, exclusion >= 0. */
 int mtm_debug_second_peaks(mtm_ctx* ctx, const float* planes, int n, const int32_t* oh, const int32_t* ow,
                            const int32_t* firsts, int mode_min, int exclusion, mtm_hit* out);
+
+/* mtm_match_blocks_passes over the pairs of a frame stack in one call.  passes as mtm_match_blocks_passes
+ * takes them, frames and mode as mtm_match_blocks_stack; n_frames >= 2.  With n = the blocks of all passes:
+ * Per-pair results (planes == NULL): out_hits[p n + j] = mtm_match_blocks_passes' out[j] for pair p, bit for bit, nbhd
+ * likewise - every pair runs its own chain of passes on the device, all passes of the pairs of a frame chunk ahead of the
+ * next upload, every frame uploaded once (plus a chunk's carried frame).
+ * Ensemble (planes != NULL; nbhd is ignored): pass 0 sums mtm_match_blocks_stack's planes over its grid; their peaks (as
+ * mtm_match_blocks_stack_at records them) steer pass 1 as a pass's records steer the next in mtm_match_blocks_passes, and
+ * so on.  planes: every pass's N_p (2 margin_p + 1)^2 floats, pass after pass; out_hits (may be NULL): the n peak records.
+ * All planes together above MTM_OPT_BOXES_MAX_FLOATS return MTM_E_INVALID.  A pass needs every pair: a stack that fits one
+ * frame chunk goes up once, any other once per pass.  One host wait per call. */
+int mtm_match_blocks_stack_passes(mtm_ctx* ctx, const void* const* frames, int n_frames, int rows, int cols, int chans,
+                                  int dtype, int64_t row_stride_bytes, const mtm_block_pass* passes, int n_passes, int method,
+                                  int mode, mtm_hit* out_hits, float* nbhd, float* planes);
+
+/* Test support: blocks_plane_peak_kernel on constructed sums (ctx == NULL: the same rule on the host).  acc: n planes of
+ * side x side float64 sums (side odd); block k's clipped box covers cells oy <= cy < oy + oh[k], ox <= cx < ox + ow[k],
+ * (ox, oy) = clip[2 k], clip[2 k + 1].  planes_out: n side^2 floats, (float)(acc / pairs) inside the box and NaN outside;
+ * recs_out[k]: the peak as mtm_match_blocks_stack_at records it for a block centred on (0, 0) - x = dx, y = dy, w = h = 0 -,
+ * (-1, -1) and NaN for a plane without a number. */
+int mtm_debug_plane_peaks(mtm_ctx* ctx, const double* acc, int n, int side, const int32_t* clip, const int32_t* oh,
+                          const int32_t* ow, int pairs, int method, float* planes_out, mtm_hit* recs_out);
+
 
 /* Window deformation.  THE RULE, in integers.  A coarse grid of nx x ny blocks of size (wc, hc) at stride (sx,
  * sy), row-major, carries displacements d[j nx + i] = (dx, dy).  Coordinates are doubled: pixel x is X2 = 2 x, the centre of a

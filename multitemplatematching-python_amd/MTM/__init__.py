@@ -26,7 +26,7 @@ pinned_empty = _lib.pinned_empty        # numpy arrays in page-locked memory (fa
 
 __all__ = ["NMS", "Hit", "matchTemplates", "findMatches", "computeScoreMap", "TemplateMatcher", "matchTemplatesBatch",
            "findMatchesPyramid", "matchTemplatesPyramid", "findMatchesInBoxes", "matchTemplatesInBoxes", "trackTemplates",
-           "hitNeighbourhoods", "refineHits", "matchBlocks", "matchBlocksStack", "matchBlocksMultipass",
+           "hitNeighbourhoods", "refineHits", "matchBlocks", "matchBlocksStack", "matchBlocksMultipass", "matchBlocksStackMultipass",
            "deformImage", "pinned_empty", "drawBoxesOnRGB",
            "drawBoxesOnGray", "TM_SQDIFF", "TM_SQDIFF_NORMED", "TM_CCORR", "TM_CCORR_NORMED",
            "TM_CCOEFF", "TM_CCOEFF_NORMED", "__version__"]
@@ -718,5 +718,5 @@ from .pyramid import findMatchesPyramid, matchTemplatesPyramid  # noqa: E402  (c
 from .boxes import findMatchesInBoxes, matchTemplatesInBoxes  # noqa: E402  (many searchBoxes in one call)
 from .tracking import trackTemplates  # noqa: E402  (templates tracked through a stack of frames)
 from .subpixel import hitNeighbourhoods, refineHits  # noqa: E402  (sub-pixel positions from score neighbourhoods)
-from .blocks import matchBlocks, matchBlocksStack, matchBlocksMultipass  # noqa: E402  (block matching between two images, over a frame stack, coarse to fine)
+from .blocks import matchBlocks, matchBlocksStack, matchBlocksMultipass, matchBlocksStackMultipass  # noqa: E402  (block matching between two images, over a frame stack, coarse to fine)
 from .blocks import deformImage  # noqa: E402  (an image warped by a measured displacement field, on the device)

@@ -228,6 +228,17 @@ SYMBOLS = {
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p]),
+    "mtm_match_blocks_stack_at": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    "mtm_match_blocks_stack_passes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                                                     ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p]),
+    "mtm_debug_plane_peaks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
     "mtm_debug_plan_blocks_stack": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                                    _P(ctypes.c_int64), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
@@ -719,6 +730,27 @@ def debug_steer_q8(positions, nbhd, predicted, grid_shape, step, mode_min, smoot
                                  None if flags is None else flags.ctypes.data, None if steer is None else steer.ctypes.data,
                                  nx, ny, sx, sy, int(mode_min), int(bool(smooth)), out.ctypes.data), "mtm_debug_steer_q8")
     return out
+
+
+def debug_plane_peaks(acc, clip, oh, ow, pairs, method, context=None):
+    """Test support (mtm_debug_plane_peaks): the means and peaks of constructed planes of sums.  `acc`: an (N, side, side)
+    float64 array; block k's clipped box covers the cells oy <= cy < oy + oh[k], ox <= cx < ox + ow[k], (ox, oy) = clip[k].
+    Returns (planes (N, side, side) float32 - (float)(acc / pairs) inside the box, NaN outside -, records: x = dx, y = dy
+    of the peak, (-1, -1) and NaN for a plane without a number).  `context` None: the same rule on the host, no GPU."""
+    a = np.ascontiguousarray(acc, dtype=np.float64)
+    if a.ndim != 3 or a.shape[1] != a.shape[2]:
+        raise ValueError("debug_plane_peaks: acc must be (N, side, side)")
+    n, side = a.shape[0], a.shape[1]
+    clip = np.ascontiguousarray(clip, dtype=np.int32).reshape(n, 2)
+    oh = np.ascontiguousarray(oh, dtype=np.int32).reshape(n)
+    ow = np.ascontiguousarray(ow, dtype=np.int32).reshape(n)
+    planes = np.empty((n, side, side), dtype=np.float32)
+    recs = np.zeros(n, dtype=HIT_DTYPE)
+    lib = load() if context is None else context._lib
+    check(lib.mtm_debug_plane_peaks(None if context is None else context._h, a.ctypes.data, n, side, clip.ctypes.data,
+                                    oh.ctypes.data, ow.ctypes.data, int(pairs), int(method), planes.ctypes.data,
+                                    recs.ctypes.data), "mtm_debug_plane_peaks")
+    return planes, recs
 
 
 def debug_second_peaks(planes, mode_min, exclusion, firsts=None, context=None):
@@ -1396,6 +1428,73 @@ class Context(_RecordMemo):
         check(self._lib.mtm_match_blocks_stack(*args, out.ctypes.data, nbhd.ctypes.data if with_nbhd else None, None),
               "mtm_match_blocks_stack")
         return out, nbhd
+
+    def _frames_args(self, frames):
+        """(args, keep): the eight leading arguments of the mtm_match_blocks_stack_at / _passes entry points - the context,
+        the frames' pointers, their number, the shape, pixel kind and row stride they share - and what the pointers point
+        into, for the caller to hold until its call returns."""
+        rows = [_pixel_rows(a) for a in frames]
+        if len({r[2] for r in rows}) > 1:       # (one row stride for every frame)
+            rows = [_pixel_rows(np.ascontiguousarray(a)) for a in frames]
+        a0, _, stride = rows[0]
+        chans = 1 if a0.ndim == 2 else a0.shape[2]
+        ptrs = (ctypes.c_void_p * len(rows))(*[r[1] for r in rows])
+        return (self._h, ptrs, len(rows), a0.shape[0], a0.shape[1], chans, _dtype_code(a0), stride), (rows, ptrs)
+
+    def match_blocks_stack_at(self, frames, blocks, offsets, margin, method, mode, with_nbhd=False, planes=False):
+        """match_blocks_stack with a displacement per block, shared by the pairs (mtm_match_blocks_stack_at): `offsets` an
+        (N, 2) int32 array of (dx, dy), block k's box that of match_blocks_at.  Returns (records, neighbourhoods or None) as
+        match_blocks_stack does or, `planes`, (the (N, 2 margin + 1, 2 margin + 1) float32 planes of means around every
+        block's moved position, the N records of their peaks) - both computed on the device."""
+        blocks = block_records(blocks)
+        n, npairs, side = len(blocks), len(frames) - 1, 2 * int(margin) + 1
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32).reshape(n, 2)
+        if planes:
+            if npairs < 1:
+                raise ValueError("match_blocks_stack_at: planes need at least two frames")
+            out, recs = np.empty((n, side, side), dtype=np.float32), np.empty(n, dtype=HIT_DTYPE)
+            if n == 0:
+                return out, recs
+        else:
+            out = np.empty(max(npairs, 0) * n, dtype=HIT_DTYPE)
+            nbhd = np.empty((len(out), 3, 3), dtype=np.float32) if with_nbhd else None
+            if len(out) == 0:
+                return out, nbhd
+        head, keep = self._frames_args(frames)
+        args = head + (blocks.ctypes.data, offsets.ctypes.data, n, int(margin), int(method), int(mode))
+        if planes:
+            check(self._lib.mtm_match_blocks_stack_at(*args, recs.ctypes.data, None, out.ctypes.data), "mtm_match_blocks_stack_at")
+            return out, recs
+        check(self._lib.mtm_match_blocks_stack_at(*args, out.ctypes.data, nbhd.ctypes.data if with_nbhd else None, None),
+              "mtm_match_blocks_stack_at")
+        return out, nbhd
+
+    def match_blocks_stack_passes(self, frames, passes, counts, method, mode, with_nbhd=False, planes=False):
+        """match_blocks_passes over the pairs of a frame stack in one native call (mtm_match_blocks_stack_passes): `passes`
+        BLOCK_PASS_DTYPE records, `counts` the blocks of every pass's grid.  Returns (records, pair-major and pass-major
+        within a pair: (len(frames) - 1) * sum(counts); neighbourhoods in the same order, or None) or, `planes`, (a flat
+        float32 array of every pass's planes of means, pass after pass - counts[p] * (2 margin_p + 1)^2 floats each -, the
+        sum(counts) records of their peaks, pass-major)."""
+        passes = block_pass_records(passes)
+        n, npairs = int(sum(counts)), len(frames) - 1
+        if npairs < 1:
+            raise ValueError("match_blocks_stack_passes: needs at least two frames")
+        head, keep = self._frames_args(frames)
+        args = head + (passes.ctypes.data, len(passes), int(method), int(mode))
+        name = "mtm_match_blocks_stack_passes"
+        if planes:
+            out = np.empty(int(sum(int(k) * (2 * int(a["margin"]) + 1) ** 2 for k, a in zip(counts, passes))), dtype=np.float32)
+            recs = np.empty(n, dtype=HIT_DTYPE)
+            check(self._lib.mtm_match_blocks_stack_passes(*args, recs.ctypes.data, None, out.ctypes.data), name)
+            return out, recs
+        out = np.empty(npairs * n, dtype=HIT_DTYPE)
+        nbhd = np.empty((len(out), 3, 3), dtype=np.float32) if with_nbhd else None
+        check(self._lib.mtm_match_blocks_stack_passes(*args, out.ctypes.data, nbhd.ctypes.data if with_nbhd else None, None), name)
+        return out, nbhd
+
+    def debug_plane_peaks(self, acc, clip, oh, ow, pairs, method):
+        """Test support: the module's debug_plane_peaks on this context - blocks_plane_peak_kernel, launched once."""
+        return debug_plane_peaks(acc, clip, oh, ow, pairs, method, context=self)
 
     def hit_neighbourhoods(self, image, points):
         """The 3 x 3 score neighbourhoods of `points` (POINT_DTYPE records: a template of the current set and a window of

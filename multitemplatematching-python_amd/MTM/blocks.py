@@ -65,7 +65,11 @@ offsets=)`` and ``predict_offsets``), masks with uint16 or float32 images, maske
 ``matchBlocksStack`` is the movie form: the pairs of a stack of frames - each frame against the previous or against the
 first - in one native call (mtm_match_blocks_stack), every frame uploaded once; per pair the very results of
 ``matchBlocks``, or (``ensemble=True``) every block's correlation plane averaged over the pairs and its peak
-(``plane_peaks``): ensemble correlation, for movies whose single pairs are too noisy to peak.
+(``plane_peaks``): ensemble correlation, for movies whose single pairs are too noisy to peak.  ``offsets=`` centres every
+block's box on a predicted displacement shared by the pairs (mtm_match_blocks_stack_at), the planes then lying around the
+moved blocks (``moved_blocks``), and ``matchBlocksStackMultipass`` is the coarse-to-fine scheme over a movie
+(mtm_match_blocks_stack_passes): per pair the passes of ``matchBlocksMultipass``, or - ``ensemble=True`` -
+passes whose ensemble peaks steer the next, what micro-PIV runs on movies whose single pairs are too noisy to peak.
 """
 import numbers
 
@@ -74,7 +78,7 @@ import numpy as np
 from . import _lib, subpixel
 from . import TM_CCOEFF_NORMED
 
-__all__ = ["matchBlocks", "matchBlocksStack", "matchBlocksMultipass", "plane_peaks", "grid", "search_box", "search_box_at",
+__all__ = ["matchBlocks", "matchBlocksStack", "matchBlocksMultipass", "matchBlocksStackMultipass", "moved_blocks", "plane_peaks", "grid", "search_box", "search_box_at",
            "predict_offsets", "displacements", "grid_shape", "validate", "second_peaks", "peak_ratio", "displacement_field",
            "field_at", "deform", "deformImage", "to_q8", "smooth_displacements", "mask_fraction"]
 
@@ -108,6 +112,17 @@ def search_box_at(block, offset, margin, shape):
     H, W = int(shape[0]), int(shape[1])
     cx, cy = min(max(x + dx, 0), W - w), min(max(y + dy, 0), H - h)
     return search_box((cx, cy, w, h), margin, shape)
+
+
+def moved_blocks(blocks, offsets, shape):
+    """Where ``offsets`` move ``blocks`` in an image of shape ``shape``: an (N, 4) int64 array of ``(cx, cy, w, h)``, the
+    position of every block moved by its ``(dx, dy)`` and clamped so that the block still lies inside the image, ``cx =
+    min(max(x + dx, 0), W - w)`` and ``cy`` likewise - the block ``search_box_at`` widens, and the block the planes of
+    ``matchBlocksStack(ensemble=True, offsets=)`` lie around.  ``blocks`` and ``offsets`` as ``matchBlocks`` takes them."""
+    b = _check_blocks(blocks, np.empty((int(shape[0]), int(shape[1])), np.uint8))
+    out = b.copy()
+    out[:, :2] += _check_offsets(offsets, b, shape)
+    return out
 
 
 def _pair(v, what, who="grid"):
@@ -735,6 +750,35 @@ def matchBlocks(reference: np.ndarray, image: np.ndarray, blocks, margin: int, m
     return res if r is None else res + _second_arrays(raw2)
 
 
+def _check_passes(passes, image):
+    """passes -> (the list, its BLOCK_PASS_DTYPE records for images shaped and typed as ``image``, every pass's grid)."""
+    try:
+        pl = list(passes)
+    except TypeError:
+        raise TypeError("passes must be a sequence of (block, step, margin) (got %s)" % type(passes).__name__) from None
+    if not pl:
+        raise ValueError("passes is empty")
+    rec = np.empty(len(pl), dtype=_lib.BLOCK_PASS_DTYPE)
+    grids = []
+    for p, item in enumerate(pl):
+        who = "passes[%d]" % p
+        try:
+            block, step, margin = item
+        except (TypeError, ValueError):
+            raise ValueError("%s must be (block, step, margin) (got %r)" % (who, item)) from None
+        w, h, sx, sy, nx, ny = _grid_axes(image.shape, block, step, who)
+        _check_margin(margin, who + ": ")
+        if nx * ny == 0:
+            raise ValueError("%s: no %d x %d block fits the %d x %d images (empty grid)" % (
+                who, w, h, image.shape[0], image.shape[1]))
+        if image.dtype == np.uint16 and w * h > _U16_MAX_PIXELS:
+            raise ValueError("%s: uint16 blocks of more than 2^21 pixels are not supported (their exact correlations would "
+                             "pass 2^53)" % who)
+        rec[p] = (w, h, sx, sy, _clip_margin(margin, image.shape))
+        grids.append(grid(image.shape, block, step))
+    return pl, rec, grids
+
+
 def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, method: int = TM_CCOEFF_NORMED, *,
                          refine: bool = False, context=None, validate=None, second=None, deform: bool = False,
                          steer: str = "integer"):
@@ -847,30 +891,7 @@ def matchBlocksMultipass(reference: np.ndarray, image: np.ndarray, passes, metho
             if isinstance(validate, (bool, np.bool_, str)) or not hasattr(validate, "__len__") or len(validate) != 2:
                 raise ValueError("validate must be None, True or (threshold, epsilon) (got %r)" % (validate,))
             validate = _check_validate_params(validate[0], validate[1], "validate")
-    try:
-        pl = list(passes)
-    except TypeError:
-        raise TypeError("passes must be a sequence of (block, step, margin) (got %s)" % type(passes).__name__) from None
-    if not pl:
-        raise ValueError("passes is empty")
-    rec = np.empty(len(pl), dtype=_lib.BLOCK_PASS_DTYPE)
-    grids = []
-    for p, item in enumerate(pl):
-        who = "passes[%d]" % p
-        try:
-            block, step, margin = item
-        except (TypeError, ValueError):
-            raise ValueError("%s must be (block, step, margin) (got %r)" % (who, item)) from None
-        w, h, sx, sy, nx, ny = _grid_axes(image.shape, block, step, who)
-        _check_margin(margin, who + ": ")
-        if nx * ny == 0:
-            raise ValueError("%s: no %d x %d block fits the %d x %d images (empty grid)" % (
-                who, w, h, image.shape[0], image.shape[1]))
-        if reference.dtype == np.uint16 and w * h > _U16_MAX_PIXELS:
-            raise ValueError("%s: uint16 blocks of more than 2^21 pixels are not supported (their exact correlations would "
-                             "pass 2^53)" % who)
-        rec[p] = (w, h, sx, sy, _clip_margin(margin, image.shape))
-        grids.append(grid(image.shape, block, step))
+    pl, rec, grids = _check_passes(passes, image)
     counts = [len(g) for g in grids]
     if deform and len(pl) * max(image.shape[0], image.shape[1]) > _DEFORM_MAX:
         raise ValueError("matchBlocksMultipass: deform=True takes len(passes) * max(H, W) of at most 2^22 (got %d passes "
@@ -1069,7 +1090,7 @@ def peak_ratio(scores, second_scores, method):
 
 
 def matchBlocksStack(frames, blocks, margin: int, method: int = TM_CCOEFF_NORMED, *, reference: str = "previous",
-                     refine: bool = False, ensemble: bool = False, context=None):
+                     refine: bool = False, ensemble: bool = False, context=None, offsets=None):
     """
     ``matchBlocks`` over a stack of F frames in one native call.  ``frames``: a sequence of F arrays of one shape and dtype
     or one array with a leading frame axis.  Pair p (0 .. F - 2) searches ``frames[p + 1]``; its reference is ``frames[p]``
@@ -1084,6 +1105,15 @@ def matchBlocksStack(frames, blocks, margin: int, method: int = TM_CCOEFF_NORMED
     by their number -, NaN where the block's clipped search box has no such displacement.  ``positions`` (N, 2) and
     ``scores`` (N,) are ``plane_peaks(planes, blocks, method, refine)``.  Needs two frames at least, and planes of at
     most OPT_BOXES_MAX_FLOATS cells in all.
+
+    ``offsets``: ``None`` (the call above: the same native entry with the same arguments) or an (N, 2) integer array of
+    predicted displacements ``(dx, dy)``, shared by every pair and checked as ``matchBlocks``' (mtm_match_blocks_stack_at):
+    block k of every pair is searched in ``search_box_at(blocks[k], offsets[k], margin, shape)``.  ``ensemble=False``:
+    ``positions[p], scores[p]`` are exactly ``matchBlocks(ref_p, frames[p + 1], blocks, margin, method, refine=refine,
+    offsets=offsets)``.  ``ensemble=True``: with ``moved = moved_blocks(blocks, offsets, shape)``, ``planes[k, m + dy, m +
+    dx]`` is the mean over the pairs - the arithmetic above - of block k's score at position ``(moved[k, 0] + dx, moved[k,
+    1] + dy)``, NaN where the clipped box has no such output, and ``positions, scores`` are ``plane_peaks(planes, moved,
+    method, refine)``; the means and the NaN fill are computed on the device.  Zero offsets give the call without them.
     """
     fl = _check_frames(frames)
     _check_method(method, "matchBlocksStack")
@@ -1093,6 +1123,7 @@ def matchBlocksStack(frames, blocks, margin: int, method: int = TM_CCOEFF_NORMED
     _check_flag(refine, "refine")
     _check_flag(ensemble, "ensemble")
     b = _check_blocks(blocks, fl[0])
+    off = None if offsets is None else _check_offsets(offsets, b, fl[0].shape)
     n, pairs = len(b), len(fl) - 1
     if ensemble and pairs < 1:
         raise ValueError("ensemble=True needs two frames at least: there is no pair to average")
@@ -1112,10 +1143,94 @@ def matchBlocksStack(frames, blocks, margin: int, method: int = TM_CCOEFF_NORMED
             if n * side * side > budget:
                 raise ValueError("ensemble=True: the planes of %d blocks at margin %d hold %d floats, more than the "
                                  "context's OPT_BOXES_MAX_FLOATS = %d" % (n, m, n * side * side, budget))
-            planes = ctx.match_blocks_stack(fl, rec, m, int(method), mode, planes=True)
-        else:
+            if off is None:
+                planes = ctx.match_blocks_stack(fl, rec, m, int(method), mode, planes=True)
+            else:
+                planes, _ = ctx.match_blocks_stack_at(fl, rec, off, m, int(method), mode, planes=True)
+        elif off is None:
             raw, nbhd = ctx.match_blocks_stack(fl, rec, m, int(method), mode, with_nbhd=refine)
+        else:
+            raw, nbhd = ctx.match_blocks_stack_at(fl, rec, off, m, int(method), mode, with_nbhd=refine)
     if ensemble:
-        positions, scores = plane_peaks(planes, b, int(method), refine)
+        moved = b if off is None else b + np.concatenate((off.astype(_I64), np.zeros((n, 2), _I64)), axis=1)
+        positions, scores = plane_peaks(planes, moved, int(method), refine)
         return positions, scores, planes
     return _positions_scores(raw, nbhd, method, refine, (pairs, n))     # (one fit over every pair and block)
+
+
+def matchBlocksStackMultipass(frames, passes, method: int = TM_CCOEFF_NORMED, *, reference: str = "previous",
+                              refine: bool = False, ensemble: bool = False, context=None):
+    """
+    Coarse-to-fine block matching over a stack of F frames in one native call with one host wait
+    (mtm_match_blocks_stack_passes).  ``frames`` and ``reference`` as ``matchBlocksStack`` takes them,
+    ``passes`` as ``matchBlocksMultipass`` does.  Returns a list with one tuple per pass.
+
+    ``ensemble=False``: every pass gives ``(blocks_p, positions_p (F - 1, N_p, 2), scores_p (F - 1, N_p))``, slice ``[q]``
+    being pass p of ``matchBlocksMultipass(ref_q, frames[q + 1], passes, method, refine=refine)``, bit for bit.  Every pair
+    runs its own chain of passes on the device - records, the next pass's boxes, the next pass -, every frame goes up
+    once, in ``matchBlocksStack``'s frame chunks, and all passes of a chunk's pairs run before the next upload.  One frame
+    gives arrays with a leading 0.
+
+    ``ensemble=True``: every pass gives ``(blocks_p, positions_p (N_p, 2), scores_p (N_p,), planes_p (N_p, 2 m_p + 1, 2 m_p
+    + 1))``: the passes run on ensemble planes, each centred on what the ensemble peak of the pass before found - the
+    integer peak steers, never the refined one.  The call equals, bit for bit, the loop
+
+        steer = None
+        for p, (block, step, margin) in enumerate(passes):
+            b = grid(shape, block, step)
+            off = None if p == 0 else predict_offsets(shape, passes[p - 1][:2], steer, passes[p][:2])
+            steer, _, _ = matchBlocksStack(frames, b, margin, method, reference=reference, ensemble=True, offsets=off)
+            pos, sc, planes = matchBlocksStack(frames, b, margin, method, reference=reference, ensemble=True, offsets=off,
+                                               refine=refine)
+
+    Every pass needs every pair: a stack that fits one frame chunk (OPT_BATCH_MAX_ROWS) goes up once, any other once per
+    pass.  Needs two frames at least; the planes of all passes together hold at most OPT_BOXES_MAX_FLOATS floats
+    (ValueError before any native call otherwise).
+
+    Not in this version: ``validate``, ``second``, ``deform``, ``steer`` and ``mask``.  Scope and checks as the two
+    functions'; the templates set on the context are left alone.
+    """
+    fl = _check_frames(frames)
+    _check_method(method, "matchBlocksStackMultipass")
+    if not isinstance(reference, str) or reference not in _REFERENCE_MODES:
+        raise ValueError('reference must be "previous" or "first" (got %r)' % (reference,))
+    _check_flag(refine, "refine")
+    _check_flag(ensemble, "ensemble")
+    pl, rec, grids = _check_passes(passes, fl[0])
+    pairs, shape = len(fl) - 1, fl[0].shape
+    if ensemble and pairs < 1:
+        raise ValueError("ensemble=True needs two frames at least: there is no pair to average")
+    counts = [len(g) for g in grids]
+    sides = [2 * int(a["margin"]) + 1 for a in rec]
+    ptype = np.float64 if refine else _I64
+    if pairs == 0:
+        return [(g, np.zeros((0, len(g), 2), dtype=ptype), np.zeros((0, len(g)), dtype=np.float32)) for g in grids]
+    ctx = context or _lib.default_context()     # (only now: every argument error above comes before "no GPU")
+    mode = _REFERENCE_MODES[reference]
+    with ctx.lock:
+        if ensemble:
+            budget, cells = int(ctx.get_option(_lib.OPT_BOXES_MAX_FLOATS)), sum(k * sd * sd for k, sd in zip(counts, sides))
+            if cells > budget:
+                raise ValueError("ensemble=True: the planes of %d passes hold %d floats, more than the context's "
+                                 "OPT_BOXES_MAX_FLOATS = %d" % (len(pl), cells, budget))
+            flat, raw = ctx.match_blocks_stack_passes(fl, rec, counts, int(method), mode, planes=True)
+        else:
+            raw, nbhd = ctx.match_blocks_stack_passes(fl, rec, counts, int(method), mode, with_nbhd=refine)
+    out, at = [], 0
+    if not ensemble:
+        positions, scores = _positions_scores(raw, nbhd, method, refine, (pairs, sum(counts)))    # (one fit over everything)
+        for g in grids:
+            out.append((g, positions[:, at:at + len(g)], scores[:, at:at + len(g)]))
+            at += len(g)
+        return out
+    steer, cell = None, 0
+    for p, g in enumerate(grids):
+        planes = flat[cell:cell + len(g) * sides[p] ** 2].reshape(len(g), sides[p], sides[p])
+        # the blocks the pass's planes lie around: the grid moved by what the peaks of the pass before predict
+        moved = g if p == 0 else moved_blocks(g, predict_offsets(shape, pl[p - 1][:2], steer, pl[p][:2]), shape)
+        steer, scores = _positions_scores(raw[at:at + len(g)], None, method, False)         # (the device's peak records)
+        positions = plane_peaks(planes, moved, int(method), True)[0] if refine else steer
+        out.append((g, positions, scores, planes))
+        at += len(g)
+        cell += len(g) * sides[p] ** 2
+    return out

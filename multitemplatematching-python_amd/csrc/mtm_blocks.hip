@@ -17,6 +17,9 @@
 // (steer-q8, smooth), in stream order; every pass has its own row of keys, records and neighbourhoods.
 // mtm_match_blocks_masked is the single-pass chain with a static mask over the reference: the mask goes up
 // once into blk_mask behind the images, and every launch of blocks_pair is the masked sibling of the unmasked kernel.
+// mtm_match_blocks_stack_at / mtm_match_blocks_stack_passes run the pass chain for the pairs of a frame stack
+// (match_block_stack_passes): the same tables, views and launches, every pair with a row of keys, records and
+// neighbourhoods of its own - or, ensemble planes, pass after pass over all pairs, the planes' peaks steering the next.
 // Every entry point composes the same host steps: check_block_entry / check_block_pair, stage_block_call (buffers, the
 // call's clock, uploads), blocks_pair (a pair's launch chain, the one place its kernels are launched), launch_lanes (the
 // one-lane-per-block launches), finish_block_call (copies back, the single wait, timing); debug entries: debug_block_run.
@@ -112,7 +115,7 @@ int stage_block_call(mtm_ctx* c, const BlockStage& S, Before&& before) {
     const struct { DevBuf& buf; size_t bytes; } sized[] = {
         {c->blk_tpx, S.max_bytes},                          {c->blk_td, sizeof(TemplDev) * n},
         {c->blk_acc, sizeof(double) * S.cells},             {c->blk_keys, sizeof(unsigned long long) * n_keys},
-        {c->blk_recs, S.recs ? sizeof(mtm_hit) * n : 0},    {c->blk_nbhd, S.nbhd ? sizeof(float) * 9 * n_keys : 0},
+        {c->blk_recs, S.recs ? sizeof(mtm_hit) * (S.cells ? n : S.key_rows * n) : 0},    {c->blk_nbhd, S.nbhd ? sizeof(float) * 9 * n_keys : 0},
         {c->blk_valid, S.validate ? n : 0},                 {c->blk_steer, S.validate ? sizeof(mtm_hit) * n : 0},
         {c->blk_plane, sizeof(float) * S.plane_floats},     {c->blk_keys2, S.poff ? sizeof(unsigned long long) * n : 0},
         {c->blk_recs2, S.poff ? sizeof(mtm_hit) * n : 0},   {c->blk_warp, S.warp_bytes},
@@ -194,6 +197,9 @@ struct BlockSink {
     unsigned long long* keys;
     float* nbhd;
     int side, first;
+    // planes over the fixed tile table (units a kernel computed): the pass's planes of sums and its clip offsets, device
+    double* acc = nullptr;
+    const int32_t* clip = nullptr;
 };
 
 // The device tables a chain reads, indexed as its plan indexes them: the call's buffers from their start, or - one pass
@@ -331,7 +337,10 @@ int blocks_pair(mtm_ctx* c, const BlockPlan& P, const BlockTables& B, int rows, 
                         HIPC(hipGetLastError());
                         return MTM_OK;
                     }
-                if (S.side > 0)
+                if (S.side > 0 && B.fixed)
+                    hipLaunchKernelGGL((blocks_plane_fixed_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo, tpx,
+                                       toff, td, units, B.tiles + t0, method, S.clip, S.side, S.first, S.acc);
+                else if (S.side > 0)
                     hipLaunchKernelGGL((blocks_plane_kernel<CH, U16>), dim3(nt), dim3(256), 0, c->stream, img, img_lo, tpx, toff,
                                        td, units, B.tiles + t0, method, c->blk_clip.as<int32_t>(), S.side, S.first,
                                        c->blk_acc.as<double>());
@@ -471,10 +480,11 @@ struct BlockPassHost {
     std::vector<size_t> dtab_at;
 };
 
-// Stage the call: H, the buffers they and the asked-for results need, both images up once, then the call's clock and the
-// tables (stage_block_call).  steer = 1 with a pass to steer: the neighbourhoods exist whether or not the caller asked.
-int stage_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPassPlan>& Q, const BlockPassCall& A,
-                       BlockPassHost& H) {
+// Stage the call: H and what the buffers they and the asked-for results need (pass_stage: the host side, shared with the
+// stack form), both images up once, then the call's clock and the tables (stage_block_call).  steer = 1 with a pass to
+// steer: the neighbourhoods exist whether or not the caller asked.
+BlockStage pass_stage(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPassPlan>& Q, const BlockPassCall& A,
+                      BlockPassHost& H) {
     size_t max_bytes = 0;
     for (const BlockPassPlan& q : Q) {
         H.blocks.insert(H.blocks.end(), q.blocks.begin(), q.blocks.end());
@@ -510,6 +520,11 @@ int stage_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPa
         S.dtab = H.dtab.empty() ? nullptr : H.dtab.data(), S.dtab_words = H.dtab.size();
         if (Q.size() > 1) S.warp_bytes = warp_bytes(I.rows, (int)round_up((size_t)I.cols + kPadCols, 64), I.chans, I.dtype);
     }
+    return S;
+}
+int stage_block_passes(mtm_ctx* c, const BlockPair& I, const std::vector<BlockPassPlan>& Q, const BlockPassCall& A,
+                       BlockPassHost& H) {
+    const BlockStage S = pass_stage(c, I, Q, A, H);
     // the mask goes up once, into a buffer of its own, on the call's stream: behind the images, ahead of the gather
     return stage_block_call(c, S, [&]() -> int {
         MTMC(upload_block_pair(c, I));
@@ -533,13 +548,16 @@ struct BlockPass {
     float* nbhd;
     uint8_t* valid;
     int32_t* pred;
+    int32_t* clip;                      // the pass's clip offsets (a call that sums planes; else unused)
     const BlockSecondPass* X;           // (with poff and keys2)
     const mtm_hit* prev;                // the records of `before` that steer this pass: validated or raw
     size_t dtab;                        // the pass's deform tables start at this word of blk_dtab
     bool warped, q8, steers, moved;
 };
+// row: the first key, record and neighbourhood of the pair the pass runs for (the stack form: every pair has a row of the
+// call's blocks; else 0) - the tables and units are the call's, shared by the pairs.
 BlockPass block_pass_view(mtm_ctx* c, const std::vector<BlockPassPlan>& Q, const BlockPassCall& A, BlockPassHost& H, size_t p,
-                          size_t b0, size_t t0) {
+                          size_t b0, size_t t0, size_t row = 0) {
     BlockPass V{Q[p], p > 0 ? &Q[p - 1] : nullptr, (int)Q[p].blocks.size(), method_mode_min(A.method) ? 1 : 0,
                 ctx_block_tables(c, b0, t0, !A.plan_tiles)};
     // warped: a deformed pass p >= 1 searches the image warped by its steering records' field, over the host's units
@@ -550,9 +568,10 @@ BlockPass block_pass_view(mtm_ctx* c, const std::vector<BlockPassPlan>& Q, const
     V.steers = V.q8 && p + 1 < Q.size();
     // moved: blocks_unit_kernel moves the boxes - by the previous pass's records or pass 0's offsets; else the host's units
     V.moved = !V.warped && (p > 0 || A.offsets);
-    V.keys = c->blk_keys.as<unsigned long long>() + b0;
-    V.recs = c->blk_recs.as<mtm_hit>() + b0;
-    V.nbhd = A.nbhd || V.steers ? c->blk_nbhd.as<float>() + 9 * b0 : nullptr;
+    V.keys = c->blk_keys.as<unsigned long long>() + row + b0;
+    V.recs = c->blk_recs.as<mtm_hit>() + row + b0;
+    V.nbhd = A.nbhd || V.steers ? c->blk_nbhd.as<float>() + 9 * (row + b0) : nullptr;
+    V.clip = c->blk_clip.p ? c->blk_clip.as<int32_t>() + 2 * b0 : nullptr;
     V.valid = A.valid ? c->blk_valid.as<uint8_t>() + b0 : nullptr;
     V.steer = A.valid ? c->blk_steer.as<mtm_hit>() + b0 : nullptr;
     V.pred = A.predicted ? c->blk_pred.as<int32_t>() + 2 * b0 : nullptr;
@@ -570,7 +589,8 @@ BlockPass block_pass_view(mtm_ctx* c, const std::vector<BlockPassPlan>& Q, const
 // What the pass searches, ahead of its chain.  Warped: the steering records become compact displacements
 // (deform_disp_kernel; q8: the nodes are already there) and the ORIGINAL image - the stack's slot 1 - is warped by their
 // field into blk_warp, *wimg.  Moved: blocks_unit_kernel's units.  Else nothing: the host's units.
-int pass_search(mtm_ctx* c, const BlockPair& I, const BlockPass& V, ImageDev* wimg) {
+// clip != nullptr (a call that sums planes): blocks_unit_clip_kernel, which writes the units' clip offsets there as well.
+int pass_search(mtm_ctx* c, const BlockPair& I, const BlockPass& V, ImageDev* wimg, int32_t* clip = nullptr) {
     if (V.warped) {
         const BlockGrid& g = V.before->grid;
         if (!V.q8) MTMC(launch_lanes(c, deform_disp_kernel, V.before->blocks.size(), V.prev, g, c->blk_disp.as<int32_t>()));
@@ -579,6 +599,9 @@ int pass_search(mtm_ctx* c, const BlockPair& I, const BlockPass& V, ImageDev* wi
                            c->slot[c->cur].u8b.as<uint8_t>() + st.u8_plane + (size_t)I.rows * st.u8_pitch, I.chans, I.dtype, g,
                            V.dtab, V.q8));
         *wimg = warp_view(c, I.rows, I.cols, I.chans);
+    } else if (V.moved && clip) {
+        return launch_lanes(c, blocks_unit_clip_kernel, V.np, V.B.blocks, V.np, V.before ? nullptr : c->blk_offs.as<int32_t>(),
+                            V.prev, V.before ? V.before->grid : BlockGrid{}, V.q.margin, I.rows, I.cols, V.B.units, clip);
     } else if (V.moved) {
         return launch_lanes(c, blocks_unit_kernel, V.np, V.B.blocks, V.np, V.before ? nullptr : c->blk_offs.as<int32_t>(), V.prev,
                             V.before ? V.before->grid : BlockGrid{}, V.q.margin, I.rows, I.cols, V.B.units);
@@ -709,9 +732,230 @@ int debug_block_run(mtm_ctx* c, const char* who, std::initializer_list<DebugBuf>
     return MTM_OK;
 }
 
+// ---- the pass chain over a frame stack (mtm_match_blocks_stack_at, mtm_match_blocks_stack_passes)
+
+// The frames of a stack entry point, of one shape, pixel kind and row stride.
+struct BlockFrames {
+    const void* const* frames;
+    int n_frames, rows, cols, chans, dtype;
+    int64_t row_stride_bytes;
+};
+
+// What both stack-pass entries check behind their own arguments: the frames, and what blocks ask of them.
+int check_block_frames(mtm_ctx* c, const char* who, bool args_ok, int method, int mode, const BlockFrames& F) {
+    MTMC(check_block_entry(c, who,
+                           args_ok && F.n_frames >= 0 && (F.n_frames == 0 || F.frames) &&
+                               (mode == MTM_BLOCKS_REF_PREVIOUS || mode == MTM_BLOCKS_REF_FIRST),
+                           method));
+    for (int f = 0; f < F.n_frames; ++f)
+        MTMC(check_image_args(F.frames[f], F.rows, F.cols, F.chans, F.dtype, F.row_stride_bytes, who));
+    return check_block_images(who, "frames", F.rows, F.chans, F.dtype);
+}
+
+// The planes of the passes Q hold cells[p + 1] - cells[p] floats each, side_p = 2 margin_p + 1; all of them together stay
+// within MTM_OPT_BOXES_MAX_FLOATS, else MTM_E_INVALID naming both numbers.
+int plan_pass_planes(mtm_ctx* c, const char* who, const std::vector<BlockPassPlan>& Q, std::vector<size_t>& cells) {
+    unsigned __int128 total = 0;
+    cells.assign(1, 0);
+    bool wide = false;
+    for (const BlockPassPlan& q : Q) {
+        const unsigned __int128 side = 2 * (unsigned __int128)q.margin + 1;
+        wide = wide || side > (unsigned __int128)INT_MAX;
+        total += (unsigned __int128)q.blocks.size() * side * side;
+        cells.push_back((size_t)total);
+    }
+    if (wide || total > (unsigned __int128)c->boxes_max_floats) {
+        const std::string cells_s = total >> 63 ? std::string("2^63 or more") : std::to_string((long long)total);
+        set_error(std::string(who) + ": the planes of " + std::to_string(Q.size()) + " pass(es) hold " + cells_s +
+                  " floats, more than MTM_OPT_BOXES_MAX_FLOATS = " + std::to_string((long long)c->boxes_max_floats));
+        return MTM_E_INVALID;
+    }
+    return MTM_OK;
+}
+
+// match_block_passes over the pairs of a frame stack: the same host tables (pass_stage), views (block_pass_view) and
+// launches (pass_search, blocks_pair, pass_records), the frames going up in mtm_match_blocks_stack's chunks
+// (plan_blocks_stack) - one host wait.  A.out: the records; A.offsets: pass 0 follows an uploaded displacement.
+// Per pair (planes == nullptr): pair r has row r of the call's keys, records and neighbourhoods - n = the blocks of all
+// passes, pass-major within the row -, and for every pair of a frame chunk all passes run, each steered by the pair's own
+// records of the pass before, ahead of the next upload.  A.out: (n_frames - 1) n records, A.nbhd likewise.
+// Ensemble (planes != nullptr): pass after pass - every pair adds to the pass's planes of sums (blocks_plane_fixed_kernel
+// at the clip offsets the host planned, pass 0 without offsets, or blocks_unit_clip_kernel computed), then
+// blocks_plane_peak_kernel makes the means and the records that steer the next pass.  A pass needs every pair: a stack
+// that fits one frame chunk goes up once, any other once per pass.  planes: every pass's, pass-major; A.out: n records.
+int match_block_stack_passes(mtm_ctx* c, const BlockFrames& F, const std::vector<BlockPassPlan>& Q, const BlockPassCall& A, int mode,
+                             float* planes, const std::vector<size_t>& cells) {
+    const BlockPair I{nullptr, 0, nullptr, 0, F.rows, F.cols, F.chans, F.dtype};
+    const size_t np = (size_t)F.n_frames - 1;
+    const bool ens = planes != nullptr;
+    BlockPassHost H;
+    BlockStage S = pass_stage(c, I, Q, A, H);
+    const size_t n = S.n;
+    std::vector<int32_t> clip;
+    if (ens) {
+        for (const BlockPassPlan& q : Q) clip.insert(clip.end(), q.plan.clip.begin(), q.plan.clip.end());
+        S.cells = S.plane_floats = cells.back();
+        S.clip = clip.data();
+        S.nbhd = false;
+    } else {
+        S.key_rows = np;
+    }
+    // the call's clock starts ahead of the uploads: the frames go up chunk by chunk between the pairs' chains
+    MTMC(stage_block_call(c, S, [] { return MTM_OK; }));
+
+    const std::vector<StackChunk> chunks = plan_blocks_stack(F.n_frames, track_chunk_frames(c, F.rows, F.cols, F.chans), mode);
+    std::vector<const void*> px;
+    auto upload = [&](const StackChunk& K) -> int {
+        px.assign(1, F.frames[K.carried]);
+        px.insert(px.end(), F.frames + K.f0, F.frames + K.f0 + K.nf);
+        adopt_image(c, (K.nf + 1) * F.rows, F.cols, F.chans, F.dtype);
+        return upload_image_stack(c, c->slot[c->cur], px.data(), K.nf + 1, F.row_stride_bytes, F.rows, F.cols, F.chans, F.dtype,
+                                  c->stream);
+    };
+    auto r_slot = [&](int i) { return mode == MTM_BLOCKS_REF_FIRST ? 0 : i; };
+    // one pass, one block chunk, mode "first": the gathered templates outlive the pairs of a frame chunk
+    const bool gather_once = mode == MTM_BLOCKS_REF_FIRST && Q.size() == 1 && Q[0].plan.chunks.size() == 1;
+    ImageDev none{};
+    if (!ens) {
+        for (const StackChunk& K : chunks) {
+            MTMC(upload(K));
+            for (int i = 0; i < K.nf; ++i) {
+                const size_t pair = (size_t)(K.p0 + i);
+                size_t b0 = 0, t0 = 0;
+                for (size_t p = 0; p < Q.size(); ++p) {
+                    const BlockPass V = block_pass_view(c, Q, A, H, p, b0, t0, pair * n);
+                    // (uploaded offsets move pass 0's boxes alike for every pair: once)
+                    if (p > 0 || pair == 0) MTMC(pass_search(c, I, V, &none));
+                    MTMC(blocks_pair(c, V.q.plan, V.B, F.rows, F.chans, F.dtype, A.method, r_slot(i), i + 1,
+                                     !(gather_once && i > 0), BlockSink{V.keys, V.nbhd, 0, 0}));
+                    MTMC(pass_records(c, A, V));
+                    b0 += V.q.blocks.size();
+                    t0 += V.q.plan.tiles.size();
+                }
+            }
+        }
+        return finish_block_call(c, {{A.out, c->blk_recs.p, sizeof(mtm_hit) * np * n},
+                                     {A.nbhd, c->blk_nbhd.p, sizeof(float) * 9 * np * n}}, np * n);
+    }
+    const bool resident = chunks.size() == 1;
+    if (resident) MTMC(upload(chunks[0]));
+    size_t b0 = 0, t0 = 0;
+    for (size_t p = 0; p < Q.size(); ++p) {
+        const BlockPass V = block_pass_view(c, Q, A, H, p, b0, t0);
+        const int side = 2 * V.q.margin + 1;
+        double* acc = c->blk_acc.as<double>() + cells[p];
+        MTMC(pass_search(c, I, V, &none, V.clip));
+        for (const StackChunk& K : chunks) {
+            if (!resident) MTMC(upload(K));
+            for (int i = 0; i < K.nf; ++i)
+                MTMC(blocks_pair(c, V.q.plan, V.B, F.rows, F.chans, F.dtype, A.method, r_slot(i), i + 1, !(gather_once && i > 0),
+                                 BlockSink{nullptr, nullptr, side, K.p0 + i == 0 ? 1 : 0, acc, V.clip}));
+        }
+        MTMC(for_launch_slices(0, (size_t)V.np, [&](size_t k0, unsigned nk) -> int {
+            hipLaunchKernelGGL(blocks_plane_peak_kernel, dim3(nk), dim3(256), 0, c->stream, acc, V.B.units, V.clip, V.B.blocks,
+                               (int)k0, side, (double)np, V.mode_min, c->blk_plane.as<float>() + cells[p], V.recs);
+            HIPC(hipGetLastError());
+            return MTM_OK;
+        }));
+        b0 += V.q.blocks.size();
+        t0 += V.q.plan.tiles.size();
+    }
+    return finish_block_call(c, {{planes, c->blk_plane.p, sizeof(float) * cells.back()}, {A.out, c->blk_recs.p, sizeof(mtm_hit) * n}},
+                             n);
+}
+
 }  // namespace
 
 extern "C" {
+
+int mtm_match_blocks_stack_at(mtm_ctx* c, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                              int64_t row_stride_bytes, const mtm_block* blocks, const int32_t* offsets, int n_blocks, int margin,
+                              int method, int mode, mtm_hit* out_hits, float* nbhd, float* planes) {
+    const char* who = "mtm_match_blocks_stack_at";
+    const BlockFrames F{frames, n_frames, rows, cols, chans, dtype, row_stride_bytes};
+    MTMC(check_block_frames(c, who,
+                            n_blocks >= 0 && margin >= 0 &&
+                                (n_blocks == 0 || (blocks && offsets && n_frames >= 2 && (out_hits || planes))),
+                            method, mode, F));
+    std::vector<BlockPassPlan> Q(1);
+    Q[0].grid = BlockGrid{};
+    Q[0].margin = margin;
+    MTMC(plan_blocks(rows, cols, chans, dtype, blocks, n_blocks, margin, 4 * (long long)c->boxes_max_floats, who, Q[0].plan, false));
+    if (n_blocks == 0) return MTM_OK;
+    MTMC(fix_block_tiles(Q[0].plan, rows, cols, blocks, margin, who));
+    Q[0].blocks.assign(blocks, blocks + n_blocks);
+    std::vector<size_t> cells;
+    if (planes) MTMC(plan_pass_planes(c, who, Q, cells));
+    BlockPassCall A{method, out_hits, planes ? nullptr : nbhd};
+    A.offsets = offsets;
+    return match_block_stack_passes(c, F, Q, A, mode, planes, cells);
+}
+
+int mtm_match_blocks_stack_passes(mtm_ctx* c, const void* const* frames, int n_frames, int rows, int cols, int chans, int dtype,
+                                  int64_t row_stride_bytes, const mtm_block_pass* passes, int n_passes, int method, int mode,
+                                  mtm_hit* out_hits, float* nbhd, float* planes) {
+    const char* who = "mtm_match_blocks_stack_passes";
+    const BlockFrames F{frames, n_frames, rows, cols, chans, dtype, row_stride_bytes};
+    MTMC(check_block_frames(c, who, n_passes >= 1 && passes && n_frames >= 2 && (out_hits || planes), method, mode, F));
+    std::vector<BlockPassPlan> Q;
+    MTMC(plan_block_passes(rows, cols, chans, dtype, passes, n_passes, 4 * (long long)c->boxes_max_floats, who, Q));
+    std::vector<size_t> cells;
+    if (planes) MTMC(plan_pass_planes(c, who, Q, cells));
+    return match_block_stack_passes(c, F, Q, BlockPassCall{method, out_hits, planes ? nullptr : nbhd}, mode, planes, cells);
+}
+
+int mtm_debug_plane_peaks(mtm_ctx* c, const double* acc, int n, int side, const int32_t* clip, const int32_t* oh,
+                          const int32_t* ow, int pairs, int method, float* planes_out, mtm_hit* recs_out) {
+    const char* who = "mtm_debug_plane_peaks";
+    bool ok = acc && clip && oh && ow && planes_out && recs_out && n >= 1 && side >= 1 && side % 2 == 1 && pairs >= 1 &&
+              method >= MTM_TM_SQDIFF && method <= MTM_TM_CCOEFF_NORMED && (long long)side * side * n <= INT_MAX;
+    for (int k = 0; ok && k < n; ++k)
+        ok = oh[k] >= 0 && ow[k] >= 0 && oh[k] <= side && ow[k] <= side && clip[2 * k] >= 0 && clip[2 * k + 1] >= 0 &&
+             clip[2 * k] <= side && clip[2 * k + 1] <= side;
+    if (!ok) {
+        set_error(std::string(who) + ": bad arguments");
+        return MTM_E_INVALID;
+    }
+    const int mode_min = method_mode_min(method) ? 1 : 0, m = side / 2;
+    const size_t nn = (size_t)n, cells = (size_t)side * (size_t)side;
+    // block k: a unit whose plane is centred on displacement (0, 0) - the records carry (dx, dy)
+    std::vector<TrackUnit> units(nn);
+    for (int k = 0; k < n; ++k) units[(size_t)k] = TrackUnit{k, clip[2 * k + 1] - m, clip[2 * k] - m, oh[k], ow[k]};
+    if (!c) {           // the rule itself, on the host
+        for (size_t k = 0; k < nn; ++k) {
+            const TrackUnit& U = units[k];
+            const int ox = clip[2 * k], oy = clip[2 * k + 1];
+            unsigned long long best = 0ull;
+            for (size_t idx = 0; idx < cells; ++idx) {
+                const int y = (int)(idx / (size_t)side) - oy, x = (int)(idx % (size_t)side) - ox;
+                const bool in = y >= 0 && y < U.oh && x >= 0 && x < U.ow;
+                const float v = in ? (float)(acc[k * cells + idx] / (double)pairs) : NAN;
+                planes_out[k * cells + idx] = v;
+                const unsigned long long key = second_cell_key(v, mode_min, (uint32_t)idx);
+                best = key > best ? key : best;
+            }
+            recs_out[k] = best ? key_record(key_index(best), planes_out[k * cells + key_index(best)], (int)k, U.y0 - oy, U.x0 - ox,
+                                            side, 0, 0)
+                               : second_key_record(0ull, mode_min, (int)k, 0, 0, side, 0, 0);
+        }
+        return MTM_OK;
+    }
+    const std::vector<mtm_block> blocks(nn, mtm_block{0, 0, 0, 0});
+    return debug_block_run(
+        c, who,
+        {{c->blk_acc, sizeof(double) * nn * cells, acc, nullptr}, {c->blk_clip, sizeof(int32_t) * 2 * nn, clip, nullptr},
+         {c->blk_units, sizeof(TrackUnit) * nn, units.data(), nullptr}, {c->blk_blocks, sizeof(mtm_block) * nn, blocks.data(), nullptr},
+         {c->blk_plane, sizeof(float) * nn * cells, nullptr, planes_out}, {c->blk_recs, sizeof(mtm_hit) * nn, nullptr, recs_out}},
+        [&]() -> int {
+            return for_launch_slices(0, nn, [&](size_t k0, unsigned nk) -> int {
+                hipLaunchKernelGGL(blocks_plane_peak_kernel, dim3(nk), dim3(256), 0, c->stream, c->blk_acc.as<double>(),
+                                   c->blk_units.as<TrackUnit>(), c->blk_clip.as<int32_t>(), c->blk_blocks.as<mtm_block>(), (int)k0,
+                                   side, (double)pairs, mode_min, c->blk_plane.as<float>(), c->blk_recs.as<mtm_hit>());
+                HIPC(hipGetLastError());
+                return MTM_OK;
+            });
+        });
+}
 
 int mtm_match_blocks_at(mtm_ctx* c, const void* reference, int64_t reference_stride_bytes, const void* image,
                         int64_t image_stride_bytes, int rows, int cols, int chans, int dtype, const mtm_block* blocks,

@@ -52,6 +52,17 @@ MTM_HOST_DEVICE inline BlockUnitBox blocks_unit_at_inl(const mtm_block& b, long 
     return BlockUnitBox{(int)y0, (int)x0, (int)(y1 - y0 - b.h + 1), (int)(x1 - x0 - b.w + 1)};
 }
 
+// The moved and clamped position (cx, cy) blocks_unit_at_inl widens: MTM.blocks.moved_blocks' numbers.  The unit of the
+// moved block starts at (x0, y0) = (max(cx - margin, 0), max(cy - margin, 0)), so output (y, x) of its map is cell
+// (y + y0 - (cy - margin), x + x0 - (cx - margin)) of the block's (2 margin + 1)^2 plane of displacements around (cx, cy).
+MTM_HOST_DEVICE inline void blocks_moved_at_inl(const mtm_block& b, long long dx, long long dy, int rows, int cols, int* cx,
+                                                int* cy) {
+    long long x = (long long)b.x + dx, y = (long long)b.y + dy;
+    const long long mx = (long long)cols - b.w, my = (long long)rows - b.h;
+    *cx = (int)(x < 0 ? 0 : (x > mx ? mx : x));
+    *cy = (int)(y < 0 ? 0 : (y > my ? my : y));
+}
+
 // The displacement a pass predicts for block `b` of its own grid from the previous pass's records `prev` (image
 // coordinates, one per block of grid `c` in grid order): that of the coarse block with the nearest centre.
 MTM_HOST_DEVICE inline void blocks_predict_inl(const BlockGrid& c, const mtm_hit* prev, const mtm_block& b, long long* dx,

@@ -13,6 +13,9 @@
 // A mask over the reference (5.6.5): blocks_gather_masked_kernel cuts T M and the mask, blocks_score_masked_kernel,
 // blocks_score_plane_masked_kernel and blocks_nbhd_masked_kernel are the masked siblings over one tile body of their own
 // (blocks_tile_masked); the unmasked kernels are untouched by them.
+// The passes over a frame stack (5.6.6): blocks_unit_clip_kernel computes a unit together with its clip offsets,
+// blocks_plane_fixed_kernel sums planes over the fixed tile table at those offsets, blocks_plane_peak_kernel turns a pass's
+// sums into means, NaN fill and the peak record that steers the next pass.
 // The rules (mtm_blocks_*.h, mtm_quality_key.h, mtm_templ_stats.h) are the single source of host and device; one of each:
 // the tile body of the four score kernels (blocks_tile; the kernels supply the sink), the key's decoder, the record that
 // steers (blocks_steer_record_inl).  Launched by mtm_blocks.hip only.
@@ -499,6 +502,128 @@ __global__ __launch_bounds__(256) void blocks_plane_kernel(ImageDev img, const u
                                         *cell = first ? (double)s : *cell + (double)s;
                                     }
                                 });
+}
+
+// ---- ensemble planes of boxes that follow a displacement (mtm_match_blocks_stack_at, mtm_match_blocks_stack_passes)
+
+// blocks_unit_kernel's sibling for a call that sums planes: the same unit - the same arguments and functions -, and the
+// block's clip offsets next to it: clip[2 k], clip[2 k + 1] = (ox, oy) = (U.x0 - (cx - margin), U.y0 - (cy - margin)) with
+// (cx, cy) the moved and clamped position (blocks_moved_at_inl) - what BlockPlan::clip is to the host's units, both >= 0 -,
+// one 8-byte store.
+__global__ __launch_bounds__(256) void blocks_unit_clip_kernel(const mtm_block* __restrict__ blocks, int n,
+                                                               const int32_t* __restrict__ offs, const mtm_hit* __restrict__ prev,
+                                                               BlockGrid coarse, int margin, int rows, int cols,
+                                                               TrackUnit* __restrict__ units, int32_t* __restrict__ clip) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const mtm_block B = blocks[k];
+    long long dx, dy;
+    if (prev) {
+        blocks_predict_inl(coarse, prev, B, &dx, &dy);
+    } else {
+        dx = offs[2 * (size_t)k];
+        dy = offs[2 * (size_t)k + 1];
+    }
+    const BlockUnitBox u = blocks_unit_at_inl(B, dx, dy, margin, rows, cols);
+    int cx, cy;
+    blocks_moved_at_inl(B, dx, dy, rows, cols, &cx, &cy);
+    units[k] = TrackUnit{k, u.y0, u.x0, u.oh, u.ow};
+    *reinterpret_cast<int2*>(clip + 2 * (size_t)k) = make_int2(u.x0 - (cx - margin), u.y0 - (cy - margin));
+}
+
+// blocks_plane_kernel over the FIXED tile table for units and clip offsets that blocks_unit_clip_kernel computed: the same
+// body, score and read-modify-write, with blocks_score_fixed_kernel's early exit for a tile outside the unit's map.  Every
+// output of the unit's map has one tile and one lane, so a cell still has one writer per launch; y + oy <= 2 margin and
+// x + ox <= 2 margin for every output of a moved unit, and the guard against `side` stays.
+template <int CH, bool U16>
+__global__ __launch_bounds__(256) void blocks_plane_fixed_kernel(ImageDev img, const uint8_t* __restrict__ lo_b,
+                                                                 const uint8_t* __restrict__ tpx,
+                                                                 const long long* __restrict__ toff,
+                                                                 const TemplDev* __restrict__ td,
+                                                                 const TrackUnit* __restrict__ units,
+                                                                 const TrackTile* __restrict__ tiles, int method,
+                                                                 const int32_t* __restrict__ clip, int side, int first,
+                                                                 double* __restrict__ acc) {
+    __shared__ __attribute__((aligned(16))) WinTemplLds Tl[U16 ? 2 : 1];
+    __shared__ __attribute__((aligned(16))) WinImageLds Il[U16 ? 2 : 1];
+    blocks_tile<CH, U16, true>(Tl, Il, img, lo_b, tpx, toff, td, units, tiles, method,
+                               [&](const TrackTile& K, const TrackUnit&, bool inside, int y, int x, auto&& score) {
+                                   const int cy = y + clip[2 * K.u0 + 1], cx = x + clip[2 * K.u0];
+                                   if (inside && cy >= 0 && cx >= 0 && cy < side && cx < side) {
+                                       const float s = score();
+                                       double* cell = acc + ((size_t)K.u0 * (size_t)side + (size_t)cy) * (size_t)side + (size_t)cx;
+                                       *cell = first ? (double)s : *cell + (double)s;
+                                   }
+                               });
+}
+
+// Grid: one 256-thread work-group per block (launch slice; block k = k0 + blockIdx.x), behind the last pair's plane launch:
+// the block's side x side plane of sums becomes its plane of means and its peak.  Cell (cy, cx) lies in the clipped box iff
+// oy <= cy < oy + U.oh and ox <= cx < ox + U.ow, (ox, oy) = clip[2 k], clip[2 k + 1]; such a cell's mean is
+// (float)(acc / pairs) - the division in float64, one rounding to float32 -, every other cell is the quiet NaN (its sum is
+// not read), and all side^2 cells are stored to planes.  The peak is plane_peaks' (MTM.blocks): the largest mean - the
+// smallest, mode_min - over the cells that are not NaN, -0 equal to +0, of equal ones the first in row-major order:
+// second_cell_key's key (mtm_blocks_second.h) with the plane's row-major index.  Lanes walk idx = tid, tid + 256, .. in
+// order; the wave's maximum by the shuffle ladder, the four waves through 32 B of LDS: integer maxima, so the result is
+// the same whatever the schedule.  The lane that holds the peak writes recs[k]: the peak's position (cx_k + dx, cy_k + dy) in image
+// coordinates - (cx_k, cy_k) = (U.x0 - ox + margin, U.y0 - oy + margin), the moved block - and the plane's own float32 at
+// that cell (a -0 stays -0); a plane without a number gives (-1, -1) and NaN.  Reads acc, writes planes and recs only.
+__global__ __launch_bounds__(256) void blocks_plane_peak_kernel(const double* __restrict__ acc,
+                                                                const TrackUnit* __restrict__ units,
+                                                                const int32_t* __restrict__ clip,
+                                                                const mtm_block* __restrict__ blocks, int k0, int side,
+                                                                double pairs, int mode_min, float* __restrict__ planes,
+                                                                mtm_hit* __restrict__ recs) {
+    __shared__ unsigned long long red[4];
+    const int k = k0 + (int)blockIdx.x;
+    const int tid = threadIdx.x;
+    const TrackUnit U = units[k];
+    const int ox = clip[2 * (size_t)k], oy = clip[2 * (size_t)k + 1];
+    const uint32_t sd = (uint32_t)side, n = sd * sd;        // (side^2 <= the planes' float budget < 2^31)
+    const double* __restrict__ a = acc + (size_t)k * n;
+    float* __restrict__ p = planes + (size_t)k * n;
+    // the lane's cell (cy, cx) steps by 256 cells: 256 / side rows and 256 % side columns, with one carry
+    const uint32_t sy = 256u / sd, sx = 256u % sd;
+    uint32_t cy = (uint32_t)tid / sd, cx = (uint32_t)tid % sd;
+    unsigned long long best = 0ull;
+    float best_v = __builtin_nanf("");
+    for (uint32_t idx = (uint32_t)tid; idx < n; idx += 256u) {
+        const int y = (int)cy - oy, x = (int)cx - ox;
+        float v = __builtin_nanf("");
+        if (y >= 0 && y < U.oh && x >= 0 && x < U.ow) v = (float)(a[idx] / pairs);
+        p[idx] = v;
+        const unsigned long long key = second_cell_key(v, mode_min, idx);
+        if (key > best) {
+            best = key;
+            best_v = v;
+        }
+        cy += sy;
+        cx += sx;
+        if (cx >= sd) {
+            cx -= sd;
+            ++cy;
+        }
+    }
+    unsigned long long top = best;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = __shfl_xor(top, off);
+        top = o > top ? o : top;
+    }
+    if ((tid & 63) == 0) red[tid >> 6] = top;
+    __syncthreads();
+    unsigned long long b = red[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) b = red[w] > b ? red[w] : b;
+    // the lane that holds the winning cell writes the record (keys of different cells differ: one lane), or - no cell
+    // holds a number - thread 0 the record that says so
+    const mtm_block B = blocks[k];
+    if (b != 0ull && best == b) {
+        const uint32_t idx = key_index(b);
+        recs[k] = key_record(idx, best_v, k, U.y0 - oy, U.x0 - ox, side, B.w, B.h);
+    } else if (b == 0ull && tid == 0) {
+        recs[k] = second_key_record(0ull, mode_min, k, 0, 0, side, B.w, B.h);
+    }
 }
 
 // Grid: one 256-thread work-group per block (launch slice; block k = k0 + blockIdx.x), after the chunk's score launches:

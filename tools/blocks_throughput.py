@@ -23,6 +23,20 @@ frames of noise around a weak pattern that moves by (2, 1) a frame (``noisy_movi
 deviations above the correlation noise of a block), the fraction of blocks found at that step by the pairs' own peaks
 (``noisy_found_pairs``, mean over the pairs) and by the ensemble peak (``noisy_found_ensemble``).
 
+--stack F --passes: coarse to fine over the movie - the two passes of --passes below, milliseconds per PAIR of
+  stack_passes   - matchBlocksStackMultipass(frames, passes): one native call, every frame uploaded once
+  loop_multipass - matchBlocksMultipass over the F - 1 pairs, what a user writes without the call
+  stack_wide     - matchBlocksStack(frames, grid, margin): the single pass at the workload's (wide) margin
+with ``equal_to_loop`` (stack_passes against loop_multipass, every pass and pair, positions and score bits).
+--stack F --passes --ensemble: the passes on ensemble planes - milliseconds per PAIR of
+  stack_passes_ensemble - matchBlocksStackMultipass(frames, passes, ensemble=True)
+  by_hand               - the loop of matchBlocksStack(ensemble=True, offsets=) and predict_offsets the call documents
+with ``equal_to_loop`` (every pass: positions, score bits and planes) and, on ``noisy_movie`` moved by more than the dense
+margin a frame (at most 8 frames), the share of the dense grid's blocks clear of the border found at the step by the pairs'
+own multipass (``noisy_found_pairs_multipass``, mean over the pairs), by the single-pass ensemble at the dense margin
+(``noisy_found_ensemble_single``) and by the ensemble multipass (``noisy_found_ensemble_multipass``).
+Both forms append their lines to profiles/blocks/stack_passes_throughput.jsonl (``--out`` names another file).
+
 --passes: coarse to fine instead - milliseconds per call of
   single    - matchBlocks(reference, image, grid, margin): today's single pass at the workload's margin
   multipass - matchBlocksMultipass with a sparse wide pass (the workload's block at stride 2 x the block, the workload's
@@ -87,7 +101,7 @@ host); ``masked_at_vs_unmasked_at_device`` compares like with like.  The score l
 pixels: a few discs and a band cut out, generated and seeded (``static_mask``).  The lines also go to
 profiles/blocks/mask_throughput.jsonl (``--out`` names another file).
 
-Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F]
+Usage: tools/blocks_throughput.py [--reps 5] [--warmup 2] [--only K1|K2|K3] [--stack F [--passes [--ensemble]]]
        [--passes [--validate | --deform [--steer refined]]]
        [--second [r]] [--mask [--no-loop] [--out FILE]]
 """
@@ -262,6 +276,81 @@ def run_stack(MTM, spec, n_frames, reps, warmup):
         "noisy_found_ensemble": round(found(epos), 4),
         "reps": reps,
     }
+
+
+def run_stack_passes(MTM, spec, n_frames, reps, warmup, ensemble):
+    from MTM import blocks as B
+    name, hw, chans, dtype, side, margin = spec
+    frames = movie(spec, n_frames)
+    method = MTM.TM_CCOEFF_NORMED
+    pairs = n_frames - 1
+    fine_margin = max(1, margin // 4)
+    passes = [(side, 2 * side, margin), (side, side, fine_margin)]
+    grid = B.grid(frames[0].shape, side)
+
+    def loop_multipass(fr=frames):
+        return [MTM.matchBlocksMultipass(fr[p], fr[p + 1], passes, method) for p in range(len(fr) - 1)]
+
+    def by_hand(fr=frames):
+        out, off, steer = [], None, None
+        for p, (block, step, m) in enumerate(passes):
+            b = B.grid(fr[0].shape, block, step)
+            if p:
+                off = B.predict_offsets(fr[0].shape, passes[p - 1][:2], steer, passes[p][:2])
+            steer, sc, planes = MTM.matchBlocksStack(fr, b, m, method, ensemble=True, offsets=off)
+            out.append((b, steer, sc, planes))
+        return out
+
+    if ensemble:
+        methods = {"stack_passes_ensemble": lambda: MTM.matchBlocksStackMultipass(frames, passes, method, ensemble=True),
+                   "by_hand": by_hand}
+    else:
+        methods = {"stack_passes": lambda: MTM.matchBlocksStackMultipass(frames, passes, method),
+                   "loop_multipass": loop_multipass,
+                   "stack_wide": lambda: MTM.matchBlocksStack(frames, grid, margin, method)}
+    results = {}
+    for k, fn in methods.items():
+        for _ in range(warmup):
+            results[k] = fn()
+    ms = {k: [] for k in methods}
+    for _ in range(reps):
+        for k, fn in methods.items():
+            t0 = time.perf_counter()
+            fn()
+            ms[k].append((time.perf_counter() - t0) * 1e3 / pairs)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    out = {
+        "workload": name, "image": "%dx%dx%d %s" % (hw[0], hw[1], chans, dtype), "frames": n_frames, "pairs": pairs,
+        "blocks": int(len(grid)), "block": side, "passes": [[b, st, m] for b, st, m in passes], "ensemble": ensemble,
+        "ms_per_pair": {k: round(v, 3) for k, v in med.items()},
+        "ms_per_pair_min": {k: round(min(v), 3) for k, v in ms.items()},
+        "reps": reps,
+    }
+    if ensemble:
+        out["equal_to_loop"] = all(bool((a[1] == b[1]).all() and a[2].tobytes() == b[2].tobytes() and
+                                        np.array_equal(a[3], b[3], equal_nan=True))
+                                   for a, b in zip(results["stack_passes_ensemble"], results["by_hand"]))
+        out["vs_by_hand"] = round(med["by_hand"] / med["stack_passes_ensemble"], 2)
+        step = (fine_margin + 2, -(fine_margin + 1))
+        noisy = noisy_movie(spec, min(n_frames, 8), step=step)
+        inner = (grid[:, 0] >= 2 * side) & (grid[:, 1] >= 2 * side) & (grid[:, 0] + 3 * side <= hw[1]) & \
+            (grid[:, 1] + 3 * side <= hw[0])
+        found = lambda pos: float(np.mean((B.displacements(grid, pos)[inner] == step).all(axis=1)))      # noqa: E731
+        out.update({
+            "noisy_frames": len(noisy), "noisy_step": list(step), "blocks_counted": int(inner.sum()),
+            "noisy_found_pairs_multipass": round(float(np.mean(
+                [found(p) for p in MTM.matchBlocksStackMultipass(noisy, passes, method)[1][1]])), 4),
+            "noisy_found_ensemble_single": round(found(MTM.matchBlocksStack(noisy, grid, fine_margin, method, ensemble=True)[0]), 4),
+            "noisy_found_ensemble_multipass": round(found(
+                MTM.matchBlocksStackMultipass(noisy, passes, method, ensemble=True)[1][1]), 4)})
+    else:
+        loop = results["loop_multipass"]
+        out["equal_to_loop"] = all(bool((g[1][q] == loop[q][p][1]).all() and g[2][q].tobytes() == loop[q][p][2].tobytes())
+                                   for p, g in enumerate(results["stack_passes"]) for q in range(pairs))
+        out["vs_loop_multipass"] = round(med["loop_multipass"] / med["stack_passes"], 2)
+        out["vs_stack_wide"] = round(med["stack_wide"] / med["stack_passes"], 2)
+        out["found_shift"] = float(np.mean((B.displacements(grid, results["stack_passes"][1][1][0]) == (3, -2)).all(axis=1)))
+    return out
 
 
 def quadrant_pair(spec, seed=0):
@@ -841,13 +930,23 @@ def main():
                     help="with --passes --deform: refined = the deformed passes steered by sub-pixel positions, three passes")
     ap.add_argument("--mask", action="store_true", help="a static mask over the reference: masked, unmasked and the loop (K1, K3)")
     ap.add_argument("--no-loop", action="store_true", help="with --mask: leave the by-hand loop out (profiler runs)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "blocks", "mask_throughput.jsonl"),
-                    help="with --mask: the file the lines are written to")
+    ap.add_argument("--ensemble", action="store_true", help="with --stack F --passes: the passes on ensemble planes")
+    ap.add_argument("--out", default=None,
+                    help="with --mask: the file the lines are written to (default profiles/blocks/mask_throughput.jsonl); with "
+                         "--stack F --passes: appended to (default profiles/blocks/stack_passes_throughput.jsonl)")
     args = ap.parse_args()
     if args.mask and (args.passes or args.stack or args.second is not None):
         ap.error("--mask goes alone")
     if args.steer == "refined" and not args.deform:
         ap.error("--steer refined goes with --passes --deform")
+    stack_passes = bool(args.stack and args.passes)
+    if args.ensemble and not stack_passes:
+        ap.error("--ensemble goes with --stack F --passes")
+    if stack_passes and (args.stack < 2 or args.validate or args.deform or args.second is not None):
+        ap.error("--stack F --passes takes two frames at least and goes with --ensemble only")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "blocks", "stack_passes_throughput.jsonl" if stack_passes
+                                else "mask_throughput.jsonl")
     if args.validate and not args.passes:
         ap.error("--validate goes with --passes")
     if args.deform and (not args.passes or args.validate or args.second is not None):
@@ -865,6 +964,9 @@ def main():
             if spec[3] == "uint8":
                 lines.append(json.dumps(run_mask(MTM, spec, args.reps, args.warmup, not args.no_loop)))
                 print(lines[-1], flush=True)
+        elif stack_passes:
+            lines.append(json.dumps(run_stack_passes(MTM, spec, args.stack, args.reps, args.warmup, args.ensemble)))
+            print(lines[-1], flush=True)
         elif args.second is not None:
             print(json.dumps(run_second(MTM, spec, args.reps, args.warmup, args.second, args.passes)), flush=True)
         elif args.passes and args.deform and args.steer == "refined":
@@ -885,6 +987,9 @@ def main():
             print(json.dumps(run(MTM, spec, args.reps, args.warmup)), flush=True)
     if args.mask and lines and not args.no_loop:
         with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    if stack_passes and lines:
+        with open(args.out, "a") as f:
             f.write("\n".join(lines) + "\n")
 
 
